@@ -13,6 +13,11 @@ only waits and forwards the exit code).  Under `python -m torch.distributed.run 
 --gpus N` the ranks are already there (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the environment).  Either way
 WORLD_SIZE must equal --gpus and every rank needs its own visible GPU, otherwise the run fails loudly instead of
 printing a line for fewer GPUs.  N = 1 goes through the same RCCL path (a one-rank process group).
+
+A plain run does what the headline needs: set-up, pre-warm and warm-up steps, the K timed steps, the line.  `--full`
+adds what is measured or checked beside it: the cold-clock value, the device state under load, bit-exact parity against
+the CPU oracle with the CPU baselines, and the drop-in-caller figures; in a plain run those fields are null.
+`--dump-outputs DIR` writes the results of the last timed step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import importlib
@@ -38,9 +43,16 @@ def parse_args(argv=None):
                          "profiles/r03_bench_warmup_sensitivity.txt")
     ap.add_argument("--log-size", type=int, default=20)
     ap.add_argument("--instances", type=int, default=5, help="instances per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the drop-in-caller figures (host slices, lone calls)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline sample budget")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: value_without_prewarm, "
+                         "device_state_under_load, parity against the CPU oracle with cpu_baseline, drop_in_caller "
+                         "(all null in a plain run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the results of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip parity and the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the drop-in-caller figures (host slices, lone calls) and the device state")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-baseline sample budget (--full)")
     ap.add_argument("--depth", type=int, default=1, choices=[1, 2, 3],
                     help="steps submitted ahead of the one being collected (submit/wait API, at most 4 batches in flight)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
@@ -65,6 +77,8 @@ def resolve_world(args, environ):
     No torch, no GPU: this runs before anything else."""
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "RANK" in environ:
         world = int(environ.get("WORLD_SIZE", "1"))
         if world != args.gpus:
@@ -224,8 +238,8 @@ def main(argv=None):
         red_ms.append(t.reduce_ms)
         fin_ms.append(t.final_ms)
 
-    # Device state under this load (rank 0): rocm-smi asked for shader clock and package power while the pre-warm and
-    # warm-up steps run -- the same pipelined load as the timed steps, but OUTSIDE the timed region, so the child
+    # Device state under this load (rank 0, --full): rocm-smi asked for shader clock and package power while the
+    # pre-warm and warm-up steps run -- the same pipelined load as the timed steps, but OUTSIDE the timed region, so the child
     # processes cannot touch `value`.  The pipeline is power-limited (profiles/r04_clock_power_during_bench.txt): the
     # clock it actually runs at belongs beside peaks that are quoted at the nominal 2.4 GHz.  Never an error.
     state_samples, state_stop = [], None
@@ -247,15 +261,16 @@ def main(argv=None):
 
     cold_value = None
     if args.prewarm_steps > 0:
-        # what the plain (W warm-up, K timed) recipe gives on a device whose clocks have not ramped up yet -- reported
-        # beside `value` as `value_without_prewarm` so that a reader comparing by (steps, warmup) sees both
-        run_steps(args.warmup, lambda t: None)
-        barrier()
-        tc0 = time.perf_counter()
-        run_steps(args.steps, lambda t: None)
-        barrier()
-        cold_value = inst * world * args.steps / (time.perf_counter() - tc0)
-        if rank == 0 and not args.no_extras:
+        if args.full:
+            # what the plain (W warm-up, K timed) recipe gives on a device whose clocks have not ramped up yet --
+            # reported beside `value` as `value_without_prewarm` so that a reader comparing by (steps, warmup) sees both
+            run_steps(args.warmup, lambda t: None)
+            barrier()
+            tc0 = time.perf_counter()
+            run_steps(args.steps, lambda t: None)
+            barrier()
+            cold_value = inst * world * args.steps / (time.perf_counter() - tc0)
+        if rank == 0 and args.full and not args.no_extras:
             import threading
             state_stop = threading.Event()
             state_thread = threading.Thread(target=sample_device_state, daemon=True)
@@ -288,6 +303,8 @@ def main(argv=None):
     elapsed = float(te.item())
     if ranks_seen != world or len(allr) != world * inst or any(r == bytes(96) for r in allr):
         raise SystemExit(f"bench.py: only {ranks_seen} of {world} ranks answered the RCCL gather")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, allr)
     tm = cfg.timings()
     window = tm.window_size
 
@@ -384,7 +401,7 @@ def main(argv=None):
 
     # ---- parity on every rank + CPU baseline (rank 0, single-GPU run only)
     cpu, parity_ok, extras = None, True, None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import bn254_ref as o
         from oracle import c_oracle as co
         cores_all = co.default_threads()
@@ -474,7 +491,8 @@ def main(argv=None):
             "ipc_mode_legacy_env": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "<unset>"),
             "ranks_pinned_to_gpu_numa_node": bool(numa_pinned),
             "collective": "rccl" if args.backend == "nccl" else "gloo (rehearsal, not RCCL)",
-            "parity": ("bit-exact vs the CPU oracle on every rank's own instances" if not args.no_cpu_baseline
+            "parity": ("not checked in a plain run (bench.py --full checks it)" if not args.full
+                       else "bit-exact vs the CPU oracle on every rank's own instances" if not args.no_cpu_baseline
                        else "not checked in this run (--no-cpu-baseline)"),
             "config": {"workload": f"log_size={args.log_size}, {inst} instances per GPU, h2c BN254 G1 "
                                    f"(gpu_msm_h2c pipeline, window {window})",
@@ -514,6 +532,26 @@ def main(argv=None):
         cfg.free(d_sc[j])
     cfg.close()
     dist.destroy_process_group()
+
+
+def dump_outputs(directory, results):
+    """--dump-outputs: the results of the last timed step, one row per instance in global instance order (every rank's
+    instances, as gathered), as float64 arrays of 16-bit limbs, least significant first (exact in float64):
+      msm_results.npy         (instances, 3, 16)  the 96-byte result a caller receives: X, Y, Z Montgomery little-endian,
+                                                  normalised by the library (Z = Montgomery 1, or 0 at infinity)
+      msm_results_affine.npy  (instances, 2, 16)  the canonical affine (x, y) of the same points; (0, 0) = infinity
+    The inputs are the device generator's seeded instances, so the same arguments give the same arrays."""
+    import numpy as np
+    from oracle import bn254_ref as o
+    os.makedirs(directory, exist_ok=True)
+    raw = np.frombuffer(b"".join(results), dtype="<u2").reshape(len(results), 3, 16).astype(np.float64)
+    aff = np.zeros((len(results), 2, 16), dtype=np.float64)
+    for i, r in enumerate(results):
+        p = o.decode_jacobian_mont_le(r)
+        if p is not None:
+            aff[i] = np.frombuffer(o.int_to_le_bytes32(p[0]) + o.int_to_le_bytes32(p[1]), dtype="<u2").reshape(2, 16)
+    np.save(os.path.join(directory, "msm_results.npy"), raw)
+    np.save(os.path.join(directory, "msm_results_affine.npy"), aff)
 
 
 def drop_in_caller_figures(m, cfg, h_sc, h_pts, n, inst, expect):

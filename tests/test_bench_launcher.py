@@ -115,3 +115,42 @@ def test_bench_gpus_2_without_two_gpus_fails_loudly():
     assert p.returncode != 0
     assert "n_gpus" not in p.stdout
     assert "cannot run here" in p.stderr or "rank failed" in p.stderr
+
+
+def test_plain_and_full_options():
+    """A plain run is what the headline needs; --full adds the rest; --steps is the number of timed steps."""
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    b = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert b.full is True and b.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.resolve_world(bench.parse_args(["--steps", "0"]), {})
+
+
+def test_dump_outputs_layout(tmp_path):
+    """--dump-outputs: the 96-byte results (X, Y, Z Montgomery LE) and their canonical affine form, as 16-bit limbs in
+    float64, one row per instance; infinity is Z = 0 in the raw form and (0, 0) in the affine one."""
+    import numpy as np
+    from oracle import bn254_ref as o
+
+    def result96(aff):
+        if aff is None:
+            return o.int_to_le_bytes32(o.fq_to_mont(1)) * 2 + bytes(32)
+        return b"".join(o.int_to_le_bytes32(o.fq_to_mont(c)) for c in (aff[0], aff[1], 1))
+
+    pts = [o.scalar_mul(5, o.GEN), None, o.GEN]
+    res = [result96(p) for p in pts]
+    bench.dump_outputs(str(tmp_path / "d"), res)
+    raw = np.load(tmp_path / "d" / "msm_results.npy")
+    aff = np.load(tmp_path / "d" / "msm_results_affine.npy")
+    assert raw.dtype == np.float64 and raw.shape == (3, 3, 16)
+    assert aff.dtype == np.float64 and aff.shape == (3, 2, 16)
+
+    def limbs_to_int(row):
+        return sum(int(v) << (16 * j) for j, v in enumerate(row))
+
+    for i, p in enumerate(pts):
+        assert b"".join(o.int_to_le_bytes32(limbs_to_int(raw[i, k])) for k in range(3)) == res[i]
+        want = (0, 0) if p is None else p
+        assert (limbs_to_int(aff[i, 0]), limbs_to_int(aff[i, 1])) == want
+    assert sum(f.stat().st_size for f in (tmp_path / "d").iterdir()) < 64 << 20
