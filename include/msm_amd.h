@@ -468,6 +468,40 @@ int msm_amd_test_op_host(int op, const uint32_t* a, const uint32_t* b, uint32_t*
 int msm_amd_test_hold(msm_amd_ctx* ctx, uint32_t max_ms, void** handle);
 int msm_amd_test_release(msm_amd_ctx* ctx, void* handle);
 
+/* Stage tap for tests: the intermediate buffers of the batch the ctx last waited for (a blocking call, or
+ * msm_amd_wait_batch), read AFTER the call -- the call itself runs the shipped pipeline unchanged.  Instance j of a
+ * batch of at most four instances (the ctx's workspaces are used round-robin); a larger batch: MSM_AMD_INPUT_ERROR.
+ * The record stays valid until the next call on the ctx. */
+enum {
+  MSM_AMD_TP_C = 0, MSM_AMD_TP_W, MSM_AMD_TP_W_DIGITS, MSM_AMD_TP_N, MSM_AMD_TP_N_SCALARS, MSM_AMD_TP_LB, MSM_AMD_TP_NB,
+  MSM_AMD_TP_CH, MSM_AMD_TP_HB, MSM_AMD_TP_MB, MSM_AMD_TP_FB, MSM_AMD_TP_Q, MSM_AMD_TP_TILED, MSM_AMD_TP_BALLOT,
+  MSM_AMD_TP_WIDE_DIGITS, MSM_AMD_TP_LONE,   /* 1: the call ran as a lone call (one stream, lone-call reduce geometry) */
+  MSM_AMD_TP_TOTAL_ITEMS, MSM_AMD_TP_MULTI_COUNT, MSM_AMD_TP_DEFERRED,   /* plan counters; deferred = split buckets
+                                                                            summed by combine_big_kernel */
+  MSM_AMD_TP_RED_GROUP, MSM_AMD_TP_RB_THREADS, MSM_AMD_TP_INSTANCES, MSM_AMD_TP_WORKSPACE, MSM_AMD_TP_FRONT_THREADS,
+  MSM_AMD_TEST_PLAN_WORDS
+};
+/* out: count >= MSM_AMD_TEST_PLAN_WORDS words, indexed by MSM_AMD_TP_*. */
+int msm_amd_test_last_plan(msm_amd_ctx* ctx, uint32_t j, uint32_t* out, size_t count);
+/* Buffers of msm_amd_test_stage_copy (W windows, n entries per window, nb = 2^lb slots per window): */
+enum {
+  MSM_AMD_STAGE_DIGITS = 0,    /* [W_digits][n_scalars] u16 (c <= 15) or u32: sign << (bits - 1) | magnitude */
+  MSM_AMD_STAGE_SORTED = 1,    /* [W][n] u32 point index | sign << 31, grouped by slot */
+  MSM_AMD_STAGE_BUCKET_SIZE = 2,   /* [W][nb] u32 */
+  MSM_AMD_STAGE_BUCKET_START = 3,  /* [W][nb] u32, offset inside the window's slice of SORTED */
+  MSM_AMD_STAGE_ITEM_START = 4,    /* [W][nb] u32, first work item of the slot inside its window */
+  MSM_AMD_STAGE_WIN_ITEMS = 5,     /* [W] u32, first work item of the window (exclusive scan of the item counts) */
+  MSM_AMD_STAGE_ORDER = 6,         /* [total_items] (slot, chunk) u32 pairs, the accumulate kernel's lane order */
+  MSM_AMD_STAGE_MULTI_LIST = 7,    /* [multi_count] u32 slots split into more than one work item */
+  MSM_AMD_STAGE_BUCKETS = 8,       /* [W][nb] Jacobian BE32 (24 u32); slots with bucket size 0 hold stale data */
+  MSM_AMD_STAGE_PARTIAL = 9        /* [W][lb + 1] Jacobian BE32: bit-k subset sums over the slot index, then the total */
+};
+/* out == NULL: *bytes receives the size of the buffer; otherwise *bytes must equal it. */
+int msm_amd_test_stage_copy(msm_amd_ctx* ctx, uint32_t j, int which, void* out, size_t* bytes);
+/* Fill the point-valued buffers of every workspace (buckets, item partials, reduce scratch, window partials) with one
+ * byte over their whole capacity.  Index and count buffers are never touched. */
+int msm_amd_test_fill_workspaces(msm_amd_ctx* ctx, uint8_t byte);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 int msm_amd_last_timings(const msm_amd_ctx* ctx, msm_amd_timings* out);
 /* Algorithmic HBM bytes of one MSM: whole pipeline and accumulation only. */

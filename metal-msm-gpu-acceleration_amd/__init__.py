@@ -57,7 +57,15 @@ EXPORTS = [
     "msm_amd_shard_count", "msm_amd_ctx_device", "msm_amd_pin_thread_to_device", "msm_amd_gather_init",
     "msm_amd_gather_size", "msm_amd_gather_all", "msm_amd_gather_last_error", "msm_amd_gather_destroy",
     "msm_amd_host_msm", "msm_amd_tuned_split", "msm_amd_host_threads", "msm_amd_generate_instance_host", "msm_amd_test_op_ifma",
+    "msm_amd_test_last_plan", "msm_amd_test_stage_copy", "msm_amd_test_fill_workspaces",
 ]
+
+# stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
+TEST_PLAN_FIELDS = ("c", "W", "W_digits", "n", "n_scalars", "lb", "nb", "CH", "hb", "mb", "fb", "Q", "tiled", "ballot",
+                    "wide_digits", "lone", "total_items", "multi_count", "deferred", "red_group", "rb_threads",
+                    "instances", "workspace", "front_threads")
+(STAGE_DIGITS, STAGE_SORTED, STAGE_BUCKET_SIZE, STAGE_BUCKET_START, STAGE_ITEM_START, STAGE_WIN_ITEMS, STAGE_ORDER,
+ STAGE_MULTI_LIST, STAGE_BUCKETS, STAGE_PARTIAL) = range(10)
 
 
 AFTER_SORT_FN = ctypes.CFUNCTYPE(None, c_void_p)   # msm_amd_after_sort_fn
@@ -173,6 +181,9 @@ def _lib():
         L.msm_amd_set_bases_cache_verify.argtypes = [c_void_p, c_int]
         L.msm_amd_test_hold.argtypes = [c_void_p, c_uint32, POINTER(c_void_p)]
         L.msm_amd_test_release.argtypes = [c_void_p, c_void_p]
+        L.msm_amd_test_last_plan.argtypes = [c_void_p, c_uint32, c_void_p, c_size_t]
+        L.msm_amd_test_stage_copy.argtypes = [c_void_p, c_uint32, c_int, c_void_p, POINTER(c_size_t)]
+        L.msm_amd_test_fill_workspaces.argtypes = [c_void_p, ctypes.c_uint8]
         L.msm_amd_msm_batch_multi.argtypes = [POINTER(c_void_p), c_size_t, c_int, c_int, c_size_t, POINTER(c_void_p),
                                               POINTER(c_void_p), POINTER(c_size_t), c_void_p]
         L.msm_amd_msm_batch_multi_device.argtypes = L.msm_amd_msm_batch_multi.argtypes
@@ -326,6 +337,24 @@ class MsmConfig:
 
     def test_release(self, handle):
         self._check(_lib().msm_amd_test_release(self.h, handle))
+
+    def test_last_plan(self, j=0) -> dict:
+        """Plan and plan counters of instance j of the batch this ctx last waited for (stage tap)."""
+        out = (c_uint32 * len(TEST_PLAN_FIELDS))()
+        self._check(_lib().msm_amd_test_last_plan(self.h, j, out, len(out)))
+        return dict(zip(TEST_PLAN_FIELDS, out))
+
+    def test_stage_copy(self, which, j=0) -> bytes:
+        """One workspace buffer (STAGE_*) of instance j of the batch this ctx last waited for (stage tap)."""
+        nbytes = c_size_t(0)
+        self._check(_lib().msm_amd_test_stage_copy(self.h, j, which, None, ctypes.byref(nbytes)))
+        out = ctypes.create_string_buffer(max(1, nbytes.value))
+        self._check(_lib().msm_amd_test_stage_copy(self.h, j, which, out, ctypes.byref(nbytes)))
+        return out.raw[:nbytes.value]
+
+    def test_fill_workspaces(self, byte: int):
+        """Fill the point-valued workspace buffers with one byte (stale-data tests)."""
+        self._check(_lib().msm_amd_test_fill_workspaces(self.h, byte))
 
     def device(self) -> int:
         return _lib().msm_amd_ctx_device(self.h)

@@ -148,6 +148,8 @@ constexpr int kMaxBatches = 4;   // batches that may be in flight between submit
 struct Batch {
   std::vector<InstanceSlot> slots;
   std::vector<Plan> plans;
+  std::vector<int> ws_index;   // workspace each instance ran in (read by the msm_amd_test_* stage tap only)
+  bool lone = false;
   void* out = nullptr;
   size_t n_inst = 0;
   bool active = false;
@@ -190,6 +192,7 @@ struct msm_amd_ctx {
   int next_ws = 0;
   DeviceBuf scratch_a, scratch_b, scratch_c, scratch_b2, scratch_c2;
   Batch batches[kMaxBatches];
+  int last_waited = -1;   // batch of the last successful wait_batch (msm_amd_test_last_plan / msm_amd_test_stage_copy)
   msm_amd_timings timings{};
   float after_sort_state = -1.0f;   // timings.reserved2[1] of the next wait (see msm_amd_gpu_msm_h2c_sync)
   float after_sort_lead_ms = 0.0f;  // timings.reserved2[2]: device time from the callback to the end of accumulation
@@ -977,9 +980,13 @@ int submit_batch_device(msm_amd_ctx* ctx, int scalar_layout, int point_layout, s
   Batch& B = ctx->batches[id];
   if (B.slots.size() < n_inst) B.slots.resize(n_inst);
   B.plans.assign(n_inst, Plan{});
+  B.ws_index.assign(n_inst, 0);
+  B.lone = lone;
   B.out = out_host;
   B.n_inst = n_inst;
+  if (ctx->last_waited == id) ctx->last_waited = -1;   // its record is about to be overwritten
   for (size_t i = 0; i < n_inst; ++i) {
+    B.ws_index[i] = ctx->next_ws;
     Workspace& w = ctx->ws[ctx->next_ws];
     ctx->next_ws = (ctx->next_ws + 1) % kWorkspaces;
     int rc = enqueue_msm(ctx, w, B.slots[i], scalar_layout, point_layout, d_scalars[i], d_points[i], n[i], &B.plans[i],
@@ -1070,6 +1077,7 @@ int wait_batch(msm_amd_ctx* ctx, int ticket, bool internal = true) {
     accumulate_timings(ctx, B.slots[i], B.plans[i], done[i].final_ms, B.n_inst);
   }
   B.active = false;
+  ctx->last_waited = ticket;
   reap_graveyard(ctx);
   return MSM_AMD_OK;
 }
@@ -2855,6 +2863,138 @@ int msm_amd_test_release(msm_amd_ctx* ctx, void* handle) {
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // bounded by the kernel's own limit
   HIP_TRY(ctx, hipHostFree(handle));
   return MSM_AMD_OK;
+}
+
+// Stage tap (test aid): what the last instance batch left in its workspaces.  Nothing here runs inside enqueue_msm;
+// it reads the host record of the batch (plans, workspace indices, the plan counters copied behind the partial points)
+// and copies device buffers after the wait, so the pipeline under test is exactly the shipped one.
+static int tap_batch(msm_amd_ctx* ctx, uint32_t j, const Batch** out) {
+  if (ctx->last_waited < 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "stage tap: no batch has been waited for");
+  const Batch& B = ctx->batches[ctx->last_waited];
+  if (B.active || B.n_inst > (size_t)kWorkspaces || B.ws_index.size() != B.n_inst)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, "stage tap: the last batch had more instances than the ctx has workspaces");
+  if (j >= B.n_inst) return fail(ctx, MSM_AMD_INPUT_ERROR, "stage tap: no such instance in the last batch");
+  *out = &B;
+  return MSM_AMD_OK;
+}
+
+int msm_amd_test_last_plan(msm_amd_ctx* ctx, uint32_t j, uint32_t* out, size_t count) {
+  if (!ctx || !out || count < MSM_AMD_TEST_PLAN_WORDS) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_last_plan arguments");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  const Batch* B = nullptr;
+  if (int rc = tap_batch(ctx, j, &B)) return rc;
+  const Plan& p = B->plans[j];
+  const InstanceSlot& s = B->slots[j];
+  PlanCounters pc;
+  std::memcpy(&pc, s.h_partial + s.h_partial_cap, sizeof pc);
+  uint32_t v[MSM_AMD_TEST_PLAN_WORDS] = {};
+  v[MSM_AMD_TP_C] = p.c;
+  v[MSM_AMD_TP_W] = p.W;
+  v[MSM_AMD_TP_W_DIGITS] = p.W_digits;
+  v[MSM_AMD_TP_N] = p.n;
+  v[MSM_AMD_TP_N_SCALARS] = p.n_scalars;
+  v[MSM_AMD_TP_LB] = p.lb;
+  v[MSM_AMD_TP_NB] = p.nb;
+  v[MSM_AMD_TP_CH] = p.CH;
+  v[MSM_AMD_TP_HB] = p.hb;
+  v[MSM_AMD_TP_MB] = p.mb;
+  v[MSM_AMD_TP_FB] = p.fb;
+  v[MSM_AMD_TP_Q] = p.Q;
+  v[MSM_AMD_TP_TILED] = p.tiled;
+  v[MSM_AMD_TP_BALLOT] = p.ballot;
+  v[MSM_AMD_TP_WIDE_DIGITS] = p.wide_digits ? 1u : 0u;
+  v[MSM_AMD_TP_LONE] = B->lone ? 1u : 0u;
+  v[MSM_AMD_TP_TOTAL_ITEMS] = pc.total_items;
+  v[MSM_AMD_TP_MULTI_COUNT] = pc.multi_count;
+  v[MSM_AMD_TP_DEFERRED] = pc.pad[0];
+  v[MSM_AMD_TP_RED_GROUP] = p.red_group;
+  v[MSM_AMD_TP_RB_THREADS] = p.rb_threads;
+  v[MSM_AMD_TP_INSTANCES] = (uint32_t)B->n_inst;
+  v[MSM_AMD_TP_WORKSPACE] = (uint32_t)B->ws_index[j];
+  v[MSM_AMD_TP_FRONT_THREADS] = p.front_threads;
+  std::memcpy(out, v, sizeof v);
+  return MSM_AMD_OK;
+}
+
+int msm_amd_test_stage_copy(msm_amd_ctx* ctx, uint32_t j, int which, void* out, size_t* bytes) {
+  if (!ctx || !bytes) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_stage_copy arguments");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  const Batch* B = nullptr;
+  if (int rc = tap_batch(ctx, j, &B)) return rc;
+  const Plan& p = B->plans[j];
+  Workspace& w = ctx->ws[B->ws_index[j]];
+  PlanCounters pc;
+  std::memcpy(&pc, B->slots[j].h_partial + B->slots[j].h_partial_cap, sizeof pc);
+  const DeviceBuf* src = nullptr;
+  size_t dev_bytes = 0, out_bytes = 0;
+  switch (which) {
+    case MSM_AMD_STAGE_DIGITS:
+      src = &w.digits;
+      dev_bytes = (size_t)p.W_digits * p.n_scalars * (p.wide_digits ? 4 : 2);
+      break;
+    case MSM_AMD_STAGE_SORTED: src = &w.sorted; dev_bytes = (size_t)p.W * p.n * 4; break;
+    case MSM_AMD_STAGE_BUCKET_SIZE: src = &w.bsize; dev_bytes = p.total_buckets * 4; break;
+    case MSM_AMD_STAGE_BUCKET_START: src = &w.bstart; dev_bytes = p.total_buckets * 4; break;
+    case MSM_AMD_STAGE_ITEM_START: src = &w.istart; dev_bytes = p.total_buckets * 4; break;
+    case MSM_AMD_STAGE_WIN_ITEMS: src = &w.win_items; dev_bytes = (size_t)p.W * 4; break;
+    case MSM_AMD_STAGE_ORDER: src = &w.order; dev_bytes = (size_t)pc.total_items * 8; break;
+    case MSM_AMD_STAGE_MULTI_LIST: src = &w.multi_list; dev_bytes = (size_t)pc.multi_count * 4; break;
+    case MSM_AMD_STAGE_BUCKETS: src = &w.buckets; dev_bytes = p.total_buckets * sizeof(PtI); break;
+    case MSM_AMD_STAGE_PARTIAL: src = &w.partial; dev_bytes = p.partial_count * sizeof(Jacobian); break;
+    default: return fail(ctx, MSM_AMD_INPUT_ERROR, "test_stage_copy: unknown buffer");
+  }
+  const bool points = which == MSM_AMD_STAGE_BUCKETS || which == MSM_AMD_STAGE_PARTIAL;
+  out_bytes = points ? dev_bytes / (which == MSM_AMD_STAGE_BUCKETS ? sizeof(PtI) : sizeof(Jacobian)) * 96 : dev_bytes;
+  if (!out) {   // size query
+    *bytes = out_bytes;
+    return MSM_AMD_OK;
+  }
+  if (*bytes != out_bytes)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, "test_stage_copy: the buffer holds " + std::to_string(out_bytes) + " bytes");
+  if (dev_bytes > src->cap) return fail(ctx, MSM_AMD_INPUT_ERROR, "test_stage_copy: buffer smaller than the plan");
+  if (dev_bytes == 0) return MSM_AMD_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<uint8_t> h(dev_bytes);
+  HIP_TRY(ctx, hipMemcpyAsync(h.data(), src->p, dev_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (int rc = sync_stream_bounded(ctx, ctx->stream, __func__)) return rc;
+  if (!points) {
+    std::memcpy(out, h.data(), dev_bytes);
+    return MSM_AMD_OK;
+  }
+  // point buffers leave in the wire layout of the stage entry points: Jacobian, 3 x 8 u32 most significant first
+  uint32_t* o = (uint32_t*)out;
+  if (which == MSM_AMD_STAGE_BUCKETS) {
+    for (size_t i = 0; i < p.total_buckets; ++i) {
+      PtI q;
+      std::memcpy(&q, h.data() + i * sizeof(PtI), sizeof q);
+      jac_to_be32(pti_to_ext(q), o + i * 24);
+    }
+  } else {
+    for (size_t i = 0; i < p.partial_count; ++i) {
+      Jacobian q;
+      std::memcpy(&q, h.data() + i * sizeof(Jacobian), sizeof q);
+      jac_to_be32(q, o + i * 24);
+    }
+  }
+  return MSM_AMD_OK;
+}
+
+// Point-valued workspace buffers only: a poisoned index or count could make a kernel gather from wild addresses, a
+// poisoned point can only make a result wrong.
+int msm_amd_test_fill_workspaces(msm_amd_ctx* ctx, uint8_t byte) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (int rc = recover_if_stalled(ctx)) return rc;
+  for (const Batch& b : ctx->batches)
+    if (b.active) return fail(ctx, MSM_AMD_INPUT_ERROR, "test_fill_workspaces: a batch is in flight");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!drain_or_mark_stalled(ctx)) return fail(ctx, MSM_AMD_PIPELINE_ERROR, "test_fill_workspaces: device busy");
+  for (Workspace& w : ctx->ws) {
+    DeviceBuf* bufs[] = {&w.buckets, &w.item_partials, &w.S, &w.T, &w.partial};
+    for (DeviceBuf* b : bufs)
+      if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
+  }
+  return sync_stream_bounded(ctx, ctx->stream, __func__);
 }
 
 int msm_amd_last_timings(const msm_amd_ctx* ctx, msm_amd_timings* out) {

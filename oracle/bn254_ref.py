@@ -215,6 +215,25 @@ def prepare_buckets_indices(scalars, window_size: int, num_windows: int):
     return out
 
 
+def signed_digits(k: int, c: int, W: int = None):
+    """Signed-digit recoding of the per-call pipeline (digits_kernel, k_sort.hip): the raw c-bit window value plus
+    the carry of the window below; a value above 2^(c-1) becomes v - 2^c and carries 1 into the next window.  So
+    k = sum_w d_w 2^(c w) with d_w in (-2^(c-1), 2^(c-1)].  W defaults to the pipeline's floor(254 / c) + 1 windows,
+    whose top window absorbs the last carry for every k < 2^254."""
+    if W is None:
+        W = MODULUS_BIT_SIZE // c + 1
+    half, mask = 1 << (c - 1), (1 << c) - 1
+    out, carry = [], 0
+    for w in range(W):
+        v = ((k >> (c * w)) & mask) + carry
+        carry = 0
+        if v > half:
+            v -= 1 << c
+            carry = 1
+        out.append(v)
+    return out
+
+
 def sort_buckets_indices(pairs):
     """sort_buckets_indices (sort_buckets.rs:15-34): stable sort by .0 (tests only require the
     multiset to be preserved and keys non-decreasing, sort_buckets.rs:111-125)."""

@@ -44,6 +44,16 @@ def lib():
         L.oracle_fr_from_mont.restype = None
         L.oracle_jac_double.argtypes = [c_char_p, c_void_p]
         L.oracle_jac_double.restype = None
+        L.oracle_stage_buckets.argtypes = [c_void_p, c_size_t, c_uint32, c_uint32, c_char_p, c_void_p]
+        L.oracle_stage_buckets.restype = None
+        L.oracle_stage_partials.argtypes = [c_char_p, c_uint32, c_uint32, c_void_p, c_void_p]
+        L.oracle_stage_partials.restype = None
+        L.oracle_jac_mismatches.argtypes = [c_char_p, c_char_p, c_size_t, c_void_p, ctypes.POINTER(c_size_t)]
+        L.oracle_jac_mismatches.restype = c_size_t
+        L.oracle_step_count.restype = c_uint32
+        L.oracle_replay_items.argtypes = [c_void_p, c_void_p, c_void_p, c_size_t, c_uint32, c_uint32, c_uint32,
+                                          c_char_p, c_void_p]
+        L.oracle_replay_items.restype = None
         _LIB = L
     return _LIB
 
@@ -158,3 +168,56 @@ def fr_from_mont(a):
     out = ctypes.create_string_buffer(32)
     lib().oracle_fr_from_mont(a, out)
     return out.raw
+
+
+# ---- stage oracle of the per-call pipeline (tests/test_gpu_pipeline_stages.py) -----------------------------------
+# Jacobian values are 96-byte records (x, y, z Montgomery, 32-byte little-endian each; z = 0 is the identity).
+STEP_CLASSES = ("identity_skip", "first_point", "phase_a_double", "phase_a_cancel", "phase_a_generic",
+                "phase_b_generic", "phase_b_double", "phase_b_cancel", "split_small", "split_big",
+                "split_item_identity", "split_all_equal")
+
+
+def _ptr(a):
+    return a.ctypes.data_as(c_void_p)
+
+
+def stage_buckets(digits, points64: bytes, lb: int) -> bytes:
+    """Bucket sums [W][2^lb] of a signed digit matrix digits[W][n] (numpy int32) over h2c affine points."""
+    import numpy as np
+    d = np.ascontiguousarray(digits, dtype=np.int32)
+    W, n = d.shape
+    out = ctypes.create_string_buffer(W * (1 << lb) * 96)
+    lib().oracle_stage_buckets(_ptr(d), n, W, lb, points64, out)
+    return out.raw
+
+
+def stage_partials(buckets96: bytes, W: int, lb: int):
+    """(partial [W][lb + 1], window sums [W]) of a bucket matrix: bit-k subset sums over the slot index, the total,
+    and sum_s (s + 1) B[w][s]."""
+    part = ctypes.create_string_buffer(W * (lb + 1) * 96)
+    win = ctypes.create_string_buffer(W * 96)
+    lib().oracle_stage_partials(buckets96, W, lb, part, win)
+    return part.raw, win.raw
+
+
+def jac_mismatches(a96: bytes, b96: bytes, mask=None):
+    """(number of entries whose group elements differ, first such index) -- masked entries only if a mask is given."""
+    import numpy as np
+    count = len(a96) // 96
+    assert len(b96) == len(a96)
+    m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint32)
+    first = c_size_t(0)
+    bad = lib().oracle_jac_mismatches(a96, b96, count, None if m is None else _ptr(m), ctypes.byref(first))
+    return bad, first.value
+
+
+def replay_items(sorted_u32, bucket_start, bucket_size, n: int, W: int, lb: int, CH: int, points64: bytes):
+    """Per-step classes of the accumulate kernel's state machine over the work items of a plan (dict by class)."""
+    import numpy as np
+    assert lib().oracle_step_count() == len(STEP_CLASSES)
+    counts = np.zeros(len(STEP_CLASSES), dtype=np.uint64)
+    s = np.ascontiguousarray(sorted_u32, dtype=np.uint32)
+    bs = np.ascontiguousarray(bucket_start, dtype=np.uint32)
+    bz = np.ascontiguousarray(bucket_size, dtype=np.uint32)
+    lib().oracle_replay_items(_ptr(s), _ptr(bs), _ptr(bz), n, W, lb, CH, points64, _ptr(counts))
+    return dict(zip(STEP_CLASSES, (int(v) for v in counts)))

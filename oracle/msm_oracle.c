@@ -652,3 +652,158 @@ int oracle_dlog_instance(const uint8_t* a0_canon32, const uint8_t* d_canon32, co
   free(th); free(jobs);
   return 0;
 }
+
+/* ------------------------------------------------------------------------------------------------ */
+/* Stage oracle of the per-call pipeline (tests/test_gpu_pipeline_stages.py).  Points are h2c affine records
+ * (64 B, Montgomery, (0,0) = identity); Jacobian values are jac_t records (96 B, Montgomery LE, z = 0 identity). */
+static inline void aff_at(aff_t* q, const uint8_t* points64, size_t i) { memcpy(q, points64 + i * 64, 64); }
+
+/* 1: a == b as group elements, 0: not */
+static int jac_eq(const jac_t* a, const jac_t* b) {
+  const int ia = jac_is_id(a), ib = jac_is_id(b);
+  if (ia || ib) return ia == ib;
+  fe za2, zb2, za3, zb3, l, r;
+  QSQR(&za2, &a->z); QSQR(&zb2, &b->z);
+  QMUL(&l, &a->x, &zb2); QMUL(&r, &b->x, &za2);
+  if (!fe_eq(&l, &r)) return 0;
+  QMUL(&za3, &za2, &a->z); QMUL(&zb3, &zb2, &b->z);
+  QMUL(&l, &a->y, &zb3); QMUL(&r, &b->y, &za3);
+  return fe_eq(&l, &r);
+}
+/* 1: a == q, -1: a == -q, 0: neither (a, q finite) */
+static int jac_aff_cmp(const jac_t* a, const aff_t* q) {
+  fe z2, z3, t;
+  QSQR(&z2, &a->z); QMUL(&t, &q->x, &z2);
+  if (!fe_eq(&t, &a->x)) return 0;
+  QMUL(&z3, &z2, &a->z); QMUL(&t, &q->y, &z3);
+  return fe_eq(&t, &a->y) ? 1 : -1;
+}
+
+/* buckets[w][s] = sum of sign(d) P_i over the points i whose digit d = digits[w * n + i] has |d| = s + 1 */
+void oracle_stage_buckets(const int32_t* digits, size_t n, uint32_t W, uint32_t lb, const uint8_t* points64,
+                          uint8_t* buckets96) {
+  const size_t nb = (size_t)1 << lb;
+  jac_t* B = (jac_t*)buckets96;
+  for (size_t b = 0; b < (size_t)W * nb; ++b) jac_set_id(&B[b]);
+  for (uint32_t w = 0; w < W; ++w)
+    for (size_t i = 0; i < n; ++i) {
+      const int32_t d = digits[(size_t)w * n + i];
+      if (d == 0) continue;
+      aff_t q;
+      aff_at(&q, points64, i);
+      if (aff_is_id(&q)) continue;
+      jac_t* acc = &B[(size_t)w * nb + (size_t)(d < 0 ? -d : d) - 1];
+      jac_madd_signed(acc, acc, &q, d < 0);
+    }
+}
+
+/* partial[w][k] = sum of B[w][s] over the slots s with bit k set (k < lb), partial[w][lb] = sum of all B[w][s];
+ * window[w] = sum_s (s + 1) B[w][s] (running sums) */
+void oracle_stage_partials(const uint8_t* buckets96, uint32_t W, uint32_t lb, uint8_t* partial96, uint8_t* window96) {
+  const size_t nb = (size_t)1 << lb;
+  const jac_t* B = (const jac_t*)buckets96;
+  jac_t* P = (jac_t*)partial96;
+  jac_t* S = (jac_t*)window96;
+  for (uint32_t w = 0; w < W; ++w) {
+    jac_t* pw = P + (size_t)w * (lb + 1);
+    for (uint32_t k = 0; k <= lb; ++k) jac_set_id(&pw[k]);
+    jac_t run, acc;
+    jac_set_id(&run);
+    jac_set_id(&acc);
+    for (size_t s = nb; s-- > 0;) {
+      const jac_t* b = &B[(size_t)w * nb + s];
+      for (uint32_t k = 0; k < lb; ++k)
+        if ((s >> k) & 1) jac_add(&pw[k], &pw[k], b);
+      jac_add(&pw[lb], &pw[lb], b);
+      jac_add(&run, &run, b);
+      jac_add(&acc, &acc, &run);
+    }
+    S[w] = acc;
+  }
+}
+
+/* Entries i (with mask[i] != 0, or all if mask is NULL) where a[i] and b[i] are different group elements; the first
+ * such index goes to *first (count if none). */
+size_t oracle_jac_mismatches(const uint8_t* a96, const uint8_t* b96, size_t count, const uint32_t* mask, size_t* first) {
+  const jac_t* A = (const jac_t*)a96;
+  const jac_t* B = (const jac_t*)b96;
+  size_t bad = 0;
+  *first = count;
+  for (size_t i = 0; i < count; ++i) {
+    if (mask && !mask[i]) continue;
+    if (!jac_eq(&A[i], &B[i])) {
+      if (bad++ == 0) *first = i;
+    }
+  }
+  return bad;
+}
+
+/* Replay of accumulate_item (k_accumulate.hip) and of the combine pass, step by step in the order the kernel takes
+ * the points (the `sorted` slice of every work item), classifying each step by what the kernel's state machine does.
+ * counts[ORACLE_STEP_*] += occurrences; item sums are not returned (the bucket values come from oracle_stage_buckets). */
+enum {
+  ORACLE_STEP_IDENTITY_SKIP = 0,   /* an identity base: skipped */
+  ORACLE_STEP_FIRST,               /* first point of an item (or after a cancellation): kEmpty -> kOne */
+  ORACLE_STEP_A_DOUBLE,            /* phase A, accumulator (one affine point) == point: doubling */
+  ORACLE_STEP_A_CANCEL,            /* phase A, accumulator == -point: vanished -> kEmpty */
+  ORACLE_STEP_A_GENERIC,           /* phase A affine + affine */
+  ORACLE_STEP_B_GENERIC,           /* phase B mixed addition */
+  ORACLE_STEP_B_DOUBLE,            /* phase B, accumulator == point: doubling */
+  ORACLE_STEP_B_CANCEL,            /* phase B, accumulator == -point: vanished, back to phase A */
+  ORACLE_STEP_SPLIT_SMALL,         /* split bucket of <= 8 items (combine_small_kernel) */
+  ORACLE_STEP_SPLIT_BIG,           /* split bucket of > 8 items (combine_big_kernel) */
+  ORACLE_STEP_SPLIT_ITEM_IDENTITY, /* split bucket with an item that sums to the identity */
+  ORACLE_STEP_SPLIT_ALL_EQUAL,     /* split bucket whose item sums are all the same finite point */
+  ORACLE_STEP_COUNT
+};
+uint32_t oracle_step_count(void) { return ORACLE_STEP_COUNT; }
+
+void oracle_replay_items(const uint32_t* sorted, const uint32_t* bucket_start, const uint32_t* bucket_size, size_t n,
+                         uint32_t W, uint32_t lb, uint32_t CH, const uint8_t* points64, uint64_t* counts) {
+  enum { kEmpty, kOne, kMany };
+  const size_t nb = (size_t)1 << lb;
+  for (size_t b = 0; b < (size_t)W * nb; ++b) {
+    const uint32_t size = bucket_size[b];
+    if (size == 0) continue;
+    const uint32_t* slice = sorted + (b >> lb) * n + bucket_start[b];
+    const uint32_t nitems = (size + CH - 1) / CH;
+    int any_identity = 0, all_equal = 1;
+    jac_t first_sum;
+    for (uint32_t j = 0; j < nitems; ++j) {
+      const uint32_t lo = j * CH, cnt = size - lo < CH ? size - lo : CH;
+      jac_t acc;
+      jac_set_id(&acc);
+      int state = kEmpty;
+      for (uint32_t i = 0; i < cnt; ++i) {
+        const uint32_t e = slice[lo + i];
+        aff_t q;
+        aff_at(&q, points64, e & 0x7FFFFFFFu);
+        if (aff_is_id(&q)) { counts[ORACLE_STEP_IDENTITY_SKIP]++; continue; }
+        if (e >> 31) f_neg(&FQ, &q.y, &q.y);
+        if (state == kEmpty) {
+          counts[ORACLE_STEP_FIRST]++;
+          acc.x = q.x; acc.y = q.y; acc.z = FQ.one;
+          state = kOne;
+          continue;
+        }
+        const int cmp = jac_aff_cmp(&acc, &q);
+        const int phase_a = state == kOne;
+        if (cmp == 1) counts[phase_a ? ORACLE_STEP_A_DOUBLE : ORACLE_STEP_B_DOUBLE]++;
+        else if (cmp == -1) counts[phase_a ? ORACLE_STEP_A_CANCEL : ORACLE_STEP_B_CANCEL]++;
+        else counts[phase_a ? ORACLE_STEP_A_GENERIC : ORACLE_STEP_B_GENERIC]++;
+        jac_madd(&acc, &acc, &q);
+        state = jac_is_id(&acc) ? kEmpty : kMany;
+      }
+      if (nitems > 1) {
+        if (jac_is_id(&acc)) any_identity = 1;
+        if (j == 0) first_sum = acc;
+        else if (!jac_eq(&acc, &first_sum)) all_equal = 0;
+      }
+    }
+    if (nitems > 1) {
+      counts[nitems <= 8 ? ORACLE_STEP_SPLIT_SMALL : ORACLE_STEP_SPLIT_BIG]++;
+      if (any_identity) counts[ORACLE_STEP_SPLIT_ITEM_IDENTITY]++;
+      if (all_equal && !jac_is_id(&first_sum)) counts[ORACLE_STEP_SPLIT_ALL_EQUAL]++;
+    }
+  }
+}

@@ -179,3 +179,49 @@ def test_batched_affine_corner_cases():
         got, _ = co.msm_best_ex(sb, pb, n, threads, groups)
         assert o.decode_jacobian_mont_le(got) == want
     assert o.decode_jacobian_mont_le(co.msm_chunked(sb, pb, n, 2)) == want
+
+
+def _digit_edge_scalars(c, rng):
+    """0, 1, r - 1, 2^(c w) +- 1, scalars whose every window is 2^(c-1) or 2^(c-1) + 1 (carry chains), random ones."""
+    W = o.MODULUS_BIT_SIZE // c + 1
+    ks = [0, 1, 2, o.R_ORDER - 1, o.R_ORDER - 2, (1 << 14) + 1]
+    for w in range(1, W):
+        if c * w < 254:
+            ks += [(1 << (c * w)) - 1, (1 << (c * w)) + 1, 1 << (c * w)]
+    half = 1 << (c - 1)
+    for extra in range(2):
+        k = sum((half + (extra if (w % 2 or extra == 0) else 0)) << (c * w) for w in range(W))
+        ks.append(k % o.R_ORDER)
+        ks.append(sum((half + 1) << (c * w) for w in range(W)) % o.R_ORDER)
+        ks.append(sum(half << (c * w) for w in range(W)) % (1 << 254))
+    ks += [rng.randrange(o.R_ORDER) for _ in range(40)]
+    ks += [rng.randrange(1 << 254) for _ in range(10)]
+    return ks
+
+
+@pytest.mark.parametrize("c", range(2, 25))
+def test_signed_digits_properties(c):
+    """signed_digits restates the recoding of digits_kernel: exact value, digit range, no carry out of the top window."""
+    rng = random.Random(c)
+    W = o.MODULUS_BIT_SIZE // c + 1
+    half = 1 << (c - 1)
+    for k in _digit_edge_scalars(c, rng):
+        d = o.signed_digits(k, c)
+        assert len(d) == W
+        assert sum(dw << (c * w) for w, dw in enumerate(d)) == k
+        assert all(-half < dw <= half for dw in d)
+        # the top window never carries: one more window would always be 0
+        assert o.signed_digits(k, c, W + 1)[W] == 0
+        # the top window's raw value leaves room for the carry: it never becomes negative
+        assert d[-1] >= 0
+
+
+def test_signed_digits_known():
+    # 2^14 + 1 at c = 14 (the reference's breaking scalar of prepare_buckets_indices): windows 1, 1
+    assert o.signed_digits((1 << 14) + 1, 14)[:3] == [1, 1, 0]
+    # 2^(c-1) stays positive, 2^(c-1) + 1 becomes negative with a carry
+    assert o.signed_digits(8, 4)[:2] == [8, 0]
+    assert o.signed_digits(9, 4)[:2] == [-7, 1]
+    # a carry chain: every window 2^(c-1) + 1 -> every digit negative except where the carry lands on the top
+    d = o.signed_digits(sum(9 << (4 * w) for w in range(4)), 4)
+    assert d[:5] == [-7, -6, -6, -6, 1]
