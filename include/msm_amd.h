@@ -463,6 +463,37 @@ int msm_amd_test_op(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t*
 /* The same operation bodies executed on the host CPU (no GPU needed): host-logic tests. */
 int msm_amd_test_op_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count);
 
+/* ---- raw-limb test ops of the 29-bit-limb internal representation (csrc/bn254_fq29.hip.h, bn254_ec29.hip.h) -----
+ * The limbs pass through exactly as given: no from_ext, no byte reversal, no normalisation in or out, so that a test
+ * can put operands at the edges of the bounds contract and read result limbs.  Fixed-width records: a and b are 36
+ * little-endian u32 per element, out is 40.  a0 / a1 (b0 / b1) are words 0..8 / 9..17 of a (b); a point (PtI) is
+ * X, Y, ZZ, ZZZ in 36 words, an affine base (AffI) x, y in 18.  count <= 2^24; unknown ops: MSM_AMD_INPUT_ERROR. */
+enum {
+  MSM_AMD_RAW_FE_MUL = 0,        /* out[0..8] = mul(a0, b0) */
+  MSM_AMD_RAW_FE_SQR = 1,        /* sqr(a0) */
+  MSM_AMD_RAW_FE_MUL2 = 2,       /* mul2(a0, a1, b0, b1) = a0 a1 + b0 b1, one reduction */
+  MSM_AMD_RAW_FE_SUB_K4E30 = 3,  /* sub<K>(a0, b0) = a0 + K - b0, not normalised */
+  MSM_AMD_RAW_FE_SUB_K8E30 = 4,
+  MSM_AMD_RAW_FE_SUB_K8E31 = 5,
+  MSM_AMD_RAW_FE_SUB_K16E30 = 6,
+  MSM_AMD_RAW_FE_SUB_K16E31 = 7,
+  MSM_AMD_RAW_FE_NORM = 8,
+  MSM_AMD_RAW_FE_NEG = 9,
+  MSM_AMD_RAW_FE_NEG_WIDE = 10,
+  MSM_AMD_RAW_FE_CANONICAL = 11, /* canonical(a0, rounds = min(b0[0], 64)) */
+  MSM_AMD_RAW_FE_TO_EXT = 12,    /* out[0..7] = to_ext(a0), little-endian */
+  MSM_AMD_RAW_FE_PACK_UNPACK = 13, /* out[0..8] = unpack256(pack256(a0)), out[9..16] = pack256(a0) */
+  MSM_AMD_RAW_FE_ZERO = 14,      /* out[0] = maybe_zero(a0, bound = b0[0]), out[1] = is_zero_exact(a0) */
+  MSM_AMD_RAW_PT_MADD = 15,      /* out[0..35] = PtI a + AffI b (pti_madd_head + pti_madd_tail), out[36] = vanished */
+  MSM_AMD_RAW_PT_MMADD = 16,     /* affine (a0, a1) + AffI b (pti_mmadd_head + pti_mmadd_tail), out[36] = vanished */
+  MSM_AMD_RAW_PT_ADD_NZ = 17,    /* PtI a + PtI b, neither the identity (pti_add_nz), out[36] = vanished */
+  MSM_AMD_RAW_PT_ADD = 18,       /* pti_add: identities allowed, out[36] = 0 */
+  MSM_AMD_RAW_PT_DOUBLE = 19     /* pti_double(a) */
+};
+int msm_amd_test_op_raw(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count);
+/* The same bodies on the host CPU (no GPU needed). */
+int msm_amd_test_op_raw_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count);
+
 /* Test aid for the bounded waits: keeps the ctx's main stream busy for at most max_ms (<= 5000) or until
  * msm_amd_test_release(handle).  The kernel carries its own time limit. */
 int msm_amd_test_hold(msm_amd_ctx* ctx, uint32_t max_ms, void** handle);

@@ -26,6 +26,11 @@ POINT_BYTES = {POINT_H2C_AFFINE: 64, POINT_ARK_PROJECTIVE: 96, POINT_ARK_AFFINE:
  OP_EC29_ADD, OP_EC29_MADD_CHAIN, OP_EC29_ADD_CHAIN, OP_EC29_MMADD, OP_H64_FP_MUL, OP_H64_FP_ADD, OP_H64_FP_SUB,
  OP_H64_EC_ADD, OP_H64_EC_DBL, OP_FP29_MUL_KARATSUBA, OP_FP29_LOCKSTEP_PAIR, OP_FP29_LOCKSTEP_MIX,
  OP_FP29_LOCKSTEP_TRIPLE, OP_FP29_MUL2_KARATSUBA, OP_H64_FP_INV, OP_H64_FP_INV_FERMAT) = range(39)
+# raw-limb test ops (MSM_AMD_RAW_*): records of RAW_IN_WORDS u32 per operand, RAW_OUT_WORDS per result
+(RAW_FE_MUL, RAW_FE_SQR, RAW_FE_MUL2, RAW_FE_SUB_K4E30, RAW_FE_SUB_K8E30, RAW_FE_SUB_K8E31, RAW_FE_SUB_K16E30,
+ RAW_FE_SUB_K16E31, RAW_FE_NORM, RAW_FE_NEG, RAW_FE_NEG_WIDE, RAW_FE_CANONICAL, RAW_FE_TO_EXT, RAW_FE_PACK_UNPACK,
+ RAW_FE_ZERO, RAW_PT_MADD, RAW_PT_MMADD, RAW_PT_ADD_NZ, RAW_PT_ADD, RAW_PT_DOUBLE) = range(20)
+RAW_IN_WORDS, RAW_OUT_WORDS = 36, 40
 
 
 def op_is_point(op):
@@ -42,6 +47,7 @@ EXPORTS = [
     "msm_amd_copy_to_host", "msm_amd_stream", "msm_amd_synchronize", "msm_amd_generate_instance",
     "msm_amd_prepare_buckets_indices", "msm_amd_sort_buckets_indices", "msm_amd_bucket_wise_accumulation",
     "msm_amd_sum_reduction", "msm_amd_final_accumulation", "msm_amd_test_op", "msm_amd_test_op_host",
+    "msm_amd_test_op_raw", "msm_amd_test_op_raw_host",
     "msm_amd_last_timings",
     "msm_amd_algorithmic_bytes", "msm_amd_version",
     "msm_amd_instances_save", "msm_amd_instances_open", "msm_amd_instances_count", "msm_amd_instances_size",
@@ -171,6 +177,8 @@ def _lib():
         L.msm_amd_final_accumulation.argtypes = [c_void_p, c_uint32, c_uint32, c_void_p]
         L.msm_amd_test_op.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_test_op_host.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
+        L.msm_amd_test_op_raw.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t]
+        L.msm_amd_test_op_raw_host.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_last_timings.argtypes = [c_void_p, POINTER(Timings)]
         L.msm_amd_algorithmic_bytes.argtypes = [c_size_t, c_uint32, c_int]
         L.msm_amd_algorithmic_bytes.restype = c_uint64
@@ -485,6 +493,13 @@ class MsmConfig:
         self._check(_lib().msm_amd_test_op(self.h, op, _u32buf(a), _u32buf(b), out, count))
         return list(out)
 
+    def test_op_raw(self, op, a, b, count):
+        """Raw-limb op (MSM_AMD_RAW_*) on the device: a, b flat u32 lists of count * RAW_IN_WORDS; returns
+        count * RAW_OUT_WORDS u32."""
+        out = (c_uint32 * (count * RAW_OUT_WORDS))()
+        self._check(_lib().msm_amd_test_op_raw(self.h, op, _raw_in(a, count), _raw_in(b, count), out, count))
+        return list(out)
+
 
 def msm_batch_multi(configs, scalars_list, points_list, ns, scalar_layout=SCALAR_MONT_LE,
                     point_layout=POINT_H2C_AFFINE, device=False):
@@ -615,6 +630,21 @@ def test_op_host(op, a, b, count):
     per = 24 if op_is_point(op) else 8
     out = (c_uint32 * (count * per))()
     st = _lib().msm_amd_test_op_host(op, _u32buf(a), _u32buf(b), out, count)
+    if st != OK:
+        raise MsmError(st)
+    return list(out)
+
+
+def _raw_in(seq, count):
+    if len(seq) != count * RAW_IN_WORDS:
+        raise ValueError(f"a raw-limb operand holds {RAW_IN_WORDS} words per element")
+    return _u32buf(seq)
+
+
+def test_op_raw_host(op, a, b, count):
+    """Same raw-limb op bodies as MsmConfig.test_op_raw, executed on the host CPU by the library (no GPU)."""
+    out = (c_uint32 * (count * RAW_OUT_WORDS))()
+    st = _lib().msm_amd_test_op_raw_host(op, _raw_in(a, count), _raw_in(b, count), out, count)
     if st != OK:
         raise MsmError(st)
     return list(out)

@@ -228,6 +228,15 @@ test_op_kernel(int op, const u256* __restrict__ a, const u256* __restrict__ b, u
   run_test_op(op, a, b, out, t);
 }
 
+// Raw-limb single-op kernel (run_test_op_raw in test_ops.hip.h): kRawInWords u32 per operand, kRawOutWords per result.
+__global__ void __launch_bounds__(64)
+test_op_raw_kernel(int op, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t* __restrict__ out,
+                   uint32_t count) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= count) return;
+  run_test_op_raw(op, a, b, out, t);
+}
+
 // ------------------------------------------------------------------------------------------------
 void launch_ref_prepare(hipStream_t st, const u256* scalars, uint32_t n, uint32_t c, uint32_t W, uint2* pairs) {
   hipLaunchKernelGGL(ref_prepare_kernel, dim3((n + 255) / 256), dim3(256), 0, st, scalars, n, c, W, pairs);
@@ -284,6 +293,10 @@ void launch_filter_scatter(hipStream_t st, const u256* scalars, const Affine* po
 
 void launch_test_op(hipStream_t st, int op, const u256* a, const u256* b, u256* out, uint32_t count) {
   hipLaunchKernelGGL(test_op_kernel, dim3((count + 63) / 64), dim3(64), 0, st, op, a, b, out, count);
+}
+
+void launch_test_op_raw(hipStream_t st, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t count) {
+  hipLaunchKernelGGL(test_op_raw_kernel, dim3((count + 63) / 64), dim3(64), 0, st, op, a, b, out, count);
 }
 
 }  // namespace msm_amd

@@ -117,6 +117,7 @@ void launch_filter_count(hipStream_t st, const u256* scalars, uint32_t n, uint32
 void launch_filter_scatter(hipStream_t st, const u256* scalars, const Affine* points, uint32_t n,
                            const uint32_t* block_counts, u256* out_scalars, Affine* out_points);
 void launch_test_op(hipStream_t st, int op, const u256* a, const u256* b, u256* out, uint32_t count);
+void launch_test_op_raw(hipStream_t st, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t count);
 
 // host_msm.hip (host code only)
 Jacobian host_msm(const u256* scalars, int scalars_mont, const Affine* points, size_t n, int threads, bool* ok = nullptr);   // *ok = false: host allocation failed

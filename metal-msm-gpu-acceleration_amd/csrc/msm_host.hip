@@ -2836,6 +2836,36 @@ int msm_amd_test_op_host(int op, const uint32_t* a, const uint32_t* b, uint32_t*
   return MSM_AMD_OK;
 }
 
+// Raw-limb test ops: the internal limbs pass through unchanged (no from_ext, no reversal, no normalisation).
+static bool test_op_raw_args(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
+  return a && b && out && count > 0 && count <= (1u << 24) && op >= 0 && op < kRawOpCount;
+}
+
+int msm_amd_test_op_raw(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
+  if (!ctx || !test_op_raw_args(op, a, b, out, count)) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_op_raw arguments");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t in_bytes = count * kRawInWords * 4, out_bytes = count * kRawOutWords * 4;
+  int rc;
+  if ((rc = ensure(ctx, ctx->scratch_a, in_bytes))) return rc;
+  if ((rc = ensure(ctx, ctx->scratch_b, in_bytes))) return rc;
+  if ((rc = ensure(ctx, ctx->scratch_c, out_bytes))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_a.p, a, in_bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_b.p, b, in_bytes, hipMemcpyHostToDevice, st));
+  launch_test_op_raw(st, op, (const uint32_t*)ctx->scratch_a.p, (const uint32_t*)ctx->scratch_b.p,
+                     (uint32_t*)ctx->scratch_c.p, (uint32_t)count);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch_c.p, out_bytes, hipMemcpyDeviceToHost, st));
+  return sync_stream_bounded(ctx, st, __func__);
+}
+
+int msm_amd_test_op_raw_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
+  if (!test_op_raw_args(op, a, b, out, count)) return MSM_AMD_INPUT_ERROR;
+  for (size_t t = 0; t < count; ++t) run_test_op_raw(op, a, b, out, (uint32_t)t);
+  return MSM_AMD_OK;
+}
+
 // Test aid: occupy the ctx's main stream for at most max_ms (<= 5000) or until msm_amd_test_release -- what a stalled
 // device looks like to the host waits.  The kernel has its own time bound, so nothing can stay blocked.
 int msm_amd_test_hold(msm_amd_ctx* ctx, uint32_t max_ms, void** handle) {

@@ -143,6 +143,103 @@ MSM_HD void run_test_op(int op, const u256* a, const u256* b, u256* out, uint32_
   po[t] = r;
 }
 
+// ---- raw-limb ops (msm_amd_test_op_raw / _host, MSM_AMD_RAW_*): the internal limbs go in and come out exactly as
+// given, so that a test can put operands at the edges of the bounds contract and see result limbs, not only values.
+// Record of element t: a, b = kRawInWords u32 from t * kRawInWords, out = kRawOutWords u32 from t * kRawOutWords.
+constexpr int kRawInWords = 36, kRawOutWords = 40, kRawOpCount = 20;
+
+MSM_HD fe29 raw_fe(const uint32_t* w) {
+  fe29 r;
+  MSM_UNROLL for (int i = 0; i < 9; ++i) r.l[i] = w[i];
+  return r;
+}
+MSM_HD void raw_put_fe(uint32_t* w, const fe29& f) {
+  MSM_UNROLL for (int i = 0; i < 9; ++i) w[i] = f.l[i];
+}
+MSM_HD PtI raw_pt(const uint32_t* w) {
+  PtI r;
+  r.x = raw_fe(w);
+  r.y = raw_fe(w + 9);
+  r.zz = raw_fe(w + 18);
+  r.zzz = raw_fe(w + 27);
+  return r;
+}
+MSM_HD void raw_put_pt(uint32_t* w, const PtI& p) {
+  raw_put_fe(w, p.x);
+  raw_put_fe(w + 9, p.y);
+  raw_put_fe(w + 18, p.zz);
+  raw_put_fe(w + 27, p.zzz);
+}
+
+MSM_HD void run_test_op_raw(int op, const uint32_t* a_all, const uint32_t* b_all, uint32_t* out_all, uint32_t t) {
+  const uint32_t* a = a_all + (size_t)t * kRawInWords;
+  const uint32_t* b = b_all + (size_t)t * kRawInWords;
+  uint32_t* out = out_all + (size_t)t * kRawOutWords;
+  uint32_t r[kRawOutWords];
+  MSM_UNROLL for (int i = 0; i < kRawOutWords; ++i) r[i] = 0;
+  const fe29 a0 = raw_fe(a), a1 = raw_fe(a + 9), b0 = raw_fe(b), b1 = raw_fe(b + 9);
+  bool vanished = false;
+  switch (op) {
+    case 0: raw_put_fe(r, Fq29::mul(a0, b0)); break;                // MSM_AMD_RAW_FE_MUL
+    case 1: raw_put_fe(r, Fq29::sqr(a0)); break;                    // FE_SQR
+    case 2: raw_put_fe(r, Fq29::mul2(a0, a1, b0, b1)); break;       // FE_MUL2: a0 * a1 + b0 * b1
+    case 3: raw_put_fe(r, Fq29::sub<K4E30>(a0, b0)); break;         // FE_SUB_K4E30 ... FE_SUB_K16E31: not normalised
+    case 4: raw_put_fe(r, Fq29::sub<K8E30>(a0, b0)); break;
+    case 5: raw_put_fe(r, Fq29::sub<K8E31>(a0, b0)); break;
+    case 6: raw_put_fe(r, Fq29::sub<K16E30>(a0, b0)); break;
+    case 7: raw_put_fe(r, Fq29::sub<K16E31>(a0, b0)); break;
+    case 8: raw_put_fe(r, Fq29::norm(a0)); break;                   // FE_NORM
+    case 9: raw_put_fe(r, Fq29::neg(a0)); break;                    // FE_NEG
+    case 10: raw_put_fe(r, Fq29::neg_wide(a0)); break;              // FE_NEG_WIDE
+    case 11:                                                        // FE_CANONICAL: rounds = b0.l[0], at most 64
+      raw_put_fe(r, Fq29::canonical(a0, (int)(b0.l[0] < 64u ? b0.l[0] : 64u)));
+      break;
+    case 12: {                                                      // FE_TO_EXT: 8 words little-endian
+      const u256 e = Fq29::to_ext(a0);
+      MSM_UNROLL for (int i = 0; i < 8; ++i) r[i] = e.v[i];
+      break;
+    }
+    case 13: {                                                      // FE_PACK_UNPACK: limbs, then the packed words
+      const u256 w = Fq29::pack256(a0);
+      raw_put_fe(r, Fq29::unpack256(w));
+      MSM_UNROLL for (int i = 0; i < 8; ++i) r[9 + i] = w.v[i];
+      break;
+    }
+    case 14:                                                        // FE_ZERO: maybe_zero(a0, bound = b0.l[0]), exact
+      r[0] = Fq29::maybe_zero(a0, b0.l[0]) ? 1u : 0u;
+      r[1] = Fq29::is_zero_exact(a0) ? 1u : 0u;
+      break;
+    case 15: {   // PT_MADD: PtI a + AffI b (b = x, y: 18 words) through the head / tail pair of accumulate_kernel
+      PtI p = raw_pt(a);
+      AffI q;
+      q.x = b0;
+      q.y = b1;
+      fe29 U2, S2;
+      pti_madd_head(p, q.x, q.y, U2, S2);
+      raw_put_pt(r, pti_madd_tail(p, U2, S2, [&]() { return q; }, vanished));
+      r[36] = vanished ? 1u : 0u;
+      break;
+    }
+    case 16: {   // PT_MMADD: (a0, a1) + AffI b by the head / tail pair
+      AffI q;
+      q.x = b0;
+      q.y = b1;
+      fe29 P, R;
+      pti_mmadd_head(a0, a1, q.x, q.y, P, R);
+      raw_put_pt(r, pti_mmadd_tail(a0, a1, P, R, [&]() { return q; }, vanished));
+      r[36] = vanished ? 1u : 0u;
+      break;
+    }
+    case 17:     // PT_ADD_NZ: PtI a + PtI b, neither the identity
+      raw_put_pt(r, pti_add_nz(raw_pt(a), raw_pt(b), vanished));
+      r[36] = vanished ? 1u : 0u;
+      break;
+    case 18: raw_put_pt(r, pti_add(raw_pt(a), raw_pt(b))); break;   // PT_ADD: identities allowed; no vanished flag
+    case 19: raw_put_pt(r, pti_double(raw_pt(a))); break;           // PT_DOUBLE
+  }
+  MSM_UNROLL for (int i = 0; i < kRawOutWords; ++i) out[i] = r[i];
+}
+
 #if defined(MSM_AMD_EXPERIMENTS)
 constexpr int kTestOpMax = 36;   // 27..31 exist on the host only (msm_host.hip), 32..36: the experimental multiplication forms
 #else

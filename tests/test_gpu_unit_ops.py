@@ -152,3 +152,42 @@ def test_unshipped_multiplication_variants_on_the_device(cfg, msm_pkg):
     assert run(msm_pkg.OP_FP29_MUL2_KARATSUBA) == [2 * x * y % P for x, y in zip(a, b)]
     with pytest.raises(msm_pkg.MsmError):
         cfg.test_op(msm_pkg.OP_H64_FP_MUL, fa, fb, cnt)
+
+
+def test_fp29_internal_ops_on_the_device(cfg, msm_pkg):
+    """Ops 14..21 (the internal field ops: mul, sqr, the five lifted subtractions, the round trip) on the GPU with the
+    EDGE values of test_host_fe29: same answers as the host twin and as the oracle."""
+    from test_host_fe29 import EDGE
+    rng = random.Random(1421)
+    a = EDGE + [rng.randrange(o.P) for _ in range(200)]
+    b = list(reversed(EDGE)) + [rng.randrange(o.P) for _ in range(200)]
+    a, b = a + EDGE * len(EDGE), b + [y for y in EDGE for _ in EDGE]    # every EDGE pair
+    cnt = len(a)
+    fa, fb = sum((fq_be32(x) for x in a), []), sum((fq_be32(x) for x in b), [])
+    P = o.P
+    expect = {msm_pkg.OP_FP29_MUL: [x * y % P for x, y in zip(a, b)], msm_pkg.OP_FP29_SQR: [x * x % P for x in a],
+              msm_pkg.OP_FP29_SUB_K4E30: [(x - y) % P for x, y in zip(a, b)],
+              msm_pkg.OP_FP29_SUB_K8E30: [(x - y) % P for x, y in zip(a, b)],
+              msm_pkg.OP_FP29_SUB_K8E31: [(x - 3 * y) % P for x, y in zip(a, b)],
+              msm_pkg.OP_FP29_SUB_K16E30: [(x - y) % P for x, y in zip(a, b)],
+              msm_pkg.OP_FP29_SUB_K16E31: [(x - 3 * y) % P for x, y in zip(a, b)],
+              msm_pkg.OP_FP29_ROUNDTRIP: a}
+    for op, exp in expect.items():
+        flat = cfg.test_op(op, fa, fb, cnt)
+        assert list(flat) == list(msm_pkg.test_op_host(op, fa, fb, cnt)), op
+        assert [be32_fq(flat[8 * i:8 * i + 8]) for i in range(cnt)] == exp, op
+
+
+def test_ec29_add_chain_on_the_device(cfg, msm_pkg):
+    """Op 25 (16 chained full additions in the lazy form) on the GPU, incl. identities, doubling and cancellation."""
+    rng = random.Random(25)
+    P = [rand_point(rng) for _ in range(10)]
+    cases = [(P[0], P[1]), (None, P[2]), (P[3], P[3]), (P[4], o.aff_neg(P[4])), (P[5], None),
+             (o.scalar_mul(16, P[6]), o.aff_neg(P[6])), (o.scalar_mul(5, P[7]), o.aff_neg(P[7])), (P[8], P[9])]
+    cnt = len(cases)
+    a = sum((o.encode_point_be32(rand_jac(rng, p)) for p, _ in cases), [])
+    b = sum((o.encode_point_be32(rand_jac(rng, q)) for _, q in cases), [])
+    dev = cfg.test_op(msm_pkg.OP_EC29_ADD_CHAIN, a, b, cnt)
+    assert list(dev) == list(msm_pkg.test_op_host(msm_pkg.OP_EC29_ADD_CHAIN, a, b, cnt))
+    exp = [o.aff_add(p, o.scalar_mul(16, q)) if q is not None else p for p, q in cases]
+    assert [decode_be32_affine(dev[24 * i:24 * i + 24]) for i in range(cnt)] == exp

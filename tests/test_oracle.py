@@ -225,3 +225,57 @@ def test_signed_digits_known():
     # a carry chain: every window 2^(c-1) + 1 -> every digit negative except where the carry lands on the top
     d = o.signed_digits(sum(9 << (4 * w) for w in range(4)), 4)
     assert d[:5] == [-7, -6, -6, -6, 1]
+
+
+# ---- oracle/fq29_ref.py: the big-integer model of the 29-bit-limb internal representation -----------------------------
+def test_fq29_model_constants_come_from_the_header():
+    from oracle import fq29_ref as m
+    assert m.P == o.P and m.RHO == 1 << 261
+    for name, limbs in m.KL.items():
+        assert m.value(limbs) == m.KMULT[name] * o.P
+    assert (m.INV["X"], m.INV["Y"], m.INV["ZZ"], m.INV["ZZZ"]) == (m.FB.INV_X, m.FB.INV_Y, m.FB.INV_ZZ, m.FB.INV_ZZZ)
+    assert m.PINV29 * o.P % (1 << 29) == 1
+
+
+def test_fq29_corpus_meets_its_preconditions():
+    """Every generated operand is inside the contract it claims (else a failure would be the corpus's, not the
+    code's), and the edge records are really at the edge."""
+    from oracle import fq29_ref as m
+    for op in range(m.FE_ZERO + 1):
+        for a, b in m.field_corpus(op):
+            assert not m.field_pre(op, a, b), (m.OP_NAMES[op], a, b)
+    at_max = m.field_corpus(m.FE_MUL)[0][0][:9]
+    assert at_max[:8] == [m.MUL_LIMB_MAX] * 8 and m.value(at_max) <= m.MUL_VALUE_MAX < m.value(at_max) + (1 << 232)
+    for op in (m.PT_MADD, m.PT_MMADD, m.PT_ADD_NZ, m.PT_ADD, m.PT_DOUBLE):
+        corpus = m.point_corpus(op, n=8)
+        for a, b, _, _ in corpus:
+            assert not m.point_pre(op, a, b), m.OP_NAMES[op]
+    # the lifted points reach the invariant's edge: Y within p of 6 p, some limb at 2^29 + 7
+    pts = [c[0] for c in m.point_corpus(m.PT_DOUBLE, n=8)]
+    assert max(m.value(a[9:18]) for a in pts) > 5 * o.P
+    assert max(max(a[0:8]) for a in pts) == m.NORM_LIMB_MAX
+
+
+def test_fq29_model_agrees_with_bn254_ref():
+    """On canonical inputs the model's Montgomery multiplication, to_ext and XYZZ decoding are the plain field and
+    group operations of bn254_ref."""
+    from oracle import fq29_ref as m
+    rng = random.Random(29)
+    for _ in range(200):
+        x, y = rng.randrange(o.P), rng.randrange(o.P)
+        r = m.mont(m.to_mont(x) * m.to_mont(y))
+        assert r < 2 * o.P and m.from_mont(r) == x * y % o.P
+        assert m.mont(m.to_mont(x) * m.DOUT) % o.P == o.fq_to_mont(x)
+    for _ in range(20):
+        p = rand_point(rng)
+        for target in (None, "X", "ZZ"):
+            limbs = m.xyzz(p, rng, target=target)
+            assert m.decode_point([w for f in limbs for w in f]) == p and not m.point_post(sum(limbs, []))
+    q = rand_point(rng)
+    bx, by = m.affine_base(q, True)
+    assert m.affine_of(bx, by) == q
+    assert m.decode_point(m.rec(m.canon(m.to_mont(1)), m.canon(m.to_mont(1)), [0] * 9, [0] * 9)) is None
+    # the filter: every j p below the bound passes, the exact test tells the near misses apart
+    for bound in (6, 18):
+        assert all(m.maybe_zero((j * o.P) & m.MASK, bound) for j in range(bound))
+        assert not m.maybe_zero((bound * o.P) & m.MASK, bound)
