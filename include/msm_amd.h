@@ -488,7 +488,11 @@ enum {
   MSM_AMD_RAW_PT_MMADD = 16,     /* affine (a0, a1) + AffI b (pti_mmadd_head + pti_mmadd_tail), out[36] = vanished */
   MSM_AMD_RAW_PT_ADD_NZ = 17,    /* PtI a + PtI b, neither the identity (pti_add_nz), out[36] = vanished */
   MSM_AMD_RAW_PT_ADD = 18,       /* pti_add: identities allowed, out[36] = 0 */
-  MSM_AMD_RAW_PT_DOUBLE = 19     /* pti_double(a) */
+  MSM_AMD_RAW_PT_DOUBLE = 19,    /* pti_double(a) */
+  /* the point additions' forms with wide quotient digits (reduce_columns<true>): 20..31 stay unknown */
+  MSM_AMD_RAW_FE_MUL_WIDE = 32,  /* mul_np(a0, b0) */
+  MSM_AMD_RAW_FE_SQR_WIDE = 33,  /* sqr_np(a0) */
+  MSM_AMD_RAW_FE_MUL2_WIDE = 34  /* mul2w_np(a0, a1, b0, b1) */
 };
 int msm_amd_test_op_raw(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count);
 /* The same bodies on the host CPU (no GPU needed). */

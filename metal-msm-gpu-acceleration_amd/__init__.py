@@ -30,6 +30,7 @@ POINT_BYTES = {POINT_H2C_AFFINE: 64, POINT_ARK_PROJECTIVE: 96, POINT_ARK_AFFINE:
 (RAW_FE_MUL, RAW_FE_SQR, RAW_FE_MUL2, RAW_FE_SUB_K4E30, RAW_FE_SUB_K8E30, RAW_FE_SUB_K8E31, RAW_FE_SUB_K16E30,
  RAW_FE_SUB_K16E31, RAW_FE_NORM, RAW_FE_NEG, RAW_FE_NEG_WIDE, RAW_FE_CANONICAL, RAW_FE_TO_EXT, RAW_FE_PACK_UNPACK,
  RAW_FE_ZERO, RAW_PT_MADD, RAW_PT_MMADD, RAW_PT_ADD_NZ, RAW_PT_ADD, RAW_PT_DOUBLE) = range(20)
+RAW_FE_MUL_WIDE, RAW_FE_SQR_WIDE, RAW_FE_MUL2_WIDE = range(32, 35)   # the point additions' wide-digit forms
 RAW_IN_WORDS, RAW_OUT_WORDS = 36, 40
 
 

@@ -6,8 +6,8 @@
 //   PtI  144 bytes: X, Y, ZZ, ZZZ (9 limbs each), extended Jacobian ("XYZZ": x = X/ZZ, y = Y/ZZZ,
 //        ZZ^3 = ZZZ^2); ZZ limbs all zero = identity
 // Formulas (EFD, short Weierstrass a = 0, XYZZ): mixed addition madd-2008-s (8M + 2S), addition add-2008-s
-// (12M + 2S), doubling dbl-2008-s-1.  One squaring less per mixed addition than Jacobian madd (8M + 3S) and
-// two less per full addition; no small-constant multiples, which would cost extra normalisations on lazily
+// (12M + 2S in 11 reductions), doubling dbl-2008-s-1.  One squaring less per mixed addition than Jacobian madd
+// (8M + 3S) and two less per full addition; no small-constant multiples, which would cost extra normalisations on lazily
 // reduced limbs.  The reference's operator+ (ec_point.h.metal:13-69) is Jacobian add-2007-bl (11M + 5S) on
 // 32-bit limbs for every pair.
 //
@@ -304,37 +304,44 @@ MSM_HD PtI pti_mmadd(const fe29& px, const fe29& py, const AffI& q) {
   return pti_mmadd(px, py, q, vanished);
 }
 
-// p + q, both XYZZ, neither the identity.  add-2008-s, 12M + 2S.
+// p + q, both XYZZ, neither the identity.  add-2008-s (12M + 2S) with its 14 products grouped into 11 Montgomery
+// reductions instead of 13:
+//   P = X2 ZZ1 - X1 ZZ2,  R = Y2 ZZZ1 - Y1 ZZZ2        (double products: U1, U2, S1, S2 are never reduced alone)
+//   V = ZZ2 PP,  Tz = ZZZ2 PPP,  Q = X1 V (= U1 PP),  ZZ3 = ZZ1 V,  ZZZ3 = ZZZ1 Tz,  Y3 = R (Q - X3) - Y1 Tz
+// Every value is the one of the textbook grouping (the same Montgomery factors), P and R now reduction outputs:
+// P < 1.40 p, so its one-limb zero filter needs bound 2 only.
 MSM_HD PtI pti_add_nz(const PtI& p_in, const PtI& q_in, bool& vanished) {
+  MSM_ISA_MARK("begin full_addition");
   // pins once per basic block, multiplications without pins of their own (see pti_madd_head)
   PtI p, q;
   p.x = pin_limbs(p_in.x); p.y = pin_limbs(p_in.y); p.zz = pin_limbs(p_in.zz); p.zzz = pin_limbs(p_in.zzz);
   q.x = pin_limbs(q_in.x); q.y = pin_limbs(q_in.y); q.zz = pin_limbs(q_in.zz); q.zzz = pin_limbs(q_in.zzz);
-  const fe29 U1a = Fq29::mul_np(p.x, q.zz);
-  const fe29 U2 = Fq29::mul_np(q.x, p.zz);
-  const fe29 S1a = Fq29::mul_np(p.y, q.zzz);
-  const fe29 S2 = Fq29::mul_np(q.y, p.zzz);
-  const fe29 P0 = Fq29::norm(Fq29::sub<K4E30>(U2, U1a));     // < 5.2 p
-  const fe29 R0 = Fq29::norm(Fq29::sub<K4E30>(S2, S1a));     // < 5.1 p
-  if (Fq29::maybe_zero(P0, 6)) {
+  const fe29 P0 = Fq29::mul2w_np(q.x, p.zz, p.x, Fq29::neg_wide(q.zz));      // U2 - U1 + 4 U1' p   < 1.40 p
+  const fe29 R0 = Fq29::mul2w_np(q.y, p.zzz, p.y, Fq29::neg_wide(q.zzz));    // S2 - S1 + 4 S1' p   < 1.21 p
+  if (Fq29::maybe_zero(P0, 2)) {
+    MSM_ISA_MARK("rare full_addition");
     if (Fq29::is_zero_exact(P0)) {
       if (Fq29::is_zero_exact(R0)) return pti_double(p);
       vanished = true;   // q == -p
       return pti_identity();
     }
   }
-  const fe29 P = pin_limbs(P0), R = pin_limbs(R0), U1 = pin_limbs(U1a), S1 = pin_limbs(S1a), ZZ1 = pin_limbs(p.zz),
+  MSM_ISA_MARK("resume full_addition");
+  const fe29 P = pin_limbs(P0), R = pin_limbs(R0), X1 = pin_limbs(p.x), Y1 = pin_limbs(p.y), ZZ1 = pin_limbs(p.zz),
              ZZ2 = pin_limbs(q.zz), ZZZ1 = pin_limbs(p.zzz), ZZZ2 = pin_limbs(q.zzz);
   const fe29 PP = Fq29::sqr_np(P);
   const fe29 PPP = Fq29::mul_np(P, PP);
-  const fe29 Q = Fq29::mul_np(U1, PP);
+  const fe29 V = Fq29::mul_np(ZZ2, PP);
+  const fe29 Tz = Fq29::mul_np(ZZZ2, PPP);
+  const fe29 Q = Fq29::mul_np(X1, V);
   const fe29 RR = Fq29::sqr_np(R);
   PtI r;
-  r.x = Fq29::norm(Fq29::sub<K8E31>(RR, Fq29::add(PPP, Fq29::add(Q, Q))));               // < 9.2 p
-  const fe29 T = Fq29::sub<K16E30>(Q, r.x);      // un-normalised, like -PPP (see pti_madd)   // < 17.1 p
-  r.y = Fq29::mul2_np(R, T, S1, Fq29::neg_wide(PPP));    // R*T - S1*PPP in one reduction      // < 1.2 p
-  r.zz = Fq29::mul_np(Fq29::mul_np(ZZ1, ZZ2), PP);
-  r.zzz = Fq29::mul_np(Fq29::mul_np(ZZZ1, ZZZ2), PPP);
+  r.x = Fq29::norm(Fq29::sub<K8E31>(RR, Fq29::add(PPP, Fq29::add(Q, Q))));               // < 9.01 p
+  const fe29 T = Fq29::sub<K16E30>(Q, r.x);      // un-normalised, like -Tz (see pti_madd)    // < 17.1 p
+  r.y = Fq29::mul2_np(R, T, Y1, Fq29::neg_wide(Tz));     // R*T - Y1*Tz in one reduction       // < 1.26 p
+  r.zz = Fq29::mul_np(ZZ1, V);
+  r.zzz = Fq29::mul_np(ZZZ1, Tz);
+  MSM_ISA_MARK("end full_addition");
   return r;
 }
 MSM_HD PtI pti_add_nz(const PtI& p, const PtI& q) {

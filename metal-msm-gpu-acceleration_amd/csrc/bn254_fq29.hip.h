@@ -149,11 +149,16 @@ struct Fq29 {
   }
 
   // Montgomery reduction of 17 column sums (columns of weight 2^(29k)) modulo p with radix 2^261.
+  // WIDE = true: quotient digits 0..7 keep all 32 bits of A[k] * INV (one v_and less each; A[k] + m p0 = 0 mod 2^29
+  // holds for the whole product), digit 8 keeps its mask.  The digits then add up to m or m + rho, so the result is
+  // the masked one or that + p (odds ~2^-26), still < s / rho + p (1 + 2^-26) with limbs 0..7 < 2^29; the Montgomery
+  // terms of a column grow by up to 7 p_j 2^29 per digit -- tools/fq29_bounds.py checks every wide use.
+  template <bool WIDE = false>
   MSM_HD static fe29 reduce_columns(uint64_t (&A)[17]) {
     uint64_t carry = 0;
     MSM_UNROLL for (int k = 0; k < 9; ++k) {
       A[k] += carry;
-      const uint32_t m = ((uint32_t)A[k] * INV) & MASK;
+      const uint32_t m = (WIDE && k < 8) ? (uint32_t)A[k] * INV : ((uint32_t)A[k] * INV) & MASK;
       MSM_UNROLL for (int j = 0; j < 9; ++j) A[k + j] += (uint64_t)m * p(j);
       carry = A[k] >> 29;
     }
@@ -179,7 +184,7 @@ struct Fq29 {
   // PIN = false (mul_np / mul2_np / sqr_np below): the caller has pinned the operands itself, ONCE per basic block
   // (pin_limbs on a value that is used again later costs a v_mov per limb: the empty asm's output is a new value, the
   // old one must survive beside it.  Pinning inside every multiplication cost the mixed addition 81 v_mov.)
-  template <bool PIN = true>
+  template <bool PIN = true, bool WIDE = false>
   MSM_HD static fe29 mul(const fe29& a_in, const fe29& b_in) {
     const fe29 a = PIN ? pin_limbs(a_in) : a_in, b = PIN ? pin_limbs(b_in) : b_in;
 #if defined(MSM_AMD_EXPERIMENTS) && defined(MSM_FQ29_FIPS)
@@ -198,13 +203,13 @@ struct Fq29 {
       }
       A[k] = s;
     }
-    return reduce_columns(A);
+    return reduce_columns<WIDE>(A);
   }
 
   // (a*b + c*d)*rho^-1 with ONE Montgomery reduction: 81 + 81 + 81 limb products instead of 2 x (81 + 81).
   // All four operands must be normalised (limbs <= 2^29 + 8) so that a column of 18 + 9 products stays
   // below 2^64.  Used for Y3 = R*T - Y1*PPP with d = -PPP.
-  template <bool PIN = true>
+  template <bool PIN = true, bool WIDE = false>
   MSM_HD static fe29 mul2(const fe29& a_in, const fe29& b_in, const fe29& c_in, const fe29& d_in) {
     const fe29 a = PIN ? pin_limbs(a_in) : a_in, b = PIN ? pin_limbs(b_in) : b_in, c = PIN ? pin_limbs(c_in) : c_in,
                d = PIN ? pin_limbs(d_in) : d_in;
@@ -227,11 +232,11 @@ struct Fq29 {
       }
       A[k] = s;
     }
-    return reduce_columns(A);
+    return reduce_columns<WIDE>(A);
   }
 
   // a*a*rho^-1: 45 + 81 limb products (cross products use the doubled operand).
-  template <bool PIN = true>
+  template <bool PIN = true, bool WIDE = false>
   MSM_HD static fe29 sqr(const fe29& a_in) {
     const fe29 a = PIN ? pin_limbs(a_in) : a_in;
 #if defined(MSM_AMD_EXPERIMENTS) && defined(MSM_FQ29_FIPS)
@@ -255,11 +260,17 @@ struct Fq29 {
       if ((k & 1) == 0) s += (uint64_t)a.l[k >> 1] * a.l[k >> 1];
       A[k] = s;
     }
-    return reduce_columns(A);
+    return reduce_columns<WIDE>(A);
   }
-  MSM_HD static fe29 mul_np(const fe29& a, const fe29& b) { return mul<false>(a, b); }
-  MSM_HD static fe29 sqr_np(const fe29& a) { return sqr<false>(a); }
+  // The point additions' forms: no pins, wide quotient digits (reduce_columns<true>).  mul2_np keeps the masked
+  // digits: with wide ones a column of the Y3 double product R*T - Y1*PPP (T un-normalised) could reach 2^65.
+  // mul2w_np: the double products whose operands leave room for wide digits (pti_add_nz's P and R).
+  MSM_HD static fe29 mul_np(const fe29& a, const fe29& b) { return mul<false, true>(a, b); }
+  MSM_HD static fe29 sqr_np(const fe29& a) { return sqr<false, true>(a); }
   MSM_HD static fe29 mul2_np(const fe29& a, const fe29& b, const fe29& c, const fe29& d) { return mul2<false>(a, b, c, d); }
+  MSM_HD static fe29 mul2w_np(const fe29& a, const fe29& b, const fe29& c, const fe29& d) {
+    return mul2<false, true>(a, b, c, d);
+  }
 
   // 256-bit little-endian integer -> 9 x 29-bit limbs (pure bit slicing, value unchanged).
   MSM_HD static fe29 unpack256(const u256& x) {

@@ -2838,7 +2838,8 @@ int msm_amd_test_op_host(int op, const uint32_t* a, const uint32_t* b, uint32_t*
 
 // Raw-limb test ops: the internal limbs pass through unchanged (no from_ext, no reversal, no normalisation).
 static bool test_op_raw_args(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
-  return a && b && out && count > 0 && count <= (1u << 24) && op >= 0 && op < kRawOpCount;
+  return a && b && out && count > 0 && count <= (1u << 24) && op >= 0 &&
+         (op < kRawOpCount || (op >= kRawWideFirst && op < kRawWideFirst + kRawWideCount));
 }
 
 int msm_amd_test_op_raw(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {

@@ -146,7 +146,8 @@ MSM_HD void run_test_op(int op, const u256* a, const u256* b, u256* out, uint32_
 // ---- raw-limb ops (msm_amd_test_op_raw / _host, MSM_AMD_RAW_*): the internal limbs go in and come out exactly as
 // given, so that a test can put operands at the edges of the bounds contract and see result limbs, not only values.
 // Record of element t: a, b = kRawInWords u32 from t * kRawInWords, out = kRawOutWords u32 from t * kRawOutWords.
-constexpr int kRawInWords = 36, kRawOutWords = 40, kRawOpCount = 20;
+// Ops 0..kRawOpCount-1, and kRawWideFirst.. (the wide-digit multiplication forms of the point additions).
+constexpr int kRawInWords = 36, kRawOutWords = 40, kRawOpCount = 20, kRawWideFirst = 32, kRawWideCount = 3;
 
 MSM_HD fe29 raw_fe(const uint32_t* w) {
   fe29 r;
@@ -236,6 +237,11 @@ MSM_HD void run_test_op_raw(int op, const uint32_t* a_all, const uint32_t* b_all
       break;
     case 18: raw_put_pt(r, pti_add(raw_pt(a), raw_pt(b))); break;   // PT_ADD: identities allowed; no vanished flag
     case 19: raw_put_pt(r, pti_double(raw_pt(a))); break;           // PT_DOUBLE
+    case 32: raw_put_fe(r, Fq29::mul_np(pin_limbs(a0), pin_limbs(b0))); break;   // FE_MUL_WIDE
+    case 33: raw_put_fe(r, Fq29::sqr_np(pin_limbs(a0))); break;                  // FE_SQR_WIDE
+    case 34:                                                                      // FE_MUL2_WIDE
+      raw_put_fe(r, Fq29::mul2w_np(pin_limbs(a0), pin_limbs(a1), pin_limbs(b0), pin_limbs(b1)));
+      break;
   }
   MSM_UNROLL for (int i = 0; i < kRawOutWords; ++i) out[i] = r[i];
 }

@@ -63,14 +63,20 @@ def canonical(name):          # an unpacked base coordinate: canonical limbs of 
     return Fe([MASK] * 8 + [P >> 232], 1.0, name)
 
 
-def _reduce(cols, what):
+# quotient digit maxima of reduce_columns: masked (29 bits) or wide (WIDE = true: digits 0..7 keep 32 bits, digit 8 its
+# mask; the result may then be the masked one + p, i.e. up to p (1 + 2^-26) above s / rho)
+DIGIT_MAX = {False: [MASK] * 9, True: [(1 << 32) - 1] * 8 + [MASK]}
+WIDE_EXTRA = 2.0 ** -26 * 1.01
+
+
+def _reduce(cols, what, wide=False):
     """Montgomery reduction of worst-case column sums; returns the worst-case top limb (final carry)."""
     A = list(cols) + [0] * (17 - len(cols))
     carry = 0
     for k in range(9):
         A[k] += carry
         for j in range(9):
-            A[k + j] += MASK * PL[j]
+            A[k + j] += DIGIT_MAX[wide][k] * PL[j]
         if A[k] >= 1 << 64:
             fail(f"{what}: column {k} can reach 2^{A[k].bit_length()} during the reduction")
         carry = A[k] >> 29
@@ -91,29 +97,30 @@ def _mul_cols(pairs):
     return cols
 
 
-def _out(pairs, name, what):
+def _out(pairs, name, what, wide=False):
     for a, b in pairs:
         for f in (a, b):
             if max(f.mx) >= 1 << 32:
                 fail(f"{what}: operand {f.name} has a limb beyond 32 bits")
-    carry = _reduce(_mul_cols(pairs), what)
-    val = sum(a.val * b.val for a, b in pairs) * P / RHO + 1.0
+    carry = _reduce(_mul_cols(pairs), what + (" (wide digits)" if wide else ""), wide)
+    val = sum(a.val * b.val for a, b in pairs) * P / RHO + 1.0 + (WIDE_EXTRA if wide else 0.0)
     top = min(carry, top_from_value(val))
     return Fe([MASK] * 8 + [top], val, name)
 
 
-def mul(a, b, name):
-    return _out([(a, b)], name, f"mul {name} = {a.name} * {b.name}")
+# wide=True: the forms with wide quotient digits (Fq29::mul_np, sqr_np, mul2w_np; mul2_np is masked)
+def mul(a, b, name, wide=False):
+    return _out([(a, b)], name, f"mul {name} = {a.name} * {b.name}", wide)
 
 
-def mul2(a, b, c, d, name):
-    return _out([(a, b), (c, d)], name, f"mul2 {name} = {a.name}*{b.name} + {c.name}*{d.name}")
+def mul2(a, b, c, d, name, wide=False):
+    return _out([(a, b), (c, d)], name, f"mul2 {name} = {a.name}*{b.name} + {c.name}*{d.name}", wide)
 
 
-def sqr(a, name):
+def sqr(a, name, wide=False):
     if max(a.mx) * 2 >= 1 << 32:
         fail(f"sqr {name}: doubled limb of {a.name} leaves 32 bits")
-    return _out([(a, a)], name, f"sqr {name} = {a.name}^2")
+    return _out([(a, a)], name, f"sqr {name} = {a.name}^2", wide)
 
 
 def add(a, b, name=None):
@@ -180,6 +187,7 @@ def point_invariant():
 
 
 # ---- the formulas of bn254_ec29.hip.h ----------------------------------------------------------------------
+WD = True   # the point additions' products use wide quotient digits where the header's _np forms do
 def pti_double(px, py, pzz, pzzz, where):
     U = add(py, py, "U")
     V = sqr(U, "V")
@@ -214,20 +222,20 @@ def stored_base_y(qy, name="+-y1"):
 def pti_madd(where="pti_madd"):
     px, py, pzz, pzzz = point_invariant()
     qx, qy = canonical("x2"), negated_base_y(canonical("y2"))
-    U2 = mul(qx, pzz, "U2")
-    S2 = mul(qy, pzzz, "S2")
+    U2 = mul(qx, pzz, "U2", WD)
+    S2 = mul(qy, pzzz, "S2", WD)
     Pd = norm(sub("K16E30", U2, px, "P"), "P")
     R = norm(sub("K8E30", S2, py, "R"), "R")
     maybe_zero(Pd, 18)
-    PP = sqr(Pd, "PP")
-    PPP = mul(Pd, PP, "PPP")
-    Q = mul(px, PP, "Q")
-    RR = sqr(R, "RR")
+    PP = sqr(Pd, "PP", WD)
+    PPP = mul(Pd, PP, "PPP", WD)
+    Q = mul(px, PP, "Q", WD)
+    RR = sqr(R, "RR", WD)
     X3 = norm(sub("K8E31", RR, add(PPP, add(Q, Q)), "X3"), "X3")
     T = sub("K16E30", Q, X3, "T")                            # un-normalised: its partner R is normalised
-    Y3 = mul2(R, T, py, neg_wide(PPP, "-PPP"), "Y3")
-    ZZ3 = mul(pzz, PP, "ZZ3")
-    ZZZ3 = mul(pzzz, PPP, "ZZZ3")
+    Y3 = mul2(R, T, py, neg_wide(PPP, "-PPP"), "Y3")          # mul2_np: masked digits
+    ZZ3 = mul(pzz, PP, "ZZ3", WD)
+    ZZZ3 = mul(pzzz, PPP, "ZZZ3", WD)
     check_point(X3, Y3, ZZ3, ZZZ3, where)
     one = Fe([MASK] * 8 + [P >> 232], 1.0, "one")           # the doubling path restarts from pti_from_affi(q)
     pti_double(qx, stored_base_y(canonical("y2")), one, one, where)
@@ -240,10 +248,10 @@ def pti_mmadd(where="pti_mmadd"):
     Pd = norm(sub("K16E30", qx, px, "P"), "P")
     R = norm(sub("K8E30", qy, py, "R"), "R")
     maybe_zero(Pd, 18)
-    PP = sqr(Pd, "PP")
-    PPP = mul(Pd, PP, "PPP")
-    Q = mul(px, PP, "Q")
-    RR = sqr(R, "RR")
+    PP = sqr(Pd, "PP", WD)
+    PPP = mul(Pd, PP, "PPP", WD)
+    Q = mul(px, PP, "Q", WD)
+    RR = sqr(R, "RR", WD)
     X3 = norm(sub("K8E31", RR, add(PPP, add(Q, Q)), "X3"), "X3")
     T = norm(sub("K16E30", Q, X3, "T"), "T")
     Y3 = mul2(R, T, py, neg_wide(PPP, "-PPP"), "Y3")
@@ -253,26 +261,26 @@ def pti_mmadd(where="pti_mmadd"):
 
 
 def pti_add_nz(where="pti_add_nz"):
+    """add-2008-s in 11 reductions: P and R as double products with the subtrahend negated (neg_wide), V = ZZ2 PP and
+    Tz = ZZZ2 PPP shared by Q / ZZ3 and Y3 / ZZZ3"""
     px, py, pzz, pzzz = point_invariant()
     qx, qy, qzz, qzzz = point_invariant()
     for f, n in ((qx, "X2"), (qy, "Y2"), (qzz, "ZZ2"), (qzzz, "ZZZ2")):
         f.name = n
-    U1 = mul(px, qzz, "U1")
-    U2 = mul(qx, pzz, "U2")
-    S1 = mul(py, qzzz, "S1")
-    S2 = mul(qy, pzzz, "S2")
-    Pd = norm(sub("K4E30", U2, U1, "P"), "P")
-    R = norm(sub("K4E30", S2, S1, "R"), "R")
-    maybe_zero(Pd, 6)
-    PP = sqr(Pd, "PP")
-    PPP = mul(Pd, PP, "PPP")
-    Q = mul(U1, PP, "Q")
-    RR = sqr(R, "RR")
+    Pd = mul2(qx, pzz, px, neg_wide(qzz, "-ZZ2"), "P", WD)
+    R = mul2(qy, pzzz, py, neg_wide(qzzz, "-ZZZ2"), "R", WD)
+    maybe_zero(Pd, 2)
+    PP = sqr(Pd, "PP", WD)
+    PPP = mul(Pd, PP, "PPP", WD)
+    V = mul(qzz, PP, "V", WD)
+    Tz = mul(qzzz, PPP, "Tz", WD)
+    Q = mul(px, V, "Q", WD)
+    RR = sqr(R, "RR", WD)
     X3 = norm(sub("K8E31", RR, add(PPP, add(Q, Q)), "X3"), "X3")
     T = sub("K16E30", Q, X3, "T")
-    Y3 = mul2(R, T, S1, neg_wide(PPP, "-PPP"), "Y3")
-    ZZ3 = mul(mul(pzz, qzz, "ZZ12"), PP, "ZZ3")
-    ZZZ3 = mul(mul(pzzz, qzzz, "ZZZ12"), PPP, "ZZZ3")
+    Y3 = mul2(R, T, py, neg_wide(Tz, "-Tz"), "Y3")            # mul2_np: masked digits
+    ZZ3 = mul(pzz, V, "ZZ3", WD)
+    ZZZ3 = mul(pzzz, Tz, "ZZZ3", WD)
     check_point(X3, Y3, ZZ3, ZZZ3, where)
     pti_double(px, py, pzz, pzzz, where)
 

@@ -1,4 +1,4 @@
-"""Instruction counts of the shipped accumulate kernel, taken from the compiler's own assembly.
+"""Instruction counts of the shipped accumulate kernel (and of the full addition), taken from the compiler's own assembly.
 
 `make -C metal-msm-gpu-acceleration_amd/csrc isa-counts` (part of `all`) compiles k_accumulate.hip once more with
 `--cuda-device-only -S` (same flags as the object that goes into libmsm_amd.so) and runs this script on the result.
@@ -17,7 +17,10 @@ whatever multiplication the compiler hoisted above the path split (it speculates
 for every lane; those regions sit between the loop header and the first mark).  The script fails loudly if the
 totals do not look like 8M + 2S / 4M + 2S on 9 x 29-bit limbs.
 
-Usage: python tools/isa_counts.py k_accumulate.s out.json
+The full addition (pti_add_nz, add-2008-s 12M + 2S in 11 reductions) is counted the same way in sum_groups_kernel
+(k_reduce.hip, the second assembly file): marks "begin / rare / resume / end full_addition" inside pti_add_nz.
+
+Usage: python tools/isa_counts.py k_accumulate.s out.json [k_reduce.s]
 """
 import collections
 import json
@@ -152,7 +155,21 @@ def summarise(c):
                                      key=lambda kv: -kv[1])[:14])}
 
 
-def main(src, dst):
+def full_addition(src):
+    """Counts of pti_add_nz inside sum_groups_kernel's loop (the exceptional block excluded)."""
+    for name, body in functions(open(src).read().splitlines()):
+        if "sum_groups_kernel" not in name:
+            continue
+        pc = tally(body)
+        fa = summarise(pc["full_addition"])
+        # 12M + 2S in 11 reductions: 8 x 171 + 2 x 135 + 3 x 252 + 11 = ~2045 (minus what the compiler folds)
+        if not 1900 <= fa["multiplier"] <= 2400:
+            raise SystemExit(f"{name}: full addition counts {fa['multiplier']} multiplier instructions, expected ~2050")
+        return {"symbol": name, "full_addition": fa}
+    raise SystemExit("sum_groups_kernel not found")
+
+
+def main(src, dst, reduce_src=None):
     lines = open(src).read().splitlines()
     out = {"source": "compiler assembly of k_accumulate.hip (hipcc --cuda-device-only -S, flags of the shipped object)",
            "multiplier_instructions": list(MULT), "kernels": {}}
@@ -195,10 +212,16 @@ def main(src, dst):
     out["multiplier_per_affine_start"] = k["affine_start"]["multiplier"]
     out["valu_per_mixed_addition"] = k["mixed_addition"]["valu"]
     out["valu_per_affine_start"] = k["affine_start"]["valu"]
+    if reduce_src:
+        out["sum_groups_kernel"] = full_addition(reduce_src)
+        out["multiplier_per_full_addition"] = out["sum_groups_kernel"]["full_addition"]["multiplier"]
+        out["valu_per_full_addition"] = out["sum_groups_kernel"]["full_addition"]["valu"]
     json.dump(out, open(dst, "w"), indent=1)
     print(f"isa_counts: mixed addition {k['mixed_addition']['multiplier']} multiplier / {k['mixed_addition']['valu']} VALU "
-          f"instructions, affine start {k['affine_start']['multiplier']} / {k['affine_start']['valu']} -> {dst}")
+          f"instructions, affine start {k['affine_start']['multiplier']} / {k['affine_start']['valu']}"
+          + (f", full addition {out['multiplier_per_full_addition']} / {out['valu_per_full_addition']}" if reduce_src else "")
+          + f" -> {dst}")
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2])
+    main(sys.argv[1], sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else None)
