@@ -537,6 +537,51 @@ int msm_amd_test_stage_copy(msm_amd_ctx* ctx, uint32_t j, int which, void* out, 
  * byte over their whole capacity.  Index and count buffers are never touched. */
 int msm_amd_test_fill_workspaces(msm_amd_ctx* ctx, uint8_t byte);
 
+/* ---- BN254 G2 MSM ------------------------------------------------------------------------------ */
+/* G2 is the twist y^2 = x^3 + 3 / (9 + u) over Fq2 = Fq[u] / (u^2 + 1); an Fq2 element is c0 then c1, each 32 B
+ * Montgomery LE (R = 2^256).  Scalars use the MSM_AMD_SCALAR_* layouts above; inputs are taken as points of the
+ * r-torsion subgroup (no subgroup check).  The result is 192 B Jacobian, Montgomery LE (x.c0, x.c1, y.c0, y.c1, z.c0,
+ * z.c1), normalised to z = (R mod p, 0); the identity is ((R, 0), (R, 0), (0, 0)). */
+enum {
+  MSM_AMD_G2_POINT_H2C_AFFINE = 0, /* halo2curves bn256::G2Affine {x, y}: 128 B, identity = all zero */
+  MSM_AMD_G2_POINT_ARK_AFFINE = 1  /* ark_bn254::G2Affine {x, y, infinity: bool}: 136 B, flag at byte 128 */
+};
+/* Bytes per point of a G2 layout, 0 for an unknown layout. */
+size_t msm_amd_g2_point_bytes(int g2_point_layout);
+/* One blocking G2 MSM on the GPU, host buffers (n scalars of 32 B, n points of msm_amd_g2_point_bytes).  Unknown
+ * layouts, or a null pointer with n > 0, return MSM_AMD_INPUT_ERROR.  No CPU fallback.  The window is
+ * msm_amd_auto_window_size_lone(n) unless msm_amd_set_window_size forced one; msm_amd_last_timings reports the
+ * stages (convert_ms: scalar and base conversion, accumulate_ms: accumulation + combine, reduce_ms: window reduction
+ * and the copy of its partial points). */
+int msm_amd_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points,
+                   size_t n, void* out192);
+/* The same with scalars and points in device memory on ctx's device. */
+int msm_amd_msm_g2_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars,
+                          const void* d_points, size_t n, void* out192);
+/* The CPU G2 MSM of the library (no ctx, no GPU): windowed bucket method on 4 x 64-bit limbs; threads <= 0: up to 16
+ * host threads.  Same layouts and result form as msm_amd_msm_g2. */
+int msm_amd_host_msm_g2(int scalar_layout, int g2_point_layout, const void* scalars, const void* points, size_t n,
+                        int threads, void* out192);
+/* Test aid: out[i] = start + i * step for i < n, MSM_AMD_G2_POINT_H2C_AFFINE records (host code, threads <= 0: up to
+ * 16 host threads). */
+int msm_amd_test_g2_progression(const void* start128, const void* step128, size_t n, int threads, void* out);
+/* Raw-limb G2 test ops: operands of MSM_AMD_G2_RAW_IN_WORDS u32, results of MSM_AMD_G2_RAW_OUT_WORDS u32.
+ * fq2 = 18 words (c0 limbs 0..8, c1 limbs 0..8, 29-bit internal limbs); affine = x, y (36 words);
+ * XYZZ point = X, Y, ZZ, ZZZ (72 words).  Result: the fq2 or point from word 0, word 72 = 1 if the sum vanished. */
+enum { MSM_AMD_G2_RAW_IN_WORDS = 72, MSM_AMD_G2_RAW_OUT_WORDS = 80 };
+enum {
+  MSM_AMD_G2_RAW_FQ2_MUL = 0,    /* a * b */
+  MSM_AMD_G2_RAW_FQ2_SQR = 1,    /* a^2 */
+  MSM_AMD_G2_RAW_PT_MADD = 2,    /* XYZZ a + affine b (madd-2008-s), neither the identity */
+  MSM_AMD_G2_RAW_PT_MMADD = 3,   /* affine a + affine b, neither the identity */
+  MSM_AMD_G2_RAW_PT_ADD_NZ = 4,  /* XYZZ a + XYZZ b, neither the identity (add-2008-s) */
+  MSM_AMD_G2_RAW_PT_ADD = 5,     /* XYZZ a + XYZZ b, identities allowed */
+  MSM_AMD_G2_RAW_PT_DOUBLE = 6   /* 2 a, a not the identity */
+};
+int msm_amd_test_op_g2(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count);
+/* The same bodies on the host CPU (no GPU needed). */
+int msm_amd_test_op_g2_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 int msm_amd_last_timings(const msm_amd_ctx* ctx, msm_amd_timings* out);
 /* Algorithmic HBM bytes of one MSM: whole pipeline and accumulation only. */

@@ -32,6 +32,12 @@ POINT_BYTES = {POINT_H2C_AFFINE: 64, POINT_ARK_PROJECTIVE: 96, POINT_ARK_AFFINE:
  RAW_FE_ZERO, RAW_PT_MADD, RAW_PT_MMADD, RAW_PT_ADD_NZ, RAW_PT_ADD, RAW_PT_DOUBLE) = range(20)
 RAW_FE_MUL_WIDE, RAW_FE_SQR_WIDE, RAW_FE_MUL2_WIDE = range(32, 35)   # the point additions' wide-digit forms
 RAW_IN_WORDS, RAW_OUT_WORDS = 36, 40
+# BN254 G2 (MSM_AMD_G2_*): point layouts, raw-limb test ops and their record widths
+G2_POINT_H2C_AFFINE, G2_POINT_ARK_AFFINE = 0, 1
+G2_POINT_BYTES = {G2_POINT_H2C_AFFINE: 128, G2_POINT_ARK_AFFINE: 136}
+(G2_RAW_FQ2_MUL, G2_RAW_FQ2_SQR, G2_RAW_PT_MADD, G2_RAW_PT_MMADD, G2_RAW_PT_ADD_NZ, G2_RAW_PT_ADD,
+ G2_RAW_PT_DOUBLE) = range(7)
+G2_RAW_IN_WORDS, G2_RAW_OUT_WORDS = 72, 80
 
 
 def op_is_point(op):
@@ -65,6 +71,8 @@ EXPORTS = [
     "msm_amd_gather_size", "msm_amd_gather_all", "msm_amd_gather_last_error", "msm_amd_gather_destroy",
     "msm_amd_host_msm", "msm_amd_tuned_split", "msm_amd_host_threads", "msm_amd_generate_instance_host", "msm_amd_test_op_ifma",
     "msm_amd_test_last_plan", "msm_amd_test_stage_copy", "msm_amd_test_fill_workspaces",
+    "msm_amd_g2_point_bytes", "msm_amd_msm_g2", "msm_amd_msm_g2_device", "msm_amd_host_msm_g2",
+    "msm_amd_test_g2_progression", "msm_amd_test_op_g2", "msm_amd_test_op_g2_host",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -220,6 +228,14 @@ def _lib():
         L.msm_amd_gather_destroy.argtypes = [c_void_p]
         L.msm_amd_gather_destroy.restype = None
         L.msm_amd_host_msm.argtypes = [c_int, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+        L.msm_amd_g2_point_bytes.argtypes = [c_int]
+        L.msm_amd_g2_point_bytes.restype = c_size_t
+        L.msm_amd_msm_g2.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+        L.msm_amd_msm_g2_device.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+        L.msm_amd_host_msm_g2.argtypes = [c_int, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+        L.msm_amd_test_g2_progression.argtypes = [c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+        L.msm_amd_test_op_g2.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t]
+        L.msm_amd_test_op_g2_host.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_generate_instance_host.argtypes = [c_uint64, c_size_t, c_int, c_void_p, c_void_p, c_int]
         L.msm_amd_test_op_ifma.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_tuned_split.argtypes = [c_size_t]
@@ -502,6 +518,29 @@ class MsmConfig:
         return list(out)
 
 
+    # ---- BN254 G2 --------------------------------------------------------------------------------
+    def msm_g2(self, scalars: bytes, points: bytes, n: int, scalar_layout=SCALAR_MONT_LE,
+               point_layout=G2_POINT_H2C_AFFINE) -> bytes:
+        """One blocking G2 MSM on the GPU from host buffers: 192-byte normalised Jacobian (Montgomery LE)."""
+        out = ctypes.create_string_buffer(192)
+        self._check(_lib().msm_amd_msm_g2(self.h, scalar_layout, point_layout, scalars, points, n, out))
+        return out.raw
+
+    def msm_g2_device(self, d_scalars, d_points, n: int, scalar_layout=SCALAR_MONT_LE,
+                      point_layout=G2_POINT_H2C_AFFINE) -> bytes:
+        """msm_g2 with scalars and points already in device memory (pointers from alloc / to_device)."""
+        out = ctypes.create_string_buffer(192)
+        self._check(_lib().msm_amd_msm_g2_device(self.h, scalar_layout, point_layout, d_scalars, d_points, n, out))
+        return out.raw
+
+    def test_op_g2(self, op, a, b, count):
+        """Raw-limb G2 op (MSM_AMD_G2_RAW_*) on the device: a, b flat u32 lists of count * G2_RAW_IN_WORDS; returns
+        count * G2_RAW_OUT_WORDS u32."""
+        out = (c_uint32 * (count * G2_RAW_OUT_WORDS))()
+        self._check(_lib().msm_amd_test_op_g2(self.h, op, _g2_raw_in(a, count), _g2_raw_in(b, count), out, count))
+        return list(out)
+
+
 def msm_batch_multi(configs, scalars_list, points_list, ns, scalar_layout=SCALAR_MONT_LE,
                     point_layout=POINT_H2C_AFFINE, device=False):
     """The instance loop sharded over several configs (gpu_profiler.rs:101-106): instance j -> configs[j mod G], one
@@ -646,6 +685,44 @@ def test_op_raw_host(op, a, b, count):
     """Same raw-limb op bodies as MsmConfig.test_op_raw, executed on the host CPU by the library (no GPU)."""
     out = (c_uint32 * (count * RAW_OUT_WORDS))()
     st = _lib().msm_amd_test_op_raw_host(op, _raw_in(a, count), _raw_in(b, count), out, count)
+    if st != OK:
+        raise MsmError(st)
+    return list(out)
+
+
+def g2_point_bytes(layout) -> int:
+    return _lib().msm_amd_g2_point_bytes(layout)
+
+
+def host_msm_g2(scalars: bytes, points: bytes, n: int, threads=0, scalar_layout=SCALAR_MONT_LE,
+                point_layout=G2_POINT_H2C_AFFINE) -> bytes:
+    """The product's CPU G2 MSM (no GPU): 192-byte normalised Jacobian, the form msm_g2 returns."""
+    out = ctypes.create_string_buffer(192)
+    st = _lib().msm_amd_host_msm_g2(scalar_layout, point_layout, scalars, points, n, threads, out)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw
+
+
+def g2_progression(start: bytes, step: bytes, n: int, threads=0) -> bytes:
+    """n G2 points start + i * step (halo2curves G2Affine records, 128 B each), generated on the host by the library."""
+    out = ctypes.create_string_buffer(128 * n)
+    st = _lib().msm_amd_test_g2_progression(start, step, n, threads, out)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw
+
+
+def _g2_raw_in(seq, count):
+    if len(seq) != count * G2_RAW_IN_WORDS:
+        raise ValueError(f"a raw-limb G2 operand holds {G2_RAW_IN_WORDS} words per element")
+    return _u32buf(seq)
+
+
+def test_op_g2_host(op, a, b, count):
+    """Same raw-limb G2 op bodies as MsmConfig.test_op_g2, executed on the host CPU by the library (no GPU)."""
+    out = (c_uint32 * (count * G2_RAW_OUT_WORDS))()
+    st = _lib().msm_amd_test_op_g2_host(op, _g2_raw_in(a, count), _g2_raw_in(b, count), out, count)
     if st != OK:
         raise MsmError(st)
     return list(out)

@@ -25,8 +25,10 @@
 #include "../../include/msm_amd.h"
 #include "device_common.hip.h"
 #include "launch.h"
+#include "launch_g2.h"
 #include "host_fq64.h"
 #include "test_ops.hip.h"
+#include "test_ops_g2.hip.h"
 
 using namespace msm_amd;
 
@@ -164,6 +166,19 @@ struct msm_amd_tables {
   void* d_tables = nullptr;   // W * n AffPacked
 };
 
+// Buffers of the G2 MSM (msm_amd_msm_g2*): one blocking call at a time on the main stream.  `ws` holds the scalar
+// front end's buffers (digits, sort, work items, scalar conversion) -- its own, so a G2 call never touches what a G1
+// instance of the same ctx may still be using; the point-valued buffers are G2-sized.
+struct G2State {
+  enum { EV_G2_START = 0, EV_G2_CONVERT, EV_G2_DIGITS, EV_G2_SORT, EV_G2_ACC, EV_G2_REDUCE, EV_G2_COUNT };
+  Workspace ws;
+  DeviceBuf bases, buckets, item_partials, S, T, partial, in_scalars, in_points;
+  Jacobian2* h_partial = nullptr;   // pinned
+  size_t h_partial_cap = 0;
+  hipEvent_t ev[EV_G2_COUNT] = {};
+  bool has_events = false;
+};
+
 struct msm_amd_ctx {
   int device = 0;
   hipStream_t stream = nullptr;          // main stream: conversion, digits, sort, accumulate; stage entry points
@@ -185,6 +200,7 @@ struct msm_amd_ctx {
   bool overlap_front = true;             // MSM_AMD_OVERLAP_FRONT=0 puts the front end on the main stream
   bool lone_single_stream = true;        // MSM_AMD_LONE_SINGLE_STREAM=0: a lone instance uses the stream split too
   Workspace ws[kWorkspaces];
+  G2State g2;
   std::mutex mu;
   std::string last_error;
   uint32_t forced_window = 0;
@@ -1908,6 +1924,8 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
     kill_event(ctx->ws[k].acc_done);
     kill_event(ctx->ws[k].reduce_done);
   }
+  for (hipEvent_t& e : ctx->g2.ev) kill_event(e);
+  ctx->g2.has_events = false;
   for (hipEvent_t& e : ctx->uploaded) kill_event(e);
   kill_event(ctx->upload_done);
   kill_event(ctx->after_sort_mark);
@@ -1921,6 +1939,18 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
                          &w.sorted, &w.order, &w.multi_list, &w.redo_list, &w.counters, &w.bases29, &w.buckets, &w.item_partials,
                          &w.S, &w.T, &w.partial, &w.conv_scalars, &w.conv_points, &w.conv_tmp};
     for (DeviceBuf* b : bufs) kill_buf(*b);
+  }
+  {
+    G2State& g = ctx->g2;
+    Workspace& w = g.ws;
+    DeviceBuf* bufs[] = {&w.digits, &w.coarse_cnt, &w.region_start, &w.tmp_idx, &w.tmp_fine, &w.tmp_idx2, &w.tmp_fine2,
+                         &w.mid_cnt, &w.region_start2, &w.bsize, &w.bstart, &w.istart, &w.win_items, &w.size_bins,
+                         &w.sorted, &w.order, &w.multi_list, &w.counters, &w.conv_scalars, &g.bases, &g.buckets,
+                         &g.item_partials, &g.S, &g.T, &g.partial, &g.in_scalars, &g.in_points};
+    for (DeviceBuf* b : bufs) kill_buf(*b);
+    if (g.h_partial) (void)hipHostFree(g.h_partial);
+    g.h_partial = nullptr;
+    g.h_partial_cap = 0;
   }
   for (msm_amd_tables* t : ctx->live_tables) {   // tables the caller did not free
     (void)hipFree(t->d_tables);
@@ -3042,6 +3072,222 @@ uint64_t msm_amd_algorithmic_bytes(size_t n, uint32_t window_size, int accumulat
   const uint64_t totB = W * ((1ull << c) - 1);
   if (accumulate_only) return 72ull * n * W + 96ull * totB;
   return 32ull * n + 72ull * n * W + 2ull * 96ull * totB;
+}
+
+}  // extern "C"
+
+// ---- BN254 G2 MSM (one blocking call on the main stream) -----------------------------------------------------------
+namespace {
+
+// The whole G2 MSM of device-resident inputs: scalar conversion, digits and sort exactly as enqueue_msm does them (into
+// the G2 state's own front-end buffers), then the G2 kernels, the copy of the partial points, a bounded wait and the
+// host Horner pass.  ctx->mu held by the caller.
+int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars, const void* d_points,
+               size_t n, void* out192) {
+  if (n > 0x7FFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, "n >= 2^31");
+  if (int rc = recover_if_stalled(ctx)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  G2State& g = ctx->g2;
+  Workspace& w = g.ws;
+  hipStream_t st = ctx->stream;
+  const uint32_t c = ctx->forced_window ? ctx->forced_window : auto_window_lone(n);
+  Plan p = make_plan(n, c);
+  p.red_group = pick_reduce_group(p);
+  p.rb_threads = 0;
+  int rc;
+  if (!g.has_events) {
+    for (hipEvent_t& e : g.ev) HIP_TRY(ctx, hipEventCreate(&e));
+    g.has_events = true;
+  }
+  if (p.partial_count > g.h_partial_cap) {
+    if ((rc = quiesce_for_allocation(ctx, "the page-locked G2 result slot"))) return rc;
+    if (g.h_partial) HIP_TRY(ctx, hipHostFree(g.h_partial));
+    g.h_partial = nullptr;
+    g.h_partial_cap = 0;
+    HIP_TRY(ctx, hipHostMalloc((void**)&g.h_partial, p.partial_count * sizeof(Jacobian2), hipHostMallocDefault));
+    g.h_partial_cap = p.partial_count;
+  }
+  if ((rc = ensure(ctx, w.digits, (size_t)p.W * n * (p.wide_digits ? sizeof(uint32_t) : sizeof(uint16_t))))) return rc;
+  if ((rc = ensure(ctx, w.coarse_cnt, (size_t)p.W * p.Q * (1u << p.hb) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.region_start, (size_t)p.W * ((1u << p.hb) + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.tmp_idx, (size_t)p.W * n * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.tmp_fine, (size_t)p.W * n * sizeof(uint16_t)))) return rc;
+  if (p.mb) {
+    if ((rc = ensure(ctx, w.tmp_idx2, (size_t)p.W * n * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(ctx, w.tmp_fine2, (size_t)p.W * n * sizeof(uint16_t)))) return rc;
+    if ((rc = ensure(ctx, w.mid_cnt, ((size_t)p.W << p.hb) * p.Q2 * (1u << p.mb) * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(ctx, w.region_start2, (size_t)p.W * ((1u << (p.hb + p.mb)) + 1) * sizeof(uint32_t)))) return rc;
+  }
+  if ((rc = ensure(ctx, w.bsize, p.total_buckets * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.bstart, p.total_buckets * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.istart, p.total_buckets * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.win_items, (1024 + 2 * 1024) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.size_bins, (size_t)(p.CH + 1) * ((p.total_buckets + p.front_threads - 1) / p.front_threads) *
+                                         sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.sorted, (size_t)p.W * n * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.order, p.max_items * sizeof(uint2)))) return rc;
+  if ((rc = ensure(ctx, w.multi_list, p.max_items * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.counters, sizeof(PlanCounters)))) return rc;
+  if ((rc = ensure(ctx, g.bases, n * sizeof(Aff2Packed)))) return rc;
+  if ((rc = ensure(ctx, g.buckets, p.total_buckets * sizeof(PtI2)))) return rc;
+  if ((rc = ensure(ctx, g.item_partials, p.max_items * sizeof(PtI2)))) return rc;
+  if ((rc = ensure(ctx, g.S, p.total_segs * sizeof(PtI2)))) return rc;
+  if ((rc = ensure(ctx, g.T, p.total_segs * sizeof(PtI2)))) return rc;
+  if ((rc = ensure(ctx, g.partial, p.partial_count * sizeof(Jacobian2)))) return rc;
+  SortBuffers sb{};
+  sb.digits = w.digits.p;
+  sb.coarse_cnt = (uint32_t*)w.coarse_cnt.p;
+  sb.region_start = (uint32_t*)w.region_start.p;
+  sb.tmp_idx = (uint32_t*)w.tmp_idx.p;
+  sb.tmp_fine = (uint16_t*)w.tmp_fine.p;
+  sb.tmp_idx2 = (uint32_t*)w.tmp_idx2.p;
+  sb.tmp_fine2 = (uint16_t*)w.tmp_fine2.p;
+  sb.mid_cnt = (uint32_t*)w.mid_cnt.p;
+  sb.region_start2 = (uint32_t*)w.region_start2.p;
+  sb.bucket_size = (uint32_t*)w.bsize.p;
+  sb.bucket_start = (uint32_t*)w.bstart.p;
+  sb.item_start = (uint32_t*)w.istart.p;
+  sb.win_items = (uint32_t*)w.win_items.p;
+  sb.tile_sums = (uint2*)((uint32_t*)w.win_items.p + 1024);
+  sb.size_bins = (uint32_t*)w.size_bins.p;
+  sb.sorted = (uint32_t*)w.sorted.p;
+  sb.order = (uint2*)w.order.p;
+  sb.multi_list = (uint32_t*)w.multi_list.p;
+  sb.redo_list = nullptr;
+  sb.counters = (PlanCounters*)w.counters.p;
+
+  HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_START], st));
+  const u256* sc = nullptr;
+  const Affine* unused = nullptr;
+  int sc_mont = 0;
+  if ((rc = convert_inputs(ctx, w, st, scalar_layout, MSM_AMD_POINT_PREPARED, d_scalars, nullptr, n, &sc, &sc_mont,
+                           &unused)))
+    return rc;
+  launch_convert_bases_g2(st, d_points, g2_point_layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n,
+                          (Aff2Packed*)g.bases.p);
+  HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_CONVERT], st));
+  launch_digits(st, p, sc, sc_mont, sb.digits);
+  HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_DIGITS], st));
+  launch_sort(st, p, sb);
+  HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_SORT], st));
+  // the bucket matrix is not cleared: the window reduction reads bucket_size (see enqueue_msm)
+  launch_accumulate_g2(st, p, (const Aff2Packed*)g.bases.p, sb, (PtI2*)g.buckets.p, (PtI2*)g.item_partials.p);
+  launch_combine_g2(st, p, sb, (PtI2*)g.buckets.p, (PtI2*)g.item_partials.p);
+  HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_ACC], st));
+  launch_reduce_g2(st, p, (const PtI2*)g.buckets.p, (const uint32_t*)w.bsize.p, (PtI2*)g.S.p, (PtI2*)g.T.p,
+                   (Jacobian2*)g.partial.p);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(g.h_partial, g.partial.p, p.partial_count * sizeof(Jacobian2), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_REDUCE], st));
+  const hipError_t we = wait_event(g.ev[G2State::EV_G2_REDUCE], ctx->wait_timeout_ms);
+  if (we == hipErrorNotReady) {
+    ctx->stalled = true;
+    return fail(ctx, MSM_AMD_PIPELINE_ERROR,
+                "timed out after " + std::to_string(ctx->wait_timeout_ms) + " ms waiting for the G2 MSM");
+  }
+  if (we != hipSuccess) return fail(ctx, MSM_AMD_PIPELINE_ERROR, std::string("G2 MSM: ") + hipGetErrorString(we));
+  const auto t0 = std::chrono::steady_clock::now();
+  const Jacobian2 res = host_combine_g2(g.h_partial, p);
+  const float final_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  std::memcpy(out192, &res, 192);
+  auto span = [&](int a, int b) {
+    float t = 0;
+    if (hipEventElapsedTime(&t, g.ev[a], g.ev[b]) != hipSuccess) {
+      (void)hipGetLastError();
+      t = 0;
+    }
+    return t;
+  };
+  msm_amd_timings& T = ctx->timings;
+  T = msm_amd_timings{};
+  T.convert_ms = span(G2State::EV_G2_START, G2State::EV_G2_CONVERT);
+  T.digits_ms = span(G2State::EV_G2_CONVERT, G2State::EV_G2_DIGITS);
+  T.sort_ms = span(G2State::EV_G2_DIGITS, G2State::EV_G2_SORT);
+  T.accumulate_ms = span(G2State::EV_G2_SORT, G2State::EV_G2_ACC);
+  T.accumulate_kernel_ms = T.accumulate_ms;
+  T.reduce_ms = span(G2State::EV_G2_ACC, G2State::EV_G2_REDUCE);
+  T.total_gpu_ms = span(G2State::EV_G2_START, G2State::EV_G2_REDUCE);
+  T.final_ms = final_ms;
+  T.n = (uint32_t)n;
+  T.window_size = p.c;
+  T.num_windows = p.W_digits;
+  T.reserved = 1;
+  reap_graveyard(ctx);
+  return MSM_AMD_OK;
+}
+
+// the identity result ((R, 0), (R, 0), (0, 0)) of an empty G2 MSM
+void g2_identity_out(void* out192) {
+  Jacobian2 r{};
+  r.x.c0 = Fq::one();
+  r.y.c0 = Fq::one();
+  std::memcpy(out192, &r, 192);
+}
+
+int g2_args(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points, size_t n,
+            const void* out192) {
+  if (!ctx || !out192) return MSM_AMD_INPUT_ERROR;
+  if (scalar_layout != MSM_AMD_SCALAR_MONT_LE && scalar_layout != MSM_AMD_SCALAR_CANON_LE &&
+      scalar_layout != MSM_AMD_SCALAR_CANON_BE32)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
+  if (msm_amd_g2_point_bytes(g2_point_layout) == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown G2 point layout");
+  if (n > 0 && (!scalars || !points)) return fail(ctx, MSM_AMD_INPUT_ERROR, "null pointer with n > 0");
+  return MSM_AMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_msm_g2_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars,
+                          const void* d_points, size_t n, void* out192) {
+  if (int rc = g2_args(ctx, scalar_layout, g2_point_layout, d_scalars, d_points, n, out192)) return rc;
+  if (n == 0) {
+    g2_identity_out(out192);
+    return MSM_AMD_OK;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return run_msm_g2(ctx, scalar_layout, g2_point_layout, d_scalars, d_points, n, out192);
+}
+
+int msm_amd_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points,
+                   size_t n, void* out192) {
+  if (int rc = g2_args(ctx, scalar_layout, g2_point_layout, scalars, points, n, out192)) return rc;
+  if (n == 0) {
+    g2_identity_out(out192);
+    return MSM_AMD_OK;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = recover_if_stalled(ctx)) return rc;
+  G2State& g = ctx->g2;
+  const size_t sb = n * 32, pb = n * msm_amd_g2_point_bytes(g2_point_layout);
+  int rc;
+  if ((rc = ensure(ctx, g.in_scalars, sb))) return rc;
+  if ((rc = ensure(ctx, g.in_points, pb))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(g.in_scalars.p, scalars, sb, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(g.in_points.p, points, pb, hipMemcpyHostToDevice, ctx->stream));
+  return run_msm_g2(ctx, scalar_layout, g2_point_layout, g.in_scalars.p, g.in_points.p, n, out192);
+}
+
+int msm_amd_test_op_g2(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
+  if (!ctx || op < 0 || op >= G2RAW_OPS || count == 0 || count > (1u << 20) || !a || !b || !out)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_op_g2 arguments");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  const size_t in_bytes = count * kG2RawIn * 4, out_bytes = count * kG2RawOut * 4;
+  int rc;
+  if ((rc = ensure(ctx, ctx->scratch_a, in_bytes))) return rc;
+  if ((rc = ensure(ctx, ctx->scratch_b, in_bytes))) return rc;
+  if ((rc = ensure(ctx, ctx->scratch_c, out_bytes))) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_a.p, a, in_bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_b.p, b, in_bytes, hipMemcpyHostToDevice, st));
+  launch_test_op_g2(st, op, (const uint32_t*)ctx->scratch_a.p, (const uint32_t*)ctx->scratch_b.p,
+                    (uint32_t*)ctx->scratch_c.p, (uint32_t)count);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch_c.p, out_bytes, hipMemcpyDeviceToHost, st));
+  return sync_stream_bounded(ctx, st, __func__);
 }
 
 }  // extern "C"

@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""Value bounds of the G2 arithmetic (bn254_fq2_29.hip.h, bn254_ec2_29.hip.h) by interval arithmetic, in multiples of
+p per Fq2 component.  Every operation mirrors the code: which operand a multiplication negates through the 32 p lift,
+which lifted constant each subtraction uses, where X3 and the doubling are squashed.  Iterates the point invariant to
+its fixed point under madd, mmadd, the full addition and the doubling, and asserts
+  * every subtrahend is below the lift of its subtraction (sub<K>: b < K p; mul / sqr: b1 / a1 < 32 p),
+  * every multiplication operand is below 64 p (limb 8 < 2^28 after norm(): the 64-bit column sums then hold),
+  * the zero filters' operand P stays below kG2ZeroFilter = 16 p.
+Prints the invariant and the intermediate bounds; exit status 1 if an assertion fails."""
+import sys
+
+P = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47
+RP = P / 2 ** 261          # rho' = p / rho
+LIMIT = 64                 # normalised operand value bound
+ZERO_FILTER = 16
+
+
+def chk(a):
+    assert max(a) < LIMIT, a
+    return a
+
+
+def mul(a, b):             # c0 = a0 b0 + a1 (32 p - b1), c1 = a0 b1 + a1 b0
+    assert b[1] < 32, b
+    chk(a), chk(b)
+    return (1 + RP * (a[0] * b[0] + a[1] * 32), 1 + RP * (a[0] * b[1] + a[1] * b[0]))
+
+
+def sqr(a):                # c0 = (a0 + a1)(a0 - a1 + 32 p), c1 = (2 a0) a1
+    assert a[1] < 32, a
+    chk(a)
+    return (1 + RP * (a[0] + a[1]) * (a[0] + 32), 1 + RP * 2 * a[0] * a[1])
+
+
+def add(a, b):
+    return (a[0] + b[0], a[1] + b[1])
+
+
+def sub(a, b, k):
+    assert max(b) < k, (b, k)
+    return (a[0] + k, a[1] + k)
+
+
+def squash(a):
+    chk(a)
+    return (1 + RP * a[0], 1 + RP * a[1])
+
+
+SEEN = {}
+
+
+def note(name, v):
+    SEEN[name] = tuple(max(x, y) for x, y in zip(SEEN.get(name, (0, 0)), v))
+    return v
+
+
+def tail(P_, R, U1, S1, tag):
+    PP = sqr(P_)
+    PPP = mul(P_, PP)
+    Q = mul(U1, PP)
+    RR = sqr(R)
+    X3 = squash(sub(RR, add(PPP, add(Q, Q)), 16))
+    T = sub(Q, X3, 4)
+    Y3 = sub(mul(R, T), mul(S1, PPP), 8)
+    for k, v in (("PP", PP), ("PPP", PPP), ("Q", Q), ("RR", RR), ("T", T)):
+        note(f"{tag}.{k}", v)
+    return X3, Y3, PP, PPP
+
+
+def madd(X, Y, ZZ, ZZZ, qx, qy):
+    U2, S2 = mul(qx, ZZ), mul(qy, ZZZ)
+    P_, R = note("madd.P", sub(U2, X, 4)), note("madd.R", sub(S2, Y, 16))
+    X3, Y3, PP, PPP = tail(P_, R, X, Y, "madd")
+    return X3, Y3, mul(ZZ, PP), mul(ZZZ, PPP)
+
+
+def mmadd(x1, y1, x2, y2):
+    P_, R = note("mmadd.P", sub(x2, x1, 4)), note("mmadd.R", sub(y2, y1, 16))
+    return tail(P_, R, x1, y1, "mmadd")
+
+
+def add_nz(X1, Y1, ZZ1, ZZZ1, X2, Y2, ZZ2, ZZZ2):
+    U1, U2, S1, S2 = mul(X1, ZZ2), mul(X2, ZZ1), mul(Y1, ZZZ2), mul(Y2, ZZZ1)
+    P_, R = note("add.P", sub(U2, U1, 8)), note("add.R", sub(S2, S1, 8))
+    X3, Y3, PP, PPP = tail(P_, R, U1, S1, "add")
+    return X3, Y3, mul(mul(ZZ1, ZZ2), PP), mul(mul(ZZZ1, ZZZ2), PPP)
+
+
+def double(X1, Y1, ZZ1, ZZZ1):
+    U = add(Y1, Y1)
+    V = sqr(U)
+    W = mul(U, V)
+    S = mul(X1, V)
+    XX = sqr(X1)
+    M = add(XX, add(XX, XX))
+    X3 = squash(sub(sqr(M), add(S, S), 32))
+    T = sub(S, X3, 4)
+    Y3 = squash(sub(mul(M, T), mul(W, Y1), 8))
+    return X3, Y3, squash(mul(V, ZZ1)), squash(mul(W, ZZZ1))
+
+
+def widen(a, b):
+    return tuple(tuple(max(x, y) for x, y in zip(u, v)) for u, v in zip(a, b))
+
+
+def main():
+    base_x, base_y = (1, 1), (4, 4)        # canonical x; y canonical or its 4 p negation
+    pt = ((1, 1), (1, 1), (1, 1), (1, 1))  # X, Y, ZZ, ZZZ
+    for _ in range(20):
+        new = widen(pt, madd(*pt, base_x, base_y))
+        new = widen(new, mmadd(base_x, base_y, base_x, base_y))
+        new = widen(new, add_nz(*new, *new))
+        new = widen(new, double(*new))
+        new = widen(new, double(base_x, base_y, (1, 1), (1, 1)))
+        if new == pt:
+            break
+        pt = new
+    else:
+        raise AssertionError("no fixed point")
+    for name in ("madd.P", "mmadd.P", "add.P"):
+        assert max(SEEN[name]) < ZERO_FILTER, (name, SEEN[name])
+    claimed = {"X": 1.21, "Y": 13.4, "ZZ": 3.2, "ZZZ": 2.04}
+    for (name, lim), v in zip(claimed.items(), pt):
+        assert max(v) < lim, (name, v, lim)
+    print("invariant: " + "  ".join(f"{k} < {max(v):.3f} p" for k, v in zip(claimed, pt)))
+    for k in sorted(SEEN):
+        print(f"  {k:10s} < {max(SEEN[k]):.2f} p")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
