@@ -544,9 +544,13 @@ int msm_amd_test_fill_workspaces(msm_amd_ctx* ctx, uint8_t byte);
  * z.c1), normalised to z = (R mod p, 0); the identity is ((R, 0), (R, 0), (0, 0)). */
 enum {
   MSM_AMD_G2_POINT_H2C_AFFINE = 0, /* halo2curves bn256::G2Affine {x, y}: 128 B, identity = all zero */
-  MSM_AMD_G2_POINT_ARK_AFFINE = 1  /* ark_bn254::G2Affine {x, y, infinity: bool}: 136 B, flag at byte 128 */
+  MSM_AMD_G2_POINT_ARK_AFFINE = 1, /* ark_bn254::G2Affine {x, y, infinity: bool}: 136 B, flag at byte 128 */
+  MSM_AMD_G2_POINT_PREPARED = 2,   /* device-only: 128-byte records written by msm_amd_g2_bases_upload /
+                                      msm_amd_g2_bases_prepare_device (opaque internal form of affine G2 points) */
+  MSM_AMD_G2_POINT_TABLES = 3      /* the "points" pointer is a msm_amd_g2_tables handle */
 };
-/* Bytes per point of a G2 layout, 0 for an unknown layout. */
+enum { MSM_AMD_G2_PREPARED_BYTES = 128 };   /* record size of a prepared array */
+/* Bytes per point of a HOST G2 layout; 0 for an unknown layout and for the two device-only ones. */
 size_t msm_amd_g2_point_bytes(int g2_point_layout);
 /* One blocking G2 MSM on the GPU, host buffers (n scalars of 32 B, n points of msm_amd_g2_point_bytes).  Unknown
  * layouts, or a null pointer with n > 0, return MSM_AMD_INPUT_ERROR.  No CPU fallback.  The window is
@@ -555,9 +559,40 @@ size_t msm_amd_g2_point_bytes(int g2_point_layout);
  * and the copy of its partial points). */
 int msm_amd_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points,
                    size_t n, void* out192);
-/* The same with scalars and points in device memory on ctx's device. */
+/* The same with scalars and points in device memory on ctx's device.  Also takes MSM_AMD_G2_POINT_PREPARED (d_points =
+ * a prepared array) and MSM_AMD_G2_POINT_TABLES (d_points = a table handle; n must equal the table's n), which the
+ * host-buffer entry points refuse with MSM_AMD_INPUT_ERROR. */
 int msm_amd_msm_g2_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars,
                           const void* d_points, size_t n, void* out192);
+
+/* Persistent G2 bases (the G2 query of a Groth16 proving key is set once and multiplied by a fresh witness per proof):
+ * msm_amd_bases_upload / _prepare_device / msm_amd_msm_prepared on G2.  The points (a host layout) are converted once
+ * into 128-byte internal records resident on the device; free a prepared array with msm_amd_device_free.  Results are
+ * byte for byte those of msm_amd_msm_g2 on the same inputs.  msm_amd_last_timings: convert_ms is then the scalar
+ * conversion alone. */
+int msm_amd_g2_bases_upload(msm_amd_ctx* ctx, int g2_point_layout, const void* points, size_t n, void** d_prepared);
+int msm_amd_g2_bases_prepare_device(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n,
+                                    void* d_prepared /* n x 128 bytes */);
+int msm_amd_msm_g2_prepared(msm_amd_ctx* ctx, int scalar_layout, const void* scalars /* host */, const void* d_prepared,
+                            size_t n, void* out192);
+
+/* Precomputed G2 window tables (msm_amd_tables_* on G2): 2^(c w) P_i for every window w, W x n x 128 bytes (1.9 GB for
+ * 2^20 points at c = 18).  All windows share ONE set of 2^(c-1) buckets: the window reduction sums one bucket set
+ * instead of W and the host Horner pass walks c bit positions instead of 254.  Built from the two host layouts;
+ * window_size 0 = automatic, else 4..21 with windows * n < 2^31.  Same results byte for byte at every window.  A
+ * handle belongs to its ctx and to G2: a G1 table handle here, or a G2 handle in a G1 call, is MSM_AMD_INPUT_ERROR.
+ * msm_amd_destroy releases tables the caller did not free.  msm_amd_last_timings: num_windows = digit windows per
+ * scalar. */
+typedef struct msm_amd_g2_tables msm_amd_g2_tables;
+int msm_amd_g2_tables_build(msm_amd_ctx* ctx, int g2_point_layout, const void* points, size_t n, uint32_t window_size,
+                            msm_amd_g2_tables** out);
+int msm_amd_g2_tables_build_device(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n,
+                                   uint32_t window_size, msm_amd_g2_tables** out);
+int msm_amd_g2_tables_info(msm_amd_ctx* ctx, const msm_amd_g2_tables* tables, size_t* n, uint32_t* window_size,
+                           uint32_t* num_windows, size_t* device_bytes);
+int msm_amd_g2_tables_free(msm_amd_ctx* ctx, msm_amd_g2_tables* tables);
+int msm_amd_msm_g2_tables(msm_amd_ctx* ctx, const msm_amd_g2_tables* tables, int scalar_layout,
+                          const void* scalars /* host */, void* out192);
 /* The CPU G2 MSM of the library (no ctx, no GPU): windowed bucket method on 4 x 64-bit limbs; threads <= 0: up to 16
  * host threads.  Same layouts and result form as msm_amd_msm_g2. */
 int msm_amd_host_msm_g2(int scalar_layout, int g2_point_layout, const void* scalars, const void* points, size_t n,
@@ -576,11 +611,21 @@ enum {
   MSM_AMD_G2_RAW_PT_MMADD = 3,   /* affine a + affine b, neither the identity */
   MSM_AMD_G2_RAW_PT_ADD_NZ = 4,  /* XYZZ a + XYZZ b, neither the identity (add-2008-s) */
   MSM_AMD_G2_RAW_PT_ADD = 5,     /* XYZZ a + XYZZ b, identities allowed */
-  MSM_AMD_G2_RAW_PT_DOUBLE = 6   /* 2 a, a not the identity */
+  MSM_AMD_G2_RAW_PT_DOUBLE = 6,  /* 2 a, a not the identity */
+  MSM_AMD_G2_RAW_FQ2_INV = 7,    /* a^-1, a != 0, a < 32 p */
+  MSM_AMD_G2_RAW_PT_TO_AFFINE = 8 /* XYZZ a (not the identity) -> affine x, y in words 0..35, canonical limbs */
 };
 int msm_amd_test_op_g2(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count);
 /* The same bodies on the host CPU (no GPU needed). */
 int msm_amd_test_op_g2_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count);
+/* Test aids of the G2 tables: `count` entries of window w from point `first` on, as MSM_AMD_G2_POINT_H2C_AFFINE
+ * records (identity = all zero) ... */
+int msm_amd_test_g2_tables_read(msm_amd_ctx* ctx, const msm_amd_g2_tables* tables, uint32_t w, size_t first,
+                                size_t count, void* out);
+/* ... and the host twin of the table build (no ctx, no GPU; the same bodies on the CPU): all num_windows x n entries
+ * in the same form, out[(w * n + i) * 128]; points in a host layout; threads <= 0: up to 16 host threads. */
+int msm_amd_test_g2_table_host(int g2_point_layout, const void* points, size_t n, uint32_t window_size,
+                               uint32_t num_windows, int threads, void* out);
 
 /* ---- introspection --------------------------------------------------------------------------- */
 int msm_amd_last_timings(const msm_amd_ctx* ctx, msm_amd_timings* out);

@@ -33,10 +33,11 @@ POINT_BYTES = {POINT_H2C_AFFINE: 64, POINT_ARK_PROJECTIVE: 96, POINT_ARK_AFFINE:
 RAW_FE_MUL_WIDE, RAW_FE_SQR_WIDE, RAW_FE_MUL2_WIDE = range(32, 35)   # the point additions' wide-digit forms
 RAW_IN_WORDS, RAW_OUT_WORDS = 36, 40
 # BN254 G2 (MSM_AMD_G2_*): point layouts, raw-limb test ops and their record widths
-G2_POINT_H2C_AFFINE, G2_POINT_ARK_AFFINE = 0, 1
+G2_POINT_H2C_AFFINE, G2_POINT_ARK_AFFINE, G2_POINT_PREPARED, G2_POINT_TABLES = 0, 1, 2, 3
+G2_PREPARED_BYTES = 128
 G2_POINT_BYTES = {G2_POINT_H2C_AFFINE: 128, G2_POINT_ARK_AFFINE: 136}
 (G2_RAW_FQ2_MUL, G2_RAW_FQ2_SQR, G2_RAW_PT_MADD, G2_RAW_PT_MMADD, G2_RAW_PT_ADD_NZ, G2_RAW_PT_ADD,
- G2_RAW_PT_DOUBLE) = range(7)
+ G2_RAW_PT_DOUBLE, G2_RAW_FQ2_INV, G2_RAW_PT_TO_AFFINE) = range(9)
 G2_RAW_IN_WORDS, G2_RAW_OUT_WORDS = 72, 80
 
 
@@ -73,6 +74,9 @@ EXPORTS = [
     "msm_amd_test_last_plan", "msm_amd_test_stage_copy", "msm_amd_test_fill_workspaces",
     "msm_amd_g2_point_bytes", "msm_amd_msm_g2", "msm_amd_msm_g2_device", "msm_amd_host_msm_g2",
     "msm_amd_test_g2_progression", "msm_amd_test_op_g2", "msm_amd_test_op_g2_host",
+    "msm_amd_g2_bases_upload", "msm_amd_g2_bases_prepare_device", "msm_amd_msm_g2_prepared",
+    "msm_amd_g2_tables_build", "msm_amd_g2_tables_build_device", "msm_amd_g2_tables_info", "msm_amd_g2_tables_free",
+    "msm_amd_msm_g2_tables", "msm_amd_test_g2_tables_read", "msm_amd_test_g2_table_host",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -236,6 +240,17 @@ def _lib():
         L.msm_amd_test_g2_progression.argtypes = [c_void_p, c_void_p, c_size_t, c_int, c_void_p]
         L.msm_amd_test_op_g2.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_test_op_g2_host.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
+        L.msm_amd_g2_bases_upload.argtypes = [c_void_p, c_int, c_void_p, c_size_t, POINTER(c_void_p)]
+        L.msm_amd_g2_bases_prepare_device.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p]
+        L.msm_amd_msm_g2_prepared.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+        L.msm_amd_g2_tables_build.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_uint32, POINTER(c_void_p)]
+        L.msm_amd_g2_tables_build_device.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_uint32, POINTER(c_void_p)]
+        L.msm_amd_g2_tables_info.argtypes = [c_void_p, c_void_p, POINTER(c_size_t), POINTER(c_uint32),
+                                             POINTER(c_uint32), POINTER(c_size_t)]
+        L.msm_amd_g2_tables_free.argtypes = [c_void_p, c_void_p]
+        L.msm_amd_msm_g2_tables.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+        L.msm_amd_test_g2_tables_read.argtypes = [c_void_p, c_void_p, c_uint32, c_size_t, c_size_t, c_void_p]
+        L.msm_amd_test_g2_table_host.argtypes = [c_int, c_void_p, c_size_t, c_uint32, c_uint32, c_int, c_void_p]
         L.msm_amd_generate_instance_host.argtypes = [c_uint64, c_size_t, c_int, c_void_p, c_void_p, c_int]
         L.msm_amd_test_op_ifma.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_tuned_split.argtypes = [c_size_t]
@@ -528,9 +543,64 @@ class MsmConfig:
 
     def msm_g2_device(self, d_scalars, d_points, n: int, scalar_layout=SCALAR_MONT_LE,
                       point_layout=G2_POINT_H2C_AFFINE) -> bytes:
-        """msm_g2 with scalars and points already in device memory (pointers from alloc / to_device)."""
+        """msm_g2 with scalars and points already in device memory (pointers from alloc / to_device); d_points may
+        also be a prepared array (G2_POINT_PREPARED) or a table handle (G2_POINT_TABLES)."""
         out = ctypes.create_string_buffer(192)
         self._check(_lib().msm_amd_msm_g2_device(self.h, scalar_layout, point_layout, d_scalars, d_points, n, out))
+        return out.raw
+
+    # ---- persistent G2 bases and precomputed G2 window tables (bases_upload ... msm_tables on G2) ----
+    def g2_bases_upload(self, points: bytes, n: int, point_layout=G2_POINT_H2C_AFFINE) -> int:
+        """Convert once, keep resident; returns a device pointer to pass with G2_POINT_PREPARED (free with .free)."""
+        p = c_void_p()
+        self._check(_lib().msm_amd_g2_bases_upload(self.h, point_layout, points, n, ctypes.byref(p)))
+        return p.value
+
+    def g2_bases_prepare_device(self, d_points, n, point_layout=G2_POINT_H2C_AFFINE) -> int:
+        out = self.alloc(G2_PREPARED_BYTES * n)
+        try:
+            self._check(_lib().msm_amd_g2_bases_prepare_device(self.h, point_layout, c_void_p(d_points), n,
+                                                               c_void_p(out)))
+        except MsmError:
+            self.free(out)
+            raise
+        return out
+
+    def msm_g2_prepared(self, scalars: bytes, d_prepared, n, scalar_layout=SCALAR_MONT_LE) -> bytes:
+        out = ctypes.create_string_buffer(192)
+        self._check(_lib().msm_amd_msm_g2_prepared(self.h, scalar_layout, scalars, c_void_p(d_prepared), n, out))
+        return out.raw
+
+    def g2_tables_build(self, points: bytes, n: int, point_layout=G2_POINT_H2C_AFFINE, window_size=0) -> int:
+        """Returns a G2 table handle: pass it as the points pointer with G2_POINT_TABLES, free with g2_tables_free."""
+        h = c_void_p()
+        self._check(_lib().msm_amd_g2_tables_build(self.h, point_layout, points, n, window_size, ctypes.byref(h)))
+        return h.value
+
+    def g2_tables_build_device(self, d_points, n, point_layout=G2_POINT_H2C_AFFINE, window_size=0) -> int:
+        h = c_void_p()
+        self._check(_lib().msm_amd_g2_tables_build_device(self.h, point_layout, c_void_p(d_points), n, window_size,
+                                                          ctypes.byref(h)))
+        return h.value
+
+    def g2_tables_info(self, tables):
+        n, nbytes, c, W = c_size_t(), c_size_t(), c_uint32(), c_uint32()
+        self._check(_lib().msm_amd_g2_tables_info(self.h, c_void_p(tables), ctypes.byref(n), ctypes.byref(c),
+                                                  ctypes.byref(W), ctypes.byref(nbytes)))
+        return {"n": n.value, "window_size": c.value, "num_windows": W.value, "device_bytes": nbytes.value}
+
+    def g2_tables_free(self, tables):
+        self._check(_lib().msm_amd_g2_tables_free(self.h, c_void_p(tables)))
+
+    def msm_g2_tables(self, scalars: bytes, tables, scalar_layout=SCALAR_MONT_LE) -> bytes:
+        out = ctypes.create_string_buffer(192)
+        self._check(_lib().msm_amd_msm_g2_tables(self.h, c_void_p(tables), scalar_layout, scalars, out))
+        return out.raw
+
+    def g2_tables_read(self, tables, w, first, count) -> bytes:
+        """Test aid: `count` entries of window w from point `first` on, G2_POINT_H2C_AFFINE records."""
+        out = ctypes.create_string_buffer(128 * count)
+        self._check(_lib().msm_amd_test_g2_tables_read(self.h, c_void_p(tables), w, first, count, out))
         return out.raw
 
     def test_op_g2(self, op, a, b, count):
@@ -699,6 +769,17 @@ def host_msm_g2(scalars: bytes, points: bytes, n: int, threads=0, scalar_layout=
     """The product's CPU G2 MSM (no GPU): 192-byte normalised Jacobian, the form msm_g2 returns."""
     out = ctypes.create_string_buffer(192)
     st = _lib().msm_amd_host_msm_g2(scalar_layout, point_layout, scalars, points, n, threads, out)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw
+
+
+def g2_table_host(points: bytes, n: int, window_size: int, num_windows: int, threads=0,
+                  point_layout=G2_POINT_H2C_AFFINE) -> bytes:
+    """Host twin of the G2 table build (no GPU): num_windows * n G2_POINT_H2C_AFFINE records, entry (w, i) at
+    128 * (w * n + i)."""
+    out = ctypes.create_string_buffer(128 * n * num_windows)
+    st = _lib().msm_amd_test_g2_table_host(point_layout, points, n, window_size, num_windows, threads, out)
     if st != OK:
         raise MsmError(st)
     return out.raw

@@ -14,6 +14,9 @@
 // Intermediate values stay below 20 p (P < 9.3 p, R < 20 p), inside the 32 p lift of Fq2::mul / sqr.  The
 // exceptional cases (P = Q -> doubling, P = -Q -> identity) are filtered on the one-limb test of both components of P
 // (Fq2::maybe_zero, bound 16 > 9.3) and confirmed exactly; the doubling squashes all of its outputs.
+// XYZZ -> affine (pt2_to_affine, the table build) costs ONE inversion: t = (ZZ ZZZ)^-1, x = X t ZZZ, y = Y t ZZ.
+// For any carried point (bounds above): ZZ ZZZ < 1.7 p, t < 1.2 p, X t < 1.24 p, Y t < 3.7 p, x < 1.25 p,
+// y < 1.3 p -- multiplication outputs below 2 p, what aff2_pack takes.
 #pragma once
 #include "bn254_ec.hip.h"
 #include "bn254_fq2_29.hip.h"
@@ -102,6 +105,19 @@ MSM_HD Aff2I aff2_unpack_finite(const Aff2Packed& p) {
   return r;
 }
 
+// memory form -> external affine (canonical Montgomery R = 2^256; the identity marker -> all zero)
+MSM_HD Affine2 aff2packed_to_ext(const Aff2Packed& p) {
+  Affine2 r;
+  if (aff2packed_is_identity(p)) {
+    r.x.c0 = r.x.c1 = r.y.c0 = r.y.c1 = u256_zero();
+    return r;
+  }
+  const Aff2I a = aff2_unpack_finite(p);
+  Fq2::to_ext(a.x, r.x.c0, r.x.c1);
+  Fq2::to_ext(a.y, r.y.c0, r.y.c1);
+  return r;
+}
+
 // Jacobian (X, Y, Z) -> (X, Y, Z^2, Z^3)
 MSM_HD PtI2 pt2_from_ext(const Jacobian2& p) {
   if (u256_is_zero(p.z.c0) && u256_is_zero(p.z.c1)) return pt2_identity();
@@ -146,6 +162,35 @@ MSM_HD PtI2 pt2_double(const PtI2& p) {   // p not the identity
   r.zz = Fq2::squash(Fq2::mul(V, p.zz));
   r.zzz = Fq2::squash(Fq2::mul(W, p.zzz));
   return r;
+}
+
+// (X, Y, ZZ, ZZZ), not the identity -> affine (X / ZZ, Y / ZZZ) with one inversion.  The outputs are multiplication
+// results below 2 p (header), NOT canonical: aff2_pack canonicalises them.
+MSM_HD Aff2I pt2_to_affine(const PtI2& p) {
+  const fq2 t = Fq2::inv(Fq2::mul(p.zz, p.zzz));
+  Aff2I r;
+  r.x = Fq2::mul(Fq2::mul(p.x, t), p.zzz);
+  r.y = Fq2::mul(Fq2::mul(p.y, t), p.zz);
+  return r;
+}
+
+// The precomputed window tables of one base (build_tables_g2_kernel and its host twin): entry w = 2^(c w) P as
+// Aff2Packed, handed to put(w, record).  Window 0 is the converted base; window w is c doublings of window w - 1,
+// re-started from its stored affine entry (canonical coordinates, ZZ = ZZZ = 1), then pt2_to_affine.  P is taken as a
+// point of odd order (r-torsion), so no doubling meets y = 0; the identity stays the identity marker throughout.
+template <class Put>
+MSM_HD void g2_table_walk(const Affine2& ext, uint32_t c, uint32_t W, Put&& put) {
+  Aff2Packed rec = aff2_pack(aff2i_from_ext(ext));
+  put(0u, rec);
+  const bool ident = aff2packed_is_identity(rec);
+  MSM_NO_UNROLL for (uint32_t w = 1; w < W; ++w) {
+    if (!ident) {
+      PtI2 p = pt2_from_aff(aff2_unpack_finite(rec));
+      MSM_NO_UNROLL for (uint32_t i = 0; i < c; ++i) p = pt2_double(p);
+      rec = aff2_pack(pt2_to_affine(p));
+    }
+    put(w, rec);
+  }
 }
 
 // The common tail of the additions: X3 = R^2 - PPP - 2Q (squashed), Y3 = R (Q - X3) - S1 PPP.

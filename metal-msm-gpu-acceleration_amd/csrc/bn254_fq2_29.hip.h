@@ -17,9 +17,21 @@
 //   sqr(a)         : c0 = (a0 + a1)(a0 - a1 + 32 p), c1 = (2 a0) a1: two single products;  a1 < 32 p
 //                    c0 < (1 + rho' (A0 + A1)(A0 + 32)) p,  c1 < (1 + rho' 2 A0 A1) p
 //   squash(a)      : a * (rho mod p) / rho = a, value < (1 + rho' A) p: brings any operand back to ~1 p
+//   inv_fq(a)      : Fq inversion a^(p-2) on fe29 (0 -> 0); a a valid Fq29::mul operand, value < A p with A <= 32;
+//                    result a multiplication output (exact limbs), value < (1 + 1.02 rho' A) p <= 1.2 p
+//   inv(a)         : conj(a) (a0^2 + a1^2)^-1, ONE inv_fq (0 -> 0);  a normalised, a < 32 p
+//                    n = norm_fq(a) < (1 + rho' 2 A^2) p <= 13.1 p,  n^-1 < (1 + 1.02 rho' 13.1) p < 1.08 p,
+//                    c0 = a0 n^-1, c1 = (32 p - a1) n^-1: multiplication outputs (exact limbs) < (1 + rho' 32 * 1.08) p
+//                    < 1.21 p
 //   to_ext / is_zero_exact : any normalised operand < 64 p
 #pragma once
 #include "bn254_fq29.hip.h"
+
+#if defined(__HIPCC__)
+#define MSM_NO_UNROLL _Pragma("unroll 1")
+#else
+#define MSM_NO_UNROLL
+#endif
 
 namespace msm_amd {
 
@@ -66,6 +78,31 @@ struct Fq2 {
 
   // a0^2 + a1^2 (the norm to Fq; an element of Fq2 is invertible iff it is non-zero); a < 32 p: < (1 + rho' 2 A^2) p
   MSM_HD static fe29 norm_fq(const fq2& a) { return Fq29::mul2(a.c0, a.c0, a.c1, a.c1); }
+
+  // Fq inversion a^-1 = a^(p - 2) by square-and-multiply over the fixed exponent, most significant bit first (the 7
+  // leading zero bits of the top limb square `one`): 261 squarings, one multiplication per set bit.  The running power
+  // r stays below 1.02 p before every multiplication (r < 1 + rho' 1.02 * 32 = 1.2 p after a multiplication by
+  // a < 32 p, < 1.01 p after the next squaring), so every operand is a valid one, and the result -- bit 0 of p - 2 is
+  // set, it ends on a multiplication -- is < (1 + rho' 1.02 A) p.  Set-up code (the table build): the loops are not
+  // unrolled, the exponent limbs are immediates.
+  MSM_HD static fe29 inv_fq(const fe29& a) {
+    fe29 r = Fq29::one();
+    MSM_NO_UNROLL for (int j = 8; j >= 0; --j) {
+      uint32_t e = 0;   // limb j of p - 2 (p(0) >= 2: only limb 0 differs from p)
+      MSM_UNROLL for (int k = 0; k < 9; ++k) e = (k == j) ? (Fq29::p(k) - (k == 0 ? 2u : 0u)) : e;
+      MSM_NO_UNROLL for (int b = 28; b >= 0; --b) {
+        r = Fq29::sqr(r);
+        if ((e >> b) & 1u) r = Fq29::mul(r, a);
+      }
+    }
+    return r;
+  }
+
+  // a^-1 = conj(a) / (a0^2 + a1^2); a normalised, < 32 p (see the contract above)
+  MSM_HD static fq2 inv(const fq2& a) {
+    const fe29 ninv = inv_fq(norm_fq(a));
+    return fq2{Fq29::mul(a.c0, ninv), Fq29::mul(sub1<32>(Fq29::zero(), a.c1), ninv)};
+  }
 
   // a == 0 needs both components zero; `bound`: a < bound p for the one-limb filter of each component
   MSM_HD static bool maybe_zero(const fq2& a, uint32_t bound) {

@@ -206,6 +206,38 @@ int msm_amd_test_g2_progression(const void* start128, const void* step128, size_
   return MSM_AMD_OK;
 }
 
+// Host twin of build_tables_g2_kernel: g2_table_walk per point on the CPU, entries as external affine records.
+int msm_amd_test_g2_table_host(int g2_point_layout, const void* points, size_t n, uint32_t window_size,
+                               uint32_t num_windows, int threads, void* out) {
+  using namespace msm_amd;
+  if (msm_amd_g2_point_bytes(g2_point_layout) == 0 || !points || !out || n == 0 || window_size == 0 ||
+      window_size > 32 || num_windows == 0)
+    return MSM_AMD_INPUT_ERROR;
+  const uint8_t* pt = (const uint8_t*)points;
+  uint8_t* o = (uint8_t*)out;
+  std::atomic<size_t> next{0};
+  auto worker = [&]() {
+    for (;;) {
+      const size_t i = next.fetch_add(1);
+      if (i >= n) break;
+      h64::Aff2 raw;
+      read_g2_point(g2_point_layout, pt, i, raw);
+      Affine2 a;
+      std::memcpy(&a, &raw, sizeof a);
+      g2_table_walk(a, window_size, num_windows, [&](uint32_t w, const Aff2Packed& rec) {
+        const Affine2 e = aff2packed_to_ext(rec);
+        std::memcpy(o + ((size_t)w * n + i) * 128, &e, 128);
+      });
+    }
+  };
+  const unsigned T = (unsigned)std::min<size_t>(pick_threads(threads), n);
+  std::vector<std::thread> pool;
+  for (unsigned t = 1; t < T; ++t) pool.emplace_back(worker);
+  worker();
+  for (std::thread& th : pool) th.join();
+  return MSM_AMD_OK;
+}
+
 int msm_amd_test_op_g2_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
   using namespace msm_amd;
   if (op < 0 || op >= G2RAW_OPS || (count > 0 && (!a || !b || !out))) return MSM_AMD_INPUT_ERROR;

@@ -66,6 +66,36 @@ void launch_convert_bases_g2(hipStream_t st, const void* in, int ark, uint32_t n
   hipLaunchKernelGGL(convert_bases_g2_kernel, dim3((n + 255) / 256), dim3(256), 0, st, (const uint8_t*)in, ark, n, out);
 }
 
+// Precomputed window tables (build_tables_kernel of k_misc.hip on G2): tables[w * n + i] = 2^(c w) P_i as Aff2Packed,
+// so that window w of scalar i adds into the SAME bucket set as window 0.  One lane per point walks the windows
+// (g2_table_walk): c doublings from the previous entry, one inversion per entry.  A set-up cost, paid once per key.
+__global__ void __launch_bounds__(64)
+build_tables_g2_kernel(const uint8_t* __restrict__ in, int ark, uint32_t n, uint32_t c, uint32_t W,
+                       Aff2Packed* __restrict__ tables) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const uint32_t* src = reinterpret_cast<const uint32_t*>(in + (size_t)t * (ark ? 136 : 128));
+  auto word8 = [&](int off) {   // word loads, as convert_bases_g2_kernel
+    u256 r;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) r.v[i] = src[off + i];
+    return r;
+  };
+  Affine2 a;
+  a.x.c0 = word8(0);
+  a.x.c1 = word8(8);
+  a.y.c0 = word8(16);
+  a.y.c1 = word8(24);
+  if (ark && (src[32] & 0xFFu)) a.x.c0 = a.x.c1 = a.y.c0 = a.y.c1 = u256_zero();
+  g2_table_walk(a, c, W, [&](uint32_t w, const Aff2Packed& rec) { store16(&tables[(size_t)w * n + t], rec); });
+}
+
+void launch_build_tables_g2(hipStream_t st, const void* in, int ark, uint32_t n, uint32_t c, uint32_t W,
+                            Aff2Packed* tables) {
+  hipLaunchKernelGGL(build_tables_g2_kernel, dim3((n + 63) / 64), dim3(64), 0, st, (const uint8_t*)in, ark, n, c, W,
+                     tables);
+}
+
 // ---- accumulation -----------------------------------------------------------------------------------------------
 // One lane per work item (bucket b, chunk j): points [j CH, min(size, (j + 1) CH)) of the bucket's slice of `sorted`,
 // in the order `order` gives (descending length).  The state machine of accumulate_kernel: kEmpty (identity), kOne

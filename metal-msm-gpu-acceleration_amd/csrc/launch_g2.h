@@ -10,6 +10,9 @@ namespace msm_amd {
 // bases: n external G2 affine records, 128 B (halo2curves G2Affine, identity = all zero) or, ark != 0, 136 B (ark-bn254
 // G2Affine: x, y, then the infinity flag at byte 128) -> n Aff2Packed
 void launch_convert_bases_g2(hipStream_t st, const void* in, int ark, uint32_t n, Aff2Packed* out);
+// window tables of n bases in an external layout: tables[w * n + i] = 2^(c w) P_i, W * n Aff2Packed
+void launch_build_tables_g2(hipStream_t st, const void* in, int ark, uint32_t n, uint32_t c, uint32_t W,
+                            Aff2Packed* tables);
 // The work items of launch_sort, one lane each, as accumulate_kernel: buckets [W][nb] or partials of split buckets
 void launch_accumulate_g2(hipStream_t st, const Plan& p, const Aff2Packed* bases, const SortBuffers& b, PtI2* buckets,
                           PtI2* partials);

@@ -166,6 +166,14 @@ struct msm_amd_tables {
   void* d_tables = nullptr;   // W * n AffPacked
 };
 
+// The same for G2 (msm_amd_g2_tables_*): W * n Aff2Packed; validated by membership in msm_amd_ctx::live_g2_tables, so
+// that a G1 handle is no G2 handle and the reverse.
+struct msm_amd_g2_tables {
+  size_t n = 0;
+  uint32_t c = 0, W = 0;
+  void* d_tables = nullptr;
+};
+
 // Buffers of the G2 MSM (msm_amd_msm_g2*): one blocking call at a time on the main stream.  `ws` holds the scalar
 // front end's buffers (digits, sort, work items, scalar conversion) -- its own, so a G2 call never touches what a G1
 // instance of the same ctx may still be using; the point-valued buffers are G2-sized.
@@ -205,6 +213,7 @@ struct msm_amd_ctx {
   std::string last_error;
   uint32_t forced_window = 0;
   std::vector<msm_amd_tables*> live_tables;
+  std::vector<msm_amd_g2_tables*> live_g2_tables;
   int next_ws = 0;
   DeviceBuf scratch_a, scratch_b, scratch_c, scratch_b2, scratch_c2;
   Batch batches[kMaxBatches];
@@ -1957,6 +1966,11 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
     delete t;
   }
   ctx->live_tables.clear();
+  for (msm_amd_g2_tables* t : ctx->live_g2_tables) {
+    (void)hipFree(t->d_tables);
+    delete t;
+  }
+  ctx->live_g2_tables.clear();
   for (DeviceBuf* b : {&ctx->scratch_a, &ctx->scratch_b, &ctx->scratch_c, &ctx->scratch_b2, &ctx->scratch_c2}) kill_buf(*b);
   bases_cache_clear(ctx);   // (entries and unused reserves go through the graveyard)
   for (const msm_amd_ctx::CacheReserve& r : ctx->cache_reserve) ctx->graveyard.push_back(r.d);
@@ -3079,6 +3093,14 @@ uint64_t msm_amd_algorithmic_bytes(size_t n, uint32_t window_size, int accumulat
 // ---- BN254 G2 MSM (one blocking call on the main stream) -----------------------------------------------------------
 namespace {
 
+const msm_amd_g2_tables* find_g2_tables(const msm_amd_ctx* ctx, const void* handle) {
+  for (const msm_amd_g2_tables* t : ctx->live_g2_tables)
+    if ((const void*)t == handle) return t;
+  return nullptr;
+}
+
+// d_points: n records of a host layout, a prepared array (MSM_AMD_G2_POINT_PREPARED: no base conversion) or a table
+// handle (MSM_AMD_G2_POINT_TABLES: the one-window plan of enqueue_msm, every digit window adds into one bucket set).
 // The whole G2 MSM of device-resident inputs: scalar conversion, digits and sort exactly as enqueue_msm does them (into
 // the G2 state's own front-end buffers), then the G2 kernels, the copy of the partial points, a bounded wait and the
 // host Horner pass.  ctx->mu held by the caller.
@@ -3090,8 +3112,16 @@ int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const v
   G2State& g = ctx->g2;
   Workspace& w = g.ws;
   hipStream_t st = ctx->stream;
-  const uint32_t c = ctx->forced_window ? ctx->forced_window : auto_window_lone(n);
-  Plan p = make_plan(n, c);
+  const msm_amd_g2_tables* tb = nullptr;
+  if (g2_point_layout == MSM_AMD_G2_POINT_TABLES) {   // d_points is the handle of msm_amd_g2_tables_build*
+    tb = find_g2_tables(ctx, d_points);
+    if (!tb) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
+    if (n != tb->n) return fail(ctx, MSM_AMD_INPUT_ERROR, "n differs from the number of points the tables hold");
+  }
+  const bool prepared = tb != nullptr || g2_point_layout == MSM_AMD_G2_POINT_PREPARED;
+  const uint32_t c = tb ? tb->c : (ctx->forced_window ? ctx->forced_window : auto_window_lone(n));
+  Plan p = tb ? make_plan(n, c, tb->W) : make_plan(n, c);
+  const size_t ne = p.n;   // sorted entries per window: the points, or W_digits * points with tables (enqueue_msm)
   p.red_group = pick_reduce_group(p);
   p.rb_threads = 0;
   int rc;
@@ -3107,14 +3137,14 @@ int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const v
     HIP_TRY(ctx, hipHostMalloc((void**)&g.h_partial, p.partial_count * sizeof(Jacobian2), hipHostMallocDefault));
     g.h_partial_cap = p.partial_count;
   }
-  if ((rc = ensure(ctx, w.digits, (size_t)p.W * n * (p.wide_digits ? sizeof(uint32_t) : sizeof(uint16_t))))) return rc;
+  if ((rc = ensure(ctx, w.digits, (size_t)p.W * ne * (p.wide_digits ? sizeof(uint32_t) : sizeof(uint16_t))))) return rc;
   if ((rc = ensure(ctx, w.coarse_cnt, (size_t)p.W * p.Q * (1u << p.hb) * sizeof(uint32_t)))) return rc;
   if ((rc = ensure(ctx, w.region_start, (size_t)p.W * ((1u << p.hb) + 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.tmp_idx, (size_t)p.W * n * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.tmp_fine, (size_t)p.W * n * sizeof(uint16_t)))) return rc;
+  if ((rc = ensure(ctx, w.tmp_idx, (size_t)p.W * ne * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.tmp_fine, (size_t)p.W * ne * sizeof(uint16_t)))) return rc;
   if (p.mb) {
-    if ((rc = ensure(ctx, w.tmp_idx2, (size_t)p.W * n * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(ctx, w.tmp_fine2, (size_t)p.W * n * sizeof(uint16_t)))) return rc;
+    if ((rc = ensure(ctx, w.tmp_idx2, (size_t)p.W * ne * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(ctx, w.tmp_fine2, (size_t)p.W * ne * sizeof(uint16_t)))) return rc;
     if ((rc = ensure(ctx, w.mid_cnt, ((size_t)p.W << p.hb) * p.Q2 * (1u << p.mb) * sizeof(uint32_t)))) return rc;
     if ((rc = ensure(ctx, w.region_start2, (size_t)p.W * ((1u << (p.hb + p.mb)) + 1) * sizeof(uint32_t)))) return rc;
   }
@@ -3124,11 +3154,11 @@ int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const v
   if ((rc = ensure(ctx, w.win_items, (1024 + 2 * 1024) * sizeof(uint32_t)))) return rc;
   if ((rc = ensure(ctx, w.size_bins, (size_t)(p.CH + 1) * ((p.total_buckets + p.front_threads - 1) / p.front_threads) *
                                          sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.sorted, (size_t)p.W * n * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.sorted, (size_t)p.W * ne * sizeof(uint32_t)))) return rc;
   if ((rc = ensure(ctx, w.order, p.max_items * sizeof(uint2)))) return rc;
   if ((rc = ensure(ctx, w.multi_list, p.max_items * sizeof(uint32_t)))) return rc;
   if ((rc = ensure(ctx, w.counters, sizeof(PlanCounters)))) return rc;
-  if ((rc = ensure(ctx, g.bases, n * sizeof(Aff2Packed)))) return rc;
+  if (!prepared && (rc = ensure(ctx, g.bases, n * sizeof(Aff2Packed)))) return rc;
   if ((rc = ensure(ctx, g.buckets, p.total_buckets * sizeof(PtI2)))) return rc;
   if ((rc = ensure(ctx, g.item_partials, p.max_items * sizeof(PtI2)))) return rc;
   if ((rc = ensure(ctx, g.S, p.total_segs * sizeof(PtI2)))) return rc;
@@ -3160,18 +3190,21 @@ int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const v
   const u256* sc = nullptr;
   const Affine* unused = nullptr;
   int sc_mont = 0;
-  if ((rc = convert_inputs(ctx, w, st, scalar_layout, MSM_AMD_POINT_PREPARED, d_scalars, nullptr, n, &sc, &sc_mont,
-                           &unused)))
+  if ((rc = convert_inputs(ctx, w, st, scalar_layout, MSM_AMD_POINT_PREPARED, d_scalars, nullptr, p.n_scalars, &sc,
+                           &sc_mont, &unused)))
     return rc;
-  launch_convert_bases_g2(st, d_points, g2_point_layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n,
-                          (Aff2Packed*)g.bases.p);
+  const Aff2Packed* bases = tb ? (const Aff2Packed*)tb->d_tables
+                               : (prepared ? (const Aff2Packed*)d_points : (const Aff2Packed*)g.bases.p);
+  if (!prepared)
+    launch_convert_bases_g2(st, d_points, g2_point_layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n,
+                            (Aff2Packed*)g.bases.p);
   HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_CONVERT], st));
   launch_digits(st, p, sc, sc_mont, sb.digits);
   HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_DIGITS], st));
   launch_sort(st, p, sb);
   HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_SORT], st));
   // the bucket matrix is not cleared: the window reduction reads bucket_size (see enqueue_msm)
-  launch_accumulate_g2(st, p, (const Aff2Packed*)g.bases.p, sb, (PtI2*)g.buckets.p, (PtI2*)g.item_partials.p);
+  launch_accumulate_g2(st, p, bases, sb, (PtI2*)g.buckets.p, (PtI2*)g.item_partials.p);
   launch_combine_g2(st, p, sb, (PtI2*)g.buckets.p, (PtI2*)g.item_partials.p);
   HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_ACC], st));
   launch_reduce_g2(st, p, (const PtI2*)g.buckets.p, (const uint32_t*)w.bsize.p, (PtI2*)g.S.p, (PtI2*)g.T.p,
@@ -3224,14 +3257,72 @@ void g2_identity_out(void* out192) {
   std::memcpy(out192, &r, 192);
 }
 
+// `device`: the device-resident entry point, which also takes the two device-only layouts (host layouts are the ones
+// msm_amd_g2_point_bytes knows)
 int g2_args(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points, size_t n,
-            const void* out192) {
+            const void* out192, bool device = false) {
   if (!ctx || !out192) return MSM_AMD_INPUT_ERROR;
   if (scalar_layout != MSM_AMD_SCALAR_MONT_LE && scalar_layout != MSM_AMD_SCALAR_CANON_LE &&
       scalar_layout != MSM_AMD_SCALAR_CANON_BE32)
     return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
-  if (msm_amd_g2_point_bytes(g2_point_layout) == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown G2 point layout");
+  const bool device_only = g2_point_layout == MSM_AMD_G2_POINT_PREPARED || g2_point_layout == MSM_AMD_G2_POINT_TABLES;
+  if (msm_amd_g2_point_bytes(g2_point_layout) == 0 && !(device && device_only))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown G2 point layout");
   if (n > 0 && (!scalars || !points)) return fail(ctx, MSM_AMD_INPUT_ERROR, "null pointer with n > 0");
+  return MSM_AMD_OK;
+}
+
+bool g2_scalar_layout_ok(int scalar_layout) {
+  return scalar_layout == MSM_AMD_SCALAR_MONT_LE || scalar_layout == MSM_AMD_SCALAR_CANON_LE ||
+         scalar_layout == MSM_AMD_SCALAR_CANON_BE32;
+}
+
+// Conversion of a resident G2 point array (a host layout) to Aff2Packed records; ctx->mu held by the caller.
+int prepare_bases_g2_locked(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n, void* d_prepared) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!drain_or_mark_stalled(ctx)) return fail(ctx, MSM_AMD_PIPELINE_ERROR, "device busy past the wait bound");   // a set-up step
+  hipStream_t st = ctx->stream;
+  launch_convert_bases_g2(st, d_points, g2_point_layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n,
+                          (Aff2Packed*)d_prepared);
+  HIP_TRY(ctx, hipGetLastError());
+  return sync_stream_bounded(ctx, st, __func__);
+}
+
+// The automatic table window.  auto_table_window (G1) balances the W n mixed additions against the 2^(c-1) buckets of
+// the window reduction; the same balance holds on G2 (every term costs the same factor more), so it is the starting
+// point, and the measurement of DESIGN.md section 8 keeps it.
+uint32_t auto_g2_table_window(size_t n) { return auto_table_window(n); }
+
+int g2_tables_build_locked(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n, uint32_t window_size,
+                           msm_amd_g2_tables** out) {
+  const uint32_t c = window_size ? window_size : auto_g2_table_window(n);
+  if (c < 4 || c > 21) return fail(ctx, MSM_AMD_INPUT_ERROR, "table window_size must be 0 (auto) or 4..21");
+  const uint32_t W = kModulusBits / c + 1;
+  if ((size_t)W * n > 0x7FFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, "windows * n must stay below 2^31");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!drain_or_mark_stalled(ctx)) return fail(ctx, MSM_AMD_PIPELINE_ERROR, "device busy past the wait bound");   // a set-up step
+  hipStream_t st = ctx->stream;
+  void* d_tab = nullptr;
+  if (int qrc = quiesce_for_allocation(ctx, "the G2 window tables")) return qrc;
+  HIP_TRY(ctx, hipMalloc(&d_tab, (size_t)W * n * sizeof(Aff2Packed)));
+  launch_build_tables_g2(st, d_points, g2_point_layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n, c, W,
+                         (Aff2Packed*)d_tab);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && sync_stream_bounded(ctx, st, "G2 table build")) {
+    ctx->graveyard.push_back(d_tab);   // the build may still be running: released when the ctx is idle
+    return MSM_AMD_PIPELINE_ERROR;
+  }
+  if (e != hipSuccess) {
+    (void)hipFree(d_tab);
+    HIP_TRY(ctx, e);
+  }
+  auto* t = new msm_amd_g2_tables();
+  t->n = n;
+  t->c = c;
+  t->W = W;
+  t->d_tables = d_tab;
+  ctx->live_g2_tables.push_back(t);
+  *out = t;
   return MSM_AMD_OK;
 }
 
@@ -3241,13 +3332,149 @@ extern "C" {
 
 int msm_amd_msm_g2_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars,
                           const void* d_points, size_t n, void* out192) {
-  if (int rc = g2_args(ctx, scalar_layout, g2_point_layout, d_scalars, d_points, n, out192)) return rc;
-  if (n == 0) {
+  if (int rc = g2_args(ctx, scalar_layout, g2_point_layout, d_scalars, d_points, n, out192, true)) return rc;
+  if (n == 0 && g2_point_layout != MSM_AMD_G2_POINT_TABLES) {   // (a table never holds 0 points: n mismatch below)
     g2_identity_out(out192);
     return MSM_AMD_OK;
   }
   std::lock_guard<std::mutex> lk(ctx->mu);
   return run_msm_g2(ctx, scalar_layout, g2_point_layout, d_scalars, d_points, n, out192);
+}
+
+int msm_amd_g2_bases_prepare_device(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n,
+                                    void* d_prepared) {
+  if (!ctx || !d_points || !d_prepared || n == 0 || n > 0x7FFFFFFFull)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, "bad g2_bases_prepare arguments");
+  if (msm_amd_g2_point_bytes(g2_point_layout) == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad G2 point layout");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  return prepare_bases_g2_locked(ctx, g2_point_layout, d_points, n, d_prepared);
+}
+
+int msm_amd_g2_bases_upload(msm_amd_ctx* ctx, int g2_point_layout, const void* points, size_t n, void** d_prepared) {
+  if (!ctx || !points || !d_prepared || n == 0 || n > 0x7FFFFFFFull)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, "bad g2_bases_upload arguments");
+  const size_t pb = msm_amd_g2_point_bytes(g2_point_layout);
+  if (pb == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad G2 point layout");
+  *d_prepared = nullptr;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc;
+  if ((rc = ensure(ctx, ctx->g2.in_points, n * pb))) return rc;
+  void* d_out = nullptr;
+  if (int qrc = quiesce_for_allocation(ctx, "the resident copy of the G2 bases")) return qrc;
+  HIP_TRY(ctx, hipMalloc(&d_out, n * sizeof(Aff2Packed)));
+  hipError_t e = hipMemcpy(ctx->g2.in_points.p, points, n * pb, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(d_out);
+    HIP_TRY(ctx, e);
+  }
+  if ((rc = prepare_bases_g2_locked(ctx, g2_point_layout, ctx->g2.in_points.p, n, d_out))) {
+    if (rc == MSM_AMD_PIPELINE_ERROR) ctx->graveyard.push_back(d_out);   // the conversion may still be running
+    else (void)hipFree(d_out);
+    return rc;
+  }
+  *d_prepared = d_out;
+  return MSM_AMD_OK;
+}
+
+// host scalars -> the G2 state's staging buffer, on the stream the MSM runs on (stream order does the rest)
+static int g2_stage_scalars(msm_amd_ctx* ctx, const void* scalars, size_t n) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = recover_if_stalled(ctx)) return rc;
+  if (int rc = ensure(ctx, ctx->g2.in_scalars, n * 32)) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->g2.in_scalars.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  return MSM_AMD_OK;
+}
+
+int msm_amd_msm_g2_prepared(msm_amd_ctx* ctx, int scalar_layout, const void* scalars, const void* d_prepared, size_t n,
+                            void* out192) {
+  if (!ctx || !scalars || !d_prepared || !out192 || n == 0)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, "bad msm_g2_prepared arguments");
+  if (!g2_scalar_layout_ok(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  if (int rc = g2_stage_scalars(ctx, scalars, n)) return rc;
+  return run_msm_g2(ctx, scalar_layout, MSM_AMD_G2_POINT_PREPARED, ctx->g2.in_scalars.p, d_prepared, n, out192);
+}
+
+int msm_amd_g2_tables_build_device(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n,
+                                   uint32_t window_size, msm_amd_g2_tables** out) {
+  if (!ctx || !d_points || !out || n == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad g2_tables_build arguments");
+  *out = nullptr;
+  if (msm_amd_g2_point_bytes(g2_point_layout) == 0)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, "G2 tables are built from one of the host point layouts");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  return g2_tables_build_locked(ctx, g2_point_layout, d_points, n, window_size, out);
+}
+
+int msm_amd_g2_tables_build(msm_amd_ctx* ctx, int g2_point_layout, const void* points, size_t n, uint32_t window_size,
+                            msm_amd_g2_tables** out) {
+  if (!ctx || !points || !out || n == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad g2_tables_build arguments");
+  *out = nullptr;
+  const size_t pb = msm_amd_g2_point_bytes(g2_point_layout);
+  if (pb == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "G2 tables are built from one of the host point layouts");
+  if (n > 0x7FFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, "windows * n must stay below 2^31");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = ensure(ctx, ctx->g2.in_points, n * pb)) return rc;
+  HIP_TRY(ctx, hipMemcpy(ctx->g2.in_points.p, points, n * pb, hipMemcpyHostToDevice));
+  return g2_tables_build_locked(ctx, g2_point_layout, ctx->g2.in_points.p, n, window_size, out);
+}
+
+int msm_amd_g2_tables_info(msm_amd_ctx* ctx, const msm_amd_g2_tables* tables, size_t* n, uint32_t* window_size,
+                           uint32_t* num_windows, size_t* device_bytes) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  const msm_amd_g2_tables* t = find_g2_tables(ctx, tables);
+  if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
+  if (n) *n = t->n;
+  if (window_size) *window_size = t->c;
+  if (num_windows) *num_windows = t->W;
+  if (device_bytes) *device_bytes = (size_t)t->W * t->n * sizeof(Aff2Packed);
+  return MSM_AMD_OK;
+}
+
+int msm_amd_g2_tables_free(msm_amd_ctx* ctx, msm_amd_g2_tables* tables) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  auto it = std::find(ctx->live_g2_tables.begin(), ctx->live_g2_tables.end(), tables);
+  if (it == ctx->live_g2_tables.end()) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->live_g2_tables.erase(it);
+  if (drain_or_mark_stalled(ctx)) (void)hipFree(tables->d_tables);
+  else ctx->graveyard.push_back(tables->d_tables);   // hipFree would wait for the device without bound
+  delete tables;
+  return MSM_AMD_OK;
+}
+
+int msm_amd_msm_g2_tables(msm_amd_ctx* ctx, const msm_amd_g2_tables* tables, int scalar_layout, const void* scalars,
+                          void* out192) {
+  if (!ctx || !tables || !scalars || !out192) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad msm_g2_tables arguments");
+  if (!g2_scalar_layout_ok(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  const msm_amd_g2_tables* t = find_g2_tables(ctx, tables);
+  if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
+  if (int rc = g2_stage_scalars(ctx, scalars, t->n)) return rc;
+  return run_msm_g2(ctx, scalar_layout, MSM_AMD_G2_POINT_TABLES, ctx->g2.in_scalars.p, tables, t->n, out192);
+}
+
+int msm_amd_test_g2_tables_read(msm_amd_ctx* ctx, const msm_amd_g2_tables* tables, uint32_t w, size_t first,
+                                size_t count, void* out) {
+  if (!ctx || !out || count == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad g2_tables_read arguments");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  const msm_amd_g2_tables* t = find_g2_tables(ctx, tables);
+  if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
+  if (w >= t->W || first >= t->n || count > t->n - first)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, "window or point range outside the table");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<Aff2Packed> rec(count);
+  HIP_TRY(ctx, hipMemcpyAsync(rec.data(), (const Aff2Packed*)t->d_tables + (size_t)w * t->n + first,
+                              count * sizeof(Aff2Packed), hipMemcpyDeviceToHost, ctx->stream));
+  if (int rc = sync_stream_bounded(ctx, ctx->stream, __func__)) return rc;
+  for (size_t i = 0; i < count; ++i) {
+    const Affine2 e = aff2packed_to_ext(rec[i]);
+    std::memcpy((uint8_t*)out + i * 128, &e, 128);
+  }
+  return MSM_AMD_OK;
 }
 
 int msm_amd_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points,

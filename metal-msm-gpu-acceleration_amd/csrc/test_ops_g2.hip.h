@@ -19,7 +19,9 @@ enum {
   G2RAW_PT_ADD_NZ = 4,   // a, b PtI2 (neither the identity)
   G2RAW_PT_ADD = 5,      // a, b PtI2
   G2RAW_PT_DOUBLE = 6,   // a PtI2 (not identity)
-  G2RAW_OPS = 7
+  G2RAW_FQ2_INV = 7,     // a fq2 (non-zero, < 32 p)
+  G2RAW_PT_TO_AFFINE = 8,   // a PtI2 (not identity) -> canonical affine x, y in words 0..35
+  G2RAW_OPS = 9
 };
 constexpr int kG2RawIn = 72, kG2RawOut = 80;
 
@@ -78,6 +80,13 @@ MSM_HD void run_test_op_g2(int op, const uint32_t* a, const uint32_t* b, uint32_
     case G2RAW_PT_ADD_NZ: g2raw_put_pt(out, pt2_add_nz(g2raw_pt(a), g2raw_pt(b), vanished)); break;
     case G2RAW_PT_ADD: g2raw_put_pt(out, pt2_add(g2raw_pt(a), g2raw_pt(b))); break;
     case G2RAW_PT_DOUBLE: g2raw_put_pt(out, pt2_double(g2raw_pt(a))); break;
+    case G2RAW_FQ2_INV: g2raw_put_fq2(out, Fq2::inv(g2raw_fq2(a))); break;
+    case G2RAW_PT_TO_AFFINE: {
+      const Aff2I r = pt2_to_affine(g2raw_pt(a));   // the canonical limbs aff2_pack stores
+      g2raw_put_fq2(out, fq2{Fq29::canonical(r.x.c0, 1), Fq29::canonical(r.x.c1, 1)});
+      g2raw_put_fq2(out + 18, fq2{Fq29::canonical(r.y.c0, 1), Fq29::canonical(r.y.c1, 1)});
+      break;
+    }
     default: break;
   }
   out[72] = vanished ? 1u : 0u;

@@ -2,7 +2,11 @@
 """G2 MSM timing on one ctx: one JSON line with, per size (2^16, 2^18, 2^20), the median ms of a lone blocking G2 call
 on device-resident inputs, the G1 lone call on device-resident inputs of the same size, their ratio and the G2 stage
 split from the library's HIP events (msm_amd_last_timings), plus the CPU G2 MSM at 2^16.
-Usage: python tools/g2_bench.py [--reps R] [--sizes 16,18,20] [--out FILE]"""
+Next to that per-call figure (`g2_ms`, the caller layout converted on every call), the same scalars through prepared
+bases (`prepared_ms`) and through precomputed window tables at the automatic window (`tables_ms`): median, min and max
+of each series, their stage splits, the table's window / windows / bytes and `tables_build_ms`; and one host-caller row
+at 2^20: msm_g2 (host points and scalars) against msm_g2_prepared and msm_g2_tables (host scalars only).
+Usage: python tools/g2_bench.py [--reps R] [--sizes 16,18,20] [--sweep 14,16,18] [--out FILE]"""
 import argparse
 import importlib
 import json
@@ -21,6 +25,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--sizes", default="16,18,20")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sweep", default="", help="table windows to time besides the automatic one, e.g. 14,16,18")
     args = ap.parse_args()
     import numpy as np
     import g2_ref as g
@@ -38,16 +43,56 @@ def main():
             ds, dp = cfg.alloc(len(sc)), cfg.alloc(len(pts))
             cfg.to_device(ds, sc)
             cfg.to_device(dp, pts)
-            g2, split = [], []
-            cfg.msm_g2_device(ds, dp, n, scalar_layout=1)   # warm-up (allocations)
-            for _ in range(args.reps):
-                t0 = time.perf_counter()
-                cfg.msm_g2_device(ds, dp, n, scalar_layout=1)
-                g2.append((time.perf_counter() - t0) * 1e3)
-                t = cfg.timings()
-                split.append({"convert": t.convert_ms, "digits": t.digits_ms, "sort": t.sort_ms,
-                              "accumulate_combine": t.accumulate_ms, "reduce_copy": t.reduce_ms,
-                              "host_horner": t.final_ms, "gpu_total": t.total_gpu_ms, "window": t.window_size})
+            def series(d_points, layout):
+                """lone blocking msm_g2_device calls: (ms per rep, stage split per rep)"""
+                ms, split = [], []
+                cfg.msm_g2_device(ds, d_points, n, scalar_layout=1, point_layout=layout)   # warm-up (allocations)
+                for _ in range(args.reps):
+                    t0 = time.perf_counter()
+                    cfg.msm_g2_device(ds, d_points, n, scalar_layout=1, point_layout=layout)
+                    ms.append((time.perf_counter() - t0) * 1e3)
+                    t = cfg.timings()
+                    split.append({"convert": t.convert_ms, "digits": t.digits_ms, "sort": t.sort_ms,
+                                  "accumulate_combine": t.accumulate_ms, "reduce_copy": t.reduce_ms,
+                                  "host_horner": t.final_ms, "gpu_total": t.total_gpu_ms, "window": t.window_size})
+                return ms, split
+
+            def summary(ms, split):
+                mid = sorted(range(len(ms)), key=lambda i: ms[i])[len(ms) // 2]
+                return (round(statistics.median(ms), 3), round(min(ms), 3), round(max(ms), 3),
+                        {k: (round(v, 3) if isinstance(v, float) else v) for k, v in split[mid].items()})
+
+            g2, split = series(dp, pkg.G2_POINT_H2C_AFFINE)
+            d_prep = cfg.g2_bases_prepare_device(dp, n)
+            prep, prep_split = series(d_prep, pkg.G2_POINT_PREPARED)
+            t0 = time.perf_counter()
+            tables = cfg.g2_tables_build_device(dp, n)
+            tables_build_ms = (time.perf_counter() - t0) * 1e3
+            info = cfg.g2_tables_info(tables)
+            tab, tab_split = series(tables, pkg.G2_POINT_TABLES)
+            sweep = {}
+            for c in (int(x) for x in args.sweep.split(",") if x):
+                if (254 // c + 1) * n >= 1 << 31:
+                    continue
+                tc = cfg.g2_tables_build_device(dp, n, window_size=c)
+                ms, _ = series(tc, pkg.G2_POINT_TABLES)
+                cfg.g2_tables_free(tc)
+                sweep[str(c)] = round(statistics.median(ms), 3)
+            host_row = None
+            if logn == 20:   # a host caller: points and scalars in host memory against scalars only
+                def host_series(fn):
+                    fn()
+                    ms = []
+                    for _ in range(args.reps):
+                        t0 = time.perf_counter()
+                        fn()
+                        ms.append((time.perf_counter() - t0) * 1e3)
+                    return {"median": round(statistics.median(ms), 3), "min": round(min(ms), 3), "max": round(max(ms), 3)}
+                host_row = {"msm_g2_ms": host_series(lambda: cfg.msm_g2(sc, pts, n, scalar_layout=1)),
+                            "msm_g2_prepared_ms": host_series(lambda: cfg.msm_g2_prepared(sc, d_prep, n, scalar_layout=1)),
+                            "msm_g2_tables_ms": host_series(lambda: cfg.msm_g2_tables(sc, tables, scalar_layout=1))}
+            cfg.g2_tables_free(tables)
+            cfg.free(d_prep)
             cfg.free(ds)
             cfg.free(dp)
             gp, gs = cfg.generate_instance(o.SEED_BASE, n, True)
@@ -59,10 +104,23 @@ def main():
                 g1.append((time.perf_counter() - t0) * 1e3)
             cfg.free(gp)
             cfg.free(gs)
-            mid = sorted(range(len(g2)), key=lambda i: g2[i])[len(g2) // 2]
-            entry = {"g2_ms": round(statistics.median(g2), 3), "g1_ms": round(statistics.median(g1), 3),
-                     "split_ms": {k: (round(v, 3) if isinstance(v, float) else v) for k, v in split[mid].items()}}
+            g2_med, g2_min, g2_max, g2_split = summary(g2, split)
+            entry = {"g2_ms": g2_med, "g1_ms": round(statistics.median(g1), 3), "split_ms": g2_split}
             entry["g2_over_g1"] = round(entry["g2_ms"] / entry["g1_ms"], 2)
+            entry["g2_min_ms"], entry["g2_max_ms"] = g2_min, g2_max
+            (entry["prepared_ms"], entry["prepared_min_ms"], entry["prepared_max_ms"],
+             entry["prepared_split_ms"]) = summary(prep, prep_split)
+            (entry["tables_ms"], entry["tables_min_ms"], entry["tables_max_ms"],
+             entry["tables_split_ms"]) = summary(tab, tab_split)
+            entry["tables_window"], entry["tables_windows"] = info["window_size"], info["num_windows"]
+            entry["tables_bytes"] = info["device_bytes"]
+            entry["tables_build_ms"] = round(tables_build_ms, 1)
+            entry["tables_over_g2"] = round(entry["tables_ms"] / entry["g2_ms"], 3)
+            entry["prepared_over_g2"] = round(entry["prepared_ms"] / entry["g2_ms"], 3)
+            if sweep:
+                entry["tables_sweep_ms"] = sweep
+            if host_row:
+                res["host_caller_2^20"] = host_row
             res["sizes"][f"2^{logn}"] = entry
             if logn == 16:
                 t0 = time.perf_counter()

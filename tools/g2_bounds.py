@@ -5,7 +5,10 @@ which lifted constant each subtraction uses, where X3 and the doubling are squas
 its fixed point under madd, mmadd, the full addition and the doubling, and asserts
   * every subtrahend is below the lift of its subtraction (sub<K>: b < K p; mul / sqr: b1 / a1 < 32 p),
   * every multiplication operand is below 64 p (limb 8 < 2^28 after norm(): the 64-bit column sums then hold),
-  * the zero filters' operand P stays below kG2ZeroFilter = 16 p.
+  * the zero filters' operand P stays below kG2ZeroFilter = 16 p,
+  * the inversion (Fq2::inv_fq: the square-and-multiply chain over p - 2, Fq2::inv on top of norm_fq) keeps its running
+    power a valid operand and meets the output bounds the headers state, and pt2_to_affine of any point inside the
+    invariant yields coordinates below 2 p (what Fq29::pack_canonical, one conditional subtraction, takes).
 Prints the invariant and the intermediate bounds; exit status 1 if an assertion fails."""
 import sys
 
@@ -99,6 +102,33 @@ def double(X1, Y1, ZZ1, ZZZ1):
     return X3, Y3, squash(mul(V, ZZ1)), squash(mul(W, ZZZ1))
 
 
+def fe_inv(a):            # Fq2::inv_fq: r = one; per bit of p - 2 (msb first): r = r^2, then r = r a on a set bit
+    assert a < 32, a
+    r, worst = 1.0, 1.0
+    for bit in bin(P - 2)[2:].rjust(9 * 29, "0"):   # the loop walks all 261 bit positions of the 9 limbs
+        r = 1 + RP * r * r
+        worst = max(worst, r)                       # the operand of the next multiplication / squaring
+        if bit == "1":
+            r = 1 + RP * r * a
+    assert worst < 1.02 and r < 1 + 1.02 * RP * a + 1e-12, (worst, r)
+    return r
+
+
+def fq2_inv(a):           # conj(a) / norm_fq(a): norm_fq = mul2(a0, a0, a1, a1), then two single products
+    chk(a)
+    assert max(a) < 32, a
+    n = 1 + RP * (a[0] * a[0] + a[1] * a[1])
+    ninv = fe_inv(n)
+    return (1 + RP * a[0] * ninv, 1 + RP * 32 * ninv)
+
+
+def to_affine(X, Y, ZZ, ZZZ):   # t = (ZZ ZZZ)^-1, x = (X t) ZZZ, y = (Y t) ZZ
+    t = note("affine.t", fq2_inv(note("affine.ZZ*ZZZ", mul(ZZ, ZZZ))))
+    x = mul(note("affine.Xt", mul(X, t)), ZZZ)
+    y = mul(note("affine.Yt", mul(Y, t)), ZZ)
+    return note("affine.x", x), note("affine.y", y)
+
+
 def widen(a, b):
     return tuple(tuple(max(x, y) for x, y in zip(u, v)) for u, v in zip(a, b))
 
@@ -122,6 +152,13 @@ def main():
     claimed = {"X": 1.21, "Y": 13.4, "ZZ": 3.2, "ZZZ": 2.04}
     for (name, lim), v in zip(claimed.items(), pt):
         assert max(v) < lim, (name, v, lim)
+    # the inversion at the edge of its stated input bound, and the to-affine step of the table build on any carried point
+    edge = fq2_inv((32 - 1e-9, 32 - 1e-9))
+    assert max(edge) < 1.21, edge
+    note("inv(32p)", edge)
+    x, y = to_affine(*pt)
+    assert max(x) < 1.25 and max(y) < 1.3 and max(SEEN["affine.t"]) < 1.2, (x, y)
+    assert max(SEEN["affine.ZZ*ZZZ"]) < 1.7 and max(SEEN["affine.Xt"]) < 1.24 and max(SEEN["affine.Yt"]) < 3.7
     print("invariant: " + "  ".join(f"{k} < {max(v):.3f} p" for k, v in zip(claimed, pt)))
     for k in sorted(SEEN):
         print(f"  {k:10s} < {max(SEEN[k]):.2f} p")
