@@ -514,6 +514,8 @@ enum {
   MSM_AMD_TP_TOTAL_ITEMS, MSM_AMD_TP_MULTI_COUNT, MSM_AMD_TP_DEFERRED,   /* plan counters; deferred = split buckets
                                                                             summed by combine_big_kernel */
   MSM_AMD_TP_RED_GROUP, MSM_AMD_TP_RB_THREADS, MSM_AMD_TP_INSTANCES, MSM_AMD_TP_WORKSPACE, MSM_AMD_TP_FRONT_THREADS,
+  MSM_AMD_TP_FUSED_FRONT,   /* 1: digits and the pass-1 histogram of the sort ran as one kernel (digits_hist_kernel) */
+  MSM_AMD_TP_PACKED,        /* 1: sort pass 1 wrote one packed u32 per entry (fine | index << fb | sign << 31) */
   MSM_AMD_TEST_PLAN_WORDS
 };
 /* out: count >= MSM_AMD_TEST_PLAN_WORDS words, indexed by MSM_AMD_TP_*. */

@@ -82,7 +82,7 @@ EXPORTS = [
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
 TEST_PLAN_FIELDS = ("c", "W", "W_digits", "n", "n_scalars", "lb", "nb", "CH", "hb", "mb", "fb", "Q", "tiled", "ballot",
                     "wide_digits", "lone", "total_items", "multi_count", "deferred", "red_group", "rb_threads",
-                    "instances", "workspace", "front_threads")
+                    "instances", "workspace", "front_threads", "fused_front", "packed")
 (STAGE_DIGITS, STAGE_SORTED, STAGE_BUCKET_SIZE, STAGE_BUCKET_START, STAGE_ITEM_START, STAGE_WIN_ITEMS, STAGE_ORDER,
  STAGE_MULTI_LIST, STAGE_BUCKETS, STAGE_PARTIAL) = range(10)
 

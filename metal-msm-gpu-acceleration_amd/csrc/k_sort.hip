@@ -23,17 +23,11 @@ constexpr int kSortThreads = 1024;       // hist / plan / scatter workgroup size
 // and every digit is one v_alignbit + v_and on fixed words of the scalar instead of a 16-way select chain over a
 // run-time word index (the common window sizes of the pipelined policy; 375 -> ~140 instructions per scalar).
 // C = 0: c and W from the arguments.
-template <typename D, int C = 0>
-__global__ void __launch_bounds__(256)
-digits_kernel(const u256* __restrict__ scalars, uint32_t n, uint32_t c_arg, uint32_t W_arg, int scalars_mont,
-              D* __restrict__ digits) {
-  constexpr uint32_t kSignShift = 8 * sizeof(D) - 1;
+// scalar_digits: the W signed digits of one scalar, handed to emit(w, magnitude, negative) window by window.
+template <int C, typename Emit>
+__device__ __forceinline__ void scalar_digits(u256 k, int scalars_mont, uint32_t c_arg, uint32_t W_arg, Emit emit) {
   const uint32_t c = C > 0 ? (uint32_t)C : c_arg;
   const uint32_t W = C > 0 ? (uint32_t)(254 / (C > 0 ? C : 1) + 1) : W_arg;
-  __builtin_amdgcn_s_setprio(kFrontPriority);
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n) return;
-  u256 k = load_u256(&scalars[t]);
   if (scalars_mont) {
     k = Fr::from_mont(k);
   } else {
@@ -44,7 +38,8 @@ digits_kernel(const u256* __restrict__ scalars, uint32_t n, uint32_t c_arg, uint
   }
   const uint32_t half = 1u << (c - 1);
   uint32_t carry = 0;
-#pragma unroll
+  constexpr int kUnroll = C > 0 ? 254 / (C > 0 ? C : 1) + 1 : 1;   // run-time W: rolled
+#pragma unroll kUnroll
   for (uint32_t w = 0; w < W; ++w) {
     const uint32_t start = w * c;
     uint32_t v = (start < 256 ? u256_extract_bits(k, start, c) : 0u) + carry;
@@ -55,7 +50,60 @@ digits_kernel(const u256* __restrict__ scalars, uint32_t n, uint32_t c_arg, uint
       neg = 1;
       carry = 1;
     }
+    emit(w, v, neg);
+  }
+}
+
+template <typename D, int C = 0>
+__global__ void __launch_bounds__(256)
+digits_kernel(const u256* __restrict__ scalars, uint32_t n, uint32_t c_arg, uint32_t W_arg, int scalars_mont,
+              D* __restrict__ digits) {
+  constexpr uint32_t kSignShift = 8 * sizeof(D) - 1;
+  __builtin_amdgcn_s_setprio(kFrontPriority);
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  scalar_digits<C>(load_u256(&scalars[t]), scalars_mont, c_arg, W_arg, [&](uint32_t w, uint32_t v, uint32_t neg) {
     digits[(size_t)w * n + t] = (D)(v | (neg << kSignShift));
+  });
+}
+
+// Stage 1 fused with the histogram of sort pass 1 (per-call pipeline, where the digit windows are the sort windows).
+// grid = (S, Q): chunk q of pass 1 is cut into S pieces of kDigitsSpan scalars, one 256-thread workgroup each (a grid
+// of only Q big workgroups, one per chunk, leaves most CUs without digit work: 34 workgroups at 2^20 points took
+// 1.0 ms beside an accumulate grid and set the pipeline's period).  A thread walks the scalars lo + tid, += blockDim
+// of its piece, writes their digits as digits_kernel does, and counts every non-zero magnitude into its window's
+// coarse region (LDS, W * nhi counters) while the digit is still in a register: coarse_hist_kernel's pass over the
+// digit matrix (W * n entries read back from memory) falls away.  The pieces of a chunk add their counters into
+// coarse_cnt[w][q][hi] -- the layout coarse_hist_kernel writes -- which launch_digits_hist has zeroed.
+constexpr uint32_t kDigitsThreads = 256;
+constexpr uint32_t kDigitsSpan = kDigitsThreads * 8;
+template <typename D, int C = 0>
+__global__ void __launch_bounds__(kDigitsThreads)
+digits_hist_kernel(const u256* __restrict__ scalars, uint32_t n, uint32_t c_arg, uint32_t W_arg, int scalars_mont,
+                   uint32_t fb, uint32_t nhi, uint32_t chunk, D* __restrict__ digits,
+                   uint32_t* __restrict__ coarse_cnt /* [W][Q][nhi], zero */) {
+  constexpr uint32_t kSignShift = 8 * sizeof(D) - 1;
+  const uint32_t W = C > 0 ? (uint32_t)(254 / (C > 0 ? C : 1) + 1) : W_arg;
+  __builtin_amdgcn_s_setprio(kFrontPriority);
+  extern __shared__ uint32_t lds_u32[];   // [W][nhi]
+  const uint32_t q = blockIdx.y, Q = gridDim.y;
+  const uint32_t lo = q * chunk + blockIdx.x * kDigitsSpan;
+  const uint32_t hi = min(min(n, (q + 1) * chunk), lo + kDigitsSpan);
+  if (lo >= hi) return;   // (whole workgroup)
+  for (uint32_t i = threadIdx.x; i < W * nhi; i += blockDim.x) lds_u32[i] = 0;
+  __syncthreads();
+#pragma unroll 1
+  for (uint32_t t = lo + threadIdx.x; t < hi; t += blockDim.x) {
+    scalar_digits<C>(load_u256(&scalars[t]), scalars_mont, c_arg, W_arg, [&](uint32_t w, uint32_t v, uint32_t neg) {
+      digits[(size_t)w * n + t] = (D)(v | (neg << kSignShift));
+      if (v) atomicAdd(&lds_u32[w * nhi + ((v - 1) >> fb)], 1u);
+    });
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < W * nhi; i += blockDim.x) {
+    const uint32_t w = i / nhi, r = i - w * nhi;
+    const uint32_t cnt = lds_u32[i];
+    if (cnt) atomicAdd(&coarse_cnt[((size_t)w * Q + q) * nhi + r], cnt);
   }
 }
 
@@ -69,7 +117,8 @@ digits_kernel(const u256* __restrict__ scalars, uint32_t n, uint32_t c_arg, uint
 //           every (chunk q, window w) workgroup moves its points into 2^hb coarse regions of the window.
 //           A workgroup owns one contiguous run per region (positions from returning LDS atomics on 2^hb
 //           region cursors), so its stores extend the same few lines and one L2 assembles them whole.
-//           Payload: index|sign (u32) + fine digit (u16).
+//           Payload: index|sign (u32) + fine digit (u16), or ONE u32 fine | index << fb1 | sign << 31 when the
+//           plan says the three fit (Plan::packed: tmp_fine is then neither written nor read).
 //   pass 2  fine_sort_kernel: one workgroup per (region, window) counting-sorts its ~16 k points over the
 //           2^fb fine slots entirely in LDS (histogram, scan, scatter into an LDS staging buffer) and writes
 //           the region back fully coalesced, together with the bucket sizes.  Regions larger than the staging
@@ -164,7 +213,7 @@ template <typename D, bool BALLOT>
 __global__ void __launch_bounds__(kSortThreads)
 coarse_scatter_kernel(const D* __restrict__ digits, uint32_t n, uint32_t hb, uint32_t fb, uint32_t chunk,
                       const uint32_t* __restrict__ coarse_base /* [W][Q][nhi] */, uint32_t* __restrict__ tmp_idx,
-                      uint16_t* __restrict__ tmp_fine) {
+                      uint16_t* __restrict__ tmp_fine, uint32_t packed) {
   __builtin_amdgcn_s_setprio(kFrontPriority);
   extern __shared__ uint32_t lds_u32[];   // [nhi] region cursors
   const uint32_t nhi = 1u << hb;
@@ -188,8 +237,12 @@ coarse_scatter_kernel(const D* __restrict__ digits, uint32_t n, uint32_t hb, uin
       const uint32_t slot = m - 1;
       const uint32_t pos = wave_claim(m ? slot >> fb : 0u, hb, m != 0, lds_u32);
       if (m) {
-        ti[pos] = t | ((v >> kSignShift) << 31);
-        tf[pos] = (uint16_t)(slot & fmask);
+        if (packed) {
+          ti[pos] = (slot & fmask) | (t << fb) | ((v >> kSignShift) << 31);
+        } else {
+          ti[pos] = t | ((v >> kSignShift) << 31);
+          tf[pos] = (uint16_t)(slot & fmask);
+        }
       }
     }
     return;
@@ -200,8 +253,12 @@ coarse_scatter_kernel(const D* __restrict__ digits, uint32_t n, uint32_t hb, uin
     if (m) {
       const uint32_t slot = m - 1;
       const uint32_t pos = atomicAdd(&lds_u32[slot >> fb], 1u);
-      ti[pos] = t | ((v >> kSignShift) << 31);   // bit 31: the digit is negative, add -P
-      tf[pos] = (uint16_t)(slot & fmask);
+      if (packed) {
+        ti[pos] = (slot & fmask) | (t << fb) | ((v >> kSignShift) << 31);
+      } else {
+        ti[pos] = t | ((v >> kSignShift) << 31);   // bit 31: the digit is negative, add -P
+        tf[pos] = (uint16_t)(slot & fmask);
+      }
     }
   }
 }
@@ -374,7 +431,7 @@ __device__ __forceinline__ void tile_scatter(uint32_t lo, uint32_t hi, uint32_t 
       const uint32_t r = st_reg[j];
       const uint32_t gp = gbase[r] + (j - off[r]);
       out_idx[gp] = st_idx[j];
-      out_fine[gp] = st_fine[j];
+      if (out_fine) out_fine[gp] = st_fine[j];   // nullptr: the payload carries the fine digit (Plan::packed)
     }
     __syncthreads();
   }
@@ -384,7 +441,7 @@ template <typename D>
 __global__ void __launch_bounds__(kSortThreads)
 coarse_scatter_tiled_kernel(const D* __restrict__ digits, uint32_t n, uint32_t hb, uint32_t fb, uint32_t chunk,
                             const uint32_t* __restrict__ coarse_base, uint32_t* __restrict__ tmp_idx,
-                            uint16_t* __restrict__ tmp_fine) {
+                            uint16_t* __restrict__ tmp_fine, uint32_t packed) {
   __builtin_amdgcn_s_setprio(kFrontPriority);
   extern __shared__ uint32_t lds_u32[];
   constexpr uint32_t kSignShift = 8 * sizeof(D) - 1;
@@ -400,12 +457,13 @@ coarse_scatter_tiled_kernel(const D* __restrict__ digits, uint32_t n, uint32_t h
     if (!m) return false;
     const uint32_t slot = m - 1;
     *pay = t | ((v >> kSignShift) << 31);   // bit 31: the digit is negative, add -P
+    if (packed) *pay = (slot & fmask) | (t << fb) | ((v >> kSignShift) << 31);
     *fin = slot & fmask;
     *reg = slot >> fb;
     return true;
   };
   tile_scatter(lo, hi, nhi, hb, load, coarse_base + ((size_t)w * Q + q) * nhi, tmp_idx + (size_t)w * n,
-               tmp_fine + (size_t)w * n, lds_u32);
+               packed ? nullptr : tmp_fine + (size_t)w * n, lds_u32);
 }
 
 __global__ void __launch_bounds__(kSortThreads)
@@ -437,7 +495,8 @@ mid_scatter_tiled_kernel(const uint32_t* __restrict__ tmp_idx, const uint16_t* _
 // grid = (nhi, W), block = 1024, dynamic LDS = (kFineCap + 2 * nfine + 32) * 4 bytes.
 // Loops are kept rolled (<= 32 VGPRs): the 4 waves/SIMD of a 1024-thread workgroup must fit into the 128
 // VGPRs that two resident accumulate waves leave free on a SIMD, or the workgroup waits for the accumulate tail.
-template <bool BALLOT>
+// PACKED: tmp_idx entries are fine | index << fb | sign << 31 (Plan::packed) and tmp_fine is not read.
+template <bool BALLOT, bool PACKED>
 __global__ void __launch_bounds__(kSortThreads)
 fine_sort_kernel(const uint32_t* __restrict__ tmp_idx, const uint16_t* __restrict__ tmp_fine, uint32_t n,
                  uint32_t lb, uint32_t fb, const uint32_t* __restrict__ region_start,
@@ -456,10 +515,14 @@ fine_sort_kernel(const uint32_t* __restrict__ tmp_idx, const uint16_t* __restric
   const uint32_t* ti = tmp_idx + (size_t)w * n + rs;
   const uint16_t* tf = tmp_fine + (size_t)w * n + rs;
   uint32_t* out = sorted + (size_t)w * n + rs;
+  const uint32_t fmask = nfine - 1u;
+  // entry i of the region: its fine digit, and the index | sign << 31 that `sorted` holds
+  auto fine_of = [&](uint32_t i) { return PACKED ? (ti[i] & fmask) : (uint32_t)tf[i]; };
+  auto unpack = [&](uint32_t v) { return PACKED ? ((v & 0x80000000u) | ((v & 0x7FFFFFFFu) >> fb)) : v; };
   for (uint32_t i = threadIdx.x; i < nfine; i += blockDim.x) bins[i] = 0;
   __syncthreads();
 #pragma unroll 1
-  for (uint32_t i = threadIdx.x; i < size; i += blockDim.x) atomicAdd(&bins[tf[i]], 1u);
+  for (uint32_t i = threadIdx.x; i < size; i += blockDim.x) atomicAdd(&bins[fine_of(i)], 1u);
   __syncthreads();
   // exclusive scan of the fine histogram (nfine <= 1024: one bin per thread)
   const uint32_t cnt = (threadIdx.x < nfine) ? bins[threadIdx.x] : 0u;
@@ -477,24 +540,28 @@ fine_sort_kernel(const uint32_t* __restrict__ tmp_idx, const uint16_t* __restric
       for (uint32_t i0 = 0; i0 < size; i0 += blockDim.x) {
         const uint32_t i = i0 + threadIdx.x;
         const bool valid = i < size;
-        const uint32_t pos = wave_claim(valid ? (uint32_t)tf[i] : 0u, fb, valid, bins);
-        if (valid) staging[pos] = ti[i];
+        const uint32_t v = (PACKED && valid) ? ti[i] : 0u;
+        const uint32_t f = PACKED ? (v & fmask) : (valid ? (uint32_t)tf[i] : 0u);
+        const uint32_t pos = wave_claim(f, fb, valid, bins);
+        if (valid) staging[pos] = PACKED ? unpack(v) : ti[i];
       }
     } else {
 #pragma unroll 1
       for (uint32_t i = threadIdx.x; i < size; i += blockDim.x) {
-        const uint32_t pos = atomicAdd(&bins[tf[i]], 1u);
-        staging[pos] = ti[i];
+        const uint32_t v = ti[i];
+        const uint32_t pos = atomicAdd(&bins[PACKED ? (v & fmask) : (uint32_t)tf[i]], 1u);
+        staging[pos] = unpack(v);
       }
     }
     __syncthreads();
-  #pragma unroll 1
-  for (uint32_t i = threadIdx.x; i < size; i += blockDim.x) out[i] = staging[i];
+#pragma unroll 1
+    for (uint32_t i = threadIdx.x; i < size; i += blockDim.x) out[i] = staging[i];
   } else {
-  #pragma unroll 1
-  for (uint32_t i = threadIdx.x; i < size; i += blockDim.x) {
-      const uint32_t pos = atomicAdd(&bins[tf[i]], 1u);
-      out[pos] = ti[i];
+#pragma unroll 1
+    for (uint32_t i = threadIdx.x; i < size; i += blockDim.x) {
+      const uint32_t v = ti[i];
+      const uint32_t pos = atomicAdd(&bins[PACKED ? (v & fmask) : (uint32_t)tf[i]], 1u);
+      out[pos] = unpack(v);
     }
   }
 }
@@ -768,8 +835,10 @@ int sort_set_attributes(const char** failed) {
       {(const void*)coarse_scatter_tiled_kernel<uint16_t>, "coarse_scatter_tiled_kernel<u16>"},
       {(const void*)coarse_scatter_tiled_kernel<uint32_t>, "coarse_scatter_tiled_kernel<u32>"},
       {(const void*)mid_scatter_tiled_kernel, "mid_scatter_tiled_kernel"},
-      {(const void*)fine_sort_kernel<false>, "fine_sort_kernel"},
-      {(const void*)fine_sort_kernel<true>, "fine_sort_kernel<ballot>"}};
+      {(const void*)fine_sort_kernel<false, false>, "fine_sort_kernel"},
+      {(const void*)fine_sort_kernel<true, false>, "fine_sort_kernel<ballot>"},
+      {(const void*)fine_sort_kernel<false, true>, "fine_sort_kernel<packed>"},
+      {(const void*)fine_sort_kernel<true, true>, "fine_sort_kernel<ballot, packed>"}};
   for (auto& k : ks) {
     if (hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds) != hipSuccess) {
       (void)hipGetLastError();
@@ -800,10 +869,32 @@ void launch_digits(hipStream_t st, const Plan& p, const u256* scalars, int scala
                        (uint16_t*)digits);
 }
 
-void launch_sort(hipStream_t st, const Plan& p, const SortBuffers& b) {
+void launch_digits_hist(hipStream_t st, const Plan& p, const u256* scalars, int scalars_mont, const SortBuffers& b) {
+  const uint32_t nhi = 1u << p.hb;
+  const uint32_t fb1 = p.mb + p.fb;
+  const dim3 grid((p.chunk + kDigitsSpan - 1) / kDigitsSpan, p.Q), block(kDigitsThreads);
+  const size_t lds = (size_t)p.W * nhi * 4;
+  (void)hipMemsetAsync(b.coarse_cnt, 0, (size_t)p.W * p.Q * nhi * sizeof(uint32_t), st);   // the pieces of a chunk add up
+#define LAUNCH_DIGITS_HIST_C(D, CC)                                                                                 \
+  hipLaunchKernelGGL((digits_hist_kernel<D, CC>), grid, block, lds, st, scalars, p.n_scalars, p.c, p.W_digits,       \
+                     scalars_mont, fb1, nhi, p.chunk, (D*)b.digits, b.coarse_cnt)
+  if (p.W_digits == 254 / p.c + 1) {   // (always so; the specialisations compute W from C)
+    if (p.wide_digits && p.c == 17) { LAUNCH_DIGITS_HIST_C(uint32_t, 17); return; }
+    if (p.wide_digits && p.c == 16) { LAUNCH_DIGITS_HIST_C(uint32_t, 16); return; }
+    if (!p.wide_digits && p.c == 15) { LAUNCH_DIGITS_HIST_C(uint16_t, 15); return; }
+    if (!p.wide_digits && p.c == 13) { LAUNCH_DIGITS_HIST_C(uint16_t, 13); return; }
+  }
+  if (p.wide_digits) LAUNCH_DIGITS_HIST_C(uint32_t, 0); else LAUNCH_DIGITS_HIST_C(uint16_t, 0);
+#undef LAUNCH_DIGITS_HIST_C
+}
+
+void launch_sort(hipStream_t st, const Plan& p, const SortBuffers& b, bool have_hist) {
   const uint32_t nhi = 1u << p.hb, nmid = 1u << p.mb, nfine = 1u << p.fb;
-  const uint32_t fb1 = p.mb + p.fb;   // bits of the slot that pass 1 leaves in tmp_fine
-  if (p.wide_digits)
+  const uint32_t fb1 = p.mb + p.fb;   // bits of the slot that pass 1 leaves in tmp_fine (or in the packed payload)
+  const uint32_t packed = p.packed ? 1u : 0u;
+  if (have_hist) {
+    // launch_digits_hist has filled coarse_cnt
+  } else if (p.wide_digits)
     hipLaunchKernelGGL(coarse_hist_kernel<uint32_t>, dim3(p.Q, p.W), dim3(p.front_threads), nhi * 4, st,
                        (const uint32_t*)b.digits, p.n, fb1, nhi, p.chunk, b.coarse_cnt);
   else
@@ -813,18 +904,19 @@ void launch_sort(hipStream_t st, const Plan& p, const SortBuffers& b) {
   // ranking: bit 0 of p.ballot = coarse / middle scatter passes, bit 1 = pass 2 (see wave_claim)
   const bool bc = (p.ballot & 1u) != 0, bf = (p.ballot & 2u) != 0;
 #define LAUNCH_COARSE_SCATTER(D, B)                                                                                 \
-  hipLaunchKernelGGL((coarse_scatter_kernel<D, B>), dim3(p.Q, p.W), dim3(p.front_threads), nhi * 4, st,             \
-                     (const D*)b.digits, p.n, p.hb, fb1, p.chunk, (const uint32_t*)b.coarse_cnt, b.tmp_idx, b.tmp_fine)
+  hipLaunchKernelGGL((coarse_scatter_kernel<D, B>), dim3(p.Q, p.W), dim3(p.front_threads), nhi * 4, st,              \
+                     (const D*)b.digits, p.n, p.hb, fb1, p.chunk, (const uint32_t*)b.coarse_cnt, b.tmp_idx, b.tmp_fine, \
+                     packed)
   const bool tiled = p.tiled && p.front_threads == kSortThreads && nhi <= kTileMaxRegions && nmid <= kTileMaxRegions;
   if (tiled) {
     if (p.wide_digits)
       hipLaunchKernelGGL(coarse_scatter_tiled_kernel<uint32_t>, dim3(p.Q, p.W), dim3(p.tile_threads), kTileLdsBytes, st,
                          (const uint32_t*)b.digits, p.n, p.hb, fb1, p.chunk, (const uint32_t*)b.coarse_cnt, b.tmp_idx,
-                         b.tmp_fine);
+                         b.tmp_fine, packed);
     else
       hipLaunchKernelGGL(coarse_scatter_tiled_kernel<uint16_t>, dim3(p.Q, p.W), dim3(p.tile_threads), kTileLdsBytes, st,
                          (const uint16_t*)b.digits, p.n, p.hb, fb1, p.chunk, (const uint32_t*)b.coarse_cnt, b.tmp_idx,
-                         b.tmp_fine);
+                         b.tmp_fine, packed);
   } else if (p.wide_digits) {
     if (bc) LAUNCH_COARSE_SCATTER(uint32_t, true); else LAUNCH_COARSE_SCATTER(uint32_t, false);
   } else {
@@ -857,14 +949,16 @@ void launch_sort(hipStream_t st, const Plan& p, const SortBuffers& b) {
     fine_regions = b.region_start2;
     fine_nhi = nhi * nmid;
   }
-  if (bf)
-    hipLaunchKernelGGL(fine_sort_kernel<true>, dim3(fine_nhi, p.W), dim3(std::max(p.front_threads, nfine)),
-                       (kFineCap + nfine + 32) * 4, st, fine_idx, fine_fine, p.n, p.lb, p.fb, fine_regions, b.sorted,
-                       b.bucket_size);
-  else
-    hipLaunchKernelGGL(fine_sort_kernel<false>, dim3(fine_nhi, p.W), dim3(std::max(p.front_threads, nfine)),
-                       (kFineCap + nfine + 32) * 4, st, fine_idx, fine_fine, p.n, p.lb, p.fb, fine_regions, b.sorted,
-                       b.bucket_size);
+#define LAUNCH_FINE_SORT(B, PK)                                                                                     \
+  hipLaunchKernelGGL((fine_sort_kernel<B, PK>), dim3(fine_nhi, p.W), dim3(std::max(p.front_threads, nfine)),         \
+                     (kFineCap + nfine + 32) * 4, st, fine_idx, fine_fine, p.n, p.lb, p.fb, fine_regions, b.sorted,  \
+                     b.bucket_size)
+  if (packed) {   // (two-level sorts only: fb1 = fb)
+    if (bf) LAUNCH_FINE_SORT(true, true); else LAUNCH_FINE_SORT(false, true);
+  } else {
+    if (bf) LAUNCH_FINE_SORT(true, false); else LAUNCH_FINE_SORT(false, false);
+  }
+#undef LAUNCH_FINE_SORT
   const unsigned tiles = (unsigned)((p.nb + kPlanTile - 1) / kPlanTile);
   if (tiles > 1)
     hipLaunchKernelGGL(plan_tile_sums_kernel, dim3(tiles, p.W), dim3(p.front_threads), 0, st,

@@ -26,6 +26,10 @@ struct Plan {
   uint32_t tiled;             // sort: coarse / middle scatter stage a tile in LDS and write whole runs (tile_scatter)
   uint32_t ballot;            // sort ranking: bit 0 coarse / middle passes, bit 1 pass 2 use the wave multisplit
   uint32_t front_threads;     // workgroup size of the sort / planning kernels (256..1024)
+  bool fused_front;           // digits and the histogram of sort pass 1 run as one kernel (launch_digits_hist): the
+                              // digit windows are the sort windows (per-call pipeline, not the table pipeline)
+  bool packed;                // sort pass 1 writes ONE u32 per entry, fine | index << fb | sign << 31, and tmp_fine is
+                              // not used: two-level sorts (mb = 0) with bits(n - 1) + 1 + fb <= 32
   uint32_t CH;                // accumulate: max points per work item (bucket chunk)
   uint32_t red_L, red_H;      // reduce: column / row bits of the slot index (L = ceil(lb / 2), H = lb - L)
   uint32_t rb_threads;        // reduce: threads per bit-subset sum (0 = by the sum's length; 64 for pipelined instances)
@@ -45,7 +49,8 @@ struct SortBuffers {
   uint32_t* coarse_cnt;       // [W][Q][2^hb]  per-chunk region counts, then write positions
   uint32_t* region_start;     // [W][2^hb + 1]
   uint32_t* tmp_idx;          // [W][n]        pass-1 output: index | sign << 31, grouped by coarse region
-  uint16_t* tmp_fine;         // [W][n]        pass-1 output: fine digit
+                              //               (Plan::packed: fine | index << fb | sign << 31)
+  uint16_t* tmp_fine;         // [W][n]        pass-1 output: fine digit (unused when Plan::packed)
   uint32_t* tmp_idx2;         // [W][n]        middle-pass output (three-level sort only)
   uint16_t* tmp_fine2;        // [W][n]
   uint32_t* mid_cnt;          // [W * 2^hb][Q2][2^mb]
@@ -67,7 +72,11 @@ struct SortBuffers {
 int sort_set_attributes(const char** failed);
 void launch_build_tables(hipStream_t st, const Affine* in, uint32_t n, uint32_t c, uint32_t W, AffPacked* tables);
 void launch_digits(hipStream_t st, const Plan& p, const u256* scalars, int scalars_mont, void* digits);
-void launch_sort(hipStream_t st, const Plan& p, const SortBuffers& b);
+// digits + the per-chunk region counts of sort pass 1 in one kernel (Plan::fused_front; zeroes b.coarse_cnt first);
+// follow it with launch_sort(..., have_hist = true)
+void launch_digits_hist(hipStream_t st, const Plan& p, const u256* scalars, int scalars_mont, const SortBuffers& b);
+// have_hist: b.coarse_cnt already holds the counts (launch_digits_hist); otherwise coarse_hist_kernel counts the digits
+void launch_sort(hipStream_t st, const Plan& p, const SortBuffers& b, bool have_hist = false);
 void launch_be32_to_le(hipStream_t st, const uint32_t* in, size_t words, uint32_t* out);
 void launch_ark_affine_to_affine(hipStream_t st, const uint8_t* in, uint32_t n, Affine* out);
 

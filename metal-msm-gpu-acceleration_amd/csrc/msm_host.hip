@@ -547,6 +547,10 @@ Plan make_plan(size_t n_scalars, uint32_t c, uint32_t windows = 0) {
   }
   p.ballot = kDefaultBallot;
   if (const char* e = std::getenv("MSM_AMD_BALLOT")) p.ballot = (uint32_t)std::atoi(e) & 3u;
+  // front-end traffic: digits_hist_kernel counts the digits it has just made, and where index, sign and fine digit
+  // fit one u32 (headline: 20 + 1 + 10 bits) pass 1 hands pass 2 one array instead of two (k_sort.hip)
+  p.fused_front = windows == 0;
+  p.packed = p.mb == 0 && n >= 1 && floor_log2(std::max<size_t>(n - 1, 1)) + 1 + 1 + p.fb <= 32;
   p.Q2 = 1;
   if (p.mb) {
     const uint32_t regions = p.W << p.hb;
@@ -903,9 +907,9 @@ int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_l
   if (!prepared && !wide)   // external 8 x u32 -> packed internal domain
     launch_convert_bases(fs, pts, p.n, fill ? fill : (AffPacked*)w.bases29.p);
   HIP_TRY(ctx, hipEventRecord(slot.ev[EV_CONVERT], fs));
-  launch_digits(fs, p, sc, sc_mont, sb.digits);
+  if (p.fused_front) launch_digits_hist(fs, p, sc, sc_mont, sb); else launch_digits(fs, p, sc, sc_mont, sb.digits);
   HIP_TRY(ctx, hipEventRecord(slot.ev[EV_DIGITS], fs));
-  launch_sort(fs, p, sb);
+  launch_sort(fs, p, sb, p.fused_front);
   HIP_TRY(ctx, hipEventRecord(slot.ev[EV_SORT], fs));
   // the bucket matrix is NOT cleared: a bucket without points gets no work item and is never written; the window
   // reduction reads bucket_size and takes such a slot as the identity (the reference relies on Metal's zero-filled
@@ -2987,6 +2991,8 @@ int msm_amd_test_last_plan(msm_amd_ctx* ctx, uint32_t j, uint32_t* out, size_t c
   v[MSM_AMD_TP_INSTANCES] = (uint32_t)B->n_inst;
   v[MSM_AMD_TP_WORKSPACE] = (uint32_t)B->ws_index[j];
   v[MSM_AMD_TP_FRONT_THREADS] = p.front_threads;
+  v[MSM_AMD_TP_FUSED_FRONT] = p.fused_front ? 1u : 0u;
+  v[MSM_AMD_TP_PACKED] = p.packed ? 1u : 0u;
   std::memcpy(out, v, sizeof v);
   return MSM_AMD_OK;
 }
@@ -3199,9 +3205,9 @@ int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const v
     launch_convert_bases_g2(st, d_points, g2_point_layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n,
                             (Aff2Packed*)g.bases.p);
   HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_CONVERT], st));
-  launch_digits(st, p, sc, sc_mont, sb.digits);
+  if (p.fused_front) launch_digits_hist(st, p, sc, sc_mont, sb); else launch_digits(st, p, sc, sc_mont, sb.digits);
   HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_DIGITS], st));
-  launch_sort(st, p, sb);
+  launch_sort(st, p, sb, p.fused_front);
   HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_SORT], st));
   // the bucket matrix is not cleared: the window reduction reads bucket_size (see enqueue_msm)
   launch_accumulate_g2(st, p, bases, sb, (PtI2*)g.buckets.p, (PtI2*)g.item_partials.p);
