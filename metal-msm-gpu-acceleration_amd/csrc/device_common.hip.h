@@ -27,6 +27,11 @@
 //                         Jacobian): window value = total + sum_k 2^k CB_k + 2^L sum_k 2^k RB_k
 //   host                  Horner over the bit positions of the (lb + 1) * W partial points (msm_host.hip host_combine)
 //
+// The bodies of combine_small/big, sum_groups and reduce_bits and the host planner of the reduction levels are
+// templates over the point type (point_stages.hip.h): these G1 kernels and the *_g2_kernel twins of k_g2.hip are thin
+// wrappers around them.  The G2 MSM (k_g2.hip) shares the whole front stream and has its own base conversion, table
+// build and accumulate kernel.
+//
 // This replaces the reference's prepare_buckets_indices / sort_buckets (CPU rayon sort!) /
 // bucket_wise_accumulation / sum_reduction_partial+final kernels (src/metal/shader/msm.h.metal:17-562,
 // src/metal/msm/sort_buckets.rs:15-34) with a design derived for wave64 + 160 KB LDS + eight non-coherent L2s:

@@ -2,6 +2,7 @@
 // See device_common.hip.h for the pipeline overview.
 #include "device_common.hip.h"
 #include "launch.h"
+#include "point_stages.hip.h"
 
 namespace msm_amd {
 
@@ -160,35 +161,14 @@ __global__ void __launch_bounds__(64) accumulate_kernel(MSM_ACC_PARAMS) {
 #include "experiments/k_accumulate_variants.inc"
 #endif
 
-// Buckets that were split into several items (only skewed digit distributions produce them: equal scalars,
-// the narrow top window of small window sizes).  Two passes over multi_list:
-//   combine_small_kernel  one lane per listed bucket; sums up to kSerialItems partials serially, defers
-//                         larger buckets to big_list
-//   combine_big_kernel    one 64-lane workgroup per deferred bucket (grid-stride): strided partial sums +
-//                         6-level LDS tree
-constexpr uint32_t kSerialItems = 8;
-
+// The combine pass for split buckets (bodies shared with G2: point_stages.hip.h).
 __global__ void __launch_bounds__(64)
 combine_small_kernel(const uint32_t* __restrict__ multi_list, PlanCounters* __restrict__ counters,
                      const uint32_t* __restrict__ bucket_size, const uint32_t* __restrict__ item_start,
                      const uint32_t* __restrict__ win_base, uint32_t lb, uint32_t CH,
                      const PtI* __restrict__ partials, PtI* __restrict__ buckets, uint32_t* __restrict__ big_list) {
-  // the grid covers every possible split bucket (one lane each, launch_combine): no grid-stride loop, fewer live
-  // registers (164 VGPRs)
-  const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
-  if (m >= counters->multi_count) return;
-  const uint32_t b = multi_list[m];
-  const uint32_t nitems = (bucket_size[b] + CH - 1) / CH;
-  if (nitems > kSerialItems) {
-    big_list[atomicAdd(&counters->pad[0], 1u)] = b;   // pad[0] = number of deferred buckets
-    return;
-  }
-  const PtI* src = partials + (size_t)win_base[b >> lb] + item_start[b];
-  const PtI* const end = src + nitems;
-  PtI acc = load_pti(src);
-#pragma unroll 1
-  for (++src; src != end; ++src) acc = pti_add(acc, load_pti(src));
-  store_pti(&buckets[multi_list[m]], acc);   // b is re-read: one live register less across the loop
+  combine_small_body<G1Stages>(multi_list, counters, bucket_size, item_start, win_base, lb, CH, partials, buckets,
+                               big_list);
 }
 
 __global__ void __launch_bounds__(64)
@@ -197,28 +177,7 @@ combine_big_kernel(const uint32_t* __restrict__ big_list, const PlanCounters* __
                    const uint32_t* __restrict__ win_base, uint32_t lb, uint32_t CH,
                    const PtI* __restrict__ partials, PtI* __restrict__ buckets) {
   __shared__ PtI sh[64];
-  const uint32_t count = counters->pad[0];
-  for (uint32_t m = blockIdx.x; m < count; m += gridDim.x) {
-    const uint32_t b = big_list[m];
-    const uint32_t nitems = (bucket_size[b] + CH - 1) / CH;
-    const PtI* src = partials + (size_t)win_base[b >> lb] + item_start[b];
-    PtI acc = pti_identity();
-#pragma unroll 1
-    for (uint32_t i = threadIdx.x; i < nitems; i += 64) acc = pti_add(acc, load_pti(&src[i]));
-    store_pti(&sh[threadIdx.x], acc);
-    __syncthreads();
-#pragma unroll 1
-    for (uint32_t stride = 32; stride >= 1; stride >>= 1) {
-      if (threadIdx.x < stride) {
-        const PtI x = load_pti(&sh[threadIdx.x]);
-        const PtI y = load_pti(&sh[threadIdx.x + stride]);
-        store_pti(&sh[threadIdx.x], pti_add(x, y));
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) store_pti(&buckets[b], load_pti(&sh[0]));
-    __syncthreads();
-  }
+  combine_big_body<G1Stages>(sh, big_list, counters, bucket_size, item_start, win_base, lb, CH, partials, buckets);
 }
 
 // variant: 0 = three waves per SIMD (no prefetch), 1 = two waves per SIMD (register pin, prefetch), 2 = register-lean
@@ -277,18 +236,8 @@ void launch_accumulate(hipStream_t st, const Plan& p, const void* bases_any, int
   if (after_kernel) (void)hipEventRecord(after_kernel, st);
 }
 
-// Sums the partial results of split buckets (no-op launches when nothing was split).
 void launch_combine(hipStream_t st, const Plan& p, const SortBuffers& b, PtI* buckets, PtI* partials) {
-  // multi_list doubles as big_list storage: its second half (entries max_items/2 ..) is free because a split
-  // bucket accounts for at least two items
-  uint32_t* big_list = b.multi_list + p.max_items / 2 + 1;
-  // one lane per possibly-split bucket: at most one split bucket per two items
-  hipLaunchKernelGGL(combine_small_kernel, dim3((unsigned)((p.max_items / 2 + 63) / 64)), dim3(64), 0, st, (const uint32_t*)b.multi_list, b.counters,
-                     (const uint32_t*)b.bucket_size, (const uint32_t*)b.item_start, (const uint32_t*)b.win_items, p.lb,
-                     p.CH, (const PtI*)partials, buckets, big_list);
-  hipLaunchKernelGGL(combine_big_kernel, dim3(512), dim3(64), 0, st, (const uint32_t*)big_list,
-                     (const PlanCounters*)b.counters, (const uint32_t*)b.bucket_size, (const uint32_t*)b.item_start,
-                     (const uint32_t*)b.win_items, p.lb, p.CH, (const PtI*)partials, buckets);
+  launch_combine_pair(st, p, b, buckets, partials, combine_small_kernel, combine_big_kernel);
 }
 
 }  // namespace msm_amd

@@ -160,19 +160,16 @@ struct Batch {
 
 // Precomputed window tables of one set of bases (msm_amd_tables_*): tables[w * n + i] = 2^(c w) P_i, packed form.
 // Handles are validated by membership in msm_amd_ctx::live_tables, never by dereferencing the caller's pointer.
-struct msm_amd_tables {
+struct TablesRecord {
   size_t n = 0;
   uint32_t c = 0, W = 0;
-  void* d_tables = nullptr;   // W * n AffPacked
+  void* d_tables = nullptr;   // W * n AffPacked (G1) or Aff2Packed (G2)
 };
+struct msm_amd_tables : TablesRecord {};
 
-// The same for G2 (msm_amd_g2_tables_*): W * n Aff2Packed; validated by membership in msm_amd_ctx::live_g2_tables, so
+// The same record for G2 (msm_amd_g2_tables_*), as a type and a live list (msm_amd_ctx::live_g2_tables) of its own, so
 // that a G1 handle is no G2 handle and the reverse.
-struct msm_amd_g2_tables {
-  size_t n = 0;
-  uint32_t c = 0, W = 0;
-  void* d_tables = nullptr;
-};
+struct msm_amd_g2_tables : TablesRecord {};
 
 // Buffers of the G2 MSM (msm_amd_msm_g2*): one blocking call at a time on the main stream.  `ws` holds the scalar
 // front end's buffers (digits, sort, work items, scalar conversion) -- its own, so a G2 call never touches what a G1
@@ -773,10 +770,125 @@ int enqueue_reduce(msm_amd_ctx* ctx, Workspace& w, hipStream_t st, const Plan& p
   return MSM_AMD_OK;
 }
 
-const msm_amd_tables* find_tables(const msm_amd_ctx* ctx, const void* handle) {
-  for (const msm_amd_tables* t : ctx->live_tables)
+// ---- table handles, G1 and G2: H = msm_amd_tables (ctx->live_tables) or msm_amd_g2_tables (ctx->live_g2_tables) ----
+template <class H>
+const H* find_tables(const std::vector<H*>& live, const void* handle) {
+  for (const H* t : live)
     if ((const void*)t == handle) return t;
   return nullptr;
+}
+
+// window_size 0 = `auto_c`; the window and the number of windows of a table over n points
+int tables_geometry(msm_amd_ctx* ctx, size_t n, uint32_t window_size, uint32_t auto_c, uint32_t* c, uint32_t* W) {
+  *c = window_size ? window_size : auto_c;
+  if (*c < 4 || *c > 21) return fail(ctx, MSM_AMD_INPUT_ERROR, "table window_size must be 0 (auto) or 4..21");
+  *W = kModulusBits / *c + 1;
+  if ((size_t)*W * n > 0x7FFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, "windows * n must stay below 2^31");
+  return MSM_AMD_OK;
+}
+
+// The tail of a table build: room for W * n records of record_bytes, the build kernel (`launch(d_tables)` on
+// ctx->stream), a bounded wait and the new handle in `live`.  `what` names the group in messages ("" or "G2 ").
+template <class H, class Launch>
+int tables_build_tail(msm_amd_ctx* ctx, std::vector<H*>& live, size_t n, uint32_t c, uint32_t W, size_t record_bytes,
+                      const std::string& what, Launch&& launch, H** out) {
+  void* d_tab = nullptr;
+  if (int qrc = quiesce_for_allocation(ctx, ("the " + what + "window tables").c_str())) return qrc;
+  HIP_TRY(ctx, hipMalloc(&d_tab, (size_t)W * n * record_bytes));
+  launch(d_tab);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && sync_stream_bounded(ctx, ctx->stream, (what + "table build").c_str())) {
+    ctx->graveyard.push_back(d_tab);   // the build may still be running: released when the ctx is idle
+    return MSM_AMD_PIPELINE_ERROR;
+  }
+  if (e != hipSuccess) {
+    (void)hipFree(d_tab);
+    HIP_TRY(ctx, e);
+  }
+  H* t = new H();
+  t->n = n;
+  t->c = c;
+  t->W = W;
+  t->d_tables = d_tab;
+  live.push_back(t);
+  *out = t;
+  return MSM_AMD_OK;
+}
+
+// ctx->mu held by the caller, as for every helper here
+template <class H>
+int tables_info(msm_amd_ctx* ctx, const std::vector<H*>& live, const H* tables, size_t record_bytes,
+                const char* not_a_handle, size_t* n, uint32_t* window_size, uint32_t* num_windows,
+                size_t* device_bytes) {
+  const H* t = find_tables(live, tables);
+  if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, not_a_handle);
+  if (n) *n = t->n;
+  if (window_size) *window_size = t->c;
+  if (num_windows) *num_windows = t->W;
+  if (device_bytes) *device_bytes = (size_t)t->W * t->n * record_bytes;
+  return MSM_AMD_OK;
+}
+
+template <class H>
+int tables_free(msm_amd_ctx* ctx, std::vector<H*>& live, H* tables, const char* not_a_handle) {
+  auto it = std::find(live.begin(), live.end(), tables);
+  if (it == live.end()) return fail(ctx, MSM_AMD_INPUT_ERROR, not_a_handle);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  live.erase(it);
+  if (drain_or_mark_stalled(ctx)) (void)hipFree(tables->d_tables);
+  else ctx->graveyard.push_back(tables->d_tables);   // hipFree would wait for the device without bound
+  delete tables;
+  return MSM_AMD_OK;
+}
+
+// msm_amd_destroy: tables the caller did not free
+template <class H>
+void tables_release_all(std::vector<H*>& live) {
+  for (H* t : live) {
+    (void)hipFree(t->d_tables);
+    delete t;
+  }
+  live.clear();
+}
+
+// Host points -> `stage` (device scratch) -> a fresh device array of out_bytes that `convert(staged, d_out)` fills and
+// waits for with the ctx's bound (prepare_bases_locked and its G2 twin); *d_prepared receives the array.
+template <class Convert>
+int upload_and_prepare(msm_amd_ctx* ctx, DeviceBuf& stage, const void* points, size_t in_bytes, size_t out_bytes,
+                       const char* what, Convert&& convert, void** d_prepared) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = ensure(ctx, stage, in_bytes)) return rc;
+  void* d_out = nullptr;
+  if (int qrc = quiesce_for_allocation(ctx, what)) return qrc;
+  HIP_TRY(ctx, hipMalloc(&d_out, out_bytes));
+  hipError_t e = hipMemcpy(stage.p, points, in_bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(d_out);
+    HIP_TRY(ctx, e);
+  }
+  if (int rc = convert(stage.p, d_out)) {
+    // a bounded wait that timed out: the conversion may still be running, and hipFree would wait for the device
+    // without bound -- released when the ctx is idle
+    if (rc == MSM_AMD_PIPELINE_ERROR) ctx->graveyard.push_back(d_out);
+    else (void)hipFree(d_out);
+    return rc;
+  }
+  *d_prepared = d_out;
+  return MSM_AMD_OK;
+}
+
+bool scalar_layout_ok(int scalar_layout) {
+  return scalar_layout >= MSM_AMD_SCALAR_MONT_LE && scalar_layout <= MSM_AMD_SCALAR_CANON_BE32;
+}
+
+// ms between two recorded events (0 if either cannot be read)
+float event_span(hipEvent_t a, hipEvent_t b) {
+  float t = 0;
+  if (hipEventElapsedTime(&t, a, b) != hipSuccess) {
+    (void)hipGetLastError();
+    t = 0;
+  }
+  return t;
 }
 
 // Row / column sums of the window reduction for a LONE call: with no neighbouring instance to fill the machine, the
@@ -789,13 +901,62 @@ uint32_t pick_reduce_group(const Plan&) {
   return kReduceGroupMin;
 }
 
+// The buffers of the scalar front end (digits, sort, work-item planning) of one MSM in workspace w, grown to plan p,
+// and the SortBuffers that name them (redo_list stays null: experiments only, see enqueue_msm).  p.n = sorted entries
+// per window (the points, or W_digits * points with tables).
+int front_buffers(msm_amd_ctx* ctx, Workspace& w, const Plan& p, SortBuffers* sb) {
+  int rc;
+  if ((rc = ensure(ctx, w.digits, (size_t)p.W * p.n * (p.wide_digits ? sizeof(uint32_t) : sizeof(uint16_t))))) return rc;
+  if ((rc = ensure(ctx, w.coarse_cnt, (size_t)p.W * p.Q * (1u << p.hb) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.region_start, (size_t)p.W * ((1u << p.hb) + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.tmp_idx, (size_t)p.W * p.n * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.tmp_fine, (size_t)p.W * p.n * sizeof(uint16_t)))) return rc;
+  if (p.mb) {
+    if ((rc = ensure(ctx, w.tmp_idx2, (size_t)p.W * p.n * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(ctx, w.tmp_fine2, (size_t)p.W * p.n * sizeof(uint16_t)))) return rc;
+    if ((rc = ensure(ctx, w.mid_cnt, ((size_t)p.W << p.hb) * p.Q2 * (1u << p.mb) * sizeof(uint32_t)))) return rc;
+    if ((rc = ensure(ctx, w.region_start2, (size_t)p.W * ((1u << (p.hb + p.mb)) + 1) * sizeof(uint32_t)))) return rc;
+  }
+  if ((rc = ensure(ctx, w.bsize, p.total_buckets * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.bstart, p.total_buckets * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.istart, p.total_buckets * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.win_items, (1024 + 2 * 1024) * sizeof(uint32_t)))) return rc;   // + tile_sums (<= 1024 tiles)
+  if ((rc = ensure(ctx, w.size_bins, (size_t)(p.CH + 1) * ((p.total_buckets + p.front_threads - 1) / p.front_threads) *
+                                         sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.sorted, (size_t)p.W * p.n * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.order, p.max_items * sizeof(uint2)))) return rc;
+  if ((rc = ensure(ctx, w.multi_list, p.max_items * sizeof(uint32_t)))) return rc;
+  if ((rc = ensure(ctx, w.counters, sizeof(PlanCounters)))) return rc;
+  *sb = SortBuffers{};
+  sb->digits = w.digits.p;
+  sb->coarse_cnt = (uint32_t*)w.coarse_cnt.p;
+  sb->region_start = (uint32_t*)w.region_start.p;
+  sb->tmp_idx = (uint32_t*)w.tmp_idx.p;
+  sb->tmp_fine = (uint16_t*)w.tmp_fine.p;
+  sb->tmp_idx2 = (uint32_t*)w.tmp_idx2.p;
+  sb->tmp_fine2 = (uint16_t*)w.tmp_fine2.p;
+  sb->mid_cnt = (uint32_t*)w.mid_cnt.p;
+  sb->region_start2 = (uint32_t*)w.region_start2.p;
+  sb->bucket_size = (uint32_t*)w.bsize.p;
+  sb->bucket_start = (uint32_t*)w.bstart.p;
+  sb->item_start = (uint32_t*)w.istart.p;
+  sb->win_items = (uint32_t*)w.win_items.p;
+  sb->tile_sums = (uint2*)((uint32_t*)w.win_items.p + 1024);   // second half of the same small buffer
+  sb->size_bins = (uint32_t*)w.size_bins.p;
+  sb->sorted = (uint32_t*)w.sorted.p;
+  sb->order = (uint2*)w.order.p;
+  sb->multi_list = (uint32_t*)w.multi_list.p;
+  sb->counters = (PlanCounters*)w.counters.p;
+  return MSM_AMD_OK;
+}
+
 // Enqueue one whole MSM on the ctx stream; results land in slot.h_partial after slot.ev[EV_REDUCE].
 int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_layout, int point_layout, const void* d_scalars,
                 const void* d_points, size_t n, Plan* plan_out, bool lone) {
   hipStream_t st = ctx->stream;
   const msm_amd_tables* tb = nullptr;
   if (point_layout == MSM_AMD_POINT_TABLES) {   // d_points is the handle of msm_amd_tables_build*
-    tb = find_tables(ctx, d_points);
+    tb = find_tables(ctx->live_tables, d_points);
     if (!tb) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a table handle of this ctx");
     if (n != tb->n) return fail(ctx, MSM_AMD_INPUT_ERROR, "n differs from the number of points the tables hold");
   }
@@ -810,28 +971,12 @@ int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_l
   int rc;
   if ((rc = slot_prepare(ctx, slot, p.partial_count))) return rc;
   n = p.n;   // from here on: sorted entries per window (= points, or W_digits * points with tables)
-  if ((rc = ensure(ctx, w.digits, (size_t)p.W * n * (p.wide_digits ? sizeof(uint32_t) : sizeof(uint16_t))))) return rc;
-  if ((rc = ensure(ctx, w.coarse_cnt, (size_t)p.W * p.Q * (1u << p.hb) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.region_start, (size_t)p.W * ((1u << p.hb) + 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.tmp_idx, (size_t)p.W * n * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.tmp_fine, (size_t)p.W * n * sizeof(uint16_t)))) return rc;
-  if (p.mb) {
-    if ((rc = ensure(ctx, w.tmp_idx2, (size_t)p.W * n * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(ctx, w.tmp_fine2, (size_t)p.W * n * sizeof(uint16_t)))) return rc;
-    if ((rc = ensure(ctx, w.mid_cnt, ((size_t)p.W << p.hb) * p.Q2 * (1u << p.mb) * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(ctx, w.region_start2, (size_t)p.W * ((1u << (p.hb + p.mb)) + 1) * sizeof(uint32_t)))) return rc;
+  SortBuffers sb{};
+  if ((rc = front_buffers(ctx, w, p, &sb))) return rc;
+  if (ctx->acc_variant == 4) {   // experiments build: the hand-allocated kernel's redo pass
+    if ((rc = ensure(ctx, w.redo_list, p.max_items * sizeof(uint32_t)))) return rc;
+    sb.redo_list = (uint32_t*)w.redo_list.p;
   }
-  if ((rc = ensure(ctx, w.bsize, p.total_buckets * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.bstart, p.total_buckets * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.istart, p.total_buckets * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.win_items, (1024 + 2 * 1024) * sizeof(uint32_t)))) return rc;   // + tile_sums (<= 1024 tiles)
-  if ((rc = ensure(ctx, w.size_bins, (size_t)(p.CH + 1) * ((p.total_buckets + p.front_threads - 1) / p.front_threads) *
-                                         sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.sorted, (size_t)p.W * n * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.order, p.max_items * sizeof(uint2)))) return rc;
-  if ((rc = ensure(ctx, w.multi_list, p.max_items * sizeof(uint32_t)))) return rc;
-  if (ctx->acc_variant == 4 && (rc = ensure(ctx, w.redo_list, p.max_items * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.counters, sizeof(PlanCounters)))) return rc;
   const bool prepared = point_layout == MSM_AMD_POINT_PREPARED || tb != nullptr;
   AffPacked* const fill = prepared ? nullptr : ctx->convert_into;   // bases cache fill: convert straight into the entry
 #if defined(MSM_AMD_EXPERIMENTS)
@@ -845,28 +990,6 @@ int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_l
   if (!prepared && !fill && (rc = ensure(ctx, w.bases29, n * base_record))) return rc;
   if ((rc = ensure(ctx, w.buckets, p.total_buckets * sizeof(PtI)))) return rc;
   if ((rc = ensure(ctx, w.item_partials, p.max_items * sizeof(PtI)))) return rc;
-  SortBuffers sb{};
-  sb.digits = w.digits.p;
-  sb.coarse_cnt = (uint32_t*)w.coarse_cnt.p;
-  sb.region_start = (uint32_t*)w.region_start.p;
-  sb.tmp_idx = (uint32_t*)w.tmp_idx.p;
-  sb.tmp_fine = (uint16_t*)w.tmp_fine.p;
-  sb.tmp_idx2 = (uint32_t*)w.tmp_idx2.p;
-  sb.tmp_fine2 = (uint16_t*)w.tmp_fine2.p;
-  sb.mid_cnt = (uint32_t*)w.mid_cnt.p;
-  sb.region_start2 = (uint32_t*)w.region_start2.p;
-  sb.bucket_size = (uint32_t*)w.bsize.p;
-  sb.bucket_start = (uint32_t*)w.bstart.p;
-  sb.item_start = (uint32_t*)w.istart.p;
-  sb.win_items = (uint32_t*)w.win_items.p;
-  sb.tile_sums = (uint2*)((uint32_t*)w.win_items.p + 1024);   // second half of the same small buffer
-  sb.size_bins = (uint32_t*)w.size_bins.p;
-  sb.sorted = (uint32_t*)w.sorted.p;
-  sb.order = (uint2*)w.order.p;
-  sb.multi_list = (uint32_t*)w.multi_list.p;
-  sb.redo_list = (uint32_t*)w.redo_list.p;
-  sb.counters = (PlanCounters*)w.counters.p;
-
   // Four streams (front, main, two alternating reduce streams), kWorkspaces workspaces (consecutive instances take
   // consecutive workspaces):
   //   front  : conversion, digits, sort, planning, bucket clear of instance i -- needs the workspace's previous
@@ -945,14 +1068,7 @@ int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_l
 }
 
 void accumulate_timings(msm_amd_ctx* ctx, InstanceSlot& s, const Plan& p, float final_ms, size_t n_inst) {
-  auto span = [&](int a, int b) {
-    float t = 0;
-    if (hipEventElapsedTime(&t, s.ev[a], s.ev[b]) != hipSuccess) {
-      (void)hipGetLastError();
-      t = 0;
-    }
-    return t;
-  };
+  auto span = [&](int a, int b) { return event_span(s.ev[a], s.ev[b]); };
   float ms[EV_COUNT] = {0};
   ms[EV_CONVERT] = span(EV_START, EV_CONVERT);
   ms[EV_DIGITS] = span(EV_CONVERT, EV_DIGITS);
@@ -1965,16 +2081,8 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
     g.h_partial = nullptr;
     g.h_partial_cap = 0;
   }
-  for (msm_amd_tables* t : ctx->live_tables) {   // tables the caller did not free
-    (void)hipFree(t->d_tables);
-    delete t;
-  }
-  ctx->live_tables.clear();
-  for (msm_amd_g2_tables* t : ctx->live_g2_tables) {
-    (void)hipFree(t->d_tables);
-    delete t;
-  }
-  ctx->live_g2_tables.clear();
+  tables_release_all(ctx->live_tables);
+  tables_release_all(ctx->live_g2_tables);
   for (DeviceBuf* b : {&ctx->scratch_a, &ctx->scratch_b, &ctx->scratch_c, &ctx->scratch_b2, &ctx->scratch_c2}) kill_buf(*b);
   bases_cache_clear(ctx);   // (entries and unused reserves go through the graveyard)
   for (const msm_amd_ctx::CacheReserve& r : ctx->cache_reserve) ctx->graveyard.push_back(r.d);
@@ -2389,23 +2497,10 @@ int msm_amd_bases_upload(msm_amd_ctx* ctx, int point_layout, const void* points,
   if (pb == 0 || point_layout == MSM_AMD_POINT_PREPARED) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad point layout");
   *d_prepared = nullptr;
   std::lock_guard<std::mutex> g(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc;
-  if ((rc = ensure(ctx, ctx->scratch_c, n * pb))) return rc;
-  void* d_out = nullptr;
-  if (int qrc = quiesce_for_allocation(ctx, "the resident copy of the bases")) return qrc;
-  HIP_TRY(ctx, hipMalloc(&d_out, n * sizeof(AffPacked)));
-  hipError_t e = hipMemcpy(ctx->scratch_c.p, points, n * pb, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(d_out);
-    HIP_TRY(ctx, e);
-  }
-  if ((rc = prepare_bases_locked(ctx, point_layout, ctx->scratch_c.p, n, d_out))) {
-    (void)hipFree(d_out);
-    return rc;
-  }
-  *d_prepared = d_out;
-  return MSM_AMD_OK;
+  return upload_and_prepare(
+      ctx, ctx->scratch_c, points, n * pb, n * sizeof(AffPacked), "the resident copy of the bases",
+      [&](const void* staged, void* d_out) { return prepare_bases_locked(ctx, point_layout, staged, n, d_out); },
+      d_prepared);
 }
 
 // ---- precomputed window tables ------------------------------------------------------------
@@ -2432,10 +2527,8 @@ static uint32_t auto_table_window(size_t n) {
 
 static int tables_build_locked(msm_amd_ctx* ctx, int point_layout, const void* d_points, size_t n, uint32_t window_size,
                                msm_amd_tables** out) {
-  const uint32_t c = window_size ? window_size : auto_table_window(n);
-  if (c < 4 || c > 21) return fail(ctx, MSM_AMD_INPUT_ERROR, "table window_size must be 0 (auto) or 4..21");
-  const uint32_t W = kModulusBits / c + 1;
-  if ((size_t)W * n > 0x7FFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, "windows * n must stay below 2^31");
+  uint32_t c, W;
+  if (int grc = tables_geometry(ctx, n, window_size, auto_table_window(n), &c, &W)) return grc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!drain_or_mark_stalled(ctx)) return fail(ctx, MSM_AMD_PIPELINE_ERROR, "device busy past the wait bound");   // a set-up step: the conversion scratch of workspace 0 must be idle
   hipStream_t st = ctx->stream;
@@ -2447,27 +2540,8 @@ static int tables_build_locked(msm_amd_ctx* ctx, int point_layout, const void* d
   if ((rc = convert_inputs(ctx, ctx->ws[0], st, MSM_AMD_SCALAR_CANON_LE, point_layout, d_points, d_points, n, &sc,
                            &sc_mont, &pts)))
     return rc;
-  void* d_tab = nullptr;
-  if (int qrc = quiesce_for_allocation(ctx, "the window tables")) return qrc;
-  HIP_TRY(ctx, hipMalloc(&d_tab, (size_t)W * n * sizeof(AffPacked)));
-  launch_build_tables(st, pts, (uint32_t)n, c, W, (AffPacked*)d_tab);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && sync_stream_bounded(ctx, st, "table build")) {
-    ctx->graveyard.push_back(d_tab);   // the build may still be running: released when the ctx is idle
-    return MSM_AMD_PIPELINE_ERROR;
-  }
-  if (e != hipSuccess) {
-    (void)hipFree(d_tab);
-    HIP_TRY(ctx, e);
-  }
-  auto* t = new msm_amd_tables();
-  t->n = n;
-  t->c = c;
-  t->W = W;
-  t->d_tables = d_tab;
-  ctx->live_tables.push_back(t);
-  *out = t;
-  return MSM_AMD_OK;
+  return tables_build_tail(ctx, ctx->live_tables, n, c, W, sizeof(AffPacked), "",
+                           [&](void* d_tab) { launch_build_tables(st, pts, (uint32_t)n, c, W, (AffPacked*)d_tab); }, out);
 }
 
 int msm_amd_tables_build_device(msm_amd_ctx* ctx, int point_layout, const void* d_points, size_t n, uint32_t window_size,
@@ -2497,35 +2571,22 @@ int msm_amd_tables_info(msm_amd_ctx* ctx, const msm_amd_tables* tables, size_t* 
                         uint32_t* num_windows, size_t* device_bytes) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
   std::lock_guard<std::mutex> g(ctx->mu);
-  const msm_amd_tables* t = find_tables(ctx, tables);
-  if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a table handle of this ctx");
-  if (n) *n = t->n;
-  if (window_size) *window_size = t->c;
-  if (num_windows) *num_windows = t->W;
-  if (device_bytes) *device_bytes = (size_t)t->W * t->n * sizeof(AffPacked);
-  return MSM_AMD_OK;
+  return tables_info(ctx, ctx->live_tables, tables, sizeof(AffPacked), "not a table handle of this ctx", n, window_size,
+                     num_windows, device_bytes);
 }
 
 int msm_amd_tables_free(msm_amd_ctx* ctx, msm_amd_tables* tables) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
   std::lock_guard<std::mutex> g(ctx->mu);
-  auto it = std::find(ctx->live_tables.begin(), ctx->live_tables.end(), tables);
-  if (it == ctx->live_tables.end()) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a table handle of this ctx");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->live_tables.erase(it);
-  if (drain_or_mark_stalled(ctx)) (void)hipFree(tables->d_tables);
-  else ctx->graveyard.push_back(tables->d_tables);   // hipFree would wait for the device without bound
-  delete tables;
-  return MSM_AMD_OK;
+  return tables_free(ctx, ctx->live_tables, tables, "not a table handle of this ctx");
 }
 
 int msm_amd_msm_tables(msm_amd_ctx* ctx, const msm_amd_tables* tables, int scalar_layout, const void* scalars,
                        void* out96) {
   if (!ctx || !tables || !scalars || !out96) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad msm_tables arguments");
-  if (scalar_layout < MSM_AMD_SCALAR_MONT_LE || scalar_layout > MSM_AMD_SCALAR_CANON_BE32)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
+  if (!scalar_layout_ok(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
   std::lock_guard<std::mutex> g(ctx->mu);
-  const msm_amd_tables* t = find_tables(ctx, tables);
+  const msm_amd_tables* t = find_tables(ctx->live_tables, tables);
   if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a table handle of this ctx");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int rc;
@@ -2544,8 +2605,7 @@ int msm_amd_msm_prepared(msm_amd_ctx* ctx, int scalar_layout, const void* scalar
                          void* out96) {
   if (!ctx || !scalars || !d_prepared || !out96 || n == 0)
     return fail(ctx, MSM_AMD_INPUT_ERROR, "bad msm_prepared arguments");
-  if (scalar_layout < MSM_AMD_SCALAR_MONT_LE || scalar_layout > MSM_AMD_SCALAR_CANON_BE32)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
+  if (!scalar_layout_ok(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
   std::lock_guard<std::mutex> g(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int rc;
@@ -3099,16 +3159,10 @@ uint64_t msm_amd_algorithmic_bytes(size_t n, uint32_t window_size, int accumulat
 // ---- BN254 G2 MSM (one blocking call on the main stream) -----------------------------------------------------------
 namespace {
 
-const msm_amd_g2_tables* find_g2_tables(const msm_amd_ctx* ctx, const void* handle) {
-  for (const msm_amd_g2_tables* t : ctx->live_g2_tables)
-    if ((const void*)t == handle) return t;
-  return nullptr;
-}
-
 // d_points: n records of a host layout, a prepared array (MSM_AMD_G2_POINT_PREPARED: no base conversion) or a table
 // handle (MSM_AMD_G2_POINT_TABLES: the one-window plan of enqueue_msm, every digit window adds into one bucket set).
-// The whole G2 MSM of device-resident inputs: scalar conversion, digits and sort exactly as enqueue_msm does them (into
-// the G2 state's own front-end buffers), then the G2 kernels, the copy of the partial points, a bounded wait and the
+// The whole G2 MSM of device-resident inputs: scalar conversion, digits and sort as in enqueue_msm (front_buffers on
+// the G2 state's own workspace), then the G2 kernels, the copy of the partial points, a bounded wait and the
 // host Horner pass.  ctx->mu held by the caller.
 int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars, const void* d_points,
                size_t n, void* out192) {
@@ -3120,14 +3174,13 @@ int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const v
   hipStream_t st = ctx->stream;
   const msm_amd_g2_tables* tb = nullptr;
   if (g2_point_layout == MSM_AMD_G2_POINT_TABLES) {   // d_points is the handle of msm_amd_g2_tables_build*
-    tb = find_g2_tables(ctx, d_points);
+    tb = find_tables(ctx->live_g2_tables, d_points);
     if (!tb) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
     if (n != tb->n) return fail(ctx, MSM_AMD_INPUT_ERROR, "n differs from the number of points the tables hold");
   }
   const bool prepared = tb != nullptr || g2_point_layout == MSM_AMD_G2_POINT_PREPARED;
   const uint32_t c = tb ? tb->c : (ctx->forced_window ? ctx->forced_window : auto_window_lone(n));
   Plan p = tb ? make_plan(n, c, tb->W) : make_plan(n, c);
-  const size_t ne = p.n;   // sorted entries per window: the points, or W_digits * points with tables (enqueue_msm)
   p.red_group = pick_reduce_group(p);
   p.rb_threads = 0;
   int rc;
@@ -3143,55 +3196,14 @@ int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const v
     HIP_TRY(ctx, hipHostMalloc((void**)&g.h_partial, p.partial_count * sizeof(Jacobian2), hipHostMallocDefault));
     g.h_partial_cap = p.partial_count;
   }
-  if ((rc = ensure(ctx, w.digits, (size_t)p.W * ne * (p.wide_digits ? sizeof(uint32_t) : sizeof(uint16_t))))) return rc;
-  if ((rc = ensure(ctx, w.coarse_cnt, (size_t)p.W * p.Q * (1u << p.hb) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.region_start, (size_t)p.W * ((1u << p.hb) + 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.tmp_idx, (size_t)p.W * ne * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.tmp_fine, (size_t)p.W * ne * sizeof(uint16_t)))) return rc;
-  if (p.mb) {
-    if ((rc = ensure(ctx, w.tmp_idx2, (size_t)p.W * ne * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(ctx, w.tmp_fine2, (size_t)p.W * ne * sizeof(uint16_t)))) return rc;
-    if ((rc = ensure(ctx, w.mid_cnt, ((size_t)p.W << p.hb) * p.Q2 * (1u << p.mb) * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(ctx, w.region_start2, (size_t)p.W * ((1u << (p.hb + p.mb)) + 1) * sizeof(uint32_t)))) return rc;
-  }
-  if ((rc = ensure(ctx, w.bsize, p.total_buckets * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.bstart, p.total_buckets * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.istart, p.total_buckets * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.win_items, (1024 + 2 * 1024) * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.size_bins, (size_t)(p.CH + 1) * ((p.total_buckets + p.front_threads - 1) / p.front_threads) *
-                                         sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.sorted, (size_t)p.W * ne * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.order, p.max_items * sizeof(uint2)))) return rc;
-  if ((rc = ensure(ctx, w.multi_list, p.max_items * sizeof(uint32_t)))) return rc;
-  if ((rc = ensure(ctx, w.counters, sizeof(PlanCounters)))) return rc;
+  SortBuffers sb{};
+  if ((rc = front_buffers(ctx, w, p, &sb))) return rc;
   if (!prepared && (rc = ensure(ctx, g.bases, n * sizeof(Aff2Packed)))) return rc;
   if ((rc = ensure(ctx, g.buckets, p.total_buckets * sizeof(PtI2)))) return rc;
   if ((rc = ensure(ctx, g.item_partials, p.max_items * sizeof(PtI2)))) return rc;
   if ((rc = ensure(ctx, g.S, p.total_segs * sizeof(PtI2)))) return rc;
   if ((rc = ensure(ctx, g.T, p.total_segs * sizeof(PtI2)))) return rc;
   if ((rc = ensure(ctx, g.partial, p.partial_count * sizeof(Jacobian2)))) return rc;
-  SortBuffers sb{};
-  sb.digits = w.digits.p;
-  sb.coarse_cnt = (uint32_t*)w.coarse_cnt.p;
-  sb.region_start = (uint32_t*)w.region_start.p;
-  sb.tmp_idx = (uint32_t*)w.tmp_idx.p;
-  sb.tmp_fine = (uint16_t*)w.tmp_fine.p;
-  sb.tmp_idx2 = (uint32_t*)w.tmp_idx2.p;
-  sb.tmp_fine2 = (uint16_t*)w.tmp_fine2.p;
-  sb.mid_cnt = (uint32_t*)w.mid_cnt.p;
-  sb.region_start2 = (uint32_t*)w.region_start2.p;
-  sb.bucket_size = (uint32_t*)w.bsize.p;
-  sb.bucket_start = (uint32_t*)w.bstart.p;
-  sb.item_start = (uint32_t*)w.istart.p;
-  sb.win_items = (uint32_t*)w.win_items.p;
-  sb.tile_sums = (uint2*)((uint32_t*)w.win_items.p + 1024);
-  sb.size_bins = (uint32_t*)w.size_bins.p;
-  sb.sorted = (uint32_t*)w.sorted.p;
-  sb.order = (uint2*)w.order.p;
-  sb.multi_list = (uint32_t*)w.multi_list.p;
-  sb.redo_list = nullptr;
-  sb.counters = (PlanCounters*)w.counters.p;
-
   HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_START], st));
   const u256* sc = nullptr;
   const Affine* unused = nullptr;
@@ -3229,14 +3241,7 @@ int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const v
   const Jacobian2 res = host_combine_g2(g.h_partial, p);
   const float final_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   std::memcpy(out192, &res, 192);
-  auto span = [&](int a, int b) {
-    float t = 0;
-    if (hipEventElapsedTime(&t, g.ev[a], g.ev[b]) != hipSuccess) {
-      (void)hipGetLastError();
-      t = 0;
-    }
-    return t;
-  };
+  auto span = [&](int a, int b) { return event_span(g.ev[a], g.ev[b]); };
   msm_amd_timings& T = ctx->timings;
   T = msm_amd_timings{};
   T.convert_ms = span(G2State::EV_G2_START, G2State::EV_G2_CONVERT);
@@ -3268,19 +3273,12 @@ void g2_identity_out(void* out192) {
 int g2_args(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points, size_t n,
             const void* out192, bool device = false) {
   if (!ctx || !out192) return MSM_AMD_INPUT_ERROR;
-  if (scalar_layout != MSM_AMD_SCALAR_MONT_LE && scalar_layout != MSM_AMD_SCALAR_CANON_LE &&
-      scalar_layout != MSM_AMD_SCALAR_CANON_BE32)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
+  if (!scalar_layout_ok(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
   const bool device_only = g2_point_layout == MSM_AMD_G2_POINT_PREPARED || g2_point_layout == MSM_AMD_G2_POINT_TABLES;
   if (msm_amd_g2_point_bytes(g2_point_layout) == 0 && !(device && device_only))
     return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown G2 point layout");
   if (n > 0 && (!scalars || !points)) return fail(ctx, MSM_AMD_INPUT_ERROR, "null pointer with n > 0");
   return MSM_AMD_OK;
-}
-
-bool g2_scalar_layout_ok(int scalar_layout) {
-  return scalar_layout == MSM_AMD_SCALAR_MONT_LE || scalar_layout == MSM_AMD_SCALAR_CANON_LE ||
-         scalar_layout == MSM_AMD_SCALAR_CANON_BE32;
 }
 
 // Conversion of a resident G2 point array (a host layout) to Aff2Packed records; ctx->mu held by the caller.
@@ -3294,42 +3292,19 @@ int prepare_bases_g2_locked(msm_amd_ctx* ctx, int g2_point_layout, const void* d
   return sync_stream_bounded(ctx, st, __func__);
 }
 
-// The automatic table window.  auto_table_window (G1) balances the W n mixed additions against the 2^(c-1) buckets of
-// the window reduction; the same balance holds on G2 (every term costs the same factor more), so it is the starting
-// point, and the measurement of DESIGN.md section 8 keeps it.
-uint32_t auto_g2_table_window(size_t n) { return auto_table_window(n); }
-
 int g2_tables_build_locked(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n, uint32_t window_size,
                            msm_amd_g2_tables** out) {
-  const uint32_t c = window_size ? window_size : auto_g2_table_window(n);
-  if (c < 4 || c > 21) return fail(ctx, MSM_AMD_INPUT_ERROR, "table window_size must be 0 (auto) or 4..21");
-  const uint32_t W = kModulusBits / c + 1;
-  if ((size_t)W * n > 0x7FFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, "windows * n must stay below 2^31");
+  // The automatic table window: auto_table_window (G1) balances the W n mixed additions against the 2^(c-1) buckets of
+  // the window reduction; the same balance holds on G2 (every term costs the same factor more), so it is the starting
+  // point, and the measurement of DESIGN.md section 8 keeps it.
+  uint32_t c, W;
+  if (int grc = tables_geometry(ctx, n, window_size, auto_table_window(n), &c, &W)) return grc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!drain_or_mark_stalled(ctx)) return fail(ctx, MSM_AMD_PIPELINE_ERROR, "device busy past the wait bound");   // a set-up step
-  hipStream_t st = ctx->stream;
-  void* d_tab = nullptr;
-  if (int qrc = quiesce_for_allocation(ctx, "the G2 window tables")) return qrc;
-  HIP_TRY(ctx, hipMalloc(&d_tab, (size_t)W * n * sizeof(Aff2Packed)));
-  launch_build_tables_g2(st, d_points, g2_point_layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n, c, W,
-                         (Aff2Packed*)d_tab);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && sync_stream_bounded(ctx, st, "G2 table build")) {
-    ctx->graveyard.push_back(d_tab);   // the build may still be running: released when the ctx is idle
-    return MSM_AMD_PIPELINE_ERROR;
-  }
-  if (e != hipSuccess) {
-    (void)hipFree(d_tab);
-    HIP_TRY(ctx, e);
-  }
-  auto* t = new msm_amd_g2_tables();
-  t->n = n;
-  t->c = c;
-  t->W = W;
-  t->d_tables = d_tab;
-  ctx->live_g2_tables.push_back(t);
-  *out = t;
-  return MSM_AMD_OK;
+  return tables_build_tail(ctx, ctx->live_g2_tables, n, c, W, sizeof(Aff2Packed), "G2 ", [&](void* d_tab) {
+    launch_build_tables_g2(ctx->stream, d_points, g2_point_layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n, c, W,
+                           (Aff2Packed*)d_tab);
+  }, out);
 }
 
 }  // namespace
@@ -3363,24 +3338,10 @@ int msm_amd_g2_bases_upload(msm_amd_ctx* ctx, int g2_point_layout, const void* p
   if (pb == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad G2 point layout");
   *d_prepared = nullptr;
   std::lock_guard<std::mutex> g(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc;
-  if ((rc = ensure(ctx, ctx->g2.in_points, n * pb))) return rc;
-  void* d_out = nullptr;
-  if (int qrc = quiesce_for_allocation(ctx, "the resident copy of the G2 bases")) return qrc;
-  HIP_TRY(ctx, hipMalloc(&d_out, n * sizeof(Aff2Packed)));
-  hipError_t e = hipMemcpy(ctx->g2.in_points.p, points, n * pb, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(d_out);
-    HIP_TRY(ctx, e);
-  }
-  if ((rc = prepare_bases_g2_locked(ctx, g2_point_layout, ctx->g2.in_points.p, n, d_out))) {
-    if (rc == MSM_AMD_PIPELINE_ERROR) ctx->graveyard.push_back(d_out);   // the conversion may still be running
-    else (void)hipFree(d_out);
-    return rc;
-  }
-  *d_prepared = d_out;
-  return MSM_AMD_OK;
+  return upload_and_prepare(
+      ctx, ctx->g2.in_points, points, n * pb, n * sizeof(Aff2Packed), "the resident copy of the G2 bases",
+      [&](const void* staged, void* d_out) { return prepare_bases_g2_locked(ctx, g2_point_layout, staged, n, d_out); },
+      d_prepared);
 }
 
 // host scalars -> the G2 state's staging buffer, on the stream the MSM runs on (stream order does the rest)
@@ -3396,7 +3357,7 @@ int msm_amd_msm_g2_prepared(msm_amd_ctx* ctx, int scalar_layout, const void* sca
                             void* out192) {
   if (!ctx || !scalars || !d_prepared || !out192 || n == 0)
     return fail(ctx, MSM_AMD_INPUT_ERROR, "bad msm_g2_prepared arguments");
-  if (!g2_scalar_layout_ok(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
+  if (!scalar_layout_ok(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
   std::lock_guard<std::mutex> g(ctx->mu);
   if (int rc = g2_stage_scalars(ctx, scalars, n)) return rc;
   return run_msm_g2(ctx, scalar_layout, MSM_AMD_G2_POINT_PREPARED, ctx->g2.in_scalars.p, d_prepared, n, out192);
@@ -3430,34 +3391,22 @@ int msm_amd_g2_tables_info(msm_amd_ctx* ctx, const msm_amd_g2_tables* tables, si
                            uint32_t* num_windows, size_t* device_bytes) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
   std::lock_guard<std::mutex> g(ctx->mu);
-  const msm_amd_g2_tables* t = find_g2_tables(ctx, tables);
-  if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
-  if (n) *n = t->n;
-  if (window_size) *window_size = t->c;
-  if (num_windows) *num_windows = t->W;
-  if (device_bytes) *device_bytes = (size_t)t->W * t->n * sizeof(Aff2Packed);
-  return MSM_AMD_OK;
+  return tables_info(ctx, ctx->live_g2_tables, tables, sizeof(Aff2Packed), "not a G2 table handle of this ctx", n,
+                     window_size, num_windows, device_bytes);
 }
 
 int msm_amd_g2_tables_free(msm_amd_ctx* ctx, msm_amd_g2_tables* tables) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
   std::lock_guard<std::mutex> g(ctx->mu);
-  auto it = std::find(ctx->live_g2_tables.begin(), ctx->live_g2_tables.end(), tables);
-  if (it == ctx->live_g2_tables.end()) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->live_g2_tables.erase(it);
-  if (drain_or_mark_stalled(ctx)) (void)hipFree(tables->d_tables);
-  else ctx->graveyard.push_back(tables->d_tables);   // hipFree would wait for the device without bound
-  delete tables;
-  return MSM_AMD_OK;
+  return tables_free(ctx, ctx->live_g2_tables, tables, "not a G2 table handle of this ctx");
 }
 
 int msm_amd_msm_g2_tables(msm_amd_ctx* ctx, const msm_amd_g2_tables* tables, int scalar_layout, const void* scalars,
                           void* out192) {
   if (!ctx || !tables || !scalars || !out192) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad msm_g2_tables arguments");
-  if (!g2_scalar_layout_ok(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
+  if (!scalar_layout_ok(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
   std::lock_guard<std::mutex> g(ctx->mu);
-  const msm_amd_g2_tables* t = find_g2_tables(ctx, tables);
+  const msm_amd_g2_tables* t = find_tables(ctx->live_g2_tables, tables);
   if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
   if (int rc = g2_stage_scalars(ctx, scalars, t->n)) return rc;
   return run_msm_g2(ctx, scalar_layout, MSM_AMD_G2_POINT_TABLES, ctx->g2.in_scalars.p, tables, t->n, out192);
@@ -3467,7 +3416,7 @@ int msm_amd_test_g2_tables_read(msm_amd_ctx* ctx, const msm_amd_g2_tables* table
                                 size_t count, void* out) {
   if (!ctx || !out || count == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad g2_tables_read arguments");
   std::lock_guard<std::mutex> g(ctx->mu);
-  const msm_amd_g2_tables* t = find_g2_tables(ctx, tables);
+  const msm_amd_g2_tables* t = find_tables(ctx->live_g2_tables, tables);
   if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
   if (w >= t->W || first >= t->n || count > t->n - first)
     return fail(ctx, MSM_AMD_INPUT_ERROR, "window or point range outside the table");
