@@ -542,7 +542,7 @@ int msm_amd_test_fill_workspaces(msm_amd_ctx* ctx, uint8_t byte);
 /* ---- BN254 G2 MSM ------------------------------------------------------------------------------ */
 /* G2 is the twist y^2 = x^3 + 3 / (9 + u) over Fq2 = Fq[u] / (u^2 + 1); an Fq2 element is c0 then c1, each 32 B
  * Montgomery LE (R = 2^256).  Scalars use the MSM_AMD_SCALAR_* layouts above; inputs are taken as points of the
- * r-torsion subgroup (no subgroup check).  The result is 192 B Jacobian, Montgomery LE (x.c0, x.c1, y.c0, y.c1, z.c0,
+ * r-torsion subgroup (no subgroup check; msm_amd_g2_check_points below is the check).  The result is 192 B Jacobian, Montgomery LE (x.c0, x.c1, y.c0, y.c1, z.c0,
  * z.c1), normalised to z = (R mod p, 0); the identity is ((R, 0), (R, 0), (0, 0)). */
 enum {
   MSM_AMD_G2_POINT_H2C_AFFINE = 0, /* halo2curves bn256::G2Affine {x, y}: 128 B, identity = all zero */
@@ -628,6 +628,54 @@ int msm_amd_test_g2_tables_read(msm_amd_ctx* ctx, const msm_amd_g2_tables* table
  * in the same form, out[(w * n + i) * 128]; points in a host layout; threads <= 0: up to 16 host threads. */
 int msm_amd_test_g2_table_host(int g2_point_layout, const void* points, size_t n, uint32_t window_size,
                                uint32_t num_windows, int threads, void* out);
+
+/* ---- point validation (G1 and G2) ------------------------------------------------------------------
+ * The MSM entry points multiply whatever they are handed.  These calls judge a point array first -- the one-time check
+ * of a proving key or an SRS before msm_amd_tables_build / msm_amd_g2_tables_build.  Every record gets ONE reason code,
+ * the first rule that fails; the rule is the same on the GPU and in the host twins. */
+enum {
+  MSM_AMD_POINT_VALID = 0,           /* passes every requested check */
+  MSM_AMD_POINT_NOT_REDUCED = 1,     /* some coordinate, read as a 256-bit integer in the layout's own form (the
+                                        Montgomery residue), is >= p */
+  MSM_AMD_POINT_NOT_ON_CURVE = 2,    /* G1: y^2 != x^3 + 3 (Jacobian layouts: Y^2 != X^3 + 3 Z^6); G2: y^2 != x^3 + 3 / (9 + u) */
+  MSM_AMD_POINT_NOT_IN_SUBGROUP = 3  /* G2 only: on the curve, but [r] P != O */
+};
+/* Identity encodings are valid: (0, 0) / all zero in the halo2curves layouts; the infinity flag of the ark affine
+ * layouts (whatever the coordinate bytes of a flagged record); Z = 0 in the two G1 Jacobian layouts (whose coordinates
+ * are still range-checked). */
+enum {
+  MSM_AMD_CHECK_CURVE = 1,    /* rules 1 and 2 */
+  MSM_AMD_CHECK_SUBGROUP = 2  /* implies CURVE and adds rule 3; on G1 (cofactor 1) accepted and equal to CURVE */
+};
+typedef struct msm_amd_check_report {
+  uint64_t n_checked, n_invalid, n_identity;   /* n_identity: records valid as an identity encoding */
+  uint64_t first_invalid;        /* smallest index with a non-zero reason; UINT64_MAX if none */
+  uint32_t first_reason;         /* its reason code (0 if none) */
+  uint32_t by_reason[4];         /* records per reason code (index 0 = valid) */
+  float device_ms;               /* kernel time, 0 for the host twins */
+} msm_amd_check_report;
+/* MSM_AMD_OK means the check ran: invalid points are reported in `report`, never in the status.  n == 0: OK and an empty
+ * report.  MSM_AMD_INPUT_ERROR: checks == 0 or unknown bits, a null pointer with n > 0, a null report, n >= 2^32, an
+ * unknown layout or a device-only one (*_PREPARED, *_TABLES: the library's own output).  G1 takes the four host layouts,
+ * G2 both of its host layouts.  reasons (n bytes, one reason code per record) may be NULL.  The ctx calls serialise on
+ * the ctx and first wait -- bounded, msm_amd_set_wait_timeout_ms -- for its earlier work: a ctx that stays busy, or a
+ * check that does not finish in time, returns MSM_AMD_PIPELINE_ERROR and msm_amd_last_error names the check.  Host
+ * buffers go up in chunks through the ctx's page-locked staging ring. */
+int msm_amd_check_points(msm_amd_ctx* ctx, int point_layout, const void* points, size_t n, uint32_t checks,
+                         uint8_t* reasons, msm_amd_check_report* report);
+int msm_amd_check_points_device(msm_amd_ctx* ctx, int point_layout, const void* d_points, size_t n, uint32_t checks,
+                                uint8_t* d_reasons /* device memory, or NULL */, msm_amd_check_report* report);
+int msm_amd_g2_check_points(msm_amd_ctx* ctx, int g2_point_layout, const void* points, size_t n, uint32_t checks,
+                            uint8_t* reasons, msm_amd_check_report* report);
+int msm_amd_g2_check_points_device(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n,
+                                   uint32_t checks, uint8_t* d_reasons /* device memory, or NULL */,
+                                   msm_amd_check_report* report);
+/* The same checks on the CPU (no ctx, no GPU; the same bodies compiled for the host); threads <= 0: up to 16 host
+ * threads. */
+int msm_amd_host_check_points(int point_layout, const void* points, size_t n, uint32_t checks, int threads,
+                              uint8_t* reasons, msm_amd_check_report* report);
+int msm_amd_host_g2_check_points(int g2_point_layout, const void* points, size_t n, uint32_t checks, int threads,
+                                 uint8_t* reasons, msm_amd_check_report* report);
 
 /* ---- introspection --------------------------------------------------------------------------- */
 int msm_amd_last_timings(const msm_amd_ctx* ctx, msm_amd_timings* out);

@@ -39,6 +39,9 @@ G2_POINT_BYTES = {G2_POINT_H2C_AFFINE: 128, G2_POINT_ARK_AFFINE: 136}
 (G2_RAW_FQ2_MUL, G2_RAW_FQ2_SQR, G2_RAW_PT_MADD, G2_RAW_PT_MMADD, G2_RAW_PT_ADD_NZ, G2_RAW_PT_ADD,
  G2_RAW_PT_DOUBLE, G2_RAW_FQ2_INV, G2_RAW_PT_TO_AFFINE) = range(9)
 G2_RAW_IN_WORDS, G2_RAW_OUT_WORDS = 72, 80
+# point validation (MSM_AMD_POINT_VALID ..., MSM_AMD_CHECK_*)
+POINT_VALID, POINT_NOT_REDUCED, POINT_NOT_ON_CURVE, POINT_NOT_IN_SUBGROUP = range(4)
+CHECK_CURVE, CHECK_SUBGROUP = 1, 2
 
 
 def op_is_point(op):
@@ -77,6 +80,8 @@ EXPORTS = [
     "msm_amd_g2_bases_upload", "msm_amd_g2_bases_prepare_device", "msm_amd_msm_g2_prepared",
     "msm_amd_g2_tables_build", "msm_amd_g2_tables_build_device", "msm_amd_g2_tables_info", "msm_amd_g2_tables_free",
     "msm_amd_msm_g2_tables", "msm_amd_test_g2_tables_read", "msm_amd_test_g2_table_host",
+    "msm_amd_check_points", "msm_amd_check_points_device", "msm_amd_g2_check_points", "msm_amd_g2_check_points_device",
+    "msm_amd_host_check_points", "msm_amd_host_g2_check_points",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -95,6 +100,18 @@ class Timings(ctypes.Structure):
                 ("reduce_ms", c_float), ("final_ms", c_float), ("total_gpu_ms", c_float), ("n", c_uint32),
                 ("window_size", c_uint32), ("num_windows", c_uint32), ("reserved", c_uint32),
                 ("accumulate_kernel_ms", c_float), ("reserved2", c_float * 3)]
+
+
+class CheckReport(ctypes.Structure):   # msm_amd_check_report
+    _fields_ = [("n_checked", c_uint64), ("n_invalid", c_uint64), ("n_identity", c_uint64), ("first_invalid", c_uint64),
+                ("first_reason", c_uint32), ("by_reason", c_uint32 * 4), ("device_ms", c_float)]
+
+    def as_dict(self) -> dict:
+        """first_invalid is None when every record is valid (UINT64_MAX in the C struct)."""
+        first = None if self.first_invalid == 0xFFFFFFFFFFFFFFFF else self.first_invalid
+        return {"n_checked": self.n_checked, "n_invalid": self.n_invalid, "n_identity": self.n_identity,
+                "first_invalid": first, "first_reason": self.first_reason, "by_reason": list(self.by_reason),
+                "device_ms": self.device_ms}
 
 
 class MsmError(RuntimeError):
@@ -251,6 +268,12 @@ def _lib():
         L.msm_amd_msm_g2_tables.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
         L.msm_amd_test_g2_tables_read.argtypes = [c_void_p, c_void_p, c_uint32, c_size_t, c_size_t, c_void_p]
         L.msm_amd_test_g2_table_host.argtypes = [c_int, c_void_p, c_size_t, c_uint32, c_uint32, c_int, c_void_p]
+        L.msm_amd_check_points.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_uint32, c_void_p, POINTER(CheckReport)]
+        L.msm_amd_check_points_device.argtypes = L.msm_amd_check_points.argtypes
+        L.msm_amd_g2_check_points.argtypes = L.msm_amd_check_points.argtypes
+        L.msm_amd_g2_check_points_device.argtypes = L.msm_amd_check_points.argtypes
+        L.msm_amd_host_check_points.argtypes = [c_int, c_void_p, c_size_t, c_uint32, c_int, c_void_p, POINTER(CheckReport)]
+        L.msm_amd_host_g2_check_points.argtypes = L.msm_amd_host_check_points.argtypes
         L.msm_amd_generate_instance_host.argtypes = [c_uint64, c_size_t, c_int, c_void_p, c_void_p, c_int]
         L.msm_amd_test_op_ifma.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_tuned_split.argtypes = [c_size_t]
@@ -603,6 +626,35 @@ class MsmConfig:
         self._check(_lib().msm_amd_test_g2_tables_read(self.h, c_void_p(tables), w, first, count, out))
         return out.raw
 
+    # ---- point validation (range, on-curve, G2 subgroup) -------------------------------------------
+    def _check_host_buffers(self, fn, points, n, checks, point_layout, want_reasons):
+        rep = CheckReport()
+        reasons = ctypes.create_string_buffer(max(n, 1)) if want_reasons else None
+        self._check(fn(self.h, point_layout, points, n, checks, reasons, ctypes.byref(rep)))
+        return rep.as_dict(), (reasons.raw[:n] if want_reasons else None)
+
+    def _check_device(self, fn, d_points, n, checks, point_layout, d_reasons):
+        rep = CheckReport()
+        self._check(fn(self.h, point_layout, c_void_p(d_points), n, checks, c_void_p(d_reasons), ctypes.byref(rep)))
+        return rep.as_dict()
+
+    def check_points(self, points: bytes, n: int, checks=CHECK_CURVE, point_layout=POINT_H2C_AFFINE, reasons=True):
+        """Judge n G1 points (a host layout) on the GPU: (report dict, n reason bytes or None)."""
+        return self._check_host_buffers(_lib().msm_amd_check_points, points, n, checks, point_layout, reasons)
+
+    def check_points_device(self, d_points, n: int, checks=CHECK_CURVE, point_layout=POINT_H2C_AFFINE, d_reasons=None):
+        """The same on device-resident points; d_reasons: n bytes of device memory or None.  Returns the report."""
+        return self._check_device(_lib().msm_amd_check_points_device, d_points, n, checks, point_layout, d_reasons)
+
+    def g2_check_points(self, points: bytes, n: int, checks=CHECK_CURVE | CHECK_SUBGROUP,
+                        point_layout=G2_POINT_H2C_AFFINE, reasons=True):
+        """Judge n G2 points on the GPU (CHECK_SUBGROUP: [r] P = O): (report dict, n reason bytes or None)."""
+        return self._check_host_buffers(_lib().msm_amd_g2_check_points, points, n, checks, point_layout, reasons)
+
+    def g2_check_points_device(self, d_points, n: int, checks=CHECK_CURVE | CHECK_SUBGROUP,
+                               point_layout=G2_POINT_H2C_AFFINE, d_reasons=None):
+        return self._check_device(_lib().msm_amd_g2_check_points_device, d_points, n, checks, point_layout, d_reasons)
+
     def test_op_g2(self, op, a, b, count):
         """Raw-limb G2 op (MSM_AMD_G2_RAW_*) on the device: a, b flat u32 lists of count * G2_RAW_IN_WORDS; returns
         count * G2_RAW_OUT_WORDS u32."""
@@ -792,6 +844,26 @@ def g2_progression(start: bytes, step: bytes, n: int, threads=0) -> bytes:
     if st != OK:
         raise MsmError(st)
     return out.raw
+
+
+def _host_check(fn, points, n, checks, threads, point_layout, want_reasons):
+    rep = CheckReport()
+    reasons = ctypes.create_string_buffer(max(n, 1)) if want_reasons else None
+    st = fn(point_layout, points, n, checks, threads, reasons, ctypes.byref(rep))
+    if st != OK:
+        raise MsmError(st)
+    return rep.as_dict(), (reasons.raw[:n] if want_reasons else None)
+
+
+def host_check_points(points: bytes, n: int, checks=CHECK_CURVE, threads=0, point_layout=POINT_H2C_AFFINE, reasons=True):
+    """Host twin of MsmConfig.check_points (no GPU): (report dict, n reason bytes or None)."""
+    return _host_check(_lib().msm_amd_host_check_points, points, n, checks, threads, point_layout, reasons)
+
+
+def host_g2_check_points(points: bytes, n: int, checks=CHECK_CURVE | CHECK_SUBGROUP, threads=0,
+                         point_layout=G2_POINT_H2C_AFFINE, reasons=True):
+    """Host twin of MsmConfig.g2_check_points (no GPU)."""
+    return _host_check(_lib().msm_amd_host_g2_check_points, points, n, checks, threads, point_layout, reasons)
 
 
 def _g2_raw_in(seq, count):

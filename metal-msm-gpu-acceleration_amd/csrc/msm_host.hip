@@ -26,6 +26,7 @@
 #include "device_common.hip.h"
 #include "launch.h"
 #include "launch_g2.h"
+#include "launch_check.h"
 #include "host_fq64.h"
 #include "test_ops.hip.h"
 #include "test_ops_g2.hip.h"
@@ -171,6 +172,16 @@ struct msm_amd_tables : TablesRecord {};
 // that a G1 handle is no G2 handle and the reverse.
 struct msm_amd_g2_tables : TablesRecord {};
 
+// Buffers of a point check (msm_amd_check_points*, msm_amd_g2_check_points*): the 64-byte counters and their page-locked
+// copy, the reason bytes and, for G1, the staging of host points.  One per group: a G2 check touches G2State only.
+struct CheckState {
+  enum { EV_CHECK_START = 0, EV_CHECK_KERNEL, EV_CHECK_DONE, EV_CHECK_COUNT };
+  DeviceBuf in_points, reasons, counters;
+  CheckCounters* h_counters = nullptr;   // pinned
+  hipEvent_t ev[EV_CHECK_COUNT] = {};
+  bool ready = false;
+};
+
 // Buffers of the G2 MSM (msm_amd_msm_g2*): one blocking call at a time on the main stream.  `ws` holds the scalar
 // front end's buffers (digits, sort, work items, scalar conversion) -- its own, so a G2 call never touches what a G1
 // instance of the same ctx may still be using; the point-valued buffers are G2-sized.
@@ -182,6 +193,7 @@ struct G2State {
   size_t h_partial_cap = 0;
   hipEvent_t ev[EV_G2_COUNT] = {};
   bool has_events = false;
+  CheckState check;   // msm_amd_g2_check_points*: host points are staged in in_points above
 };
 
 struct msm_amd_ctx {
@@ -206,6 +218,7 @@ struct msm_amd_ctx {
   bool lone_single_stream = true;        // MSM_AMD_LONE_SINGLE_STREAM=0: a lone instance uses the stream split too
   Workspace ws[kWorkspaces];
   G2State g2;
+  CheckState check;   // msm_amd_check_points* (G1)
   std::mutex mu;
   std::string last_error;
   uint32_t forced_window = 0;
@@ -2055,6 +2068,10 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
   }
   for (hipEvent_t& e : ctx->g2.ev) kill_event(e);
   ctx->g2.has_events = false;
+  for (CheckState* cs : {&ctx->check, &ctx->g2.check}) {
+    for (hipEvent_t& e : cs->ev) kill_event(e);
+    cs->ready = false;
+  }
   for (hipEvent_t& e : ctx->uploaded) kill_event(e);
   kill_event(ctx->upload_done);
   kill_event(ctx->after_sort_mark);
@@ -2080,6 +2097,11 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
     if (g.h_partial) (void)hipHostFree(g.h_partial);
     g.h_partial = nullptr;
     g.h_partial_cap = 0;
+  }
+  for (CheckState* cs : {&ctx->check, &ctx->g2.check}) {
+    for (DeviceBuf* b : {&cs->in_points, &cs->reasons, &cs->counters}) kill_buf(*b);
+    if (cs->h_counters) (void)hipHostFree(cs->h_counters);
+    cs->h_counters = nullptr;
   }
   tables_release_all(ctx->live_tables);
   tables_release_all(ctx->live_g2_tables);
@@ -3470,6 +3492,141 @@ int msm_amd_test_op_g2(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch_c.p, out_bytes, hipMemcpyDeviceToHost, st));
   return sync_stream_bounded(ctx, st, __func__);
+}
+
+}  // extern "C"
+
+// ---- point validation (msm_amd_check_points*, msm_amd_g2_check_points*) ---------------------------------------------
+namespace {
+
+const char* check_name(bool g2) { return g2 ? "msm_amd_g2_check_points" : "msm_amd_check_points"; }
+
+int check_args(msm_amd_ctx* ctx, bool g2, int layout, const void* points, size_t n, uint32_t checks,
+               const msm_amd_check_report* report) {
+  if (!ctx || !report) return MSM_AMD_INPUT_ERROR;
+  const std::string who = check_name(g2);
+  if (check_stride(g2, layout) == 0)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": takes the host point layouts only (not *_PREPARED / *_TABLES)");
+  if (checks == 0 || (checks & ~(uint32_t)(MSM_AMD_CHECK_CURVE | MSM_AMD_CHECK_SUBGROUP)))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": checks must be MSM_AMD_CHECK_CURVE and / or MSM_AMD_CHECK_SUBGROUP");
+  if (n > 0xFFFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": n >= 2^32");
+  if (n > 0 && !points) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": null pointer with n > 0");
+  return MSM_AMD_OK;
+}
+
+// Every ctx check call starts here (ctx->mu held): the ctx's earlier work is waited for, with the wait bound.
+int check_begin(msm_amd_ctx* ctx, bool g2) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = recover_if_stalled(ctx)) return fail(ctx, rc, std::string(check_name(g2)) + ": " + ctx->last_error);
+  if (!drain_or_mark_stalled(ctx))
+    return fail(ctx, MSM_AMD_PIPELINE_ERROR, std::string(check_name(g2)) + ": device busy past the wait bound of " +
+                                                 std::to_string(ctx->wait_timeout_ms) + " ms (msm_amd_synchronize waits again)");
+  return MSM_AMD_OK;
+}
+
+// The check of n device-resident records on the main stream and the bounded wait for its counters.  The ctx is idle
+// (check_begin), so the first call may allocate the counters and their page-locked copy.
+int run_check(msm_amd_ctx* ctx, CheckState& cs, bool g2, int layout, const void* d_points, size_t n, uint32_t checks,
+              uint8_t* d_reasons, msm_amd_check_report* report) {
+  hipStream_t st = ctx->stream;
+  if (!cs.ready) {
+    if (int rc = quiesce_for_allocation(ctx, "the report buffer of a point check")) return rc;
+    if (int rc = ensure(ctx, cs.counters, sizeof(CheckCounters))) return rc;
+    if (!cs.h_counters) HIP_TRY(ctx, hipHostMalloc((void**)&cs.h_counters, sizeof(CheckCounters), hipHostMallocDefault));
+    for (hipEvent_t& e : cs.ev)
+      if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    cs.ready = true;
+  }
+  CheckCounters* d_counters = (CheckCounters*)cs.counters.p;
+  launch_check_reset(st, d_counters);
+  HIP_TRY(ctx, hipEventRecord(cs.ev[CheckState::EV_CHECK_START], st));
+  if (g2)
+    launch_check_g2(st, d_points, layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n, checks, d_reasons, d_counters);
+  else
+    launch_check_g1(st, d_points, layout, (uint32_t)check_stride(false, layout), (uint32_t)n, d_reasons, d_counters);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(cs.ev[CheckState::EV_CHECK_KERNEL], st));
+  HIP_TRY(ctx, hipMemcpyAsync(cs.h_counters, d_counters, sizeof(CheckCounters), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipEventRecord(cs.ev[CheckState::EV_CHECK_DONE], st));
+  const hipError_t we = wait_event(cs.ev[CheckState::EV_CHECK_DONE], ctx->wait_timeout_ms);
+  if (we == hipErrorNotReady) {
+    ctx->stalled = true;
+    return fail(ctx, MSM_AMD_PIPELINE_ERROR, "timed out after " + std::to_string(ctx->wait_timeout_ms) +
+                                                 " ms waiting for " + check_name(g2));
+  }
+  if (we != hipSuccess) return fail(ctx, MSM_AMD_PIPELINE_ERROR, std::string(check_name(g2)) + ": " + hipGetErrorString(we));
+  check_report_from_counters(*cs.h_counters, n, event_span(cs.ev[CheckState::EV_CHECK_START], cs.ev[CheckState::EV_CHECK_KERNEL]),
+                             report);
+  return MSM_AMD_OK;
+}
+
+void empty_check_report(msm_amd_check_report* report) {
+  CheckCounters none{};
+  none.first_key = ~0ull;
+  check_report_from_counters(none, 0, 0.0f, report);
+}
+
+int check_device(msm_amd_ctx* ctx, bool g2, int layout, const void* d_points, size_t n, uint32_t checks,
+                 uint8_t* d_reasons, msm_amd_check_report* report) {
+  if (int rc = check_args(ctx, g2, layout, d_points, n, checks, report)) return rc;
+  if (n == 0) {
+    empty_check_report(report);
+    return MSM_AMD_OK;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (int rc = check_begin(ctx, g2)) return rc;
+  return run_check(ctx, g2 ? ctx->g2.check : ctx->check, g2, layout, d_points, n, checks, d_reasons, report);
+}
+
+// Host buffers: the points go up in chunks through the page-locked staging ring into the group's staging buffer (grown
+// only on an idle ctx, like every workspace), the reason bytes come back after the counters.
+int check_host_buffers(msm_amd_ctx* ctx, bool g2, int layout, const void* points, size_t n, uint32_t checks,
+                       uint8_t* reasons, msm_amd_check_report* report) {
+  if (int rc = check_args(ctx, g2, layout, points, n, checks, report)) return rc;
+  if (n == 0) {
+    empty_check_report(report);
+    return MSM_AMD_OK;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (int rc = check_begin(ctx, g2)) return rc;
+  CheckState& cs = g2 ? ctx->g2.check : ctx->check;
+  DeviceBuf& stage = g2 ? ctx->g2.in_points : cs.in_points;
+  const size_t bytes = n * check_stride(g2, layout);
+  int rc;
+  if ((rc = ensure(ctx, stage, bytes))) return rc;
+  if (reasons && (rc = ensure(ctx, cs.reasons, n))) return rc;
+  if ((rc = staged_upload(ctx, stage.p, points, bytes, ctx->stream))) return rc;
+  uint8_t* d_reasons = reasons ? (uint8_t*)cs.reasons.p : nullptr;
+  if ((rc = run_check(ctx, cs, g2, layout, stage.p, n, checks, d_reasons, report))) return rc;
+  if (reasons) {
+    HIP_TRY(ctx, hipMemcpyAsync(reasons, d_reasons, n, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = sync_stream_bounded(ctx, ctx->stream, check_name(g2)))) return rc;
+  }
+  return MSM_AMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_check_points(msm_amd_ctx* ctx, int point_layout, const void* points, size_t n, uint32_t checks,
+                         uint8_t* reasons, msm_amd_check_report* report) {
+  return check_host_buffers(ctx, false, point_layout, points, n, checks, reasons, report);
+}
+
+int msm_amd_check_points_device(msm_amd_ctx* ctx, int point_layout, const void* d_points, size_t n, uint32_t checks,
+                                uint8_t* d_reasons, msm_amd_check_report* report) {
+  return check_device(ctx, false, point_layout, d_points, n, checks, d_reasons, report);
+}
+
+int msm_amd_g2_check_points(msm_amd_ctx* ctx, int g2_point_layout, const void* points, size_t n, uint32_t checks,
+                            uint8_t* reasons, msm_amd_check_report* report) {
+  return check_host_buffers(ctx, true, g2_point_layout, points, n, checks, reasons, report);
+}
+
+int msm_amd_g2_check_points_device(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n,
+                                   uint32_t checks, uint8_t* d_reasons, msm_amd_check_report* report) {
+  return check_device(ctx, true, g2_point_layout, d_points, n, checks, d_reasons, report);
 }
 
 }  // extern "C"

@@ -9,6 +9,10 @@ its fixed point under madd, mmadd, the full addition and the doubling, and asser
   * the inversion (Fq2::inv_fq: the square-and-multiply chain over p - 2, Fq2::inv on top of norm_fq) keeps its running
     power a valid operand and meets the output bounds the headers state, and pt2_to_affine of any point inside the
     invariant yields coordinates below 2 p (what Fq29::pack_canonical, one conditional subtraction, takes).
+The subgroup test of the point validation (check_points.hip.h) is part of the fixed point: psi (conjugation through the
+32 p / 4 p lifts, the products by gx, gy, the squashed ZZ, ZZZ), the negation of a point, the ladder's base (canonicalised
+like a stored base) and the final comparison D = L + (-R) by the full addition all stay inside the same invariant; the
+curve equation's subtrahend stays below its 8 p lift.
 Prints the invariant and the intermediate bounds; exit status 1 if an assertion fails."""
 import sys
 
@@ -129,6 +133,41 @@ def to_affine(X, Y, ZZ, ZZZ):   # t = (ZZ ZZZ)^-1, x = (X t) ZZZ, y = (Y t) ZZ
     return note("affine.x", x), note("affine.y", y)
 
 
+# ---- point validation (check_points.hip.h) --------------------------------------------------------------------------
+def conj(a, k):           # (a0, k p - a1): the lift must cover a1; the result is anything up to k p
+    assert a[1] < k, (a, k)
+    return (a[0], k)
+
+
+def mul_const(c, b):      # Fq2::mul(c, b) with b = conj(., 32): b1 <= 32 p (2 kc(K16E30) - b1 stays positive limb-wise)
+    assert b[1] <= 32, b
+    chk(c), chk((b[0], 0))
+    return (1 + RP * (c[0] * b[0] + c[1] * 32), 1 + RP * (c[0] * b[1] + c[1] * b[0]))
+
+
+def psi(X, Y, ZZ, ZZZ):   # pt2_psi: (gx conj(X), gy conj(Y), squash(conj(ZZ)), squash(conj(ZZZ))), gx, gy canonical
+    const = (1, 1)
+    return (note("psi.X", mul_const(const, conj(X, 32))), note("psi.Y", mul_const(const, conj(Y, 32))),
+            note("psi.ZZ", squash(conj(ZZ, 4))), note("psi.ZZZ", squash(conj(ZZZ, 4))))
+
+
+def neg_pt(X, Y, ZZ, ZZZ):   # pt2_neg: Y' = squash(32 p - Y)
+    assert max(Y) < 32, Y
+    return X, note("neg.Y", squash((32, 32))), ZZ, ZZZ
+
+
+def curve_equation():     # y^2 - (x^3 + b') + 8 p with x, y from_ext outputs (< 1.01 p), b' canonical
+    x = y = (1.01, 1.01)
+    t = note("curve.x^3", mul(sqr(x), x))
+    d = note("curve.d", sub(sqr(y), add(t, (1, 1)), 8))
+    chk(d)                # is_zero_exact: a multiplication operand
+    # G1 (Fq29 single products): x^3 < 1 + rho' 1.01 (1 + rho' 1.01^2), Jacobian b = 3 Z^6 < 3.1 p, subtrahend < 4.2 p
+    z2 = 1 + RP * 1.01 * 1.01
+    z6 = 1 + RP * (1 + RP * z2 * z2) * z2
+    assert (1 + RP * 1.01 * z2) + 3 * z6 < 8
+    return d
+
+
 def widen(a, b):
     return tuple(tuple(max(x, y) for x, y in zip(u, v)) for u, v in zip(a, b))
 
@@ -142,6 +181,9 @@ def main():
         new = widen(new, add_nz(*new, *new))
         new = widen(new, double(*new))
         new = widen(new, double(base_x, base_y, (1, 1), (1, 1)))
+        new = widen(new, psi(*new))                    # the subgroup test: psi of a carried point, ...
+        new = widen(new, neg_pt(*psi(*new)))           # ... its negation, ...
+        new = widen(new, add_nz(*new, *neg_pt(*new)))  # ... and the final comparison L + (-R)
         if new == pt:
             break
         pt = new
@@ -159,6 +201,8 @@ def main():
     x, y = to_affine(*pt)
     assert max(x) < 1.25 and max(y) < 1.3 and max(SEEN["affine.t"]) < 1.2, (x, y)
     assert max(SEEN["affine.ZZ*ZZZ"]) < 1.7 and max(SEEN["affine.Xt"]) < 1.24 and max(SEEN["affine.Yt"]) < 3.7
+    assert max(SEEN["psi.X"]) < 1.21 and max(SEEN["psi.Y"]) < 1.3 and max(SEEN["psi.ZZ"]) < 1.03 and max(SEEN["neg.Y"]) < 1.2
+    assert max(curve_equation()) < 9.5
     print("invariant: " + "  ".join(f"{k} < {max(v):.3f} p" for k, v in zip(claimed, pt)))
     for k in sorted(SEEN):
         print(f"  {k:10s} < {max(SEEN[k]):.2f} p")
