@@ -535,9 +535,16 @@ enum {
 };
 /* out == NULL: *bytes receives the size of the buffer; otherwise *bytes must equal it. */
 int msm_amd_test_stage_copy(msm_amd_ctx* ctx, uint32_t j, int which, void* out, size_t* bytes);
-/* Fill the point-valued buffers of every workspace (buckets, item partials, reduce scratch, window partials) with one
- * byte over their whole capacity.  Index and count buffers are never touched. */
+/* Fill the point-valued buffers of every workspace (buckets, item partials, reduce scratch, window partials), those of
+ * the G2 MSM included, with one byte over their whole capacity.  Index and count buffers are never touched. */
 int msm_amd_test_fill_workspaces(msm_amd_ctx* ctx, uint8_t byte);
+/* The same tap for the G2 MSM: the last msm_amd_msm_g2* call of the ctx (per-call, prepared or tables), read AFTER the
+ * call.  MSM_AMD_INPUT_ERROR before any G2 MSM has succeeded and after a failed one; G1 calls in between change nothing.
+ * The plan words are the MSM_AMD_TP_* ones with LONE = 1, INSTANCES = 1, WORKSPACE = 0.  The index and count buffers
+ * have the formats above; MSM_AMD_STAGE_BUCKETS and MSM_AMD_STAGE_PARTIAL are 192-byte records in the result form of
+ * msm_amd_msm_g2 (Jacobian, Montgomery LE, not normalised); z all zero = the identity. */
+int msm_amd_test_g2_last_plan(msm_amd_ctx* ctx, uint32_t* out, size_t count);
+int msm_amd_test_g2_stage_copy(msm_amd_ctx* ctx, int which, void* out, size_t* bytes);
 
 /* ---- BN254 G2 MSM ------------------------------------------------------------------------------ */
 /* G2 is the twist y^2 = x^3 + 3 / (9 + u) over Fq2 = Fq[u] / (u^2 + 1); an Fq2 element is c0 then c1, each 32 B

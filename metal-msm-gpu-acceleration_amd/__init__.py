@@ -75,6 +75,7 @@ EXPORTS = [
     "msm_amd_gather_size", "msm_amd_gather_all", "msm_amd_gather_last_error", "msm_amd_gather_destroy",
     "msm_amd_host_msm", "msm_amd_tuned_split", "msm_amd_host_threads", "msm_amd_generate_instance_host", "msm_amd_test_op_ifma",
     "msm_amd_test_last_plan", "msm_amd_test_stage_copy", "msm_amd_test_fill_workspaces",
+    "msm_amd_test_g2_last_plan", "msm_amd_test_g2_stage_copy",
     "msm_amd_g2_point_bytes", "msm_amd_msm_g2", "msm_amd_msm_g2_device", "msm_amd_host_msm_g2",
     "msm_amd_test_g2_progression", "msm_amd_test_op_g2", "msm_amd_test_op_g2_host",
     "msm_amd_g2_bases_upload", "msm_amd_g2_bases_prepare_device", "msm_amd_msm_g2_prepared",
@@ -222,6 +223,8 @@ def _lib():
         L.msm_amd_test_last_plan.argtypes = [c_void_p, c_uint32, c_void_p, c_size_t]
         L.msm_amd_test_stage_copy.argtypes = [c_void_p, c_uint32, c_int, c_void_p, POINTER(c_size_t)]
         L.msm_amd_test_fill_workspaces.argtypes = [c_void_p, ctypes.c_uint8]
+        L.msm_amd_test_g2_last_plan.argtypes = [c_void_p, c_void_p, c_size_t]
+        L.msm_amd_test_g2_stage_copy.argtypes = [c_void_p, c_int, c_void_p, POINTER(c_size_t)]
         L.msm_amd_msm_batch_multi.argtypes = [POINTER(c_void_p), c_size_t, c_int, c_int, c_size_t, POINTER(c_void_p),
                                               POINTER(c_void_p), POINTER(c_size_t), c_void_p]
         L.msm_amd_msm_batch_multi_device.argtypes = L.msm_amd_msm_batch_multi.argtypes
@@ -418,6 +421,20 @@ class MsmConfig:
     def test_fill_workspaces(self, byte: int):
         """Fill the point-valued workspace buffers with one byte (stale-data tests)."""
         self._check(_lib().msm_amd_test_fill_workspaces(self.h, byte))
+
+    def test_g2_last_plan(self) -> dict:
+        """Plan and plan counters of the last G2 MSM of this ctx (stage tap)."""
+        out = (c_uint32 * len(TEST_PLAN_FIELDS))()
+        self._check(_lib().msm_amd_test_g2_last_plan(self.h, out, len(out)))
+        return dict(zip(TEST_PLAN_FIELDS, out))
+
+    def test_g2_stage_copy(self, which) -> bytes:
+        """One buffer (STAGE_*) of the last G2 MSM of this ctx; buckets and partials as 192-byte Jacobian records."""
+        nbytes = c_size_t(0)
+        self._check(_lib().msm_amd_test_g2_stage_copy(self.h, which, None, ctypes.byref(nbytes)))
+        out = ctypes.create_string_buffer(max(1, nbytes.value))
+        self._check(_lib().msm_amd_test_g2_stage_copy(self.h, which, out, ctypes.byref(nbytes)))
+        return out.raw[:nbytes.value]
 
     def device(self) -> int:
         return _lib().msm_amd_ctx_device(self.h)

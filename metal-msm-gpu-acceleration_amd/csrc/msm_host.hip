@@ -194,6 +194,10 @@ struct G2State {
   hipEvent_t ev[EV_G2_COUNT] = {};
   bool has_events = false;
   CheckState check;   // msm_amd_g2_check_points*: host points are staged in in_points above
+  // Stage tap (msm_amd_test_g2_last_plan / msm_amd_test_g2_stage_copy): the plan of the last run_msm_g2, valid only
+  // while that call was the last one and succeeded.  The plan counters stay in ws.counters until the next G2 call.
+  Plan last_plan{};
+  bool has_last_plan = false;
 };
 
 struct msm_amd_ctx {
@@ -3039,15 +3043,9 @@ static int tap_batch(msm_amd_ctx* ctx, uint32_t j, const Batch** out) {
   return MSM_AMD_OK;
 }
 
-int msm_amd_test_last_plan(msm_amd_ctx* ctx, uint32_t j, uint32_t* out, size_t count) {
-  if (!ctx || !out || count < MSM_AMD_TEST_PLAN_WORDS) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_last_plan arguments");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  const Batch* B = nullptr;
-  if (int rc = tap_batch(ctx, j, &B)) return rc;
-  const Plan& p = B->plans[j];
-  const InstanceSlot& s = B->slots[j];
-  PlanCounters pc;
-  std::memcpy(&pc, s.h_partial + s.h_partial_cap, sizeof pc);
+// The MSM_AMD_TP_* words of one instance (G1: instance j of a batch; G2: the last run_msm_g2)
+static void tap_plan_words(const Plan& p, const PlanCounters& pc, bool lone, uint32_t instances, uint32_t workspace,
+                           uint32_t* out) {
   uint32_t v[MSM_AMD_TEST_PLAN_WORDS] = {};
   v[MSM_AMD_TP_C] = p.c;
   v[MSM_AMD_TP_W] = p.W;
@@ -3064,32 +3062,47 @@ int msm_amd_test_last_plan(msm_amd_ctx* ctx, uint32_t j, uint32_t* out, size_t c
   v[MSM_AMD_TP_TILED] = p.tiled;
   v[MSM_AMD_TP_BALLOT] = p.ballot;
   v[MSM_AMD_TP_WIDE_DIGITS] = p.wide_digits ? 1u : 0u;
-  v[MSM_AMD_TP_LONE] = B->lone ? 1u : 0u;
+  v[MSM_AMD_TP_LONE] = lone ? 1u : 0u;
   v[MSM_AMD_TP_TOTAL_ITEMS] = pc.total_items;
   v[MSM_AMD_TP_MULTI_COUNT] = pc.multi_count;
   v[MSM_AMD_TP_DEFERRED] = pc.pad[0];
   v[MSM_AMD_TP_RED_GROUP] = p.red_group;
   v[MSM_AMD_TP_RB_THREADS] = p.rb_threads;
-  v[MSM_AMD_TP_INSTANCES] = (uint32_t)B->n_inst;
-  v[MSM_AMD_TP_WORKSPACE] = (uint32_t)B->ws_index[j];
+  v[MSM_AMD_TP_INSTANCES] = instances;
+  v[MSM_AMD_TP_WORKSPACE] = workspace;
   v[MSM_AMD_TP_FRONT_THREADS] = p.front_threads;
   v[MSM_AMD_TP_FUSED_FRONT] = p.fused_front ? 1u : 0u;
   v[MSM_AMD_TP_PACKED] = p.packed ? 1u : 0u;
   std::memcpy(out, v, sizeof v);
-  return MSM_AMD_OK;
 }
 
-int msm_amd_test_stage_copy(msm_amd_ctx* ctx, uint32_t j, int which, void* out, size_t* bytes) {
-  if (!ctx || !bytes) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_stage_copy arguments");
+int msm_amd_test_last_plan(msm_amd_ctx* ctx, uint32_t j, uint32_t* out, size_t count) {
+  if (!ctx || !out || count < MSM_AMD_TEST_PLAN_WORDS) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_last_plan arguments");
   std::lock_guard<std::mutex> g(ctx->mu);
   const Batch* B = nullptr;
   if (int rc = tap_batch(ctx, j, &B)) return rc;
-  const Plan& p = B->plans[j];
-  Workspace& w = ctx->ws[B->ws_index[j]];
+  const InstanceSlot& s = B->slots[j];
   PlanCounters pc;
-  std::memcpy(&pc, B->slots[j].h_partial + B->slots[j].h_partial_cap, sizeof pc);
+  std::memcpy(&pc, s.h_partial + s.h_partial_cap, sizeof pc);
+  tap_plan_words(B->plans[j], pc, B->lone, (uint32_t)B->n_inst, (uint32_t)B->ws_index[j], out);
+  return MSM_AMD_OK;
+}
+
+// The point-valued buffers of a group and how one record of each leaves through the tap
+struct TapPoints {
+  const DeviceBuf* buckets;   // [W][nb] internal points
+  const DeviceBuf* partial;   // [W][lb + 1] external points
+  size_t bucket_bytes, partial_bytes, out_bytes;   // record sizes: internal point, external point, tap output
+  void (*bucket_out)(const uint8_t* rec, uint8_t* out);
+  void (*partial_out)(const uint8_t* rec, uint8_t* out);
+};
+
+// One buffer of a finished call: `w` holds the index and count buffers (the same formats for G1 and G2), `pts` the
+// point-valued ones.  ctx->mu held by the caller.
+static int tap_stage_copy(msm_amd_ctx* ctx, const Workspace& w, const Plan& p, const PlanCounters& pc,
+                          const TapPoints& pts, int which, void* out, size_t* bytes) {
   const DeviceBuf* src = nullptr;
-  size_t dev_bytes = 0, out_bytes = 0;
+  size_t dev_bytes = 0, records = 0;
   switch (which) {
     case MSM_AMD_STAGE_DIGITS:
       src = &w.digits;
@@ -3102,12 +3115,20 @@ int msm_amd_test_stage_copy(msm_amd_ctx* ctx, uint32_t j, int which, void* out, 
     case MSM_AMD_STAGE_WIN_ITEMS: src = &w.win_items; dev_bytes = (size_t)p.W * 4; break;
     case MSM_AMD_STAGE_ORDER: src = &w.order; dev_bytes = (size_t)pc.total_items * 8; break;
     case MSM_AMD_STAGE_MULTI_LIST: src = &w.multi_list; dev_bytes = (size_t)pc.multi_count * 4; break;
-    case MSM_AMD_STAGE_BUCKETS: src = &w.buckets; dev_bytes = p.total_buckets * sizeof(PtI); break;
-    case MSM_AMD_STAGE_PARTIAL: src = &w.partial; dev_bytes = p.partial_count * sizeof(Jacobian); break;
+    case MSM_AMD_STAGE_BUCKETS:
+      src = pts.buckets;
+      records = p.total_buckets;
+      dev_bytes = records * pts.bucket_bytes;
+      break;
+    case MSM_AMD_STAGE_PARTIAL:
+      src = pts.partial;
+      records = p.partial_count;
+      dev_bytes = records * pts.partial_bytes;
+      break;
     default: return fail(ctx, MSM_AMD_INPUT_ERROR, "test_stage_copy: unknown buffer");
   }
   const bool points = which == MSM_AMD_STAGE_BUCKETS || which == MSM_AMD_STAGE_PARTIAL;
-  out_bytes = points ? dev_bytes / (which == MSM_AMD_STAGE_BUCKETS ? sizeof(PtI) : sizeof(Jacobian)) * 96 : dev_bytes;
+  const size_t out_bytes = points ? records * pts.out_bytes : dev_bytes;
   if (!out) {   // size query
     *bytes = out_bytes;
     return MSM_AMD_OK;
@@ -3124,22 +3145,35 @@ int msm_amd_test_stage_copy(msm_amd_ctx* ctx, uint32_t j, int which, void* out, 
     std::memcpy(out, h.data(), dev_bytes);
     return MSM_AMD_OK;
   }
-  // point buffers leave in the wire layout of the stage entry points: Jacobian, 3 x 8 u32 most significant first
-  uint32_t* o = (uint32_t*)out;
-  if (which == MSM_AMD_STAGE_BUCKETS) {
-    for (size_t i = 0; i < p.total_buckets; ++i) {
-      PtI q;
-      std::memcpy(&q, h.data() + i * sizeof(PtI), sizeof q);
-      jac_to_be32(pti_to_ext(q), o + i * 24);
-    }
-  } else {
-    for (size_t i = 0; i < p.partial_count; ++i) {
-      Jacobian q;
-      std::memcpy(&q, h.data() + i * sizeof(Jacobian), sizeof q);
-      jac_to_be32(q, o + i * 24);
-    }
-  }
+  const bool bk = which == MSM_AMD_STAGE_BUCKETS;
+  const size_t rec = bk ? pts.bucket_bytes : pts.partial_bytes;
+  for (size_t i = 0; i < records; ++i)
+    (bk ? pts.bucket_out : pts.partial_out)(h.data() + i * rec, (uint8_t*)out + i * pts.out_bytes);
   return MSM_AMD_OK;
+}
+
+// G1 point buffers leave in the wire layout of the stage entry points: Jacobian, 3 x 8 u32 most significant first
+static void tap_g1_bucket(const uint8_t* rec, uint8_t* out) {
+  PtI q;
+  std::memcpy(&q, rec, sizeof q);
+  jac_to_be32(pti_to_ext(q), (uint32_t*)out);
+}
+static void tap_g1_partial(const uint8_t* rec, uint8_t* out) {
+  Jacobian q;
+  std::memcpy(&q, rec, sizeof q);
+  jac_to_be32(q, (uint32_t*)out);
+}
+
+int msm_amd_test_stage_copy(msm_amd_ctx* ctx, uint32_t j, int which, void* out, size_t* bytes) {
+  if (!ctx || !bytes) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_stage_copy arguments");
+  std::lock_guard<std::mutex> g(ctx->mu);
+  const Batch* B = nullptr;
+  if (int rc = tap_batch(ctx, j, &B)) return rc;
+  const Workspace& w = ctx->ws[B->ws_index[j]];
+  PlanCounters pc;
+  std::memcpy(&pc, B->slots[j].h_partial + B->slots[j].h_partial_cap, sizeof pc);
+  const TapPoints pts = {&w.buckets, &w.partial, sizeof(PtI), sizeof(Jacobian), 96, tap_g1_bucket, tap_g1_partial};
+  return tap_stage_copy(ctx, w, B->plans[j], pc, pts, which, out, bytes);
 }
 
 // Point-valued workspace buffers only: a poisoned index or count could make a kernel gather from wild addresses, a
@@ -3157,6 +3191,9 @@ int msm_amd_test_fill_workspaces(msm_amd_ctx* ctx, uint8_t byte) {
     for (DeviceBuf* b : bufs)
       if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
   }
+  G2State& g2 = ctx->g2;   // the G2 MSM's own point buffers (its index and count buffers live in g2.ws: untouched)
+  for (DeviceBuf* b : {&g2.buckets, &g2.item_partials, &g2.S, &g2.T, &g2.partial})
+    if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
   return sync_stream_bounded(ctx, ctx->stream, __func__);
 }
 
@@ -3188,6 +3225,7 @@ namespace {
 // host Horner pass.  ctx->mu held by the caller.
 int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars, const void* d_points,
                size_t n, void* out192) {
+  ctx->g2.has_last_plan = false;   // the stage tap reads nothing of a call that failed
   if (n > 0x7FFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, "n >= 2^31");
   if (int rc = recover_if_stalled(ctx)) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3279,6 +3317,8 @@ int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const v
   T.num_windows = p.W_digits;
   T.reserved = 1;
   reap_graveyard(ctx);
+  g.last_plan = p;
+  g.has_last_plan = true;
   return MSM_AMD_OK;
 }
 
@@ -3472,6 +3512,45 @@ int msm_amd_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, con
   HIP_TRY(ctx, hipMemcpyAsync(g.in_scalars.p, scalars, sb, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(g.in_points.p, points, pb, hipMemcpyHostToDevice, ctx->stream));
   return run_msm_g2(ctx, scalar_layout, g2_point_layout, g.in_scalars.p, g.in_points.p, n, out192);
+}
+
+// Stage tap of the G2 MSM (test aid): plan, plan counters and buffers of the last run_msm_g2, read after the call.
+// The counters are still in the G2 workspace (nothing but a G2 call writes it) and are copied here, not in the call.
+static int tap_g2(msm_amd_ctx* ctx, PlanCounters* pc) {
+  if (!ctx->g2.has_last_plan) return fail(ctx, MSM_AMD_INPUT_ERROR, "G2 stage tap: no G2 MSM of this ctx has succeeded last");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipMemcpyAsync(pc, ctx->g2.ws.counters.p, sizeof *pc, hipMemcpyDeviceToHost, ctx->stream));
+  return sync_stream_bounded(ctx, ctx->stream, __func__);
+}
+
+// G2 point buffers leave in the result form of msm_amd_msm_g2 (192 B Jacobian, Montgomery LE; identity: z all zero)
+static void tap_g2_bucket(const uint8_t* rec, uint8_t* out) {
+  PtI2 q;
+  std::memcpy(&q, rec, sizeof q);
+  const Jacobian2 e = pt2_to_ext(q);
+  std::memcpy(out, &e, sizeof e);
+}
+static void tap_g2_partial(const uint8_t* rec, uint8_t* out) { std::memcpy(out, rec, sizeof(Jacobian2)); }
+
+int msm_amd_test_g2_last_plan(msm_amd_ctx* ctx, uint32_t* out, size_t count) {
+  if (!ctx || !out || count < MSM_AMD_TEST_PLAN_WORDS)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_g2_last_plan arguments");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PlanCounters pc;
+  if (int rc = tap_g2(ctx, &pc)) return rc;
+  tap_plan_words(ctx->g2.last_plan, pc, true, 1, 0, out);
+  return MSM_AMD_OK;
+}
+
+int msm_amd_test_g2_stage_copy(msm_amd_ctx* ctx, int which, void* out, size_t* bytes) {
+  if (!ctx || !bytes) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_g2_stage_copy arguments");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PlanCounters pc;
+  if (int rc = tap_g2(ctx, &pc)) return rc;
+  const G2State& g = ctx->g2;
+  const TapPoints pts = {&g.buckets, &g.partial, sizeof(PtI2), sizeof(Jacobian2), sizeof(Jacobian2), tap_g2_bucket,
+                         tap_g2_partial};
+  return tap_stage_copy(ctx, g.ws, g.last_plan, pc, pts, which, out, bytes);
 }
 
 int msm_amd_test_op_g2(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
