@@ -64,13 +64,15 @@ enum {
 };
 
 /* Per-stage device times of the last MSM on this ctx, milliseconds, from hipEvents on the ctx stream
- * (replaces the log::debug! Instant timers of msm.rs:193-214, 288-328). */
+ * (replaces the log::debug! Instant timers of msm.rs:193-214, 288-328).  A G1 instance and a G2 call run the same
+ * instance body with the same stage events, so every field means the same for both groups. */
 typedef struct msm_amd_timings {
   float convert_ms;     /* input layout conversion (0 when inputs are already native) */
   float digits_ms;      /* prepare_buckets_indices */
   float sort_ms;        /* sort_buckets: hist + prefix + scan + scatter (+ bucket ordering) */
-  float accumulate_ms;  /* bucket_wise_accumulation (dominant kernel) */
-  float reduce_ms;      /* sum_reduction: segment + tree kernels */
+  float accumulate_ms;  /* bucket_wise_accumulation (dominant kernel): the accumulate kernel alone */
+  float reduce_ms;      /* the combine pass over split buckets, then sum_reduction (segment + tree kernels) and the copy
+                           of its partial points */
   float final_ms;       /* final_accumulation on the host (wall clock) */
   float total_gpu_ms;   /* SUM of the stage spans above (stages of neighbouring instances overlap on other streams,
                            so this is not a wall interval) */
@@ -564,8 +566,9 @@ size_t msm_amd_g2_point_bytes(int g2_point_layout);
 /* One blocking G2 MSM on the GPU, host buffers (n scalars of 32 B, n points of msm_amd_g2_point_bytes).  Unknown
  * layouts, or a null pointer with n > 0, return MSM_AMD_INPUT_ERROR.  No CPU fallback.  The window is
  * msm_amd_auto_window_size_lone(n) unless msm_amd_set_window_size forced one; msm_amd_last_timings reports the
- * stages (convert_ms: scalar and base conversion, accumulate_ms: accumulation + combine, reduce_ms: window reduction
- * and the copy of its partial points). */
+ * stages as for one lone G1 instance (convert_ms: scalar and base conversion; accumulate_ms = accumulate_kernel_ms: the
+ * accumulate kernel alone; reduce_ms: combine pass, window reduction and the copy of its partial points; total_gpu_ms:
+ * the sum of the stage spans; reserved = 1; reserved2[0]: work items of the accumulate grid). */
 int msm_amd_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points,
                    size_t n, void* out192);
 /* The same with scalars and points in device memory on ctx's device.  Also takes MSM_AMD_G2_POINT_PREPARED (d_points =

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -53,11 +54,19 @@ enum {
   EV_ACC_K0 = EV_ACC_S, EV_ACC_K1 = EV_ACC, EV_RED_S = EV_ACC
 };
 
+// The host side of one instance, G1 or G2: its stage events and the page-locked landing place of its results --
+// h_partial_cap partial points of ext_bytes each (Jacobian or Jacobian2), then one more record of that size that
+// receives the plan counters of the instance (work-item statistics for timings and the stage tap).
 struct InstanceSlot {
   hipEvent_t ev[EV_COUNT];
-  Jacobian* h_partial = nullptr;   // pinned
-  size_t h_partial_cap = 0;
+  uint8_t* h_partial = nullptr;   // pinned
+  size_t h_partial_cap = 0, ext_bytes = 0;
   bool has_events = false;
+  PlanCounters counters() const {
+    PlanCounters pc;
+    std::memcpy(&pc, h_partial + h_partial_cap * ext_bytes, sizeof pc);
+    return pc;
+  }
 };
 
 }  // namespace
@@ -72,6 +81,7 @@ struct Workspace {
   DeviceBuf digits, coarse_cnt, region_start, tmp_idx, tmp_fine, tmp_idx2, tmp_fine2, mid_cnt, region_start2, bsize, bstart, istart, win_items, size_bins, sorted,
       order, multi_list, redo_list, counters, bases29, buckets, item_partials, S, T, partial, conv_scalars, conv_points,
       conv_tmp;
+  // hand-off events between the streams of the ctx (null in a workspace that one stream alone uses: G2State::ws)
   hipEvent_t front_done = nullptr;    // front stream: sorted indices / work items of this workspace are ready
   hipEvent_t acc_done = nullptr;      // main stream: buckets of this workspace are complete (incl. combine)
   hipEvent_t reduce_done = nullptr;   // reduce stream: buckets / partial of this workspace are free again
@@ -182,20 +192,16 @@ struct CheckState {
   bool ready = false;
 };
 
-// Buffers of the G2 MSM (msm_amd_msm_g2*): one blocking call at a time on the main stream.  `ws` holds the scalar
-// front end's buffers (digits, sort, work items, scalar conversion) -- its own, so a G2 call never touches what a G1
-// instance of the same ctx may still be using; the point-valued buffers are G2-sized.
+// State of the G2 MSM (msm_amd_msm_g2*): one blocking call at a time on the main stream, through the instance body of
+// G1 (enqueue_instance) in a workspace and a slot of its own -- a G2 call never touches what a G1 instance of the same
+// ctx may still be using.  `ws` is used on the main stream only and therefore has no hand-off events.
 struct G2State {
-  enum { EV_G2_START = 0, EV_G2_CONVERT, EV_G2_DIGITS, EV_G2_SORT, EV_G2_ACC, EV_G2_REDUCE, EV_G2_COUNT };
   Workspace ws;
-  DeviceBuf bases, buckets, item_partials, S, T, partial, in_scalars, in_points;
-  Jacobian2* h_partial = nullptr;   // pinned
-  size_t h_partial_cap = 0;
-  hipEvent_t ev[EV_G2_COUNT] = {};
-  bool has_events = false;
+  InstanceSlot slot;
+  DeviceBuf in_scalars, in_points;   // staging of host inputs
   CheckState check;   // msm_amd_g2_check_points*: host points are staged in in_points above
   // Stage tap (msm_amd_test_g2_last_plan / msm_amd_test_g2_stage_copy): the plan of the last run_msm_g2, valid only
-  // while that call was the last one and succeeded.  The plan counters stay in ws.counters until the next G2 call.
+  // while that call was the last one and succeeded.  Its plan counters are in `slot`, behind the partial points.
   Plan last_plan{};
   bool has_last_plan = false;
 };
@@ -669,18 +675,20 @@ int set_kernel_attributes(msm_amd_ctx* ctx) {
   return MSM_AMD_OK;
 }
 
-int slot_prepare(msm_amd_ctx* ctx, InstanceSlot& s, size_t partial_count) {
+// Events and page-locked room for partial_count points of ext_bytes each (+ the record of the plan counters).
+int slot_prepare(msm_amd_ctx* ctx, InstanceSlot& s, size_t partial_count, size_t ext_bytes) {
   if (!s.has_events) {
     for (int i = 0; i < EV_COUNT; ++i) HIP_TRY(ctx, hipEventCreate(&s.ev[i]));
     s.has_events = true;
   }
-  if (partial_count > s.h_partial_cap) {
+  if (partial_count > s.h_partial_cap || ext_bytes != s.ext_bytes) {
     if (int rc = quiesce_for_allocation(ctx, "a page-locked result slot")) return rc;
     if (s.h_partial) HIP_TRY(ctx, hipHostFree(s.h_partial));
     s.h_partial = nullptr;
-    // one extra record at the end receives the plan counters of the instance (work-item statistics for timings)
-    HIP_TRY(ctx, hipHostMalloc((void**)&s.h_partial, (partial_count + 1) * sizeof(Jacobian), hipHostMallocDefault));
+    s.h_partial_cap = 0;
+    HIP_TRY(ctx, hipHostMalloc((void**)&s.h_partial, (partial_count + 1) * ext_bytes, hipHostMallocDefault));
     s.h_partial_cap = partial_count;
+    s.ext_bytes = ext_bytes;
   }
   return MSM_AMD_OK;
 }
@@ -699,11 +707,10 @@ hipStream_t front_stream_of(const msm_amd_ctx* ctx, bool lone) {
   return (lone || !ctx->overlap_front) ? ctx->stream : ctx->front_stream;
 }
 
-// Bring inputs to the native device layout (affine 64 B Montgomery LE; scalars 32 B LE).
+// Bring inputs to the native device layout (scalars 32 B LE; affine 64 B Montgomery LE), on stream st.
 // On return *scalars_native / *points_native point to device memory valid until the next call.
-int convert_inputs(msm_amd_ctx* ctx, Workspace& w, hipStream_t st, int scalar_layout, int point_layout, const void* d_scalars,
-                   const void* d_points, size_t n, const u256** scalars_native, int* scalars_mont,
-                   const Affine** points_native) {
+int convert_scalars(msm_amd_ctx* ctx, Workspace& w, hipStream_t st, int scalar_layout, const void* d_scalars, size_t n,
+                    const u256** scalars_native, int* scalars_mont) {
   switch (scalar_layout) {
     case MSM_AMD_SCALAR_MONT_LE:
       *scalars_native = (const u256*)d_scalars;
@@ -724,6 +731,12 @@ int convert_inputs(msm_amd_ctx* ctx, Workspace& w, hipStream_t st, int scalar_la
     default:
       return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
   }
+  HIP_TRY(ctx, hipGetLastError());
+  return MSM_AMD_OK;
+}
+
+int convert_points(msm_amd_ctx* ctx, Workspace& w, hipStream_t st, int point_layout, const void* d_points, size_t n,
+                   const Affine** points_native) {
   switch (point_layout) {
     case MSM_AMD_POINT_PREPARED:   // already in the internal packed form (msm_amd_bases_*): nothing to convert
       *points_native = nullptr;
@@ -775,16 +788,13 @@ size_t point_bytes(int layout) {
   return 0;
 }
 
-// Window reduction of a production-layout bucket matrix: buckets [W][nb] -> partial [W][K+1] on device.
-int enqueue_reduce(msm_amd_ctx* ctx, Workspace& w, hipStream_t st, const Plan& p, const PtI* buckets,
-                   const uint32_t* bucket_size) {
+// Room for the window reduction of plan p in workspace w: the two scratch families S, T (internal points) and the
+// partial points (external points).
+int reduce_buffers(msm_amd_ctx* ctx, Workspace& w, const Plan& p, size_t internal_bytes, size_t ext_bytes) {
   int rc;
-  if ((rc = ensure(ctx, w.S, p.total_segs * sizeof(PtI)))) return rc;
-  if ((rc = ensure(ctx, w.T, p.total_segs * sizeof(PtI)))) return rc;
-  if ((rc = ensure(ctx, w.partial, p.partial_count * sizeof(Jacobian)))) return rc;
-  launch_reduce(st, p, buckets, bucket_size, (PtI*)w.S.p, (PtI*)w.T.p, (Jacobian*)w.partial.p);
-  HIP_TRY(ctx, hipGetLastError());
-  return MSM_AMD_OK;
+  if ((rc = ensure(ctx, w.S, p.total_segs * internal_bytes))) return rc;
+  if ((rc = ensure(ctx, w.T, p.total_segs * internal_bytes))) return rc;
+  return ensure(ctx, w.partial, p.partial_count * ext_bytes);
 }
 
 // ---- table handles, G1 and G2: H = msm_amd_tables (ctx->live_tables) or msm_amd_g2_tables (ctx->live_g2_tables) ----
@@ -967,56 +977,37 @@ int front_buffers(msm_amd_ctx* ctx, Workspace& w, const Plan& p, SortBuffers* sb
   return MSM_AMD_OK;
 }
 
-// Enqueue one whole MSM on the ctx stream; results land in slot.h_partial after slot.ev[EV_REDUCE].
-int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_layout, int point_layout, const void* d_scalars,
-                const void* d_points, size_t n, Plan* plan_out, bool lone) {
-  hipStream_t st = ctx->stream;
-  const msm_amd_tables* tb = nullptr;
-  if (point_layout == MSM_AMD_POINT_TABLES) {   // d_points is the handle of msm_amd_tables_build*
-    tb = find_tables(ctx->live_tables, d_points);
-    if (!tb) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a table handle of this ctx");
-    if (n != tb->n) return fail(ctx, MSM_AMD_INPUT_ERROR, "n differs from the number of points the tables hold");
-  }
-  const uint32_t c = tb ? tb->c : (ctx->forced_window ? ctx->forced_window : (lone ? auto_window_lone(n) : auto_window(n)));
-  Plan p = tb ? make_plan(n, c, tb->W) : make_plan(n, c);
+// The plan of one instance: make_plan and what depends on whether the instance has the machine to itself.
+Plan instance_plan(size_t n, uint32_t c, uint32_t table_windows, bool lone) {
+  Plan p = make_plan(n, c, table_windows);
   if (lone) p.red_group = pick_reduce_group(p);   // (pipelined small instances: 2^16 -6 %, 2^18 +3 % -- not taken)
   p.rb_threads = lone ? 0u : 64u;                 // one wave per bit-subset sum beside a resident accumulate grid (k_reduce.hip)
   // the tile-staged scatter (1024-thread workgroups, 60 VGPRs, 64 KB of LDS) is for a sort that has the machine to
   // itself; beside a resident accumulate grid it is slower than the plain scatter (4 x 2^22 points: 6.15 vs 5.65 ms per MSM)
   if (!lone && !std::getenv("MSM_AMD_TILED")) p.tiled = 0;
-  *plan_out = p;
-  int rc;
-  if ((rc = slot_prepare(ctx, slot, p.partial_count))) return rc;
-  n = p.n;   // from here on: sorted entries per window (= points, or W_digits * points with tables)
-  SortBuffers sb{};
-  if ((rc = front_buffers(ctx, w, p, &sb))) return rc;
-  if (ctx->acc_variant == 4) {   // experiments build: the hand-allocated kernel's redo pass
-    if ((rc = ensure(ctx, w.redo_list, p.max_items * sizeof(uint32_t)))) return rc;
-    sb.redo_list = (uint32_t*)w.redo_list.p;
-  }
-  const bool prepared = point_layout == MSM_AMD_POINT_PREPARED || tb != nullptr;
-  AffPacked* const fill = prepared ? nullptr : ctx->convert_into;   // bases cache fill: convert straight into the entry
-#if defined(MSM_AMD_EXPERIMENTS)
-  // variant 8: bases converted inside this call go into WIDE records (128 B: x, y, -y as limbs)
-  const bool wide = !prepared && !fill && ctx->acc_variant == 8;
-  const size_t base_record = wide ? sizeof(AffWide) : sizeof(AffPacked);
-#else
-  const bool wide = false;
-  const size_t base_record = sizeof(AffPacked);
-#endif
-  if (!prepared && !fill && (rc = ensure(ctx, w.bases29, n * base_record))) return rc;
-  if ((rc = ensure(ctx, w.buckets, p.total_buckets * sizeof(PtI)))) return rc;
-  if ((rc = ensure(ctx, w.item_partials, p.max_items * sizeof(PtI)))) return rc;
-  // Four streams (front, main, two alternating reduce streams), kWorkspaces workspaces (consecutive instances take
-  // consecutive workspaces):
-  //   front  : conversion, digits, sort, planning, bucket clear of instance i -- needs the workspace's previous
-  //            accumulate and reduction done; runs while instance i-1 accumulates and i-2 reduces
-  //   main   : accumulate of instance i                                      -- needs front(i)
-  //   reduce : combine + window reduction + copy of instance i               -- needs main(i)
-  hipStream_t fs = front_stream_of(ctx, lone);
-  hipStream_t rs = (lone || !ctx->overlap_reduce)
-                       ? st
-                       : ctx->reduce_streams[ctx->alt_reduce ? ctx->seq++ % kReduceStreams : 0];
+  return p;
+}
+
+// What the instance body knows of the group it runs (G1 or G2): the record sizes of the point-valued buffers and the
+// four launches, bound by the caller to the plan and the workspace of the instance.  Each launch enqueues on the
+// stream it is handed.
+struct PointStages {
+  size_t bases_bytes;      // room the base conversion needs in Workspace::bases29 (0: the bases are resident elsewhere)
+  size_t internal_bytes;   // internal point (PtI / PtI2): buckets, item partials, S, T
+  size_t ext_bytes;        // external point (Jacobian / Jacobian2): the partial points
+  std::function<int(hipStream_t)> convert_bases;   // the caller's points -> packed bases
+  // `before` / `after` are recorded directly around the accumulate kernel
+  std::function<void(hipStream_t, const SortBuffers&, hipEvent_t before, hipEvent_t after)> accumulate;
+  std::function<void(hipStream_t, const SortBuffers&)> combine;
+  std::function<void(hipStream_t)> reduce;   // Workspace::buckets, bsize -> partial
+};
+
+// The group-independent front end of one instance on stream fs: scalar conversion, the group's base conversion (inside
+// the convert span), digits, sort and work-item planning, with their stage events; then the main stream waits for it.
+// rs: the stream the instance will reduce on.
+int enqueue_front(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, const Plan& p, const SortBuffers& sb, hipStream_t fs,
+                  hipStream_t rs, bool lone, int scalar_layout, const void* d_scalars, const PointStages& g) {
+  hipStream_t st = ctx->stream;
   if (w.acc_pending && (fs != st || lone)) {   // the previous accumulate in this workspace still reads its plan ...
     HIP_TRY(ctx, hipStreamWaitEvent(fs, w.acc_done, 0));
   }
@@ -1033,55 +1024,135 @@ int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_l
   }
   HIP_TRY(ctx, hipEventRecord(slot.ev[EV_START], fs));
   const u256* sc = nullptr;
-  const Affine* pts = nullptr;
-  int sc_mont = 0;
-  if ((rc = convert_inputs(ctx, w, fs, scalar_layout, tb ? MSM_AMD_POINT_PREPARED : point_layout, d_scalars, d_points,
-                           p.n_scalars, &sc, &sc_mont, &pts)))
-    return rc;
-  const AffPacked* bases = tb ? (const AffPacked*)tb->d_tables
-                              : (prepared ? (const AffPacked*)d_points
-                                          : (fill ? (const AffPacked*)fill : (const AffPacked*)w.bases29.p));
-#if defined(MSM_AMD_EXPERIMENTS)
-  if (wide) launch_convert_bases_wide(fs, pts, p.n, (AffWide*)w.bases29.p);
-#endif
-  if (!prepared && !wide)   // external 8 x u32 -> packed internal domain
-    launch_convert_bases(fs, pts, p.n, fill ? fill : (AffPacked*)w.bases29.p);
+  int sc_mont = 0, rc;
+  if ((rc = convert_scalars(ctx, w, fs, scalar_layout, d_scalars, p.n_scalars, &sc, &sc_mont))) return rc;
+  if ((rc = g.convert_bases(fs))) return rc;
   HIP_TRY(ctx, hipEventRecord(slot.ev[EV_CONVERT], fs));
   if (p.fused_front) launch_digits_hist(fs, p, sc, sc_mont, sb); else launch_digits(fs, p, sc, sc_mont, sb.digits);
   HIP_TRY(ctx, hipEventRecord(slot.ev[EV_DIGITS], fs));
   launch_sort(fs, p, sb, p.fused_front);
   HIP_TRY(ctx, hipEventRecord(slot.ev[EV_SORT], fs));
-  // the bucket matrix is NOT cleared: a bucket without points gets no work item and is never written; the window
-  // reduction reads bucket_size and takes such a slot as the identity (the reference relies on Metal's zero-filled
-  // fresh buffers instead, msm.rs:154-156)
   if (fs != st) {
     HIP_TRY(ctx, hipEventRecord(w.front_done, fs));
     HIP_TRY(ctx, hipStreamWaitEvent(st, w.front_done, 0));
   }
+  return MSM_AMD_OK;
+}
+
+// The point-valued half of one instance: accumulate on the main stream; combine, window reduction and the copy of the
+// partial points and the plan counters into the slot on stream rs.
+int enqueue_points(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, const Plan& p, const SortBuffers& sb, hipStream_t rs,
+                   const PointStages& g) {
+  hipStream_t st = ctx->stream;
+  // the bucket matrix is NOT cleared: a bucket without points gets no work item and is never written; the window
+  // reduction reads bucket_size and takes such a slot as the identity (the reference relies on Metal's zero-filled
+  // fresh buffers instead, msm.rs:154-156)
   if (w.reduce_pending) {   // the previous user of this workspace may still be reducing its buckets
     if (rs != st) HIP_TRY(ctx, hipStreamWaitEvent(st, w.reduce_done, 0));
     w.reduce_pending = false;
   }
-  launch_accumulate(st, p, bases, wide ? 1 : 0, sb, (PtI*)w.buckets.p, (PtI*)w.item_partials.p,
-                    ctx->acc_variant, ctx->acc_lds, slot.ev[EV_ACC_K0], slot.ev[EV_ACC_K1]);
-  HIP_TRY(ctx, hipEventRecord(w.acc_done, st));
-  w.acc_pending = true;
-
+  g.accumulate(st, sb, slot.ev[EV_ACC_K0], slot.ev[EV_ACC_K1]);
+  if (w.acc_done) {
+    HIP_TRY(ctx, hipEventRecord(w.acc_done, st));
+    w.acc_pending = true;
+  }
   // combine (split buckets) + window reduction + copy: off the main stream, which goes straight to the next
   // accumulate.  front(i+2) reuses this workspace's plan buffers, which combine still reads: it waits for
-  // reduce_done as well (see the top of this function).
+  // reduce_done as well (see the top of enqueue_front).
   if (rs != st) HIP_TRY(ctx, hipStreamWaitEvent(rs, w.acc_done, 0));
-  launch_combine(rs, p, sb, (PtI*)w.buckets.p, (PtI*)w.item_partials.p);
-  if ((rc = enqueue_reduce(ctx, w, rs, p, (const PtI*)w.buckets.p, (const uint32_t*)w.bsize.p))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(slot.h_partial, w.partial.p, p.partial_count * sizeof(Jacobian),
-                              hipMemcpyDeviceToHost, rs));
-  HIP_TRY(ctx, hipMemcpyAsync(slot.h_partial + slot.h_partial_cap, w.counters.p, sizeof(PlanCounters),
+  g.combine(rs, sb);
+  if (int rc = reduce_buffers(ctx, w, p, g.internal_bytes, g.ext_bytes)) return rc;
+  g.reduce(rs);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(slot.h_partial, w.partial.p, p.partial_count * g.ext_bytes, hipMemcpyDeviceToHost, rs));
+  HIP_TRY(ctx, hipMemcpyAsync(slot.h_partial + slot.h_partial_cap * g.ext_bytes, w.counters.p, sizeof(PlanCounters),
                               hipMemcpyDeviceToHost, rs));
   HIP_TRY(ctx, hipEventRecord(slot.ev[EV_REDUCE], rs));
-  HIP_TRY(ctx, hipEventRecord(w.reduce_done, rs));
-  w.reduce_pending = true;
+  if (w.reduce_done) {
+    HIP_TRY(ctx, hipEventRecord(w.reduce_done, rs));
+    w.reduce_pending = true;
+  }
   HIP_TRY(ctx, hipGetLastError());
   return MSM_AMD_OK;
+}
+
+// Enqueue one whole instance of plan p, G1 or G2, in workspace w; the partial points and the plan counters land in
+// slot.h_partial after slot.ev[EV_REDUCE].  Four streams (front, main, two alternating reduce streams), kWorkspaces
+// workspaces (consecutive instances take consecutive workspaces):
+//   front  : conversion, digits, sort, planning of instance i -- needs the workspace's previous accumulate and
+//            reduction done; runs while instance i-1 accumulates and i-2 reduces
+//   main   : accumulate of instance i                         -- needs front(i)
+//   reduce : combine + window reduction + copy of instance i  -- needs main(i)
+// A lone instance has all three on the main stream (lone_call).
+int enqueue_instance(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, const Plan& p, bool lone, int scalar_layout,
+                     const void* d_scalars, const PointStages& g) {
+  int rc;
+  if ((rc = slot_prepare(ctx, slot, p.partial_count, g.ext_bytes))) return rc;
+  SortBuffers sb{};
+  if ((rc = front_buffers(ctx, w, p, &sb))) return rc;
+  if (ctx->acc_variant == 4) {   // experiments build: the hand-allocated kernel's redo pass
+    if ((rc = ensure(ctx, w.redo_list, p.max_items * sizeof(uint32_t)))) return rc;
+    sb.redo_list = (uint32_t*)w.redo_list.p;
+  }
+  if (g.bases_bytes && (rc = ensure(ctx, w.bases29, g.bases_bytes))) return rc;
+  if ((rc = ensure(ctx, w.buckets, p.total_buckets * g.internal_bytes))) return rc;
+  if ((rc = ensure(ctx, w.item_partials, p.max_items * g.internal_bytes))) return rc;
+  hipStream_t fs = front_stream_of(ctx, lone);
+  hipStream_t rs = (lone || !ctx->overlap_reduce)
+                       ? ctx->stream
+                       : ctx->reduce_streams[ctx->alt_reduce ? ctx->seq++ % kReduceStreams : 0];
+  if ((rc = enqueue_front(ctx, w, slot, p, sb, fs, rs, lone, scalar_layout, d_scalars, g))) return rc;
+  return enqueue_points(ctx, w, slot, p, sb, rs, g);
+}
+
+// One G1 instance: d_points holds n points of point_layout, prepared bases or, with MSM_AMD_POINT_TABLES, is the handle
+// of msm_amd_tables_build*.
+int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_layout, int point_layout, const void* d_scalars,
+                const void* d_points, size_t n, Plan* plan_out, bool lone) {
+  const msm_amd_tables* tb = nullptr;
+  if (point_layout == MSM_AMD_POINT_TABLES) {
+    tb = find_tables(ctx->live_tables, d_points);
+    if (!tb) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a table handle of this ctx");
+    if (n != tb->n) return fail(ctx, MSM_AMD_INPUT_ERROR, "n differs from the number of points the tables hold");
+  }
+  const uint32_t c = tb ? tb->c : (ctx->forced_window ? ctx->forced_window : (lone ? auto_window_lone(n) : auto_window(n)));
+  const Plan p = instance_plan(n, c, tb ? tb->W : 0, lone);
+  *plan_out = p;
+  const bool prepared = point_layout == MSM_AMD_POINT_PREPARED || tb != nullptr;
+  AffPacked* const fill = prepared ? nullptr : ctx->convert_into;   // bases cache fill: convert straight into the entry
+#if defined(MSM_AMD_EXPERIMENTS)
+  // variant 8: bases converted inside this call go into WIDE records (128 B: x, y, -y as limbs)
+  const bool wide = !prepared && !fill && ctx->acc_variant == 8;
+  const size_t base_record = wide ? sizeof(AffWide) : sizeof(AffPacked);
+#else
+  const bool wide = false;
+  const size_t base_record = sizeof(AffPacked);
+#endif
+  PointStages g;
+  g.bases_bytes = (prepared || fill) ? 0 : p.n * base_record;
+  g.internal_bytes = sizeof(PtI);
+  g.ext_bytes = sizeof(Jacobian);
+  g.convert_bases = [&](hipStream_t fs) -> int {
+    const Affine* pts = nullptr;
+    if (int rc = convert_points(ctx, w, fs, prepared ? MSM_AMD_POINT_PREPARED : point_layout, d_points, p.n_scalars, &pts))
+      return rc;
+#if defined(MSM_AMD_EXPERIMENTS)
+    if (wide) launch_convert_bases_wide(fs, pts, p.n, (AffWide*)w.bases29.p);
+#endif
+    if (!prepared && !wide)   // external 8 x u32 -> packed internal domain
+      launch_convert_bases(fs, pts, p.n, fill ? fill : (AffPacked*)w.bases29.p);
+    return MSM_AMD_OK;
+  };
+  g.accumulate = [&](hipStream_t st, const SortBuffers& sb, hipEvent_t before, hipEvent_t after) {
+    const void* bases = tb ? tb->d_tables : (prepared ? d_points : (fill ? (const void*)fill : w.bases29.p));
+    launch_accumulate(st, p, bases, wide ? 1 : 0, sb, (PtI*)w.buckets.p, (PtI*)w.item_partials.p, ctx->acc_variant,
+                      ctx->acc_lds, before, after);
+  };
+  g.combine = [&](hipStream_t st, const SortBuffers& sb) { launch_combine(st, p, sb, (PtI*)w.buckets.p, (PtI*)w.item_partials.p); };
+  g.reduce = [&](hipStream_t st) {
+    launch_reduce(st, p, (const PtI*)w.buckets.p, (const uint32_t*)w.bsize.p, (PtI*)w.S.p, (PtI*)w.T.p, (Jacobian*)w.partial.p);
+  };
+  return enqueue_instance(ctx, w, slot, p, lone, scalar_layout, d_scalars, g);
 }
 
 void accumulate_timings(msm_amd_ctx* ctx, InstanceSlot& s, const Plan& p, float final_ms, size_t n_inst) {
@@ -1106,9 +1177,7 @@ void accumulate_timings(msm_amd_ctx* ctx, InstanceSlot& s, const Plan& p, float 
   T.window_size = p.c;
   T.num_windows = p.W_digits;
   T.reserved = (uint32_t)n_inst;
-  PlanCounters pc;
-  std::memcpy(&pc, s.h_partial + s.h_partial_cap, sizeof pc);
-  T.reserved2[0] = (float)pc.total_items;   // work items (= lanes with work) of the last instance's accumulate grid
+  T.reserved2[0] = (float)s.counters().total_items;   // work items (= lanes with work) of the last instance's accumulate grid
   T.reserved2[1] = ctx->after_sort_state;
   T.reserved2[2] = ctx->after_sort_lead_ms;
 }
@@ -1173,6 +1242,20 @@ unsigned finish_threads(size_t n_inst) {
   return (unsigned)std::max<size_t>(1, std::min<size_t>({(size_t)4, n_inst / 4, (size_t)hw / 2}));
 }
 
+// wait_event on s.ev[EV_REDUCE] ran into the ctx's bound: the ctx is stalled, and the error names `what` and the last
+// stage event of the instance the device did get to.
+int wait_timed_out(msm_amd_ctx* ctx, const InstanceSlot& s, const std::string& what, const char* tail = "") {
+  ctx->stalled = true;
+  int reached = -1;
+  for (int e = 0; e < EV_COUNT; ++e) {
+    if (hipEventQuery(s.ev[e]) == hipSuccess) reached = e;
+  }
+  (void)hipGetLastError();
+  return fail(ctx, MSM_AMD_PIPELINE_ERROR,
+              "timed out after " + std::to_string(ctx->wait_timeout_ms) + " ms waiting for event 'reduce' of " + what +
+                  "; last event reached: " + (reached < 0 ? "none" : kEventNames[reached]) + tail);
+}
+
 // `internal`: the caller is one of the library's blocking entry points, which cannot hand the ticket back to its own
 // caller -- on a timed-out wait the batch is marked abandoned (released by recover_if_stalled once the device is idle).
 // Through msm_amd_wait_batch the ticket stays valid and the caller may wait again.
@@ -1205,7 +1288,7 @@ int wait_batch(msm_amd_ctx* ctx, int ticket, bool internal = true) {
         continue;
       }
       const auto t0 = std::chrono::steady_clock::now();
-      const Jacobian res = normalise(host_combine(s.h_partial, B.plans[i]));
+      const Jacobian res = normalise(host_combine((const Jacobian*)s.h_partial, B.plans[i]));
       done[i].final_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
       std::memcpy((uint8_t*)B.out + i * 96, &res, 96);
     }
@@ -1217,19 +1300,11 @@ int wait_batch(msm_amd_ctx* ctx, int ticket, bool internal = true) {
   for (std::thread& th : pool) th.join();
   for (size_t i = 0; i < B.n_inst; ++i) {
     if (done[i].err == hipErrorNotReady) {   // the bound of the wait was reached: the work is still in flight
-      ctx->stalled = true;
       if (internal) B.abandoned = true;
-      const InstanceSlot& s = B.slots[i];
-      int reached = -1;   // last stage event of this instance the device did get to
-      for (int e = 0; e < EV_COUNT; ++e) {
-        if (hipEventQuery(s.ev[e]) == hipSuccess) reached = e;
-      }
-      (void)hipGetLastError();
-      return fail(ctx, MSM_AMD_PIPELINE_ERROR,
-                  "timed out after " + std::to_string(timeout_ms) + " ms waiting for event 'reduce' of instance " +
-                      std::to_string(i) + " of " + std::to_string(B.n_inst) + " (ticket " + std::to_string(ticket) +
-                      "); last event reached: " + (reached < 0 ? "none" : kEventNames[reached]) +
-                      (internal ? "" : "; the ticket stays valid"));
+      return wait_timed_out(ctx, B.slots[i],
+                            "instance " + std::to_string(i) + " of " + std::to_string(B.n_inst) + " (ticket " +
+                                std::to_string(ticket) + ")",
+                            internal ? "" : "; the ticket stays valid");
     }
     if (done[i].err != hipSuccess) {   // release the ticket on every exit: a failed wait must not block later submits
       if (!drain_or_mark_stalled(ctx)) B.abandoned = true;
@@ -2059,19 +2134,19 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
     s = nullptr;
   };
   // 1. events
+  auto kill_slot_events = [&](InstanceSlot& s) {
+    if (s.has_events)
+      for (int i = 0; i < EV_COUNT; ++i) kill_event(s.ev[i]);
+    s.has_events = false;
+  };
   for (Batch& B : ctx->batches)
-    for (InstanceSlot& s : B.slots) {
-      if (s.has_events)
-        for (int i = 0; i < EV_COUNT; ++i) kill_event(s.ev[i]);
-      s.has_events = false;
-    }
+    for (InstanceSlot& s : B.slots) kill_slot_events(s);
   for (int k = 0; k < kWorkspaces; ++k) {
     kill_event(ctx->ws[k].front_done);
     kill_event(ctx->ws[k].acc_done);
     kill_event(ctx->ws[k].reduce_done);
   }
-  for (hipEvent_t& e : ctx->g2.ev) kill_event(e);
-  ctx->g2.has_events = false;
+  kill_slot_events(ctx->g2.slot);   // (g2.ws has no hand-off events)
   for (CheckState* cs : {&ctx->check, &ctx->g2.check}) {
     for (hipEvent_t& e : cs->ev) kill_event(e);
     cs->ready = false;
@@ -2082,26 +2157,22 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
   uploader_shutdown(ctx);
   stager_shutdown(ctx);
   // 2. memory
-  for (int k = 0; k < kWorkspaces; ++k) {
-    Workspace& w = ctx->ws[k];
+  auto kill_workspace = [&](Workspace& w) {
     DeviceBuf* bufs[] = {&w.digits, &w.coarse_cnt, &w.region_start, &w.tmp_idx, &w.tmp_fine, &w.tmp_idx2, &w.tmp_fine2,
                          &w.mid_cnt, &w.region_start2, &w.bsize, &w.bstart, &w.istart, &w.win_items, &w.size_bins,
                          &w.sorted, &w.order, &w.multi_list, &w.redo_list, &w.counters, &w.bases29, &w.buckets, &w.item_partials,
                          &w.S, &w.T, &w.partial, &w.conv_scalars, &w.conv_points, &w.conv_tmp};
     for (DeviceBuf* b : bufs) kill_buf(*b);
-  }
-  {
-    G2State& g = ctx->g2;
-    Workspace& w = g.ws;
-    DeviceBuf* bufs[] = {&w.digits, &w.coarse_cnt, &w.region_start, &w.tmp_idx, &w.tmp_fine, &w.tmp_idx2, &w.tmp_fine2,
-                         &w.mid_cnt, &w.region_start2, &w.bsize, &w.bstart, &w.istart, &w.win_items, &w.size_bins,
-                         &w.sorted, &w.order, &w.multi_list, &w.counters, &w.conv_scalars, &g.bases, &g.buckets,
-                         &g.item_partials, &g.S, &g.T, &g.partial, &g.in_scalars, &g.in_points};
-    for (DeviceBuf* b : bufs) kill_buf(*b);
-    if (g.h_partial) (void)hipHostFree(g.h_partial);
-    g.h_partial = nullptr;
-    g.h_partial_cap = 0;
-  }
+  };
+  auto kill_slot_memory = [](InstanceSlot& s) {
+    if (s.h_partial) (void)hipHostFree(s.h_partial);
+    s.h_partial = nullptr;
+    s.h_partial_cap = 0;
+  };
+  for (Workspace& w : ctx->ws) kill_workspace(w);
+  kill_workspace(ctx->g2.ws);
+  for (DeviceBuf* b : {&ctx->g2.in_scalars, &ctx->g2.in_points}) kill_buf(*b);
+  kill_slot_memory(ctx->g2.slot);
   for (CheckState* cs : {&ctx->check, &ctx->g2.check}) {
     for (DeviceBuf* b : {&cs->in_points, &cs->reasons, &cs->counters}) kill_buf(*b);
     if (cs->h_counters) (void)hipHostFree(cs->h_counters);
@@ -2116,11 +2187,7 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
   for (void* p : ctx->graveyard) (void)hipFree(p);
   ctx->graveyard.clear();
   for (Batch& B : ctx->batches) {
-    for (InstanceSlot& s : B.slots) {
-      if (s.h_partial) (void)hipHostFree(s.h_partial);
-      s.h_partial = nullptr;
-      s.h_partial_cap = 0;
-    }
+    for (InstanceSlot& s : B.slots) kill_slot_memory(s);
     B.slots.clear();
     B.active = B.abandoned = false;
   }
@@ -2495,12 +2562,8 @@ static int prepare_bases_locked(msm_amd_ctx* ctx, int point_layout, const void* 
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!drain_or_mark_stalled(ctx)) return fail(ctx, MSM_AMD_PIPELINE_ERROR, "device busy past the wait bound");   // a set-up step: the conversion scratch of workspace 0 must be idle
   hipStream_t st = ctx->stream;
-  const u256* sc = nullptr;
   const Affine* pts = nullptr;
-  int sc_mont = 0, rc;
-  if ((rc = convert_inputs(ctx, ctx->ws[0], st, MSM_AMD_SCALAR_CANON_LE, point_layout, d_points, d_points, n, &sc,
-                           &sc_mont, &pts)))
-    return rc;
+  if (int rc = convert_points(ctx, ctx->ws[0], st, point_layout, d_points, n, &pts)) return rc;
   launch_convert_bases(st, pts, (uint32_t)n, (AffPacked*)d_prepared);
   HIP_TRY(ctx, hipGetLastError());
   if (int src_ = sync_stream_bounded(ctx, st, __func__)) return src_;
@@ -2558,14 +2621,10 @@ static int tables_build_locked(msm_amd_ctx* ctx, int point_layout, const void* d
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!drain_or_mark_stalled(ctx)) return fail(ctx, MSM_AMD_PIPELINE_ERROR, "device busy past the wait bound");   // a set-up step: the conversion scratch of workspace 0 must be idle
   hipStream_t st = ctx->stream;
-  const u256* sc = nullptr;
   const Affine* pts = nullptr;
-  int sc_mont = 0, rc;
   if (point_layout == MSM_AMD_POINT_PREPARED || point_layout == MSM_AMD_POINT_TABLES)
     return fail(ctx, MSM_AMD_INPUT_ERROR, "tables are built from one of the host point layouts");
-  if ((rc = convert_inputs(ctx, ctx->ws[0], st, MSM_AMD_SCALAR_CANON_LE, point_layout, d_points, d_points, n, &sc,
-                           &sc_mont, &pts)))
-    return rc;
+  if (int rc = convert_points(ctx, ctx->ws[0], st, point_layout, d_points, n, &pts)) return rc;
   return tables_build_tail(ctx, ctx->live_tables, n, c, W, sizeof(AffPacked), "",
                            [&](void* d_tab) { launch_build_tables(st, pts, (uint32_t)n, c, W, (AffPacked*)d_tab); }, out);
 }
@@ -2841,15 +2900,18 @@ int msm_amd_sum_reduction(msm_amd_ctx* ctx, const uint32_t* buckets_be32, uint32
   const size_t in_bytes = (size_t)buckets_size * num_windows * 96;
   if ((rc = ensure(ctx, ctx->scratch_a, in_bytes))) return rc;
   if ((rc = ensure(ctx, ctx->scratch_b, in_bytes))) return rc;
-  if ((rc = ensure(ctx, ctx->ws[0].buckets, p.total_buckets * sizeof(PtI)))) return rc;
+  Workspace& ws = ctx->ws[0];
+  if ((rc = ensure(ctx, ws.buckets, p.total_buckets * sizeof(PtI)))) return rc;
+  if ((rc = reduce_buffers(ctx, ws, p, sizeof(PtI), sizeof(Jacobian)))) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_a.p, buckets_be32, in_bytes, hipMemcpyHostToDevice, st));
   const size_t words = (size_t)buckets_size * num_windows * 3;
   launch_be32_to_le(st, (const uint32_t*)ctx->scratch_a.p, words, (uint32_t*)ctx->scratch_b.p);
-  launch_pad_buckets(st, (const Jacobian*)ctx->scratch_b.p, buckets_size, p.W, p.lb, (PtI*)ctx->ws[0].buckets.p);
-  if ((rc = enqueue_reduce(ctx, ctx->ws[0], st, p, (const PtI*)ctx->ws[0].buckets.p, nullptr))) return rc;
+  launch_pad_buckets(st, (const Jacobian*)ctx->scratch_b.p, buckets_size, p.W, p.lb, (PtI*)ws.buckets.p);
+  // every bucket holds a valid point: no bucket_size
+  launch_reduce(st, p, (const PtI*)ws.buckets.p, nullptr, (PtI*)ws.S.p, (PtI*)ws.T.p, (Jacobian*)ws.partial.p);
+  HIP_TRY(ctx, hipGetLastError());
   std::vector<Jacobian> partial(p.partial_count);
-  HIP_TRY(ctx, hipMemcpyAsync(partial.data(), ctx->ws[0].partial.p, p.partial_count * sizeof(Jacobian),
-                              hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(partial.data(), ws.partial.p, p.partial_count * sizeof(Jacobian), hipMemcpyDeviceToHost, st));
   if (int src_ = sync_stream_bounded(ctx, st, __func__)) return src_;
   // per-window value: reuse the fused Horner with a single window
   Plan one = p;
@@ -3081,10 +3143,7 @@ int msm_amd_test_last_plan(msm_amd_ctx* ctx, uint32_t j, uint32_t* out, size_t c
   std::lock_guard<std::mutex> g(ctx->mu);
   const Batch* B = nullptr;
   if (int rc = tap_batch(ctx, j, &B)) return rc;
-  const InstanceSlot& s = B->slots[j];
-  PlanCounters pc;
-  std::memcpy(&pc, s.h_partial + s.h_partial_cap, sizeof pc);
-  tap_plan_words(B->plans[j], pc, B->lone, (uint32_t)B->n_inst, (uint32_t)B->ws_index[j], out);
+  tap_plan_words(B->plans[j], B->slots[j].counters(), B->lone, (uint32_t)B->n_inst, (uint32_t)B->ws_index[j], out);
   return MSM_AMD_OK;
 }
 
@@ -3170,10 +3229,8 @@ int msm_amd_test_stage_copy(msm_amd_ctx* ctx, uint32_t j, int which, void* out, 
   const Batch* B = nullptr;
   if (int rc = tap_batch(ctx, j, &B)) return rc;
   const Workspace& w = ctx->ws[B->ws_index[j]];
-  PlanCounters pc;
-  std::memcpy(&pc, B->slots[j].h_partial + B->slots[j].h_partial_cap, sizeof pc);
   const TapPoints pts = {&w.buckets, &w.partial, sizeof(PtI), sizeof(Jacobian), 96, tap_g1_bucket, tap_g1_partial};
-  return tap_stage_copy(ctx, w, B->plans[j], pc, pts, which, out, bytes);
+  return tap_stage_copy(ctx, w, B->plans[j], B->slots[j].counters(), pts, which, out, bytes);
 }
 
 // Point-valued workspace buffers only: a poisoned index or count could make a kernel gather from wild addresses, a
@@ -3186,14 +3243,12 @@ int msm_amd_test_fill_workspaces(msm_amd_ctx* ctx, uint8_t byte) {
     if (b.active) return fail(ctx, MSM_AMD_INPUT_ERROR, "test_fill_workspaces: a batch is in flight");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!drain_or_mark_stalled(ctx)) return fail(ctx, MSM_AMD_PIPELINE_ERROR, "test_fill_workspaces: device busy");
-  for (Workspace& w : ctx->ws) {
-    DeviceBuf* bufs[] = {&w.buckets, &w.item_partials, &w.S, &w.T, &w.partial};
-    for (DeviceBuf* b : bufs)
+  Workspace* all[kWorkspaces + 1];
+  for (int k = 0; k < kWorkspaces; ++k) all[k] = &ctx->ws[k];
+  all[kWorkspaces] = &ctx->g2.ws;
+  for (Workspace* w : all)
+    for (DeviceBuf* b : {&w->buckets, &w->item_partials, &w->S, &w->T, &w->partial})
       if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
-  }
-  G2State& g2 = ctx->g2;   // the G2 MSM's own point buffers (its index and count buffers live in g2.ws: untouched)
-  for (DeviceBuf* b : {&g2.buckets, &g2.item_partials, &g2.S, &g2.T, &g2.partial})
-    if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
   return sync_stream_bounded(ctx, ctx->stream, __func__);
 }
 
@@ -3218,20 +3273,17 @@ uint64_t msm_amd_algorithmic_bytes(size_t n, uint32_t window_size, int accumulat
 // ---- BN254 G2 MSM (one blocking call on the main stream) -----------------------------------------------------------
 namespace {
 
-// d_points: n records of a host layout, a prepared array (MSM_AMD_G2_POINT_PREPARED: no base conversion) or a table
-// handle (MSM_AMD_G2_POINT_TABLES: the one-window plan of enqueue_msm, every digit window adds into one bucket set).
-// The whole G2 MSM of device-resident inputs: scalar conversion, digits and sort as in enqueue_msm (front_buffers on
-// the G2 state's own workspace), then the G2 kernels, the copy of the partial points, a bounded wait and the
-// host Horner pass.  ctx->mu held by the caller.
+// The whole G2 MSM of device-resident inputs: one lone instance (enqueue_instance with the G2 launches) in the G2
+// state's own workspace and slot on the main stream, a bounded wait and the host Horner pass.  d_points: n records of a
+// host layout, a prepared array (MSM_AMD_G2_POINT_PREPARED: no base conversion) or a table handle
+// (MSM_AMD_G2_POINT_TABLES: the one-window plan, every digit window adds into one bucket set).  ctx->mu held by the caller.
 int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars, const void* d_points,
                size_t n, void* out192) {
-  ctx->g2.has_last_plan = false;   // the stage tap reads nothing of a call that failed
+  G2State& g2 = ctx->g2;
+  g2.has_last_plan = false;   // the stage tap reads nothing of a call that failed
   if (n > 0x7FFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, "n >= 2^31");
   if (int rc = recover_if_stalled(ctx)) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  G2State& g = ctx->g2;
-  Workspace& w = g.ws;
-  hipStream_t st = ctx->stream;
   const msm_amd_g2_tables* tb = nullptr;
   if (g2_point_layout == MSM_AMD_G2_POINT_TABLES) {   // d_points is the handle of msm_amd_g2_tables_build*
     tb = find_tables(ctx->live_g2_tables, d_points);
@@ -3240,85 +3292,42 @@ int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const v
   }
   const bool prepared = tb != nullptr || g2_point_layout == MSM_AMD_G2_POINT_PREPARED;
   const uint32_t c = tb ? tb->c : (ctx->forced_window ? ctx->forced_window : auto_window_lone(n));
-  Plan p = tb ? make_plan(n, c, tb->W) : make_plan(n, c);
-  p.red_group = pick_reduce_group(p);
-  p.rb_threads = 0;
-  int rc;
-  if (!g.has_events) {
-    for (hipEvent_t& e : g.ev) HIP_TRY(ctx, hipEventCreate(&e));
-    g.has_events = true;
-  }
-  if (p.partial_count > g.h_partial_cap) {
-    if ((rc = quiesce_for_allocation(ctx, "the page-locked G2 result slot"))) return rc;
-    if (g.h_partial) HIP_TRY(ctx, hipHostFree(g.h_partial));
-    g.h_partial = nullptr;
-    g.h_partial_cap = 0;
-    HIP_TRY(ctx, hipHostMalloc((void**)&g.h_partial, p.partial_count * sizeof(Jacobian2), hipHostMallocDefault));
-    g.h_partial_cap = p.partial_count;
-  }
-  SortBuffers sb{};
-  if ((rc = front_buffers(ctx, w, p, &sb))) return rc;
-  if (!prepared && (rc = ensure(ctx, g.bases, n * sizeof(Aff2Packed)))) return rc;
-  if ((rc = ensure(ctx, g.buckets, p.total_buckets * sizeof(PtI2)))) return rc;
-  if ((rc = ensure(ctx, g.item_partials, p.max_items * sizeof(PtI2)))) return rc;
-  if ((rc = ensure(ctx, g.S, p.total_segs * sizeof(PtI2)))) return rc;
-  if ((rc = ensure(ctx, g.T, p.total_segs * sizeof(PtI2)))) return rc;
-  if ((rc = ensure(ctx, g.partial, p.partial_count * sizeof(Jacobian2)))) return rc;
-  HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_START], st));
-  const u256* sc = nullptr;
-  const Affine* unused = nullptr;
-  int sc_mont = 0;
-  if ((rc = convert_inputs(ctx, w, st, scalar_layout, MSM_AMD_POINT_PREPARED, d_scalars, nullptr, p.n_scalars, &sc,
-                           &sc_mont, &unused)))
-    return rc;
-  const Aff2Packed* bases = tb ? (const Aff2Packed*)tb->d_tables
-                               : (prepared ? (const Aff2Packed*)d_points : (const Aff2Packed*)g.bases.p);
-  if (!prepared)
-    launch_convert_bases_g2(st, d_points, g2_point_layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n,
-                            (Aff2Packed*)g.bases.p);
-  HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_CONVERT], st));
-  if (p.fused_front) launch_digits_hist(st, p, sc, sc_mont, sb); else launch_digits(st, p, sc, sc_mont, sb.digits);
-  HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_DIGITS], st));
-  launch_sort(st, p, sb, p.fused_front);
-  HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_SORT], st));
-  // the bucket matrix is not cleared: the window reduction reads bucket_size (see enqueue_msm)
-  launch_accumulate_g2(st, p, bases, sb, (PtI2*)g.buckets.p, (PtI2*)g.item_partials.p);
-  launch_combine_g2(st, p, sb, (PtI2*)g.buckets.p, (PtI2*)g.item_partials.p);
-  HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_ACC], st));
-  launch_reduce_g2(st, p, (const PtI2*)g.buckets.p, (const uint32_t*)w.bsize.p, (PtI2*)g.S.p, (PtI2*)g.T.p,
-                   (Jacobian2*)g.partial.p);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(g.h_partial, g.partial.p, p.partial_count * sizeof(Jacobian2), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipEventRecord(g.ev[G2State::EV_G2_REDUCE], st));
-  const hipError_t we = wait_event(g.ev[G2State::EV_G2_REDUCE], ctx->wait_timeout_ms);
-  if (we == hipErrorNotReady) {
-    ctx->stalled = true;
-    return fail(ctx, MSM_AMD_PIPELINE_ERROR,
-                "timed out after " + std::to_string(ctx->wait_timeout_ms) + " ms waiting for the G2 MSM");
-  }
+  const Plan p = instance_plan(n, c, tb ? tb->W : 0, true);
+  Workspace& w = g2.ws;
+  InstanceSlot& slot = g2.slot;
+  PointStages g;
+  g.bases_bytes = prepared ? 0 : n * sizeof(Aff2Packed);
+  g.internal_bytes = sizeof(PtI2);
+  g.ext_bytes = sizeof(Jacobian2);
+  g.convert_bases = [&](hipStream_t st) -> int {
+    if (!prepared)
+      launch_convert_bases_g2(st, d_points, g2_point_layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n,
+                              (Aff2Packed*)w.bases29.p);
+    return MSM_AMD_OK;
+  };
+  g.accumulate = [&](hipStream_t st, const SortBuffers& sb, hipEvent_t before, hipEvent_t after) {
+    const void* bases = tb ? tb->d_tables : (prepared ? d_points : w.bases29.p);
+    (void)hipEventRecord(before, st);
+    launch_accumulate_g2(st, p, (const Aff2Packed*)bases, sb, (PtI2*)w.buckets.p, (PtI2*)w.item_partials.p);
+    (void)hipEventRecord(after, st);
+  };
+  g.combine = [&](hipStream_t st, const SortBuffers& sb) { launch_combine_g2(st, p, sb, (PtI2*)w.buckets.p, (PtI2*)w.item_partials.p); };
+  g.reduce = [&](hipStream_t st) {
+    launch_reduce_g2(st, p, (const PtI2*)w.buckets.p, (const uint32_t*)w.bsize.p, (PtI2*)w.S.p, (PtI2*)w.T.p, (Jacobian2*)w.partial.p);
+  };
+  if (int rc = enqueue_instance(ctx, w, slot, p, true, scalar_layout, d_scalars, g)) return rc;
+  const hipError_t we = wait_event(slot.ev[EV_REDUCE], ctx->wait_timeout_ms);
+  if (we == hipErrorNotReady) return wait_timed_out(ctx, slot, "the G2 MSM");
   if (we != hipSuccess) return fail(ctx, MSM_AMD_PIPELINE_ERROR, std::string("G2 MSM: ") + hipGetErrorString(we));
   const auto t0 = std::chrono::steady_clock::now();
-  const Jacobian2 res = host_combine_g2(g.h_partial, p);
+  const Jacobian2 res = host_combine_g2((const Jacobian2*)slot.h_partial, p);
   const float final_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
   std::memcpy(out192, &res, 192);
-  auto span = [&](int a, int b) { return event_span(g.ev[a], g.ev[b]); };
-  msm_amd_timings& T = ctx->timings;
-  T = msm_amd_timings{};
-  T.convert_ms = span(G2State::EV_G2_START, G2State::EV_G2_CONVERT);
-  T.digits_ms = span(G2State::EV_G2_CONVERT, G2State::EV_G2_DIGITS);
-  T.sort_ms = span(G2State::EV_G2_DIGITS, G2State::EV_G2_SORT);
-  T.accumulate_ms = span(G2State::EV_G2_SORT, G2State::EV_G2_ACC);
-  T.accumulate_kernel_ms = T.accumulate_ms;
-  T.reduce_ms = span(G2State::EV_G2_ACC, G2State::EV_G2_REDUCE);
-  T.total_gpu_ms = span(G2State::EV_G2_START, G2State::EV_G2_REDUCE);
-  T.final_ms = final_ms;
-  T.n = (uint32_t)n;
-  T.window_size = p.c;
-  T.num_windows = p.W_digits;
-  T.reserved = 1;
+  ctx->timings = msm_amd_timings{};
+  accumulate_timings(ctx, slot, p, final_ms, 1);
   reap_graveyard(ctx);
-  g.last_plan = p;
-  g.has_last_plan = true;
+  g2.last_plan = p;
+  g2.has_last_plan = true;
   return MSM_AMD_OK;
 }
 
@@ -3502,26 +3511,17 @@ int msm_amd_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, con
     return MSM_AMD_OK;
   }
   std::lock_guard<std::mutex> lk(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (int rc = recover_if_stalled(ctx)) return rc;
   G2State& g = ctx->g2;
-  const size_t sb = n * 32, pb = n * msm_amd_g2_point_bytes(g2_point_layout);
-  int rc;
-  if ((rc = ensure(ctx, g.in_scalars, sb))) return rc;
-  if ((rc = ensure(ctx, g.in_points, pb))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(g.in_scalars.p, scalars, sb, hipMemcpyHostToDevice, ctx->stream));
+  const size_t pb = n * msm_amd_g2_point_bytes(g2_point_layout);
+  if (int rc = g2_stage_scalars(ctx, scalars, n)) return rc;
+  if (int rc = ensure(ctx, g.in_points, pb)) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(g.in_points.p, points, pb, hipMemcpyHostToDevice, ctx->stream));
   return run_msm_g2(ctx, scalar_layout, g2_point_layout, g.in_scalars.p, g.in_points.p, n, out192);
 }
 
-// Stage tap of the G2 MSM (test aid): plan, plan counters and buffers of the last run_msm_g2, read after the call.
-// The counters are still in the G2 workspace (nothing but a G2 call writes it) and are copied here, not in the call.
-static int tap_g2(msm_amd_ctx* ctx, PlanCounters* pc) {
-  if (!ctx->g2.has_last_plan) return fail(ctx, MSM_AMD_INPUT_ERROR, "G2 stage tap: no G2 MSM of this ctx has succeeded last");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipMemcpyAsync(pc, ctx->g2.ws.counters.p, sizeof *pc, hipMemcpyDeviceToHost, ctx->stream));
-  return sync_stream_bounded(ctx, ctx->stream, __func__);
-}
+// Stage tap of the G2 MSM (test aid): plan, plan counters (behind the partial points in the G2 slot, as for a G1
+// instance) and buffers of the last run_msm_g2, read after the call.
+static const char* const kNoG2Plan = "G2 stage tap: no G2 MSM of this ctx has succeeded last";
 
 // G2 point buffers leave in the result form of msm_amd_msm_g2 (192 B Jacobian, Montgomery LE; identity: z all zero)
 static void tap_g2_bucket(const uint8_t* rec, uint8_t* out) {
@@ -3536,21 +3536,19 @@ int msm_amd_test_g2_last_plan(msm_amd_ctx* ctx, uint32_t* out, size_t count) {
   if (!ctx || !out || count < MSM_AMD_TEST_PLAN_WORDS)
     return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_g2_last_plan arguments");
   std::lock_guard<std::mutex> lk(ctx->mu);
-  PlanCounters pc;
-  if (int rc = tap_g2(ctx, &pc)) return rc;
-  tap_plan_words(ctx->g2.last_plan, pc, true, 1, 0, out);
+  if (!ctx->g2.has_last_plan) return fail(ctx, MSM_AMD_INPUT_ERROR, kNoG2Plan);
+  tap_plan_words(ctx->g2.last_plan, ctx->g2.slot.counters(), true, 1, 0, out);
   return MSM_AMD_OK;
 }
 
 int msm_amd_test_g2_stage_copy(msm_amd_ctx* ctx, int which, void* out, size_t* bytes) {
   if (!ctx || !bytes) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_g2_stage_copy arguments");
   std::lock_guard<std::mutex> lk(ctx->mu);
-  PlanCounters pc;
-  if (int rc = tap_g2(ctx, &pc)) return rc;
   const G2State& g = ctx->g2;
-  const TapPoints pts = {&g.buckets, &g.partial, sizeof(PtI2), sizeof(Jacobian2), sizeof(Jacobian2), tap_g2_bucket,
+  if (!g.has_last_plan) return fail(ctx, MSM_AMD_INPUT_ERROR, kNoG2Plan);
+  const TapPoints pts = {&g.ws.buckets, &g.ws.partial, sizeof(PtI2), sizeof(Jacobian2), sizeof(Jacobian2), tap_g2_bucket,
                          tap_g2_partial};
-  return tap_stage_copy(ctx, g.ws, g.last_plan, pc, pts, which, out, bytes);
+  return tap_stage_copy(ctx, g.ws, g.last_plan, g.slot.counters(), pts, which, out, bytes);
 }
 
 int msm_amd_test_op_g2(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {

@@ -167,3 +167,106 @@ def test_g1_unchanged_by_g2_calls(cfg, msm_pkg):
     finally:
         cfg.free(dp)
         cfg.free(ds)
+
+
+# ---- one instance body for G1 and G2: the G2 call in its own workspace and slot ---------------------------------------
+def _g1_on_device(cfg, seed, n):
+    """(d_scalars, d_points, the C oracle's result as a canonical affine point) of a generated G1 instance"""
+    from oracle import bn254_ref as o
+    from oracle import c_oracle as co
+    points, scalars = co.gen_instance(seed, n)
+    ds, dp = cfg.alloc(len(scalars)), cfg.alloc(len(points))
+    cfg.to_device(ds, scalars)
+    cfg.to_device(dp, points)
+    return ds, dp, o.decode_jacobian_mont_le(co.msm_best(scalars, points, n, 2))
+
+
+def _assert_g1(out, exp):
+    from oracle import bn254_ref as o
+    assert o.decode_jacobian_mont_le(out) == exp
+
+
+def test_g2_between_g1_submit_and_wait(cfg, msm_pkg):
+    """a G2 MSM while a G1 batch of the same ctx is between submit and wait: the G2 call runs in its own workspace and
+    slot, so neither disturbs the other"""
+    from oracle import bn254_ref as o
+    n1, n2 = 1 << 10, 1 << 8
+    sc2, pts2, exp2 = progression_instance(msm_pkg, n2, 0xABCDE, 0x1357, 8)
+    g1 = [_g1_on_device(cfg, o.SEED_BASE + 30 + i, n1) for i in range(2)]
+    try:
+        h = cfg.submit_batch_device([i[0] for i in g1], [i[1] for i in g1], [n1, n1])
+        out2 = cfg.msm_g2(sc2, pts2, n2, scalar_layout=SCALAR_CANON_LE)
+        outs = cfg.wait_batch(h)
+        th.assert_result(out2, exp2)
+        assert out2 == msm_pkg.host_msm_g2(sc2, pts2, n2, threads=4, scalar_layout=SCALAR_CANON_LE)
+        for out, inst in zip(outs, g1):
+            _assert_g1(out, inst[2])
+    finally:
+        for ds, dp, _ in g1:
+            cfg.free(ds)
+            cfg.free(dp)
+
+
+def test_g2_timings_mean_what_g1_timings_mean(cfg, msm_pkg):
+    """msm_amd_last_timings after a G2 call whose combine pass runs (equal scalars: every window has one bucket of 2^8
+    points, cut into items of CH = 16): the accumulate fields are the accumulate kernel alone, the total is the sum of
+    the stage spans and reserved2[0] the work items, as for a G1 instance"""
+    n = 1 << 8
+    d = 4242
+    pts = msm_pkg.g2_progression(g.encode_h2c(g.scalar_mul(d, g.GEN2)), g.encode_h2c(g.scalar_mul(d, g.GEN2)), n)
+    k = 0x0FEDCBA987654321FEDCBA9876543210F
+    out = cfg.msm_g2(g.encode_scalar(k, 1) * n, pts, n, scalar_layout=SCALAR_CANON_LE)
+    t = cfg.timings()
+    p = cfg.test_g2_last_plan()
+    th.assert_result(out, g.scalar_mul(k * d * (n * (n + 1) // 2) % g.R_ORDER, g.GEN2))
+    assert p["CH"] == 16 and p["multi_count"] > 0, p   # the combine pass had work
+    assert (t.n, t.window_size, t.num_windows) == (p["n_scalars"], p["c"], p["W_digits"])
+    assert t.n == n
+    assert t.reserved == 1
+    assert t.reserved2[0] == p["total_items"]
+    assert t.accumulate_kernel_ms == t.accumulate_ms
+    stages = (t.convert_ms, t.digits_ms, t.sort_ms, t.accumulate_ms, t.reduce_ms)
+    print("G2 timings:", stages, t.total_gpu_ms)
+    assert all(s > 0.0 for s in stages[1:]), stages
+    assert t.total_gpu_ms == pytest.approx(sum(stages), rel=1e-6)   # a float sum of five floats
+
+
+def test_g2_slot_reuse_across_sizes_and_groups(msm_pkg):
+    """2^6, 2^10 and 2^6 points again through one ctx (the G2 slot and workspace grow, then hold a smaller instance), a
+    lone G1 call in between: every result exact, and after every G2 call the plan tap reads what a fresh ctx reads"""
+    from oracle import bn254_ref as o
+    COUNTERS = ("total_items", "multi_count", "deferred")
+    small = progression_instance(msm_pkg, 1 << 6, 77, 5, 6)
+    big = progression_instance(msm_pkg, 1 << 10, 99, 3, 10)
+    ctx = msm_pkg.MsmConfig(0)
+    try:
+        def g2_call(c, inst):
+            sc, pts, exp = inst
+            n = len(sc) // 32
+            out = c.msm_g2(sc, pts, n, scalar_layout=SCALAR_CANON_LE)
+            th.assert_result(out, exp)
+            assert out == msm_pkg.host_msm_g2(sc, pts, n, threads=4, scalar_layout=SCALAR_CANON_LE)
+            return c.test_g2_last_plan()
+
+        fresh = {}
+        for name, inst in (("small", small), ("big", big)):
+            f = msm_pkg.MsmConfig(0)
+            try:
+                fresh[name] = g2_call(f, inst)
+            finally:
+                f.close()
+        assert fresh["small"]["total_items"] != fresh["big"]["total_items"]
+        n1 = 1 << 10
+        ds, dp, exp1 = _g1_on_device(ctx, o.SEED_BASE + 40, n1)
+        try:
+            for name, inst in (("small", small), ("big", big), ("small", small)):
+                p = g2_call(ctx, inst)
+                assert p == fresh[name], (name, {k: (p[k], fresh[name][k]) for k in COUNTERS})
+                _assert_g1(ctx.msm_batch_device([ds], [dp], [n1])[0], exp1)
+                assert ctx.test_last_plan()["lone"] == 1
+                assert ctx.test_g2_last_plan() == fresh[name]   # the G1 call left the G2 slot alone
+        finally:
+            ctx.free(ds)
+            ctx.free(dp)
+    finally:
+        ctx.close()

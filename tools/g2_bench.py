@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """G2 MSM timing on one ctx: one JSON line with, per size (2^16, 2^18, 2^20), the median ms of a lone blocking G2 call
 on device-resident inputs, the G1 lone call on device-resident inputs of the same size, their ratio and the G2 stage
-split from the library's HIP events (msm_amd_last_timings), plus the CPU G2 MSM at 2^16.
+split from the library's HIP events (msm_amd_last_timings: G1's definitions -- `accumulate` is the accumulate kernel
+alone, the combine pass counts under `combine_reduce_copy`, `gpu_total` is the sum of the spans), plus the CPU G2 MSM
+at 2^16.
 Next to that per-call figure (`g2_ms`, the caller layout converted on every call), the same scalars through prepared
 bases (`prepared_ms`) and through precomputed window tables at the automatic window (`tables_ms`): median, min and max
 of each series, their stage splits, the table's window / windows / bytes and `tables_build_ms`; and one host-caller row
@@ -53,7 +55,7 @@ def main():
                     ms.append((time.perf_counter() - t0) * 1e3)
                     t = cfg.timings()
                     split.append({"convert": t.convert_ms, "digits": t.digits_ms, "sort": t.sort_ms,
-                                  "accumulate_combine": t.accumulate_ms, "reduce_copy": t.reduce_ms,
+                                  "accumulate": t.accumulate_ms, "combine_reduce_copy": t.reduce_ms,
                                   "host_horner": t.final_ms, "gpu_total": t.total_gpu_ms, "window": t.window_size})
                 return ms, split
 
