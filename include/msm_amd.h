@@ -494,7 +494,11 @@ enum {
   /* the point additions' forms with wide quotient digits (reduce_columns<true>): 20..31 stay unknown */
   MSM_AMD_RAW_FE_MUL_WIDE = 32,  /* mul_np(a0, b0) */
   MSM_AMD_RAW_FE_SQR_WIDE = 33,  /* sqr_np(a0) */
-  MSM_AMD_RAW_FE_MUL2_WIDE = 34  /* mul2w_np(a0, a1, b0, b1) */
+  MSM_AMD_RAW_FE_MUL2_WIDE = 34, /* mul2w_np(a0, a1, b0, b1) */
+  /* 35 stays unknown (tests pin it as refused) */
+  MSM_AMD_RAW_FE_SQRT = 36       /* square root of a0 (normalised, < 8 p) by the ladder of the decompression kernels
+                                    (csrc/compress_points.hip.h): out[0..8] = root, out[9] = 1 if there is one, else
+                                    all zero; b ignored */
 };
 int msm_amd_test_op_raw(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count);
 /* The same bodies on the host CPU (no GPU needed). */
@@ -625,7 +629,10 @@ enum {
   MSM_AMD_G2_RAW_PT_ADD = 5,     /* XYZZ a + XYZZ b, identities allowed */
   MSM_AMD_G2_RAW_PT_DOUBLE = 6,  /* 2 a, a not the identity */
   MSM_AMD_G2_RAW_FQ2_INV = 7,    /* a^-1, a != 0, a < 32 p */
-  MSM_AMD_G2_RAW_PT_TO_AFFINE = 8 /* XYZZ a (not the identity) -> affine x, y in words 0..35, canonical limbs */
+  MSM_AMD_G2_RAW_PT_TO_AFFINE = 8, /* XYZZ a (not the identity) -> affine x, y in words 0..35, canonical limbs */
+  /* 9 stays unknown (tests pin it as refused) */
+  MSM_AMD_G2_RAW_FQ2_SQRT = 10   /* square root of the fq2 a (components normalised, < 4 p) as the G2 decompression
+                                    takes it: root in words 0..17, word 72 = 1 if there is one, else all zero */
 };
 int msm_amd_test_op_g2(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count);
 /* The same bodies on the host CPU (no GPU needed). */
@@ -642,13 +649,16 @@ int msm_amd_test_g2_table_host(int g2_point_layout, const void* points, size_t n
 /* ---- point validation (G1 and G2) ------------------------------------------------------------------
  * The MSM entry points multiply whatever they are handed.  These calls judge a point array first -- the one-time check
  * of a proving key or an SRS before msm_amd_tables_build / msm_amd_g2_tables_build.  Every record gets ONE reason code,
- * the first rule that fails; the rule is the same on the GPU and in the host twins. */
+ * the first rule that fails; the rule is the same on the GPU and in the host twins.  A key that arrives compressed goes
+ * through msm_amd_decompress_points* (below) first: decompress, then check, then tables. */
 enum {
   MSM_AMD_POINT_VALID = 0,           /* passes every requested check */
   MSM_AMD_POINT_NOT_REDUCED = 1,     /* some coordinate, read as a 256-bit integer in the layout's own form (the
                                         Montgomery residue), is >= p */
   MSM_AMD_POINT_NOT_ON_CURVE = 2,    /* G1: y^2 != x^3 + 3 (Jacobian layouts: Y^2 != X^3 + 3 Z^6); G2: y^2 != x^3 + 3 / (9 + u) */
-  MSM_AMD_POINT_NOT_IN_SUBGROUP = 3  /* G2 only: on the curve, but [r] P != O */
+  MSM_AMD_POINT_NOT_IN_SUBGROUP = 3, /* G2 only: on the curve, but [r] P != O */
+  MSM_AMD_POINT_BAD_ENCODING = 4     /* compressed records only (msm_amd_decompress_points* below): flag bits that no
+                                        encoder writes; never produced by the checks of this section */
 };
 /* Identity encodings are valid: (0, 0) / all zero in the halo2curves layouts; the infinity flag of the ark affine
  * layouts (whatever the coordinate bytes of a flagged record); Z = 0 in the two G1 Jacobian layouts (whose coordinates
@@ -686,6 +696,88 @@ int msm_amd_host_check_points(int point_layout, const void* points, size_t n, ui
                               uint8_t* reasons, msm_amd_check_report* report);
 int msm_amd_host_g2_check_points(int g2_point_layout, const void* points, size_t n, uint32_t checks, int threads,
                                  uint8_t* reasons, msm_amd_check_report* report);
+
+/* ---- compressed points (G1 and G2) ------------------------------------------------------------------
+ * Keys travel and rest compressed: x and one or two flag bits, 32 B per G1 point and 64 B per G2 point.  These calls
+ * decompress on the GPU (one modular square root per G1 point; two, and an inversion, per G2 point) and compress (a few
+ * instructions per point).  Both formats store x as the CANONICAL integer (not Montgomery), little-endian, 32 B; for G2
+ * x.c0 comes first, then x.c1, 64 B in all.  p < 2^254, so the top two bits of the LAST byte (byte 31 for G1, byte 63
+ * for G2) are free and carry the flags; "x" below is the integer after those two bits are masked off.
+ *   MSM_AMD_COMPRESSED_ARK     what ark-serialize 0.4 writes for ark_bn254::G1Affine / G2Affine in compressed mode:
+ *                              0x80 set: y is the LARGER of {y, p - y};  0x40 set: the record is the identity.
+ *                              Order on Fq: the canonical integers.  Order on Fq2: compare c1 first, c0 on a tie.
+ *   MSM_AMD_COMPRESSED_PARITY  the halo2curves-family convention:
+ *                              0x80 set: the record is the identity;  0x40 set: sign(y) = 1.
+ *                              G1: sign(y) is the least significant bit of canonical y.  G2: sign(y) is the least
+ *                              significant bit of y.c0, or of y.c1 when y.c0 = 0 (for every y != 0 exactly one of y
+ *                              and -y has sign 1).
+ * The written rule is the contract.  Byte compatibility with a particular release of the crates named above is
+ * UNPINNED (neither crate was available to test against) -- least certain for the G2 case of
+ * PARITY.  Values from 2 on are free for further formats (gnark's big-endian form is not implemented).
+ *
+ * Decoding is strict.  Each record gets ONE reason code, the first rule that fails, in this order:
+ *   4 MSM_AMD_POINT_BAD_ENCODING  both flag bits are set, or the identity flag is set together with any non-zero bit
+ *                                 of x (a flagged identity has all other 255 / 511 bits zero)
+ *   1 MSM_AMD_POINT_NOT_REDUCED   x >= p, or (G2) either component >= p
+ *   2 MSM_AMD_POINT_NOT_ON_CURVE  x^3 + 3 (G1) or x^3 + 3 / (9 + u) (G2) has no square root
+ *   0 MSM_AMD_POINT_VALID         otherwise.  Reason 3 is never produced here: the subgroup test stays with
+ *                                 msm_amd_g2_check_points*.  Recipe for an untrusted G2 key: decompress, then
+ *                                 msm_amd_g2_check_points_device(..., MSM_AMD_CHECK_SUBGROUP) on the output, then
+ *                                 msm_amd_g2_tables_build_device. */
+enum {
+  MSM_AMD_COMPRESSED_ARK = 0,
+  MSM_AMD_COMPRESSED_PARITY = 1
+};
+typedef struct msm_amd_decompress_report {
+  uint64_t n_checked, n_invalid, n_identity, first_invalid;  /* as msm_amd_check_report */
+  uint32_t first_reason, by_reason[5];
+  float device_ms;
+} msm_amd_decompress_report;
+/* Bytes per compressed record: 32 for group 1, 64 for group 2; 0 for an unknown format or group. */
+size_t msm_amd_compressed_bytes(int format, int group /* 1 or 2 */);
+/* Decompression: n records of `in` -> n records of `out` in point_layout_out, reasons (n bytes, may be NULL) and the
+ * report.  Output layouts: G1 MSM_AMD_POINT_H2C_AFFINE / _ARK_AFFINE, G2 MSM_AMD_G2_POINT_H2C_AFFINE / _ARK_AFFINE; the
+ * _device calls also take MSM_AMD_POINT_PREPARED / MSM_AMD_G2_POINT_PREPARED and then write, bit for bit, the 64-byte /
+ * 128-byte records msm_amd_bases_prepare_device / msm_amd_g2_bases_prepare_device would write from the decompressed
+ * affine points: a compressed key on the device becomes MSM-ready bases in one pass, usable at once with
+ * msm_amd_msm_device / msm_amd_msm_g2_device / *_tables_build_device.  An invalid record yields the layout's identity
+ * encoding in `out` (all zero; ark affine: zero coordinates and the flag byte 1) and its reason in `reasons`: the output
+ * is always fully defined.
+ * Status and arguments as msm_amd_check_points*: MSM_AMD_OK means the pass ran; n == 0: OK and an empty report;
+ * MSM_AMD_INPUT_ERROR: an unknown format or layout, *_TABLES, *_PREPARED on a host-buffer or host-twin call, a null
+ * pointer with n > 0, a null report, n >= 2^32.  The ctx calls serialise on the ctx and first wait -- bounded -- for its
+ * earlier work (a busy ctx: MSM_AMD_PIPELINE_ERROR, msm_amd_last_error names the call); host buffers go up in chunks
+ * through the page-locked staging ring; a G2 call touches the G2 state of the ctx only. */
+int msm_amd_decompress_points(msm_amd_ctx* ctx, int format, const void* in, size_t n, int point_layout_out, void* out,
+                              uint8_t* reasons, msm_amd_decompress_report* report);
+int msm_amd_decompress_points_device(msm_amd_ctx* ctx, int format, const void* d_in, size_t n, int point_layout_out,
+                                     void* d_out, uint8_t* d_reasons, msm_amd_decompress_report* report);
+int msm_amd_g2_decompress_points(msm_amd_ctx* ctx, int format, const void* in, size_t n, int g2_point_layout_out,
+                                 void* out, uint8_t* reasons, msm_amd_decompress_report* report);
+int msm_amd_g2_decompress_points_device(msm_amd_ctx* ctx, int format, const void* d_in, size_t n,
+                                        int g2_point_layout_out, void* d_out, uint8_t* d_reasons,
+                                        msm_amd_decompress_report* report);
+/* The same on the CPU (no ctx, no GPU; the same bodies compiled for the host); threads <= 0: up to 16 host threads. */
+int msm_amd_host_decompress_points(int format, const void* in, size_t n, int point_layout_out, int threads, void* out,
+                                   uint8_t* reasons, msm_amd_decompress_report* report);
+int msm_amd_host_g2_decompress_points(int format, const void* in, size_t n, int g2_point_layout_out, int threads,
+                                      void* out, uint8_t* reasons, msm_amd_decompress_report* report);
+/* Compression: n affine records (the two affine host layouts of the group) -> n compressed records.  An identity
+ * encoding becomes the format's identity record.  A record whose stored coordinate is >= p is written as all 0xFF (no
+ * valid encoding in either format) and counted in *n_bad (may be NULL).  Points are not checked for being on the curve.
+ * Status and argument rules as above (no report; *_PREPARED and *_TABLES are refused everywhere). */
+int msm_amd_compress_points(msm_amd_ctx* ctx, int point_layout_in, const void* in, size_t n, int format, void* out,
+                            uint64_t* n_bad);
+int msm_amd_compress_points_device(msm_amd_ctx* ctx, int point_layout_in, const void* d_in, size_t n, int format,
+                                   void* d_out, uint64_t* n_bad);
+int msm_amd_g2_compress_points(msm_amd_ctx* ctx, int g2_point_layout_in, const void* in, size_t n, int format, void* out,
+                               uint64_t* n_bad);
+int msm_amd_g2_compress_points_device(msm_amd_ctx* ctx, int g2_point_layout_in, const void* d_in, size_t n, int format,
+                                      void* d_out, uint64_t* n_bad);
+int msm_amd_host_compress_points(int point_layout_in, const void* in, size_t n, int format, int threads, void* out,
+                                 uint64_t* n_bad);
+int msm_amd_host_g2_compress_points(int g2_point_layout_in, const void* in, size_t n, int format, int threads, void* out,
+                                    uint64_t* n_bad);
 
 /* ---- introspection --------------------------------------------------------------------------- */
 int msm_amd_last_timings(const msm_amd_ctx* ctx, msm_amd_timings* out);

@@ -31,6 +31,7 @@ POINT_BYTES = {POINT_H2C_AFFINE: 64, POINT_ARK_PROJECTIVE: 96, POINT_ARK_AFFINE:
  RAW_FE_SUB_K16E31, RAW_FE_NORM, RAW_FE_NEG, RAW_FE_NEG_WIDE, RAW_FE_CANONICAL, RAW_FE_TO_EXT, RAW_FE_PACK_UNPACK,
  RAW_FE_ZERO, RAW_PT_MADD, RAW_PT_MMADD, RAW_PT_ADD_NZ, RAW_PT_ADD, RAW_PT_DOUBLE) = range(20)
 RAW_FE_MUL_WIDE, RAW_FE_SQR_WIDE, RAW_FE_MUL2_WIDE = range(32, 35)   # the point additions' wide-digit forms
+RAW_FE_SQRT = 36   # the Fq root of the decompression kernels (35 stays unknown)
 RAW_IN_WORDS, RAW_OUT_WORDS = 36, 40
 # BN254 G2 (MSM_AMD_G2_*): point layouts, raw-limb test ops and their record widths
 G2_POINT_H2C_AFFINE, G2_POINT_ARK_AFFINE, G2_POINT_PREPARED, G2_POINT_TABLES = 0, 1, 2, 3
@@ -38,10 +39,14 @@ G2_PREPARED_BYTES = 128
 G2_POINT_BYTES = {G2_POINT_H2C_AFFINE: 128, G2_POINT_ARK_AFFINE: 136}
 (G2_RAW_FQ2_MUL, G2_RAW_FQ2_SQR, G2_RAW_PT_MADD, G2_RAW_PT_MMADD, G2_RAW_PT_ADD_NZ, G2_RAW_PT_ADD,
  G2_RAW_PT_DOUBLE, G2_RAW_FQ2_INV, G2_RAW_PT_TO_AFFINE) = range(9)
+G2_RAW_FQ2_SQRT = 10   # the Fq2 root of the G2 decompression (9 stays unknown)
 G2_RAW_IN_WORDS, G2_RAW_OUT_WORDS = 72, 80
 # point validation (MSM_AMD_POINT_VALID ..., MSM_AMD_CHECK_*)
 POINT_VALID, POINT_NOT_REDUCED, POINT_NOT_ON_CURVE, POINT_NOT_IN_SUBGROUP = range(4)
 CHECK_CURVE, CHECK_SUBGROUP = 1, 2
+# compressed points (MSM_AMD_COMPRESSED_*, MSM_AMD_POINT_BAD_ENCODING)
+COMPRESSED_ARK, COMPRESSED_PARITY = 0, 1
+POINT_BAD_ENCODING = 4
 
 
 def op_is_point(op):
@@ -83,6 +88,11 @@ EXPORTS = [
     "msm_amd_msm_g2_tables", "msm_amd_test_g2_tables_read", "msm_amd_test_g2_table_host",
     "msm_amd_check_points", "msm_amd_check_points_device", "msm_amd_g2_check_points", "msm_amd_g2_check_points_device",
     "msm_amd_host_check_points", "msm_amd_host_g2_check_points",
+    "msm_amd_compressed_bytes", "msm_amd_decompress_points", "msm_amd_decompress_points_device",
+    "msm_amd_g2_decompress_points", "msm_amd_g2_decompress_points_device", "msm_amd_host_decompress_points",
+    "msm_amd_host_g2_decompress_points", "msm_amd_compress_points", "msm_amd_compress_points_device",
+    "msm_amd_g2_compress_points", "msm_amd_g2_compress_points_device", "msm_amd_host_compress_points",
+    "msm_amd_host_g2_compress_points",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -113,6 +123,12 @@ class CheckReport(ctypes.Structure):   # msm_amd_check_report
         return {"n_checked": self.n_checked, "n_invalid": self.n_invalid, "n_identity": self.n_identity,
                 "first_invalid": first, "first_reason": self.first_reason, "by_reason": list(self.by_reason),
                 "device_ms": self.device_ms}
+
+
+class DecompressReport(ctypes.Structure):   # msm_amd_decompress_report
+    _fields_ = [("n_checked", c_uint64), ("n_invalid", c_uint64), ("n_identity", c_uint64), ("first_invalid", c_uint64),
+                ("first_reason", c_uint32), ("by_reason", c_uint32 * 5), ("device_ms", c_float)]
+    as_dict = CheckReport.as_dict
 
 
 class MsmError(RuntimeError):
@@ -277,6 +293,20 @@ def _lib():
         L.msm_amd_g2_check_points_device.argtypes = L.msm_amd_check_points.argtypes
         L.msm_amd_host_check_points.argtypes = [c_int, c_void_p, c_size_t, c_uint32, c_int, c_void_p, POINTER(CheckReport)]
         L.msm_amd_host_g2_check_points.argtypes = L.msm_amd_host_check_points.argtypes
+        L.msm_amd_compressed_bytes.argtypes = [c_int, c_int]
+        L.msm_amd_compressed_bytes.restype = c_size_t
+        for name in ("msm_amd_decompress_points", "msm_amd_decompress_points_device", "msm_amd_g2_decompress_points",
+                     "msm_amd_g2_decompress_points_device"):
+            getattr(L, name).argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p, c_void_p,
+                                         POINTER(DecompressReport)]
+        for name in ("msm_amd_host_decompress_points", "msm_amd_host_g2_decompress_points"):
+            getattr(L, name).argtypes = [c_int, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p,
+                                         POINTER(DecompressReport)]
+        for name in ("msm_amd_compress_points", "msm_amd_compress_points_device", "msm_amd_g2_compress_points",
+                     "msm_amd_g2_compress_points_device"):
+            getattr(L, name).argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p, POINTER(c_uint64)]
+        for name in ("msm_amd_host_compress_points", "msm_amd_host_g2_compress_points"):
+            getattr(L, name).argtypes = [c_int, c_void_p, c_size_t, c_int, c_int, c_void_p, POINTER(c_uint64)]
         L.msm_amd_generate_instance_host.argtypes = [c_uint64, c_size_t, c_int, c_void_p, c_void_p, c_int]
         L.msm_amd_test_op_ifma.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_tuned_split.argtypes = [c_size_t]
@@ -672,6 +702,44 @@ class MsmConfig:
                                point_layout=G2_POINT_H2C_AFFINE, d_reasons=None):
         return self._check_device(_lib().msm_amd_g2_check_points_device, d_points, n, checks, point_layout, d_reasons)
 
+    # ---- compressed points -------------------------------------------------------------------------
+    def decompress_points(self, data: bytes, n: int, fmt=COMPRESSED_ARK, point_layout=POINT_H2C_AFFINE, g2=False,
+                          reasons=True):
+        """Decompress n records (32 B, G2: 64 B) on the GPU from host memory: (points bytes, report dict, n reason
+        bytes or None).  point_layout: an affine host layout of the group."""
+        fn = _lib().msm_amd_g2_decompress_points if g2 else _lib().msm_amd_decompress_points
+        out = ctypes.create_string_buffer(max(1, n * decompressed_bytes(point_layout, g2)))
+        rs = ctypes.create_string_buffer(max(n, 1)) if reasons else None
+        rep = DecompressReport()
+        self._check(fn(self.h, fmt, data, n, point_layout, out, rs, ctypes.byref(rep)))
+        return out.raw[:n * decompressed_bytes(point_layout, g2)], rep.as_dict(), (rs.raw[:n] if reasons else None)
+
+    def decompress_points_device(self, d_in, n: int, d_out, fmt=COMPRESSED_ARK, point_layout=POINT_PREPARED, g2=False,
+                                 d_reasons=None) -> dict:
+        """The same between device buffers; also takes POINT_PREPARED / G2_POINT_PREPARED (MSM-ready bases in one
+        pass).  Returns the report."""
+        fn = _lib().msm_amd_g2_decompress_points_device if g2 else _lib().msm_amd_decompress_points_device
+        rep = DecompressReport()
+        self._check(fn(self.h, fmt, c_void_p(d_in), n, point_layout, c_void_p(d_out), c_void_p(d_reasons),
+                       ctypes.byref(rep)))
+        return rep.as_dict()
+
+    def compress_points(self, points: bytes, n: int, fmt=COMPRESSED_ARK, point_layout=POINT_H2C_AFFINE, g2=False):
+        """Compress n affine points (a host layout) on the GPU: (records bytes, n_bad)."""
+        fn = _lib().msm_amd_g2_compress_points if g2 else _lib().msm_amd_compress_points
+        size = 64 if g2 else 32
+        out = ctypes.create_string_buffer(max(1, n * size))
+        bad = c_uint64(0)
+        self._check(fn(self.h, point_layout, points, n, fmt, out, ctypes.byref(bad)))
+        return out.raw[:n * size], bad.value
+
+    def compress_points_device(self, d_in, n: int, d_out, fmt=COMPRESSED_ARK, point_layout=POINT_H2C_AFFINE,
+                               g2=False) -> int:
+        fn = _lib().msm_amd_g2_compress_points_device if g2 else _lib().msm_amd_compress_points_device
+        bad = c_uint64(0)
+        self._check(fn(self.h, point_layout, c_void_p(d_in), n, fmt, c_void_p(d_out), ctypes.byref(bad)))
+        return bad.value
+
     def test_op_g2(self, op, a, b, count):
         """Raw-limb G2 op (MSM_AMD_G2_RAW_*) on the device: a, b flat u32 lists of count * G2_RAW_IN_WORDS; returns
         count * G2_RAW_OUT_WORDS u32."""
@@ -881,6 +949,43 @@ def host_g2_check_points(points: bytes, n: int, checks=CHECK_CURVE | CHECK_SUBGR
                          point_layout=G2_POINT_H2C_AFFINE, reasons=True):
     """Host twin of MsmConfig.g2_check_points (no GPU)."""
     return _host_check(_lib().msm_amd_host_g2_check_points, points, n, checks, threads, point_layout, reasons)
+
+
+def compressed_bytes(fmt, group) -> int:
+    return _lib().msm_amd_compressed_bytes(fmt, group)
+
+
+def decompressed_bytes(point_layout, g2=False) -> int:
+    """record size of an output layout of the decompression (prepared records included), 0 = not one"""
+    if g2:
+        return G2_PREPARED_BYTES if point_layout == G2_POINT_PREPARED else G2_POINT_BYTES.get(point_layout, 0)
+    return 64 if point_layout == POINT_PREPARED else {POINT_H2C_AFFINE: 64, POINT_ARK_AFFINE: 72}.get(point_layout, 0)
+
+
+def host_decompress_points(data: bytes, n: int, fmt=COMPRESSED_ARK, point_layout=POINT_H2C_AFFINE, g2=False, threads=0,
+                           reasons=True):
+    """Host twin of MsmConfig.decompress_points (no GPU): (points bytes, report dict, n reason bytes or None)."""
+    fn = _lib().msm_amd_host_g2_decompress_points if g2 else _lib().msm_amd_host_decompress_points
+    size = decompressed_bytes(point_layout, g2)
+    out = ctypes.create_string_buffer(max(1, n * size))
+    rs = ctypes.create_string_buffer(max(n, 1)) if reasons else None
+    rep = DecompressReport()
+    st = fn(fmt, data, n, point_layout, threads, out, rs, ctypes.byref(rep))
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:n * size], rep.as_dict(), (rs.raw[:n] if reasons else None)
+
+
+def host_compress_points(points: bytes, n: int, fmt=COMPRESSED_ARK, point_layout=POINT_H2C_AFFINE, g2=False, threads=0):
+    """Host twin of MsmConfig.compress_points (no GPU): (records bytes, n_bad)."""
+    fn = _lib().msm_amd_host_g2_compress_points if g2 else _lib().msm_amd_host_compress_points
+    size = 64 if g2 else 32
+    out = ctypes.create_string_buffer(max(1, n * size))
+    bad = c_uint64(0)
+    st = fn(point_layout, points, n, fmt, threads, out, ctypes.byref(bad))
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:n * size], bad.value
 
 
 def _g2_raw_in(seq, count):

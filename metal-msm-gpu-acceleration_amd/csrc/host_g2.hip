@@ -13,6 +13,7 @@
 #include "host_fq2_64.h"
 #include "launch_g2.h"
 #include "test_ops_g2.hip.h"
+#include "compress_points.hip.h"
 
 namespace msm_amd {
 
@@ -240,7 +241,12 @@ int msm_amd_test_g2_table_host(int g2_point_layout, const void* points, size_t n
 
 int msm_amd_test_op_g2_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
   using namespace msm_amd;
-  if (op < 0 || op >= G2RAW_OPS || (count > 0 && (!a || !b || !out))) return MSM_AMD_INPUT_ERROR;
+  if (op < 0 || (op >= G2RAW_OPS && op != MSM_AMD_G2_RAW_FQ2_SQRT) || (count > 0 && (!a || !b || !out)))
+    return MSM_AMD_INPUT_ERROR;
+  if (op == MSM_AMD_G2_RAW_FQ2_SQRT) {   // the root of the G2 decompression (compress_points.hip.h)
+    for (size_t i = 0; i < count; ++i) raw_sqrt_fq2(a + i * kG2RawIn, out + i * kG2RawOut);
+    return MSM_AMD_OK;
+  }
   for (size_t i = 0; i < count; ++i) run_test_op_g2(op, a + i * kG2RawIn, b + i * kG2RawIn, out + i * kG2RawOut);
   return MSM_AMD_OK;
 }

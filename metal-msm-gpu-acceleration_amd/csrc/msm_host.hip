@@ -28,6 +28,7 @@
 #include "launch.h"
 #include "launch_g2.h"
 #include "launch_check.h"
+#include "launch_compress.h"
 #include "host_fq64.h"
 #include "test_ops.hip.h"
 #include "test_ops_g2.hip.h"
@@ -192,6 +193,17 @@ struct CheckState {
   bool ready = false;
 };
 
+// Buffers of a decompress / compress call (msm_amd_decompress_points*, msm_amd_compress_points* and their G2 forms): the
+// 64-byte counters and their page-locked copy, the reason bytes and, for the host-buffer calls, the staging of the
+// caller's input and output.  One per group: a G2 call touches G2State only.
+struct CompressState {
+  enum { EV_COMP_START = 0, EV_COMP_KERNEL, EV_COMP_DONE, EV_COMP_COUNT };
+  DeviceBuf in, out, reasons, counters;
+  CompressCounters* h_counters = nullptr;   // pinned
+  hipEvent_t ev[EV_COMP_COUNT] = {};
+  bool ready = false;
+};
+
 // State of the G2 MSM (msm_amd_msm_g2*): one blocking call at a time on the main stream, through the instance body of
 // G1 (enqueue_instance) in a workspace and a slot of its own -- a G2 call never touches what a G1 instance of the same
 // ctx may still be using.  `ws` is used on the main stream only and therefore has no hand-off events.
@@ -200,6 +212,7 @@ struct G2State {
   InstanceSlot slot;
   DeviceBuf in_scalars, in_points;   // staging of host inputs
   CheckState check;   // msm_amd_g2_check_points*: host points are staged in in_points above
+  CompressState compress;   // msm_amd_g2_decompress_points*, msm_amd_g2_compress_points*
   // Stage tap (msm_amd_test_g2_last_plan / msm_amd_test_g2_stage_copy): the plan of the last run_msm_g2, valid only
   // while that call was the last one and succeeded.  Its plan counters are in `slot`, behind the partial points.
   Plan last_plan{};
@@ -229,6 +242,7 @@ struct msm_amd_ctx {
   Workspace ws[kWorkspaces];
   G2State g2;
   CheckState check;   // msm_amd_check_points* (G1)
+  CompressState compress;   // msm_amd_decompress_points*, msm_amd_compress_points* (G1)
   std::mutex mu;
   std::string last_error;
   uint32_t forced_window = 0;
@@ -2151,6 +2165,10 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
     for (hipEvent_t& e : cs->ev) kill_event(e);
     cs->ready = false;
   }
+  for (CompressState* cs : {&ctx->compress, &ctx->g2.compress}) {
+    for (hipEvent_t& e : cs->ev) kill_event(e);
+    cs->ready = false;
+  }
   for (hipEvent_t& e : ctx->uploaded) kill_event(e);
   kill_event(ctx->upload_done);
   kill_event(ctx->after_sort_mark);
@@ -2175,6 +2193,11 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
   kill_slot_memory(ctx->g2.slot);
   for (CheckState* cs : {&ctx->check, &ctx->g2.check}) {
     for (DeviceBuf* b : {&cs->in_points, &cs->reasons, &cs->counters}) kill_buf(*b);
+    if (cs->h_counters) (void)hipHostFree(cs->h_counters);
+    cs->h_counters = nullptr;
+  }
+  for (CompressState* cs : {&ctx->compress, &ctx->g2.compress}) {
+    for (DeviceBuf* b : {&cs->in, &cs->out, &cs->reasons, &cs->counters}) kill_buf(*b);
     if (cs->h_counters) (void)hipHostFree(cs->h_counters);
     cs->h_counters = nullptr;
   }
@@ -3035,7 +3058,7 @@ int msm_amd_test_op_host(int op, const uint32_t* a, const uint32_t* b, uint32_t*
 // Raw-limb test ops: the internal limbs pass through unchanged (no from_ext, no reversal, no normalisation).
 static bool test_op_raw_args(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
   return a && b && out && count > 0 && count <= (1u << 24) && op >= 0 &&
-         (op < kRawOpCount || (op >= kRawWideFirst && op < kRawWideFirst + kRawWideCount));
+         (op < kRawOpCount || (op >= kRawWideFirst && op < kRawWideFirst + kRawWideCount) || op == MSM_AMD_RAW_FE_SQRT);
 }
 
 int msm_amd_test_op_raw(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
@@ -3050,8 +3073,11 @@ int msm_amd_test_op_raw(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint3
   if ((rc = ensure(ctx, ctx->scratch_c, out_bytes))) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_a.p, a, in_bytes, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_b.p, b, in_bytes, hipMemcpyHostToDevice, st));
-  launch_test_op_raw(st, op, (const uint32_t*)ctx->scratch_a.p, (const uint32_t*)ctx->scratch_b.p,
-                     (uint32_t*)ctx->scratch_c.p, (uint32_t)count);
+  if (op == MSM_AMD_RAW_FE_SQRT)   // the root ladder has a kernel of its own (k_compress.hip)
+    launch_sqrt_raw(st, false, (const uint32_t*)ctx->scratch_a.p, (uint32_t*)ctx->scratch_c.p, (uint32_t)count);
+  else
+    launch_test_op_raw(st, op, (const uint32_t*)ctx->scratch_a.p, (const uint32_t*)ctx->scratch_b.p,
+                       (uint32_t*)ctx->scratch_c.p, (uint32_t)count);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch_c.p, out_bytes, hipMemcpyDeviceToHost, st));
   return sync_stream_bounded(ctx, st, __func__);
@@ -3059,6 +3085,10 @@ int msm_amd_test_op_raw(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint3
 
 int msm_amd_test_op_raw_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
   if (!test_op_raw_args(op, a, b, out, count)) return MSM_AMD_INPUT_ERROR;
+  if (op == MSM_AMD_RAW_FE_SQRT) {
+    for (size_t t = 0; t < count; ++t) raw_sqrt_fq(a + t * kRawInWords, out + t * kRawOutWords);
+    return MSM_AMD_OK;
+  }
   for (size_t t = 0; t < count; ++t) run_test_op_raw(op, a, b, out, (uint32_t)t);
   return MSM_AMD_OK;
 }
@@ -3552,7 +3582,8 @@ int msm_amd_test_g2_stage_copy(msm_amd_ctx* ctx, int which, void* out, size_t* b
 }
 
 int msm_amd_test_op_g2(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
-  if (!ctx || op < 0 || op >= G2RAW_OPS || count == 0 || count > (1u << 20) || !a || !b || !out)
+  if (!ctx || op < 0 || (op >= G2RAW_OPS && op != MSM_AMD_G2_RAW_FQ2_SQRT) || count == 0 || count > (1u << 20) || !a || !b ||
+      !out)
     return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_op_g2 arguments");
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3564,8 +3595,11 @@ int msm_amd_test_op_g2(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32
   if ((rc = ensure(ctx, ctx->scratch_c, out_bytes))) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_a.p, a, in_bytes, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_b.p, b, in_bytes, hipMemcpyHostToDevice, st));
-  launch_test_op_g2(st, op, (const uint32_t*)ctx->scratch_a.p, (const uint32_t*)ctx->scratch_b.p,
-                    (uint32_t*)ctx->scratch_c.p, (uint32_t)count);
+  if (op == MSM_AMD_G2_RAW_FQ2_SQRT)
+    launch_sqrt_raw(st, true, (const uint32_t*)ctx->scratch_a.p, (uint32_t*)ctx->scratch_c.p, (uint32_t)count);
+  else
+    launch_test_op_g2(st, op, (const uint32_t*)ctx->scratch_a.p, (const uint32_t*)ctx->scratch_b.p,
+                      (uint32_t*)ctx->scratch_c.p, (uint32_t)count);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch_c.p, out_bytes, hipMemcpyDeviceToHost, st));
   return sync_stream_bounded(ctx, st, __func__);
@@ -3704,6 +3738,199 @@ int msm_amd_g2_check_points(msm_amd_ctx* ctx, int g2_point_layout, const void* p
 int msm_amd_g2_check_points_device(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n,
                                    uint32_t checks, uint8_t* d_reasons, msm_amd_check_report* report) {
   return check_device(ctx, true, g2_point_layout, d_points, n, checks, d_reasons, report);
+}
+
+}  // extern "C"
+
+// ---- compressed points (msm_amd_decompress_points*, msm_amd_compress_points* and their G2 forms) -----------------------
+// The discipline of the check driver above: ctx lock, bounded drain of the ctx's earlier work, counters and staging
+// sized on the idle ctx only, host input through the page-locked staging ring, a bounded poll for the counters.
+namespace {
+
+std::string compress_name(bool g2, bool decompress) {
+  return std::string(g2 ? "msm_amd_g2_" : "msm_amd_") + (decompress ? "decompress_points" : "compress_points");
+}
+
+// layout: the output layout of a decompression, the input layout of a compression
+int compress_args(msm_amd_ctx* ctx, const std::string& who, bool g2, bool prepared_ok, int format, int layout,
+                  const void* in, const void* out, size_t n) {
+  if (!compress_format_known(format))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": unknown format (MSM_AMD_COMPRESSED_ARK / _PARITY)");
+  if (compress_stride(g2, layout, prepared_ok) == 0)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + (prepared_ok ? ": takes the two affine layouts and *_PREPARED (not *_TABLES)"
+                                                             : ": takes the two affine host layouts only"));
+  if (n > 0xFFFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": n >= 2^32");
+  if (n > 0 && (!in || !out)) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": null pointer with n > 0");
+  return MSM_AMD_OK;
+}
+
+// Every ctx call starts here (ctx->mu held): the ctx's earlier work is waited for, with the wait bound.
+int compress_begin(msm_amd_ctx* ctx, const std::string& who) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = recover_if_stalled(ctx)) return fail(ctx, rc, who + ": " + ctx->last_error);
+  if (!drain_or_mark_stalled(ctx))
+    return fail(ctx, MSM_AMD_PIPELINE_ERROR, who + ": device busy past the wait bound of " +
+                                                 std::to_string(ctx->wait_timeout_ms) + " ms (msm_amd_synchronize waits again)");
+  return MSM_AMD_OK;
+}
+
+// One pass over n device-resident records on the main stream and the bounded wait for its counters (*cs.h_counters).
+// The ctx is idle (compress_begin), so the first call may allocate the counters and their page-locked copy.
+int run_compress(msm_amd_ctx* ctx, CompressState& cs, const std::string& who, bool g2, bool decompress, int format,
+                 int layout, const void* d_in, size_t n, void* d_out, uint8_t* d_reasons, float* device_ms) {
+  hipStream_t st = ctx->stream;
+  if (!cs.ready) {
+    if (int rc = quiesce_for_allocation(ctx, "the report buffer of a decompress / compress call")) return rc;
+    if (int rc = ensure(ctx, cs.counters, sizeof(CompressCounters))) return rc;
+    if (!cs.h_counters) HIP_TRY(ctx, hipHostMalloc((void**)&cs.h_counters, sizeof(CompressCounters), hipHostMallocDefault));
+    for (hipEvent_t& e : cs.ev)
+      if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    cs.ready = true;
+  }
+  CompressCounters* d_counters = (CompressCounters*)cs.counters.p;
+  const uint32_t stride = (uint32_t)compress_stride(g2, layout, true);
+  launch_compress_reset(st, d_counters);
+  HIP_TRY(ctx, hipEventRecord(cs.ev[CompressState::EV_COMP_START], st));
+  if (decompress)
+    launch_decompress(st, g2, format, d_in, (uint32_t)n, layout, stride, d_out, d_reasons, d_counters);
+  else
+    launch_compress(st, g2, layout, stride, d_in, (uint32_t)n, format, d_out, d_counters);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(cs.ev[CompressState::EV_COMP_KERNEL], st));
+  HIP_TRY(ctx, hipMemcpyAsync(cs.h_counters, d_counters, sizeof(CompressCounters), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipEventRecord(cs.ev[CompressState::EV_COMP_DONE], st));
+  const hipError_t we = wait_event(cs.ev[CompressState::EV_COMP_DONE], ctx->wait_timeout_ms);
+  if (we == hipErrorNotReady) {
+    ctx->stalled = true;
+    return fail(ctx, MSM_AMD_PIPELINE_ERROR, "timed out after " + std::to_string(ctx->wait_timeout_ms) + " ms waiting for " + who);
+  }
+  if (we != hipSuccess) return fail(ctx, MSM_AMD_PIPELINE_ERROR, who + ": " + hipGetErrorString(we));
+  *device_ms = event_span(cs.ev[CompressState::EV_COMP_START], cs.ev[CompressState::EV_COMP_KERNEL]);
+  return MSM_AMD_OK;
+}
+
+void empty_decompress_report(msm_amd_decompress_report* report) {
+  CompressCounters none{};
+  none.first_key = ~0ull;
+  decompress_report_from_counters(none, 0, 0.0f, report);
+}
+
+// host == false: in / out / reasons are device memory.  host == true: the input goes up in chunks through the
+// page-locked staging ring into the group's staging buffer (grown only on an idle ctx, like every workspace), output
+// and reason bytes come back after the counters.
+int decompress_call(msm_amd_ctx* ctx, bool g2, bool host, int format, const void* in, size_t n, int layout, void* out,
+                    uint8_t* reasons, msm_amd_decompress_report* report) {
+  if (!ctx || !report) return MSM_AMD_INPUT_ERROR;
+  const std::string who = compress_name(g2, true) + (host ? "" : "_device");
+  if (int rc = compress_args(ctx, who, g2, !host, format, layout, in, out, n)) return rc;
+  if (n == 0) {
+    empty_decompress_report(report);
+    return MSM_AMD_OK;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (int rc = compress_begin(ctx, who)) return rc;
+  CompressState& cs = g2 ? ctx->g2.compress : ctx->compress;
+  const size_t in_bytes = n * (g2 ? 64 : 32), out_bytes = n * compress_stride(g2, layout, true);
+  const void* d_in = in;
+  void* d_out = out;
+  uint8_t* d_reasons = reasons;
+  int rc;
+  if (host) {
+    if ((rc = ensure(ctx, cs.in, in_bytes))) return rc;
+    if ((rc = ensure(ctx, cs.out, out_bytes))) return rc;
+    if (reasons && (rc = ensure(ctx, cs.reasons, n))) return rc;
+    if ((rc = staged_upload(ctx, cs.in.p, in, in_bytes, ctx->stream))) return rc;
+    d_in = cs.in.p;
+    d_out = cs.out.p;
+    d_reasons = reasons ? (uint8_t*)cs.reasons.p : nullptr;
+  }
+  float ms = 0.0f;
+  if ((rc = run_compress(ctx, cs, who, g2, true, format, layout, d_in, n, d_out, d_reasons, &ms))) return rc;
+  decompress_report_from_counters(*cs.h_counters, n, ms, report);
+  if (host) {
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (reasons) HIP_TRY(ctx, hipMemcpyAsync(reasons, d_reasons, n, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = sync_stream_bounded(ctx, ctx->stream, who.c_str()))) return rc;
+  }
+  return MSM_AMD_OK;
+}
+
+int compress_call(msm_amd_ctx* ctx, bool g2, bool host, int layout, const void* in, size_t n, int format, void* out,
+                  uint64_t* n_bad) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  const std::string who = compress_name(g2, false) + (host ? "" : "_device");
+  if (int rc = compress_args(ctx, who, g2, false, format, layout, in, out, n)) return rc;
+  if (n == 0) {
+    if (n_bad) *n_bad = 0;
+    return MSM_AMD_OK;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (int rc = compress_begin(ctx, who)) return rc;
+  CompressState& cs = g2 ? ctx->g2.compress : ctx->compress;
+  const size_t in_bytes = n * compress_stride(g2, layout, false), out_bytes = n * (g2 ? 64 : 32);
+  const void* d_in = in;
+  void* d_out = out;
+  int rc;
+  if (host) {
+    if ((rc = ensure(ctx, cs.in, in_bytes))) return rc;
+    if ((rc = ensure(ctx, cs.out, out_bytes))) return rc;
+    if ((rc = staged_upload(ctx, cs.in.p, in, in_bytes, ctx->stream))) return rc;
+    d_in = cs.in.p;
+    d_out = cs.out.p;
+  }
+  float ms = 0.0f;
+  if ((rc = run_compress(ctx, cs, who, g2, false, format, layout, d_in, n, d_out, nullptr, &ms))) return rc;
+  if (n_bad) *n_bad = cs.h_counters->by_reason[kPointNotReduced];
+  if (host) {
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = sync_stream_bounded(ctx, ctx->stream, who.c_str()))) return rc;
+  }
+  return MSM_AMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_decompress_points(msm_amd_ctx* ctx, int format, const void* in, size_t n, int point_layout_out, void* out,
+                              uint8_t* reasons, msm_amd_decompress_report* report) {
+  return decompress_call(ctx, false, true, format, in, n, point_layout_out, out, reasons, report);
+}
+
+int msm_amd_decompress_points_device(msm_amd_ctx* ctx, int format, const void* d_in, size_t n, int point_layout_out,
+                                     void* d_out, uint8_t* d_reasons, msm_amd_decompress_report* report) {
+  return decompress_call(ctx, false, false, format, d_in, n, point_layout_out, d_out, d_reasons, report);
+}
+
+int msm_amd_g2_decompress_points(msm_amd_ctx* ctx, int format, const void* in, size_t n, int g2_point_layout_out,
+                                 void* out, uint8_t* reasons, msm_amd_decompress_report* report) {
+  return decompress_call(ctx, true, true, format, in, n, g2_point_layout_out, out, reasons, report);
+}
+
+int msm_amd_g2_decompress_points_device(msm_amd_ctx* ctx, int format, const void* d_in, size_t n,
+                                        int g2_point_layout_out, void* d_out, uint8_t* d_reasons,
+                                        msm_amd_decompress_report* report) {
+  return decompress_call(ctx, true, false, format, d_in, n, g2_point_layout_out, d_out, d_reasons, report);
+}
+
+int msm_amd_compress_points(msm_amd_ctx* ctx, int point_layout_in, const void* in, size_t n, int format, void* out,
+                            uint64_t* n_bad) {
+  return compress_call(ctx, false, true, point_layout_in, in, n, format, out, n_bad);
+}
+
+int msm_amd_compress_points_device(msm_amd_ctx* ctx, int point_layout_in, const void* d_in, size_t n, int format,
+                                   void* d_out, uint64_t* n_bad) {
+  return compress_call(ctx, false, false, point_layout_in, d_in, n, format, d_out, n_bad);
+}
+
+int msm_amd_g2_compress_points(msm_amd_ctx* ctx, int g2_point_layout_in, const void* in, size_t n, int format, void* out,
+                               uint64_t* n_bad) {
+  return compress_call(ctx, true, true, g2_point_layout_in, in, n, format, out, n_bad);
+}
+
+int msm_amd_g2_compress_points_device(msm_amd_ctx* ctx, int g2_point_layout_in, const void* d_in, size_t n, int format,
+                                      void* d_out, uint64_t* n_bad) {
+  return compress_call(ctx, true, false, g2_point_layout_in, d_in, n, format, d_out, n_bad);
 }
 
 }  // extern "C"

@@ -13,6 +13,11 @@ The subgroup test of the point validation (check_points.hip.h) is part of the fi
 32 p / 4 p lifts, the products by gx, gy, the squashed ZZ, ZZZ), the negation of a point, the ladder's base (canonicalised
 like a stored base) and the final comparison D = L + (-R) by the full addition all stay inside the same invariant; the
 curve equation's subtrahend stays below its 8 p lift.
+The square roots of the decompression kernels (compress_points.hip.h) are re-derived too: the 2-bit-window ladder over
+(p + 1) / 4 (every operand of a multiplication a valid one, the result below 1.05 p for an operand below 8 p), the
+acceptance test through the 8 p lift, the Fq2 root (norm, halving, the negation through the 4 p lift, the inversion of
+2 c, the final comparison through Fq2::sub<8>), the sign selection (canonical integer, the negated root squashed) and
+the right-hand sides x^3 + b the two decoders feed in.
 Prints the invariant and the intermediate bounds; exit status 1 if an assertion fails."""
 import sys
 
@@ -168,6 +173,61 @@ def curve_equation():     # y^2 - (x^3 + b') + 8 p with x, y from_ext outputs (<
     return d
 
 
+# ---- square roots (compress_points.hip.h) -----------------------------------------------------------------------------
+def fe_sqrt(a):           # comp_sqrt_candidate: table a, a^2, a^3; per 2-bit window (msb first): r = (r^2)^2, r = r a^w
+    assert a < 8, a       # the contract; the acceptance test subtracts a through the 8 p lift
+    a2 = 1 + RP * a * a
+    a3 = 1 + RP * a2 * a
+    table = {1: a, 2: a2, 3: a3}
+    e = (P + 1) // 4
+    r, worst, products = 1.0, 1.0, 0
+    for b in range(254, -1, -2):
+        r = 1 + RP * r * r
+        r = 1 + RP * r * r
+        worst = max(worst, r)
+        w = (e >> b) & 3
+        if w:
+            r = 1 + RP * r * table[w]
+            products += 1
+            worst = max(worst, r)
+    assert products == 88 and worst < 1.05 and max(a2, a3) < 1.38, (products, worst, a2, a3)
+    d = (1 + RP * r * r) + 8          # r^2 - a + 8 p: normalised, the operand of is_zero_exact
+    assert d < 9.02 and 1 + RP * d < 2, d
+    return r
+
+
+def fq2_sqrt(a):          # comp_sqrt_fq2: a = (a0, a1), components normalised, < 4 p
+    assert max(a) < 4, a
+    n = 1 + RP * (a[0] * a[0] + a[1] * a[1])                # norm_fq: mul2(a0, a0, a1, a1)
+    r1 = fe_sqrt(max(a[0], n))                             # in1 = a1 == 0 ? a0 : norm
+    half = 1 + RP * (a[0] + r1) * 1                        # (a0 + r1) (rho / 2 mod p) / rho
+    r2 = fe_sqrt(max(4.0, half))                           # in2 = a1 == 0 ? 4 p - a0 : half
+    inv = fe_inv(2 * r2)                                   # inv_fq(norm(r2 + r2))
+    w = 1 + RP * a[1] * inv
+    root = (max(r1, r2, w), max(r2, w))
+    d = sub(sqr(root), a, 8)                               # root^2 - a through Fq2::sub<8>
+    chk(d)
+    note("sqrt.norm", (n, n)), note("sqrt.half", (half, half)), note("sqrt.w", (w, w)), note("sqrt.root", root)
+    assert n < 1.19 and half < 1.03 and w < 1.03 and max(root) < 1.05, (n, half, w, root)
+    return root
+
+
+def decompress():         # the two decoders: x from the canonical integer, the right-hand side, the sign selection
+    x = 1 + RP * 6 * 1                                     # mul(unpack256(x < 2^254 < 6 p), rho^2 mod p)
+    rhs1 = (1 + RP * (1 + RP * x * x) * x) + 1             # x^3 + b, b canonical
+    y = fe_sqrt(rhs1)
+    neg = 1 + RP * 4 * 1                                   # squash(neg(y)): neg < 4 p needs y < 3.9 p
+    assert rhs1 < 2.02 and y < 3.9 and neg < 1.03 and max(x, y, neg) < 2    # packers take values below 2 p
+    t = mul(sqr((x, x)), (x, x))
+    rhs2 = add(t, (1, 1))
+    assert max(rhs2) < 2.21, rhs2
+    y2 = fq2_sqrt(rhs2)
+    assert max(y2) < 2
+    note("decompress.rhs", rhs2)
+    lifted = fe_sqrt(8 - 1e-9)                             # the raw-limb op at the edge of its contract
+    assert lifted < 1.05
+
+
 def widen(a, b):
     return tuple(tuple(max(x, y) for x, y in zip(u, v)) for u, v in zip(a, b))
 
@@ -203,6 +263,8 @@ def main():
     assert max(SEEN["affine.ZZ*ZZZ"]) < 1.7 and max(SEEN["affine.Xt"]) < 1.24 and max(SEEN["affine.Yt"]) < 3.7
     assert max(SEEN["psi.X"]) < 1.21 and max(SEEN["psi.Y"]) < 1.3 and max(SEEN["psi.ZZ"]) < 1.03 and max(SEEN["neg.Y"]) < 1.2
     assert max(curve_equation()) < 9.5
+    decompress()
+    fq2_sqrt((4 - 1e-9, 4 - 1e-9))         # the raw-limb Fq2 root at the edge of its contract
     print("invariant: " + "  ".join(f"{k} < {max(v):.3f} p" for k, v in zip(claimed, pt)))
     for k in sorted(SEEN):
         print(f"  {k:10s} < {max(SEEN[k]):.2f} p")
