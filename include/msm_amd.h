@@ -542,7 +542,8 @@ enum {
 /* out == NULL: *bytes receives the size of the buffer; otherwise *bytes must equal it. */
 int msm_amd_test_stage_copy(msm_amd_ctx* ctx, uint32_t j, int which, void* out, size_t* bytes);
 /* Fill the point-valued buffers of every workspace (buckets, item partials, reduce scratch, window partials), those of
- * the G2 MSM included, with one byte over their whole capacity.  Index and count buffers are never touched. */
+ * the G2 MSM included, and the intermediate records and fixed-base tables of the mul_points calls, with one byte over
+ * their whole capacity.  Index and count buffers are never touched. */
 int msm_amd_test_fill_workspaces(msm_amd_ctx* ctx, uint8_t byte);
 /* The same tap for the G2 MSM: the last msm_amd_msm_g2* call of the ctx (per-call, prepared or tables), read AFTER the
  * call.  MSM_AMD_INPUT_ERROR before any G2 MSM has succeeded and after a failed one; G1 calls in between change nothing.
@@ -778,6 +779,56 @@ int msm_amd_host_compress_points(int point_layout_in, const void* in, size_t n, 
                                  uint64_t* n_bad);
 int msm_amd_host_g2_compress_points(int g2_point_layout_in, const void* in, size_t n, int format, int threads, void* out,
                                     uint64_t* n_bad);
+
+/* ---- batch scalar multiplication (G1 and G2) ---------------------------------------------------------
+ * Every call above CONSUMES a point array; these produce one: out[i] = [s_i] P_i (MSM_AMD_MUL_BASE_EACH) or
+ * out[i] = [s_i] P for one base P (MSM_AMD_MUL_BASE_ONE; arkworks' FixedBase::msm / batch_mul) -- an SRS or a test key
+ * ([tau^i] G), a ceremony contribution (P_i -> [tau^i] P_i), a re-randomised key, benchmark inputs.
+ * Scalars: n records of 32 B in one of the MSM_AMD_SCALAR_* layouts, read exactly as the MSM entry points read them (a
+ * canonical layout is reduced mod r).  The result is the group element [s] P for that integer s < r, written as its
+ * CANONICAL affine coordinates, so the bytes are unique; it is multiplied as a curve point whatever its order (a G2 base
+ * outside the r-torsion included).
+ * points: n records (BASE_EACH) or ONE record (BASE_ONE) of point_layout_in -- G1: the four host layouts, G2: both host
+ * layouts; the _device calls also take MSM_AMD_POINT_PREPARED / MSM_AMD_G2_POINT_PREPARED (BASE_ONE: one prepared record).
+ * out: n records of point_layout_out, one of the two affine host layouts of the group; the _device calls also take
+ * *_PREPARED and then write, bit for bit, the records msm_amd_bases_prepare_device / msm_amd_g2_bases_prepare_device would
+ * write from the affine result: a generated array is MSM-ready at once (msm_amd_msm_device, *_tables_build_device,
+ * *_check_points_device, *_compress_points_device take it as it is).  A result that is the identity (s = 0, an identity
+ * base, [s] P = O for a G2 base of small order) is written as the layout's identity encoding, exactly as the decompress
+ * calls write it; the output is always fully defined.  Inputs are NOT validated: a base that is not on the curve gives
+ * unspecified but defined bytes.
+ * BASE_ONE always runs the fixed-base path (a table of [d 2^(8 w)] P, at most 32 mixed additions per output), BASE_EACH
+ * a 256-step double-and-add ladder per record; both end in a batched normalisation, one inversion per 16 consecutive
+ * outputs.  The call may run in chunks of outputs (one intermediate record per output of a chunk); no byte of the
+ * result depends on that.
+ * Status and arguments as msm_amd_check_points*: n == 0: MSM_AMD_OK, nothing is touched; MSM_AMD_INPUT_ERROR: an unknown
+ * layout or base mode, *_TABLES, *_PREPARED on a host-buffer call or a host twin, a null pointer with n > 0, n >= 2^32.
+ * The ctx calls serialise on the ctx and first wait -- bounded -- for its earlier work (a busy ctx:
+ * MSM_AMD_PIPELINE_ERROR, msm_amd_last_error names the call); host buffers go up through the page-locked staging ring;
+ * a G2 call touches the G2 state of the ctx only. */
+enum {
+  MSM_AMD_MUL_BASE_EACH = 0,  /* points: n records, out[i] = [s_i] P_i */
+  MSM_AMD_MUL_BASE_ONE = 1    /* points: ONE record, out[i] = [s_i] P */
+};
+int msm_amd_mul_points(msm_amd_ctx* ctx, int scalar_layout, int point_layout_in, int base_mode, const void* scalars,
+                       const void* points, size_t n, int point_layout_out, void* out);
+int msm_amd_mul_points_device(msm_amd_ctx* ctx, int scalar_layout, int point_layout_in, int base_mode,
+                              const void* d_scalars, const void* d_points, size_t n, int point_layout_out, void* d_out);
+int msm_amd_g2_mul_points(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout_in, int base_mode, const void* scalars,
+                          const void* points, size_t n, int g2_point_layout_out, void* out);
+int msm_amd_g2_mul_points_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout_in, int base_mode,
+                                 const void* d_scalars, const void* d_points, size_t n, int g2_point_layout_out,
+                                 void* d_out);
+/* The same on the CPU (no ctx, no GPU; the same bodies compiled for the host); threads <= 0: up to 16 host threads. */
+int msm_amd_host_mul_points(int scalar_layout, int point_layout_in, int base_mode, const void* scalars, const void* points,
+                            size_t n, int point_layout_out, int threads, void* out);
+int msm_amd_host_g2_mul_points(int scalar_layout, int g2_point_layout_in, int base_mode, const void* scalars,
+                               const void* points, size_t n, int g2_point_layout_out, int threads, void* out);
+/* Test aid (no ctx): the constants of the two paths for group 1 or 2 -- out[0] window c of the fixed-base table,
+ * [1] its windows W, [2] its entries W 2^(c-1), [3] K, the number of consecutive outputs that share one inversion.
+ * (Development knob MSM_AMD_MUL_CHUNK at msm_amd_init: outputs per chunk of the ctx calls, rounded up to a multiple
+ * of K; default 2^18.) */
+int msm_amd_test_mul_plan(int group /* 1 or 2 */, uint32_t out[4]);
 
 /* ---- introspection --------------------------------------------------------------------------- */
 int msm_amd_last_timings(const msm_amd_ctx* ctx, msm_amd_timings* out);

@@ -47,6 +47,8 @@ CHECK_CURVE, CHECK_SUBGROUP = 1, 2
 # compressed points (MSM_AMD_COMPRESSED_*, MSM_AMD_POINT_BAD_ENCODING)
 COMPRESSED_ARK, COMPRESSED_PARITY = 0, 1
 POINT_BAD_ENCODING = 4
+# batch scalar multiplication (MSM_AMD_MUL_BASE_*)
+MUL_BASE_EACH, MUL_BASE_ONE = 0, 1
 
 
 def op_is_point(op):
@@ -93,6 +95,8 @@ EXPORTS = [
     "msm_amd_host_g2_decompress_points", "msm_amd_compress_points", "msm_amd_compress_points_device",
     "msm_amd_g2_compress_points", "msm_amd_g2_compress_points_device", "msm_amd_host_compress_points",
     "msm_amd_host_g2_compress_points",
+    "msm_amd_mul_points", "msm_amd_mul_points_device", "msm_amd_g2_mul_points", "msm_amd_g2_mul_points_device",
+    "msm_amd_host_mul_points", "msm_amd_host_g2_mul_points", "msm_amd_test_mul_plan",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -307,6 +311,12 @@ def _lib():
             getattr(L, name).argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p, POINTER(c_uint64)]
         for name in ("msm_amd_host_compress_points", "msm_amd_host_g2_compress_points"):
             getattr(L, name).argtypes = [c_int, c_void_p, c_size_t, c_int, c_int, c_void_p, POINTER(c_uint64)]
+        for name in ("msm_amd_mul_points", "msm_amd_mul_points_device", "msm_amd_g2_mul_points",
+                     "msm_amd_g2_mul_points_device"):
+            getattr(L, name).argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+        for name in ("msm_amd_host_mul_points", "msm_amd_host_g2_mul_points"):
+            getattr(L, name).argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]
+        L.msm_amd_test_mul_plan.argtypes = [c_int, POINTER(c_uint32)]
         L.msm_amd_generate_instance_host.argtypes = [c_uint64, c_size_t, c_int, c_void_p, c_void_p, c_int]
         L.msm_amd_test_op_ifma.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_tuned_split.argtypes = [c_size_t]
@@ -740,6 +750,25 @@ class MsmConfig:
         self._check(fn(self.h, point_layout, c_void_p(d_in), n, fmt, c_void_p(d_out), ctypes.byref(bad)))
         return bad.value
 
+    # ---- batch scalar multiplication --------------------------------------------------------------
+    def mul_points(self, scalars: bytes, points: bytes, n: int, base_mode=MUL_BASE_EACH, scalar_layout=SCALAR_MONT_LE,
+                   point_layout=POINT_H2C_AFFINE, point_layout_out=POINT_H2C_AFFINE, g2=False) -> bytes:
+        """out[i] = [s_i] P_i (MUL_BASE_EACH: n point records) or [s_i] P (MUL_BASE_ONE: one record) on the GPU from
+        host memory: n affine records of point_layout_out."""
+        fn = _lib().msm_amd_g2_mul_points if g2 else _lib().msm_amd_mul_points
+        size = decompressed_bytes(point_layout_out, g2)
+        out = ctypes.create_string_buffer(max(1, n * size))
+        self._check(fn(self.h, scalar_layout, point_layout, base_mode, scalars, points, n, point_layout_out, out))
+        return out.raw[:n * size]
+
+    def mul_points_device(self, d_scalars, d_points, n: int, d_out, base_mode=MUL_BASE_EACH, scalar_layout=SCALAR_MONT_LE,
+                          point_layout=POINT_H2C_AFFINE, point_layout_out=POINT_PREPARED, g2=False) -> None:
+        """The same between device buffers; points and output may also be POINT_PREPARED / G2_POINT_PREPARED records
+        (a generated array is MSM-ready at once)."""
+        fn = _lib().msm_amd_g2_mul_points_device if g2 else _lib().msm_amd_mul_points_device
+        self._check(fn(self.h, scalar_layout, point_layout, base_mode, c_void_p(d_scalars), c_void_p(d_points), n,
+                       point_layout_out, c_void_p(d_out)))
+
     def test_op_g2(self, op, a, b, count):
         """Raw-limb G2 op (MSM_AMD_G2_RAW_*) on the device: a, b flat u32 lists of count * G2_RAW_IN_WORDS; returns
         count * G2_RAW_OUT_WORDS u32."""
@@ -986,6 +1015,28 @@ def host_compress_points(points: bytes, n: int, fmt=COMPRESSED_ARK, point_layout
     if st != OK:
         raise MsmError(st)
     return out.raw[:n * size], bad.value
+
+
+def host_mul_points(scalars: bytes, points: bytes, n: int, base_mode=MUL_BASE_EACH, scalar_layout=SCALAR_MONT_LE,
+                    point_layout=POINT_H2C_AFFINE, point_layout_out=POINT_H2C_AFFINE, g2=False, threads=0) -> bytes:
+    """Host twin of MsmConfig.mul_points (no GPU)."""
+    fn = _lib().msm_amd_host_g2_mul_points if g2 else _lib().msm_amd_host_mul_points
+    size = decompressed_bytes(point_layout_out, g2)
+    out = ctypes.create_string_buffer(max(1, n * size))
+    st = fn(scalar_layout, point_layout, base_mode, scalars, points, n, point_layout_out, threads, out)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:n * size]
+
+
+def mul_plan(group=1) -> dict:
+    """Constants of the scalar-multiplication paths (msm_amd_test_mul_plan): window c, windows W and entries of the
+    fixed-base table, and K, the number of consecutive outputs that share one inversion."""
+    out = (c_uint32 * 4)()
+    st = _lib().msm_amd_test_mul_plan(group, out)
+    if st != OK:
+        raise MsmError(st)
+    return {"c": out[0], "W": out[1], "entries": out[2], "K": out[3]}
 
 
 def _g2_raw_in(seq, count):

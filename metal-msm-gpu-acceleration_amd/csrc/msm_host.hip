@@ -29,6 +29,7 @@
 #include "launch_g2.h"
 #include "launch_check.h"
 #include "launch_compress.h"
+#include "launch_mul.h"
 #include "host_fq64.h"
 #include "test_ops.hip.h"
 #include "test_ops_g2.hip.h"
@@ -204,6 +205,13 @@ struct CompressState {
   bool ready = false;
 };
 
+// Buffers of a scalar-multiplication call (msm_amd_mul_points*, msm_amd_g2_mul_points*): the fixed-base table, the XYZZ
+// records of one chunk of outputs and, for the host-buffer calls, the staging of scalars, bases and output.  One per
+// group: a G2 call touches G2State only.
+struct MulState {
+  DeviceBuf table, xyzz, in_scalars, in_points, out;
+};
+
 // State of the G2 MSM (msm_amd_msm_g2*): one blocking call at a time on the main stream, through the instance body of
 // G1 (enqueue_instance) in a workspace and a slot of its own -- a G2 call never touches what a G1 instance of the same
 // ctx may still be using.  `ws` is used on the main stream only and therefore has no hand-off events.
@@ -213,6 +221,7 @@ struct G2State {
   DeviceBuf in_scalars, in_points;   // staging of host inputs
   CheckState check;   // msm_amd_g2_check_points*: host points are staged in in_points above
   CompressState compress;   // msm_amd_g2_decompress_points*, msm_amd_g2_compress_points*
+  MulState mul;             // msm_amd_g2_mul_points*
   // Stage tap (msm_amd_test_g2_last_plan / msm_amd_test_g2_stage_copy): the plan of the last run_msm_g2, valid only
   // while that call was the last one and succeeded.  Its plan counters are in `slot`, behind the partial points.
   Plan last_plan{};
@@ -243,6 +252,8 @@ struct msm_amd_ctx {
   G2State g2;
   CheckState check;   // msm_amd_check_points* (G1)
   CompressState compress;   // msm_amd_decompress_points*, msm_amd_compress_points* (G1)
+  MulState mul;             // msm_amd_mul_points* (G1)
+  size_t mul_chunk = (size_t)1 << 18;   // outputs per chunk of a mul_points call (MSM_AMD_MUL_CHUNK), a multiple of kMulNormGroup
   std::mutex mu;
   std::string last_error;
   uint32_t forced_window = 0;
@@ -2056,6 +2067,10 @@ int msm_amd_init(int device, msm_amd_ctx** out) {
             hipEventCreateWithFlags(&ctx->uploaded[1], hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&ctx->upload_done, hipEventDisableTiming) == hipSuccess;
   ctx->wait_timeout_ms = default_wait_timeout_ms();
+  if (const char* e = std::getenv("MSM_AMD_MUL_CHUNK")) {
+    const size_t want = std::max<size_t>(1, (size_t)std::strtoull(e, nullptr, 10));
+    ctx->mul_chunk = std::min<size_t>((want + kMulNormGroup - 1) / kMulNormGroup * kMulNormGroup, (size_t)1 << 24);
+  }
   if (const char* e = std::getenv("MSM_AMD_BASES_CACHE_VERIFY")) ctx->bases_cache_verify = std::strcmp(e, "full") == 0;
   if (const char* e = std::getenv("MSM_AMD_BASES_CACHE_MB")) {
     ctx->bases_cache_budget = (size_t)std::strtoull(e, nullptr, 10) << 20;
@@ -2201,6 +2216,8 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
     if (cs->h_counters) (void)hipHostFree(cs->h_counters);
     cs->h_counters = nullptr;
   }
+  for (MulState* ms : {&ctx->mul, &ctx->g2.mul})
+    for (DeviceBuf* b : {&ms->table, &ms->xyzz, &ms->in_scalars, &ms->in_points, &ms->out}) kill_buf(*b);
   tables_release_all(ctx->live_tables);
   tables_release_all(ctx->live_g2_tables);
   for (DeviceBuf* b : {&ctx->scratch_a, &ctx->scratch_b, &ctx->scratch_c, &ctx->scratch_b2, &ctx->scratch_c2}) kill_buf(*b);
@@ -3279,6 +3296,9 @@ int msm_amd_test_fill_workspaces(msm_amd_ctx* ctx, uint8_t byte) {
   for (Workspace* w : all)
     for (DeviceBuf* b : {&w->buckets, &w->item_partials, &w->S, &w->T, &w->partial})
       if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
+  for (MulState* ms : {&ctx->mul, &ctx->g2.mul})   // the XYZZ records and the fixed-base table of the mul_points calls
+    for (DeviceBuf* b : {&ms->xyzz, &ms->table})
+      if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
   return sync_stream_bounded(ctx, ctx->stream, __func__);
 }
 
@@ -3931,6 +3951,103 @@ int msm_amd_g2_compress_points(msm_amd_ctx* ctx, int g2_point_layout_in, const v
 int msm_amd_g2_compress_points_device(msm_amd_ctx* ctx, int g2_point_layout_in, const void* d_in, size_t n, int format,
                                       void* d_out, uint64_t* n_bad) {
   return compress_call(ctx, true, false, g2_point_layout_in, d_in, n, format, d_out, n_bad);
+}
+
+}  // extern "C"
+
+// ---- batch scalar multiplication (msm_amd_mul_points*, msm_amd_g2_mul_points*) ------------------------------------------
+// The discipline of the check and compress drivers above: ctx lock, bounded drain of the ctx's earlier work, every
+// buffer sized on the idle ctx before anything is enqueued, host input through the page-locked staging ring, the output
+// behind a bounded stream wait.  The outputs run in chunks of ctx->mul_chunk records (a multiple of the normalisation
+// group, so the groups of a chunked call are those of an unchunked one), all enqueued on the main stream: stream order
+// hands the XYZZ buffer from one chunk to the next.
+namespace {
+
+std::string mul_name(bool g2, bool host) {
+  return std::string(g2 ? "msm_amd_g2_mul_points" : "msm_amd_mul_points") + (host ? "" : "_device");
+}
+
+int mul_call(msm_amd_ctx* ctx, bool g2, bool host, int scalar_layout, int layout_in, int base_mode, const void* scalars,
+             const void* points, size_t n, int layout_out, void* out) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  const std::string who = mul_name(g2, host);
+  const size_t in_stride = mul_in_stride(g2, layout_in, !host), out_stride = mul_out_stride(g2, layout_out, !host);
+  if (!mul_scalar_layout_known(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": unknown scalar layout");
+  if (in_stride == 0)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + (host ? ": points in a host layout only (not *_PREPARED / *_TABLES)"
+                                                      : ": points in a host layout or *_PREPARED (not *_TABLES)"));
+  if (out_stride == 0)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + (host ? ": output in one of the two affine host layouts only"
+                                                      : ": output in one of the two affine layouts or *_PREPARED"));
+  if (base_mode != MSM_AMD_MUL_BASE_EACH && base_mode != MSM_AMD_MUL_BASE_ONE)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": base_mode must be MSM_AMD_MUL_BASE_EACH or MSM_AMD_MUL_BASE_ONE");
+  if (n > 0xFFFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": n >= 2^32");
+  if (n == 0) return MSM_AMD_OK;
+  if (!scalars || !points || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": null pointer with n > 0");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (int rc = compress_begin(ctx, who)) return rc;   // device, stall recovery, the bounded drain
+  MulState& ms = g2 ? ctx->g2.mul : ctx->mul;
+  const bool one = base_mode == MSM_AMD_MUL_BASE_ONE;
+  const size_t n_points = one ? 1 : n, chunk = std::min(n, ctx->mul_chunk);
+  int rc;
+  // the ctx is idle: every buffer of the call is sized now (ensure quiesces before it allocates)
+  if (one && (rc = ensure(ctx, ms.table, mul_table_bytes(g2)))) return rc;
+  if ((rc = ensure(ctx, ms.xyzz, chunk * mul_xyzz_bytes(g2)))) return rc;
+  const void* d_scalars = scalars;
+  const void* d_points = points;
+  void* d_out = out;
+  hipStream_t st = ctx->stream;
+  if (host) {
+    if ((rc = ensure(ctx, ms.in_scalars, n * 32))) return rc;
+    if ((rc = ensure(ctx, ms.in_points, n_points * in_stride))) return rc;
+    if ((rc = ensure(ctx, ms.out, n * out_stride))) return rc;
+    if ((rc = staged_upload(ctx, ms.in_scalars.p, scalars, n * 32, st))) return rc;
+    if ((rc = staged_upload(ctx, ms.in_points.p, points, n_points * in_stride, st))) return rc;
+    d_scalars = ms.in_scalars.p;
+    d_points = ms.in_points.p;
+    d_out = ms.out.p;
+  }
+  if (one) launch_mul_table(st, g2, layout_in, d_points, ms.table.p);
+  for (size_t first = 0; first < n; first += chunk) {
+    const uint32_t m = (uint32_t)std::min(chunk, n - first);
+    const uint8_t* sc = (const uint8_t*)d_scalars + first * 32;
+    if (one)
+      launch_mul_fixed(st, g2, scalar_layout, sc, m, ms.table.p, ms.xyzz.p);
+    else
+      launch_mul_each(st, g2, scalar_layout, sc, layout_in, (const uint8_t*)d_points + first * in_stride, m, ms.xyzz.p);
+    launch_mul_normalise(st, g2, ms.xyzz.p, m, layout_out, (uint8_t*)d_out + first * out_stride);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  if (host) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, n * out_stride, hipMemcpyDeviceToHost, st));
+  return sync_stream_bounded(ctx, st, who.c_str());
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_mul_points(msm_amd_ctx* ctx, int scalar_layout, int point_layout_in, int base_mode, const void* scalars,
+                       const void* points, size_t n, int point_layout_out, void* out) {
+  return mul_call(ctx, false, true, scalar_layout, point_layout_in, base_mode, scalars, points, n, point_layout_out, out);
+}
+
+int msm_amd_mul_points_device(msm_amd_ctx* ctx, int scalar_layout, int point_layout_in, int base_mode,
+                              const void* d_scalars, const void* d_points, size_t n, int point_layout_out, void* d_out) {
+  return mul_call(ctx, false, false, scalar_layout, point_layout_in, base_mode, d_scalars, d_points, n, point_layout_out,
+                  d_out);
+}
+
+int msm_amd_g2_mul_points(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout_in, int base_mode, const void* scalars,
+                          const void* points, size_t n, int g2_point_layout_out, void* out) {
+  return mul_call(ctx, true, true, scalar_layout, g2_point_layout_in, base_mode, scalars, points, n, g2_point_layout_out,
+                  out);
+}
+
+int msm_amd_g2_mul_points_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout_in, int base_mode,
+                                 const void* d_scalars, const void* d_points, size_t n, int g2_point_layout_out,
+                                 void* d_out) {
+  return mul_call(ctx, true, false, scalar_layout, g2_point_layout_in, base_mode, d_scalars, d_points, n,
+                  g2_point_layout_out, d_out);
 }
 
 }  // extern "C"

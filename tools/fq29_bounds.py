@@ -285,17 +285,72 @@ def pti_add_nz(where="pti_add_nz"):
     pti_double(px, py, pzz, pzzz, where)
 
 
+def widen(a, b, name):
+    return Fe([max(x, y) for x, y in zip(a.mx, b.mx)], max(a.val, b.val), name)
+
+
+def inv_fq(a, name):
+    """Fq2::inv_fq (bn254_fq2_29.hip.h): r = one; per bit of p - 2 over the 261 bit positions of the limbs, most
+    significant first: r = r^2, then r = r a on a set bit"""
+    r = Fe([MASK] * 8 + [P >> 232], 1.0, "one")
+    for bit in bin(P - 2)[2:].rjust(261, "0"):
+        r = sqr(r, "r^2")
+        if bit == "1":
+            r = mul(r, a, "r*a")
+    r.name = name
+    return r
+
+
+def mul_points(group=16, where="mul_normalise"):
+    """mul_points.hip.h.  The ladder and the digit walk are pti_double and pti_madd on points of the invariant with a
+    canonical base or its normalised negation -- the cases above (pti_double is checked at the invariant inside
+    pti_add_nz, the negated base inside pti_madd).  New is the shared inversion of the normalisation: a = ZZ ZZZ (one for
+    an identity record), prefix products, inv_fq, the backward pass, the numerators X ZZZ and ZZ Y, and the affine
+    coordinates handed to affi_pack / to_ext, which canonicalise multiplication outputs below 2 p."""
+    px, py, pzz, pzzz = point_invariant()
+    one = Fe([MASK] * 8 + [P >> 232], 1.0, "one")
+    a = widen(mul(pzz, pzzz, "a"), one, "a")
+    xn, yn = mul(px, pzzz, "X*ZZZ"), mul(pzz, py, "ZZ*Y")
+    pre = one
+    for _ in range(group):
+        pre = widen(pre, mul(pre, a, "pre"), "pre")
+    inv = inv_fq(pre, "inv")
+    t = one
+    for _ in range(group):
+        t = widen(t, mul(inv, pre, "t"), "t")
+        inv = widen(inv, mul(inv, a, "inv"), "inv")
+    x, y = mul(xn, t, "x"), mul(yn, t, "y")
+    for f, lim in ((a, 1.04), (pre, 1.01), (inv, 1.01), (t, 1.01), (xn, 1.12), (yn, 1.10), (x, 1.01), (y, 1.01)):
+        if f.val >= lim + 0.005:
+            fail(f"{where}: {f.name} may reach {f.val:.3f}p, the header says < {lim}p")
+    for f in (x, y):
+        if f.val >= 2.0 or max(f.mx[:8]) > MASK:
+            fail(f"{where}: {f.name} is not a multiplication output below 2 p")
+    # a Jacobian base record (MulG1::load_base): zi = inv_fq(from_ext(z)), x = X zi^2, y = Y zi^3, then canonical(., 1)
+    ext = Fe([MASK] * 8 + [(1 << 24) - 1], (1 << 256) / P, "ext")          # any 256-bit integer: unpack256
+    cin = Fe([MASK] * 8 + [P >> 232], 1.0, "cin")
+    z, X, Y = mul(ext, cin, "z"), mul(ext, cin, "X"), mul(ext, cin, "Y")
+    zi = inv_fq(z, "zi")
+    zi2 = sqr(zi, "zi2")
+    bx, by = mul(X, zi2, "bx"), mul(Y, mul(zi2, zi, "zi3"), "by")
+    for f in (z, bx, by):
+        if f.val >= 2.0:
+            fail(f"load_base: {f.name} may reach {f.val:.2f}p, canonical(., 1) takes values below 2 p")
+
+
 def main():
     pti_madd()
     pti_mmadd()
     pti_add_nz()
+    mul_points()
     if problems:
         print("LIMB BOUNDS VIOLATED:")
         for p in sorted(set(problems)):
             print("  -", p)
         return 1
     print("fq29 bounds: every column sum < 2^64, every lifted subtraction non-negative, every returned point within "
-          "the invariant (pti_madd, pti_mmadd, pti_add_nz, pti_double)")
+          "the invariant (pti_madd, pti_mmadd, pti_add_nz, pti_double); the shared inversion of mul_points.hip.h hands "
+          "coordinates below 2 p to the packers")
     return 0
 
 

@@ -18,6 +18,11 @@ The square roots of the decompression kernels (compress_points.hip.h) are re-der
 acceptance test through the 8 p lift, the Fq2 root (norm, halving, the negation through the 4 p lift, the inversion of
 2 c, the final comparison through Fq2::sub<8>), the sign selection (canonical integer, the negated root squashed) and
 the right-hand sides x^3 + b the two decoders feed in.
+The batch scalar multiplication (mul_points.hip.h) adds no new point operation -- its ladder is doublings and mixed
+additions of carried points with a canonical base or its 4 p negation, its digit walk mixed additions alone, both inside
+the fixed point -- but a new normalisation: the shared inversion over kMulNormGroup records (prefix products of
+ZZ ZZZ with the identity's substitute one, Fq2::inv of the last prefix, the backward pass) and the numerators X ZZZ and
+ZZ Y; the affine coordinates it hands to aff2_pack / to_ext stay below 2 p.
 Prints the invariant and the intermediate bounds; exit status 1 if an assertion fails."""
 import sys
 
@@ -228,6 +233,31 @@ def decompress():         # the two decoders: x from the canonical integer, the 
     assert lifted < 1.05
 
 
+# ---- batch scalar multiplication (mul_points.hip.h) -------------------------------------------------------------------
+def mul_normalise(X, Y, ZZ, ZZZ, group=16):
+    """mul_normalise<MulG2> on `group` records of the invariant; an identity record contributes a = one = (rho mod p, 0)"""
+    one = (1.0, 0.0)
+    a = note("norm.a", tuple(max(u, v) for u, v in zip(mul(ZZ, ZZZ), one)))
+    xn, yn = note("norm.X*ZZZ", mul(X, ZZZ)), note("norm.ZZ*Y", mul(ZZ, Y))     # Y second: the 32 p lift multiplies ZZ
+    pre, worst = one, one
+    for _ in range(group):                                 # pre_i = pre_(i-1) a_i; every prefix is an operand later
+        pre = mul(pre, a)
+        worst = tuple(max(u, v) for u, v in zip(worst, pre))
+    note("norm.pre", worst)
+    inv = fq2_inv(worst)
+    t_worst = (0.0, 0.0)
+    for _ in range(group):                                 # t_i = inv pre_(i-1), inv = inv a_i
+        t = mul(inv, worst)
+        inv = tuple(max(u, v) for u, v in zip(inv, mul(inv, a)))
+        t_worst = tuple(max(u, v) for u, v in zip(t_worst, t))
+    note("norm.t", t_worst), note("norm.inv", inv)
+    x, y = note("norm.x", mul(xn, t_worst)), note("norm.y", mul(yn, t_worst))
+    assert max(a) < 1.29 and max(worst) < 1.21 and max(t_worst) < 1.24 and max(inv) < 1.24, (a, worst, t_worst, inv)
+    assert max(xn) < 1.25 and max(yn) < 1.51 and max(x) < 1.21 and max(y) < 1.27, (xn, yn, x, y)
+    assert max(x) < 2 and max(y) < 2                       # what Fq29::pack_canonical / to_ext canonicalise
+    return x, y
+
+
 def widen(a, b):
     return tuple(tuple(max(x, y) for x, y in zip(u, v)) for u, v in zip(a, b))
 
@@ -264,6 +294,7 @@ def main():
     assert max(SEEN["psi.X"]) < 1.21 and max(SEEN["psi.Y"]) < 1.3 and max(SEEN["psi.ZZ"]) < 1.03 and max(SEEN["neg.Y"]) < 1.2
     assert max(curve_equation()) < 9.5
     decompress()
+    mul_normalise(*pt)
     fq2_sqrt((4 - 1e-9, 4 - 1e-9))         # the raw-limb Fq2 root at the edge of its contract
     print("invariant: " + "  ".join(f"{k} < {max(v):.3f} p" for k, v in zip(claimed, pt)))
     for k in sorted(SEEN):
