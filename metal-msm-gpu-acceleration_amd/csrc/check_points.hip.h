@@ -37,25 +37,35 @@
 #include <string.h>
 
 #include "bn254_ec2_29.hip.h"
+#include "point_report.hip.h"
 
 namespace msm_amd {
 
-enum : uint32_t { kPointValid = 0, kPointNotReduced = 1, kPointNotOnCurve = 2, kPointNotInSubgroup = 3 };
 enum : uint32_t { kCheckCurve = 1, kCheckSubgroup = 2 };
-// G1 layouts as the C ABI numbers them (MSM_AMD_POINT_*; host_check.hip asserts the match)
-enum : int { kLayoutH2cAffine = 0, kLayoutArkProjective = 1, kLayoutArkAffine = 2, kLayoutJacBe32 = 3 };
+// Point layouts as the C ABI numbers them (MSM_AMD_POINT_*, MSM_AMD_G2_POINT_*; host_check.hip asserts the match)
+enum : int { kLayoutH2cAffine = 0, kLayoutArkProjective = 1, kLayoutArkAffine = 2, kLayoutJacBe32 = 3, kLayoutPrepared = 4 };
+enum : int { kG2LayoutH2cAffine = 0, kG2LayoutArkAffine = 1, kG2LayoutPrepared = 2 };
+// Kinds of layout an entry point may accept: the affine host layouts, the Jacobian / projective host layouts (G1 only),
+// the library's own *_PREPARED records
+enum : uint32_t { kKindAffine = 1, kKindJacobian = 2, kKindPrepared = 4, kKindHost = kKindAffine | kKindJacobian };
+
+// Record size of `layout` in its group if the layout is of one of `kinds`, 0 otherwise (unknown layouts, *_TABLES)
+MSM_HD uint32_t point_record_bytes(bool g2, int layout, uint32_t kinds) {
+  uint32_t kind = 0, bytes = 0;
+  if (g2) {
+    if (layout == kG2LayoutH2cAffine) kind = kKindAffine, bytes = 128;
+    else if (layout == kG2LayoutArkAffine) kind = kKindAffine, bytes = 136;
+    else if (layout == kG2LayoutPrepared) kind = kKindPrepared, bytes = 128;
+  } else {
+    if (layout == kLayoutH2cAffine) kind = kKindAffine, bytes = 64;
+    else if (layout == kLayoutArkAffine) kind = kKindAffine, bytes = 72;
+    else if (layout == kLayoutArkProjective || layout == kLayoutJacBe32) kind = kKindJacobian, bytes = 96;
+    else if (layout == kLayoutPrepared) kind = kKindPrepared, bytes = 64;
+  }
+  return (kind & kinds) ? bytes : 0u;
+}
 
 constexpr uint64_t kBnX0 = 4965661367192848881ull;   // p = 36 x0^4 + 36 x0^3 + 24 x0^2 + 6 x0 + 1, 63 bits
-
-// Device counters of one check call (64 bytes; k_check.hip adds to them with one atomic per wave and counter).
-struct CheckCounters {
-  uint32_t by_reason[4];
-  uint32_t n_identity;
-  uint32_t pad0;
-  uint64_t first_key;   // min over invalid records of (index << 2 | reason); all ones = none
-  uint32_t pad1[8];
-};
-static_assert(sizeof(CheckCounters) == 64, "CheckCounters must be 64 bytes");
 
 // Word `w` of a record (records of the ark affine layouts are only 8-byte aligned: word loads throughout)
 MSM_HD uint32_t check_word(const uint8_t* rec, int w) {

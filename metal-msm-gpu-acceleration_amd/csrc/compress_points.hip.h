@@ -37,19 +37,6 @@
 namespace msm_amd {
 
 enum : int { kCompressedArk = 0, kCompressedParity = 1 };
-enum : uint32_t { kPointBadEncoding = 4 };
-// output layouts of decompression / input layouts of compression as the C ABI numbers them (host_compress.hip asserts)
-enum : int { kLayoutPrepared = 4 };
-enum : int { kG2LayoutH2cAffine = 0, kG2LayoutArkAffine = 1, kG2LayoutPrepared = 2 };
-
-// Device counters of one decompress / compress call (64 bytes, the shape of CheckCounters with a fifth reason)
-struct CompressCounters {
-  uint32_t by_reason[5];   // compress: [1] = records written as all 0xFF
-  uint32_t n_identity;
-  uint64_t first_key;      // min over invalid records of (index << 3 | reason); all ones = none
-  uint32_t pad[8];
-};
-static_assert(sizeof(CompressCounters) == 64, "CompressCounters must be 64 bytes");
 
 MSM_HD constexpr uint32_t comp_const(int which, int i) {
   constexpr uint32_t c[2][9] = {

@@ -3,11 +3,8 @@
 // (msm_host.hip) use.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <thread>
-#include <vector>
-
 #include "../../include/msm_amd.h"
+#include "host_threads.h"
 #include "launch_mul.h"
 
 namespace msm_amd {
@@ -18,14 +15,6 @@ static_assert(MSM_AMD_SCALAR_MONT_LE == 0 && MSM_AMD_SCALAR_CANON_LE == 1 && MSM
 static_assert(sizeof(PtI) % 16 == 0 && sizeof(PtI2) % 16 == 0 && sizeof(AffPacked) == 64 && sizeof(Aff2Packed) == 128,
               "records move in 16-byte pieces");
 
-size_t mul_in_stride(bool g2, int layout, bool prepared_too) {
-  if (!prepared_too && layout == (g2 ? (int)MSM_AMD_G2_POINT_PREPARED : (int)MSM_AMD_POINT_PREPARED)) return 0;
-  return g2 ? MulG2::in_stride(layout) : MulG1::in_stride(layout);
-}
-size_t mul_out_stride(bool g2, int layout, bool prepared_too) {
-  if (!prepared_too && layout == (g2 ? (int)MSM_AMD_G2_POINT_PREPARED : (int)MSM_AMD_POINT_PREPARED)) return 0;
-  return g2 ? MulG2::out_stride(layout) : MulG1::out_stride(layout);
-}
 bool mul_scalar_layout_known(int scalar_layout) {
   return scalar_layout >= MSM_AMD_SCALAR_MONT_LE && scalar_layout <= MSM_AMD_SCALAR_CANON_BE32;
 }
@@ -34,29 +23,10 @@ size_t mul_table_bytes(bool g2) { return (size_t)kMulTableEntries * (g2 ? sizeof
 
 namespace {
 
-unsigned worker_count(int threads, size_t items) {
-  const unsigned want = threads > 0 ? (unsigned)threads : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-  return (unsigned)std::max<size_t>(1, std::min<size_t>(want, items));
-}
-
-// fn(lo, hi) on T threads over [0, items)
-template <typename F>
-void for_ranges(unsigned T, size_t items, F fn) {
-  const size_t chunk = (items + T - 1) / T;
-  auto worker = [&](unsigned t) {
-    const size_t lo = std::min(items, t * chunk), hi = std::min(items, lo + chunk);
-    if (lo < hi) fn(lo, hi);
-  };
-  std::vector<std::thread> pool;
-  for (unsigned t = 1; t < T; ++t) pool.emplace_back(worker, t);
-  worker(0);
-  for (std::thread& th : pool) th.join();
-}
-
 template <class G>
 int host_mul(int scalar_layout, int layout_in, int base_mode, const void* scalars_v, const void* points_v, size_t n,
              int layout_out, int threads, void* out_v) {
-  const size_t in_stride = mul_in_stride(G::kG2, layout_in, false), out_stride = mul_out_stride(G::kG2, layout_out, false);
+  const size_t in_stride = point_record_bytes(G::kG2, layout_in, kKindHost), out_stride = point_record_bytes(G::kG2, layout_out, kKindAffine);
   if (!mul_scalar_layout_known(scalar_layout) || in_stride == 0 || out_stride == 0 ||
       (base_mode != kMulBaseEach && base_mode != kMulBaseOne) || n > 0xFFFFFFFFull)
     return MSM_AMD_INPUT_ERROR;
@@ -69,12 +39,12 @@ int host_mul(int scalar_layout, int layout_in, int base_mode, const void* scalar
   if (base_mode == kMulBaseOne) {
     table.resize(kMulTableEntries);
     const typename G::Aff base = G::load_base(layout_in, points);
-    for_ranges(worker_count(threads, kMulTableEntries), kMulTableEntries, [&](size_t lo, size_t hi) {
+    for_ranges(worker_count(threads, kMulTableEntries), kMulTableEntries, [&](unsigned, size_t lo, size_t hi) {
       for (size_t e = lo; e < hi; ++e) table[e] = mul_table_entry<G>(base, (uint32_t)e);
     });
   }
   const size_t groups = (n + kMulNormGroup - 1) / kMulNormGroup;
-  for_ranges(worker_count(threads, groups), groups, [&](size_t lo, size_t hi) {
+  for_ranges(worker_count(threads, groups), groups, [&](unsigned, size_t lo, size_t hi) {
     alignas(16) typename G::Pt recs[kMulNormGroup];
     for (size_t g = lo; g < hi; ++g) {
       const size_t first = g * kMulNormGroup;

@@ -3,39 +3,15 @@
 //   decompress_g2_kernel   64-byte records -> affine or prepared 128-byte records: two Fq roots and one inversion
 //   compress_g1_kernel / compress_g2_kernel   affine records -> compressed records (two / four Montgomery reductions)
 //   sqrt_raw_kernel        the root bodies at raw limbs (MSM_AMD_RAW_FE_SQRT, MSM_AMD_G2_RAW_FQ2_SQRT)
-// Report: as k_check.hip -- every wave ballots its lanes per reason code and adds the popcounts to the 64-byte
-// CompressCounters with one atomic per wave and non-zero counter; the first invalid lane of a wave folds
-// (index << 3 | reason) into first_key with one 64-bit atomic minimum.  An invalid record still gets an output: the
-// layout's identity encoding.  None of these kernels uses scratch (`make resource-usage`, tests/test_gpu_compress.py).
+// Report: point_report<5> of point_report.hip.h.  An invalid record still gets an output: the layout's identity
+// encoding.  None of these kernels uses scratch (`make resource-usage`, tests/test_gpu_compress.py).
 #include "launch_compress.h"
 
 namespace msm_amd {
 
-__device__ __forceinline__ void compress_report(bool active, uint32_t t, uint32_t reason, bool identity,
-                                                uint8_t* __restrict__ reasons, CompressCounters* __restrict__ counters) {
-  if (active && reasons) reasons[t] = (uint8_t)reason;
-  const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-  for (uint32_t r = 0; r < 5; ++r) {
-    const uint64_t m = __ballot(active && reason == r);
-    if (lane == 0 && m) atomicAdd(&counters->by_reason[r], (uint32_t)__popcll(m));
-  }
-  const uint64_t mi = __ballot(active && identity);
-  if (lane == 0 && mi) atomicAdd(&counters->n_identity, (uint32_t)__popcll(mi));
-  const uint64_t bad = __ballot(active && reason != kPointValid);
-  if (bad && lane == (uint32_t)(__ffsll((unsigned long long)bad) - 1))
-    atomicMin(reinterpret_cast<unsigned long long*>(&counters->first_key), ((unsigned long long)t << 3) | reason);
-}
-
-__global__ void __launch_bounds__(64) compress_reset_kernel(CompressCounters* __restrict__ counters) {
-  uint32_t* w = reinterpret_cast<uint32_t*>(counters);
-  if (threadIdx.x < 16) w[threadIdx.x] = (threadIdx.x == 6 || threadIdx.x == 7) ? 0xFFFFFFFFu : 0u;
-}
-static_assert(offsetof(CompressCounters, first_key) == 24, "compress_reset_kernel writes first_key as words 6, 7");
-
 __global__ void __launch_bounds__(256)
 decompress_g1_kernel(const uint8_t* __restrict__ in, int format, uint32_t n, int layout, uint32_t stride,
-                     uint8_t* __restrict__ out, uint8_t* __restrict__ reasons, CompressCounters* __restrict__ counters) {
+                     uint8_t* __restrict__ out, uint8_t* __restrict__ reasons, PointCounters* __restrict__ counters) {
   const uint64_t t64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;   // n may be close to 2^32
   const bool active = t64 < n;
   const uint32_t t = (uint32_t)t64;
@@ -46,12 +22,12 @@ decompress_g1_kernel(const uint8_t* __restrict__ in, int format, uint32_t n, int
     reason = decompress_record_g1(format, in + (size_t)t * 32, pt, identity);
     decompress_store_g1(layout, out + (size_t)t * stride, pt);
   }
-  compress_report(active, t, reason, identity, reasons, counters);
+  point_report<5>(active, t, reason, identity, reasons, counters);
 }
 
 __global__ void __launch_bounds__(256)
 decompress_g2_kernel(const uint8_t* __restrict__ in, int format, uint32_t n, int layout, uint32_t stride,
-                     uint8_t* __restrict__ out, uint8_t* __restrict__ reasons, CompressCounters* __restrict__ counters) {
+                     uint8_t* __restrict__ out, uint8_t* __restrict__ reasons, PointCounters* __restrict__ counters) {
   const uint64_t t64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool active = t64 < n;
   const uint32_t t = (uint32_t)t64;
@@ -62,18 +38,18 @@ decompress_g2_kernel(const uint8_t* __restrict__ in, int format, uint32_t n, int
     reason = decompress_record_g2(format, in + (size_t)t * 64, pt, identity);
     decompress_store_g2(layout, out + (size_t)t * stride, pt);
   }
-  compress_report(active, t, reason, identity, reasons, counters);
+  point_report<5>(active, t, reason, identity, reasons, counters);
 }
 
 // records written as all 0xFF are counted in by_reason[kPointNotReduced]: one ballot and one atomic per wave
-__device__ __forceinline__ void compress_count_bad(bool bad, CompressCounters* __restrict__ counters) {
+__device__ __forceinline__ void compress_count_bad(bool bad, PointCounters* __restrict__ counters) {
   const uint64_t m = __ballot(bad);
   if ((threadIdx.x & 63u) == 0 && m) atomicAdd(&counters->by_reason[kPointNotReduced], (uint32_t)__popcll(m));
 }
 
 __global__ void __launch_bounds__(256)
 compress_g1_kernel(const uint8_t* __restrict__ in, int layout, uint32_t stride, uint32_t n, int format,
-                   uint8_t* __restrict__ out, CompressCounters* __restrict__ counters) {
+                   uint8_t* __restrict__ out, PointCounters* __restrict__ counters) {
   const uint64_t t64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool active = t64 < n;
   const uint32_t t = (uint32_t)t64;
@@ -84,7 +60,7 @@ compress_g1_kernel(const uint8_t* __restrict__ in, int layout, uint32_t stride, 
 
 __global__ void __launch_bounds__(256)
 compress_g2_kernel(const uint8_t* __restrict__ in, int layout, uint32_t stride, uint32_t n, int format,
-                   uint8_t* __restrict__ out, CompressCounters* __restrict__ counters) {
+                   uint8_t* __restrict__ out, PointCounters* __restrict__ counters) {
   const uint64_t t64 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool active = t64 < n;
   const uint32_t t = (uint32_t)t64;
@@ -103,12 +79,8 @@ sqrt_raw_kernel(int g2, const uint32_t* __restrict__ a, uint32_t* __restrict__ o
 
 static dim3 compress_grid(uint32_t n) { return dim3((uint32_t)(((uint64_t)n + 255) / 256)); }
 
-void launch_compress_reset(hipStream_t st, CompressCounters* counters) {
-  hipLaunchKernelGGL(compress_reset_kernel, dim3(1), dim3(64), 0, st, counters);
-}
-
 void launch_decompress(hipStream_t st, bool g2, int format, const void* in, uint32_t n, int layout, uint32_t stride,
-                       void* out, uint8_t* reasons, CompressCounters* counters) {
+                       void* out, uint8_t* reasons, PointCounters* counters) {
   if (g2)
     hipLaunchKernelGGL(decompress_g2_kernel, compress_grid(n), dim3(256), 0, st, (const uint8_t*)in, format, n, layout, stride,
                        (uint8_t*)out, reasons, counters);
@@ -118,7 +90,7 @@ void launch_decompress(hipStream_t st, bool g2, int format, const void* in, uint
 }
 
 void launch_compress(hipStream_t st, bool g2, int layout, uint32_t stride, const void* in, uint32_t n, int format, void* out,
-                     CompressCounters* counters) {
+                     PointCounters* counters) {
   if (g2)
     hipLaunchKernelGGL(compress_g2_kernel, compress_grid(n), dim3(256), 0, st, (const uint8_t*)in, layout, stride, n, format,
                        (uint8_t*)out, counters);

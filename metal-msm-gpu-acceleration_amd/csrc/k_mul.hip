@@ -70,10 +70,10 @@ void launch_mul_each(hipStream_t st, bool g2, int scalar_layout, const void* sca
                      uint32_t n, void* xyzz) {
   if (g2)
     hipLaunchKernelGGL(mul_each_kernel<MulG2>, dim3((uint32_t)(((uint64_t)n + 63) / 64)), dim3(64), 0, st, scalar_layout,
-                       (const uint8_t*)scalars, layout_in, MulG2::in_stride(layout_in), (const uint8_t*)points, n, (PtI2*)xyzz);
+                       (const uint8_t*)scalars, layout_in, point_record_bytes(true, layout_in, kKindHost | kKindPrepared), (const uint8_t*)points, n, (PtI2*)xyzz);
   else
     hipLaunchKernelGGL(mul_each_kernel<MulG1>, dim3((uint32_t)(((uint64_t)n + 255) / 256)), dim3(256), 0, st, scalar_layout,
-                       (const uint8_t*)scalars, layout_in, MulG1::in_stride(layout_in), (const uint8_t*)points, n, (PtI*)xyzz);
+                       (const uint8_t*)scalars, layout_in, point_record_bytes(false, layout_in, kKindHost | kKindPrepared), (const uint8_t*)points, n, (PtI*)xyzz);
 }
 
 void launch_mul_normalise(hipStream_t st, bool g2, void* xyzz, uint32_t n, int layout_out, void* out) {
@@ -81,10 +81,10 @@ void launch_mul_normalise(hipStream_t st, bool g2, void* xyzz, uint32_t n, int l
   const dim3 grid((uint32_t)((groups + 63) / 64)), block(64);
   if (g2)
     hipLaunchKernelGGL(mul_normalise_kernel<MulG2>, grid, block, 0, st, (PtI2*)xyzz, n, layout_out,
-                       MulG2::out_stride(layout_out), (uint8_t*)out);
+                       point_record_bytes(true, layout_out, kKindAffine | kKindPrepared), (uint8_t*)out);
   else
     hipLaunchKernelGGL(mul_normalise_kernel<MulG1>, grid, block, 0, st, (PtI*)xyzz, n, layout_out,
-                       MulG1::out_stride(layout_out), (uint8_t*)out);
+                       point_record_bytes(false, layout_out, kKindAffine | kKindPrepared), (uint8_t*)out);
 }
 
 }  // namespace msm_amd

@@ -17,9 +17,7 @@ void launch_mul_each(hipStream_t st, bool g2, int scalar_layout, const void* sca
 // n XYZZ records (overwritten) -> n affine records of layout_out, one inversion per kMulNormGroup consecutive records
 void launch_mul_normalise(hipStream_t st, bool g2, void* xyzz, uint32_t n, int layout_out, void* out);
 
-// host_mul.hip: record sizes of the layouts a call takes (`prepared_too`: the device calls), 0 = refused
-size_t mul_in_stride(bool g2, int layout, bool prepared_too);
-size_t mul_out_stride(bool g2, int layout, bool prepared_too);
+// host_mul.hip
 bool mul_scalar_layout_known(int scalar_layout);
 size_t mul_xyzz_bytes(bool g2);
 size_t mul_table_bytes(bool g2);

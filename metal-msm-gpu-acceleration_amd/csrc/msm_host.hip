@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -184,32 +185,18 @@ struct msm_amd_tables : TablesRecord {};
 // that a G1 handle is no G2 handle and the reverse.
 struct msm_amd_g2_tables : TablesRecord {};
 
-// Buffers of a point check (msm_amd_check_points*, msm_amd_g2_check_points*): the 64-byte counters and their page-locked
-// copy, the reason bytes and, for G1, the staging of host points.  One per group: a G2 check touches G2State only.
-struct CheckState {
-  enum { EV_CHECK_START = 0, EV_CHECK_KERNEL, EV_CHECK_DONE, EV_CHECK_COUNT };
-  DeviceBuf in_points, reasons, counters;
-  CheckCounters* h_counters = nullptr;   // pinned
-  hipEvent_t ev[EV_CHECK_COUNT] = {};
-  bool ready = false;
-};
-
-// Buffers of a decompress / compress call (msm_amd_decompress_points*, msm_amd_compress_points* and their G2 forms): the
-// 64-byte counters and their page-locked copy, the reason bytes and, for the host-buffer calls, the staging of the
-// caller's input and output.  One per group: a G2 call touches G2State only.
-struct CompressState {
-  enum { EV_COMP_START = 0, EV_COMP_KERNEL, EV_COMP_DONE, EV_COMP_COUNT };
-  DeviceBuf in, out, reasons, counters;
-  CompressCounters* h_counters = nullptr;   // pinned
-  hipEvent_t ev[EV_COMP_COUNT] = {};
-  bool ready = false;
-};
-
-// Buffers of a scalar-multiplication call (msm_amd_mul_points*, msm_amd_g2_mul_points*): the fixed-base table, the XYZZ
-// records of one chunk of outputs and, for the host-buffer calls, the staging of scalars, bases and output.  One per
-// group: a G2 call touches G2State only.
-struct MulState {
-  DeviceBuf table, xyzz, in_scalars, in_points, out;
+// Buffers of the point calls of one group (check, decompress, compress and mul_points; point_call below): the staging of
+// the host-buffer calls, the 64-byte counters with their page-locked copy and events, and the device-side scratch of
+// mul_points.  One per group: a G2 call touches G2State only.
+struct PointCallState {
+  enum { EV_PT_START = 0, EV_PT_KERNEL, EV_PT_DONE, EV_PT_COUNT };
+  DeviceBuf in[2], out, reasons;   // staging of host inputs (mul_points: scalars, bases), output and reason bytes
+  DeviceBuf counters;              // PointCounters
+  DeviceBuf table, xyzz;           // mul_points: the fixed-base table, the XYZZ records of one chunk of outputs
+  PointCounters* h_counters = nullptr;   // pinned
+  hipEvent_t ev[EV_PT_COUNT] = {};
+  bool ready = false;              // counters, h_counters and ev exist
+  std::array<DeviceBuf*, 7> bufs() { return {&in[0], &in[1], &out, &reasons, &counters, &table, &xyzz}; }
 };
 
 // State of the G2 MSM (msm_amd_msm_g2*): one blocking call at a time on the main stream, through the instance body of
@@ -219,9 +206,7 @@ struct G2State {
   Workspace ws;
   InstanceSlot slot;
   DeviceBuf in_scalars, in_points;   // staging of host inputs
-  CheckState check;   // msm_amd_g2_check_points*: host points are staged in in_points above
-  CompressState compress;   // msm_amd_g2_decompress_points*, msm_amd_g2_compress_points*
-  MulState mul;             // msm_amd_g2_mul_points*
+  PointCallState points;   // the G2 point calls; msm_amd_g2_check_points stages host points in in_points above
   // Stage tap (msm_amd_test_g2_last_plan / msm_amd_test_g2_stage_copy): the plan of the last run_msm_g2, valid only
   // while that call was the last one and succeeded.  Its plan counters are in `slot`, behind the partial points.
   Plan last_plan{};
@@ -250,9 +235,7 @@ struct msm_amd_ctx {
   bool lone_single_stream = true;        // MSM_AMD_LONE_SINGLE_STREAM=0: a lone instance uses the stream split too
   Workspace ws[kWorkspaces];
   G2State g2;
-  CheckState check;   // msm_amd_check_points* (G1)
-  CompressState compress;   // msm_amd_decompress_points*, msm_amd_compress_points* (G1)
-  MulState mul;             // msm_amd_mul_points* (G1)
+  PointCallState points;   // the G1 point calls
   size_t mul_chunk = (size_t)1 << 18;   // outputs per chunk of a mul_points call (MSM_AMD_MUL_CHUNK), a multiple of kMulNormGroup
   std::mutex mu;
   std::string last_error;
@@ -2176,13 +2159,9 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
     kill_event(ctx->ws[k].reduce_done);
   }
   kill_slot_events(ctx->g2.slot);   // (g2.ws has no hand-off events)
-  for (CheckState* cs : {&ctx->check, &ctx->g2.check}) {
-    for (hipEvent_t& e : cs->ev) kill_event(e);
-    cs->ready = false;
-  }
-  for (CompressState* cs : {&ctx->compress, &ctx->g2.compress}) {
-    for (hipEvent_t& e : cs->ev) kill_event(e);
-    cs->ready = false;
+  for (PointCallState* ps : {&ctx->points, &ctx->g2.points}) {
+    for (hipEvent_t& e : ps->ev) kill_event(e);
+    ps->ready = false;
   }
   for (hipEvent_t& e : ctx->uploaded) kill_event(e);
   kill_event(ctx->upload_done);
@@ -2206,18 +2185,11 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
   kill_workspace(ctx->g2.ws);
   for (DeviceBuf* b : {&ctx->g2.in_scalars, &ctx->g2.in_points}) kill_buf(*b);
   kill_slot_memory(ctx->g2.slot);
-  for (CheckState* cs : {&ctx->check, &ctx->g2.check}) {
-    for (DeviceBuf* b : {&cs->in_points, &cs->reasons, &cs->counters}) kill_buf(*b);
-    if (cs->h_counters) (void)hipHostFree(cs->h_counters);
-    cs->h_counters = nullptr;
+  for (PointCallState* ps : {&ctx->points, &ctx->g2.points}) {
+    for (DeviceBuf* b : ps->bufs()) kill_buf(*b);
+    if (ps->h_counters) (void)hipHostFree(ps->h_counters);
+    ps->h_counters = nullptr;
   }
-  for (CompressState* cs : {&ctx->compress, &ctx->g2.compress}) {
-    for (DeviceBuf* b : {&cs->in, &cs->out, &cs->reasons, &cs->counters}) kill_buf(*b);
-    if (cs->h_counters) (void)hipHostFree(cs->h_counters);
-    cs->h_counters = nullptr;
-  }
-  for (MulState* ms : {&ctx->mul, &ctx->g2.mul})
-    for (DeviceBuf* b : {&ms->table, &ms->xyzz, &ms->in_scalars, &ms->in_points, &ms->out}) kill_buf(*b);
   tables_release_all(ctx->live_tables);
   tables_release_all(ctx->live_g2_tables);
   for (DeviceBuf* b : {&ctx->scratch_a, &ctx->scratch_b, &ctx->scratch_c, &ctx->scratch_b2, &ctx->scratch_c2}) kill_buf(*b);
@@ -3296,8 +3268,8 @@ int msm_amd_test_fill_workspaces(msm_amd_ctx* ctx, uint8_t byte) {
   for (Workspace* w : all)
     for (DeviceBuf* b : {&w->buckets, &w->item_partials, &w->S, &w->T, &w->partial})
       if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
-  for (MulState* ms : {&ctx->mul, &ctx->g2.mul})   // the XYZZ records and the fixed-base table of the mul_points calls
-    for (DeviceBuf* b : {&ms->xyzz, &ms->table})
+  for (PointCallState* ps : {&ctx->points, &ctx->g2.points})   // the XYZZ records and the fixed-base table of the mul_points calls
+    for (DeviceBuf* b : {&ps->xyzz, &ps->table})
       if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
   return sync_stream_bounded(ctx, ctx->stream, __func__);
 }
@@ -3627,113 +3599,218 @@ int msm_amd_test_op_g2(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32
 
 }  // extern "C"
 
-// ---- point validation (msm_amd_check_points*, msm_amd_g2_check_points*) ---------------------------------------------
+// ---- the point calls: check, decompress, compress and mul_points of both groups -------------------------------------
+// One discipline for all sixteen entry points (point_call): ctx lock, bounded drain of the ctx's earlier work, every
+// buffer sized on the idle ctx before anything is enqueued, host input through the page-locked staging ring, the
+// caller's kernels on the main stream, a bounded poll for the 64-byte counters (the calls that have them), output and
+// reason bytes behind a bounded stream wait.  Each call below validates its own enums, describes its buffers in a
+// PointCall and passes two callables: one enqueues its kernels, one takes the finished counters.
 namespace {
 
-const char* check_name(bool g2) { return g2 ? "msm_amd_g2_check_points" : "msm_amd_check_points"; }
+struct PointCall {
+  std::string who;                  // the entry point, in every message
+  const char* first_use = nullptr;  // counters != 0: what a first call of the group names when it has to wait to allocate
+  bool g2 = false, host = false;    // host: in / out / reasons are host memory and go through the group's staging
+  bool counters = false;            // reset, timed by events and read back; mul_points has none
+  bool null_arg = false;            // some required pointer is null
+  size_t n = 0;                     // records (and reason bytes)
+  const void* in[2] = {};
+  size_t in_bytes[2] = {};
+  void* out = nullptr;
+  size_t out_bytes = 0;
+  uint8_t* reasons = nullptr;       // optional
+  size_t table_bytes = 0, xyzz_bytes = 0;
+  DeviceBuf* stage_in0 = nullptr;   // staging of in[0] if not the state's own (the G2 check: G2State::in_points)
+};
 
-int check_args(msm_amd_ctx* ctx, bool g2, int layout, const void* points, size_t n, uint32_t checks,
-               const msm_amd_check_report* report) {
-  if (!ctx || !report) return MSM_AMD_INPUT_ERROR;
-  const std::string who = check_name(g2);
-  if (check_stride(g2, layout) == 0)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": takes the host point layouts only (not *_PREPARED / *_TABLES)");
-  if (checks == 0 || (checks & ~(uint32_t)(MSM_AMD_CHECK_CURVE | MSM_AMD_CHECK_SUBGROUP)))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": checks must be MSM_AMD_CHECK_CURVE and / or MSM_AMD_CHECK_SUBGROUP");
-  if (n > 0xFFFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": n >= 2^32");
-  if (n > 0 && !points) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": null pointer with n > 0");
-  return MSM_AMD_OK;
-}
+// what the kernels of a call see: device memory throughout
+struct PointIo {
+  const void* in[2];
+  void* out;
+  uint8_t* reasons;
+  PointCounters* counters;
+  void *table, *xyzz;
+};
 
-// Every ctx check call starts here (ctx->mu held): the ctx's earlier work is waited for, with the wait bound.
-int check_begin(msm_amd_ctx* ctx, bool g2) {
+// launch(stream, io) enqueues the call's kernels; done(counters, device_ms) takes the result of a call with counters
+// (and the empty counters of a call with n == 0, whatever its kind).
+template <class Launch, class Done>
+int point_call(msm_amd_ctx* ctx, const PointCall& c, Launch launch, Done done) {
+  if (c.n > 0xFFFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": n >= 2^32");
+  if (c.n == 0) {
+    done(point_counters_empty(), 0.0f);
+    return MSM_AMD_OK;
+  }
+  if (c.null_arg) return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": null pointer with n > 0");
+  std::lock_guard<std::mutex> lk(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (int rc = recover_if_stalled(ctx)) return fail(ctx, rc, std::string(check_name(g2)) + ": " + ctx->last_error);
+  if (int rc = recover_if_stalled(ctx)) return fail(ctx, rc, c.who + ": " + ctx->last_error);
   if (!drain_or_mark_stalled(ctx))
-    return fail(ctx, MSM_AMD_PIPELINE_ERROR, std::string(check_name(g2)) + ": device busy past the wait bound of " +
+    return fail(ctx, MSM_AMD_PIPELINE_ERROR, c.who + ": device busy past the wait bound of " +
                                                  std::to_string(ctx->wait_timeout_ms) + " ms (msm_amd_synchronize waits again)");
-  return MSM_AMD_OK;
-}
-
-// The check of n device-resident records on the main stream and the bounded wait for its counters.  The ctx is idle
-// (check_begin), so the first call may allocate the counters and their page-locked copy.
-int run_check(msm_amd_ctx* ctx, CheckState& cs, bool g2, int layout, const void* d_points, size_t n, uint32_t checks,
-              uint8_t* d_reasons, msm_amd_check_report* report) {
+  PointCallState& s = c.g2 ? ctx->g2.points : ctx->points;
   hipStream_t st = ctx->stream;
-  if (!cs.ready) {
-    if (int rc = quiesce_for_allocation(ctx, "the report buffer of a point check")) return rc;
-    if (int rc = ensure(ctx, cs.counters, sizeof(CheckCounters))) return rc;
-    if (!cs.h_counters) HIP_TRY(ctx, hipHostMalloc((void**)&cs.h_counters, sizeof(CheckCounters), hipHostMallocDefault));
-    for (hipEvent_t& e : cs.ev)
-      if (!e) HIP_TRY(ctx, hipEventCreate(&e));
-    cs.ready = true;
-  }
-  CheckCounters* d_counters = (CheckCounters*)cs.counters.p;
-  launch_check_reset(st, d_counters);
-  HIP_TRY(ctx, hipEventRecord(cs.ev[CheckState::EV_CHECK_START], st));
-  if (g2)
-    launch_check_g2(st, d_points, layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n, checks, d_reasons, d_counters);
-  else
-    launch_check_g1(st, d_points, layout, (uint32_t)check_stride(false, layout), (uint32_t)n, d_reasons, d_counters);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipEventRecord(cs.ev[CheckState::EV_CHECK_KERNEL], st));
-  HIP_TRY(ctx, hipMemcpyAsync(cs.h_counters, d_counters, sizeof(CheckCounters), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipEventRecord(cs.ev[CheckState::EV_CHECK_DONE], st));
-  const hipError_t we = wait_event(cs.ev[CheckState::EV_CHECK_DONE], ctx->wait_timeout_ms);
-  if (we == hipErrorNotReady) {
-    ctx->stalled = true;
-    return fail(ctx, MSM_AMD_PIPELINE_ERROR, "timed out after " + std::to_string(ctx->wait_timeout_ms) +
-                                                 " ms waiting for " + check_name(g2));
-  }
-  if (we != hipSuccess) return fail(ctx, MSM_AMD_PIPELINE_ERROR, std::string(check_name(g2)) + ": " + hipGetErrorString(we));
-  check_report_from_counters(*cs.h_counters, n, event_span(cs.ev[CheckState::EV_CHECK_START], cs.ev[CheckState::EV_CHECK_KERNEL]),
-                             report);
-  return MSM_AMD_OK;
-}
-
-void empty_check_report(msm_amd_check_report* report) {
-  CheckCounters none{};
-  none.first_key = ~0ull;
-  check_report_from_counters(none, 0, 0.0f, report);
-}
-
-int check_device(msm_amd_ctx* ctx, bool g2, int layout, const void* d_points, size_t n, uint32_t checks,
-                 uint8_t* d_reasons, msm_amd_check_report* report) {
-  if (int rc = check_args(ctx, g2, layout, d_points, n, checks, report)) return rc;
-  if (n == 0) {
-    empty_check_report(report);
-    return MSM_AMD_OK;
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (int rc = check_begin(ctx, g2)) return rc;
-  return run_check(ctx, g2 ? ctx->g2.check : ctx->check, g2, layout, d_points, n, checks, d_reasons, report);
-}
-
-// Host buffers: the points go up in chunks through the page-locked staging ring into the group's staging buffer (grown
-// only on an idle ctx, like every workspace), the reason bytes come back after the counters.
-int check_host_buffers(msm_amd_ctx* ctx, bool g2, int layout, const void* points, size_t n, uint32_t checks,
-                       uint8_t* reasons, msm_amd_check_report* report) {
-  if (int rc = check_args(ctx, g2, layout, points, n, checks, report)) return rc;
-  if (n == 0) {
-    empty_check_report(report);
-    return MSM_AMD_OK;
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (int rc = check_begin(ctx, g2)) return rc;
-  CheckState& cs = g2 ? ctx->g2.check : ctx->check;
-  DeviceBuf& stage = g2 ? ctx->g2.in_points : cs.in_points;
-  const size_t bytes = n * check_stride(g2, layout);
   int rc;
-  if ((rc = ensure(ctx, stage, bytes))) return rc;
-  if (reasons && (rc = ensure(ctx, cs.reasons, n))) return rc;
-  if ((rc = staged_upload(ctx, stage.p, points, bytes, ctx->stream))) return rc;
-  uint8_t* d_reasons = reasons ? (uint8_t*)cs.reasons.p : nullptr;
-  if ((rc = run_check(ctx, cs, g2, layout, stage.p, n, checks, d_reasons, report))) return rc;
-  if (reasons) {
-    HIP_TRY(ctx, hipMemcpyAsync(reasons, d_reasons, n, hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = sync_stream_bounded(ctx, ctx->stream, check_name(g2)))) return rc;
+  // the ctx is idle: the first call with counters allocates them, and every buffer of this call is sized now
+  if (c.counters && !s.ready) {
+    if ((rc = quiesce_for_allocation(ctx, c.first_use))) return rc;
+    if ((rc = ensure(ctx, s.counters, sizeof(PointCounters)))) return rc;
+    if (!s.h_counters) HIP_TRY(ctx, hipHostMalloc((void**)&s.h_counters, sizeof(PointCounters), hipHostMallocDefault));
+    for (hipEvent_t& e : s.ev)
+      if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    s.ready = true;
   }
+  if ((rc = ensure(ctx, s.table, c.table_bytes))) return rc;
+  if ((rc = ensure(ctx, s.xyzz, c.xyzz_bytes))) return rc;
+  PointIo io = {{c.in[0], c.in[1]}, c.out, c.reasons, (PointCounters*)s.counters.p, s.table.p, s.xyzz.p};
+  if (c.host) {
+    DeviceBuf* stage[2] = {c.stage_in0 ? c.stage_in0 : &s.in[0], &s.in[1]};
+    for (int k = 0; k < 2; ++k)
+      if ((rc = ensure(ctx, *stage[k], c.in_bytes[k]))) return rc;
+    if ((rc = ensure(ctx, s.out, c.out_bytes))) return rc;
+    if (c.reasons && (rc = ensure(ctx, s.reasons, c.n))) return rc;
+    for (int k = 0; k < 2; ++k)
+      if (c.in_bytes[k]) {
+        if ((rc = staged_upload(ctx, stage[k]->p, c.in[k], c.in_bytes[k], st))) return rc;
+        io.in[k] = stage[k]->p;
+      }
+    if (c.out_bytes) io.out = s.out.p;
+    if (c.reasons) io.reasons = (uint8_t*)s.reasons.p;
+  }
+  if (c.counters) {
+    launch_point_reset(st, io.counters);
+    HIP_TRY(ctx, hipEventRecord(s.ev[PointCallState::EV_PT_START], st));
+  }
+  launch(st, io);
+  HIP_TRY(ctx, hipGetLastError());
+  if (c.counters) {
+    HIP_TRY(ctx, hipEventRecord(s.ev[PointCallState::EV_PT_KERNEL], st));
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_counters, io.counters, sizeof(PointCounters), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipEventRecord(s.ev[PointCallState::EV_PT_DONE], st));
+    const hipError_t we = wait_event(s.ev[PointCallState::EV_PT_DONE], ctx->wait_timeout_ms);
+    if (we == hipErrorNotReady) {
+      ctx->stalled = true;
+      return fail(ctx, MSM_AMD_PIPELINE_ERROR, "timed out after " + std::to_string(ctx->wait_timeout_ms) + " ms waiting for " + c.who);
+    }
+    if (we != hipSuccess) return fail(ctx, MSM_AMD_PIPELINE_ERROR, c.who + ": " + hipGetErrorString(we));
+    done(*s.h_counters, event_span(s.ev[PointCallState::EV_PT_START], s.ev[PointCallState::EV_PT_KERNEL]));
+  }
+  const bool copy_out = c.host && c.out_bytes, copy_reasons = c.host && c.reasons;
+  if (copy_out) HIP_TRY(ctx, hipMemcpyAsync(c.out, io.out, c.out_bytes, hipMemcpyDeviceToHost, st));
+  if (copy_reasons) HIP_TRY(ctx, hipMemcpyAsync(c.reasons, io.reasons, c.n, hipMemcpyDeviceToHost, st));
+  // (a call with counters and nothing to copy back has already waited for all of its work)
+  if (!c.counters || copy_out || copy_reasons) return sync_stream_bounded(ctx, st, c.who.c_str());
   return MSM_AMD_OK;
+}
+
+// ---- point validation (msm_amd_check_points*, msm_amd_g2_check_points*) ---------------------------------------------
+int check_call(msm_amd_ctx* ctx, bool g2, bool host, int layout, const void* points, size_t n, uint32_t checks,
+               uint8_t* reasons, msm_amd_check_report* report) {
+  if (!ctx || !report) return MSM_AMD_INPUT_ERROR;
+  PointCall c;
+  c.who = g2 ? "msm_amd_g2_check_points" : "msm_amd_check_points";   // the _device calls go by the same name
+  const uint32_t stride = point_record_bytes(g2, layout, kKindHost);
+  if (stride == 0)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": takes the host point layouts only (not *_PREPARED / *_TABLES)");
+  if (checks == 0 || (checks & ~(uint32_t)(MSM_AMD_CHECK_CURVE | MSM_AMD_CHECK_SUBGROUP)))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": checks must be MSM_AMD_CHECK_CURVE and / or MSM_AMD_CHECK_SUBGROUP");
+  c.first_use = "the report buffer of a point check";
+  c.g2 = g2, c.host = host, c.counters = true, c.n = n;
+  c.null_arg = !points;
+  c.in[0] = points, c.in_bytes[0] = n * stride;
+  c.reasons = reasons;
+  if (g2) c.stage_in0 = &ctx->g2.in_points;
+  return point_call(
+      ctx, c,
+      [&](hipStream_t st, const PointIo& io) {
+        if (g2)
+          launch_check_g2(st, io.in[0], layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n, checks, io.reasons, io.counters);
+        else
+          launch_check_g1(st, io.in[0], layout, stride, (uint32_t)n, io.reasons, io.counters);
+      },
+      [&](const PointCounters& pc, float ms) { point_report_decode(pc, n, ms, report); });
+}
+
+// ---- compressed points (msm_amd_decompress_points*, msm_amd_compress_points* and their G2 forms) ----------------------
+// layout: the output layout of a decompression, the input layout of a compression
+int compress_call(msm_amd_ctx* ctx, bool g2, bool host, bool decompress, int format, int layout, const void* in, size_t n,
+                  void* out, uint8_t* reasons, msm_amd_decompress_report* report, uint64_t* n_bad) {
+  if (!ctx || (decompress && !report)) return MSM_AMD_INPUT_ERROR;
+  PointCall c;
+  c.who = std::string(g2 ? "msm_amd_g2_" : "msm_amd_") + (decompress ? "decompress_points" : "compress_points") +
+          (host ? "" : "_device");
+  const bool prepared_ok = decompress && !host;
+  const uint32_t stride = point_record_bytes(g2, layout, prepared_ok ? kKindAffine | kKindPrepared : kKindAffine);
+  if (!compress_format_known(format))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": unknown format (MSM_AMD_COMPRESSED_ARK / _PARITY)");
+  if (stride == 0)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + (prepared_ok ? ": takes the two affine layouts and *_PREPARED (not *_TABLES)"
+                                                               : ": takes the two affine host layouts only"));
+  const size_t wire = g2 ? 64 : 32;
+  c.first_use = "the report buffer of a decompress / compress call";
+  c.g2 = g2, c.host = host, c.counters = true, c.n = n;
+  c.null_arg = !in || !out;
+  c.in[0] = in, c.in_bytes[0] = n * (decompress ? wire : stride);
+  c.out = out, c.out_bytes = n * (decompress ? stride : wire);
+  c.reasons = reasons;
+  return point_call(
+      ctx, c,
+      [&](hipStream_t st, const PointIo& io) {
+        if (decompress)
+          launch_decompress(st, g2, format, io.in[0], (uint32_t)n, layout, stride, io.out, io.reasons, io.counters);
+        else
+          launch_compress(st, g2, layout, stride, io.in[0], (uint32_t)n, format, io.out, io.counters);
+      },
+      [&](const PointCounters& pc, float ms) {
+        if (decompress) point_report_decode(pc, n, ms, report);
+        else if (n_bad) *n_bad = pc.by_reason[kPointNotReduced];
+      });
+}
+
+// ---- batch scalar multiplication (msm_amd_mul_points*, msm_amd_g2_mul_points*) ------------------------------------------
+// The outputs run in chunks of ctx->mul_chunk records (a multiple of the normalisation group, so the groups of a
+// chunked call are those of an unchunked one), all enqueued on the main stream: stream order hands the XYZZ buffer from
+// one chunk to the next.  No counters and no event wait: the bounded stream wait at the end of point_call is the call's.
+int mul_call(msm_amd_ctx* ctx, bool g2, bool host, int scalar_layout, int layout_in, int base_mode, const void* scalars,
+             const void* points, size_t n, int layout_out, void* out) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  PointCall c;
+  c.who = std::string(g2 ? "msm_amd_g2_mul_points" : "msm_amd_mul_points") + (host ? "" : "_device");
+  const uint32_t prepared = host ? 0u : (uint32_t)kKindPrepared;
+  const size_t in_stride = point_record_bytes(g2, layout_in, kKindHost | prepared),
+               out_stride = point_record_bytes(g2, layout_out, kKindAffine | prepared);
+  if (!mul_scalar_layout_known(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": unknown scalar layout");
+  if (in_stride == 0)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + (host ? ": points in a host layout only (not *_PREPARED / *_TABLES)"
+                                                        : ": points in a host layout or *_PREPARED (not *_TABLES)"));
+  if (out_stride == 0)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + (host ? ": output in one of the two affine host layouts only"
+                                                        : ": output in one of the two affine layouts or *_PREPARED"));
+  if (base_mode != MSM_AMD_MUL_BASE_EACH && base_mode != MSM_AMD_MUL_BASE_ONE)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": base_mode must be MSM_AMD_MUL_BASE_EACH or MSM_AMD_MUL_BASE_ONE");
+  const bool one = base_mode == MSM_AMD_MUL_BASE_ONE;
+  const size_t chunk = std::min(n, ctx->mul_chunk);
+  c.g2 = g2, c.host = host, c.n = n;
+  c.null_arg = !scalars || !points || !out;
+  c.in[0] = scalars, c.in_bytes[0] = n * 32;
+  c.in[1] = points, c.in_bytes[1] = (one ? 1 : n) * in_stride;
+  c.out = out, c.out_bytes = n * out_stride;
+  c.table_bytes = one ? mul_table_bytes(g2) : 0, c.xyzz_bytes = chunk * mul_xyzz_bytes(g2);
+  return point_call(
+      ctx, c,
+      [&](hipStream_t st, const PointIo& io) {
+        if (one) launch_mul_table(st, g2, layout_in, io.in[1], io.table);
+        for (size_t first = 0; first < n; first += chunk) {
+          const uint32_t m = (uint32_t)std::min(chunk, n - first);
+          const uint8_t* sc = (const uint8_t*)io.in[0] + first * 32;
+          if (one)
+            launch_mul_fixed(st, g2, scalar_layout, sc, m, io.table, io.xyzz);
+          else
+            launch_mul_each(st, g2, scalar_layout, sc, layout_in, (const uint8_t*)io.in[1] + first * in_stride, m, io.xyzz);
+          launch_mul_normalise(st, g2, io.xyzz, m, layout_out, (uint8_t*)io.out + first * out_stride);
+        }
+      },
+      [](const PointCounters&, float) {});
 }
 
 }  // namespace
@@ -3742,289 +3819,64 @@ extern "C" {
 
 int msm_amd_check_points(msm_amd_ctx* ctx, int point_layout, const void* points, size_t n, uint32_t checks,
                          uint8_t* reasons, msm_amd_check_report* report) {
-  return check_host_buffers(ctx, false, point_layout, points, n, checks, reasons, report);
+  return check_call(ctx, false, true, point_layout, points, n, checks, reasons, report);
 }
 
 int msm_amd_check_points_device(msm_amd_ctx* ctx, int point_layout, const void* d_points, size_t n, uint32_t checks,
                                 uint8_t* d_reasons, msm_amd_check_report* report) {
-  return check_device(ctx, false, point_layout, d_points, n, checks, d_reasons, report);
+  return check_call(ctx, false, false, point_layout, d_points, n, checks, d_reasons, report);
 }
 
 int msm_amd_g2_check_points(msm_amd_ctx* ctx, int g2_point_layout, const void* points, size_t n, uint32_t checks,
                             uint8_t* reasons, msm_amd_check_report* report) {
-  return check_host_buffers(ctx, true, g2_point_layout, points, n, checks, reasons, report);
+  return check_call(ctx, true, true, g2_point_layout, points, n, checks, reasons, report);
 }
 
 int msm_amd_g2_check_points_device(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n,
                                    uint32_t checks, uint8_t* d_reasons, msm_amd_check_report* report) {
-  return check_device(ctx, true, g2_point_layout, d_points, n, checks, d_reasons, report);
+  return check_call(ctx, true, false, g2_point_layout, d_points, n, checks, d_reasons, report);
 }
-
-}  // extern "C"
-
-// ---- compressed points (msm_amd_decompress_points*, msm_amd_compress_points* and their G2 forms) -----------------------
-// The discipline of the check driver above: ctx lock, bounded drain of the ctx's earlier work, counters and staging
-// sized on the idle ctx only, host input through the page-locked staging ring, a bounded poll for the counters.
-namespace {
-
-std::string compress_name(bool g2, bool decompress) {
-  return std::string(g2 ? "msm_amd_g2_" : "msm_amd_") + (decompress ? "decompress_points" : "compress_points");
-}
-
-// layout: the output layout of a decompression, the input layout of a compression
-int compress_args(msm_amd_ctx* ctx, const std::string& who, bool g2, bool prepared_ok, int format, int layout,
-                  const void* in, const void* out, size_t n) {
-  if (!compress_format_known(format))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": unknown format (MSM_AMD_COMPRESSED_ARK / _PARITY)");
-  if (compress_stride(g2, layout, prepared_ok) == 0)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, who + (prepared_ok ? ": takes the two affine layouts and *_PREPARED (not *_TABLES)"
-                                                             : ": takes the two affine host layouts only"));
-  if (n > 0xFFFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": n >= 2^32");
-  if (n > 0 && (!in || !out)) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": null pointer with n > 0");
-  return MSM_AMD_OK;
-}
-
-// Every ctx call starts here (ctx->mu held): the ctx's earlier work is waited for, with the wait bound.
-int compress_begin(msm_amd_ctx* ctx, const std::string& who) {
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (int rc = recover_if_stalled(ctx)) return fail(ctx, rc, who + ": " + ctx->last_error);
-  if (!drain_or_mark_stalled(ctx))
-    return fail(ctx, MSM_AMD_PIPELINE_ERROR, who + ": device busy past the wait bound of " +
-                                                 std::to_string(ctx->wait_timeout_ms) + " ms (msm_amd_synchronize waits again)");
-  return MSM_AMD_OK;
-}
-
-// One pass over n device-resident records on the main stream and the bounded wait for its counters (*cs.h_counters).
-// The ctx is idle (compress_begin), so the first call may allocate the counters and their page-locked copy.
-int run_compress(msm_amd_ctx* ctx, CompressState& cs, const std::string& who, bool g2, bool decompress, int format,
-                 int layout, const void* d_in, size_t n, void* d_out, uint8_t* d_reasons, float* device_ms) {
-  hipStream_t st = ctx->stream;
-  if (!cs.ready) {
-    if (int rc = quiesce_for_allocation(ctx, "the report buffer of a decompress / compress call")) return rc;
-    if (int rc = ensure(ctx, cs.counters, sizeof(CompressCounters))) return rc;
-    if (!cs.h_counters) HIP_TRY(ctx, hipHostMalloc((void**)&cs.h_counters, sizeof(CompressCounters), hipHostMallocDefault));
-    for (hipEvent_t& e : cs.ev)
-      if (!e) HIP_TRY(ctx, hipEventCreate(&e));
-    cs.ready = true;
-  }
-  CompressCounters* d_counters = (CompressCounters*)cs.counters.p;
-  const uint32_t stride = (uint32_t)compress_stride(g2, layout, true);
-  launch_compress_reset(st, d_counters);
-  HIP_TRY(ctx, hipEventRecord(cs.ev[CompressState::EV_COMP_START], st));
-  if (decompress)
-    launch_decompress(st, g2, format, d_in, (uint32_t)n, layout, stride, d_out, d_reasons, d_counters);
-  else
-    launch_compress(st, g2, layout, stride, d_in, (uint32_t)n, format, d_out, d_counters);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipEventRecord(cs.ev[CompressState::EV_COMP_KERNEL], st));
-  HIP_TRY(ctx, hipMemcpyAsync(cs.h_counters, d_counters, sizeof(CompressCounters), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipEventRecord(cs.ev[CompressState::EV_COMP_DONE], st));
-  const hipError_t we = wait_event(cs.ev[CompressState::EV_COMP_DONE], ctx->wait_timeout_ms);
-  if (we == hipErrorNotReady) {
-    ctx->stalled = true;
-    return fail(ctx, MSM_AMD_PIPELINE_ERROR, "timed out after " + std::to_string(ctx->wait_timeout_ms) + " ms waiting for " + who);
-  }
-  if (we != hipSuccess) return fail(ctx, MSM_AMD_PIPELINE_ERROR, who + ": " + hipGetErrorString(we));
-  *device_ms = event_span(cs.ev[CompressState::EV_COMP_START], cs.ev[CompressState::EV_COMP_KERNEL]);
-  return MSM_AMD_OK;
-}
-
-void empty_decompress_report(msm_amd_decompress_report* report) {
-  CompressCounters none{};
-  none.first_key = ~0ull;
-  decompress_report_from_counters(none, 0, 0.0f, report);
-}
-
-// host == false: in / out / reasons are device memory.  host == true: the input goes up in chunks through the
-// page-locked staging ring into the group's staging buffer (grown only on an idle ctx, like every workspace), output
-// and reason bytes come back after the counters.
-int decompress_call(msm_amd_ctx* ctx, bool g2, bool host, int format, const void* in, size_t n, int layout, void* out,
-                    uint8_t* reasons, msm_amd_decompress_report* report) {
-  if (!ctx || !report) return MSM_AMD_INPUT_ERROR;
-  const std::string who = compress_name(g2, true) + (host ? "" : "_device");
-  if (int rc = compress_args(ctx, who, g2, !host, format, layout, in, out, n)) return rc;
-  if (n == 0) {
-    empty_decompress_report(report);
-    return MSM_AMD_OK;
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (int rc = compress_begin(ctx, who)) return rc;
-  CompressState& cs = g2 ? ctx->g2.compress : ctx->compress;
-  const size_t in_bytes = n * (g2 ? 64 : 32), out_bytes = n * compress_stride(g2, layout, true);
-  const void* d_in = in;
-  void* d_out = out;
-  uint8_t* d_reasons = reasons;
-  int rc;
-  if (host) {
-    if ((rc = ensure(ctx, cs.in, in_bytes))) return rc;
-    if ((rc = ensure(ctx, cs.out, out_bytes))) return rc;
-    if (reasons && (rc = ensure(ctx, cs.reasons, n))) return rc;
-    if ((rc = staged_upload(ctx, cs.in.p, in, in_bytes, ctx->stream))) return rc;
-    d_in = cs.in.p;
-    d_out = cs.out.p;
-    d_reasons = reasons ? (uint8_t*)cs.reasons.p : nullptr;
-  }
-  float ms = 0.0f;
-  if ((rc = run_compress(ctx, cs, who, g2, true, format, layout, d_in, n, d_out, d_reasons, &ms))) return rc;
-  decompress_report_from_counters(*cs.h_counters, n, ms, report);
-  if (host) {
-    HIP_TRY(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (reasons) HIP_TRY(ctx, hipMemcpyAsync(reasons, d_reasons, n, hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = sync_stream_bounded(ctx, ctx->stream, who.c_str()))) return rc;
-  }
-  return MSM_AMD_OK;
-}
-
-int compress_call(msm_amd_ctx* ctx, bool g2, bool host, int layout, const void* in, size_t n, int format, void* out,
-                  uint64_t* n_bad) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  const std::string who = compress_name(g2, false) + (host ? "" : "_device");
-  if (int rc = compress_args(ctx, who, g2, false, format, layout, in, out, n)) return rc;
-  if (n == 0) {
-    if (n_bad) *n_bad = 0;
-    return MSM_AMD_OK;
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (int rc = compress_begin(ctx, who)) return rc;
-  CompressState& cs = g2 ? ctx->g2.compress : ctx->compress;
-  const size_t in_bytes = n * compress_stride(g2, layout, false), out_bytes = n * (g2 ? 64 : 32);
-  const void* d_in = in;
-  void* d_out = out;
-  int rc;
-  if (host) {
-    if ((rc = ensure(ctx, cs.in, in_bytes))) return rc;
-    if ((rc = ensure(ctx, cs.out, out_bytes))) return rc;
-    if ((rc = staged_upload(ctx, cs.in.p, in, in_bytes, ctx->stream))) return rc;
-    d_in = cs.in.p;
-    d_out = cs.out.p;
-  }
-  float ms = 0.0f;
-  if ((rc = run_compress(ctx, cs, who, g2, false, format, layout, d_in, n, d_out, nullptr, &ms))) return rc;
-  if (n_bad) *n_bad = cs.h_counters->by_reason[kPointNotReduced];
-  if (host) {
-    HIP_TRY(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if ((rc = sync_stream_bounded(ctx, ctx->stream, who.c_str()))) return rc;
-  }
-  return MSM_AMD_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int msm_amd_decompress_points(msm_amd_ctx* ctx, int format, const void* in, size_t n, int point_layout_out, void* out,
                               uint8_t* reasons, msm_amd_decompress_report* report) {
-  return decompress_call(ctx, false, true, format, in, n, point_layout_out, out, reasons, report);
+  return compress_call(ctx, false, true, true, format, point_layout_out, in, n, out, reasons, report, nullptr);
 }
 
 int msm_amd_decompress_points_device(msm_amd_ctx* ctx, int format, const void* d_in, size_t n, int point_layout_out,
                                      void* d_out, uint8_t* d_reasons, msm_amd_decompress_report* report) {
-  return decompress_call(ctx, false, false, format, d_in, n, point_layout_out, d_out, d_reasons, report);
+  return compress_call(ctx, false, false, true, format, point_layout_out, d_in, n, d_out, d_reasons, report, nullptr);
 }
 
 int msm_amd_g2_decompress_points(msm_amd_ctx* ctx, int format, const void* in, size_t n, int g2_point_layout_out,
                                  void* out, uint8_t* reasons, msm_amd_decompress_report* report) {
-  return decompress_call(ctx, true, true, format, in, n, g2_point_layout_out, out, reasons, report);
+  return compress_call(ctx, true, true, true, format, g2_point_layout_out, in, n, out, reasons, report, nullptr);
 }
 
 int msm_amd_g2_decompress_points_device(msm_amd_ctx* ctx, int format, const void* d_in, size_t n,
                                         int g2_point_layout_out, void* d_out, uint8_t* d_reasons,
                                         msm_amd_decompress_report* report) {
-  return decompress_call(ctx, true, false, format, d_in, n, g2_point_layout_out, d_out, d_reasons, report);
+  return compress_call(ctx, true, false, true, format, g2_point_layout_out, d_in, n, d_out, d_reasons, report, nullptr);
 }
 
 int msm_amd_compress_points(msm_amd_ctx* ctx, int point_layout_in, const void* in, size_t n, int format, void* out,
                             uint64_t* n_bad) {
-  return compress_call(ctx, false, true, point_layout_in, in, n, format, out, n_bad);
+  return compress_call(ctx, false, true, false, format, point_layout_in, in, n, out, nullptr, nullptr, n_bad);
 }
 
 int msm_amd_compress_points_device(msm_amd_ctx* ctx, int point_layout_in, const void* d_in, size_t n, int format,
                                    void* d_out, uint64_t* n_bad) {
-  return compress_call(ctx, false, false, point_layout_in, d_in, n, format, d_out, n_bad);
+  return compress_call(ctx, false, false, false, format, point_layout_in, d_in, n, d_out, nullptr, nullptr, n_bad);
 }
 
 int msm_amd_g2_compress_points(msm_amd_ctx* ctx, int g2_point_layout_in, const void* in, size_t n, int format, void* out,
                                uint64_t* n_bad) {
-  return compress_call(ctx, true, true, g2_point_layout_in, in, n, format, out, n_bad);
+  return compress_call(ctx, true, true, false, format, g2_point_layout_in, in, n, out, nullptr, nullptr, n_bad);
 }
 
 int msm_amd_g2_compress_points_device(msm_amd_ctx* ctx, int g2_point_layout_in, const void* d_in, size_t n, int format,
                                       void* d_out, uint64_t* n_bad) {
-  return compress_call(ctx, true, false, g2_point_layout_in, d_in, n, format, d_out, n_bad);
+  return compress_call(ctx, true, false, false, format, g2_point_layout_in, d_in, n, d_out, nullptr, nullptr, n_bad);
 }
-
-}  // extern "C"
-
-// ---- batch scalar multiplication (msm_amd_mul_points*, msm_amd_g2_mul_points*) ------------------------------------------
-// The discipline of the check and compress drivers above: ctx lock, bounded drain of the ctx's earlier work, every
-// buffer sized on the idle ctx before anything is enqueued, host input through the page-locked staging ring, the output
-// behind a bounded stream wait.  The outputs run in chunks of ctx->mul_chunk records (a multiple of the normalisation
-// group, so the groups of a chunked call are those of an unchunked one), all enqueued on the main stream: stream order
-// hands the XYZZ buffer from one chunk to the next.
-namespace {
-
-std::string mul_name(bool g2, bool host) {
-  return std::string(g2 ? "msm_amd_g2_mul_points" : "msm_amd_mul_points") + (host ? "" : "_device");
-}
-
-int mul_call(msm_amd_ctx* ctx, bool g2, bool host, int scalar_layout, int layout_in, int base_mode, const void* scalars,
-             const void* points, size_t n, int layout_out, void* out) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  const std::string who = mul_name(g2, host);
-  const size_t in_stride = mul_in_stride(g2, layout_in, !host), out_stride = mul_out_stride(g2, layout_out, !host);
-  if (!mul_scalar_layout_known(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": unknown scalar layout");
-  if (in_stride == 0)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, who + (host ? ": points in a host layout only (not *_PREPARED / *_TABLES)"
-                                                      : ": points in a host layout or *_PREPARED (not *_TABLES)"));
-  if (out_stride == 0)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, who + (host ? ": output in one of the two affine host layouts only"
-                                                      : ": output in one of the two affine layouts or *_PREPARED"));
-  if (base_mode != MSM_AMD_MUL_BASE_EACH && base_mode != MSM_AMD_MUL_BASE_ONE)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": base_mode must be MSM_AMD_MUL_BASE_EACH or MSM_AMD_MUL_BASE_ONE");
-  if (n > 0xFFFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": n >= 2^32");
-  if (n == 0) return MSM_AMD_OK;
-  if (!scalars || !points || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": null pointer with n > 0");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (int rc = compress_begin(ctx, who)) return rc;   // device, stall recovery, the bounded drain
-  MulState& ms = g2 ? ctx->g2.mul : ctx->mul;
-  const bool one = base_mode == MSM_AMD_MUL_BASE_ONE;
-  const size_t n_points = one ? 1 : n, chunk = std::min(n, ctx->mul_chunk);
-  int rc;
-  // the ctx is idle: every buffer of the call is sized now (ensure quiesces before it allocates)
-  if (one && (rc = ensure(ctx, ms.table, mul_table_bytes(g2)))) return rc;
-  if ((rc = ensure(ctx, ms.xyzz, chunk * mul_xyzz_bytes(g2)))) return rc;
-  const void* d_scalars = scalars;
-  const void* d_points = points;
-  void* d_out = out;
-  hipStream_t st = ctx->stream;
-  if (host) {
-    if ((rc = ensure(ctx, ms.in_scalars, n * 32))) return rc;
-    if ((rc = ensure(ctx, ms.in_points, n_points * in_stride))) return rc;
-    if ((rc = ensure(ctx, ms.out, n * out_stride))) return rc;
-    if ((rc = staged_upload(ctx, ms.in_scalars.p, scalars, n * 32, st))) return rc;
-    if ((rc = staged_upload(ctx, ms.in_points.p, points, n_points * in_stride, st))) return rc;
-    d_scalars = ms.in_scalars.p;
-    d_points = ms.in_points.p;
-    d_out = ms.out.p;
-  }
-  if (one) launch_mul_table(st, g2, layout_in, d_points, ms.table.p);
-  for (size_t first = 0; first < n; first += chunk) {
-    const uint32_t m = (uint32_t)std::min(chunk, n - first);
-    const uint8_t* sc = (const uint8_t*)d_scalars + first * 32;
-    if (one)
-      launch_mul_fixed(st, g2, scalar_layout, sc, m, ms.table.p, ms.xyzz.p);
-    else
-      launch_mul_each(st, g2, scalar_layout, sc, layout_in, (const uint8_t*)d_points + first * in_stride, m, ms.xyzz.p);
-    launch_mul_normalise(st, g2, ms.xyzz.p, m, layout_out, (uint8_t*)d_out + first * out_stride);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  if (host) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, n * out_stride, hipMemcpyDeviceToHost, st));
-  return sync_stream_bounded(ctx, st, who.c_str());
-}
-
-}  // namespace
-
-extern "C" {
 
 int msm_amd_mul_points(msm_amd_ctx* ctx, int scalar_layout, int point_layout_in, int base_mode, const void* scalars,
                        const void* points, size_t n, int point_layout_out, void* out) {

@@ -103,15 +103,6 @@ struct MulG1 {
   using F = fe29;
   static constexpr bool kG2 = false;
 
-  // record size of an input layout (the four host layouts and MSM_AMD_POINT_PREPARED), 0 otherwise
-  MSM_HD static uint32_t in_stride(int layout) {
-    return layout == kLayoutH2cAffine ? 64u : layout == kLayoutArkAffine ? 72u
-         : (layout == kLayoutArkProjective || layout == kLayoutJacBe32) ? 96u : layout == kLayoutPrepared ? 64u : 0u;
-  }
-  // record size of an output layout (the two affine host layouts and MSM_AMD_POINT_PREPARED), 0 otherwise
-  MSM_HD static uint32_t out_stride(int layout) {
-    return layout == kLayoutH2cAffine ? 64u : layout == kLayoutArkAffine ? 72u : layout == kLayoutPrepared ? 64u : 0u;
-  }
   MSM_HD static Aff aff_identity() { return AffI{Fq29::zero(), Fq29::zero()}; }
   MSM_HD static bool aff_is_identity(const Aff& a) { return affi_is_identity(a); }
   // One base record in the caller's layout -> canonical internal affine form; every identity encoding -> zero limbs.
@@ -210,10 +201,6 @@ struct MulG2 {
   using F = fq2;
   static constexpr bool kG2 = true;
 
-  MSM_HD static uint32_t in_stride(int layout) {
-    return layout == kG2LayoutH2cAffine ? 128u : layout == kG2LayoutArkAffine ? 136u : layout == kG2LayoutPrepared ? 128u : 0u;
-  }
-  MSM_HD static uint32_t out_stride(int layout) { return in_stride(layout); }
   MSM_HD static Aff aff_identity() { return Aff2I{Fq2::zero(), Fq2::zero()}; }
   MSM_HD static bool aff_is_identity(const Aff& a) { return aff2i_is_identity(a); }
   MSM_HD static Aff load_base(int layout, const uint8_t* rec) {

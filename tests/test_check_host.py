@@ -183,15 +183,7 @@ def test_endomorphism_identity_in_the_model():
 
 # ---- 5. registers ------------------------------------------------------------------------------------------------------
 def test_check_kernels_use_no_scratch():
-    notes = th._device_notes(os.path.join(CSRC, "k_check.o"))
-    kernels = {}
-    name = None
-    for line in notes.splitlines():
-        s = line.strip().lstrip("- ")
-        if s.startswith(".name:"):
-            name = s.split(":", 1)[1].strip()
-        elif s.startswith(".private_segment_fixed_size:") and name:
-            kernels[name] = int(s.split(":", 1)[1])
+    kernels = th.kernel_scratch(os.path.join(CSRC, "k_check.o"))
     check = {k: v for k, v in kernels.items() if "check_" in k}
     assert any("check_g1_kernel" in k for k in check) and any("check_g2_kernel" in k for k in check), kernels
     assert len(kernels) >= 3 and all(v == 0 for v in kernels.values()), kernels

@@ -223,14 +223,7 @@ def test_root_ops_keep_their_neighbours_refused(msm_pkg):
 
 def test_compress_kernels_use_no_scratch():
     """the code object of k_compress.hip, read the way test_g2_host reads k_g2's"""
-    notes = th._device_notes(os.path.join(th.CSRC, "k_compress.o"))
-    kernels, name = {}, None
-    for line in notes.splitlines():
-        s = line.strip().lstrip("- ")
-        if s.startswith(".name:"):
-            name = s.split(":", 1)[1].strip()
-        elif s.startswith(".private_segment_fixed_size:") and name:
-            kernels[name] = int(s.split(":", 1)[1])
+    kernels = th.kernel_scratch(os.path.join(th.CSRC, "k_compress.o"))
     ours = {k: v for k, v in kernels.items() if "compress_g1_kernel" in k or "compress_g2_kernel" in k}
     assert len(ours) == 4, kernels
     assert all(v == 0 for v in ours.values()), ours

@@ -266,16 +266,20 @@ def _device_notes(obj):
         shutil.rmtree(d)
 
 
-def test_g2_kernels_use_no_scratch():
-    notes = _device_notes(os.path.join(CSRC, "k_g2.o"))
-    kernels = {}
-    name = None
-    for line in notes.splitlines():
+def kernel_scratch(obj):
+    """private segment (scratch) bytes per kernel of the gfx950 code object inside a hipcc object file"""
+    kernels, name = {}, None
+    for line in _device_notes(obj).splitlines():
         s = line.strip().lstrip("- ")
         if s.startswith(".name:"):
             name = s.split(":", 1)[1].strip()
         elif s.startswith(".private_segment_fixed_size:") and name:
             kernels[name] = int(s.split(":", 1)[1])
+    return kernels
+
+
+def test_g2_kernels_use_no_scratch():
+    kernels = kernel_scratch(os.path.join(CSRC, "k_g2.o"))
     g2 = {k: v for k, v in kernels.items() if "_g2_kernel" in k}
     assert len(g2) >= 7, kernels
     assert all(v == 0 for v in g2.values()), g2

@@ -209,15 +209,7 @@ def test_argument_errors(msm_pkg):
 
 def mul_kernels_scratch():
     """private segment size per kernel of k_mul.hip's code object, read the way test_g2_host reads k_g2's"""
-    notes = th._device_notes(os.path.join(th.CSRC, "k_mul.o"))
-    kernels, name = {}, None
-    for line in notes.splitlines():
-        s = line.strip().lstrip("- ")
-        if s.startswith(".name:"):
-            name = s.split(":", 1)[1].strip()
-        elif s.startswith(".private_segment_fixed_size:") and name:
-            kernels[name] = int(s.split(":", 1)[1])
-    return kernels
+    return th.kernel_scratch(os.path.join(th.CSRC, "k_mul.o"))
 
 
 def test_mul_kernels_use_no_scratch():
