@@ -829,6 +829,28 @@ int msm_amd_host_g2_mul_points(int scalar_layout, int g2_point_layout_in, int ba
  * (Development knob MSM_AMD_MUL_CHUNK at msm_amd_init: outputs per chunk of the ctx calls, rounded up to a multiple
  * of K; default 2^18.) */
 int msm_amd_test_mul_plan(int group /* 1 or 2 */, uint32_t out[4]);
+/* Test aid: one stage of msm_amd_mul_points on input the caller wrote, on the GPU (host buffers, staged like the host-buffer
+ * calls) and on the CPU (the same bodies compiled for the host).  group: 1 or 2.
+ *   MSM_AMD_MUL_STAGE_FIXED      the signed-digit walk of BASE_ONE over the caller's table.  in: n scalars of 32 bytes,
+ *     layout: their MSM_AMD_SCALAR_* layout; table: entries [2] of msm_amd_test_mul_plan, entry w 2^(c-1) + d - 1 standing
+ *     for [d 2^(c w)] P, each the canonical x, y of the internal Montgomery domain (radix 2^261; G2: x.c0, x.c1, y.c0,
+ *     y.c1), 32 little-endian bytes per coordinate; an entry whose first coordinate is 2^256 - 1 is the identity.
+ *     out: n raw XYZZ records as the walk leaves them, 36 (G1) / 72 (G2) words of 29-bit limbs: X, Y, ZZ, ZZZ, G2 c0
+ *     before c1; ZZ limbs all zero = identity.
+ *   MSM_AMD_MUL_STAGE_NORMALISE  the shared inversion.  in: n such XYZZ records inside the point invariant (X < 10 p,
+ *     Y < 6 p, ZZ < 2.8 p, ZZZ < 2 p; G2: 1.21, 13.4, 3.2, 2.04 per component; limbs 0..7 <= 2^29 + 7), layout: an affine
+ *     host point layout of the group; table is not read.  out: n affine records of that layout, consecutive groups of
+ *     [3] of msm_amd_test_mul_plan sharing one inversion.  The stage runs on a copy: `in` is not written.
+ *   MSM_AMD_MUL_STAGE_NORMALISE_RECORDS  the same stage on the same input; out: that copy as the stage leaves it, n XYZZ
+ *     records holding the intermediates of the shared inversion in the places of X, Y, ZZ, ZZZ: X ZZZ, ZZ Y,
+ *     a_i = ZZ ZZZ and the prefix product before record i (an identity record: exact zero limbs, zero limbs, one, the
+ *     prefix).  For the bound checks of the chain; the affine bytes are dropped.
+ * MSM_AMD_INPUT_ERROR for an unknown group, stage or layout and for n >= 2^32; n == 0 touches nothing; a null pointer
+ * with n > 0 is refused. */
+enum { MSM_AMD_MUL_STAGE_FIXED = 0, MSM_AMD_MUL_STAGE_NORMALISE = 1, MSM_AMD_MUL_STAGE_NORMALISE_RECORDS = 2 };
+int msm_amd_test_mul_stage(msm_amd_ctx* ctx, int group, int which, int layout, const void* in, const void* table,
+                           size_t n, void* out);
+int msm_amd_test_mul_stage_host(int group, int which, int layout, const void* in, const void* table, size_t n, void* out);
 
 /* ---- introspection --------------------------------------------------------------------------- */
 int msm_amd_last_timings(const msm_amd_ctx* ctx, msm_amd_timings* out);

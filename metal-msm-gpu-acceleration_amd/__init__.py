@@ -97,6 +97,7 @@ EXPORTS = [
     "msm_amd_host_g2_compress_points",
     "msm_amd_mul_points", "msm_amd_mul_points_device", "msm_amd_g2_mul_points", "msm_amd_g2_mul_points_device",
     "msm_amd_host_mul_points", "msm_amd_host_g2_mul_points", "msm_amd_test_mul_plan",
+    "msm_amd_test_mul_stage", "msm_amd_test_mul_stage_host",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -317,6 +318,8 @@ def _lib():
         for name in ("msm_amd_host_mul_points", "msm_amd_host_g2_mul_points"):
             getattr(L, name).argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]
         L.msm_amd_test_mul_plan.argtypes = [c_int, POINTER(c_uint32)]
+        L.msm_amd_test_mul_stage.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+        L.msm_amd_test_mul_stage_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
         L.msm_amd_generate_instance_host.argtypes = [c_uint64, c_size_t, c_int, c_void_p, c_void_p, c_int]
         L.msm_amd_test_op_ifma.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_tuned_split.argtypes = [c_size_t]
@@ -769,6 +772,14 @@ class MsmConfig:
         self._check(fn(self.h, scalar_layout, point_layout, base_mode, c_void_p(d_scalars), c_void_p(d_points), n,
                        point_layout_out, c_void_p(d_out)))
 
+    def test_mul_stage(self, group, which, layout, data: bytes, table, n: int) -> bytes:
+        """One stage of mul_points on the GPU (msm_amd_test_mul_stage): MUL_STAGE_FIXED walks the caller's table over n
+        scalars and returns the raw XYZZ records, MUL_STAGE_NORMALISE turns n XYZZ records into affine ones,
+        MUL_STAGE_NORMALISE_RECORDS returns the records as that stage leaves them."""
+        out = ctypes.create_string_buffer(max(1, n * mul_stage_out_bytes(group, which, layout)))
+        self._check(_lib().msm_amd_test_mul_stage(self.h, group, which, layout, data, table, n, out))
+        return out.raw[:n * mul_stage_out_bytes(group, which, layout)]
+
     def test_op_g2(self, op, a, b, count):
         """Raw-limb G2 op (MSM_AMD_G2_RAW_*) on the device: a, b flat u32 lists of count * G2_RAW_IN_WORDS; returns
         count * G2_RAW_OUT_WORDS u32."""
@@ -1037,6 +1048,25 @@ def mul_plan(group=1) -> dict:
     if st != OK:
         raise MsmError(st)
     return {"c": out[0], "W": out[1], "entries": out[2], "K": out[3]}
+
+
+MUL_STAGE_FIXED, MUL_STAGE_NORMALISE, MUL_STAGE_NORMALISE_RECORDS = 0, 1, 2       # MSM_AMD_MUL_STAGE_*
+MUL_XYZZ_WORDS = {1: 36, 2: 72}                   # u32 per raw XYZZ record of the stage entries
+
+
+def mul_stage_out_bytes(group, which, layout) -> int:
+    """bytes per output record of a stage entry: a raw XYZZ record, or an affine record of the layout"""
+    return decompressed_bytes(layout, group == 2) if which == MUL_STAGE_NORMALISE else 4 * MUL_XYZZ_WORDS.get(group, 0)
+
+
+def test_mul_stage_host(group, which, layout, data: bytes, table, n: int) -> bytes:
+    """MsmConfig.test_mul_stage on the host CPU (msm_amd_test_mul_stage_host: the same bodies, no GPU)."""
+    size = mul_stage_out_bytes(group, which, layout)
+    out = ctypes.create_string_buffer(max(1, n * size))
+    st = _lib().msm_amd_test_mul_stage_host(group, which, layout, data, table, n, out)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:n * size]
 
 
 def _g2_raw_in(seq, count):

@@ -3903,3 +3903,102 @@ int msm_amd_g2_mul_points_device(msm_amd_ctx* ctx, int scalar_layout, int g2_poi
 }
 
 }  // extern "C"
+
+// ---- stage entries of the batch scalar multiplication (test aid: msm_amd_test_mul_stage, msm_amd_test_mul_stage_host) ----
+// The digit walk and the shared normalisation of mul_points.hip.h on inputs the public calls never produce: a table the
+// caller wrote (identity entries, an entry equal to a partial sum or to its negative) and XYZZ records at the edge of
+// the point invariant.  The device form goes through point_call and the launch wrappers of launch_mul.h like
+// msm_amd_mul_points; the host form runs the bodies host_mul.hip runs.  NORMALISE works on a copy of the records,
+// because mul_normalise overwrites them; NORMALISE_RECORDS returns that copy instead of the affine bytes.
+namespace {
+
+struct MulStage {
+  bool g2 = false, fixed = false, records = false;
+  size_t in_stride = 0, out_stride = 0;   // bytes per record of `in` and of `out`
+  size_t affine_stride = 0;               // the two normalisation stages: bytes per affine record
+};
+
+// false: an unknown group, stage or layout
+bool mul_stage_shape(int group, int which, int layout, MulStage* s) {
+  if ((group != 1 && group != 2) || which < MSM_AMD_MUL_STAGE_FIXED || which > MSM_AMD_MUL_STAGE_NORMALISE_RECORDS) return false;
+  s->g2 = group == 2;
+  s->fixed = which == MSM_AMD_MUL_STAGE_FIXED;
+  s->records = which == MSM_AMD_MUL_STAGE_NORMALISE_RECORDS;
+  if (s->fixed) {
+    if (!mul_scalar_layout_known(layout)) return false;
+    s->in_stride = 32, s->out_stride = mul_xyzz_bytes(s->g2);
+    return true;
+  }
+  s->affine_stride = point_record_bytes(s->g2, layout, kKindAffine);
+  s->in_stride = mul_xyzz_bytes(s->g2);
+  s->out_stride = s->records ? s->in_stride : s->affine_stride;
+  return s->affine_stride != 0;
+}
+
+template <class G>
+void mul_stage_host(const MulStage& s, int layout, const uint8_t* in, const void* table, size_t n, uint8_t* out) {
+  if (s.fixed) {
+    for (size_t i = 0; i < n; ++i)
+      G::store_pt((typename G::Pt*)(out + i * s.out_stride),
+                  mul_fixed<G>(mul_scalar(layout, in + i * 32), (const typename G::Packed*)table));
+    return;
+  }
+  alignas(16) typename G::Pt recs[kMulNormGroup];
+  std::vector<uint8_t> affine(s.records ? kMulNormGroup * s.affine_stride : 0);
+  for (size_t first = 0; first < n; first += kMulNormGroup) {   // the groups of mul_normalise_kernel
+    const uint32_t m = (uint32_t)std::min<size_t>(kMulNormGroup, n - first);
+    std::memcpy(recs, in + first * s.in_stride, m * s.in_stride);
+    mul_normalise<G>(recs, m, layout, (uint32_t)s.affine_stride, s.records ? affine.data() : out + first * s.affine_stride);
+    if (s.records) std::memcpy(out + first * s.in_stride, recs, m * s.in_stride);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_test_mul_stage(msm_amd_ctx* ctx, int group, int which, int layout, const void* in, const void* table,
+                           size_t n, void* out) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  MulStage s;
+  if (!mul_stage_shape(group, which, layout, &s))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_mul_stage: unknown group, stage or layout");
+  PointCall c;
+  c.who = "msm_amd_test_mul_stage";
+  c.g2 = s.g2, c.host = true, c.n = n;
+  c.null_arg = !in || !out || (s.fixed && !table);
+  c.in[0] = in, c.in_bytes[0] = n * s.in_stride;
+  c.in[1] = table, c.in_bytes[1] = s.fixed ? mul_table_bytes(s.g2) : 0;
+  c.out = out, c.out_bytes = n * s.out_stride;
+  if (s.records) c.xyzz_bytes = n * s.affine_stride;   // where the affine bytes of NORMALISE_RECORDS go
+  hipError_t copied = hipSuccess;
+  const int rc = point_call(
+      ctx, c,
+      [&](hipStream_t st, const PointIo& io) {
+        if (s.fixed) {
+          launch_mul_fixed(st, s.g2, layout, io.in[0], (uint32_t)n, io.in[1], io.out);
+        } else if (s.records) {   // the records move to the output buffer and are normalised there
+          copied = hipMemcpyAsync(io.out, io.in[0], n * s.in_stride, hipMemcpyDeviceToDevice, st);
+          launch_mul_normalise(st, s.g2, io.out, (uint32_t)n, layout, io.xyzz);
+        } else {                  // io.in[0] is the staged copy of the caller's records: the kernel may overwrite it
+          launch_mul_normalise(st, s.g2, const_cast<void*>(io.in[0]), (uint32_t)n, layout, io.out);
+        }
+      },
+      [](const PointCounters&, float) {});
+  if (rc == MSM_AMD_OK && copied != hipSuccess) return fail(ctx, MSM_AMD_PIPELINE_ERROR, std::string("msm_amd_test_mul_stage: ") + hipGetErrorString(copied));
+  return rc;
+}
+
+int msm_amd_test_mul_stage_host(int group, int which, int layout, const void* in, const void* table, size_t n, void* out) {
+  MulStage s;
+  if (!mul_stage_shape(group, which, layout, &s) || n > 0xFFFFFFFFull) return MSM_AMD_INPUT_ERROR;
+  if (n == 0) return MSM_AMD_OK;
+  if (!in || !out || (s.fixed && !table)) return MSM_AMD_INPUT_ERROR;
+  if (s.g2)
+    mul_stage_host<MulG2>(s, layout, (const uint8_t*)in, table, n, (uint8_t*)out);
+  else
+    mul_stage_host<MulG1>(s, layout, (const uint8_t*)in, table, n, (uint8_t*)out);
+  return MSM_AMD_OK;
+}
+
+}  // extern "C"

@@ -41,6 +41,9 @@
 //   a = ZZ ZZZ < 1.29;  pre = pre a < 1.21 at every step;  Fq2::inv(pre) < 1.21;  t = inv pre < 1.24,  inv = inv a < 1.24
 //   X ZZZ < 1.25;  ZZ Y < 1.51 (Y is the SECOND operand: the 32 p lift of Fq2::mul multiplies the first one's c1, and
 //   Y ZZ would reach 3.8);  x < 1.21,  y < 1.27: multiplication outputs below 2 p, what aff2_pack and to_ext canonicalise
+//   These figures are for the points the additions produce (the tool's fixed point, c0 and c1 apart).  A record with
+//   all eight components at the stated maxima at once is coarser: a < 1.65,  ZZ Y < 1.86,  y < 1.30, the rest as above
+//   -- still multiplication outputs below 2 p (tools/g2_bounds.py: MUL_NORM_AT_INV; tests/test_mul_stages_host.py)
 #pragma once
 #include "compress_points.hip.h"
 #include "device_common.hip.h"

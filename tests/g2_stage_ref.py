@@ -11,14 +11,31 @@ exactly when their discrete logs agree mod r.
   replay_items           the state machine of accumulate_g2_kernel on discrete logs, counting STEP_CLASSES
   sort_reference         sorted / bucket_start / bucket_size of a digit matrix on the CPU, any order inside a bucket
   constructed_instance   one-window input that reaches every class of the state machine and both combine kernels
-  decode_records         tapped 192-byte Jacobian records -> affine points (None = identity)"""
+  decode_records         tapped 192-byte Jacobian records -> affine points (None = identity)
+  xyzz_lifted, xyzz_post 72-word XYZZ records at the edge of the point invariant, and the invariant as a checker"""
+import importlib.util
+import os
 import random
+from fractions import Fraction
 
 import numpy as np
 
 import g2_ref as g
 
 R = g.R_ORDER
+
+
+def _load_bounds():
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "g2_bounds.py")
+    spec = importlib.util.spec_from_file_location("g2_bounds", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+BOUNDS = _load_bounds()
+INV = BOUNDS.INV                 # the point invariant of bn254_ec2_29.hip.h, from the tool that proves it
+COORDS = ("X", "Y", "ZZ", "ZZZ")
 
 # ---- s G2 from a byte-window table --------------------------------------------------------------------------------
 _ROWS = []     # _ROWS[j][b] = b 256^j G2, b = 0 .. 255 (None for b = 0); rows are built when first needed
@@ -268,3 +285,36 @@ def constructed_instance(seed=7):
     p = P()
     bucket([p] * 1040)                                      # 65 equal items: doubling inside the LDS tree
     return ks, dl
+
+
+# ---- XYZZ records at the edge of the invariant ------------------------------------------------------------------------
+def xyzz_post(words72):
+    """the invariant of a stored / carried G2 point on the raw limbs: every component below INV[coordinate] p, limbs
+    0..7 <= 2^29 + 7.  Returns a list of violations."""
+    bad = []
+    for i in range(8):
+        name, fe = COORDS[i // 2], words72[9 * i:9 * i + 9]
+        if g.value(fe) >= Fraction(str(INV[name])) * g.P:
+            bad.append(f"{name}.c{i % 2} = {g.value(fe) / g.P:.3f} p, the invariant says < {INV[name]} p")
+        if max(fe[:8]) > g.f.NORM_LIMB_MAX:
+            bad.append(f"{name}.c{i % 2} has a limb {max(fe[:8]):#x} above 2^29 + 7")
+    return bad
+
+
+def xyzz_lifted(pt, rng, lifts=(True,) * 8):
+    """72 words of the affine point pt with a random Z.  Component i of (X.c0, X.c1, Y.c0, ..., ZZZ.c1) with lifts[i]
+    set carries the largest multiple of p that keeps it below its bound, in the limb form that borrows from the upper
+    limbs (limbs 0..7 up to 2^29 + 7); the others are canonical.  X < 1.21 p has room for one p only above a residue
+    below 0.21 p, so Z is drawn until every lifted component of X has such a residue."""
+    room = (Fraction(str(INV["X"])) - 1) * g.P
+    while True:
+        z = g.rand_fq2(rng)
+        zz = g.mul2(z, z)
+        zzz = g.mul2(zz, z)
+        comps = [v * g.RHO % g.P for c in (g.mul2(pt[0], zz), g.mul2(pt[1], zzz), zz, zzz) for v in c]
+        if zz != g.ZERO2 and all(comps[i] < room for i in (0, 1) if lifts[i]):
+            break
+    out = []
+    for i, v in enumerate(comps):
+        out += g.f.borrowed(g.f.lift(v, INV[COORDS[i // 2]])) if lifts[i] else g.limbs_of(v)
+    return out

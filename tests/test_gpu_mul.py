@@ -1,6 +1,7 @@
 """GPU tests of the batch scalar multiplication: the device entry, the host-buffer entry and the host twin byte for byte,
 all against the big-integer models at the planted records and at 32 random positions, over lane tails, wave and
-workgroup edges; prepared output against the bases conversion and in an MSM; the normalisation cases; the G2 base of
+workgroup edges; whole arrays (scalar and base progressions, every table entry, the digit edges) and the G1 inputs that
+take the exceptional branches, against the model at EVERY position; prepared output against the bases conversion and in an MSM; the normalisation cases; the G2 base of
 order 10069; the sum identity; the chain with check / compress / decompress; isolation; chunking; the bounded wait; no
 scratch.  Expected values come from mul_ref (the models), never from the library."""
 import random
@@ -331,6 +332,57 @@ def test_mul_behind_a_held_stream_times_out_and_recovers(msm_pkg):
         c2.close()
 
 
-# ---- 9. resources ---------------------------------------------------------------------------------------------------------------------------
+# ---- 9. the model at every position -------------------------------------------------------------------------------------------------
+def assert_all(got, group, lo, exp, names=None):
+    hst.assert_same(got, hst.encoded(group, lo, exp), group, lo, names)
+
+
+@pytest.mark.parametrize("group", GROUPS)
+@pytest.mark.parametrize("n", [257, 4099])
+def test_scalar_progression_one_base(cfg, msm_pkg, group, n):
+    ks, base, exp = m.scalar_progression(group, 4099)
+    lo = m.OUT_LAYOUTS[group][n % 2]
+    assert_all(everywhere(cfg, msm_pkg, group, m.ONE, ks[:n], [base] * n, lo=lo), group, lo, exp[:n])
+
+
+@pytest.mark.parametrize("group", GROUPS)
+def test_whole_table_and_digit_edges(cfg, msm_pkg, group):
+    plan = msm_pkg.mul_plan(group)
+    ks, names, base, exp = m.table_case(group, plan["c"], plan["W"])
+    assert_all(everywhere(cfg, msm_pkg, group, m.ONE, ks, [base] * len(ks), sl=1), group, 0, exp, names)
+
+
+@pytest.mark.parametrize("group", GROUPS)
+@pytest.mark.parametrize("which", ["random", "r - 1"])
+def test_base_progression_each(cfg, msm_pkg, group, which):
+    s = m.R - 1 if which == "r - 1" else random.Random(808).randrange(m.R)
+    bases, exp = m.base_progression(group, s, 257)
+    assert_all(everywhere(cfg, msm_pkg, group, m.EACH, [s] * 257, bases, sl=2), group, 0, exp)
+
+
+@pytest.mark.parametrize("group", GROUPS)
+@pytest.mark.parametrize("mode", MODES)
+def test_star_scalar_doubles_in_the_last_addition(cfg, msm_pkg, group, mode):
+    """s* = 96 2^248 - r, s* +- 1, s* + r, s* + 4 r on three bases (mul_ref.S_STAR)"""
+    stored, ks = m.star_scalars()
+    for base, layouts in m.star_bases(group):
+        exp = [m.expected(group, k, base) for k in ks]
+        for sl in layouts:                                    # the Montgomery layout stores the reduced scalar
+            assert_all(everywhere(cfg, msm_pkg, group, mode, stored if sl else ks, [base] * len(ks), sl=sl), group, 0, exp)
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("y", m.ORDER3_Y)
+def test_g1_base_of_order_3(cfg, msm_pkg, mode, y):
+    """The G1 base (0, y) of order 3: doubling, vanishing sum and identity table entries on G1.  Pins the branch
+    behaviour of the additions, not an API promise: the header leaves bases off the curve unspecified."""
+    ks, bases, exp = hst.order3_case(mode, y)
+    got = everywhere(cfg, msm_pkg, 1, mode, ks, bases)
+    assert_all(got, 1, 0, exp)
+    for i, k in enumerate(ks):
+        assert (got[64 * i:64 * i + 64] == bytes(64)) == (k % 3 == 0), i
+
+
+# ---- 10. resources ---------------------------------------------------------------------------------------------------------------------------
 def test_mul_kernels_use_no_scratch():
     hst.test_mul_kernels_use_no_scratch()

@@ -179,6 +179,75 @@ def test_one_base_equals_each_on_the_replicated_base(msm_pkg, group):
     assert_same(one[:3 * m.OUT_BYTES[(group, 0)]], want(group, 0, ks[:3], [base] * 3), group, 0)
 
 
+# ---- the model at every position -----------------------------------------------------------------------------------------------
+def encoded(group, layout_out, points):
+    return b"".join(m.out_record(group, layout_out, p) for p in points)
+
+
+@pytest.mark.parametrize("group", GROUPS)
+@pytest.mark.parametrize("n", [257, 4099])
+def test_scalar_progression_one_base(msm_pkg, group, n):
+    """s_i = s_0 + i d on a random base: all n records against additions of the model"""
+    ks, base, exp = m.scalar_progression(group, 4099)
+    lo = m.OUT_LAYOUTS[group][n % 2]
+    got = host_mul(msm_pkg, group, m.ONE, ks[:n], [base], layout_out=lo)
+    assert_same(got, encoded(group, lo, exp[:n]), group, lo)
+
+
+@pytest.mark.parametrize("group", GROUPS)
+def test_whole_table_and_digit_edges(msm_pkg, group):
+    """every table entry alone, every negated entry with its carry, the digit rule at 0x7f / 0x80 / 0x81 / 0xff"""
+    plan = msm_pkg.mul_plan(group)
+    ks, names, base, exp = m.table_case(group, plan["c"], plan["W"])
+    got = host_mul(msm_pkg, group, m.ONE, ks, [base], scalar_layout=1)
+    assert_same(got, encoded(group, 0, exp), group, 0, names)
+
+
+@pytest.mark.parametrize("group", GROUPS)
+@pytest.mark.parametrize("which", ["random", "r - 1"])
+def test_base_progression_each(msm_pkg, group, which):
+    """P_i = P_0 + i Q under one scalar: all n records"""
+    s = m.R - 1 if which == "r - 1" else random.Random(808).randrange(m.R)
+    bases, exp = m.base_progression(group, s, 257)
+    got = host_mul(msm_pkg, group, m.EACH, [s] * 257, bases, scalar_layout=2)
+    assert_same(got, encoded(group, 0, exp), group, 0)
+
+
+@pytest.mark.parametrize("group", GROUPS)
+@pytest.mark.parametrize("mode", MODES)
+def test_star_scalar_doubles_in_the_last_addition(msm_pkg, group, mode):
+    """s* = 96 2^248 - r and its neighbours, s* also stored as s* + r and s* + 4 r: the last mixed addition of the digit
+    walk meets its own table entry"""
+    stored, ks = m.star_scalars()
+    for base, layouts in m.star_bases(group):
+        exp = encoded(group, 0, [m.expected(group, k, base) for k in ks])
+        for sl in layouts:                                    # the Montgomery layout stores the reduced scalar
+            got = host_mul(msm_pkg, group, mode, stored if sl else ks, [base] * (len(ks) if mode == m.EACH else 1),
+                           scalar_layout=sl)
+            assert_same(got, exp, group, 0)
+
+
+def order3_case(mode, y):
+    ks = m.order3_scalars()
+    pt = (0, y % c.P)
+    bases = [pt if mode == m.ONE or i % 2 == 0 else m.neg(1, pt) for i in range(len(ks))]
+    return ks, bases, [m.expected(1, k, b) for k, b in zip(ks, bases)]
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("y", m.ORDER3_Y)
+def test_g1_base_of_order_3(msm_pkg, mode, y):
+    """(0, y) has order 3 under the chord-and-tangent formulas (a = 0, b is never read): every ladder step and every
+    digit meets acc == +-P, and the fixed-base table holds identity entries.  This pins the branch behaviour of the
+    additions (doubling, vanishing sum, identity entry); it is not an API promise -- the header leaves bases off the
+    curve unspecified."""
+    ks, bases, exp = order3_case(mode, y)
+    got = host_mul(msm_pkg, 1, mode, ks, bases if mode == m.EACH else bases[:1])
+    assert_same(got, encoded(1, 0, exp), 1, 0)
+    for i, k in enumerate(ks):
+        assert (records(got, 64)[i] == bytes(64)) == (k % 3 == 0), i
+
+
 def test_argument_errors(msm_pkg):
     L, IE, OK = msm_pkg.lib(), msm_pkg.INPUT_ERROR, msm_pkg.OK
     sc, pts, out = ctypes.create_string_buffer(32 * 4), ctypes.create_string_buffer(136 * 4), ctypes.create_string_buffer(136 * 4)
