@@ -852,6 +852,53 @@ int msm_amd_test_mul_stage(msm_amd_ctx* ctx, int group, int which, int layout, c
                            size_t n, void* out);
 int msm_amd_test_mul_stage_host(int group, int which, int layout, const void* in, const void* table, size_t n, void* out);
 
+/* ---- number-theoretic transform over Fr ----------------------------------------------------------------
+ * The MSM calls CONSUME device-resident scalars; in a prover those scalars are outputs of a transform over Fr (halo2's
+ * best_fft next to best_multiexp, the inverse and coset transforms of Groth16's h-query).  These calls produce them
+ * where the MSM reads them: msm_amd_ntt_device(..., MSM_AMD_NTT_INVERSE, ...) and msm_amd_msm_device on the same pointer.
+ * Lengths: r - 1 = 2^28 t with t odd, so n = 2^log_n, 0 <= log_n <= 28, and the primitive n-th root is
+ * w = rho^(2^(28 - log_n)) for a 2^28-th root rho chosen by an enum, because the two crate families differ:
+ *   MSM_AMD_NTT_ROOT_ARK  rho = 5^t mod r = 19103219067921713944291392827692070036145651957329286315305642004821462161904
+ *   MSM_AMD_NTT_ROOT_H2C  rho = 7^t mod r = 0x03ddb9f5166d18b798865ea93dd31f743215cf6dd39329c8d34f1ed960c37c9c
+ * The library derives rho as g^t on the host; tests/test_ntt_host.py holds the two values and checks rho^(2^27) = -1.
+ * UNPINNED: that they equal ark-bn254's TWO_ADIC_ROOT_OF_UNITY and halo2curves' ROOT_OF_UNITY is recollection only
+ * (neither crate was available to test against).
+ * Definitions, all mod r, natural order in and out; g is an optional coset shift (shift32; NULL: g = 1):
+ *   MSM_AMD_NTT_FORWARD  out[k] = sum_{i<n} in[i] g^i w^(i k): the evaluations of the polynomial on g H
+ *   MSM_AMD_NTT_INVERSE  out[i] = g^-i n^-1 sum_{k<n} in[k] w^(-i k): the exact inverse of FORWARD with the same g (the
+ *                        library inverts g and n on the host)
+ * Scalars: 32-byte records in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE (MSM_AMD_SCALAR_CANON_BE32:
+ * MSM_AMD_INPUT_ERROR); the shift and the output use the layout of the input.  Inputs are read as the MSM reads them:
+ * any 256-bit value is taken mod r.  Every output is the fully reduced residue, so the bytes are unique.
+ * A call transforms n_vec >= 1 vectors stored back to back, n_vec n < 2^32.
+ * A domain holds the twiddles of one (root, log_n) on the ctx's device -- w^j for j < n/2, device_bytes = 16 n (32 for
+ * n = 1) -- and serves both directions.  msm_amd_destroy releases the domains the caller did not free.
+ * Status: n_vec == 0: MSM_AMD_OK, nothing is touched.  MSM_AMD_INPUT_ERROR: an unknown root, direction or layout;
+ * log_n > 28; a null pointer with n_vec > 0; g = 0 mod r; n_vec n >= 2^32; a domain handle of another ctx, a freed one or
+ * a table handle; device buffers that are not 16-byte aligned or that overlap without being equal -- d_out == d_in (in
+ * place) and disjoint buffers are both valid, and an out-of-place call leaves d_in unchanged.
+ * The ctx calls serialise on the ctx and first wait -- bounded -- for its earlier work (a busy ctx:
+ * MSM_AMD_PIPELINE_ERROR, msm_amd_last_error names the call); a transform of more than 2^10 elements uses one
+ * ctx-owned buffer of the size of the batch; msm_amd_ntt uploads the batch through the page-locked staging ring.
+ * (Development knob MSM_AMD_NTT_TILE_LOG = 2 .. 10 at msm_amd_init: elements per workgroup of a pass as a power of two;
+ * default 10.  No byte of a result depends on it.) */
+enum { MSM_AMD_NTT_ROOT_ARK = 0, MSM_AMD_NTT_ROOT_H2C = 1 };
+enum { MSM_AMD_NTT_FORWARD = 0, MSM_AMD_NTT_INVERSE = 1 };
+typedef struct msm_amd_ntt_domain msm_amd_ntt_domain;
+int msm_amd_ntt_domain_build(msm_amd_ctx* ctx, int root, uint32_t log_n, msm_amd_ntt_domain** out);
+int msm_amd_ntt_domain_info(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int* root, uint32_t* log_n,
+                            size_t* device_bytes, void* omega32 /* w, 32 B MONT_LE; may be NULL, like the others */);
+int msm_amd_ntt_domain_free(msm_amd_ctx* ctx, msm_amd_ntt_domain* domain);
+int msm_amd_ntt(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int scalar_layout,
+                const void* shift32 /* g in scalar_layout, or NULL */, const void* in, void* out, size_t n_vec);
+/* kernel_ms (optional, as msm_amd_sort_pairs_device): device time of the passes between two events */
+int msm_amd_ntt_device(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int scalar_layout,
+                       const void* shift32 /* HOST memory, or NULL */, const void* d_in, void* d_out, size_t n_vec,
+                       float* kernel_ms);
+/* The same on the CPU (no ctx, no GPU; the same bodies compiled for the host); threads <= 0: up to 16 host threads. */
+int msm_amd_host_ntt(int root, uint32_t log_n, int direction, int scalar_layout, const void* shift32, const void* in,
+                     void* out, size_t n_vec, int threads);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 int msm_amd_last_timings(const msm_amd_ctx* ctx, msm_amd_timings* out);
 /* Algorithmic HBM bytes of one MSM: whole pipeline and accumulation only. */

@@ -49,6 +49,9 @@ COMPRESSED_ARK, COMPRESSED_PARITY = 0, 1
 POINT_BAD_ENCODING = 4
 # batch scalar multiplication (MSM_AMD_MUL_BASE_*)
 MUL_BASE_EACH, MUL_BASE_ONE = 0, 1
+# number-theoretic transform over Fr (MSM_AMD_NTT_ROOT_*, MSM_AMD_NTT_FORWARD / _INVERSE)
+NTT_ROOT_ARK, NTT_ROOT_H2C = 0, 1
+NTT_FORWARD, NTT_INVERSE = 0, 1
 
 
 def op_is_point(op):
@@ -98,6 +101,8 @@ EXPORTS = [
     "msm_amd_mul_points", "msm_amd_mul_points_device", "msm_amd_g2_mul_points", "msm_amd_g2_mul_points_device",
     "msm_amd_host_mul_points", "msm_amd_host_g2_mul_points", "msm_amd_test_mul_plan",
     "msm_amd_test_mul_stage", "msm_amd_test_mul_stage_host",
+    "msm_amd_ntt_domain_build", "msm_amd_ntt_domain_info", "msm_amd_ntt_domain_free", "msm_amd_ntt", "msm_amd_ntt_device",
+    "msm_amd_host_ntt",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -320,6 +325,14 @@ def _lib():
         L.msm_amd_test_mul_plan.argtypes = [c_int, POINTER(c_uint32)]
         L.msm_amd_test_mul_stage.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
         L.msm_amd_test_mul_stage_host.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+        L.msm_amd_ntt_domain_build.argtypes = [c_void_p, c_int, c_uint32, POINTER(c_void_p)]
+        L.msm_amd_ntt_domain_info.argtypes = [c_void_p, c_void_p, POINTER(c_int), POINTER(c_uint32), POINTER(c_size_t),
+                                              c_void_p]
+        L.msm_amd_ntt_domain_free.argtypes = [c_void_p, c_void_p]
+        L.msm_amd_ntt.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t]
+        L.msm_amd_ntt_device.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                         POINTER(c_float)]
+        L.msm_amd_host_ntt.argtypes = [c_int, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int]
         L.msm_amd_generate_instance_host.argtypes = [c_uint64, c_size_t, c_int, c_void_p, c_void_p, c_int]
         L.msm_amd_test_op_ifma.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_tuned_split.argtypes = [c_size_t]
@@ -780,6 +793,27 @@ class MsmConfig:
         self._check(_lib().msm_amd_test_mul_stage(self.h, group, which, layout, data, table, n, out))
         return out.raw[:n * mul_stage_out_bytes(group, which, layout)]
 
+    # ---- number-theoretic transform over Fr ------------------------------------------------------
+    def ntt_domain(self, root, log_n) -> "NttDomain":
+        """Twiddles of one (root, log_n) on this ctx's device (msm_amd_ntt_domain_build)."""
+        h = c_void_p()
+        self._check(_lib().msm_amd_ntt_domain_build(self.h, root, log_n, ctypes.byref(h)))
+        return NttDomain(self, h)
+
+    def ntt(self, dom, data: bytes, direction=NTT_FORWARD, scalar_layout=SCALAR_MONT_LE, shift=None, n_vec=1) -> bytes:
+        """n_vec transforms of host records (msm_amd_ntt); shift: 32 bytes in scalar_layout, or None."""
+        out = ctypes.create_string_buffer(max(1, len(data)))
+        self._check(_lib().msm_amd_ntt(self.h, _ntt_handle(dom), direction, scalar_layout, shift, data, out, n_vec))
+        return out.raw[:len(data)]
+
+    def ntt_device(self, dom, d_in, d_out, direction=NTT_FORWARD, scalar_layout=SCALAR_MONT_LE, shift=None,
+                   n_vec=1) -> float:
+        """The same on device-resident records, d_out == d_in or disjoint (msm_amd_ntt_device); returns kernel_ms."""
+        ms = c_float(0)
+        self._check(_lib().msm_amd_ntt_device(self.h, _ntt_handle(dom), direction, scalar_layout, shift, c_void_p(d_in),
+                                              c_void_p(d_out), n_vec, ctypes.byref(ms)))
+        return ms.value
+
     def test_op_g2(self, op, a, b, count):
         """Raw-limb G2 op (MSM_AMD_G2_RAW_*) on the device: a, b flat u32 lists of count * G2_RAW_IN_WORDS; returns
         count * G2_RAW_OUT_WORDS u32."""
@@ -1038,6 +1072,36 @@ def host_mul_points(scalars: bytes, points: bytes, n: int, base_mode=MUL_BASE_EA
     if st != OK:
         raise MsmError(st)
     return out.raw[:n * size]
+
+
+class NttDomain:
+    """A transform domain of one MsmConfig (msm_amd_ntt_domain_*)."""
+
+    def __init__(self, cfg, handle):
+        self.cfg, self.h = cfg, handle
+
+    def info(self) -> dict:
+        root, log_n, nbytes, omega = c_int(0), c_uint32(0), c_size_t(0), ctypes.create_string_buffer(32)
+        self.cfg._check(_lib().msm_amd_ntt_domain_info(self.cfg.h, self.h, ctypes.byref(root), ctypes.byref(log_n),
+                                                       ctypes.byref(nbytes), omega))
+        return {"root": root.value, "log_n": log_n.value, "device_bytes": nbytes.value, "omega": omega.raw}
+
+    def free(self):
+        self.cfg._check(_lib().msm_amd_ntt_domain_free(self.cfg.h, self.h))
+
+
+def _ntt_handle(dom):
+    return dom.h if isinstance(dom, NttDomain) else dom
+
+
+def host_ntt(data: bytes, root, log_n, direction=NTT_FORWARD, scalar_layout=SCALAR_MONT_LE, shift=None, n_vec=1,
+             threads=0) -> bytes:
+    """Host twin of MsmConfig.ntt (no GPU)."""
+    out = ctypes.create_string_buffer(max(1, len(data)))
+    st = _lib().msm_amd_host_ntt(root, log_n, direction, scalar_layout, shift, data, out, n_vec, threads)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:len(data)]
 
 
 def mul_plan(group=1) -> dict:

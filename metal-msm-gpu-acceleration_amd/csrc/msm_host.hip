@@ -31,6 +31,7 @@
 #include "launch_check.h"
 #include "launch_compress.h"
 #include "launch_mul.h"
+#include "launch_ntt.h"
 #include "host_fq64.h"
 #include "test_ops.hip.h"
 #include "test_ops_g2.hip.h"
@@ -185,6 +186,24 @@ struct msm_amd_tables : TablesRecord {};
 // that a G1 handle is no G2 handle and the reverse.
 struct msm_amd_g2_tables : TablesRecord {};
 
+// The twiddles of one (root, log_n) (msm_amd_ntt_domain_*): d_tw[j] = omega^j, j < n/2, Montgomery.  A handle type and
+// a live list (msm_amd_ctx::live_ntt) of its own: a table handle is no domain and the reverse.
+struct msm_amd_ntt_domain {
+  int root = 0;
+  uint32_t log_n = 0;
+  size_t bytes = 0;
+  void* d_tw = nullptr;
+  u256 omega{};
+};
+
+// Buffers of the transform calls (ntt_call): the ONE batch-sized scratch of a plan with more than one pass, the power
+// table of a call's shift and the two events behind kernel_ms.  Host input is staged in the scalar staging of the G1
+// point calls (PointCallState::in[0]) and transformed in place there.
+struct NttState {
+  DeviceBuf scratch, pow;
+  hipEvent_t ev[2] = {};
+};
+
 // Buffers of the point calls of one group (check, decompress, compress and mul_points; point_call below): the staging of
 // the host-buffer calls, the 64-byte counters with their page-locked copy and events, and the device-side scratch of
 // mul_points.  One per group: a G2 call touches G2State only.
@@ -242,6 +261,9 @@ struct msm_amd_ctx {
   uint32_t forced_window = 0;
   std::vector<msm_amd_tables*> live_tables;
   std::vector<msm_amd_g2_tables*> live_g2_tables;
+  std::vector<msm_amd_ntt_domain*> live_ntt;
+  NttState ntt;
+  uint32_t ntt_tile_log = kNttTileLog;   // elements per workgroup of a transform pass, as a power of two (MSM_AMD_NTT_TILE_LOG)
   int next_ws = 0;
   DeviceBuf scratch_a, scratch_b, scratch_c, scratch_b2, scratch_c2;
   Batch batches[kMaxBatches];
@@ -2054,6 +2076,8 @@ int msm_amd_init(int device, msm_amd_ctx** out) {
     const size_t want = std::max<size_t>(1, (size_t)std::strtoull(e, nullptr, 10));
     ctx->mul_chunk = std::min<size_t>((want + kMulNormGroup - 1) / kMulNormGroup * kMulNormGroup, (size_t)1 << 24);
   }
+  if (const char* e = std::getenv("MSM_AMD_NTT_TILE_LOG"))
+    ctx->ntt_tile_log = (uint32_t)std::max(2, std::min((int)kNttTileLog, std::atoi(e)));
   if (const char* e = std::getenv("MSM_AMD_BASES_CACHE_VERIFY")) ctx->bases_cache_verify = std::strcmp(e, "full") == 0;
   if (const char* e = std::getenv("MSM_AMD_BASES_CACHE_MB")) {
     ctx->bases_cache_budget = (size_t)std::strtoull(e, nullptr, 10) << 20;
@@ -2163,6 +2187,7 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
     for (hipEvent_t& e : ps->ev) kill_event(e);
     ps->ready = false;
   }
+  for (hipEvent_t& e : ctx->ntt.ev) kill_event(e);
   for (hipEvent_t& e : ctx->uploaded) kill_event(e);
   kill_event(ctx->upload_done);
   kill_event(ctx->after_sort_mark);
@@ -2192,6 +2217,12 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
   }
   tables_release_all(ctx->live_tables);
   tables_release_all(ctx->live_g2_tables);
+  for (msm_amd_ntt_domain* d : ctx->live_ntt) {   // domains the caller did not free
+    (void)hipFree(d->d_tw);
+    delete d;
+  }
+  ctx->live_ntt.clear();
+  for (DeviceBuf* b : {&ctx->ntt.scratch, &ctx->ntt.pow}) kill_buf(*b);
   for (DeviceBuf* b : {&ctx->scratch_a, &ctx->scratch_b, &ctx->scratch_c, &ctx->scratch_b2, &ctx->scratch_c2}) kill_buf(*b);
   bases_cache_clear(ctx);   // (entries and unused reserves go through the graveyard)
   for (const msm_amd_ctx::CacheReserve& r : ctx->cache_reserve) ctx->graveyard.push_back(r.d);
@@ -3271,6 +3302,8 @@ int msm_amd_test_fill_workspaces(msm_amd_ctx* ctx, uint8_t byte) {
   for (PointCallState* ps : {&ctx->points, &ctx->g2.points})   // the XYZZ records and the fixed-base table of the mul_points calls
     for (DeviceBuf* b : {&ps->xyzz, &ps->table})
       if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
+  for (DeviceBuf* b : {&ctx->ntt.scratch, &ctx->ntt.pow})   // the transform's pass buffer and shift powers
+    if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
   return sync_stream_bounded(ctx, ctx->stream, __func__);
 }
 
@@ -3999,6 +4032,152 @@ int msm_amd_test_mul_stage_host(int group, int which, int layout, const void* in
   else
     mul_stage_host<MulG1>(s, layout, (const uint8_t*)in, table, n, (uint8_t*)out);
   return MSM_AMD_OK;
+}
+
+}  // extern "C"
+
+// ---- number-theoretic transform over Fr (msm_amd_ntt_domain_*, msm_amd_ntt, msm_amd_ntt_device) --------------------------
+// The discipline of point_call: ctx lock, bounded drain of the ctx's earlier work, every buffer sized on the idle ctx
+// before anything is enqueued, host input through the page-locked staging ring, the passes on the main stream, the
+// result behind a bounded stream wait.  Domain handles are validated by membership in ctx->live_ntt.
+namespace {
+
+const msm_amd_ntt_domain* find_ntt_domain(const msm_amd_ctx* ctx, const void* handle) {
+  for (const msm_amd_ntt_domain* d : ctx->live_ntt)
+    if ((const void*)d == handle) return d;
+  return nullptr;
+}
+
+int ntt_call(msm_amd_ctx* ctx, const msm_amd_ntt_domain* handle, bool host, int direction, int scalar_layout,
+             const void* shift32, const void* in, void* out, size_t n_vec, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  const std::string who = host ? "msm_amd_ntt" : "msm_amd_ntt_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (!ntt_direction_known(direction)) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": direction must be MSM_AMD_NTT_FORWARD or MSM_AMD_NTT_INVERSE");
+  if (!ntt_layout_known(scalar_layout))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": scalars in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE only");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_ntt_domain* dom = find_ntt_domain(ctx, handle);
+  if (!dom) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": not a transform domain of this ctx");
+  if (((uint64_t)n_vec >> (32 - dom->log_n)) != 0) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": n_vec * n >= 2^32");
+  if (n_vec == 0) return MSM_AMD_OK;
+  if (!in || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": null pointer with n_vec > 0");
+  u256 g;
+  if (!ntt_read_shift(scalar_layout, shift32, &g)) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": the shift is 0 mod r");
+  const size_t bytes = (n_vec << dom->log_n) * 32;
+  if (!host) {
+    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
+    if ((a | b) & 15u) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": d_in and d_out must be 16-byte aligned");
+    if (a != b && a < b + bytes && b < a + bytes)
+      return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": d_out must be d_in itself or disjoint from it");
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = recover_if_stalled(ctx)) return fail(ctx, rc, who + ": " + ctx->last_error);
+  if (!drain_or_mark_stalled(ctx))
+    return fail(ctx, MSM_AMD_PIPELINE_ERROR, who + ": device busy past the wait bound of " +
+                                                 std::to_string(ctx->wait_timeout_ms) + " ms (msm_amd_synchronize waits again)");
+  // the ctx is idle: every buffer of this call is sized now
+  NttState& s = ctx->ntt;
+  hipStream_t st = ctx->stream;
+  int rc;
+  NttLaunch c{};
+  c.tw = dom->d_tw, c.log_n = dom->log_n, c.tile_log = ctx->ntt_tile_log;
+  c.direction = direction, c.layout = scalar_layout, c.n_vec = n_vec;
+  u256 tab[kNttPowEntries];
+  ntt_shift_setup(g, direction, dom->log_n, tab, &c.sc);
+  if (ntt_plan(c.log_n, c.tile_log).passes > 1 && (rc = ensure(ctx, s.scratch, bytes))) return rc;
+  if (shift32 && (rc = ensure(ctx, s.pow, sizeof tab))) return rc;
+  if (host && (rc = ensure(ctx, ctx->points.in[0], bytes))) return rc;
+  for (hipEvent_t& e : s.ev)
+    if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+  c.scratch = s.scratch.p;
+  c.in = in, c.out = out;
+  if (host) {   // staged, transformed in place, copied back
+    if ((rc = staged_upload(ctx, ctx->points.in[0].p, in, bytes, st))) return rc;
+    c.in = c.out = ctx->points.in[0].p;
+  }
+  if (shift32) {
+    if ((rc = staged_upload(ctx, s.pow.p, tab, sizeof tab, st))) return rc;
+    c.pow_tab = s.pow.p;
+  }
+  HIP_TRY(ctx, hipEventRecord(s.ev[0], st));
+  launch_ntt(st, c);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(s.ev[1], st));
+  if (host) HIP_TRY(ctx, hipMemcpyAsync(out, c.out, bytes, hipMemcpyDeviceToHost, st));
+  if ((rc = sync_stream_bounded(ctx, st, who.c_str()))) return rc;
+  if (kernel_ms) *kernel_ms = event_span(s.ev[0], s.ev[1]);
+  return MSM_AMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_ntt_domain_build(msm_amd_ctx* ctx, int root, uint32_t log_n, msm_amd_ntt_domain** out) {
+  if (!ctx || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_ntt_domain_build: null pointer");
+  *out = nullptr;
+  if (!ntt_root_known(root)) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_ntt_domain_build: root must be MSM_AMD_NTT_ROOT_ARK or MSM_AMD_NTT_ROOT_H2C");
+  if (log_n > kNttMaxLog) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_ntt_domain_build: log_n must be 0..28");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = recover_if_stalled(ctx)) return rc;
+  if (int qrc = quiesce_for_allocation(ctx, "the twiddles of a transform domain")) return qrc;
+  const u256 omega = ntt_omega(root, log_n);
+  const size_t bytes = std::max<size_t>(32, ((size_t)1 << log_n) / 2 * 32);   // n = 1: no entry, one record of room
+  void* d_tw = nullptr;
+  HIP_TRY(ctx, hipMalloc(&d_tw, bytes));
+  launch_ntt_twiddles(ctx->stream, omega, log_n, d_tw);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && sync_stream_bounded(ctx, ctx->stream, "transform domain build")) {
+    ctx->graveyard.push_back(d_tw);   // the build may still be running: released when the ctx is idle
+    return MSM_AMD_PIPELINE_ERROR;
+  }
+  if (e != hipSuccess) {
+    (void)hipFree(d_tw);
+    HIP_TRY(ctx, e);
+  }
+  msm_amd_ntt_domain* d = new msm_amd_ntt_domain();
+  d->root = root, d->log_n = log_n, d->bytes = bytes, d->d_tw = d_tw, d->omega = omega;
+  ctx->live_ntt.push_back(d);
+  *out = d;
+  return MSM_AMD_OK;
+}
+
+int msm_amd_ntt_domain_info(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int* root, uint32_t* log_n,
+                            size_t* device_bytes, void* omega32) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_ntt_domain* d = find_ntt_domain(ctx, domain);
+  if (!d) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_ntt_domain_info: not a transform domain of this ctx");
+  if (root) *root = d->root;
+  if (log_n) *log_n = d->log_n;
+  if (device_bytes) *device_bytes = d->bytes;
+  if (omega32) std::memcpy(omega32, d->omega.v, 32);
+  return MSM_AMD_OK;
+}
+
+int msm_amd_ntt_domain_free(msm_amd_ctx* ctx, msm_amd_ntt_domain* domain) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  auto it = std::find(ctx->live_ntt.begin(), ctx->live_ntt.end(), domain);
+  if (it == ctx->live_ntt.end()) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_ntt_domain_free: not a transform domain of this ctx");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->live_ntt.erase(it);
+  if (drain_or_mark_stalled(ctx)) (void)hipFree(domain->d_tw);
+  else ctx->graveyard.push_back(domain->d_tw);   // hipFree would wait for the device without bound
+  delete domain;
+  return MSM_AMD_OK;
+}
+
+int msm_amd_ntt(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int scalar_layout, const void* shift32,
+                const void* in, void* out, size_t n_vec) {
+  return ntt_call(ctx, domain, true, direction, scalar_layout, shift32, in, out, n_vec, nullptr);
+}
+
+int msm_amd_ntt_device(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int scalar_layout,
+                       const void* shift32, const void* d_in, void* d_out, size_t n_vec, float* kernel_ms) {
+  return ntt_call(ctx, domain, false, direction, scalar_layout, shift32, d_in, d_out, n_vec, kernel_ms);
 }
 
 }  // extern "C"
