@@ -215,7 +215,11 @@ int msm_amd_msm_batch_device(msm_amd_ctx* ctx, int scalar_layout, int point_layo
 /* Pipelined form of msm_amd_msm_batch_device: submit enqueues all GPU work of the batch and returns a ticket;
  * wait finishes it (host Horner pass) and fills out_host (n_inst x 96 B, must stay valid until then).  Up to 4
  * batches may be in flight, so the front end of batch k+1 runs under the accumulation of batch k and the host
- * work of batch k under the GPU work of batch k+1.  The d_scalars / d_points / n arrays are read at submit. */
+ * work of batch k under the GPU work of batch k+1.  The d_scalars / d_points / n arrays (the pointer lists) are read
+ * at submit.  The device buffers they name are another matter: the point buffers of every layout -- the caller's own
+ * MSM_AMD_POINT_H2C_AFFINE array as much as a prepared array or a table -- are gathered by the accumulate kernel itself
+ * and are READ UNTIL THE BATCH HAS BEEN WAITED FOR (msm_amd_wait_batch, or the return of a blocking call); do not free or
+ * overwrite them before.  They are never written. */
 int msm_amd_submit_batch_device(msm_amd_ctx* ctx, int scalar_layout, int point_layout, size_t n_inst,
                                 const void* const* d_scalars, const void* const* d_points, const size_t* n,
                                 void* out_host, int* ticket);
@@ -496,9 +500,16 @@ enum {
   MSM_AMD_RAW_FE_SQR_WIDE = 33,  /* sqr_np(a0) */
   MSM_AMD_RAW_FE_MUL2_WIDE = 34, /* mul2w_np(a0, a1, b0, b1) */
   /* 35 stays unknown (tests pin it as refused) */
-  MSM_AMD_RAW_FE_SQRT = 36       /* square root of a0 (normalised, < 8 p) by the ladder of the decompression kernels
+  MSM_AMD_RAW_FE_SQRT = 36,      /* square root of a0 (normalised, < 8 p) by the ladder of the decompression kernels
                                     (csrc/compress_points.hip.h): out[0..8] = root, out[9] = 1 if there is one, else
                                     all zero; b ignored */
+  MSM_AMD_RAW_BASES_IN_PLACE = 40 /* external records as the accumulate kernel gathers them in place (the image of
+                                    the point on the isomorphic curve E': limbs of x << 3 and y << 2).  a[0..15],
+                                    a[16..31], b[1..16]: records 0, 1, 2 (x, y: 8 + 8 words, little-endian); a[32]:
+                                    bit k = negate record k; b[0] = 0: out[0..8], out[9..17] = the limbs of record 0,
+                                    out[18] = its sixteen words are all zero, out[19..27] = its lazily negated y;
+                                    b[0] = 1: out[0..35] = record 0 + record 1 by the affine start, out[36] = vanished;
+                                    b[0] = 2: (record 0 + record 1) + record 2 by the mixed addition */
 };
 int msm_amd_test_op_raw(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count);
 /* The same bodies on the host CPU (no GPU needed). */

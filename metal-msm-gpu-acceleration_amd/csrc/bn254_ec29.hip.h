@@ -16,6 +16,20 @@
 //      X < 10 p      Y < 6 p      ZZ < 2.8 p      ZZZ < 2 p      limbs 0..7 < 2^29 + 8
 // (pti_mmadd sets the X and ZZ figures: its R < 12.1 p and ZZ3 = P^2 with P < 17.1 p).  tools/fq29_bounds.py
 // re-derives every bound below by interval arithmetic and checks that no 64-bit column sum can overflow.
+//
+// The isomorphic curve E'.  The caller's bases are canonical E = x R mod p with R = 2^256; the limbs of E << 3 and of
+// E << 2 (Fq29::unpack256_shl, pure slicing) stand, with rho = 2^261, for x' = x / 4 and y' = y / 8.  (x, y) ->
+// (x / 4, y / 8) maps E: y^2 = x^3 + 3 onto E': y'^2 = x'^3 + 3/64 as a group isomorphism, and every formula below is
+// an a = 0 formula in which b does not appear, so accumulate, combine, the window reduction and the host's Horner
+// pass compute on such limbs, unchanged, the image of the sum on E'; the host halves Z once per instance to come
+// back (msm_host.hip: iso_to_e).  accumulate_kernel<.., ExtBases> reads the caller's array this way instead of the
+// packed copy convert_bases_kernel would write.  Bounds on E' (tools/fq29_bounds.py, the "(E')" entries):
+//      base x < 8 p, y < 4 p, -y = 8 p - y (K8E30: the top limb of a y near 4 p is above K4E30's), exact 29-bit limbs
+//      affine start: P, R = q - p + 12 p < 20 p (K12E30: top limb above a coordinate's), zero filter 21,
+//                    X3 < 11.4 p, ZZ3 = P^2 < 3.4 p (below the 4 p that pti_add_nz's -ZZ2 needs), ZZZ3 < 1.4 p
+//      mixed addition: U2 < 1.16 p, P < 17.2 p (filter 18 as on E), outputs as on E
+//      stored points: X < 11.5 p   Y < 8 p (a lone negated base)   ZZ < 3.4 p   ZZZ < 2 p
+// pti_add_nz and pti_double take such points as they are (P < 1.50 p, R < 1.28 p).
 // The exceptional cases (equal points -> doubling, opposite points -> identity) are detected with the
 // one-limb filter Fq29::maybe_zero, confirmed exactly (Fq29::is_zero_exact) and resolved by pti_double / the
 // identity, all on the same limbs.
@@ -36,6 +50,13 @@ struct PtI {
 };
 static_assert(sizeof(AffPacked) == 64, "AffPacked must be 64 bytes");
 static_assert(sizeof(PtI) == 144, "PtI must be 144 bytes");
+
+// Bounds of the one-limb zero filters (Fq29::maybe_zero) on P at each site: the smallest integer above the value bound
+// tools/fq29_bounds.py derives for it -- the tool prints both and tests/test_bases_in_place_bounds.py compares them.
+constexpr uint32_t kZeroFilterMadd = 18;       // pti_madd_tail, on E and E': P < 17.2 p
+constexpr uint32_t kZeroFilterMmadd = 18;      // pti_mmadd_tail on E: P < 17.1 p
+constexpr uint32_t kZeroFilterMmaddIso = 21;   // pti_mmadd_tail on E': P < 20.1 p
+constexpr uint32_t kZeroFilterAdd = 2;         // pti_add_nz, on E and E': P < 1.50 p
 
 MSM_HD bool affi_is_identity(const AffI& p) {
   uint32_t o = 0;
@@ -111,6 +132,23 @@ MSM_HD AffI affi_unpack_finite(const AffPacked& p) {
   return r;
 }
 
+// The caller's external record read in place: the image of the point on E' (see the top of this file).  No identity
+// test here either; the caller tests the sixteen words (affine_words_zero).
+MSM_HD AffI affi_from_ext_iso(const Affine& p) {
+  AffI r;
+  r.x = Fq29::unpack256_shl<3>(p.x);
+  r.y = Fq29::unpack256_shl<2>(p.y);
+  return r;
+}
+// "all sixteen words zero", the identity of the external layout, in 3-input ORs
+MSM_HD bool affine_words_zero(const Affine& p) {
+  const uint32_t a = p.x.v[0] | p.x.v[1] | p.x.v[2], b = p.x.v[3] | p.x.v[4] | p.x.v[5], c = p.x.v[6] | p.x.v[7] | p.y.v[0],
+                 d = p.y.v[1] | p.y.v[2] | p.y.v[3], e = p.y.v[4] | p.y.v[5] | p.y.v[6];
+  return ((a | b | c) | (d | e | p.y.v[7])) == 0;
+}
+// -y of a base on E' (y < 4 p) without the carry round: 8 p - y, limbs < 2^30.5 (see Fq29::neg_wide)
+MSM_HD fe29 neg_wide_iso(const fe29& y) { return Fq29::sub<K8E30>(Fq29::zero(), y); }
+
 // Jacobian (X, Y, Z) -> (X, Y, Z^2, Z^3)
 MSM_HD PtI pti_from_ext(const Jacobian& p) {
   if (jac_is_identity(p)) return pti_identity();
@@ -174,7 +212,7 @@ template <class ReloadQ>
 MSM_HD PtI pti_madd_tail(const PtI& p, const fe29& U2, const fe29& S2, ReloadQ&& reload_q, bool& vanished) {
   const fe29 P0 = Fq29::norm(Fq29::sub<K16E30>(U2, p.x));   // < 17.1 p
   const fe29 R0 = Fq29::norm(Fq29::sub<K8E30>(S2, p.y));    // <  9.1 p
-  if (Fq29::maybe_zero(P0, 18)) {
+  if (Fq29::maybe_zero(P0, kZeroFilterMadd)) {
     MSM_ISA_MARK("rare mixed_addition");
     if (Fq29::is_zero_exact(P0)) {   // same x: either q == p (double) or q == -p (identity)
       if (Fq29::is_zero_exact(R0)) return pti_double(pti_from_affi(reload_q()));
@@ -199,15 +237,21 @@ MSM_HD PtI pti_madd_tail(const PtI& p, const fe29& U2, const fe29& S2, ReloadQ&&
   r.zzz = Fq29::mul_np(ZZZ1, PPP);
   return r;
 }
-// The affine + affine start likewise: the head consumes q.
+// The affine + affine start likewise: the head consumes q.  ISO: both points are bases on E' (x < 8 p, |y| <= 8 p).
+template <bool ISO = false>
 MSM_HD void pti_mmadd_head(const fe29& px, const fe29& py, const fe29& qx, const fe29& qy, fe29& P, fe29& R) {
-  P = Fq29::norm(Fq29::sub<K16E30>(qx, px));   // < 17.1 p
-  R = Fq29::norm(Fq29::sub<K8E30>(qy, py));    // < 12.1 p (q.y may be an un-normalised negation, py not)
+  if (ISO) {
+    P = Fq29::norm(Fq29::sub<K12E30>(qx, px));   // < 20.1 p
+    R = Fq29::norm(Fq29::sub<K12E30>(qy, py));   // < 20.1 p
+  } else {
+    P = Fq29::norm(Fq29::sub<K16E30>(qx, px));   // < 17.1 p
+    R = Fq29::norm(Fq29::sub<K8E30>(qy, py));    // < 12.1 p (q.y may be an un-normalised negation, py not)
+  }
 }
-template <class ReloadQ>
+template <bool ISO = false, class ReloadQ>
 MSM_HD PtI pti_mmadd_tail(const fe29& px, const fe29& py, const fe29& P, const fe29& R, ReloadQ&& reload_q,
                           bool& vanished) {
-  if (Fq29::maybe_zero(P, 18)) {
+  if (Fq29::maybe_zero(P, ISO ? kZeroFilterMmaddIso : kZeroFilterMmadd)) {
     MSM_ISA_MARK("rare affine_start");
     if (Fq29::is_zero_exact(P)) {   // same x: either q == p (double) or q == -p (identity)
       if (Fq29::is_zero_exact(R)) return pti_double(pti_from_affi(reload_q()));
@@ -222,10 +266,10 @@ MSM_HD PtI pti_mmadd_tail(const fe29& px, const fe29& py, const fe29& P, const f
   const fe29 Q = Fq29::mul_np(X1, PP);
   const fe29 RR = Fq29::sqr_np(Rp);
   PtI r;
-  r.x = Fq29::norm(Fq29::sub<K8E31>(RR, Fq29::add(PPP, Fq29::add(Q, Q))));               // < 9.9 p
+  r.x = Fq29::norm(Fq29::sub<K8E31>(RR, Fq29::add(PPP, Fq29::add(Q, Q))));               // < 9.9 p (E': 11.4 p)
   const fe29 T = Fq29::norm(Fq29::sub<K16E30>(Q, r.x));                                   // < 17.2 p
   r.y = Fq29::mul2_np(Rp, T, Y1, Fq29::neg_wide(PPP));   // R*T - Y1*PPP in one reduction      // < 1.2 p
-  r.zz = PP;                                                                              // < 2.8 p
+  r.zz = PP;                                                                              // < 2.8 p (E': 3.4 p)
   r.zzz = PPP;
   return r;
 }
@@ -309,7 +353,7 @@ MSM_HD PtI pti_mmadd(const fe29& px, const fe29& py, const AffI& q) {
 //   P = X2 ZZ1 - X1 ZZ2,  R = Y2 ZZZ1 - Y1 ZZZ2        (double products: U1, U2, S1, S2 are never reduced alone)
 //   V = ZZ2 PP,  Tz = ZZZ2 PPP,  Q = X1 V (= U1 PP),  ZZ3 = ZZ1 V,  ZZZ3 = ZZZ1 Tz,  Y3 = R (Q - X3) - Y1 Tz
 // Every value is the one of the textbook grouping (the same Montgomery factors), P and R now reduction outputs:
-// P < 1.40 p, so its one-limb zero filter needs bound 2 only.
+// P < 1.40 p (1.50 p for points on E'), so its one-limb zero filter needs bound 2 only.
 MSM_HD PtI pti_add_nz(const PtI& p_in, const PtI& q_in, bool& vanished) {
   MSM_ISA_MARK("begin full_addition");
   // pins once per basic block, multiplications without pins of their own (see pti_madd_head)
@@ -318,7 +362,7 @@ MSM_HD PtI pti_add_nz(const PtI& p_in, const PtI& q_in, bool& vanished) {
   q.x = pin_limbs(q_in.x); q.y = pin_limbs(q_in.y); q.zz = pin_limbs(q_in.zz); q.zzz = pin_limbs(q_in.zzz);
   const fe29 P0 = Fq29::mul2w_np(q.x, p.zz, p.x, Fq29::neg_wide(q.zz));      // U2 - U1 + 4 U1' p   < 1.40 p
   const fe29 R0 = Fq29::mul2w_np(q.y, p.zzz, p.y, Fq29::neg_wide(q.zzz));    // S2 - S1 + 4 S1' p   < 1.21 p
-  if (Fq29::maybe_zero(P0, 2)) {
+  if (Fq29::maybe_zero(P0, kZeroFilterAdd)) {
     MSM_ISA_MARK("rare full_addition");
     if (Fq29::is_zero_exact(P0)) {
       if (Fq29::is_zero_exact(R0)) return pti_double(p);

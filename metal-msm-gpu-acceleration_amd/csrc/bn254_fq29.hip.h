@@ -66,7 +66,7 @@ MSM_HD fe29 pin_limbs(const fe29& a) {
 #define MSM_ISA_MARK(name) ((void)0)
 #endif
 
-enum KSel { K4E30 = 0, K8E30 = 1, K8E31 = 2, K16E30 = 3, K16E31 = 4 };
+enum KSel { K4E30 = 0, K8E30 = 1, K8E31 = 2, K16E30 = 3, K16E31 = 4, K12E30 = 5 };
 
 struct Fq29 {
   static constexpr uint32_t MASK = 0x1FFFFFFFu;
@@ -93,14 +93,16 @@ struct Fq29 {
                                0x11B7BC3Cu, 0x1CBD99BAu, 0x183340FBu, 0x000E0A77u};
     return c[i];
   }
-  // k*p with limbs lifted by 2^e (see header): K4E30, K8E30, K8E31, K16E30, K16E31
+  // k*p with limbs lifted by 2^e (see header): K4E30, K8E30, K8E31, K16E30, K16E31, K12E30
+  // (K12E30: the affine start on bases read in place, whose coordinates reach 8 p with a top limb above K8E30's)
   MSM_HD static constexpr uint32_t kc(int sel, int i) {
-    constexpr uint32_t c[5][9] = {
+    constexpr uint32_t c[6][9] = {
         {0x41F3F51Cu, 0x441182D9u, 0x51CA8D3Au, 0x4B548B41u, 0x561765DEu, 0x4B6D0300u, 0x429B8502u, 0x597098CEu, 0x00C19137u},
         {0x43E7EA38u, 0x482305B4u, 0x43951A76u, 0x56A91685u, 0x4C2ECBBEu, 0x56DA0603u, 0x45370A06u, 0x52E1319Eu, 0x01832271u},
         {0x83E7EA38u, 0x882305B2u, 0x83951A74u, 0x96A91683u, 0x8C2ECBBCu, 0x96DA0601u, 0x85370A04u, 0x92E1319Cu, 0x0183226Fu},
         {0x47CFD470u, 0x50460B6Au, 0x472A34EEu, 0x4D522D0Cu, 0x585D977Fu, 0x4DB40C08u, 0x4A6E140Fu, 0x45C2633Eu, 0x030644E5u},
-        {0x87CFD470u, 0x90460B68u, 0x872A34ECu, 0x8D522D0Au, 0x985D977Du, 0x8DB40C06u, 0x8A6E140Du, 0x85C2633Cu, 0x030644E3u}};
+        {0x87CFD470u, 0x90460B68u, 0x872A34ECu, 0x8D522D0Au, 0x985D977Du, 0x8DB40C06u, 0x8A6E140Du, 0x85C2633Cu, 0x030644E3u},
+        {0x45DBDF54u, 0x4C34888Fu, 0x555FA7B2u, 0x41FDA1C8u, 0x4246319Fu, 0x42470906u, 0x47D28F0Bu, 0x4C51CA6Eu, 0x0244B3ABu}};
     return c[sel][i];
   }
 
@@ -277,6 +279,25 @@ struct Fq29 {
     fe29 t;
     MSM_UNROLL for (int i = 0; i < 9; ++i) {
       const int bit = 29 * i;
+      const int w = bit >> 5, s = bit & 31;
+      uint32_t v = x.v[w] >> s;
+      if (s > 3 && w + 1 < 8) v |= x.v[w + 1] << (32 - s);
+      t.l[i] = (i < 8) ? (v & MASK) : v;
+    }
+    return t;
+  }
+
+  // The limbs of x << SH for a canonical x < p (SH <= 3): the same slicing with every bit offset moved down by SH.
+  // Limbs 0..7 < 2^29 exactly, value = x 2^SH < 2^SH p.  With R = 2^256 outside and rho = 2^261 inside, the limbs of
+  // E << 3 and E << 2 stand for x / 4 and y / 8: the coordinates of the same point on the isomorphic curve E'
+  // (bn254_ec29.hip.h), which is how accumulate_kernel reads the caller's bases in place.
+  template <int SH>
+  MSM_HD static fe29 unpack256_shl(const u256& x) {
+    static_assert(SH >= 0 && SH <= 3, "the top limb holds 232 - SH .. 255 of x");
+    fe29 t;
+    t.l[0] = (x.v[0] << SH) & MASK;
+    MSM_UNROLL for (int i = 1; i < 9; ++i) {
+      const int bit = 29 * i - SH;
       const int w = bit >> 5, s = bit & 31;
       uint32_t v = x.v[w] >> s;
       if (s > 3 && w + 1 < 8) v |= x.v[w + 1] << (32 - s);

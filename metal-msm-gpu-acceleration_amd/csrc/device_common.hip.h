@@ -5,7 +5,10 @@
 // slots per window; slot i holds the points whose digit magnitude is i + 1):
 //
 //   front stream (k_sort.hip, k_misc.hip)
-//   convert_bases_kernel  bases (affine 64 B, Montgomery R = 2^256) -> bases29 (64 B packed, internal domain 2^261)
+//   convert_bases_kernel  bases (affine 64 B, Montgomery R = 2^256) -> bases29 (64 B packed, internal domain 2^261);
+//                         only where the packed record is kept or the caller's array cannot be gathered later (prepared
+//                         bases, tables, the bases cache, host slices of a batch) -- otherwise accumulate_kernel reads
+//                         the external records in place, as the image of the points on E' (bn254_ec29.hip.h)
 //   digits_kernel         scalars (32 B, Montgomery or canonical) -> digits[W][n] (u16 = sign << 15 | magnitude)
 //   coarse_hist_kernel    digits -> coarse_cnt[W][Q][2^hb]   LDS histogram of the high slot bits per (chunk, window)
 //   coarse_prefix_kernel  coarse_cnt -> region_start[W][2^hb + 1], coarse_cnt := first position per (chunk, region)
@@ -16,7 +19,7 @@
 //   size_hist/scan/scatter  work items counting-sorted by descending length -> order[], list of split buckets
 //
 //   main stream (k_accumulate.hip)
-//   accumulate_kernel     one lane per work item: sorted + bases29 -> buckets[W][nb] (XYZZ, 144 B) or
+//   accumulate_kernel     one lane per work item: sorted + bases (external in place / bases29) -> buckets[W][nb] (XYZZ, 144 B) or
 //                         item_partials for split buckets                                      <- dominant
 //
 //   reduce stream (k_accumulate.hip, k_reduce.hip)

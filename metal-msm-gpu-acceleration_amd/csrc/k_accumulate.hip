@@ -32,9 +32,29 @@ namespace msm_amd {
 // (it needs 180): with several streams in flight this leaves register file and wave slots for the sort / reduce kernels
 // of the neighbouring instances, which otherwise cannot be placed until the whole accumulate grid has drained (measured
 // in round 1: a 1024-thread plan_kernel workgroup waited 1.4 ms behind 3-wave accumulate waves).
-template <bool PIN>
+//
+// The record kind is a compile-time parameter.  PackedBases: the 64-byte AffPacked record of the internal domain
+// (MSM_AMD_POINT_PREPARED, the tables, the bases cache).  ExtBases: the caller's own 64-byte external record, gathered in
+// place and sliced into the coordinates of the same point on the isomorphic curve E' (bn254_ec29.hip.h) -- no
+// conversion pass, no packed copy; the host maps the instance's result back.  The two differ in the unpacking, the
+// identity test (one word / all sixteen words zero), the lazy negation of y and the constants of the affine start.
+struct PackedBases {
+  using Rec = AffPacked;
+  static constexpr bool kIso = false;
+  static __device__ __forceinline__ bool is_identity(const Rec& r) { return affpacked_is_identity(r); }
+  static __device__ __forceinline__ AffI unpack(const Rec& r) { return affi_unpack_finite(r); }
+  static __device__ __forceinline__ fe29 neg_y(const fe29& y) { return Fq29::neg_wide(y); }
+};
+struct ExtBases {
+  using Rec = Affine;
+  static constexpr bool kIso = true;
+  static __device__ __forceinline__ bool is_identity(const Rec& r) { return affine_words_zero(r); }
+  static __device__ __forceinline__ AffI unpack(const Rec& r) { return affi_from_ext_iso(r); }
+  static __device__ __forceinline__ fe29 neg_y(const fe29& y) { return neg_wide_iso(y); }
+};
+template <bool PIN, class B>
 __device__ __forceinline__ void
-accumulate_item(const uint32_t slot, const AffPacked* __restrict__ bases, const uint32_t* __restrict__ sorted,
+accumulate_item(const uint32_t slot, const typename B::Rec* __restrict__ bases, const uint32_t* __restrict__ sorted,
                    const uint32_t* __restrict__ bucket_start, const uint32_t* __restrict__ bucket_size,
                    const uint32_t* __restrict__ item_start, const uint32_t* __restrict__ win_base,
                    const uint2* __restrict__ order, const PlanCounters* __restrict__ counters, uint32_t n,
@@ -53,7 +73,8 @@ accumulate_item(const uint32_t slot, const AffPacked* __restrict__ bases, const 
   uint32_t state = kEmpty;
   uint32_t cur_idx = idx[0];
   uint32_t next_idx = cnt > 1 ? idx[1] : 0u;
-  AffPacked pre;
+  using Rec = typename B::Rec;
+  Rec pre;
   pre.x = load_u256(&bases[cur_idx & 0x7FFFFFFFu].x);
   pre.y = load_u256(&bases[cur_idx & 0x7FFFFFFFu].y);
   uint32_t i = 0;
@@ -62,23 +83,23 @@ accumulate_item(const uint32_t slot, const AffPacked* __restrict__ bases, const 
   // register form of a gathered record: unpacked, y negated for a negative digit (-y without the carry round, limbs
   // < 2^30.5: y only ever multiplies the normalised ZZZ1 or enters the lifted subtraction of pti_mmadd; bounds:
   // tools/fq29_bounds.py)
-  auto signed_point = [](const AffPacked& rec, uint32_t entry) {
-    AffI r = affi_unpack_finite(rec);
+  auto signed_point = [](const Rec& rec, uint32_t entry) {
+    AffI r = B::unpack(rec);
     const bool negate = (entry >> 31) != 0;
-    const fe29 ny = Fq29::neg_wide(r.y);
+    const fe29 ny = B::neg_y(r.y);
 #pragma unroll
     for (int l = 0; l < 9; ++l) r.y.l[l] = negate ? ny.l[l] : r.y.l[l];
     return r;
   };
   // the exceptional case q == p (a doubling) needs q after its registers have been given away: gathered again
   auto regather = [&](uint32_t entry) {
-    AffPacked rec;
+    Rec rec;
     rec.x = load_u256(&bases[entry & 0x7FFFFFFFu].x);
     rec.y = load_u256(&bases[entry & 0x7FFFFFFFu].y);
     return signed_point(rec, entry);
   };
   auto take = [&](AffI& cur) -> bool {
-    const bool ident = affpacked_is_identity(pre);
+    const bool ident = B::is_identity(pre);
     cur = signed_point(pre, cur_idx);
     // the unpacking above is done before the registers of `pre` are loaded again (the statement ties the 18 limbs)
     asm volatile("" : "+v"(cur.x.l[0]), "+v"(cur.x.l[1]), "+v"(cur.x.l[2]), "+v"(cur.x.l[3]), "+v"(cur.x.l[4]),
@@ -105,8 +126,8 @@ accumulate_item(const uint32_t slot, const AffPacked* __restrict__ bases, const 
         MSM_ISA_MARK("begin affine_start");
         bool vanished = false;
         fe29 P, R;
-        pti_mmadd_head(acc.x, acc.y, cur.x, cur.y, P, R);
-        acc = pti_mmadd_tail(acc.x, acc.y, P, R, [&]() { return regather(this_idx); }, vanished);
+        pti_mmadd_head<B::kIso>(acc.x, acc.y, cur.x, cur.y, P, R);
+        acc = pti_mmadd_tail<B::kIso>(acc.x, acc.y, P, R, [&]() { return regather(this_idx); }, vanished);
         state = vanished ? (uint32_t)kEmpty : (uint32_t)kMany;
         MSM_ISA_MARK("end");
       } else {
@@ -139,17 +160,18 @@ accumulate_item(const uint32_t slot, const AffPacked* __restrict__ bases, const 
   }
 }
 
-#define MSM_ACC_PARAMS const AffPacked* __restrict__ bases, const uint32_t* __restrict__ sorted,                       \
+#define MSM_ACC_PARAMS_OF(Rec) const Rec* __restrict__ bases, const uint32_t* __restrict__ sorted,                    \
                        const uint32_t* __restrict__ bucket_start, const uint32_t* __restrict__ bucket_size,           \
                        const uint32_t* __restrict__ item_start, const uint32_t* __restrict__ win_base,                \
                        const uint2* __restrict__ order, const PlanCounters* __restrict__ counters, uint32_t n,        \
                        uint32_t lb, uint32_t CH, PtI* __restrict__ buckets, PtI* __restrict__ partials
+#define MSM_ACC_PARAMS MSM_ACC_PARAMS_OF(AffPacked)
 #define MSM_ACC_FWD bases, sorted, bucket_start, bucket_size, item_start, win_base, order, counters, n, lb, CH, buckets, partials
-// accumulate_kernel<true>: the shipped kernel (two waves per SIMD, pinned).  accumulate_kernel<false>: the same body
-// without the pin (MSM_AMD_LOW_OCC=0; it needs 180 VGPRs, so it is a two-wave kernel too).
-template <bool PIN>
-__global__ void __launch_bounds__(64) accumulate_kernel(MSM_ACC_PARAMS) {
-  accumulate_item<PIN>(blockIdx.x * blockDim.x + threadIdx.x, MSM_ACC_FWD);
+// accumulate_kernel<true, B>: the shipped kernel (two waves per SIMD, pinned).  accumulate_kernel<false, B>: the same
+// body without the pin (MSM_AMD_LOW_OCC=0; it needs 180 VGPRs, so it is a two-wave kernel too).
+template <bool PIN, class B>
+__global__ void __launch_bounds__(64) accumulate_kernel(MSM_ACC_PARAMS_OF(typename B::Rec)) {
+  accumulate_item<PIN, B>(blockIdx.x * blockDim.x + threadIdx.x, MSM_ACC_FWD);
 }
 // Other builds of this kernel -- the single-loop shape of rounds 1-4, three waves per SIMD, the register-lean
 // product-scanning form at four, the compiler's column form at four with Y / ZZ / ZZZ parked in LDS, the hand-allocated
@@ -183,6 +205,7 @@ combine_big_kernel(const uint32_t* __restrict__ big_list, const PlanCounters* __
 // variant: 0 = three waves per SIMD (no prefetch), 1 = two waves per SIMD (register pin, prefetch), 2 = register-lean
 // (four waves per SIMD).  lds_bytes > 0 caps the resident workgroups per CU through the LDS allocation (160 KiB per
 // CU: 13 KiB per 64-lane workgroup = 12 waves per CU = 3 per SIMD), leaving register file for the other streams.
+// p.on_iso: bases_any is the caller's external Affine array, read in place (shipped kernel only).
 void launch_accumulate(hipStream_t st, const Plan& p, const void* bases_any, int wide, const SortBuffers& b, PtI* buckets,
                        PtI* partials, int variant, uint32_t lds_bytes, hipEvent_t before_kernel, hipEvent_t after_kernel) {
   if (before_kernel) (void)hipEventRecord(before_kernel, st);
@@ -227,10 +250,21 @@ void launch_accumulate(hipStream_t st, const Plan& p, const void* bases_any, int
     hipLaunchKernelGGL(accumulate_kernel_r4, grid, block, lds_bytes, st, MSM_ACC_ARGS);
   } else
 #endif
-  if (variant == 1) {
-    hipLaunchKernelGGL(accumulate_kernel<true>, grid, block, lds_bytes, st, MSM_ACC_ARGS);
+  if (p.on_iso) {
+    const Affine* ext = (const Affine*)bases_any;
+#define MSM_ACC_ARGS_EXT ext, (const uint32_t*)b.sorted, (const uint32_t*)b.bucket_start, (const uint32_t*)b.bucket_size, \
+                         (const uint32_t*)b.item_start, (const uint32_t*)b.win_items, (const uint2*)b.order,             \
+                         (const PlanCounters*)b.counters, p.n, p.lb, p.CH, buckets, partials
+    if (variant == 1) {
+      hipLaunchKernelGGL((accumulate_kernel<true, ExtBases>), grid, block, lds_bytes, st, MSM_ACC_ARGS_EXT);
+    } else {
+      hipLaunchKernelGGL((accumulate_kernel<false, ExtBases>), grid, block, lds_bytes, st, MSM_ACC_ARGS_EXT);
+    }
+#undef MSM_ACC_ARGS_EXT
+  } else if (variant == 1) {
+    hipLaunchKernelGGL((accumulate_kernel<true, PackedBases>), grid, block, lds_bytes, st, MSM_ACC_ARGS);
   } else {
-    hipLaunchKernelGGL(accumulate_kernel<false>, grid, block, lds_bytes, st, MSM_ACC_ARGS);
+    hipLaunchKernelGGL((accumulate_kernel<false, PackedBases>), grid, block, lds_bytes, st, MSM_ACC_ARGS);
   }
 #undef MSM_ACC_ARGS
   if (after_kernel) (void)hipEventRecord(after_kernel, st);

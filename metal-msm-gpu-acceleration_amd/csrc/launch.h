@@ -35,6 +35,9 @@ struct Plan {
   uint32_t rb_threads;        // reduce: threads per bit-subset sum (0 = by the sum's length; 64 for pipelined instances)
   uint32_t red_group;         // reduce: additions per lane and level of the row / column sums (kReduceGroupMin..16)
   size_t total_buckets, total_segs, partial_count, max_items;
+  bool on_iso;                // G1: accumulate gathers the caller's external bases in place, so every point of the
+                              // instance (buckets, partials, the Horner sum) is the image on the isomorphic curve E'
+                              // (bn254_ec29.hip.h) until the host maps it back (msm_host.hip: iso_to_e)
 };
 
 // Device-side bookkeeping words written by the planning kernels.
@@ -81,7 +84,7 @@ void launch_be32_to_le(hipStream_t st, const uint32_t* in, size_t words, uint32_
 void launch_ark_affine_to_affine(hipStream_t st, const uint8_t* in, uint32_t n, Affine* out);
 
 // k_accumulate.hip
-// bases: AffPacked records; wide != 0 (experiments build, variant 8): AffWide records
+// bases: AffPacked records; p.on_iso: the caller's Affine records; wide != 0 (experiments build, variant 8): AffWide
 void launch_accumulate(hipStream_t st, const Plan& p, const void* bases, int wide, const SortBuffers& b, PtI* buckets,
                        PtI* partials, int variant, uint32_t lds_bytes, hipEvent_t before_kernel, hipEvent_t after_kernel);
 

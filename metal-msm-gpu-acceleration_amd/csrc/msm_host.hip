@@ -300,6 +300,8 @@ struct msm_amd_ctx {
   };
   std::vector<CacheReserve> cache_reserve;
   AffPacked* convert_into = nullptr;   // enqueue_msm writes the converted bases of the next instance here (a cache fill)
+  bool staging_points = false;         // the next instance's points sit in a staging set that is uploaded into again once
+                                       // its digits are done (run_batch_host): accumulate cannot gather them in place
   // Device buffers replaced by bigger ones while work was in flight.  hipFree synchronises the whole device: inside
   // a submit it would stall the pipeline and, on a device that does not answer, block without bound.  They are
   // freed when the ctx has nothing in flight (reap_graveyard) or at msm_amd_destroy.
@@ -672,6 +674,14 @@ void jac_to_be32(const Jacobian& p, uint32_t* l) {
 
 // Normalise to z = R mod p (or the canonical identity (1,1,0) in Montgomery form).
 Jacobian normalise(const Jacobian& p) { return h64::store(h64::normalise(h64::load(p))); }
+
+// E' -> E for a Jacobian point (Plan::on_iso): x = 4 x', y = 8 y' is Z <- Z / 2.  The identity (Z = 0) stays.
+Jacobian iso_to_e(const Jacobian& q) {
+  static const h64::Fe half = h64::inv(h64::dbl(h64::one()));
+  h64::Jac j = h64::load(q);
+  j.z = h64::mul(j.z, half);
+  return h64::store(j);
+}
 
 // Window value  W_w = partial[w][lb] + sum_k 2^k * partial[w][k]  (total; bit sums of the column sums for k < L, of the
 // row sums -- already offset by L -- for L <= k < lb; see k_reduce.hip) and the final Horner sum_w 2^(c*w) W_w, fused
@@ -1146,10 +1156,16 @@ int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_l
     if (n != tb->n) return fail(ctx, MSM_AMD_INPUT_ERROR, "n differs from the number of points the tables hold");
   }
   const uint32_t c = tb ? tb->c : (ctx->forced_window ? ctx->forced_window : (lone ? auto_window_lone(n) : auto_window(n)));
-  const Plan p = instance_plan(n, c, tb ? tb->W : 0, lone);
-  *plan_out = p;
+  Plan p = instance_plan(n, c, tb ? tb->W : 0, lone);
   const bool prepared = point_layout == MSM_AMD_POINT_PREPARED || tb != nullptr;
   AffPacked* const fill = prepared ? nullptr : ctx->convert_into;   // bases cache fill: convert straight into the entry
+  // Bases that are not kept (no prepared array, table or cache entry) are not converted: accumulate gathers the external
+  // records in place -- the caller's device array (H2C_AFFINE) or the Affine array convert_points wrote into the
+  // workspace (ark layouts, BE32) -- and the instance runs on E'.  Host slices of msm_amd_msm_batch stay on the
+  // conversion kernel (their staging set is re-used after EV_DIGITS), and so do the experiments build's variant kernels.
+  const bool in_place = !prepared && !fill && !ctx->staging_points && (ctx->acc_variant == 0 || ctx->acc_variant == 1);
+  p.on_iso = in_place;
+  *plan_out = p;
 #if defined(MSM_AMD_EXPERIMENTS)
   // variant 8: bases converted inside this call go into WIDE records (128 B: x, y, -y as limbs)
   const bool wide = !prepared && !fill && ctx->acc_variant == 8;
@@ -1159,7 +1175,8 @@ int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_l
   const size_t base_record = sizeof(AffPacked);
 #endif
   PointStages g;
-  g.bases_bytes = (prepared || fill) ? 0 : p.n * base_record;
+  g.bases_bytes = (prepared || fill || in_place) ? 0 : p.n * base_record;
+  const Affine* ext_bases = nullptr;   // in_place: set by convert_bases, read by accumulate (enqueued after it)
   g.internal_bytes = sizeof(PtI);
   g.ext_bytes = sizeof(Jacobian);
   g.convert_bases = [&](hipStream_t fs) -> int {
@@ -1169,12 +1186,14 @@ int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_l
 #if defined(MSM_AMD_EXPERIMENTS)
     if (wide) launch_convert_bases_wide(fs, pts, p.n, (AffWide*)w.bases29.p);
 #endif
-    if (!prepared && !wide)   // external 8 x u32 -> packed internal domain
+    ext_bases = pts;
+    if (!prepared && !wide && !in_place)   // external 8 x u32 -> packed internal domain
       launch_convert_bases(fs, pts, p.n, fill ? fill : (AffPacked*)w.bases29.p);
     return MSM_AMD_OK;
   };
   g.accumulate = [&](hipStream_t st, const SortBuffers& sb, hipEvent_t before, hipEvent_t after) {
-    const void* bases = tb ? tb->d_tables : (prepared ? d_points : (fill ? (const void*)fill : w.bases29.p));
+    const void* bases = tb ? tb->d_tables
+                           : (prepared ? d_points : (fill ? (const void*)fill : (in_place ? (const void*)ext_bases : w.bases29.p)));
     launch_accumulate(st, p, bases, wide ? 1 : 0, sb, (PtI*)w.buckets.p, (PtI*)w.item_partials.p, ctx->acc_variant,
                       ctx->acc_lds, before, after);
   };
@@ -1318,7 +1337,9 @@ int wait_batch(msm_amd_ctx* ctx, int ticket, bool internal = true) {
         continue;
       }
       const auto t0 = std::chrono::steady_clock::now();
-      const Jacobian res = normalise(host_combine((const Jacobian*)s.h_partial, B.plans[i]));
+      // the one place every consumer of a G1 instance goes through: a sum computed on E' comes back to E here
+      const Jacobian sum = host_combine((const Jacobian*)s.h_partial, B.plans[i]);
+      const Jacobian res = normalise(B.plans[i].on_iso ? iso_to_e(sum) : sum);
       done[i].final_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
       std::memcpy((uint8_t*)B.out + i * 96, &res, 96);
     }
@@ -1966,9 +1987,11 @@ int run_batch_host(msm_amd_ctx* ctx, int scalar_layout, int point_layout, size_t
     const void* dp = dev_points ? points[i] : (cached[i] ? cached[i] : ((i & 1) ? ctx->scratch_c2 : ctx->scratch_c).p);
     int ticket = -1;
     ctx->convert_into = fill[i];
+    ctx->staging_points = !dev_points && !cached[i];
     rc = submit_batch_device(ctx, scalar_layout, cached[i] ? (int)MSM_AMD_POINT_PREPARED : point_layout, 1, &ds, &dp, &n[i],
                              (uint8_t*)out + i * 96, &ticket, lone ? 1 : 0);
     ctx->convert_into = nullptr;
+    ctx->staging_points = false;
     if (rc) return bail_upload(rc);
     tickets[i] = ticket;
   }
@@ -3078,7 +3101,8 @@ int msm_amd_test_op_host(int op, const uint32_t* a, const uint32_t* b, uint32_t*
 // Raw-limb test ops: the internal limbs pass through unchanged (no from_ext, no reversal, no normalisation).
 static bool test_op_raw_args(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
   return a && b && out && count > 0 && count <= (1u << 24) && op >= 0 &&
-         (op < kRawOpCount || (op >= kRawWideFirst && op < kRawWideFirst + kRawWideCount) || op == MSM_AMD_RAW_FE_SQRT);
+         (op < kRawOpCount || (op >= kRawWideFirst && op < kRawWideFirst + kRawWideCount) || op == MSM_AMD_RAW_FE_SQRT ||
+          op == MSM_AMD_RAW_BASES_IN_PLACE);
 }
 
 int msm_amd_test_op_raw(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
@@ -3202,8 +3226,9 @@ struct TapPoints {
   const DeviceBuf* buckets;   // [W][nb] internal points
   const DeviceBuf* partial;   // [W][lb + 1] external points
   size_t bucket_bytes, partial_bytes, out_bytes;   // record sizes: internal point, external point, tap output
-  void (*bucket_out)(const uint8_t* rec, uint8_t* out);
-  void (*partial_out)(const uint8_t* rec, uint8_t* out);
+  // on_iso: the tapped plan ran on E' (Plan::on_iso) and the record is mapped back to E on its way out
+  void (*bucket_out)(const uint8_t* rec, uint8_t* out, bool on_iso);
+  void (*partial_out)(const uint8_t* rec, uint8_t* out, bool on_iso);
 };
 
 // One buffer of a finished call: `w` holds the index and count buffers (the same formats for G1 and G2), `pts` the
@@ -3257,20 +3282,21 @@ static int tap_stage_copy(msm_amd_ctx* ctx, const Workspace& w, const Plan& p, c
   const bool bk = which == MSM_AMD_STAGE_BUCKETS;
   const size_t rec = bk ? pts.bucket_bytes : pts.partial_bytes;
   for (size_t i = 0; i < records; ++i)
-    (bk ? pts.bucket_out : pts.partial_out)(h.data() + i * rec, (uint8_t*)out + i * pts.out_bytes);
+    (bk ? pts.bucket_out : pts.partial_out)(h.data() + i * rec, (uint8_t*)out + i * pts.out_bytes, p.on_iso);
   return MSM_AMD_OK;
 }
 
 // G1 point buffers leave in the wire layout of the stage entry points: Jacobian, 3 x 8 u32 most significant first
-static void tap_g1_bucket(const uint8_t* rec, uint8_t* out) {
+static void tap_g1_bucket(const uint8_t* rec, uint8_t* out, bool on_iso) {
   PtI q;
   std::memcpy(&q, rec, sizeof q);
-  jac_to_be32(pti_to_ext(q), (uint32_t*)out);
+  const Jacobian j = pti_to_ext(q);
+  jac_to_be32(on_iso ? iso_to_e(j) : j, (uint32_t*)out);
 }
-static void tap_g1_partial(const uint8_t* rec, uint8_t* out) {
+static void tap_g1_partial(const uint8_t* rec, uint8_t* out, bool on_iso) {
   Jacobian q;
   std::memcpy(&q, rec, sizeof q);
-  jac_to_be32(q, (uint32_t*)out);
+  jac_to_be32(on_iso ? iso_to_e(q) : q, (uint32_t*)out);
 }
 
 int msm_amd_test_stage_copy(msm_amd_ctx* ctx, uint32_t j, int which, void* out, size_t* bytes) {
@@ -3579,13 +3605,13 @@ int msm_amd_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, con
 static const char* const kNoG2Plan = "G2 stage tap: no G2 MSM of this ctx has succeeded last";
 
 // G2 point buffers leave in the result form of msm_amd_msm_g2 (192 B Jacobian, Montgomery LE; identity: z all zero)
-static void tap_g2_bucket(const uint8_t* rec, uint8_t* out) {
+static void tap_g2_bucket(const uint8_t* rec, uint8_t* out, bool) {
   PtI2 q;
   std::memcpy(&q, rec, sizeof q);
   const Jacobian2 e = pt2_to_ext(q);
   std::memcpy(out, &e, sizeof e);
 }
-static void tap_g2_partial(const uint8_t* rec, uint8_t* out) { std::memcpy(out, rec, sizeof(Jacobian2)); }
+static void tap_g2_partial(const uint8_t* rec, uint8_t* out, bool) { std::memcpy(out, rec, sizeof(Jacobian2)); }
 
 int msm_amd_test_g2_last_plan(msm_amd_ctx* ctx, uint32_t* out, size_t count) {
   if (!ctx || !out || count < MSM_AMD_TEST_PLAN_WORDS)

@@ -242,6 +242,41 @@ MSM_HD void run_test_op_raw(int op, const uint32_t* a_all, const uint32_t* b_all
     case 34:                                                                      // FE_MUL2_WIDE
       raw_put_fe(r, Fq29::mul2w_np(pin_limbs(a0), pin_limbs(a1), pin_limbs(b0), pin_limbs(b1)));
       break;
+    case 40: {   // BASES_IN_PLACE: external records as accumulate_kernel<.., ExtBases> takes them (the image on E')
+      // a[0..15], a[16..31], b[1..16]: three external records (x, y: 8 + 8 words); a[32]: bit k = negate record k;
+      // b[0]: 0 = unpack record 0, 1 = affine start rec0 + rec1, 2 = (rec0 + rec1) + rec2 by the mixed addition
+      Affine e[3];
+      MSM_UNROLL for (int i = 0; i < 8; ++i) {
+        e[0].x.v[i] = a[i];      e[0].y.v[i] = a[8 + i];
+        e[1].x.v[i] = a[16 + i]; e[1].y.v[i] = a[24 + i];
+        e[2].x.v[i] = b[1 + i];  e[2].y.v[i] = b[9 + i];
+      }
+      AffI q[3];
+      MSM_UNROLL for (int k = 0; k < 3; ++k) {
+        q[k] = affi_from_ext_iso(e[k]);
+        if ((a[32] >> k) & 1u) q[k].y = neg_wide_iso(q[k].y);
+      }
+      if (b[0] == 0) {
+        const AffI u = affi_from_ext_iso(e[0]);
+        raw_put_fe(r, u.x);
+        raw_put_fe(r + 9, u.y);
+        r[18] = affine_words_zero(e[0]) ? 1u : 0u;
+        raw_put_fe(r + 19, neg_wide_iso(u.y));
+        break;
+      }
+      const PtI one = pti_from_affi(q[0]);
+      fe29 P, R;
+      pti_mmadd_head<true>(one.x, one.y, q[1].x, q[1].y, P, R);
+      PtI acc = pti_mmadd_tail<true>(one.x, one.y, P, R, [&]() { return q[1]; }, vanished);
+      if (b[0] == 2 && !vanished) {
+        fe29 U2, S2;
+        pti_madd_head(acc, q[2].x, q[2].y, U2, S2);
+        acc = pti_madd_tail(acc, U2, S2, [&]() { return q[2]; }, vanished);
+      }
+      raw_put_pt(r, acc);
+      r[36] = vanished ? 1u : 0u;
+      break;
+    }
   }
   MSM_UNROLL for (int i = 0; i < kRawOutWords; ++i) out[i] = r[i];
 }

@@ -31,7 +31,7 @@ def _table(name, rows=1):
 PL = _table("p")[0]
 assert sum(l << (29 * i) for i, l in enumerate(PL)) == P
 KC = _table("kc")
-KNAMES = ["K4E30", "K8E30", "K8E31", "K16E30", "K16E31"]
+KNAMES = ["K4E30", "K8E30", "K8E31", "K16E30", "K16E31", "K12E30"]
 KMULT = {}
 for name, limbs in zip(KNAMES, KC):
     v = sum(l << (29 * i) for i, l in enumerate(limbs))
@@ -162,33 +162,90 @@ def neg(a, name):
     return norm(sub("K4E30", zero(), a, name), name)
 
 
-def maybe_zero(a, bound):
-    if a.val >= bound:
-        fail(f"maybe_zero({a.name}, {bound}): value bound {a.val:.2f}p is not below the filter's {bound}")
+# the one-limb zero filters: the bound each site needs (the smallest integer above the value bound of its operand) and
+# the constant the header gives it (kZeroFilter* in bn254_ec29.hip.h); main() prints both
+EC_HDR = os.path.join(ROOT, "metal-msm-gpu-acceleration_amd", "csrc", "bn254_ec29.hip.h")
+FILTERS = {m.group(1): int(m.group(2))
+           for m in re.finditer(r"constexpr uint32_t (kZeroFilter\w+) = (\d+);", open(EC_HDR).read())}
+derived_filters = {}
 
 
-# the invariant of every stored / loop-carried point (multiples of p); pti_mmadd sets it: ZZ3 = P^2 with P < 17.1 p
-# gives 2.72 p, X3 = R^2 - ... + 8 p with R < 12.1 p gives 9.86 p
-INV_X, INV_Y, INV_ZZ, INV_ZZZ = 10.0, 6.0, 2.8, 2.0
+def maybe_zero(a, site):
+    need = int(a.val) + 1
+    derived_filters[site] = max(need, derived_filters.get(site, 0))
+    bound = FILTERS.get(site)
+    if bound is None:
+        fail(f"maybe_zero({a.name}, {site}): the header has no constant {site}")
+    elif a.val >= bound:
+        fail(f"maybe_zero({a.name}, {site} = {bound}): value bound {a.val:.2f}p is not below the filter's {bound}")
 
 
-def check_point(x, y, zz, zzz, where):
-    for f, lim in ((x, INV_X), (y, INV_Y), (zz, INV_ZZ), (zzz, INV_ZZZ)):
+# the invariant of every stored / loop-carried point (multiples of p).  On E (packed bases) pti_mmadd sets it: ZZ3 = P^2
+# with P < 17.1 p gives 2.72 p, X3 = R^2 - ... + 8 p with R < 12.1 p gives 9.86 p.  On E' (the caller's bases read in
+# place: x = E << 3 < 8 p, y = E << 2 < 4 p, -y = 8 p - y) P and R of the affine start are below 24.1 p, which gives
+# ZZ3 < 4.5 p and X3 < 12.5 p, and a bucket of ONE base stores x < 8 p, |y| <= 8 p as they were gathered.
+class Inv:
+    def __init__(self, name, x, y, zz, zzz):
+        self.name, self.x, self.y, self.zz, self.zzz = name, x, y, zz, zzz
+
+
+INV_E = Inv("E", 10.0, 6.0, 2.8, 2.0)
+INV_ISO = Inv("E'", 11.5, 8.0, 3.4, 2.0)
+INV_X, INV_Y, INV_ZZ, INV_ZZZ = INV_E.x, INV_E.y, INV_E.zz, INV_E.zzz
+
+
+def check_point(x, y, zz, zzz, where, inv=INV_E):
+    for f, lim in ((x, inv.x), (y, inv.y), (zz, inv.zz), (zzz, inv.zzz)):
         if f.val > lim:
             fail(f"{where}: {f.name} may reach {f.val:.2f}p, the invariant says < {lim}p")
         if max(f.mx[:8]) > MASK + 8:
             fail(f"{where}: {f.name} leaves limbs above 2^29 + 8")
 
 
-def point_invariant():
+def point_invariant(inv=INV_E):
     def coord(name, val):
         return Fe([MASK + 8] * 8 + [top_from_value(val) + 1], val, name)
-    return coord("X1", INV_X), coord("Y1", INV_Y), coord("ZZ1", INV_ZZ), coord("ZZZ1", INV_ZZZ)
+    return coord("X1", inv.x), coord("Y1", inv.y), coord("ZZ1", inv.zz), coord("ZZZ1", inv.zzz)
+
+
+# ---- the bases as the accumulate kernel sees them -----------------------------------------------------------
+class Bases:
+    """packed: canonical x, y < p of the internal domain (AffPacked), -y = 4 p - y.
+    in place: the caller's canonical E = x R mod p sliced out of E << 3 (x) and E << 2 (y) -- Fq29::unpack256_shl -- the
+    coordinates of the image on E': y'^2 = x'^3 + 3/64; exact 29-bit limbs, values < 8 p and < 4 p, -y = 8 p - y (the
+    top limb of a y just below 4 p is above the borrowed top limb of K4E30)."""
+
+    def __init__(self, iso):
+        self.iso = iso
+        self.inv = INV_ISO if iso else INV_E
+        self.tag = " (E')" if iso else ""
+        self.neg_sel = "K8E30" if iso else "K4E30"
+        self.start_sel = ("K12E30", "K12E30") if iso else ("K16E30", "K8E30")   # pti_mmadd_head: P, R
+        self.filter_mmadd = "kZeroFilterMmaddIso" if iso else "kZeroFilterMmadd"
+
+    def x(self, name):
+        return Fe([MASK] * 8 + [(8 * (P - 1)) >> 232], 8.0, name) if self.iso else canonical(name)
+
+    def y(self, name):
+        return Fe([MASK] * 8 + [(4 * (P - 1)) >> 232], 4.0, name) if self.iso else canonical(name)
+
+    def negated_y(self, name="+-y2"):
+        """accumulate_kernel: cur.y = negate ? -y : y  (no carry round)"""
+        qy = self.y(name[2:])
+        n = sub(self.neg_sel, zero(), qy, "-y")
+        return Fe([max(a, b) for a, b in zip(n.mx, qy.mx)], max(n.val, qy.val), name)
+
+    def stored_y(self, name="+-y1"):
+        """pti_from_affi: the y of a point that becomes an accumulator is normalised"""
+        return norm(self.negated_y(name), name)
+
+
+PACKED, IN_PLACE = Bases(False), Bases(True)
 
 
 # ---- the formulas of bn254_ec29.hip.h ----------------------------------------------------------------------
 WD = True   # the point additions' products use wide quotient digits where the header's _np forms do
-def pti_double(px, py, pzz, pzzz, where):
+def pti_double(px, py, pzz, pzzz, where, inv=INV_E):
     U = add(py, py, "U")
     V = sqr(U, "V")
     W = mul(U, V, "W")
@@ -201,11 +258,11 @@ def pti_double(px, py, pzz, pzzz, where):
     Y3 = norm(sub("K4E30", mul(M, T, "MT"), mul(W, py, "WY"), "Y3"), "Y3")
     ZZ3 = mul(V, pzz, "ZZ3")
     ZZZ3 = mul(W, pzzz, "ZZZ3")
-    check_point(X3, Y3, ZZ3, ZZZ3, where + " (doubling)")
+    check_point(X3, Y3, ZZ3, ZZZ3, where + " (doubling)", inv)
 
 
-def neg_wide(a, name):
-    return sub("K4E30", zero(), a, name)
+def neg_wide(a, name, sel="K4E30"):
+    return sub(sel, zero(), a, name)
 
 
 def negated_base_y(qy, name="+-y2"):
@@ -219,14 +276,23 @@ def stored_base_y(qy, name="+-y1"):
     return norm(negated_base_y(qy, name), name)
 
 
-def pti_madd(where="pti_madd"):
-    px, py, pzz, pzzz = point_invariant()
-    qx, qy = canonical("x2"), negated_base_y(canonical("y2"))
+def general_point(inv):
+    """the accumulator of the mixed addition: a sum of at least two bases (pti_mmadd, pti_madd or pti_double output),
+    whose Y is below 6 p on either curve -- only a lone base (pti_from_affi) carries the 8 p of a negated y on E'"""
+    px, py, pzz, pzzz = point_invariant(inv)
+    y6 = point_invariant(INV_E)[1]
+    return px, y6, pzz, pzzz
+
+
+def pti_madd(bases=PACKED):
+    where = "pti_madd" + bases.tag
+    px, py, pzz, pzzz = general_point(bases.inv)
+    qx, qy = bases.x("x2"), bases.negated_y()
     U2 = mul(qx, pzz, "U2", WD)
     S2 = mul(qy, pzzz, "S2", WD)
     Pd = norm(sub("K16E30", U2, px, "P"), "P")
     R = norm(sub("K8E30", S2, py, "R"), "R")
-    maybe_zero(Pd, 18)
+    maybe_zero(Pd, "kZeroFilterMadd")
     PP = sqr(Pd, "PP", WD)
     PPP = mul(Pd, PP, "PPP", WD)
     Q = mul(px, PP, "Q", WD)
@@ -236,18 +302,22 @@ def pti_madd(where="pti_madd"):
     Y3 = mul2(R, T, py, neg_wide(PPP, "-PPP"), "Y3")          # mul2_np: masked digits
     ZZ3 = mul(pzz, PP, "ZZ3", WD)
     ZZZ3 = mul(pzzz, PPP, "ZZZ3", WD)
-    check_point(X3, Y3, ZZ3, ZZZ3, where)
+    check_point(X3, Y3, ZZ3, ZZZ3, where, bases.inv)
+    if Y3.val > INV_E.y:
+        fail(f"{where}: Y3 may reach {Y3.val:.2f}p, the accumulator of the next mixed addition is taken below {INV_E.y}p")
     one = Fe([MASK] * 8 + [P >> 232], 1.0, "one")           # the doubling path restarts from pti_from_affi(q)
-    pti_double(qx, stored_base_y(canonical("y2")), one, one, where)
+    pti_double(qx, bases.stored_y(), one, one, where, INV_E)   # a doubling's outputs obey E's figures on either curve
+    return {"U2": U2, "P": Pd, "R": R, "X3": X3, "Y3": Y3, "ZZ3": ZZ3, "ZZZ3": ZZZ3}
 
 
-def pti_mmadd(where="pti_mmadd"):
-    # both operands affine; p = a previous base (its y possibly a lazily negated value < 4 p), q likewise
-    px, py = canonical("x1"), stored_base_y(canonical("y1"))
-    qx, qy = canonical("x2"), negated_base_y(canonical("y2"))
-    Pd = norm(sub("K16E30", qx, px, "P"), "P")
-    R = norm(sub("K8E30", qy, py, "R"), "R")
-    maybe_zero(Pd, 18)
+def pti_mmadd(bases=PACKED):
+    # both operands affine; p = a previous base (its y possibly a lazily negated value), q likewise
+    where = "pti_mmadd" + bases.tag
+    px, py = bases.x("x1"), bases.stored_y()
+    qx, qy = bases.x("x2"), bases.negated_y()
+    Pd = norm(sub(bases.start_sel[0], qx, px, "P"), "P")
+    R = norm(sub(bases.start_sel[1], qy, py, "R"), "R")
+    maybe_zero(Pd, bases.filter_mmadd)
     PP = sqr(Pd, "PP", WD)
     PPP = mul(Pd, PP, "PPP", WD)
     Q = mul(px, PP, "Q", WD)
@@ -255,21 +325,26 @@ def pti_mmadd(where="pti_mmadd"):
     X3 = norm(sub("K8E31", RR, add(PPP, add(Q, Q)), "X3"), "X3")
     T = norm(sub("K16E30", Q, X3, "T"), "T")
     Y3 = mul2(R, T, py, neg_wide(PPP, "-PPP"), "Y3")
-    check_point(X3, Y3, PP, PPP, where)
+    check_point(X3, Y3, PP, PPP, where, bases.inv)
+    if Y3.val > INV_E.y:
+        fail(f"{where}: Y3 may reach {Y3.val:.2f}p, the accumulator of the next mixed addition is taken below {INV_E.y}p")
     one = Fe([MASK] * 8 + [P >> 232], 1.0, "one")
-    pti_double(qx, stored_base_y(canonical("y2")), one, one, where)
+    pti_double(qx, bases.stored_y(), one, one, where, INV_E)
+    return {"P": Pd, "R": R, "X3": X3, "Y3": Y3, "ZZ3": PP, "ZZZ3": PPP}
 
 
-def pti_add_nz(where="pti_add_nz"):
+def pti_add_nz(inv=INV_E):
     """add-2008-s in 11 reductions: P and R as double products with the subtrahend negated (neg_wide), V = ZZ2 PP and
-    Tz = ZZZ2 PPP shared by Q / ZZ3 and Y3 / ZZZ3"""
-    px, py, pzz, pzzz = point_invariant()
-    qx, qy, qzz, qzzz = point_invariant()
+    Tz = ZZZ2 PPP shared by Q / ZZ3 and Y3 / ZZZ3.  The operands are any two points of the invariant: sums, doublings
+    and, through pti_from_affi, lone bases (ZZ = ZZZ = one, inside the same figures)."""
+    where = "pti_add_nz" + ("" if inv is INV_E else " (E')")
+    px, py, pzz, pzzz = point_invariant(inv)
+    qx, qy, qzz, qzzz = point_invariant(inv)
     for f, n in ((qx, "X2"), (qy, "Y2"), (qzz, "ZZ2"), (qzzz, "ZZZ2")):
         f.name = n
     Pd = mul2(qx, pzz, px, neg_wide(qzz, "-ZZ2"), "P", WD)
     R = mul2(qy, pzzz, py, neg_wide(qzzz, "-ZZZ2"), "R", WD)
-    maybe_zero(Pd, 2)
+    maybe_zero(Pd, "kZeroFilterAdd")
     PP = sqr(Pd, "PP", WD)
     PPP = mul(Pd, PP, "PPP", WD)
     V = mul(qzz, PP, "V", WD)
@@ -281,8 +356,9 @@ def pti_add_nz(where="pti_add_nz"):
     Y3 = mul2(R, T, py, neg_wide(Tz, "-Tz"), "Y3")            # mul2_np: masked digits
     ZZ3 = mul(pzz, V, "ZZ3", WD)
     ZZZ3 = mul(pzzz, Tz, "ZZZ3", WD)
-    check_point(X3, Y3, ZZ3, ZZZ3, where)
-    pti_double(px, py, pzz, pzzz, where)
+    check_point(X3, Y3, ZZ3, ZZZ3, where, INV_E)    # a full addition's outputs obey E's figures on either curve
+    pti_double(px, py, pzz, pzzz, where, inv)
+    return {"P": Pd, "R": R, "X3": X3, "Y3": Y3, "ZZ3": ZZ3, "ZZZ3": ZZZ3}
 
 
 def widen(a, b, name):
@@ -345,11 +421,19 @@ def mul_points(group=16, where="mul_normalise"):
             fail(f"load_base: {f.name} may reach {f.val:.2f}p, canonical(., 1) takes values below 2 p")
 
 
-def main():
-    pti_madd()
-    pti_mmadd()
-    pti_add_nz()
+def main(verbose=False):
+    figures = {}
+    for bases in (PACKED, IN_PLACE):
+        figures["pti_madd" + bases.tag] = pti_madd(bases)
+        figures["pti_mmadd" + bases.tag] = pti_mmadd(bases)
+    figures["pti_add_nz"] = pti_add_nz(INV_E)
+    figures["pti_add_nz (E')"] = pti_add_nz(INV_ISO)
     mul_points()
+    for site in sorted(derived_filters):
+        print(f"zero filter {site}: needs {derived_filters[site]}, the header has {FILTERS.get(site)}")
+    if verbose:
+        for where, fs in figures.items():
+            print(where + ": " + ", ".join(f"{k} < {v.val:.2f} p" for k, v in fs.items()))
     if problems:
         print("LIMB BOUNDS VIOLATED:")
         for p in sorted(set(problems)):
@@ -362,4 +446,4 @@ def main():
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(main(verbose="-v" in sys.argv[1:]))

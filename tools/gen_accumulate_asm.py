@@ -42,7 +42,7 @@ def _arr(name):
 
 P_LIMBS = _arr("p")
 ONE = _arr("one_c")
-_kc = re.search(r"kc\(int sel, int i\) \{.*?c\[5\]\[9\] = \{(.*?)\};", _h, re.S).group(1)
+_kc = re.search(r"kc\(int sel, int i\) \{.*?c\[\d\]\[9\] = \{(.*?)\};", _h, re.S).group(1)
 KC = [[int(x.strip().rstrip("u"), 16) for x in row.split(",")] for row in re.findall(r"\{([^{}]*)\}", _kc)]
 K4E30, K8E30, K8E31, K16E30, K16E31 = range(5)
 MASK = 0x1FFFFFFF
@@ -50,7 +50,7 @@ INV = int(re.search(r"INV = (0x[0-9A-Fa-f]+)u", _h).group(1), 16)
 PINV = int(re.search(r"PINV = (0x[0-9A-Fa-f]+)u", _h).group(1), 16)
 P = sum(v << (29 * i) for i, v in enumerate(P_LIMBS))
 RHO = 1 << 261
-assert len(KC) == 5 and all(len(r) == 9 for r in KC) and (INV * P + 1) % (1 << 29) == 0 and (PINV * P) % (1 << 29) == 1
+assert len(KC) >= 5 and all(len(r) == 9 for r in KC) and (INV * P + 1) % (1 << 29) == 0 and (PINV * P) % (1 << 29) == 1
 assert sum(v << (29 * i) for i, v in enumerate(ONE)) == RHO % P
 
 # ---- register map (v0 .. v86) -----------------------------------------------------------------------------------------

@@ -34,6 +34,6 @@ print("PINV29    0x%08X   ( p^-1 mod 2^29)" % (pow(P, -1, 1 << B)))
 print("ONE29    ", [hex(v) for v in limbs(RHO % P)], " rho mod p (internal one)")
 print("C_IN     ", [hex(v) for v in limbs(pow(2, 2 * B * L - 256, P))], " 2^(2*261-256) mod p: ext -> int")
 print("D_OUT    ", [hex(v) for v in limbs(pow(2, 256, P))], " 2^256 mod p: int -> ext")
-for k, e in ((4, 30), (8, 30), (8, 31), (16, 30), (16, 31)):
+for k, e in ((4, 30), (8, 30), (8, 31), (16, 30), (16, 31), (12, 30)):
     print(f"K{k}E{e}  ", [hex(v) for v in lifted(k, e)], f" top-limb headroom {limbs(k*P)[8] - (1 << (e-B))}")
 print("p/rho =", P / RHO, " p>>232 =", P >> 232, hex(P >> 232))

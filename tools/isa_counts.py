@@ -180,11 +180,13 @@ def main(src, dst, reduce_src=None):
         if lean:
             variant = "lean_4_waves"
         elif "accumulate_kernelILb1E" in name:
-            variant = "low_occupancy_2_waves"       # the shipped kernel
+            variant = "low_occupancy_2_waves"       # the shipped kernel, on the caller's bases read in place ...
         elif "accumulate_kernelILb0E" in name:
             variant = "without_register_pin"
         else:
             variant = re.sub(r"^_ZN7msm_amd\d+", "", name)[:40]   # experiments build: keyed by symbol
+        if "PackedBases" in name:
+            variant += "_packed"                    # ... and on packed records (prepared bases, tables, the bases cache)
         try:
             pc = tally(body)
         except StopIteration:
@@ -212,6 +214,10 @@ def main(src, dst, reduce_src=None):
     out["multiplier_per_affine_start"] = k["affine_start"]["multiplier"]
     out["valu_per_mixed_addition"] = k["mixed_addition"]["valu"]
     out["valu_per_affine_start"] = k["affine_start"]["valu"]
+    kp = out["kernels"].get("low_occupancy_2_waves_packed")
+    if kp:
+        out["multiplier_per_mixed_addition_packed"] = kp["mixed_addition"]["multiplier"]
+        out["valu_per_mixed_addition_packed"] = kp["mixed_addition"]["valu"]
     if reduce_src:
         out["sum_groups_kernel"] = full_addition(reduce_src)
         out["multiplier_per_full_addition"] = out["sum_groups_kernel"]["full_addition"]["multiplier"]
