@@ -910,6 +910,67 @@ int msm_amd_ntt_device(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int d
 int msm_amd_host_ntt(int root, uint32_t log_n, int direction, int scalar_layout, const void* shift32, const void* in,
                      void* out, size_t n_vec, int threads);
 
+/* ---- vectors over Fr: element-wise ops, batch inversion, prefix products ----------------------------------
+ * Between a transform and an MSM a prover does arithmetic on whole vectors of Fr: Groth16's h = (a.b - c) (g^n - 1)^-1
+ * between the coset transforms, the grand products z[i+1] = z[i] num[i] / den[i] of the halo2 / PLONK permutation and
+ * lookup arguments (arkworks batch_inversion, halo2 batch_invert, then a running product), random linear combinations
+ * a + k b before a commitment.  These calls do it where the transform leaves the data and the MSM reads it.
+ * Scalars as in msm_amd_ntt*: 32-byte records in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE
+ * (MSM_AMD_SCALAR_CANON_BE32: MSM_AMD_INPUT_ERROR); any 256-bit input is taken mod r; every output is the fully reduced
+ * residue in the layout of the input, so the bytes are unique.  k32 is one record in the same layout, in HOST memory for
+ * every call.
+ * Aliasing: out may be any operand itself (in place); operands may alias each other freely (a == b squares); an
+ * out-of-place call leaves its inputs unchanged.
+ * Sizes: n == 0 (or n_vec == 0): MSM_AMD_OK, nothing is touched, *n_zero = 0.  MSM_AMD_INPUT_ERROR: n >= 2^32 (prefix
+ * products: n n_vec >= 2^32); an unknown op, mode or layout; a null pointer for an operand the op reads (operands the
+ * op does not read, and k32 for ops without k, are ignored); device pointers that are not 16-byte aligned; an output
+ * that overlaps an operand without being equal to it.
+ * The ctx calls serialise on the ctx and first wait -- bounded -- for its earlier work (a busy ctx:
+ * MSM_AMD_PIPELINE_ERROR, msm_amd_last_error names the call).  The host-buffer forms upload through the page-locked
+ * staging ring into ctx-owned buffers.  kernel_ms (optional): device time of the kernels between events.
+ * msm_amd_fr_batch_inverse*: ONE field inversion per call.  The device multiplies the records up (zeros read as one),
+ * T -- the product of everything non-zero -- and the zero count come back in one 64-byte copy, the host inverts T, and
+ * a last kernel turns T^-1 into every record's inverse: two bounded waits per call, kernel_ms is the sum of the two
+ * device spans.  All records zero: T = 1, every output 0, *n_zero = n.
+ * msm_amd_fr_prefix_product*: a multi-launch scan in stream order (tile products, the scan of the tile products --
+ * recursively past 2^18 records per vector -- then the tiles); it uses ctx-owned memory of about n n_vec / 2^9 records.
+ * (Development knob MSM_AMD_FR_TILE_LOG = 2 .. 9 at msm_amd_init: records per tile as a power of two; default 9, the
+ * inversion uses at most 8.  No byte of a result depends on it.) */
+enum { MSM_AMD_FR_ADD = 0,           /* out = a + b            */
+       MSM_AMD_FR_SUB = 1,           /* out = a - b            */
+       MSM_AMD_FR_MUL = 2,           /* out = a b              */
+       MSM_AMD_FR_SCALE = 3,         /* out = k a              */
+       MSM_AMD_FR_AXPY = 4,          /* out = a + k b          */
+       MSM_AMD_FR_MULSUB_SCALE = 5   /* out = k (a b - c)      */ };
+int msm_amd_fr_map(msm_amd_ctx* ctx, int op, int scalar_layout, const void* k32, const void* a, const void* b, const void* c,
+                   size_t n, void* out);
+int msm_amd_fr_map_device(msm_amd_ctx* ctx, int op, int scalar_layout, const void* k32 /* HOST memory */, const void* d_a,
+                          const void* d_b, const void* d_c, size_t n, void* d_out, float* kernel_ms);
+/* The same on the CPU (no ctx, no GPU; the same bodies compiled for the host); threads <= 0: up to 16 host threads. */
+int msm_amd_host_fr_map(int op, int scalar_layout, const void* k32, const void* a, const void* b, const void* c, size_t n,
+                        int threads, void* out);
+
+/* out[i] = in[i]^-1; in[i] = 0 mod r gives out[i] = 0 (arkworks batch_inversion / halo2 batch_invert), counted in
+ * *n_zero (optional) */
+int msm_amd_fr_batch_inverse(msm_amd_ctx* ctx, int scalar_layout, const void* in, size_t n, void* out, uint64_t* n_zero);
+int msm_amd_fr_batch_inverse_device(msm_amd_ctx* ctx, int scalar_layout, const void* d_in, size_t n, void* d_out,
+                                    uint64_t* n_zero, float* kernel_ms);
+int msm_amd_host_fr_batch_inverse(int scalar_layout, const void* in, size_t n, int threads, void* out, uint64_t* n_zero);
+
+enum { MSM_AMD_FR_PREFIX_INCLUSIVE = 0,  /* out[i] = prod_{j<=i} in[j]             */
+       MSM_AMD_FR_PREFIX_EXCLUSIVE = 1   /* out[0] = 1, out[i] = prod_{j<i} in[j]  */ };
+/* n_vec vectors of n records back to back, any n >= 1 (not only powers of two); the product restarts at every vector */
+int msm_amd_fr_prefix_product(msm_amd_ctx* ctx, int scalar_layout, int mode, const void* in, size_t n, size_t n_vec,
+                              void* out);
+int msm_amd_fr_prefix_product_device(msm_amd_ctx* ctx, int scalar_layout, int mode, const void* d_in, size_t n, size_t n_vec,
+                                     void* d_out, float* kernel_ms);
+int msm_amd_host_fr_prefix_product(int scalar_layout, int mode, const void* in, size_t n, size_t n_vec, int threads,
+                                   void* out);
+
+/* Test aid (no ctx): the plan of a scan over n_vec vectors of n at a tile of 2^tile_log (2 .. 9): out[0] levels, out[1]
+ * launches (2 levels - 1), out[2] tiles of the first level over all vectors, out[3] records of ctx-owned device memory */
+int msm_amd_test_fr_plan(size_t n, size_t n_vec, uint32_t tile_log, uint64_t out[4]);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 int msm_amd_last_timings(const msm_amd_ctx* ctx, msm_amd_timings* out);
 /* Algorithmic HBM bytes of one MSM: whole pipeline and accumulation only. */

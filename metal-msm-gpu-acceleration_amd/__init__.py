@@ -53,6 +53,9 @@ MUL_BASE_EACH, MUL_BASE_ONE = 0, 1
 # number-theoretic transform over Fr (MSM_AMD_NTT_ROOT_*, MSM_AMD_NTT_FORWARD / _INVERSE)
 NTT_ROOT_ARK, NTT_ROOT_H2C = 0, 1
 NTT_FORWARD, NTT_INVERSE = 0, 1
+# vectors over Fr (MSM_AMD_FR_*)
+FR_ADD, FR_SUB, FR_MUL, FR_SCALE, FR_AXPY, FR_MULSUB_SCALE = range(6)
+FR_PREFIX_INCLUSIVE, FR_PREFIX_EXCLUSIVE = 0, 1
 
 
 def op_is_point(op):
@@ -104,6 +107,10 @@ EXPORTS = [
     "msm_amd_test_mul_stage", "msm_amd_test_mul_stage_host",
     "msm_amd_ntt_domain_build", "msm_amd_ntt_domain_info", "msm_amd_ntt_domain_free", "msm_amd_ntt", "msm_amd_ntt_device",
     "msm_amd_host_ntt",
+    "msm_amd_fr_map", "msm_amd_fr_map_device", "msm_amd_host_fr_map",
+    "msm_amd_fr_batch_inverse", "msm_amd_fr_batch_inverse_device", "msm_amd_host_fr_batch_inverse",
+    "msm_amd_fr_prefix_product", "msm_amd_fr_prefix_product_device", "msm_amd_host_fr_prefix_product",
+    "msm_amd_test_fr_plan",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -334,6 +341,19 @@ def _lib():
         L.msm_amd_ntt_device.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                          POINTER(c_float)]
         L.msm_amd_host_ntt.argtypes = [c_int, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int]
+        L.msm_amd_fr_map.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+        L.msm_amd_fr_map_device.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                            c_void_p, POINTER(c_float)]
+        L.msm_amd_host_fr_map.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+        L.msm_amd_fr_batch_inverse.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p, POINTER(c_uint64)]
+        L.msm_amd_fr_batch_inverse_device.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p, POINTER(c_uint64),
+                                                      POINTER(c_float)]
+        L.msm_amd_host_fr_batch_inverse.argtypes = [c_int, c_void_p, c_size_t, c_int, c_void_p, POINTER(c_uint64)]
+        L.msm_amd_fr_prefix_product.argtypes = [c_void_p, c_int, c_int, c_void_p, c_size_t, c_size_t, c_void_p]
+        L.msm_amd_fr_prefix_product_device.argtypes = [c_void_p, c_int, c_int, c_void_p, c_size_t, c_size_t, c_void_p,
+                                                       POINTER(c_float)]
+        L.msm_amd_host_fr_prefix_product.argtypes = [c_int, c_int, c_void_p, c_size_t, c_size_t, c_int, c_void_p]
+        L.msm_amd_test_fr_plan.argtypes = [c_size_t, c_size_t, c_uint32, POINTER(c_uint64)]
         L.msm_amd_generate_instance_host.argtypes = [c_uint64, c_size_t, c_int, c_void_p, c_void_p, c_int]
         L.msm_amd_test_op_ifma.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_tuned_split.argtypes = [c_size_t]
@@ -815,6 +835,51 @@ class MsmConfig:
                                               c_void_p(d_out), n_vec, ctypes.byref(ms)))
         return ms.value
 
+    # ---- vectors over Fr ---------------------------------------------------------------------------
+    def fr_map(self, op, a: bytes, b: bytes = None, c: bytes = None, k: bytes = None, scalar_layout=SCALAR_MONT_LE) -> bytes:
+        """out[i] = op(k, a[i], b[i], c[i]) on host records (msm_amd_fr_map); k: 32 bytes in scalar_layout"""
+        n = len(a) // 32 if a is not None else 0
+        out = ctypes.create_string_buffer(max(1, 32 * n))
+        self._check(_lib().msm_amd_fr_map(self.h, op, scalar_layout, k, a, b, c, n, out))
+        return out.raw[:32 * n]
+
+    def fr_map_device(self, op, d_a, d_b, d_c, n: int, d_out, k: bytes = None, scalar_layout=SCALAR_MONT_LE) -> float:
+        """The same on device-resident records, d_out an operand itself or disjoint (msm_amd_fr_map_device); returns
+        kernel_ms."""
+        ms = c_float(0)
+        self._check(_lib().msm_amd_fr_map_device(self.h, op, scalar_layout, k, c_void_p(d_a), c_void_p(d_b), c_void_p(d_c), n,
+                                                 c_void_p(d_out), ctypes.byref(ms)))
+        return ms.value
+
+    def fr_batch_inverse(self, data: bytes, scalar_layout=SCALAR_MONT_LE):
+        """(records of the inverses -- 0 for 0 --, the number of zeros) of host records (msm_amd_fr_batch_inverse)"""
+        n, zeros = len(data) // 32, c_uint64(0)
+        out = ctypes.create_string_buffer(max(1, len(data)))
+        self._check(_lib().msm_amd_fr_batch_inverse(self.h, scalar_layout, data, n, out, ctypes.byref(zeros)))
+        return out.raw[:32 * n], zeros.value
+
+    def fr_batch_inverse_device(self, d_in, n: int, d_out, scalar_layout=SCALAR_MONT_LE):
+        """The same on device-resident records (msm_amd_fr_batch_inverse_device); returns (n_zero, kernel_ms)."""
+        zeros, ms = c_uint64(0), c_float(0)
+        self._check(_lib().msm_amd_fr_batch_inverse_device(self.h, scalar_layout, c_void_p(d_in), n, c_void_p(d_out),
+                                                           ctypes.byref(zeros), ctypes.byref(ms)))
+        return zeros.value, ms.value
+
+    def fr_prefix_product(self, data: bytes, mode=FR_PREFIX_INCLUSIVE, scalar_layout=SCALAR_MONT_LE, n_vec=1) -> bytes:
+        """Running products of n_vec vectors of host records, restarting at every vector (msm_amd_fr_prefix_product)"""
+        n = len(data) // 32 // n_vec if n_vec else 0
+        out = ctypes.create_string_buffer(max(1, len(data)))
+        self._check(_lib().msm_amd_fr_prefix_product(self.h, scalar_layout, mode, data, n, n_vec, out))
+        return out.raw[:32 * n * n_vec]
+
+    def fr_prefix_product_device(self, d_in, n: int, d_out, mode=FR_PREFIX_INCLUSIVE, scalar_layout=SCALAR_MONT_LE,
+                                 n_vec=1) -> float:
+        """The same on device-resident records (msm_amd_fr_prefix_product_device); returns kernel_ms."""
+        ms = c_float(0)
+        self._check(_lib().msm_amd_fr_prefix_product_device(self.h, scalar_layout, mode, c_void_p(d_in), n, n_vec,
+                                                            c_void_p(d_out), ctypes.byref(ms)))
+        return ms.value
+
     def test_op_g2(self, op, a, b, count):
         """Raw-limb G2 op (MSM_AMD_G2_RAW_*) on the device: a, b flat u32 lists of count * G2_RAW_IN_WORDS; returns
         count * G2_RAW_OUT_WORDS u32."""
@@ -1103,6 +1168,47 @@ def host_ntt(data: bytes, root, log_n, direction=NTT_FORWARD, scalar_layout=SCAL
     if st != OK:
         raise MsmError(st)
     return out.raw[:len(data)]
+
+
+def host_fr_map(op, a: bytes, b: bytes = None, c: bytes = None, k: bytes = None, scalar_layout=SCALAR_MONT_LE,
+                threads=0) -> bytes:
+    """Host twin of MsmConfig.fr_map (no GPU)."""
+    n = len(a) // 32 if a is not None else 0
+    out = ctypes.create_string_buffer(max(1, 32 * n))
+    st = _lib().msm_amd_host_fr_map(op, scalar_layout, k, a, b, c, n, threads, out)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:32 * n]
+
+
+def host_fr_batch_inverse(data: bytes, scalar_layout=SCALAR_MONT_LE, threads=0):
+    """Host twin of MsmConfig.fr_batch_inverse (no GPU): (records, n_zero)."""
+    n, zeros = len(data) // 32, c_uint64(0)
+    out = ctypes.create_string_buffer(max(1, len(data)))
+    st = _lib().msm_amd_host_fr_batch_inverse(scalar_layout, data, n, threads, out, ctypes.byref(zeros))
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:32 * n], zeros.value
+
+
+def host_fr_prefix_product(data: bytes, mode=FR_PREFIX_INCLUSIVE, scalar_layout=SCALAR_MONT_LE, n_vec=1, threads=0) -> bytes:
+    """Host twin of MsmConfig.fr_prefix_product (no GPU)."""
+    n = len(data) // 32 // n_vec if n_vec else 0
+    out = ctypes.create_string_buffer(max(1, len(data)))
+    st = _lib().msm_amd_host_fr_prefix_product(scalar_layout, mode, data, n, n_vec, threads, out)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:32 * n * n_vec]
+
+
+def test_fr_plan(n, n_vec=1, tile_log=9) -> dict:
+    """The plan of a prefix-product scan (msm_amd_test_fr_plan): levels, launches, tiles of the first level over all
+    vectors, records of ctx-owned device memory."""
+    out = (c_uint64 * 4)()
+    st = _lib().msm_amd_test_fr_plan(n, n_vec, tile_log, out)
+    if st != OK:
+        raise MsmError(st)
+    return {"levels": out[0], "launches": out[1], "tiles": out[2], "records": out[3]}
 
 
 def mul_plan(group=1) -> dict:

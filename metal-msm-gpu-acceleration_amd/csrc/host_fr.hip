@@ -1,0 +1,210 @@
+// Host twins of the Fr vector calls (no ctx, no GPU): the load, store and op bodies of fr_vec.hip.h on the CPU, the
+// records split over the host threads -- the map record by record, the inversion with one inversion per range (the
+// classic trick), the prefix products in two phases (the product of every range, then the ranges from their carries);
+// and the argument checks the twins share with the host driver (msm_host.hip).  The bytes of a result are unique, so the
+// way a twin cuts the work shows nowhere.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "../../include/msm_amd.h"
+#include "host_threads.h"
+#include "launch_fr.h"
+#include "launch_ntt.h"
+
+namespace msm_amd {
+
+static_assert(kFrAdd == MSM_AMD_FR_ADD && kFrSub == MSM_AMD_FR_SUB && kFrMul == MSM_AMD_FR_MUL &&
+              kFrScale == MSM_AMD_FR_SCALE && kFrAxpy == MSM_AMD_FR_AXPY && kFrMulsubScale == MSM_AMD_FR_MULSUB_SCALE, "ops");
+static_assert(kFrInclusive == MSM_AMD_FR_PREFIX_INCLUSIVE && kFrExclusive == MSM_AMD_FR_PREFIX_EXCLUSIVE, "modes");
+
+bool fr_layout_known(int scalar_layout) { return ntt_layout_known(scalar_layout); }
+bool fr_mode_known(int mode) { return mode == kFrInclusive || mode == kFrExclusive; }
+
+u256 fr_read_k(int op, int scalar_layout, const void* k32) {
+  if (!(fr_op_reads(op) & kFrReadsK) || !k32) return Fr::one();
+  uint32_t rec[8];
+  std::memcpy(rec, k32, 32);
+  return ntt_load(scalar_layout, rec);
+}
+
+bool fr_overlap_ok(const void* out, const void* p, size_t bytes) {
+  const uintptr_t a = (uintptr_t)out, b = (uintptr_t)p;
+  return a == b || a + bytes <= b || b + bytes <= a;
+}
+
+const char* fr_map_check(int op, int scalar_layout, const void* k32, const void* a, const void* b, const void* c, size_t n,
+                         const void* out, bool device) {
+  const unsigned reads = fr_op_reads(op);
+  if (!reads) return "op must be one of MSM_AMD_FR_ADD .. MSM_AMD_FR_MULSUB_SCALE";
+  if (!fr_layout_known(scalar_layout)) return "scalars in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE only";
+  if ((uint64_t)n >> 32) return "n >= 2^32";
+  if (n == 0) return nullptr;
+  const void* operand[3] = {a, b, c};
+  if (!out || ((reads & kFrReadsK) && !k32)) return "null pointer with n > 0";
+  for (int i = 0; i < 3; ++i) {
+    if (!(reads & (1u << i))) continue;
+    if (!operand[i]) return "null pointer for an operand the op reads";
+    if (device && ((uintptr_t)operand[i] & 15u)) return "device buffers must be 16-byte aligned";
+    if (!fr_overlap_ok(out, operand[i], n * 32)) return "the output must be an operand itself or disjoint from it";
+  }
+  if (device && ((uintptr_t)out & 15u)) return "device buffers must be 16-byte aligned";
+  return nullptr;
+}
+
+const char* fr_unary_check(int scalar_layout, const void* in, uint64_t n, uint64_t n_vec, const void* out, bool device) {
+  if (!fr_layout_known(scalar_layout)) return "scalars in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE only";
+  if ((n >> 32) || (n_vec >> 32) || ((n * n_vec) >> 32)) return "n * n_vec >= 2^32";
+  if (n == 0 || n_vec == 0) return nullptr;
+  if (!in || !out) return "null pointer with n > 0";
+  if (device && (((uintptr_t)in | (uintptr_t)out) & 15u)) return "device buffers must be 16-byte aligned";
+  if (!fr_overlap_ok(out, in, n * n_vec * 32)) return "the output must be the input itself or disjoint from it";
+  return nullptr;
+}
+
+namespace {
+
+u256 host_get(int layout, const uint8_t* base, size_t i) {
+  uint32_t rec[8];
+  std::memcpy(rec, base + i * 32, 32);
+  return ntt_load(layout, rec);
+}
+void host_put(int layout, uint8_t* base, size_t i, const u256& x) {
+  uint32_t rec[8];
+  ntt_store(layout, x, rec);
+  std::memcpy(base + i * 32, rec, 32);
+}
+
+template <int OP>
+void host_map_op(int layout, const u256& k, const uint8_t* a, const uint8_t* b, const uint8_t* c, size_t n, int threads,
+                 uint8_t* out) {
+  constexpr unsigned reads = fr_op_reads(OP);
+  for_ranges(worker_count(threads, n), n, [&](unsigned, size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; ++i) {
+      const u256 x = host_get(layout, a, i);
+      const u256 y = (reads & kFrReadsB) ? host_get(layout, b, i) : x;
+      const u256 z = (reads & kFrReadsC) ? host_get(layout, c, i) : x;
+      host_put(layout, out, i, fr_map_op<OP>(k, x, y, z));
+    }
+  });
+}
+
+int host_fr_map(int op, int layout, const void* k32, const void* a_v, const void* b_v, const void* c_v, size_t n, int threads,
+                void* out_v) {
+  if (fr_map_check(op, layout, k32, a_v, b_v, c_v, n, out_v, false)) return MSM_AMD_INPUT_ERROR;
+  if (n == 0) return MSM_AMD_OK;
+  const u256 k = fr_read_k(op, layout, k32);
+  const uint8_t *a = (const uint8_t*)a_v, *b = (const uint8_t*)b_v, *c = (const uint8_t*)c_v;
+  uint8_t* out = (uint8_t*)out_v;
+  switch (op) {
+    case kFrAdd: host_map_op<kFrAdd>(layout, k, a, b, c, n, threads, out); break;
+    case kFrSub: host_map_op<kFrSub>(layout, k, a, b, c, n, threads, out); break;
+    case kFrMul: host_map_op<kFrMul>(layout, k, a, b, c, n, threads, out); break;
+    case kFrScale: host_map_op<kFrScale>(layout, k, a, b, c, n, threads, out); break;
+    case kFrAxpy: host_map_op<kFrAxpy>(layout, k, a, b, c, n, threads, out); break;
+    default: host_map_op<kFrMulsubScale>(layout, k, a, b, c, n, threads, out); break;
+  }
+  return MSM_AMD_OK;
+}
+
+int host_fr_batch_inverse(int layout, const void* in_v, size_t n, int threads, void* out_v, uint64_t* n_zero) {
+  if (n_zero) *n_zero = 0;
+  if (fr_unary_check(layout, in_v, n, 1, out_v, false)) return MSM_AMD_INPUT_ERROR;
+  if (n == 0) return MSM_AMD_OK;
+  const uint8_t* in = (const uint8_t*)in_v;
+  uint8_t* out = (uint8_t*)out_v;
+  const unsigned T = worker_count(threads, n);
+  std::vector<uint64_t> zeros(T, 0);
+  for_ranges(T, n, [&](unsigned t, size_t lo, size_t hi) {
+    if (lo >= hi) return;
+    // before[i - lo] = the product of the non-zero records lo .. i - 1
+    std::vector<u256> before(hi - lo);
+    u256 acc = Fr::one();
+    for (size_t i = lo; i < hi; ++i) {
+      before[i - lo] = acc;
+      const u256 x = host_get(layout, in, i);
+      if (u256_is_zero(x)) ++zeros[t];
+      else acc = Fr::mul(acc, x);
+    }
+    u256 inv = ntt_fr_inv(acc);   // of the product up to and including record i
+    for (size_t i = hi; i-- > lo;) {
+      const u256 x = host_get(layout, in, i);
+      if (u256_is_zero(x)) {
+        host_put(layout, out, i, x);
+        continue;
+      }
+      host_put(layout, out, i, Fr::mul(inv, before[i - lo]));
+      inv = Fr::mul(inv, x);
+    }
+  });
+  if (n_zero)
+    for (uint64_t z : zeros) *n_zero += z;
+  return MSM_AMD_OK;
+}
+
+int host_fr_prefix_product(int layout, int mode, const void* in_v, size_t n, size_t n_vec, int threads, void* out_v) {
+  if (!fr_mode_known(mode) || fr_unary_check(layout, in_v, n, n_vec, out_v, false)) return MSM_AMD_INPUT_ERROR;
+  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
+  const uint8_t* in = (const uint8_t*)in_v;
+  uint8_t* out = (uint8_t*)out_v;
+  const size_t total = n * n_vec;
+  const unsigned T = worker_count(threads, total);
+  // phase 1: per range, the product of its records from the last start of a vector in it (or from its first record)
+  std::vector<u256> tail(T, Fr::one());
+  std::vector<char> restarts(T, 0);
+  for_ranges(T, total, [&](unsigned t, size_t lo, size_t hi) {
+    u256 acc = Fr::one();
+    for (size_t i = lo; i < hi; ++i) {
+      if (i % n == 0) acc = Fr::one(), restarts[t] = 1;
+      acc = Fr::mul(acc, host_get(layout, in, i));
+    }
+    tail[t] = acc;
+  });
+  // the product before the first record of every range
+  std::vector<u256> carry(T, Fr::one());
+  for (unsigned t = 1; t < T; ++t) carry[t] = restarts[t - 1] ? tail[t - 1] : Fr::mul(carry[t - 1], tail[t - 1]);
+  // phase 2
+  for_ranges(T, total, [&](unsigned t, size_t lo, size_t hi) {
+    u256 run = carry[t];
+    for (size_t i = lo; i < hi; ++i) {
+      if (i % n == 0) run = Fr::one();
+      const u256 nxt = Fr::mul(run, host_get(layout, in, i));
+      host_put(layout, out, i, mode == kFrInclusive ? nxt : run);
+      run = nxt;
+    }
+  });
+  return MSM_AMD_OK;
+}
+
+}  // namespace
+}  // namespace msm_amd
+
+extern "C" {
+
+int msm_amd_host_fr_map(int op, int scalar_layout, const void* k32, const void* a, const void* b, const void* c, size_t n,
+                        int threads, void* out) {
+  return msm_amd::host_fr_map(op, scalar_layout, k32, a, b, c, n, threads, out);
+}
+
+int msm_amd_host_fr_batch_inverse(int scalar_layout, const void* in, size_t n, int threads, void* out, uint64_t* n_zero) {
+  return msm_amd::host_fr_batch_inverse(scalar_layout, in, n, threads, out, n_zero);
+}
+
+int msm_amd_host_fr_prefix_product(int scalar_layout, int mode, const void* in, size_t n, size_t n_vec, int threads,
+                                   void* out) {
+  return msm_amd::host_fr_prefix_product(scalar_layout, mode, in, n, n_vec, threads, out);
+}
+
+int msm_amd_test_fr_plan(size_t n, size_t n_vec, uint32_t tile_log, uint64_t out[4]) {
+  using namespace msm_amd;
+  const uint64_t n64 = n, v64 = n_vec;
+  if (!out || tile_log < kFrMinTileLog || tile_log > kFrTileLog || (n64 >> 32) || (v64 >> 32) || ((n64 * v64) >> 32))
+    return MSM_AMD_INPUT_ERROR;
+  out[0] = out[1] = out[2] = out[3] = 0;
+  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
+  const FrScanPlan p = fr_scan_plan(n, n_vec, tile_log);
+  out[0] = p.levels, out[1] = p.launches, out[2] = p.tiles[0] * n_vec, out[3] = p.records;
+  return MSM_AMD_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,314 @@
+// Kernels over vectors of BN254 Fr (fr_vec.hip.h):
+//   fr_map_kernel<OP>      one lane per record, consecutive lanes on consecutive records: load (to_mont for CANON_LE), the
+//                          op, store (from_mont for CANON_LE).  k arrives by value.
+//   fr_tile_reduce_kernel  one wave per tile: every lane multiplies the records lane, lane + 64, ... of the tile, six
+//                          shuffle steps fold the 64 lane products; the inversion's form reads a zero as one and counts it.
+//   fr_tile_scan_kernel    one wave per tile: the tile goes to LDS at unit stride, lane t owns the 2^(T-6) consecutive
+//                          records t 2^(T-6) ..: its product (lane 0 starts from the tile's carry), six shuffle steps for
+//                          the inclusive scan of the 64 lane products, a second walk that writes the running products
+//                          back to LDS, and the tile leaves at unit stride.
+//   fr_inv_apply_kernel    one wave per tile, two LDS images (the records, and the running product before each record of
+//                          a lane): c = T^-1 P_(b-1) S_(b+1) inverts the tile's product, the prefix and suffix scans of
+//                          the lane products turn it into the inverse of each lane's product, and the backward sweep of
+//                          the classic batch inversion runs inside the lane.
+// Phases are ordered by launch order on one stream only; no kernel reads what another workgroup of its launch wrote.
+// LDS images are eight word planes; slot m sits at m + (m >> log2(records per lane)), so that the unit-stride accesses
+// and the walks of the lanes (stride = records per lane) are both free of bank conflicts, bar one 2-way per access.
+// No scratch, no register array indexed at run time (`make resource-usage`); the walks are not unrolled.
+#include "launch_fr.h"
+
+namespace msm_amd {
+
+namespace {
+
+struct FrTileArgs {
+  const uint32_t* src;
+  uint32_t* dst;               // scan
+  const uint32_t* carry;       // scan: one raw record per tile, the product before it; null: one
+  uint32_t* totals;            // reduce: one raw record per tile
+  unsigned long long* zeros;   // reduce with zero_one: the count
+  uint64_t len, tiles;         // records and tiles per vector
+  uint32_t tile_log;
+  int layout, mode, reverse, zero_one;
+};
+
+struct FrInvArgs {
+  const uint32_t* src;
+  uint32_t* dst;
+  const uint32_t* P;
+  const uint32_t* S;
+  uint64_t len, tiles;
+  uint32_t tile_log;
+  int layout;
+  u256 t_inv;
+};
+
+// An LDS image of a tile: eight planes of 2^T + 64 words, sized at the launch (fr_image_bytes) so that a smaller tile
+// lets more waves share a CU
+struct Image {
+  uint32_t* lds;
+  uint32_t plane, per_log;
+};
+__host__ __device__ constexpr uint32_t fr_image_bytes(uint32_t tile_log) { return 8u * ((1u << tile_log) + kFrWave) * 4u; }
+__device__ __forceinline__ Image image(uint32_t* lds, uint32_t tile_log) {
+  return Image{lds, (1u << tile_log) + kFrWave, tile_log > 6u ? tile_log - 6u : 0u};
+}
+__device__ __forceinline__ u256 lds_get(const Image& im, uint32_t m) {
+  const uint32_t p = m + (m >> im.per_log);
+  u256 x;
+  MSM_UNROLL for (int w = 0; w < 8; ++w) x.v[w] = im.lds[w * im.plane + p];
+  return x;
+}
+__device__ __forceinline__ void lds_put(const Image& im, uint32_t m, const u256& x) {
+  const uint32_t p = m + (m >> im.per_log);
+  MSM_UNROLL for (int w = 0; w < 8; ++w) im.lds[w * im.plane + p] = x.v[w];
+}
+
+// 32-byte records of 16-byte aligned buffers move as two dwordx4
+__device__ __forceinline__ u256 load_rec(const uint32_t* rec) {
+  const uint4 a = ((const uint4*)rec)[0], b = ((const uint4*)rec)[1];
+  u256 x;
+  x.v[0] = a.x, x.v[1] = a.y, x.v[2] = a.z, x.v[3] = a.w, x.v[4] = b.x, x.v[5] = b.y, x.v[6] = b.z, x.v[7] = b.w;
+  return x;
+}
+__device__ __forceinline__ void store_rec(uint32_t* rec, const u256& x) {
+  ((uint4*)rec)[0] = make_uint4(x.v[0], x.v[1], x.v[2], x.v[3]);
+  ((uint4*)rec)[1] = make_uint4(x.v[4], x.v[5], x.v[6], x.v[7]);
+}
+
+__device__ __forceinline__ u256 wave_up(const u256& x, uint32_t d) {
+  u256 r;
+  MSM_UNROLL for (int w = 0; w < 8; ++w) r.v[w] = __shfl_up(x.v[w], d);
+  return r;
+}
+__device__ __forceinline__ u256 wave_down(const u256& x, uint32_t d) {
+  u256 r;
+  MSM_UNROLL for (int w = 0; w < 8; ++w) r.v[w] = __shfl_down(x.v[w], d);
+  return r;
+}
+__device__ __forceinline__ u256 wave_xor(const u256& x, uint32_t d) {
+  u256 r;
+  MSM_UNROLL for (int w = 0; w < 8; ++w) r.v[w] = __shfl_xor(x.v[w], (int)d);
+  return r;
+}
+
+// The tile of a workgroup: vector v, first index and record count inside the vector
+struct TilePlace {
+  uint64_t base, first;
+  uint32_t cnt;
+};
+__device__ __forceinline__ TilePlace tile_place(uint64_t b, uint64_t len, uint64_t tiles, uint32_t tile_log) {
+  TilePlace t;
+  const uint64_t v = b / tiles;
+  t.base = v * len;
+  t.first = (b - v * tiles) << tile_log;
+  const uint64_t left = len - t.first;
+  t.cnt = left < ((uint64_t)1 << tile_log) ? (uint32_t)left : (1u << tile_log);
+  return t;
+}
+// slot m of the tile -> record of the buffer (reverse: the vector is walked from its last record down)
+__device__ __forceinline__ uint64_t tile_record(const TilePlace& t, uint64_t len, int reverse, uint32_t m) {
+  const uint64_t i = t.first + m;
+  return t.base + (reverse ? len - 1 - i : i);
+}
+
+template <int OP>
+__global__ void __launch_bounds__(kFrMapThreads) fr_map_kernel(int layout, u256 k, const uint32_t* A, const uint32_t* B,
+                                                                const uint32_t* C, uint64_t n, uint32_t* out) {
+  constexpr unsigned reads = fr_op_reads(OP);
+  const uint64_t i = (uint64_t)blockIdx.x * kFrMapThreads + threadIdx.x;
+  if (i >= n) return;
+  const u256 a = fr_load(layout, load_rec(A + i * 8));
+  u256 b = a, c = a;
+  if (reads & kFrReadsB) b = fr_load(layout, load_rec(B + i * 8));
+  if (reads & kFrReadsC) c = fr_load(layout, load_rec(C + i * 8));
+  store_rec(out + i * 8, fr_store(layout, fr_map_op<OP>(k, a, b, c)));
+}
+
+__global__ void __launch_bounds__(kFrWave) fr_tile_reduce_kernel(FrTileArgs a) {
+  const uint32_t lane = threadIdx.x;
+  const TilePlace t = tile_place(blockIdx.x, a.len, a.tiles, a.tile_log);
+  u256 acc = Fr::one();
+  uint32_t zc = 0;
+  NTT_NO_UNROLL for (uint32_t m = lane; m < t.cnt; m += kFrWave) {
+    u256 x = fr_load(a.layout, load_rec(a.src + tile_record(t, a.len, a.reverse, m) * 8));
+    if (a.zero_one) {
+      const bool z = u256_is_zero(x);
+      zc += z ? 1u : 0u;
+      x = fr_select(z, Fr::one(), x);
+    }
+    acc = Fr::mul(acc, x);
+  }
+  NTT_NO_UNROLL for (uint32_t d = kFrWave / 2; d != 0; d >>= 1) {
+    acc = Fr::mul(acc, wave_xor(acc, d));
+    zc += (uint32_t)__shfl_xor((int)zc, (int)d);
+  }
+  if (lane == 0) {
+    store_rec(a.totals + (uint64_t)blockIdx.x * 8, acc);
+    if (a.zero_one && zc) atomicAdd(a.zeros, (unsigned long long)zc);
+  }
+}
+
+__global__ void __launch_bounds__(kFrWave) fr_tile_scan_kernel(FrTileArgs a) {
+  extern __shared__ uint32_t fr_lds[];
+  const Image lds = image(fr_lds, a.tile_log);
+  const uint32_t lane = threadIdx.x;
+  const TilePlace t = tile_place(blockIdx.x, a.len, a.tiles, a.tile_log);
+  const uint32_t per = 1u << lds.per_log, m0 = lane << lds.per_log;
+
+  NTT_NO_UNROLL for (uint32_t m = lane; m < t.cnt; m += kFrWave)
+    lds_put(lds, m, fr_load(a.layout, load_rec(a.src + tile_record(t, a.len, a.reverse, m) * 8)));
+  __syncthreads();
+
+  // the product of the lane's records; lane 0 carries the product before the tile
+  const u256 carry = a.carry ? load_rec(a.carry + (uint64_t)blockIdx.x * 8) : Fr::one();
+  u256 acc = fr_select(lane == 0, carry, Fr::one());
+  NTT_NO_UNROLL for (uint32_t j = 0; j < per; ++j) {
+    if (m0 + j >= t.cnt) break;
+    acc = Fr::mul(acc, lds_get(lds, m0 + j));
+  }
+  NTT_NO_UNROLL for (uint32_t d = 1; d < kFrWave; d <<= 1) {
+    const u256 y = wave_up(acc, d);
+    acc = Fr::mul(acc, fr_select(lane >= d, y, Fr::one()));
+  }
+  // the product before the lane's first record, then the running products
+  u256 run = fr_select(lane == 0, carry, wave_up(acc, 1));
+  NTT_NO_UNROLL for (uint32_t j = 0; j < per; ++j) {
+    const uint32_t m = m0 + j;
+    if (m >= t.cnt) break;
+    const u256 nxt = Fr::mul(run, lds_get(lds, m));
+    lds_put(lds, m, a.mode == kFrInclusive ? nxt : run);
+    run = nxt;
+  }
+  __syncthreads();
+
+  NTT_NO_UNROLL for (uint32_t m = lane; m < t.cnt; m += kFrWave)
+    store_rec(a.dst + tile_record(t, a.len, a.reverse, m) * 8, fr_store(a.layout, lds_get(lds, m)));
+}
+
+__global__ void __launch_bounds__(kFrWave) fr_inv_apply_kernel(FrInvArgs a) {
+  extern __shared__ uint32_t fr_lds[];
+  const Image lds_x = image(fr_lds, a.tile_log), lds_p = image(fr_lds + fr_image_bytes(a.tile_log) / 4u, a.tile_log);
+  const uint32_t lane = threadIdx.x;
+  const uint64_t b = blockIdx.x;
+  const TilePlace t = tile_place(b, a.len, a.tiles, a.tile_log);
+  const uint32_t per = 1u << lds_x.per_log, m0 = lane << lds_x.per_log;
+
+  NTT_NO_UNROLL for (uint32_t m = lane; m < t.cnt; m += kFrWave)
+    lds_put(lds_x, m, fr_load(a.layout, load_rec(a.src + tile_record(t, a.len, 0, m) * 8)));
+  __syncthreads();
+
+  // forward: the running product before each record of the lane (zeros read as one), and the lane's product
+  u256 acc = Fr::one();
+  NTT_NO_UNROLL for (uint32_t j = 0; j < per; ++j) {
+    const uint32_t m = m0 + j;
+    if (m >= t.cnt) break;
+    const u256 x = lds_get(lds_x, m);
+    lds_put(lds_p, m, acc);
+    acc = Fr::mul(acc, fr_select(u256_is_zero(x), Fr::one(), x));
+  }
+  // inclusive prefix and suffix products of the lane products
+  u256 pre = acc, suf = acc;
+  NTT_NO_UNROLL for (uint32_t d = 1; d < kFrWave; d <<= 1) {
+    const u256 y = wave_up(pre, d), z = wave_down(suf, d);
+    pre = Fr::mul(pre, fr_select(lane >= d, y, Fr::one()));
+    suf = Fr::mul(suf, fr_select(lane + d < kFrWave, z, Fr::one()));
+  }
+  const u256 before = fr_select(lane == 0, Fr::one(), wave_up(pre, 1));
+  const u256 after = fr_select(lane == kFrWave - 1, Fr::one(), wave_down(suf, 1));
+  // the inverse of the tile's product, then of the lane's product
+  u256 inv = a.t_inv;
+  if (b > 0) inv = Fr::mul(inv, load_rec(a.P + (b - 1) * 8));
+  if (b + 1 < a.tiles) inv = Fr::mul(inv, load_rec(a.S + (b + 1) * 8));
+  inv = Fr::mul(Fr::mul(inv, before), after);
+  // backward: inv is the inverse of the product up to and including record j
+  NTT_NO_UNROLL for (uint32_t j = per; j-- != 0;) {
+    const uint32_t m = m0 + j;
+    if (m >= t.cnt) continue;
+    const u256 x = lds_get(lds_x, m);
+    const bool z = u256_is_zero(x);
+    const u256 o = Fr::mul(inv, lds_get(lds_p, m));
+    inv = Fr::mul(inv, fr_select(z, Fr::one(), x));
+    lds_put(lds_x, m, fr_select(z, x, o));
+  }
+  __syncthreads();
+
+  NTT_NO_UNROLL for (uint32_t m = lane; m < t.cnt; m += kFrWave)
+    store_rec(a.dst + tile_record(t, a.len, 0, m) * 8, fr_store(a.layout, lds_get(lds_x, m)));
+}
+
+template <int OP>
+void launch_map_op(hipStream_t st, int layout, const u256& k, const void* a, const void* b, const void* c, size_t n, void* out) {
+  hipLaunchKernelGGL(fr_map_kernel<OP>, dim3((uint32_t)((n + kFrMapThreads - 1) / kFrMapThreads)), dim3(kFrMapThreads), 0, st,
+                     layout, k, (const uint32_t*)a, (const uint32_t*)b, (const uint32_t*)c, (uint64_t)n, (uint32_t*)out);
+}
+
+void launch_reduce(hipStream_t st, const FrTileArgs& a, uint64_t n_vec) {
+  hipLaunchKernelGGL(fr_tile_reduce_kernel, dim3((uint32_t)(a.tiles * n_vec)), dim3(kFrWave), 0, st, a);
+}
+void launch_scan(hipStream_t st, const FrTileArgs& a, uint64_t n_vec) {
+  hipLaunchKernelGGL(fr_tile_scan_kernel, dim3((uint32_t)(a.tiles * n_vec)), dim3(kFrWave), fr_image_bytes(a.tile_log), st, a);
+}
+
+}  // namespace
+
+void launch_fr_map(hipStream_t st, int op, int layout, const u256& k, const void* a, const void* b, const void* c, size_t n,
+                   void* out) {
+  switch (op) {
+    case kFrAdd: return launch_map_op<kFrAdd>(st, layout, k, a, b, c, n, out);
+    case kFrSub: return launch_map_op<kFrSub>(st, layout, k, a, b, c, n, out);
+    case kFrMul: return launch_map_op<kFrMul>(st, layout, k, a, b, c, n, out);
+    case kFrScale: return launch_map_op<kFrScale>(st, layout, k, a, b, c, n, out);
+    case kFrAxpy: return launch_map_op<kFrAxpy>(st, layout, k, a, b, c, n, out);
+    default: return launch_map_op<kFrMulsubScale>(st, layout, k, a, b, c, n, out);
+  }
+}
+
+uint32_t launch_fr_scan(hipStream_t st, const FrScanLaunch& c) {
+  const FrScanPlan plan = fr_scan_plan(c.n, c.n_vec, c.tile_log);
+  uint32_t* work = (uint32_t*)c.work;
+  auto level = [&](uint32_t k) {   // the reads of level k, for a reduction or for the scan in place
+    FrTileArgs a{};
+    a.len = plan.len[k], a.tiles = plan.tiles[k], a.tile_log = c.tile_log;
+    a.src = k == 0 ? (const uint32_t*)c.in : work + plan.offset[k] * 8;
+    a.dst = k == 0 ? (uint32_t*)c.out : work + plan.offset[k] * 8;
+    a.layout = k == 0 ? c.layout : kFrRaw;
+    a.reverse = k == 0 && c.reverse;
+    a.mode = k == 0 ? c.mode : kFrExclusive;
+    if (k + 1 < plan.levels) a.carry = a.totals = work + plan.offset[k + 1] * 8;
+    return a;
+  };
+  for (uint32_t k = 0; k + 1 < plan.levels; ++k) launch_reduce(st, level(k), c.n_vec);
+  for (uint32_t k = plan.levels; k-- != 0;) launch_scan(st, level(k), c.n_vec);
+  return plan.launches;
+}
+
+uint32_t launch_fr_inv_products(hipStream_t st, int layout, const void* in, uint64_t n, uint32_t tile_log, void* work_v) {
+  const FrInvPlan ip = fr_inv_plan(n, tile_log);
+  uint32_t* work = (uint32_t*)work_v;
+  uint32_t* count = work + (ip.p_off + ip.tiles) * 8;
+  (void)hipMemsetAsync(count, 0, 32, st);
+  FrTileArgs a{};
+  a.src = (const uint32_t*)in, a.totals = work + ip.t_off * 8, a.zeros = (unsigned long long*)count;
+  a.len = n, a.tiles = ip.tiles, a.tile_log = ip.tile_log, a.layout = layout, a.zero_one = 1;
+  launch_reduce(st, a, 1);
+  FrScanLaunch s{};
+  s.in = work + ip.t_off * 8, s.work = work + ip.scan_off * 8;
+  s.n = ip.tiles, s.n_vec = 1, s.tile_log = tile_log, s.layout = kFrRaw, s.mode = kFrInclusive;
+  s.out = work + ip.p_off * 8;
+  uint32_t launches = 1 + launch_fr_scan(st, s);
+  s.out = work + ip.s_off * 8, s.reverse = true;
+  return launches + launch_fr_scan(st, s);
+}
+
+void launch_fr_inv_apply(hipStream_t st, int layout, const void* in, uint64_t n, uint32_t tile_log, const void* work_v,
+                         const u256& t_inv, void* out) {
+  const FrInvPlan ip = fr_inv_plan(n, tile_log);
+  const uint32_t* work = (const uint32_t*)work_v;
+  FrInvArgs a{};
+  a.src = (const uint32_t*)in, a.dst = (uint32_t*)out, a.P = work + ip.p_off * 8, a.S = work + ip.s_off * 8;
+  a.len = n, a.tiles = ip.tiles, a.tile_log = ip.tile_log, a.layout = layout, a.t_inv = t_inv;
+  hipLaunchKernelGGL(fr_inv_apply_kernel, dim3((uint32_t)ip.tiles), dim3(kFrWave), 2 * fr_image_bytes(a.tile_log), st, a);
+}
+
+}  // namespace msm_amd

@@ -31,6 +31,7 @@
 #include "launch_check.h"
 #include "launch_compress.h"
 #include "launch_mul.h"
+#include "launch_fr.h"
 #include "launch_ntt.h"
 #include "host_fq64.h"
 #include "test_ops.hip.h"
@@ -204,6 +205,15 @@ struct NttState {
   hipEvent_t ev[2] = {};
 };
 
+// Buffers of the Fr vector calls (fr_*_call): the staging of the host-buffer forms (three operands; the result is
+// written over the first), the tile totals of a scan or an inversion (fr_scan_plan, fr_inv_plan), the page-locked
+// landing place of an inversion's T and zero count, and two pairs of events behind kernel_ms.
+struct FrState {
+  DeviceBuf in[3], work;
+  uint8_t* h_tail = nullptr;   // pinned: T (32 bytes), then the zero count
+  hipEvent_t ev[4] = {};
+};
+
 // Buffers of the point calls of one group (check, decompress, compress and mul_points; point_call below): the staging of
 // the host-buffer calls, the 64-byte counters with their page-locked copy and events, and the device-side scratch of
 // mul_points.  One per group: a G2 call touches G2State only.
@@ -263,6 +273,8 @@ struct msm_amd_ctx {
   std::vector<msm_amd_g2_tables*> live_g2_tables;
   std::vector<msm_amd_ntt_domain*> live_ntt;
   NttState ntt;
+  FrState fr;
+  uint32_t fr_tile_log = kFrTileLog;     // records per tile of a scan, as a power of two (MSM_AMD_FR_TILE_LOG)
   uint32_t ntt_tile_log = kNttTileLog;   // elements per workgroup of a transform pass, as a power of two (MSM_AMD_NTT_TILE_LOG)
   int next_ws = 0;
   DeviceBuf scratch_a, scratch_b, scratch_c, scratch_b2, scratch_c2;
@@ -2101,6 +2113,8 @@ int msm_amd_init(int device, msm_amd_ctx** out) {
   }
   if (const char* e = std::getenv("MSM_AMD_NTT_TILE_LOG"))
     ctx->ntt_tile_log = (uint32_t)std::max(2, std::min((int)kNttTileLog, std::atoi(e)));
+  if (const char* e = std::getenv("MSM_AMD_FR_TILE_LOG"))
+    ctx->fr_tile_log = (uint32_t)std::max((int)kFrMinTileLog, std::min((int)kFrTileLog, std::atoi(e)));
   if (const char* e = std::getenv("MSM_AMD_BASES_CACHE_VERIFY")) ctx->bases_cache_verify = std::strcmp(e, "full") == 0;
   if (const char* e = std::getenv("MSM_AMD_BASES_CACHE_MB")) {
     ctx->bases_cache_budget = (size_t)std::strtoull(e, nullptr, 10) << 20;
@@ -2211,6 +2225,7 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
     ps->ready = false;
   }
   for (hipEvent_t& e : ctx->ntt.ev) kill_event(e);
+  for (hipEvent_t& e : ctx->fr.ev) kill_event(e);
   for (hipEvent_t& e : ctx->uploaded) kill_event(e);
   kill_event(ctx->upload_done);
   kill_event(ctx->after_sort_mark);
@@ -2246,6 +2261,9 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
   }
   ctx->live_ntt.clear();
   for (DeviceBuf* b : {&ctx->ntt.scratch, &ctx->ntt.pow}) kill_buf(*b);
+  for (DeviceBuf* b : {&ctx->fr.in[0], &ctx->fr.in[1], &ctx->fr.in[2], &ctx->fr.work}) kill_buf(*b);
+  if (ctx->fr.h_tail) (void)hipHostFree(ctx->fr.h_tail);
+  ctx->fr.h_tail = nullptr;
   for (DeviceBuf* b : {&ctx->scratch_a, &ctx->scratch_b, &ctx->scratch_c, &ctx->scratch_b2, &ctx->scratch_c2}) kill_buf(*b);
   bases_cache_clear(ctx);   // (entries and unused reserves go through the graveyard)
   for (const msm_amd_ctx::CacheReserve& r : ctx->cache_reserve) ctx->graveyard.push_back(r.d);
@@ -3330,6 +3348,8 @@ int msm_amd_test_fill_workspaces(msm_amd_ctx* ctx, uint8_t byte) {
       if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
   for (DeviceBuf* b : {&ctx->ntt.scratch, &ctx->ntt.pow})   // the transform's pass buffer and shift powers
     if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
+  for (DeviceBuf* b : {&ctx->fr.in[0], &ctx->fr.in[1], &ctx->fr.in[2], &ctx->fr.work})   // the Fr vector calls: staging, tile totals
+    if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
   return sync_stream_bounded(ctx, ctx->stream, __func__);
 }
 
@@ -4204,6 +4224,184 @@ int msm_amd_ntt(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int directio
 int msm_amd_ntt_device(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int scalar_layout,
                        const void* shift32, const void* d_in, void* d_out, size_t n_vec, float* kernel_ms) {
   return ntt_call(ctx, domain, false, direction, scalar_layout, shift32, d_in, d_out, n_vec, kernel_ms);
+}
+
+}  // extern "C"
+
+// ---- vectors over Fr (msm_amd_fr_map*, msm_amd_fr_batch_inverse*, msm_amd_fr_prefix_product*) --------------------------------
+// The discipline of ntt_call: ctx lock, bounded drain of the ctx's earlier work, every buffer sized on the idle ctx
+// before anything is enqueued, host operands through the page-locked staging ring, the kernels on the main stream
+// between events, the result behind a bounded stream wait.  The inversion waits twice: T comes back, the host inverts it.
+namespace {
+
+int fr_begin(msm_amd_ctx* ctx, const std::string& who) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = recover_if_stalled(ctx)) return fail(ctx, rc, who + ": " + ctx->last_error);
+  if (!drain_or_mark_stalled(ctx))
+    return fail(ctx, MSM_AMD_PIPELINE_ERROR, who + ": device busy past the wait bound of " +
+                                                 std::to_string(ctx->wait_timeout_ms) + " ms (msm_amd_synchronize waits again)");
+  for (hipEvent_t& e : ctx->fr.ev)
+    if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+  return MSM_AMD_OK;
+}
+
+int fr_map_call(msm_amd_ctx* ctx, bool host, int op, int scalar_layout, const void* k32, const void* a, const void* b,
+                const void* c, size_t n, void* out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  const std::string who = host ? "msm_amd_fr_map" : "msm_amd_fr_map_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_map_check(op, scalar_layout, k32, a, b, c, n, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": " + why);
+  if (n == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (int rc = fr_begin(ctx, who)) return rc;
+  // the ctx is idle: every buffer of this call is sized now
+  FrState& s = ctx->fr;
+  hipStream_t st = ctx->stream;
+  const size_t bytes = n * 32;
+  const unsigned reads = fr_op_reads(op);
+  const void* operand[3] = {a, b, c};
+  void* d_out = out;
+  int rc;
+  if (host) {   // staged, the result over the first operand, copied back
+    for (int i = 0; i < 3; ++i)
+      if ((reads & (1u << i)) && (rc = ensure(ctx, s.in[i], bytes))) return rc;
+    for (int i = 0; i < 3; ++i) {
+      if (!(reads & (1u << i))) continue;
+      if ((rc = staged_upload(ctx, s.in[i].p, operand[i], bytes, st))) return rc;
+      operand[i] = s.in[i].p;
+    }
+    d_out = s.in[0].p;
+  }
+  HIP_TRY(ctx, hipEventRecord(s.ev[0], st));
+  launch_fr_map(st, op, scalar_layout, fr_read_k(op, scalar_layout, k32), operand[0], operand[1], operand[2], n, d_out);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(s.ev[1], st));
+  if (host) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
+  if ((rc = sync_stream_bounded(ctx, st, who.c_str()))) return rc;
+  if (kernel_ms) *kernel_ms = event_span(s.ev[0], s.ev[1]);
+  return MSM_AMD_OK;
+}
+
+int fr_prefix_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int mode, const void* in, size_t n, size_t n_vec, void* out,
+                   float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  const std::string who = host ? "msm_amd_fr_prefix_product" : "msm_amd_fr_prefix_product_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (!fr_mode_known(mode))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": mode must be MSM_AMD_FR_PREFIX_INCLUSIVE or MSM_AMD_FR_PREFIX_EXCLUSIVE");
+  if (const char* why = fr_unary_check(scalar_layout, in, n, n_vec, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": " + why);
+  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (int rc = fr_begin(ctx, who)) return rc;
+  FrState& s = ctx->fr;
+  hipStream_t st = ctx->stream;
+  const size_t bytes = n * n_vec * 32;
+  FrScanLaunch c{};
+  c.n = n, c.n_vec = n_vec, c.tile_log = ctx->fr_tile_log, c.layout = scalar_layout, c.mode = mode;
+  int rc;
+  if ((rc = ensure(ctx, s.work, std::max<size_t>(32, fr_scan_plan(n, n_vec, c.tile_log).records * 32)))) return rc;
+  if (host && (rc = ensure(ctx, s.in[0], bytes))) return rc;
+  c.in = in, c.out = out, c.work = s.work.p;
+  if (host) {   // staged, scanned in place, copied back
+    if ((rc = staged_upload(ctx, s.in[0].p, in, bytes, st))) return rc;
+    c.in = c.out = s.in[0].p;
+  }
+  HIP_TRY(ctx, hipEventRecord(s.ev[0], st));
+  launch_fr_scan(st, c);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(s.ev[1], st));
+  if (host) HIP_TRY(ctx, hipMemcpyAsync(out, c.out, bytes, hipMemcpyDeviceToHost, st));
+  if ((rc = sync_stream_bounded(ctx, st, who.c_str()))) return rc;
+  if (kernel_ms) *kernel_ms = event_span(s.ev[0], s.ev[1]);
+  return MSM_AMD_OK;
+}
+
+int fr_inverse_call(msm_amd_ctx* ctx, bool host, int scalar_layout, const void* in, size_t n, void* out, uint64_t* n_zero,
+                    float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  const std::string who = host ? "msm_amd_fr_batch_inverse" : "msm_amd_fr_batch_inverse_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (n_zero) *n_zero = 0;
+  if (const char* why = fr_unary_check(scalar_layout, in, n, 1, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": " + why);
+  if (n == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (int rc = fr_begin(ctx, who)) return rc;
+  FrState& s = ctx->fr;
+  hipStream_t st = ctx->stream;
+  const size_t bytes = n * 32;
+  const uint32_t tile_log = ctx->fr_tile_log;
+  const FrInvPlan plan = fr_inv_plan(n, tile_log);
+  int rc;
+  if ((rc = ensure(ctx, s.work, plan.records * 32))) return rc;
+  if (host && (rc = ensure(ctx, s.in[0], bytes))) return rc;
+  if (!s.h_tail) {
+    if (int qrc = quiesce_for_allocation(ctx, "the landing place of an inversion's product")) return qrc;
+    HIP_TRY(ctx, hipHostMalloc((void**)&s.h_tail, 64, hipHostMallocDefault));
+  }
+  const void* d_in = in;
+  void* d_out = out;
+  if (host) {   // staged, inverted in place, copied back
+    if ((rc = staged_upload(ctx, s.in[0].p, in, bytes, st))) return rc;
+    d_in = d_out = s.in[0].p;
+  }
+  // span 1: the products; T and the zero count come back
+  HIP_TRY(ctx, hipEventRecord(s.ev[0], st));
+  launch_fr_inv_products(st, scalar_layout, d_in, n, tile_log, s.work.p);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(s.ev[1], st));
+  HIP_TRY(ctx, hipMemcpyAsync(s.h_tail, fr_inv_tail(s.work.p, plan), 64, hipMemcpyDeviceToHost, st));
+  if ((rc = sync_stream_bounded(ctx, st, who.c_str()))) return rc;
+  u256 total;
+  uint64_t zeros;
+  std::memcpy(total.v, s.h_tail, 32);
+  std::memcpy(&zeros, s.h_tail + 32, 8);
+  const u256 t_inv = ntt_fr_inv(total);   // zeros were read as one: T != 0
+  // span 2: every record's inverse
+  HIP_TRY(ctx, hipEventRecord(s.ev[2], st));
+  launch_fr_inv_apply(st, scalar_layout, d_in, n, tile_log, s.work.p, t_inv, d_out);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(s.ev[3], st));
+  if (host) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
+  if ((rc = sync_stream_bounded(ctx, st, who.c_str()))) return rc;
+  if (n_zero) *n_zero = zeros;
+  if (kernel_ms) *kernel_ms = event_span(s.ev[0], s.ev[1]) + event_span(s.ev[2], s.ev[3]);
+  return MSM_AMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_fr_map(msm_amd_ctx* ctx, int op, int scalar_layout, const void* k32, const void* a, const void* b, const void* c,
+                   size_t n, void* out) {
+  return fr_map_call(ctx, true, op, scalar_layout, k32, a, b, c, n, out, nullptr);
+}
+
+int msm_amd_fr_map_device(msm_amd_ctx* ctx, int op, int scalar_layout, const void* k32, const void* d_a, const void* d_b,
+                          const void* d_c, size_t n, void* d_out, float* kernel_ms) {
+  return fr_map_call(ctx, false, op, scalar_layout, k32, d_a, d_b, d_c, n, d_out, kernel_ms);
+}
+
+int msm_amd_fr_batch_inverse(msm_amd_ctx* ctx, int scalar_layout, const void* in, size_t n, void* out, uint64_t* n_zero) {
+  return fr_inverse_call(ctx, true, scalar_layout, in, n, out, n_zero, nullptr);
+}
+
+int msm_amd_fr_batch_inverse_device(msm_amd_ctx* ctx, int scalar_layout, const void* d_in, size_t n, void* d_out,
+                                    uint64_t* n_zero, float* kernel_ms) {
+  return fr_inverse_call(ctx, false, scalar_layout, d_in, n, d_out, n_zero, kernel_ms);
+}
+
+int msm_amd_fr_prefix_product(msm_amd_ctx* ctx, int scalar_layout, int mode, const void* in, size_t n, size_t n_vec,
+                              void* out) {
+  return fr_prefix_call(ctx, true, scalar_layout, mode, in, n, n_vec, out, nullptr);
+}
+
+int msm_amd_fr_prefix_product_device(msm_amd_ctx* ctx, int scalar_layout, int mode, const void* d_in, size_t n, size_t n_vec,
+                                     void* d_out, float* kernel_ms) {
+  return fr_prefix_call(ctx, false, scalar_layout, mode, d_in, n, n_vec, d_out, kernel_ms);
 }
 
 }  // extern "C"
