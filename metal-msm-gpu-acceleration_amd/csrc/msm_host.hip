@@ -22,6 +22,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/msm_amd.h"
@@ -174,59 +175,59 @@ struct Batch {
   bool abandoned = false;   // a blocking entry point gave up waiting for it (wait timeout): released once the device is idle
 };
 
-// Precomputed window tables of one set of bases (msm_amd_tables_*): tables[w * n + i] = 2^(c w) P_i, packed form.
-// Handles are validated by membership in msm_amd_ctx::live_tables, never by dereferencing the caller's pointer.
-struct TablesRecord {
+// What the three handle kinds share: one device allocation.  Handles are validated by membership in the live list of
+// their kind (find_handle), never by dereferencing the caller's pointer; each kind is a type and a live list of its own,
+// so that a G1 table handle is no G2 table handle, neither is a transform domain, and the reverse.
+struct DeviceHandle {
+  void* d_mem = nullptr;
+  size_t bytes = 0;
+};
+
+// Precomputed window tables of one set of bases (msm_amd_tables_*, msm_amd_g2_tables_*): d_mem[w * n + i] = 2^(c w) P_i,
+// W * n AffPacked (G1, msm_amd_ctx::live_tables) or Aff2Packed (G2, msm_amd_ctx::live_g2_tables).
+struct TablesRecord : DeviceHandle {
   size_t n = 0;
   uint32_t c = 0, W = 0;
-  void* d_tables = nullptr;   // W * n AffPacked (G1) or Aff2Packed (G2)
 };
 struct msm_amd_tables : TablesRecord {};
-
-// The same record for G2 (msm_amd_g2_tables_*), as a type and a live list (msm_amd_ctx::live_g2_tables) of its own, so
-// that a G1 handle is no G2 handle and the reverse.
 struct msm_amd_g2_tables : TablesRecord {};
 
-// The twiddles of one (root, log_n) (msm_amd_ntt_domain_*): d_tw[j] = omega^j, j < n/2, Montgomery.  A handle type and
-// a live list (msm_amd_ctx::live_ntt) of its own: a table handle is no domain and the reverse.
-struct msm_amd_ntt_domain {
+// The twiddles of one (root, log_n) (msm_amd_ntt_domain_*, msm_amd_ctx::live_ntt): d_mem[j] = omega^j, j < n/2, Montgomery.
+struct msm_amd_ntt_domain : DeviceHandle {
   int root = 0;
   uint32_t log_n = 0;
-  size_t bytes = 0;
-  void* d_tw = nullptr;
   u256 omega{};
 };
 
-// Buffers of the transform calls (ntt_call): the ONE batch-sized scratch of a plan with more than one pass, the power
-// table of a call's shift and the two events behind kernel_ms.  Host input is staged in the scalar staging of the G1
-// point calls (PointCallState::in[0]) and transformed in place there.
-struct NttState {
-  DeviceBuf scratch, pow;
-  hipEvent_t ev[2] = {};
-};
-
-// Buffers of the Fr vector calls (fr_*_call): the staging of the host-buffer forms (three operands; the result is
-// written over the first), the tile totals of a scan or an inversion (fr_scan_plan, fr_inv_plan), the page-locked
-// landing place of an inversion's T and zero count, and two pairs of events behind kernel_ms.
-struct FrState {
-  DeviceBuf in[3], work;
-  uint8_t* h_tail = nullptr;   // pinned: T (32 bytes), then the zero count
-  hipEvent_t ev[4] = {};
-};
-
-// Buffers of the point calls of one group (check, decompress, compress and mul_points; point_call below): the staging of
-// the host-buffer calls, the 64-byte counters with their page-locked copy and events, and the device-side scratch of
-// mul_points.  One per group: a G2 call touches G2State only.
-struct PointCallState {
-  enum { EV_PT_START = 0, EV_PT_KERNEL, EV_PT_DONE, EV_PT_COUNT };
-  DeviceBuf in[2], out, reasons;   // staging of host inputs (mul_points: scalars, bases), output and reason bytes
-  DeviceBuf counters;              // PointCounters
+// Buffers of the blocking vector calls (device_call below): the staging of the host-buffer forms, the 64-byte record a
+// call reads back with its page-locked copy (the PointCounters of a check, decompress or compress call; T and the zero
+// count of a batch inversion), the device-side work buffers and two pairs of events behind kernel_ms.  Every such call
+// starts on an idle ctx and blocks until it is done, so one set serves the G1 point calls, the transform and the Fr
+// vector calls; G2State has a second one, so that a G2 call touches G2State only.
+struct CallState {
+  DeviceBuf in[3], out, reasons;   // staging of host inputs, output and reason bytes
+  DeviceBuf record;                // PointCounters
   DeviceBuf table, xyzz;           // mul_points: the fixed-base table, the XYZZ records of one chunk of outputs
-  PointCounters* h_counters = nullptr;   // pinned
-  hipEvent_t ev[EV_PT_COUNT] = {};
-  bool ready = false;              // counters, h_counters and ev exist
-  std::array<DeviceBuf*, 7> bufs() { return {&in[0], &in[1], &out, &reasons, &counters, &table, &xyzz}; }
+  DeviceBuf scratch, pow;          // transform: the ONE batch-sized scratch of a plan with more than one pass, the powers of a shift
+  DeviceBuf work;                  // Fr scan and inversion: the tile totals (fr_scan_plan, fr_inv_plan)
+  uint8_t* h_record = nullptr;     // pinned, 64 bytes
+  hipEvent_t ev[4] = {};           // start and end of the first and of the second span
+  bool ready = false;              // record, h_record and ev exist
+  // everything but the record: what a kernel reads only after its own call has written it, so what
+  // msm_amd_test_fill_workspaces may poison
+  std::array<DeviceBuf*, 10> scratch_bufs() { return {&in[0], &in[1], &in[2], &out, &reasons, &table, &xyzz, &scratch, &pow, &work}; }
+  // msm_amd_destroy, with its own ways of releasing a buffer and an event
+  template <class KillBuf, class KillEvent>
+  void release(KillBuf kill_buf, KillEvent kill_event) {
+    kill_buf(record);
+    for (DeviceBuf* b : scratch_bufs()) kill_buf(*b);
+    for (hipEvent_t& e : ev) kill_event(e);
+    if (h_record) (void)hipHostFree(h_record);
+    h_record = nullptr;
+    ready = false;
+  }
 };
+static_assert(sizeof(PointCounters) == 64, "CallState::record and h_record hold one PointCounters");
 
 // State of the G2 MSM (msm_amd_msm_g2*): one blocking call at a time on the main stream, through the instance body of
 // G1 (enqueue_instance) in a workspace and a slot of its own -- a G2 call never touches what a G1 instance of the same
@@ -235,7 +236,7 @@ struct G2State {
   Workspace ws;
   InstanceSlot slot;
   DeviceBuf in_scalars, in_points;   // staging of host inputs
-  PointCallState points;   // the G2 point calls; msm_amd_g2_check_points stages host points in in_points above
+  CallState calls;   // the G2 point calls; msm_amd_g2_check_points stages host points in in_points above
   // Stage tap (msm_amd_test_g2_last_plan / msm_amd_test_g2_stage_copy): the plan of the last run_msm_g2, valid only
   // while that call was the last one and succeeded.  Its plan counters are in `slot`, behind the partial points.
   Plan last_plan{};
@@ -264,7 +265,7 @@ struct msm_amd_ctx {
   bool lone_single_stream = true;        // MSM_AMD_LONE_SINGLE_STREAM=0: a lone instance uses the stream split too
   Workspace ws[kWorkspaces];
   G2State g2;
-  PointCallState points;   // the G1 point calls
+  CallState calls;   // the G1 point calls, the transform and the Fr vector calls
   size_t mul_chunk = (size_t)1 << 18;   // outputs per chunk of a mul_points call (MSM_AMD_MUL_CHUNK), a multiple of kMulNormGroup
   std::mutex mu;
   std::string last_error;
@@ -272,8 +273,6 @@ struct msm_amd_ctx {
   std::vector<msm_amd_tables*> live_tables;
   std::vector<msm_amd_g2_tables*> live_g2_tables;
   std::vector<msm_amd_ntt_domain*> live_ntt;
-  NttState ntt;
-  FrState fr;
   uint32_t fr_tile_log = kFrTileLog;     // records per tile of a scan, as a power of two (MSM_AMD_FR_TILE_LOG)
   uint32_t ntt_tile_log = kNttTileLog;   // elements per workgroup of a transform pass, as a power of two (MSM_AMD_NTT_TILE_LOG)
   int next_ws = 0;
@@ -849,9 +848,10 @@ int reduce_buffers(msm_amd_ctx* ctx, Workspace& w, const Plan& p, size_t interna
   return ensure(ctx, w.partial, p.partial_count * ext_bytes);
 }
 
-// ---- table handles, G1 and G2: H = msm_amd_tables (ctx->live_tables) or msm_amd_g2_tables (ctx->live_g2_tables) ----
+// ---- handles: H = msm_amd_tables (ctx->live_tables), msm_amd_g2_tables (ctx->live_g2_tables) or msm_amd_ntt_domain
+// (ctx->live_ntt).  ctx->mu is held by the caller, as for every helper here.
 template <class H>
-const H* find_tables(const std::vector<H*>& live, const void* handle) {
+const H* find_handle(const std::vector<H*>& live, const void* handle) {
   for (const H* t : live)
     if ((const void*)t == handle) return t;
   return nullptr;
@@ -866,66 +866,72 @@ int tables_geometry(msm_amd_ctx* ctx, size_t n, uint32_t window_size, uint32_t a
   return MSM_AMD_OK;
 }
 
-// The tail of a table build: room for W * n records of record_bytes, the build kernel (`launch(d_tables)` on
-// ctx->stream), a bounded wait and the new handle in `live`.  `what` names the group in messages ("" or "G2 ").
+// The tail of a build: `bytes` of device memory (`memory` names it in messages), the build kernel (`launch(d_mem)` on
+// ctx->stream), a bounded wait (for `build`) and the new handle in `live`; the caller fills in what its kind adds to
+// DeviceHandle.
 template <class H, class Launch>
-int tables_build_tail(msm_amd_ctx* ctx, std::vector<H*>& live, size_t n, uint32_t c, uint32_t W, size_t record_bytes,
-                      const std::string& what, Launch&& launch, H** out) {
-  void* d_tab = nullptr;
-  if (int qrc = quiesce_for_allocation(ctx, ("the " + what + "window tables").c_str())) return qrc;
-  HIP_TRY(ctx, hipMalloc(&d_tab, (size_t)W * n * record_bytes));
-  launch(d_tab);
+int handle_build_tail(msm_amd_ctx* ctx, std::vector<H*>& live, size_t bytes, const std::string& memory,
+                      const std::string& build, Launch&& launch, H** out) {
+  void* d_mem = nullptr;
+  if (int qrc = quiesce_for_allocation(ctx, memory.c_str())) return qrc;
+  HIP_TRY(ctx, hipMalloc(&d_mem, bytes));
+  launch(d_mem);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess && sync_stream_bounded(ctx, ctx->stream, (what + "table build").c_str())) {
-    ctx->graveyard.push_back(d_tab);   // the build may still be running: released when the ctx is idle
+  if (e == hipSuccess && sync_stream_bounded(ctx, ctx->stream, build.c_str())) {
+    ctx->graveyard.push_back(d_mem);   // the build may still be running: released when the ctx is idle
     return MSM_AMD_PIPELINE_ERROR;
   }
   if (e != hipSuccess) {
-    (void)hipFree(d_tab);
+    (void)hipFree(d_mem);
     HIP_TRY(ctx, e);
   }
-  H* t = new H();
-  t->n = n;
-  t->c = c;
-  t->W = W;
-  t->d_tables = d_tab;
-  live.push_back(t);
-  *out = t;
+  H* h = new H();
+  h->d_mem = d_mem, h->bytes = bytes;
+  live.push_back(h);
+  *out = h;
   return MSM_AMD_OK;
 }
 
-// ctx->mu held by the caller, as for every helper here
+// Room for W * n records of record_bytes and handle_build_tail; `group` is "" or "G2 " in messages.
+template <class H, class Launch>
+int tables_build_tail(msm_amd_ctx* ctx, std::vector<H*>& live, size_t n, uint32_t c, uint32_t W, size_t record_bytes,
+                      const std::string& group, Launch&& launch, H** out) {
+  if (int rc = handle_build_tail(ctx, live, (size_t)W * n * record_bytes, "the " + group + "window tables",
+                                 group + "table build", launch, out)) return rc;
+  (*out)->n = n, (*out)->c = c, (*out)->W = W;
+  return MSM_AMD_OK;
+}
+
 template <class H>
-int tables_info(msm_amd_ctx* ctx, const std::vector<H*>& live, const H* tables, size_t record_bytes,
-                const char* not_a_handle, size_t* n, uint32_t* window_size, uint32_t* num_windows,
-                size_t* device_bytes) {
-  const H* t = find_tables(live, tables);
+int tables_info(msm_amd_ctx* ctx, const std::vector<H*>& live, const H* tables, const char* not_a_handle, size_t* n,
+                uint32_t* window_size, uint32_t* num_windows, size_t* device_bytes) {
+  const H* t = find_handle(live, tables);
   if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, not_a_handle);
   if (n) *n = t->n;
   if (window_size) *window_size = t->c;
   if (num_windows) *num_windows = t->W;
-  if (device_bytes) *device_bytes = (size_t)t->W * t->n * record_bytes;
+  if (device_bytes) *device_bytes = t->bytes;
   return MSM_AMD_OK;
 }
 
 template <class H>
-int tables_free(msm_amd_ctx* ctx, std::vector<H*>& live, H* tables, const char* not_a_handle) {
-  auto it = std::find(live.begin(), live.end(), tables);
+int handle_free(msm_amd_ctx* ctx, std::vector<H*>& live, H* handle, const char* not_a_handle) {
+  auto it = std::find(live.begin(), live.end(), handle);
   if (it == live.end()) return fail(ctx, MSM_AMD_INPUT_ERROR, not_a_handle);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   live.erase(it);
-  if (drain_or_mark_stalled(ctx)) (void)hipFree(tables->d_tables);
-  else ctx->graveyard.push_back(tables->d_tables);   // hipFree would wait for the device without bound
-  delete tables;
+  if (drain_or_mark_stalled(ctx)) (void)hipFree(handle->d_mem);
+  else ctx->graveyard.push_back(handle->d_mem);   // hipFree would wait for the device without bound
+  delete handle;
   return MSM_AMD_OK;
 }
 
-// msm_amd_destroy: tables the caller did not free
+// msm_amd_destroy: handles the caller did not free
 template <class H>
-void tables_release_all(std::vector<H*>& live) {
-  for (H* t : live) {
-    (void)hipFree(t->d_tables);
-    delete t;
+void handle_release_all(std::vector<H*>& live) {
+  for (H* h : live) {
+    (void)hipFree(h->d_mem);
+    delete h;
   }
   live.clear();
 }
@@ -1163,7 +1169,7 @@ int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_l
                 const void* d_points, size_t n, Plan* plan_out, bool lone) {
   const msm_amd_tables* tb = nullptr;
   if (point_layout == MSM_AMD_POINT_TABLES) {
-    tb = find_tables(ctx->live_tables, d_points);
+    tb = find_handle(ctx->live_tables, d_points);
     if (!tb) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a table handle of this ctx");
     if (n != tb->n) return fail(ctx, MSM_AMD_INPUT_ERROR, "n differs from the number of points the tables hold");
   }
@@ -1204,7 +1210,7 @@ int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_l
     return MSM_AMD_OK;
   };
   g.accumulate = [&](hipStream_t st, const SortBuffers& sb, hipEvent_t before, hipEvent_t after) {
-    const void* bases = tb ? tb->d_tables
+    const void* bases = tb ? tb->d_mem
                            : (prepared ? d_points : (fill ? (const void*)fill : (in_place ? (const void*)ext_bases : w.bases29.p)));
     launch_accumulate(st, p, bases, wide ? 1 : 0, sb, (PtI*)w.buckets.p, (PtI*)w.item_partials.p, ctx->acc_variant,
                       ctx->acc_lds, before, after);
@@ -2220,12 +2226,6 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
     kill_event(ctx->ws[k].reduce_done);
   }
   kill_slot_events(ctx->g2.slot);   // (g2.ws has no hand-off events)
-  for (PointCallState* ps : {&ctx->points, &ctx->g2.points}) {
-    for (hipEvent_t& e : ps->ev) kill_event(e);
-    ps->ready = false;
-  }
-  for (hipEvent_t& e : ctx->ntt.ev) kill_event(e);
-  for (hipEvent_t& e : ctx->fr.ev) kill_event(e);
   for (hipEvent_t& e : ctx->uploaded) kill_event(e);
   kill_event(ctx->upload_done);
   kill_event(ctx->after_sort_mark);
@@ -2248,22 +2248,10 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
   kill_workspace(ctx->g2.ws);
   for (DeviceBuf* b : {&ctx->g2.in_scalars, &ctx->g2.in_points}) kill_buf(*b);
   kill_slot_memory(ctx->g2.slot);
-  for (PointCallState* ps : {&ctx->points, &ctx->g2.points}) {
-    for (DeviceBuf* b : ps->bufs()) kill_buf(*b);
-    if (ps->h_counters) (void)hipHostFree(ps->h_counters);
-    ps->h_counters = nullptr;
-  }
-  tables_release_all(ctx->live_tables);
-  tables_release_all(ctx->live_g2_tables);
-  for (msm_amd_ntt_domain* d : ctx->live_ntt) {   // domains the caller did not free
-    (void)hipFree(d->d_tw);
-    delete d;
-  }
-  ctx->live_ntt.clear();
-  for (DeviceBuf* b : {&ctx->ntt.scratch, &ctx->ntt.pow}) kill_buf(*b);
-  for (DeviceBuf* b : {&ctx->fr.in[0], &ctx->fr.in[1], &ctx->fr.in[2], &ctx->fr.work}) kill_buf(*b);
-  if (ctx->fr.h_tail) (void)hipHostFree(ctx->fr.h_tail);
-  ctx->fr.h_tail = nullptr;
+  for (CallState* cs : {&ctx->calls, &ctx->g2.calls}) cs->release(kill_buf, kill_event);
+  handle_release_all(ctx->live_tables);   // handles the caller did not free
+  handle_release_all(ctx->live_g2_tables);
+  handle_release_all(ctx->live_ntt);
   for (DeviceBuf* b : {&ctx->scratch_a, &ctx->scratch_b, &ctx->scratch_c, &ctx->scratch_b2, &ctx->scratch_c2}) kill_buf(*b);
   bases_cache_clear(ctx);   // (entries and unused reserves go through the graveyard)
   for (const msm_amd_ctx::CacheReserve& r : ctx->cache_reserve) ctx->graveyard.push_back(r.d);
@@ -2740,14 +2728,14 @@ int msm_amd_tables_info(msm_amd_ctx* ctx, const msm_amd_tables* tables, size_t* 
                         uint32_t* num_windows, size_t* device_bytes) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
   std::lock_guard<std::mutex> g(ctx->mu);
-  return tables_info(ctx, ctx->live_tables, tables, sizeof(AffPacked), "not a table handle of this ctx", n, window_size,
+  return tables_info(ctx, ctx->live_tables, tables, "not a table handle of this ctx", n, window_size,
                      num_windows, device_bytes);
 }
 
 int msm_amd_tables_free(msm_amd_ctx* ctx, msm_amd_tables* tables) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
   std::lock_guard<std::mutex> g(ctx->mu);
-  return tables_free(ctx, ctx->live_tables, tables, "not a table handle of this ctx");
+  return handle_free(ctx, ctx->live_tables, tables, "not a table handle of this ctx");
 }
 
 int msm_amd_msm_tables(msm_amd_ctx* ctx, const msm_amd_tables* tables, int scalar_layout, const void* scalars,
@@ -2755,7 +2743,7 @@ int msm_amd_msm_tables(msm_amd_ctx* ctx, const msm_amd_tables* tables, int scala
   if (!ctx || !tables || !scalars || !out96) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad msm_tables arguments");
   if (!scalar_layout_ok(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
   std::lock_guard<std::mutex> g(ctx->mu);
-  const msm_amd_tables* t = find_tables(ctx->live_tables, tables);
+  const msm_amd_tables* t = find_handle(ctx->live_tables, tables);
   if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a table handle of this ctx");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   int rc;
@@ -3343,13 +3331,9 @@ int msm_amd_test_fill_workspaces(msm_amd_ctx* ctx, uint8_t byte) {
   for (Workspace* w : all)
     for (DeviceBuf* b : {&w->buckets, &w->item_partials, &w->S, &w->T, &w->partial})
       if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
-  for (PointCallState* ps : {&ctx->points, &ctx->g2.points})   // the XYZZ records and the fixed-base table of the mul_points calls
-    for (DeviceBuf* b : {&ps->xyzz, &ps->table})
+  for (CallState* cs : {&ctx->calls, &ctx->g2.calls})   // staging and work buffers of the vector calls; never their 64-byte record
+    for (DeviceBuf* b : cs->scratch_bufs())
       if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
-  for (DeviceBuf* b : {&ctx->ntt.scratch, &ctx->ntt.pow})   // the transform's pass buffer and shift powers
-    if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
-  for (DeviceBuf* b : {&ctx->fr.in[0], &ctx->fr.in[1], &ctx->fr.in[2], &ctx->fr.work})   // the Fr vector calls: staging, tile totals
-    if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
   return sync_stream_bounded(ctx, ctx->stream, __func__);
 }
 
@@ -3387,7 +3371,7 @@ int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const v
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const msm_amd_g2_tables* tb = nullptr;
   if (g2_point_layout == MSM_AMD_G2_POINT_TABLES) {   // d_points is the handle of msm_amd_g2_tables_build*
-    tb = find_tables(ctx->live_g2_tables, d_points);
+    tb = find_handle(ctx->live_g2_tables, d_points);
     if (!tb) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
     if (n != tb->n) return fail(ctx, MSM_AMD_INPUT_ERROR, "n differs from the number of points the tables hold");
   }
@@ -3407,7 +3391,7 @@ int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const v
     return MSM_AMD_OK;
   };
   g.accumulate = [&](hipStream_t st, const SortBuffers& sb, hipEvent_t before, hipEvent_t after) {
-    const void* bases = tb ? tb->d_tables : (prepared ? d_points : w.bases29.p);
+    const void* bases = tb ? tb->d_mem : (prepared ? d_points : w.bases29.p);
     (void)hipEventRecord(before, st);
     launch_accumulate_g2(st, p, (const Aff2Packed*)bases, sb, (PtI2*)w.buckets.p, (PtI2*)w.item_partials.p);
     (void)hipEventRecord(after, st);
@@ -3563,14 +3547,14 @@ int msm_amd_g2_tables_info(msm_amd_ctx* ctx, const msm_amd_g2_tables* tables, si
                            uint32_t* num_windows, size_t* device_bytes) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
   std::lock_guard<std::mutex> g(ctx->mu);
-  return tables_info(ctx, ctx->live_g2_tables, tables, sizeof(Aff2Packed), "not a G2 table handle of this ctx", n,
+  return tables_info(ctx, ctx->live_g2_tables, tables, "not a G2 table handle of this ctx", n,
                      window_size, num_windows, device_bytes);
 }
 
 int msm_amd_g2_tables_free(msm_amd_ctx* ctx, msm_amd_g2_tables* tables) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
   std::lock_guard<std::mutex> g(ctx->mu);
-  return tables_free(ctx, ctx->live_g2_tables, tables, "not a G2 table handle of this ctx");
+  return handle_free(ctx, ctx->live_g2_tables, tables, "not a G2 table handle of this ctx");
 }
 
 int msm_amd_msm_g2_tables(msm_amd_ctx* ctx, const msm_amd_g2_tables* tables, int scalar_layout, const void* scalars,
@@ -3578,7 +3562,7 @@ int msm_amd_msm_g2_tables(msm_amd_ctx* ctx, const msm_amd_g2_tables* tables, int
   if (!ctx || !tables || !scalars || !out192) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad msm_g2_tables arguments");
   if (!scalar_layout_ok(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
   std::lock_guard<std::mutex> g(ctx->mu);
-  const msm_amd_g2_tables* t = find_tables(ctx->live_g2_tables, tables);
+  const msm_amd_g2_tables* t = find_handle(ctx->live_g2_tables, tables);
   if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
   if (int rc = g2_stage_scalars(ctx, scalars, t->n)) return rc;
   return run_msm_g2(ctx, scalar_layout, MSM_AMD_G2_POINT_TABLES, ctx->g2.in_scalars.p, tables, t->n, out192);
@@ -3588,13 +3572,13 @@ int msm_amd_test_g2_tables_read(msm_amd_ctx* ctx, const msm_amd_g2_tables* table
                                 size_t count, void* out) {
   if (!ctx || !out || count == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad g2_tables_read arguments");
   std::lock_guard<std::mutex> g(ctx->mu);
-  const msm_amd_g2_tables* t = find_tables(ctx->live_g2_tables, tables);
+  const msm_amd_g2_tables* t = find_handle(ctx->live_g2_tables, tables);
   if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
   if (w >= t->W || first >= t->n || count > t->n - first)
     return fail(ctx, MSM_AMD_INPUT_ERROR, "window or point range outside the table");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   std::vector<Aff2Packed> rec(count);
-  HIP_TRY(ctx, hipMemcpyAsync(rec.data(), (const Aff2Packed*)t->d_tables + (size_t)w * t->n + first,
+  HIP_TRY(ctx, hipMemcpyAsync(rec.data(), (const Aff2Packed*)t->d_mem + (size_t)w * t->n + first,
                               count * sizeof(Aff2Packed), hipMemcpyDeviceToHost, ctx->stream));
   if (int rc = sync_stream_bounded(ctx, ctx->stream, __func__)) return rc;
   for (size_t i = 0; i < count; ++i) {
@@ -3678,134 +3662,174 @@ int msm_amd_test_op_g2(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32
 
 }  // extern "C"
 
-// ---- the point calls: check, decompress, compress and mul_points of both groups -------------------------------------
-// One discipline for all sixteen entry points (point_call): ctx lock, bounded drain of the ctx's earlier work, every
-// buffer sized on the idle ctx before anything is enqueued, host input through the page-locked staging ring, the
-// caller's kernels on the main stream, a bounded poll for the 64-byte counters (the calls that have them), output and
-// reason bytes behind a bounded stream wait.  Each call below validates its own enums, describes its buffers in a
-// PointCall and passes two callables: one enqueues its kernels, one takes the finished counters.
+// ---- the blocking vector calls: the point calls of both groups, the transform, the vectors over Fr ------------------------
+// One driver for all of them (device_call): the device set, a bounded drain of the ctx's earlier work, every buffer sized
+// on the idle ctx before anything is enqueued, host input through the page-locked staging ring, the caller's kernels on
+// the main stream (between events when the call is timed), the 64-byte record of a call that has one behind a bounded
+// wait, output and reason bytes behind a bounded stream wait.  Each call below validates its own arguments, takes
+// ctx->mu, describes its buffers in a DeviceCall and passes a callable that enqueues its kernels; one that takes the
+// finished record, and the kernels that follow it, are optional.
 namespace {
 
-struct PointCall {
-  std::string who;                  // the entry point, in every message
-  const char* first_use = nullptr;  // counters != 0: what a first call of the group names when it has to wait to allocate
-  bool g2 = false, host = false;    // host: in / out / reasons are host memory and go through the group's staging
-  bool counters = false;            // reset, timed by events and read back; mul_points has none
-  bool null_arg = false;            // some required pointer is null
-  size_t n = 0;                     // records (and reason bytes)
-  const void* in[2] = {};
-  size_t in_bytes[2] = {};
+struct DeviceCall {
+  std::string who;              // the entry point, in every message
+  bool g2 = false;              // the buffers are G2State::calls
+  bool host = false;            // out / reasons are host memory: written in the staging and copied back
+  unsigned host_in = 0;         // bit k: in[k] is host memory and goes through the staging
+  bool in_place = false;        // host: the result is written over the staged in[0] and copied back from there
+  bool counters = false;        // the record is PointCounters: reset before the kernels, read back behind them
+  float* kernel_ms = nullptr;   // optional: the device time of the kernels
+  size_t n = 0;                 // reason bytes
+  const void* in[3] = {};
+  size_t in_bytes[3] = {};
+  DeviceBuf* stage[3] = {};     // the staging of in[k] if not CallState::in[k] (G2State::in_points, CallState::pow)
   void* out = nullptr;
   size_t out_bytes = 0;
-  uint8_t* reasons = nullptr;       // optional
-  size_t table_bytes = 0, xyzz_bytes = 0;
-  DeviceBuf* stage_in0 = nullptr;   // staging of in[0] if not the state's own (the G2 check: G2State::in_points)
+  uint8_t* reasons = nullptr;   // optional
+  struct {
+    DeviceBuf* buf;
+    size_t bytes;
+  } work[2] = {};               // device-side buffers of the kernels
+  void all_host(bool h) { host = h, host_in = h ? 7u : 0u; }
 };
 
 // what the kernels of a call see: device memory throughout
-struct PointIo {
-  const void* in[2];
+struct CallIo {
+  const void* in[3];
   void* out;
   uint8_t* reasons;
   PointCounters* counters;
-  void *table, *xyzz;
+  const void* record;   // the 64 bytes to read back: `counters` of a call that has them; else null, unless launch sets it
 };
 
-// launch(stream, io) enqueues the call's kernels; done(counters, device_ms) takes the result of a call with counters
-// (and the empty counters of a call with n == 0, whatever its kind).
-template <class Launch, class Done>
-int point_call(msm_amd_ctx* ctx, const PointCall& c, Launch launch, Done done) {
-  if (c.n > 0xFFFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": n >= 2^32");
-  if (c.n == 0) {
-    done(point_counters_empty(), 0.0f);
-    return MSM_AMD_OK;
-  }
-  if (c.null_arg) return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": null pointer with n > 0");
-  std::lock_guard<std::mutex> lk(ctx->mu);
+// ctx->mu is held.  launch(stream, io) enqueues the kernels and returns a status.  A call with a record gets it back
+// behind a bounded wait: then(record, device_ms) takes it on the host, and launch2(stream, io), if there is one,
+// enqueues the kernels that needed it.  kernel_ms is the time of the one or two spans of kernels, without the host's
+// step between them; an event is recorded only for a call that has counters or asks for the time (one hipEventRecord
+// costs ~6 us of stream idle time, see EV_START above).
+template <class Launch, class Then, class Launch2>
+int device_call(msm_amd_ctx* ctx, const DeviceCall& c, Launch launch, Then then, Launch2 launch2) {
+  constexpr bool two_spans = !std::is_null_pointer<Launch2>::value;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (int rc = recover_if_stalled(ctx)) return fail(ctx, rc, c.who + ": " + ctx->last_error);
   if (!drain_or_mark_stalled(ctx))
     return fail(ctx, MSM_AMD_PIPELINE_ERROR, c.who + ": device busy past the wait bound of " +
                                                  std::to_string(ctx->wait_timeout_ms) + " ms (msm_amd_synchronize waits again)");
-  PointCallState& s = c.g2 ? ctx->g2.points : ctx->points;
+  CallState& s = c.g2 ? ctx->g2.calls : ctx->calls;
   hipStream_t st = ctx->stream;
   int rc;
-  // the ctx is idle: the first call with counters allocates them, and every buffer of this call is sized now
-  if (c.counters && !s.ready) {
-    if ((rc = quiesce_for_allocation(ctx, c.first_use))) return rc;
-    if ((rc = ensure(ctx, s.counters, sizeof(PointCounters)))) return rc;
-    if (!s.h_counters) HIP_TRY(ctx, hipHostMalloc((void**)&s.h_counters, sizeof(PointCounters), hipHostMallocDefault));
+  // the ctx is idle: the first call creates the record and the events, and every buffer of this call is sized now
+  if (!s.ready) {
+    if ((rc = ensure(ctx, s.record, sizeof(PointCounters)))) return rc;
+    if (!s.h_record) HIP_TRY(ctx, hipHostMalloc((void**)&s.h_record, sizeof(PointCounters), hipHostMallocDefault));
     for (hipEvent_t& e : s.ev)
       if (!e) HIP_TRY(ctx, hipEventCreate(&e));
     s.ready = true;
   }
-  if ((rc = ensure(ctx, s.table, c.table_bytes))) return rc;
-  if ((rc = ensure(ctx, s.xyzz, c.xyzz_bytes))) return rc;
-  PointIo io = {{c.in[0], c.in[1]}, c.out, c.reasons, (PointCounters*)s.counters.p, s.table.p, s.xyzz.p};
-  if (c.host) {
-    DeviceBuf* stage[2] = {c.stage_in0 ? c.stage_in0 : &s.in[0], &s.in[1]};
-    for (int k = 0; k < 2; ++k)
-      if ((rc = ensure(ctx, *stage[k], c.in_bytes[k]))) return rc;
-    if ((rc = ensure(ctx, s.out, c.out_bytes))) return rc;
-    if (c.reasons && (rc = ensure(ctx, s.reasons, c.n))) return rc;
-    for (int k = 0; k < 2; ++k)
-      if (c.in_bytes[k]) {
-        if ((rc = staged_upload(ctx, stage[k]->p, c.in[k], c.in_bytes[k], st))) return rc;
-        io.in[k] = stage[k]->p;
-      }
-    if (c.out_bytes) io.out = s.out.p;
-    if (c.reasons) io.reasons = (uint8_t*)s.reasons.p;
+  for (const auto& w : c.work)
+    if (w.buf && (rc = ensure(ctx, *w.buf, w.bytes))) return rc;
+  DeviceBuf* stage[3];
+  for (int k = 0; k < 3; ++k) {
+    stage[k] = c.stage[k] ? c.stage[k] : &s.in[k];
+    if ((c.host_in >> k & 1) && (rc = ensure(ctx, *stage[k], c.in_bytes[k]))) return rc;
   }
-  if (c.counters) {
-    launch_point_reset(st, io.counters);
-    HIP_TRY(ctx, hipEventRecord(s.ev[PointCallState::EV_PT_START], st));
-  }
-  launch(st, io);
-  HIP_TRY(ctx, hipGetLastError());
-  if (c.counters) {
-    HIP_TRY(ctx, hipEventRecord(s.ev[PointCallState::EV_PT_KERNEL], st));
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_counters, io.counters, sizeof(PointCounters), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipEventRecord(s.ev[PointCallState::EV_PT_DONE], st));
-    const hipError_t we = wait_event(s.ev[PointCallState::EV_PT_DONE], ctx->wait_timeout_ms);
-    if (we == hipErrorNotReady) {
-      ctx->stalled = true;
-      return fail(ctx, MSM_AMD_PIPELINE_ERROR, "timed out after " + std::to_string(ctx->wait_timeout_ms) + " ms waiting for " + c.who);
+  if (c.host && !c.in_place && (rc = ensure(ctx, s.out, c.out_bytes))) return rc;
+  if (c.host && c.reasons && (rc = ensure(ctx, s.reasons, c.n))) return rc;
+  CallIo io = {{c.in[0], c.in[1], c.in[2]}, c.out, c.reasons, (PointCounters*)s.record.p, c.counters ? s.record.p : nullptr};
+  for (int k = 0; k < 3; ++k)
+    if ((c.host_in >> k & 1) && c.in_bytes[k]) {
+      if ((rc = staged_upload(ctx, stage[k]->p, c.in[k], c.in_bytes[k], st))) return rc;
+      io.in[k] = stage[k]->p;
     }
-    if (we != hipSuccess) return fail(ctx, MSM_AMD_PIPELINE_ERROR, c.who + ": " + hipGetErrorString(we));
-    done(*s.h_counters, event_span(s.ev[PointCallState::EV_PT_START], s.ev[PointCallState::EV_PT_KERNEL]));
+  if (c.host && c.out_bytes) io.out = c.in_place ? const_cast<void*>(io.in[0]) : s.out.p;
+  if (c.host && c.reasons) io.reasons = (uint8_t*)s.reasons.p;
+  const bool timed = c.counters || c.kernel_ms;
+  auto span = [&](auto& enqueue, int first_event) -> int {
+    if (timed) HIP_TRY(ctx, hipEventRecord(s.ev[first_event], st));
+    if (int lrc = enqueue(st, io)) return lrc;
+    HIP_TRY(ctx, hipGetLastError());
+    if (timed) HIP_TRY(ctx, hipEventRecord(s.ev[first_event + 1], st));
+    return MSM_AMD_OK;
+  };
+  if (c.counters) launch_point_reset(st, io.counters);
+  if ((rc = span(launch, 0))) return rc;
+  const bool has_record = io.record != nullptr;
+  bool pending = true;   // work enqueued and not waited for
+  float ms = 0.0f;
+  if (has_record) {
+    HIP_TRY(ctx, hipMemcpyAsync(s.h_record, io.record, sizeof(PointCounters), hipMemcpyDeviceToHost, st));
+    if ((rc = sync_stream_bounded(ctx, st, c.who.c_str()))) return rc;
+    if (timed) ms = event_span(s.ev[0], s.ev[1]);
+    then(s.h_record, ms);
+    if constexpr (two_spans) {
+      if ((rc = span(launch2, 2))) return rc;
+    } else {
+      pending = false;
+    }
   }
-  const bool copy_out = c.host && c.out_bytes, copy_reasons = c.host && c.reasons;
-  if (copy_out) HIP_TRY(ctx, hipMemcpyAsync(c.out, io.out, c.out_bytes, hipMemcpyDeviceToHost, st));
-  if (copy_reasons) HIP_TRY(ctx, hipMemcpyAsync(c.reasons, io.reasons, c.n, hipMemcpyDeviceToHost, st));
-  // (a call with counters and nothing to copy back has already waited for all of its work)
-  if (!c.counters || copy_out || copy_reasons) return sync_stream_bounded(ctx, st, c.who.c_str());
+  if (c.host && c.out_bytes) HIP_TRY(ctx, hipMemcpyAsync(c.out, io.out, c.out_bytes, hipMemcpyDeviceToHost, st));
+  if (c.host && c.reasons) HIP_TRY(ctx, hipMemcpyAsync(c.reasons, io.reasons, c.n, hipMemcpyDeviceToHost, st));
+  if (c.host && (c.out_bytes || c.reasons)) pending = true;
+  if (pending && (rc = sync_stream_bounded(ctx, st, c.who.c_str()))) return rc;
+  if (timed && !has_record) ms = event_span(s.ev[0], s.ev[1]);
+  if (timed && two_spans) ms += event_span(s.ev[2], s.ev[3]);
+  if (c.kernel_ms) *c.kernel_ms = ms;
   return MSM_AMD_OK;
+}
+
+template <class Launch, class Then>
+int device_call(msm_amd_ctx* ctx, const DeviceCall& c, Launch launch, Then then) {
+  return device_call(ctx, c, launch, then, nullptr);
+}
+
+template <class Launch>
+int device_call(msm_amd_ctx* ctx, const DeviceCall& c, Launch launch) {
+  return device_call(ctx, c, launch, [](const uint8_t*, float) {}, nullptr);
+}
+
+// The point calls: n records (and reason bytes) of host or of device memory throughout; null_arg: some required
+// pointer is null.  done(counters, device_ms) takes the result of a call with counters (and the empty counters of a
+// call with n == 0, whatever its kind).
+template <class Launch, class Done>
+int point_call(msm_amd_ctx* ctx, const DeviceCall& c, bool null_arg, Launch launch, Done done) {
+  if (c.n > 0xFFFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": n >= 2^32");
+  if (c.n == 0) {
+    done(point_counters_empty(), 0.0f);
+    return MSM_AMD_OK;
+  }
+  if (null_arg) return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": null pointer with n > 0");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return device_call(ctx, c, launch, [&](const uint8_t* record, float ms) {
+    PointCounters pc;
+    std::memcpy(&pc, record, sizeof pc);
+    done(pc, ms);
+  });
 }
 
 // ---- point validation (msm_amd_check_points*, msm_amd_g2_check_points*) ---------------------------------------------
 int check_call(msm_amd_ctx* ctx, bool g2, bool host, int layout, const void* points, size_t n, uint32_t checks,
                uint8_t* reasons, msm_amd_check_report* report) {
   if (!ctx || !report) return MSM_AMD_INPUT_ERROR;
-  PointCall c;
+  DeviceCall c;
   c.who = g2 ? "msm_amd_g2_check_points" : "msm_amd_check_points";   // the _device calls go by the same name
   const uint32_t stride = point_record_bytes(g2, layout, kKindHost);
   if (stride == 0)
     return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": takes the host point layouts only (not *_PREPARED / *_TABLES)");
   if (checks == 0 || (checks & ~(uint32_t)(MSM_AMD_CHECK_CURVE | MSM_AMD_CHECK_SUBGROUP)))
     return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": checks must be MSM_AMD_CHECK_CURVE and / or MSM_AMD_CHECK_SUBGROUP");
-  c.first_use = "the report buffer of a point check";
-  c.g2 = g2, c.host = host, c.counters = true, c.n = n;
-  c.null_arg = !points;
+  c.g2 = g2, c.counters = true, c.n = n;
+  c.all_host(host);
   c.in[0] = points, c.in_bytes[0] = n * stride;
   c.reasons = reasons;
-  if (g2) c.stage_in0 = &ctx->g2.in_points;
+  if (g2) c.stage[0] = &ctx->g2.in_points;
   return point_call(
-      ctx, c,
-      [&](hipStream_t st, const PointIo& io) {
+      ctx, c, !points,
+      [&](hipStream_t st, const CallIo& io) {
         if (g2)
           launch_check_g2(st, io.in[0], layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n, checks, io.reasons, io.counters);
         else
           launch_check_g1(st, io.in[0], layout, stride, (uint32_t)n, io.reasons, io.counters);
+        return MSM_AMD_OK;
       },
       [&](const PointCounters& pc, float ms) { point_report_decode(pc, n, ms, report); });
 }
@@ -3815,7 +3839,7 @@ int check_call(msm_amd_ctx* ctx, bool g2, bool host, int layout, const void* poi
 int compress_call(msm_amd_ctx* ctx, bool g2, bool host, bool decompress, int format, int layout, const void* in, size_t n,
                   void* out, uint8_t* reasons, msm_amd_decompress_report* report, uint64_t* n_bad) {
   if (!ctx || (decompress && !report)) return MSM_AMD_INPUT_ERROR;
-  PointCall c;
+  DeviceCall c;
   c.who = std::string(g2 ? "msm_amd_g2_" : "msm_amd_") + (decompress ? "decompress_points" : "compress_points") +
           (host ? "" : "_device");
   const bool prepared_ok = decompress && !host;
@@ -3826,19 +3850,19 @@ int compress_call(msm_amd_ctx* ctx, bool g2, bool host, bool decompress, int for
     return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + (prepared_ok ? ": takes the two affine layouts and *_PREPARED (not *_TABLES)"
                                                                : ": takes the two affine host layouts only"));
   const size_t wire = g2 ? 64 : 32;
-  c.first_use = "the report buffer of a decompress / compress call";
-  c.g2 = g2, c.host = host, c.counters = true, c.n = n;
-  c.null_arg = !in || !out;
+  c.g2 = g2, c.counters = true, c.n = n;
+  c.all_host(host);
   c.in[0] = in, c.in_bytes[0] = n * (decompress ? wire : stride);
   c.out = out, c.out_bytes = n * (decompress ? stride : wire);
   c.reasons = reasons;
   return point_call(
-      ctx, c,
-      [&](hipStream_t st, const PointIo& io) {
+      ctx, c, !in || !out,
+      [&](hipStream_t st, const CallIo& io) {
         if (decompress)
           launch_decompress(st, g2, format, io.in[0], (uint32_t)n, layout, stride, io.out, io.reasons, io.counters);
         else
           launch_compress(st, g2, layout, stride, io.in[0], (uint32_t)n, format, io.out, io.counters);
+        return MSM_AMD_OK;
       },
       [&](const PointCounters& pc, float ms) {
         if (decompress) point_report_decode(pc, n, ms, report);
@@ -3849,11 +3873,11 @@ int compress_call(msm_amd_ctx* ctx, bool g2, bool host, bool decompress, int for
 // ---- batch scalar multiplication (msm_amd_mul_points*, msm_amd_g2_mul_points*) ------------------------------------------
 // The outputs run in chunks of ctx->mul_chunk records (a multiple of the normalisation group, so the groups of a
 // chunked call are those of an unchunked one), all enqueued on the main stream: stream order hands the XYZZ buffer from
-// one chunk to the next.  No counters and no event wait: the bounded stream wait at the end of point_call is the call's.
+// one chunk to the next.  No counters and no event: the bounded stream wait at the end of device_call is the call's.
 int mul_call(msm_amd_ctx* ctx, bool g2, bool host, int scalar_layout, int layout_in, int base_mode, const void* scalars,
              const void* points, size_t n, int layout_out, void* out) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
-  PointCall c;
+  DeviceCall c;
   c.who = std::string(g2 ? "msm_amd_g2_mul_points" : "msm_amd_mul_points") + (host ? "" : "_device");
   const uint32_t prepared = host ? 0u : (uint32_t)kKindPrepared;
   const size_t in_stride = point_record_bytes(g2, layout_in, kKindHost | prepared),
@@ -3869,25 +3893,28 @@ int mul_call(msm_amd_ctx* ctx, bool g2, bool host, int scalar_layout, int layout
     return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": base_mode must be MSM_AMD_MUL_BASE_EACH or MSM_AMD_MUL_BASE_ONE");
   const bool one = base_mode == MSM_AMD_MUL_BASE_ONE;
   const size_t chunk = std::min(n, ctx->mul_chunk);
-  c.g2 = g2, c.host = host, c.n = n;
-  c.null_arg = !scalars || !points || !out;
+  CallState& s = g2 ? ctx->g2.calls : ctx->calls;
+  c.g2 = g2, c.n = n;
+  c.all_host(host);
   c.in[0] = scalars, c.in_bytes[0] = n * 32;
   c.in[1] = points, c.in_bytes[1] = (one ? 1 : n) * in_stride;
   c.out = out, c.out_bytes = n * out_stride;
-  c.table_bytes = one ? mul_table_bytes(g2) : 0, c.xyzz_bytes = chunk * mul_xyzz_bytes(g2);
+  c.work[0] = {&s.table, one ? mul_table_bytes(g2) : 0}, c.work[1] = {&s.xyzz, chunk * mul_xyzz_bytes(g2)};
   return point_call(
-      ctx, c,
-      [&](hipStream_t st, const PointIo& io) {
-        if (one) launch_mul_table(st, g2, layout_in, io.in[1], io.table);
+      ctx, c, !scalars || !points || !out,
+      [&](hipStream_t st, const CallIo& io) {
+        void *table = s.table.p, *xyzz = s.xyzz.p;
+        if (one) launch_mul_table(st, g2, layout_in, io.in[1], table);
         for (size_t first = 0; first < n; first += chunk) {
           const uint32_t m = (uint32_t)std::min(chunk, n - first);
           const uint8_t* sc = (const uint8_t*)io.in[0] + first * 32;
           if (one)
-            launch_mul_fixed(st, g2, scalar_layout, sc, m, io.table, io.xyzz);
+            launch_mul_fixed(st, g2, scalar_layout, sc, m, table, xyzz);
           else
-            launch_mul_each(st, g2, scalar_layout, sc, layout_in, (const uint8_t*)io.in[1] + first * in_stride, m, io.xyzz);
-          launch_mul_normalise(st, g2, io.xyzz, m, layout_out, (uint8_t*)io.out + first * out_stride);
+            launch_mul_each(st, g2, scalar_layout, sc, layout_in, (const uint8_t*)io.in[1] + first * in_stride, m, xyzz);
+          launch_mul_normalise(st, g2, xyzz, m, layout_out, (uint8_t*)io.out + first * out_stride);
         }
+        return MSM_AMD_OK;
       },
       [](const PointCounters&, float) {});
 }
@@ -3986,7 +4013,7 @@ int msm_amd_g2_mul_points_device(msm_amd_ctx* ctx, int scalar_layout, int g2_poi
 // ---- stage entries of the batch scalar multiplication (test aid: msm_amd_test_mul_stage, msm_amd_test_mul_stage_host) ----
 // The digit walk and the shared normalisation of mul_points.hip.h on inputs the public calls never produce: a table the
 // caller wrote (identity entries, an entry equal to a partial sum or to its negative) and XYZZ records at the edge of
-// the point invariant.  The device form goes through point_call and the launch wrappers of launch_mul.h like
+// the point invariant.  The device form goes through point_call (device_call) and the launch wrappers of launch_mul.h like
 // msm_amd_mul_points; the host form runs the bodies host_mul.hip runs.  NORMALISE works on a copy of the records,
 // because mul_normalise overwrites them; NORMALISE_RECORDS returns that copy instead of the affine bytes.
 namespace {
@@ -4042,30 +4069,29 @@ int msm_amd_test_mul_stage(msm_amd_ctx* ctx, int group, int which, int layout, c
   MulStage s;
   if (!mul_stage_shape(group, which, layout, &s))
     return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_mul_stage: unknown group, stage or layout");
-  PointCall c;
+  DeviceCall c;
   c.who = "msm_amd_test_mul_stage";
-  c.g2 = s.g2, c.host = true, c.n = n;
-  c.null_arg = !in || !out || (s.fixed && !table);
+  CallState& cs = s.g2 ? ctx->g2.calls : ctx->calls;
+  c.g2 = s.g2, c.n = n;
+  c.all_host(true);
   c.in[0] = in, c.in_bytes[0] = n * s.in_stride;
   c.in[1] = table, c.in_bytes[1] = s.fixed ? mul_table_bytes(s.g2) : 0;
   c.out = out, c.out_bytes = n * s.out_stride;
-  if (s.records) c.xyzz_bytes = n * s.affine_stride;   // where the affine bytes of NORMALISE_RECORDS go
-  hipError_t copied = hipSuccess;
-  const int rc = point_call(
-      ctx, c,
-      [&](hipStream_t st, const PointIo& io) {
+  if (s.records) c.work[0] = {&cs.xyzz, n * s.affine_stride};   // where the affine bytes of NORMALISE_RECORDS go
+  return point_call(
+      ctx, c, !in || !out || (s.fixed && !table),
+      [&](hipStream_t st, const CallIo& io) -> int {
         if (s.fixed) {
           launch_mul_fixed(st, s.g2, layout, io.in[0], (uint32_t)n, io.in[1], io.out);
         } else if (s.records) {   // the records move to the output buffer and are normalised there
-          copied = hipMemcpyAsync(io.out, io.in[0], n * s.in_stride, hipMemcpyDeviceToDevice, st);
-          launch_mul_normalise(st, s.g2, io.out, (uint32_t)n, layout, io.xyzz);
+          HIP_TRY(ctx, hipMemcpyAsync(io.out, io.in[0], n * s.in_stride, hipMemcpyDeviceToDevice, st));
+          launch_mul_normalise(st, s.g2, io.out, (uint32_t)n, layout, cs.xyzz.p);
         } else {                  // io.in[0] is the staged copy of the caller's records: the kernel may overwrite it
           launch_mul_normalise(st, s.g2, const_cast<void*>(io.in[0]), (uint32_t)n, layout, io.out);
         }
+        return MSM_AMD_OK;
       },
       [](const PointCounters&, float) {});
-  if (rc == MSM_AMD_OK && copied != hipSuccess) return fail(ctx, MSM_AMD_PIPELINE_ERROR, std::string("msm_amd_test_mul_stage: ") + hipGetErrorString(copied));
-  return rc;
 }
 
 int msm_amd_test_mul_stage_host(int group, int which, int layout, const void* in, const void* table, size_t n, void* out) {
@@ -4083,27 +4109,22 @@ int msm_amd_test_mul_stage_host(int group, int which, int layout, const void* in
 }  // extern "C"
 
 // ---- number-theoretic transform over Fr (msm_amd_ntt_domain_*, msm_amd_ntt, msm_amd_ntt_device) --------------------------
-// The discipline of point_call: ctx lock, bounded drain of the ctx's earlier work, every buffer sized on the idle ctx
-// before anything is enqueued, host input through the page-locked staging ring, the passes on the main stream, the
-// result behind a bounded stream wait.  Domain handles are validated by membership in ctx->live_ntt.
+// Through device_call: the passes on the main stream; the host form transforms the staged copy of its input in place.
+// Domain handles are validated by membership in ctx->live_ntt, under the lock and before anything is sized by them.
 namespace {
-
-const msm_amd_ntt_domain* find_ntt_domain(const msm_amd_ctx* ctx, const void* handle) {
-  for (const msm_amd_ntt_domain* d : ctx->live_ntt)
-    if ((const void*)d == handle) return d;
-  return nullptr;
-}
 
 int ntt_call(msm_amd_ctx* ctx, const msm_amd_ntt_domain* handle, bool host, int direction, int scalar_layout,
              const void* shift32, const void* in, void* out, size_t n_vec, float* kernel_ms) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
-  const std::string who = host ? "msm_amd_ntt" : "msm_amd_ntt_device";
+  DeviceCall c;
+  c.who = host ? "msm_amd_ntt" : "msm_amd_ntt_device";
+  const std::string& who = c.who;
   if (kernel_ms) *kernel_ms = 0.f;
   if (!ntt_direction_known(direction)) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": direction must be MSM_AMD_NTT_FORWARD or MSM_AMD_NTT_INVERSE");
   if (!ntt_layout_known(scalar_layout))
     return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": scalars in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE only");
   std::lock_guard<std::mutex> lk(ctx->mu);
-  const msm_amd_ntt_domain* dom = find_ntt_domain(ctx, handle);
+  const msm_amd_ntt_domain* dom = find_handle(ctx->live_ntt, handle);
   if (!dom) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": not a transform domain of this ctx");
   if (((uint64_t)n_vec >> (32 - dom->log_n)) != 0) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": n_vec * n >= 2^32");
   if (n_vec == 0) return MSM_AMD_OK;
@@ -4117,43 +4138,22 @@ int ntt_call(msm_amd_ctx* ctx, const msm_amd_ntt_domain* handle, bool host, int 
     if (a != b && a < b + bytes && b < a + bytes)
       return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": d_out must be d_in itself or disjoint from it");
   }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (int rc = recover_if_stalled(ctx)) return fail(ctx, rc, who + ": " + ctx->last_error);
-  if (!drain_or_mark_stalled(ctx))
-    return fail(ctx, MSM_AMD_PIPELINE_ERROR, who + ": device busy past the wait bound of " +
-                                                 std::to_string(ctx->wait_timeout_ms) + " ms (msm_amd_synchronize waits again)");
-  // the ctx is idle: every buffer of this call is sized now
-  NttState& s = ctx->ntt;
-  hipStream_t st = ctx->stream;
-  int rc;
-  NttLaunch c{};
-  c.tw = dom->d_tw, c.log_n = dom->log_n, c.tile_log = ctx->ntt_tile_log;
-  c.direction = direction, c.layout = scalar_layout, c.n_vec = n_vec;
-  u256 tab[kNttPowEntries];
-  ntt_shift_setup(g, direction, dom->log_n, tab, &c.sc);
-  if (ntt_plan(c.log_n, c.tile_log).passes > 1 && (rc = ensure(ctx, s.scratch, bytes))) return rc;
-  if (shift32 && (rc = ensure(ctx, s.pow, sizeof tab))) return rc;
-  if (host && (rc = ensure(ctx, ctx->points.in[0], bytes))) return rc;
-  for (hipEvent_t& e : s.ev)
-    if (!e) HIP_TRY(ctx, hipEventCreate(&e));
-  c.scratch = s.scratch.p;
-  c.in = in, c.out = out;
-  if (host) {   // staged, transformed in place, copied back
-    if ((rc = staged_upload(ctx, ctx->points.in[0].p, in, bytes, st))) return rc;
-    c.in = c.out = ctx->points.in[0].p;
-  }
-  if (shift32) {
-    if ((rc = staged_upload(ctx, s.pow.p, tab, sizeof tab, st))) return rc;
-    c.pow_tab = s.pow.p;
-  }
-  HIP_TRY(ctx, hipEventRecord(s.ev[0], st));
-  launch_ntt(st, c);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipEventRecord(s.ev[1], st));
-  if (host) HIP_TRY(ctx, hipMemcpyAsync(out, c.out, bytes, hipMemcpyDeviceToHost, st));
-  if ((rc = sync_stream_bounded(ctx, st, who.c_str()))) return rc;
-  if (kernel_ms) *kernel_ms = event_span(s.ev[0], s.ev[1]);
-  return MSM_AMD_OK;
+  CallState& s = ctx->calls;
+  NttLaunch t{};
+  t.tw = dom->d_mem, t.log_n = dom->log_n, t.tile_log = ctx->ntt_tile_log;
+  t.direction = direction, t.layout = scalar_layout, t.n_vec = n_vec;
+  u256 tab[kNttPowEntries];   // the powers of the shift: host memory in either form, staged in `pow`
+  ntt_shift_setup(g, direction, dom->log_n, tab, &t.sc);
+  c.host = c.in_place = host, c.host_in = (host ? 1u : 0u) | 2u, c.kernel_ms = kernel_ms;
+  c.in[0] = in, c.in_bytes[0] = bytes;
+  c.in[1] = tab, c.in_bytes[1] = shift32 ? sizeof tab : 0, c.stage[1] = &s.pow;
+  c.out = out, c.out_bytes = bytes;
+  c.work[0] = {&s.scratch, ntt_plan(t.log_n, t.tile_log).passes > 1 ? bytes : 0};
+  return device_call(ctx, c, [&](hipStream_t st, const CallIo& io) {
+    t.in = io.in[0], t.out = io.out, t.scratch = s.scratch.p, t.pow_tab = shift32 ? io.in[1] : nullptr;
+    launch_ntt(st, t);
+    return MSM_AMD_OK;
+  });
 }
 
 }  // namespace
@@ -4168,25 +4168,12 @@ int msm_amd_ntt_domain_build(msm_amd_ctx* ctx, int root, uint32_t log_n, msm_amd
   std::lock_guard<std::mutex> lk(ctx->mu);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (int rc = recover_if_stalled(ctx)) return rc;
-  if (int qrc = quiesce_for_allocation(ctx, "the twiddles of a transform domain")) return qrc;
   const u256 omega = ntt_omega(root, log_n);
   const size_t bytes = std::max<size_t>(32, ((size_t)1 << log_n) / 2 * 32);   // n = 1: no entry, one record of room
-  void* d_tw = nullptr;
-  HIP_TRY(ctx, hipMalloc(&d_tw, bytes));
-  launch_ntt_twiddles(ctx->stream, omega, log_n, d_tw);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && sync_stream_bounded(ctx, ctx->stream, "transform domain build")) {
-    ctx->graveyard.push_back(d_tw);   // the build may still be running: released when the ctx is idle
-    return MSM_AMD_PIPELINE_ERROR;
-  }
-  if (e != hipSuccess) {
-    (void)hipFree(d_tw);
-    HIP_TRY(ctx, e);
-  }
-  msm_amd_ntt_domain* d = new msm_amd_ntt_domain();
-  d->root = root, d->log_n = log_n, d->bytes = bytes, d->d_tw = d_tw, d->omega = omega;
-  ctx->live_ntt.push_back(d);
-  *out = d;
+  if (int rc = handle_build_tail(ctx, ctx->live_ntt, bytes, "the twiddles of a transform domain", "transform domain build",
+                                 [&](void* d_tw) { launch_ntt_twiddles(ctx->stream, omega, log_n, d_tw); }, out))
+    return rc;
+  (*out)->root = root, (*out)->log_n = log_n, (*out)->omega = omega;
   return MSM_AMD_OK;
 }
 
@@ -4194,7 +4181,7 @@ int msm_amd_ntt_domain_info(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, 
                             size_t* device_bytes, void* omega32) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  const msm_amd_ntt_domain* d = find_ntt_domain(ctx, domain);
+  const msm_amd_ntt_domain* d = find_handle(ctx->live_ntt, domain);
   if (!d) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_ntt_domain_info: not a transform domain of this ctx");
   if (root) *root = d->root;
   if (log_n) *log_n = d->log_n;
@@ -4206,14 +4193,7 @@ int msm_amd_ntt_domain_info(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, 
 int msm_amd_ntt_domain_free(msm_amd_ctx* ctx, msm_amd_ntt_domain* domain) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  auto it = std::find(ctx->live_ntt.begin(), ctx->live_ntt.end(), domain);
-  if (it == ctx->live_ntt.end()) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_ntt_domain_free: not a transform domain of this ctx");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->live_ntt.erase(it);
-  if (drain_or_mark_stalled(ctx)) (void)hipFree(domain->d_tw);
-  else ctx->graveyard.push_back(domain->d_tw);   // hipFree would wait for the device without bound
-  delete domain;
-  return MSM_AMD_OK;
+  return handle_free(ctx, ctx->live_ntt, domain, "msm_amd_ntt_domain_free: not a transform domain of this ctx");
 }
 
 int msm_amd_ntt(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int scalar_layout, const void* shift32,
@@ -4229,146 +4209,96 @@ int msm_amd_ntt_device(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int d
 }  // extern "C"
 
 // ---- vectors over Fr (msm_amd_fr_map*, msm_amd_fr_batch_inverse*, msm_amd_fr_prefix_product*) --------------------------------
-// The discipline of ntt_call: ctx lock, bounded drain of the ctx's earlier work, every buffer sized on the idle ctx
-// before anything is enqueued, host operands through the page-locked staging ring, the kernels on the main stream
-// between events, the result behind a bounded stream wait.  The inversion waits twice: T comes back, the host inverts it.
+// Through device_call: the host forms compute over the staged copy of their first operand.  The inversion has two spans
+// of kernels: T and the zero count come back as the call's 64-byte record, the host inverts T.
 namespace {
-
-int fr_begin(msm_amd_ctx* ctx, const std::string& who) {
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (int rc = recover_if_stalled(ctx)) return fail(ctx, rc, who + ": " + ctx->last_error);
-  if (!drain_or_mark_stalled(ctx))
-    return fail(ctx, MSM_AMD_PIPELINE_ERROR, who + ": device busy past the wait bound of " +
-                                                 std::to_string(ctx->wait_timeout_ms) + " ms (msm_amd_synchronize waits again)");
-  for (hipEvent_t& e : ctx->fr.ev)
-    if (!e) HIP_TRY(ctx, hipEventCreate(&e));
-  return MSM_AMD_OK;
-}
 
 int fr_map_call(msm_amd_ctx* ctx, bool host, int op, int scalar_layout, const void* k32, const void* a, const void* b,
                 const void* c, size_t n, void* out, float* kernel_ms) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
-  const std::string who = host ? "msm_amd_fr_map" : "msm_amd_fr_map_device";
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_map" : "msm_amd_fr_map_device";
   if (kernel_ms) *kernel_ms = 0.f;
   if (const char* why = fr_map_check(op, scalar_layout, k32, a, b, c, n, out, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": " + why);
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
   if (n == 0) return MSM_AMD_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  if (int rc = fr_begin(ctx, who)) return rc;
-  // the ctx is idle: every buffer of this call is sized now
-  FrState& s = ctx->fr;
-  hipStream_t st = ctx->stream;
-  const size_t bytes = n * 32;
   const unsigned reads = fr_op_reads(op);
   const void* operand[3] = {a, b, c};
-  void* d_out = out;
-  int rc;
-  if (host) {   // staged, the result over the first operand, copied back
-    for (int i = 0; i < 3; ++i)
-      if ((reads & (1u << i)) && (rc = ensure(ctx, s.in[i], bytes))) return rc;
-    for (int i = 0; i < 3; ++i) {
-      if (!(reads & (1u << i))) continue;
-      if ((rc = staged_upload(ctx, s.in[i].p, operand[i], bytes, st))) return rc;
-      operand[i] = s.in[i].p;
-    }
-    d_out = s.in[0].p;
-  }
-  HIP_TRY(ctx, hipEventRecord(s.ev[0], st));
-  launch_fr_map(st, op, scalar_layout, fr_read_k(op, scalar_layout, k32), operand[0], operand[1], operand[2], n, d_out);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipEventRecord(s.ev[1], st));
-  if (host) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
-  if ((rc = sync_stream_bounded(ctx, st, who.c_str()))) return rc;
-  if (kernel_ms) *kernel_ms = event_span(s.ev[0], s.ev[1]);
-  return MSM_AMD_OK;
+  d.host = d.in_place = host, d.host_in = host ? reads : 0u, d.kernel_ms = kernel_ms;
+  for (int i = 0; i < 3; ++i) d.in[i] = operand[i], d.in_bytes[i] = (reads >> i & 1) ? n * 32 : 0;
+  d.out = out, d.out_bytes = n * 32;
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    launch_fr_map(st, op, scalar_layout, fr_read_k(op, scalar_layout, k32), io.in[0], io.in[1], io.in[2], n, io.out);
+    return MSM_AMD_OK;
+  });
 }
 
 int fr_prefix_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int mode, const void* in, size_t n, size_t n_vec, void* out,
                    float* kernel_ms) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
-  const std::string who = host ? "msm_amd_fr_prefix_product" : "msm_amd_fr_prefix_product_device";
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_prefix_product" : "msm_amd_fr_prefix_product_device";
   if (kernel_ms) *kernel_ms = 0.f;
   if (!fr_mode_known(mode))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": mode must be MSM_AMD_FR_PREFIX_INCLUSIVE or MSM_AMD_FR_PREFIX_EXCLUSIVE");
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": mode must be MSM_AMD_FR_PREFIX_INCLUSIVE or MSM_AMD_FR_PREFIX_EXCLUSIVE");
   if (const char* why = fr_unary_check(scalar_layout, in, n, n_vec, out, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": " + why);
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
   if (n == 0 || n_vec == 0) return MSM_AMD_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  if (int rc = fr_begin(ctx, who)) return rc;
-  FrState& s = ctx->fr;
-  hipStream_t st = ctx->stream;
-  const size_t bytes = n * n_vec * 32;
+  CallState& s = ctx->calls;
   FrScanLaunch c{};
   c.n = n, c.n_vec = n_vec, c.tile_log = ctx->fr_tile_log, c.layout = scalar_layout, c.mode = mode;
-  int rc;
-  if ((rc = ensure(ctx, s.work, std::max<size_t>(32, fr_scan_plan(n, n_vec, c.tile_log).records * 32)))) return rc;
-  if (host && (rc = ensure(ctx, s.in[0], bytes))) return rc;
-  c.in = in, c.out = out, c.work = s.work.p;
-  if (host) {   // staged, scanned in place, copied back
-    if ((rc = staged_upload(ctx, s.in[0].p, in, bytes, st))) return rc;
-    c.in = c.out = s.in[0].p;
-  }
-  HIP_TRY(ctx, hipEventRecord(s.ev[0], st));
-  launch_fr_scan(st, c);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipEventRecord(s.ev[1], st));
-  if (host) HIP_TRY(ctx, hipMemcpyAsync(out, c.out, bytes, hipMemcpyDeviceToHost, st));
-  if ((rc = sync_stream_bounded(ctx, st, who.c_str()))) return rc;
-  if (kernel_ms) *kernel_ms = event_span(s.ev[0], s.ev[1]);
-  return MSM_AMD_OK;
+  d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = n * n_vec * 32;
+  d.out = out, d.out_bytes = n * n_vec * 32;
+  d.work[0] = {&s.work, std::max<size_t>(32, fr_scan_plan(n, n_vec, c.tile_log).records * 32)};
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    c.in = io.in[0], c.out = io.out, c.work = s.work.p;
+    launch_fr_scan(st, c);
+    return MSM_AMD_OK;
+  });
 }
 
 int fr_inverse_call(msm_amd_ctx* ctx, bool host, int scalar_layout, const void* in, size_t n, void* out, uint64_t* n_zero,
                     float* kernel_ms) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
-  const std::string who = host ? "msm_amd_fr_batch_inverse" : "msm_amd_fr_batch_inverse_device";
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_batch_inverse" : "msm_amd_fr_batch_inverse_device";
   if (kernel_ms) *kernel_ms = 0.f;
   if (n_zero) *n_zero = 0;
   if (const char* why = fr_unary_check(scalar_layout, in, n, 1, out, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": " + why);
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
   if (n == 0) return MSM_AMD_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  if (int rc = fr_begin(ctx, who)) return rc;
-  FrState& s = ctx->fr;
-  hipStream_t st = ctx->stream;
-  const size_t bytes = n * 32;
+  CallState& s = ctx->calls;
   const uint32_t tile_log = ctx->fr_tile_log;
   const FrInvPlan plan = fr_inv_plan(n, tile_log);
-  int rc;
-  if ((rc = ensure(ctx, s.work, plan.records * 32))) return rc;
-  if (host && (rc = ensure(ctx, s.in[0], bytes))) return rc;
-  if (!s.h_tail) {
-    if (int qrc = quiesce_for_allocation(ctx, "the landing place of an inversion's product")) return qrc;
-    HIP_TRY(ctx, hipHostMalloc((void**)&s.h_tail, 64, hipHostMallocDefault));
-  }
-  const void* d_in = in;
-  void* d_out = out;
-  if (host) {   // staged, inverted in place, copied back
-    if ((rc = staged_upload(ctx, s.in[0].p, in, bytes, st))) return rc;
-    d_in = d_out = s.in[0].p;
-  }
-  // span 1: the products; T and the zero count come back
-  HIP_TRY(ctx, hipEventRecord(s.ev[0], st));
-  launch_fr_inv_products(st, scalar_layout, d_in, n, tile_log, s.work.p);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipEventRecord(s.ev[1], st));
-  HIP_TRY(ctx, hipMemcpyAsync(s.h_tail, fr_inv_tail(s.work.p, plan), 64, hipMemcpyDeviceToHost, st));
-  if ((rc = sync_stream_bounded(ctx, st, who.c_str()))) return rc;
-  u256 total;
-  uint64_t zeros;
-  std::memcpy(total.v, s.h_tail, 32);
-  std::memcpy(&zeros, s.h_tail + 32, 8);
-  const u256 t_inv = ntt_fr_inv(total);   // zeros were read as one: T != 0
-  // span 2: every record's inverse
-  HIP_TRY(ctx, hipEventRecord(s.ev[2], st));
-  launch_fr_inv_apply(st, scalar_layout, d_in, n, tile_log, s.work.p, t_inv, d_out);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipEventRecord(s.ev[3], st));
-  if (host) HIP_TRY(ctx, hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
-  if ((rc = sync_stream_bounded(ctx, st, who.c_str()))) return rc;
-  if (n_zero) *n_zero = zeros;
-  if (kernel_ms) *kernel_ms = event_span(s.ev[0], s.ev[1]) + event_span(s.ev[2], s.ev[3]);
-  return MSM_AMD_OK;
+  d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = n * 32;
+  d.out = out, d.out_bytes = n * 32;
+  d.work[0] = {&s.work, plan.records * 32};
+  uint64_t zeros = 0;
+  u256 t_inv;
+  const int rc = device_call(
+      ctx, d,
+      [&](hipStream_t st, CallIo& io) {   // span 1: the products; T and the zero count come back
+        launch_fr_inv_products(st, scalar_layout, io.in[0], n, tile_log, s.work.p);
+        io.record = fr_inv_tail(s.work.p, plan);
+        return MSM_AMD_OK;
+      },
+      [&](const uint8_t* tail, float) {
+        u256 total;
+        std::memcpy(total.v, tail, 32);
+        std::memcpy(&zeros, tail + 32, 8);
+        t_inv = ntt_fr_inv(total);   // zeros were read as one: T != 0
+      },
+      [&](hipStream_t st, const CallIo& io) {   // span 2: every record's inverse
+        launch_fr_inv_apply(st, scalar_layout, io.in[0], n, tile_log, s.work.p, t_inv, io.out);
+        return MSM_AMD_OK;
+      });
+  if (rc == MSM_AMD_OK && n_zero) *n_zero = zeros;
+  return rc;
 }
 
 }  // namespace

@@ -9,8 +9,10 @@ import pytest
 
 import check_ref as c
 import compress_ref as r
+import fr_ref as f
 import g2_ref as g
 import mul_ref as m
+import ntt_ref as t
 
 pytestmark = pytest.mark.gpu
 
@@ -110,6 +112,65 @@ def test_point_calls_share_one_state_and_leave_the_msm_alone(msm_pkg):
         assert o.decode_jacobian_mont_le(cfg.msm(scalars, points, n)) == want
         point_calls(cfg, msm_pkg, 1)
         point_calls(cfg, msm_pkg, 2)
+        assert o.decode_jacobian_mont_le(cfg.msm(scalars, points, n)) == want
+    finally:
+        cfg.close()
+
+
+def test_points_transform_and_fr_calls_share_one_state(msm_pkg):
+    """The G1 point calls, the transform and the Fr vector calls use ONE staging set and ONE 64-byte record (counters of a
+    check; T and the zero count of an inversion).  On one fresh ctx, in this order, every result equals its host twin: a
+    call must see neither the record nor a staged tail of the call before it.  2^12 is a transform of two passes (pass
+    buffer and shift powers in use), 2^9 and 2^8 are the tiles of the scan and of the inversion."""
+    n = 1 << 10
+    points, scalars = msm_pkg.generate_instance_host(o.SEED_BASE + 5, n)
+    want = o.decode_jacobian_mont_le(msm_pkg.host_msm(scalars, points, n))
+    mont, canon = msm_pkg.SCALAR_MONT_LE, msm_pkg.SCALAR_CANON_LE
+    cfg = msm_pkg.setup_metal_state()
+    try:
+        assert o.decode_jacobian_mont_le(cfg.msm(scalars, points, n)) == want
+        big, small = cfg.ntt_domain(t.ARK, 12), cfg.ntt_domain(t.H2C, 9)
+
+        # 1. transform, two passes, with a shift
+        data, shift = t.encode(t.random_vector(31, 1 << 12), canon), t.shift_record(9, canon)
+        assert cfg.ntt(big, data, t.INVERSE, canon, shift) == msm_pkg.host_ntt(data, t.ARK, 12, t.INVERSE, canon, shift)
+
+        # 2. map of three distinct operands
+        a, b, c3 = (f.encode(f.random_values(40 + j, (1 << 9) + 7), mont) for j in range(3))
+        k = f.encode([12345], mont)
+        assert cfg.fr_map(f.MULSUB_SCALE, a, b, c3, k, mont) == msm_pkg.host_fr_map(f.MULSUB_SCALE, a, b, c3, k, mont)
+
+        # 3. check: the record carries counters
+        buf = planted(valid_points(msm_pkg, 1, 257), 64, {256: offenders(1)[1].encode()})
+        rep, reasons = cfg.check_points(buf, 257, checks=1, point_layout=c.H2C)
+        h_rep, h_reasons = msm_pkg.host_check_points(buf, 257, checks=1, point_layout=c.H2C)
+        assert reasons == h_reasons and drop_ms(rep) == drop_ms(h_rep)
+        assert rep["n_invalid"] == 1 and rep["first_invalid"] == 256 and reasons.count(0) == 256
+
+        # 4. inversion: the same record carries T and the zero count
+        vals = f.random_values(50, (1 << 8) + 1)
+        vals[100] = 0
+        inv = f.encode(vals, mont)
+        got, zeros = cfg.fr_batch_inverse(inv, mont)
+        assert (got, zeros) == msm_pkg.host_fr_batch_inverse(inv, mont) and zeros == 1 and got[3200:3232] == bytes(32)
+
+        # 5. mul_points: one base for 17 scalars
+        ks = m.planted_scalars(msm_pkg.mul_plan(1)["c"], msm_pkg.mul_plan(1)["W"])[0][:17]
+        sc, base = m.scalars_bytes(ks, 1), m.base_record(1, c.H2C, m.random_points(1, 1, 17)[0])
+        assert cfg.mul_points(sc, base, 17, m.ONE, 1, c.H2C, c.H2C) == msm_pkg.host_mul_points(sc, base, 17, m.ONE, 1, c.H2C, c.H2C)
+
+        # 6. smaller than what the staging holds by now
+        data = t.encode(t.random_vector(32, 1 << 9), mont)
+        assert cfg.ntt(small, data, t.FORWARD, mont) == msm_pkg.host_ntt(data, t.H2C, 9, t.FORWARD, mont)
+        vecs = f.encode(f.random_values(60, 3 * ((1 << 9) + 1)), canon)
+        assert cfg.fr_prefix_product(vecs, f.EXCLUSIVE, canon, 3) == msm_pkg.host_fr_prefix_product(vecs, f.EXCLUSIVE, canon, 3)
+
+        # 7. check again, one valid record: a clean report, and exactly one reason byte written
+        one, raw_rep, two_bytes = valid_points(msm_pkg, 1, 1), msm_pkg.CheckReport(), ctypes.create_string_buffer(b"\xAA\xAA", 2)
+        assert msm_pkg.lib().msm_amd_check_points(cfg.h, c.H2C, one, 1, 1, two_bytes, ctypes.byref(raw_rep)) == msm_pkg.OK
+        assert raw_rep.n_invalid == 0 and raw_rep.first_invalid == 0xFFFFFFFFFFFFFFFF and two_bytes.raw == b"\x00\xAA"
+        assert drop_ms(raw_rep.as_dict()) == drop_ms(msm_pkg.host_check_points(one, 1, checks=1, point_layout=c.H2C)[0])
+
         assert o.decode_jacobian_mont_le(cfg.msm(scalars, points, n)) == want
     finally:
         cfg.close()
