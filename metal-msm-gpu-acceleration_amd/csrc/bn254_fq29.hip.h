@@ -19,7 +19,11 @@
 //
 // Bounds contract (p/rho = 0.0059):
 //   mul/sqr operands : every limb <= 2^30 + 2^8, value <= ~40 p   (then all column sums stay < 2^64)
-//   mul/sqr result   : limbs 0..7 < 2^29 exactly, limb 8 = carry; value < p * (alpha*beta*0.0059 + 1)
+//   mul/sqr result   : limbs 0..7 < 2^29 exactly, limb 8 = carry; value < p * (alpha*beta*0.0059 + 1 + 2^-27)
+//                      (the _np forms with wide quotient digits: + 2^-24).  The value is a b / rho mod p, + p in
+//                      at most 2^-27.3 (wide: 2^-24.3) of all products: the low quotient digits reduce with a multiple of p
+//                      and may overshoot the canonical quotient by rho (reduce_columns).  Nothing may rely on WHICH of
+//                      the two comes back; canonical(., 1) and the zero tests take either.
 //   sub<K>(a, b)     : b limbs <= lift(K) - 2^(e-29), b value within the top-limb headroom of K;
 //                      result = a - b + k*p, limbs < 2^32 -- NOT a valid mul operand until norm()
 //   norm(a)          : limbs 0..7 < 2^29 + 8, value unchanged
@@ -151,14 +155,62 @@ struct Fq29 {
   }
 
   // Montgomery reduction of 17 column sums (columns of weight 2^(29k)) modulo p with radix 2^261.
-  // WIDE = true: quotient digits 0..7 keep all 32 bits of A[k] * INV (one v_and less each; A[k] + m p0 = 0 mod 2^29
-  // holds for the whole product), digit 8 keeps its mask.  The digits then add up to m or m + rho, so the result is
-  // the masked one or that + p (odds ~2^-26), still < s / rho + p (1 + 2^-26) with limbs 0..7 < 2^29; the Montgomery
-  // terms of a column grow by up to 7 p_j 2^29 per digit -- tools/fq29_bounds.py checks every wide use.
-  template <bool WIDE = false>
+  //
+  // Digits 0..6 reduce with N = INVF p, a multiple of p that is -1 modulo 2^29: INVF = INV + 2 * 2^29, so
+  // N + 1 = 2^29 NPP with the 9-limb constant NPP = npp(0..8) (tools/gen_fq29_constants.py: of the 64 choices
+  // INV + t 2^29, t = 2 has the smallest limb sum, 2^29.94 against p's 2^30.59).  With the digit m taken straight from
+  // the column -- no multiplication by INV --
+  //     A[k] + m N = (A[k] - m) + 2^29 (m NPP):
+  // the nine products m npp(j) go to columns k + 1 .. k + 9 and A[k] - m hands its upper bits to column k + 1.
+  //   WIDE = false: m = the low 29 bits of A[k]; A[k] - m = 2^29 (A[k] >> 29), the usual carry.
+  //   WIDE = true : m = the low 32 bits of A[k], the low register of the pair; A[k] - m = 2^32 hi32(A[k]) = 2^29 (8 hi32):
+  //                 the carry is ONE multiply-add into column k + 1 (the factor sits in a scalar register, see carry_factor),
+  //                 no 64-bit shift and no 64-bit addition.
+  // Digits 7 and 8 are the classic ones, m = A[k] * INV (digit 7 unmasked when WIDE, digit 8 always masked), so that the
+  // reduced columns still end at weight 2^261 exactly.
+  // Value: the digits add up to a quotient Q = Q0 (mod rho) with Q0 < rho the canonical one.  Digit k <= 6 contributes
+  // m INVF 2^(29k) < 2^(32 + 30.1 + 174) when WIDE (2^(29 + 30.1 + 174) masked), digit 7 below 2^(32 + 203): together
+  // less than 2^236.7 = 2^-24.3 rho (masked: 2^233.7).  So Q is Q0 or Q0 + rho, and the result is mont(s) or mont(s) + p, below s / rho + p (1 + 2^-24)
+  // (masked: p (1 + 2^-27)), limbs 0..7 < 2^29.  The + p is taken only when Q0 < 2^236.7 (masked: 2^233.7), at most 2^-24.3 (2^-27.3) of all products.
+  // tools/fq29_bounds.py checks the columns (< 2^64) of every use and every bound that leans on the result's.
+  // FRIENDLY = false: every digit the classic way, A[k + j] += (A[k] * INV) p(j) -- the form the experiments' generated
+  // assembly (tools/gen_accumulate_asm.py) implements; the default of -DMSM_FQ29_CLASSIC_REDC builds, for A/B runs.
+  // NPP = (INVF p + 1) / 2^29, INVF = 0x44866389
+  MSM_HD static constexpr uint32_t npp(int i) {
+    constexpr uint32_t c[9] = {0x0872952Du, 0x0808854Au, 0x065124E0u, 0x029B9885u, 0x03F6B850u,
+                               0x148E9764u, 0x02B3E954u, 0x0843F777u, 0x0067A061u};
+    return c[i];
+  }
+  static constexpr int FRIENDLY_DIGITS = 7;
+#if defined(MSM_FQ29_CLASSIC_REDC)   // A/B builds (tools/build_variant.sh) only
+  static constexpr bool FRIENDLY_DEFAULT = false;
+#else
+  static constexpr bool FRIENDLY_DEFAULT = true;
+#endif
+  // 8 as an opaque scalar: a literal would let LLVM turn hi * 8 + A into a 64-bit shift and a 64-bit addition again.
+  MSM_HD static uint32_t carry_factor() {
+    uint32_t eight = 8;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(eight));
+#endif
+    return eight;
+  }
+  template <bool WIDE = false, bool FRIENDLY = FRIENDLY_DEFAULT>
   MSM_HD static fe29 reduce_columns(uint64_t (&A)[17]) {
     uint64_t carry = 0;
     MSM_UNROLL for (int k = 0; k < 9; ++k) {
+      if (FRIENDLY && k < FRIENDLY_DIGITS) {
+        if (WIDE) {
+          const uint32_t m = (uint32_t)A[k], hi = (uint32_t)(A[k] >> 32);
+          MSM_UNROLL for (int j = 0; j < 9; ++j) A[k + 1 + j] += (uint64_t)m * npp(j);
+          A[k + 1] += (uint64_t)hi * carry_factor();
+        } else {
+          const uint32_t m = (uint32_t)A[k] & MASK;
+          MSM_UNROLL for (int j = 0; j < 9; ++j) A[k + 1 + j] += (uint64_t)m * npp(j);
+          A[k + 1] += A[k] >> 29;
+        }
+        continue;
+      }
       A[k] += carry;
       const uint32_t m = (WIDE && k < 8) ? (uint32_t)A[k] * INV : ((uint32_t)A[k] * INV) & MASK;
       MSM_UNROLL for (int j = 0; j < 9; ++j) A[k + j] += (uint64_t)m * p(j);
@@ -173,7 +225,6 @@ struct Fq29 {
     r.l[8] = (uint32_t)carry;
     return r;
   }
-
 
   // The multiplication forms that were built, measured and NOT shipped (product scanning, lockstep chains, one
   // Karatsuba level: DESIGN.md / HISTORY.md) live in experiments/fq29_variants.inc; they are members of this struct only

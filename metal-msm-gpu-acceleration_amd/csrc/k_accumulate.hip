@@ -193,7 +193,7 @@ combine_small_kernel(const uint32_t* __restrict__ multi_list, PlanCounters* __re
                                big_list);
 }
 
-__global__ void __launch_bounds__(64)
+__global__ void __launch_bounds__(64, 3)   // 3 waves per SIMD: at most 168 VGPRs
 combine_big_kernel(const uint32_t* __restrict__ big_list, const PlanCounters* __restrict__ counters,
                    const uint32_t* __restrict__ bucket_size, const uint32_t* __restrict__ item_start,
                    const uint32_t* __restrict__ win_base, uint32_t lb, uint32_t CH,

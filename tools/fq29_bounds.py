@@ -63,17 +63,47 @@ def canonical(name):          # an unpacked base coordinate: canonical limbs of 
     return Fe([MASK] * 8 + [P >> 232], 1.0, name)
 
 
-# quotient digit maxima of reduce_columns: masked (29 bits) or wide (WIDE = true: digits 0..7 keep 32 bits, digit 8 its
-# mask; the result may then be the masked one + p, i.e. up to p (1 + 2^-26) above s / rho)
+# reduce_columns: digits 0..6 reduce with N = INVF p = 2^29 NPP - 1 (the digit is the column's own low 29 bits, or its
+# low 32 bits when WIDE; the products digit * NPP_j go to columns k + 1 .. k + 9; the rest of the column is the carry),
+# digits 7 and 8 are the classic A[k] * INV (digit 7 keeps 32 bits when WIDE, digit 8 its mask).
+NPP = _table("npp")[0]
+INV29 = int(re.search(r"INV = 0x([0-9A-Fa-f]+)u", src).group(1), 16)
+FRIENDLY_DIGITS = int(re.search(r"FRIENDLY_DIGITS = (\d+);", src).group(1))
+assert (INV29 * P + 1) % (1 << 29) == 0
+_N = (sum(l << (29 * i) for i, l in enumerate(NPP)) << 29) - 1
+assert _N % P == 0 and (_N // P) % (1 << 29) == INV29, "npp is not (INVF p + 1) / 2^29 with INVF = INV mod 2^29"
+INVF = _N // P
 DIGIT_MAX = {False: [MASK] * 9, True: [(1 << 32) - 1] * 8 + [MASK]}
-WIDE_EXTRA = 2.0 ** -26 * 1.01
+
+
+def quotient_excess(wide):
+    """The digits add up to Q = Q0 (mod rho), Q0 < rho the canonical quotient, and Q = T + digit_8 2^232 with T the sum
+    of digits 0..7 at their weights: Q is Q0, or Q0 + rho when Q0 < T.  Returns the largest T over rho: the result is
+    below s / rho + p (1 + that), and it is mont(s) + p only for products whose Q0 is below T."""
+    d = DIGIT_MAX[wide]
+    t = sum(d[k] * INVF << (29 * k) for k in range(FRIENDLY_DIGITS)) + sum(d[k] << (29 * k) for k in range(FRIENDLY_DIGITS, 8))
+    assert t < RHO
+    return t / RHO
+
+
+EXTRA = {w: quotient_excess(w) * 1.001 for w in (False, True)}
+assert EXTRA[True] < 2.0 ** -24 and EXTRA[False] < 2.0 ** -27, EXTRA
+WIDE_EXTRA = EXTRA[True]
 
 
 def _reduce(cols, what, wide=False):
-    """Montgomery reduction of worst-case column sums; returns the worst-case top limb (final carry)."""
+    """Montgomery reduction of worst-case column sums (every step is monotone in the columns, so every digit and every
+    carry at its maximum bounds them all); returns the worst-case top limb (final carry)."""
     A = list(cols) + [0] * (17 - len(cols))
     carry = 0
     for k in range(9):
+        if k < FRIENDLY_DIGITS:
+            if A[k] >= 1 << 64:
+                fail(f"{what}: column {k} can reach 2^{A[k].bit_length()} during the reduction")
+            for j in range(9):
+                A[k + 1 + j] += DIGIT_MAX[wide][k] * NPP[j]
+            A[k + 1] += (A[k] >> 32) * 8 if wide else A[k] >> 29
+            continue
         A[k] += carry
         for j in range(9):
             A[k + j] += DIGIT_MAX[wide][k] * PL[j]
@@ -103,7 +133,7 @@ def _out(pairs, name, what, wide=False):
             if max(f.mx) >= 1 << 32:
                 fail(f"{what}: operand {f.name} has a limb beyond 32 bits")
     carry = _reduce(_mul_cols(pairs), what + (" (wide digits)" if wide else ""), wide)
-    val = sum(a.val * b.val for a, b in pairs) * P / RHO + 1.0 + (WIDE_EXTRA if wide else 0.0)
+    val = sum(a.val * b.val for a, b in pairs) * P / RHO + 1.0 + EXTRA[wide]
     top = min(carry, top_from_value(val))
     return Fe([MASK] * 8 + [top], val, name)
 
@@ -421,8 +451,23 @@ def mul_points(group=16, where="mul_normalise"):
             fail(f"load_base: {f.name} may reach {f.val:.2f}p, canonical(., 1) takes values below 2 p")
 
 
+def contracts():
+    """The operand contracts the headers state, whatever the caller: bn254_fq29.hip.h (mul / sqr: limbs <= 2^30 + 2^8,
+    value <= 40 p; masked and wide digits) and bn254_fq2_29.hip.h (every operand of G2's mul / mul2 / sqr normalised:
+    limbs 0..7 <= 2^29 + 8, limb 8 < 2^28, masked digits).  Returns the result bounds in multiples of p."""
+    lazy = Fe([(1 << 30) + (1 << 8)] * 8 + [top_from_value(40.0)], 40.0, "lazy")
+    g2 = Fe([MASK + 8] * 8 + [(1 << 28) - 1], 64.0, "normalised")
+    out = {}
+    for wide in (False, True):
+        tag = " (wide)" if wide else ""
+        out["mul" + tag] = mul(lazy, lazy, "lazy*lazy" + tag, wide)
+        out["sqr" + tag] = sqr(lazy, "lazy^2" + tag, wide)
+    out["mul2 (Fq2)"] = mul2(g2, g2, g2, g2, "Fq2 double product")
+    return out
+
+
 def main(verbose=False):
-    figures = {}
+    figures = {"operand contracts": contracts()}
     for bases in (PACKED, IN_PLACE):
         figures["pti_madd" + bases.tag] = pti_madd(bases)
         figures["pti_mmadd" + bases.tag] = pti_mmadd(bases)

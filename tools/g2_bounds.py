@@ -28,6 +28,10 @@ import sys
 
 P = 0x30644E72E131A029B85045B68181585D97816A916871CA8D3C208C16D87CFD47
 RP = P / 2 ** 261          # rho' = p / rho
+# a reduction's result is below s / rho + ONE p: the low quotient digits of Fq29::reduce_columns reduce with a multiple of p
+# and overshoot the canonical quotient by less than 2^-27 rho (masked digits, the only ones G2 uses; tools/fq29_bounds.py
+# derives the figure and checks the 64-bit columns of a double product of four normalised operands)
+ONE = 1 + 2.0 ** -27
 LIMIT = 64                 # normalised operand value bound
 ZERO_FILTER = 16
 # the point invariant bn254_ec2_29.hip.h states (per component, multiples of p); main() proves the fixed point below it,
@@ -49,13 +53,13 @@ def chk(a):
 def mul(a, b):             # c0 = a0 b0 + a1 (32 p - b1), c1 = a0 b1 + a1 b0
     assert b[1] < 32, b
     chk(a), chk(b)
-    return (1 + RP * (a[0] * b[0] + a[1] * 32), 1 + RP * (a[0] * b[1] + a[1] * b[0]))
+    return (ONE + RP * (a[0] * b[0] + a[1] * 32), ONE + RP * (a[0] * b[1] + a[1] * b[0]))
 
 
 def sqr(a):                # c0 = (a0 + a1)(a0 - a1 + 32 p), c1 = (2 a0) a1
     assert a[1] < 32, a
     chk(a)
-    return (1 + RP * (a[0] + a[1]) * (a[0] + 32), 1 + RP * 2 * a[0] * a[1])
+    return (ONE + RP * (a[0] + a[1]) * (a[0] + 32), ONE + RP * 2 * a[0] * a[1])
 
 
 def add(a, b):
@@ -69,7 +73,7 @@ def sub(a, b, k):
 
 def squash(a):
     chk(a)
-    return (1 + RP * a[0], 1 + RP * a[1])
+    return (ONE + RP * a[0], ONE + RP * a[1])
 
 
 SEEN = {}
@@ -129,10 +133,10 @@ def fe_inv(a):            # Fq2::inv_fq: r = one; per bit of p - 2 (msb first): 
     assert a < 32, a
     r, worst = 1.0, 1.0
     for bit in bin(P - 2)[2:].rjust(9 * 29, "0"):   # the loop walks all 261 bit positions of the 9 limbs
-        r = 1 + RP * r * r
+        r = ONE + RP * r * r
         worst = max(worst, r)                       # the operand of the next multiplication / squaring
         if bit == "1":
-            r = 1 + RP * r * a
+            r = ONE + RP * r * a
     assert worst < 1.02 and r < 1 + 1.02 * RP * a + 1e-12, (worst, r)
     return r
 
@@ -140,9 +144,9 @@ def fe_inv(a):            # Fq2::inv_fq: r = one; per bit of p - 2 (msb first): 
 def fq2_inv(a):           # conj(a) / norm_fq(a): norm_fq = mul2(a0, a0, a1, a1), then two single products
     chk(a)
     assert max(a) < 32, a
-    n = 1 + RP * (a[0] * a[0] + a[1] * a[1])
+    n = ONE + RP * (a[0] * a[0] + a[1] * a[1])
     ninv = fe_inv(n)
-    return (1 + RP * a[0] * ninv, 1 + RP * 32 * ninv)
+    return (ONE + RP * a[0] * ninv, ONE + RP * 32 * ninv)
 
 
 def to_affine(X, Y, ZZ, ZZZ):   # t = (ZZ ZZZ)^-1, x = (X t) ZZZ, y = (Y t) ZZ
@@ -161,7 +165,7 @@ def conj(a, k):           # (a0, k p - a1): the lift must cover a1; the result i
 def mul_const(c, b):      # Fq2::mul(c, b) with b = conj(., 32): b1 <= 32 p (2 kc(K16E30) - b1 stays positive limb-wise)
     assert b[1] <= 32, b
     chk(c), chk((b[0], 0))
-    return (1 + RP * (c[0] * b[0] + c[1] * 32), 1 + RP * (c[0] * b[1] + c[1] * b[0]))
+    return (ONE + RP * (c[0] * b[0] + c[1] * 32), ONE + RP * (c[0] * b[1] + c[1] * b[0]))
 
 
 def psi(X, Y, ZZ, ZZZ):   # pt2_psi: (gx conj(X), gy conj(Y), squash(conj(ZZ)), squash(conj(ZZZ))), gx, gy canonical
@@ -181,43 +185,43 @@ def curve_equation():     # y^2 - (x^3 + b') + 8 p with x, y from_ext outputs (<
     d = note("curve.d", sub(sqr(y), add(t, (1, 1)), 8))
     chk(d)                # is_zero_exact: a multiplication operand
     # G1 (Fq29 single products): x^3 < 1 + rho' 1.01 (1 + rho' 1.01^2), Jacobian b = 3 Z^6 < 3.1 p, subtrahend < 4.2 p
-    z2 = 1 + RP * 1.01 * 1.01
-    z6 = 1 + RP * (1 + RP * z2 * z2) * z2
-    assert (1 + RP * 1.01 * z2) + 3 * z6 < 8
+    z2 = ONE + RP * 1.01 * 1.01
+    z6 = ONE + RP * (ONE + RP * z2 * z2) * z2
+    assert (ONE + RP * 1.01 * z2) + 3 * z6 < 8
     return d
 
 
 # ---- square roots (compress_points.hip.h) -----------------------------------------------------------------------------
 def fe_sqrt(a):           # comp_sqrt_candidate: table a, a^2, a^3; per 2-bit window (msb first): r = (r^2)^2, r = r a^w
     assert a < 8, a       # the contract; the acceptance test subtracts a through the 8 p lift
-    a2 = 1 + RP * a * a
-    a3 = 1 + RP * a2 * a
+    a2 = ONE + RP * a * a
+    a3 = ONE + RP * a2 * a
     table = {1: a, 2: a2, 3: a3}
     e = (P + 1) // 4
     r, worst, products = 1.0, 1.0, 0
     for b in range(254, -1, -2):
-        r = 1 + RP * r * r
-        r = 1 + RP * r * r
+        r = ONE + RP * r * r
+        r = ONE + RP * r * r
         worst = max(worst, r)
         w = (e >> b) & 3
         if w:
-            r = 1 + RP * r * table[w]
+            r = ONE + RP * r * table[w]
             products += 1
             worst = max(worst, r)
     assert products == 88 and worst < 1.05 and max(a2, a3) < 1.38, (products, worst, a2, a3)
-    d = (1 + RP * r * r) + 8          # r^2 - a + 8 p: normalised, the operand of is_zero_exact
-    assert d < 9.02 and 1 + RP * d < 2, d
+    d = (ONE + RP * r * r) + 8          # r^2 - a + 8 p: normalised, the operand of is_zero_exact
+    assert d < 9.02 and ONE + RP * d < 2, d
     return r
 
 
 def fq2_sqrt(a):          # comp_sqrt_fq2: a = (a0, a1), components normalised, < 4 p
     assert max(a) < 4, a
-    n = 1 + RP * (a[0] * a[0] + a[1] * a[1])                # norm_fq: mul2(a0, a0, a1, a1)
+    n = ONE + RP * (a[0] * a[0] + a[1] * a[1])                # norm_fq: mul2(a0, a0, a1, a1)
     r1 = fe_sqrt(max(a[0], n))                             # in1 = a1 == 0 ? a0 : norm
-    half = 1 + RP * (a[0] + r1) * 1                        # (a0 + r1) (rho / 2 mod p) / rho
+    half = ONE + RP * (a[0] + r1) * 1                        # (a0 + r1) (rho / 2 mod p) / rho
     r2 = fe_sqrt(max(4.0, half))                           # in2 = a1 == 0 ? 4 p - a0 : half
     inv = fe_inv(2 * r2)                                   # inv_fq(norm(r2 + r2))
-    w = 1 + RP * a[1] * inv
+    w = ONE + RP * a[1] * inv
     root = (max(r1, r2, w), max(r2, w))
     d = sub(sqr(root), a, 8)                               # root^2 - a through Fq2::sub<8>
     chk(d)
@@ -227,10 +231,10 @@ def fq2_sqrt(a):          # comp_sqrt_fq2: a = (a0, a1), components normalised, 
 
 
 def decompress():         # the two decoders: x from the canonical integer, the right-hand side, the sign selection
-    x = 1 + RP * 6 * 1                                     # mul(unpack256(x < 2^254 < 6 p), rho^2 mod p)
-    rhs1 = (1 + RP * (1 + RP * x * x) * x) + 1             # x^3 + b, b canonical
+    x = ONE + RP * 6 * 1                                     # mul(unpack256(x < 2^254 < 6 p), rho^2 mod p)
+    rhs1 = (ONE + RP * (ONE + RP * x * x) * x) + 1             # x^3 + b, b canonical
     y = fe_sqrt(rhs1)
-    neg = 1 + RP * 4 * 1                                   # squash(neg(y)): neg < 4 p needs y < 3.9 p
+    neg = ONE + RP * 4 * 1                                   # squash(neg(y)): neg < 4 p needs y < 3.9 p
     assert rhs1 < 2.02 and y < 3.9 and neg < 1.03 and max(x, y, neg) < 2    # packers take values below 2 p
     t = mul(sqr((x, x)), (x, x))
     rhs2 = add(t, (1, 1))
