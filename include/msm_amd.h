@@ -909,6 +909,33 @@ int msm_amd_ntt_device(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int d
 /* The same on the CPU (no ctx, no GPU; the same bodies compiled for the host); threads <= 0: up to 16 host threads. */
 int msm_amd_host_ntt(int root, uint32_t log_n, int direction, int scalar_layout, const void* shift32, const void* in,
                      void* out, size_t n_vec, int threads);
+/* Test aids of the transform.  A call of log_n levels at a tile of 2^tile_log elements per workgroup (2 .. 10; the ctx
+ * calls use MSM_AMD_NTT_TILE_LOG) runs ceil(log_n / tile_log) passes (one for log_n = 0); pass k covers the levels
+ * level0 .. level0 + levels - 1 of the decimation-in-frequency network, on tiles of 2^levels elements at stride
+ * 2^sigma, and a workgroup holds 2^low neighbouring index bits below the tile bits.
+ * msm_amd_test_ntt_plan (no ctx): out[0] = the pass count, then level0, levels, sigma, low of every pass -- out holds
+ *   1 + 4 * 28 words.  The values are the ones the kernel launches compute.
+ * msm_amd_test_ntt_slots (no ctx): out[m], m < 2^tile_log = the flat element index v n + i (over a batch of any size:
+ *   the kernel drops indices >= n_vec n) that slot m of workgroup wg < 2^32 holds in pass `pass` of that plan; the
+ *   function the kernel calls, compiled for the host.
+ * msm_amd_test_ntt_passes: msm_amd_ntt stopped after the first `passes` passes of its plan, 1 <= passes <= the pass
+ *   count.  Below the count, out = the ctx's pass buffer as those passes left it: n_vec n fully reduced Montgomery
+ *   residues (whatever scalar_layout) at the positions of the network -- what msm_amd_test_host_ntt_levels writes for
+ *   the levels those passes cover.  With the full count, out = what msm_amd_ntt returns.
+ * msm_amd_test_host_ntt_levels (no ctx): msm_amd_host_ntt stopped after `levels` <= log_n levels; out = its work array
+ *   as it stands: Montgomery residues, input conversion and the FORWARD shift applied, no permutation to natural
+ *   order, no INVERSE scaling (levels = log_n: position bitrev(k) holds the k-th sum).
+ * msm_amd_test_ntt_twiddles: `count` records of the domain's table from entry `first`: out[j] = w^(first + j), MONT_LE,
+ *   first + count <= n / 2.
+ * MSM_AMD_INPUT_ERROR for values outside these ranges and what msm_amd_ntt / msm_amd_host_ntt refuse; a null pointer with
+ * work to do is refused; n_vec == 0 or count == 0 touches nothing. */
+int msm_amd_test_ntt_plan(uint32_t log_n, uint32_t tile_log, uint32_t* out);
+int msm_amd_test_ntt_slots(uint32_t log_n, uint32_t tile_log, uint32_t pass, uint64_t wg, uint64_t* out);
+int msm_amd_test_ntt_passes(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int scalar_layout,
+                            const void* shift32, const void* in, void* out, size_t n_vec, uint32_t passes);
+int msm_amd_test_host_ntt_levels(int root, uint32_t log_n, int direction, int scalar_layout, const void* shift32,
+                                 const void* in, void* out, size_t n_vec, uint32_t levels, int threads);
+int msm_amd_test_ntt_twiddles(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, size_t first, size_t count, void* out);
 
 /* ---- vectors over Fr: element-wise ops, batch inversion, prefix products ----------------------------------
  * Between a transform and an MSM a prover does arithmetic on whole vectors of Fr: Groth16's h = (a.b - c) (g^n - 1)^-1

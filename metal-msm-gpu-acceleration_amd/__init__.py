@@ -107,6 +107,8 @@ EXPORTS = [
     "msm_amd_test_mul_stage", "msm_amd_test_mul_stage_host",
     "msm_amd_ntt_domain_build", "msm_amd_ntt_domain_info", "msm_amd_ntt_domain_free", "msm_amd_ntt", "msm_amd_ntt_device",
     "msm_amd_host_ntt",
+    "msm_amd_test_ntt_plan", "msm_amd_test_ntt_slots", "msm_amd_test_ntt_passes", "msm_amd_test_host_ntt_levels",
+    "msm_amd_test_ntt_twiddles",
     "msm_amd_fr_map", "msm_amd_fr_map_device", "msm_amd_host_fr_map",
     "msm_amd_fr_batch_inverse", "msm_amd_fr_batch_inverse_device", "msm_amd_host_fr_batch_inverse",
     "msm_amd_fr_prefix_product", "msm_amd_fr_prefix_product_device", "msm_amd_host_fr_prefix_product",
@@ -341,6 +343,13 @@ def _lib():
         L.msm_amd_ntt_device.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                          POINTER(c_float)]
         L.msm_amd_host_ntt.argtypes = [c_int, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_int]
+        L.msm_amd_test_ntt_plan.argtypes = [c_uint32, c_uint32, POINTER(c_uint32)]
+        L.msm_amd_test_ntt_slots.argtypes = [c_uint32, c_uint32, c_uint32, c_uint64, POINTER(c_uint64)]
+        L.msm_amd_test_ntt_passes.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                              c_uint32]
+        L.msm_amd_test_host_ntt_levels.argtypes = [c_int, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                   c_uint32, c_int]
+        L.msm_amd_test_ntt_twiddles.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]
         L.msm_amd_fr_map.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
         L.msm_amd_fr_map_device.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                             c_void_p, POINTER(c_float)]
@@ -835,6 +844,21 @@ class MsmConfig:
                                               c_void_p(d_out), n_vec, ctypes.byref(ms)))
         return ms.value
 
+    def test_ntt_passes(self, dom, data: bytes, passes, direction=NTT_FORWARD, scalar_layout=SCALAR_MONT_LE, shift=None,
+                        n_vec=1) -> bytes:
+        """MsmConfig.ntt stopped after the first `passes` passes of its plan (msm_amd_test_ntt_passes): below the plan's
+        count the pass buffer -- Montgomery residues at the positions of the network --, with it the result of ntt."""
+        out = ctypes.create_string_buffer(max(1, len(data)))
+        self._check(_lib().msm_amd_test_ntt_passes(self.h, _ntt_handle(dom), direction, scalar_layout, shift, data, out,
+                                                   n_vec, passes))
+        return out.raw[:len(data)]
+
+    def test_ntt_twiddles(self, dom, first, count) -> bytes:
+        """count records of a domain's table from entry first (msm_amd_test_ntt_twiddles): omega^j in MONT_LE"""
+        out = ctypes.create_string_buffer(max(1, 32 * count))
+        self._check(_lib().msm_amd_test_ntt_twiddles(self.h, _ntt_handle(dom), first, count, out))
+        return out.raw[:32 * count]
+
     # ---- vectors over Fr ---------------------------------------------------------------------------
     def fr_map(self, op, a: bytes, b: bytes = None, c: bytes = None, k: bytes = None, scalar_layout=SCALAR_MONT_LE) -> bytes:
         """out[i] = op(k, a[i], b[i], c[i]) on host records (msm_amd_fr_map); k: 32 bytes in scalar_layout"""
@@ -1168,6 +1192,35 @@ def host_ntt(data: bytes, root, log_n, direction=NTT_FORWARD, scalar_layout=SCAL
     if st != OK:
         raise MsmError(st)
     return out.raw[:len(data)]
+
+
+def test_host_ntt_levels(data: bytes, root, log_n, levels, direction=NTT_FORWARD, scalar_layout=SCALAR_MONT_LE, shift=None,
+                         n_vec=1, threads=0) -> bytes:
+    """host_ntt stopped after `levels` levels (msm_amd_test_host_ntt_levels): the work array as it stands, Montgomery
+    residues, no permutation, no scaling."""
+    out = ctypes.create_string_buffer(max(1, len(data)))
+    st = _lib().msm_amd_test_host_ntt_levels(root, log_n, direction, scalar_layout, shift, data, out, n_vec, levels, threads)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:len(data)]
+
+
+def test_ntt_plan(log_n, tile_log=10) -> list:
+    """The passes of a transform (msm_amd_test_ntt_plan): one dict of level0, levels, sigma, low per pass."""
+    out = (c_uint32 * (1 + 4 * 28))()
+    st = _lib().msm_amd_test_ntt_plan(log_n, tile_log, out)
+    if st != OK:
+        raise MsmError(st)
+    return [dict(zip(("level0", "levels", "sigma", "low"), out[1 + 4 * k:5 + 4 * k])) for k in range(out[0])]
+
+
+def test_ntt_slots(log_n, tile_log, pass_index, wg) -> list:
+    """The flat element index of every slot of workgroup wg in one pass (msm_amd_test_ntt_slots: ntt_slot_index)."""
+    out = (c_uint64 * (1 << min(max(tile_log, 0), 10)))()
+    st = _lib().msm_amd_test_ntt_slots(log_n, tile_log, pass_index, wg, out)
+    if st != OK:
+        raise MsmError(st)
+    return list(out)
 
 
 def host_fr_map(op, a: bytes, b: bytes = None, c: bytes = None, k: bytes = None, scalar_layout=SCALAR_MONT_LE,

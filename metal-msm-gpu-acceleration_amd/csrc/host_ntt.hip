@@ -1,6 +1,7 @@
 // Host twin of the transform (no ctx, no GPU): the butterfly, conversion and scaling bodies of ntt.hip.h on the CPU, one
-// level of the network at a time, each level split over the host threads; and the argument checks the twin shares
-// with the host driver (msm_host.hip).
+// level of the network at a time, each level split over the host threads; the argument checks the twin shares with
+// the host driver (msm_host.hip); and the test aids that need no ctx: the twin stopped after some levels, the plan and
+// the slot map of ntt.hip.h as the kernels see them.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -33,10 +34,14 @@ bool ntt_read_shift(int scalar_layout, const void* shift32, u256* g) {
 
 namespace {
 
+constexpr uint32_t kAllLevels = ~0u;
+
+// levels == kAllLevels: the transform.  levels <= log_n (msm_amd_test_host_ntt_levels): the work array after that many
+// levels as it stands -- Montgomery residues at the positions of the network, no permutation, no scaling.
 int host_ntt(int root, uint32_t log_n, int direction, int layout, const void* shift32, const void* in_v, void* out_v,
-             size_t n_vec, int threads) {
+             size_t n_vec, int threads, uint32_t levels) {
   if (!ntt_root_known(root) || !ntt_direction_known(direction) || !ntt_layout_known(layout) || log_n > kNttMaxLog ||
-      ((uint64_t)n_vec >> (32 - log_n)) != 0)
+      ((uint64_t)n_vec >> (32 - log_n)) != 0 || (levels != kAllLevels && levels > log_n))
     return MSM_AMD_INPUT_ERROR;
   if (n_vec == 0) return MSM_AMD_OK;
   u256 g;
@@ -77,7 +82,7 @@ int host_ntt(int root, uint32_t log_n, int direction, int layout, const void* sh
       work[idx] = x;
     }
   });
-  for (uint32_t level = 0; level < log_n; ++level) {
+  for (uint32_t level = 0; level < (levels == kAllLevels ? log_n : levels); ++level) {
     const uint32_t bit = log_n - 1 - level;
     const size_t h = (size_t)1 << bit;
     for_ranges(worker_count(threads, total / 2), total / 2, [&](unsigned, size_t lo, size_t hi) {
@@ -86,6 +91,10 @@ int host_ntt(int root, uint32_t log_n, int direction, int layout, const void* sh
         ntt_bfly(work[idx], work[idx + h], tw[ntt_twiddle_index((uint32_t)idx & nmask, log_n, level)]);
       }
     });
+  }
+  if (levels != kAllLevels) {
+    std::memcpy(out, work.data(), total * 32);
+    return MSM_AMD_OK;
   }
   for_ranges(T, total, [&](unsigned, size_t lo, size_t hi) {
     for (size_t idx = lo; idx < hi; ++idx) {
@@ -108,7 +117,39 @@ extern "C" {
 
 int msm_amd_host_ntt(int root, uint32_t log_n, int direction, int scalar_layout, const void* shift32, const void* in,
                      void* out, size_t n_vec, int threads) {
-  return msm_amd::host_ntt(root, log_n, direction, scalar_layout, shift32, in, out, n_vec, threads);
+  return msm_amd::host_ntt(root, log_n, direction, scalar_layout, shift32, in, out, n_vec, threads, msm_amd::kAllLevels);
+}
+
+int msm_amd_test_host_ntt_levels(int root, uint32_t log_n, int direction, int scalar_layout, const void* shift32,
+                                 const void* in, void* out, size_t n_vec, uint32_t levels, int threads) {
+  if (levels == msm_amd::kAllLevels) return MSM_AMD_INPUT_ERROR;
+  return msm_amd::host_ntt(root, log_n, direction, scalar_layout, shift32, in, out, n_vec, threads, levels);
+}
+
+int msm_amd_test_ntt_plan(uint32_t log_n, uint32_t tile_log, uint32_t* out) {
+  using namespace msm_amd;
+  if (!out || log_n > kNttMaxLog || tile_log < 2 || tile_log > kNttTileLog) return MSM_AMD_INPUT_ERROR;
+  const NttPlan plan = ntt_plan(log_n, tile_log);
+  out[0] = plan.passes;
+  uint32_t level = 0;
+  for (uint32_t k = 0; k < plan.passes; ++k) {
+    const NttPass p = ntt_pass(log_n, level, plan.levels[k], tile_log);
+    out[1 + 4 * k] = p.level0, out[2 + 4 * k] = p.levels, out[3 + 4 * k] = p.sigma, out[4 + 4 * k] = p.low;
+    level += plan.levels[k];
+  }
+  return MSM_AMD_OK;
+}
+
+int msm_amd_test_ntt_slots(uint32_t log_n, uint32_t tile_log, uint32_t pass, uint64_t wg, uint64_t* out) {
+  using namespace msm_amd;
+  if (!out || log_n > kNttMaxLog || tile_log < 2 || tile_log > kNttTileLog || (wg >> 32) != 0) return MSM_AMD_INPUT_ERROR;
+  const NttPlan plan = ntt_plan(log_n, tile_log);
+  if (pass >= plan.passes) return MSM_AMD_INPUT_ERROR;
+  uint32_t level = 0;
+  for (uint32_t k = 0; k < pass; ++k) level += plan.levels[k];
+  const NttPass p = ntt_pass(log_n, level, plan.levels[pass], tile_log);
+  for (uint32_t m = 0; m < (1u << tile_log); ++m) out[m] = ntt_slot_index(p, wg, m);
+  return MSM_AMD_OK;
 }
 
 }  // extern "C"

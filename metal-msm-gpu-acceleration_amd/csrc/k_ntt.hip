@@ -200,7 +200,7 @@ void launch_ntt_twiddles(hipStream_t st, const u256& omega, uint32_t log_n, void
                      count, (u256*)d_tw);
 }
 
-uint32_t launch_ntt(hipStream_t st, const NttLaunch& c) {
+uint32_t launch_ntt(hipStream_t st, const NttLaunch& c, uint32_t max_passes) {
   const NttPlan plan = ntt_plan(c.log_n, c.tile_log);
   NttArgs a{};
   a.tw = (const u256*)c.tw;
@@ -210,8 +210,9 @@ uint32_t launch_ntt(hipStream_t st, const NttLaunch& c) {
   a.layout = c.layout, a.direction = c.direction;
   a.sc = c.sc;
   const uint32_t wgs = (uint32_t)((a.total + ((uint64_t)1 << c.tile_log) - 1) >> c.tile_log);
+  const uint32_t run = plan.passes < max_passes ? plan.passes : max_passes;
   uint32_t level = 0;
-  for (uint32_t k = 0; k < plan.passes; ++k) {
+  for (uint32_t k = 0; k < run; ++k) {
     a.first = k == 0, a.last = k + 1 == plan.passes;
     a.level0 = level, a.levels = plan.levels[k];
     // one pass: in -> out.  More: in -> scratch, scratch in place, scratch -> out (each of the earlier passes writes the
@@ -221,7 +222,7 @@ uint32_t launch_ntt(hipStream_t st, const NttLaunch& c) {
     hipLaunchKernelGGL(ntt_pass_kernel, dim3(wgs), dim3(kNttThreads), 0, st, a);
     level += plan.levels[k];
   }
-  return plan.passes;
+  return run;
 }
 
 }  // namespace msm_amd

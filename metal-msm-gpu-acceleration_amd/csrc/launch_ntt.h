@@ -21,8 +21,11 @@ struct NttLaunch {
   void* scratch;         // n_vec * n records, used when the plan has more than one pass
   size_t n_vec;
 };
-// every pass of one call, in stream order; returns the number of launches
-uint32_t launch_ntt(hipStream_t st, const NttLaunch& c);
+constexpr uint32_t kNttAllPasses = ~0u;
+// the first max_passes passes of one call (kNttAllPasses: the call), in stream order; returns the number of launches.
+// Stopped before the last pass of its plan (msm_amd_test_ntt_passes), the state is in `scratch`: Montgomery residues
+// at the positions the passes read.
+uint32_t launch_ntt(hipStream_t st, const NttLaunch& c, uint32_t max_passes);
 
 // host_ntt.hip
 bool ntt_root_known(int root);

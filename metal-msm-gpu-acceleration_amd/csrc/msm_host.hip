@@ -4113,11 +4113,13 @@ int msm_amd_test_mul_stage_host(int group, int which, int layout, const void* in
 // Domain handles are validated by membership in ctx->live_ntt, under the lock and before anything is sized by them.
 namespace {
 
+// max_passes: kNttAllPasses, or 1 .. the pass count of the plan (msm_amd_test_ntt_passes, host buffers): what the first
+// max_passes passes wrote -- short of the plan's count that is the pass buffer, copied over the staged input.
 int ntt_call(msm_amd_ctx* ctx, const msm_amd_ntt_domain* handle, bool host, int direction, int scalar_layout,
-             const void* shift32, const void* in, void* out, size_t n_vec, float* kernel_ms) {
+             const void* shift32, const void* in, void* out, size_t n_vec, float* kernel_ms, uint32_t max_passes) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
   DeviceCall c;
-  c.who = host ? "msm_amd_ntt" : "msm_amd_ntt_device";
+  c.who = max_passes != kNttAllPasses ? "msm_amd_test_ntt_passes" : host ? "msm_amd_ntt" : "msm_amd_ntt_device";
   const std::string& who = c.who;
   if (kernel_ms) *kernel_ms = 0.f;
   if (!ntt_direction_known(direction)) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": direction must be MSM_AMD_NTT_FORWARD or MSM_AMD_NTT_INVERSE");
@@ -4127,6 +4129,10 @@ int ntt_call(msm_amd_ctx* ctx, const msm_amd_ntt_domain* handle, bool host, int 
   const msm_amd_ntt_domain* dom = find_handle(ctx->live_ntt, handle);
   if (!dom) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": not a transform domain of this ctx");
   if (((uint64_t)n_vec >> (32 - dom->log_n)) != 0) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": n_vec * n >= 2^32");
+  const uint32_t plan_passes = ntt_plan(dom->log_n, ctx->ntt_tile_log).passes;
+  if (max_passes != kNttAllPasses && (max_passes == 0 || max_passes > plan_passes))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": passes must be 1 .. the pass count of the plan");
+  const bool stopped = max_passes < plan_passes;   // the last pass does not run
   if (n_vec == 0) return MSM_AMD_OK;
   if (!in || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": null pointer with n_vec > 0");
   u256 g;
@@ -4148,10 +4154,11 @@ int ntt_call(msm_amd_ctx* ctx, const msm_amd_ntt_domain* handle, bool host, int 
   c.in[0] = in, c.in_bytes[0] = bytes;
   c.in[1] = tab, c.in_bytes[1] = shift32 ? sizeof tab : 0, c.stage[1] = &s.pow;
   c.out = out, c.out_bytes = bytes;
-  c.work[0] = {&s.scratch, ntt_plan(t.log_n, t.tile_log).passes > 1 ? bytes : 0};
-  return device_call(ctx, c, [&](hipStream_t st, const CallIo& io) {
+  c.work[0] = {&s.scratch, plan_passes > 1 ? bytes : 0};
+  return device_call(ctx, c, [&](hipStream_t st, const CallIo& io) -> int {
     t.in = io.in[0], t.out = io.out, t.scratch = s.scratch.p, t.pow_tab = shift32 ? io.in[1] : nullptr;
-    launch_ntt(st, t);
+    launch_ntt(st, t, max_passes);
+    if (stopped) HIP_TRY(ctx, hipMemcpyAsync(io.out, s.scratch.p, bytes, hipMemcpyDeviceToDevice, st));
     return MSM_AMD_OK;
   });
 }
@@ -4198,12 +4205,33 @@ int msm_amd_ntt_domain_free(msm_amd_ctx* ctx, msm_amd_ntt_domain* domain) {
 
 int msm_amd_ntt(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int scalar_layout, const void* shift32,
                 const void* in, void* out, size_t n_vec) {
-  return ntt_call(ctx, domain, true, direction, scalar_layout, shift32, in, out, n_vec, nullptr);
+  return ntt_call(ctx, domain, true, direction, scalar_layout, shift32, in, out, n_vec, nullptr, kNttAllPasses);
 }
 
 int msm_amd_ntt_device(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int scalar_layout,
                        const void* shift32, const void* d_in, void* d_out, size_t n_vec, float* kernel_ms) {
-  return ntt_call(ctx, domain, false, direction, scalar_layout, shift32, d_in, d_out, n_vec, kernel_ms);
+  return ntt_call(ctx, domain, false, direction, scalar_layout, shift32, d_in, d_out, n_vec, kernel_ms, kNttAllPasses);
+}
+
+int msm_amd_test_ntt_passes(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int scalar_layout,
+                            const void* shift32, const void* in, void* out, size_t n_vec, uint32_t passes) {
+  if (passes == kNttAllPasses) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_ntt_passes: passes must be 1 .. the pass count of the plan");
+  return ntt_call(ctx, domain, true, direction, scalar_layout, shift32, in, out, n_vec, nullptr, passes);
+}
+
+int msm_amd_test_ntt_twiddles(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, size_t first, size_t count, void* out) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_ntt_domain* d = find_handle(ctx->live_ntt, domain);
+  if (!d) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_ntt_twiddles: not a transform domain of this ctx");
+  const size_t entries = ((size_t)1 << d->log_n) / 2;
+  if (first > entries || count > entries - first)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_ntt_twiddles: range outside the n/2 entries of the table");
+  if (count == 0) return MSM_AMD_OK;
+  if (!out) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_ntt_twiddles: null pointer with count > 0");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipMemcpyAsync(out, (const u256*)d->d_mem + first, count * 32, hipMemcpyDeviceToHost, ctx->stream));
+  return sync_stream_bounded(ctx, ctx->stream, __func__);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 """Model side of the transform tests (msm_amd_ntt*, msm_amd_host_ntt): Python integers only.  The two 2^28-th roots as
 g^t, a naive O(n^2) DFT, a recursive radix-2 transform for the sizes the naive one cannot reach, the closed form for
-sparse inputs, and the record encoders of the two scalar layouts.  Nothing here calls the library."""
+sparse inputs, the state of the library's network after some of its levels, and the record encoders of the two scalar
+layouts.  Nothing here calls the library."""
 import functools
 import random
 
@@ -83,6 +84,51 @@ def sparse_forward(terms, root, log_n, k, g=1):
     """out[k] of FORWARD for an input with coefficient c at position i for (i, c) in terms"""
     w, n = omega(root, log_n), 1 << log_n
     return sum(c * pow(g, i, R) * pow(w, i * k % n, R) for i, c in terms) % R
+
+
+def bitrev(x, bits):
+    return int(format(x, "0%db" % bits)[::-1], 2) if bits else 0
+
+
+def level_states(a, root, log_n, direction, g=1):
+    """the decimation-in-frequency network of csrc/ntt.hip.h's head comment on natural-order input: yields the state
+    after 0, 1, .. log_n levels (a fresh list each).  a[i] g^i comes first when the direction is FORWARD (INVERSE scales
+    after the network, so its states are those of the plain sums); level l pairs i with i + h, h = n >> (l + 1), for
+    every i with bit log_n - 1 - l clear: a[i], a[i + h] <- a[i] + a[i + h], (a[i] - a[i + h]) w^((i mod h) << l)."""
+    n = 1 << log_n
+    assert len(a) == n
+    a = [x % R for x in a]
+    if direction == FORWARD:
+        t = 1
+        for i in range(n):
+            a[i] = a[i] * t % R
+            t = t * g % R
+    yield list(a)
+    w = omega(root, log_n)
+    for level in range(log_n):
+        h = n >> (level + 1)
+        step = pow(w, 1 << level, R)          # w^((i mod h) << l) = step^(i mod h)
+        tw, t = [], 1
+        for _ in range(h):
+            tw.append(t)
+            t = t * step % R
+        for base in range(0, n, 2 * h):
+            for j in range(h):
+                i = base + j
+                x, y = a[i], a[i + h]
+                a[i] = (x + y) % R
+                a[i + h] = (x - y) * tw[j] % R
+        yield list(a)
+
+
+def levels_state(a, root, log_n, direction, g=1, levels=None):
+    """the state of that network after `levels` levels (default: all).  After log_n levels position bitrev(k) holds
+    sum_i a[i] w^(i k): transform(FORWARD)[k], and g^i n transform(INVERSE)[i] for k = (n - i) mod n."""
+    levels = log_n if levels is None else levels
+    assert 0 <= levels <= log_n
+    for done, state in enumerate(level_states(a, root, log_n, direction, g)):
+        if done == levels:
+            return state
 
 
 def encode(values, layout):
