@@ -994,6 +994,43 @@ int msm_amd_fr_prefix_product_device(msm_amd_ctx* ctx, int scalar_layout, int mo
 int msm_amd_host_fr_prefix_product(int scalar_layout, int mode, const void* in, size_t n, size_t n_vec, int threads,
                                    void* out);
 
+/* ---- polynomials over Fr: evaluate, divide by X - z, combine ----------------------------------------------
+ * What a KZG opening does between the transforms and the MSM of the quotient (halo2 eval_polynomial and kate_division,
+ * arkworks DensePolynomial / (X - z); the fold f = sum_v k^v p_v of a GWC / SHPLONK multi-opening).  A polynomial is n
+ * coefficients, lowest degree first; n_vec polynomials lie back to back.  Records, layouts, reduction of any 256-bit
+ * word, alignment, n n_vec < 2^32 with any n >= 1, the empty calls (n == 0 or n_vec == 0: MSM_AMD_OK, nothing is
+ * touched), the bounded waits and msm_amd_last_error are those of msm_amd_fr_prefix_product*.  z32 / k32 is one record
+ * in the same layout, in HOST memory for every call; y_out / rem_out are n_vec records in HOST memory for every call
+ * (they come back in one copy through ctx-owned page-locked memory, in the call's one bounded wait), fully reduced.
+ * The device side runs on the tiles and levels of the prefix products (ctx-owned memory of about n n_vec / 2^9
+ * records plus n_vec): tiles start at index 0 of a polynomial, level k + 1 holds the values of the tiles of level k
+ * and is the same problem at the point z^(2^T); the host squares z about 40 times per call and every kernel gets the
+ * powers it needs by value. */
+/* y[v] = sum_i c_v[i] z^i.  y_out null with work to do: MSM_AMD_INPUT_ERROR. */
+int msm_amd_fr_poly_eval(msm_amd_ctx* ctx, int scalar_layout, const void* z32, const void* coeffs, size_t n, size_t n_vec,
+                         void* y_out);
+int msm_amd_fr_poly_eval_device(msm_amd_ctx* ctx, int scalar_layout, const void* z32 /* HOST memory */, const void* d_coeffs,
+                                size_t n, size_t n_vec, void* y_out /* HOST memory */, float* kernel_ms);
+int msm_amd_host_fr_poly_eval(int scalar_layout, const void* z32, const void* coeffs, size_t n, size_t n_vec, int threads,
+                              void* y_out);
+/* With s_i = sum_{j >= i} c_j z^(j - i):  out[i] = s_(i+1) for i < n - 1 and out[n - 1] = 0 -- the n - 1 coefficients of
+ * (p(X) - p(z)) / (X - z), padded to n so that the MSM of the quotient takes the same n bases --, rem[v] = s_0 = p_v(z)
+ * (rem_out may be null).  out == in (in place) or disjoint: an out-of-place call leaves `in` unchanged, a partial
+ * overlap is MSM_AMD_INPUT_ERROR. */
+int msm_amd_fr_poly_div_linear(msm_amd_ctx* ctx, int scalar_layout, const void* z32, const void* in, size_t n, size_t n_vec,
+                               void* out, void* rem_out);
+int msm_amd_fr_poly_div_linear_device(msm_amd_ctx* ctx, int scalar_layout, const void* z32 /* HOST memory */,
+                                      const void* d_in, size_t n, size_t n_vec, void* d_out, void* rem_out /* HOST memory */,
+                                      float* kernel_ms);
+int msm_amd_host_fr_poly_div_linear(int scalar_layout, const void* z32, const void* in, size_t n, size_t n_vec, int threads,
+                                    void* out, void* rem_out);
+/* out[i] = sum_{v < n_vec} k^v a[v n + i], i < n: n records.  out may be the first vector of a (out == a) or disjoint
+ * from all n n_vec records of a; anything else is MSM_AMD_INPUT_ERROR. */
+int msm_amd_fr_lincomb(msm_amd_ctx* ctx, int scalar_layout, const void* k32, const void* a, size_t n, size_t n_vec, void* out);
+int msm_amd_fr_lincomb_device(msm_amd_ctx* ctx, int scalar_layout, const void* k32 /* HOST memory */, const void* d_a, size_t n,
+                              size_t n_vec, void* d_out, float* kernel_ms);
+int msm_amd_host_fr_lincomb(int scalar_layout, const void* k32, const void* a, size_t n, size_t n_vec, int threads, void* out);
+
 /* Test aid (no ctx): the plan of a scan over n_vec vectors of n at a tile of 2^tile_log (2 .. 9): out[0] levels, out[1]
  * launches (2 levels - 1), out[2] tiles of the first level over all vectors, out[3] records of ctx-owned device memory */
 int msm_amd_test_fr_plan(size_t n, size_t n_vec, uint32_t tile_log, uint64_t out[4]);

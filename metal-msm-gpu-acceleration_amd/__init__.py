@@ -113,6 +113,9 @@ EXPORTS = [
     "msm_amd_fr_batch_inverse", "msm_amd_fr_batch_inverse_device", "msm_amd_host_fr_batch_inverse",
     "msm_amd_fr_prefix_product", "msm_amd_fr_prefix_product_device", "msm_amd_host_fr_prefix_product",
     "msm_amd_test_fr_plan",
+    "msm_amd_fr_poly_eval", "msm_amd_fr_poly_eval_device", "msm_amd_host_fr_poly_eval",
+    "msm_amd_fr_poly_div_linear", "msm_amd_fr_poly_div_linear_device", "msm_amd_host_fr_poly_div_linear",
+    "msm_amd_fr_lincomb", "msm_amd_fr_lincomb_device", "msm_amd_host_fr_lincomb",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -363,6 +366,19 @@ def _lib():
                                                        POINTER(c_float)]
         L.msm_amd_host_fr_prefix_product.argtypes = [c_int, c_int, c_void_p, c_size_t, c_size_t, c_int, c_void_p]
         L.msm_amd_test_fr_plan.argtypes = [c_size_t, c_size_t, c_uint32, POINTER(c_uint64)]
+        L.msm_amd_fr_poly_eval.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]
+        L.msm_amd_fr_poly_eval_device.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
+                                                  POINTER(c_float)]
+        L.msm_amd_host_fr_poly_eval.argtypes = [c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_int, c_void_p]
+        L.msm_amd_fr_poly_div_linear.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p]
+        L.msm_amd_fr_poly_div_linear_device.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
+                                                        c_void_p, POINTER(c_float)]
+        L.msm_amd_host_fr_poly_div_linear.argtypes = [c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_int, c_void_p,
+                                                      c_void_p]
+        L.msm_amd_fr_lincomb.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]
+        L.msm_amd_fr_lincomb_device.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
+                                                POINTER(c_float)]
+        L.msm_amd_host_fr_lincomb.argtypes = [c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_int, c_void_p]
         L.msm_amd_generate_instance_host.argtypes = [c_uint64, c_size_t, c_int, c_void_p, c_void_p, c_int]
         L.msm_amd_test_op_ifma.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_tuned_split.argtypes = [c_size_t]
@@ -904,6 +920,55 @@ class MsmConfig:
                                                             c_void_p(d_out), ctypes.byref(ms)))
         return ms.value
 
+    # ---- polynomials over Fr: n_vec polynomials of n coefficients back to back, lowest degree first -------
+    def fr_poly_eval(self, coeffs: bytes, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1) -> bytes:
+        """The n_vec records p_v(z) of host coefficients (msm_amd_fr_poly_eval); z: 32 bytes in scalar_layout"""
+        n = len(coeffs) // 32 // n_vec if n_vec else 0
+        y = ctypes.create_string_buffer(max(1, 32 * n_vec))
+        self._check(_lib().msm_amd_fr_poly_eval(self.h, scalar_layout, z, coeffs, n, n_vec, y))
+        return y.raw[:32 * n_vec] if n else b""
+
+    def fr_poly_eval_device(self, d_coeffs, n: int, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1):
+        """The same on device-resident coefficients (msm_amd_fr_poly_eval_device); returns (records, kernel_ms)."""
+        ms = c_float(0)
+        y = ctypes.create_string_buffer(max(1, 32 * n_vec))
+        self._check(_lib().msm_amd_fr_poly_eval_device(self.h, scalar_layout, z, c_void_p(d_coeffs), n, n_vec, y,
+                                                       ctypes.byref(ms)))
+        return (y.raw[:32 * n_vec] if n else b""), ms.value
+
+    def fr_poly_div_linear(self, data: bytes, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1):
+        """(the quotients of p_v by X - z, padded with a zero record to n; the remainders p_v(z)) of host coefficients
+        (msm_amd_fr_poly_div_linear)"""
+        n = len(data) // 32 // n_vec if n_vec else 0
+        out = ctypes.create_string_buffer(max(1, len(data)))
+        rem = ctypes.create_string_buffer(max(1, 32 * n_vec))
+        self._check(_lib().msm_amd_fr_poly_div_linear(self.h, scalar_layout, z, data, n, n_vec, out, rem))
+        return out.raw[:32 * n * n_vec], (rem.raw[:32 * n_vec] if n else b"")
+
+    def fr_poly_div_linear_device(self, d_in, n: int, d_out, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1, rem=True):
+        """The same on device-resident coefficients, d_out == d_in or disjoint (msm_amd_fr_poly_div_linear_device);
+        returns (remainders -- None with rem=False: rem_out is null --, kernel_ms)."""
+        ms = c_float(0)
+        r = ctypes.create_string_buffer(max(1, 32 * n_vec)) if rem else None
+        self._check(_lib().msm_amd_fr_poly_div_linear_device(self.h, scalar_layout, z, c_void_p(d_in), n, n_vec,
+                                                             c_void_p(d_out), r, ctypes.byref(ms)))
+        return ((r.raw[:32 * n_vec] if n else b"") if rem else None), ms.value
+
+    def fr_lincomb(self, data: bytes, k: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1) -> bytes:
+        """out[i] = sum_v k^v a[v n + i] of host records (msm_amd_fr_lincomb)"""
+        n = len(data) // 32 // n_vec if n_vec else 0
+        out = ctypes.create_string_buffer(max(1, 32 * n))
+        self._check(_lib().msm_amd_fr_lincomb(self.h, scalar_layout, k, data, n, n_vec, out))
+        return out.raw[:32 * n]
+
+    def fr_lincomb_device(self, d_a, n: int, d_out, k: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1) -> float:
+        """The same on device-resident records, d_out the first vector or disjoint from all (msm_amd_fr_lincomb_device);
+        returns kernel_ms."""
+        ms = c_float(0)
+        self._check(_lib().msm_amd_fr_lincomb_device(self.h, scalar_layout, k, c_void_p(d_a), n, n_vec, c_void_p(d_out),
+                                                     ctypes.byref(ms)))
+        return ms.value
+
     def test_op_g2(self, op, a, b, count):
         """Raw-limb G2 op (MSM_AMD_G2_RAW_*) on the device: a, b flat u32 lists of count * G2_RAW_IN_WORDS; returns
         count * G2_RAW_OUT_WORDS u32."""
@@ -1252,6 +1317,37 @@ def host_fr_prefix_product(data: bytes, mode=FR_PREFIX_INCLUSIVE, scalar_layout=
     if st != OK:
         raise MsmError(st)
     return out.raw[:32 * n * n_vec]
+
+
+def host_fr_poly_eval(coeffs: bytes, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1, threads=0) -> bytes:
+    """Host twin of MsmConfig.fr_poly_eval (no GPU)."""
+    n = len(coeffs) // 32 // n_vec if n_vec else 0
+    y = ctypes.create_string_buffer(max(1, 32 * n_vec))
+    st = _lib().msm_amd_host_fr_poly_eval(scalar_layout, z, coeffs, n, n_vec, threads, y)
+    if st != OK:
+        raise MsmError(st)
+    return y.raw[:32 * n_vec] if n else b""
+
+
+def host_fr_poly_div_linear(data: bytes, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1, threads=0):
+    """Host twin of MsmConfig.fr_poly_div_linear (no GPU): (quotients, remainders)."""
+    n = len(data) // 32 // n_vec if n_vec else 0
+    out = ctypes.create_string_buffer(max(1, len(data)))
+    rem = ctypes.create_string_buffer(max(1, 32 * n_vec))
+    st = _lib().msm_amd_host_fr_poly_div_linear(scalar_layout, z, data, n, n_vec, threads, out, rem)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:32 * n * n_vec], (rem.raw[:32 * n_vec] if n else b"")
+
+
+def host_fr_lincomb(data: bytes, k: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1, threads=0) -> bytes:
+    """Host twin of MsmConfig.fr_lincomb (no GPU)."""
+    n = len(data) // 32 // n_vec if n_vec else 0
+    out = ctypes.create_string_buffer(max(1, 32 * n))
+    st = _lib().msm_amd_host_fr_lincomb(scalar_layout, k, data, n, n_vec, threads, out)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:32 * n]
 
 
 def test_fr_plan(n, n_vec=1, tile_log=9) -> dict:

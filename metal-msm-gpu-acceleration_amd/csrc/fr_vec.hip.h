@@ -1,4 +1,5 @@
-// Vectors over BN254 Fr (msm_amd_fr_map*, msm_amd_fr_batch_inverse*, msm_amd_fr_prefix_product*): the bodies shared by
+// Vectors over BN254 Fr (msm_amd_fr_map*, msm_amd_fr_batch_inverse*, msm_amd_fr_prefix_product*; the polynomial calls
+// msm_amd_fr_poly_*, msm_amd_fr_lincomb* run on the same scan plan, see launch_fr.h): the bodies shared by
 // the kernels (k_fr.hip), the host twin (host_fr.hip) and the host driver (msm_host.hip).  Everything here compiles for
 // the device and for the host (MSM_HD).  Records are read with ntt_load and written with ntt_store (ntt.hip.h): any
 // 256-bit input is taken mod r, every output is the fully reduced residue in the layout of the input.

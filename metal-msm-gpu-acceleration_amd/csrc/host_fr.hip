@@ -1,6 +1,7 @@
 // Host twins of the Fr vector calls (no ctx, no GPU): the load, store and op bodies of fr_vec.hip.h on the CPU, the
 // records split over the host threads -- the map record by record, the inversion with one inversion per range (the
-// classic trick), the prefix products in two phases (the product of every range, then the ranges from their carries);
+// classic trick), the prefix products in two phases (the product of every range, then the ranges from their carries),
+// the polynomial calls likewise (a range's Horner value, then the ranges from the sums behind them);
 // and the argument checks the twins share with the host driver (msm_host.hip).  The bytes of a result are unique, so the
 // way a twin cuts the work shows nowhere.
 #include <hip/hip_runtime.h>
@@ -59,6 +60,35 @@ const char* fr_unary_check(int scalar_layout, const void* in, uint64_t n, uint64
   if (!in || !out) return "null pointer with n > 0";
   if (device && (((uintptr_t)in | (uintptr_t)out) & 15u)) return "device buffers must be 16-byte aligned";
   if (!fr_overlap_ok(out, in, n * n_vec * 32)) return "the output must be the input itself or disjoint from it";
+  return nullptr;
+}
+
+u256 fr_read_record(int scalar_layout, const void* rec32) {
+  uint32_t rec[8];
+  std::memcpy(rec, rec32, 32);
+  return ntt_load(scalar_layout, rec);
+}
+
+const char* fr_poly_check(int scalar_layout, const void* z32, const void* in, uint64_t n, uint64_t n_vec, const void* out,
+                          const void* values, bool divide, bool device) {
+  if (!fr_layout_known(scalar_layout)) return "scalars in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE only";
+  if ((n >> 32) || (n_vec >> 32) || ((n * n_vec) >> 32)) return "n * n_vec >= 2^32";
+  if (n == 0 || n_vec == 0) return nullptr;
+  if (!z32 || !in || (divide ? !out : !values)) return "null pointer with n > 0";
+  if (device && (((uintptr_t)in | (uintptr_t)out) & 15u)) return "device buffers must be 16-byte aligned";
+  if (divide && !fr_overlap_ok(out, in, n * n_vec * 32)) return "the output must be the input itself or disjoint from it";
+  return nullptr;
+}
+
+const char* fr_lincomb_check(int scalar_layout, const void* k32, const void* a, uint64_t n, uint64_t n_vec, const void* out,
+                             bool device) {
+  if (!fr_layout_known(scalar_layout)) return "scalars in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE only";
+  if ((n >> 32) || (n_vec >> 32) || ((n * n_vec) >> 32)) return "n * n_vec >= 2^32";
+  if (n == 0 || n_vec == 0) return nullptr;
+  if (!k32 || !a || !out) return "null pointer with n > 0";
+  if (device && (((uintptr_t)a | (uintptr_t)out) & 15u)) return "device buffers must be 16-byte aligned";
+  const uintptr_t o = (uintptr_t)out, p = (uintptr_t)a;
+  if (o != p && !(o + n * 32 <= p || p + n * n_vec * 32 <= o)) return "the output must be the first vector or disjoint from every vector";
   return nullptr;
 }
 
@@ -176,10 +206,108 @@ int host_fr_prefix_product(int layout, int mode, const void* in_v, size_t n, siz
   return MSM_AMD_OK;
 }
 
+u256 host_pow(u256 base, uint64_t e) {
+  u256 acc = Fr::one();
+  for (; e != 0; e >>= 1) {
+    if (e & 1) acc = Fr::mul(acc, base);
+    base = Fr::mul(base, base);
+  }
+  return acc;
+}
+
+// The suffix sums s_i = sum_(j >= i) c_j z^(j - i) of n_vec vectors, the flat index space cut into T ranges.
+// A range's first piece is what it holds of the vector its first record lies in.  Phase 1 leaves the Horner value of the
+// first piece of every range that starts inside a vector; from them, last range first, s behind every range's last
+// record.  Phase 2 walks every range down from there.  out null: the evaluation, one walk, which leaves the value of every
+// piece that starts a vector and adds z^len s behind the range's last record to the one piece that a range end cuts.
+int host_fr_poly(int layout, const void* z32, const void* in_v, size_t n, size_t n_vec, int threads, void* out_v, void* val_v,
+                 bool divide) {
+  if (fr_poly_check(layout, z32, in_v, n, n_vec, out_v, val_v, divide, false)) return MSM_AMD_INPUT_ERROR;
+  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
+  const u256 z = fr_read_record(layout, z32);
+  const uint8_t* in = (const uint8_t*)in_v;
+  uint8_t *out = (uint8_t*)out_v, *val = (uint8_t*)val_v;
+  const size_t total = n * n_vec;
+  const unsigned T = worker_count(threads, total);
+  const size_t chunk = (total + T - 1) / T;
+  auto lo_of = [&](unsigned t) { return std::min(total, t * chunk); };
+  auto hi_of = [&](unsigned t) { return std::min(total, lo_of(t) + chunk); };
+  auto piece_end = [&](size_t lo, size_t hi) { return std::min(hi, (lo / n + 1) * n); };   // of the first piece
+  std::vector<u256> head(T, u256_zero()), behind(T, u256_zero()), value(divide ? 0 : n_vec, u256_zero());
+  // phase 1
+  for_ranges(T, total, [&](unsigned t, size_t lo, size_t hi) {
+    const size_t stop = divide ? (lo % n ? piece_end(lo, hi) : lo) : hi;
+    u256 run = u256_zero();
+    for (size_t i = stop; i-- > lo;) {
+      run = Fr::add(Fr::mul(run, z), host_get(layout, in, i));
+      if (i % n == 0) value[i / n] = run, run = u256_zero();
+    }
+    head[t] = run;
+  });
+  // s behind the last record of every range
+  for (unsigned t = T - 1; t-- != 0;) {
+    const size_t lo = lo_of(t + 1), hi = hi_of(t + 1);
+    if (hi_of(t) % n == 0 || lo >= hi) continue;
+    const size_t e = piece_end(lo, hi);
+    behind[t] = e % n == 0 ? head[t + 1] : Fr::add(head[t + 1], Fr::mul(host_pow(z, e - lo), behind[t + 1]));
+  }
+  if (!divide) {
+    for (unsigned t = 0; t < T; ++t) {
+      const size_t hi = hi_of(t);
+      if (hi % n == 0 || lo_of(t) >= hi || (hi - 1) / n * n < lo_of(t)) continue;   // the range end cuts a piece that starts a vector
+      value[hi / n] = Fr::add(value[hi / n], Fr::mul(host_pow(z, hi % n), behind[t]));
+    }
+    for (size_t v = 0; v < n_vec; ++v) host_put(layout, val, v, value[v]);
+    return MSM_AMD_OK;
+  }
+  // phase 2
+  for_ranges(T, total, [&](unsigned t, size_t lo, size_t hi) {
+    u256 run = behind[t];
+    for (size_t i = hi; i-- > lo;) {
+      if ((i + 1) % n == 0) run = u256_zero();
+      const u256 c = host_get(layout, in, i);
+      host_put(layout, out, i, run);
+      run = Fr::add(Fr::mul(run, z), c);
+      if (val && i % n == 0) host_put(layout, val, i / n, run);
+    }
+  });
+  return MSM_AMD_OK;
+}
+
+int host_fr_lincomb(int layout, const void* k32, const void* a_v, size_t n, size_t n_vec, int threads, void* out_v) {
+  if (fr_lincomb_check(layout, k32, a_v, n, n_vec, out_v, false)) return MSM_AMD_INPUT_ERROR;
+  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
+  const u256 k = fr_read_record(layout, k32);
+  const uint8_t* a = (const uint8_t*)a_v;
+  uint8_t* out = (uint8_t*)out_v;
+  for_ranges(worker_count(threads, n), n, [&](unsigned, size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; ++i) {
+      u256 acc = host_get(layout, a, (n_vec - 1) * n + i);
+      for (size_t v = n_vec - 1; v-- != 0;) acc = Fr::add(Fr::mul(acc, k), host_get(layout, a, v * n + i));
+      host_put(layout, out, i, acc);
+    }
+  });
+  return MSM_AMD_OK;
+}
+
 }  // namespace
 }  // namespace msm_amd
 
 extern "C" {
+
+int msm_amd_host_fr_poly_eval(int scalar_layout, const void* z32, const void* coeffs, size_t n, size_t n_vec, int threads,
+                              void* y_out) {
+  return msm_amd::host_fr_poly(scalar_layout, z32, coeffs, n, n_vec, threads, nullptr, y_out, false);
+}
+
+int msm_amd_host_fr_poly_div_linear(int scalar_layout, const void* z32, const void* in, size_t n, size_t n_vec, int threads,
+                                    void* out, void* rem_out) {
+  return msm_amd::host_fr_poly(scalar_layout, z32, in, n, n_vec, threads, out, rem_out, true);
+}
+
+int msm_amd_host_fr_lincomb(int scalar_layout, const void* k32, const void* a, size_t n, size_t n_vec, int threads, void* out) {
+  return msm_amd::host_fr_lincomb(scalar_layout, k32, a, n, n_vec, threads, out);
+}
 
 int msm_amd_host_fr_map(int op, int scalar_layout, const void* k32, const void* a, const void* b, const void* c, size_t n,
                         int threads, void* out) {

@@ -11,6 +11,17 @@
 //                          a lane): c = T^-1 P_(b-1) S_(b+1) inverts the tile's product, the prefix and suffix scans of
 //                          the lane products turn it into the inverse of each lane's product, and the backward sweep of
 //                          the classic batch inversion runs inside the lane.
+//   fr_poly_reduce_kernel  one wave per tile, no LDS: the tile's value H_b = sum_m c_(b 2^T + m) z^m.  Lane l runs Horner in
+//                          z^64 over the records l, l + 64, ..., six xor-shuffle steps v_l += z^(2^s) v_(l xor 2^s) fold
+//                          the lanes; a partial tile reads as padded with zeros.
+//   fr_poly_scan_kernel    one wave per tile: s_i = sum_(j >= i) c_j z^(j - i).  The tile goes to LDS at unit stride, lane
+//                          t walks its records backwards, acc = acc z + c (the lane of a full tile's last record starts
+//                          from the tile's carry, s at the first record of the next tile), six shuffle steps with the
+//                          uniform multipliers z^(per 2^s) for the suffix scan of the lane values, a second backward
+//                          walk that writes s_(i+1) (the division) or s_i (the upper levels) to LDS, and the tile leaves
+//                          at unit stride.  Tiles start at index 0 of a vector, so that only the highest tile is partial
+//                          and its carry is zero: every multiplier is uniform.
+//   fr_lincomb_kernel      one lane per index i: Horner in k over a_v[i], v from the last vector down.
 // Phases are ordered by launch order on one stream only; no kernel reads what another workgroup of its launch wrote.
 // LDS images are eight word planes; slot m sits at m + (m >> log2(records per lane)), so that the unit-stride accesses
 // and the walks of the lanes (stride = records per lane) are both free of bank conflicts, bar one 2-way per access.
@@ -41,6 +52,19 @@ struct FrInvArgs {
   uint32_t tile_log;
   int layout;
   u256 t_inv;
+};
+
+// The powers of a level's point z come by value: no table in memory, no power computed on the device
+struct FrPolyArgs {
+  const uint32_t* src;
+  uint32_t* dst;               // scan
+  const uint32_t* carry;       // scan: the level above, s of tile b + 1 is the carry of tile b; null: every carry is zero
+  uint32_t* totals;            // reduce: one raw record per tile; scan: s_0 of every tile, raw (optional)
+  uint64_t len, tiles;         // records and tiles per vector
+  uint32_t tile_log;
+  int layout, shift;           // shift: slot i takes s_(i+1), the quotient by X - z
+  u256 z;                      // the point of the level
+  u256 step[7];                // reduce: z^(2^s), s < 6, and z^64; scan: z^(per 2^s), s < 6
 };
 
 // An LDS image of a tile: eight planes of 2^T + 64 words, sized at the launch (fr_image_bytes) so that a smaller tile
@@ -237,6 +261,75 @@ __global__ void __launch_bounds__(kFrWave) fr_inv_apply_kernel(FrInvArgs a) {
     store_rec(a.dst + tile_record(t, a.len, 0, m) * 8, fr_store(a.layout, lds_get(lds_x, m)));
 }
 
+__global__ void __launch_bounds__(kFrWave) fr_poly_reduce_kernel(FrPolyArgs a) {
+  const uint32_t lane = threadIdx.x;
+  const TilePlace t = tile_place(blockIdx.x, a.len, a.tiles, a.tile_log);
+  const uint32_t* src = a.src + t.base * 8;
+  u256 acc = u256_zero();
+  if (lane < t.cnt) {
+    // the lane's highest record first
+    uint64_t i = t.first + lane + ((t.cnt - 1 - lane) & ~(kFrWave - 1));
+    acc = fr_load(a.layout, load_rec(src + i * 8));
+    NTT_NO_UNROLL while (i >= t.first + kFrWave) {
+      i -= kFrWave;
+      acc = Fr::add(Fr::mul(acc, a.step[6]), fr_load(a.layout, load_rec(src + i * 8)));
+    }
+  }
+  NTT_NO_UNROLL for (uint32_t s = 0; s < 6; ++s) acc = Fr::add(acc, Fr::mul(a.step[s], wave_xor(acc, 1u << s)));
+  if (lane == 0) store_rec(a.totals + (uint64_t)blockIdx.x * 8, acc);
+}
+
+__global__ void __launch_bounds__(kFrWave) fr_poly_scan_kernel(FrPolyArgs a) {
+  extern __shared__ uint32_t fr_lds[];
+  const Image lds = image(fr_lds, a.tile_log);
+  const uint32_t lane = threadIdx.x;
+  const uint64_t v = blockIdx.x / a.tiles, b = blockIdx.x - v * a.tiles;
+  const TilePlace t = tile_place(blockIdx.x, a.len, a.tiles, a.tile_log);
+  const uint32_t per = 1u << lds.per_log, m0 = lane << lds.per_log;
+  const uint32_t top = ((1u << a.tile_log) >> lds.per_log) - 1u;   // the lane of a full tile's last record
+
+  NTT_NO_UNROLL for (uint32_t m = lane; m < t.cnt; m += kFrWave)
+    lds_put(lds, m, fr_load(a.layout, load_rec(a.src + (t.base + t.first + m) * 8)));
+  __syncthreads();
+
+  // s at the first record of the next tile: record b + 1 of this vector in the level above
+  const u256 carry = a.carry && b + 1 < a.tiles ? load_rec(a.carry + (v * a.tiles + b + 1) * 8) : u256_zero();
+  u256 acc = fr_select(lane == top, carry, u256_zero());
+  NTT_NO_UNROLL for (uint32_t j = per; j-- != 0;) {
+    if (m0 + j >= t.cnt) continue;
+    acc = Fr::add(Fr::mul(acc, a.z), lds_get(lds, m0 + j));
+  }
+  // the suffix scan of the lane values: acc becomes s at the lane's first record
+  NTT_NO_UNROLL for (uint32_t s = 0; s < 6; ++s) {
+    const uint32_t d = 1u << s;
+    const u256 y = wave_down(acc, d);
+    acc = Fr::add(acc, Fr::mul(a.step[s], fr_select(lane + d < kFrWave, y, u256_zero())));
+  }
+  if (a.totals && lane == 0) store_rec(a.totals + (uint64_t)blockIdx.x * 8, acc);
+  // s behind the lane's last record, then down the lane
+  u256 run = fr_select(lane == top, carry, wave_down(acc, 1));
+  NTT_NO_UNROLL for (uint32_t j = per; j-- != 0;) {
+    const uint32_t m = m0 + j;
+    if (m >= t.cnt) continue;
+    const u256 nxt = Fr::add(Fr::mul(run, a.z), lds_get(lds, m));
+    lds_put(lds, m, a.shift ? run : nxt);
+    run = nxt;
+  }
+  __syncthreads();
+
+  NTT_NO_UNROLL for (uint32_t m = lane; m < t.cnt; m += kFrWave)
+    store_rec(a.dst + (t.base + t.first + m) * 8, fr_store(a.layout, lds_get(lds, m)));
+}
+
+__global__ void __launch_bounds__(kFrMapThreads) fr_lincomb_kernel(int layout, u256 k, const uint32_t* A, uint64_t n,
+                                                                    uint64_t n_vec, uint32_t* out) {
+  const uint64_t i = (uint64_t)blockIdx.x * kFrMapThreads + threadIdx.x;
+  if (i >= n) return;
+  u256 acc = fr_load(layout, load_rec(A + ((n_vec - 1) * n + i) * 8));
+  NTT_NO_UNROLL for (uint64_t v = n_vec - 1; v-- != 0;) acc = Fr::add(Fr::mul(acc, k), fr_load(layout, load_rec(A + (v * n + i) * 8)));
+  store_rec(out + i * 8, fr_store(layout, acc));
+}
+
 template <int OP>
 void launch_map_op(hipStream_t st, int layout, const u256& k, const void* a, const void* b, const void* c, size_t n, void* out) {
   hipLaunchKernelGGL(fr_map_kernel<OP>, dim3((uint32_t)((n + kFrMapThreads - 1) / kFrMapThreads)), dim3(kFrMapThreads), 0, st,
@@ -281,6 +374,56 @@ uint32_t launch_fr_scan(hipStream_t st, const FrScanLaunch& c) {
   for (uint32_t k = 0; k + 1 < plan.levels; ++k) launch_reduce(st, level(k), c.n_vec);
   for (uint32_t k = plan.levels; k-- != 0;) launch_scan(st, level(k), c.n_vec);
   return plan.launches;
+}
+
+uint32_t launch_fr_poly(hipStream_t st, const FrPolyLaunch& c) {
+  const FrScanPlan plan = fr_scan_plan(c.n, c.n_vec, c.tile_log);
+  const uint32_t per_log = c.tile_log > 6u ? c.tile_log - 6u : 0u;
+  uint32_t* work = (uint32_t*)c.work;
+  // z^(2^j): level k works at the point z^(2^(T k))
+  u256 pw[kFrPolyPowers];
+  pw[0] = c.z;
+  for (uint32_t j = 1; j < kFrPolyPowers; ++j) pw[j] = Fr::mul(pw[j - 1], pw[j - 1]);
+  auto level = [&](uint32_t k, bool scan) {
+    FrPolyArgs a{};
+    a.len = plan.len[k], a.tiles = plan.tiles[k], a.tile_log = c.tile_log;
+    a.src = k == 0 ? (const uint32_t*)c.in : work + plan.offset[k] * 8;
+    a.layout = k == 0 ? c.layout : kFrRaw;
+    const bool last = k + 1 == plan.levels;
+    uint32_t* above = last ? work + plan.records * 8 : work + plan.offset[k + 1] * 8;
+    const uint32_t e = c.tile_log * k;
+    a.z = pw[e];
+    if (scan) {
+      a.dst = k == 0 ? (uint32_t*)c.out : work + plan.offset[k] * 8;
+      a.shift = k == 0;
+      a.carry = last ? nullptr : above;
+      a.totals = last ? above : nullptr;
+      for (uint32_t s = 0; s < 6; ++s) a.step[s] = pw[e + per_log + s];
+    } else {
+      a.totals = above;
+      for (uint32_t s = 0; s < 7; ++s) a.step[s] = pw[e + s];
+    }
+    return a;
+  };
+  auto reduce = [&](uint32_t k) {
+    const FrPolyArgs a = level(k, false);
+    hipLaunchKernelGGL(fr_poly_reduce_kernel, dim3((uint32_t)(a.tiles * c.n_vec)), dim3(kFrWave), 0, st, a);
+  };
+  if (!c.divide) {
+    for (uint32_t k = 0; k < plan.levels; ++k) reduce(k);
+    return plan.levels;
+  }
+  for (uint32_t k = 0; k + 1 < plan.levels; ++k) reduce(k);
+  for (uint32_t k = plan.levels; k-- != 0;) {
+    const FrPolyArgs a = level(k, true);
+    hipLaunchKernelGGL(fr_poly_scan_kernel, dim3((uint32_t)(a.tiles * c.n_vec)), dim3(kFrWave), fr_image_bytes(a.tile_log), st, a);
+  }
+  return plan.launches;
+}
+
+void launch_fr_lincomb(hipStream_t st, int layout, const u256& k, const void* a, uint64_t n, uint64_t n_vec, void* out) {
+  hipLaunchKernelGGL(fr_lincomb_kernel, dim3((uint32_t)((n + kFrMapThreads - 1) / kFrMapThreads)), dim3(kFrMapThreads), 0, st,
+                     layout, k, (const uint32_t*)a, n, n_vec, (uint32_t*)out);
 }
 
 uint32_t launch_fr_inv_products(hipStream_t st, int layout, const void* in, uint64_t n, uint32_t tile_log, void* work_v) {

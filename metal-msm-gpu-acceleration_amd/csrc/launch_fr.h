@@ -26,6 +26,33 @@ struct FrScanLaunch {
 // every launch of one scan, in stream order; returns the number of launches
 uint32_t launch_fr_scan(hipStream_t st, const FrScanLaunch& c);
 
+// Polynomials over Fr: n_vec vectors of n coefficients, lowest degree first, on the tiles and levels of fr_scan_plan.
+// Level k + 1 holds the values H_b = sum_m c_(b 2^T + m) x^m of the tiles of level k at that level's point x =
+// z^(2^(T k)): the same problem at the point x^(2^T).  Tiles start at index 0 of a vector, so every tile that has a
+// successor is full and every multiplier is uniform.
+//   evaluation  levels reductions, the last one leaves p_v(z)
+//   division    levels - 1 reductions, then the scan s_i = sum_(j >= i) c_j x^(j - i) of every level from the top down,
+//               every tile starting from s of the level above; level 0 writes out[i] = s_(i+1), out[n - 1] = 0, and
+//               the top level leaves s_0 = p_v(z)
+// The n_vec values p_v(z) are raw records (reduced Montgomery residues) behind the totals: work + fr_poly_values(plan).
+// z^(2^j), j < 48: level k reads j from T k up to T k + max(6, T - 1), and T k < 32 because 2^(T k) < n < 2^32
+constexpr uint32_t kFrPolyPowers = 48;
+struct FrPolyLaunch {
+  const void* in;     // n_vec * n records
+  void* out;          // division: n_vec * n records, in == out is allowed
+  void* work;         // fr_scan_plan(n, n_vec, tile_log).records + n_vec records
+  uint64_t n, n_vec;
+  uint32_t tile_log;
+  int layout;
+  bool divide;
+  u256 z;             // Montgomery and reduced
+};
+inline size_t fr_poly_values(const FrScanPlan& p) { return (size_t)p.records * 32; }
+// every launch of one evaluation or division, in stream order; returns the number of launches
+uint32_t launch_fr_poly(hipStream_t st, const FrPolyLaunch& c);
+// out[i] = sum_v k^v a[v n + i], i < n; out may be a
+void launch_fr_lincomb(hipStream_t st, int layout, const u256& k, const void* a, uint64_t n, uint64_t n_vec, void* out);
+
 // The first span of an inversion: the tile products of `in` with zeros read as one, their inclusive prefix (P) and
 // suffix (S) products in `work` (fr_inv_plan), and the number of zeros in the first 8 bytes of the record behind P.
 // T and the count are the 64 bytes at fr_inv_tail(work, plan).
@@ -46,6 +73,14 @@ u256 fr_read_k(int op, int scalar_layout, const void* k32);
 bool fr_overlap_ok(const void* out, const void* p, size_t bytes);
 const char* fr_map_check(int op, int scalar_layout, const void* k32, const void* a, const void* b, const void* c, size_t n,
                          const void* out, bool device);
+// one record in host memory -> reduced Montgomery residue
+u256 fr_read_record(int scalar_layout, const void* rec32);
+// msm_amd_fr_poly_eval* (values required, out unused) and msm_amd_fr_poly_div_linear* (out required, values optional)
+const char* fr_poly_check(int scalar_layout, const void* z32, const void* in, uint64_t n, uint64_t n_vec, const void* out,
+                          const void* values, bool divide, bool device);
+// msm_amd_fr_lincomb*: out is the first vector of a or disjoint from all of a
+const char* fr_lincomb_check(int scalar_layout, const void* k32, const void* a, uint64_t n, uint64_t n_vec, const void* out,
+                             bool device);
 const char* fr_unary_check(int scalar_layout, const void* in, uint64_t n, uint64_t n_vec, const void* out, bool device);
 
 }  // namespace msm_amd

@@ -211,6 +211,8 @@ struct CallState {
   DeviceBuf scratch, pow;          // transform: the ONE batch-sized scratch of a plan with more than one pass, the powers of a shift
   DeviceBuf work;                  // Fr scan and inversion: the tile totals (fr_scan_plan, fr_inv_plan)
   uint8_t* h_record = nullptr;     // pinned, 64 bytes
+  uint8_t* h_values = nullptr;     // pinned: the values a call reads back beside its output (p_v(z) of the polynomial calls)
+  size_t h_values_cap = 0;
   hipEvent_t ev[4] = {};           // start and end of the first and of the second span
   bool ready = false;              // record, h_record and ev exist
   // everything but the record: what a kernel reads only after its own call has written it, so what
@@ -223,7 +225,9 @@ struct CallState {
     for (DeviceBuf* b : scratch_bufs()) kill_buf(*b);
     for (hipEvent_t& e : ev) kill_event(e);
     if (h_record) (void)hipHostFree(h_record);
-    h_record = nullptr;
+    if (h_values) (void)hipHostFree(h_values);
+    h_record = h_values = nullptr;
+    h_values_cap = 0;
     ready = false;
   }
 };
@@ -3690,6 +3694,7 @@ struct DeviceCall {
     DeviceBuf* buf;
     size_t bytes;
   } work[2] = {};               // device-side buffers of the kernels
+  size_t values_bytes = 0;      // what launch leaves at CallIo::values comes back in CallState::h_values
   void all_host(bool h) { host = h, host_in = h ? 7u : 0u; }
 };
 
@@ -3700,6 +3705,7 @@ struct CallIo {
   uint8_t* reasons;
   PointCounters* counters;
   const void* record;   // the 64 bytes to read back: `counters` of a call that has them; else null, unless launch sets it
+  const void* values;   // DeviceCall::values_bytes to read back behind the kernels; launch sets it
 };
 
 // ctx->mu is held.  launch(stream, io) enqueues the kernels and returns a status.  A call with a record gets it back
@@ -3728,6 +3734,12 @@ int device_call(msm_amd_ctx* ctx, const DeviceCall& c, Launch launch, Then then,
   }
   for (const auto& w : c.work)
     if (w.buf && (rc = ensure(ctx, *w.buf, w.bytes))) return rc;
+  if (c.values_bytes > s.h_values_cap) {
+    if (s.h_values) (void)hipHostFree(s.h_values);
+    s.h_values = nullptr, s.h_values_cap = 0;
+    HIP_TRY(ctx, hipHostMalloc((void**)&s.h_values, c.values_bytes, hipHostMallocDefault));
+    s.h_values_cap = c.values_bytes;
+  }
   DeviceBuf* stage[3];
   for (int k = 0; k < 3; ++k) {
     stage[k] = c.stage[k] ? c.stage[k] : &s.in[k];
@@ -3735,7 +3747,8 @@ int device_call(msm_amd_ctx* ctx, const DeviceCall& c, Launch launch, Then then,
   }
   if (c.host && !c.in_place && (rc = ensure(ctx, s.out, c.out_bytes))) return rc;
   if (c.host && c.reasons && (rc = ensure(ctx, s.reasons, c.n))) return rc;
-  CallIo io = {{c.in[0], c.in[1], c.in[2]}, c.out, c.reasons, (PointCounters*)s.record.p, c.counters ? s.record.p : nullptr};
+  CallIo io = {{c.in[0], c.in[1], c.in[2]}, c.out, c.reasons, (PointCounters*)s.record.p, c.counters ? s.record.p : nullptr,
+               nullptr};
   for (int k = 0; k < 3; ++k)
     if ((c.host_in >> k & 1) && c.in_bytes[k]) {
       if ((rc = staged_upload(ctx, stage[k]->p, c.in[k], c.in_bytes[k], st))) return rc;
@@ -3769,7 +3782,8 @@ int device_call(msm_amd_ctx* ctx, const DeviceCall& c, Launch launch, Then then,
   }
   if (c.host && c.out_bytes) HIP_TRY(ctx, hipMemcpyAsync(c.out, io.out, c.out_bytes, hipMemcpyDeviceToHost, st));
   if (c.host && c.reasons) HIP_TRY(ctx, hipMemcpyAsync(c.reasons, io.reasons, c.n, hipMemcpyDeviceToHost, st));
-  if (c.host && (c.out_bytes || c.reasons)) pending = true;
+  if (c.values_bytes) HIP_TRY(ctx, hipMemcpyAsync(s.h_values, io.values, c.values_bytes, hipMemcpyDeviceToHost, st));
+  if ((c.host && (c.out_bytes || c.reasons)) || c.values_bytes) pending = true;
   if (pending && (rc = sync_stream_bounded(ctx, st, c.who.c_str()))) return rc;
   if (timed && !has_record) ms = event_span(s.ev[0], s.ev[1]);
   if (timed && two_spans) ms += event_span(s.ev[2], s.ev[3]);
@@ -4236,9 +4250,11 @@ int msm_amd_test_ntt_twiddles(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain
 
 }  // extern "C"
 
-// ---- vectors over Fr (msm_amd_fr_map*, msm_amd_fr_batch_inverse*, msm_amd_fr_prefix_product*) --------------------------------
+// ---- vectors over Fr (msm_amd_fr_map*, msm_amd_fr_batch_inverse*, msm_amd_fr_prefix_product*, msm_amd_fr_poly_*,
+// msm_amd_fr_lincomb*) ------------------------------------------------------------------------------------------------------
 // Through device_call: the host forms compute over the staged copy of their first operand.  The inversion has two spans
-// of kernels: T and the zero count come back as the call's 64-byte record, the host inverts T.
+// of kernels: T and the zero count come back as the call's 64-byte record, the host inverts T.  The polynomial calls
+// read p_v(z) back through the call's page-locked values buffer, in the one bounded wait behind their kernels.
 namespace {
 
 int fr_map_call(msm_amd_ctx* ctx, bool host, int op, int scalar_layout, const void* k32, const void* a, const void* b,
@@ -4329,9 +4345,100 @@ int fr_inverse_call(msm_amd_ctx* ctx, bool host, int scalar_layout, const void* 
   return rc;
 }
 
+// p_v(z) come back as raw records through CallState::h_values and leave in the caller's layout
+void fr_values_out(const CallState& s, int scalar_layout, size_t n_vec, void* out) {
+  for (size_t v = 0; v < n_vec; ++v) {
+    u256 x;
+    std::memcpy(x.v, s.h_values + v * 32, 32);
+    uint32_t rec[8];
+    ntt_store(scalar_layout, x, rec);
+    std::memcpy((uint8_t*)out + v * 32, rec, 32);
+  }
+}
+
+// msm_amd_fr_poly_eval* (divide false: out is unused, values required) and msm_amd_fr_poly_div_linear*
+int fr_poly_call(msm_amd_ctx* ctx, bool host, bool divide, int scalar_layout, const void* z32, const void* in, size_t n,
+                 size_t n_vec, void* out, void* values, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = std::string(divide ? "msm_amd_fr_poly_div_linear" : "msm_amd_fr_poly_eval") + (host ? "" : "_device");
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_poly_check(scalar_layout, z32, in, n, n_vec, out, values, divide, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  CallState& s = ctx->calls;
+  FrPolyLaunch c{};
+  c.n = n, c.n_vec = n_vec, c.tile_log = ctx->fr_tile_log, c.layout = scalar_layout, c.divide = divide;
+  c.z = fr_read_record(scalar_layout, z32);
+  const FrScanPlan plan = fr_scan_plan(n, n_vec, c.tile_log);
+  d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = n * n_vec * 32;
+  d.out = out, d.out_bytes = divide ? n * n_vec * 32 : 0;
+  d.work[0] = {&s.work, fr_poly_values(plan) + n_vec * 32};
+  d.values_bytes = values ? n_vec * 32 : 0;
+  const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
+    c.in = io.in[0], c.out = io.out, c.work = s.work.p;
+    launch_fr_poly(st, c);
+    io.values = (const uint8_t*)s.work.p + fr_poly_values(plan);
+    return MSM_AMD_OK;
+  });
+  if (rc == MSM_AMD_OK && values) fr_values_out(s, scalar_layout, n_vec, values);
+  return rc;
+}
+
+int fr_lincomb_call(msm_amd_ctx* ctx, bool host, int scalar_layout, const void* k32, const void* a, size_t n, size_t n_vec,
+                    void* out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_lincomb" : "msm_amd_fr_lincomb_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_lincomb_check(scalar_layout, k32, a, n, n_vec, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  // the host form folds into the first vector of the staged copy
+  d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = a, d.in_bytes[0] = n * n_vec * 32;
+  d.out = out, d.out_bytes = n * 32;
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    launch_fr_lincomb(st, scalar_layout, fr_read_record(scalar_layout, k32), io.in[0], n, n_vec, io.out);
+    return MSM_AMD_OK;
+  });
+}
+
 }  // namespace
 
 extern "C" {
+
+int msm_amd_fr_poly_eval(msm_amd_ctx* ctx, int scalar_layout, const void* z32, const void* coeffs, size_t n, size_t n_vec,
+                         void* y_out) {
+  return fr_poly_call(ctx, true, false, scalar_layout, z32, coeffs, n, n_vec, nullptr, y_out, nullptr);
+}
+
+int msm_amd_fr_poly_eval_device(msm_amd_ctx* ctx, int scalar_layout, const void* z32, const void* d_coeffs, size_t n,
+                                size_t n_vec, void* y_out, float* kernel_ms) {
+  return fr_poly_call(ctx, false, false, scalar_layout, z32, d_coeffs, n, n_vec, nullptr, y_out, kernel_ms);
+}
+
+int msm_amd_fr_poly_div_linear(msm_amd_ctx* ctx, int scalar_layout, const void* z32, const void* in, size_t n, size_t n_vec,
+                               void* out, void* rem_out) {
+  return fr_poly_call(ctx, true, true, scalar_layout, z32, in, n, n_vec, out, rem_out, nullptr);
+}
+
+int msm_amd_fr_poly_div_linear_device(msm_amd_ctx* ctx, int scalar_layout, const void* z32, const void* d_in, size_t n,
+                                      size_t n_vec, void* d_out, void* rem_out, float* kernel_ms) {
+  return fr_poly_call(ctx, false, true, scalar_layout, z32, d_in, n, n_vec, d_out, rem_out, kernel_ms);
+}
+
+int msm_amd_fr_lincomb(msm_amd_ctx* ctx, int scalar_layout, const void* k32, const void* a, size_t n, size_t n_vec, void* out) {
+  return fr_lincomb_call(ctx, true, scalar_layout, k32, a, n, n_vec, out, nullptr);
+}
+
+int msm_amd_fr_lincomb_device(msm_amd_ctx* ctx, int scalar_layout, const void* k32, const void* d_a, size_t n, size_t n_vec,
+                              void* d_out, float* kernel_ms) {
+  return fr_lincomb_call(ctx, false, scalar_layout, k32, d_a, n, n_vec, d_out, kernel_ms);
+}
 
 int msm_amd_fr_map(msm_amd_ctx* ctx, int op, int scalar_layout, const void* k32, const void* a, const void* b, const void* c,
                    size_t n, void* out) {
