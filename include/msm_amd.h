@@ -1031,6 +1031,61 @@ int msm_amd_fr_lincomb_device(msm_amd_ctx* ctx, int scalar_layout, const void* k
                               size_t n_vec, void* d_out, float* kernel_ms);
 int msm_amd_host_fr_lincomb(int scalar_layout, const void* k32, const void* a, size_t n, size_t n_vec, int threads, void* out);
 
+/* ---- sparse matrix times vector over Fr: the R1CS witness map ------------------------------------------------
+ * Every R1CS prover starts from A z, B z, C z: three sparse matrices over Fr, fixed per circuit, times the assignment of
+ * one proof (arkworks witness_map_from_matrices; the same step in snarkjs and bellman; Marlin and Spartan-style provers
+ * multiply sparse matrices over Fr as well).  A matrix is built once per key and lives on the device; a product reads x
+ * and writes y where the transforms and the Fr vector calls work.
+ *   y[i] = sum_{k in [row_ptr[i], row_ptr[i+1])} values[k] x[col_idx[k]] mod r,   i < n_rows
+ * The matrix is CSR in HOST memory: row_ptr of n_rows + 1 offsets, col_idx and values of nnz = row_ptr[n_rows] entries.  A
+ * row may be empty (y[i] = 0); a column may repeat within a row (the terms add); an explicit zero value is legal.
+ * Records as in the Fr vector calls: MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE (MSM_AMD_SCALAR_CANON_BE32:
+ * MSM_AMD_INPUT_ERROR), any 256-bit word is taken mod r, every y[i] is the fully reduced residue -- the bytes of y are
+ * unique and depend on no order of summation, plan or thread count.  The layout of `values` is fixed at the build; the
+ * layout of x and y is chosen per call; the handle keeps Montgomery residues.
+ * msm_amd_fr_matrix_build: MSM_AMD_INPUT_ERROR for a null pointer (col_idx and values may be null only with nnz == 0),
+ * n_rows == 0, n_cols == 0, n_rows or n_cols or nnz >= 2^32, row_ptr[0] != 0, a decreasing row_ptr and any col_idx[k] >=
+ * n_cols -- every column is checked on the host before anything is uploaded, so a bad matrix never becomes a wild read
+ * on the device.  The values are reduced and deduplicated (r + 1 and 1 share an entry; R1CS values are mostly +-1): the
+ * device holds 8 bytes per entry -- column and dictionary id -- and 32 per distinct value; n_distinct and the size of the
+ * one allocation come back from msm_amd_fr_matrix_info, where any out pointer may be null.  msm_amd_destroy releases the
+ * handles the caller did not free.
+ * msm_amd_fr_matvec*: MSM_AMD_INPUT_ERROR for a pointer that is not a live matrix handle of this ctx (a transform domain
+ * or a table handle is none; a freed handle neither), a null x or y, a device pointer that is not 16-byte aligned, a y
+ * that overlaps x in any way (the product is out of place only: a row gathers from all of x), and d_x or d_y overlapping
+ * the matrix.  The calls serialise on the ctx and wait -- bounded -- for its earlier work (a busy ctx:
+ * MSM_AMD_PIPELINE_ERROR, msm_amd_last_error names the call); the host-buffer form uploads x through the page-locked
+ * staging ring and copies y back; kernel_ms (optional) is the device time of the kernels.
+ * On the device short rows take one lane each, longer rows one wave per segment, and a row of several segments leaves
+ * partial sums in ctx-owned memory that a last launch folds: one to three launches in stream order, nothing waits on
+ * another workgroup.  (Development knobs at msm_amd_init: MSM_AMD_FR_MAT_LONG = 1 .. 4096, rows above this many entries
+ * leave the lane path, default 32; MSM_AMD_FR_MAT_SEG_LOG = 6 .. 20, entries per wave of the other path as a power of
+ * two, default 8 (measured: profiles/fr_mat_ab.txt); MSM_AMD_FR_MAT_SIGNS = 0 / 1, the kernels that add and subtract
+ * entries of value 1 and r - 1 without a product, default 0.  A matrix is planned at its build.  No byte of a result
+ * depends on any of them.) */
+typedef struct msm_amd_fr_matrix msm_amd_fr_matrix;
+int msm_amd_fr_matrix_build(msm_amd_ctx* ctx, int scalar_layout, size_t n_rows, size_t n_cols,
+                            const uint64_t* row_ptr /* n_rows + 1 */, const uint32_t* col_idx /* nnz */,
+                            const void* values /* nnz x 32 B */, msm_amd_fr_matrix** out); /* all HOST memory */
+int msm_amd_fr_matrix_info(msm_amd_ctx* ctx, const msm_amd_fr_matrix* matrix, size_t* n_rows, size_t* n_cols, size_t* nnz,
+                           size_t* n_distinct, size_t* device_bytes);
+int msm_amd_fr_matrix_free(msm_amd_ctx* ctx, msm_amd_fr_matrix* matrix);
+int msm_amd_fr_matvec(msm_amd_ctx* ctx, const msm_amd_fr_matrix* matrix, int scalar_layout, const void* x, void* y);
+int msm_amd_fr_matvec_device(msm_amd_ctx* ctx, const msm_amd_fr_matrix* matrix, int scalar_layout, const void* d_x, void* d_y,
+                             float* kernel_ms);
+/* The same on the CPU (no ctx, no GPU): scalar_layout is that of values, x and y; the same argument checks; rows go to
+ * the threads in ranges of equal entry count; threads <= 0: up to 16 host threads. */
+int msm_amd_host_fr_matvec(int scalar_layout, size_t n_rows, size_t n_cols, const uint64_t* row_ptr, const uint32_t* col_idx,
+                           const void* values, const void* x, int threads, void* y);
+/* Test aid (no ctx, CPU only): the plan of a matrix with these row offsets at long_rows (1 .. 4096) and seg_log (6 .. 20).
+ * counts: [0] lane rows, [1] wave rows, [2] segments, [3] split rows, [4] partial records, [5] launches (1, 2 or 3), [6]
+ * dispatched waves (one per 64 consecutive rows, one per segment, one per split row), [7] 0.  segs (may be null with
+ * segs_cap == 0) receives the first segs_cap segment records of four words: row, first entry, entry count, partial slot
+ * (0xFFFFFFFF: the segment is its whole row and stores to y).  The other test aid of these calls is
+ * msm_amd_test_fill_workspaces: it poisons the partial records too. */
+int msm_amd_test_fr_matrix_plan(size_t n_rows, const uint64_t* row_ptr, uint32_t long_rows, uint32_t seg_log,
+                                uint64_t counts[8], uint32_t* segs, size_t segs_cap);
+
 /* Test aid (no ctx): the plan of a scan over n_vec vectors of n at a tile of 2^tile_log (2 .. 9): out[0] levels, out[1]
  * launches (2 levels - 1), out[2] tiles of the first level over all vectors, out[3] records of ctx-owned device memory */
 int msm_amd_test_fr_plan(size_t n, size_t n_vec, uint32_t tile_log, uint64_t out[4]);

@@ -116,6 +116,8 @@ EXPORTS = [
     "msm_amd_fr_poly_eval", "msm_amd_fr_poly_eval_device", "msm_amd_host_fr_poly_eval",
     "msm_amd_fr_poly_div_linear", "msm_amd_fr_poly_div_linear_device", "msm_amd_host_fr_poly_div_linear",
     "msm_amd_fr_lincomb", "msm_amd_fr_lincomb_device", "msm_amd_host_fr_lincomb",
+    "msm_amd_fr_matrix_build", "msm_amd_fr_matrix_info", "msm_amd_fr_matrix_free", "msm_amd_fr_matvec",
+    "msm_amd_fr_matvec_device", "msm_amd_host_fr_matvec", "msm_amd_test_fr_matrix_plan",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -379,6 +381,16 @@ def _lib():
         L.msm_amd_fr_lincomb_device.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
                                                 POINTER(c_float)]
         L.msm_amd_host_fr_lincomb.argtypes = [c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_int, c_void_p]
+        L.msm_amd_fr_matrix_build.argtypes = [c_void_p, c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p,
+                                              POINTER(c_void_p)]
+        L.msm_amd_fr_matrix_info.argtypes = [c_void_p, c_void_p] + [POINTER(c_size_t)] * 5
+        L.msm_amd_fr_matrix_free.argtypes = [c_void_p, c_void_p]
+        L.msm_amd_fr_matvec.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+        L.msm_amd_fr_matvec_device.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_float)]
+        L.msm_amd_host_fr_matvec.argtypes = [c_int, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                             c_void_p]
+        L.msm_amd_test_fr_matrix_plan.argtypes = [c_size_t, c_void_p, c_uint32, c_uint32, POINTER(c_uint64), c_void_p,
+                                                  c_size_t]
         L.msm_amd_generate_instance_host.argtypes = [c_uint64, c_size_t, c_int, c_void_p, c_void_p, c_int]
         L.msm_amd_test_op_ifma.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_tuned_split.argtypes = [c_size_t]
@@ -969,6 +981,37 @@ class MsmConfig:
                                                      ctypes.byref(ms)))
         return ms.value
 
+    # ---- sparse matrix times vector over Fr ---------------------------------------------------------
+    def fr_matrix_build(self, n_rows, n_cols, row_ptr, col_idx, values: bytes, scalar_layout=SCALAR_MONT_LE) -> "FrMatrix":
+        """A CSR matrix of host data on this ctx's device (msm_amd_fr_matrix_build): row_ptr of n_rows + 1 offsets and
+        col_idx of nnz columns (sequences of int, or the packed u64 / u32 bytes), values of nnz records; col_idx and
+        values may be None with nnz == 0."""
+        h = c_void_p()
+        self._check(_lib().msm_amd_fr_matrix_build(self.h, scalar_layout, n_rows, n_cols, _csr_u64(row_ptr),
+                                                   _csr_u32(col_idx), values, ctypes.byref(h)))
+        return FrMatrix(self, h)
+
+    def fr_matrix_info(self, mat) -> dict:
+        return _fr_matrix_info(self, _fr_matrix_handle(mat))
+
+    def fr_matrix_free(self, mat):
+        self._check(_lib().msm_amd_fr_matrix_free(self.h, _fr_matrix_handle(mat)))
+
+    def fr_matvec(self, mat, x: bytes, scalar_layout=SCALAR_MONT_LE, n_rows=None) -> bytes:
+        """y = M x of host records (msm_amd_fr_matvec); n_rows: the rows of the matrix if the caller knows them"""
+        if n_rows is None:
+            n_rows = self.fr_matrix_info(mat)["n_rows"]
+        y = ctypes.create_string_buffer(max(1, 32 * n_rows))
+        self._check(_lib().msm_amd_fr_matvec(self.h, _fr_matrix_handle(mat), scalar_layout, x, y))
+        return y.raw[:32 * n_rows]
+
+    def fr_matvec_device(self, mat, d_x, d_y, scalar_layout=SCALAR_MONT_LE) -> float:
+        """The same on device-resident records, d_y disjoint from d_x (msm_amd_fr_matvec_device); returns kernel_ms."""
+        ms = c_float(0)
+        self._check(_lib().msm_amd_fr_matvec_device(self.h, _fr_matrix_handle(mat), scalar_layout, c_void_p(d_x),
+                                                    c_void_p(d_y), ctypes.byref(ms)))
+        return ms.value
+
     def test_op_g2(self, op, a, b, count):
         """Raw-limb G2 op (MSM_AMD_G2_RAW_*) on the device: a, b flat u32 lists of count * G2_RAW_IN_WORDS; returns
         count * G2_RAW_OUT_WORDS u32."""
@@ -1286,6 +1329,69 @@ def test_ntt_slots(log_n, tile_log, pass_index, wg) -> list:
     if st != OK:
         raise MsmError(st)
     return list(out)
+
+
+class FrMatrix:
+    """A sparse matrix over Fr of one MsmConfig (msm_amd_fr_matrix_*)."""
+
+    def __init__(self, cfg, handle):
+        self.cfg, self.h = cfg, handle
+
+    def info(self) -> dict:
+        return _fr_matrix_info(self.cfg, self.h)
+
+    def free(self):
+        self.cfg._check(_lib().msm_amd_fr_matrix_free(self.cfg.h, self.h))
+
+
+def _fr_matrix_handle(mat):
+    return mat.h if isinstance(mat, (FrMatrix, NttDomain)) else mat
+
+
+def _fr_matrix_info(cfg, handle) -> dict:
+    out = [c_size_t(0) for _ in range(5)]
+    cfg._check(_lib().msm_amd_fr_matrix_info(cfg.h, handle, *[ctypes.byref(v) for v in out]))
+    return dict(zip(("n_rows", "n_cols", "nnz", "n_distinct", "device_bytes"), (v.value for v in out)))
+
+
+def _csr_u64(seq):
+    """row offsets for the C side: packed bytes as they are, a sequence as a u64 array, None as null"""
+    if seq is None or isinstance(seq, (bytes, bytearray)):
+        return seq if seq is None else bytes(seq)
+    return (c_uint64 * len(seq))(*seq)
+
+
+def _csr_u32(seq):
+    if seq is None or isinstance(seq, (bytes, bytearray)):
+        return seq if seq is None else bytes(seq)
+    return (c_uint32 * max(1, len(seq)))(*seq)
+
+
+def host_fr_matvec(n_rows, n_cols, row_ptr, col_idx, values: bytes, x: bytes, scalar_layout=SCALAR_MONT_LE, threads=0,
+                   y=None) -> bytes:
+    """Host twin of MsmConfig.fr_matrix_build + fr_matvec (no GPU); y: a ctypes buffer to write into (argument tests)"""
+    out = ctypes.create_string_buffer(max(1, 32 * n_rows)) if y is None else y
+    st = _lib().msm_amd_host_fr_matvec(scalar_layout, n_rows, n_cols, _csr_u64(row_ptr), _csr_u32(col_idx), values, x,
+                                       threads, out)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:32 * n_rows] if y is None else None
+
+
+def test_fr_matrix_plan(row_ptr, long_rows=32, seg_log=8, segs_cap=0) -> dict:
+    """The plan of a matrix with these row offsets (msm_amd_test_fr_matrix_plan): the counts by name, and `segs`, the
+    first segs_cap segment records as (row, first, count, slot) with slot None for a row of one segment."""
+    n_rows = (len(row_ptr) // 8 if isinstance(row_ptr, (bytes, bytearray)) else len(row_ptr)) - 1
+    counts = (c_uint64 * 8)()
+    segs = (c_uint32 * (4 * max(1, segs_cap)))()
+    st = _lib().msm_amd_test_fr_matrix_plan(n_rows, _csr_u64(row_ptr), long_rows, seg_log, counts, segs, segs_cap)
+    if st != OK:
+        raise MsmError(st)
+    plan = dict(zip(("lane_rows", "wave_rows", "segments", "split_rows", "partials", "launches", "waves"), counts))
+    take = min(segs_cap, plan["segments"])
+    plan["segs"] = [(segs[4 * k], segs[4 * k + 1], segs[4 * k + 2], None if segs[4 * k + 3] == 0xFFFFFFFF else segs[4 * k + 3])
+                    for k in range(take)]
+    return plan
 
 
 def host_fr_map(op, a: bytes, b: bytes = None, c: bytes = None, k: bytes = None, scalar_layout=SCALAR_MONT_LE,

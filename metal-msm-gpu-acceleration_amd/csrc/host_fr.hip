@@ -1,7 +1,8 @@
 // Host twins of the Fr vector calls (no ctx, no GPU): the load, store and op bodies of fr_vec.hip.h on the CPU, the
 // records split over the host threads -- the map record by record, the inversion with one inversion per range (the
 // classic trick), the prefix products in two phases (the product of every range, then the ranges from their carries),
-// the polynomial calls likewise (a range's Horner value, then the ranges from the sums behind them);
+// the polynomial calls likewise (a range's Horner value, then the ranges from the sums behind them), the sparse product
+// row by row over ranges of equal entry count;
 // and the argument checks the twins share with the host driver (msm_host.hip).  The bytes of a result are unique, so the
 // way a twin cuts the work shows nowhere.
 #include <hip/hip_runtime.h>
@@ -90,6 +91,100 @@ const char* fr_lincomb_check(int scalar_layout, const void* k32, const void* a, 
   const uintptr_t o = (uintptr_t)out, p = (uintptr_t)a;
   if (o != p && !(o + n * 32 <= p || p + n * n_vec * 32 <= o)) return "the output must be the first vector or disjoint from every vector";
   return nullptr;
+}
+
+const char* fr_matrix_check(int scalar_layout, uint64_t n_rows, uint64_t n_cols, const uint64_t* row_ptr,
+                            const uint32_t* col_idx, const void* values) {
+  if (!fr_layout_known(scalar_layout)) return "scalars in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE only";
+  if (n_rows == 0 || n_cols == 0) return "n_rows and n_cols must be at least 1";
+  if ((n_rows >> 32) || (n_cols >> 32)) return "n_rows or n_cols >= 2^32";
+  if (!row_ptr) return "null row_ptr";
+  if (row_ptr[0] != 0) return "row_ptr[0] must be 0";
+  for (uint64_t i = 0; i < n_rows; ++i) {
+    if (row_ptr[i + 1] < row_ptr[i]) return "row_ptr must not decrease";
+    if (row_ptr[i + 1] >> 32) return "nnz >= 2^32";
+  }
+  const uint64_t nnz = row_ptr[n_rows];
+  if (nnz && (!col_idx || !values)) return "null col_idx or values with nnz > 0";
+  for (uint64_t k = 0; k < nnz; ++k)
+    if (col_idx[k] >= n_cols) return "a column index is not below n_cols";
+  return nullptr;
+}
+
+const char* fr_matvec_check(int scalar_layout, uint64_t n_rows, uint64_t n_cols, const void* x, const void* y, bool device) {
+  if (!fr_layout_known(scalar_layout)) return "scalars in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE only";
+  if (!x || !y) return "null x or y";
+  if (device && (((uintptr_t)x | (uintptr_t)y) & 15u)) return "device buffers must be 16-byte aligned";
+  const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
+  if (a < b + n_rows * 32 && b < a + n_cols * 32) return "y must not overlap x: the product is out of place only";
+  return nullptr;
+}
+
+namespace {
+
+struct FrMatDictionary {
+  std::vector<u256> records;
+  static constexpr uint32_t kEmpty = 0xFFFFFFFFu;   // ids stay below it: nnz < 2^32
+  std::vector<uint32_t> slots = std::vector<uint32_t>(1024, kEmpty);   // open addressing, a power of two
+  static uint64_t hash(const u256& x) {
+    uint64_t h = 0x9E3779B97F4A7C15ull;
+    for (int w = 0; w < 8; ++w) h = (h ^ x.v[w]) * 0xFF51AFD7ED558CCDull, h ^= h >> 29;
+    return h;
+  }
+  static bool same(const u256& a, const u256& b) { return std::memcmp(a.v, b.v, 32) == 0; }
+  void place(uint32_t id) {
+    const size_t mask = slots.size() - 1;
+    size_t at = hash(records[id]) & mask;
+    while (slots[at] != kEmpty) at = (at + 1) & mask;
+    slots[at] = id;
+  }
+  uint32_t id_of(const u256& x) {
+    const size_t mask = slots.size() - 1;
+    for (size_t at = hash(x) & mask;; at = (at + 1) & mask) {
+      if (slots[at] == kEmpty) break;
+      if (same(records[slots[at]], x)) return slots[at];
+    }
+    records.push_back(x);
+    const uint32_t id = (uint32_t)(records.size() - 1);
+    if (records.size() * 2 > slots.size()) {
+      slots.assign(slots.size() * 2, kEmpty);
+      for (uint32_t j = 0; j <= id; ++j) place(j);
+    } else {
+      place(id);
+    }
+    return id;
+  }
+};
+
+}  // namespace
+
+void fr_mat_build_image(int scalar_layout, uint64_t n_rows, const uint64_t* row_ptr, const uint32_t* col_idx,
+                        const void* values, uint32_t long_rows, uint32_t seg_log, FrMatPlan* plan, FrMatImage* at,
+                        uint64_t* n_distinct, uint64_t* dict_records, std::vector<uint8_t>* image) {
+  const uint64_t nnz = row_ptr[n_rows];
+  std::vector<uint32_t> ids(nnz);
+  FrMatDictionary dict;
+  dict.id_of(Fr::one());                            // id 0
+  dict.id_of(Fr::sub(u256_zero(), Fr::one()));      // id 1
+  bool used[2] = {false, false};
+  for (uint64_t k = 0; k < nnz; ++k) {
+    ids[k] = dict.id_of(fr_read_record(scalar_layout, (const uint8_t*)values + k * 32));
+    if (ids[k] < 2) used[ids[k]] = true;
+  }
+  std::vector<FrMatSeg> segs;
+  std::vector<FrMatSplit> splits;
+  *plan = fr_mat_plan(n_rows, row_ptr, long_rows, seg_log, &segs, &splits);
+  *dict_records = dict.records.size();
+  *n_distinct = *dict_records - (used[0] ? 0 : 1) - (used[1] ? 0 : 1);
+  *at = fr_mat_image(n_rows, nnz, *dict_records, *plan);
+  image->assign(at->bytes, 0);
+  uint32_t* row_off = (uint32_t*)(image->data() + at->row_off);
+  for (uint64_t i = 0; i <= n_rows; ++i) row_off[i] = (uint32_t)row_ptr[i];
+  uint32_t* ent = (uint32_t*)(image->data() + at->ent);
+  for (uint64_t k = 0; k < nnz; ++k) ent[2 * k] = col_idx[k], ent[2 * k + 1] = ids[k];
+  std::memcpy(image->data() + at->dict, dict.records.data(), *dict_records * 32);
+  if (!segs.empty()) std::memcpy(image->data() + at->segs, segs.data(), segs.size() * sizeof(FrMatSeg));
+  if (!splits.empty()) std::memcpy(image->data() + at->splits, splits.data(), splits.size() * sizeof(FrMatSplit));
 }
 
 namespace {
@@ -290,10 +385,58 @@ int host_fr_lincomb(int layout, const void* k32, const void* a_v, size_t n, size
   return MSM_AMD_OK;
 }
 
+// Rows in T ranges of about equal entry count: range t starts at the first row whose offset reaches t nnz / T
+int host_fr_matvec(int layout, uint64_t n_rows, uint64_t n_cols, const uint64_t* row_ptr, const uint32_t* col_idx,
+                   const void* values_v, const void* x_v, int threads, void* y_v) {
+  if (fr_matrix_check(layout, n_rows, n_cols, row_ptr, col_idx, values_v) || fr_matvec_check(layout, n_rows, n_cols, x_v, y_v, false))
+    return MSM_AMD_INPUT_ERROR;
+  const uint8_t *values = (const uint8_t*)values_v, *x = (const uint8_t*)x_v;
+  uint8_t* y = (uint8_t*)y_v;
+  const uint64_t nnz = row_ptr[n_rows];
+  const unsigned T = worker_count(threads, n_rows);
+  std::vector<uint64_t> start(T + 1, n_rows);
+  start[0] = 0;
+  for (unsigned t = 1; t < T; ++t)
+    start[t] = std::lower_bound(row_ptr, row_ptr + n_rows, nnz / T * t + nnz % T * t / T) - row_ptr;
+  for_ranges(T, T, [&](unsigned, size_t lo, size_t hi) {
+    for (size_t t = lo; t < hi; ++t)
+      for (uint64_t i = start[t]; i < start[t + 1]; ++i) {
+        u256 acc = u256_zero();
+        for (uint64_t k = row_ptr[i]; k < row_ptr[i + 1]; ++k)
+          acc = Fr::add(acc, Fr::mul(host_get(layout, values, k), host_get(layout, x, col_idx[k])));
+        host_put(layout, y, i, acc);
+      }
+  });
+  return MSM_AMD_OK;
+}
+
 }  // namespace
 }  // namespace msm_amd
 
 extern "C" {
+
+int msm_amd_host_fr_matvec(int scalar_layout, size_t n_rows, size_t n_cols, const uint64_t* row_ptr, const uint32_t* col_idx,
+                           const void* values, const void* x, int threads, void* y) {
+  return msm_amd::host_fr_matvec(scalar_layout, n_rows, n_cols, row_ptr, col_idx, values, x, threads, y);
+}
+
+int msm_amd_test_fr_matrix_plan(size_t n_rows, const uint64_t* row_ptr, uint32_t long_rows, uint32_t seg_log,
+                                uint64_t counts[8], uint32_t* segs, size_t segs_cap) {
+  using namespace msm_amd;
+  const uint64_t rows = n_rows;
+  if (!counts || !row_ptr || rows == 0 || (rows >> 32) || long_rows < kFrMatMinLong || long_rows > kFrMatMaxLong ||
+      seg_log < kFrMatMinSegLog || seg_log > kFrMatMaxSegLog || (segs_cap && !segs) || row_ptr[0] != 0)
+    return MSM_AMD_INPUT_ERROR;
+  for (uint64_t i = 0; i < rows; ++i)
+    if (row_ptr[i + 1] < row_ptr[i] || (row_ptr[i + 1] >> 32)) return MSM_AMD_INPUT_ERROR;
+  std::vector<FrMatSeg> all;
+  const FrMatPlan p = fr_mat_plan(rows, row_ptr, long_rows, seg_log, &all, nullptr);
+  const uint64_t c[8] = {p.lane_rows, p.wave_rows, p.segments, p.split_rows, p.partials, p.launches, p.waves, 0};
+  std::memcpy(counts, c, sizeof c);
+  const size_t take = std::min<size_t>(segs_cap, all.size());
+  if (take) std::memcpy(segs, all.data(), take * sizeof(FrMatSeg));
+  return MSM_AMD_OK;
+}
 
 int msm_amd_host_fr_poly_eval(int scalar_layout, const void* z32, const void* coeffs, size_t n, size_t n_vec, int threads,
                               void* y_out) {

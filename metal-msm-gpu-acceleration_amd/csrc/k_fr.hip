@@ -22,6 +22,13 @@
 //                          at unit stride.  Tiles start at index 0 of a vector, so that only the highest tile is partial
 //                          and its carry is zero: every multiplier is uniform.
 //   fr_lincomb_kernel      one lane per index i: Horner in k over a_v[i], v from the last vector down.
+//   fr_mat_lane_kernel     y = M x, rows of at most LONG entries (fr_mat.hip.h): one lane per row, consecutive lanes on
+//                          consecutive rows; per entry one 8-byte (column, id) load, the dictionary record and the gathered
+//                          x record (two dwordx4 each), one product, one addition.  A lane of a longer row stores nothing.
+//                          <SIGNS>: an entry whose value is 1 or r - 1 is added or subtracted without a product.
+//   fr_mat_wave_kernel     one wave per segment of a longer row: lane l takes the entries l, l + 64, ..., six xor-shuffle
+//                          additions fold the lanes, lane 0 stores y[row], or the raw partial sum of a split row.
+//   fr_mat_fold_kernel     one wave per split row: the sum of its partials, the same fold, y[row].
 // Phases are ordered by launch order on one stream only; no kernel reads what another workgroup of its launch wrote.
 // LDS images are eight word planes; slot m sits at m + (m >> log2(records per lane)), so that the unit-stride accesses
 // and the walks of the lanes (stride = records per lane) are both free of bank conflicts, bar one 2-way per access.
@@ -330,6 +337,66 @@ __global__ void __launch_bounds__(kFrMapThreads) fr_lincomb_kernel(int layout, u
   store_rec(out + i * 8, fr_store(layout, acc));
 }
 
+struct FrMatArgs {
+  const uint32_t* row_off;   // n_rows + 1
+  const uint2* ent;          // (column, dictionary id)
+  const uint32_t* dict;      // raw records
+  const uint4* segs;         // FrMatSeg
+  const uint4* splits;       // FrMatSplit
+  const uint32_t* x;
+  uint32_t* y;
+  uint32_t* partial;         // raw records
+  uint64_t n_rows;
+  uint32_t long_rows;
+  int layout;
+};
+
+// acc + value x[column] for entry k of the matrix.  SIGNS: the dictionary ids 0 and 1 are pinned to 1 and r - 1 (fr_mat.hip.h),
+// and such an entry is added or subtracted without the product and without its dictionary record
+template <bool SIGNS>
+__device__ __forceinline__ u256 mat_add_term(const FrMatArgs& a, const u256& acc, uint32_t k) {
+  const uint2 e = a.ent[k];
+  const u256 x = fr_load(a.layout, load_rec(a.x + (uint64_t)e.x * 8));
+  if (SIGNS && e.y < 2u) return e.y ? Fr::sub(acc, x) : Fr::add(acc, x);
+  return Fr::add(acc, Fr::mul(load_rec(a.dict + (uint64_t)e.y * 8), x));
+}
+__device__ __forceinline__ u256 wave_sum(u256 acc) {
+  NTT_NO_UNROLL for (uint32_t d = kFrWave / 2; d != 0; d >>= 1) acc = Fr::add(acc, wave_xor(acc, d));
+  return acc;
+}
+
+template <bool SIGNS>
+__global__ void __launch_bounds__(kFrMapThreads) fr_mat_lane_kernel(FrMatArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * kFrMapThreads + threadIdx.x;
+  if (i >= a.n_rows) return;
+  const uint32_t lo = a.row_off[i], hi = a.row_off[i + 1];
+  if (hi - lo > a.long_rows) return;
+  u256 acc = u256_zero();
+  NTT_NO_UNROLL for (uint32_t k = lo; k < hi; ++k) acc = mat_add_term<SIGNS>(a, acc, k);
+  store_rec(a.y + i * 8, fr_store(a.layout, acc));
+}
+
+template <bool SIGNS>
+__global__ void __launch_bounds__(kFrWave) fr_mat_wave_kernel(FrMatArgs a) {
+  const uint32_t lane = threadIdx.x;
+  const uint4 s = a.segs[blockIdx.x];   // row, first, count, slot
+  u256 acc = u256_zero();
+  NTT_NO_UNROLL for (uint32_t m = lane; m < s.z; m += kFrWave) acc = mat_add_term<SIGNS>(a, acc, s.y + m);
+  acc = wave_sum(acc);
+  if (lane != 0) return;
+  if (s.w == kFrMatDirect) store_rec(a.y + (uint64_t)s.x * 8, fr_store(a.layout, acc));
+  else store_rec(a.partial + (uint64_t)s.w * 8, acc);
+}
+
+__global__ void __launch_bounds__(kFrWave) fr_mat_fold_kernel(FrMatArgs a) {
+  const uint32_t lane = threadIdx.x;
+  const uint4 s = a.splits[blockIdx.x];   // row, slot, count
+  u256 acc = u256_zero();
+  NTT_NO_UNROLL for (uint32_t m = lane; m < s.z; m += kFrWave) acc = Fr::add(acc, load_rec(a.partial + ((uint64_t)s.y + m) * 8));
+  acc = wave_sum(acc);
+  if (lane == 0) store_rec(a.y + (uint64_t)s.x * 8, fr_store(a.layout, acc));
+}
+
 template <int OP>
 void launch_map_op(hipStream_t st, int layout, const u256& k, const void* a, const void* b, const void* c, size_t n, void* out) {
   hipLaunchKernelGGL(fr_map_kernel<OP>, dim3((uint32_t)((n + kFrMapThreads - 1) / kFrMapThreads)), dim3(kFrMapThreads), 0, st,
@@ -424,6 +491,23 @@ uint32_t launch_fr_poly(hipStream_t st, const FrPolyLaunch& c) {
 void launch_fr_lincomb(hipStream_t st, int layout, const u256& k, const void* a, uint64_t n, uint64_t n_vec, void* out) {
   hipLaunchKernelGGL(fr_lincomb_kernel, dim3((uint32_t)((n + kFrMapThreads - 1) / kFrMapThreads)), dim3(kFrMapThreads), 0, st,
                      layout, k, (const uint32_t*)a, n, n_vec, (uint32_t*)out);
+}
+
+uint32_t launch_fr_matvec(hipStream_t st, const FrMatLaunch& c) {
+  const uint8_t* img = (const uint8_t*)c.image;
+  FrMatArgs a{};
+  a.row_off = (const uint32_t*)(img + c.at.row_off), a.ent = (const uint2*)(img + c.at.ent);
+  a.dict = (const uint32_t*)(img + c.at.dict), a.segs = (const uint4*)(img + c.at.segs);
+  a.splits = (const uint4*)(img + c.at.splits);
+  a.x = (const uint32_t*)c.x, a.y = (uint32_t*)c.y, a.partial = (uint32_t*)c.work;
+  a.n_rows = c.n_rows, a.long_rows = c.long_rows, a.layout = c.layout;
+  const dim3 lane_grid((uint32_t)((c.n_rows + kFrMapThreads - 1) / kFrMapThreads)), wave_grid((uint32_t)c.plan.segments);
+  if (c.signs) hipLaunchKernelGGL(fr_mat_lane_kernel<true>, lane_grid, dim3(kFrMapThreads), 0, st, a);
+  else hipLaunchKernelGGL(fr_mat_lane_kernel<false>, lane_grid, dim3(kFrMapThreads), 0, st, a);
+  if (c.plan.segments && c.signs) hipLaunchKernelGGL(fr_mat_wave_kernel<true>, wave_grid, dim3(kFrWave), 0, st, a);
+  else if (c.plan.segments) hipLaunchKernelGGL(fr_mat_wave_kernel<false>, wave_grid, dim3(kFrWave), 0, st, a);
+  if (c.plan.split_rows) hipLaunchKernelGGL(fr_mat_fold_kernel, dim3((uint32_t)c.plan.split_rows), dim3(kFrWave), 0, st, a);
+  return (uint32_t)c.plan.launches;
 }
 
 uint32_t launch_fr_inv_products(hipStream_t st, int layout, const void* in, uint64_t n, uint32_t tile_log, void* work_v) {

@@ -5,6 +5,7 @@
 
 #include <cstddef>
 
+#include "fr_mat.hip.h"
 #include "fr_vec.hip.h"
 
 namespace msm_amd {
@@ -64,6 +65,22 @@ inline const void* fr_inv_tail(const void* work, const FrInvPlan& p) {
 void launch_fr_inv_apply(hipStream_t st, int layout, const void* in, uint64_t n, uint32_t tile_log, const void* work,
                          const u256& t_inv, void* out);
 
+// y = M x (fr_mat.hip.h): the lane launch, the wave launch if the plan has a wave row, the fold launch if it has a
+// split row, in stream order; returns the number of launches
+struct FrMatLaunch {
+  const void* image;   // the device allocation of the matrix (FrMatImage)
+  FrMatImage at;
+  FrMatPlan plan;
+  uint64_t n_rows;
+  uint32_t long_rows;
+  int layout;          // of x and y
+  bool signs;          // the kernels that add and subtract entries of value 1 and r - 1 without a product
+  const void* x;       // n_cols records
+  void* y;             // n_rows records, disjoint from x
+  void* work;          // plan.partials raw records (may be null without a split row)
+};
+uint32_t launch_fr_matvec(hipStream_t st, const FrMatLaunch& c);
+
 // host_fr.hip.  Each check returns null or what is wrong, for msm_amd_last_error.
 bool fr_layout_known(int scalar_layout);   // MONT_LE and CANON_LE
 bool fr_mode_known(int mode);
@@ -82,5 +99,16 @@ const char* fr_poly_check(int scalar_layout, const void* z32, const void* in, ui
 const char* fr_lincomb_check(int scalar_layout, const void* k32, const void* a, uint64_t n, uint64_t n_vec, const void* out,
                              bool device);
 const char* fr_unary_check(int scalar_layout, const void* in, uint64_t n, uint64_t n_vec, const void* out, bool device);
+// a CSR matrix in host memory (msm_amd_fr_matrix_build, msm_amd_host_fr_matvec): sizes, row_ptr and EVERY column
+const char* fr_matrix_check(int scalar_layout, uint64_t n_rows, uint64_t n_cols, const uint64_t* row_ptr,
+                            const uint32_t* col_idx, const void* values);
+// x (n_cols records) and y (n_rows records) of a product: out of place only, no overlap of any kind
+const char* fr_matvec_check(int scalar_layout, uint64_t n_rows, uint64_t n_cols, const void* x, const void* y, bool device);
+// The device image of a checked matrix in host memory: values reduced mod r and deduplicated into the dictionary (ids 0
+// and 1 are always 1 and r - 1, whether they occur or not: dict_records counts them, n_distinct only what occurs), the
+// plan at (long_rows, seg_log), every part at its place of fr_mat_image
+void fr_mat_build_image(int scalar_layout, uint64_t n_rows, const uint64_t* row_ptr, const uint32_t* col_idx,
+                        const void* values, uint32_t long_rows, uint32_t seg_log, FrMatPlan* plan, FrMatImage* at,
+                        uint64_t* n_distinct, uint64_t* dict_records, std::vector<uint8_t>* image);
 
 }  // namespace msm_amd

@@ -175,7 +175,7 @@ struct Batch {
   bool abandoned = false;   // a blocking entry point gave up waiting for it (wait timeout): released once the device is idle
 };
 
-// What the three handle kinds share: one device allocation.  Handles are validated by membership in the live list of
+// What the handle kinds share: one device allocation.  Handles are validated by membership in the live list of
 // their kind (find_handle), never by dereferencing the caller's pointer; each kind is a type and a live list of its own,
 // so that a G1 table handle is no G2 table handle, neither is a transform domain, and the reverse.
 struct DeviceHandle {
@@ -199,6 +199,15 @@ struct msm_amd_ntt_domain : DeviceHandle {
   u256 omega{};
 };
 
+// A sparse matrix over Fr (msm_amd_fr_matrix_*, msm_amd_ctx::live_fr_mat): d_mem is the image of fr_mat_image, planned at
+// the ctx's (fr_mat_long, fr_mat_seg_log) of the build.
+struct msm_amd_fr_matrix : DeviceHandle {
+  uint64_t n_rows = 0, n_cols = 0, nnz = 0, n_distinct = 0;
+  uint32_t long_rows = 0;
+  FrMatPlan plan{};
+  FrMatImage at{};
+};
+
 // Buffers of the blocking vector calls (device_call below): the staging of the host-buffer forms, the 64-byte record a
 // call reads back with its page-locked copy (the PointCounters of a check, decompress or compress call; T and the zero
 // count of a batch inversion), the device-side work buffers and two pairs of events behind kernel_ms.  Every such call
@@ -209,7 +218,8 @@ struct CallState {
   DeviceBuf record;                // PointCounters
   DeviceBuf table, xyzz;           // mul_points: the fixed-base table, the XYZZ records of one chunk of outputs
   DeviceBuf scratch, pow;          // transform: the ONE batch-sized scratch of a plan with more than one pass, the powers of a shift
-  DeviceBuf work;                  // Fr scan and inversion: the tile totals (fr_scan_plan, fr_inv_plan)
+  DeviceBuf work;                  // Fr scan and inversion: the tile totals (fr_scan_plan, fr_inv_plan); the partial sums of
+                                   // the split rows of a sparse product (fr_mat_plan)
   uint8_t* h_record = nullptr;     // pinned, 64 bytes
   uint8_t* h_values = nullptr;     // pinned: the values a call reads back beside its output (p_v(z) of the polynomial calls)
   size_t h_values_cap = 0;
@@ -277,7 +287,11 @@ struct msm_amd_ctx {
   std::vector<msm_amd_tables*> live_tables;
   std::vector<msm_amd_g2_tables*> live_g2_tables;
   std::vector<msm_amd_ntt_domain*> live_ntt;
+  std::vector<msm_amd_fr_matrix*> live_fr_mat;
   uint32_t fr_tile_log = kFrTileLog;     // records per tile of a scan, as a power of two (MSM_AMD_FR_TILE_LOG)
+  uint32_t fr_mat_long = kFrMatLong;     // rows of a sparse matrix above this many entries take the wave path (MSM_AMD_FR_MAT_LONG)
+  bool fr_mat_signs = false;             // the product kernels that skip the product for values 1 and r - 1 (MSM_AMD_FR_MAT_SIGNS)
+  uint32_t fr_mat_seg_log = kFrMatSegLog;   // entries per wave of that path, as a power of two (MSM_AMD_FR_MAT_SEG_LOG)
   uint32_t ntt_tile_log = kNttTileLog;   // elements per workgroup of a transform pass, as a power of two (MSM_AMD_NTT_TILE_LOG)
   int next_ws = 0;
   DeviceBuf scratch_a, scratch_b, scratch_c, scratch_b2, scratch_c2;
@@ -852,8 +866,8 @@ int reduce_buffers(msm_amd_ctx* ctx, Workspace& w, const Plan& p, size_t interna
   return ensure(ctx, w.partial, p.partial_count * ext_bytes);
 }
 
-// ---- handles: H = msm_amd_tables (ctx->live_tables), msm_amd_g2_tables (ctx->live_g2_tables) or msm_amd_ntt_domain
-// (ctx->live_ntt).  ctx->mu is held by the caller, as for every helper here.
+// ---- handles: H = msm_amd_tables (ctx->live_tables), msm_amd_g2_tables (ctx->live_g2_tables), msm_amd_ntt_domain
+// (ctx->live_ntt) or msm_amd_fr_matrix (ctx->live_fr_mat).  ctx->mu is held by the caller, as for every helper here.
 template <class H>
 const H* find_handle(const std::vector<H*>& live, const void* handle) {
   for (const H* t : live)
@@ -2125,6 +2139,11 @@ int msm_amd_init(int device, msm_amd_ctx** out) {
     ctx->ntt_tile_log = (uint32_t)std::max(2, std::min((int)kNttTileLog, std::atoi(e)));
   if (const char* e = std::getenv("MSM_AMD_FR_TILE_LOG"))
     ctx->fr_tile_log = (uint32_t)std::max((int)kFrMinTileLog, std::min((int)kFrTileLog, std::atoi(e)));
+  if (const char* e = std::getenv("MSM_AMD_FR_MAT_LONG"))
+    ctx->fr_mat_long = (uint32_t)std::max((int)kFrMatMinLong, std::min((int)kFrMatMaxLong, std::atoi(e)));
+  if (const char* e = std::getenv("MSM_AMD_FR_MAT_SIGNS")) ctx->fr_mat_signs = std::atoi(e) != 0;
+  if (const char* e = std::getenv("MSM_AMD_FR_MAT_SEG_LOG"))
+    ctx->fr_mat_seg_log = (uint32_t)std::max((int)kFrMatMinSegLog, std::min((int)kFrMatMaxSegLog, std::atoi(e)));
   if (const char* e = std::getenv("MSM_AMD_BASES_CACHE_VERIFY")) ctx->bases_cache_verify = std::strcmp(e, "full") == 0;
   if (const char* e = std::getenv("MSM_AMD_BASES_CACHE_MB")) {
     ctx->bases_cache_budget = (size_t)std::strtoull(e, nullptr, 10) << 20;
@@ -2256,6 +2275,7 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
   handle_release_all(ctx->live_tables);   // handles the caller did not free
   handle_release_all(ctx->live_g2_tables);
   handle_release_all(ctx->live_ntt);
+  handle_release_all(ctx->live_fr_mat);
   for (DeviceBuf* b : {&ctx->scratch_a, &ctx->scratch_b, &ctx->scratch_c, &ctx->scratch_b2, &ctx->scratch_c2}) kill_buf(*b);
   bases_cache_clear(ctx);   // (entries and unused reserves go through the graveyard)
   for (const msm_amd_ctx::CacheReserve& r : ctx->cache_reserve) ctx->graveyard.push_back(r.d);
@@ -4467,6 +4487,111 @@ int msm_amd_fr_prefix_product(msm_amd_ctx* ctx, int scalar_layout, int mode, con
 int msm_amd_fr_prefix_product_device(msm_amd_ctx* ctx, int scalar_layout, int mode, const void* d_in, size_t n, size_t n_vec,
                                      void* d_out, float* kernel_ms) {
   return fr_prefix_call(ctx, false, scalar_layout, mode, d_in, n, n_vec, d_out, kernel_ms);
+}
+
+}  // extern "C"
+
+// ---- sparse matrix times vector over Fr (msm_amd_fr_matrix_*, msm_amd_fr_matvec*) ------------------------------------------
+// The build checks every column on the host before anything is uploaded, so that no index of the image can leave x, the
+// dictionary or the partials.  A product is a device_call: x through the staging in the host form, the partial sums of the
+// split rows in CallState::work, the launches of launch_fr_matvec on the main stream.
+namespace {
+
+int fr_matvec_call(msm_amd_ctx* ctx, const msm_amd_fr_matrix* handle, bool host, int scalar_layout, const void* x, void* y,
+                   float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_matvec" : "msm_amd_fr_matvec_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_fr_matrix* m = find_handle(ctx->live_fr_mat, handle);
+  if (!m) return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": not a matrix handle of this ctx");
+  if (const char* why = fr_matvec_check(scalar_layout, m->n_rows, m->n_cols, x, y, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (!host) {
+    const uintptr_t lo = (uintptr_t)m->d_mem, hi = lo + m->bytes, a = (uintptr_t)x, b = (uintptr_t)y;
+    if ((a < hi && lo < a + m->n_cols * 32) || (b < hi && lo < b + m->n_rows * 32))
+      return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": d_x and d_y must not overlap the matrix");
+  }
+  CallState& s = ctx->calls;
+  FrMatLaunch c{};
+  c.image = m->d_mem, c.at = m->at, c.plan = m->plan, c.n_rows = m->n_rows, c.long_rows = m->long_rows, c.layout = scalar_layout;
+  c.signs = ctx->fr_mat_signs;
+  d.host = host, d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = x, d.in_bytes[0] = m->n_cols * 32;
+  d.out = y, d.out_bytes = m->n_rows * 32;
+  d.work[0] = {&s.work, std::max<size_t>(32, m->plan.partials * 32)};
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    c.x = io.in[0], c.y = io.out, c.work = s.work.p;
+    launch_fr_matvec(st, c);
+    return MSM_AMD_OK;
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_fr_matrix_build(msm_amd_ctx* ctx, int scalar_layout, size_t n_rows, size_t n_cols, const uint64_t* row_ptr,
+                            const uint32_t* col_idx, const void* values, msm_amd_fr_matrix** out) {
+  if (!ctx || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_fr_matrix_build: null pointer");
+  *out = nullptr;
+  if (const char* why = fr_matrix_check(scalar_layout, n_rows, n_cols, row_ptr, col_idx, values))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, std::string("msm_amd_fr_matrix_build: ") + why);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = recover_if_stalled(ctx)) return rc;
+  FrMatPlan plan;
+  FrMatImage at;
+  uint64_t n_distinct = 0, dict_records = 0;
+  std::vector<uint8_t> image;
+  fr_mat_build_image(scalar_layout, n_rows, row_ptr, col_idx, values, ctx->fr_mat_long, ctx->fr_mat_seg_log, &plan, &at,
+                     &n_distinct, &dict_records, &image);
+  int up = MSM_AMD_OK;
+  if (int rc = handle_build_tail(ctx, ctx->live_fr_mat, at.bytes, "a sparse matrix", "matrix build",
+                                 [&](void* d_mem) { up = staged_upload(ctx, d_mem, image.data(), image.size(), ctx->stream); },
+                                 out))
+    return rc;
+  if (up) {   // the upload did not go through: nothing may read the allocation
+    msm_amd_fr_matrix* h = *out;
+    *out = nullptr;
+    const std::string why = ctx->last_error;
+    handle_free(ctx, ctx->live_fr_mat, h, "");
+    return fail(ctx, up, "msm_amd_fr_matrix_build: " + why);
+  }
+  msm_amd_fr_matrix* h = *out;
+  h->n_rows = n_rows, h->n_cols = n_cols, h->nnz = row_ptr[n_rows], h->n_distinct = n_distinct;
+  h->long_rows = ctx->fr_mat_long, h->plan = plan, h->at = at;
+  return MSM_AMD_OK;
+}
+
+int msm_amd_fr_matrix_info(msm_amd_ctx* ctx, const msm_amd_fr_matrix* matrix, size_t* n_rows, size_t* n_cols, size_t* nnz,
+                           size_t* n_distinct, size_t* device_bytes) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_fr_matrix* m = find_handle(ctx->live_fr_mat, matrix);
+  if (!m) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_fr_matrix_info: not a matrix handle of this ctx");
+  if (n_rows) *n_rows = m->n_rows;
+  if (n_cols) *n_cols = m->n_cols;
+  if (nnz) *nnz = m->nnz;
+  if (n_distinct) *n_distinct = m->n_distinct;
+  if (device_bytes) *device_bytes = m->bytes;
+  return MSM_AMD_OK;
+}
+
+int msm_amd_fr_matrix_free(msm_amd_ctx* ctx, msm_amd_fr_matrix* matrix) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return handle_free(ctx, ctx->live_fr_mat, matrix, "msm_amd_fr_matrix_free: not a matrix handle of this ctx");
+}
+
+int msm_amd_fr_matvec(msm_amd_ctx* ctx, const msm_amd_fr_matrix* matrix, int scalar_layout, const void* x, void* y) {
+  return fr_matvec_call(ctx, matrix, true, scalar_layout, x, y, nullptr);
+}
+
+int msm_amd_fr_matvec_device(msm_amd_ctx* ctx, const msm_amd_fr_matrix* matrix, int scalar_layout, const void* d_x, void* d_y,
+                             float* kernel_ms) {
+  return fr_matvec_call(ctx, matrix, false, scalar_layout, d_x, d_y, kernel_ms);
 }
 
 }  // extern "C"
