@@ -1086,6 +1086,80 @@ int msm_amd_host_fr_matvec(int scalar_layout, size_t n_rows, size_t n_cols, cons
 int msm_amd_test_fr_matrix_plan(size_t n_rows, const uint64_t* row_ptr, uint32_t long_rows, uint32_t seg_log,
                                 uint64_t counts[8], uint32_t* segs, size_t segs_cap);
 
+/* ---- multilinear tables over Fr and the rounds of a sumcheck ---------------------------------------------------
+ * Spartan, HyperPlonk, Nova / HyperNova and GKR-style provers spend their time between the MSMs in the sumcheck protocol
+ * over multilinear tables: each round sums a low-degree combination of a few tables, takes a challenge and halves every
+ * table.  These calls do that on the device, where msm_amd_fr_matvec_device leaves A z, B z, C z.
+ * A table is n = 2^m records f[i], the value at x = (x_0 .. x_(m-1)) with x_j = bit j of i.  Records, layouts
+ * (MSM_AMD_SCALAR_MONT_LE, _CANON_LE; _CANON_BE32: MSM_AMD_INPUT_ERROR), "any 256-bit word is taken mod r", fully reduced
+ * outputs (unique bytes), 16-byte alignment of device pointers, the bounded waits and msm_amd_last_error are those of
+ * msm_amd_fr_prefix_product*.  n_vec tables lie `stride` records apart (stride >= n, n_vec stride < 2^32).  Challenges and
+ * points are records in HOST memory in the call's layout, for every form of every call; y_out and g_out are HOST memory too
+ * and come back through ctx-owned page-locked memory in the call's one bounded wait.
+ * Two orders, because both are in use:
+ *   MSM_AMD_MLE_LOW   step s binds x_s:        f'[i] = f[2i] + r (f[2i+1] - f[2i]), i < n/2  (arkworks
+ *                     DenseMultilinearExtension::fix_variables)
+ *   MSM_AMD_MLE_HIGH  step s binds x_(m-1-s):  f'[i] = f[i] + r (f[i + n/2] - f[i])           (Spartan / Nova
+ *                     bound_poly_var_top)
+ * Sizes and errors: n a power of two, 2 <= n < 2^32.  n_vec == 0: MSM_AMD_OK, nothing is touched.  MSM_AMD_INPUT_ERROR: n
+ * not a power of two or < 2; n_bind == 0 or > m; stride < n; n_vec stride >= 2^32; an unknown order, form or layout; n_vec
+ * outside a form's range; a null pointer the call reads or writes; misaligned device pointers; the overlap rules of
+ * msm_amd_fr_mle_bind*.  The host twins msm_amd_host_fr_* (no ctx, no GPU; the same bodies compiled for the host) make
+ * the same checks; threads <= 0: up to 16 host threads; no byte depends on the thread count.
+ * (Development knob at msm_amd_init: MSM_AMD_FR_MLE_CHUNK_LOG = 6 .. 20, the pairs per wave of a round as a power of two,
+ * default 8 (measured: profiles/mle_ab.txt); the evaluation runs on the tiles of MSM_AMD_FR_TILE_LOG.  No byte of a result
+ * depends on either.) */
+enum { MSM_AMD_MLE_LOW = 0, MSM_AMD_MLE_HIGH = 1 };
+enum { MSM_AMD_SUMCHECK_PRODUCT = 0,   /* F = prod_j f_j, n_vec 1 .. 4, d = n_vec */
+       MSM_AMD_SUMCHECK_EQ_AB_C = 1    /* n_vec = 4, tables eq, a, b, c: F = eq (a b - c), d = 3 */ };
+/* n_bind steps (1 <= n_bind <= m) with r[0], r[1], .. on each table.  The first n >> n_bind records of output table v (at
+ * out + 32 v stride) are the result; the call may also write the rest of that table's first n/2 records (unspecified
+ * content) and writes no other byte of out.  out == in is allowed with MSM_AMD_MLE_HIGH; otherwise out must be disjoint
+ * from the whole input span of (n_vec - 1) stride + n records: MSM_AMD_MLE_LOW is out of place only, a partial overlap is
+ * MSM_AMD_INPUT_ERROR.  An out-of-place call leaves `in` unchanged.  One launch folds up to three variables; LOW with more
+ * than one launch uses ctx-owned memory of n_vec n / 8 records. */
+int msm_amd_fr_mle_bind(msm_amd_ctx* ctx, int scalar_layout, int order, const void* r /* n_bind records */, size_t n_bind,
+                        const void* in, size_t n, size_t n_vec, size_t stride, void* out);
+int msm_amd_fr_mle_bind_device(msm_amd_ctx* ctx, int scalar_layout, int order, const void* r /* HOST memory */, size_t n_bind,
+                               const void* d_in, size_t n, size_t n_vec, size_t stride, void* d_out, float* kernel_ms);
+int msm_amd_host_fr_mle_bind(int scalar_layout, int order, const void* r, size_t n_bind, const void* in, size_t n, size_t n_vec,
+                             size_t stride, int threads, void* out);
+/* y[v] = the one record left of table v after m steps at point[0 .. m-1]; `in` is never written.  HIGH at a point equals
+ * LOW at the reversed point. */
+int msm_amd_fr_mle_eval(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point /* m records */, const void* in,
+                        size_t n, size_t n_vec, size_t stride, void* y_out /* n_vec records */);
+int msm_amd_fr_mle_eval_device(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point /* HOST memory */,
+                               const void* d_in, size_t n, size_t n_vec, size_t stride, void* y_out /* HOST memory */,
+                               float* kernel_ms);
+int msm_amd_host_fr_mle_eval(int scalar_layout, int order, const void* point, const void* in, size_t n, size_t n_vec,
+                             size_t stride, int threads, void* y_out);
+/* out[i] = prod_s (bit v(s) of i ? point[s] : 1 - point[s]), i < 2^m, with v(s) = s for LOW and m - 1 - s for HIGH;
+ * 1 <= m <= 31.  eval(f, order, point) = sum_i out[i] f[i]. */
+int msm_amd_fr_eq_table(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point /* m records */, size_t m, void* out);
+int msm_amd_fr_eq_table_device(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point /* HOST memory */, size_t m,
+                               void* d_out /* 2^m records */, float* kernel_ms);
+int msm_amd_host_fr_eq_table(int scalar_layout, int order, const void* point, size_t m, int threads, void* out);
+/* One round's polynomial.  With h = n/2 and (lo_j(x), hi_j(x)) the two records of table j that the next step of `order`
+ * would combine at output index x (LOW: 2x, 2x + 1; HIGH: x, x + h), f_j(t, x) = lo_j + t (hi_j - lo_j) and
+ *   g_out[t] = sum_(x < h) F(f_0(t, x), ..),  t = 0 .. d, t an integer mod r.
+ * All d + 1 values come back, g(1) included, so that a caller can check g(0) + g(1) against its claim.  `in` is never
+ * written.  PRODUCT with one table is the sum of a table, with two an inner product (Spartan's second sumcheck); EQ_AB_C
+ * is Spartan's first sumcheck, the R1CS zero check. */
+int msm_amd_fr_sumcheck_round(msm_amd_ctx* ctx, int scalar_layout, int order, int form, const void* in, size_t n, size_t n_vec,
+                              size_t stride, void* g_out /* d + 1 records */);
+int msm_amd_fr_sumcheck_round_device(msm_amd_ctx* ctx, int scalar_layout, int order, int form, const void* d_in, size_t n,
+                                     size_t n_vec, size_t stride, void* g_out /* HOST memory */, float* kernel_ms);
+int msm_amd_host_fr_sumcheck_round(int scalar_layout, int order, int form, const void* in, size_t n, size_t n_vec, size_t stride,
+                                   int threads, void* g_out);
+/* Test aid (no ctx, CPU only): the plan of one of these calls at chunk_log (6 .. 20) and tile_log (2 .. 9).  For the eq
+ * table n is m; the plan of a bind or an eval takes the tables at stride n.  counts: [0] launches, [1] dispatched waves,
+ * [2] records of ctx-owned device memory, [3] the same in bytes, [4] levels (round: 1 + fold launches; eval: launches),
+ * [5] waves of the first launch of a round or an eval, [6] records the call defines (round: d + 1), [7] 0.
+ * msm_amd_test_fill_workspaces poisons the partial records and the levels of these calls too. */
+enum { MSM_AMD_MLE_CALL_BIND = 0, MSM_AMD_MLE_CALL_EVAL = 1, MSM_AMD_MLE_CALL_EQ_TABLE = 2, MSM_AMD_MLE_CALL_ROUND = 3 };
+int msm_amd_test_fr_mle_plan(int call, int order, int form, size_t n, size_t n_vec, uint32_t n_bind, uint32_t chunk_log,
+                             uint32_t tile_log, uint64_t counts[8]);
+
 /* Test aid (no ctx): the plan of a scan over n_vec vectors of n at a tile of 2^tile_log (2 .. 9): out[0] levels, out[1]
  * launches (2 levels - 1), out[2] tiles of the first level over all vectors, out[3] records of ctx-owned device memory */
 int msm_amd_test_fr_plan(size_t n, size_t n_vec, uint32_t tile_log, uint64_t out[4]);

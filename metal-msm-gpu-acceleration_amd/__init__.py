@@ -56,6 +56,9 @@ NTT_FORWARD, NTT_INVERSE = 0, 1
 # vectors over Fr (MSM_AMD_FR_*)
 FR_ADD, FR_SUB, FR_MUL, FR_SCALE, FR_AXPY, FR_MULSUB_SCALE = range(6)
 FR_PREFIX_INCLUSIVE, FR_PREFIX_EXCLUSIVE = 0, 1
+MLE_LOW, MLE_HIGH = 0, 1
+SUMCHECK_PRODUCT, SUMCHECK_EQ_AB_C = 0, 1
+MLE_CALL_BIND, MLE_CALL_EVAL, MLE_CALL_EQ_TABLE, MLE_CALL_ROUND = range(4)
 
 
 def op_is_point(op):
@@ -118,6 +121,11 @@ EXPORTS = [
     "msm_amd_fr_lincomb", "msm_amd_fr_lincomb_device", "msm_amd_host_fr_lincomb",
     "msm_amd_fr_matrix_build", "msm_amd_fr_matrix_info", "msm_amd_fr_matrix_free", "msm_amd_fr_matvec",
     "msm_amd_fr_matvec_device", "msm_amd_host_fr_matvec", "msm_amd_test_fr_matrix_plan",
+    "msm_amd_fr_mle_bind", "msm_amd_fr_mle_bind_device", "msm_amd_host_fr_mle_bind",
+    "msm_amd_fr_mle_eval", "msm_amd_fr_mle_eval_device", "msm_amd_host_fr_mle_eval",
+    "msm_amd_fr_eq_table", "msm_amd_fr_eq_table_device", "msm_amd_host_fr_eq_table",
+    "msm_amd_fr_sumcheck_round", "msm_amd_fr_sumcheck_round_device", "msm_amd_host_fr_sumcheck_round",
+    "msm_amd_test_fr_mle_plan",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -391,6 +399,24 @@ def _lib():
                                              c_void_p]
         L.msm_amd_test_fr_matrix_plan.argtypes = [c_size_t, c_void_p, c_uint32, c_uint32, POINTER(c_uint64), c_void_p,
                                                   c_size_t]
+        L.msm_amd_fr_mle_bind.argtypes = [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_size_t,
+                                          c_void_p]
+        L.msm_amd_fr_mle_bind_device.argtypes = L.msm_amd_fr_mle_bind.argtypes + [POINTER(c_float)]
+        L.msm_amd_host_fr_mle_bind.argtypes = [c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_size_t, c_int,
+                                               c_void_p]
+        L.msm_amd_fr_mle_eval.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_void_p]
+        L.msm_amd_fr_mle_eval_device.argtypes = L.msm_amd_fr_mle_eval.argtypes + [POINTER(c_float)]
+        L.msm_amd_host_fr_mle_eval.argtypes = [c_int, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t, c_int, c_void_p]
+        L.msm_amd_fr_eq_table.argtypes = [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]
+        L.msm_amd_fr_eq_table_device.argtypes = L.msm_amd_fr_eq_table.argtypes + [POINTER(c_float)]
+        L.msm_amd_host_fr_eq_table.argtypes = [c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]
+        L.msm_amd_fr_sumcheck_round.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_size_t, c_size_t,
+                                                c_void_p]
+        L.msm_amd_fr_sumcheck_round_device.argtypes = L.msm_amd_fr_sumcheck_round.argtypes + [POINTER(c_float)]
+        L.msm_amd_host_fr_sumcheck_round.argtypes = [c_int, c_int, c_int, c_void_p, c_size_t, c_size_t, c_size_t, c_int,
+                                                     c_void_p]
+        L.msm_amd_test_fr_mle_plan.argtypes = [c_int, c_int, c_int, c_size_t, c_size_t, c_uint32, c_uint32, c_uint32,
+                                               POINTER(c_uint64)]
         L.msm_amd_generate_instance_host.argtypes = [c_uint64, c_size_t, c_int, c_void_p, c_void_p, c_int]
         L.msm_amd_test_op_ifma.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_tuned_split.argtypes = [c_size_t]
@@ -1012,6 +1038,78 @@ class MsmConfig:
                                                     c_void_p(d_y), ctypes.byref(ms)))
         return ms.value
 
+    # ---- multilinear tables over Fr and sumcheck rounds: n_vec tables of n = 2^m records, `stride` records apart ----
+    def fr_mle_bind(self, data: bytes, r: bytes, n: int, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, n_vec=1, stride=None,
+                    out: bytes = None) -> bytes:
+        """len(r) / 32 steps of `order` on host tables (msm_amd_fr_mle_bind): the output span of (n_vec - 1) stride + n / 2
+        records, or all of `out` if given: the call writes over a copy of it, so that what it leaves alone shows."""
+        stride = n if stride is None else stride
+        span = 32 * ((n_vec - 1) * stride + n // 2) if n_vec else 0
+        size = len(out) if out is not None else span
+        buf = ctypes.create_string_buffer(out if out is not None else b"\xFF" * span, size + 1)
+        self._check(_lib().msm_amd_fr_mle_bind(self.h, scalar_layout, order, r, len(r) // 32 if r else 0, data, n, n_vec,
+                                               stride, buf))
+        return buf.raw[:size]
+
+    def fr_mle_bind_device(self, d_in, n: int, d_out, r: bytes, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, n_vec=1,
+                           stride=None, n_bind=None) -> float:
+        """The same on device-resident tables, d_out == d_in with MLE_HIGH or disjoint (msm_amd_fr_mle_bind_device);
+        returns kernel_ms."""
+        ms = c_float(0)
+        n_bind = (len(r) // 32 if r else 0) if n_bind is None else n_bind
+        self._check(_lib().msm_amd_fr_mle_bind_device(self.h, scalar_layout, order, r, n_bind, c_void_p(d_in), n, n_vec,
+                                                      n if stride is None else stride, c_void_p(d_out), ctypes.byref(ms)))
+        return ms.value
+
+    def fr_mle_eval(self, data: bytes, point: bytes, n: int, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, n_vec=1,
+                    stride=None) -> bytes:
+        """The n_vec records f_v(point) of host tables (msm_amd_fr_mle_eval); point: log2 n records in scalar_layout"""
+        y = ctypes.create_string_buffer(max(1, 32 * n_vec))
+        self._check(_lib().msm_amd_fr_mle_eval(self.h, scalar_layout, order, point, data, n, n_vec,
+                                               n if stride is None else stride, y))
+        return y.raw[:32 * n_vec]
+
+    def fr_mle_eval_device(self, d_in, n: int, point: bytes, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, n_vec=1,
+                           stride=None):
+        """The same on device-resident tables (msm_amd_fr_mle_eval_device); returns (records, kernel_ms)."""
+        ms = c_float(0)
+        y = ctypes.create_string_buffer(max(1, 32 * n_vec))
+        self._check(_lib().msm_amd_fr_mle_eval_device(self.h, scalar_layout, order, point, c_void_p(d_in), n, n_vec,
+                                                      n if stride is None else stride, y, ctypes.byref(ms)))
+        return y.raw[:32 * n_vec], ms.value
+
+    def fr_eq_table(self, point: bytes, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, m=None) -> bytes:
+        """The 2^m records eq(point, .) in host memory (msm_amd_fr_eq_table)"""
+        m = (len(point) // 32 if point else 0) if m is None else m
+        out = ctypes.create_string_buffer(max(1, 32 << m if 0 < m < 32 else 1))
+        self._check(_lib().msm_amd_fr_eq_table(self.h, scalar_layout, order, point, m, out))
+        return out.raw[:32 << m]
+
+    def fr_eq_table_device(self, d_out, point: bytes, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, m=None) -> float:
+        """The same into device memory of 2^m records (msm_amd_fr_eq_table_device); returns kernel_ms."""
+        ms = c_float(0)
+        m = (len(point) // 32 if point else 0) if m is None else m
+        self._check(_lib().msm_amd_fr_eq_table_device(self.h, scalar_layout, order, point, m, c_void_p(d_out),
+                                                      ctypes.byref(ms)))
+        return ms.value
+
+    def fr_sumcheck_round(self, data: bytes, n: int, form=SUMCHECK_PRODUCT, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE,
+                          n_vec=1, stride=None) -> bytes:
+        """The d + 1 records g(0) .. g(d) of one round over host tables (msm_amd_fr_sumcheck_round)"""
+        g = ctypes.create_string_buffer(32 * 5)
+        self._check(_lib().msm_amd_fr_sumcheck_round(self.h, scalar_layout, order, form, data, n, n_vec,
+                                                     n if stride is None else stride, g))
+        return g.raw[:32 * sumcheck_values(form, n_vec)]
+
+    def fr_sumcheck_round_device(self, d_in, n: int, form=SUMCHECK_PRODUCT, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE,
+                                 n_vec=1, stride=None):
+        """The same on device-resident tables (msm_amd_fr_sumcheck_round_device); returns (records, kernel_ms)."""
+        ms = c_float(0)
+        g = ctypes.create_string_buffer(32 * 5)
+        self._check(_lib().msm_amd_fr_sumcheck_round_device(self.h, scalar_layout, order, form, c_void_p(d_in), n, n_vec,
+                                                            n if stride is None else stride, g, ctypes.byref(ms)))
+        return g.raw[:32 * sumcheck_values(form, n_vec)], ms.value
+
     def test_op_g2(self, op, a, b, count):
         """Raw-limb G2 op (MSM_AMD_G2_RAW_*) on the device: a, b flat u32 lists of count * G2_RAW_IN_WORDS; returns
         count * G2_RAW_OUT_WORDS u32."""
@@ -1454,6 +1552,65 @@ def host_fr_lincomb(data: bytes, k: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1
     if st != OK:
         raise MsmError(st)
     return out.raw[:32 * n]
+
+
+def sumcheck_values(form, n_vec) -> int:
+    """d + 1 of a round: the records msm_amd_fr_sumcheck_round* return (0 when there is nothing to do)"""
+    return 0 if n_vec == 0 else 4 if form == SUMCHECK_EQ_AB_C else n_vec + 1
+
+
+def host_fr_mle_bind(data: bytes, r: bytes, n: int, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, n_vec=1, stride=None,
+                     threads=0, out: bytes = None) -> bytes:
+    """Host twin of MsmConfig.fr_mle_bind (no GPU)."""
+    stride = n if stride is None else stride
+    span = 32 * ((n_vec - 1) * stride + n // 2) if n_vec else 0
+    size = len(out) if out is not None else span
+    buf = ctypes.create_string_buffer(out if out is not None else b"\xFF" * span, size + 1)
+    st = _lib().msm_amd_host_fr_mle_bind(scalar_layout, order, r, len(r) // 32 if r else 0, data, n, n_vec, stride, threads, buf)
+    if st != OK:
+        raise MsmError(st)
+    return buf.raw[:size]
+
+
+def host_fr_mle_eval(data: bytes, point: bytes, n: int, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, n_vec=1, stride=None,
+                     threads=0) -> bytes:
+    """Host twin of MsmConfig.fr_mle_eval (no GPU)."""
+    y = ctypes.create_string_buffer(max(1, 32 * n_vec))
+    st = _lib().msm_amd_host_fr_mle_eval(scalar_layout, order, point, data, n, n_vec, n if stride is None else stride,
+                                         threads, y)
+    if st != OK:
+        raise MsmError(st)
+    return y.raw[:32 * n_vec]
+
+
+def host_fr_eq_table(point: bytes, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, threads=0, m=None) -> bytes:
+    """Host twin of MsmConfig.fr_eq_table (no GPU)."""
+    m = (len(point) // 32 if point else 0) if m is None else m
+    out = ctypes.create_string_buffer(max(1, 32 << m if 0 < m < 32 else 1))
+    st = _lib().msm_amd_host_fr_eq_table(scalar_layout, order, point, m, threads, out)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:32 << m]
+
+
+def host_fr_sumcheck_round(data: bytes, n: int, form=SUMCHECK_PRODUCT, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, n_vec=1,
+                           stride=None, threads=0) -> bytes:
+    """Host twin of MsmConfig.fr_sumcheck_round (no GPU)."""
+    g = ctypes.create_string_buffer(32 * 5)
+    st = _lib().msm_amd_host_fr_sumcheck_round(scalar_layout, order, form, data, n, n_vec, n if stride is None else stride,
+                                               threads, g)
+    if st != OK:
+        raise MsmError(st)
+    return g.raw[:32 * sumcheck_values(form, n_vec)]
+
+
+def test_fr_mle_plan(call, n, n_vec=1, order=MLE_LOW, form=SUMCHECK_PRODUCT, n_bind=1, chunk_log=8, tile_log=9) -> dict:
+    """The plan of a multilinear call (msm_amd_test_fr_mle_plan); call: MLE_CALL_*; for the eq table n is m."""
+    out = (c_uint64 * 8)()
+    st = _lib().msm_amd_test_fr_mle_plan(call, order, form, n, n_vec, n_bind, chunk_log, tile_log, out)
+    if st != OK:
+        raise MsmError(st)
+    return dict(zip(("launches", "waves", "records", "bytes", "levels", "first_waves", "values"), out))
 
 
 def test_fr_plan(n, n_vec=1, tile_log=9) -> dict:

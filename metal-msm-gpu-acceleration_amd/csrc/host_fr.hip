@@ -2,7 +2,8 @@
 // records split over the host threads -- the map record by record, the inversion with one inversion per range (the
 // classic trick), the prefix products in two phases (the product of every range, then the ranges from their carries),
 // the polynomial calls likewise (a range's Horner value, then the ranges from the sums behind them), the sparse product
-// row by row over ranges of equal entry count;
+// row by row over ranges of equal entry count, the multilinear calls step by step over ranges of outputs (a round: the sums
+// of every range of pairs, added in range order);
 // and the argument checks the twins share with the host driver (msm_host.hip).  The bytes of a result are unique, so the
 // way a twin cuts the work shows nowhere.
 #include <hip/hip_runtime.h>
@@ -18,6 +19,8 @@ namespace msm_amd {
 
 static_assert(kFrAdd == MSM_AMD_FR_ADD && kFrSub == MSM_AMD_FR_SUB && kFrMul == MSM_AMD_FR_MUL &&
               kFrScale == MSM_AMD_FR_SCALE && kFrAxpy == MSM_AMD_FR_AXPY && kFrMulsubScale == MSM_AMD_FR_MULSUB_SCALE, "ops");
+static_assert(kFrMleLow == MSM_AMD_MLE_LOW && kFrMleHigh == MSM_AMD_MLE_HIGH && kFrSumProduct == MSM_AMD_SUMCHECK_PRODUCT &&
+              kFrSumEqAbC == MSM_AMD_SUMCHECK_EQ_AB_C, "orders and forms");
 static_assert(kFrInclusive == MSM_AMD_FR_PREFIX_INCLUSIVE && kFrExclusive == MSM_AMD_FR_PREFIX_EXCLUSIVE, "modes");
 
 bool fr_layout_known(int scalar_layout) { return ntt_layout_known(scalar_layout); }
@@ -117,6 +120,71 @@ const char* fr_matvec_check(int scalar_layout, uint64_t n_rows, uint64_t n_cols,
   if (device && (((uintptr_t)x | (uintptr_t)y) & 15u)) return "device buffers must be 16-byte aligned";
   const uintptr_t a = (uintptr_t)x, b = (uintptr_t)y;
   if (a < b + n_rows * 32 && b < a + n_cols * 32) return "y must not overlap x: the product is out of place only";
+  return nullptr;
+}
+
+namespace {
+const char* const kMleLayout = "scalars in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE only";
+const char* const kMleOrder = "order must be MSM_AMD_MLE_LOW or MSM_AMD_MLE_HIGH";
+const char* const kMleAlign = "device buffers must be 16-byte aligned";
+bool spans_apart(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x + a_bytes <= y || y + b_bytes <= x;
+}
+}  // namespace
+
+const char* fr_mle_tables_check(uint64_t n, uint64_t n_vec, uint64_t stride) {
+  if (n < 2 || (n >> 32) || (n & (n - 1))) return "n must be a power of two, 2 <= n < 2^32";
+  if (stride < n) return "stride < n";
+  if ((stride >> 32) || (n_vec >> 32) || ((n_vec * stride) >> 32)) return "n_vec * stride >= 2^32";
+  return nullptr;
+}
+
+const char* fr_mle_bind_check(int scalar_layout, int order, const void* r, uint64_t n_bind, const void* in, uint64_t n,
+                              uint64_t n_vec, uint64_t stride, const void* out, bool device) {
+  if (!fr_layout_known(scalar_layout)) return kMleLayout;
+  if (!fr_mle_order_known(order)) return kMleOrder;
+  if (n_vec == 0) return nullptr;
+  if (const char* why = fr_mle_tables_check(n, n_vec, stride)) return why;
+  if (n_bind == 0 || n_bind > fr_mle_log2(n)) return "n_bind must be 1 .. log2 n";
+  if (!r || !in || !out) return "null pointer with work to do";
+  if (device && (((uintptr_t)in | (uintptr_t)out) & 15u)) return kMleAlign;
+  if (out == in) return order == kFrMleHigh ? nullptr : "MSM_AMD_MLE_LOW is out of place only";
+  if (!spans_apart(in, ((n_vec - 1) * stride + n) * 32, out, ((n_vec - 1) * stride + n / 2) * 32))
+    return "the output must be the input itself (MSM_AMD_MLE_HIGH) or disjoint from all of it";
+  return nullptr;
+}
+
+const char* fr_mle_eval_check(int scalar_layout, int order, const void* point, const void* in, uint64_t n, uint64_t n_vec,
+                              uint64_t stride, const void* y_out, bool device) {
+  if (!fr_layout_known(scalar_layout)) return kMleLayout;
+  if (!fr_mle_order_known(order)) return kMleOrder;
+  if (n_vec == 0) return nullptr;
+  if (const char* why = fr_mle_tables_check(n, n_vec, stride)) return why;
+  if (!point || !in || !y_out) return "null pointer with work to do";
+  if (device && ((uintptr_t)in & 15u)) return kMleAlign;
+  return nullptr;
+}
+
+const char* fr_eq_table_check(int scalar_layout, int order, const void* point, uint64_t m, const void* out, bool device) {
+  if (!fr_layout_known(scalar_layout)) return kMleLayout;
+  if (!fr_mle_order_known(order)) return kMleOrder;
+  if (m < 1 || m > kFrMleMaxVars) return "m must be 1 .. 31";
+  if (!point || !out) return "null pointer";
+  if (device && ((uintptr_t)out & 15u)) return kMleAlign;
+  return nullptr;
+}
+
+const char* fr_sumcheck_check(int scalar_layout, int order, int form, const void* in, uint64_t n, uint64_t n_vec,
+                              uint64_t stride, const void* g_out, bool device) {
+  if (!fr_layout_known(scalar_layout)) return kMleLayout;
+  if (!fr_mle_order_known(order)) return kMleOrder;
+  if (form != kFrSumProduct && form != kFrSumEqAbC) return "form must be MSM_AMD_SUMCHECK_PRODUCT or MSM_AMD_SUMCHECK_EQ_AB_C";
+  if (n_vec == 0) return nullptr;
+  if (!fr_mle_degree(form, n_vec)) return "n_vec must be 1 .. 4 for MSM_AMD_SUMCHECK_PRODUCT and 4 for MSM_AMD_SUMCHECK_EQ_AB_C";
+  if (const char* why = fr_mle_tables_check(n, n_vec, stride)) return why;
+  if (!in || !g_out) return "null pointer with work to do";
+  if (device && ((uintptr_t)in & 15u)) return kMleAlign;
   return nullptr;
 }
 
@@ -410,10 +478,180 @@ int host_fr_matvec(int layout, uint64_t n_rows, uint64_t n_cols, const uint64_t*
   return MSM_AMD_OK;
 }
 
+// ---- multilinear tables (fr_mle.hip.h) -------------------------------------------------------------------------------------
+// a call's work is cut into ranges of at least 2^10 items, so that a short table starts no thread
+unsigned mle_workers(int threads, uint64_t items) { return worker_count(threads, (size_t)((items + 1023) >> 10)); }
+
+// n_bind steps of `order` on one table of n records: what is left, as Montgomery residues
+std::vector<u256> host_mle_fold(int layout, int order, const u256* r, uint32_t n_bind, const uint8_t* tab, uint64_t n, int threads) {
+  std::vector<u256> cur, nxt;
+  uint64_t len = n;
+  for (uint32_t s = 0; s < n_bind; ++s) {
+    const uint64_t h = len / 2;
+    nxt.resize(h);
+    for_ranges(mle_workers(threads, h), h, [&](unsigned, size_t lo, size_t hi) {
+      for (size_t i = lo; i < hi; ++i) {
+        const size_t a = order == kFrMleHigh ? i : 2 * i, b = order == kFrMleHigh ? i + h : 2 * i + 1;
+        nxt[i] = s == 0 ? fr_mle_fold(host_get(layout, tab, a), host_get(layout, tab, b), r[0]) : fr_mle_fold(cur[a], cur[b], r[s]);
+      }
+    });
+    cur.swap(nxt);
+    len = h;
+  }
+  return cur;
+}
+
+void host_read_records(int layout, const void* src, uint64_t count, u256* dst) {
+  for (uint64_t j = 0; j < count; ++j) dst[j] = fr_read_record(layout, (const uint8_t*)src + j * 32);
+}
+
+int host_fr_mle_bind(int layout, int order, const void* r32, size_t n_bind, const void* in_v, size_t n, size_t n_vec,
+                     size_t stride, int threads, void* out_v) {
+  if (fr_mle_bind_check(layout, order, r32, n_bind, in_v, n, n_vec, stride, out_v, false)) return MSM_AMD_INPUT_ERROR;
+  if (n_vec == 0) return MSM_AMD_OK;
+  u256 r[kFrMleMaxVars];
+  host_read_records(layout, r32, n_bind, r);
+  for (size_t v = 0; v < n_vec; ++v) {
+    const std::vector<u256> left = host_mle_fold(layout, order, r, (uint32_t)n_bind, (const uint8_t*)in_v + v * stride * 32, n, threads);
+    for (size_t i = 0; i < left.size(); ++i) host_put(layout, (uint8_t*)out_v + v * stride * 32, i, left[i]);
+  }
+  return MSM_AMD_OK;
+}
+
+int host_fr_mle_eval(int layout, int order, const void* point32, const void* in_v, size_t n, size_t n_vec, size_t stride,
+                     int threads, void* y_out) {
+  if (fr_mle_eval_check(layout, order, point32, in_v, n, n_vec, stride, y_out, false)) return MSM_AMD_INPUT_ERROR;
+  if (n_vec == 0) return MSM_AMD_OK;
+  const uint32_t m = fr_mle_log2(n);
+  u256 r[kFrMleMaxVars];
+  host_read_records(layout, point32, m, r);
+  for (size_t v = 0; v < n_vec; ++v)
+    host_put(layout, (uint8_t*)y_out, v, host_mle_fold(layout, order, r, m, (const uint8_t*)in_v + v * stride * 32, n, threads)[0]);
+  return MSM_AMD_OK;
+}
+
+// out[i] = lo[i mod 2^k] hi[i / 2^k]: the factors of the lower and of the upper bits, one product per output
+int host_fr_eq_table(int layout, int order, const void* point32, size_t m, int threads, void* out_v) {
+  if (fr_eq_table_check(layout, order, point32, m, out_v, false)) return MSM_AMD_INPUT_ERROR;
+  u256 p[kFrMleMaxVars], by_bit[kFrMleMaxVars];
+  host_read_records(layout, point32, m, p);
+  for (size_t b = 0; b < m; ++b) by_bit[b] = p[order == kFrMleHigh ? m - 1 - b : b];
+  auto table = [&](uint32_t first, uint32_t bits) {
+    std::vector<u256> t(1, Fr::one());
+    for (uint32_t b = 0; b < bits; ++b) {
+      const u256 one_less = Fr::sub(Fr::one(), by_bit[first + b]);
+      t.resize(t.size() * 2);
+      for (size_t i = t.size() / 2; i-- != 0;) t[i + t.size() / 2] = Fr::mul(t[i], by_bit[first + b]), t[i] = Fr::mul(t[i], one_less);
+    }
+    return t;
+  };
+  const uint32_t k = (uint32_t)m / 2;
+  const std::vector<u256> lo = table(0, k), hi = table(k, (uint32_t)m - k);
+  const uint64_t n = (uint64_t)1 << m;
+  for_ranges(mle_workers(threads, n), n, [&](unsigned, size_t a, size_t b) {
+    for (size_t i = a; i < b; ++i) host_put(layout, (uint8_t*)out_v, i, Fr::mul(lo[i & ((1u << k) - 1)], hi[i >> k]));
+  });
+  return MSM_AMD_OK;
+}
+
+template <int FORM, int K>
+void host_round_form(int layout, int order, const uint8_t* in, uint64_t n, uint64_t stride, int threads, u256* g) {
+  using Sums = FrMleSums<FORM, K>;
+  const uint64_t h = n / 2;
+  const unsigned T = mle_workers(threads, h);
+  std::vector<Sums> part(T);
+  for_ranges(T, h, [&](unsigned t, size_t a, size_t b) {
+    Sums s;
+    s.clear();
+    for (size_t x = a; x < b; ++x) {
+      u256 lo[K], hi[K];
+      for (int j = 0; j < K; ++j) {
+        lo[j] = host_get(layout, in + j * stride * 32, order == kFrMleHigh ? x : 2 * x);
+        hi[j] = host_get(layout, in + j * stride * 32, order == kFrMleHigh ? x + h : 2 * x + 1);
+      }
+      s.add_pair(lo, hi);
+    }
+    part[t] = s;
+  });
+  for (int v = 0; v < Sums::kValues; ++v) {
+    g[v] = u256_zero();
+    for (unsigned t = 0; t < T; ++t) g[v] = Fr::add(g[v], part[t].g[v]);
+  }
+}
+
+int host_fr_sumcheck_round(int layout, int order, int form, const void* in_v, size_t n, size_t n_vec, size_t stride, int threads,
+                           void* g_out) {
+  if (fr_sumcheck_check(layout, order, form, in_v, n, n_vec, stride, g_out, false)) return MSM_AMD_INPUT_ERROR;
+  if (n_vec == 0) return MSM_AMD_OK;
+  const uint8_t* in = (const uint8_t*)in_v;
+  u256 g[kFrMleMaxValues];
+  if (form == kFrSumEqAbC) host_round_form<kFrSumEqAbC, 4>(layout, order, in, n, stride, threads, g);
+  else if (n_vec == 1) host_round_form<kFrSumProduct, 1>(layout, order, in, n, stride, threads, g);
+  else if (n_vec == 2) host_round_form<kFrSumProduct, 2>(layout, order, in, n, stride, threads, g);
+  else if (n_vec == 3) host_round_form<kFrSumProduct, 3>(layout, order, in, n, stride, threads, g);
+  else host_round_form<kFrSumProduct, 4>(layout, order, in, n, stride, threads, g);
+  for (uint32_t t = 0; t <= fr_mle_degree(form, n_vec); ++t) host_put(layout, (uint8_t*)g_out, t, g[t]);
+  return MSM_AMD_OK;
+}
+
 }  // namespace
 }  // namespace msm_amd
 
 extern "C" {
+
+int msm_amd_host_fr_mle_bind(int scalar_layout, int order, const void* r, size_t n_bind, const void* in, size_t n, size_t n_vec,
+                             size_t stride, int threads, void* out) {
+  return msm_amd::host_fr_mle_bind(scalar_layout, order, r, n_bind, in, n, n_vec, stride, threads, out);
+}
+
+int msm_amd_host_fr_mle_eval(int scalar_layout, int order, const void* point, const void* in, size_t n, size_t n_vec,
+                             size_t stride, int threads, void* y_out) {
+  return msm_amd::host_fr_mle_eval(scalar_layout, order, point, in, n, n_vec, stride, threads, y_out);
+}
+
+int msm_amd_host_fr_eq_table(int scalar_layout, int order, const void* point, size_t m, int threads, void* out) {
+  return msm_amd::host_fr_eq_table(scalar_layout, order, point, m, threads, out);
+}
+
+int msm_amd_host_fr_sumcheck_round(int scalar_layout, int order, int form, const void* in, size_t n, size_t n_vec, size_t stride,
+                                   int threads, void* g_out) {
+  return msm_amd::host_fr_sumcheck_round(scalar_layout, order, form, in, n, n_vec, stride, threads, g_out);
+}
+
+int msm_amd_test_fr_mle_plan(int call, int order, int form, size_t n, size_t n_vec, uint32_t n_bind, uint32_t chunk_log,
+                             uint32_t tile_log, uint64_t counts[8]) {
+  using namespace msm_amd;
+  if (!counts || chunk_log < kFrMleMinChunkLog || chunk_log > kFrMleMaxChunkLog || tile_log < kFrMinTileLog ||
+      tile_log > kFrTileLog || !fr_mle_order_known(order))
+    return MSM_AMD_INPUT_ERROR;
+  uint64_t c[8] = {};
+  if (call == MSM_AMD_MLE_CALL_EQ_TABLE) {   // n is m
+    if (n < 1 || n > kFrMleMaxVars) return MSM_AMD_INPUT_ERROR;
+    const uint64_t lanes = (uint64_t)1 << (n >= kFrMleEqWideFrom ? n - kFrMleEqSpread : n);
+    c[0] = 1, c[1] = (lanes + kFrWave - 1) / kFrWave, c[6] = (uint64_t)1 << n;
+  } else {
+    if (n_vec == 0 || fr_mle_tables_check(n, n_vec, n)) return MSM_AMD_INPUT_ERROR;
+    if (call == MSM_AMD_MLE_CALL_BIND) {
+      if (n_bind == 0 || n_bind > fr_mle_log2(n)) return MSM_AMD_INPUT_ERROR;
+      const FrMleBindPlan p = fr_mle_bind_plan(order, n, n_vec, n_bind);
+      c[0] = p.launches, c[1] = p.waves, c[2] = p.work_records, c[4] = p.launches, c[6] = (n >> n_bind) * n_vec;
+    } else if (call == MSM_AMD_MLE_CALL_EVAL) {
+      const FrScanPlan p = fr_scan_plan(n, n_vec, tile_log);
+      c[0] = p.levels, c[2] = p.records + n_vec, c[4] = p.levels, c[5] = p.tiles[0] * n_vec, c[6] = n_vec;
+      for (uint32_t k = 0; k < p.levels; ++k) c[1] += p.tiles[k] * n_vec;
+    } else if (call == MSM_AMD_MLE_CALL_ROUND) {
+      const uint32_t d = fr_mle_degree(form, n_vec);
+      if (!d) return MSM_AMD_INPUT_ERROR;
+      const FrMleRoundPlan p = fr_mle_round_plan(n, d + 1, chunk_log);
+      c[0] = p.launches, c[1] = p.waves, c[2] = p.records, c[4] = p.levels, c[5] = p.count[0], c[6] = p.values;
+    } else {
+      return MSM_AMD_INPUT_ERROR;
+    }
+  }
+  c[3] = c[2] * 32;
+  std::memcpy(counts, c, sizeof c);
+  return MSM_AMD_OK;
+}
 
 int msm_amd_host_fr_matvec(int scalar_layout, size_t n_rows, size_t n_cols, const uint64_t* row_ptr, const uint32_t* col_idx,
                            const void* values, const void* x, int threads, void* y) {

@@ -29,6 +29,18 @@
 //   fr_mat_wave_kernel     one wave per segment of a longer row: lane l takes the entries l, l + 64, ..., six xor-shuffle
 //                          additions fold the lanes, lane 0 stores y[row], or the raw partial sum of a split row.
 //   fr_mat_fold_kernel     one wave per split row: the sum of its partials, the same fold, y[row].
+//   fr_sumcheck_round_kernel<FORM, K>  (fr_mle.hip.h) one wave per chunk of 2^C pairs: lane l takes the pairs l, l + 64, ... of
+//                          the chunk (HIGH: both records at unit stride across the wave; LOW: the two records of a pair are 64
+//                          contiguous bytes), d + 1 sums per lane in registers, six xor-shuffle additions each, lane 0 stores
+//                          d + 1 raw partial records.
+//   fr_mle_fold_kernel     one wave per 2^10 partials of one t: their sum, the same fold.
+//   fr_mle_eval_kernel<P>  one wave per tile of 2^c records: lane l folds the records l, l + 64, ... (a tree in registers
+//                          over the tile's upper variables), six xor-shuffle steps fold the variables of the lane index,
+//                          lane 0 stores the tile's record.
+//   fr_mle_bind_kernel<K>  one lane per output: a tree over its 2^K records (HIGH: n / 2^K apart, unit stride across the
+//                          lanes; LOW: 2^K consecutive records).
+//   fr_eq_table_kernel<S>  one lane per 2^S outputs: the product of the factors of the index bits below, then S doublings;
+//                          the 2 m factors come by value.
 // Phases are ordered by launch order on one stream only; no kernel reads what another workgroup of its launch wrote.
 // LDS images are eight word planes; slot m sits at m + (m >> log2(records per lane)), so that the unit-stride accesses
 // and the walks of the lanes (stride = records per lane) are both free of bank conflicts, bar one 2-way per access.
@@ -397,6 +409,137 @@ __global__ void __launch_bounds__(kFrWave) fr_mat_fold_kernel(FrMatArgs a) {
   if (lane == 0) store_rec(a.y + (uint64_t)s.x * 8, fr_store(a.layout, acc));
 }
 
+// ---- multilinear tables and sumcheck rounds (fr_mle.hip.h) -------------------------------------------------------------------
+struct FrMleRoundArgs {
+  const uint32_t* in;
+  uint32_t* partial;         // plane t: waves raw records
+  uint64_t stride, h, waves;
+  uint32_t chunk_log;
+  int layout, order;
+};
+struct FrMleFoldArgs {
+  const uint32_t* src;       // plane t: count raw records
+  uint32_t* dst;             // plane t: groups raw records
+  uint64_t count, groups;
+};
+struct FrMleEvalArgs {
+  const uint32_t* src;
+  uint32_t* dst;             // one raw record per tile
+  uint64_t stride, tiles;    // records between the tables of src, tiles per table
+  uint32_t tile_log, cnt_log;   // records per tile: 2^cnt_log <= 2^tile_log
+  int layout;
+  u256 r[kFrTileLog];        // the challenge of variable j of the tile
+};
+struct FrMleBindArgs {
+  const uint32_t* in;
+  uint32_t* out;
+  uint64_t total;                  // outputs over all tables
+  uint64_t in_stride, out_stride;  // records between tables
+  uint64_t lane_step, rec_step;    // records between the first records of two outputs, and between the records of one
+  uint32_t q_log;                  // outputs per table, as a power of two
+  int in_layout, out_layout;
+  u256 r[kFrMleBindVars];          // the challenge of bit b of the record's number within its output
+};
+struct FrMleEqArgs {
+  uint32_t* out;
+  uint32_t m;
+  int layout;
+  u256 f[kFrMleMaxVars][2];        // bit b of the index clear / set
+};
+
+// The fold of the 2^K records src, src + step, ...: bit b of a record's number meets r[b].  A tree in registers.
+template <int K>
+__device__ __forceinline__ u256 mle_tree(const uint32_t* src, uint64_t step, int layout, const u256* r) {
+  if constexpr (K == 0) {
+    return fr_load(layout, load_rec(src));
+  } else {
+    const u256 lo = mle_tree<K - 1>(src, step, layout, r);
+    const u256 hi = mle_tree<K - 1>(src + (step << (K - 1)) * 8, step, layout, r);
+    return fr_mle_fold(lo, hi, r[K - 1]);
+  }
+}
+
+// two waves per SIMD: 256 registers, so that the four-table product stays clear of AGPRs and of scratch
+template <int FORM, int K>
+__global__ void __launch_bounds__(kFrWave, 2) fr_sumcheck_round_kernel(FrMleRoundArgs a) {
+  const uint32_t lane = threadIdx.x;
+  const uint64_t first = (uint64_t)blockIdx.x << a.chunk_log;
+  const uint32_t cnt = 1u << a.chunk_log;
+  FrMleSums<FORM, K> s;
+  s.clear();
+  NTT_NO_UNROLL for (uint32_t m = lane; m < cnt; m += kFrWave) {
+    const uint64_t x = first + m;
+    const uint64_t i_lo = a.order == kFrMleHigh ? x : 2 * x, i_hi = a.order == kFrMleHigh ? x + a.h : 2 * x + 1;
+    u256 lo[K], hi[K];
+    MSM_UNROLL for (int j = 0; j < K; ++j) {
+      lo[j] = fr_load(a.layout, load_rec(a.in + ((uint64_t)j * a.stride + i_lo) * 8));
+      hi[j] = fr_load(a.layout, load_rec(a.in + ((uint64_t)j * a.stride + i_hi) * 8));
+    }
+    s.add_pair(lo, hi);
+  }
+  MSM_UNROLL for (int t = 0; t < FrMleSums<FORM, K>::kValues; ++t) {
+    const u256 sum = wave_sum(s.g[t]);
+    if (lane == 0) store_rec(a.partial + ((uint64_t)t * a.waves + blockIdx.x) * 8, sum);
+  }
+}
+
+__global__ void __launch_bounds__(kFrWave) fr_mle_fold_kernel(FrMleFoldArgs a) {
+  const uint32_t lane = threadIdx.x;
+  const uint64_t t = blockIdx.x / a.groups, g = blockIdx.x - t * a.groups;
+  const uint64_t first = g << kFrMleFoldLog, left = a.count - first;
+  const uint32_t cnt = left < (1u << kFrMleFoldLog) ? (uint32_t)left : (1u << kFrMleFoldLog);
+  u256 acc = u256_zero();
+  NTT_NO_UNROLL for (uint32_t m = lane; m < cnt; m += kFrWave) acc = Fr::add(acc, load_rec(a.src + (t * a.count + first + m) * 8));
+  acc = wave_sum(acc);
+  if (lane == 0) store_rec(a.dst + (uint64_t)blockIdx.x * 8, acc);
+}
+
+template <int PER_LOG>
+__global__ void __launch_bounds__(kFrWave) fr_mle_eval_kernel(FrMleEvalArgs a) {
+  const uint32_t lane = threadIdx.x;
+  const uint64_t v = blockIdx.x / a.tiles, b = blockIdx.x - v * a.tiles;
+  const uint32_t* src = a.src + (v * a.stride + (b << a.tile_log)) * 8;
+  u256 acc = u256_zero();
+  if ((lane >> a.cnt_log) == 0) acc = mle_tree<PER_LOG>(src + lane * 8, kFrWave, a.layout, a.r + 6);
+  const uint32_t steps = a.cnt_log < 6u ? a.cnt_log : 6u;
+  NTT_NO_UNROLL for (uint32_t s = 0; s < steps; ++s) {
+    const u256 other = wave_xor(acc, 1u << s);
+    const bool up = (lane >> s) & 1u;
+    acc = fr_mle_fold(fr_select(up, other, acc), fr_select(up, acc, other), a.r[s]);
+  }
+  if (lane == 0) store_rec(a.dst + (uint64_t)blockIdx.x * 8, acc);
+}
+
+template <int K>
+__global__ void __launch_bounds__(kFrMapThreads) fr_mle_bind_kernel(FrMleBindArgs a) {
+  const uint64_t idx = (uint64_t)blockIdx.x * kFrMapThreads + threadIdx.x;
+  if (idx >= a.total) return;
+  const uint64_t v = idx >> a.q_log, i = idx - (v << a.q_log);
+  const u256 x = mle_tree<K>(a.in + (v * a.in_stride + i * a.lane_step) * 8, a.rec_step, a.in_layout, a.r);
+  store_rec(a.out + (v * a.out_stride + i) * 8, fr_store(a.out_layout, x));
+}
+
+// acc holds the factors of the bits below `bit`; the S bits from there double it
+template <int S>
+__device__ __forceinline__ void eq_spread(const FrMleEqArgs& a, const u256& acc, uint64_t i, uint32_t bit) {
+  if constexpr (S == 0) {
+    store_rec(a.out + i * 8, fr_store(a.layout, acc));
+  } else {
+    eq_spread<S - 1>(a, Fr::mul(acc, a.f[bit][0]), i, bit + 1);
+    eq_spread<S - 1>(a, Fr::mul(acc, a.f[bit][1]), i + ((uint64_t)1 << bit), bit + 1);
+  }
+}
+
+template <int S>
+__global__ void __launch_bounds__(kFrMapThreads) fr_eq_table_kernel(FrMleEqArgs a) {
+  const uint64_t idx = (uint64_t)blockIdx.x * kFrMapThreads + threadIdx.x;
+  const uint32_t low = a.m - S;   // >= 1
+  if (idx >> low) return;
+  u256 acc = fr_select(idx & 1u, a.f[0][1], a.f[0][0]);
+  NTT_NO_UNROLL for (uint32_t b = 1; b < low; ++b) acc = Fr::mul(acc, fr_select((idx >> b) & 1u, a.f[b][1], a.f[b][0]));
+  eq_spread<S>(a, acc, idx, low);
+}
+
 template <int OP>
 void launch_map_op(hipStream_t st, int layout, const u256& k, const void* a, const void* b, const void* c, size_t n, void* out) {
   hipLaunchKernelGGL(fr_map_kernel<OP>, dim3((uint32_t)((n + kFrMapThreads - 1) / kFrMapThreads)), dim3(kFrMapThreads), 0, st,
@@ -508,6 +651,100 @@ uint32_t launch_fr_matvec(hipStream_t st, const FrMatLaunch& c) {
   else if (c.plan.segments) hipLaunchKernelGGL(fr_mat_wave_kernel<false>, wave_grid, dim3(kFrWave), 0, st, a);
   if (c.plan.split_rows) hipLaunchKernelGGL(fr_mat_fold_kernel, dim3((uint32_t)c.plan.split_rows), dim3(kFrWave), 0, st, a);
   return (uint32_t)c.plan.launches;
+}
+
+template <int FORM, int K>
+void launch_round_form(hipStream_t st, const FrMleRoundArgs& a) {
+  hipLaunchKernelGGL((fr_sumcheck_round_kernel<FORM, K>), dim3((uint32_t)a.waves), dim3(kFrWave), 0, st, a);
+}
+
+uint32_t launch_fr_sumcheck_round(hipStream_t st, const FrMleRoundLaunch& c) {
+  const FrMleRoundPlan plan = fr_mle_round_plan(c.n, fr_mle_degree(c.form, c.n_vec) + 1, c.chunk_log);
+  uint32_t* work = (uint32_t*)c.work;
+  FrMleRoundArgs a{};
+  a.in = (const uint32_t*)c.in, a.partial = work + plan.offset[0] * 8;
+  a.stride = c.stride, a.h = c.n / 2, a.waves = plan.count[0], a.chunk_log = plan.chunk_log;
+  a.layout = c.layout, a.order = c.order;
+  if (c.form == kFrSumEqAbC) launch_round_form<kFrSumEqAbC, 4>(st, a);
+  else if (c.n_vec == 1) launch_round_form<kFrSumProduct, 1>(st, a);
+  else if (c.n_vec == 2) launch_round_form<kFrSumProduct, 2>(st, a);
+  else if (c.n_vec == 3) launch_round_form<kFrSumProduct, 3>(st, a);
+  else launch_round_form<kFrSumProduct, 4>(st, a);
+  for (uint32_t k = 1; k < plan.levels; ++k) {
+    FrMleFoldArgs f{};
+    f.src = work + plan.offset[k - 1] * 8, f.dst = work + plan.offset[k] * 8;
+    f.count = plan.count[k - 1], f.groups = plan.count[k];
+    hipLaunchKernelGGL(fr_mle_fold_kernel, dim3((uint32_t)(f.groups * plan.values)), dim3(kFrWave), 0, st, f);
+  }
+  return plan.launches;
+}
+
+uint32_t launch_fr_mle_eval(hipStream_t st, const FrMleEvalLaunch& c) {
+  const FrScanPlan plan = fr_scan_plan(c.n, c.n_vec, c.tile_log);
+  uint32_t* work = (uint32_t*)c.work;
+  uint32_t var = 0;
+  for (uint32_t k = 0; k < plan.levels; ++k) {
+    const bool last = k + 1 == plan.levels;
+    FrMleEvalArgs a{};
+    a.src = k == 0 ? (const uint32_t*)c.in : work + plan.offset[k] * 8;
+    a.dst = last ? work + plan.records * 8 : work + plan.offset[k + 1] * 8;
+    a.stride = k == 0 ? c.stride : plan.len[k], a.tiles = plan.tiles[k];
+    a.tile_log = c.tile_log;
+    a.cnt_log = fr_mle_log2(plan.len[k] < ((uint64_t)1 << c.tile_log) ? plan.len[k] : (uint64_t)1 << c.tile_log);
+    a.layout = k == 0 ? c.layout : kFrRaw;
+    // lane l holds the records l, l + 64, ...: variables 0 .. 5 of the tile are the lane's bits, the rest its tree's
+    for (uint32_t j = 0; j < a.cnt_log; ++j) a.r[j] = c.r[var + j];
+    var += a.cnt_log;
+    const dim3 grid((uint32_t)(a.tiles * c.n_vec));
+    switch (fr_mle_per_log((uint64_t)1 << a.cnt_log)) {
+      case 0: hipLaunchKernelGGL(fr_mle_eval_kernel<0>, grid, dim3(kFrWave), 0, st, a); break;
+      case 1: hipLaunchKernelGGL(fr_mle_eval_kernel<1>, grid, dim3(kFrWave), 0, st, a); break;
+      case 2: hipLaunchKernelGGL(fr_mle_eval_kernel<2>, grid, dim3(kFrWave), 0, st, a); break;
+      default: hipLaunchKernelGGL(fr_mle_eval_kernel<3>, grid, dim3(kFrWave), 0, st, a); break;
+    }
+  }
+  return plan.levels;
+}
+
+uint32_t launch_fr_mle_bind(hipStream_t st, const FrMleBindLaunch& c) {
+  const FrMleBindPlan plan = fr_mle_bind_plan(c.order, c.n, c.n_vec, c.n_bind);
+  const bool high = c.order == kFrMleHigh;
+  uint64_t len = c.n;
+  uint32_t used = 0;
+  const uint32_t* src = (const uint32_t*)c.in;
+  uint64_t src_stride = c.stride;
+  for (uint32_t k = 0; k < plan.launches; ++k) {
+    const uint32_t vars = plan.vars[k];
+    const bool last = k + 1 == plan.launches;
+    // HIGH: into the output, and in place from there.  LOW: output and workspace in turn, the last launch into the output.
+    const bool to_out = high || ((plan.launches - 1 - k) & 1u) == 0;
+    const uint64_t q = len >> vars;
+    FrMleBindArgs a{};
+    a.in = src, a.out = to_out ? (uint32_t*)c.out : (uint32_t*)c.work;
+    a.total = q * c.n_vec, a.q_log = fr_mle_log2(q);
+    a.in_stride = src_stride, a.out_stride = to_out ? c.stride : q;
+    a.lane_step = high ? 1 : (uint64_t)1 << vars, a.rec_step = high ? q : 1;
+    a.in_layout = k == 0 ? c.layout : kFrRaw, a.out_layout = last ? c.layout : kFrRaw;
+    // step s of the launch binds bit s of the record's number (LOW) or bit vars - 1 - s (HIGH)
+    for (uint32_t s = 0; s < vars; ++s) a.r[high ? vars - 1 - s : s] = c.r[used + s];
+    const dim3 grid((uint32_t)((a.total + kFrMapThreads - 1) / kFrMapThreads));
+    if (vars == 1) hipLaunchKernelGGL(fr_mle_bind_kernel<1>, grid, dim3(kFrMapThreads), 0, st, a);
+    else if (vars == 2) hipLaunchKernelGGL(fr_mle_bind_kernel<2>, grid, dim3(kFrMapThreads), 0, st, a);
+    else hipLaunchKernelGGL(fr_mle_bind_kernel<3>, grid, dim3(kFrMapThreads), 0, st, a);
+    src = a.out, src_stride = a.out_stride, len = q, used += vars;
+  }
+  return plan.launches;
+}
+
+void launch_fr_eq_table(hipStream_t st, int layout, const u256* point_by_bit, uint32_t m, void* out) {
+  FrMleEqArgs a{};
+  a.out = (uint32_t*)out, a.m = m, a.layout = layout;
+  for (uint32_t b = 0; b < m; ++b) a.f[b][0] = Fr::sub(Fr::one(), point_by_bit[b]), a.f[b][1] = point_by_bit[b];
+  const bool wide = m >= kFrMleEqWideFrom;
+  const uint64_t lanes = (uint64_t)1 << (wide ? m - kFrMleEqSpread : m);
+  const dim3 grid((uint32_t)((lanes + kFrMapThreads - 1) / kFrMapThreads));
+  if (wide) hipLaunchKernelGGL(fr_eq_table_kernel<(int)kFrMleEqSpread>, grid, dim3(kFrMapThreads), 0, st, a);
+  else hipLaunchKernelGGL(fr_eq_table_kernel<0>, grid, dim3(kFrMapThreads), 0, st, a);
 }
 
 uint32_t launch_fr_inv_products(hipStream_t st, int layout, const void* in, uint64_t n, uint32_t tile_log, void* work_v) {

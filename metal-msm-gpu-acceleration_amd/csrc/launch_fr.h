@@ -6,6 +6,7 @@
 #include <cstddef>
 
 #include "fr_mat.hip.h"
+#include "fr_mle.hip.h"
 #include "fr_vec.hip.h"
 
 namespace msm_amd {
@@ -81,6 +82,38 @@ struct FrMatLaunch {
 };
 uint32_t launch_fr_matvec(hipStream_t st, const FrMatLaunch& c);
 
+// Multilinear tables and sumcheck rounds (fr_mle.hip.h).  Tables lie `stride` records apart; challenges are reduced
+// Montgomery residues in the order of LOW: r[j] meets variable x_j (the driver reverses the point of a HIGH evaluation).
+struct FrMleRoundLaunch {
+  const void* in;      // n_vec tables of n records
+  void* work;          // fr_mle_round_plan(n, d + 1, chunk_log).records raw records; the d + 1 values at values_off
+  uint64_t n, n_vec, stride;
+  uint32_t chunk_log;
+  int layout, order, form;
+};
+uint32_t launch_fr_sumcheck_round(hipStream_t st, const FrMleRoundLaunch& c);
+struct FrMleEvalLaunch {
+  const void* in;
+  void* work;          // fr_scan_plan(n, n_vec, tile_log).records + n_vec raw records; the n_vec values behind the levels
+  uint64_t n, n_vec, stride;
+  uint32_t tile_log;
+  int layout;
+  u256 r[kFrMleMaxVars];   // r[j] meets x_j
+};
+uint32_t launch_fr_mle_eval(hipStream_t st, const FrMleEvalLaunch& c);
+struct FrMleBindLaunch {
+  const void* in;
+  void* out;           // HIGH: may be in
+  void* work;          // fr_mle_bind_plan(..).work_records raw records (may be null for none)
+  uint64_t n, n_vec, stride;
+  uint32_t n_bind;
+  int layout, order;
+  u256 r[kFrMleMaxVars];   // r[s] is the challenge of step s of `order`
+};
+uint32_t launch_fr_mle_bind(hipStream_t st, const FrMleBindLaunch& c);
+// out[i] = prod_b (bit b of i ? point_by_bit[b] : 1 - point_by_bit[b]), i < 2^m
+void launch_fr_eq_table(hipStream_t st, int layout, const u256* point_by_bit, uint32_t m, void* out);
+
 // host_fr.hip.  Each check returns null or what is wrong, for msm_amd_last_error.
 bool fr_layout_known(int scalar_layout);   // MONT_LE and CANON_LE
 bool fr_mode_known(int mode);
@@ -104,6 +137,17 @@ const char* fr_matrix_check(int scalar_layout, uint64_t n_rows, uint64_t n_cols,
                             const uint32_t* col_idx, const void* values);
 // x (n_cols records) and y (n_rows records) of a product: out of place only, no overlap of any kind
 const char* fr_matvec_check(int scalar_layout, uint64_t n_rows, uint64_t n_cols, const void* x, const void* y, bool device);
+// The multilinear calls.  Every check first looks at layout, order and form, then lets n_vec == 0 pass (nothing to do), then
+// at the sizes, the pointers and the overlap rules.  fr_mle_tables_check is the part they share: n a power of two, 2 <= n <
+// 2^32, stride >= n, n_vec stride < 2^32.
+const char* fr_mle_tables_check(uint64_t n, uint64_t n_vec, uint64_t stride);
+const char* fr_mle_bind_check(int scalar_layout, int order, const void* r, uint64_t n_bind, const void* in, uint64_t n,
+                              uint64_t n_vec, uint64_t stride, const void* out, bool device);
+const char* fr_mle_eval_check(int scalar_layout, int order, const void* point, const void* in, uint64_t n, uint64_t n_vec,
+                              uint64_t stride, const void* y_out, bool device);
+const char* fr_eq_table_check(int scalar_layout, int order, const void* point, uint64_t m, const void* out, bool device);
+const char* fr_sumcheck_check(int scalar_layout, int order, int form, const void* in, uint64_t n, uint64_t n_vec,
+                              uint64_t stride, const void* g_out, bool device);
 // The device image of a checked matrix in host memory: values reduced mod r and deduplicated into the dictionary (ids 0
 // and 1 are always 1 and r - 1, whether they occur or not: dict_records counts them, n_distinct only what occurs), the
 // plan at (long_rows, seg_log), every part at its place of fr_mat_image

@@ -219,7 +219,8 @@ struct CallState {
   DeviceBuf table, xyzz;           // mul_points: the fixed-base table, the XYZZ records of one chunk of outputs
   DeviceBuf scratch, pow;          // transform: the ONE batch-sized scratch of a plan with more than one pass, the powers of a shift
   DeviceBuf work;                  // Fr scan and inversion: the tile totals (fr_scan_plan, fr_inv_plan); the partial sums of
-                                   // the split rows of a sparse product (fr_mat_plan)
+                                   // the split rows of a sparse product (fr_mat_plan); the partial sums of a sumcheck round,
+                                   // the levels of a multilinear evaluation, the turns of a LOW bind (fr_mle.hip.h)
   uint8_t* h_record = nullptr;     // pinned, 64 bytes
   uint8_t* h_values = nullptr;     // pinned: the values a call reads back beside its output (p_v(z) of the polynomial calls)
   size_t h_values_cap = 0;
@@ -292,6 +293,7 @@ struct msm_amd_ctx {
   uint32_t fr_mat_long = kFrMatLong;     // rows of a sparse matrix above this many entries take the wave path (MSM_AMD_FR_MAT_LONG)
   bool fr_mat_signs = false;             // the product kernels that skip the product for values 1 and r - 1 (MSM_AMD_FR_MAT_SIGNS)
   uint32_t fr_mat_seg_log = kFrMatSegLog;   // entries per wave of that path, as a power of two (MSM_AMD_FR_MAT_SEG_LOG)
+  uint32_t fr_mle_chunk_log = kFrMleChunkLog;   // pairs per wave of a sumcheck round, as a power of two (MSM_AMD_FR_MLE_CHUNK_LOG)
   uint32_t ntt_tile_log = kNttTileLog;   // elements per workgroup of a transform pass, as a power of two (MSM_AMD_NTT_TILE_LOG)
   int next_ws = 0;
   DeviceBuf scratch_a, scratch_b, scratch_c, scratch_b2, scratch_c2;
@@ -2142,6 +2144,8 @@ int msm_amd_init(int device, msm_amd_ctx** out) {
   if (const char* e = std::getenv("MSM_AMD_FR_MAT_LONG"))
     ctx->fr_mat_long = (uint32_t)std::max((int)kFrMatMinLong, std::min((int)kFrMatMaxLong, std::atoi(e)));
   if (const char* e = std::getenv("MSM_AMD_FR_MAT_SIGNS")) ctx->fr_mat_signs = std::atoi(e) != 0;
+  if (const char* e = std::getenv("MSM_AMD_FR_MLE_CHUNK_LOG"))
+    ctx->fr_mle_chunk_log = (uint32_t)std::max((int)kFrMleMinChunkLog, std::min((int)kFrMleMaxChunkLog, std::atoi(e)));
   if (const char* e = std::getenv("MSM_AMD_FR_MAT_SEG_LOG"))
     ctx->fr_mat_seg_log = (uint32_t)std::max((int)kFrMatMinSegLog, std::min((int)kFrMatMaxSegLog, std::atoi(e)));
   if (const char* e = std::getenv("MSM_AMD_BASES_CACHE_VERIFY")) ctx->bases_cache_verify = std::strcmp(e, "full") == 0;
@@ -4592,6 +4596,171 @@ int msm_amd_fr_matvec(msm_amd_ctx* ctx, const msm_amd_fr_matrix* matrix, int sca
 int msm_amd_fr_matvec_device(msm_amd_ctx* ctx, const msm_amd_fr_matrix* matrix, int scalar_layout, const void* d_x, void* d_y,
                              float* kernel_ms) {
   return fr_matvec_call(ctx, matrix, false, scalar_layout, d_x, d_y, kernel_ms);
+}
+
+}  // extern "C"
+
+// ---- multilinear tables over Fr and sumcheck rounds (msm_amd_fr_mle_bind*, msm_amd_fr_mle_eval*, msm_amd_fr_eq_table*,
+// msm_amd_fr_sumcheck_round*) ------------------------------------------------------------------------------------------------
+// Through device_call.  Challenges and points are read once on the host and reach the kernels by value.  The values of an
+// evaluation or a round come back through CallState::h_values.  The host form of a bind copies back the records the call
+// defines and no byte between the tables: one strided copy behind the kernels.
+namespace {
+
+int fr_mle_bind_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int order, const void* r32, size_t n_bind, const void* in,
+                     size_t n, size_t n_vec, size_t stride, void* out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_mle_bind" : "msm_amd_fr_mle_bind_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_mle_bind_check(scalar_layout, order, r32, n_bind, in, n, n_vec, stride, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n_vec == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  CallState& s = ctx->calls;
+  FrMleBindLaunch c{};
+  c.n = n, c.n_vec = n_vec, c.stride = stride, c.n_bind = (uint32_t)n_bind, c.layout = scalar_layout, c.order = order;
+  for (size_t k = 0; k < n_bind; ++k) c.r[k] = fr_read_record(scalar_layout, (const uint8_t*)r32 + k * 32);
+  const FrMleBindPlan plan = fr_mle_bind_plan(order, n, n_vec, c.n_bind);
+  const size_t span = ((n_vec - 1) * stride + n) * 32, left = (n >> n_bind) * 32;
+  // the host form works from the staged input into the staged output; the strided copy below brings the result back
+  d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = span;
+  d.out = out;
+  d.work[0] = {&s.work, std::max<size_t>(32, plan.work_records * 32)};
+  if (host) d.work[1] = {&s.out, span};
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) -> int {
+    c.in = io.in[0], c.out = host ? s.out.p : io.out, c.work = s.work.p;
+    launch_fr_mle_bind(st, c);
+    if (host)
+      HIP_TRY(ctx, hipMemcpy2DAsync(out, stride * 32, s.out.p, stride * 32, left, n_vec, hipMemcpyDeviceToHost, st));
+    return MSM_AMD_OK;
+  });
+}
+
+int fr_mle_eval_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int order, const void* point32, const void* in, size_t n,
+                     size_t n_vec, size_t stride, void* y_out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_mle_eval" : "msm_amd_fr_mle_eval_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_mle_eval_check(scalar_layout, order, point32, in, n, n_vec, stride, y_out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n_vec == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  CallState& s = ctx->calls;
+  FrMleEvalLaunch c{};
+  c.n = n, c.n_vec = n_vec, c.stride = stride, c.tile_log = ctx->fr_tile_log, c.layout = scalar_layout;
+  const uint32_t m = fr_mle_log2(n);
+  // the kernels fold x_j at r[j]: HIGH binds x_(m-1-s) at point[s]
+  for (uint32_t k = 0; k < m; ++k)
+    c.r[order == kFrMleHigh ? m - 1 - k : k] = fr_read_record(scalar_layout, (const uint8_t*)point32 + (size_t)k * 32);
+  const FrScanPlan plan = fr_scan_plan(n, n_vec, c.tile_log);
+  d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = ((n_vec - 1) * stride + n) * 32;
+  d.work[0] = {&s.work, fr_poly_values(plan) + n_vec * 32};
+  d.values_bytes = n_vec * 32;
+  const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
+    c.in = io.in[0], c.work = s.work.p;
+    launch_fr_mle_eval(st, c);
+    io.values = (const uint8_t*)s.work.p + fr_poly_values(plan);
+    return MSM_AMD_OK;
+  });
+  if (rc == MSM_AMD_OK) fr_values_out(s, scalar_layout, n_vec, y_out);
+  return rc;
+}
+
+int fr_eq_table_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int order, const void* point32, size_t m, void* out,
+                     float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_eq_table" : "msm_amd_fr_eq_table_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_eq_table_check(scalar_layout, order, point32, m, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  u256 by_bit[kFrMleMaxVars];
+  for (size_t k = 0; k < m; ++k)
+    by_bit[order == kFrMleHigh ? m - 1 - k : k] = fr_read_record(scalar_layout, (const uint8_t*)point32 + k * 32);
+  d.host = host, d.kernel_ms = kernel_ms;
+  d.out = out, d.out_bytes = ((size_t)1 << m) * 32;
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    launch_fr_eq_table(st, scalar_layout, by_bit, (uint32_t)m, io.out);
+    return MSM_AMD_OK;
+  });
+}
+
+int fr_sumcheck_round_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int order, int form, const void* in, size_t n,
+                           size_t n_vec, size_t stride, void* g_out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_sumcheck_round" : "msm_amd_fr_sumcheck_round_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_sumcheck_check(scalar_layout, order, form, in, n, n_vec, stride, g_out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n_vec == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  CallState& s = ctx->calls;
+  FrMleRoundLaunch c{};
+  c.n = n, c.n_vec = n_vec, c.stride = stride, c.chunk_log = ctx->fr_mle_chunk_log;
+  c.layout = scalar_layout, c.order = order, c.form = form;
+  const uint32_t values = fr_mle_degree(form, n_vec) + 1;
+  const FrMleRoundPlan plan = fr_mle_round_plan(n, values, c.chunk_log);
+  d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = ((n_vec - 1) * stride + n) * 32;
+  d.work[0] = {&s.work, plan.records * 32};
+  d.values_bytes = values * 32;
+  const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
+    c.in = io.in[0], c.work = s.work.p;
+    launch_fr_sumcheck_round(st, c);
+    io.values = (const uint8_t*)s.work.p + plan.values_off * 32;
+    return MSM_AMD_OK;
+  });
+  if (rc == MSM_AMD_OK) fr_values_out(s, scalar_layout, values, g_out);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_fr_mle_bind(msm_amd_ctx* ctx, int scalar_layout, int order, const void* r, size_t n_bind, const void* in, size_t n,
+                        size_t n_vec, size_t stride, void* out) {
+  return fr_mle_bind_call(ctx, true, scalar_layout, order, r, n_bind, in, n, n_vec, stride, out, nullptr);
+}
+
+int msm_amd_fr_mle_bind_device(msm_amd_ctx* ctx, int scalar_layout, int order, const void* r, size_t n_bind, const void* d_in,
+                               size_t n, size_t n_vec, size_t stride, void* d_out, float* kernel_ms) {
+  return fr_mle_bind_call(ctx, false, scalar_layout, order, r, n_bind, d_in, n, n_vec, stride, d_out, kernel_ms);
+}
+
+int msm_amd_fr_mle_eval(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point, const void* in, size_t n,
+                        size_t n_vec, size_t stride, void* y_out) {
+  return fr_mle_eval_call(ctx, true, scalar_layout, order, point, in, n, n_vec, stride, y_out, nullptr);
+}
+
+int msm_amd_fr_mle_eval_device(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point, const void* d_in, size_t n,
+                               size_t n_vec, size_t stride, void* y_out, float* kernel_ms) {
+  return fr_mle_eval_call(ctx, false, scalar_layout, order, point, d_in, n, n_vec, stride, y_out, kernel_ms);
+}
+
+int msm_amd_fr_eq_table(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point, size_t m, void* out) {
+  return fr_eq_table_call(ctx, true, scalar_layout, order, point, m, out, nullptr);
+}
+
+int msm_amd_fr_eq_table_device(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point, size_t m, void* d_out,
+                               float* kernel_ms) {
+  return fr_eq_table_call(ctx, false, scalar_layout, order, point, m, d_out, kernel_ms);
+}
+
+int msm_amd_fr_sumcheck_round(msm_amd_ctx* ctx, int scalar_layout, int order, int form, const void* in, size_t n, size_t n_vec,
+                              size_t stride, void* g_out) {
+  return fr_sumcheck_round_call(ctx, true, scalar_layout, order, form, in, n, n_vec, stride, g_out, nullptr);
+}
+
+int msm_amd_fr_sumcheck_round_device(msm_amd_ctx* ctx, int scalar_layout, int order, int form, const void* d_in, size_t n,
+                                     size_t n_vec, size_t stride, void* g_out, float* kernel_ms) {
+  return fr_sumcheck_round_call(ctx, false, scalar_layout, order, form, d_in, n, n_vec, stride, g_out, kernel_ms);
 }
 
 }  // extern "C"
