@@ -503,13 +503,17 @@ enum {
   MSM_AMD_RAW_FE_SQRT = 36,      /* square root of a0 (normalised, < 8 p) by the ladder of the decompression kernels
                                     (csrc/compress_points.hip.h): out[0..8] = root, out[9] = 1 if there is one, else
                                     all zero; b ignored */
-  MSM_AMD_RAW_BASES_IN_PLACE = 40 /* external records as the accumulate kernel gathers them in place (the image of
+  MSM_AMD_RAW_BASES_IN_PLACE = 40,/* external records as the accumulate kernel gathers them in place (the image of
                                     the point on the isomorphic curve E': limbs of x << 3 and y << 2).  a[0..15],
                                     a[16..31], b[1..16]: records 0, 1, 2 (x, y: 8 + 8 words, little-endian); a[32]:
                                     bit k = negate record k; b[0] = 0: out[0..8], out[9..17] = the limbs of record 0,
                                     out[18] = its sixteen words are all zero, out[19..27] = its lazily negated y;
                                     b[0] = 1: out[0..35] = record 0 + record 1 by the affine start, out[36] = vanished;
                                     b[0] = 2: (record 0 + record 1) + record 2 by the mixed addition */
+  MSM_AMD_RAW_FE_MUL_SUB = 44,   /* mul_sub_np<K>(a0, a1, b0) = a0 a1 / rho + K - b0, the lifted subtraction folded into
+                                    the reduction; K = b1[0]: 0..5 = K4E30, K8E30, K8E31, K16E30, K16E31, K12E30 (any
+                                    other: zero limbs) */
+  MSM_AMD_RAW_FE_SQR_SUB = 45    /* sqr_sub_np<K>(a0, b0) = a0^2 / rho + K - b0, K = b1[0] */
 };
 int msm_amd_test_op_raw(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count);
 /* The same bodies on the host CPU (no GPU needed). */

@@ -33,6 +33,7 @@ POINT_BYTES = {POINT_H2C_AFFINE: 64, POINT_ARK_PROJECTIVE: 96, POINT_ARK_AFFINE:
 RAW_FE_MUL_WIDE, RAW_FE_SQR_WIDE, RAW_FE_MUL2_WIDE = range(32, 35)   # the point additions' wide-digit forms
 RAW_FE_SQRT = 36   # the Fq root of the decompression kernels (35 stays unknown)
 RAW_BASES_IN_PLACE = 40   # external records as accumulate gathers them in place: unpack, affine start, mixed addition
+RAW_FE_MUL_SUB, RAW_FE_SQR_SUB = 44, 45   # mul_sub_np<K> / sqr_sub_np<K>: the lifted subtraction folded into the reduction
 RAW_IN_WORDS, RAW_OUT_WORDS = 36, 40
 # BN254 G2 (MSM_AMD_G2_*): point layouts, raw-limb test ops and their record widths
 G2_POINT_H2C_AFFINE, G2_POINT_ARK_AFFINE, G2_POINT_PREPARED, G2_POINT_TABLES = 0, 1, 2, 3

@@ -16,6 +16,10 @@
 //      X < 10 p      Y < 6 p      ZZ < 2.8 p      ZZZ < 2 p      limbs 0..7 < 2^29 + 8
 // (pti_mmadd sets the X and ZZ figures: its R < 12.1 p and ZZ3 = P^2 with P < 17.1 p).  tools/fq29_bounds.py
 // re-derives every bound below by interval arithmetic and checks that no 64-bit column sum can overflow.
+// The 2^29 + 8 is what Fq29::norm leaves: the Y of a lone base (pti_from_affi) and the doubling's outputs.  Every
+// coordinate an addition returns is the output of a reduction, limbs 0..7 < 2^29 exactly: X3 = R^2 - PPP - 2 Q and the
+// mixed addition's P = U2 - X1, R = S2 - Y1 have their lifted subtraction folded into the reduction of the product
+// (Fq29::sqr_sub_np / mul_sub_np: K - x joins the columns in front of the output carry chain; values as before).
 //
 // The isomorphic curve E'.  The caller's bases are canonical E = x R mod p with R = 2^256; the limbs of E << 3 and of
 // E << 2 (Fq29::unpack256_shl, pure slicing) stand, with rho = 2^261, for x' = x / 4 and y' = y / 8.  (x, y) ->
@@ -202,16 +206,16 @@ MSM_HD PtI pti_double(const PtI& p) {   // p not the identity
 // Pins (pin_limbs, bn254_fq29.hip.h) are set ONCE per basic block and the pinned value replaces the old one -- p.zz and
 // p.zzz in the head (hence the non-const p), everything the long block of the tail reads at its top -- and the
 // multiplications inside run without pins of their own.
-MSM_HD void pti_madd_head(PtI& p, const fe29& qx, const fe29& qy, fe29& U2, fe29& S2) {
+// The head returns P = U2 - X1 and R = S2 - Y1 themselves: the lifted subtractions ride on the reductions of U2 and S2
+// (Fq29::mul_sub_np), so P and R come back with exact 29-bit limbs and no carry round of their own.
+MSM_HD void pti_madd_head(PtI& p, const fe29& qx, const fe29& qy, fe29& P0, fe29& R0) {
   p.zz = pin_limbs(p.zz);
   p.zzz = pin_limbs(p.zzz);
-  U2 = Fq29::mul_np(pin_limbs(qx), p.zz);
-  S2 = Fq29::mul_np(pin_limbs(qy), p.zzz);
+  P0 = Fq29::mul_sub_np<K16E30>(pin_limbs(qx), p.zz, p.x);    // U2 - X1 + 16 p   < 17.1 p
+  R0 = Fq29::mul_sub_np<K8E30>(pin_limbs(qy), p.zzz, p.y);    // S2 - Y1 +  8 p   <  9.1 p
 }
 template <class ReloadQ>
-MSM_HD PtI pti_madd_tail(const PtI& p, const fe29& U2, const fe29& S2, ReloadQ&& reload_q, bool& vanished) {
-  const fe29 P0 = Fq29::norm(Fq29::sub<K16E30>(U2, p.x));   // < 17.1 p
-  const fe29 R0 = Fq29::norm(Fq29::sub<K8E30>(S2, p.y));    // <  9.1 p
+MSM_HD PtI pti_madd_tail(const PtI& p, const fe29& P0, const fe29& R0, ReloadQ&& reload_q, bool& vanished) {
   if (Fq29::maybe_zero(P0, kZeroFilterMadd)) {
     MSM_ISA_MARK("rare mixed_addition");
     if (Fq29::is_zero_exact(P0)) {   // same x: either q == p (double) or q == -p (identity)
@@ -227,8 +231,7 @@ MSM_HD PtI pti_madd_tail(const PtI& p, const fe29& U2, const fe29& S2, ReloadQ&&
   const fe29 PP = Fq29::sqr_np(P);
   const fe29 PPP = Fq29::mul_np(P, PP);
   const fe29 Q = Fq29::mul_np(X1, PP);
-  const fe29 RR = Fq29::sqr_np(R);
-  r.x = Fq29::norm(Fq29::sub<K8E31>(RR, Fq29::add(PPP, Fq29::add(Q, Q))));               // < 9.5 p
+  r.x = Fq29::sqr_sub_np<K8E31>(R, Fq29::add(PPP, Fq29::add(Q, Q)));    // R^2 - PPP - 2 Q   // < 9.5 p
   // T and -PPP stay un-normalised (limbs < 2^31 / 2^30.5): their partners R and Y1 in the double product are
   // normalised, and tools/fq29_bounds.py checks that no column of R*T + Y1*(-PPP) can reach 2^64
   const fe29 T = Fq29::sub<K16E30>(Q, r.x);                                               // < 17.2 p
@@ -264,9 +267,8 @@ MSM_HD PtI pti_mmadd_tail(const fe29& px, const fe29& py, const fe29& P, const f
   const fe29 PP = Fq29::sqr_np(Pp);
   const fe29 PPP = Fq29::mul_np(Pp, PP);
   const fe29 Q = Fq29::mul_np(X1, PP);
-  const fe29 RR = Fq29::sqr_np(Rp);
   PtI r;
-  r.x = Fq29::norm(Fq29::sub<K8E31>(RR, Fq29::add(PPP, Fq29::add(Q, Q))));               // < 9.9 p (E': 11.4 p)
+  r.x = Fq29::sqr_sub_np<K8E31>(Rp, Fq29::add(PPP, Fq29::add(Q, Q)));   // R^2 - PPP - 2 Q   // < 9.9 p (E': 11.4 p)
   const fe29 T = Fq29::norm(Fq29::sub<K16E30>(Q, r.x));                                   // < 17.2 p
   r.y = Fq29::mul2_np(Rp, T, Y1, Fq29::neg_wide(PPP));   // R*T - Y1*PPP in one reduction      // < 1.2 p
   r.zz = PP;                                                                              // < 2.8 p (E': 3.4 p)
@@ -282,10 +284,10 @@ MSM_HD PtI pti_madd(const PtI& p, const AffI& q, bool& vanished) {
   const fe29 U2 = Fq29::mul_karatsuba(q.x, p.zz);
   const fe29 S2 = Fq29::mul_karatsuba(q.y, p.zzz);
 #else
-  fe29 U2, S2;
+  fe29 P0, R0;
   PtI pp = p;
-  pti_madd_head(pp, q.x, q.y, U2, S2);
-  return pti_madd_tail(pp, U2, S2, [&]() { return q; }, vanished);
+  pti_madd_head(pp, q.x, q.y, P0, R0);
+  return pti_madd_tail(pp, P0, R0, [&]() { return q; }, vanished);
 #endif
 #if defined(MSM_AMD_EXPERIMENTS) && (defined(MSM_FQ29_LOCKSTEP) || defined(MSM_FQ29_KARATSUBA))
   const fe29 P = Fq29::norm(Fq29::sub<K16E30>(U2, p.x));   // < 17.1 p
@@ -378,9 +380,8 @@ MSM_HD PtI pti_add_nz(const PtI& p_in, const PtI& q_in, bool& vanished) {
   const fe29 V = Fq29::mul_np(ZZ2, PP);
   const fe29 Tz = Fq29::mul_np(ZZZ2, PPP);
   const fe29 Q = Fq29::mul_np(X1, V);
-  const fe29 RR = Fq29::sqr_np(R);
   PtI r;
-  r.x = Fq29::norm(Fq29::sub<K8E31>(RR, Fq29::add(PPP, Fq29::add(Q, Q))));               // < 9.01 p
+  r.x = Fq29::sqr_sub_np<K8E31>(R, Fq29::add(PPP, Fq29::add(Q, Q)));    // R^2 - PPP - 2 Q   // < 9.01 p
   const fe29 T = Fq29::sub<K16E30>(Q, r.x);      // un-normalised, like -Tz (see pti_madd)    // < 17.1 p
   r.y = Fq29::mul2_np(R, T, Y1, Fq29::neg_wide(Tz));     // R*T - Y1*Tz in one reduction       // < 1.26 p
   r.zz = Fq29::mul_np(ZZ1, V);

@@ -27,6 +27,9 @@
 //   sub<K>(a, b)     : b limbs <= lift(K) - 2^(e-29), b value within the top-limb headroom of K;
 //                      result = a - b + k*p, limbs < 2^32 -- NOT a valid mul operand until norm()
 //   norm(a)          : limbs 0..7 < 2^29 + 8, value unchanged
+//   mul_sub_np<K>(a, b, x), sqr_sub_np<K>(a, x) : a, b mul operands, x as sub<K>'s b; the value of
+//                      norm(sub<K>(mul_np(a, b), x)) with limbs 0..7 < 2^29 exactly, limb 8 = carry + K[8] - x[8]:
+//                      the difference K - x joins the reduced columns in front of the output carry chain
 #pragma once
 #include "bn254_fq.hip.h"
 
@@ -195,8 +198,21 @@ struct Fq29 {
 #endif
     return eight;
   }
-  template <bool WIDE = false, bool FRIENDLY = FRIENDLY_DEFAULT>
-  MSM_HD static fe29 reduce_columns(uint64_t (&A)[17]) {
+  // 1 the same way: limb * 1 + A is ONE multiply-add on the 64-bit column, where a plain 64-bit addition of a 32-bit
+  // limb costs a move for its zero upper half on top (reduce_columns' additive tail).
+  MSM_HD static uint32_t unit_factor() {
+    uint32_t one = 1;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+s"(one));
+#endif
+    return one;
+  }
+  // TAIL: the additive tail d (9 limbs, each below 2^32; the lifted difference K - x of mul_sub_np / sqr_sub_np) joins
+  // the reduced columns in front of the output carry chain: d[0..7] go to columns 9..16, which no quotient digit reads,
+  // and d[8] to the top limb.  The chain that runs anyway normalises the sum: the result is the value of the reduction
+  // plus value(d), limbs 0..7 < 2^29 exactly, limb 8 = the last carry + d[8].
+  template <bool WIDE = false, bool FRIENDLY = FRIENDLY_DEFAULT, bool TAIL = false>
+  MSM_HD static fe29 reduce_columns(uint64_t (&A)[17], const fe29* d = nullptr) {
     uint64_t carry = 0;
     MSM_UNROLL for (int k = 0; k < 9; ++k) {
       if (FRIENDLY && k < FRIENDLY_DIGITS) {
@@ -216,13 +232,16 @@ struct Fq29 {
       MSM_UNROLL for (int j = 0; j < 9; ++j) A[k + j] += (uint64_t)m * p(j);
       carry = A[k] >> 29;
     }
+    if (TAIL) {
+      MSM_UNROLL for (int k = 9; k < 17; ++k) A[k] += (uint64_t)d->l[k - 9] * unit_factor();
+    }
     fe29 r;
     MSM_UNROLL for (int k = 9; k < 17; ++k) {
       A[k] += carry;
       r.l[k - 9] = (uint32_t)A[k] & MASK;
       carry = A[k] >> 29;
     }
-    r.l[8] = (uint32_t)carry;
+    r.l[8] = TAIL ? (uint32_t)carry + d->l[8] : (uint32_t)carry;
     return r;
   }
 
@@ -248,6 +267,11 @@ struct Fq29 {
     }
 #endif
     uint64_t A[17];
+    mul_columns(a, b, A);
+    return reduce_columns<WIDE>(A);
+  }
+  // the 17 column sums of a * b
+  MSM_HD static void mul_columns(const fe29& a, const fe29& b, uint64_t (&A)[17]) {
     MSM_UNROLL for (int k = 0; k < 17; ++k) {
       uint64_t s = 0;
       MSM_UNROLL for (int i = 0; i < 9; ++i) {
@@ -256,7 +280,6 @@ struct Fq29 {
       }
       A[k] = s;
     }
-    return reduce_columns<WIDE>(A);
   }
 
   // (a*b + c*d)*rho^-1 with ONE Montgomery reduction: 81 + 81 + 81 limb products instead of 2 x (81 + 81).
@@ -301,9 +324,14 @@ struct Fq29 {
       return fips<1, true>(xs, ys);
     }
 #endif
+    uint64_t A[17];
+    sqr_columns(a, A);
+    return reduce_columns<WIDE>(A);
+  }
+  // the 17 column sums of a * a
+  MSM_HD static void sqr_columns(const fe29& a, uint64_t (&A)[17]) {
     uint32_t d[9];
     MSM_UNROLL for (int i = 0; i < 9; ++i) d[i] = a.l[i] << 1;   // operand limbs <= 2^30 + 2^8 -> < 2^32
-    uint64_t A[17];
     MSM_UNROLL for (int k = 0; k < 17; ++k) {
       uint64_t s = 0;
       MSM_UNROLL for (int i = 0; i < 9; ++i) {
@@ -313,7 +341,6 @@ struct Fq29 {
       if ((k & 1) == 0) s += (uint64_t)a.l[k >> 1] * a.l[k >> 1];
       A[k] = s;
     }
-    return reduce_columns<WIDE>(A);
   }
   // The point additions' forms: no pins, wide quotient digits (reduce_columns<true>).  mul2_np keeps the masked
   // digits: with wide ones a column of the Y3 double product R*T - Y1*PPP (T un-normalised) could reach 2^65.
@@ -323,6 +350,33 @@ struct Fq29 {
   MSM_HD static fe29 mul2_np(const fe29& a, const fe29& b, const fe29& c, const fe29& d) { return mul2<false>(a, b, c, d); }
   MSM_HD static fe29 mul2w_np(const fe29& a, const fe29& b, const fe29& c, const fe29& d) {
     return mul2<false, true>(a, b, c, d);
+  }
+  // a product with the lifted subtraction folded into its reduction (reduce_columns' additive tail):
+  //   mul_sub_np<K>(a, b, x) = a b / rho + K - x,   sqr_sub_np<K>(a, x) = a^2 / rho + K - x.
+  // Value: that of norm(sub<K>(mul_np(a, b), x)).  Limbs 0..7 < 2^29 exactly (norm leaves 2^29 + 8), limb 8 = the
+  // carry + K[8] - x[8].  x obeys sub<K>'s operand contract; no pins, wide digits.  The 18 instructions of the lifted
+  // subtraction and norm's second carry round (26) become 9 subtractions from a literal and 8 multiply-adds.
+  template <int SEL>
+  MSM_HD static fe29 mul_sub_np(const fe29& a, const fe29& b, const fe29& x) {
+#if defined(MSM_AMD_EXPERIMENTS) && defined(MSM_FQ29_FIPS)
+    return norm(sub<SEL>(mul_np(a, b), x));
+#endif
+    fe29 d;
+    MSM_UNROLL for (int i = 0; i < 9; ++i) d.l[i] = kc(SEL, i) - x.l[i];
+    uint64_t A[17];
+    mul_columns(a, b, A);
+    return reduce_columns<true, FRIENDLY_DEFAULT, true>(A, &d);
+  }
+  template <int SEL>
+  MSM_HD static fe29 sqr_sub_np(const fe29& a, const fe29& x) {
+#if defined(MSM_AMD_EXPERIMENTS) && defined(MSM_FQ29_FIPS)
+    return norm(sub<SEL>(sqr_np(a), x));
+#endif
+    fe29 d;
+    MSM_UNROLL for (int i = 0; i < 9; ++i) d.l[i] = kc(SEL, i) - x.l[i];
+    uint64_t A[17];
+    sqr_columns(a, A);
+    return reduce_columns<true, FRIENDLY_DEFAULT, true>(A, &d);
   }
 
   // 256-bit little-endian integer -> 9 x 29-bit limbs (pure bit slicing, value unchanged).

@@ -143,9 +143,9 @@ accumulate_item(const uint32_t slot, const typename B::Rec* __restrict__ bases, 
       if (take(cur)) continue;
       MSM_ISA_MARK("begin mixed_addition");
       bool vanished = false;
-      fe29 U2, S2;
-      pti_madd_head(acc, cur.x, cur.y, U2, S2);   // cur dies here: its pins cost no copies
-      acc = pti_madd_tail(acc, U2, S2, [&]() { return regather(this_idx); }, vanished);
+      fe29 P0, R0;
+      pti_madd_head(acc, cur.x, cur.y, P0, R0);   // cur dies here: its pins cost no copies
+      acc = pti_madd_tail(acc, P0, R0, [&]() { return regather(this_idx); }, vanished);
       MSM_ISA_MARK("end");
       if (vanished) {
         state = kEmpty;

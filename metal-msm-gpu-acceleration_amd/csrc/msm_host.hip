@@ -3136,7 +3136,7 @@ int msm_amd_test_op_host(int op, const uint32_t* a, const uint32_t* b, uint32_t*
 static bool test_op_raw_args(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
   return a && b && out && count > 0 && count <= (1u << 24) && op >= 0 &&
          (op < kRawOpCount || (op >= kRawWideFirst && op < kRawWideFirst + kRawWideCount) || op == MSM_AMD_RAW_FE_SQRT ||
-          op == MSM_AMD_RAW_BASES_IN_PLACE);
+          op == MSM_AMD_RAW_BASES_IN_PLACE || (op >= kRawFoldFirst && op < kRawFoldFirst + kRawFoldCount));
 }
 
 int msm_amd_test_op_raw(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {

@@ -146,8 +146,21 @@ MSM_HD void run_test_op(int op, const u256* a, const u256* b, u256* out, uint32_
 // ---- raw-limb ops (msm_amd_test_op_raw / _host, MSM_AMD_RAW_*): the internal limbs go in and come out exactly as
 // given, so that a test can put operands at the edges of the bounds contract and see result limbs, not only values.
 // Record of element t: a, b = kRawInWords u32 from t * kRawInWords, out = kRawOutWords u32 from t * kRawOutWords.
-// Ops 0..kRawOpCount-1, and kRawWideFirst.. (the wide-digit multiplication forms of the point additions).
-constexpr int kRawInWords = 36, kRawOutWords = 40, kRawOpCount = 20, kRawWideFirst = 32, kRawWideCount = 3;
+// Ops 0..kRawOpCount-1, kRawWideFirst.. (the wide-digit multiplication forms of the point additions) and kRawFoldFirst..
+// (the same with the lifted subtraction folded into the reduction).
+constexpr int kRawInWords = 36, kRawOutWords = 40, kRawOpCount = 20, kRawWideFirst = 32, kRawWideCount = 3,
+              kRawFoldFirst = 44, kRawFoldCount = 2;
+
+// mul_sub_np<K> / sqr_sub_np<K> (a = nullptr: the squaring of b) with K chosen at run time, for the raw ops
+MSM_HD fe29 raw_fold(uint32_t sel, const fe29* a, const fe29& b, const fe29& x) {
+  switch (sel) {
+#define MSM_RAW_FOLD(K) case K: return a ? Fq29::mul_sub_np<K>(*a, b, x) : Fq29::sqr_sub_np<K>(b, x);
+    MSM_RAW_FOLD(K4E30) MSM_RAW_FOLD(K8E30) MSM_RAW_FOLD(K8E31) MSM_RAW_FOLD(K16E30) MSM_RAW_FOLD(K16E31)
+    MSM_RAW_FOLD(K12E30)
+#undef MSM_RAW_FOLD
+  }
+  return Fq29::zero();
+}
 
 MSM_HD fe29 raw_fe(const uint32_t* w) {
   fe29 r;
@@ -277,6 +290,12 @@ MSM_HD void run_test_op_raw(int op, const uint32_t* a_all, const uint32_t* b_all
       r[36] = vanished ? 1u : 0u;
       break;
     }
+    case 44: {                                                                    // FE_MUL_SUB: K = b1.l[0]
+      const fe29 pa = pin_limbs(a0);
+      raw_put_fe(r, raw_fold(b1.l[0], &pa, pin_limbs(a1), b0));
+      break;
+    }
+    case 45: raw_put_fe(r, raw_fold(b1.l[0], nullptr, pin_limbs(a0), b0)); break;   // FE_SQR_SUB
   }
   MSM_UNROLL for (int i = 0; i < kRawOutWords; ++i) out[i] = r[i];
 }

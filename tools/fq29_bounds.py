@@ -4,8 +4,8 @@ bn254_ec29.hip.h).
 The hot kernels never propagate carries between field operations: limbs are only BOUNDED, and a 64-bit column sum
 of a multiplication that overflowed would be silent.  This script re-states the group-law formulas over intervals
 (per-limb maxima, value bound in multiples of p) and checks, for every multiplication, squaring and double
-product, that no column of products + Montgomery terms + carries can reach 2^64, that no lifted subtraction can
-go negative in any limb, that no limb leaves 32 bits, that the one-limb zero filters are given a large enough
+product, that no column of products + Montgomery terms + carries (+ the additive tail K - x where the lifted subtraction
+is folded into the reduction: mul_sub_np / sqr_sub_np) can reach 2^64, that no lifted subtraction can go negative in any limb, that no limb leaves 32 bits, that the one-limb zero filters are given a large enough
 bound, and that every point an addition returns satisfies the invariant the next addition assumes
 (X < 10 p, Y < 6 p, ZZ < 2.8 p, ZZZ < 2 p, limbs 0..7 < 2^29 + 8).  Run: python tools/fq29_bounds.py  (exit 0 = all hold).
 The constants are read from the header, the formulas below mirror bn254_ec29.hip.h line by line -- when one
@@ -91,9 +91,10 @@ assert EXTRA[True] < 2.0 ** -24 and EXTRA[False] < 2.0 ** -27, EXTRA
 WIDE_EXTRA = EXTRA[True]
 
 
-def _reduce(cols, what, wide=False):
+def _reduce(cols, what, wide=False, tail=None):
     """Montgomery reduction of worst-case column sums (every step is monotone in the columns, so every digit and every
-    carry at its maximum bounds them all); returns the worst-case top limb (final carry)."""
+    carry at its maximum bounds them all); returns the worst-case top limb (final carry).  tail: the limb maxima of
+    reduce_columns' additive tail; limbs 0..7 join columns 9..16 in front of the output carry chain."""
     A = list(cols) + [0] * (17 - len(cols))
     carry = 0
     for k in range(9):
@@ -110,6 +111,9 @@ def _reduce(cols, what, wide=False):
         if A[k] >= 1 << 64:
             fail(f"{what}: column {k} can reach 2^{A[k].bit_length()} during the reduction")
         carry = A[k] >> 29
+    if tail is not None:
+        for k in range(9, 17):
+            A[k] += tail[k - 9]
     for k in range(9, 17):
         A[k] += carry
         if A[k] >= 1 << 64:
@@ -136,6 +140,47 @@ def _out(pairs, name, what, wide=False):
     val = sum(a.val * b.val for a, b in pairs) * P / RHO + 1.0 + EXTRA[wide]
     top = min(carry, top_from_value(val))
     return Fe([MASK] * 8 + [top], val, name)
+
+
+def _out_sub(pairs, sel, x, name, what):
+    """The forms with the lifted subtraction folded into the reduction (Fq29::mul_sub_np, sqr_sub_np: wide digits):
+    d = K - x limb by limb, x under sub<K>'s operand contract (so no limb of d goes negative and every one stays below
+    2^32); d[0..7] join columns 9..16, d[8] the top limb.  Checked: the columns with the injected term (< 2^64), the
+    top limb carry + K[8] - x[8] (not negative: x[8] <= K[8]; inside 32 bits).  The output carry chain leaves limbs
+    0..7 below 2^29 exactly, so the top limb is also the value's own: floor(value / 2^232)."""
+    K = KL[sel]
+    for a, b in pairs:
+        for f in (a, b):
+            if max(f.mx) >= 1 << 32:
+                fail(f"{what}: operand {f.name} has a limb beyond 32 bits")
+    for i in range(9):
+        if x.mx[i] > K[i]:
+            fail(f"{what}: limb {i} of the subtrahend {x.name} may exceed the lift of {sel} ({x.mx[i]:#x} > {K[i]:#x})")
+    if x.val > KMULT[sel]:
+        fail(f"{what}: subtrahend value {x.val:.2f}p above the {KMULT[sel]}p of {sel}")
+    d = list(K)                                  # the largest K - x: x = 0
+    if max(d) >= 1 << 32:
+        fail(f"{what}: a limb of {sel} - {x.name} leaves 32 bits")
+    carry = _reduce(_mul_cols(pairs), what + " (wide digits, additive tail)", True, d)
+    if carry + d[8] >= 1 << 32:
+        fail(f"{what}: the top limb carry + K[8] - x[8] may leave 32 bits")
+    val = sum(a.val * b.val for a, b in pairs) * P / RHO + 1.0 + EXTRA[True] + KMULT[sel]
+    top = min(carry + d[8], top_from_value(val))
+    folds.add(what)
+    return Fe([MASK] * 8 + [top], val, name)
+
+
+folds = set()                                    # every folded subtraction the formulas below use (main() counts them)
+
+
+def mul_sub(sel, a, b, x, name):
+    return _out_sub([(a, b)], sel, x, name, f"mul_sub<{sel}> {name} = {a.name} * {b.name} - {x.name}")
+
+
+def sqr_sub(sel, a, x, name):
+    if max(a.mx) * 2 >= 1 << 32:
+        fail(f"sqr_sub {name}: doubled limb of {a.name} leaves 32 bits")
+    return _out_sub([(a, a)], sel, x, name, f"sqr_sub<{sel}> {name} = {a.name}^2 - {x.name}")
 
 
 # wide=True: the forms with wide quotient digits (Fq29::mul_np, sqr_np, mul2w_np; mul2_np is masked)
@@ -318,16 +363,14 @@ def pti_madd(bases=PACKED):
     where = "pti_madd" + bases.tag
     px, py, pzz, pzzz = general_point(bases.inv)
     qx, qy = bases.x("x2"), bases.negated_y()
-    U2 = mul(qx, pzz, "U2", WD)
-    S2 = mul(qy, pzzz, "S2", WD)
-    Pd = norm(sub("K16E30", U2, px, "P"), "P")
-    R = norm(sub("K8E30", S2, py, "R"), "R")
+    U2 = mul(qx, pzz, "U2", WD)                              # the figure only: the head folds X1 and Y1 in
+    Pd = mul_sub("K16E30", qx, pzz, px, "P")                 # pti_madd_head: U2 - X1, S2 - Y1 in the reductions
+    R = mul_sub("K8E30", qy, pzzz, py, "R")
     maybe_zero(Pd, "kZeroFilterMadd")
     PP = sqr(Pd, "PP", WD)
     PPP = mul(Pd, PP, "PPP", WD)
     Q = mul(px, PP, "Q", WD)
-    RR = sqr(R, "RR", WD)
-    X3 = norm(sub("K8E31", RR, add(PPP, add(Q, Q)), "X3"), "X3")
+    X3 = sqr_sub("K8E31", R, add(PPP, add(Q, Q)), "X3")      # R^2 - PPP - 2 Q in the reduction of R^2
     T = sub("K16E30", Q, X3, "T")                            # un-normalised: its partner R is normalised
     Y3 = mul2(R, T, py, neg_wide(PPP, "-PPP"), "Y3")          # mul2_np: masked digits
     ZZ3 = mul(pzz, PP, "ZZ3", WD)
@@ -351,8 +394,7 @@ def pti_mmadd(bases=PACKED):
     PP = sqr(Pd, "PP", WD)
     PPP = mul(Pd, PP, "PPP", WD)
     Q = mul(px, PP, "Q", WD)
-    RR = sqr(R, "RR", WD)
-    X3 = norm(sub("K8E31", RR, add(PPP, add(Q, Q)), "X3"), "X3")
+    X3 = sqr_sub("K8E31", R, add(PPP, add(Q, Q)), "X3")
     T = norm(sub("K16E30", Q, X3, "T"), "T")
     Y3 = mul2(R, T, py, neg_wide(PPP, "-PPP"), "Y3")
     check_point(X3, Y3, PP, PPP, where, bases.inv)
@@ -380,8 +422,7 @@ def pti_add_nz(inv=INV_E):
     V = mul(qzz, PP, "V", WD)
     Tz = mul(qzzz, PPP, "Tz", WD)
     Q = mul(px, V, "Q", WD)
-    RR = sqr(R, "RR", WD)
-    X3 = norm(sub("K8E31", RR, add(PPP, add(Q, Q)), "X3"), "X3")
+    X3 = sqr_sub("K8E31", R, add(PPP, add(Q, Q)), "X3")
     T = sub("K16E30", Q, X3, "T")
     Y3 = mul2(R, T, py, neg_wide(Tz, "-Tz"), "Y3")            # mul2_np: masked digits
     ZZ3 = mul(pzz, V, "ZZ3", WD)
@@ -463,6 +504,11 @@ def contracts():
         out["mul" + tag] = mul(lazy, lazy, "lazy*lazy" + tag, wide)
         out["sqr" + tag] = sqr(lazy, "lazy^2" + tag, wide)
     out["mul2 (Fq2)"] = mul2(g2, g2, g2, g2, "Fq2 double product")
+    # the folded forms at the same operand limit, the subtrahend anywhere under sub<K>'s contract (the tail is K - 0)
+    for sel in KNAMES:
+        x = Fe(KL[sel], KMULT[sel], "x")
+        out[f"mul_sub<{sel}>"] = mul_sub(sel, lazy, lazy, x, f"lazy*lazy-x ({sel})")
+        out[f"sqr_sub<{sel}>"] = sqr_sub(sel, lazy, x, f"lazy^2-x ({sel})")
     return out
 
 
@@ -476,6 +522,8 @@ def main(verbose=False):
     mul_points()
     for site in sorted(derived_filters):
         print(f"zero filter {site}: needs {derived_filters[site]}, the header has {FILTERS.get(site)}")
+    print(f"folded subtractions (mul_sub_np / sqr_sub_np): {len(folds)} uses, every one with wide digits, columns < 2^64 "
+          f"with the tail, top limb inside 32 bits")
     if verbose:
         for where, fs in figures.items():
             print(where + ": " + ", ".join(f"{k} < {v.val:.2f} p" for k, v in fs.items()))
