@@ -225,6 +225,64 @@ int msm_amd_submit_batch_device(msm_amd_ctx* ctx, int scalar_layout, int point_l
                                 void* out_host, int* ticket);
 int msm_amd_wait_batch(msm_amd_ctx* ctx, int ticket);
 
+/* ---- scalars of bounded width ------------------------------------------------------------------
+ * Witness vectors, lookup multiplicities, selector columns and folding challenges are short: bits, bytes, 32 / 64-bit
+ * words, 128-bit challenges, and "small negatives" r - k.  A bounded call plans for `bits` bits instead of 254:
+ * bits / c + 1 digit windows are extracted, sorted, accumulated and reduced, and the window is the one measured for that
+ * width (msm_amd_auto_window_size_bounded).
+ * Value and sign: the value of a record is its residue s mod r (MSM_AMD_SCALAR_MONT_LE records are de-Montgomeryed,
+ * raw MSM_AMD_SCALAR_CANON_* words reduced first, as everywhere).  MSM_AMD_WIDTH_UNSIGNED: the magnitude is s.
+ * MSM_AMD_WIDTH_SIGNED: the magnitude is min(s, r - s) and the record counts as negative when s > (r - 1) / 2 (its
+ * point is subtracted).  bits: 1..254 unsigned, 1..253 signed (a signed bound of 253 takes every residue); anything
+ * else, or another sign, is MSM_AMD_INPUT_ERROR.
+ * Contract: the result is the group element, and so the bytes, of the unbounded call on the same inputs.  A record whose
+ * magnitude is 2^bits or more makes the call return MSM_AMD_INPUT_ERROR after its GPU work: msm_amd_last_error gives the
+ * number of such records and the index of the first of them (and the instance, for a batch; for a call the library cut
+ * into point ranges the count is that of the first violating range), the output is left untouched and the ctx stays
+ * usable -- a wrong result is never returned.  A bound of 254 unsigned is the unbounded call.
+ * What it buys (one MI355X, profiles/bounded_bench.json): every width from 8 to 128 bits is faster than the unbounded call
+ * on the same scalars at 2^16, 2^20 and 2^22 points, 8-bit values 5 - 12x from 2^20 points, +-small values up to 18x.
+ * Scalars of ONE or two bits are the exception: every point lands in the same bucket, which is cut into thousands of
+ * work items and summed by the combine pass, and from 2^20 points the unbounded call (whose other windows keep the
+ * work items long) is up to 2.4x faster -- keep boolean vectors on msm_amd_msm* (DESIGN.md section 8.10). */
+enum { MSM_AMD_WIDTH_UNSIGNED = 0, MSM_AMD_WIDTH_SIGNED = 1 };
+/* The width of a vector: *bits = the largest bit length of a magnitude (0 for an all-zero vector and for n == 0);
+ * stats (optional, 4 words): zero records, negative records (signed only), the lowest index of a widest record, 0.
+ * Scalars: MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE, host memory / device memory (_device), n < 2^32.  One
+ * pass over the records and a fold of per-wave partials; a blocking call like the Fr vector calls.  Scan a circuit's
+ * witness once, then commit with msm_amd_msm_bounded_device at that width. */
+int msm_amd_scalar_width(msm_amd_ctx* ctx, int scalar_layout, const void* scalars, size_t n, int sign, uint32_t* bits,
+                         uint64_t stats[4]);
+int msm_amd_scalar_width_device(msm_amd_ctx* ctx, int scalar_layout, const void* d_scalars, size_t n, int sign,
+                                uint32_t* bits, uint64_t stats[4]);
+/* Host twin (no ctx, no GPU); threads <= 0: up to 16 host threads. */
+int msm_amd_host_scalar_width(int scalar_layout, const void* scalars, size_t n, int sign, int threads, uint32_t* bits,
+                              uint64_t stats[4]);
+/* msm_amd_msm / msm_amd_msm_device / msm_amd_msm_batch_device / msm_amd_submit_batch_device at a bounded width; every
+ * point layout of the unbounded form, MSM_AMD_POINT_PREPARED and MSM_AMD_POINT_TABLES included (a table is used through
+ * its first bits / c + 1 windows, at the table's c).  One bits / sign for a whole batch; a ticket is collected by
+ * msm_amd_wait_batch, which reports a violated bound. */
+int msm_amd_msm_bounded(msm_amd_ctx* ctx, int scalar_layout, int point_layout, const void* scalars, const void* points,
+                        size_t n, uint32_t bits, int sign, void* out96);
+int msm_amd_msm_bounded_device(msm_amd_ctx* ctx, int scalar_layout, int point_layout, const void* d_scalars,
+                               const void* d_points, size_t n, uint32_t bits, int sign, void* out96_host);
+int msm_amd_msm_batch_bounded_device(msm_amd_ctx* ctx, int scalar_layout, int point_layout, size_t n_inst,
+                                     const void* const* d_scalars, const void* const* d_points, const size_t* n,
+                                     uint32_t bits, int sign, void* out_host);
+int msm_amd_submit_batch_bounded_device(msm_amd_ctx* ctx, int scalar_layout, int point_layout, size_t n_inst,
+                                        const void* const* d_scalars, const void* const* d_points, const size_t* n,
+                                        uint32_t bits, int sign, void* out_host, int* ticket);
+/* The CPU MSM at that width (msm_amd_host_msm): MSM_AMD_INPUT_ERROR, output untouched, for a record beyond the bound. */
+int msm_amd_host_msm_bounded(int scalar_layout, int point_layout, const void* scalars, const void* points, size_t n,
+                             uint32_t bits, int sign, int threads, void* out96);
+/* The window a bounded call of n points uses (lone != 0: one instance with nothing else in flight); bits = 254 gives
+ * msm_amd_auto_window_size / msm_amd_auto_window_size_lone.  msm_amd_set_window_size overrides it.  Measured on MI355X
+ * from 2^16 to 2^22 points (profiles/bounded_sweep.txt): up to 16 bits ONE window that holds the whole scalar
+ * (c = bits + 1); above, the fewest windows whose top digit is wide enough that no bucket outgrows a work item (32 and 64
+ * bits: c = 17; 128 bits: c = 10 from 2^19 points), and c <= 13 for instances up to 2^18 points that need four windows
+ * or more or run pipelined at 2^16.  Below 2^15 points: the window of the unbounded call. */
+uint32_t msm_amd_auto_window_size_bounded(size_t n, uint32_t bits, int lone);
+
 /* Upper bound of every host wait for the GPU inside the library, in milliseconds (default 60 000, or the environment
  * variable MSM_AMD_WAIT_TIMEOUT_MS at msm_amd_init; 0 = wait without bound).  The reference's gpu_msm_h2c_sync is one
  * blocking call that always returns (msm.rs:237-349); so is every call here: a wait that reaches the bound returns
@@ -597,6 +655,13 @@ int msm_amd_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, con
 int msm_amd_msm_g2_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars,
                           const void* d_points, size_t n, void* out192);
 
+/* The two calls above at a bounded width ("scalars of bounded width" above: bits, sign, the contract and the error of a
+ * violated bound); the device form takes MSM_AMD_G2_POINT_PREPARED and MSM_AMD_G2_POINT_TABLES as well. */
+int msm_amd_msm_g2_bounded(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars,
+                           const void* points, size_t n, uint32_t bits, int sign, void* out192);
+int msm_amd_msm_g2_bounded_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars,
+                                  const void* d_points, size_t n, uint32_t bits, int sign, void* out192);
+
 /* Persistent G2 bases (the G2 query of a Groth16 proving key is set once and multiplied by a fresh witness per proof):
  * msm_amd_bases_upload / _prepare_device / msm_amd_msm_prepared on G2.  The points (a host layout) are converted once
  * into 128-byte internal records resident on the device; free a prepared array with msm_amd_device_free.  Results are
@@ -629,6 +694,9 @@ int msm_amd_msm_g2_tables(msm_amd_ctx* ctx, const msm_amd_g2_tables* tables, int
  * host threads.  Same layouts and result form as msm_amd_msm_g2. */
 int msm_amd_host_msm_g2(int scalar_layout, int g2_point_layout, const void* scalars, const void* points, size_t n,
                         int threads, void* out192);
+/* ... at a bounded width: MSM_AMD_INPUT_ERROR, output untouched, for a record beyond the bound. */
+int msm_amd_host_msm_g2_bounded(int scalar_layout, int g2_point_layout, const void* scalars, const void* points, size_t n,
+                                uint32_t bits, int sign, int threads, void* out192);
 /* Test aid: out[i] = start + i * step for i < n, MSM_AMD_G2_POINT_H2C_AFFINE records (host code, threads <= 0: up to
  * 16 host threads). */
 int msm_amd_test_g2_progression(const void* start128, const void* step128, size_t n, int threads, void* out);

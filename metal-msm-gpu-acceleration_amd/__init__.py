@@ -58,6 +58,7 @@ NTT_FORWARD, NTT_INVERSE = 0, 1
 FR_ADD, FR_SUB, FR_MUL, FR_SCALE, FR_AXPY, FR_MULSUB_SCALE = range(6)
 FR_PREFIX_INCLUSIVE, FR_PREFIX_EXCLUSIVE = 0, 1
 MLE_LOW, MLE_HIGH = 0, 1
+WIDTH_UNSIGNED, WIDTH_SIGNED = 0, 1
 SUMCHECK_PRODUCT, SUMCHECK_EQ_AB_C = 0, 1
 MLE_CALL_BIND, MLE_CALL_EVAL, MLE_CALL_EQ_TABLE, MLE_CALL_ROUND = range(4)
 
@@ -127,6 +128,10 @@ EXPORTS = [
     "msm_amd_fr_eq_table", "msm_amd_fr_eq_table_device", "msm_amd_host_fr_eq_table",
     "msm_amd_fr_sumcheck_round", "msm_amd_fr_sumcheck_round_device", "msm_amd_host_fr_sumcheck_round",
     "msm_amd_test_fr_mle_plan",
+    "msm_amd_scalar_width", "msm_amd_scalar_width_device", "msm_amd_host_scalar_width",
+    "msm_amd_msm_bounded", "msm_amd_msm_bounded_device", "msm_amd_msm_batch_bounded_device",
+    "msm_amd_submit_batch_bounded_device", "msm_amd_msm_g2_bounded", "msm_amd_msm_g2_bounded_device",
+    "msm_amd_host_msm_bounded", "msm_amd_host_msm_g2_bounded", "msm_amd_auto_window_size_bounded",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -420,6 +425,21 @@ def _lib():
                                                POINTER(c_uint64)]
         L.msm_amd_generate_instance_host.argtypes = [c_uint64, c_size_t, c_int, c_void_p, c_void_p, c_int]
         L.msm_amd_test_op_ifma.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
+        if hasattr(L, "msm_amd_scalar_width"):   # (an MSM_AMD_LIB build from before the bounded-width calls still loads)
+            L.msm_amd_scalar_width.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_int, POINTER(c_uint32), POINTER(c_uint64)]
+            L.msm_amd_scalar_width_device.argtypes = L.msm_amd_scalar_width.argtypes
+            L.msm_amd_host_scalar_width.argtypes = [c_int, c_void_p, c_size_t, c_int, c_int, POINTER(c_uint32), POINTER(c_uint64)]
+            L.msm_amd_msm_bounded.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_void_p]
+            L.msm_amd_msm_bounded_device.argtypes = L.msm_amd_msm_bounded.argtypes
+            L.msm_amd_msm_batch_bounded_device.argtypes = [c_void_p, c_int, c_int, c_size_t, c_void_p, c_void_p, c_void_p,
+                                                           c_uint32, c_int, c_void_p]
+            L.msm_amd_submit_batch_bounded_device.argtypes = L.msm_amd_msm_batch_bounded_device.argtypes + [POINTER(c_int)]
+            L.msm_amd_msm_g2_bounded.argtypes = L.msm_amd_msm_bounded.argtypes
+            L.msm_amd_msm_g2_bounded_device.argtypes = L.msm_amd_msm_bounded.argtypes
+            L.msm_amd_host_msm_bounded.argtypes = [c_int, c_int, c_void_p, c_void_p, c_size_t, c_uint32, c_int, c_int, c_void_p]
+            L.msm_amd_host_msm_g2_bounded.argtypes = L.msm_amd_host_msm_bounded.argtypes
+            L.msm_amd_auto_window_size_bounded.argtypes = [c_size_t, c_uint32, c_int]
+            L.msm_amd_auto_window_size_bounded.restype = c_uint32
         L.msm_amd_tuned_split.argtypes = [c_size_t]
         L.msm_amd_tuned_split.restype = c_size_t
         _LIB = L
@@ -514,6 +534,64 @@ class MsmConfig:
         ticket, out, k = handle
         self._check(_lib().msm_amd_wait_batch(self.h, ticket))
         return [out.raw[96 * i:96 * i + 96] for i in range(k)]
+
+    # ---- scalars of bounded width: magnitudes below 2^bits (WIDTH_SIGNED: min(s, r - s)).  A record beyond the bound
+    # raises MsmError(INPUT_ERROR) after the GPU work and leaves `out` (a caller's ctypes buffer, optional) untouched.
+    def scalar_width(self, scalars: bytes, n: int, sign=WIDTH_UNSIGNED, scalar_layout=SCALAR_MONT_LE):
+        """(bits, {"zeros", "negatives", "widest"}) of n host scalars."""
+        return _width_result(lambda b, st: self._check(
+            _lib().msm_amd_scalar_width(self.h, scalar_layout, scalars, n, sign, b, st)))
+
+    def scalar_width_device(self, d_scalars, n: int, sign=WIDTH_UNSIGNED, scalar_layout=SCALAR_MONT_LE):
+        return _width_result(lambda b, st: self._check(
+            _lib().msm_amd_scalar_width_device(self.h, scalar_layout, d_scalars, n, sign, b, st)))
+
+    def msm_bounded(self, scalars: bytes, points, n: int, bits: int, sign=WIDTH_UNSIGNED, scalar_layout=SCALAR_MONT_LE,
+                    point_layout=POINT_H2C_AFFINE, out=None) -> bytes:
+        """points: host bytes, or the device pointer / table handle of POINT_PREPARED / POINT_TABLES."""
+        out = ctypes.create_string_buffer(96) if out is None else out
+        self._check(_lib().msm_amd_msm_bounded(self.h, scalar_layout, point_layout, scalars, points, n, bits, sign, out))
+        return out.raw[:96]
+
+    def msm_bounded_device(self, d_scalars, d_points, n: int, bits: int, sign=WIDTH_UNSIGNED, scalar_layout=SCALAR_MONT_LE,
+                           point_layout=POINT_H2C_AFFINE, out=None) -> bytes:
+        out = ctypes.create_string_buffer(96) if out is None else out
+        self._check(_lib().msm_amd_msm_bounded_device(self.h, scalar_layout, point_layout, d_scalars, d_points, n, bits, sign,
+                                                      out))
+        return out.raw[:96]
+
+    def msm_batch_bounded_device(self, d_scalars, d_points, ns, bits: int, sign=WIDTH_UNSIGNED,
+                                 scalar_layout=SCALAR_MONT_LE, point_layout=POINT_H2C_AFFINE, out=None):
+        k = len(ns)
+        sp, pp, nn = (c_void_p * k)(*d_scalars), (c_void_p * k)(*d_points), (c_size_t * k)(*ns)
+        out = ctypes.create_string_buffer(96 * k) if out is None else out
+        self._check(_lib().msm_amd_msm_batch_bounded_device(self.h, scalar_layout, point_layout, k, sp, pp, nn, bits, sign, out))
+        return [out.raw[96 * i:96 * i + 96] for i in range(k)]
+
+    def submit_batch_bounded_device(self, d_scalars, d_points, ns, bits: int, sign=WIDTH_UNSIGNED,
+                                    scalar_layout=SCALAR_MONT_LE, point_layout=POINT_H2C_AFFINE, out=None):
+        """Returns a handle for wait_batch, which raises for a violated bound."""
+        k = len(ns)
+        sp, pp, nn = (c_void_p * k)(*d_scalars), (c_void_p * k)(*d_points), (c_size_t * k)(*ns)
+        out = ctypes.create_string_buffer(96 * k) if out is None else out
+        ticket = c_int(-1)
+        self._check(_lib().msm_amd_submit_batch_bounded_device(self.h, scalar_layout, point_layout, k, sp, pp, nn, bits, sign,
+                                                               out, ctypes.byref(ticket)))
+        return (ticket.value, out, k)
+
+    def msm_g2_bounded(self, scalars: bytes, points: bytes, n: int, bits: int, sign=WIDTH_UNSIGNED,
+                       scalar_layout=SCALAR_MONT_LE, point_layout=G2_POINT_H2C_AFFINE, out=None) -> bytes:
+        out = ctypes.create_string_buffer(192) if out is None else out
+        self._check(_lib().msm_amd_msm_g2_bounded(self.h, scalar_layout, point_layout, scalars, points, n, bits, sign, out))
+        return out.raw[:192]
+
+    def msm_g2_bounded_device(self, d_scalars, d_points, n: int, bits: int, sign=WIDTH_UNSIGNED,
+                              scalar_layout=SCALAR_MONT_LE, point_layout=G2_POINT_H2C_AFFINE, out=None) -> bytes:
+        """d_points: device records, a prepared array (G2_POINT_PREPARED) or a table handle (G2_POINT_TABLES)."""
+        out = ctypes.create_string_buffer(192) if out is None else out
+        self._check(_lib().msm_amd_msm_g2_bounded_device(self.h, scalar_layout, point_layout, d_scalars, d_points, n, bits,
+                                                         sign, out))
+        return out.raw[:192]
 
     def set_wait_timeout_ms(self, ms: int):
         """Upper bound of every host wait for the GPU (0 = none); a wait that reaches it raises PIPELINE_ERROR."""
@@ -1231,6 +1309,42 @@ def host_msm(scalars: bytes, points: bytes, n: int, threads=0, scalar_layout=SCA
     if st != OK:
         raise MsmError(st)
     return out.raw
+
+
+def _width_result(call):
+    bits = c_uint32(0)
+    stats = (c_uint64 * 4)()
+    call(ctypes.byref(bits), stats)
+    return bits.value, {"zeros": stats[0], "negatives": stats[1], "widest": stats[2]}
+
+
+def _host_status(st):
+    if st != OK:
+        raise MsmError(st)
+
+
+def host_scalar_width(scalars: bytes, n: int, sign=WIDTH_UNSIGNED, scalar_layout=SCALAR_MONT_LE, threads=0):
+    """Host twin of MsmConfig.scalar_width."""
+    return _width_result(lambda b, st: _host_status(
+        _lib().msm_amd_host_scalar_width(scalar_layout, scalars, n, sign, threads, b, st)))
+
+
+def host_msm_bounded(scalars: bytes, points: bytes, n: int, bits: int, sign=WIDTH_UNSIGNED, threads=0,
+                     scalar_layout=SCALAR_MONT_LE, point_layout=POINT_H2C_AFFINE, out=None) -> bytes:
+    out = ctypes.create_string_buffer(96) if out is None else out
+    _host_status(_lib().msm_amd_host_msm_bounded(scalar_layout, point_layout, scalars, points, n, bits, sign, threads, out))
+    return out.raw[:96]
+
+
+def host_msm_g2_bounded(scalars: bytes, points: bytes, n: int, bits: int, sign=WIDTH_UNSIGNED, threads=0,
+                        scalar_layout=SCALAR_MONT_LE, point_layout=G2_POINT_H2C_AFFINE, out=None) -> bytes:
+    out = ctypes.create_string_buffer(192) if out is None else out
+    _host_status(_lib().msm_amd_host_msm_g2_bounded(scalar_layout, point_layout, scalars, points, n, bits, sign, threads, out))
+    return out.raw[:192]
+
+
+def auto_window_size_bounded(n: int, bits: int, lone=False) -> int:
+    return _lib().msm_amd_auto_window_size_bounded(n, bits, 1 if lone else 0)
 
 
 def generate_instance_host(seed, n, scalars_mont=True, threads=0):

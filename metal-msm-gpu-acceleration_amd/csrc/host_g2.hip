@@ -14,6 +14,7 @@
 #include "launch_g2.h"
 #include "test_ops_g2.hip.h"
 #include "compress_points.hip.h"
+#include "scalar_width.hip.h"
 
 namespace msm_amd {
 
@@ -96,8 +97,9 @@ size_t msm_amd_g2_point_bytes(int layout) {
 
 // CPU G2 MSM: unsigned c-bit windows, one bucket set per window, Jacobian + affine bucket additions, running sums;
 // windows are spread over `threads` host threads.
-int msm_amd_host_msm_g2(int scalar_layout, int g2_point_layout, const void* scalars, const void* points, size_t n,
-                        int threads, void* out192) {
+// width.bounded(): ceil(bits / c) windows; a signed call folds k > (r - 1) / 2 to r - k and negates the base instead.
+static int host_msm_g2_entry(int scalar_layout, int g2_point_layout, const void* scalars, const void* points, size_t n,
+                             int threads, msm_amd::WidthBound width, void* out192) {
   using namespace msm_amd;
   if (!out192 || msm_amd_g2_point_bytes(g2_point_layout) == 0) return MSM_AMD_INPUT_ERROR;
   if (scalar_layout != MSM_AMD_SCALAR_MONT_LE && scalar_layout != MSM_AMD_SCALAR_CANON_LE &&
@@ -111,11 +113,17 @@ int msm_amd_host_msm_g2(int scalar_layout, int g2_point_layout, const void* scal
   for (size_t i = 0; i < n; ++i) {
     read_g2_point(g2_point_layout, pt, i, base[i]);
     k[i] = read_scalar(scalar_layout, sc, i);
+    if (width.bounded()) {
+      uint32_t flip;
+      k[i] = scalar_magnitude(k[i], width.sign, &flip);
+      if (u256_bit_length(k[i]) > width.bits) return MSM_AMD_INPUT_ERROR;   // beyond the bound: the output stays as it was
+      if (flip) base[i].y = h64::neg2(base[i].y);
+    }
     if (h64::aff2_is_identity(base[i])) k[i] = u256_zero();
   }
   uint32_t c = 3;
   while (c < 16 && ((size_t)1 << (c + 3)) < n) ++c;
-  const uint32_t W = (254 + c - 1) / c;
+  const uint32_t W = (width.width() + c - 1) / c;
   std::vector<h64::Jac2> win(W);
   std::atomic<uint32_t> next{0};
   auto worker = [&]() {
@@ -149,6 +157,20 @@ int msm_amd_host_msm_g2(int scalar_layout, int g2_point_layout, const void* scal
   const h64::Jac2 nrm = h64::normalise2(acc);
   std::memcpy(out192, &nrm, 192);
   return MSM_AMD_OK;
+}
+
+int msm_amd_host_msm_g2(int scalar_layout, int g2_point_layout, const void* scalars, const void* points, size_t n,
+                        int threads, void* out192) {
+  return host_msm_g2_entry(scalar_layout, g2_point_layout, scalars, points, n, threads, msm_amd::WidthBound{}, out192);
+}
+
+int msm_amd_host_msm_g2_bounded(int scalar_layout, int g2_point_layout, const void* scalars, const void* points, size_t n,
+                                uint32_t bits, int sign, int threads, void* out192) {
+  using namespace msm_amd;
+  if (width_bound_check(bits, sign)) return MSM_AMD_INPUT_ERROR;
+  WidthBound width;
+  width.bits = bits, width.sign = (uint32_t)sign;
+  return host_msm_g2_entry(scalar_layout, g2_point_layout, scalars, points, n, threads, width, out192);
 }
 
 // out[i] = start + i step (i < n), halo2curves G2Affine records (identity = all zero); threads over index ranges, one

@@ -38,6 +38,7 @@
 #include "../../include/msm_amd.h"
 #include "device_common.hip.h"
 #include "launch.h"
+#include "host_threads.h"
 #include "host_fq64.h"
 #include "host_ifma.h"
 
@@ -469,13 +470,14 @@ uint32_t segments_for(uint32_t c, uint32_t groups, int threads) {   // phase-2 t
   const uint32_t half = 1u << (c - 1);
   return threads <= 1 ? 1u : std::max(1u, std::min(groups, half / 32 ? half / 32 : 1u));
 }
-Choice window_for(size_t n, int threads, bool vec = false) {
+// bits: the width of the scalars (254 unless the call is bounded): W = bits / c + 1 windows
+Choice window_for(size_t n, int threads, bool vec = false, uint32_t bits = kScalarBits) {
   if (n < 32) return {3, 1, 0};   // the reference's policy for tiny instances (msm.rs:137-138)
   Choice best{4, 1, 0};
   double best_cost = 1e300;
   const uint32_t max_groups = threads <= 1 ? 1u : 8u;
   for (uint32_t c = 4; c <= 15; ++c) {
-    const uint32_t W = 254 / c + 1;
+    const uint32_t W = bits / c + 1;
     const double nb = (double)(1u << (c - 1));
     for (uint32_t groups = 1; groups <= max_groups; ++groups) {
       if (groups > 1 && n / groups < 256) break;
@@ -535,10 +537,11 @@ struct ScratchLease {
   }
 };
 
-Jacobian run(const u256* scalars, int scalars_mont, const Aff* points, size_t n, int threads, bool& ok) {
+Jacobian run(const u256* scalars, int scalars_mont, const Aff* points, size_t n, int threads, bool& ok, WidthBound width,
+             uint64_t* violations, uint64_t* first) {
   const int T = std::max(1, std::min<int>(threads, (int)std::min<size_t>((n + 63) / 64, 256)));
   const bool vec = ifma::available() && std::getenv("MSM_AMD_HOST_NO_IFMA") == nullptr;
-  Choice choice = window_for(n, T, vec);
+  Choice choice = window_for(n, T, vec, width.width());
   if (const char* e = std::getenv("MSM_AMD_HOST_WINDOW")) {   // experiments (tools/dbg/cpu_sweep.sh)
     const int v = std::atoi(e);
     if (v >= 3 && v <= 15) choice.c = (uint32_t)v;
@@ -555,8 +558,9 @@ Jacobian run(const u256* scalars, int scalars_mont, const Aff* points, size_t n,
   }
   const bool use_vec = vec && choice.batch != 0;
   const uint32_t c = choice.c, groups = choice.groups;
-  const uint32_t W = 254 / c + 1;
+  const uint32_t W = width.width() / c + 1;
   const uint32_t half = 1u << (c - 1);   // buckets per window: slot b <-> digit magnitude b + 1
+  std::atomic<uint64_t> viol_count{0}, viol_first{~(uint64_t)0};
   const uint32_t segs = segments_for(c, groups, T);   // phase-2 tasks per window
   const uint32_t seg_len = (half + segs - 1) / segs;
   const size_t digit_bytes = ((size_t)W * n * sizeof(int16_t) + 63) & ~(size_t)63;
@@ -602,6 +606,15 @@ Jacobian run(const u256* scalars, int scalars_mont, const Aff* points, size_t n,
           k = scalars[i];
           for (int t = 0; t < 5; ++t) k = Fr::reduce_once(k);
         }
+        uint32_t flip = 0;
+        if (width.bounded()) {   // the sign fold and the bound, on every record (an identity point's too), as the GPU does
+          k = scalar_magnitude(k, width.sign, &flip);
+          if (u256_bit_length(k) > width.bits) {
+            viol_count.fetch_add(1, std::memory_order_relaxed);
+            uint64_t seen = viol_first.load(std::memory_order_relaxed);
+            while (i < seen && !viol_first.compare_exchange_weak(seen, i, std::memory_order_relaxed)) {}
+          }
+        }
         if (h64::is_zero(points[i].x) && h64::is_zero(points[i].y)) k = u256_zero();   // affine identity (0, 0): no digits
         uint32_t carry = 0;
         for (uint32_t w = 0; w < W; ++w) {
@@ -613,7 +626,7 @@ Jacobian run(const u256* scalars, int scalars_mont, const Aff* points, size_t n,
             d = (int32_t)v - (int32_t)(1u << c);
             carry = 1;
           }
-          digits[(size_t)w * n + i] = (int16_t)d;
+          digits[(size_t)w * n + i] = (int16_t)(flip ? -d : d);
         }
       }
       if (use_vec) ifma::convert((const uint64_t*)(points + lo), (uint64_t*)(points_q + lo), (hi - lo) * 2, 0);
@@ -669,6 +682,8 @@ Jacobian run(const u256* scalars, int scalars_mont, const Aff* points, size_t n,
     for (uint32_t s = 0; s < segs; ++s) total = h64::jadd(total, part[(size_t)w * segs + s]);
   }
   stamp("horner");
+  if (violations) *violations = viol_count.load();
+  if (first) *first = viol_first.load();
   return h64::store(total);
 }
 
@@ -676,9 +691,12 @@ Jacobian run(const u256* scalars, int scalars_mont, const Aff* points, size_t n,
 
 // sum_i k_i * P_i on `threads` host threads.  scalars: 32-byte LE (Montgomery if scalars_mont), points: 64-byte
 // affine Montgomery LE with (0,0) = identity.  The result is NOT normalised (callers add it to a GPU partial first).
-Jacobian host_msm(const u256* scalars, int scalars_mont, const Affine* points, size_t n, int threads, bool* ok) {
+Jacobian host_msm(const u256* scalars, int scalars_mont, const Affine* points, size_t n, int threads, bool* ok,
+                  WidthBound width, uint64_t* violations, uint64_t* first) {
   bool fine = true;
-  const Jacobian r = n == 0 ? jac_identity() : run(scalars, scalars_mont, (const Aff*)points, n, threads, fine);
+  if (violations) *violations = 0;
+  const Jacobian r = n == 0 ? jac_identity()
+                            : run(scalars, scalars_mont, (const Aff*)points, n, threads, fine, width, violations, first);
   if (ok) *ok = fine;
   return r;
 }
@@ -689,18 +707,67 @@ extern "C" {
 
 // The CPU MSM as an entry point of its own: no ctx, no GPU (`gpu_profiler <log> <inst> cpu`).  h2c affine points;
 // scalars MONT_LE or CANON_LE.  threads <= 0: every CPU the process may run on.
-int msm_amd_host_msm(int scalar_layout, int point_layout, const void* scalars, const void* points, size_t n, int threads,
-                     void* out96) {
+static int host_msm_entry(int scalar_layout, int point_layout, const void* scalars, const void* points, size_t n, int threads,
+                          msm_amd::WidthBound width, void* out96) {
   using namespace msm_amd;
   if (!scalars || !points || !out96 || n == 0) return MSM_AMD_INPUT_ERROR;
   if (point_layout != MSM_AMD_POINT_H2C_AFFINE) return MSM_AMD_INPUT_ERROR;
   if (scalar_layout != MSM_AMD_SCALAR_MONT_LE && scalar_layout != MSM_AMD_SCALAR_CANON_LE) return MSM_AMD_INPUT_ERROR;
   if (threads <= 0) threads = msm_amd_host_threads();
   bool ok = true;
-  const Jacobian r = host_msm((const u256*)scalars, scalar_layout == MSM_AMD_SCALAR_MONT_LE, (const Affine*)points, n, threads, &ok);
+  uint64_t violations = 0;
+  const Jacobian r = host_msm((const u256*)scalars, scalar_layout == MSM_AMD_SCALAR_MONT_LE, (const Affine*)points, n, threads,
+                              &ok, width, &violations);
   if (!ok) return MSM_AMD_PIPELINE_ERROR;   // host allocation failed
+  if (violations) return MSM_AMD_INPUT_ERROR;   // a record beyond the bound: the output stays as it was
   const h64::Jac nrm = h64::normalise(h64::load(r));
   std::memcpy(out96, &nrm, 96);
+  return MSM_AMD_OK;
+}
+
+int msm_amd_host_msm(int scalar_layout, int point_layout, const void* scalars, const void* points, size_t n, int threads,
+                     void* out96) {
+  return host_msm_entry(scalar_layout, point_layout, scalars, points, n, threads, msm_amd::WidthBound{}, out96);
+}
+
+// The CPU MSM at the width of its scalars: bits / c + 1 windows, the sign folded in front of the digits
+int msm_amd_host_msm_bounded(int scalar_layout, int point_layout, const void* scalars, const void* points, size_t n,
+                             uint32_t bits, int sign, int threads, void* out96) {
+  using namespace msm_amd;
+  if (width_bound_check(bits, sign)) return MSM_AMD_INPUT_ERROR;
+  WidthBound width;
+  width.bits = bits, width.sign = (uint32_t)sign;
+  return host_msm_entry(scalar_layout, point_layout, scalars, points, n, threads, width, out96);
+}
+
+// Host twin of the width scan: a plain loop over thread ranges, folded in index order.
+int msm_amd_host_scalar_width(int scalar_layout, const void* scalars, size_t n, int sign, int threads, uint32_t* bits,
+                              uint64_t* stats) {
+  using namespace msm_amd;
+  if (scalar_width_check(scalar_layout, scalars, n, sign, bits)) return MSM_AMD_INPUT_ERROR;
+  WidthStats total;
+  if (n) {
+    const unsigned T = worker_count(threads, n);
+    std::vector<WidthStats> part(T);
+    const u256* sc = (const u256*)scalars;
+    for_ranges(T, n, [&](unsigned t, size_t lo, size_t hi) {
+      WidthStats w;
+      w.widest = lo;
+      for (size_t i = lo; i < hi; ++i) {
+        uint32_t neg;
+        u256 rec;
+        std::memcpy(&rec, sc + i, 32);
+        const uint32_t len = u256_bit_length(
+            scalar_magnitude(scalar_residue(rec, scalar_layout == MSM_AMD_SCALAR_MONT_LE), (uint32_t)sign, &neg));
+        if (len > w.bits) w.bits = len, w.widest = i;
+        w.zeros += len == 0, w.negatives += neg;
+      }
+      part[t] = w;
+    });
+    total = part[0];
+    for (unsigned t = 1; t < T; ++t) width_stats_merge(total, part[t]);
+  }
+  scalar_width_out(total, bits, stats);
   return MSM_AMD_OK;
 }
 

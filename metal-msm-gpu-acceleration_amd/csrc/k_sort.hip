@@ -23,6 +23,61 @@ constexpr int kSortThreads = 1024;       // hist / plan / scatter workgroup size
 // and every digit is one v_alignbit + v_and on fixed words of the scalar instead of a 16-way select chain over a
 // run-time word index (the common window sizes of the pipelined policy; 375 -> ~140 instructions per scalar).
 // C = 0: c and W from the arguments.
+// B (a bounded call, msm_amd_msm_bounded*: Plan::bits): the scalar's magnitude stays below 2^bits and W = bits / c + 1
+// windows are emitted.  After the reduction a signed call replaces k > (r - 1) / 2 by r - k and XORs that flip into the
+// sign of every digit (the point is subtracted instead); the magnitude's bit length is compared with the bound, and a
+// record that exceeds it counts itself and offers its index -- two atomics on the violation only, the call's result
+// is then discarded by the host (wait_batch).  WT > 0 (with C > 0): the window count is a compile-time constant too;
+// WT = 0 with C > 0: W comes from the arguments and leaves the unrolled loop by a wave-uniform branch.
+// The kernels of the unbounded call below keep their own text (scalar_digits, digits_kernel, digits_hist_kernel): their
+// code and their resource figures are those of the full-width pipeline.
+struct DigitBound {
+  uint32_t bits, sign;
+  uint32_t* viol;   // PlanCounters::viol: [0] violating records, [1] max of ~index (zeroed by the front end)
+};
+template <int C, int WT, bool B, typename Emit>
+__device__ __forceinline__ void scalar_digits_w(u256 k, int scalars_mont, uint32_t c_arg, uint32_t W_arg,
+                                                const DigitBound& bd, uint32_t t, Emit emit) {
+  constexpr uint32_t kW = C > 0 ? (uint32_t)(WT > 0 ? WT : 254 / (C > 0 ? C : 1) + 1) : 0u;
+  const uint32_t c = C > 0 ? (uint32_t)C : c_arg;
+  const uint32_t W = C > 0 ? kW : W_arg;
+  if (scalars_mont) {
+    k = Fr::from_mont(k);
+  } else {
+    // canonical layouts carry raw 256-bit integers (instance files, FFI callers): bring them below r first, so
+    // that every window size sees the same scalar (2^256 / r < 6: at most five subtractions)
+#pragma unroll 1
+    for (int i = 0; i < 5; ++i) k = Fr::reduce_once(k);
+  }
+  uint32_t flip = 0;
+  if constexpr (B) {
+    k = scalar_magnitude(k, bd.sign, &flip);
+    if (u256_bit_length(k) > bd.bits) {
+      atomicAdd(&bd.viol[0], 1u);
+      atomicMax(&bd.viol[1], ~t);
+    }
+  }
+  const uint32_t half = 1u << (c - 1);
+  uint32_t carry = 0;
+  constexpr int kUnroll = C > 0 ? (int)kW : 1;   // run-time c: rolled
+#pragma unroll kUnroll
+  for (uint32_t w = 0; w < W; ++w) {
+    if constexpr (B && C > 0 && WT == 0) {
+      if (w >= W_arg) break;
+    }
+    const uint32_t start = w * c;
+    uint32_t v = (start < 256 ? u256_extract_bits(k, start, c) : 0u) + carry;
+    uint32_t neg = 0;
+    carry = 0;
+    if (v > half) {
+      v = (1u << c) - v;
+      neg = 1;
+      carry = 1;
+    }
+    if constexpr (B) neg = (neg ^ flip) & (v != 0 ? 1u : 0u);
+    emit(w, v, neg);
+  }
+}
 // scalar_digits: the W signed digits of one scalar, handed to emit(w, magnitude, negative) window by window.
 template <int C, typename Emit>
 __device__ __forceinline__ void scalar_digits(u256 k, int scalars_mont, uint32_t c_arg, uint32_t W_arg, Emit emit) {
@@ -54,6 +109,19 @@ __device__ __forceinline__ void scalar_digits(u256 k, int scalars_mont, uint32_t
   }
 }
 
+template <typename D, int C, int WT, bool B>
+__device__ __forceinline__ void digits_body(const u256* __restrict__ scalars, uint32_t n, uint32_t c_arg, uint32_t W_arg,
+                                            int scalars_mont, const DigitBound& bd, D* __restrict__ digits) {
+  constexpr uint32_t kSignShift = 8 * sizeof(D) - 1;
+  __builtin_amdgcn_s_setprio(kFrontPriority);
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  scalar_digits_w<C, WT, B>(load_u256(&scalars[t]), scalars_mont, c_arg, W_arg, bd, t,
+                            [&](uint32_t w, uint32_t v, uint32_t neg) {
+    digits[(size_t)w * n + t] = (D)(v | (neg << kSignShift));
+  });
+}
+
 template <typename D, int C = 0>
 __global__ void __launch_bounds__(256)
 digits_kernel(const u256* __restrict__ scalars, uint32_t n, uint32_t c_arg, uint32_t W_arg, int scalars_mont,
@@ -67,6 +135,13 @@ digits_kernel(const u256* __restrict__ scalars, uint32_t n, uint32_t c_arg, uint
   });
 }
 
+template <typename D, int C = 0, int WT = 0>
+__global__ void __launch_bounds__(256)
+digits_bounded_kernel(const u256* __restrict__ scalars, uint32_t n, uint32_t c_arg, uint32_t W_arg, int scalars_mont,
+                      DigitBound bd, D* __restrict__ digits) {
+  digits_body<D, C, WT, true>(scalars, n, c_arg, W_arg, scalars_mont, bd, digits);
+}
+
 // Stage 1 fused with the histogram of sort pass 1 (per-call pipeline, where the digit windows are the sort windows).
 // grid = (S, Q): chunk q of pass 1 is cut into S pieces of kDigitsSpan scalars, one 256-thread workgroup each (a grid
 // of only Q big workgroups, one per chunk, leaves most CUs without digit work: 34 workgroups at 2^20 points took
@@ -77,6 +152,37 @@ digits_kernel(const u256* __restrict__ scalars, uint32_t n, uint32_t c_arg, uint
 // coarse_cnt[w][q][hi] -- the layout coarse_hist_kernel writes -- which launch_digits_hist has zeroed.
 constexpr uint32_t kDigitsThreads = 256;
 constexpr uint32_t kDigitsSpan = kDigitsThreads * 8;
+template <typename D, int C, int WT, bool B>
+__device__ __forceinline__ void digits_hist_body(const u256* __restrict__ scalars, uint32_t n, uint32_t c_arg,
+                                                 uint32_t W_arg, int scalars_mont, const DigitBound& bd, uint32_t fb,
+                                                 uint32_t nhi, uint32_t chunk, D* __restrict__ digits,
+                                                 uint32_t* __restrict__ coarse_cnt /* [W][Q][nhi], zero */) {
+  constexpr uint32_t kSignShift = 8 * sizeof(D) - 1;
+  const uint32_t W = (C > 0 && !(B && WT == 0)) ? (uint32_t)(WT > 0 ? WT : 254 / (C > 0 ? C : 1) + 1) : W_arg;
+  __builtin_amdgcn_s_setprio(kFrontPriority);
+  extern __shared__ uint32_t lds_u32[];   // [W][nhi]
+  const uint32_t q = blockIdx.y, Q = gridDim.y;
+  const uint32_t lo = q * chunk + blockIdx.x * kDigitsSpan;
+  const uint32_t hi = min(min(n, (q + 1) * chunk), lo + kDigitsSpan);
+  if (lo >= hi) return;   // (whole workgroup)
+  for (uint32_t i = threadIdx.x; i < W * nhi; i += blockDim.x) lds_u32[i] = 0;
+  __syncthreads();
+#pragma unroll 1
+  for (uint32_t t = lo + threadIdx.x; t < hi; t += blockDim.x) {
+    scalar_digits_w<C, WT, B>(load_u256(&scalars[t]), scalars_mont, c_arg, W_arg, bd, t,
+                              [&](uint32_t w, uint32_t v, uint32_t neg) {
+      digits[(size_t)w * n + t] = (D)(v | (neg << kSignShift));
+      if (v) atomicAdd(&lds_u32[w * nhi + ((v - 1) >> fb)], 1u);
+    });
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < W * nhi; i += blockDim.x) {
+    const uint32_t w = i / nhi, r = i - w * nhi;
+    const uint32_t cnt = lds_u32[i];
+    if (cnt) atomicAdd(&coarse_cnt[((size_t)w * Q + q) * nhi + r], cnt);
+  }
+}
+
 template <typename D, int C = 0>
 __global__ void __launch_bounds__(kDigitsThreads)
 digits_hist_kernel(const u256* __restrict__ scalars, uint32_t n, uint32_t c_arg, uint32_t W_arg, int scalars_mont,
@@ -104,6 +210,100 @@ digits_hist_kernel(const u256* __restrict__ scalars, uint32_t n, uint32_t c_arg,
     const uint32_t w = i / nhi, r = i - w * nhi;
     const uint32_t cnt = lds_u32[i];
     if (cnt) atomicAdd(&coarse_cnt[((size_t)w * Q + q) * nhi + r], cnt);
+  }
+}
+
+template <typename D, int C = 0, int WT = 0>
+__global__ void __launch_bounds__(kDigitsThreads)
+digits_hist_bounded_kernel(const u256* __restrict__ scalars, uint32_t n, uint32_t c_arg, uint32_t W_arg, int scalars_mont,
+                           DigitBound bd, uint32_t fb, uint32_t nhi, uint32_t chunk, D* __restrict__ digits,
+                           uint32_t* __restrict__ coarse_cnt /* [W][Q][nhi], zero */) {
+  digits_hist_body<D, C, WT, true>(scalars, n, c_arg, W_arg, scalars_mont, bd, fb, nhi, chunk, digits, coarse_cnt);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Width scan (msm_amd_scalar_width*): the largest bit length of a magnitude, the zero and negative records and the
+// lowest index of a widest record.  A wave takes kWidthPerLane runs of 64 consecutive records (lane l reads record
+// base + 64 j + l: neighbouring lanes read neighbouring records), every lane reduces its records as scalar_digits does,
+// folds them (signed) and takes the bit length by a count-leading-zeros over the words; six xor-shuffles leave the
+// wave's maximum -- as one 64-bit key, bits << 32 | ~index, so that a tie picks the lowest index -- and its sums, one
+// 16-byte partial per wave.  scalar_width_fold_kernel, one workgroup, folds the partials the same way (the pattern of
+// fr_mat_fold_kernel in k_fr.hip: a second small launch, nothing waits on another workgroup).
+constexpr uint32_t kWidthThreads = 256, kWidthPerLane = 16;
+struct WidthPartial {
+  unsigned long long key;   // bits << 32 | ~index of the lowest widest record
+  uint32_t zeros, negatives;
+};
+struct WidthResult {   // what the host reads back
+  unsigned long long key, zeros, negatives, pad;
+};
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long x) {
+#pragma unroll
+  for (int d = 32; d != 0; d >>= 1) {
+    const unsigned long long y = __shfl_xor(x, d, 64);
+    x = y > x ? y : x;
+  }
+  return x;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long x) {
+#pragma unroll
+  for (int d = 32; d != 0; d >>= 1) x += __shfl_xor(x, d, 64);
+  return x;
+}
+
+__global__ void __launch_bounds__(kWidthThreads)
+scalar_width_kernel(const u256* __restrict__ scalars, uint32_t n, int scalars_mont, uint32_t sign,
+                    WidthPartial* __restrict__ partials /* [ceil(n / (64 kWidthPerLane))] */) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = blockIdx.x * (kWidthThreads / 64u) + (threadIdx.x >> 6);
+  const uint64_t base = (uint64_t)wave * (64u * kWidthPerLane);
+  if (base >= n) return;   // (whole wave)
+  unsigned long long key = 0;
+  uint32_t zeros = 0, negatives = 0;
+#pragma unroll 1
+  for (uint32_t j = 0; j < kWidthPerLane; ++j) {
+    const uint64_t i = base + 64u * j + lane;
+    if (i >= n) break;
+    uint32_t neg;
+    const u256 m = scalar_magnitude(scalar_residue(load_u256(&scalars[i]), scalars_mont), sign, &neg);
+    const uint32_t len = u256_bit_length(m);
+    zeros += len == 0 ? 1u : 0u;
+    negatives += neg;
+    const unsigned long long k = ((unsigned long long)len << 32) | (uint32_t)~(uint32_t)i;
+    key = k > key ? k : key;
+  }
+  key = wave_max_u64(key);
+  const unsigned long long z = wave_sum_u64(zeros), g = wave_sum_u64(negatives);
+  if (lane == 0) partials[wave] = WidthPartial{key, (uint32_t)z, (uint32_t)g};
+}
+
+__global__ void __launch_bounds__(kWidthThreads)
+scalar_width_fold_kernel(const WidthPartial* __restrict__ partials, uint32_t count, WidthResult* __restrict__ out) {
+  __shared__ unsigned long long sh[3][kWidthThreads / 64];
+  unsigned long long key = 0, zeros = 0, negatives = 0;
+  for (uint32_t i = threadIdx.x; i < count; i += kWidthThreads) {
+    const WidthPartial p = partials[i];
+    key = p.key > key ? p.key : key;
+    zeros += p.zeros;
+    negatives += p.negatives;
+  }
+  key = wave_max_u64(key);
+  zeros = wave_sum_u64(zeros);
+  negatives = wave_sum_u64(negatives);
+  if ((threadIdx.x & 63u) == 0) {
+    sh[0][threadIdx.x >> 6] = key;
+    sh[1][threadIdx.x >> 6] = zeros;
+    sh[2][threadIdx.x >> 6] = negatives;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    WidthResult r{0, 0, 0, 0};
+    for (uint32_t w = 0; w < kWidthThreads / 64; ++w) {
+      r.key = sh[0][w] > r.key ? sh[0][w] : r.key;
+      r.zeros += sh[1][w];
+      r.negatives += sh[2][w];
+    }
+    *out = r;
   }
 }
 
@@ -849,9 +1049,45 @@ int sort_set_attributes(const char** failed) {
   return 0;
 }
 
-void launch_digits(hipStream_t st, const Plan& p, const u256* scalars, int scalars_mont, void* digits) {
+// Compile-time (c, W) pairs of the bounded digit kernels: the windows auto_window_bounded (msm_host.hip,
+// profiles/bounded_sweep.txt) picks at the widths provers commit to -- 8 bits: c = 9, one window; 16, 32, 64 bits from 2^19
+// points: c = 17 with 1, 2, 4 windows; 64 and 128 bits up to 2^18 points: c = 13 with 5 and 10; 128 bits above: c = 10 with
+// 13.  Other widths at c = 13, 15, 16, 17 keep the compile-time window with W from the arguments; every other window is
+// the rolled form.  X(D, C, WT)
+#define MSM_BOUNDED_PAIRS(X)                                                                                          \
+  X(uint32_t, 17, 1) X(uint32_t, 17, 2) X(uint32_t, 17, 4) X(uint16_t, 13, 5) X(uint16_t, 13, 10) X(uint16_t, 9, 1)    \
+  X(uint16_t, 10, 13)
+#define MSM_BOUNDED_WINDOWS(X) X(uint32_t, 17, 0) X(uint32_t, 16, 0) X(uint16_t, 15, 0) X(uint16_t, 13, 0)
+
+// the zeroed violation words of a bounded plan that can be violated (launched in front of the digits)
+static DigitBound digit_bound(hipStream_t st, const Plan& p, PlanCounters* counters) {
+  (void)hipMemsetAsync(counters->viol, 0, sizeof counters->viol, st);
+  return DigitBound{p.bits, p.sign, counters->viol};
+}
+
+void launch_digits(hipStream_t st, const Plan& p, const u256* scalars, int scalars_mont, void* digits,
+                   PlanCounters* counters) {
   const dim3 grid((p.n_scalars + 255) / 256), block(256);
-#define LAUNCH_DIGITS_C(D, CC)                                                                                      \
+  if (p.bits) {
+    const DigitBound bd = digit_bound(st, p, counters);
+#define LAUNCH_DIGITS_B(D, CC, WT)                                                                                  \
+  if (p.wide_digits == (sizeof(D) == 4) && p.c == CC && (WT == 0 || p.W_digits == WT)) {                             \
+    hipLaunchKernelGGL((digits_bounded_kernel<D, CC, WT>), grid, block, 0, st, scalars, p.n_scalars, p.c, p.W_digits, \
+                       scalars_mont, bd, (D*)digits);                                                                \
+    return;                                                                                                          \
+  }
+    MSM_BOUNDED_PAIRS(LAUNCH_DIGITS_B)
+    MSM_BOUNDED_WINDOWS(LAUNCH_DIGITS_B)
+#undef LAUNCH_DIGITS_B
+    if (p.wide_digits)
+      hipLaunchKernelGGL((digits_bounded_kernel<uint32_t, 0, 0>), grid, block, 0, st, scalars, p.n_scalars, p.c, p.W_digits,
+                         scalars_mont, bd, (uint32_t*)digits);
+    else
+      hipLaunchKernelGGL((digits_bounded_kernel<uint16_t, 0, 0>), grid, block, 0, st, scalars, p.n_scalars, p.c, p.W_digits,
+                         scalars_mont, bd, (uint16_t*)digits);
+    return;
+  }
+#define LAUNCH_DIGITS_C(D, CC)                                                                               \
   hipLaunchKernelGGL((digits_kernel<D, CC>), grid, block, 0, st, scalars, p.n_scalars, p.c, p.W_digits, scalars_mont, \
                      (D*)digits)
   if (p.W_digits == 254 / p.c + 1) {   // (always so; the specialisations compute W from C)
@@ -875,7 +1111,22 @@ void launch_digits_hist(hipStream_t st, const Plan& p, const u256* scalars, int 
   const dim3 grid((p.chunk + kDigitsSpan - 1) / kDigitsSpan, p.Q), block(kDigitsThreads);
   const size_t lds = (size_t)p.W * nhi * 4;
   (void)hipMemsetAsync(b.coarse_cnt, 0, (size_t)p.W * p.Q * nhi * sizeof(uint32_t), st);   // the pieces of a chunk add up
-#define LAUNCH_DIGITS_HIST_C(D, CC)                                                                                 \
+  if (p.bits) {
+    const DigitBound bd = digit_bound(st, p, b.counters);
+#define LAUNCH_DIGITS_HIST_B(D, CC, WT)                                                                             \
+  if (p.wide_digits == (sizeof(D) == 4) && (CC == 0 || p.c == CC) && (WT == 0 || p.W_digits == WT)) {                 \
+    hipLaunchKernelGGL((digits_hist_bounded_kernel<D, CC, WT>), grid, block, lds, st, scalars, p.n_scalars, p.c,      \
+                       p.W_digits, scalars_mont, bd, fb1, nhi, p.chunk, (D*)b.digits, b.coarse_cnt);                  \
+    return;                                                                                                          \
+  }
+    MSM_BOUNDED_PAIRS(LAUNCH_DIGITS_HIST_B)
+    MSM_BOUNDED_WINDOWS(LAUNCH_DIGITS_HIST_B)
+    LAUNCH_DIGITS_HIST_B(uint32_t, 0, 0)
+    LAUNCH_DIGITS_HIST_B(uint16_t, 0, 0)
+#undef LAUNCH_DIGITS_HIST_B
+    return;
+  }
+#define LAUNCH_DIGITS_HIST_C(D, CC)                                                                                \
   hipLaunchKernelGGL((digits_hist_kernel<D, CC>), grid, block, lds, st, scalars, p.n_scalars, p.c, p.W_digits,       \
                      scalars_mont, fb1, nhi, p.chunk, (D*)b.digits, b.coarse_cnt)
   if (p.W_digits == 254 / p.c + 1) {   // (always so; the specialisations compute W from C)
@@ -975,6 +1226,22 @@ void launch_sort(hipStream_t st, const Plan& p, const SortBuffers& b, bool have_
   hipLaunchKernelGGL(size_scatter_kernel, dim3(gb), dim3(size_threads), (2 * (p.CH + 1) + 2) * 4, st,
                      (const uint32_t*)b.bucket_size, (uint32_t)p.total_buckets, p.CH, (const uint32_t*)b.size_bins, b.order,
                      b.multi_list, b.counters);
+}
+
+size_t scalar_width_work_bytes(size_t n) {
+  const size_t waves = (n + 64 * kWidthPerLane - 1) / (64 * kWidthPerLane);
+  return sizeof(WidthResult) + waves * sizeof(WidthPartial);
+}
+
+// n >= 1; work: scalar_width_work_bytes(n).  The 32-byte result (key, zeros, negatives) is at the front of work.
+void launch_scalar_width(hipStream_t st, const u256* scalars, uint32_t n, int scalars_mont, uint32_t sign, void* work) {
+  const uint32_t waves = (uint32_t)(((size_t)n + 64 * kWidthPerLane - 1) / (64 * kWidthPerLane));
+  WidthPartial* partials = (WidthPartial*)((uint8_t*)work + sizeof(WidthResult));
+  const uint32_t waves_per_group = kWidthThreads / 64;
+  hipLaunchKernelGGL(scalar_width_kernel, dim3((waves + waves_per_group - 1) / waves_per_group), dim3(kWidthThreads), 0, st,
+                     scalars, n, scalars_mont, sign, partials);
+  hipLaunchKernelGGL(scalar_width_fold_kernel, dim3(1), dim3(kWidthThreads), 0, st, (const WidthPartial*)partials, waves,
+                     (WidthResult*)work);
 }
 
 void launch_be32_to_le(hipStream_t st, const uint32_t* in, size_t words, uint32_t* out) {

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "bn254_ec29.hip.h"
+#include "scalar_width.hip.h"
 
 namespace msm_amd {
 
@@ -17,6 +18,9 @@ struct Plan {
                               // (per-call pipeline: n points, W = floor(254/c) + 1 signed-digit windows;
                               //  precomputed tables: n = W_digits * n_scalars entries in ONE window)
   uint32_t n_scalars, W_digits;   // what digits_kernel sees: scalars and digit windows per scalar
+  uint32_t bits, sign;        // a bounded call whose bound a record can exceed (msm_amd_msm_bounded*): magnitudes below
+                              // 2^bits, W_digits = bits / c + 1, sign != 0 folds residues above (r - 1) / 2; bits = 0: the
+                              // unbounded call -- and a bound every residue meets (254 unsigned), which is the same plan
   bool wide_digits;           // digits are u32 (c up to 24) instead of u16 (c <= 15)
   uint32_t lb, nb;            // bucket slots per window nb = 2^lb = max(2^(c-1), 8); slot i holds |digit| = i + 1
   uint32_t Q, chunk;          // sort: chunks per window, points per chunk
@@ -45,6 +49,9 @@ struct PlanCounters {
   uint32_t total_items;       // number of accumulate work items
   uint32_t multi_count;       // number of buckets split into more than one item
   uint32_t pad[2];
+  uint32_t viol[2];           // bounded calls: records whose magnitude reaches 2^bits, and the maximum of ~index over
+                              // them (the lowest violating index, complemented); zeroed in front of the digit kernel
+  uint32_t pad2[2];
 };
 
 struct SortBuffers {
@@ -74,12 +81,18 @@ struct SortBuffers {
 // k_sort.hip
 int sort_set_attributes(const char** failed);
 void launch_build_tables(hipStream_t st, const Affine* in, uint32_t n, uint32_t c, uint32_t W, AffPacked* tables);
-void launch_digits(hipStream_t st, const Plan& p, const u256* scalars, int scalars_mont, void* digits);
+// p.bits != 0: the bounded kernels, which zero and then count into counters->viol
+void launch_digits(hipStream_t st, const Plan& p, const u256* scalars, int scalars_mont, void* digits,
+                   PlanCounters* counters);
 // digits + the per-chunk region counts of sort pass 1 in one kernel (Plan::fused_front; zeroes b.coarse_cnt first);
 // follow it with launch_sort(..., have_hist = true)
 void launch_digits_hist(hipStream_t st, const Plan& p, const u256* scalars, int scalars_mont, const SortBuffers& b);
 // have_hist: b.coarse_cnt already holds the counts (launch_digits_hist); otherwise coarse_hist_kernel counts the digits
 void launch_sort(hipStream_t st, const Plan& p, const SortBuffers& b, bool have_hist = false);
+// width scan of n >= 1 scalars; the 32-byte result (u64 bits << 32 | ~lowest widest index, u64 zeros, u64 negatives, 0)
+// lands at the front of `work` (scalar_width_work_bytes(n) bytes)
+size_t scalar_width_work_bytes(size_t n);
+void launch_scalar_width(hipStream_t st, const u256* scalars, uint32_t n, int scalars_mont, uint32_t sign, void* work);
 void launch_be32_to_le(hipStream_t st, const uint32_t* in, size_t words, uint32_t* out);
 void launch_ark_affine_to_affine(hipStream_t st, const uint8_t* in, uint32_t n, Affine* out);
 
@@ -132,6 +145,9 @@ void launch_test_op(hipStream_t st, int op, const u256* a, const u256* b, u256* 
 void launch_test_op_raw(hipStream_t st, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t count);
 
 // host_msm.hip (host code only)
-Jacobian host_msm(const u256* scalars, int scalars_mont, const Affine* points, size_t n, int threads, bool* ok = nullptr);   // *ok = false: host allocation failed
+// *ok = false: host allocation failed.  width: magnitudes below 2^bits (signed: folded first); *violations / *first
+// (optional) receive the records that exceed it and the lowest index of one -- the sum is then meaningless
+Jacobian host_msm(const u256* scalars, int scalars_mont, const Affine* points, size_t n, int threads, bool* ok = nullptr,
+                  WidthBound width = WidthBound{}, uint64_t* violations = nullptr, uint64_t* first = nullptr);
 
 }  // namespace msm_amd

@@ -168,6 +168,8 @@ struct Batch {
   std::vector<InstanceSlot> slots;
   std::vector<Plan> plans;
   std::vector<int> ws_index;   // workspace each instance ran in (read by the msm_amd_test_* stage tap only)
+  std::vector<size_t> first_index;   // bounded calls: index of each instance's first record in the caller's vector (a
+                                     // call cut into point ranges, run_split), for the message of a violated bound
   bool lone = false;
   void* out = nullptr;
   size_t n_inst = 0;
@@ -285,6 +287,12 @@ struct msm_amd_ctx {
   std::mutex mu;
   std::string last_error;
   uint32_t forced_window = 0;
+  // The width of the instances being submitted (msm_amd_msm_bounded* set it for the length of their call, under mu;
+  // enqueue_msm / run_msm_g2 plan with it); range_first, if set, holds the first record index of every instance
+  // submitted next (run_split), range_at the instance submit_batch_device starts from.
+  WidthBound bound{};
+  const size_t* range_first = nullptr;
+  size_t range_at = 0;
   std::vector<msm_amd_tables*> live_tables;
   std::vector<msm_amd_g2_tables*> live_g2_tables;
   std::vector<msm_amd_ntt_domain*> live_ntt;
@@ -553,15 +561,65 @@ uint32_t auto_window_lone(size_t n) {
   return kMaxWindow;
 }
 
-// `windows` = 0: the per-call pipeline (every signed-digit window owns a bucket set).  `windows` = W_digits > 0: the
-// precomputed-table pipeline, where the [W_digits][n_scalars] digit matrix is sorted as ONE window of
-// W_digits * n_scalars entries whose "point index" addresses the table entry 2^(c w) P_i directly.
-Plan make_plan(size_t n_scalars, uint32_t c, uint32_t windows = 0) {
+// Window of a bounded call (msm_amd_msm_bounded*).  254 bits: the two policies above.  Below: read from the sweep of every
+// window 3..17 at 2^16, 2^18, 2^20, 2^22 points x 1, 8, 16, 32, 64, 128 bits, lone and pipelined, uniform scalars below
+// 2^bits on prepared bases (tools/bounded_bench.py --sweep, profiles/bounded_sweep.txt; ms per MSM).  What it shows:
+//  - the window count W = bits / c + 1 decides first: every window sorts and accumulates all n entries.  One window
+//    that holds the whole scalar (c = bits + 1, no digit is ever negative) is the fastest form of every width up to 16:
+//    8 bits c = 9 (2^22 pipelined 0.57; c = 17: 5.87, c = 5: 2.68), 16 bits c = 17 (2^22: 0.56; c = 9: 0.83, c = 15: 7.4);
+//  - the trap of auto_window is much deeper here, because a short scalar has few other windows to hide it behind: a top
+//    digit of t = bits - (W - 1) c bits puts n entries into 2^t buckets.  32 bits at 2^20 pipelined: c = 17 (t = 15)
+//    0.35, c = 16 (the top window holds the carry alone) 2.2, c = 13 (t = 6) 1.45.  The rule below takes the fewest
+//    windows among the c whose top digit is full (t = c - 1) or wide enough that a bucket stays below the longest work
+//    item (2^t >= n / 512), and the widest top digit if there is none;
+//  - at 2^16 and 2^18 points the 2^16 buckets per window of c = 17 cost more than a fifth window saves: 64 and 128 bits
+//    want c = 13 there (2^18 lone 64 bits: 0.455 | c = 17 0.499; 128 bits: 0.674 | 0.791; pipelined 0.233 | 0.282 and
+//    0.367 | 0.593), and so does every width in a pipeline of 2^16-point instances (32 bits: c = 11 0.163 | c = 17 0.204);
+//  - 128 bits from 2^20 points: c = 10 (W = 13, t = 8) beats the rule's c = 13 at 2^20 (pipelined 1.22 | 1.83, lone
+//    1.94 | 2.78) and ties with it at 2^22 (4.31 | 4.15, lone 5.50 | 5.77): no reading of the other cells explains it,
+//    so it stands as an exception for the width of a 128-bit challenge alone;
+//  - one bit: no window differs by more than the spread (every point lands in slot 1; 2^20 lone 4.49 .. 4.52).
+// Cells where the rule is not the fastest window: 2^16 pipelined 16 bits (c = 9 0.179 | c = 6 0.152), 2^18 pipelined
+// 16 bits (c = 17 0.199 | c = 9 0.181), 2^22 pipelined 128 bits (above); all others within 3 %.  Sizes below 2^15 were
+// not swept: they keep the window of the unbounded call (and still run bits / c + 1 windows of it).
+uint32_t auto_window_bounded(size_t n, uint32_t bits, bool lone) {
+  const uint32_t c0 = lone ? auto_window_lone(n) : auto_window(n);
+  if (bits >= kModulusBits) return c0;
+  const uint32_t l = floor_log2(n);
+  if (l < 15) return c0;
+  uint32_t cmax = (uint32_t)kMaxWindow;
+  if ((!lone && l <= 17) || (l <= 18 && bits / kMaxWindow + 1 >= 4)) cmax = 13;
+  if (l >= 19 && bits > 124 && bits <= 128) return 10;
+  if (bits + 1 <= cmax) return std::max<uint32_t>(kMinWindow, bits + 1);   // one window, every digit positive
+  uint32_t best = cmax, best_W = 0, best_t = 0;
+  bool best_ok = false;
+  for (uint32_t c = 9; c <= cmax; ++c) {
+    const uint32_t W = bits / c + 1, t = bits - (W - 1) * c;
+    const bool ok = t >= std::min(c - 1, l > 9 ? l - 9 : 0u);
+    bool take;
+    if (ok != best_ok) take = ok;
+    else if (ok) take = best_W == 0 || W < best_W || (W == best_W && l >= 19);   // ties: the larger window from 2^19 points
+    else take = best_W == 0 || t > best_t || (t == best_t && l >= 19);
+    if (take) best = c, best_W = W, best_t = t, best_ok = ok;
+  }
+  return best;
+}
+
+// `windows` = 0: the per-call pipeline (every signed-digit window owns a bucket set).  `windows` > 0: the
+// precomputed-table pipeline of a table with that many windows, where the [W_digits][n_scalars] digit matrix is sorted
+// as ONE window of W_digits * n_scalars entries whose "point index" addresses the table entry 2^(c w) P_i directly (the
+// table is window-major: a bounded call's W_digits windows are a prefix of it).
+// `width`: magnitudes stay below 2^width.width() (scalar_width.hip.h) -- W_digits = width / c + 1 windows, of which the
+// top one holds at most c - 1 bits and so absorbs the last carry (254 bits: ceil(255 / c)).  Everything below follows
+// from W_digits, W and n.
+Plan make_plan(size_t n_scalars, uint32_t c, uint32_t windows = 0, WidthBound width = WidthBound{}) {
   Plan p{};
+  p.c = c;
+  p.W_digits = width.width() / c + 1;
+  if (!(width.bits == kScalarBits && !width.sign)) p.bits = width.bits, p.sign = width.sign;   // 254 unsigned: the unbounded plan
+  if (windows) windows = std::min(windows, p.W_digits);
   const size_t n = windows ? n_scalars * windows : n_scalars;
   p.n = (uint32_t)n;
-  p.c = c;
-  p.W_digits = kModulusBits / c + 1;  // signed digits: the top window absorbs the last carry (= ceil(255 / c))
   p.W = windows ? 1u : p.W_digits;
   p.n_scalars = (uint32_t)n_scalars;
   p.wide_digits = c > 15;
@@ -1056,8 +1114,8 @@ int front_buffers(msm_amd_ctx* ctx, Workspace& w, const Plan& p, SortBuffers* sb
 }
 
 // The plan of one instance: make_plan and what depends on whether the instance has the machine to itself.
-Plan instance_plan(size_t n, uint32_t c, uint32_t table_windows, bool lone) {
-  Plan p = make_plan(n, c, table_windows);
+Plan instance_plan(size_t n, uint32_t c, uint32_t table_windows, bool lone, WidthBound width = WidthBound{}) {
+  Plan p = make_plan(n, c, table_windows, width);
   if (lone) p.red_group = pick_reduce_group(p);   // (pipelined small instances: 2^16 -6 %, 2^18 +3 % -- not taken)
   p.rb_threads = lone ? 0u : 64u;                 // one wave per bit-subset sum beside a resident accumulate grid (k_reduce.hip)
   // the tile-staged scatter (1024-thread workgroups, 60 VGPRs, 64 KB of LDS) is for a sort that has the machine to
@@ -1106,7 +1164,7 @@ int enqueue_front(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, const Plan
   if ((rc = convert_scalars(ctx, w, fs, scalar_layout, d_scalars, p.n_scalars, &sc, &sc_mont))) return rc;
   if ((rc = g.convert_bases(fs))) return rc;
   HIP_TRY(ctx, hipEventRecord(slot.ev[EV_CONVERT], fs));
-  if (p.fused_front) launch_digits_hist(fs, p, sc, sc_mont, sb); else launch_digits(fs, p, sc, sc_mont, sb.digits);
+  if (p.fused_front) launch_digits_hist(fs, p, sc, sc_mont, sb); else launch_digits(fs, p, sc, sc_mont, sb.digits, sb.counters);
   HIP_TRY(ctx, hipEventRecord(slot.ev[EV_DIGITS], fs));
   launch_sort(fs, p, sb, p.fused_front);
   HIP_TRY(ctx, hipEventRecord(slot.ev[EV_SORT], fs));
@@ -1193,8 +1251,9 @@ int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_l
     if (!tb) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a table handle of this ctx");
     if (n != tb->n) return fail(ctx, MSM_AMD_INPUT_ERROR, "n differs from the number of points the tables hold");
   }
-  const uint32_t c = tb ? tb->c : (ctx->forced_window ? ctx->forced_window : (lone ? auto_window_lone(n) : auto_window(n)));
-  Plan p = instance_plan(n, c, tb ? tb->W : 0, lone);
+  const WidthBound width = ctx->bound;
+  const uint32_t c = tb ? tb->c : (ctx->forced_window ? ctx->forced_window : auto_window_bounded(n, width.width(), lone));
+  Plan p = instance_plan(n, c, tb ? tb->W : 0, lone, width);
   const bool prepared = point_layout == MSM_AMD_POINT_PREPARED || tb != nullptr;
   AffPacked* const fill = prepared ? nullptr : ctx->convert_into;   // bases cache fill: convert straight into the entry
   // Bases that are not kept (no prepared array, table or cache entry) are not converted: accumulate gathers the external
@@ -1299,6 +1358,9 @@ int submit_batch_device(msm_amd_ctx* ctx, int scalar_layout, int point_layout, s
   if (B.slots.size() < n_inst) B.slots.resize(n_inst);
   B.plans.assign(n_inst, Plan{});
   B.ws_index.assign(n_inst, 0);
+  B.first_index.assign(n_inst, 0);
+  if (ctx->range_first)
+    for (size_t i = 0; i < n_inst; ++i) B.first_index[i] = ctx->range_first[ctx->range_at + i];
   B.lone = lone;
   B.out = out_host;
   B.n_inst = n_inst;
@@ -1331,6 +1393,19 @@ unsigned finish_threads(size_t n_inst) {
 
 // wait_event on s.ev[EV_REDUCE] ran into the ctx's bound: the ctx is stalled, and the error names `what` and the last
 // stage event of the instance the device did get to.
+// msm_amd_last_error of a bounded call that met records beyond its bound
+std::string width_violation_message(const Plan& p, size_t records, size_t instances, size_t instance, size_t n_inst,
+                                    size_t index) {
+  std::string m = std::to_string(records) + " record(s) with a magnitude of 2^" + std::to_string(p.bits) + " or more (" +
+                  (p.sign ? "signed" : "unsigned") + " bound of " + std::to_string(p.bits) + " bits)";
+  if (n_inst > 1)
+    m += " in " + std::to_string(instances) + " of " + std::to_string(n_inst) + " instances; one of them: instance " +
+         std::to_string(instance) + ", index " + std::to_string(index);
+  else
+    m += "; one of them: index " + std::to_string(index);
+  return m + "; the output was not written";
+}
+
 int wait_timed_out(msm_amd_ctx* ctx, const InstanceSlot& s, const std::string& what, const char* tail = "") {
   ctx->stalled = true;
   int reached = -1;
@@ -1355,7 +1430,11 @@ int wait_batch(msm_amd_ctx* ctx, int ticket, bool internal = true) {
   struct Done {
     hipError_t err = hipSuccess;
     float final_ms = 0;
+    uint32_t viol = 0, viol_index = 0;   // a bounded instance: records beyond the bound, the lowest index of one
+    Jacobian res;                        // ... whose result waits here until every instance of the batch has kept its bound
   };
+  bool bounded = false;   // an instance whose bound a record can exceed: nothing is written before all are checked
+  for (size_t i = 0; i < B.n_inst; ++i) bounded = bounded || B.plans[i].bits != 0;
   std::vector<Done> done(B.n_inst);
   const uint32_t timeout_ms = ctx->wait_timeout_ms;
   // instance i: wait for its partial sums, Horner pass, result; instances are independent, each writes its own slot
@@ -1379,7 +1458,13 @@ int wait_batch(msm_amd_ctx* ctx, int ticket, bool internal = true) {
       const Jacobian sum = host_combine((const Jacobian*)s.h_partial, B.plans[i]);
       const Jacobian res = normalise(B.plans[i].on_iso ? iso_to_e(sum) : sum);
       done[i].final_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      std::memcpy((uint8_t*)B.out + i * 96, &res, 96);
+      if (bounded) {
+        const PlanCounters pc = s.counters();
+        if (B.plans[i].bits) done[i].viol = pc.viol[0], done[i].viol_index = ~pc.viol[1];
+        done[i].res = res;
+      } else {
+        std::memcpy((uint8_t*)B.out + i * 96, &res, 96);
+      }
     }
   };
   const unsigned T = std::min<size_t>(finish_threads(B.n_inst), B.n_inst);
@@ -1403,6 +1488,17 @@ int wait_batch(msm_amd_ctx* ctx, int ticket, bool internal = true) {
     accumulate_timings(ctx, B.slots[i], B.plans[i], done[i].final_ms, B.n_inst);
   }
   B.active = false;
+  if (bounded) {   // the GPU work is done either way; a violated bound leaves the output as it was
+    for (size_t i = 0; i < B.n_inst; ++i)
+      if (done[i].viol) {
+        size_t records = 0, instances = 0;
+        for (size_t k = 0; k < B.n_inst; ++k) records += done[k].viol, instances += done[k].viol ? 1 : 0;
+        reap_graveyard(ctx);
+        return fail(ctx, MSM_AMD_INPUT_ERROR, width_violation_message(B.plans[i], records, instances, i, B.n_inst,
+                                                                       B.first_index[i] + done[i].viol_index));
+      }
+    for (size_t i = 0; i < B.n_inst; ++i) std::memcpy((uint8_t*)B.out + i * 96, &done[i].res, 96);
+  }
   ctx->last_waited = ticket;
   reap_graveyard(ctx);
   return MSM_AMD_OK;
@@ -1751,13 +1847,20 @@ int run_split(msm_amd_ctx* ctx, int scalar_layout, int point_layout, const void*
   std::vector<const void*> sp(parts), pp(parts);
   std::vector<size_t> nn(parts);
   std::vector<uint8_t> outs((size_t)parts * 96);
+  std::vector<size_t> first(parts);
   for (unsigned k = 0; k < parts; ++k) {
     const size_t b = n * k / parts, e = n * (k + 1) / parts;
+    first[k] = b;
     sp[k] = (const uint8_t*)scalars + sb * b;
     pp[k] = (const uint8_t*)points + pb * b;
     nn[k] = e - b;
   }
   int rc;
+  ctx->range_first = first.data(), ctx->range_at = 0;
+  struct Reset {
+    msm_amd_ctx* c;
+    ~Reset() { c->range_first = nullptr, c->range_at = 0; }
+  } reset{ctx};
   if (host_buffers) {
     rc = run_batch_host(ctx, scalar_layout, point_layout, parts, sp.data(), pp.data(), nn.data(), outs.data());
   } else {
@@ -2026,6 +2129,7 @@ int run_batch_host(msm_amd_ctx* ctx, int scalar_layout, int point_layout, size_t
     int ticket = -1;
     ctx->convert_into = fill[i];
     ctx->staging_points = !dev_points && !cached[i];
+    ctx->range_at = i;
     rc = submit_batch_device(ctx, scalar_layout, cached[i] ? (int)MSM_AMD_POINT_PREPARED : point_layout, 1, &ds, &dp, &n[i],
                              (uint8_t*)out + i * 96, &ticket, lone ? 1 : 0);
     ctx->convert_into = nullptr;
@@ -2051,6 +2155,20 @@ int stage_upload(msm_amd_ctx* ctx, void* dst, const void* src, size_t bytes) {
   HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, up));
   ctx->upload_stream = up;
   ctx->upload_pending = true;
+  return MSM_AMD_OK;
+}
+
+// The instances submitted while this lives are planned with `width` (ctx->mu is held by the entry point).
+struct BoundScope {
+  msm_amd_ctx* ctx;
+  BoundScope(msm_amd_ctx* c, uint32_t bits, int sign) : ctx(c) { ctx->bound.bits = bits, ctx->bound.sign = (uint32_t)sign; }
+  ~BoundScope() { ctx->bound = WidthBound{}; }
+};
+
+// the (bits, sign) of a bounded entry point `who`
+int bound_args(msm_amd_ctx* ctx, const char* who, uint32_t bits, int sign) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  if (const char* why = width_bound_check(bits, sign)) return fail(ctx, MSM_AMD_INPUT_ERROR, std::string(who) + ": " + why);
   return MSM_AMD_OK;
 }
 
@@ -2347,6 +2465,9 @@ int msm_amd_set_window_size(msm_amd_ctx* ctx, uint32_t window_size) {
 
 uint32_t msm_amd_auto_window_size(size_t n) { return auto_window(n); }
 uint32_t msm_amd_auto_window_size_lone(size_t n) { return auto_window_lone(n); }
+uint32_t msm_amd_auto_window_size_bounded(size_t n, uint32_t bits, int lone) {
+  return auto_window_bounded(n, std::max(1u, std::min(bits, kModulusBits)), lone != 0);
+}
 
 int msm_amd_msm_batch(msm_amd_ctx* ctx, int scalar_layout, int point_layout, size_t n_inst,
                       const void* const* scalars, const void* const* points, const size_t* n, void* out) {
@@ -2655,6 +2776,40 @@ int msm_amd_set_wait_timeout_ms(msm_amd_ctx* ctx, uint32_t timeout_ms) {
 int msm_amd_msm_device(msm_amd_ctx* ctx, int scalar_layout, int point_layout, const void* d_scalars,
                        const void* d_points, size_t n, void* out96_host) {
   return msm_amd_msm_batch_device(ctx, scalar_layout, point_layout, 1, &d_scalars, &d_points, &n, out96_host);
+}
+
+// ---- scalars of bounded width: the entry points above with a plan of bits / c + 1 windows (make_plan) ------------------
+int msm_amd_msm_bounded(msm_amd_ctx* ctx, int scalar_layout, int point_layout, const void* scalars, const void* points,
+                        size_t n, uint32_t bits, int sign, void* out96) {
+  if (int rc = bound_args(ctx, __func__, bits, sign)) return rc;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  ++ctx->bases_cache_call;
+  BoundScope scope(ctx, bits, sign);
+  return run_batch_host(ctx, scalar_layout, point_layout, 1, &scalars, &points, &n, out96);
+}
+
+int msm_amd_msm_batch_bounded_device(msm_amd_ctx* ctx, int scalar_layout, int point_layout, size_t n_inst,
+                                     const void* const* d_scalars, const void* const* d_points, const size_t* n,
+                                     uint32_t bits, int sign, void* out_host) {
+  if (int rc = bound_args(ctx, __func__, bits, sign)) return rc;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  BoundScope scope(ctx, bits, sign);
+  return run_batch_device(ctx, scalar_layout, point_layout, n_inst, d_scalars, d_points, n, out_host);
+}
+
+int msm_amd_submit_batch_bounded_device(msm_amd_ctx* ctx, int scalar_layout, int point_layout, size_t n_inst,
+                                        const void* const* d_scalars, const void* const* d_points, const size_t* n,
+                                        uint32_t bits, int sign, void* out_host, int* ticket) {
+  if (int rc = bound_args(ctx, __func__, bits, sign)) return rc;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  BoundScope scope(ctx, bits, sign);
+  return submit_batch_device(ctx, scalar_layout, point_layout, n_inst, d_scalars, d_points, n, out_host, ticket);
+}
+
+int msm_amd_msm_bounded_device(msm_amd_ctx* ctx, int scalar_layout, int point_layout, const void* d_scalars,
+                               const void* d_points, size_t n, uint32_t bits, int sign, void* out96_host) {
+  return msm_amd_msm_batch_bounded_device(ctx, scalar_layout, point_layout, 1, &d_scalars, &d_points, &n, bits, sign,
+                                          out96_host);
 }
 
 // Conversion of a resident point array to the internal packed form; ctx->mu held by the caller.
@@ -3404,8 +3559,9 @@ int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const v
     if (n != tb->n) return fail(ctx, MSM_AMD_INPUT_ERROR, "n differs from the number of points the tables hold");
   }
   const bool prepared = tb != nullptr || g2_point_layout == MSM_AMD_G2_POINT_PREPARED;
-  const uint32_t c = tb ? tb->c : (ctx->forced_window ? ctx->forced_window : auto_window_lone(n));
-  const Plan p = instance_plan(n, c, tb ? tb->W : 0, true);
+  const WidthBound width = ctx->bound;
+  const uint32_t c = tb ? tb->c : (ctx->forced_window ? ctx->forced_window : auto_window_bounded(n, width.width(), true));
+  const Plan p = instance_plan(n, c, tb ? tb->W : 0, true, width);
   Workspace& w = g2.ws;
   InstanceSlot& slot = g2.slot;
   PointStages g;
@@ -3435,6 +3591,13 @@ int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const v
   const auto t0 = std::chrono::steady_clock::now();
   const Jacobian2 res = host_combine_g2((const Jacobian2*)slot.h_partial, p);
   const float final_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (p.bits) {
+    const PlanCounters pc = slot.counters();
+    if (pc.viol[0]) {
+      reap_graveyard(ctx);
+      return fail(ctx, MSM_AMD_INPUT_ERROR, width_violation_message(p, pc.viol[0], 1, 0, 1, ~pc.viol[1]));
+    }
+  }
   std::memcpy(out192, &res, 192);
   ctx->timings = msm_amd_timings{};
   accumulate_timings(ctx, slot, p, final_ms, 1);
@@ -3495,15 +3658,28 @@ int g2_tables_build_locked(msm_amd_ctx* ctx, int g2_point_layout, const void* d_
 
 extern "C" {
 
-int msm_amd_msm_g2_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars,
-                          const void* d_points, size_t n, void* out192) {
+// msm_amd_msm_g2_device and its bounded form (bits = 0: unbounded)
+static int msm_g2_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars, const void* d_points,
+                         size_t n, uint32_t bits, int sign, void* out192) {
   if (int rc = g2_args(ctx, scalar_layout, g2_point_layout, d_scalars, d_points, n, out192, true)) return rc;
   if (n == 0 && g2_point_layout != MSM_AMD_G2_POINT_TABLES) {   // (a table never holds 0 points: n mismatch below)
     g2_identity_out(out192);
     return MSM_AMD_OK;
   }
   std::lock_guard<std::mutex> lk(ctx->mu);
+  BoundScope scope(ctx, bits, sign);
   return run_msm_g2(ctx, scalar_layout, g2_point_layout, d_scalars, d_points, n, out192);
+}
+
+int msm_amd_msm_g2_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars,
+                          const void* d_points, size_t n, void* out192) {
+  return msm_g2_device(ctx, scalar_layout, g2_point_layout, d_scalars, d_points, n, 0, 0, out192);
+}
+
+int msm_amd_msm_g2_bounded_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars,
+                                  const void* d_points, size_t n, uint32_t bits, int sign, void* out192) {
+  if (int rc = bound_args(ctx, __func__, bits, sign)) return rc;
+  return msm_g2_device(ctx, scalar_layout, g2_point_layout, d_scalars, d_points, n, bits, sign, out192);
 }
 
 int msm_amd_g2_bases_prepare_device(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n,
@@ -3616,20 +3792,33 @@ int msm_amd_test_g2_tables_read(msm_amd_ctx* ctx, const msm_amd_g2_tables* table
   return MSM_AMD_OK;
 }
 
-int msm_amd_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points,
-                   size_t n, void* out192) {
+// msm_amd_msm_g2 and its bounded form (bits = 0: unbounded)
+static int msm_g2_host(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points,
+                       size_t n, uint32_t bits, int sign, void* out192) {
   if (int rc = g2_args(ctx, scalar_layout, g2_point_layout, scalars, points, n, out192)) return rc;
   if (n == 0) {
     g2_identity_out(out192);
     return MSM_AMD_OK;
   }
   std::lock_guard<std::mutex> lk(ctx->mu);
+  BoundScope scope(ctx, bits, sign);
   G2State& g = ctx->g2;
   const size_t pb = n * msm_amd_g2_point_bytes(g2_point_layout);
   if (int rc = g2_stage_scalars(ctx, scalars, n)) return rc;
   if (int rc = ensure(ctx, g.in_points, pb)) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(g.in_points.p, points, pb, hipMemcpyHostToDevice, ctx->stream));
   return run_msm_g2(ctx, scalar_layout, g2_point_layout, g.in_scalars.p, g.in_points.p, n, out192);
+}
+
+int msm_amd_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points,
+                   size_t n, void* out192) {
+  return msm_g2_host(ctx, scalar_layout, g2_point_layout, scalars, points, n, 0, 0, out192);
+}
+
+int msm_amd_msm_g2_bounded(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points,
+                           size_t n, uint32_t bits, int sign, void* out192) {
+  if (int rc = bound_args(ctx, __func__, bits, sign)) return rc;
+  return msm_g2_host(ctx, scalar_layout, g2_point_layout, scalars, points, n, bits, sign, out192);
 }
 
 // Stage tap of the G2 MSM (test aid): plan, plan counters (behind the partial points in the G2 slot, as for a G1
@@ -4761,6 +4950,54 @@ int msm_amd_fr_sumcheck_round(msm_amd_ctx* ctx, int scalar_layout, int order, in
 int msm_amd_fr_sumcheck_round_device(msm_amd_ctx* ctx, int scalar_layout, int order, int form, const void* d_in, size_t n,
                                      size_t n_vec, size_t stride, void* g_out, float* kernel_ms) {
   return fr_sumcheck_round_call(ctx, false, scalar_layout, order, form, d_in, n, n_vec, stride, g_out, kernel_ms);
+}
+
+}  // extern "C"
+
+// ---- width scan (msm_amd_scalar_width*): through device_call; the 32-byte result comes back as the call's values ----------
+namespace {
+
+int scalar_width_call(msm_amd_ctx* ctx, bool host, int scalar_layout, const void* scalars, size_t n, int sign, uint32_t* bits,
+                      uint64_t* stats) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_scalar_width" : "msm_amd_scalar_width_device";
+  if (const char* why = scalar_width_check(scalar_layout, scalars, n, sign, bits))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  WidthStats r;
+  if (n != 0) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    CallState& s = ctx->calls;
+    d.host_in = host ? 1u : 0u;
+    d.in[0] = scalars, d.in_bytes[0] = n * 32;
+    d.work[0] = {&s.work, scalar_width_work_bytes(n)};
+    d.values_bytes = 32;
+    const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
+      launch_scalar_width(st, (const u256*)io.in[0], (uint32_t)n, scalar_layout == MSM_AMD_SCALAR_MONT_LE, (uint32_t)sign,
+                          s.work.p);
+      io.values = s.work.p;
+      return MSM_AMD_OK;
+    });
+    if (rc) return rc;
+    uint64_t v[4];
+    std::memcpy(v, s.h_values, 32);
+    r.bits = (uint32_t)(v[0] >> 32), r.widest = (uint32_t)~(uint32_t)v[0], r.zeros = v[1], r.negatives = v[2];
+  }
+  scalar_width_out(r, bits, stats);
+  return MSM_AMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_scalar_width(msm_amd_ctx* ctx, int scalar_layout, const void* scalars, size_t n, int sign, uint32_t* bits,
+                         uint64_t* stats) {
+  return scalar_width_call(ctx, true, scalar_layout, scalars, n, sign, bits, stats);
+}
+int msm_amd_scalar_width_device(msm_amd_ctx* ctx, int scalar_layout, const void* d_scalars, size_t n, int sign, uint32_t* bits,
+                                uint64_t* stats) {
+  return scalar_width_call(ctx, false, scalar_layout, d_scalars, n, sign, bits, stats);
 }
 
 }  // extern "C"
