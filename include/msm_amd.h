@@ -1232,6 +1232,80 @@ enum { MSM_AMD_MLE_CALL_BIND = 0, MSM_AMD_MLE_CALL_EVAL = 1, MSM_AMD_MLE_CALL_EQ
 int msm_amd_test_fr_mle_plan(int call, int order, int form, size_t n, size_t n_vec, uint32_t n_bind, uint32_t chunk_log,
                              uint32_t tile_log, uint64_t counts[8]);
 
+/* ---- Poseidon over Fr: permutations, hashes and Merkle trees ------------------------------------------------------------
+ * The algebraic hash of the circomlib / circomlibjs / iden3 family (Grassi et al., S-box x^5) over BN254 Fr for a state of
+ * t = 2 .. 5 records: Semaphore / Tornado style membership trees, Poseidon-Merkle commitments to columns that
+ * msm_amd_ntt_device or msm_amd_fr_matvec_device leave on the device, the commitment hashes of Nova / Spartan style provers.
+ * The textbook schedule, rounds 0-based, for rho < r_f + r_p:
+ *   s[i] += ark[rho t + i];  s[i] = s[i]^5 for every i when rho < r_f/2 or rho >= r_f/2 + r_p, else for i = 0 only;
+ *   s'[i] = sum_j mds[i t + j] s[j].
+ * Records, layouts (MSM_AMD_SCALAR_MONT_LE, _CANON_LE; anything else: MSM_AMD_INPUT_ERROR), "any 256-bit word is taken mod
+ * r", fully reduced outputs (unique bytes), 16-byte alignment of device pointers, the bounded waits and msm_amd_last_error
+ * are those of msm_amd_fr_map*.  Every call serialises on the ctx.  A count of 2^32 or more is MSM_AMD_INPUT_ERROR; n == 0
+ * (n_idx == 0) is MSM_AMD_OK and touches nothing.  The host twins msm_amd_host_poseidon_* (no ctx, no GPU; the same bodies
+ * compiled for the host) take the constants directly and make the same checks; threads <= 0: up to 16 host threads; no
+ * byte depends on the thread count.
+ * (Development knob at msm_amd_init: MSM_AMD_POSEIDON_TOP_LOG = 0 .. 10, default 8 (profiles/poseidon_ab.txt): the levels
+ * of a tree of at most 2^TOP nodes run in one workgroup.  No byte of a result depends on it.) */
+typedef struct msm_amd_poseidon_params msm_amd_poseidon_params;
+/* The constants of the Poseidon paper's reference generator (generate_parameters_grain: field 1, S-box 0, 254 bits) for
+ * (t, r_f, r_p): (r_f + r_p) t round constants into ark_out and the t x t matrix, row-major, into mds_out, as records of
+ * scalar_layout.  With r_f = 8 and r_p = 56, 57, 56, 60 for t = 2, 3, 4, 5 these are circomlib's.  Pure host call.
+ * MSM_AMD_INPUT_ERROR: t outside 2 .. 5, r_f odd or zero, r_f + r_p > 128, a null output, an unknown layout. */
+int msm_amd_poseidon_constants(uint32_t t, uint32_t r_f, uint32_t r_p, int scalar_layout, void* ark_out, void* mds_out);
+/* Constants of the caller (or of msm_amd_poseidon_constants) in host memory -> a handle that keeps their Montgomery residues
+ * in one device allocation.  msm_amd_destroy frees the handles the caller left.  In every call below a handle of another
+ * kind or of another ctx, or a freed one, is MSM_AMD_INPUT_ERROR. */
+int msm_amd_poseidon_params_build(msm_amd_ctx* ctx, uint32_t t, uint32_t r_f, uint32_t r_p, int scalar_layout, const void* ark,
+                                  const void* mds, msm_amd_poseidon_params** out);
+int msm_amd_poseidon_params_info(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, uint32_t* t, uint32_t* r_f,
+                                 uint32_t* r_p, size_t* device_bytes);   /* any output pointer may be null */
+int msm_amd_poseidon_params_free(msm_amd_ctx* ctx, msm_amd_poseidon_params* params);
+/* n states of t records, back to back -> n states.  out == in is allowed, a partial overlap is MSM_AMD_INPUT_ERROR. */
+int msm_amd_poseidon_permute(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* in, size_t n,
+                             void* out);
+int msm_amd_poseidon_permute_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* d_in,
+                                    size_t n, void* d_out, float* kernel_ms);
+int msm_amd_host_poseidon_permute(uint32_t t, uint32_t r_f, uint32_t r_p, int scalar_layout, const void* ark, const void* mds,
+                                  const void* in, size_t n, int threads, void* out);
+/* n groups of t - 1 records -> n digests: state = [tag, in_0 .. in_(t-2)], digest = word 0 of the permuted state.  tag32 is
+ * one record in HOST memory; null is 0, which gives circomlib's poseidon([...]).  out == in is allowed for t = 2 only, where
+ * digest i replaces the one record it was computed from.  For t >= 3 digest i would land on a record of group i / (t - 1),
+ * which another lane reads, and nothing orders the lanes of two workgroups: there `out` must be disjoint from all of `in`,
+ * any overlap is MSM_AMD_INPUT_ERROR. */
+int msm_amd_poseidon_hash(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* tag32,
+                          const void* in, size_t n, void* out);
+int msm_amd_poseidon_hash_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout,
+                                 const void* tag32 /* HOST memory */, const void* d_in, size_t n, void* d_out, float* kernel_ms);
+int msm_amd_host_poseidon_hash(uint32_t t, uint32_t r_f, uint32_t r_p, int scalar_layout, const void* ark, const void* mds,
+                               const void* tag32, const void* in, size_t n, int threads, void* out);
+/* The tree of arity a = t - 1 (t >= 3) over n_leaves = a^d leaves, d >= 1; any other count is MSM_AMD_INPUT_ERROR: padding is
+ * the caller's policy.  Leaves are field elements and are not written.  `tree` receives the (a^d - 1) / (a - 1) inner nodes
+ * level by level, the parents of the leaves first, the root last; a node is the hash of its a children under tag32.  A
+ * tree that overlaps the leaves is MSM_AMD_INPUT_ERROR.  root32: optional, 32 bytes of HOST memory for the root. */
+int msm_amd_poseidon_merkle_build(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* tag32,
+                                  const void* leaves, size_t n_leaves, void* tree, void* root32);
+int msm_amd_poseidon_merkle_build_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout,
+                                         const void* tag32 /* HOST memory */, const void* d_leaves, size_t n_leaves,
+                                         void* d_tree, void* root32 /* HOST memory */, float* kernel_ms);
+int msm_amd_host_poseidon_merkle_build(uint32_t t, uint32_t r_f, uint32_t r_p, int scalar_layout, const void* ark, const void* mds,
+                                       const void* tag32, const void* leaves, size_t n_leaves, int threads, void* tree,
+                                       void* root32);
+/* The authentication paths of n_idx leaves of such a tree.  idx: leaf indices in HOST memory for every form; an index >=
+ * n_leaves is MSM_AMD_INPUT_ERROR, found before anything is launched.  out: d (a - 1) sibling records per index, the level
+ * of the leaves first, the siblings of a level in child order with the node's own place left out; n_idx d (a - 1) < 2^32.
+ * out must not overlap leaves or tree. */
+int msm_amd_poseidon_merkle_paths(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* leaves,
+                                  size_t n_leaves, const void* tree, const uint64_t* idx, size_t n_idx, void* out);
+int msm_amd_poseidon_merkle_paths_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout,
+                                         const void* d_leaves, size_t n_leaves, const void* d_tree,
+                                         const uint64_t* idx /* HOST memory */, size_t n_idx, void* d_out, float* kernel_ms);
+int msm_amd_host_poseidon_merkle_paths(uint32_t t, int scalar_layout, const void* leaves, size_t n_leaves, const void* tree,
+                                       const uint64_t* idx, size_t n_idx, int threads, void* out);
+/* Test aid (no ctx, CPU only): the launches of a tree build at top_log (0 .. 10).  counts: [0] launches, [1] d, [2] inner
+ * nodes, [3] levels of the last workgroup, [4] its nodes, [5 .. 7] 0, [8 + k] nodes of launch k (the last: counts[4]). */
+int msm_amd_test_poseidon_plan(uint32_t t, size_t n_leaves, uint32_t top_log, uint64_t counts[40]);
+
 /* Test aid (no ctx): the plan of a scan over n_vec vectors of n at a tile of 2^tile_log (2 .. 9): out[0] levels, out[1]
  * launches (2 levels - 1), out[2] tiles of the first level over all vectors, out[3] records of ctx-owned device memory */
 int msm_amd_test_fr_plan(size_t n, size_t n_vec, uint32_t tile_log, uint64_t out[4]);

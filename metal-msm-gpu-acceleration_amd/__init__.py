@@ -132,6 +132,12 @@ EXPORTS = [
     "msm_amd_msm_bounded", "msm_amd_msm_bounded_device", "msm_amd_msm_batch_bounded_device",
     "msm_amd_submit_batch_bounded_device", "msm_amd_msm_g2_bounded", "msm_amd_msm_g2_bounded_device",
     "msm_amd_host_msm_bounded", "msm_amd_host_msm_g2_bounded", "msm_amd_auto_window_size_bounded",
+    "msm_amd_poseidon_constants", "msm_amd_poseidon_params_build", "msm_amd_poseidon_params_info",
+    "msm_amd_poseidon_params_free", "msm_amd_poseidon_permute", "msm_amd_poseidon_permute_device",
+    "msm_amd_host_poseidon_permute", "msm_amd_poseidon_hash", "msm_amd_poseidon_hash_device", "msm_amd_host_poseidon_hash",
+    "msm_amd_poseidon_merkle_build", "msm_amd_poseidon_merkle_build_device", "msm_amd_host_poseidon_merkle_build",
+    "msm_amd_poseidon_merkle_paths", "msm_amd_poseidon_merkle_paths_device", "msm_amd_host_poseidon_merkle_paths",
+    "msm_amd_test_poseidon_plan",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -423,6 +429,27 @@ def _lib():
                                                      c_void_p]
         L.msm_amd_test_fr_mle_plan.argtypes = [c_int, c_int, c_int, c_size_t, c_size_t, c_uint32, c_uint32, c_uint32,
                                                POINTER(c_uint64)]
+        if hasattr(L, "msm_amd_poseidon_constants"):   # (an MSM_AMD_LIB build from before the Poseidon calls still loads)
+            shape = [c_uint32, c_uint32, c_uint32, c_int, c_void_p, c_void_p]   # t, r_f, r_p, layout, ark, mds
+            L.msm_amd_poseidon_constants.argtypes = shape
+            L.msm_amd_poseidon_params_build.argtypes = [c_void_p] + shape + [c_void_p]
+            L.msm_amd_poseidon_params_info.argtypes = [c_void_p, c_void_p] + [POINTER(c_uint32)] * 3 + [POINTER(c_size_t)]
+            L.msm_amd_poseidon_params_free.argtypes = [c_void_p, c_void_p]
+            L.msm_amd_poseidon_permute.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]
+            L.msm_amd_poseidon_permute_device.argtypes = L.msm_amd_poseidon_permute.argtypes + [POINTER(c_float)]
+            L.msm_amd_host_poseidon_permute.argtypes = shape + [c_void_p, c_size_t, c_int, c_void_p]
+            L.msm_amd_poseidon_hash.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+            L.msm_amd_poseidon_hash_device.argtypes = L.msm_amd_poseidon_hash.argtypes + [POINTER(c_float)]
+            L.msm_amd_host_poseidon_hash.argtypes = shape + [c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+            L.msm_amd_poseidon_merkle_build.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
+            L.msm_amd_poseidon_merkle_build_device.argtypes = L.msm_amd_poseidon_merkle_build.argtypes + [POINTER(c_float)]
+            L.msm_amd_host_poseidon_merkle_build.argtypes = shape + [c_void_p, c_void_p, c_size_t, c_int, c_void_p, c_void_p]
+            L.msm_amd_poseidon_merkle_paths.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t,
+                                                        c_void_p]
+            L.msm_amd_poseidon_merkle_paths_device.argtypes = L.msm_amd_poseidon_merkle_paths.argtypes + [POINTER(c_float)]
+            L.msm_amd_host_poseidon_merkle_paths.argtypes = [c_uint32, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int,
+                                                             c_void_p]
+            L.msm_amd_test_poseidon_plan.argtypes = [c_uint32, c_size_t, c_uint32, POINTER(c_uint64)]
         L.msm_amd_generate_instance_host.argtypes = [c_uint64, c_size_t, c_int, c_void_p, c_void_p, c_int]
         L.msm_amd_test_op_ifma.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         if hasattr(L, "msm_amd_scalar_width"):   # (an MSM_AMD_LIB build from before the bounded-width calls still loads)
@@ -1117,6 +1144,83 @@ class MsmConfig:
                                                     c_void_p(d_y), ctypes.byref(ms)))
         return ms.value
 
+    # ---- Poseidon over Fr: permutations, hashes and Merkle trees -------------------------------------
+    def poseidon_params_build(self, t, r_f, r_p, ark: bytes, mds: bytes, scalar_layout=SCALAR_MONT_LE) -> "PoseidonParams":
+        """The constants of one Poseidon instance on this ctx's device (msm_amd_poseidon_params_build): (r_f + r_p) t
+        records of round constants and t t records of the matrix, the caller's own or those of poseidon_constants()."""
+        h = c_void_p()
+        self._check(_lib().msm_amd_poseidon_params_build(self.h, t, r_f, r_p, scalar_layout, ark, mds, ctypes.byref(h)))
+        return PoseidonParams(self, h)
+
+    def poseidon_params(self, t, r_f=8, r_p=None) -> "PoseidonParams":
+        """The handle of the generated constants (circomlib's at the default rounds)"""
+        r_p = POSEIDON_R_P[t] if r_p is None else r_p
+        return self.poseidon_params_build(t, r_f, r_p, *poseidon_constants(t, r_f, r_p))
+
+    def poseidon_permute(self, params, data: bytes, n: int, scalar_layout=SCALAR_MONT_LE) -> bytes:
+        """n states of t host records -> n states (msm_amd_poseidon_permute)"""
+        t = _poseidon_t(self, params)
+        out = ctypes.create_string_buffer(max(1, 32 * n * t))
+        self._check(_lib().msm_amd_poseidon_permute(self.h, _poseidon_handle(params), scalar_layout, data, n, out))
+        return out.raw[:32 * n * t]
+
+    def poseidon_permute_device(self, params, d_in, n: int, d_out, scalar_layout=SCALAR_MONT_LE) -> float:
+        """The same on device-resident states, d_out == d_in or disjoint (msm_amd_poseidon_permute_device); returns
+        kernel_ms."""
+        ms = c_float(0)
+        self._check(_lib().msm_amd_poseidon_permute_device(self.h, _poseidon_handle(params), scalar_layout, c_void_p(d_in), n,
+                                                           c_void_p(d_out), ctypes.byref(ms)))
+        return ms.value
+
+    def poseidon_hash(self, params, data: bytes, n: int, scalar_layout=SCALAR_MONT_LE, tag: bytes = None) -> bytes:
+        """n groups of t - 1 host records -> n digests (msm_amd_poseidon_hash); tag: one record, None for 0"""
+        out = ctypes.create_string_buffer(max(1, 32 * n))
+        self._check(_lib().msm_amd_poseidon_hash(self.h, _poseidon_handle(params), scalar_layout, tag, data, n, out))
+        return out.raw[:32 * n]
+
+    def poseidon_hash_device(self, params, d_in, n: int, d_out, scalar_layout=SCALAR_MONT_LE, tag: bytes = None) -> float:
+        """The same on device-resident records (msm_amd_poseidon_hash_device); returns kernel_ms."""
+        ms = c_float(0)
+        self._check(_lib().msm_amd_poseidon_hash_device(self.h, _poseidon_handle(params), scalar_layout, tag, c_void_p(d_in), n,
+                                                        c_void_p(d_out), ctypes.byref(ms)))
+        return ms.value
+
+    def poseidon_merkle_build(self, params, leaves: bytes, n_leaves: int, scalar_layout=SCALAR_MONT_LE, tag: bytes = None):
+        """The inner nodes of the tree over host leaves, the root last, and the root (msm_amd_poseidon_merkle_build)"""
+        nodes = merkle_nodes(_poseidon_t(self, params), n_leaves)
+        tree, root = ctypes.create_string_buffer(max(1, 32 * nodes)), ctypes.create_string_buffer(32)
+        self._check(_lib().msm_amd_poseidon_merkle_build(self.h, _poseidon_handle(params), scalar_layout, tag, leaves, n_leaves,
+                                                         tree, root))
+        return tree.raw[:32 * nodes], root.raw
+
+    def poseidon_merkle_build_device(self, params, d_leaves, n_leaves: int, d_tree, scalar_layout=SCALAR_MONT_LE,
+                                     tag: bytes = None, want_root=True):
+        """The same on device-resident leaves into device memory (msm_amd_poseidon_merkle_build_device); returns
+        (root or None, kernel_ms)."""
+        ms, root = c_float(0), ctypes.create_string_buffer(32) if want_root else None
+        self._check(_lib().msm_amd_poseidon_merkle_build_device(self.h, _poseidon_handle(params), scalar_layout, tag,
+                                                                c_void_p(d_leaves), n_leaves, c_void_p(d_tree), root,
+                                                                ctypes.byref(ms)))
+        return (root.raw if want_root else None), ms.value
+
+    def poseidon_merkle_paths(self, params, leaves: bytes, n_leaves: int, tree: bytes, idx, scalar_layout=SCALAR_MONT_LE) -> bytes:
+        """d (a - 1) sibling records per leaf index of idx, host memory throughout (msm_amd_poseidon_merkle_paths)"""
+        size = 32 * len(idx) * merkle_path_records(_poseidon_t(self, params), n_leaves)
+        out = ctypes.create_string_buffer(max(1, size))
+        self._check(_lib().msm_amd_poseidon_merkle_paths(self.h, _poseidon_handle(params), scalar_layout, leaves, n_leaves, tree,
+                                                         _csr_u64(idx), len(idx), out))
+        return out.raw[:size]
+
+    def poseidon_merkle_paths_device(self, params, d_leaves, n_leaves: int, d_tree, idx, d_out,
+                                     scalar_layout=SCALAR_MONT_LE) -> float:
+        """The same from device-resident leaves and tree into device memory (msm_amd_poseidon_merkle_paths_device);
+        returns kernel_ms."""
+        ms = c_float(0)
+        self._check(_lib().msm_amd_poseidon_merkle_paths_device(self.h, _poseidon_handle(params), scalar_layout,
+                                                                c_void_p(d_leaves), n_leaves, c_void_p(d_tree), _csr_u64(idx),
+                                                                len(idx), c_void_p(d_out), ctypes.byref(ms)))
+        return ms.value
+
     # ---- multilinear tables over Fr and sumcheck rounds: n_vec tables of n = 2^m records, `stride` records apart ----
     def fr_mle_bind(self, data: bytes, r: bytes, n: int, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, n_vec=1, stride=None,
                     out: bytes = None) -> bytes:
@@ -1667,6 +1771,122 @@ def host_fr_lincomb(data: bytes, k: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1
     if st != OK:
         raise MsmError(st)
     return out.raw[:32 * n]
+
+
+class PoseidonParams:
+    """The constants of one Poseidon instance of one MsmConfig (msm_amd_poseidon_params_*)."""
+
+    def __init__(self, cfg, handle):
+        self.cfg, self.h = cfg, handle
+
+    def info(self) -> dict:
+        t, r_f, r_p, nbytes = c_uint32(0), c_uint32(0), c_uint32(0), c_size_t(0)
+        self.cfg._check(_lib().msm_amd_poseidon_params_info(self.cfg.h, self.h, ctypes.byref(t), ctypes.byref(r_f),
+                                                            ctypes.byref(r_p), ctypes.byref(nbytes)))
+        return {"t": t.value, "r_f": r_f.value, "r_p": r_p.value, "device_bytes": nbytes.value}
+
+    def free(self):
+        self.cfg._check(_lib().msm_amd_poseidon_params_free(self.cfg.h, self.h))
+
+
+POSEIDON_R_P = {2: 56, 3: 57, 4: 56, 5: 60}   # circomlib's partial rounds at r_f = 8
+
+
+def _poseidon_handle(params):
+    return params.h if isinstance(params, PoseidonParams) else params
+
+
+def _poseidon_t(cfg, params) -> int:
+    """t of a handle, to size a host output; 0 for what is no handle: the call itself then reports it"""
+    t = c_uint32(0)
+    st = _lib().msm_amd_poseidon_params_info(cfg.h, _poseidon_handle(params), ctypes.byref(t), None, None, None)
+    return t.value if st == OK else 0
+
+
+def merkle_depth(t, n_leaves) -> int:
+    """d with n_leaves = (t - 1)^d, d >= 1; 0 if there is none"""
+    a, d = t - 1, 0
+    if a < 2 or n_leaves < a:
+        return 0
+    while n_leaves > 1:
+        if n_leaves % a:
+            return 0
+        n_leaves, d = n_leaves // a, d + 1
+    return d
+
+
+def merkle_nodes(t, n_leaves) -> int:
+    """inner nodes of the tree msm_amd_poseidon_merkle_build* write (0 for a count that is no power of the arity)"""
+    return (n_leaves - 1) // (t - 2) if merkle_depth(t, n_leaves) else 0
+
+
+def merkle_path_records(t, n_leaves) -> int:
+    """sibling records per leaf index of msm_amd_poseidon_merkle_paths*"""
+    return merkle_depth(t, n_leaves) * (t - 2)
+
+
+def poseidon_constants(t, r_f=8, r_p=None, scalar_layout=SCALAR_MONT_LE):
+    """(ark, mds) of the reference generator (msm_amd_poseidon_constants): circomlib's at the default rounds"""
+    r_p = POSEIDON_R_P.get(t, 0) if r_p is None else r_p
+    ok = 2 <= t <= 5 and 0 <= r_f + r_p <= 128
+    ark = ctypes.create_string_buffer(max(1, 32 * (r_f + r_p) * t if ok else 1))
+    mds = ctypes.create_string_buffer(max(1, 32 * t * t if ok else 1))
+    st = _lib().msm_amd_poseidon_constants(t, r_f, r_p, scalar_layout, ark, mds)
+    if st != OK:
+        raise MsmError(st)
+    return ark.raw[:32 * (r_f + r_p) * t], mds.raw[:32 * t * t]
+
+
+def host_poseidon_permute(t, r_f, r_p, ark: bytes, mds: bytes, data: bytes, n: int, scalar_layout=SCALAR_MONT_LE,
+                          threads=0) -> bytes:
+    """Host twin of MsmConfig.poseidon_permute (no GPU)."""
+    out = ctypes.create_string_buffer(max(1, 32 * n * t))
+    st = _lib().msm_amd_host_poseidon_permute(t, r_f, r_p, scalar_layout, ark, mds, data, n, threads, out)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:32 * n * t]
+
+
+def host_poseidon_hash(t, r_f, r_p, ark: bytes, mds: bytes, data: bytes, n: int, scalar_layout=SCALAR_MONT_LE, tag: bytes = None,
+                       threads=0) -> bytes:
+    """Host twin of MsmConfig.poseidon_hash (no GPU)."""
+    out = ctypes.create_string_buffer(max(1, 32 * n))
+    st = _lib().msm_amd_host_poseidon_hash(t, r_f, r_p, scalar_layout, ark, mds, tag, data, n, threads, out)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:32 * n]
+
+
+def host_poseidon_merkle_build(t, r_f, r_p, ark: bytes, mds: bytes, leaves: bytes, n_leaves: int, scalar_layout=SCALAR_MONT_LE,
+                               tag: bytes = None, threads=0):
+    """Host twin of MsmConfig.poseidon_merkle_build (no GPU): (tree, root)."""
+    nodes = merkle_nodes(t, n_leaves) if t >= 3 else 0
+    tree, root = ctypes.create_string_buffer(max(1, 32 * nodes)), ctypes.create_string_buffer(32)
+    st = _lib().msm_amd_host_poseidon_merkle_build(t, r_f, r_p, scalar_layout, ark, mds, tag, leaves, n_leaves, threads, tree, root)
+    if st != OK:
+        raise MsmError(st)
+    return tree.raw[:32 * nodes], root.raw
+
+
+def host_poseidon_merkle_paths(t, leaves: bytes, n_leaves: int, tree: bytes, idx, scalar_layout=SCALAR_MONT_LE,
+                               threads=0) -> bytes:
+    """Host twin of MsmConfig.poseidon_merkle_paths (no GPU)."""
+    size = 32 * len(idx) * (merkle_path_records(t, n_leaves) if t >= 3 else 0)
+    out = ctypes.create_string_buffer(max(1, size))
+    st = _lib().msm_amd_host_poseidon_merkle_paths(t, scalar_layout, leaves, n_leaves, tree, _csr_u64(idx), len(idx), threads, out)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:size]
+
+
+def test_poseidon_plan(t, n_leaves, top_log=8) -> dict:
+    """The launches of a tree build (msm_amd_test_poseidon_plan)"""
+    out = (c_uint64 * 40)()
+    st = _lib().msm_amd_test_poseidon_plan(t, n_leaves, top_log, out)
+    if st != OK:
+        raise MsmError(st)
+    return {"launches": out[0], "depth": out[1], "nodes": out[2], "tail_levels": out[3], "tail_nodes": out[4],
+            "per_launch": list(out[8:8 + out[0]])}
 
 
 def sumcheck_values(form, n_vec) -> int:

@@ -3,7 +3,8 @@
 // classic trick), the prefix products in two phases (the product of every range, then the ranges from their carries),
 // the polynomial calls likewise (a range's Horner value, then the ranges from the sums behind them), the sparse product
 // row by row over ranges of equal entry count, the multilinear calls step by step over ranges of outputs (a round: the sums
-// of every range of pairs, added in range order);
+// of every range of pairs, added in range order), the Poseidon calls permutation by permutation over ranges, a tree level by
+// level (and the constants of the paper's Grain generator, msm_amd_poseidon_constants);
 // and the argument checks the twins share with the host driver (msm_host.hip).  The bytes of a result are unique, so the
 // way a twin cuts the work shows nowhere.
 #include <hip/hip_runtime.h>
@@ -713,6 +714,274 @@ int msm_amd_test_fr_plan(size_t n, size_t n_vec, uint32_t tile_log, uint64_t out
   if (n == 0 || n_vec == 0) return MSM_AMD_OK;
   const FrScanPlan p = fr_scan_plan(n, n_vec, tile_log);
   out[0] = p.levels, out[1] = p.launches, out[2] = p.tiles[0] * n_vec, out[3] = p.records;
+  return MSM_AMD_OK;
+}
+
+}  // extern "C"
+
+// ---- Poseidon (fr_poseidon.hip.h): the checks, the constants of the reference generator, the twins ---------------------------
+namespace msm_amd {
+
+const char* poseidon_shape_check(uint64_t t, uint64_t r_f, uint64_t r_p) {
+  if (t < kPoseidonMinT || t > kPoseidonMaxT) return "t must be 2 .. 5";
+  if (r_f == 0 || (r_f & 1u)) return "r_f must be even and at least 2";
+  if (r_f > kPoseidonMaxRounds || r_p > kPoseidonMaxRounds || r_f + r_p > kPoseidonMaxRounds) return "r_f + r_p > 128";
+  return nullptr;
+}
+
+const char* poseidon_constants_check(uint64_t t, uint64_t r_f, uint64_t r_p, int scalar_layout, const void* ark, const void* mds) {
+  if (const char* why = poseidon_shape_check(t, r_f, r_p)) return why;
+  if (!fr_layout_known(scalar_layout)) return kMleLayout;
+  if (!ark || !mds) return "null ark or mds";
+  return nullptr;
+}
+
+const char* poseidon_call_check(int kind, uint32_t t, int scalar_layout, const void* in, uint64_t n, const void* out, bool device) {
+  if (!fr_layout_known(scalar_layout)) return kMleLayout;
+  if (n >> 32) return "n >= 2^32";
+  if (n == 0) return nullptr;
+  if (!in || !out) return "null pointer with n > 0";
+  if (device && (((uintptr_t)in | (uintptr_t)out) & 15u)) return kMleAlign;
+  const uint64_t in_bytes = n * (kind == kPoseidonHash ? t - 1 : t) * 32, out_bytes = n * (kind == kPoseidonHash ? 1 : t) * 32;
+  if (kind == kPoseidonPermute || t == 2)
+    return fr_overlap_ok(out, in, in_bytes) ? nullptr : "the output must be the input itself or disjoint from it";
+  // digest i would land on a record that the lane of group i / (t - 1) reads, and nothing orders two workgroups
+  return spans_apart(in, in_bytes, out, out_bytes) ? nullptr : "with t >= 3 the digests must be disjoint from the input";
+}
+
+const char* poseidon_merkle_check(uint32_t t, int scalar_layout, const void* leaves, uint64_t n_leaves, const void* tree,
+                                  bool device) {
+  if (!fr_layout_known(scalar_layout)) return kMleLayout;
+  if (t < 3) return "a tree needs t >= 3: its arity is t - 1";
+  if ((n_leaves >> 32) || !poseidon_tree_depth(n_leaves, t - 1)) return "n_leaves must be (t - 1)^d, d >= 1, below 2^32";
+  if (!leaves || !tree) return "null leaves or tree";
+  if (device && (((uintptr_t)leaves | (uintptr_t)tree) & 15u)) return kMleAlign;
+  if (!spans_apart(leaves, n_leaves * 32, tree, (n_leaves - 1) / (t - 2) * 32)) return "the tree must not overlap the leaves";
+  return nullptr;
+}
+
+const char* poseidon_paths_check(uint32_t t, int scalar_layout, const void* leaves, uint64_t n_leaves, const void* tree,
+                                 const uint64_t* idx, uint64_t n_idx, const void* out, bool device) {
+  if (const char* why = poseidon_merkle_check(t, scalar_layout, leaves, n_leaves, tree, device)) return why;
+  const uint64_t per = (uint64_t)poseidon_tree_depth(n_leaves, t - 1) * (t - 2);
+  if ((n_idx >> 32) || ((n_idx * per) >> 32)) return "n_idx * d * (t - 2) >= 2^32";
+  if (n_idx == 0) return nullptr;
+  if (!idx || !out) return "null idx or out with n_idx > 0";
+  if (device && ((uintptr_t)out & 15u)) return kMleAlign;
+  for (uint64_t k = 0; k < n_idx; ++k)
+    if (idx[k] >= n_leaves) return "a leaf index is not below n_leaves";
+  if (!spans_apart(leaves, n_leaves * 32, out, n_idx * per * 32) ||
+      !spans_apart(tree, (n_leaves - 1) / (t - 2) * 32, out, n_idx * per * 32))
+    return "the paths must not overlap the leaves or the tree";
+  return nullptr;
+}
+
+void poseidon_build_image(uint32_t t, uint32_t r_f, uint32_t r_p, int scalar_layout, const void* ark, const void* mds,
+                          std::vector<u256>* image) {
+  const uint32_t rounds = r_f + r_p;
+  image->assign(poseidon_image_records(t, rounds), u256_zero());
+  for (uint32_t k = 0; k < poseidon_ark_records(t, rounds); ++k) (*image)[k] = fr_read_record(scalar_layout, (const uint8_t*)ark + k * 32);
+  for (uint32_t k = 0; k < t * t; ++k) (*image)[poseidon_mds_at(t, rounds) + k] = fr_read_record(scalar_layout, (const uint8_t*)mds + k * 32);
+}
+
+namespace {
+
+// The Grain LFSR of the Poseidon paper's generate_parameters_grain: 80 bits, the fields most significant bit first
+struct PoseidonGrain {
+  uint8_t s[80];
+  PoseidonGrain(uint32_t t, uint32_t r_f, uint32_t r_p) {
+    int at = 0;
+    auto field = [&](uint32_t value, int bits) {
+      for (int b = bits - 1; b >= 0; --b) s[at++] = (value >> b) & 1u;
+    };
+    field(1, 2), field(0, 4), field(254, 12), field(t, 12), field(r_f, 10), field(r_p, 10);
+    while (at < 80) s[at++] = 1;
+    for (int k = 0; k < 160; ++k) update();
+  }
+  uint8_t update() {
+    const uint8_t b = s[62] ^ s[51] ^ s[38] ^ s[23] ^ s[13] ^ s[0];
+    std::memmove(s, s + 1, 79);
+    s[79] = b;
+    return b;
+  }
+  uint8_t bit() {
+    uint8_t first = update();
+    while (!first) update(), first = update();
+    return update();
+  }
+  u256 integer() {   // 254 bits, the first one most significant
+    u256 x = u256_zero();
+    for (int b = 253; b >= 0; --b) x.v[b >> 5] |= (uint32_t)bit() << (b & 31);
+    return x;
+  }
+};
+
+bool below_modulus(const u256& x) {
+  u256 d;
+  return u256_sub(d, x, Fr::modulus()) != 0;
+}
+
+int host_poseidon_constants(uint32_t t, uint32_t r_f, uint32_t r_p, int layout, void* ark_out, void* mds_out) {
+  if (poseidon_constants_check(t, r_f, r_p, layout, ark_out, mds_out)) return MSM_AMD_INPUT_ERROR;
+  PoseidonGrain g(t, r_f, r_p);
+  for (uint32_t k = 0; k < (r_f + r_p) * t;) {
+    const u256 x = g.integer();
+    if (below_modulus(x)) host_put(layout, (uint8_t*)ark_out, k++, Fr::to_mont(x));
+  }
+  u256 xy[2 * kPoseidonMaxT];
+  for (bool again = true; again;) {
+    for (uint32_t k = 0; k < 2 * t; ++k) xy[k] = Fr::to_mont(Fr::reduce_once(g.integer()));   // 2^254 < 2 r
+    again = false;
+    for (uint32_t a = 0; a < 2 * t; ++a)
+      for (uint32_t b = a + 1; b < 2 * t; ++b) again |= u256_eq(xy[a], xy[b]);
+    // (the paper's script also draws again when some x_i + y_j is zero)
+    for (uint32_t i = 0; i < t; ++i)
+      for (uint32_t j = 0; j < t; ++j) again |= u256_is_zero(Fr::add(xy[i], xy[t + j]));
+  }
+  for (uint32_t i = 0; i < t; ++i)
+    for (uint32_t j = 0; j < t; ++j) host_put(layout, (uint8_t*)mds_out, i * t + j, ntt_fr_inv(Fr::add(xy[i], xy[t + j])));
+  return MSM_AMD_OK;
+}
+
+struct PoseidonHostImage {
+  const u256* p;
+  u256 record(uint32_t i) const { return p[i]; }
+};
+struct PoseidonHostShape {
+  uint32_t t, r_f, r_p;
+  int layout;
+  std::vector<u256> image;
+  u256 tag;
+};
+
+// a range of at least 16 permutations per thread, so that a short call starts none
+unsigned poseidon_workers(int threads, uint64_t n) { return worker_count(threads, (size_t)((n + 15) >> 4)); }
+
+template <int T, int KIND>
+void host_poseidon_run(const PoseidonHostShape& c, const uint8_t* in, uint64_t n, int threads, uint8_t* out) {
+  constexpr int IN = KIND == kPoseidonHash ? T - 1 : T, FIRST = T - IN;
+  const PoseidonHostImage image{c.image.data()};
+  for_ranges(poseidon_workers(threads, n), n, [&](unsigned, size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; ++i) {
+      u256 s[T];
+      s[0] = c.tag;
+      for (int j = 0; j < IN; ++j) s[FIRST + j] = host_get(c.layout, in, i * IN + j);
+      poseidon_permute<T>(s, image, c.r_f, c.r_p);
+      if (KIND == kPoseidonHash) host_put(c.layout, out, i, s[0]);
+      else
+        for (int j = 0; j < T; ++j) host_put(c.layout, out, i * T + j, s[j]);
+    }
+  });
+}
+
+template <int KIND>
+void host_poseidon_kind(const PoseidonHostShape& c, const void* in, uint64_t n, int threads, void* out) {
+  const uint8_t* src = (const uint8_t*)in;
+  uint8_t* dst = (uint8_t*)out;
+  if (c.t == 2) host_poseidon_run<2, KIND>(c, src, n, threads, dst);
+  else if (c.t == 3) host_poseidon_run<3, KIND>(c, src, n, threads, dst);
+  else if (c.t == 4) host_poseidon_run<4, KIND>(c, src, n, threads, dst);
+  else host_poseidon_run<5, KIND>(c, src, n, threads, dst);
+}
+
+// the shape of a twin's call; false: an argument is wrong
+bool host_poseidon_shape(uint32_t t, uint32_t r_f, uint32_t r_p, int layout, const void* ark, const void* mds, const void* tag32,
+                         PoseidonHostShape* c) {
+  if (poseidon_constants_check(t, r_f, r_p, layout, ark, mds)) return false;
+  c->t = t, c->r_f = r_f, c->r_p = r_p, c->layout = layout;
+  poseidon_build_image(t, r_f, r_p, layout, ark, mds, &c->image);
+  c->tag = tag32 ? fr_read_record(layout, tag32) : u256_zero();
+  return true;
+}
+
+int host_poseidon_call(int kind, uint32_t t, uint32_t r_f, uint32_t r_p, int layout, const void* ark, const void* mds,
+                       const void* tag32, const void* in, size_t n, int threads, void* out) {
+  PoseidonHostShape c;
+  if (!host_poseidon_shape(t, r_f, r_p, layout, ark, mds, tag32, &c)) return MSM_AMD_INPUT_ERROR;
+  if (poseidon_call_check(kind, t, layout, in, n, out, false)) return MSM_AMD_INPUT_ERROR;
+  if (n == 0) return MSM_AMD_OK;
+  if (kind == kPoseidonHash) host_poseidon_kind<kPoseidonHash>(c, in, n, threads, out);
+  else host_poseidon_kind<kPoseidonPermute>(c, in, n, threads, out);
+  return MSM_AMD_OK;
+}
+
+int host_poseidon_merkle_build(uint32_t t, uint32_t r_f, uint32_t r_p, int layout, const void* ark, const void* mds,
+                               const void* tag32, const void* leaves, size_t n_leaves, int threads, void* tree, void* root32) {
+  PoseidonHostShape c;
+  if (!host_poseidon_shape(t, r_f, r_p, layout, ark, mds, tag32, &c)) return MSM_AMD_INPUT_ERROR;
+  if (poseidon_merkle_check(t, layout, leaves, n_leaves, tree, false)) return MSM_AMD_INPUT_ERROR;
+  const PoseidonTreePlan plan = poseidon_tree_plan(n_leaves, t - 1, 0);
+  const uint8_t* src = (const uint8_t*)leaves;
+  for (uint32_t k = 0; k < plan.depth; ++k) {
+    uint8_t* dst = (uint8_t*)tree + plan.offset[k] * 32;
+    host_poseidon_kind<kPoseidonHash>(c, src, plan.count[k], threads, dst);
+    src = dst;
+  }
+  if (root32) std::memcpy(root32, (const uint8_t*)tree + (plan.nodes - 1) * 32, 32);
+  return MSM_AMD_OK;
+}
+
+int host_poseidon_merkle_paths(uint32_t t, int layout, const void* leaves, size_t n_leaves, const void* tree, const uint64_t* idx,
+                               size_t n_idx, int threads, void* out) {
+  if (t < kPoseidonMinT || t > kPoseidonMaxT) return MSM_AMD_INPUT_ERROR;
+  if (poseidon_paths_check(t, layout, leaves, n_leaves, tree, idx, n_idx, out, false)) return MSM_AMD_INPUT_ERROR;
+  if (n_idx == 0) return MSM_AMD_OK;
+  const uint32_t arity = t - 1;
+  const PoseidonTreePlan plan = poseidon_tree_plan(n_leaves, arity, 0);
+  const uint64_t per = (uint64_t)plan.depth * (arity - 1);
+  for_ranges(worker_count(threads, (n_idx + 63) >> 6), n_idx, [&](unsigned, size_t lo, size_t hi) {
+    for (size_t q = lo; q < hi; ++q) {
+      uint64_t pos = idx[q], at = q * per;
+      for (uint32_t level = 0; level < plan.depth; ++level, pos /= arity) {
+        const uint8_t* src = level == 0 ? (const uint8_t*)leaves : (const uint8_t*)tree + plan.offset[level - 1] * 32;
+        for (uint32_t child = 0; child < arity; ++child)
+          if (child != pos % arity) host_put(layout, (uint8_t*)out, at++, host_get(layout, src, pos - pos % arity + child));
+      }
+    }
+  });
+  return MSM_AMD_OK;
+}
+
+}  // namespace
+}  // namespace msm_amd
+
+extern "C" {
+
+int msm_amd_poseidon_constants(uint32_t t, uint32_t r_f, uint32_t r_p, int scalar_layout, void* ark_out, void* mds_out) {
+  return msm_amd::host_poseidon_constants(t, r_f, r_p, scalar_layout, ark_out, mds_out);
+}
+
+int msm_amd_host_poseidon_permute(uint32_t t, uint32_t r_f, uint32_t r_p, int scalar_layout, const void* ark, const void* mds,
+                                  const void* in, size_t n, int threads, void* out) {
+  return msm_amd::host_poseidon_call(msm_amd::kPoseidonPermute, t, r_f, r_p, scalar_layout, ark, mds, nullptr, in, n, threads, out);
+}
+
+int msm_amd_host_poseidon_hash(uint32_t t, uint32_t r_f, uint32_t r_p, int scalar_layout, const void* ark, const void* mds,
+                               const void* tag32, const void* in, size_t n, int threads, void* out) {
+  return msm_amd::host_poseidon_call(msm_amd::kPoseidonHash, t, r_f, r_p, scalar_layout, ark, mds, tag32, in, n, threads, out);
+}
+
+int msm_amd_host_poseidon_merkle_build(uint32_t t, uint32_t r_f, uint32_t r_p, int scalar_layout, const void* ark, const void* mds,
+                                       const void* tag32, const void* leaves, size_t n_leaves, int threads, void* tree,
+                                       void* root32) {
+  return msm_amd::host_poseidon_merkle_build(t, r_f, r_p, scalar_layout, ark, mds, tag32, leaves, n_leaves, threads, tree, root32);
+}
+
+int msm_amd_host_poseidon_merkle_paths(uint32_t t, int scalar_layout, const void* leaves, size_t n_leaves, const void* tree,
+                                       const uint64_t* idx, size_t n_idx, int threads, void* out) {
+  return msm_amd::host_poseidon_merkle_paths(t, scalar_layout, leaves, n_leaves, tree, idx, n_idx, threads, out);
+}
+
+int msm_amd_test_poseidon_plan(uint32_t t, size_t n_leaves, uint32_t top_log, uint64_t counts[40]) {
+  using namespace msm_amd;
+  if (!counts || t < 3 || t > kPoseidonMaxT || top_log > kPoseidonMaxTopLog || ((uint64_t)n_leaves >> 32) ||
+      !poseidon_tree_depth(n_leaves, t - 1))
+    return MSM_AMD_INPUT_ERROR;
+  const PoseidonTreePlan p = poseidon_tree_plan(n_leaves, t - 1, top_log);
+  uint64_t c[40] = {p.launches, p.depth, p.nodes, p.tail_levels, p.tail_nodes, 0, 0, 0};
+  for (uint32_t k = 0; k + 1 < p.launches; ++k) c[8 + k] = p.count[k];
+  c[8 + p.launches - 1] = p.tail_nodes;
+  std::memcpy(counts, c, sizeof c);
   return MSM_AMD_OK;
 }
 

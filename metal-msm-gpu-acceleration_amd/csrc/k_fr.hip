@@ -41,6 +41,13 @@
 //                          lanes; LOW: 2^K consecutive records).
 //   fr_eq_table_kernel<S>  one lane per 2^S outputs: the product of the factors of the index bits below, then S doublings;
 //                          the 2 m factors come by value.
+//   fr_poseidon_kernel<T, KIND>  (fr_poseidon.hip.h) one lane per permutation of a state of T records (KIND: the bare
+//                          permutation, or the hash of T - 1 records under a tag); the workgroup stages the constants image
+//                          in LDS once and every lane reads it at wave-uniform addresses; nothing per lane comes from memory
+//                          between the load of its inputs and the store of its outputs.
+//   fr_poseidon_tail_kernel<T>  the last levels of a Merkle tree in ONE workgroup: a level, a barrier, the next level from the
+//                          nodes just stored to the tree.
+//   fr_merkle_paths_kernel one lane per sibling record of an authentication path: a gather over the leaves and the tree.
 // Phases are ordered by launch order on one stream only; no kernel reads what another workgroup of its launch wrote.
 // LDS images are eight word planes; slot m sits at m + (m >> log2(records per lane)), so that the unit-stride accesses
 // and the walks of the lanes (stride = records per lane) are both free of bank conflicts, bar one 2-way per access.
@@ -540,6 +547,107 @@ __global__ void __launch_bounds__(kFrMapThreads) fr_eq_table_kernel(FrMleEqArgs 
   eq_spread<S>(a, acc, idx, low);
 }
 
+// ---- Poseidon (fr_poseidon.hip.h) --------------------------------------------------------------------------------------------
+struct FrPoseidonArgs {
+  const uint32_t* image;     // the constants image: raw records
+  const uint32_t* in;
+  uint32_t* out;
+  uint64_t n;                // lanes with work (the tail: nodes of its first level)
+  uint32_t records;          // of the image
+  uint32_t r_f, r_p;
+  uint32_t levels;           // the tail: levels of the workgroup
+  int layout;
+  u256 tag;
+};
+struct FrMerklePathArgs {
+  const uint32_t* leaves;
+  const uint32_t* tree;
+  const uint64_t* idx;
+  uint32_t* out;
+  uint64_t total, n_leaves;  // total = n_idx depth (arity - 1) records
+  uint32_t depth, arity;
+  int layout;
+};
+
+// The constants of a workgroup in LDS: every lane of a wave reads the same record, one broadcast of two b128 reads
+struct PoseidonLds {
+  const uint4* lds;
+  __device__ __forceinline__ u256 record(uint32_t i) const {
+    const uint4 a = lds[2 * i], b = lds[2 * i + 1];
+    u256 x;
+    x.v[0] = a.x, x.v[1] = a.y, x.v[2] = a.z, x.v[3] = a.w, x.v[4] = b.x, x.v[5] = b.y, x.v[6] = b.z, x.v[7] = b.w;
+    return x;
+  }
+};
+__device__ __forceinline__ PoseidonLds poseidon_stage(const FrPoseidonArgs& a, uint4* dst) {
+  const uint4* src = (const uint4*)a.image;
+  for (uint32_t i = threadIdx.x; i < 2 * a.records; i += kFrMapThreads) dst[i] = src[i];
+  __syncthreads();
+  return PoseidonLds{dst};
+}
+
+// One lane, one permutation: between the load of its inputs and the store of its outputs a lane reads LDS only.
+template <int T, int KIND>
+__device__ __forceinline__ void poseidon_lane(const FrPoseidonArgs& a, const PoseidonLds& c, const uint32_t* in, uint32_t* out,
+                                              uint64_t i) {
+  constexpr int IN = KIND == kPoseidonHash ? T - 1 : T, FIRST = T - IN;
+  u256 s[T];
+  if (KIND == kPoseidonHash) s[0] = a.tag;
+  MSM_UNROLL for (int j = 0; j < IN; ++j) s[FIRST + j] = fr_load(a.layout, load_rec(in + (i * IN + j) * 8));
+  poseidon_permute<T>(s, c, a.r_f, a.r_p);
+  if (KIND == kPoseidonHash) {
+    store_rec(out + i * 8, fr_store(a.layout, s[0]));
+  } else {
+    MSM_UNROLL for (int j = 0; j < T; ++j) store_rec(out + (i * T + j) * 8, fr_store(a.layout, s[j]));
+  }
+}
+
+// One lane per permutation.  In place: a permutation's lane reads and writes its own t records.  A hash with t = 2 reads
+// and writes record i alone.  For t >= 3 digest i lands on a record that lane i / (t - 1) reads, and no order holds between
+// the lanes of two workgroups: the checks refuse every overlap of such a call (poseidon_call_check).
+template <int T, int KIND>
+__global__ void __launch_bounds__(kFrMapThreads) fr_poseidon_kernel(FrPoseidonArgs a) {
+  extern __shared__ uint4 poseidon_lds[];
+  const PoseidonLds c = poseidon_stage(a, poseidon_lds);
+  const uint64_t i = (uint64_t)blockIdx.x * kFrMapThreads + threadIdx.x;
+  if (i < a.n) poseidon_lane<T, KIND>(a, c, a.in, a.out, i);
+}
+
+// The last levels of a tree in one workgroup: level after level, a barrier between them; a level's nodes go to the tree
+// and the level above reads them from there.  Every lane reaches every barrier: the trip counts are uniform.
+template <int T>
+__global__ void __launch_bounds__(kFrMapThreads) fr_poseidon_tail_kernel(FrPoseidonArgs a) {
+  extern __shared__ uint4 poseidon_lds[];
+  const PoseidonLds c = poseidon_stage(a, poseidon_lds);
+  const uint32_t* src = a.in;
+  uint32_t* dst = a.out;
+  uint32_t count = (uint32_t)a.n;
+  NTT_NO_UNROLL for (uint32_t level = 0; level < a.levels; ++level) {
+    NTT_NO_UNROLL for (uint32_t i = threadIdx.x; i < count; i += kFrMapThreads) poseidon_lane<T, kPoseidonHash>(a, c, src, dst, i);
+    __syncthreads();
+    src = dst, dst += (uint64_t)count * 8, count /= (uint32_t)(T - 1);
+  }
+}
+
+// One lane per sibling record: the walk up to its level, then one record of the leaves or of the tree
+__global__ void __launch_bounds__(kFrMapThreads) fr_merkle_paths_kernel(FrMerklePathArgs a) {
+  const uint64_t id = (uint64_t)blockIdx.x * kFrMapThreads + threadIdx.x;
+  if (id >= a.total) return;
+  const uint32_t sibs = a.arity - 1, per = a.depth * sibs;
+  const uint64_t q = id / per;
+  const uint32_t rem = (uint32_t)(id - q * per), level = rem / sibs, sib = rem - level * sibs;
+  uint64_t pos = a.idx[q], count = a.n_leaves;
+  const uint32_t* src = a.leaves;
+  const uint32_t* above = a.tree;
+  NTT_NO_UNROLL for (uint32_t k = 0; k < level; ++k) {
+    pos /= a.arity, count /= a.arity;
+    src = above, above += count * 8;
+  }
+  const uint32_t own = (uint32_t)(pos % a.arity);
+  const uint64_t child = pos - own + (sib < own ? sib : sib + 1);
+  store_rec(a.out + id * 8, fr_store(a.layout, fr_load(a.layout, load_rec(src + child * 8))));
+}
+
 template <int OP>
 void launch_map_op(hipStream_t st, int layout, const u256& k, const void* a, const void* b, const void* c, size_t n, void* out) {
   hipLaunchKernelGGL(fr_map_kernel<OP>, dim3((uint32_t)((n + kFrMapThreads - 1) / kFrMapThreads)), dim3(kFrMapThreads), 0, st,
@@ -745,6 +853,63 @@ void launch_fr_eq_table(hipStream_t st, int layout, const u256* point_by_bit, ui
   const dim3 grid((uint32_t)((lanes + kFrMapThreads - 1) / kFrMapThreads));
   if (wide) hipLaunchKernelGGL(fr_eq_table_kernel<(int)kFrMleEqSpread>, grid, dim3(kFrMapThreads), 0, st, a);
   else hipLaunchKernelGGL(fr_eq_table_kernel<0>, grid, dim3(kFrMapThreads), 0, st, a);
+}
+
+namespace {
+
+FrPoseidonArgs poseidon_args(const PoseidonLaunch& c, const void* in, uint64_t n, void* out) {
+  FrPoseidonArgs a{};
+  a.image = (const uint32_t*)c.image, a.in = (const uint32_t*)in, a.out = (uint32_t*)out, a.n = n;
+  a.records = poseidon_image_records(c.t, c.r_f + c.r_p), a.r_f = c.r_f, a.r_p = c.r_p;
+  a.layout = c.layout, a.tag = c.tag;
+  return a;
+}
+
+template <int KIND>
+void launch_poseidon_kind(hipStream_t st, uint32_t t, const FrPoseidonArgs& a) {
+  const dim3 grid((uint32_t)((a.n + kFrMapThreads - 1) / kFrMapThreads)), block(kFrMapThreads);
+  const uint32_t lds = a.records * 32;
+  if (t == 2) hipLaunchKernelGGL((fr_poseidon_kernel<2, KIND>), grid, block, lds, st, a);
+  else if (t == 3) hipLaunchKernelGGL((fr_poseidon_kernel<3, KIND>), grid, block, lds, st, a);
+  else if (t == 4) hipLaunchKernelGGL((fr_poseidon_kernel<4, KIND>), grid, block, lds, st, a);
+  else hipLaunchKernelGGL((fr_poseidon_kernel<5, KIND>), grid, block, lds, st, a);
+}
+
+}  // namespace
+
+void launch_poseidon(hipStream_t st, const PoseidonLaunch& c, int kind, const void* in, uint64_t n, void* out) {
+  const FrPoseidonArgs a = poseidon_args(c, in, n, out);
+  if (kind == kPoseidonHash) launch_poseidon_kind<kPoseidonHash>(st, c.t, a);
+  else launch_poseidon_kind<kPoseidonPermute>(st, c.t, a);
+}
+
+uint32_t launch_poseidon_tree(hipStream_t st, const PoseidonLaunch& c, const void* leaves, uint64_t n_leaves, uint32_t top_log,
+                              void* tree) {
+  const PoseidonTreePlan plan = poseidon_tree_plan(n_leaves, c.t - 1, top_log);
+  const uint32_t* src = (const uint32_t*)leaves;
+  uint32_t* dst = (uint32_t*)tree;
+  const uint32_t level_launches = plan.launches - 1;
+  for (uint32_t k = 0; k < level_launches; ++k) {
+    launch_poseidon_kind<kPoseidonHash>(st, c.t, poseidon_args(c, src, plan.count[k], dst));
+    src = dst, dst += plan.count[k] * 8;
+  }
+  FrPoseidonArgs a = poseidon_args(c, src, plan.count[level_launches], dst);
+  a.levels = plan.tail_levels;
+  const dim3 one(1), block(kFrMapThreads);
+  const uint32_t lds = a.records * 32;
+  if (c.t == 3) hipLaunchKernelGGL(fr_poseidon_tail_kernel<3>, one, block, lds, st, a);
+  else if (c.t == 4) hipLaunchKernelGGL(fr_poseidon_tail_kernel<4>, one, block, lds, st, a);
+  else hipLaunchKernelGGL(fr_poseidon_tail_kernel<5>, one, block, lds, st, a);
+  return plan.launches;
+}
+
+void launch_merkle_paths(hipStream_t st, int layout, uint32_t arity, uint32_t depth, const void* leaves, uint64_t n_leaves,
+                         const void* tree, const void* idx, uint64_t n_idx, void* out) {
+  FrMerklePathArgs a{};
+  a.leaves = (const uint32_t*)leaves, a.tree = (const uint32_t*)tree, a.idx = (const uint64_t*)idx, a.out = (uint32_t*)out;
+  a.total = n_idx * depth * (arity - 1), a.n_leaves = n_leaves, a.depth = depth, a.arity = arity, a.layout = layout;
+  hipLaunchKernelGGL(fr_merkle_paths_kernel, dim3((uint32_t)((a.total + kFrMapThreads - 1) / kFrMapThreads)), dim3(kFrMapThreads),
+                     0, st, a);
 }
 
 uint32_t launch_fr_inv_products(hipStream_t st, int layout, const void* in, uint64_t n, uint32_t tile_log, void* work_v) {

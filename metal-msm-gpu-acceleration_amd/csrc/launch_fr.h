@@ -7,6 +7,7 @@
 
 #include "fr_mat.hip.h"
 #include "fr_mle.hip.h"
+#include "fr_poseidon.hip.h"
 #include "fr_vec.hip.h"
 
 namespace msm_amd {
@@ -114,6 +115,24 @@ uint32_t launch_fr_mle_bind(hipStream_t st, const FrMleBindLaunch& c);
 // out[i] = prod_b (bit b of i ? point_by_bit[b] : 1 - point_by_bit[b]), i < 2^m
 void launch_fr_eq_table(hipStream_t st, int layout, const u256* point_by_bit, uint32_t m, void* out);
 
+// Poseidon (fr_poseidon.hip.h).  `image` is the constants image of a parameter handle in device memory; the tag is a reduced
+// Montgomery residue.  Every pointer is 16-byte aligned device memory.
+struct PoseidonLaunch {
+  const void* image;
+  uint32_t t, r_f, r_p;
+  int layout;
+  u256 tag;            // hash and tree
+};
+// n states of t records -> n states (kPoseidonPermute, out may be in), or n groups of t - 1 records -> n digests
+// (kPoseidonHash; out is in only for t = 2, else disjoint from it: see fr_poseidon_kernel)
+void launch_poseidon(hipStream_t st, const PoseidonLaunch& c, int kind, const void* in, uint64_t n, void* out);
+// every launch of poseidon_tree_plan(n_leaves, t - 1, top_log) in stream order; returns the number of launches
+uint32_t launch_poseidon_tree(hipStream_t st, const PoseidonLaunch& c, const void* leaves, uint64_t n_leaves, uint32_t top_log,
+                              void* tree);
+// out: depth (arity - 1) sibling records per index, bottom level first; idx: n_idx checked leaf indices in device memory
+void launch_merkle_paths(hipStream_t st, int layout, uint32_t arity, uint32_t depth, const void* leaves, uint64_t n_leaves,
+                         const void* tree, const void* idx, uint64_t n_idx, void* out);
+
 // host_fr.hip.  Each check returns null or what is wrong, for msm_amd_last_error.
 bool fr_layout_known(int scalar_layout);   // MONT_LE and CANON_LE
 bool fr_mode_known(int mode);
@@ -148,6 +167,20 @@ const char* fr_mle_eval_check(int scalar_layout, int order, const void* point, c
 const char* fr_eq_table_check(int scalar_layout, int order, const void* point, uint64_t m, const void* out, bool device);
 const char* fr_sumcheck_check(int scalar_layout, int order, int form, const void* in, uint64_t n, uint64_t n_vec,
                               uint64_t stride, const void* g_out, bool device);
+// The Poseidon calls.  The shape (t, r_f, r_p) is that of a parameter handle or of the twin's arguments; every check first
+// looks at the layout, then at the sizes, lets n == 0 pass where a call has one, then at pointers, alignment and overlap.
+const char* poseidon_shape_check(uint64_t t, uint64_t r_f, uint64_t r_p);
+const char* poseidon_constants_check(uint64_t t, uint64_t r_f, uint64_t r_p, int scalar_layout, const void* ark, const void* mds);
+// kind: kPoseidonPermute (n t records in and out, out == in or disjoint) or kPoseidonHash (n (t - 1) in, n out)
+const char* poseidon_call_check(int kind, uint32_t t, int scalar_layout, const void* in, uint64_t n, const void* out, bool device);
+const char* poseidon_merkle_check(uint32_t t, int scalar_layout, const void* leaves, uint64_t n_leaves, const void* tree,
+                                  bool device);
+// idx in host memory: every index is looked at
+const char* poseidon_paths_check(uint32_t t, int scalar_layout, const void* leaves, uint64_t n_leaves, const void* tree,
+                                 const uint64_t* idx, uint64_t n_idx, const void* out, bool device);
+// the constants of a caller in host memory -> the image of poseidon_image_records(t, r_f + r_p) reduced Montgomery residues
+void poseidon_build_image(uint32_t t, uint32_t r_f, uint32_t r_p, int scalar_layout, const void* ark, const void* mds,
+                          std::vector<u256>* image);
 // The device image of a checked matrix in host memory: values reduced mod r and deduplicated into the dictionary (ids 0
 // and 1 are always 1 and r - 1, whether they occur or not: dict_records counts them, n_distinct only what occurs), the
 // plan at (long_rows, seg_log), every part at its place of fr_mat_image

@@ -210,6 +210,12 @@ struct msm_amd_fr_matrix : DeviceHandle {
   FrMatImage at{};
 };
 
+// The constants of one Poseidon instance (msm_amd_poseidon_params_*, msm_amd_ctx::live_poseidon): d_mem is the constants image
+// of fr_poseidon.hip.h, reduced Montgomery residues.
+struct msm_amd_poseidon_params : DeviceHandle {
+  uint32_t t = 0, r_f = 0, r_p = 0;
+};
+
 // Buffers of the blocking vector calls (device_call below): the staging of the host-buffer forms, the 64-byte record a
 // call reads back with its page-locked copy (the PointCounters of a check, decompress or compress call; T and the zero
 // count of a batch inversion), the device-side work buffers and two pairs of events behind kernel_ms.  Every such call
@@ -297,11 +303,13 @@ struct msm_amd_ctx {
   std::vector<msm_amd_g2_tables*> live_g2_tables;
   std::vector<msm_amd_ntt_domain*> live_ntt;
   std::vector<msm_amd_fr_matrix*> live_fr_mat;
+  std::vector<msm_amd_poseidon_params*> live_poseidon;
   uint32_t fr_tile_log = kFrTileLog;     // records per tile of a scan, as a power of two (MSM_AMD_FR_TILE_LOG)
   uint32_t fr_mat_long = kFrMatLong;     // rows of a sparse matrix above this many entries take the wave path (MSM_AMD_FR_MAT_LONG)
   bool fr_mat_signs = false;             // the product kernels that skip the product for values 1 and r - 1 (MSM_AMD_FR_MAT_SIGNS)
   uint32_t fr_mat_seg_log = kFrMatSegLog;   // entries per wave of that path, as a power of two (MSM_AMD_FR_MAT_SEG_LOG)
   uint32_t fr_mle_chunk_log = kFrMleChunkLog;   // pairs per wave of a sumcheck round, as a power of two (MSM_AMD_FR_MLE_CHUNK_LOG)
+  uint32_t poseidon_top_log = kPoseidonTopLog;   // tree levels of at most 2^this nodes share the last workgroup (MSM_AMD_POSEIDON_TOP_LOG)
   uint32_t ntt_tile_log = kNttTileLog;   // elements per workgroup of a transform pass, as a power of two (MSM_AMD_NTT_TILE_LOG)
   int next_ws = 0;
   DeviceBuf scratch_a, scratch_b, scratch_c, scratch_b2, scratch_c2;
@@ -927,7 +935,8 @@ int reduce_buffers(msm_amd_ctx* ctx, Workspace& w, const Plan& p, size_t interna
 }
 
 // ---- handles: H = msm_amd_tables (ctx->live_tables), msm_amd_g2_tables (ctx->live_g2_tables), msm_amd_ntt_domain
-// (ctx->live_ntt) or msm_amd_fr_matrix (ctx->live_fr_mat).  ctx->mu is held by the caller, as for every helper here.
+// (ctx->live_ntt), msm_amd_fr_matrix (ctx->live_fr_mat) or msm_amd_poseidon_params (ctx->live_poseidon).  ctx->mu is held by
+// the caller, as for every helper here.
 template <class H>
 const H* find_handle(const std::vector<H*>& live, const void* handle) {
   for (const H* t : live)
@@ -2264,6 +2273,8 @@ int msm_amd_init(int device, msm_amd_ctx** out) {
   if (const char* e = std::getenv("MSM_AMD_FR_MAT_SIGNS")) ctx->fr_mat_signs = std::atoi(e) != 0;
   if (const char* e = std::getenv("MSM_AMD_FR_MLE_CHUNK_LOG"))
     ctx->fr_mle_chunk_log = (uint32_t)std::max((int)kFrMleMinChunkLog, std::min((int)kFrMleMaxChunkLog, std::atoi(e)));
+  if (const char* e = std::getenv("MSM_AMD_POSEIDON_TOP_LOG"))
+    ctx->poseidon_top_log = (uint32_t)std::max(0, std::min((int)kPoseidonMaxTopLog, std::atoi(e)));
   if (const char* e = std::getenv("MSM_AMD_FR_MAT_SEG_LOG"))
     ctx->fr_mat_seg_log = (uint32_t)std::max((int)kFrMatMinSegLog, std::min((int)kFrMatMaxSegLog, std::atoi(e)));
   if (const char* e = std::getenv("MSM_AMD_BASES_CACHE_VERIFY")) ctx->bases_cache_verify = std::strcmp(e, "full") == 0;
@@ -2398,6 +2409,7 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
   handle_release_all(ctx->live_g2_tables);
   handle_release_all(ctx->live_ntt);
   handle_release_all(ctx->live_fr_mat);
+  handle_release_all(ctx->live_poseidon);
   for (DeviceBuf* b : {&ctx->scratch_a, &ctx->scratch_b, &ctx->scratch_c, &ctx->scratch_b2, &ctx->scratch_c2}) kill_buf(*b);
   bases_cache_clear(ctx);   // (entries and unused reserves go through the graveyard)
   for (const msm_amd_ctx::CacheReserve& r : ctx->cache_reserve) ctx->graveyard.push_back(r.d);
@@ -4998,6 +5010,206 @@ int msm_amd_scalar_width(msm_amd_ctx* ctx, int scalar_layout, const void* scalar
 int msm_amd_scalar_width_device(msm_amd_ctx* ctx, int scalar_layout, const void* d_scalars, size_t n, int sign, uint32_t* bits,
                                 uint64_t* stats) {
   return scalar_width_call(ctx, false, scalar_layout, d_scalars, n, sign, bits, stats);
+}
+
+}  // extern "C"
+
+// ---- Poseidon over Fr (msm_amd_poseidon_params_*, msm_amd_poseidon_permute*, _hash*, _merkle_build*, _merkle_paths*) ---------
+// Through device_call.  A parameter handle is validated by membership in ctx->live_poseidon, under the lock and before
+// anything is sized by it; the tag is read once on the host and reaches the kernels by value; the root of a tree comes back
+// through CallState::h_values in the call's one bounded wait; the leaf indices of a paths call are checked on the host and
+// go through the staging in both forms.
+namespace {
+
+const char* const kNotPoseidon = ": not a Poseidon parameter handle of this ctx";
+
+PoseidonLaunch poseidon_launch(const msm_amd_poseidon_params* p, int scalar_layout, const void* tag32) {
+  PoseidonLaunch c{};
+  c.image = p->d_mem, c.t = p->t, c.r_f = p->r_f, c.r_p = p->r_p, c.layout = scalar_layout;
+  c.tag = tag32 ? fr_read_record(scalar_layout, tag32) : u256_zero();
+  return c;
+}
+
+// device memory a call writes must not be the constants
+bool poseidon_clear_of(const msm_amd_poseidon_params* p, const void* out, size_t bytes) {
+  const uintptr_t lo = (uintptr_t)p->d_mem, hi = lo + p->bytes, a = (uintptr_t)out;
+  return !(a < hi && lo < a + bytes);
+}
+
+int poseidon_call(msm_amd_ctx* ctx, const msm_amd_poseidon_params* handle, int kind, bool host, int scalar_layout,
+                  const void* tag32, const void* in, size_t n, void* out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = std::string(kind == kPoseidonHash ? "msm_amd_poseidon_hash" : "msm_amd_poseidon_permute") + (host ? "" : "_device");
+  if (kernel_ms) *kernel_ms = 0.f;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_poseidon_params* p = find_handle(ctx->live_poseidon, handle);
+  if (!p) return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + kNotPoseidon);
+  if (const char* why = poseidon_call_check(kind, p->t, scalar_layout, in, n, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n == 0) return MSM_AMD_OK;
+  const size_t in_bytes = n * (kind == kPoseidonHash ? p->t - 1 : p->t) * 32, out_bytes = n * (kind == kPoseidonHash ? 1 : p->t) * 32;
+  if (!host && !poseidon_clear_of(p, out, out_bytes))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": the output must not overlap the parameters");
+  const PoseidonLaunch c = poseidon_launch(p, scalar_layout, tag32);
+  // the host form of a permutation works in place on the staged copy of its input
+  d.host = host, d.host_in = host, d.in_place = host && kind == kPoseidonPermute, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = in_bytes;
+  d.out = out, d.out_bytes = out_bytes;
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    launch_poseidon(st, c, kind, io.in[0], n, io.out);
+    return MSM_AMD_OK;
+  });
+}
+
+int poseidon_merkle_build_call(msm_amd_ctx* ctx, const msm_amd_poseidon_params* handle, bool host, int scalar_layout,
+                               const void* tag32, const void* leaves, size_t n_leaves, void* tree, void* root32, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_poseidon_merkle_build" : "msm_amd_poseidon_merkle_build_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_poseidon_params* p = find_handle(ctx->live_poseidon, handle);
+  if (!p) return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + kNotPoseidon);
+  if (const char* why = poseidon_merkle_check(p->t, scalar_layout, leaves, n_leaves, tree, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  const PoseidonTreePlan plan = poseidon_tree_plan(n_leaves, p->t - 1, ctx->poseidon_top_log);
+  if (!host && !poseidon_clear_of(p, tree, plan.nodes * 32))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": the tree must not overlap the parameters");
+  const PoseidonLaunch c = poseidon_launch(p, scalar_layout, tag32);
+  CallState& s = ctx->calls;
+  d.host = host, d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = leaves, d.in_bytes[0] = n_leaves * 32;
+  d.out = tree, d.out_bytes = plan.nodes * 32;
+  d.values_bytes = root32 ? 32 : 0;
+  const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
+    launch_poseidon_tree(st, c, io.in[0], n_leaves, ctx->poseidon_top_log, io.out);
+    io.values = (const uint8_t*)io.out + (plan.nodes - 1) * 32;
+    return MSM_AMD_OK;
+  });
+  if (rc == MSM_AMD_OK && root32) std::memcpy(root32, s.h_values, 32);   // a node: already in the call's layout
+  return rc;
+}
+
+int poseidon_merkle_paths_call(msm_amd_ctx* ctx, const msm_amd_poseidon_params* handle, bool host, int scalar_layout,
+                               const void* leaves, size_t n_leaves, const void* tree, const uint64_t* idx, size_t n_idx, void* out,
+                               float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_poseidon_merkle_paths" : "msm_amd_poseidon_merkle_paths_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_poseidon_params* p = find_handle(ctx->live_poseidon, handle);
+  if (!p) return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + kNotPoseidon);
+  if (const char* why = poseidon_paths_check(p->t, scalar_layout, leaves, n_leaves, tree, idx, n_idx, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n_idx == 0) return MSM_AMD_OK;
+  const uint32_t arity = p->t - 1, depth = poseidon_tree_depth(n_leaves, arity);
+  const size_t nodes = (n_leaves - 1) / (arity - 1), out_bytes = n_idx * depth * (arity - 1) * 32;
+  if (!host && !poseidon_clear_of(p, out, out_bytes))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": the paths must not overlap the parameters");
+  d.host = host, d.host_in = host ? 7u : 4u, d.kernel_ms = kernel_ms;
+  d.in[0] = leaves, d.in_bytes[0] = n_leaves * 32;
+  d.in[1] = tree, d.in_bytes[1] = nodes * 32;
+  d.in[2] = idx, d.in_bytes[2] = n_idx * sizeof(uint64_t);
+  d.out = out, d.out_bytes = out_bytes;
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    launch_merkle_paths(st, scalar_layout, arity, depth, io.in[0], n_leaves, io.in[1], io.in[2], n_idx, io.out);
+    return MSM_AMD_OK;
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_poseidon_params_build(msm_amd_ctx* ctx, uint32_t t, uint32_t r_f, uint32_t r_p, int scalar_layout, const void* ark,
+                                  const void* mds, msm_amd_poseidon_params** out) {
+  if (!ctx || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_poseidon_params_build: null pointer");
+  *out = nullptr;
+  if (const char* why = poseidon_constants_check(t, r_f, r_p, scalar_layout, ark, mds))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, std::string("msm_amd_poseidon_params_build: ") + why);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = recover_if_stalled(ctx)) return rc;
+  std::vector<u256> image;
+  poseidon_build_image(t, r_f, r_p, scalar_layout, ark, mds, &image);
+  int up = MSM_AMD_OK;
+  if (int rc = handle_build_tail(ctx, ctx->live_poseidon, image.size() * 32, "the constants of a Poseidon instance",
+                                 "Poseidon parameter build",
+                                 [&](void* d_mem) { up = staged_upload(ctx, d_mem, image.data(), image.size() * 32, ctx->stream); },
+                                 out))
+    return rc;
+  if (up) {   // the upload did not go through: nothing may read the allocation
+    msm_amd_poseidon_params* h = *out;
+    *out = nullptr;
+    const std::string why = ctx->last_error;
+    handle_free(ctx, ctx->live_poseidon, h, "");
+    return fail(ctx, up, "msm_amd_poseidon_params_build: " + why);
+  }
+  (*out)->t = t, (*out)->r_f = r_f, (*out)->r_p = r_p;
+  return MSM_AMD_OK;
+}
+
+int msm_amd_poseidon_params_info(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, uint32_t* t, uint32_t* r_f,
+                                 uint32_t* r_p, size_t* device_bytes) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_poseidon_params* p = find_handle(ctx->live_poseidon, params);
+  if (!p) return fail(ctx, MSM_AMD_INPUT_ERROR, std::string("msm_amd_poseidon_params_info") + kNotPoseidon);
+  if (t) *t = p->t;
+  if (r_f) *r_f = p->r_f;
+  if (r_p) *r_p = p->r_p;
+  if (device_bytes) *device_bytes = p->bytes;
+  return MSM_AMD_OK;
+}
+
+int msm_amd_poseidon_params_free(msm_amd_ctx* ctx, msm_amd_poseidon_params* params) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return handle_free(ctx, ctx->live_poseidon, params, "msm_amd_poseidon_params_free: not a Poseidon parameter handle of this ctx");
+}
+
+int msm_amd_poseidon_permute(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* in, size_t n,
+                             void* out) {
+  return poseidon_call(ctx, params, kPoseidonPermute, true, scalar_layout, nullptr, in, n, out, nullptr);
+}
+
+int msm_amd_poseidon_permute_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* d_in,
+                                    size_t n, void* d_out, float* kernel_ms) {
+  return poseidon_call(ctx, params, kPoseidonPermute, false, scalar_layout, nullptr, d_in, n, d_out, kernel_ms);
+}
+
+int msm_amd_poseidon_hash(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* tag32,
+                          const void* in, size_t n, void* out) {
+  return poseidon_call(ctx, params, kPoseidonHash, true, scalar_layout, tag32, in, n, out, nullptr);
+}
+
+int msm_amd_poseidon_hash_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* tag32,
+                                 const void* d_in, size_t n, void* d_out, float* kernel_ms) {
+  return poseidon_call(ctx, params, kPoseidonHash, false, scalar_layout, tag32, d_in, n, d_out, kernel_ms);
+}
+
+int msm_amd_poseidon_merkle_build(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* tag32,
+                                  const void* leaves, size_t n_leaves, void* tree, void* root32) {
+  return poseidon_merkle_build_call(ctx, params, true, scalar_layout, tag32, leaves, n_leaves, tree, root32, nullptr);
+}
+
+int msm_amd_poseidon_merkle_build_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout,
+                                         const void* tag32, const void* d_leaves, size_t n_leaves, void* d_tree, void* root32,
+                                         float* kernel_ms) {
+  return poseidon_merkle_build_call(ctx, params, false, scalar_layout, tag32, d_leaves, n_leaves, d_tree, root32, kernel_ms);
+}
+
+int msm_amd_poseidon_merkle_paths(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* leaves,
+                                  size_t n_leaves, const void* tree, const uint64_t* idx, size_t n_idx, void* out) {
+  return poseidon_merkle_paths_call(ctx, params, true, scalar_layout, leaves, n_leaves, tree, idx, n_idx, out, nullptr);
+}
+
+int msm_amd_poseidon_merkle_paths_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout,
+                                         const void* d_leaves, size_t n_leaves, const void* d_tree, const uint64_t* idx,
+                                         size_t n_idx, void* d_out, float* kernel_ms) {
+  return poseidon_merkle_paths_call(ctx, params, false, scalar_layout, d_leaves, n_leaves, d_tree, idx, n_idx, d_out, kernel_ms);
 }
 
 }  // extern "C"
