@@ -1009,6 +1009,54 @@ int msm_amd_test_host_ntt_levels(int root, uint32_t log_n, int direction, int sc
                                  const void* in, void* out, size_t n_vec, uint32_t levels, int threads);
 int msm_amd_test_ntt_twiddles(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, size_t first, size_t count, void* out);
 
+/* ---- transform over G1 points: a monomial SRS to a Lagrange SRS ------------------------------------------
+ * A KZG prover that commits to columns in evaluation form (halo2, PLONK) needs the Lagrange SRS [L_i(tau)] G.  Nobody
+ * knows tau, so it can only be made by running the inverse transform over the group elements [tau^j] G of the monomial
+ * SRS (halo2's g_to_lagrange; UNPINNED: that halo2 uses exactly w^-1 and n^-1 is recollection only, like the roots
+ * above).  These calls do that with the domain handles of the scalar transform.
+ * Definitions, natural order in and out, additions in G1, w the domain's root, n = 2^log_n:
+ *   MSM_AMD_NTT_FORWARD  out[k] = sum_{i<n} [w^(i k)] in[i]
+ *   MSM_AMD_NTT_INVERSE  out[i] = [n^-1] sum_{k<n} [w^(-i k)] in[k]: the exact inverse of FORWARD.  With
+ *                        MSM_AMD_NTT_ROOT_H2C on in[j] = [tau^j] G it yields [L_i(tau)] G.
+ * Limits: one vector per call, no coset shift, G1 only.
+ * Points.  Input: the four G1 host layouts; the _device call also takes MSM_AMD_POINT_PREPARED.  Output: the two affine
+ * host layouts; the _device call also takes MSM_AMD_POINT_PREPARED and then writes the bytes msm_amd_bases_prepare_device
+ * would write from the affine result, so msm_amd_msm_device, msm_amd_tables_build_device, msm_amd_check_points_device and
+ * msm_amd_compress_points_device take the output as it is.  The output is canonical affine, so the bytes are unique; an
+ * identity result is the layout's identity encoding, as msm_amd_mul_points writes it.  Identity inputs are ordinary
+ * operands.  Inputs are not validated: an off-curve input gives unspecified but defined bytes.
+ * Buffers of the _device call: d_out == d_in (in place; the first pass consumes the input into ctx-owned work buffers
+ * before anything is written) and disjoint buffers are both valid, and an out-of-place call leaves d_in unchanged;
+ * buffers that overlap without being equal are refused.  The ctx owns two work arrays of 64 n bytes each.
+ * Status, as msm_amd_ntt and msm_amd_mul_points.  MSM_AMD_INPUT_ERROR: a null pointer; a domain handle of another ctx, a
+ * freed one or a table handle; an unknown direction or layout; MSM_AMD_POINT_TABLES; MSM_AMD_POINT_PREPARED on a
+ * host-buffer call or on the twin; overlapping device buffers; the twin: an unknown root, log_n > 28.  The ctx calls
+ * serialise on the ctx and first wait -- bounded -- for its earlier work (a busy ctx: MSM_AMD_PIPELINE_ERROR,
+ * msm_amd_last_error names the call); every buffer is sized on the idle ctx before anything is enqueued.  log_n = 0
+ * copies the one record through the normalisation.  (MSM_AMD_MUL_CHUNK also sets the outputs per chunk of a level; no
+ * byte of a result depends on it.) */
+int msm_amd_ntt_points(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int point_layout_in,
+                       const void* in, int point_layout_out, void* out);
+/* kernel_ms (optional): device time of all passes between two events */
+int msm_amd_ntt_points_device(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int point_layout_in,
+                              const void* d_in, int point_layout_out, void* d_out, float* kernel_ms);
+/* The same on the CPU (no ctx, no GPU; the same bodies compiled for the host); threads <= 0: up to 16 host threads, and
+ * never more than 16. */
+int msm_amd_host_ntt_points(int root, uint32_t log_n, int direction, int point_layout_in, const void* in,
+                            int point_layout_out, void* out, int threads);
+/* Test aids (host buffers): the call stopped after `levels` <= log_n levels of its network; out = the work array as
+ * affine records of point_layout_out in network order, no final scaling.  The network is decimation in time:
+ *   load:  work[bitrev(j)] = in[j]
+ *   level l = 1 .. log_n, for every block base b that is a multiple of 2^l and every i < 2^(l-1):
+ *     u = work[b + i],  v = [w^(+-i n / 2^l)] work[b + i + 2^(l-1)]      (- for INVERSE)
+ *     work[b + i] = u + v,  work[b + i + 2^(l-1)] = u - v
+ * so levels = log_n with FORWARD equals the public call, and levels = 0 is the bit-reversed input.
+ * levels > log_n: MSM_AMD_INPUT_ERROR; the rest as the calls they stop. */
+int msm_amd_test_ntt_points_levels(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int point_layout_in,
+                                   const void* in, uint32_t levels, int point_layout_out, void* out);
+int msm_amd_test_host_ntt_points_levels(int root, uint32_t log_n, int direction, int point_layout_in, const void* in,
+                                        uint32_t levels, int point_layout_out, void* out, int threads);
+
 /* ---- vectors over Fr: element-wise ops, batch inversion, prefix products ----------------------------------
  * Between a transform and an MSM a prover does arithmetic on whole vectors of Fr: Groth16's h = (a.b - c) (g^n - 1)^-1
  * between the coset transforms, the grand products z[i+1] = z[i] num[i] / den[i] of the halo2 / PLONK permutation and

@@ -114,6 +114,8 @@ EXPORTS = [
     "msm_amd_host_ntt",
     "msm_amd_test_ntt_plan", "msm_amd_test_ntt_slots", "msm_amd_test_ntt_passes", "msm_amd_test_host_ntt_levels",
     "msm_amd_test_ntt_twiddles",
+    "msm_amd_ntt_points", "msm_amd_ntt_points_device", "msm_amd_host_ntt_points",
+    "msm_amd_test_ntt_points_levels", "msm_amd_test_host_ntt_points_levels",
     "msm_amd_fr_map", "msm_amd_fr_map_device", "msm_amd_host_fr_map",
     "msm_amd_fr_batch_inverse", "msm_amd_fr_batch_inverse_device", "msm_amd_host_fr_batch_inverse",
     "msm_amd_fr_prefix_product", "msm_amd_fr_prefix_product_device", "msm_amd_host_fr_prefix_product",
@@ -375,6 +377,15 @@ def _lib():
         L.msm_amd_test_host_ntt_levels.argtypes = [c_int, c_uint32, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                                    c_uint32, c_int]
         L.msm_amd_test_ntt_twiddles.argtypes = [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]
+        if hasattr(L, "msm_amd_ntt_points"):   # (an MSM_AMD_LIB build from before the point transform still loads)
+            L.msm_amd_ntt_points.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]
+            L.msm_amd_ntt_points_device.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
+                                                    POINTER(c_float)]
+            L.msm_amd_host_ntt_points.argtypes = [c_int, c_uint32, c_int, c_int, c_void_p, c_int, c_void_p, c_int]
+            L.msm_amd_test_ntt_points_levels.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_uint32, c_int,
+                                                         c_void_p]
+            L.msm_amd_test_host_ntt_points_levels.argtypes = [c_int, c_uint32, c_int, c_int, c_void_p, c_uint32, c_int,
+                                                              c_void_p, c_int]
         L.msm_amd_fr_map.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
         L.msm_amd_fr_map_device.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                             c_void_p, POINTER(c_float)]
@@ -1019,6 +1030,34 @@ class MsmConfig:
         self._check(_lib().msm_amd_test_ntt_twiddles(self.h, _ntt_handle(dom), first, count, out))
         return out.raw[:32 * count]
 
+    # ---- transform over G1 points ------------------------------------------------------------------
+    def ntt_points(self, dom, points: bytes, direction=NTT_FORWARD, point_layout=POINT_H2C_AFFINE,
+                   point_layout_out=POINT_H2C_AFFINE) -> bytes:
+        """The transform of the domain's n host point records (msm_amd_ntt_points): n affine records of
+        point_layout_out.  NTT_INVERSE on [tau^j] G gives the Lagrange SRS [L_i(tau)] G."""
+        out, size = _ntt_points_out(_ntt_log_n(self, dom), points, point_layout, point_layout_out)
+        self._check(_lib().msm_amd_ntt_points(self.h, _ntt_handle(dom), direction, point_layout, points, point_layout_out,
+                                              out))
+        return out.raw[:size]
+
+    def ntt_points_device(self, dom, d_in, d_out, direction=NTT_FORWARD, point_layout=POINT_PREPARED,
+                          point_layout_out=POINT_PREPARED) -> float:
+        """The same between device buffers, d_out == d_in or disjoint; input and output may also be POINT_PREPARED
+        records, which the MSM, table, check and compress calls take as they are; returns kernel_ms."""
+        ms = c_float(0)
+        self._check(_lib().msm_amd_ntt_points_device(self.h, _ntt_handle(dom), direction, point_layout, c_void_p(d_in),
+                                                     point_layout_out, c_void_p(d_out), ctypes.byref(ms)))
+        return ms.value
+
+    def test_ntt_points_levels(self, dom, points: bytes, levels, direction=NTT_FORWARD, point_layout=POINT_H2C_AFFINE,
+                               point_layout_out=POINT_H2C_AFFINE) -> bytes:
+        """MsmConfig.ntt_points stopped after `levels` levels (msm_amd_test_ntt_points_levels): the work array as affine
+        records in network order, no final scaling."""
+        out, size = _ntt_points_out(_ntt_log_n(self, dom), points, point_layout, point_layout_out)
+        self._check(_lib().msm_amd_test_ntt_points_levels(self.h, _ntt_handle(dom), direction, point_layout, points, levels,
+                                                          point_layout_out, out))
+        return out.raw[:size]
+
     # ---- vectors over Fr ---------------------------------------------------------------------------
     def fr_map(self, op, a: bytes, b: bytes = None, c: bytes = None, k: bytes = None, scalar_layout=SCALAR_MONT_LE) -> bytes:
         """out[i] = op(k, a[i], b[i], c[i]) on host records (msm_amd_fr_map); k: 32 bytes in scalar_layout"""
@@ -1609,6 +1648,22 @@ def _ntt_handle(dom):
     return dom.h if isinstance(dom, NttDomain) else dom
 
 
+def _ntt_log_n(cfg, dom) -> int:
+    """log_n of a domain handle of cfg (an unknown handle raises the MsmError of msm_amd_ntt_domain_info)"""
+    log_n = c_uint32(0)
+    cfg._check(_lib().msm_amd_ntt_domain_info(cfg.h, _ntt_handle(dom), None, ctypes.byref(log_n), None, None))
+    return log_n.value
+
+
+def _ntt_points_out(log_n, points, point_layout, point_layout_out):
+    """(output buffer, its size) of a point transform from host records; a known input layout must come with n records"""
+    n = 1 << log_n
+    if points is not None and point_layout in POINT_BYTES and len(points) != n * POINT_BYTES[point_layout]:
+        raise ValueError(f"ntt_points: {len(points)} bytes are not {n} records of point layout {point_layout}")
+    size = n * {POINT_H2C_AFFINE: 64, POINT_ARK_AFFINE: 72}.get(point_layout_out, 0)
+    return ctypes.create_string_buffer(max(1, size)), size
+
+
 def host_ntt(data: bytes, root, log_n, direction=NTT_FORWARD, scalar_layout=SCALAR_MONT_LE, shift=None, n_vec=1,
              threads=0) -> bytes:
     """Host twin of MsmConfig.ntt (no GPU)."""
@@ -1628,6 +1683,32 @@ def test_host_ntt_levels(data: bytes, root, log_n, levels, direction=NTT_FORWARD
     if st != OK:
         raise MsmError(st)
     return out.raw[:len(data)]
+
+
+def host_ntt_points(points: bytes, root, log_n, direction=NTT_FORWARD, point_layout=POINT_H2C_AFFINE,
+                    point_layout_out=POINT_H2C_AFFINE, threads=0) -> bytes:
+    """Host twin of MsmConfig.ntt_points (no GPU)."""
+    if not 0 <= log_n <= 28:
+        raise MsmError(INPUT_ERROR)
+    out, size = _ntt_points_out(log_n, points, point_layout, point_layout_out)
+    st = _lib().msm_amd_host_ntt_points(root, log_n, direction, point_layout, points, point_layout_out, out, threads)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:size]
+
+
+def test_host_ntt_points_levels(points: bytes, root, log_n, levels, direction=NTT_FORWARD, point_layout=POINT_H2C_AFFINE,
+                                point_layout_out=POINT_H2C_AFFINE, threads=0) -> bytes:
+    """host_ntt_points stopped after `levels` levels (msm_amd_test_host_ntt_points_levels): the work array as affine
+    records in network order, no final scaling."""
+    if not 0 <= log_n <= 28:
+        raise MsmError(INPUT_ERROR)
+    out, size = _ntt_points_out(log_n, points, point_layout, point_layout_out)
+    st = _lib().msm_amd_test_host_ntt_points_levels(root, log_n, direction, point_layout, points, levels, point_layout_out,
+                                                    out, threads)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:size]
 
 
 def test_ntt_plan(log_n, tile_log=10) -> list:

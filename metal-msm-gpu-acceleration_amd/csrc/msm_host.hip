@@ -34,6 +34,7 @@
 #include "launch_mul.h"
 #include "launch_fr.h"
 #include "launch_ntt.h"
+#include "launch_nttp.h"
 #include "host_fq64.h"
 #include "test_ops.hip.h"
 #include "test_ops_g2.hip.h"
@@ -225,7 +226,8 @@ struct CallState {
   DeviceBuf in[3], out, reasons;   // staging of host inputs, output and reason bytes
   DeviceBuf record;                // PointCounters
   DeviceBuf table, xyzz;           // mul_points: the fixed-base table, the XYZZ records of one chunk of outputs
-  DeviceBuf scratch, pow;          // transform: the ONE batch-sized scratch of a plan with more than one pass, the powers of a shift
+  DeviceBuf scratch, pow;          // transform: the ONE batch-sized scratch of a plan with more than one pass, the powers of a shift;
+                                   // transform over points: `scratch` holds the two packed work arrays, back to back (2 x 64 n bytes)
   DeviceBuf work;                  // Fr scan and inversion: the tile totals (fr_scan_plan, fr_inv_plan); the partial sums of
                                    // the split rows of a sparse product (fr_mat_plan); the partial sums of a sumcheck round,
                                    // the levels of a multilinear evaluation, the turns of a LOW bind (fr_mle.hip.h)
@@ -4471,6 +4473,102 @@ int msm_amd_test_ntt_twiddles(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipMemcpyAsync(out, (const u256*)d->d_mem + first, count * 32, hipMemcpyDeviceToHost, ctx->stream));
   return sync_stream_bounded(ctx, ctx->stream, __func__);
+}
+
+}  // extern "C"
+
+// ---- transform over G1 points (msm_amd_ntt_points, msm_amd_ntt_points_device) ----------------------------------------------
+// Through device_call, all on the main stream: the load pass consumes the input into the first packed work array before
+// anything is written (so d_out == d_in is an ordinary call), every level runs in chunks of lanes through the XYZZ chunk
+// buffer of the mul calls into the other work array, and the last normalisation writes the caller's layout to `out`.
+// INVERSE ends with the ladder by n^-1 over the last work array; log_n = 0 sends its one record through that pass with
+// the factor 1.
+namespace {
+
+// levels: kNttpAllLevels, or 0 .. log_n (msm_amd_test_ntt_points_levels, host buffers): the work array after that many
+// levels, affine records of layout_out in network order, no scaling.
+int ntt_points_call(msm_amd_ctx* ctx, const msm_amd_ntt_domain* handle, bool host, int direction, int layout_in,
+                    const void* in, int layout_out, void* out, float* kernel_ms, uint32_t levels) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall c;
+  c.who = levels != kNttpAllLevels ? "msm_amd_test_ntt_points_levels" : host ? "msm_amd_ntt_points" : "msm_amd_ntt_points_device";
+  const std::string& who = c.who;
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (!ntt_direction_known(direction)) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": direction must be MSM_AMD_NTT_FORWARD or MSM_AMD_NTT_INVERSE");
+  if (!nttp_layouts_known(!host, layout_in, layout_out))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + (host ? ": points in a G1 host layout, output in one of the two affine host layouts (not *_PREPARED / *_TABLES)"
+                                                      : ": points in a G1 host layout or *_PREPARED, output in an affine layout or *_PREPARED (not *_TABLES)"));
+  const uint32_t prepared = host ? 0u : (uint32_t)kKindPrepared;
+  const size_t in_stride = point_record_bytes(false, layout_in, kKindHost | prepared),
+               out_stride = point_record_bytes(false, layout_out, kKindAffine | prepared);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_ntt_domain* dom = find_handle(ctx->live_ntt, handle);
+  if (!dom) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": not a transform domain of this ctx");
+  const uint32_t log_n = dom->log_n;
+  if (levels != kNttpAllLevels && levels > log_n) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": levels must be 0 .. log_n");
+  if (!in || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": null pointer");
+  const size_t n = (size_t)1 << log_n;
+  if (!host) {
+    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
+    if (a != b && a < b + n * out_stride && b < a + n * in_stride)
+      return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": d_out must be d_in itself or disjoint from it");
+  }
+  const uint32_t run = levels == kNttpAllLevels ? log_n : levels;
+  u256 k = u256_zero();
+  const bool laddered = levels == kNttpAllLevels && direction == kNttInverse && nttp_n_inv(log_n, &k);
+  const bool last_pass = laddered || run == 0;   // the records go through the uniform-scalar pass on their way out
+  const uint32_t lanes = (uint32_t)(n / 2), chunk_lanes = nttp_chunk_lanes(log_n, ctx->mul_chunk);
+  const size_t chunk = std::min(n, ctx->mul_chunk);   // records per chunk of the last pass
+  CallState& s = ctx->calls;
+  c.host = host, c.host_in = host ? 1u : 0u, c.kernel_ms = kernel_ms;
+  c.in[0] = in, c.in_bytes[0] = n * in_stride;
+  c.out = out, c.out_bytes = n * out_stride;
+  c.work[0] = {&s.xyzz, std::max<size_t>(2 * (size_t)chunk_lanes, chunk) * mul_xyzz_bytes(false)};
+  c.work[1] = {&s.scratch, 2 * n * sizeof(AffPacked)};
+  return device_call(ctx, c, [&](hipStream_t st, const CallIo& io) -> int {
+    AffPacked* work[2] = {(AffPacked*)s.scratch.p, (AffPacked*)s.scratch.p + n};
+    void* xyzz = s.xyzz.p;
+    launch_nttp_load(st, layout_in, io.in[0], log_n, work[0]);
+    int cur = 0;
+    for (uint32_t level = 1; level <= run; ++level) {
+      const bool to_out = level == run && !last_pass;
+      for (uint32_t lane0 = 0; lane0 < lanes; lane0 += chunk_lanes) {
+        const uint32_t m = std::min(chunk_lanes, lanes - lane0);
+        launch_nttp_level(st, work[cur], dom->d_mem, log_n, level, direction, lane0, m, xyzz);
+        launch_nttp_normalise(st, xyzz, log_n, level, lane0, m, to_out ? layout_out : kLayoutPrepared,
+                              to_out ? io.out : (void*)work[cur ^ 1]);
+      }
+      cur ^= 1;
+    }
+    if (last_pass)
+      for (size_t first = 0; first < n; first += chunk) {
+        const uint32_t m = (uint32_t)std::min(chunk, n - first);
+        launch_nttp_scale(st, work[cur], (uint32_t)first, m, laddered, k, xyzz);
+        launch_mul_normalise(st, false, xyzz, m, layout_out, (uint8_t*)io.out + first * out_stride);
+      }
+    return MSM_AMD_OK;
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_ntt_points(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int point_layout_in,
+                       const void* in, int point_layout_out, void* out) {
+  return ntt_points_call(ctx, domain, true, direction, point_layout_in, in, point_layout_out, out, nullptr, kNttpAllLevels);
+}
+
+int msm_amd_ntt_points_device(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int point_layout_in,
+                              const void* d_in, int point_layout_out, void* d_out, float* kernel_ms) {
+  return ntt_points_call(ctx, domain, false, direction, point_layout_in, d_in, point_layout_out, d_out, kernel_ms,
+                         kNttpAllLevels);
+}
+
+int msm_amd_test_ntt_points_levels(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int point_layout_in,
+                                   const void* in, uint32_t levels, int point_layout_out, void* out) {
+  if (levels == kNttpAllLevels) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_ntt_points_levels: levels must be 0 .. log_n");
+  return ntt_points_call(ctx, domain, true, direction, point_layout_in, in, point_layout_out, out, nullptr, levels);
 }
 
 }  // extern "C"

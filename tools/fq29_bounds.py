@@ -492,6 +492,28 @@ def mul_points(group=16, where="mul_normalise"):
             fail(f"load_base: {f.name} may reach {f.val:.2f}p, canonical(., 1) takes values below 2 p")
 
 
+NTTP_NEG = {"Y*one": 1.04, "-Y": 4.0}      # what the header of ntt_points.hip.h states for the negated T
+
+
+def ntt_points(where="nttp_negate"):
+    """ntt_points.hip.h.  A butterfly is T = mul_ladder(q, k) or pti_from_affi(q) on an unpacked canonical record -- the
+    ladder of mul_points.hip.h, closed under the invariant --, then u + T and u - T = pti_madd(T or -T, u) with the
+    canonical affine u: pti_madd on a point of the invariant and a canonical base, the case checked above with its
+    doubling.  New is the negation of an XYZZ point whose Y may reach the invariant's 6 p, above the 3.9 p Fq29::neg
+    takes: Y' = Y one (a product, below 1.04 p, exact 29-bit limbs), -Y' = norm(4 p - Y'); X, ZZ, ZZZ are T's own.  The
+    result must be a point of the invariant again, because pti_madd takes it as its accumulator."""
+    px, py, pzz, pzzz = point_invariant()
+    one = Fe([MASK] * 8 + [P >> 232], 1.0, "one")
+    y1 = mul(py, one, "Y*one")
+    ny = neg(y1, "-Y")
+    for f in (y1, ny):
+        lim = NTTP_NEG[f.name]
+        if f.val >= lim + MUL_NORM_SLACK:
+            fail(f"{where}: {f.name} may reach {f.val:.3f}p, the header says < {lim}p")
+    check_point(px, ny, pzz, pzzz, where)
+    return {"Y*one": y1, "-Y": ny}
+
+
 def contracts():
     """The operand contracts the headers state, whatever the caller: bn254_fq29.hip.h (mul / sqr: limbs <= 2^30 + 2^8,
     value <= 40 p; masked and wide digits) and bn254_fq2_29.hip.h (every operand of G2's mul / mul2 / sqr normalised:
@@ -520,6 +542,7 @@ def main(verbose=False):
     figures["pti_add_nz"] = pti_add_nz(INV_E)
     figures["pti_add_nz (E')"] = pti_add_nz(INV_ISO)
     mul_points()
+    figures["nttp_negate"] = ntt_points()
     for site in sorted(derived_filters):
         print(f"zero filter {site}: needs {derived_filters[site]}, the header has {FILTERS.get(site)}")
     print(f"folded subtractions (mul_sub_np / sqr_sub_np): {len(folds)} uses, every one with wide digits, columns < 2^64 "
