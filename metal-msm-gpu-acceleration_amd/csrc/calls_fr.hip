@@ -1,0 +1,750 @@
+// The blocking vector calls over Fr (device_call.h): map, prefix product, batch inversion, polynomials, linear
+// combinations, sparse matrices, multilinear tables and sumcheck rounds, the width scan, Poseidon.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "device_call.h"
+
+// ---- vectors over Fr (msm_amd_fr_map*, msm_amd_fr_batch_inverse*, msm_amd_fr_prefix_product*, msm_amd_fr_poly_*,
+// msm_amd_fr_lincomb*) ------------------------------------------------------------------------------------------------------
+// Through device_call: the host forms compute over the staged copy of their first operand.  The inversion has two spans
+// of kernels: T and the zero count come back as the call's 64-byte record, the host inverts T.  The polynomial calls
+// read p_v(z) back through the call's page-locked values buffer, in the one bounded wait behind their kernels.
+namespace {
+
+int fr_map_call(msm_amd_ctx* ctx, bool host, int op, int scalar_layout, const void* k32, const void* a, const void* b,
+                const void* c, size_t n, void* out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_map" : "msm_amd_fr_map_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_map_check(op, scalar_layout, k32, a, b, c, n, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const unsigned reads = fr_op_reads(op);
+  const void* operand[3] = {a, b, c};
+  d.host = d.in_place = host, d.host_in = host ? reads : 0u, d.kernel_ms = kernel_ms;
+  for (int i = 0; i < 3; ++i) d.in[i] = operand[i], d.in_bytes[i] = (reads >> i & 1) ? n * 32 : 0;
+  d.out = out, d.out_bytes = n * 32;
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    launch_fr_map(st, op, scalar_layout, fr_read_k(op, scalar_layout, k32), io.in[0], io.in[1], io.in[2], n, io.out);
+    return MSM_AMD_OK;
+  });
+}
+
+int fr_prefix_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int mode, const void* in, size_t n, size_t n_vec, void* out,
+                   float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_prefix_product" : "msm_amd_fr_prefix_product_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (!fr_mode_known(mode))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": mode must be MSM_AMD_FR_PREFIX_INCLUSIVE or MSM_AMD_FR_PREFIX_EXCLUSIVE");
+  if (const char* why = fr_unary_check(scalar_layout, in, n, n_vec, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  CallState& s = ctx->calls;
+  FrScanLaunch c{};
+  c.n = n, c.n_vec = n_vec, c.tile_log = ctx->fr_tile_log, c.layout = scalar_layout, c.mode = mode;
+  d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = n * n_vec * 32;
+  d.out = out, d.out_bytes = n * n_vec * 32;
+  d.work[0] = {&s.work, std::max<size_t>(32, fr_scan_plan(n, n_vec, c.tile_log).records * 32)};
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    c.in = io.in[0], c.out = io.out, c.work = s.work.p;
+    launch_fr_scan(st, c);
+    return MSM_AMD_OK;
+  });
+}
+
+int fr_inverse_call(msm_amd_ctx* ctx, bool host, int scalar_layout, const void* in, size_t n, void* out, uint64_t* n_zero,
+                    float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_batch_inverse" : "msm_amd_fr_batch_inverse_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (n_zero) *n_zero = 0;
+  if (const char* why = fr_unary_check(scalar_layout, in, n, 1, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  CallState& s = ctx->calls;
+  const uint32_t tile_log = ctx->fr_tile_log;
+  const FrInvPlan plan = fr_inv_plan(n, tile_log);
+  d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = n * 32;
+  d.out = out, d.out_bytes = n * 32;
+  d.work[0] = {&s.work, plan.records * 32};
+  uint64_t zeros = 0;
+  u256 t_inv;
+  const int rc = device_call(
+      ctx, d,
+      [&](hipStream_t st, CallIo& io) {   // span 1: the products; T and the zero count come back
+        launch_fr_inv_products(st, scalar_layout, io.in[0], n, tile_log, s.work.p);
+        io.record = fr_inv_tail(s.work.p, plan);
+        return MSM_AMD_OK;
+      },
+      [&](const uint8_t* tail, float) {
+        u256 total;
+        std::memcpy(total.v, tail, 32);
+        std::memcpy(&zeros, tail + 32, 8);
+        t_inv = ntt_fr_inv(total);   // zeros were read as one: T != 0
+      },
+      [&](hipStream_t st, const CallIo& io) {   // span 2: every record's inverse
+        launch_fr_inv_apply(st, scalar_layout, io.in[0], n, tile_log, s.work.p, t_inv, io.out);
+        return MSM_AMD_OK;
+      });
+  if (rc == MSM_AMD_OK && n_zero) *n_zero = zeros;
+  return rc;
+}
+
+// p_v(z) come back as raw records through CallState::h_values and leave in the caller's layout
+void fr_values_out(const CallState& s, int scalar_layout, size_t n_vec, void* out) {
+  for (size_t v = 0; v < n_vec; ++v) {
+    u256 x;
+    std::memcpy(x.v, s.h_values + v * 32, 32);
+    uint32_t rec[8];
+    ntt_store(scalar_layout, x, rec);
+    std::memcpy((uint8_t*)out + v * 32, rec, 32);
+  }
+}
+
+// msm_amd_fr_poly_eval* (divide false: out is unused, values required) and msm_amd_fr_poly_div_linear*
+int fr_poly_call(msm_amd_ctx* ctx, bool host, bool divide, int scalar_layout, const void* z32, const void* in, size_t n,
+                 size_t n_vec, void* out, void* values, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = std::string(divide ? "msm_amd_fr_poly_div_linear" : "msm_amd_fr_poly_eval") + (host ? "" : "_device");
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_poly_check(scalar_layout, z32, in, n, n_vec, out, values, divide, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  CallState& s = ctx->calls;
+  FrPolyLaunch c{};
+  c.n = n, c.n_vec = n_vec, c.tile_log = ctx->fr_tile_log, c.layout = scalar_layout, c.divide = divide;
+  c.z = fr_read_record(scalar_layout, z32);
+  const FrScanPlan plan = fr_scan_plan(n, n_vec, c.tile_log);
+  d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = n * n_vec * 32;
+  d.out = out, d.out_bytes = divide ? n * n_vec * 32 : 0;
+  d.work[0] = {&s.work, fr_poly_values(plan) + n_vec * 32};
+  d.values_bytes = values ? n_vec * 32 : 0;
+  const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
+    c.in = io.in[0], c.out = io.out, c.work = s.work.p;
+    launch_fr_poly(st, c);
+    io.values = (const uint8_t*)s.work.p + fr_poly_values(plan);
+    return MSM_AMD_OK;
+  });
+  if (rc == MSM_AMD_OK && values) fr_values_out(s, scalar_layout, n_vec, values);
+  return rc;
+}
+
+int fr_lincomb_call(msm_amd_ctx* ctx, bool host, int scalar_layout, const void* k32, const void* a, size_t n, size_t n_vec,
+                    void* out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_lincomb" : "msm_amd_fr_lincomb_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_lincomb_check(scalar_layout, k32, a, n, n_vec, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  // the host form folds into the first vector of the staged copy
+  d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = a, d.in_bytes[0] = n * n_vec * 32;
+  d.out = out, d.out_bytes = n * 32;
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    launch_fr_lincomb(st, scalar_layout, fr_read_record(scalar_layout, k32), io.in[0], n, n_vec, io.out);
+    return MSM_AMD_OK;
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_fr_poly_eval(msm_amd_ctx* ctx, int scalar_layout, const void* z32, const void* coeffs, size_t n, size_t n_vec,
+                         void* y_out) {
+  return fr_poly_call(ctx, true, false, scalar_layout, z32, coeffs, n, n_vec, nullptr, y_out, nullptr);
+}
+
+int msm_amd_fr_poly_eval_device(msm_amd_ctx* ctx, int scalar_layout, const void* z32, const void* d_coeffs, size_t n,
+                                size_t n_vec, void* y_out, float* kernel_ms) {
+  return fr_poly_call(ctx, false, false, scalar_layout, z32, d_coeffs, n, n_vec, nullptr, y_out, kernel_ms);
+}
+
+int msm_amd_fr_poly_div_linear(msm_amd_ctx* ctx, int scalar_layout, const void* z32, const void* in, size_t n, size_t n_vec,
+                               void* out, void* rem_out) {
+  return fr_poly_call(ctx, true, true, scalar_layout, z32, in, n, n_vec, out, rem_out, nullptr);
+}
+
+int msm_amd_fr_poly_div_linear_device(msm_amd_ctx* ctx, int scalar_layout, const void* z32, const void* d_in, size_t n,
+                                      size_t n_vec, void* d_out, void* rem_out, float* kernel_ms) {
+  return fr_poly_call(ctx, false, true, scalar_layout, z32, d_in, n, n_vec, d_out, rem_out, kernel_ms);
+}
+
+int msm_amd_fr_lincomb(msm_amd_ctx* ctx, int scalar_layout, const void* k32, const void* a, size_t n, size_t n_vec, void* out) {
+  return fr_lincomb_call(ctx, true, scalar_layout, k32, a, n, n_vec, out, nullptr);
+}
+
+int msm_amd_fr_lincomb_device(msm_amd_ctx* ctx, int scalar_layout, const void* k32, const void* d_a, size_t n, size_t n_vec,
+                              void* d_out, float* kernel_ms) {
+  return fr_lincomb_call(ctx, false, scalar_layout, k32, d_a, n, n_vec, d_out, kernel_ms);
+}
+
+int msm_amd_fr_map(msm_amd_ctx* ctx, int op, int scalar_layout, const void* k32, const void* a, const void* b, const void* c,
+                   size_t n, void* out) {
+  return fr_map_call(ctx, true, op, scalar_layout, k32, a, b, c, n, out, nullptr);
+}
+
+int msm_amd_fr_map_device(msm_amd_ctx* ctx, int op, int scalar_layout, const void* k32, const void* d_a, const void* d_b,
+                          const void* d_c, size_t n, void* d_out, float* kernel_ms) {
+  return fr_map_call(ctx, false, op, scalar_layout, k32, d_a, d_b, d_c, n, d_out, kernel_ms);
+}
+
+int msm_amd_fr_batch_inverse(msm_amd_ctx* ctx, int scalar_layout, const void* in, size_t n, void* out, uint64_t* n_zero) {
+  return fr_inverse_call(ctx, true, scalar_layout, in, n, out, n_zero, nullptr);
+}
+
+int msm_amd_fr_batch_inverse_device(msm_amd_ctx* ctx, int scalar_layout, const void* d_in, size_t n, void* d_out,
+                                    uint64_t* n_zero, float* kernel_ms) {
+  return fr_inverse_call(ctx, false, scalar_layout, d_in, n, d_out, n_zero, kernel_ms);
+}
+
+int msm_amd_fr_prefix_product(msm_amd_ctx* ctx, int scalar_layout, int mode, const void* in, size_t n, size_t n_vec,
+                              void* out) {
+  return fr_prefix_call(ctx, true, scalar_layout, mode, in, n, n_vec, out, nullptr);
+}
+
+int msm_amd_fr_prefix_product_device(msm_amd_ctx* ctx, int scalar_layout, int mode, const void* d_in, size_t n, size_t n_vec,
+                                     void* d_out, float* kernel_ms) {
+  return fr_prefix_call(ctx, false, scalar_layout, mode, d_in, n, n_vec, d_out, kernel_ms);
+}
+
+}  // extern "C"
+
+// ---- sparse matrix times vector over Fr (msm_amd_fr_matrix_*, msm_amd_fr_matvec*) ------------------------------------------
+// The build checks every column on the host before anything is uploaded, so that no index of the image can leave x, the
+// dictionary or the partials.  A product is a device_call: x through the staging in the host form, the partial sums of the
+// split rows in CallState::work, the launches of launch_fr_matvec on the main stream.
+namespace {
+
+int fr_matvec_call(msm_amd_ctx* ctx, const msm_amd_fr_matrix* handle, bool host, int scalar_layout, const void* x, void* y,
+                   float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_matvec" : "msm_amd_fr_matvec_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_fr_matrix* m = find_handle(ctx->live_fr_mat, handle);
+  if (!m) return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": not a matrix handle of this ctx");
+  if (const char* why = fr_matvec_check(scalar_layout, m->n_rows, m->n_cols, x, y, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (!host) {
+    const uintptr_t lo = (uintptr_t)m->d_mem, hi = lo + m->bytes, a = (uintptr_t)x, b = (uintptr_t)y;
+    if ((a < hi && lo < a + m->n_cols * 32) || (b < hi && lo < b + m->n_rows * 32))
+      return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": d_x and d_y must not overlap the matrix");
+  }
+  CallState& s = ctx->calls;
+  FrMatLaunch c{};
+  c.image = m->d_mem, c.at = m->at, c.plan = m->plan, c.n_rows = m->n_rows, c.long_rows = m->long_rows, c.layout = scalar_layout;
+  c.signs = ctx->fr_mat_signs;
+  d.host = host, d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = x, d.in_bytes[0] = m->n_cols * 32;
+  d.out = y, d.out_bytes = m->n_rows * 32;
+  d.work[0] = {&s.work, std::max<size_t>(32, m->plan.partials * 32)};
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    c.x = io.in[0], c.y = io.out, c.work = s.work.p;
+    launch_fr_matvec(st, c);
+    return MSM_AMD_OK;
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_fr_matrix_build(msm_amd_ctx* ctx, int scalar_layout, size_t n_rows, size_t n_cols, const uint64_t* row_ptr,
+                            const uint32_t* col_idx, const void* values, msm_amd_fr_matrix** out) {
+  if (!ctx || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_fr_matrix_build: null pointer");
+  *out = nullptr;
+  if (const char* why = fr_matrix_check(scalar_layout, n_rows, n_cols, row_ptr, col_idx, values))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, std::string("msm_amd_fr_matrix_build: ") + why);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = recover_if_stalled(ctx)) return rc;
+  FrMatPlan plan;
+  FrMatImage at;
+  uint64_t n_distinct = 0, dict_records = 0;
+  std::vector<uint8_t> image;
+  fr_mat_build_image(scalar_layout, n_rows, row_ptr, col_idx, values, ctx->fr_mat_long, ctx->fr_mat_seg_log, &plan, &at,
+                     &n_distinct, &dict_records, &image);
+  int up = MSM_AMD_OK;
+  if (int rc = handle_build_tail(ctx, ctx->live_fr_mat, at.bytes, "a sparse matrix", "matrix build",
+                                 [&](void* d_mem) { up = staged_upload(ctx, d_mem, image.data(), image.size(), ctx->stream); },
+                                 out))
+    return rc;
+  if (up) {   // the upload did not go through: nothing may read the allocation
+    msm_amd_fr_matrix* h = *out;
+    *out = nullptr;
+    const std::string why = ctx->last_error;
+    handle_free(ctx, ctx->live_fr_mat, h, "");
+    return fail(ctx, up, "msm_amd_fr_matrix_build: " + why);
+  }
+  msm_amd_fr_matrix* h = *out;
+  h->n_rows = n_rows, h->n_cols = n_cols, h->nnz = row_ptr[n_rows], h->n_distinct = n_distinct;
+  h->long_rows = ctx->fr_mat_long, h->plan = plan, h->at = at;
+  return MSM_AMD_OK;
+}
+
+int msm_amd_fr_matrix_info(msm_amd_ctx* ctx, const msm_amd_fr_matrix* matrix, size_t* n_rows, size_t* n_cols, size_t* nnz,
+                           size_t* n_distinct, size_t* device_bytes) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_fr_matrix* m = find_handle(ctx->live_fr_mat, matrix);
+  if (!m) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_fr_matrix_info: not a matrix handle of this ctx");
+  if (n_rows) *n_rows = m->n_rows;
+  if (n_cols) *n_cols = m->n_cols;
+  if (nnz) *nnz = m->nnz;
+  if (n_distinct) *n_distinct = m->n_distinct;
+  if (device_bytes) *device_bytes = m->bytes;
+  return MSM_AMD_OK;
+}
+
+int msm_amd_fr_matrix_free(msm_amd_ctx* ctx, msm_amd_fr_matrix* matrix) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return handle_free(ctx, ctx->live_fr_mat, matrix, "msm_amd_fr_matrix_free: not a matrix handle of this ctx");
+}
+
+int msm_amd_fr_matvec(msm_amd_ctx* ctx, const msm_amd_fr_matrix* matrix, int scalar_layout, const void* x, void* y) {
+  return fr_matvec_call(ctx, matrix, true, scalar_layout, x, y, nullptr);
+}
+
+int msm_amd_fr_matvec_device(msm_amd_ctx* ctx, const msm_amd_fr_matrix* matrix, int scalar_layout, const void* d_x, void* d_y,
+                             float* kernel_ms) {
+  return fr_matvec_call(ctx, matrix, false, scalar_layout, d_x, d_y, kernel_ms);
+}
+
+}  // extern "C"
+
+// ---- multilinear tables over Fr and sumcheck rounds (msm_amd_fr_mle_bind*, msm_amd_fr_mle_eval*, msm_amd_fr_eq_table*,
+// msm_amd_fr_sumcheck_round*) ------------------------------------------------------------------------------------------------
+// Through device_call.  Challenges and points are read once on the host and reach the kernels by value.  The values of an
+// evaluation or a round come back through CallState::h_values.  The host form of a bind copies back the records the call
+// defines and no byte between the tables: one strided copy behind the kernels.
+namespace {
+
+int fr_mle_bind_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int order, const void* r32, size_t n_bind, const void* in,
+                     size_t n, size_t n_vec, size_t stride, void* out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_mle_bind" : "msm_amd_fr_mle_bind_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_mle_bind_check(scalar_layout, order, r32, n_bind, in, n, n_vec, stride, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n_vec == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  CallState& s = ctx->calls;
+  FrMleBindLaunch c{};
+  c.n = n, c.n_vec = n_vec, c.stride = stride, c.n_bind = (uint32_t)n_bind, c.layout = scalar_layout, c.order = order;
+  for (size_t k = 0; k < n_bind; ++k) c.r[k] = fr_read_record(scalar_layout, (const uint8_t*)r32 + k * 32);
+  const FrMleBindPlan plan = fr_mle_bind_plan(order, n, n_vec, c.n_bind);
+  const size_t span = ((n_vec - 1) * stride + n) * 32, left = (n >> n_bind) * 32;
+  // the host form works from the staged input into the staged output; the strided copy below brings the result back
+  d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = span;
+  d.out = out;
+  d.work[0] = {&s.work, std::max<size_t>(32, plan.work_records * 32)};
+  if (host) d.work[1] = {&s.out, span};
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) -> int {
+    c.in = io.in[0], c.out = host ? s.out.p : io.out, c.work = s.work.p;
+    launch_fr_mle_bind(st, c);
+    if (host)
+      HIP_TRY(ctx, hipMemcpy2DAsync(out, stride * 32, s.out.p, stride * 32, left, n_vec, hipMemcpyDeviceToHost, st));
+    return MSM_AMD_OK;
+  });
+}
+
+int fr_mle_eval_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int order, const void* point32, const void* in, size_t n,
+                     size_t n_vec, size_t stride, void* y_out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_mle_eval" : "msm_amd_fr_mle_eval_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_mle_eval_check(scalar_layout, order, point32, in, n, n_vec, stride, y_out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n_vec == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  CallState& s = ctx->calls;
+  FrMleEvalLaunch c{};
+  c.n = n, c.n_vec = n_vec, c.stride = stride, c.tile_log = ctx->fr_tile_log, c.layout = scalar_layout;
+  const uint32_t m = fr_mle_log2(n);
+  // the kernels fold x_j at r[j]: HIGH binds x_(m-1-s) at point[s]
+  for (uint32_t k = 0; k < m; ++k)
+    c.r[order == kFrMleHigh ? m - 1 - k : k] = fr_read_record(scalar_layout, (const uint8_t*)point32 + (size_t)k * 32);
+  const FrScanPlan plan = fr_scan_plan(n, n_vec, c.tile_log);
+  d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = ((n_vec - 1) * stride + n) * 32;
+  d.work[0] = {&s.work, fr_poly_values(plan) + n_vec * 32};
+  d.values_bytes = n_vec * 32;
+  const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
+    c.in = io.in[0], c.work = s.work.p;
+    launch_fr_mle_eval(st, c);
+    io.values = (const uint8_t*)s.work.p + fr_poly_values(plan);
+    return MSM_AMD_OK;
+  });
+  if (rc == MSM_AMD_OK) fr_values_out(s, scalar_layout, n_vec, y_out);
+  return rc;
+}
+
+int fr_eq_table_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int order, const void* point32, size_t m, void* out,
+                     float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_eq_table" : "msm_amd_fr_eq_table_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_eq_table_check(scalar_layout, order, point32, m, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  u256 by_bit[kFrMleMaxVars];
+  for (size_t k = 0; k < m; ++k)
+    by_bit[order == kFrMleHigh ? m - 1 - k : k] = fr_read_record(scalar_layout, (const uint8_t*)point32 + k * 32);
+  d.host = host, d.kernel_ms = kernel_ms;
+  d.out = out, d.out_bytes = ((size_t)1 << m) * 32;
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    launch_fr_eq_table(st, scalar_layout, by_bit, (uint32_t)m, io.out);
+    return MSM_AMD_OK;
+  });
+}
+
+int fr_sumcheck_round_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int order, int form, const void* in, size_t n,
+                           size_t n_vec, size_t stride, void* g_out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_sumcheck_round" : "msm_amd_fr_sumcheck_round_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_sumcheck_check(scalar_layout, order, form, in, n, n_vec, stride, g_out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n_vec == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  CallState& s = ctx->calls;
+  FrMleRoundLaunch c{};
+  c.n = n, c.n_vec = n_vec, c.stride = stride, c.chunk_log = ctx->fr_mle_chunk_log;
+  c.layout = scalar_layout, c.order = order, c.form = form;
+  const uint32_t values = fr_mle_degree(form, n_vec) + 1;
+  const FrMleRoundPlan plan = fr_mle_round_plan(n, values, c.chunk_log);
+  d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = ((n_vec - 1) * stride + n) * 32;
+  d.work[0] = {&s.work, plan.records * 32};
+  d.values_bytes = values * 32;
+  const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
+    c.in = io.in[0], c.work = s.work.p;
+    launch_fr_sumcheck_round(st, c);
+    io.values = (const uint8_t*)s.work.p + plan.values_off * 32;
+    return MSM_AMD_OK;
+  });
+  if (rc == MSM_AMD_OK) fr_values_out(s, scalar_layout, values, g_out);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_fr_mle_bind(msm_amd_ctx* ctx, int scalar_layout, int order, const void* r, size_t n_bind, const void* in, size_t n,
+                        size_t n_vec, size_t stride, void* out) {
+  return fr_mle_bind_call(ctx, true, scalar_layout, order, r, n_bind, in, n, n_vec, stride, out, nullptr);
+}
+
+int msm_amd_fr_mle_bind_device(msm_amd_ctx* ctx, int scalar_layout, int order, const void* r, size_t n_bind, const void* d_in,
+                               size_t n, size_t n_vec, size_t stride, void* d_out, float* kernel_ms) {
+  return fr_mle_bind_call(ctx, false, scalar_layout, order, r, n_bind, d_in, n, n_vec, stride, d_out, kernel_ms);
+}
+
+int msm_amd_fr_mle_eval(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point, const void* in, size_t n,
+                        size_t n_vec, size_t stride, void* y_out) {
+  return fr_mle_eval_call(ctx, true, scalar_layout, order, point, in, n, n_vec, stride, y_out, nullptr);
+}
+
+int msm_amd_fr_mle_eval_device(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point, const void* d_in, size_t n,
+                               size_t n_vec, size_t stride, void* y_out, float* kernel_ms) {
+  return fr_mle_eval_call(ctx, false, scalar_layout, order, point, d_in, n, n_vec, stride, y_out, kernel_ms);
+}
+
+int msm_amd_fr_eq_table(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point, size_t m, void* out) {
+  return fr_eq_table_call(ctx, true, scalar_layout, order, point, m, out, nullptr);
+}
+
+int msm_amd_fr_eq_table_device(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point, size_t m, void* d_out,
+                               float* kernel_ms) {
+  return fr_eq_table_call(ctx, false, scalar_layout, order, point, m, d_out, kernel_ms);
+}
+
+int msm_amd_fr_sumcheck_round(msm_amd_ctx* ctx, int scalar_layout, int order, int form, const void* in, size_t n, size_t n_vec,
+                              size_t stride, void* g_out) {
+  return fr_sumcheck_round_call(ctx, true, scalar_layout, order, form, in, n, n_vec, stride, g_out, nullptr);
+}
+
+int msm_amd_fr_sumcheck_round_device(msm_amd_ctx* ctx, int scalar_layout, int order, int form, const void* d_in, size_t n,
+                                     size_t n_vec, size_t stride, void* g_out, float* kernel_ms) {
+  return fr_sumcheck_round_call(ctx, false, scalar_layout, order, form, d_in, n, n_vec, stride, g_out, kernel_ms);
+}
+
+}  // extern "C"
+
+// ---- width scan (msm_amd_scalar_width*): through device_call; the 32-byte result comes back as the call's values ----------
+namespace {
+
+int scalar_width_call(msm_amd_ctx* ctx, bool host, int scalar_layout, const void* scalars, size_t n, int sign, uint32_t* bits,
+                      uint64_t* stats) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_scalar_width" : "msm_amd_scalar_width_device";
+  if (const char* why = scalar_width_check(scalar_layout, scalars, n, sign, bits))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  WidthStats r;
+  if (n != 0) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    CallState& s = ctx->calls;
+    d.host_in = host ? 1u : 0u;
+    d.in[0] = scalars, d.in_bytes[0] = n * 32;
+    d.work[0] = {&s.work, scalar_width_work_bytes(n)};
+    d.values_bytes = 32;
+    const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
+      launch_scalar_width(st, (const u256*)io.in[0], (uint32_t)n, scalar_layout == MSM_AMD_SCALAR_MONT_LE, (uint32_t)sign,
+                          s.work.p);
+      io.values = s.work.p;
+      return MSM_AMD_OK;
+    });
+    if (rc) return rc;
+    uint64_t v[4];
+    std::memcpy(v, s.h_values, 32);
+    r.bits = (uint32_t)(v[0] >> 32), r.widest = (uint32_t)~(uint32_t)v[0], r.zeros = v[1], r.negatives = v[2];
+  }
+  scalar_width_out(r, bits, stats);
+  return MSM_AMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_scalar_width(msm_amd_ctx* ctx, int scalar_layout, const void* scalars, size_t n, int sign, uint32_t* bits,
+                         uint64_t* stats) {
+  return scalar_width_call(ctx, true, scalar_layout, scalars, n, sign, bits, stats);
+}
+int msm_amd_scalar_width_device(msm_amd_ctx* ctx, int scalar_layout, const void* d_scalars, size_t n, int sign, uint32_t* bits,
+                                uint64_t* stats) {
+  return scalar_width_call(ctx, false, scalar_layout, d_scalars, n, sign, bits, stats);
+}
+
+}  // extern "C"
+
+// ---- Poseidon over Fr (msm_amd_poseidon_params_*, msm_amd_poseidon_permute*, _hash*, _merkle_build*, _merkle_paths*) ---------
+// Through device_call.  A parameter handle is validated by membership in ctx->live_poseidon, under the lock and before
+// anything is sized by it; the tag is read once on the host and reaches the kernels by value; the root of a tree comes back
+// through CallState::h_values in the call's one bounded wait; the leaf indices of a paths call are checked on the host and
+// go through the staging in both forms.
+namespace {
+
+const char* const kNotPoseidon = ": not a Poseidon parameter handle of this ctx";
+
+PoseidonLaunch poseidon_launch(const msm_amd_poseidon_params* p, int scalar_layout, const void* tag32) {
+  PoseidonLaunch c{};
+  c.image = p->d_mem, c.t = p->t, c.r_f = p->r_f, c.r_p = p->r_p, c.layout = scalar_layout;
+  c.tag = tag32 ? fr_read_record(scalar_layout, tag32) : u256_zero();
+  return c;
+}
+
+// device memory a call writes must not be the constants
+bool poseidon_clear_of(const msm_amd_poseidon_params* p, const void* out, size_t bytes) {
+  const uintptr_t lo = (uintptr_t)p->d_mem, hi = lo + p->bytes, a = (uintptr_t)out;
+  return !(a < hi && lo < a + bytes);
+}
+
+int poseidon_call(msm_amd_ctx* ctx, const msm_amd_poseidon_params* handle, int kind, bool host, int scalar_layout,
+                  const void* tag32, const void* in, size_t n, void* out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = std::string(kind == kPoseidonHash ? "msm_amd_poseidon_hash" : "msm_amd_poseidon_permute") + (host ? "" : "_device");
+  if (kernel_ms) *kernel_ms = 0.f;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_poseidon_params* p = find_handle(ctx->live_poseidon, handle);
+  if (!p) return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + kNotPoseidon);
+  if (const char* why = poseidon_call_check(kind, p->t, scalar_layout, in, n, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n == 0) return MSM_AMD_OK;
+  const size_t in_bytes = n * (kind == kPoseidonHash ? p->t - 1 : p->t) * 32, out_bytes = n * (kind == kPoseidonHash ? 1 : p->t) * 32;
+  if (!host && !poseidon_clear_of(p, out, out_bytes))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": the output must not overlap the parameters");
+  const PoseidonLaunch c = poseidon_launch(p, scalar_layout, tag32);
+  // the host form of a permutation works in place on the staged copy of its input
+  d.host = host, d.host_in = host, d.in_place = host && kind == kPoseidonPermute, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = in_bytes;
+  d.out = out, d.out_bytes = out_bytes;
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    launch_poseidon(st, c, kind, io.in[0], n, io.out);
+    return MSM_AMD_OK;
+  });
+}
+
+int poseidon_merkle_build_call(msm_amd_ctx* ctx, const msm_amd_poseidon_params* handle, bool host, int scalar_layout,
+                               const void* tag32, const void* leaves, size_t n_leaves, void* tree, void* root32, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_poseidon_merkle_build" : "msm_amd_poseidon_merkle_build_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_poseidon_params* p = find_handle(ctx->live_poseidon, handle);
+  if (!p) return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + kNotPoseidon);
+  if (const char* why = poseidon_merkle_check(p->t, scalar_layout, leaves, n_leaves, tree, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  const PoseidonTreePlan plan = poseidon_tree_plan(n_leaves, p->t - 1, ctx->poseidon_top_log);
+  if (!host && !poseidon_clear_of(p, tree, plan.nodes * 32))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": the tree must not overlap the parameters");
+  const PoseidonLaunch c = poseidon_launch(p, scalar_layout, tag32);
+  CallState& s = ctx->calls;
+  d.host = host, d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = leaves, d.in_bytes[0] = n_leaves * 32;
+  d.out = tree, d.out_bytes = plan.nodes * 32;
+  d.values_bytes = root32 ? 32 : 0;
+  const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
+    launch_poseidon_tree(st, c, io.in[0], n_leaves, ctx->poseidon_top_log, io.out);
+    io.values = (const uint8_t*)io.out + (plan.nodes - 1) * 32;
+    return MSM_AMD_OK;
+  });
+  if (rc == MSM_AMD_OK && root32) std::memcpy(root32, s.h_values, 32);   // a node: already in the call's layout
+  return rc;
+}
+
+int poseidon_merkle_paths_call(msm_amd_ctx* ctx, const msm_amd_poseidon_params* handle, bool host, int scalar_layout,
+                               const void* leaves, size_t n_leaves, const void* tree, const uint64_t* idx, size_t n_idx, void* out,
+                               float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_poseidon_merkle_paths" : "msm_amd_poseidon_merkle_paths_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_poseidon_params* p = find_handle(ctx->live_poseidon, handle);
+  if (!p) return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + kNotPoseidon);
+  if (const char* why = poseidon_paths_check(p->t, scalar_layout, leaves, n_leaves, tree, idx, n_idx, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n_idx == 0) return MSM_AMD_OK;
+  const uint32_t arity = p->t - 1, depth = poseidon_tree_depth(n_leaves, arity);
+  const size_t nodes = (n_leaves - 1) / (arity - 1), out_bytes = n_idx * depth * (arity - 1) * 32;
+  if (!host && !poseidon_clear_of(p, out, out_bytes))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": the paths must not overlap the parameters");
+  d.host = host, d.host_in = host ? 7u : 4u, d.kernel_ms = kernel_ms;
+  d.in[0] = leaves, d.in_bytes[0] = n_leaves * 32;
+  d.in[1] = tree, d.in_bytes[1] = nodes * 32;
+  d.in[2] = idx, d.in_bytes[2] = n_idx * sizeof(uint64_t);
+  d.out = out, d.out_bytes = out_bytes;
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    launch_merkle_paths(st, scalar_layout, arity, depth, io.in[0], n_leaves, io.in[1], io.in[2], n_idx, io.out);
+    return MSM_AMD_OK;
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_poseidon_params_build(msm_amd_ctx* ctx, uint32_t t, uint32_t r_f, uint32_t r_p, int scalar_layout, const void* ark,
+                                  const void* mds, msm_amd_poseidon_params** out) {
+  if (!ctx || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_poseidon_params_build: null pointer");
+  *out = nullptr;
+  if (const char* why = poseidon_constants_check(t, r_f, r_p, scalar_layout, ark, mds))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, std::string("msm_amd_poseidon_params_build: ") + why);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = recover_if_stalled(ctx)) return rc;
+  std::vector<u256> image;
+  poseidon_build_image(t, r_f, r_p, scalar_layout, ark, mds, &image);
+  int up = MSM_AMD_OK;
+  if (int rc = handle_build_tail(ctx, ctx->live_poseidon, image.size() * 32, "the constants of a Poseidon instance",
+                                 "Poseidon parameter build",
+                                 [&](void* d_mem) { up = staged_upload(ctx, d_mem, image.data(), image.size() * 32, ctx->stream); },
+                                 out))
+    return rc;
+  if (up) {   // the upload did not go through: nothing may read the allocation
+    msm_amd_poseidon_params* h = *out;
+    *out = nullptr;
+    const std::string why = ctx->last_error;
+    handle_free(ctx, ctx->live_poseidon, h, "");
+    return fail(ctx, up, "msm_amd_poseidon_params_build: " + why);
+  }
+  (*out)->t = t, (*out)->r_f = r_f, (*out)->r_p = r_p;
+  return MSM_AMD_OK;
+}
+
+int msm_amd_poseidon_params_info(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, uint32_t* t, uint32_t* r_f,
+                                 uint32_t* r_p, size_t* device_bytes) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_poseidon_params* p = find_handle(ctx->live_poseidon, params);
+  if (!p) return fail(ctx, MSM_AMD_INPUT_ERROR, std::string("msm_amd_poseidon_params_info") + kNotPoseidon);
+  if (t) *t = p->t;
+  if (r_f) *r_f = p->r_f;
+  if (r_p) *r_p = p->r_p;
+  if (device_bytes) *device_bytes = p->bytes;
+  return MSM_AMD_OK;
+}
+
+int msm_amd_poseidon_params_free(msm_amd_ctx* ctx, msm_amd_poseidon_params* params) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return handle_free(ctx, ctx->live_poseidon, params, "msm_amd_poseidon_params_free: not a Poseidon parameter handle of this ctx");
+}
+
+int msm_amd_poseidon_permute(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* in, size_t n,
+                             void* out) {
+  return poseidon_call(ctx, params, kPoseidonPermute, true, scalar_layout, nullptr, in, n, out, nullptr);
+}
+
+int msm_amd_poseidon_permute_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* d_in,
+                                    size_t n, void* d_out, float* kernel_ms) {
+  return poseidon_call(ctx, params, kPoseidonPermute, false, scalar_layout, nullptr, d_in, n, d_out, kernel_ms);
+}
+
+int msm_amd_poseidon_hash(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* tag32,
+                          const void* in, size_t n, void* out) {
+  return poseidon_call(ctx, params, kPoseidonHash, true, scalar_layout, tag32, in, n, out, nullptr);
+}
+
+int msm_amd_poseidon_hash_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* tag32,
+                                 const void* d_in, size_t n, void* d_out, float* kernel_ms) {
+  return poseidon_call(ctx, params, kPoseidonHash, false, scalar_layout, tag32, d_in, n, d_out, kernel_ms);
+}
+
+int msm_amd_poseidon_merkle_build(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* tag32,
+                                  const void* leaves, size_t n_leaves, void* tree, void* root32) {
+  return poseidon_merkle_build_call(ctx, params, true, scalar_layout, tag32, leaves, n_leaves, tree, root32, nullptr);
+}
+
+int msm_amd_poseidon_merkle_build_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout,
+                                         const void* tag32, const void* d_leaves, size_t n_leaves, void* d_tree, void* root32,
+                                         float* kernel_ms) {
+  return poseidon_merkle_build_call(ctx, params, false, scalar_layout, tag32, d_leaves, n_leaves, d_tree, root32, kernel_ms);
+}
+
+int msm_amd_poseidon_merkle_paths(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* leaves,
+                                  size_t n_leaves, const void* tree, const uint64_t* idx, size_t n_idx, void* out) {
+  return poseidon_merkle_paths_call(ctx, params, true, scalar_layout, leaves, n_leaves, tree, idx, n_idx, out, nullptr);
+}
+
+int msm_amd_poseidon_merkle_paths_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout,
+                                         const void* d_leaves, size_t n_leaves, const void* d_tree, const uint64_t* idx,
+                                         size_t n_idx, void* d_out, float* kernel_ms) {
+  return poseidon_merkle_paths_call(ctx, params, false, scalar_layout, d_leaves, n_leaves, d_tree, idx, n_idx, d_out, kernel_ms);
+}
+
+}  // extern "C"

@@ -7,6 +7,12 @@
 // synchronisation in between (the reference blocks after every stage: prepare_buckets_indices.rs:35-36,
 // bucket_wise_accumulation.rs:104-105, sum_reduction.rs:80-81); the only device->host hand-off is the
 // (c-2)*W partial window points for the host Horner pass.
+//
+// This file is the MSM driver: the ctx's lifecycle, bounded waits and buffer growth, the staging ring and uploader, the
+// bases cache, the planner, the instance pipeline of G1 and G2, the stage entry points and taps.  The ctx and the other
+// types are in host_ctx.h.  The blocking vector calls (point calls, transforms, vectors over Fr) are units of their own --
+// calls_points.hip, calls_ntt.hip, calls_fr.hip, all on device_call.h -- and reach into this file only through the
+// helpers host_ctx.h declares (msm_amd::drv, defined below).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,327 +44,9 @@
 #include "host_fq64.h"
 #include "test_ops.hip.h"
 #include "test_ops_g2.hip.h"
+#include "host_ctx.h"
 
 using namespace msm_amd;
-
-namespace {
-
-constexpr uint32_t kModulusBits = 254;   // limbs_conversion.rs:172, :344
-constexpr uint32_t kMinWindow = 3, kMaxWindow = 17;   // u16 digits up to 15, u32 digits for 16 and 17
-constexpr uint32_t kDefaultBallot = 1;                // sort ranking (Plan::ballot), chosen by profiles/r02_sort_ranking_ab.txt
-constexpr size_t kCpuDispatchBelow = 17;              // msm_best: see cpu_dispatch_below()
-
-struct DeviceBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-};
-
-// One hipEventRecord costs ~6 us of stream idle time on this stack (profiles/r02_lone_call_2p18_timeline.txt: 5.7 us
-// between two kernels with one event between them, none without), so the accumulate kernel is bracketed by ONE pair
-// of events that serves as stage span, kernel span (the roofline figure of bench.py) and start of the reduce span.
-enum {
-  EV_START = 0, EV_CONVERT, EV_DIGITS, EV_SORT, EV_ACC_S, EV_ACC, EV_REDUCE, EV_COUNT,
-  EV_ACC_K0 = EV_ACC_S, EV_ACC_K1 = EV_ACC, EV_RED_S = EV_ACC
-};
-
-// The host side of one instance, G1 or G2: its stage events and the page-locked landing place of its results --
-// h_partial_cap partial points of ext_bytes each (Jacobian or Jacobian2), then one more record of that size that
-// receives the plan counters of the instance (work-item statistics for timings and the stage tap).
-struct InstanceSlot {
-  hipEvent_t ev[EV_COUNT];
-  uint8_t* h_partial = nullptr;   // pinned
-  size_t h_partial_cap = 0, ext_bytes = 0;
-  bool has_events = false;
-  PlanCounters counters() const {
-    PlanCounters pc;
-    std::memcpy(&pc, h_partial + h_partial_cap * ext_bytes, sizeof pc);
-    return pc;
-  }
-};
-
-}  // namespace
-
-// Device buffers of one in-flight MSM.  A ctx owns kWorkspaces (4) of them and uses them round-robin: the window
-// reduction of instance i runs on a side stream while the main stream accumulates instance i+1 and the front
-// stream already sorts instance i+2, each in its own workspace.  The reduction is latency-bound (about 25 dependent point additions on a few hundred
-// workgroups) and so is the sort front-end; running them side by side hides the shorter of the two.  (Running
-// whole instances on parallel streams was tried and gained little: a resident accumulate grid keeps the
-// 1024-thread sort workgroups of the other stream from being placed at all.)
-struct Workspace {
-  DeviceBuf digits, coarse_cnt, region_start, tmp_idx, tmp_fine, tmp_idx2, tmp_fine2, mid_cnt, region_start2, bsize, bstart, istart, win_items, size_bins, sorted,
-      order, multi_list, redo_list, counters, bases29, buckets, item_partials, S, T, partial, conv_scalars, conv_points,
-      conv_tmp;
-  // hand-off events between the streams of the ctx (null in a workspace that one stream alone uses: G2State::ws)
-  hipEvent_t front_done = nullptr;    // front stream: sorted indices / work items of this workspace are ready
-  hipEvent_t acc_done = nullptr;      // main stream: buckets of this workspace are complete (incl. combine)
-  hipEvent_t reduce_done = nullptr;   // reduce stream: buckets / partial of this workspace are free again
-  bool acc_pending = false, reduce_pending = false;
-};
-
-// One set of bases a host-slice caller keeps handing over (msm_amd_set_bases_cache): the converted device copy, keyed
-// by (host pointer, n, layout) and guarded by sampled checksums of the host records.  The records are cut into
-// S = n / 1024 interleaved phases (record i belongs to phase i mod S); every phase is hashed when the entry is filled,
-// and every later call re-hashes phase 0 and one rotating phase of the caller's memory (~2 k records, tens of
-// microseconds): a changed array at an unchanged address is caught at once if it touches phase 0 and within S calls
-// otherwise.  The caller's contract stays "same pointer, same bases"; the checksums are the safety net.
-struct BasesCacheEntry {
-  const void* host = nullptr;
-  size_t n = 0;
-  int layout = 0;
-  std::vector<uint64_t> phase_hash;
-  std::vector<uint64_t> chunk_hash;   // kCacheChunks contiguous slices: the FULL verification (bases_cache_verify)
-  void* d_prepared = nullptr;   // n x AffPacked
-  uint64_t last_use = 0;        // bases_cache_call of the last call that used it
-  uint64_t wanted_by = 0;       // bases_cache_call of the last call whose arguments name it (bases_cache_reserve)
-  uint32_t next_phase = 1;
-};
-
-// Upload of PAGEABLE host memory through the library's own page-locked ring: helper threads copy 4 MiB chunks into
-// pinned slots, each chunk goes on by DMA as soon as it is there.  The runtime's staged copy of pageable memory blocks
-// the calling thread either way; on the HIP 7.0 runtime (the one inside the PyTorch wheel) it also serialises with
-// the kernels of the other streams, this path does not (a page-locked source never did).
-struct Stager {
-  static constexpr size_t kChunk = (size_t)4 << 20;
-  static constexpr int kSlots = 4, kMaxHelpers = 7;
-  int n_helpers = 3;   // MSM_AMD_STAGE_HELPERS = 1 .. 7 overrides (measured: profiles/r03_staged_upload_helpers.txt)
-  void* slot[kSlots] = {};
-  hipEvent_t sent[kSlots] = {};
-  bool busy[kSlots] = {};
-  int next = 0;
-  bool ready = false;
-  // helper threads: copy parts 1 .. n_helpers of the current chunk (the caller copies part 0)
-  std::vector<std::thread> helpers;
-  std::mutex m;
-  std::condition_variable wake, finished;
-  const uint8_t* src = nullptr;
-  uint8_t* dst = nullptr;
-  size_t bytes = 0;
-  std::atomic<uint64_t> generation{0};
-  int pending = 0;
-  bool quit = false;
-};
-
-// The uploads of a host-slice batch run on a helper thread, one instance ahead of the thread that submits kernels: a
-// copy from pageable memory blocks whoever issues it (the runtime stages it, or staged_upload does), and on the
-// submitting thread that was 1.3 ms per 2^20-point instance during which nothing else got enqueued.
-struct UploadJob {
-  void* d_scalars = nullptr;
-  const void* h_scalars = nullptr;
-  size_t scalar_bytes = 0;
-  void* d_points = nullptr;
-  const void* h_points = nullptr;
-  size_t point_bytes = 0;          // 0: the points are resident (prepared bases, tables, a bases-cache hit)
-  hipEvent_t wait_for = nullptr;   // GPU-side: the previous reader of the staging set (nullptr: none)
-  hipEvent_t done = nullptr;       // recorded on the copy stream behind the copies
-};
-struct Uploader {
-  std::thread th;
-  std::mutex m;
-  std::condition_variable cv, cv_idle;
-  UploadJob job;
-  bool has_job = false, busy = false, quit = false, started = false;
-  int status = 0;
-  std::string error;
-};
-
-constexpr int kWorkspaces = 4;
-constexpr int kReduceStreams = 2;
-constexpr int kMaxBatches = 4;   // batches that may be in flight between submit and wait
-
-struct Batch {
-  std::vector<InstanceSlot> slots;
-  std::vector<Plan> plans;
-  std::vector<int> ws_index;   // workspace each instance ran in (read by the msm_amd_test_* stage tap only)
-  std::vector<size_t> first_index;   // bounded calls: index of each instance's first record in the caller's vector (a
-                                     // call cut into point ranges, run_split), for the message of a violated bound
-  bool lone = false;
-  void* out = nullptr;
-  size_t n_inst = 0;
-  bool active = false;
-  bool abandoned = false;   // a blocking entry point gave up waiting for it (wait timeout): released once the device is idle
-};
-
-// What the handle kinds share: one device allocation.  Handles are validated by membership in the live list of
-// their kind (find_handle), never by dereferencing the caller's pointer; each kind is a type and a live list of its own,
-// so that a G1 table handle is no G2 table handle, neither is a transform domain, and the reverse.
-struct DeviceHandle {
-  void* d_mem = nullptr;
-  size_t bytes = 0;
-};
-
-// Precomputed window tables of one set of bases (msm_amd_tables_*, msm_amd_g2_tables_*): d_mem[w * n + i] = 2^(c w) P_i,
-// W * n AffPacked (G1, msm_amd_ctx::live_tables) or Aff2Packed (G2, msm_amd_ctx::live_g2_tables).
-struct TablesRecord : DeviceHandle {
-  size_t n = 0;
-  uint32_t c = 0, W = 0;
-};
-struct msm_amd_tables : TablesRecord {};
-struct msm_amd_g2_tables : TablesRecord {};
-
-// The twiddles of one (root, log_n) (msm_amd_ntt_domain_*, msm_amd_ctx::live_ntt): d_mem[j] = omega^j, j < n/2, Montgomery.
-struct msm_amd_ntt_domain : DeviceHandle {
-  int root = 0;
-  uint32_t log_n = 0;
-  u256 omega{};
-};
-
-// A sparse matrix over Fr (msm_amd_fr_matrix_*, msm_amd_ctx::live_fr_mat): d_mem is the image of fr_mat_image, planned at
-// the ctx's (fr_mat_long, fr_mat_seg_log) of the build.
-struct msm_amd_fr_matrix : DeviceHandle {
-  uint64_t n_rows = 0, n_cols = 0, nnz = 0, n_distinct = 0;
-  uint32_t long_rows = 0;
-  FrMatPlan plan{};
-  FrMatImage at{};
-};
-
-// The constants of one Poseidon instance (msm_amd_poseidon_params_*, msm_amd_ctx::live_poseidon): d_mem is the constants image
-// of fr_poseidon.hip.h, reduced Montgomery residues.
-struct msm_amd_poseidon_params : DeviceHandle {
-  uint32_t t = 0, r_f = 0, r_p = 0;
-};
-
-// Buffers of the blocking vector calls (device_call below): the staging of the host-buffer forms, the 64-byte record a
-// call reads back with its page-locked copy (the PointCounters of a check, decompress or compress call; T and the zero
-// count of a batch inversion), the device-side work buffers and two pairs of events behind kernel_ms.  Every such call
-// starts on an idle ctx and blocks until it is done, so one set serves the G1 point calls, the transform and the Fr
-// vector calls; G2State has a second one, so that a G2 call touches G2State only.
-struct CallState {
-  DeviceBuf in[3], out, reasons;   // staging of host inputs, output and reason bytes
-  DeviceBuf record;                // PointCounters
-  DeviceBuf table, xyzz;           // mul_points: the fixed-base table, the XYZZ records of one chunk of outputs
-  DeviceBuf scratch, pow;          // transform: the ONE batch-sized scratch of a plan with more than one pass, the powers of a shift;
-                                   // transform over points: `scratch` holds the two packed work arrays, back to back (2 x 64 n bytes)
-  DeviceBuf work;                  // Fr scan and inversion: the tile totals (fr_scan_plan, fr_inv_plan); the partial sums of
-                                   // the split rows of a sparse product (fr_mat_plan); the partial sums of a sumcheck round,
-                                   // the levels of a multilinear evaluation, the turns of a LOW bind (fr_mle.hip.h)
-  uint8_t* h_record = nullptr;     // pinned, 64 bytes
-  uint8_t* h_values = nullptr;     // pinned: the values a call reads back beside its output (p_v(z) of the polynomial calls)
-  size_t h_values_cap = 0;
-  hipEvent_t ev[4] = {};           // start and end of the first and of the second span
-  bool ready = false;              // record, h_record and ev exist
-  // everything but the record: what a kernel reads only after its own call has written it, so what
-  // msm_amd_test_fill_workspaces may poison
-  std::array<DeviceBuf*, 10> scratch_bufs() { return {&in[0], &in[1], &in[2], &out, &reasons, &table, &xyzz, &scratch, &pow, &work}; }
-  // msm_amd_destroy, with its own ways of releasing a buffer and an event
-  template <class KillBuf, class KillEvent>
-  void release(KillBuf kill_buf, KillEvent kill_event) {
-    kill_buf(record);
-    for (DeviceBuf* b : scratch_bufs()) kill_buf(*b);
-    for (hipEvent_t& e : ev) kill_event(e);
-    if (h_record) (void)hipHostFree(h_record);
-    if (h_values) (void)hipHostFree(h_values);
-    h_record = h_values = nullptr;
-    h_values_cap = 0;
-    ready = false;
-  }
-};
-static_assert(sizeof(PointCounters) == 64, "CallState::record and h_record hold one PointCounters");
-
-// State of the G2 MSM (msm_amd_msm_g2*): one blocking call at a time on the main stream, through the instance body of
-// G1 (enqueue_instance) in a workspace and a slot of its own -- a G2 call never touches what a G1 instance of the same
-// ctx may still be using.  `ws` is used on the main stream only and therefore has no hand-off events.
-struct G2State {
-  Workspace ws;
-  InstanceSlot slot;
-  DeviceBuf in_scalars, in_points;   // staging of host inputs
-  CallState calls;   // the G2 point calls; msm_amd_g2_check_points stages host points in in_points above
-  // Stage tap (msm_amd_test_g2_last_plan / msm_amd_test_g2_stage_copy): the plan of the last run_msm_g2, valid only
-  // while that call was the last one and succeeded.  Its plan counters are in `slot`, behind the partial points.
-  Plan last_plan{};
-  bool has_last_plan = false;
-};
-
-struct msm_amd_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;          // main stream: conversion, digits, sort, accumulate; stage entry points
-  hipStream_t reduce_streams[kReduceStreams] = {};   // side streams: window reduction + copy of the partial points.
-                                         // Consecutive instances alternate between them: the tail of an instance is a
-                                         // chain of latency-bound kernels that is as long as one accumulate, so two
-                                         // of them must be able to overlap.  (More streams than the four hardware
-                                         // queues HIP gives a process -- main, front, two reduce -- share a queue
-                                         // with the accumulate grid and wait behind it: measured, 1.6x slower.)
-  bool alt_reduce = true;                // MSM_AMD_ALT_REDUCE=0: one reduce stream
-  int acc_variant = 1;                   // accumulate kernel build (launch_accumulate): 1 shipped, 0 without the register pin; experiments build: 2..12
-  uint32_t acc_lds = 0;                  // LDS bytes per accumulate workgroup: caps its waves per CU (MSM_AMD_ACC_LDS)
-  uint32_t seq = 0;
-  hipStream_t front_stream = nullptr;    // side stream: conversion, digits, sort, work-item planning
-  hipStream_t copy_stream = nullptr;     // host-buffer entry points: uploads (DMA when the caller registered its buffers)
-  hipEvent_t uploaded[2] = {nullptr, nullptr};   // per staging set: the upload on copy_stream has finished
-  std::vector<std::pair<const void*, size_t>> host_regs;   // msm_amd_host_register
-  bool overlap_reduce = true;            // MSM_AMD_OVERLAP_REDUCE=0 puts the reduction on the main stream
-  bool overlap_front = true;             // MSM_AMD_OVERLAP_FRONT=0 puts the front end on the main stream
-  bool lone_single_stream = true;        // MSM_AMD_LONE_SINGLE_STREAM=0: a lone instance uses the stream split too
-  Workspace ws[kWorkspaces];
-  G2State g2;
-  CallState calls;   // the G1 point calls, the transform and the Fr vector calls
-  size_t mul_chunk = (size_t)1 << 18;   // outputs per chunk of a mul_points call (MSM_AMD_MUL_CHUNK), a multiple of kMulNormGroup
-  std::mutex mu;
-  std::string last_error;
-  uint32_t forced_window = 0;
-  // The width of the instances being submitted (msm_amd_msm_bounded* set it for the length of their call, under mu;
-  // enqueue_msm / run_msm_g2 plan with it); range_first, if set, holds the first record index of every instance
-  // submitted next (run_split), range_at the instance submit_batch_device starts from.
-  WidthBound bound{};
-  const size_t* range_first = nullptr;
-  size_t range_at = 0;
-  std::vector<msm_amd_tables*> live_tables;
-  std::vector<msm_amd_g2_tables*> live_g2_tables;
-  std::vector<msm_amd_ntt_domain*> live_ntt;
-  std::vector<msm_amd_fr_matrix*> live_fr_mat;
-  std::vector<msm_amd_poseidon_params*> live_poseidon;
-  uint32_t fr_tile_log = kFrTileLog;     // records per tile of a scan, as a power of two (MSM_AMD_FR_TILE_LOG)
-  uint32_t fr_mat_long = kFrMatLong;     // rows of a sparse matrix above this many entries take the wave path (MSM_AMD_FR_MAT_LONG)
-  bool fr_mat_signs = false;             // the product kernels that skip the product for values 1 and r - 1 (MSM_AMD_FR_MAT_SIGNS)
-  uint32_t fr_mat_seg_log = kFrMatSegLog;   // entries per wave of that path, as a power of two (MSM_AMD_FR_MAT_SEG_LOG)
-  uint32_t fr_mle_chunk_log = kFrMleChunkLog;   // pairs per wave of a sumcheck round, as a power of two (MSM_AMD_FR_MLE_CHUNK_LOG)
-  uint32_t poseidon_top_log = kPoseidonTopLog;   // tree levels of at most 2^this nodes share the last workgroup (MSM_AMD_POSEIDON_TOP_LOG)
-  uint32_t ntt_tile_log = kNttTileLog;   // elements per workgroup of a transform pass, as a power of two (MSM_AMD_NTT_TILE_LOG)
-  int next_ws = 0;
-  DeviceBuf scratch_a, scratch_b, scratch_c, scratch_b2, scratch_c2;
-  Batch batches[kMaxBatches];
-  int last_waited = -1;   // batch of the last successful wait_batch (msm_amd_test_last_plan / msm_amd_test_stage_copy)
-  msm_amd_timings timings{};
-  float after_sort_state = -1.0f;   // timings.reserved2[1] of the next wait (see msm_amd_gpu_msm_h2c_sync)
-  float after_sort_lead_ms = 0.0f;  // timings.reserved2[2]: device time from the callback to the end of accumulation
-  hipEvent_t after_sort_mark = nullptr;   // recorded on the idle copy stream the moment the callback is about to run
-  // Scalars staged by a single-instance entry point (msm_prepared, msm_tables, gpu_msm_h2c_sync): the upload is on
-  // `upload_stream`; whichever stream enqueue_msm then picks for the front end waits for `upload_done` unless it IS
-  // that stream (the entry point cannot know: run_batch_device may turn the call into pipelined point ranges).
-  hipEvent_t upload_done = nullptr;
-  hipStream_t upload_stream = nullptr;
-  bool upload_pending = false;
-  // Upper bound of every host wait for a GPU event (MSM_AMD_WAIT_TIMEOUT_MS, msm_amd_set_wait_timeout_ms; 0 = none).
-  // A wait that runs into it returns MSM_AMD_PIPELINE_ERROR naming the event and instance not reached; the batch
-  // stays in flight (`stalled`), and the next entry point first checks whether the device has caught up.
-  uint32_t wait_timeout_ms = 60000;
-  bool stalled = false;
-  // Opt-in cache of converted bases for the host-slice entry points (msm_amd_set_bases_cache, MSM_AMD_BASES_CACHE_MB)
-  std::vector<BasesCacheEntry> bases_cache;
-  size_t bases_cache_budget = 0, bases_cache_bytes = 0;
-  // 0 = sampled verification of a hit (phase 0 + one rotating phase of the caller's records), 1 = every record
-  // re-hashed on every hit (msm_amd_set_bases_cache_verify, MSM_AMD_BASES_CACHE_VERIFY=full)
-  int bases_cache_verify = 0;
-  uint64_t bases_cache_call = 0, bases_cache_hits = 0, bases_cache_misses = 0, bases_cache_invalidations = 0;
-  // device room for cache entries, allocated at the START of a host-slice call while the ctx is idle (nothing is ever
-  // allocated under work in flight) and taken by bases_cache_insert when the instance is dispatched
-  struct CacheReserve {
-    const void* host;
-    size_t n;
-    int layout;
-    void* d;
-  };
-  std::vector<CacheReserve> cache_reserve;
-  AffPacked* convert_into = nullptr;   // enqueue_msm writes the converted bases of the next instance here (a cache fill)
-  bool staging_points = false;         // the next instance's points sit in a staging set that is uploaded into again once
-                                       // its digits are done (run_batch_host): accumulate cannot gather them in place
-  // Device buffers replaced by bigger ones while work was in flight.  hipFree synchronises the whole device: inside
-  // a submit it would stall the pipeline and, on a device that does not answer, block without bound.  They are
-  // freed when the ctx has nothing in flight (reap_graveyard) or at msm_amd_destroy.
-  std::vector<void*> graveyard;
-  Stager stager;
-  Uploader uploader;
-  int staged_uploads = -1;   // -1 = decide by the runtime version (stage_pageable()), 0 / 1 = MSM_AMD_STAGED_UPLOAD
-};
 
 namespace {
 
@@ -369,11 +57,15 @@ msm_amd_ctx* g_global_ctx = nullptr;
 // that holds ctx->mu.
 thread_local std::string* tl_error_sink = nullptr;
 
+}  // namespace
+namespace msm_amd { namespace drv __attribute__((visibility("hidden"))) {
 int fail(msm_amd_ctx* ctx, int status, const std::string& msg) {
   if (tl_error_sink) *tl_error_sink = msg;
   else if (ctx) ctx->last_error = msg;
   return status;
 }
+}}  // namespace msm_amd::drv
+namespace {
 
 // Wait for everything this ctx has enqueued (error paths and set-up steps that reuse workspace 0).
 void drain_streams(msm_amd_ctx* ctx) {
@@ -408,11 +100,6 @@ bool drain_streams_bounded(msm_amd_ctx* ctx) {
   return true;
 }
 
-// Error paths and set-up steps: the bounded drain; a device that does not get there leaves the ctx marked stalled (the
-// next entry point checks whether it has caught up) instead of holding the caller.
-bool drain_or_mark_stalled(msm_amd_ctx* ctx);
-int sync_stream_bounded(msm_amd_ctx* ctx, hipStream_t st, const char* what);
-
 // hipEventSynchronize may park the thread (it did, for more than a millisecond, inside a process that also hosts
 // torch's thread pools) and it waits without bound: a device that stalls would block the caller of a blocking MSM
 // for ever, where the reference's call always returns (msm.rs:237-349).  The waits on the critical path therefore
@@ -444,17 +131,8 @@ uint32_t default_wait_timeout_ms() {
 
 const char* const kEventNames[] = {"start", "convert", "digits", "sort", "accumulate-start", "accumulate", "reduce"};
 
-#define HIP_TRY(ctx, expr)                                                                        \
-  do {                                                                                            \
-    hipError_t _e = (expr);                                                                       \
-    if (_e != hipSuccess) {                                                                       \
-      (void)hipGetLastError();                                                                    \
-      return fail(ctx, MSM_AMD_PIPELINE_ERROR,                                                    \
-                  std::string(#expr) + ": " + hipGetErrorString(_e) + " (" __FILE__ ":" +         \
-                      std::to_string(__LINE__) + ")");                                            \
-    }                                                                                             \
-  } while (0)
-
+}  // namespace
+namespace msm_amd { namespace drv __attribute__((visibility("hidden"))) {
 // A wait on this ctx ran into its bound earlier.  Before anything new is enqueued: has the device caught up?  If every
 // stream is idle the batches a blocking entry point abandoned are released; otherwise the call fails like the wait did.
 int recover_if_stalled(msm_amd_ctx* ctx) {
@@ -468,6 +146,8 @@ int recover_if_stalled(msm_amd_ctx* ctx) {
   ctx->stalled = false;
   return MSM_AMD_OK;
 }
+}}  // namespace msm_amd::drv
+namespace {
 
 // Nothing of this ctx is in flight (every submitted batch has been waited for): outgrown buffers can go.
 void reap_graveyard(msm_amd_ctx* ctx) {
@@ -479,6 +159,8 @@ void reap_graveyard(msm_amd_ctx* ctx) {
   ctx->graveyard.clear();
 }
 
+}  // namespace
+namespace msm_amd { namespace drv __attribute__((visibility("hidden"))) {
 // hipMalloc / hipHostMalloc / hipFree / hipHostFree may wait for the device (hipFree always does).  With work in flight
 // on a device that does not answer they would block without bound, before any bounded wait is reached -- so nothing
 // is allocated or released while the ctx has work in flight: a buffer that must grow first waits, WITH the ctx's wait
@@ -532,6 +214,8 @@ int ensure(msm_amd_ctx* ctx, DeviceBuf& b, size_t bytes) {
   b.cap = want;
   return MSM_AMD_OK;
 }
+}}  // namespace msm_amd::drv
+namespace {
 
 uint32_t floor_log2(size_t n) {
   uint32_t l = 0;
@@ -936,48 +620,12 @@ int reduce_buffers(msm_amd_ctx* ctx, Workspace& w, const Plan& p, size_t interna
   return ensure(ctx, w.partial, p.partial_count * ext_bytes);
 }
 
-// ---- handles: H = msm_amd_tables (ctx->live_tables), msm_amd_g2_tables (ctx->live_g2_tables), msm_amd_ntt_domain
-// (ctx->live_ntt), msm_amd_fr_matrix (ctx->live_fr_mat) or msm_amd_poseidon_params (ctx->live_poseidon).  ctx->mu is held by
-// the caller, as for every helper here.
-template <class H>
-const H* find_handle(const std::vector<H*>& live, const void* handle) {
-  for (const H* t : live)
-    if ((const void*)t == handle) return t;
-  return nullptr;
-}
-
 // window_size 0 = `auto_c`; the window and the number of windows of a table over n points
 int tables_geometry(msm_amd_ctx* ctx, size_t n, uint32_t window_size, uint32_t auto_c, uint32_t* c, uint32_t* W) {
   *c = window_size ? window_size : auto_c;
   if (*c < 4 || *c > 21) return fail(ctx, MSM_AMD_INPUT_ERROR, "table window_size must be 0 (auto) or 4..21");
   *W = kModulusBits / *c + 1;
   if ((size_t)*W * n > 0x7FFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, "windows * n must stay below 2^31");
-  return MSM_AMD_OK;
-}
-
-// The tail of a build: `bytes` of device memory (`memory` names it in messages), the build kernel (`launch(d_mem)` on
-// ctx->stream), a bounded wait (for `build`) and the new handle in `live`; the caller fills in what its kind adds to
-// DeviceHandle.
-template <class H, class Launch>
-int handle_build_tail(msm_amd_ctx* ctx, std::vector<H*>& live, size_t bytes, const std::string& memory,
-                      const std::string& build, Launch&& launch, H** out) {
-  void* d_mem = nullptr;
-  if (int qrc = quiesce_for_allocation(ctx, memory.c_str())) return qrc;
-  HIP_TRY(ctx, hipMalloc(&d_mem, bytes));
-  launch(d_mem);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && sync_stream_bounded(ctx, ctx->stream, build.c_str())) {
-    ctx->graveyard.push_back(d_mem);   // the build may still be running: released when the ctx is idle
-    return MSM_AMD_PIPELINE_ERROR;
-  }
-  if (e != hipSuccess) {
-    (void)hipFree(d_mem);
-    HIP_TRY(ctx, e);
-  }
-  H* h = new H();
-  h->d_mem = d_mem, h->bytes = bytes;
-  live.push_back(h);
-  *out = h;
   return MSM_AMD_OK;
 }
 
@@ -1000,18 +648,6 @@ int tables_info(msm_amd_ctx* ctx, const std::vector<H*>& live, const H* tables, 
   if (window_size) *window_size = t->c;
   if (num_windows) *num_windows = t->W;
   if (device_bytes) *device_bytes = t->bytes;
-  return MSM_AMD_OK;
-}
-
-template <class H>
-int handle_free(msm_amd_ctx* ctx, std::vector<H*>& live, H* handle, const char* not_a_handle) {
-  auto it = std::find(live.begin(), live.end(), handle);
-  if (it == live.end()) return fail(ctx, MSM_AMD_INPUT_ERROR, not_a_handle);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  live.erase(it);
-  if (drain_or_mark_stalled(ctx)) (void)hipFree(handle->d_mem);
-  else ctx->graveyard.push_back(handle->d_mem);   // hipFree would wait for the device without bound
-  delete handle;
   return MSM_AMD_OK;
 }
 
@@ -1055,6 +691,8 @@ bool scalar_layout_ok(int scalar_layout) {
   return scalar_layout >= MSM_AMD_SCALAR_MONT_LE && scalar_layout <= MSM_AMD_SCALAR_CANON_BE32;
 }
 
+}  // namespace
+namespace msm_amd { namespace drv __attribute__((visibility("hidden"))) {
 // ms between two recorded events (0 if either cannot be read)
 float event_span(hipEvent_t a, hipEvent_t b) {
   float t = 0;
@@ -1064,6 +702,8 @@ float event_span(hipEvent_t a, hipEvent_t b) {
   }
   return t;
 }
+}}  // namespace msm_amd::drv
+namespace {
 
 // Row / column sums of the window reduction for a LONE call: with no neighbouring instance to fill the machine, the
 // 15-addition chains of the pipelined setting (one lane per 16 buckets: 35 k lanes at 2^18 points, 7.7 k in the second
@@ -1611,6 +1251,8 @@ bool stage_pageable(msm_amd_ctx* ctx, const void* src, size_t bytes) {
   return ctx->staged_uploads == 1 && !host_pinned(src);
 }
 
+}  // namespace
+namespace msm_amd { namespace drv __attribute__((visibility("hidden"))) {
 // hipMemcpyAsync(dst, src, bytes, H2D, stream) for a pageable src, through the ring.  Returns when the last chunk has
 // been handed to the DMA engine (the caller's buffer is no longer needed), not when it has arrived.
 int staged_upload(msm_amd_ctx* ctx, void* d_dst, const void* h_src, size_t bytes, hipStream_t stream) {
@@ -1646,6 +1288,8 @@ int staged_upload(msm_amd_ctx* ctx, void* d_dst, const void* h_src, size_t bytes
   }
   return MSM_AMD_OK;
 }
+}}  // namespace msm_amd::drv
+namespace {
 
 // A LONE call of many points runs as ONE PIPELINED BATCH of sub-instances over point ranges (the algebra of the
 // reference's GPU + CPU split, msm.rs:385-419: the MSM of a union of point ranges is the sum of the MSMs).  Alone, an
@@ -3889,1425 +3533,6 @@ int msm_amd_test_op_g2(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch_c.p, out_bytes, hipMemcpyDeviceToHost, st));
   return sync_stream_bounded(ctx, st, __func__);
-}
-
-}  // extern "C"
-
-// ---- the blocking vector calls: the point calls of both groups, the transform, the vectors over Fr ------------------------
-// One driver for all of them (device_call): the device set, a bounded drain of the ctx's earlier work, every buffer sized
-// on the idle ctx before anything is enqueued, host input through the page-locked staging ring, the caller's kernels on
-// the main stream (between events when the call is timed), the 64-byte record of a call that has one behind a bounded
-// wait, output and reason bytes behind a bounded stream wait.  Each call below validates its own arguments, takes
-// ctx->mu, describes its buffers in a DeviceCall and passes a callable that enqueues its kernels; one that takes the
-// finished record, and the kernels that follow it, are optional.
-namespace {
-
-struct DeviceCall {
-  std::string who;              // the entry point, in every message
-  bool g2 = false;              // the buffers are G2State::calls
-  bool host = false;            // out / reasons are host memory: written in the staging and copied back
-  unsigned host_in = 0;         // bit k: in[k] is host memory and goes through the staging
-  bool in_place = false;        // host: the result is written over the staged in[0] and copied back from there
-  bool counters = false;        // the record is PointCounters: reset before the kernels, read back behind them
-  float* kernel_ms = nullptr;   // optional: the device time of the kernels
-  size_t n = 0;                 // reason bytes
-  const void* in[3] = {};
-  size_t in_bytes[3] = {};
-  DeviceBuf* stage[3] = {};     // the staging of in[k] if not CallState::in[k] (G2State::in_points, CallState::pow)
-  void* out = nullptr;
-  size_t out_bytes = 0;
-  uint8_t* reasons = nullptr;   // optional
-  struct {
-    DeviceBuf* buf;
-    size_t bytes;
-  } work[2] = {};               // device-side buffers of the kernels
-  size_t values_bytes = 0;      // what launch leaves at CallIo::values comes back in CallState::h_values
-  void all_host(bool h) { host = h, host_in = h ? 7u : 0u; }
-};
-
-// what the kernels of a call see: device memory throughout
-struct CallIo {
-  const void* in[3];
-  void* out;
-  uint8_t* reasons;
-  PointCounters* counters;
-  const void* record;   // the 64 bytes to read back: `counters` of a call that has them; else null, unless launch sets it
-  const void* values;   // DeviceCall::values_bytes to read back behind the kernels; launch sets it
-};
-
-// ctx->mu is held.  launch(stream, io) enqueues the kernels and returns a status.  A call with a record gets it back
-// behind a bounded wait: then(record, device_ms) takes it on the host, and launch2(stream, io), if there is one,
-// enqueues the kernels that needed it.  kernel_ms is the time of the one or two spans of kernels, without the host's
-// step between them; an event is recorded only for a call that has counters or asks for the time (one hipEventRecord
-// costs ~6 us of stream idle time, see EV_START above).
-template <class Launch, class Then, class Launch2>
-int device_call(msm_amd_ctx* ctx, const DeviceCall& c, Launch launch, Then then, Launch2 launch2) {
-  constexpr bool two_spans = !std::is_null_pointer<Launch2>::value;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (int rc = recover_if_stalled(ctx)) return fail(ctx, rc, c.who + ": " + ctx->last_error);
-  if (!drain_or_mark_stalled(ctx))
-    return fail(ctx, MSM_AMD_PIPELINE_ERROR, c.who + ": device busy past the wait bound of " +
-                                                 std::to_string(ctx->wait_timeout_ms) + " ms (msm_amd_synchronize waits again)");
-  CallState& s = c.g2 ? ctx->g2.calls : ctx->calls;
-  hipStream_t st = ctx->stream;
-  int rc;
-  // the ctx is idle: the first call creates the record and the events, and every buffer of this call is sized now
-  if (!s.ready) {
-    if ((rc = ensure(ctx, s.record, sizeof(PointCounters)))) return rc;
-    if (!s.h_record) HIP_TRY(ctx, hipHostMalloc((void**)&s.h_record, sizeof(PointCounters), hipHostMallocDefault));
-    for (hipEvent_t& e : s.ev)
-      if (!e) HIP_TRY(ctx, hipEventCreate(&e));
-    s.ready = true;
-  }
-  for (const auto& w : c.work)
-    if (w.buf && (rc = ensure(ctx, *w.buf, w.bytes))) return rc;
-  if (c.values_bytes > s.h_values_cap) {
-    if (s.h_values) (void)hipHostFree(s.h_values);
-    s.h_values = nullptr, s.h_values_cap = 0;
-    HIP_TRY(ctx, hipHostMalloc((void**)&s.h_values, c.values_bytes, hipHostMallocDefault));
-    s.h_values_cap = c.values_bytes;
-  }
-  DeviceBuf* stage[3];
-  for (int k = 0; k < 3; ++k) {
-    stage[k] = c.stage[k] ? c.stage[k] : &s.in[k];
-    if ((c.host_in >> k & 1) && (rc = ensure(ctx, *stage[k], c.in_bytes[k]))) return rc;
-  }
-  if (c.host && !c.in_place && (rc = ensure(ctx, s.out, c.out_bytes))) return rc;
-  if (c.host && c.reasons && (rc = ensure(ctx, s.reasons, c.n))) return rc;
-  CallIo io = {{c.in[0], c.in[1], c.in[2]}, c.out, c.reasons, (PointCounters*)s.record.p, c.counters ? s.record.p : nullptr,
-               nullptr};
-  for (int k = 0; k < 3; ++k)
-    if ((c.host_in >> k & 1) && c.in_bytes[k]) {
-      if ((rc = staged_upload(ctx, stage[k]->p, c.in[k], c.in_bytes[k], st))) return rc;
-      io.in[k] = stage[k]->p;
-    }
-  if (c.host && c.out_bytes) io.out = c.in_place ? const_cast<void*>(io.in[0]) : s.out.p;
-  if (c.host && c.reasons) io.reasons = (uint8_t*)s.reasons.p;
-  const bool timed = c.counters || c.kernel_ms;
-  auto span = [&](auto& enqueue, int first_event) -> int {
-    if (timed) HIP_TRY(ctx, hipEventRecord(s.ev[first_event], st));
-    if (int lrc = enqueue(st, io)) return lrc;
-    HIP_TRY(ctx, hipGetLastError());
-    if (timed) HIP_TRY(ctx, hipEventRecord(s.ev[first_event + 1], st));
-    return MSM_AMD_OK;
-  };
-  if (c.counters) launch_point_reset(st, io.counters);
-  if ((rc = span(launch, 0))) return rc;
-  const bool has_record = io.record != nullptr;
-  bool pending = true;   // work enqueued and not waited for
-  float ms = 0.0f;
-  if (has_record) {
-    HIP_TRY(ctx, hipMemcpyAsync(s.h_record, io.record, sizeof(PointCounters), hipMemcpyDeviceToHost, st));
-    if ((rc = sync_stream_bounded(ctx, st, c.who.c_str()))) return rc;
-    if (timed) ms = event_span(s.ev[0], s.ev[1]);
-    then(s.h_record, ms);
-    if constexpr (two_spans) {
-      if ((rc = span(launch2, 2))) return rc;
-    } else {
-      pending = false;
-    }
-  }
-  if (c.host && c.out_bytes) HIP_TRY(ctx, hipMemcpyAsync(c.out, io.out, c.out_bytes, hipMemcpyDeviceToHost, st));
-  if (c.host && c.reasons) HIP_TRY(ctx, hipMemcpyAsync(c.reasons, io.reasons, c.n, hipMemcpyDeviceToHost, st));
-  if (c.values_bytes) HIP_TRY(ctx, hipMemcpyAsync(s.h_values, io.values, c.values_bytes, hipMemcpyDeviceToHost, st));
-  if ((c.host && (c.out_bytes || c.reasons)) || c.values_bytes) pending = true;
-  if (pending && (rc = sync_stream_bounded(ctx, st, c.who.c_str()))) return rc;
-  if (timed && !has_record) ms = event_span(s.ev[0], s.ev[1]);
-  if (timed && two_spans) ms += event_span(s.ev[2], s.ev[3]);
-  if (c.kernel_ms) *c.kernel_ms = ms;
-  return MSM_AMD_OK;
-}
-
-template <class Launch, class Then>
-int device_call(msm_amd_ctx* ctx, const DeviceCall& c, Launch launch, Then then) {
-  return device_call(ctx, c, launch, then, nullptr);
-}
-
-template <class Launch>
-int device_call(msm_amd_ctx* ctx, const DeviceCall& c, Launch launch) {
-  return device_call(ctx, c, launch, [](const uint8_t*, float) {}, nullptr);
-}
-
-// The point calls: n records (and reason bytes) of host or of device memory throughout; null_arg: some required
-// pointer is null.  done(counters, device_ms) takes the result of a call with counters (and the empty counters of a
-// call with n == 0, whatever its kind).
-template <class Launch, class Done>
-int point_call(msm_amd_ctx* ctx, const DeviceCall& c, bool null_arg, Launch launch, Done done) {
-  if (c.n > 0xFFFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": n >= 2^32");
-  if (c.n == 0) {
-    done(point_counters_empty(), 0.0f);
-    return MSM_AMD_OK;
-  }
-  if (null_arg) return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": null pointer with n > 0");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  return device_call(ctx, c, launch, [&](const uint8_t* record, float ms) {
-    PointCounters pc;
-    std::memcpy(&pc, record, sizeof pc);
-    done(pc, ms);
-  });
-}
-
-// ---- point validation (msm_amd_check_points*, msm_amd_g2_check_points*) ---------------------------------------------
-int check_call(msm_amd_ctx* ctx, bool g2, bool host, int layout, const void* points, size_t n, uint32_t checks,
-               uint8_t* reasons, msm_amd_check_report* report) {
-  if (!ctx || !report) return MSM_AMD_INPUT_ERROR;
-  DeviceCall c;
-  c.who = g2 ? "msm_amd_g2_check_points" : "msm_amd_check_points";   // the _device calls go by the same name
-  const uint32_t stride = point_record_bytes(g2, layout, kKindHost);
-  if (stride == 0)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": takes the host point layouts only (not *_PREPARED / *_TABLES)");
-  if (checks == 0 || (checks & ~(uint32_t)(MSM_AMD_CHECK_CURVE | MSM_AMD_CHECK_SUBGROUP)))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": checks must be MSM_AMD_CHECK_CURVE and / or MSM_AMD_CHECK_SUBGROUP");
-  c.g2 = g2, c.counters = true, c.n = n;
-  c.all_host(host);
-  c.in[0] = points, c.in_bytes[0] = n * stride;
-  c.reasons = reasons;
-  if (g2) c.stage[0] = &ctx->g2.in_points;
-  return point_call(
-      ctx, c, !points,
-      [&](hipStream_t st, const CallIo& io) {
-        if (g2)
-          launch_check_g2(st, io.in[0], layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n, checks, io.reasons, io.counters);
-        else
-          launch_check_g1(st, io.in[0], layout, stride, (uint32_t)n, io.reasons, io.counters);
-        return MSM_AMD_OK;
-      },
-      [&](const PointCounters& pc, float ms) { point_report_decode(pc, n, ms, report); });
-}
-
-// ---- compressed points (msm_amd_decompress_points*, msm_amd_compress_points* and their G2 forms) ----------------------
-// layout: the output layout of a decompression, the input layout of a compression
-int compress_call(msm_amd_ctx* ctx, bool g2, bool host, bool decompress, int format, int layout, const void* in, size_t n,
-                  void* out, uint8_t* reasons, msm_amd_decompress_report* report, uint64_t* n_bad) {
-  if (!ctx || (decompress && !report)) return MSM_AMD_INPUT_ERROR;
-  DeviceCall c;
-  c.who = std::string(g2 ? "msm_amd_g2_" : "msm_amd_") + (decompress ? "decompress_points" : "compress_points") +
-          (host ? "" : "_device");
-  const bool prepared_ok = decompress && !host;
-  const uint32_t stride = point_record_bytes(g2, layout, prepared_ok ? kKindAffine | kKindPrepared : kKindAffine);
-  if (!compress_format_known(format))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": unknown format (MSM_AMD_COMPRESSED_ARK / _PARITY)");
-  if (stride == 0)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + (prepared_ok ? ": takes the two affine layouts and *_PREPARED (not *_TABLES)"
-                                                               : ": takes the two affine host layouts only"));
-  const size_t wire = g2 ? 64 : 32;
-  c.g2 = g2, c.counters = true, c.n = n;
-  c.all_host(host);
-  c.in[0] = in, c.in_bytes[0] = n * (decompress ? wire : stride);
-  c.out = out, c.out_bytes = n * (decompress ? stride : wire);
-  c.reasons = reasons;
-  return point_call(
-      ctx, c, !in || !out,
-      [&](hipStream_t st, const CallIo& io) {
-        if (decompress)
-          launch_decompress(st, g2, format, io.in[0], (uint32_t)n, layout, stride, io.out, io.reasons, io.counters);
-        else
-          launch_compress(st, g2, layout, stride, io.in[0], (uint32_t)n, format, io.out, io.counters);
-        return MSM_AMD_OK;
-      },
-      [&](const PointCounters& pc, float ms) {
-        if (decompress) point_report_decode(pc, n, ms, report);
-        else if (n_bad) *n_bad = pc.by_reason[kPointNotReduced];
-      });
-}
-
-// ---- batch scalar multiplication (msm_amd_mul_points*, msm_amd_g2_mul_points*) ------------------------------------------
-// The outputs run in chunks of ctx->mul_chunk records (a multiple of the normalisation group, so the groups of a
-// chunked call are those of an unchunked one), all enqueued on the main stream: stream order hands the XYZZ buffer from
-// one chunk to the next.  No counters and no event: the bounded stream wait at the end of device_call is the call's.
-int mul_call(msm_amd_ctx* ctx, bool g2, bool host, int scalar_layout, int layout_in, int base_mode, const void* scalars,
-             const void* points, size_t n, int layout_out, void* out) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall c;
-  c.who = std::string(g2 ? "msm_amd_g2_mul_points" : "msm_amd_mul_points") + (host ? "" : "_device");
-  const uint32_t prepared = host ? 0u : (uint32_t)kKindPrepared;
-  const size_t in_stride = point_record_bytes(g2, layout_in, kKindHost | prepared),
-               out_stride = point_record_bytes(g2, layout_out, kKindAffine | prepared);
-  if (!mul_scalar_layout_known(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": unknown scalar layout");
-  if (in_stride == 0)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + (host ? ": points in a host layout only (not *_PREPARED / *_TABLES)"
-                                                        : ": points in a host layout or *_PREPARED (not *_TABLES)"));
-  if (out_stride == 0)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + (host ? ": output in one of the two affine host layouts only"
-                                                        : ": output in one of the two affine layouts or *_PREPARED"));
-  if (base_mode != MSM_AMD_MUL_BASE_EACH && base_mode != MSM_AMD_MUL_BASE_ONE)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": base_mode must be MSM_AMD_MUL_BASE_EACH or MSM_AMD_MUL_BASE_ONE");
-  const bool one = base_mode == MSM_AMD_MUL_BASE_ONE;
-  const size_t chunk = std::min(n, ctx->mul_chunk);
-  CallState& s = g2 ? ctx->g2.calls : ctx->calls;
-  c.g2 = g2, c.n = n;
-  c.all_host(host);
-  c.in[0] = scalars, c.in_bytes[0] = n * 32;
-  c.in[1] = points, c.in_bytes[1] = (one ? 1 : n) * in_stride;
-  c.out = out, c.out_bytes = n * out_stride;
-  c.work[0] = {&s.table, one ? mul_table_bytes(g2) : 0}, c.work[1] = {&s.xyzz, chunk * mul_xyzz_bytes(g2)};
-  return point_call(
-      ctx, c, !scalars || !points || !out,
-      [&](hipStream_t st, const CallIo& io) {
-        void *table = s.table.p, *xyzz = s.xyzz.p;
-        if (one) launch_mul_table(st, g2, layout_in, io.in[1], table);
-        for (size_t first = 0; first < n; first += chunk) {
-          const uint32_t m = (uint32_t)std::min(chunk, n - first);
-          const uint8_t* sc = (const uint8_t*)io.in[0] + first * 32;
-          if (one)
-            launch_mul_fixed(st, g2, scalar_layout, sc, m, table, xyzz);
-          else
-            launch_mul_each(st, g2, scalar_layout, sc, layout_in, (const uint8_t*)io.in[1] + first * in_stride, m, xyzz);
-          launch_mul_normalise(st, g2, xyzz, m, layout_out, (uint8_t*)io.out + first * out_stride);
-        }
-        return MSM_AMD_OK;
-      },
-      [](const PointCounters&, float) {});
-}
-
-}  // namespace
-
-extern "C" {
-
-int msm_amd_check_points(msm_amd_ctx* ctx, int point_layout, const void* points, size_t n, uint32_t checks,
-                         uint8_t* reasons, msm_amd_check_report* report) {
-  return check_call(ctx, false, true, point_layout, points, n, checks, reasons, report);
-}
-
-int msm_amd_check_points_device(msm_amd_ctx* ctx, int point_layout, const void* d_points, size_t n, uint32_t checks,
-                                uint8_t* d_reasons, msm_amd_check_report* report) {
-  return check_call(ctx, false, false, point_layout, d_points, n, checks, d_reasons, report);
-}
-
-int msm_amd_g2_check_points(msm_amd_ctx* ctx, int g2_point_layout, const void* points, size_t n, uint32_t checks,
-                            uint8_t* reasons, msm_amd_check_report* report) {
-  return check_call(ctx, true, true, g2_point_layout, points, n, checks, reasons, report);
-}
-
-int msm_amd_g2_check_points_device(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n,
-                                   uint32_t checks, uint8_t* d_reasons, msm_amd_check_report* report) {
-  return check_call(ctx, true, false, g2_point_layout, d_points, n, checks, d_reasons, report);
-}
-
-int msm_amd_decompress_points(msm_amd_ctx* ctx, int format, const void* in, size_t n, int point_layout_out, void* out,
-                              uint8_t* reasons, msm_amd_decompress_report* report) {
-  return compress_call(ctx, false, true, true, format, point_layout_out, in, n, out, reasons, report, nullptr);
-}
-
-int msm_amd_decompress_points_device(msm_amd_ctx* ctx, int format, const void* d_in, size_t n, int point_layout_out,
-                                     void* d_out, uint8_t* d_reasons, msm_amd_decompress_report* report) {
-  return compress_call(ctx, false, false, true, format, point_layout_out, d_in, n, d_out, d_reasons, report, nullptr);
-}
-
-int msm_amd_g2_decompress_points(msm_amd_ctx* ctx, int format, const void* in, size_t n, int g2_point_layout_out,
-                                 void* out, uint8_t* reasons, msm_amd_decompress_report* report) {
-  return compress_call(ctx, true, true, true, format, g2_point_layout_out, in, n, out, reasons, report, nullptr);
-}
-
-int msm_amd_g2_decompress_points_device(msm_amd_ctx* ctx, int format, const void* d_in, size_t n,
-                                        int g2_point_layout_out, void* d_out, uint8_t* d_reasons,
-                                        msm_amd_decompress_report* report) {
-  return compress_call(ctx, true, false, true, format, g2_point_layout_out, d_in, n, d_out, d_reasons, report, nullptr);
-}
-
-int msm_amd_compress_points(msm_amd_ctx* ctx, int point_layout_in, const void* in, size_t n, int format, void* out,
-                            uint64_t* n_bad) {
-  return compress_call(ctx, false, true, false, format, point_layout_in, in, n, out, nullptr, nullptr, n_bad);
-}
-
-int msm_amd_compress_points_device(msm_amd_ctx* ctx, int point_layout_in, const void* d_in, size_t n, int format,
-                                   void* d_out, uint64_t* n_bad) {
-  return compress_call(ctx, false, false, false, format, point_layout_in, d_in, n, d_out, nullptr, nullptr, n_bad);
-}
-
-int msm_amd_g2_compress_points(msm_amd_ctx* ctx, int g2_point_layout_in, const void* in, size_t n, int format, void* out,
-                               uint64_t* n_bad) {
-  return compress_call(ctx, true, true, false, format, g2_point_layout_in, in, n, out, nullptr, nullptr, n_bad);
-}
-
-int msm_amd_g2_compress_points_device(msm_amd_ctx* ctx, int g2_point_layout_in, const void* d_in, size_t n, int format,
-                                      void* d_out, uint64_t* n_bad) {
-  return compress_call(ctx, true, false, false, format, g2_point_layout_in, d_in, n, d_out, nullptr, nullptr, n_bad);
-}
-
-int msm_amd_mul_points(msm_amd_ctx* ctx, int scalar_layout, int point_layout_in, int base_mode, const void* scalars,
-                       const void* points, size_t n, int point_layout_out, void* out) {
-  return mul_call(ctx, false, true, scalar_layout, point_layout_in, base_mode, scalars, points, n, point_layout_out, out);
-}
-
-int msm_amd_mul_points_device(msm_amd_ctx* ctx, int scalar_layout, int point_layout_in, int base_mode,
-                              const void* d_scalars, const void* d_points, size_t n, int point_layout_out, void* d_out) {
-  return mul_call(ctx, false, false, scalar_layout, point_layout_in, base_mode, d_scalars, d_points, n, point_layout_out,
-                  d_out);
-}
-
-int msm_amd_g2_mul_points(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout_in, int base_mode, const void* scalars,
-                          const void* points, size_t n, int g2_point_layout_out, void* out) {
-  return mul_call(ctx, true, true, scalar_layout, g2_point_layout_in, base_mode, scalars, points, n, g2_point_layout_out,
-                  out);
-}
-
-int msm_amd_g2_mul_points_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout_in, int base_mode,
-                                 const void* d_scalars, const void* d_points, size_t n, int g2_point_layout_out,
-                                 void* d_out) {
-  return mul_call(ctx, true, false, scalar_layout, g2_point_layout_in, base_mode, d_scalars, d_points, n,
-                  g2_point_layout_out, d_out);
-}
-
-}  // extern "C"
-
-// ---- stage entries of the batch scalar multiplication (test aid: msm_amd_test_mul_stage, msm_amd_test_mul_stage_host) ----
-// The digit walk and the shared normalisation of mul_points.hip.h on inputs the public calls never produce: a table the
-// caller wrote (identity entries, an entry equal to a partial sum or to its negative) and XYZZ records at the edge of
-// the point invariant.  The device form goes through point_call (device_call) and the launch wrappers of launch_mul.h like
-// msm_amd_mul_points; the host form runs the bodies host_mul.hip runs.  NORMALISE works on a copy of the records,
-// because mul_normalise overwrites them; NORMALISE_RECORDS returns that copy instead of the affine bytes.
-namespace {
-
-struct MulStage {
-  bool g2 = false, fixed = false, records = false;
-  size_t in_stride = 0, out_stride = 0;   // bytes per record of `in` and of `out`
-  size_t affine_stride = 0;               // the two normalisation stages: bytes per affine record
-};
-
-// false: an unknown group, stage or layout
-bool mul_stage_shape(int group, int which, int layout, MulStage* s) {
-  if ((group != 1 && group != 2) || which < MSM_AMD_MUL_STAGE_FIXED || which > MSM_AMD_MUL_STAGE_NORMALISE_RECORDS) return false;
-  s->g2 = group == 2;
-  s->fixed = which == MSM_AMD_MUL_STAGE_FIXED;
-  s->records = which == MSM_AMD_MUL_STAGE_NORMALISE_RECORDS;
-  if (s->fixed) {
-    if (!mul_scalar_layout_known(layout)) return false;
-    s->in_stride = 32, s->out_stride = mul_xyzz_bytes(s->g2);
-    return true;
-  }
-  s->affine_stride = point_record_bytes(s->g2, layout, kKindAffine);
-  s->in_stride = mul_xyzz_bytes(s->g2);
-  s->out_stride = s->records ? s->in_stride : s->affine_stride;
-  return s->affine_stride != 0;
-}
-
-template <class G>
-void mul_stage_host(const MulStage& s, int layout, const uint8_t* in, const void* table, size_t n, uint8_t* out) {
-  if (s.fixed) {
-    for (size_t i = 0; i < n; ++i)
-      G::store_pt((typename G::Pt*)(out + i * s.out_stride),
-                  mul_fixed<G>(mul_scalar(layout, in + i * 32), (const typename G::Packed*)table));
-    return;
-  }
-  alignas(16) typename G::Pt recs[kMulNormGroup];
-  std::vector<uint8_t> affine(s.records ? kMulNormGroup * s.affine_stride : 0);
-  for (size_t first = 0; first < n; first += kMulNormGroup) {   // the groups of mul_normalise_kernel
-    const uint32_t m = (uint32_t)std::min<size_t>(kMulNormGroup, n - first);
-    std::memcpy(recs, in + first * s.in_stride, m * s.in_stride);
-    mul_normalise<G>(recs, m, layout, (uint32_t)s.affine_stride, s.records ? affine.data() : out + first * s.affine_stride);
-    if (s.records) std::memcpy(out + first * s.in_stride, recs, m * s.in_stride);
-  }
-}
-
-}  // namespace
-
-extern "C" {
-
-int msm_amd_test_mul_stage(msm_amd_ctx* ctx, int group, int which, int layout, const void* in, const void* table,
-                           size_t n, void* out) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  MulStage s;
-  if (!mul_stage_shape(group, which, layout, &s))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_mul_stage: unknown group, stage or layout");
-  DeviceCall c;
-  c.who = "msm_amd_test_mul_stage";
-  CallState& cs = s.g2 ? ctx->g2.calls : ctx->calls;
-  c.g2 = s.g2, c.n = n;
-  c.all_host(true);
-  c.in[0] = in, c.in_bytes[0] = n * s.in_stride;
-  c.in[1] = table, c.in_bytes[1] = s.fixed ? mul_table_bytes(s.g2) : 0;
-  c.out = out, c.out_bytes = n * s.out_stride;
-  if (s.records) c.work[0] = {&cs.xyzz, n * s.affine_stride};   // where the affine bytes of NORMALISE_RECORDS go
-  return point_call(
-      ctx, c, !in || !out || (s.fixed && !table),
-      [&](hipStream_t st, const CallIo& io) -> int {
-        if (s.fixed) {
-          launch_mul_fixed(st, s.g2, layout, io.in[0], (uint32_t)n, io.in[1], io.out);
-        } else if (s.records) {   // the records move to the output buffer and are normalised there
-          HIP_TRY(ctx, hipMemcpyAsync(io.out, io.in[0], n * s.in_stride, hipMemcpyDeviceToDevice, st));
-          launch_mul_normalise(st, s.g2, io.out, (uint32_t)n, layout, cs.xyzz.p);
-        } else {                  // io.in[0] is the staged copy of the caller's records: the kernel may overwrite it
-          launch_mul_normalise(st, s.g2, const_cast<void*>(io.in[0]), (uint32_t)n, layout, io.out);
-        }
-        return MSM_AMD_OK;
-      },
-      [](const PointCounters&, float) {});
-}
-
-int msm_amd_test_mul_stage_host(int group, int which, int layout, const void* in, const void* table, size_t n, void* out) {
-  MulStage s;
-  if (!mul_stage_shape(group, which, layout, &s) || n > 0xFFFFFFFFull) return MSM_AMD_INPUT_ERROR;
-  if (n == 0) return MSM_AMD_OK;
-  if (!in || !out || (s.fixed && !table)) return MSM_AMD_INPUT_ERROR;
-  if (s.g2)
-    mul_stage_host<MulG2>(s, layout, (const uint8_t*)in, table, n, (uint8_t*)out);
-  else
-    mul_stage_host<MulG1>(s, layout, (const uint8_t*)in, table, n, (uint8_t*)out);
-  return MSM_AMD_OK;
-}
-
-}  // extern "C"
-
-// ---- number-theoretic transform over Fr (msm_amd_ntt_domain_*, msm_amd_ntt, msm_amd_ntt_device) --------------------------
-// Through device_call: the passes on the main stream; the host form transforms the staged copy of its input in place.
-// Domain handles are validated by membership in ctx->live_ntt, under the lock and before anything is sized by them.
-namespace {
-
-// max_passes: kNttAllPasses, or 1 .. the pass count of the plan (msm_amd_test_ntt_passes, host buffers): what the first
-// max_passes passes wrote -- short of the plan's count that is the pass buffer, copied over the staged input.
-int ntt_call(msm_amd_ctx* ctx, const msm_amd_ntt_domain* handle, bool host, int direction, int scalar_layout,
-             const void* shift32, const void* in, void* out, size_t n_vec, float* kernel_ms, uint32_t max_passes) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall c;
-  c.who = max_passes != kNttAllPasses ? "msm_amd_test_ntt_passes" : host ? "msm_amd_ntt" : "msm_amd_ntt_device";
-  const std::string& who = c.who;
-  if (kernel_ms) *kernel_ms = 0.f;
-  if (!ntt_direction_known(direction)) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": direction must be MSM_AMD_NTT_FORWARD or MSM_AMD_NTT_INVERSE");
-  if (!ntt_layout_known(scalar_layout))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": scalars in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE only");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const msm_amd_ntt_domain* dom = find_handle(ctx->live_ntt, handle);
-  if (!dom) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": not a transform domain of this ctx");
-  if (((uint64_t)n_vec >> (32 - dom->log_n)) != 0) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": n_vec * n >= 2^32");
-  const uint32_t plan_passes = ntt_plan(dom->log_n, ctx->ntt_tile_log).passes;
-  if (max_passes != kNttAllPasses && (max_passes == 0 || max_passes > plan_passes))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": passes must be 1 .. the pass count of the plan");
-  const bool stopped = max_passes < plan_passes;   // the last pass does not run
-  if (n_vec == 0) return MSM_AMD_OK;
-  if (!in || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": null pointer with n_vec > 0");
-  u256 g;
-  if (!ntt_read_shift(scalar_layout, shift32, &g)) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": the shift is 0 mod r");
-  const size_t bytes = (n_vec << dom->log_n) * 32;
-  if (!host) {
-    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
-    if ((a | b) & 15u) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": d_in and d_out must be 16-byte aligned");
-    if (a != b && a < b + bytes && b < a + bytes)
-      return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": d_out must be d_in itself or disjoint from it");
-  }
-  CallState& s = ctx->calls;
-  NttLaunch t{};
-  t.tw = dom->d_mem, t.log_n = dom->log_n, t.tile_log = ctx->ntt_tile_log;
-  t.direction = direction, t.layout = scalar_layout, t.n_vec = n_vec;
-  u256 tab[kNttPowEntries];   // the powers of the shift: host memory in either form, staged in `pow`
-  ntt_shift_setup(g, direction, dom->log_n, tab, &t.sc);
-  c.host = c.in_place = host, c.host_in = (host ? 1u : 0u) | 2u, c.kernel_ms = kernel_ms;
-  c.in[0] = in, c.in_bytes[0] = bytes;
-  c.in[1] = tab, c.in_bytes[1] = shift32 ? sizeof tab : 0, c.stage[1] = &s.pow;
-  c.out = out, c.out_bytes = bytes;
-  c.work[0] = {&s.scratch, plan_passes > 1 ? bytes : 0};
-  return device_call(ctx, c, [&](hipStream_t st, const CallIo& io) -> int {
-    t.in = io.in[0], t.out = io.out, t.scratch = s.scratch.p, t.pow_tab = shift32 ? io.in[1] : nullptr;
-    launch_ntt(st, t, max_passes);
-    if (stopped) HIP_TRY(ctx, hipMemcpyAsync(io.out, s.scratch.p, bytes, hipMemcpyDeviceToDevice, st));
-    return MSM_AMD_OK;
-  });
-}
-
-}  // namespace
-
-extern "C" {
-
-int msm_amd_ntt_domain_build(msm_amd_ctx* ctx, int root, uint32_t log_n, msm_amd_ntt_domain** out) {
-  if (!ctx || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_ntt_domain_build: null pointer");
-  *out = nullptr;
-  if (!ntt_root_known(root)) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_ntt_domain_build: root must be MSM_AMD_NTT_ROOT_ARK or MSM_AMD_NTT_ROOT_H2C");
-  if (log_n > kNttMaxLog) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_ntt_domain_build: log_n must be 0..28");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (int rc = recover_if_stalled(ctx)) return rc;
-  const u256 omega = ntt_omega(root, log_n);
-  const size_t bytes = std::max<size_t>(32, ((size_t)1 << log_n) / 2 * 32);   // n = 1: no entry, one record of room
-  if (int rc = handle_build_tail(ctx, ctx->live_ntt, bytes, "the twiddles of a transform domain", "transform domain build",
-                                 [&](void* d_tw) { launch_ntt_twiddles(ctx->stream, omega, log_n, d_tw); }, out))
-    return rc;
-  (*out)->root = root, (*out)->log_n = log_n, (*out)->omega = omega;
-  return MSM_AMD_OK;
-}
-
-int msm_amd_ntt_domain_info(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int* root, uint32_t* log_n,
-                            size_t* device_bytes, void* omega32) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const msm_amd_ntt_domain* d = find_handle(ctx->live_ntt, domain);
-  if (!d) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_ntt_domain_info: not a transform domain of this ctx");
-  if (root) *root = d->root;
-  if (log_n) *log_n = d->log_n;
-  if (device_bytes) *device_bytes = d->bytes;
-  if (omega32) std::memcpy(omega32, d->omega.v, 32);
-  return MSM_AMD_OK;
-}
-
-int msm_amd_ntt_domain_free(msm_amd_ctx* ctx, msm_amd_ntt_domain* domain) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  return handle_free(ctx, ctx->live_ntt, domain, "msm_amd_ntt_domain_free: not a transform domain of this ctx");
-}
-
-int msm_amd_ntt(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int scalar_layout, const void* shift32,
-                const void* in, void* out, size_t n_vec) {
-  return ntt_call(ctx, domain, true, direction, scalar_layout, shift32, in, out, n_vec, nullptr, kNttAllPasses);
-}
-
-int msm_amd_ntt_device(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int scalar_layout,
-                       const void* shift32, const void* d_in, void* d_out, size_t n_vec, float* kernel_ms) {
-  return ntt_call(ctx, domain, false, direction, scalar_layout, shift32, d_in, d_out, n_vec, kernel_ms, kNttAllPasses);
-}
-
-int msm_amd_test_ntt_passes(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int scalar_layout,
-                            const void* shift32, const void* in, void* out, size_t n_vec, uint32_t passes) {
-  if (passes == kNttAllPasses) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_ntt_passes: passes must be 1 .. the pass count of the plan");
-  return ntt_call(ctx, domain, true, direction, scalar_layout, shift32, in, out, n_vec, nullptr, passes);
-}
-
-int msm_amd_test_ntt_twiddles(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, size_t first, size_t count, void* out) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const msm_amd_ntt_domain* d = find_handle(ctx->live_ntt, domain);
-  if (!d) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_ntt_twiddles: not a transform domain of this ctx");
-  const size_t entries = ((size_t)1 << d->log_n) / 2;
-  if (first > entries || count > entries - first)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_ntt_twiddles: range outside the n/2 entries of the table");
-  if (count == 0) return MSM_AMD_OK;
-  if (!out) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_ntt_twiddles: null pointer with count > 0");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipMemcpyAsync(out, (const u256*)d->d_mem + first, count * 32, hipMemcpyDeviceToHost, ctx->stream));
-  return sync_stream_bounded(ctx, ctx->stream, __func__);
-}
-
-}  // extern "C"
-
-// ---- transform over G1 points (msm_amd_ntt_points, msm_amd_ntt_points_device) ----------------------------------------------
-// Through device_call, all on the main stream: the load pass consumes the input into the first packed work array before
-// anything is written (so d_out == d_in is an ordinary call), every level runs in chunks of lanes through the XYZZ chunk
-// buffer of the mul calls into the other work array, and the last normalisation writes the caller's layout to `out`.
-// INVERSE ends with the ladder by n^-1 over the last work array; log_n = 0 sends its one record through that pass with
-// the factor 1.
-namespace {
-
-// levels: kNttpAllLevels, or 0 .. log_n (msm_amd_test_ntt_points_levels, host buffers): the work array after that many
-// levels, affine records of layout_out in network order, no scaling.
-int ntt_points_call(msm_amd_ctx* ctx, const msm_amd_ntt_domain* handle, bool host, int direction, int layout_in,
-                    const void* in, int layout_out, void* out, float* kernel_ms, uint32_t levels) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall c;
-  c.who = levels != kNttpAllLevels ? "msm_amd_test_ntt_points_levels" : host ? "msm_amd_ntt_points" : "msm_amd_ntt_points_device";
-  const std::string& who = c.who;
-  if (kernel_ms) *kernel_ms = 0.f;
-  if (!ntt_direction_known(direction)) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": direction must be MSM_AMD_NTT_FORWARD or MSM_AMD_NTT_INVERSE");
-  if (!nttp_layouts_known(!host, layout_in, layout_out))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, who + (host ? ": points in a G1 host layout, output in one of the two affine host layouts (not *_PREPARED / *_TABLES)"
-                                                      : ": points in a G1 host layout or *_PREPARED, output in an affine layout or *_PREPARED (not *_TABLES)"));
-  const uint32_t prepared = host ? 0u : (uint32_t)kKindPrepared;
-  const size_t in_stride = point_record_bytes(false, layout_in, kKindHost | prepared),
-               out_stride = point_record_bytes(false, layout_out, kKindAffine | prepared);
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const msm_amd_ntt_domain* dom = find_handle(ctx->live_ntt, handle);
-  if (!dom) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": not a transform domain of this ctx");
-  const uint32_t log_n = dom->log_n;
-  if (levels != kNttpAllLevels && levels > log_n) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": levels must be 0 .. log_n");
-  if (!in || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": null pointer");
-  const size_t n = (size_t)1 << log_n;
-  if (!host) {
-    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out;
-    if (a != b && a < b + n * out_stride && b < a + n * in_stride)
-      return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": d_out must be d_in itself or disjoint from it");
-  }
-  const uint32_t run = levels == kNttpAllLevels ? log_n : levels;
-  u256 k = u256_zero();
-  const bool laddered = levels == kNttpAllLevels && direction == kNttInverse && nttp_n_inv(log_n, &k);
-  const bool last_pass = laddered || run == 0;   // the records go through the uniform-scalar pass on their way out
-  const uint32_t lanes = (uint32_t)(n / 2), chunk_lanes = nttp_chunk_lanes(log_n, ctx->mul_chunk);
-  const size_t chunk = std::min(n, ctx->mul_chunk);   // records per chunk of the last pass
-  CallState& s = ctx->calls;
-  c.host = host, c.host_in = host ? 1u : 0u, c.kernel_ms = kernel_ms;
-  c.in[0] = in, c.in_bytes[0] = n * in_stride;
-  c.out = out, c.out_bytes = n * out_stride;
-  c.work[0] = {&s.xyzz, std::max<size_t>(2 * (size_t)chunk_lanes, chunk) * mul_xyzz_bytes(false)};
-  c.work[1] = {&s.scratch, 2 * n * sizeof(AffPacked)};
-  return device_call(ctx, c, [&](hipStream_t st, const CallIo& io) -> int {
-    AffPacked* work[2] = {(AffPacked*)s.scratch.p, (AffPacked*)s.scratch.p + n};
-    void* xyzz = s.xyzz.p;
-    launch_nttp_load(st, layout_in, io.in[0], log_n, work[0]);
-    int cur = 0;
-    for (uint32_t level = 1; level <= run; ++level) {
-      const bool to_out = level == run && !last_pass;
-      for (uint32_t lane0 = 0; lane0 < lanes; lane0 += chunk_lanes) {
-        const uint32_t m = std::min(chunk_lanes, lanes - lane0);
-        launch_nttp_level(st, work[cur], dom->d_mem, log_n, level, direction, lane0, m, xyzz);
-        launch_nttp_normalise(st, xyzz, log_n, level, lane0, m, to_out ? layout_out : kLayoutPrepared,
-                              to_out ? io.out : (void*)work[cur ^ 1]);
-      }
-      cur ^= 1;
-    }
-    if (last_pass)
-      for (size_t first = 0; first < n; first += chunk) {
-        const uint32_t m = (uint32_t)std::min(chunk, n - first);
-        launch_nttp_scale(st, work[cur], (uint32_t)first, m, laddered, k, xyzz);
-        launch_mul_normalise(st, false, xyzz, m, layout_out, (uint8_t*)io.out + first * out_stride);
-      }
-    return MSM_AMD_OK;
-  });
-}
-
-}  // namespace
-
-extern "C" {
-
-int msm_amd_ntt_points(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int point_layout_in,
-                       const void* in, int point_layout_out, void* out) {
-  return ntt_points_call(ctx, domain, true, direction, point_layout_in, in, point_layout_out, out, nullptr, kNttpAllLevels);
-}
-
-int msm_amd_ntt_points_device(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int point_layout_in,
-                              const void* d_in, int point_layout_out, void* d_out, float* kernel_ms) {
-  return ntt_points_call(ctx, domain, false, direction, point_layout_in, d_in, point_layout_out, d_out, kernel_ms,
-                         kNttpAllLevels);
-}
-
-int msm_amd_test_ntt_points_levels(msm_amd_ctx* ctx, const msm_amd_ntt_domain* domain, int direction, int point_layout_in,
-                                   const void* in, uint32_t levels, int point_layout_out, void* out) {
-  if (levels == kNttpAllLevels) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_ntt_points_levels: levels must be 0 .. log_n");
-  return ntt_points_call(ctx, domain, true, direction, point_layout_in, in, point_layout_out, out, nullptr, levels);
-}
-
-}  // extern "C"
-
-// ---- vectors over Fr (msm_amd_fr_map*, msm_amd_fr_batch_inverse*, msm_amd_fr_prefix_product*, msm_amd_fr_poly_*,
-// msm_amd_fr_lincomb*) ------------------------------------------------------------------------------------------------------
-// Through device_call: the host forms compute over the staged copy of their first operand.  The inversion has two spans
-// of kernels: T and the zero count come back as the call's 64-byte record, the host inverts T.  The polynomial calls
-// read p_v(z) back through the call's page-locked values buffer, in the one bounded wait behind their kernels.
-namespace {
-
-int fr_map_call(msm_amd_ctx* ctx, bool host, int op, int scalar_layout, const void* k32, const void* a, const void* b,
-                const void* c, size_t n, void* out, float* kernel_ms) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall d;
-  d.who = host ? "msm_amd_fr_map" : "msm_amd_fr_map_device";
-  if (kernel_ms) *kernel_ms = 0.f;
-  if (const char* why = fr_map_check(op, scalar_layout, k32, a, b, c, n, out, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
-  if (n == 0) return MSM_AMD_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const unsigned reads = fr_op_reads(op);
-  const void* operand[3] = {a, b, c};
-  d.host = d.in_place = host, d.host_in = host ? reads : 0u, d.kernel_ms = kernel_ms;
-  for (int i = 0; i < 3; ++i) d.in[i] = operand[i], d.in_bytes[i] = (reads >> i & 1) ? n * 32 : 0;
-  d.out = out, d.out_bytes = n * 32;
-  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
-    launch_fr_map(st, op, scalar_layout, fr_read_k(op, scalar_layout, k32), io.in[0], io.in[1], io.in[2], n, io.out);
-    return MSM_AMD_OK;
-  });
-}
-
-int fr_prefix_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int mode, const void* in, size_t n, size_t n_vec, void* out,
-                   float* kernel_ms) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall d;
-  d.who = host ? "msm_amd_fr_prefix_product" : "msm_amd_fr_prefix_product_device";
-  if (kernel_ms) *kernel_ms = 0.f;
-  if (!fr_mode_known(mode))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": mode must be MSM_AMD_FR_PREFIX_INCLUSIVE or MSM_AMD_FR_PREFIX_EXCLUSIVE");
-  if (const char* why = fr_unary_check(scalar_layout, in, n, n_vec, out, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
-  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  CallState& s = ctx->calls;
-  FrScanLaunch c{};
-  c.n = n, c.n_vec = n_vec, c.tile_log = ctx->fr_tile_log, c.layout = scalar_layout, c.mode = mode;
-  d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
-  d.in[0] = in, d.in_bytes[0] = n * n_vec * 32;
-  d.out = out, d.out_bytes = n * n_vec * 32;
-  d.work[0] = {&s.work, std::max<size_t>(32, fr_scan_plan(n, n_vec, c.tile_log).records * 32)};
-  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
-    c.in = io.in[0], c.out = io.out, c.work = s.work.p;
-    launch_fr_scan(st, c);
-    return MSM_AMD_OK;
-  });
-}
-
-int fr_inverse_call(msm_amd_ctx* ctx, bool host, int scalar_layout, const void* in, size_t n, void* out, uint64_t* n_zero,
-                    float* kernel_ms) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall d;
-  d.who = host ? "msm_amd_fr_batch_inverse" : "msm_amd_fr_batch_inverse_device";
-  if (kernel_ms) *kernel_ms = 0.f;
-  if (n_zero) *n_zero = 0;
-  if (const char* why = fr_unary_check(scalar_layout, in, n, 1, out, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
-  if (n == 0) return MSM_AMD_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  CallState& s = ctx->calls;
-  const uint32_t tile_log = ctx->fr_tile_log;
-  const FrInvPlan plan = fr_inv_plan(n, tile_log);
-  d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
-  d.in[0] = in, d.in_bytes[0] = n * 32;
-  d.out = out, d.out_bytes = n * 32;
-  d.work[0] = {&s.work, plan.records * 32};
-  uint64_t zeros = 0;
-  u256 t_inv;
-  const int rc = device_call(
-      ctx, d,
-      [&](hipStream_t st, CallIo& io) {   // span 1: the products; T and the zero count come back
-        launch_fr_inv_products(st, scalar_layout, io.in[0], n, tile_log, s.work.p);
-        io.record = fr_inv_tail(s.work.p, plan);
-        return MSM_AMD_OK;
-      },
-      [&](const uint8_t* tail, float) {
-        u256 total;
-        std::memcpy(total.v, tail, 32);
-        std::memcpy(&zeros, tail + 32, 8);
-        t_inv = ntt_fr_inv(total);   // zeros were read as one: T != 0
-      },
-      [&](hipStream_t st, const CallIo& io) {   // span 2: every record's inverse
-        launch_fr_inv_apply(st, scalar_layout, io.in[0], n, tile_log, s.work.p, t_inv, io.out);
-        return MSM_AMD_OK;
-      });
-  if (rc == MSM_AMD_OK && n_zero) *n_zero = zeros;
-  return rc;
-}
-
-// p_v(z) come back as raw records through CallState::h_values and leave in the caller's layout
-void fr_values_out(const CallState& s, int scalar_layout, size_t n_vec, void* out) {
-  for (size_t v = 0; v < n_vec; ++v) {
-    u256 x;
-    std::memcpy(x.v, s.h_values + v * 32, 32);
-    uint32_t rec[8];
-    ntt_store(scalar_layout, x, rec);
-    std::memcpy((uint8_t*)out + v * 32, rec, 32);
-  }
-}
-
-// msm_amd_fr_poly_eval* (divide false: out is unused, values required) and msm_amd_fr_poly_div_linear*
-int fr_poly_call(msm_amd_ctx* ctx, bool host, bool divide, int scalar_layout, const void* z32, const void* in, size_t n,
-                 size_t n_vec, void* out, void* values, float* kernel_ms) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall d;
-  d.who = std::string(divide ? "msm_amd_fr_poly_div_linear" : "msm_amd_fr_poly_eval") + (host ? "" : "_device");
-  if (kernel_ms) *kernel_ms = 0.f;
-  if (const char* why = fr_poly_check(scalar_layout, z32, in, n, n_vec, out, values, divide, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
-  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  CallState& s = ctx->calls;
-  FrPolyLaunch c{};
-  c.n = n, c.n_vec = n_vec, c.tile_log = ctx->fr_tile_log, c.layout = scalar_layout, c.divide = divide;
-  c.z = fr_read_record(scalar_layout, z32);
-  const FrScanPlan plan = fr_scan_plan(n, n_vec, c.tile_log);
-  d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
-  d.in[0] = in, d.in_bytes[0] = n * n_vec * 32;
-  d.out = out, d.out_bytes = divide ? n * n_vec * 32 : 0;
-  d.work[0] = {&s.work, fr_poly_values(plan) + n_vec * 32};
-  d.values_bytes = values ? n_vec * 32 : 0;
-  const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
-    c.in = io.in[0], c.out = io.out, c.work = s.work.p;
-    launch_fr_poly(st, c);
-    io.values = (const uint8_t*)s.work.p + fr_poly_values(plan);
-    return MSM_AMD_OK;
-  });
-  if (rc == MSM_AMD_OK && values) fr_values_out(s, scalar_layout, n_vec, values);
-  return rc;
-}
-
-int fr_lincomb_call(msm_amd_ctx* ctx, bool host, int scalar_layout, const void* k32, const void* a, size_t n, size_t n_vec,
-                    void* out, float* kernel_ms) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall d;
-  d.who = host ? "msm_amd_fr_lincomb" : "msm_amd_fr_lincomb_device";
-  if (kernel_ms) *kernel_ms = 0.f;
-  if (const char* why = fr_lincomb_check(scalar_layout, k32, a, n, n_vec, out, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
-  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  // the host form folds into the first vector of the staged copy
-  d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
-  d.in[0] = a, d.in_bytes[0] = n * n_vec * 32;
-  d.out = out, d.out_bytes = n * 32;
-  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
-    launch_fr_lincomb(st, scalar_layout, fr_read_record(scalar_layout, k32), io.in[0], n, n_vec, io.out);
-    return MSM_AMD_OK;
-  });
-}
-
-}  // namespace
-
-extern "C" {
-
-int msm_amd_fr_poly_eval(msm_amd_ctx* ctx, int scalar_layout, const void* z32, const void* coeffs, size_t n, size_t n_vec,
-                         void* y_out) {
-  return fr_poly_call(ctx, true, false, scalar_layout, z32, coeffs, n, n_vec, nullptr, y_out, nullptr);
-}
-
-int msm_amd_fr_poly_eval_device(msm_amd_ctx* ctx, int scalar_layout, const void* z32, const void* d_coeffs, size_t n,
-                                size_t n_vec, void* y_out, float* kernel_ms) {
-  return fr_poly_call(ctx, false, false, scalar_layout, z32, d_coeffs, n, n_vec, nullptr, y_out, kernel_ms);
-}
-
-int msm_amd_fr_poly_div_linear(msm_amd_ctx* ctx, int scalar_layout, const void* z32, const void* in, size_t n, size_t n_vec,
-                               void* out, void* rem_out) {
-  return fr_poly_call(ctx, true, true, scalar_layout, z32, in, n, n_vec, out, rem_out, nullptr);
-}
-
-int msm_amd_fr_poly_div_linear_device(msm_amd_ctx* ctx, int scalar_layout, const void* z32, const void* d_in, size_t n,
-                                      size_t n_vec, void* d_out, void* rem_out, float* kernel_ms) {
-  return fr_poly_call(ctx, false, true, scalar_layout, z32, d_in, n, n_vec, d_out, rem_out, kernel_ms);
-}
-
-int msm_amd_fr_lincomb(msm_amd_ctx* ctx, int scalar_layout, const void* k32, const void* a, size_t n, size_t n_vec, void* out) {
-  return fr_lincomb_call(ctx, true, scalar_layout, k32, a, n, n_vec, out, nullptr);
-}
-
-int msm_amd_fr_lincomb_device(msm_amd_ctx* ctx, int scalar_layout, const void* k32, const void* d_a, size_t n, size_t n_vec,
-                              void* d_out, float* kernel_ms) {
-  return fr_lincomb_call(ctx, false, scalar_layout, k32, d_a, n, n_vec, d_out, kernel_ms);
-}
-
-int msm_amd_fr_map(msm_amd_ctx* ctx, int op, int scalar_layout, const void* k32, const void* a, const void* b, const void* c,
-                   size_t n, void* out) {
-  return fr_map_call(ctx, true, op, scalar_layout, k32, a, b, c, n, out, nullptr);
-}
-
-int msm_amd_fr_map_device(msm_amd_ctx* ctx, int op, int scalar_layout, const void* k32, const void* d_a, const void* d_b,
-                          const void* d_c, size_t n, void* d_out, float* kernel_ms) {
-  return fr_map_call(ctx, false, op, scalar_layout, k32, d_a, d_b, d_c, n, d_out, kernel_ms);
-}
-
-int msm_amd_fr_batch_inverse(msm_amd_ctx* ctx, int scalar_layout, const void* in, size_t n, void* out, uint64_t* n_zero) {
-  return fr_inverse_call(ctx, true, scalar_layout, in, n, out, n_zero, nullptr);
-}
-
-int msm_amd_fr_batch_inverse_device(msm_amd_ctx* ctx, int scalar_layout, const void* d_in, size_t n, void* d_out,
-                                    uint64_t* n_zero, float* kernel_ms) {
-  return fr_inverse_call(ctx, false, scalar_layout, d_in, n, d_out, n_zero, kernel_ms);
-}
-
-int msm_amd_fr_prefix_product(msm_amd_ctx* ctx, int scalar_layout, int mode, const void* in, size_t n, size_t n_vec,
-                              void* out) {
-  return fr_prefix_call(ctx, true, scalar_layout, mode, in, n, n_vec, out, nullptr);
-}
-
-int msm_amd_fr_prefix_product_device(msm_amd_ctx* ctx, int scalar_layout, int mode, const void* d_in, size_t n, size_t n_vec,
-                                     void* d_out, float* kernel_ms) {
-  return fr_prefix_call(ctx, false, scalar_layout, mode, d_in, n, n_vec, d_out, kernel_ms);
-}
-
-}  // extern "C"
-
-// ---- sparse matrix times vector over Fr (msm_amd_fr_matrix_*, msm_amd_fr_matvec*) ------------------------------------------
-// The build checks every column on the host before anything is uploaded, so that no index of the image can leave x, the
-// dictionary or the partials.  A product is a device_call: x through the staging in the host form, the partial sums of the
-// split rows in CallState::work, the launches of launch_fr_matvec on the main stream.
-namespace {
-
-int fr_matvec_call(msm_amd_ctx* ctx, const msm_amd_fr_matrix* handle, bool host, int scalar_layout, const void* x, void* y,
-                   float* kernel_ms) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall d;
-  d.who = host ? "msm_amd_fr_matvec" : "msm_amd_fr_matvec_device";
-  if (kernel_ms) *kernel_ms = 0.f;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const msm_amd_fr_matrix* m = find_handle(ctx->live_fr_mat, handle);
-  if (!m) return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": not a matrix handle of this ctx");
-  if (const char* why = fr_matvec_check(scalar_layout, m->n_rows, m->n_cols, x, y, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
-  if (!host) {
-    const uintptr_t lo = (uintptr_t)m->d_mem, hi = lo + m->bytes, a = (uintptr_t)x, b = (uintptr_t)y;
-    if ((a < hi && lo < a + m->n_cols * 32) || (b < hi && lo < b + m->n_rows * 32))
-      return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": d_x and d_y must not overlap the matrix");
-  }
-  CallState& s = ctx->calls;
-  FrMatLaunch c{};
-  c.image = m->d_mem, c.at = m->at, c.plan = m->plan, c.n_rows = m->n_rows, c.long_rows = m->long_rows, c.layout = scalar_layout;
-  c.signs = ctx->fr_mat_signs;
-  d.host = host, d.host_in = host, d.kernel_ms = kernel_ms;
-  d.in[0] = x, d.in_bytes[0] = m->n_cols * 32;
-  d.out = y, d.out_bytes = m->n_rows * 32;
-  d.work[0] = {&s.work, std::max<size_t>(32, m->plan.partials * 32)};
-  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
-    c.x = io.in[0], c.y = io.out, c.work = s.work.p;
-    launch_fr_matvec(st, c);
-    return MSM_AMD_OK;
-  });
-}
-
-}  // namespace
-
-extern "C" {
-
-int msm_amd_fr_matrix_build(msm_amd_ctx* ctx, int scalar_layout, size_t n_rows, size_t n_cols, const uint64_t* row_ptr,
-                            const uint32_t* col_idx, const void* values, msm_amd_fr_matrix** out) {
-  if (!ctx || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_fr_matrix_build: null pointer");
-  *out = nullptr;
-  if (const char* why = fr_matrix_check(scalar_layout, n_rows, n_cols, row_ptr, col_idx, values))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, std::string("msm_amd_fr_matrix_build: ") + why);
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (int rc = recover_if_stalled(ctx)) return rc;
-  FrMatPlan plan;
-  FrMatImage at;
-  uint64_t n_distinct = 0, dict_records = 0;
-  std::vector<uint8_t> image;
-  fr_mat_build_image(scalar_layout, n_rows, row_ptr, col_idx, values, ctx->fr_mat_long, ctx->fr_mat_seg_log, &plan, &at,
-                     &n_distinct, &dict_records, &image);
-  int up = MSM_AMD_OK;
-  if (int rc = handle_build_tail(ctx, ctx->live_fr_mat, at.bytes, "a sparse matrix", "matrix build",
-                                 [&](void* d_mem) { up = staged_upload(ctx, d_mem, image.data(), image.size(), ctx->stream); },
-                                 out))
-    return rc;
-  if (up) {   // the upload did not go through: nothing may read the allocation
-    msm_amd_fr_matrix* h = *out;
-    *out = nullptr;
-    const std::string why = ctx->last_error;
-    handle_free(ctx, ctx->live_fr_mat, h, "");
-    return fail(ctx, up, "msm_amd_fr_matrix_build: " + why);
-  }
-  msm_amd_fr_matrix* h = *out;
-  h->n_rows = n_rows, h->n_cols = n_cols, h->nnz = row_ptr[n_rows], h->n_distinct = n_distinct;
-  h->long_rows = ctx->fr_mat_long, h->plan = plan, h->at = at;
-  return MSM_AMD_OK;
-}
-
-int msm_amd_fr_matrix_info(msm_amd_ctx* ctx, const msm_amd_fr_matrix* matrix, size_t* n_rows, size_t* n_cols, size_t* nnz,
-                           size_t* n_distinct, size_t* device_bytes) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const msm_amd_fr_matrix* m = find_handle(ctx->live_fr_mat, matrix);
-  if (!m) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_fr_matrix_info: not a matrix handle of this ctx");
-  if (n_rows) *n_rows = m->n_rows;
-  if (n_cols) *n_cols = m->n_cols;
-  if (nnz) *nnz = m->nnz;
-  if (n_distinct) *n_distinct = m->n_distinct;
-  if (device_bytes) *device_bytes = m->bytes;
-  return MSM_AMD_OK;
-}
-
-int msm_amd_fr_matrix_free(msm_amd_ctx* ctx, msm_amd_fr_matrix* matrix) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  return handle_free(ctx, ctx->live_fr_mat, matrix, "msm_amd_fr_matrix_free: not a matrix handle of this ctx");
-}
-
-int msm_amd_fr_matvec(msm_amd_ctx* ctx, const msm_amd_fr_matrix* matrix, int scalar_layout, const void* x, void* y) {
-  return fr_matvec_call(ctx, matrix, true, scalar_layout, x, y, nullptr);
-}
-
-int msm_amd_fr_matvec_device(msm_amd_ctx* ctx, const msm_amd_fr_matrix* matrix, int scalar_layout, const void* d_x, void* d_y,
-                             float* kernel_ms) {
-  return fr_matvec_call(ctx, matrix, false, scalar_layout, d_x, d_y, kernel_ms);
-}
-
-}  // extern "C"
-
-// ---- multilinear tables over Fr and sumcheck rounds (msm_amd_fr_mle_bind*, msm_amd_fr_mle_eval*, msm_amd_fr_eq_table*,
-// msm_amd_fr_sumcheck_round*) ------------------------------------------------------------------------------------------------
-// Through device_call.  Challenges and points are read once on the host and reach the kernels by value.  The values of an
-// evaluation or a round come back through CallState::h_values.  The host form of a bind copies back the records the call
-// defines and no byte between the tables: one strided copy behind the kernels.
-namespace {
-
-int fr_mle_bind_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int order, const void* r32, size_t n_bind, const void* in,
-                     size_t n, size_t n_vec, size_t stride, void* out, float* kernel_ms) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall d;
-  d.who = host ? "msm_amd_fr_mle_bind" : "msm_amd_fr_mle_bind_device";
-  if (kernel_ms) *kernel_ms = 0.f;
-  if (const char* why = fr_mle_bind_check(scalar_layout, order, r32, n_bind, in, n, n_vec, stride, out, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
-  if (n_vec == 0) return MSM_AMD_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  CallState& s = ctx->calls;
-  FrMleBindLaunch c{};
-  c.n = n, c.n_vec = n_vec, c.stride = stride, c.n_bind = (uint32_t)n_bind, c.layout = scalar_layout, c.order = order;
-  for (size_t k = 0; k < n_bind; ++k) c.r[k] = fr_read_record(scalar_layout, (const uint8_t*)r32 + k * 32);
-  const FrMleBindPlan plan = fr_mle_bind_plan(order, n, n_vec, c.n_bind);
-  const size_t span = ((n_vec - 1) * stride + n) * 32, left = (n >> n_bind) * 32;
-  // the host form works from the staged input into the staged output; the strided copy below brings the result back
-  d.host_in = host, d.kernel_ms = kernel_ms;
-  d.in[0] = in, d.in_bytes[0] = span;
-  d.out = out;
-  d.work[0] = {&s.work, std::max<size_t>(32, plan.work_records * 32)};
-  if (host) d.work[1] = {&s.out, span};
-  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) -> int {
-    c.in = io.in[0], c.out = host ? s.out.p : io.out, c.work = s.work.p;
-    launch_fr_mle_bind(st, c);
-    if (host)
-      HIP_TRY(ctx, hipMemcpy2DAsync(out, stride * 32, s.out.p, stride * 32, left, n_vec, hipMemcpyDeviceToHost, st));
-    return MSM_AMD_OK;
-  });
-}
-
-int fr_mle_eval_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int order, const void* point32, const void* in, size_t n,
-                     size_t n_vec, size_t stride, void* y_out, float* kernel_ms) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall d;
-  d.who = host ? "msm_amd_fr_mle_eval" : "msm_amd_fr_mle_eval_device";
-  if (kernel_ms) *kernel_ms = 0.f;
-  if (const char* why = fr_mle_eval_check(scalar_layout, order, point32, in, n, n_vec, stride, y_out, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
-  if (n_vec == 0) return MSM_AMD_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  CallState& s = ctx->calls;
-  FrMleEvalLaunch c{};
-  c.n = n, c.n_vec = n_vec, c.stride = stride, c.tile_log = ctx->fr_tile_log, c.layout = scalar_layout;
-  const uint32_t m = fr_mle_log2(n);
-  // the kernels fold x_j at r[j]: HIGH binds x_(m-1-s) at point[s]
-  for (uint32_t k = 0; k < m; ++k)
-    c.r[order == kFrMleHigh ? m - 1 - k : k] = fr_read_record(scalar_layout, (const uint8_t*)point32 + (size_t)k * 32);
-  const FrScanPlan plan = fr_scan_plan(n, n_vec, c.tile_log);
-  d.host_in = host, d.kernel_ms = kernel_ms;
-  d.in[0] = in, d.in_bytes[0] = ((n_vec - 1) * stride + n) * 32;
-  d.work[0] = {&s.work, fr_poly_values(plan) + n_vec * 32};
-  d.values_bytes = n_vec * 32;
-  const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
-    c.in = io.in[0], c.work = s.work.p;
-    launch_fr_mle_eval(st, c);
-    io.values = (const uint8_t*)s.work.p + fr_poly_values(plan);
-    return MSM_AMD_OK;
-  });
-  if (rc == MSM_AMD_OK) fr_values_out(s, scalar_layout, n_vec, y_out);
-  return rc;
-}
-
-int fr_eq_table_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int order, const void* point32, size_t m, void* out,
-                     float* kernel_ms) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall d;
-  d.who = host ? "msm_amd_fr_eq_table" : "msm_amd_fr_eq_table_device";
-  if (kernel_ms) *kernel_ms = 0.f;
-  if (const char* why = fr_eq_table_check(scalar_layout, order, point32, m, out, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  u256 by_bit[kFrMleMaxVars];
-  for (size_t k = 0; k < m; ++k)
-    by_bit[order == kFrMleHigh ? m - 1 - k : k] = fr_read_record(scalar_layout, (const uint8_t*)point32 + k * 32);
-  d.host = host, d.kernel_ms = kernel_ms;
-  d.out = out, d.out_bytes = ((size_t)1 << m) * 32;
-  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
-    launch_fr_eq_table(st, scalar_layout, by_bit, (uint32_t)m, io.out);
-    return MSM_AMD_OK;
-  });
-}
-
-int fr_sumcheck_round_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int order, int form, const void* in, size_t n,
-                           size_t n_vec, size_t stride, void* g_out, float* kernel_ms) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall d;
-  d.who = host ? "msm_amd_fr_sumcheck_round" : "msm_amd_fr_sumcheck_round_device";
-  if (kernel_ms) *kernel_ms = 0.f;
-  if (const char* why = fr_sumcheck_check(scalar_layout, order, form, in, n, n_vec, stride, g_out, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
-  if (n_vec == 0) return MSM_AMD_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  CallState& s = ctx->calls;
-  FrMleRoundLaunch c{};
-  c.n = n, c.n_vec = n_vec, c.stride = stride, c.chunk_log = ctx->fr_mle_chunk_log;
-  c.layout = scalar_layout, c.order = order, c.form = form;
-  const uint32_t values = fr_mle_degree(form, n_vec) + 1;
-  const FrMleRoundPlan plan = fr_mle_round_plan(n, values, c.chunk_log);
-  d.host_in = host, d.kernel_ms = kernel_ms;
-  d.in[0] = in, d.in_bytes[0] = ((n_vec - 1) * stride + n) * 32;
-  d.work[0] = {&s.work, plan.records * 32};
-  d.values_bytes = values * 32;
-  const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
-    c.in = io.in[0], c.work = s.work.p;
-    launch_fr_sumcheck_round(st, c);
-    io.values = (const uint8_t*)s.work.p + plan.values_off * 32;
-    return MSM_AMD_OK;
-  });
-  if (rc == MSM_AMD_OK) fr_values_out(s, scalar_layout, values, g_out);
-  return rc;
-}
-
-}  // namespace
-
-extern "C" {
-
-int msm_amd_fr_mle_bind(msm_amd_ctx* ctx, int scalar_layout, int order, const void* r, size_t n_bind, const void* in, size_t n,
-                        size_t n_vec, size_t stride, void* out) {
-  return fr_mle_bind_call(ctx, true, scalar_layout, order, r, n_bind, in, n, n_vec, stride, out, nullptr);
-}
-
-int msm_amd_fr_mle_bind_device(msm_amd_ctx* ctx, int scalar_layout, int order, const void* r, size_t n_bind, const void* d_in,
-                               size_t n, size_t n_vec, size_t stride, void* d_out, float* kernel_ms) {
-  return fr_mle_bind_call(ctx, false, scalar_layout, order, r, n_bind, d_in, n, n_vec, stride, d_out, kernel_ms);
-}
-
-int msm_amd_fr_mle_eval(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point, const void* in, size_t n,
-                        size_t n_vec, size_t stride, void* y_out) {
-  return fr_mle_eval_call(ctx, true, scalar_layout, order, point, in, n, n_vec, stride, y_out, nullptr);
-}
-
-int msm_amd_fr_mle_eval_device(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point, const void* d_in, size_t n,
-                               size_t n_vec, size_t stride, void* y_out, float* kernel_ms) {
-  return fr_mle_eval_call(ctx, false, scalar_layout, order, point, d_in, n, n_vec, stride, y_out, kernel_ms);
-}
-
-int msm_amd_fr_eq_table(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point, size_t m, void* out) {
-  return fr_eq_table_call(ctx, true, scalar_layout, order, point, m, out, nullptr);
-}
-
-int msm_amd_fr_eq_table_device(msm_amd_ctx* ctx, int scalar_layout, int order, const void* point, size_t m, void* d_out,
-                               float* kernel_ms) {
-  return fr_eq_table_call(ctx, false, scalar_layout, order, point, m, d_out, kernel_ms);
-}
-
-int msm_amd_fr_sumcheck_round(msm_amd_ctx* ctx, int scalar_layout, int order, int form, const void* in, size_t n, size_t n_vec,
-                              size_t stride, void* g_out) {
-  return fr_sumcheck_round_call(ctx, true, scalar_layout, order, form, in, n, n_vec, stride, g_out, nullptr);
-}
-
-int msm_amd_fr_sumcheck_round_device(msm_amd_ctx* ctx, int scalar_layout, int order, int form, const void* d_in, size_t n,
-                                     size_t n_vec, size_t stride, void* g_out, float* kernel_ms) {
-  return fr_sumcheck_round_call(ctx, false, scalar_layout, order, form, d_in, n, n_vec, stride, g_out, kernel_ms);
-}
-
-}  // extern "C"
-
-// ---- width scan (msm_amd_scalar_width*): through device_call; the 32-byte result comes back as the call's values ----------
-namespace {
-
-int scalar_width_call(msm_amd_ctx* ctx, bool host, int scalar_layout, const void* scalars, size_t n, int sign, uint32_t* bits,
-                      uint64_t* stats) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall d;
-  d.who = host ? "msm_amd_scalar_width" : "msm_amd_scalar_width_device";
-  if (const char* why = scalar_width_check(scalar_layout, scalars, n, sign, bits))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
-  WidthStats r;
-  if (n != 0) {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    CallState& s = ctx->calls;
-    d.host_in = host ? 1u : 0u;
-    d.in[0] = scalars, d.in_bytes[0] = n * 32;
-    d.work[0] = {&s.work, scalar_width_work_bytes(n)};
-    d.values_bytes = 32;
-    const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
-      launch_scalar_width(st, (const u256*)io.in[0], (uint32_t)n, scalar_layout == MSM_AMD_SCALAR_MONT_LE, (uint32_t)sign,
-                          s.work.p);
-      io.values = s.work.p;
-      return MSM_AMD_OK;
-    });
-    if (rc) return rc;
-    uint64_t v[4];
-    std::memcpy(v, s.h_values, 32);
-    r.bits = (uint32_t)(v[0] >> 32), r.widest = (uint32_t)~(uint32_t)v[0], r.zeros = v[1], r.negatives = v[2];
-  }
-  scalar_width_out(r, bits, stats);
-  return MSM_AMD_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int msm_amd_scalar_width(msm_amd_ctx* ctx, int scalar_layout, const void* scalars, size_t n, int sign, uint32_t* bits,
-                         uint64_t* stats) {
-  return scalar_width_call(ctx, true, scalar_layout, scalars, n, sign, bits, stats);
-}
-int msm_amd_scalar_width_device(msm_amd_ctx* ctx, int scalar_layout, const void* d_scalars, size_t n, int sign, uint32_t* bits,
-                                uint64_t* stats) {
-  return scalar_width_call(ctx, false, scalar_layout, d_scalars, n, sign, bits, stats);
-}
-
-}  // extern "C"
-
-// ---- Poseidon over Fr (msm_amd_poseidon_params_*, msm_amd_poseidon_permute*, _hash*, _merkle_build*, _merkle_paths*) ---------
-// Through device_call.  A parameter handle is validated by membership in ctx->live_poseidon, under the lock and before
-// anything is sized by it; the tag is read once on the host and reaches the kernels by value; the root of a tree comes back
-// through CallState::h_values in the call's one bounded wait; the leaf indices of a paths call are checked on the host and
-// go through the staging in both forms.
-namespace {
-
-const char* const kNotPoseidon = ": not a Poseidon parameter handle of this ctx";
-
-PoseidonLaunch poseidon_launch(const msm_amd_poseidon_params* p, int scalar_layout, const void* tag32) {
-  PoseidonLaunch c{};
-  c.image = p->d_mem, c.t = p->t, c.r_f = p->r_f, c.r_p = p->r_p, c.layout = scalar_layout;
-  c.tag = tag32 ? fr_read_record(scalar_layout, tag32) : u256_zero();
-  return c;
-}
-
-// device memory a call writes must not be the constants
-bool poseidon_clear_of(const msm_amd_poseidon_params* p, const void* out, size_t bytes) {
-  const uintptr_t lo = (uintptr_t)p->d_mem, hi = lo + p->bytes, a = (uintptr_t)out;
-  return !(a < hi && lo < a + bytes);
-}
-
-int poseidon_call(msm_amd_ctx* ctx, const msm_amd_poseidon_params* handle, int kind, bool host, int scalar_layout,
-                  const void* tag32, const void* in, size_t n, void* out, float* kernel_ms) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall d;
-  d.who = std::string(kind == kPoseidonHash ? "msm_amd_poseidon_hash" : "msm_amd_poseidon_permute") + (host ? "" : "_device");
-  if (kernel_ms) *kernel_ms = 0.f;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const msm_amd_poseidon_params* p = find_handle(ctx->live_poseidon, handle);
-  if (!p) return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + kNotPoseidon);
-  if (const char* why = poseidon_call_check(kind, p->t, scalar_layout, in, n, out, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
-  if (n == 0) return MSM_AMD_OK;
-  const size_t in_bytes = n * (kind == kPoseidonHash ? p->t - 1 : p->t) * 32, out_bytes = n * (kind == kPoseidonHash ? 1 : p->t) * 32;
-  if (!host && !poseidon_clear_of(p, out, out_bytes))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": the output must not overlap the parameters");
-  const PoseidonLaunch c = poseidon_launch(p, scalar_layout, tag32);
-  // the host form of a permutation works in place on the staged copy of its input
-  d.host = host, d.host_in = host, d.in_place = host && kind == kPoseidonPermute, d.kernel_ms = kernel_ms;
-  d.in[0] = in, d.in_bytes[0] = in_bytes;
-  d.out = out, d.out_bytes = out_bytes;
-  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
-    launch_poseidon(st, c, kind, io.in[0], n, io.out);
-    return MSM_AMD_OK;
-  });
-}
-
-int poseidon_merkle_build_call(msm_amd_ctx* ctx, const msm_amd_poseidon_params* handle, bool host, int scalar_layout,
-                               const void* tag32, const void* leaves, size_t n_leaves, void* tree, void* root32, float* kernel_ms) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall d;
-  d.who = host ? "msm_amd_poseidon_merkle_build" : "msm_amd_poseidon_merkle_build_device";
-  if (kernel_ms) *kernel_ms = 0.f;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const msm_amd_poseidon_params* p = find_handle(ctx->live_poseidon, handle);
-  if (!p) return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + kNotPoseidon);
-  if (const char* why = poseidon_merkle_check(p->t, scalar_layout, leaves, n_leaves, tree, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
-  const PoseidonTreePlan plan = poseidon_tree_plan(n_leaves, p->t - 1, ctx->poseidon_top_log);
-  if (!host && !poseidon_clear_of(p, tree, plan.nodes * 32))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": the tree must not overlap the parameters");
-  const PoseidonLaunch c = poseidon_launch(p, scalar_layout, tag32);
-  CallState& s = ctx->calls;
-  d.host = host, d.host_in = host, d.kernel_ms = kernel_ms;
-  d.in[0] = leaves, d.in_bytes[0] = n_leaves * 32;
-  d.out = tree, d.out_bytes = plan.nodes * 32;
-  d.values_bytes = root32 ? 32 : 0;
-  const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
-    launch_poseidon_tree(st, c, io.in[0], n_leaves, ctx->poseidon_top_log, io.out);
-    io.values = (const uint8_t*)io.out + (plan.nodes - 1) * 32;
-    return MSM_AMD_OK;
-  });
-  if (rc == MSM_AMD_OK && root32) std::memcpy(root32, s.h_values, 32);   // a node: already in the call's layout
-  return rc;
-}
-
-int poseidon_merkle_paths_call(msm_amd_ctx* ctx, const msm_amd_poseidon_params* handle, bool host, int scalar_layout,
-                               const void* leaves, size_t n_leaves, const void* tree, const uint64_t* idx, size_t n_idx, void* out,
-                               float* kernel_ms) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  DeviceCall d;
-  d.who = host ? "msm_amd_poseidon_merkle_paths" : "msm_amd_poseidon_merkle_paths_device";
-  if (kernel_ms) *kernel_ms = 0.f;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const msm_amd_poseidon_params* p = find_handle(ctx->live_poseidon, handle);
-  if (!p) return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + kNotPoseidon);
-  if (const char* why = poseidon_paths_check(p->t, scalar_layout, leaves, n_leaves, tree, idx, n_idx, out, !host))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
-  if (n_idx == 0) return MSM_AMD_OK;
-  const uint32_t arity = p->t - 1, depth = poseidon_tree_depth(n_leaves, arity);
-  const size_t nodes = (n_leaves - 1) / (arity - 1), out_bytes = n_idx * depth * (arity - 1) * 32;
-  if (!host && !poseidon_clear_of(p, out, out_bytes))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": the paths must not overlap the parameters");
-  d.host = host, d.host_in = host ? 7u : 4u, d.kernel_ms = kernel_ms;
-  d.in[0] = leaves, d.in_bytes[0] = n_leaves * 32;
-  d.in[1] = tree, d.in_bytes[1] = nodes * 32;
-  d.in[2] = idx, d.in_bytes[2] = n_idx * sizeof(uint64_t);
-  d.out = out, d.out_bytes = out_bytes;
-  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
-    launch_merkle_paths(st, scalar_layout, arity, depth, io.in[0], n_leaves, io.in[1], io.in[2], n_idx, io.out);
-    return MSM_AMD_OK;
-  });
-}
-
-}  // namespace
-
-extern "C" {
-
-int msm_amd_poseidon_params_build(msm_amd_ctx* ctx, uint32_t t, uint32_t r_f, uint32_t r_p, int scalar_layout, const void* ark,
-                                  const void* mds, msm_amd_poseidon_params** out) {
-  if (!ctx || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_poseidon_params_build: null pointer");
-  *out = nullptr;
-  if (const char* why = poseidon_constants_check(t, r_f, r_p, scalar_layout, ark, mds))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, std::string("msm_amd_poseidon_params_build: ") + why);
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (int rc = recover_if_stalled(ctx)) return rc;
-  std::vector<u256> image;
-  poseidon_build_image(t, r_f, r_p, scalar_layout, ark, mds, &image);
-  int up = MSM_AMD_OK;
-  if (int rc = handle_build_tail(ctx, ctx->live_poseidon, image.size() * 32, "the constants of a Poseidon instance",
-                                 "Poseidon parameter build",
-                                 [&](void* d_mem) { up = staged_upload(ctx, d_mem, image.data(), image.size() * 32, ctx->stream); },
-                                 out))
-    return rc;
-  if (up) {   // the upload did not go through: nothing may read the allocation
-    msm_amd_poseidon_params* h = *out;
-    *out = nullptr;
-    const std::string why = ctx->last_error;
-    handle_free(ctx, ctx->live_poseidon, h, "");
-    return fail(ctx, up, "msm_amd_poseidon_params_build: " + why);
-  }
-  (*out)->t = t, (*out)->r_f = r_f, (*out)->r_p = r_p;
-  return MSM_AMD_OK;
-}
-
-int msm_amd_poseidon_params_info(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, uint32_t* t, uint32_t* r_f,
-                                 uint32_t* r_p, size_t* device_bytes) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const msm_amd_poseidon_params* p = find_handle(ctx->live_poseidon, params);
-  if (!p) return fail(ctx, MSM_AMD_INPUT_ERROR, std::string("msm_amd_poseidon_params_info") + kNotPoseidon);
-  if (t) *t = p->t;
-  if (r_f) *r_f = p->r_f;
-  if (r_p) *r_p = p->r_p;
-  if (device_bytes) *device_bytes = p->bytes;
-  return MSM_AMD_OK;
-}
-
-int msm_amd_poseidon_params_free(msm_amd_ctx* ctx, msm_amd_poseidon_params* params) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  return handle_free(ctx, ctx->live_poseidon, params, "msm_amd_poseidon_params_free: not a Poseidon parameter handle of this ctx");
-}
-
-int msm_amd_poseidon_permute(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* in, size_t n,
-                             void* out) {
-  return poseidon_call(ctx, params, kPoseidonPermute, true, scalar_layout, nullptr, in, n, out, nullptr);
-}
-
-int msm_amd_poseidon_permute_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* d_in,
-                                    size_t n, void* d_out, float* kernel_ms) {
-  return poseidon_call(ctx, params, kPoseidonPermute, false, scalar_layout, nullptr, d_in, n, d_out, kernel_ms);
-}
-
-int msm_amd_poseidon_hash(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* tag32,
-                          const void* in, size_t n, void* out) {
-  return poseidon_call(ctx, params, kPoseidonHash, true, scalar_layout, tag32, in, n, out, nullptr);
-}
-
-int msm_amd_poseidon_hash_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* tag32,
-                                 const void* d_in, size_t n, void* d_out, float* kernel_ms) {
-  return poseidon_call(ctx, params, kPoseidonHash, false, scalar_layout, tag32, d_in, n, d_out, kernel_ms);
-}
-
-int msm_amd_poseidon_merkle_build(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* tag32,
-                                  const void* leaves, size_t n_leaves, void* tree, void* root32) {
-  return poseidon_merkle_build_call(ctx, params, true, scalar_layout, tag32, leaves, n_leaves, tree, root32, nullptr);
-}
-
-int msm_amd_poseidon_merkle_build_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout,
-                                         const void* tag32, const void* d_leaves, size_t n_leaves, void* d_tree, void* root32,
-                                         float* kernel_ms) {
-  return poseidon_merkle_build_call(ctx, params, false, scalar_layout, tag32, d_leaves, n_leaves, d_tree, root32, kernel_ms);
-}
-
-int msm_amd_poseidon_merkle_paths(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout, const void* leaves,
-                                  size_t n_leaves, const void* tree, const uint64_t* idx, size_t n_idx, void* out) {
-  return poseidon_merkle_paths_call(ctx, params, true, scalar_layout, leaves, n_leaves, tree, idx, n_idx, out, nullptr);
-}
-
-int msm_amd_poseidon_merkle_paths_device(msm_amd_ctx* ctx, const msm_amd_poseidon_params* params, int scalar_layout,
-                                         const void* d_leaves, size_t n_leaves, const void* d_tree, const uint64_t* idx,
-                                         size_t n_idx, void* d_out, float* kernel_ms) {
-  return poseidon_merkle_paths_call(ctx, params, false, scalar_layout, d_leaves, n_leaves, d_tree, idx, n_idx, d_out, kernel_ms);
 }
 
 }  // extern "C"
