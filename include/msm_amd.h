@@ -1358,6 +1358,80 @@ int msm_amd_test_poseidon_plan(uint32_t t, size_t n_leaves, uint32_t top_log, ui
  * launches (2 levels - 1), out[2] tiles of the first level over all vectors, out[3] records of ctx-owned device memory */
 int msm_amd_test_fr_plan(size_t n, size_t n_vec, uint32_t tile_log, uint64_t out[4]);
 
+/* ---- pairings ---------------------------------------------------------------------------------
+ * The optimal ate pairing of BN254, e: G1 x G2 -> GT, in groups of pairs: the one operation that connects the two groups
+ * the calls above handle (an SRS consistency check, a Groth16 or KZG verification where the proof was made, the inner
+ * pairing product of proof aggregation).
+ * Definition.  x = 4965661367192848881, p = 36x^4 + 36x^3 + 24x^2 + 6x + 1, r = 36x^4 + 36x^3 + 18x^2 + 6x + 1.
+ *   Fq2 = Fq[u] / (u^2 + 1), xi = 9 + u, Fq6 = Fq2[v] / (v^3 - xi), Fq12 = Fq6[w] / (w^2 - v); the twist y^2 = x^3 + 3 / xi.
+ *   e(P, Q) = f^((p^12 - 1) / r) with f = f_{6x+2,Q}(P) l_{T,pi(Q)}(P) l_{T+pi(Q),-pi^2(Q)}(P), pi the p-power Frobenius
+ *   on the twist, lines evaluated at P through the untwist.  The exponent is exactly (p^12 - 1) / r, no multiple of it.
+ *   A pair in which P or Q is the identity contributes 1.
+ * GT record: MSM_AMD_GT_BYTES = 384, twelve Fq of 32 bytes, little-endian, canonical (< p), in the order c0.c0.c0,
+ *   c0.c0.c1, c0.c1.c0, c0.c1.c1, c0.c2.c0, c0.c2.c1, c1.c0.c0, ..., c1.c2.c1 (the field order of the Fq12 structs of
+ *   arkworks and halo2curves).  MSM_AMD_GT_MONT_LE: Montgomery, R = 2^256; MSM_AMD_GT_CANON_LE: plain residues.
+ *   Byte equality with either library is NOT confirmed (tests/golden/pairing_known.json).
+ * Groups.  Group g is the product over the pairs g group_size .. (g + 1) group_size - 1 of the two point arrays;
+ *   out_gt holds n_groups records.  group_size = 1: independent pairings; n_groups = 1: one pairing product;
+ *   group_size = 0: every group is the unit.  is_one (optional): one byte per group, 1 iff its result is the unit --
+ *   the pairing check.
+ * flags.  MSM_AMD_PAIRING_MILLER_ONLY writes the group's Miller product instead of the pairing, for callers that
+ *   multiply further before ONE msm_amd_final_exponentiation.  Such a record is a REPRESENTATIVE: a Miller value is
+ *   defined only up to factors that the final exponentiation removes, and only its final exponentiation is
+ *   specified (the device and the host twin do write the same bytes).  is_one must be NULL under this flag.
+ * Points: the four G1 host layouts and the two G2 host layouts; the _device forms also take MSM_AMD_POINT_PREPARED /
+ *   MSM_AMD_G2_POINT_PREPARED records.  Table handles are refused.  Points are NOT validated: run the point checks of
+ *   both groups first (MSM_AMD_CHECK_CURVE, and MSM_AMD_CHECK_SUBGROUP for G2) on input that is not trusted.  For a
+ *   point off its curve or outside the r-torsion the result is unspecified, but the call returns and reads and
+ *   writes nothing out of bounds: the line formulas are projective and division-free, so even T = +-Q in an addition
+ *   step only yields zeros.
+ * Status.  MSM_AMD_INPUT_ERROR, output untouched: a null pointer with work to do; n_groups * group_size >= 2^32; an
+ *   unknown or refused layout; unknown flags; is_one with MILLER_ONLY.  n_groups == 0 returns MSM_AMD_OK.
+ * Where the final exponentiation runs.  One lane per group is slow for few groups: in the host-buffer form, below
+ *   MSM_AMD_PAIRING_DEVICE_FINAL_FROM groups (environment, read at every call; default 768, the measured crossover on one MI355X
+ *   against sixteen host threads) the Miller products come back and the host twin finishes them; the bytes are the same.  The _device
+ *   forms always finish on the device.  MSM_AMD_PAIRING_PAIRS_PER_LANE (1, 2, 4; default 1) sets how many pairs one lane takes,
+ *   MSM_AMD_PAIRING_F_IN_LDS (0, 1) where the Miller kernel keeps its running f. */
+enum { MSM_AMD_GT_MONT_LE = 0, MSM_AMD_GT_CANON_LE = 1 };
+enum { MSM_AMD_GT_BYTES = 384 };
+enum { MSM_AMD_PAIRING_MILLER_ONLY = 1 };
+int msm_amd_pairing_product(msm_amd_ctx* ctx, int point_layout, int g2_point_layout, const void* g1_points,
+                            const void* g2_points, size_t n_groups, size_t group_size, uint32_t flags, int gt_layout,
+                            void* out_gt, uint8_t* is_one);
+int msm_amd_pairing_product_device(msm_amd_ctx* ctx, int point_layout, int g2_point_layout, const void* d_g1_points,
+                                   const void* d_g2_points, size_t n_groups, size_t group_size, uint32_t flags,
+                                   int gt_layout, void* d_out_gt, uint8_t* d_is_one, float* kernel_ms);
+int msm_amd_host_pairing_product(int point_layout, int g2_point_layout, const void* g1_points, const void* g2_points,
+                                 size_t n_groups, size_t group_size, uint32_t flags, int gt_layout, void* out_gt,
+                                 uint8_t* is_one, int threads);
+/* out[i] = in[i]^((p^12 - 1) / r) for n GT records of gt_layout (any 256-bit field is taken mod p); out may be in;
+ * is_one optional.  The host-buffer form follows the placement rule above with n in the place of the group count. */
+int msm_amd_final_exponentiation(msm_amd_ctx* ctx, int gt_layout, const void* in, size_t n, void* out, uint8_t* is_one);
+int msm_amd_final_exponentiation_device(msm_amd_ctx* ctx, int gt_layout, const void* d_in, size_t n, void* d_out,
+                                        uint8_t* d_is_one, float* kernel_ms);
+int msm_amd_host_final_exponentiation(int gt_layout, const void* in, size_t n, void* out, uint8_t* is_one, int threads);
+/* Test aid (no ctx): the plan of a pairing product.  pairs_per_lane: 0 for the default rule, else the knob's value;
+ * device_final_from: the group count from which the device finishes, UINT64_MAX for the library's own default.  out: [0] pairs per lane, [1] lanes per group
+ * (ceil(group_size / [0]), at least 1), [2] fold levels (each multiplies four partials per lane), [3] 1 if the final
+ * exponentiation runs on the device. */
+int msm_amd_test_pairing_plan(size_t n_groups, size_t group_size, uint32_t pairs_per_lane, uint64_t device_final_from,
+                              uint32_t out[4]);
+/* Test aid: one op of the device's Fq12 arithmetic (bn254_fq12_29.hip.h) on raw 29-bit limbs, one element per call.
+ * a, b, out: MSM_AMD_FQ12_WORDS u32 each; an Fq12 in the order of the GT record, 18 words per Fq2 (c0 limbs 0..8, c1
+ * limbs 0..8); an Fq6 in the first 54 words.  Operands obey the bounds contract of that header (normalised limbs,
+ * at most 4 p per component; line coefficients below 8 p).  LINE_MUL: b = l0, l1, l3.  DOUBLE_STEP: a = T (X, Y, Z),
+ * b = x_P, y_P (9 words each); out = T', then l0, l1, l3.  ADD_STEP: the same with Q (x, y) behind T in a.
+ * An unknown op is refused. */
+enum {
+  MSM_AMD_FQ12_OP_FQ6_MUL = 0, MSM_AMD_FQ12_OP_MUL = 1, MSM_AMD_FQ12_OP_SQR = 2, MSM_AMD_FQ12_OP_CYCLO_SQR = 3,
+  MSM_AMD_FQ12_OP_LINE_MUL = 4, MSM_AMD_FQ12_OP_FROB1 = 5, MSM_AMD_FQ12_OP_FROB2 = 6, MSM_AMD_FQ12_OP_FROB3 = 7,
+  MSM_AMD_FQ12_OP_CONJ = 8, MSM_AMD_FQ12_OP_INV = 9, MSM_AMD_FQ12_OP_POW_X = 10, MSM_AMD_FQ12_OP_DOUBLE_STEP = 11,
+  MSM_AMD_FQ12_OP_ADD_STEP = 12
+};
+enum { MSM_AMD_FQ12_WORDS = 108 };
+int msm_amd_test_fq12_op(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out);
+int msm_amd_test_fq12_op_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out);
+
 /* ---- introspection --------------------------------------------------------------------------- */
 int msm_amd_last_timings(const msm_amd_ctx* ctx, msm_amd_timings* out);
 /* Algorithmic HBM bytes of one MSM: whole pipeline and accumulation only. */

@@ -61,6 +61,13 @@ MLE_LOW, MLE_HIGH = 0, 1
 WIDTH_UNSIGNED, WIDTH_SIGNED = 0, 1
 SUMCHECK_PRODUCT, SUMCHECK_EQ_AB_C = 0, 1
 MLE_CALL_BIND, MLE_CALL_EVAL, MLE_CALL_EQ_TABLE, MLE_CALL_ROUND = range(4)
+# pairings (MSM_AMD_GT_*, MSM_AMD_PAIRING_*, MSM_AMD_FQ12_OP_*)
+GT_MONT_LE, GT_CANON_LE = 0, 1
+GT_BYTES = 384
+PAIRING_MILLER_ONLY = 1
+(FQ12_OP_FQ6_MUL, FQ12_OP_MUL, FQ12_OP_SQR, FQ12_OP_CYCLO_SQR, FQ12_OP_LINE_MUL, FQ12_OP_FROB1, FQ12_OP_FROB2,
+ FQ12_OP_FROB3, FQ12_OP_CONJ, FQ12_OP_INV, FQ12_OP_POW_X, FQ12_OP_DOUBLE_STEP, FQ12_OP_ADD_STEP) = range(13)
+FQ12_WORDS = 108
 
 
 def op_is_point(op):
@@ -140,6 +147,9 @@ EXPORTS = [
     "msm_amd_poseidon_merkle_build", "msm_amd_poseidon_merkle_build_device", "msm_amd_host_poseidon_merkle_build",
     "msm_amd_poseidon_merkle_paths", "msm_amd_poseidon_merkle_paths_device", "msm_amd_host_poseidon_merkle_paths",
     "msm_amd_test_poseidon_plan",
+    "msm_amd_pairing_product", "msm_amd_pairing_product_device", "msm_amd_host_pairing_product",
+    "msm_amd_final_exponentiation", "msm_amd_final_exponentiation_device", "msm_amd_host_final_exponentiation",
+    "msm_amd_test_pairing_plan", "msm_amd_test_fq12_op", "msm_amd_test_fq12_op_host",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -461,6 +471,17 @@ def _lib():
             L.msm_amd_host_poseidon_merkle_paths.argtypes = [c_uint32, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_int,
                                                              c_void_p]
             L.msm_amd_test_poseidon_plan.argtypes = [c_uint32, c_size_t, c_uint32, POINTER(c_uint64)]
+        if hasattr(L, "msm_amd_pairing_product"):   # (an MSM_AMD_LIB build from before the pairing calls still loads)
+            shape = [c_int, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_uint32, c_int, c_void_p, c_void_p]
+            L.msm_amd_pairing_product.argtypes = [c_void_p] + shape
+            L.msm_amd_pairing_product_device.argtypes = [c_void_p] + shape + [POINTER(c_float)]
+            L.msm_amd_host_pairing_product.argtypes = shape + [c_int]
+            L.msm_amd_final_exponentiation.argtypes = [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]
+            L.msm_amd_final_exponentiation_device.argtypes = L.msm_amd_final_exponentiation.argtypes + [POINTER(c_float)]
+            L.msm_amd_host_final_exponentiation.argtypes = [c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_int]
+            L.msm_amd_test_pairing_plan.argtypes = [c_size_t, c_size_t, c_uint32, c_uint64, POINTER(c_uint32)]
+            L.msm_amd_test_fq12_op.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+            L.msm_amd_test_fq12_op_host.argtypes = [c_int, c_void_p, c_void_p, c_void_p]
         L.msm_amd_generate_instance_host.argtypes = [c_uint64, c_size_t, c_int, c_void_p, c_void_p, c_int]
         L.msm_amd_test_op_ifma.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         if hasattr(L, "msm_amd_scalar_width"):   # (an MSM_AMD_LIB build from before the bounded-width calls still loads)
@@ -1332,6 +1353,47 @@ class MsmConfig:
                                                             n if stride is None else stride, g, ctypes.byref(ms)))
         return g.raw[:32 * sumcheck_values(form, n_vec)], ms.value
 
+    # ---- pairings -------------------------------------------------------------------------------
+    def pairing_product(self, g1_points: bytes, g2_points: bytes, n_groups: int, group_size: int, flags=0,
+                        gt_layout=GT_MONT_LE, point_layout=POINT_H2C_AFFINE, g2_point_layout=G2_POINT_H2C_AFFINE,
+                        want_is_one=True):
+        """Group g = the product of e(P_i, Q_i) over its group_size pairs, on the GPU from host memory
+        (msm_amd_pairing_product); returns (n_groups GT records, is_one bytes or None)."""
+        out = ctypes.create_string_buffer(max(1, n_groups * GT_BYTES))
+        flag = ctypes.create_string_buffer(max(1, n_groups)) if want_is_one and not flags & PAIRING_MILLER_ONLY else None
+        self._check(_lib().msm_amd_pairing_product(self.h, point_layout, g2_point_layout, g1_points, g2_points, n_groups,
+                                                   group_size, flags, gt_layout, out, flag))
+        return out.raw[:n_groups * GT_BYTES], (flag.raw[:n_groups] if flag is not None else None)
+
+    def pairing_product_device(self, d_g1, d_g2, n_groups: int, group_size: int, d_out, d_is_one=None, flags=0,
+                               gt_layout=GT_MONT_LE, point_layout=POINT_H2C_AFFINE,
+                               g2_point_layout=G2_POINT_H2C_AFFINE) -> float:
+        """The same between device buffers (points may be *_PREPARED records); returns kernel_ms."""
+        ms = c_float(0)
+        self._check(_lib().msm_amd_pairing_product_device(self.h, point_layout, g2_point_layout, c_void_p(d_g1),
+                                                          c_void_p(d_g2), n_groups, group_size, flags, gt_layout,
+                                                          c_void_p(d_out), c_void_p(d_is_one), ctypes.byref(ms)))
+        return ms.value
+
+    def final_exponentiation(self, records: bytes, n: int, gt_layout=GT_MONT_LE):
+        """msm_amd_final_exponentiation on host memory; returns (records, is_one bytes)."""
+        out = ctypes.create_string_buffer(max(1, n * GT_BYTES))
+        flag = ctypes.create_string_buffer(max(1, n))
+        self._check(_lib().msm_amd_final_exponentiation(self.h, gt_layout, records, n, out, flag))
+        return out.raw[:n * GT_BYTES], flag.raw[:n]
+
+    def final_exponentiation_device(self, d_in, n: int, d_out, d_is_one=None, gt_layout=GT_MONT_LE) -> float:
+        ms = c_float(0)
+        self._check(_lib().msm_amd_final_exponentiation_device(self.h, gt_layout, c_void_p(d_in), n, c_void_p(d_out),
+                                                               c_void_p(d_is_one), ctypes.byref(ms)))
+        return ms.value
+
+    def test_fq12_op(self, op, a, b):
+        """One raw-limb Fq12 op (MSM_AMD_FQ12_OP_*) on the device: a, b lists of up to FQ12_WORDS u32; returns FQ12_WORDS."""
+        out = (c_uint32 * FQ12_WORDS)()
+        self._check(_lib().msm_amd_test_fq12_op(self.h, op, _fq12_raw(a), _fq12_raw(b), out))
+        return list(out)
+
     def test_op_g2(self, op, a, b, count):
         """Raw-limb G2 op (MSM_AMD_G2_RAW_*) on the device: a, b flat u32 lists of count * G2_RAW_IN_WORDS; returns
         count * G2_RAW_OUT_WORDS u32."""
@@ -1614,6 +1676,54 @@ def host_compress_points(points: bytes, n: int, fmt=COMPRESSED_ARK, point_layout
     if st != OK:
         raise MsmError(st)
     return out.raw[:n * size], bad.value
+
+
+def _fq12_raw(words):
+    buf = (c_uint32 * FQ12_WORDS)()
+    for i, w in enumerate(words):
+        buf[i] = w
+    return buf
+
+
+def test_fq12_op_host(op, a, b):
+    """The same op bodies as MsmConfig.test_fq12_op, on the host CPU (no GPU)."""
+    out = (c_uint32 * FQ12_WORDS)()
+    st = _lib().msm_amd_test_fq12_op_host(op, _fq12_raw(a), _fq12_raw(b), out)
+    if st != OK:
+        raise MsmError(st)
+    return list(out)
+
+
+def host_pairing_product(g1_points: bytes, g2_points: bytes, n_groups: int, group_size: int, flags=0, gt_layout=GT_MONT_LE,
+                         point_layout=POINT_H2C_AFFINE, g2_point_layout=G2_POINT_H2C_AFFINE, threads=0, want_is_one=True):
+    """Host twin of MsmConfig.pairing_product (no GPU); returns (records, is_one bytes or None)."""
+    out = ctypes.create_string_buffer(max(1, n_groups * GT_BYTES))
+    flag = ctypes.create_string_buffer(max(1, n_groups)) if want_is_one and not flags & PAIRING_MILLER_ONLY else None
+    st = _lib().msm_amd_host_pairing_product(point_layout, g2_point_layout, g1_points, g2_points, n_groups, group_size,
+                                             flags, gt_layout, out, flag, threads)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:n_groups * GT_BYTES], (flag.raw[:n_groups] if flag is not None else None)
+
+
+def host_final_exponentiation(records: bytes, n: int, gt_layout=GT_MONT_LE, threads=0):
+    out = ctypes.create_string_buffer(max(1, n * GT_BYTES))
+    flag = ctypes.create_string_buffer(max(1, n))
+    st = _lib().msm_amd_host_final_exponentiation(gt_layout, records, n, out, flag, threads)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:n * GT_BYTES], flag.raw[:n]
+
+
+def pairing_plan(n_groups: int, group_size: int, pairs_per_lane=0, device_final_from=None) -> dict:
+    """msm_amd_test_pairing_plan: the plan of a pairing product as a dict (device_final_from None: the library's default)."""
+    out = (c_uint32 * 4)()
+    if device_final_from is None:
+        device_final_from = 0xFFFFFFFFFFFFFFFF
+    st = _lib().msm_amd_test_pairing_plan(n_groups, group_size, pairs_per_lane, device_final_from, out)
+    if st != OK:
+        raise MsmError(st)
+    return dict(zip(("pairs_per_lane", "lanes_per_group", "fold_levels", "final_on_device"), out))
 
 
 def host_mul_points(scalars: bytes, points: bytes, n: int, base_mode=MUL_BASE_EACH, scalar_layout=SCALAR_MONT_LE,

@@ -1,5 +1,5 @@
 // The blocking point calls of both groups (device_call.h): validation, compressed points, batch scalar multiplication
-// with its stage entries, and the transform over G1 points with its levels tap.
+// with its stage entries, the transform over G1 points with its levels tap, and the pairing calls.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +12,8 @@
 #include "launch_compress.h"
 #include "launch_mul.h"
 #include "launch_nttp.h"
+#include "host_pairing.h"
+#include "launch_pairing.h"
 
 namespace {
 
@@ -409,6 +411,143 @@ int msm_amd_test_ntt_points_levels(msm_amd_ctx* ctx, const msm_amd_ntt_domain* d
                                    const void* in, uint32_t levels, int point_layout_out, void* out) {
   if (levels == kNttpAllLevels) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_ntt_points_levels: levels must be 0 .. log_n");
   return ntt_points_call(ctx, domain, true, direction, point_layout_in, in, point_layout_out, out, nullptr, levels);
+}
+
+}  // extern "C"
+
+// ---- pairings (msm_amd_pairing_product*, msm_amd_final_exponentiation*, msm_amd_test_fq12_op) ------------------------------
+// Through device_call, all on the main stream: the Miller kernel writes one partial product per lane into the first work
+// array, the fold levels multiply them down between the two work arrays, and the last kernel turns the one value per
+// group into its record (and its unit flag).  When the plan leaves the final exponentiation to the host (host buffers,
+// fewer groups than the threshold), that kernel only converts, and the host twin finishes the records where the caller
+// gets them.
+namespace {
+
+int pairing_call(msm_amd_ctx* ctx, bool host, int layout_g1, int layout_g2, const void* g1, const void* g2, size_t n_groups,
+                 size_t group_size, uint32_t flags, int gt_layout, void* out, uint8_t* is_one, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall c;
+  c.who = host ? "msm_amd_pairing_product" : "msm_amd_pairing_product_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  const uint32_t prepared = host ? 0u : (uint32_t)kKindPrepared;
+  const size_t s1 = point_record_bytes(false, layout_g1, kKindHost | prepared), s2 = point_record_bytes(true, layout_g2, kKindHost | prepared);
+  if (s1 == 0 || s2 == 0)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + (host ? ": points in a host layout of their group only (not *_PREPARED / *_TABLES)"
+                                                        : ": points in a host layout of their group or *_PREPARED (not *_TABLES)"));
+  if (const char* why = pairing_shape_error(n_groups, group_size, flags, gt_layout, is_one != nullptr))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": " + why);
+  if (n_groups == 0) return MSM_AMD_OK;
+  const size_t pairs = n_groups * group_size;
+  if (!out || (pairs && (!g1 || !g2))) return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": null pointer with work to do");
+  uint32_t ppl_knob;
+  uint64_t final_from;
+  bool f_in_lds;
+  pairing_knobs(&ppl_knob, &final_from, &f_in_lds);
+  const PairingPlan plan = pairing_plan(n_groups, group_size, ppl_knob, final_from);
+  const bool miller_only = (flags & MSM_AMD_PAIRING_MILLER_ONLY) != 0;
+  const bool host_final = host && !miller_only && !plan.final_on_device;
+  const size_t partial_bytes = kPairingPartialWords * sizeof(uint32_t);
+  const size_t folded = (plan.lanes_per_group + kPairingFoldRadix - 1) / kPairingFoldRadix;
+  CallState& s = ctx->calls;
+  c.host = host, c.host_in = host ? 3u : 0u, c.kernel_ms = kernel_ms;
+  c.in[0] = g1, c.in_bytes[0] = pairs * s1;
+  c.in[1] = g2, c.in_bytes[1] = pairs * s2;
+  c.out = out, c.out_bytes = n_groups * (size_t)MSM_AMD_GT_BYTES;
+  c.reasons = host_final ? nullptr : is_one, c.n = c.reasons ? n_groups : 0;
+  c.work[0] = {&s.xyzz, n_groups * plan.lanes_per_group * partial_bytes};
+  c.work[1] = {&s.scratch, plan.fold_levels ? n_groups * folded * partial_bytes : 0};
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const int rc = device_call(ctx, c, [&](hipStream_t st, const CallIo& io) -> int {
+      uint32_t *cur = (uint32_t*)s.xyzz.p, *other = (uint32_t*)s.scratch.p;
+      launch_pairing_miller(st, layout_g1, io.in[0], layout_g2, io.in[1], (uint32_t)n_groups, (uint32_t)group_size, plan, f_in_lds, cur);
+      for (uint32_t count = plan.lanes_per_group; count > 1; count = (count + kPairingFoldRadix - 1) / kPairingFoldRadix) {
+        launch_pairing_fold(st, cur, (uint32_t)n_groups, count, other);
+        std::swap(cur, other);
+      }
+      launch_pairing_final(st, cur, true, (uint32_t)n_groups, miller_only || host_final, gt_layout, io.out, io.reasons);
+      return MSM_AMD_OK;
+    });
+    if (rc) return rc;
+  }
+  if (host_final) host_final_exponentiation(gt_layout, (const uint8_t*)out, n_groups, 0, (uint8_t*)out, is_one);
+  return MSM_AMD_OK;
+}
+
+int final_exp_call(msm_amd_ctx* ctx, bool host, int gt_layout, const void* in, size_t n, void* out, uint8_t* is_one,
+                   float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall c;
+  c.who = host ? "msm_amd_final_exponentiation" : "msm_amd_final_exponentiation_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (!pairing_gt_layout_known(gt_layout))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": gt_layout must be MSM_AMD_GT_MONT_LE or MSM_AMD_GT_CANON_LE");
+  if (n > 0xFFFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": n >= 2^32");
+  if (n == 0) return MSM_AMD_OK;
+  if (!in || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, c.who + ": null pointer with n > 0");
+  uint32_t ppl_knob;
+  uint64_t final_from;
+  bool f_in_lds;
+  pairing_knobs(&ppl_knob, &final_from, &f_in_lds);
+  if (host && n < final_from) {
+    host_final_exponentiation(gt_layout, (const uint8_t*)in, n, 0, (uint8_t*)out, is_one);
+    return MSM_AMD_OK;
+  }
+  c.host = host, c.host_in = host ? 1u : 0u, c.kernel_ms = kernel_ms;
+  c.in[0] = in, c.in_bytes[0] = n * (size_t)MSM_AMD_GT_BYTES;
+  c.out = out, c.out_bytes = n * (size_t)MSM_AMD_GT_BYTES;
+  c.reasons = is_one, c.n = is_one ? n : 0;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return device_call(ctx, c, [&](hipStream_t st, const CallIo& io) -> int {
+    launch_pairing_final(st, io.in[0], false, (uint32_t)n, false, gt_layout, io.out, io.reasons);
+    return MSM_AMD_OK;
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_pairing_product(msm_amd_ctx* ctx, int point_layout, int g2_point_layout, const void* g1_points,
+                            const void* g2_points, size_t n_groups, size_t group_size, uint32_t flags, int gt_layout,
+                            void* out_gt, uint8_t* is_one) {
+  return pairing_call(ctx, true, point_layout, g2_point_layout, g1_points, g2_points, n_groups, group_size, flags, gt_layout,
+                      out_gt, is_one, nullptr);
+}
+
+int msm_amd_pairing_product_device(msm_amd_ctx* ctx, int point_layout, int g2_point_layout, const void* d_g1_points,
+                                   const void* d_g2_points, size_t n_groups, size_t group_size, uint32_t flags,
+                                   int gt_layout, void* d_out_gt, uint8_t* d_is_one, float* kernel_ms) {
+  return pairing_call(ctx, false, point_layout, g2_point_layout, d_g1_points, d_g2_points, n_groups, group_size, flags,
+                      gt_layout, d_out_gt, d_is_one, kernel_ms);
+}
+
+int msm_amd_final_exponentiation(msm_amd_ctx* ctx, int gt_layout, const void* in, size_t n, void* out, uint8_t* is_one) {
+  return final_exp_call(ctx, true, gt_layout, in, n, out, is_one, nullptr);
+}
+
+int msm_amd_final_exponentiation_device(msm_amd_ctx* ctx, int gt_layout, const void* d_in, size_t n, void* d_out,
+                                        uint8_t* d_is_one, float* kernel_ms) {
+  return final_exp_call(ctx, false, gt_layout, d_in, n, d_out, d_is_one, kernel_ms);
+}
+
+int msm_amd_test_fq12_op(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  if (op < 0 || op > MSM_AMD_FQ12_OP_ADD_STEP || !a || !b || !out)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_fq12_op: unknown op or null pointer");
+  DeviceCall c;
+  c.who = "msm_amd_test_fq12_op";
+  const size_t bytes = kPairingPartialWords * sizeof(uint32_t);
+  c.all_host(true);
+  c.host_in = 3u;
+  c.in[0] = a, c.in_bytes[0] = bytes;
+  c.in[1] = b, c.in_bytes[1] = bytes;
+  c.out = out, c.out_bytes = bytes;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return device_call(ctx, c, [&](hipStream_t st, const CallIo& io) -> int {
+    launch_test_fq12_op(st, op, (const uint32_t*)io.in[0], (const uint32_t*)io.in[1], (uint32_t*)io.out, 1);
+    return MSM_AMD_OK;
+  });
 }
 
 }  // extern "C"

@@ -1,0 +1,19 @@
+#!/bin/bash
+# AddressSanitizer + UBSan (trapping) run of the host side of the pairing calls as a stand-alone program: host_pairing.hip
+# is compiled with the host instrumented (the device code is not) and
+# linked with tools/pairing_asan_check.cpp, which calls the twins, the plan tap and the raw ops on exactly sized heap
+# buffers.  No GPU, no python.
+set -e
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
+OUT=$ROOT/build_ab/pairing_asan
+SAN="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fsanitize-trap=undefined -Xarch_host -fno-omit-frame-pointer"
+mkdir -p "$OUT"
+cd "$ROOT/metal-msm-gpu-acceleration_amd/csrc"
+for f in host_pairing; do
+  $HIPCC -O1 -g -std=c++17 -fPIC --offload-arch=${ARCH:-gfx950} -Wall -Wno-unused-function $SAN -c -o "$OUT/$f.o" $f.hip
+done
+HOST_SAN="-fsanitize=address -fsanitize=undefined -fsanitize-trap=undefined -fno-omit-frame-pointer"
+$HIPCC -x c++ -O1 -g -std=c++17 $HOST_SAN -c -o "$OUT/main.o" "$ROOT/tools/pairing_asan_check.cpp"
+$HIPCC --offload-arch=${ARCH:-gfx950} $HOST_SAN -o "$OUT/pairing_asan_check" "$OUT/main.o" "$OUT/host_pairing.o" -lpthread
+ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 "$OUT/pairing_asan_check"
