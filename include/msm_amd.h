@@ -1113,6 +1113,21 @@ int msm_amd_fr_prefix_product_device(msm_amd_ctx* ctx, int scalar_layout, int mo
                                      void* d_out, float* kernel_ms);
 int msm_amd_host_fr_prefix_product(int scalar_layout, int mode, const void* in, size_t n, size_t n_vec, int threads,
                                    void* out);
+/* The running sums on the same scan plan, workspace, modes, sizes, aliasing rules and knob: out[i] = sum_{j<=i} in[j]
+ * (INCLUSIVE) or out[0] = 0, out[i] = sum_{j<i} in[j] (EXCLUSIVE), restarting at every vector: logUp's
+ * phi[i+1] = phi[i] + h_f[i] - h_t[i]. */
+int msm_amd_fr_prefix_sum(msm_amd_ctx* ctx, int scalar_layout, int mode, const void* in, size_t n, size_t n_vec, void* out);
+int msm_amd_fr_prefix_sum_device(msm_amd_ctx* ctx, int scalar_layout, int mode, const void* d_in, size_t n, size_t n_vec,
+                                 void* d_out, float* kernel_ms);
+int msm_amd_host_fr_prefix_sum(int scalar_layout, int mode, const void* in, size_t n, size_t n_vec, int threads, void* out);
+
+/* out[i] = a[i] + k: beta + f[i] of a log-derivative lookup, the + gamma of PLONK's f + beta sigma + gamma (and, over a
+ * buffer of zeros, a fill).  An entry point of its own: msm_amd_fr_map has no seventh op.  Sizes, aliasing (out == a or
+ * disjoint) and errors as for msm_amd_fr_map with one operand; k32 is required. */
+int msm_amd_fr_shift(msm_amd_ctx* ctx, int scalar_layout, const void* k32, const void* a, size_t n, void* out);
+int msm_amd_fr_shift_device(msm_amd_ctx* ctx, int scalar_layout, const void* k32 /* HOST memory */, const void* d_a, size_t n,
+                            void* d_out, float* kernel_ms);
+int msm_amd_host_fr_shift(int scalar_layout, const void* k32, const void* a, size_t n, int threads, void* out);
 
 /* ---- polynomials over Fr: evaluate, divide by X - z, combine ----------------------------------------------
  * What a KZG opening does between the transforms and the MSM of the quotient (halo2 eval_polynomial and kate_division,
@@ -1357,6 +1372,61 @@ int msm_amd_test_poseidon_plan(uint32_t t, size_t n_leaves, uint32_t top_log, ui
 /* Test aid (no ctx): the plan of a scan over n_vec vectors of n at a tile of 2^tile_log (2 .. 9): out[0] levels, out[1]
  * launches (2 levels - 1), out[2] tiles of the first level over all vectors, out[3] records of ctx-owned device memory */
 int msm_amd_test_fr_plan(size_t n, size_t n_vec, uint32_t tile_log, uint64_t out[4]);
+
+/* ---- lookup arguments over Fr: multiplicities and row indices ------------------------------------------------------------
+ * A log-derivative lookup (logUp) needs m[j] = #{ i : f[i] = t[j] }: Fr values matched against Fr values.  A table is one
+ * column of n_rows 32-byte records, 1 <= n_rows < 2^31 (n_rows == 0: MSM_AMD_INPUT_ERROR), MSM_AMD_SCALAR_MONT_LE or
+ * MSM_AMD_SCALAR_CANON_LE, any 256-bit word taken mod r; a table of tuples is the caller's theta-compression
+ * (msm_amd_fr_lincomb_device).  The handle keeps its own reduced copy of the rows -- the caller's buffer is not referenced
+ * after the build returns -- and an open-addressing index with linear probing over them: a power of two of 32-bit slots, at
+ * least 2 n_rows, hashed over all eight words of the residue.  Rows that are equal mod r share one slot, and their
+ * representative is the SMALLEST row index, whatever the order the rows arrive in.  Every probe loop is bounded by the
+ * capacity; one that runs out (it cannot at this load) is MSM_AMD_PIPELINE_ERROR with a message, not a hang.
+ * msm_amd_fr_lookup_build_device is cheap enough for a table that depends on a per-proof challenge: one reduce-and-copy
+ * pass, one insert pass, one bounded wait that also brings the numbers of msm_amd_fr_lookup_info (longest_probe: the most
+ * slots one insert looked at).  Lifetime and misuse as for msm_amd_fr_matrix_*: bound to its ctx, a freed or foreign handle
+ * is MSM_AMD_INPUT_ERROR, msm_amd_destroy frees what is left.
+ * (Development knobs, read at every call: MSM_AMD_LOOKUP_HASH_BITS = 0 .. 32, default all: only that many bits of the hash
+ * choose the home slot, homes are taken from the top of the slot array so that chains wrap, 0 is one chain from the last
+ * slot; MSM_AMD_LOOKUP_COUNT = block (default: one atomic per distinct row per wave, the largest group of each of a
+ * workgroup's 16 waves folded through LDS first), wave (without the fold) or lane (one atomic per input).  No byte of any
+ * output depends on either.) */
+typedef struct msm_amd_fr_lookup msm_amd_fr_lookup;
+int msm_amd_fr_lookup_build(msm_amd_ctx* ctx, int scalar_layout, const void* table, size_t n_rows, msm_amd_fr_lookup** out);
+int msm_amd_fr_lookup_build_device(msm_amd_ctx* ctx, int scalar_layout, const void* d_table, size_t n_rows,
+                                   msm_amd_fr_lookup** out, float* kernel_ms);
+/* every out pointer is optional */
+int msm_amd_fr_lookup_info(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, size_t* n_rows, size_t* n_distinct,
+                           size_t* capacity, size_t* device_bytes, size_t* longest_probe);
+int msm_amd_fr_lookup_free(msm_amd_ctx* ctx, msm_amd_fr_lookup* lookup);
+/* n_vec columns of n records back to back, all looked up in the one table; n n_vec < 2^32.
+ * m_out[j] (n_rows records): the number of inputs equal to row j mod r as a fully reduced record in scalar_layout, credited
+ * to the representative only -- duplicate rows further down get 0 (any split satisfies logUp's identity; this one is
+ * deterministic).  idx_out (optional, n n_vec words): the representative's row index of every input, 0xFFFFFFFF for a value
+ * that is not in the table; written in either mode.  report (HOST memory): { n_missing, first_missing (the smallest flat
+ * index, 2^64 - 1 for none), rows_hit, max_multiplicity } -- msm_amd_msm_bounded_device can commit to m at the bit length
+ * of report[3] without a width scan.  It comes back in the call's one bounded wait.
+ * MSM_AMD_LOOKUP_STRICT: any miss is MSM_AMD_INPUT_ERROR with count and index in msm_amd_last_error (the report is filled
+ * in), and m_out is UNTOUCHED: the pass that writes it reads the miss counter on the device.  MSM_AMD_LOOKUP_COUNT_MISSING:
+ * MSM_AMD_OK, m counts the hits.  n == 0 or n_vec == 0: MSM_AMD_OK, m all zero, the report zero.
+ * MSM_AMD_INPUT_ERROR: an unknown layout or mode; a null in (with inputs), m_out or report; device pointers that are not
+ * 16-byte aligned (d_idx_out: 4); m_out or idx_out overlapping in, each other or (device) the table.  The counters live in
+ * ctx-owned memory (4 n_rows bytes). */
+enum { MSM_AMD_LOOKUP_STRICT = 0, MSM_AMD_LOOKUP_COUNT_MISSING = 1 };
+int msm_amd_fr_lookup_multiplicities(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, int scalar_layout, int on_missing,
+                                     const void* in, size_t n, size_t n_vec, void* m_out, uint32_t* idx_out,
+                                     uint64_t report[4]);
+int msm_amd_fr_lookup_multiplicities_device(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, int scalar_layout,
+                                            int on_missing, const void* d_in, size_t n, size_t n_vec, void* d_m_out,
+                                            uint32_t* d_idx_out, uint64_t report[4] /* HOST memory */, float* kernel_ms);
+/* The same on the CPU, from the table itself (no ctx, no GPU); a miss under STRICT returns MSM_AMD_INPUT_ERROR with the
+ * report filled in and m_out untouched */
+int msm_amd_host_fr_lookup_multiplicities(int scalar_layout, int on_missing, const void* table, size_t n_rows, const void* in,
+                                          size_t n, size_t n_vec, int threads, void* m_out, uint32_t* idx_out,
+                                          uint64_t report[4]);
+/* Test aid (no ctx): the index of a table of n_rows at hash_bits (0 .. 32): out[0] capacity, out[1] bytes of the device
+ * image, out[2] hash bits that choose a home, out[3] byte offset of the slots in the image */
+int msm_amd_test_fr_lookup_plan(size_t n_rows, uint32_t hash_bits, uint64_t out[4]);
 
 /* ---- pairings ---------------------------------------------------------------------------------
  * The optimal ate pairing of BN254, e: G1 x G2 -> GT, in groups of pairs: the one operation that connects the two groups

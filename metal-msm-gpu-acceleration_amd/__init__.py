@@ -57,6 +57,8 @@ NTT_FORWARD, NTT_INVERSE = 0, 1
 # vectors over Fr (MSM_AMD_FR_*)
 FR_ADD, FR_SUB, FR_MUL, FR_SCALE, FR_AXPY, FR_MULSUB_SCALE = range(6)
 FR_PREFIX_INCLUSIVE, FR_PREFIX_EXCLUSIVE = 0, 1
+LOOKUP_STRICT, LOOKUP_COUNT_MISSING = 0, 1
+LOOKUP_NOT_FOUND = 0xFFFFFFFF
 MLE_LOW, MLE_HIGH = 0, 1
 WIDTH_UNSIGNED, WIDTH_SIGNED = 0, 1
 SUMCHECK_PRODUCT, SUMCHECK_EQ_AB_C = 0, 1
@@ -150,6 +152,11 @@ EXPORTS = [
     "msm_amd_pairing_product", "msm_amd_pairing_product_device", "msm_amd_host_pairing_product",
     "msm_amd_final_exponentiation", "msm_amd_final_exponentiation_device", "msm_amd_host_final_exponentiation",
     "msm_amd_test_pairing_plan", "msm_amd_test_fq12_op", "msm_amd_test_fq12_op_host",
+    "msm_amd_fr_prefix_sum", "msm_amd_fr_prefix_sum_device", "msm_amd_host_fr_prefix_sum",
+    "msm_amd_fr_shift", "msm_amd_fr_shift_device", "msm_amd_host_fr_shift",
+    "msm_amd_fr_lookup_build", "msm_amd_fr_lookup_build_device", "msm_amd_fr_lookup_info", "msm_amd_fr_lookup_free",
+    "msm_amd_fr_lookup_multiplicities", "msm_amd_fr_lookup_multiplicities_device", "msm_amd_host_fr_lookup_multiplicities",
+    "msm_amd_test_fr_lookup_plan",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -409,6 +416,22 @@ def _lib():
                                                        POINTER(c_float)]
         L.msm_amd_host_fr_prefix_product.argtypes = [c_int, c_int, c_void_p, c_size_t, c_size_t, c_int, c_void_p]
         L.msm_amd_test_fr_plan.argtypes = [c_size_t, c_size_t, c_uint32, POINTER(c_uint64)]
+        L.msm_amd_fr_prefix_sum.argtypes = L.msm_amd_fr_prefix_product.argtypes
+        L.msm_amd_fr_prefix_sum_device.argtypes = L.msm_amd_fr_prefix_product_device.argtypes
+        L.msm_amd_host_fr_prefix_sum.argtypes = L.msm_amd_host_fr_prefix_product.argtypes
+        L.msm_amd_fr_shift.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+        L.msm_amd_fr_shift_device.argtypes = L.msm_amd_fr_shift.argtypes + [POINTER(c_float)]
+        L.msm_amd_host_fr_shift.argtypes = [c_int, c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+        L.msm_amd_fr_lookup_build.argtypes = [c_void_p, c_int, c_void_p, c_size_t, POINTER(c_void_p)]
+        L.msm_amd_fr_lookup_build_device.argtypes = L.msm_amd_fr_lookup_build.argtypes + [POINTER(c_float)]
+        L.msm_amd_fr_lookup_info.argtypes = [c_void_p, c_void_p] + [POINTER(c_size_t)] * 5
+        L.msm_amd_fr_lookup_free.argtypes = [c_void_p, c_void_p]
+        L.msm_amd_fr_lookup_multiplicities.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_size_t,
+                                                       c_void_p, c_void_p, POINTER(c_uint64)]
+        L.msm_amd_fr_lookup_multiplicities_device.argtypes = L.msm_amd_fr_lookup_multiplicities.argtypes + [POINTER(c_float)]
+        L.msm_amd_host_fr_lookup_multiplicities.argtypes = [c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t,
+                                                            c_int, c_void_p, c_void_p, POINTER(c_uint64)]
+        L.msm_amd_test_fr_lookup_plan.argtypes = [c_size_t, c_uint32, POINTER(c_uint64)]
         L.msm_amd_fr_poly_eval.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]
         L.msm_amd_fr_poly_eval_device.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
                                                   POINTER(c_float)]
@@ -1123,6 +1146,82 @@ class MsmConfig:
         self._check(_lib().msm_amd_fr_prefix_product_device(self.h, scalar_layout, mode, c_void_p(d_in), n, n_vec,
                                                             c_void_p(d_out), ctypes.byref(ms)))
         return ms.value
+
+    def fr_prefix_sum(self, data: bytes, mode=FR_PREFIX_INCLUSIVE, scalar_layout=SCALAR_MONT_LE, n_vec=1) -> bytes:
+        """Running sums of n_vec vectors of host records, restarting at every vector (msm_amd_fr_prefix_sum)"""
+        n = len(data) // 32 // n_vec if n_vec else 0
+        out = ctypes.create_string_buffer(max(1, len(data)))
+        self._check(_lib().msm_amd_fr_prefix_sum(self.h, scalar_layout, mode, data, n, n_vec, out))
+        return out.raw[:32 * n * n_vec]
+
+    def fr_prefix_sum_device(self, d_in, n: int, d_out, mode=FR_PREFIX_INCLUSIVE, scalar_layout=SCALAR_MONT_LE,
+                             n_vec=1) -> float:
+        """The same on device-resident records (msm_amd_fr_prefix_sum_device); returns kernel_ms."""
+        ms = c_float(0)
+        self._check(_lib().msm_amd_fr_prefix_sum_device(self.h, scalar_layout, mode, c_void_p(d_in), n, n_vec,
+                                                        c_void_p(d_out), ctypes.byref(ms)))
+        return ms.value
+
+    def fr_shift(self, a: bytes, k: bytes, scalar_layout=SCALAR_MONT_LE) -> bytes:
+        """out[i] = a[i] + k on host records (msm_amd_fr_shift); k: 32 bytes in scalar_layout"""
+        n = len(a) // 32 if a is not None else 0
+        out = ctypes.create_string_buffer(max(1, 32 * n))
+        self._check(_lib().msm_amd_fr_shift(self.h, scalar_layout, k, a, n, out))
+        return out.raw[:32 * n]
+
+    def fr_shift_device(self, d_a, n: int, d_out, k: bytes, scalar_layout=SCALAR_MONT_LE) -> float:
+        """The same on device-resident records, d_out == d_a or disjoint (msm_amd_fr_shift_device); returns kernel_ms."""
+        ms = c_float(0)
+        self._check(_lib().msm_amd_fr_shift_device(self.h, scalar_layout, k, c_void_p(d_a), n, c_void_p(d_out),
+                                                   ctypes.byref(ms)))
+        return ms.value
+
+    # ---- lookup tables over Fr: multiplicities and row indices --------------------------------------
+    def fr_lookup_build(self, table: bytes, scalar_layout=SCALAR_MONT_LE, n_rows=None) -> "FrLookup":
+        """The index of a table of host records on this ctx's device (msm_amd_fr_lookup_build)"""
+        h = c_void_p()
+        n_rows = len(table) // 32 if n_rows is None else n_rows
+        self._check(_lib().msm_amd_fr_lookup_build(self.h, scalar_layout, table, n_rows, ctypes.byref(h)))
+        return FrLookup(self, h)
+
+    def fr_lookup_build_device(self, d_table, n_rows: int, scalar_layout=SCALAR_MONT_LE) -> "FrLookup":
+        """The same from device-resident rows (msm_amd_fr_lookup_build_device); kernel_ms is left in .build_ms"""
+        h, ms = c_void_p(), c_float(0)
+        self._check(_lib().msm_amd_fr_lookup_build_device(self.h, scalar_layout, c_void_p(d_table), n_rows, ctypes.byref(h),
+                                                          ctypes.byref(ms)))
+        t = FrLookup(self, h)
+        t.build_ms = ms.value
+        return t
+
+    def fr_lookup_info(self, table) -> dict:
+        return _fr_lookup_info(self, _fr_lookup_handle(table))
+
+    def fr_lookup_free(self, table):
+        self._check(_lib().msm_amd_fr_lookup_free(self.h, _fr_lookup_handle(table)))
+
+    def fr_lookup_multiplicities(self, table, data: bytes, on_missing=LOOKUP_STRICT, scalar_layout=SCALAR_MONT_LE, n_vec=1,
+                                 want_idx=True, n_rows=None, m_out=None):
+        """(m, idx or None, report) of n_vec columns of host records looked up in a table (msm_amd_fr_lookup_multiplicities):
+        m as n_rows records, idx as a list of row indices (LOOKUP_NOT_FOUND for a miss), report as a dict.  A miss under
+        LOOKUP_STRICT raises MsmError with .report and .idx set.  m_out: a ctypes buffer to write into (then m is None)."""
+        n = (len(data) // 32 // n_vec if n_vec else 0) if data is not None else 1   # None: the null pointer of an argument test
+        if n_rows is None:
+            n_rows = self.fr_lookup_info(table)["n_rows"]
+        m = ctypes.create_string_buffer(max(1, 32 * n_rows)) if m_out is None else m_out
+        idx = (c_uint32 * max(1, n * n_vec))() if want_idx else None
+        rep = (c_uint64 * 4)()
+        st = _lib().msm_amd_fr_lookup_multiplicities(self.h, _fr_lookup_handle(table), scalar_layout, on_missing, data, n,
+                                                     n_vec, m, idx, rep)
+        return _lookup_result(self, st, m if m_out is None else None, n_rows, idx, n * n_vec, rep)
+
+    def fr_lookup_multiplicities_device(self, table, d_in, n: int, d_m_out, d_idx_out=None, on_missing=LOOKUP_STRICT,
+                                        scalar_layout=SCALAR_MONT_LE, n_vec=1):
+        """The same on device-resident records (msm_amd_fr_lookup_multiplicities_device); returns (report, kernel_ms)."""
+        rep, ms = (c_uint64 * 4)(), c_float(0)
+        st = _lib().msm_amd_fr_lookup_multiplicities_device(self.h, _fr_lookup_handle(table), scalar_layout, on_missing,
+                                                            c_void_p(d_in), n, n_vec, c_void_p(d_m_out), c_void_p(d_idx_out),
+                                                            rep, ctypes.byref(ms))
+        return _lookup_result(self, st, None, 0, None, 0, rep)[2], ms.value
 
     # ---- polynomials over Fr: n_vec polynomials of n coefficients back to back, lowest degree first -------
     def fr_poly_eval(self, coeffs: bytes, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1) -> bytes:
@@ -1931,6 +2030,87 @@ def host_fr_prefix_product(data: bytes, mode=FR_PREFIX_INCLUSIVE, scalar_layout=
     if st != OK:
         raise MsmError(st)
     return out.raw[:32 * n * n_vec]
+
+
+def host_fr_prefix_sum(data: bytes, mode=FR_PREFIX_INCLUSIVE, scalar_layout=SCALAR_MONT_LE, n_vec=1, threads=0) -> bytes:
+    """Host twin of MsmConfig.fr_prefix_sum (no GPU)."""
+    n = len(data) // 32 // n_vec if n_vec else 0
+    out = ctypes.create_string_buffer(max(1, len(data)))
+    st = _lib().msm_amd_host_fr_prefix_sum(scalar_layout, mode, data, n, n_vec, threads, out)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:32 * n * n_vec]
+
+
+def host_fr_shift(a: bytes, k: bytes, scalar_layout=SCALAR_MONT_LE, threads=0) -> bytes:
+    """Host twin of MsmConfig.fr_shift (no GPU)."""
+    n = len(a) // 32 if a is not None else 0
+    out = ctypes.create_string_buffer(max(1, 32 * n))
+    st = _lib().msm_amd_host_fr_shift(scalar_layout, k, a, n, threads, out)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:32 * n]
+
+
+class FrLookup:
+    """A lookup table over Fr of one MsmConfig (msm_amd_fr_lookup_*)."""
+
+    def __init__(self, cfg, handle):
+        self.cfg, self.h, self.build_ms = cfg, handle, None
+
+    def info(self) -> dict:
+        return _fr_lookup_info(self.cfg, self.h)
+
+    def free(self):
+        self.cfg._check(_lib().msm_amd_fr_lookup_free(self.cfg.h, self.h))
+
+
+def _fr_lookup_handle(table):
+    return table.h if isinstance(table, (FrLookup, FrMatrix, NttDomain)) else table
+
+
+def _fr_lookup_info(cfg, handle) -> dict:
+    out = [c_size_t(0) for _ in range(5)]
+    cfg._check(_lib().msm_amd_fr_lookup_info(cfg.h, handle, *[ctypes.byref(v) for v in out]))
+    return dict(zip(("n_rows", "n_distinct", "capacity", "device_bytes", "longest_probe"), (v.value for v in out)))
+
+
+LOOKUP_REPORT_FIELDS = ("n_missing", "first_missing", "rows_hit", "max_multiplicity")
+
+
+def _lookup_result(cfg, st, m, n_rows, idx, total, rep):
+    """(m bytes or None, idx list or None, report dict) of a multiplicities call; a failed call raises MsmError, with
+    .report and .idx set when the failure is a miss under LOOKUP_STRICT"""
+    report = dict(zip(LOOKUP_REPORT_FIELDS, rep))
+    idx_list = list(idx[:total]) if idx is not None else None
+    if st != OK:
+        err = MsmError(st, _lib().msm_amd_last_error(cfg.h).decode() if cfg is not None else "")
+        err.report, err.idx = report, idx_list
+        raise err
+    return (m.raw[:32 * n_rows] if m is not None else None), idx_list, report
+
+
+def host_fr_lookup_multiplicities(table: bytes, data: bytes, on_missing=LOOKUP_STRICT, scalar_layout=SCALAR_MONT_LE, n_vec=1,
+                                  threads=0, want_idx=True, m_out=None):
+    """Host twin of MsmConfig.fr_lookup_build + fr_lookup_multiplicities (no GPU): (m, idx or None, report); m_out: a ctypes
+    buffer to write into (then m is None)."""
+    n_rows = len(table) // 32
+    n = len(data) // 32 // n_vec if n_vec else 0
+    m = ctypes.create_string_buffer(max(1, 32 * n_rows)) if m_out is None else m_out
+    idx = (c_uint32 * max(1, n * n_vec))() if want_idx else None
+    rep = (c_uint64 * 4)()
+    st = _lib().msm_amd_host_fr_lookup_multiplicities(scalar_layout, on_missing, table, n_rows, data, n, n_vec, threads, m, idx,
+                                                      rep)
+    return _lookup_result(None, st, m if m_out is None else None, n_rows, idx, n * n_vec, rep)
+
+
+def test_fr_lookup_plan(n_rows, hash_bits=32) -> dict:
+    """The index of a table of n_rows (msm_amd_test_fr_lookup_plan)"""
+    out = (c_uint64 * 4)()
+    st = _lib().msm_amd_test_fr_lookup_plan(n_rows, hash_bits, out)
+    if st != OK:
+        raise MsmError(st)
+    return dict(zip(("capacity", "bytes", "home_bits", "slots_off"), out))
 
 
 def host_fr_poly_eval(coeffs: bytes, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1, threads=0) -> bytes:

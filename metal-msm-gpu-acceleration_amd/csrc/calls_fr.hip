@@ -38,11 +38,31 @@ int fr_map_call(msm_amd_ctx* ctx, bool host, int op, int scalar_layout, const vo
   });
 }
 
-int fr_prefix_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int mode, const void* in, size_t n, size_t n_vec, void* out,
-                   float* kernel_ms) {
+int fr_shift_call(msm_amd_ctx* ctx, bool host, int scalar_layout, const void* k32, const void* a, size_t n, void* out,
+                  float* kernel_ms) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
   DeviceCall d;
-  d.who = host ? "msm_amd_fr_prefix_product" : "msm_amd_fr_prefix_product_device";
+  d.who = host ? "msm_amd_fr_shift" : "msm_amd_fr_shift_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_shift_check(scalar_layout, k32, a, n, out, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = a, d.in_bytes[0] = n * 32;
+  d.out = out, d.out_bytes = n * 32;
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    launch_fr_shift(st, scalar_layout, fr_read_record(scalar_layout, k32), io.in[0], n, io.out);
+    return MSM_AMD_OK;
+  });
+}
+
+// msm_amd_fr_prefix_product* and (sum) msm_amd_fr_prefix_sum*
+int fr_prefix_call(msm_amd_ctx* ctx, bool host, bool sum, int scalar_layout, int mode, const void* in, size_t n, size_t n_vec,
+                   void* out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = std::string(sum ? "msm_amd_fr_prefix_sum" : "msm_amd_fr_prefix_product") + (host ? "" : "_device");
   if (kernel_ms) *kernel_ms = 0.f;
   if (!fr_mode_known(mode))
     return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": mode must be MSM_AMD_FR_PREFIX_INCLUSIVE or MSM_AMD_FR_PREFIX_EXCLUSIVE");
@@ -52,7 +72,7 @@ int fr_prefix_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int mode, con
   std::lock_guard<std::mutex> lk(ctx->mu);
   CallState& s = ctx->calls;
   FrScanLaunch c{};
-  c.n = n, c.n_vec = n_vec, c.tile_log = ctx->fr_tile_log, c.layout = scalar_layout, c.mode = mode;
+  c.n = n, c.n_vec = n_vec, c.tile_log = ctx->fr_tile_log, c.layout = scalar_layout, c.mode = mode, c.sum = sum;
   d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
   d.in[0] = in, d.in_bytes[0] = n * n_vec * 32;
   d.out = out, d.out_bytes = n * n_vec * 32;
@@ -221,12 +241,205 @@ int msm_amd_fr_batch_inverse_device(msm_amd_ctx* ctx, int scalar_layout, const v
 
 int msm_amd_fr_prefix_product(msm_amd_ctx* ctx, int scalar_layout, int mode, const void* in, size_t n, size_t n_vec,
                               void* out) {
-  return fr_prefix_call(ctx, true, scalar_layout, mode, in, n, n_vec, out, nullptr);
+  return fr_prefix_call(ctx, true, false, scalar_layout, mode, in, n, n_vec, out, nullptr);
 }
 
 int msm_amd_fr_prefix_product_device(msm_amd_ctx* ctx, int scalar_layout, int mode, const void* d_in, size_t n, size_t n_vec,
                                      void* d_out, float* kernel_ms) {
-  return fr_prefix_call(ctx, false, scalar_layout, mode, d_in, n, n_vec, d_out, kernel_ms);
+  return fr_prefix_call(ctx, false, false, scalar_layout, mode, d_in, n, n_vec, d_out, kernel_ms);
+}
+
+int msm_amd_fr_prefix_sum(msm_amd_ctx* ctx, int scalar_layout, int mode, const void* in, size_t n, size_t n_vec, void* out) {
+  return fr_prefix_call(ctx, true, true, scalar_layout, mode, in, n, n_vec, out, nullptr);
+}
+
+int msm_amd_fr_prefix_sum_device(msm_amd_ctx* ctx, int scalar_layout, int mode, const void* d_in, size_t n, size_t n_vec,
+                                 void* d_out, float* kernel_ms) {
+  return fr_prefix_call(ctx, false, true, scalar_layout, mode, d_in, n, n_vec, d_out, kernel_ms);
+}
+
+int msm_amd_fr_shift(msm_amd_ctx* ctx, int scalar_layout, const void* k32, const void* a, size_t n, void* out) {
+  return fr_shift_call(ctx, true, scalar_layout, k32, a, n, out, nullptr);
+}
+
+int msm_amd_fr_shift_device(msm_amd_ctx* ctx, int scalar_layout, const void* k32, const void* d_a, size_t n, void* d_out,
+                            float* kernel_ms) {
+  return fr_shift_call(ctx, false, scalar_layout, k32, d_a, n, d_out, kernel_ms);
+}
+
+}  // extern "C"
+
+// ---- lookup tables over Fr (msm_amd_fr_lookup_*) ------------------------------------------------------------------------------
+// A handle is validated by membership in ctx->live_fr_lookup, under the lock.  The build has one bounded wait (that of
+// handle_build_tail): the statistics of the index come back with it through the page-locked record of CallState.  A
+// multiplicities call is a device_call whose 64-byte record is the report: the counters and the report live in
+// CallState::work, the finish kernel reads the miss counter on the device, and the device form is done after the one wait
+// for its record.  The host form stages m in CallState::out and the row indices behind the report, and copies them back
+// in a second span -- m only if the call does not fail for a miss, so that the caller's m_out stays untouched then.
+namespace {
+
+const char* const kNotLookup = ": not a lookup table handle of this ctx";
+
+int fr_lookup_build_call(msm_amd_ctx* ctx, bool host, int scalar_layout, const void* table, size_t n_rows,
+                         msm_amd_fr_lookup** out, float* kernel_ms) {
+  const std::string who = host ? "msm_amd_fr_lookup_build" : "msm_amd_fr_lookup_build_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (!ctx || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": null pointer");
+  *out = nullptr;
+  if (const char* why = fr_lookup_table_check(scalar_layout, table, n_rows, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": " + why);
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = recover_if_stalled(ctx)) return rc;
+  const FrLookupPlan plan = fr_lookup_plan(n_rows, fr_lookup_hash_bits_knob());
+  CallState& s = ctx->calls;
+  if (!s.h_record) HIP_TRY(ctx, hipHostMalloc((void**)&s.h_record, sizeof(PointCounters), hipHostMallocDefault));
+  if (kernel_ms)
+    for (int k = 0; k < 2; ++k)
+      if (!s.ev[k]) HIP_TRY(ctx, hipEventCreate(&s.ev[k]));
+  std::vector<u256> rows;   // host form: the residues are formed here and uploaded into the image
+  if (host) {
+    rows.resize(n_rows);
+    for (size_t j = 0; j < n_rows; ++j) rows[j] = fr_read_record(scalar_layout, (const uint8_t*)table + j * 32);
+  }
+  int up = MSM_AMD_OK;
+  hipError_t tail = hipSuccess;
+  if (int rc = handle_build_tail(
+          ctx, ctx->live_fr_lookup, plan.bytes, "a lookup table", "lookup table build",
+          [&](void* d_mem) {
+            hipStream_t st = ctx->stream;
+            if (host && (up = staged_upload(ctx, (uint8_t*)d_mem + plan.rows_off, rows.data(), n_rows * 32, st))) return;
+            if (kernel_ms) tail = hipEventRecord(s.ev[0], st);
+            launch_fr_lookup_build(st, plan, n_rows, scalar_layout, host ? nullptr : table, d_mem);
+            if (kernel_ms && tail == hipSuccess) tail = hipEventRecord(s.ev[1], st);
+            if (tail == hipSuccess)
+              tail = hipMemcpyAsync(s.h_record, (const uint8_t*)d_mem + plan.stats_off, kLookupStatWords * 4,
+                                    hipMemcpyDeviceToHost, st);
+          },
+          out))
+    return rc;
+  msm_amd_fr_lookup* h = *out;
+  uint32_t stats[kLookupStatWords];
+  std::memcpy(stats, s.h_record, sizeof stats);
+  std::string why;
+  if (up) why = ctx->last_error;
+  else if (tail != hipSuccess) why = hipGetErrorString(tail), up = MSM_AMD_PIPELINE_ERROR;
+  else if (stats[kLookupError]) why = "an insert ran through every slot of the index", up = MSM_AMD_PIPELINE_ERROR;
+  if (up) {   // nothing may read the allocation
+    *out = nullptr;
+    handle_free(ctx, ctx->live_fr_lookup, h, "");
+    return fail(ctx, up, who + ": " + why);
+  }
+  if (kernel_ms) *kernel_ms = event_span(s.ev[0], s.ev[1]);
+  h->n_rows = n_rows, h->n_distinct = stats[kLookupDistinct], h->longest_probe = stats[kLookupLongest], h->plan = plan;
+  return MSM_AMD_OK;
+}
+
+int fr_lookup_mult_call(msm_amd_ctx* ctx, const msm_amd_fr_lookup* handle, bool host, int scalar_layout, int on_missing,
+                        const void* in, size_t n, size_t n_vec, void* m_out, uint32_t* idx_out, uint64_t* report,
+                        float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = host ? "msm_amd_fr_lookup_multiplicities" : "msm_amd_fr_lookup_multiplicities_device";
+  if (kernel_ms) *kernel_ms = 0.f;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_fr_lookup* t = find_handle(ctx->live_fr_lookup, handle);
+  if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + kNotLookup);
+  if (const char* why = fr_lookup_call_check(scalar_layout, on_missing, t->n_rows, in, n, n_vec, m_out, idx_out, report, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  const size_t total = n * n_vec;
+  if (!host) {
+    const uintptr_t lo = (uintptr_t)t->d_mem, hi = lo + t->bytes, a = (uintptr_t)m_out, b = (uintptr_t)idx_out;
+    if ((a < hi && lo < a + t->n_rows * 32) || (idx_out && b < hi && lo < b + total * 4))
+      return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": d_m_out and d_idx_out must not overlap the table");
+  }
+  CallState& s = ctx->calls;
+  FrLookupLaunch c{};
+  c.image = t->d_mem, c.plan = t->plan, c.n_rows = t->n_rows, c.layout = scalar_layout, c.on_missing = on_missing;
+  c.count_form = fr_lookup_count_knob(), c.total = total;
+  c.at = fr_lookup_work(t->n_rows, host && idx_out ? total : 0);
+  d.host_in = host && total ? 1u : 0u, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = total * 32;
+  d.work[0] = {&s.work, (size_t)c.at.bytes};
+  if (host) d.work[1] = {&s.out, (size_t)t->n_rows * 32};
+  uint64_t rep[kLookupReportWords] = {};
+  auto launch = [&](hipStream_t st, CallIo& io) {
+    uint8_t* work = (uint8_t*)s.work.p;
+    c.in = io.in[0], c.work = work, c.m_out = host ? s.out.p : m_out;
+    c.idx_out = !idx_out || !total ? nullptr : host ? (uint32_t*)(work + c.at.idx_off) : idx_out;
+    launch_fr_lookup_multiplicities(st, c);
+    io.record = work + c.at.report_off;
+    return MSM_AMD_OK;
+  };
+  auto then = [&](const uint8_t* record, float) { std::memcpy(rep, record, sizeof rep); };
+  auto strict_miss = [&] { return on_missing == kLookupStrict && total && rep[kLookupMissing] != 0; };
+  int rc;
+  if (host)
+    rc = device_call(ctx, d, launch, then, [&](hipStream_t st, const CallIo&) -> int {
+      const uint8_t* work = (const uint8_t*)s.work.p;
+      if (c.idx_out) HIP_TRY(ctx, hipMemcpyAsync(idx_out, work + c.at.idx_off, total * 4, hipMemcpyDeviceToHost, st));
+      if (!strict_miss() && !rep[kLookupReportError])
+        HIP_TRY(ctx, hipMemcpyAsync(m_out, s.out.p, t->n_rows * 32, hipMemcpyDeviceToHost, st));
+      return MSM_AMD_OK;
+    });
+  else
+    rc = device_call(ctx, d, launch, then);
+  if (rc) return rc;
+  if (rep[kLookupReportError])
+    return fail(ctx, MSM_AMD_PIPELINE_ERROR, d.who + ": a probe ran through every slot of the index");
+  for (int k = 0; k < 4; ++k) report[k] = total ? rep[k] : 0;
+  if (strict_miss())
+    return fail(ctx, MSM_AMD_INPUT_ERROR,
+                d.who + ": " + std::to_string(rep[kLookupMissing]) + " of " + std::to_string(total) +
+                    " inputs are not in the table, the first at flat index " + std::to_string(rep[kLookupFirstMissing]) +
+                    " (MSM_AMD_LOOKUP_STRICT; m_out is untouched)");
+  return MSM_AMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_fr_lookup_build(msm_amd_ctx* ctx, int scalar_layout, const void* table, size_t n_rows, msm_amd_fr_lookup** out) {
+  return fr_lookup_build_call(ctx, true, scalar_layout, table, n_rows, out, nullptr);
+}
+
+int msm_amd_fr_lookup_build_device(msm_amd_ctx* ctx, int scalar_layout, const void* d_table, size_t n_rows,
+                                   msm_amd_fr_lookup** out, float* kernel_ms) {
+  return fr_lookup_build_call(ctx, false, scalar_layout, d_table, n_rows, out, kernel_ms);
+}
+
+int msm_amd_fr_lookup_info(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, size_t* n_rows, size_t* n_distinct,
+                           size_t* capacity, size_t* device_bytes, size_t* longest_probe) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_fr_lookup* t = find_handle(ctx->live_fr_lookup, lookup);
+  if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, std::string("msm_amd_fr_lookup_info") + kNotLookup);
+  if (n_rows) *n_rows = t->n_rows;
+  if (n_distinct) *n_distinct = t->n_distinct;
+  if (capacity) *capacity = t->plan.capacity;
+  if (device_bytes) *device_bytes = t->bytes;
+  if (longest_probe) *longest_probe = t->longest_probe;
+  return MSM_AMD_OK;
+}
+
+int msm_amd_fr_lookup_free(msm_amd_ctx* ctx, msm_amd_fr_lookup* lookup) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return handle_free(ctx, ctx->live_fr_lookup, lookup, "msm_amd_fr_lookup_free: not a lookup table handle of this ctx");
+}
+
+int msm_amd_fr_lookup_multiplicities(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, int scalar_layout, int on_missing,
+                                     const void* in, size_t n, size_t n_vec, void* m_out, uint32_t* idx_out,
+                                     uint64_t report[4]) {
+  return fr_lookup_mult_call(ctx, lookup, true, scalar_layout, on_missing, in, n, n_vec, m_out, idx_out, report, nullptr);
+}
+
+int msm_amd_fr_lookup_multiplicities_device(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, int scalar_layout,
+                                            int on_missing, const void* d_in, size_t n, size_t n_vec, void* d_m_out,
+                                            uint32_t* d_idx_out, uint64_t report[4], float* kernel_ms) {
+  return fr_lookup_mult_call(ctx, lookup, false, scalar_layout, on_missing, d_in, n, n_vec, d_m_out, d_idx_out, report,
+                             kernel_ms);
 }
 
 }  // extern "C"

@@ -34,6 +34,7 @@ constexpr uint32_t kFrMapThreads = 256;
 constexpr uint32_t kFrMaxLevels = 16;      // n < 2^32 at tiles of 4
 constexpr int kFrRaw = -1;                 // layout of the tile totals: reduced Montgomery residues, no conversion
 enum { kFrAdd = 0, kFrSub, kFrMul, kFrScale, kFrAxpy, kFrMulsubScale, kFrOps };
+constexpr int kFrShift = kFrOps;           // a + k (msm_amd_fr_shift*): a kernel of the map, no op of msm_amd_fr_map (it reads 0)
 constexpr int kFrInclusive = 0, kFrExclusive = 1;
 constexpr unsigned kFrReadsA = 1, kFrReadsB = 2, kFrReadsC = 4, kFrReadsK = 8;
 
@@ -56,8 +57,15 @@ MSM_HD u256 fr_map_op(const u256& k, const u256& a, const u256& b, const u256& c
   if (OP == kFrMul) return Fr::mul(a, b);
   if (OP == kFrScale) return Fr::mul(k, a);
   if (OP == kFrAxpy) return Fr::add(a, Fr::mul(k, b));
+  if (OP == kFrShift) return Fr::add(a, k);
   return Fr::mul(k, Fr::sub(Fr::mul(a, b), c));
 }
+
+// The monoid of a scan: the products of msm_amd_fr_prefix_product*, or (SUM) the sums of msm_amd_fr_prefix_sum*
+template <bool SUM>
+MSM_HD u256 fr_scan_unit() { return SUM ? u256_zero() : Fr::one(); }
+template <bool SUM>
+MSM_HD u256 fr_scan_op(const u256& a, const u256& b) { return SUM ? Fr::add(a, b) : Fr::mul(a, b); }
 
 MSM_HD u256 fr_load(int layout, const u256& rec) { return layout == kFrRaw ? rec : ntt_load(layout, rec.v); }
 MSM_HD u256 fr_store(int layout, const u256& x) {

@@ -208,6 +208,13 @@ struct msm_amd_poseidon_params : DeviceHandle {
   uint32_t t = 0, r_f = 0, r_p = 0;
 };
 
+// A lookup table over Fr (msm_amd_fr_lookup_*, msm_amd_ctx::live_fr_lookup): d_mem is the image of fr_lookup_plan -- the
+// rows as reduced Montgomery residues, the slots of the index, the statistics of the build.
+struct msm_amd_fr_lookup : DeviceHandle {
+  uint64_t n_rows = 0, n_distinct = 0, longest_probe = 0;
+  FrLookupPlan plan{};
+};
+
 // Buffers of the blocking vector calls (device_call.h): the staging of the host-buffer forms, the 64-byte record a
 // call reads back with its page-locked copy (the PointCounters of a check, decompress or compress call; T and the zero
 // count of a batch inversion), the device-side work buffers and two pairs of events behind kernel_ms.  Every such call
@@ -349,6 +356,7 @@ struct msm_amd_ctx {
   Stager stager;
   Uploader uploader;
   int staged_uploads = -1;   // -1 = decide by the runtime version (stage_pageable()), 0 / 1 = MSM_AMD_STAGED_UPLOAD
+  std::vector<msm_amd_fr_lookup*> live_fr_lookup;   // last: every member above keeps its place
 };
 
 namespace msm_amd {
@@ -377,8 +385,8 @@ int staged_upload(msm_amd_ctx* ctx, void* d_dst, const void* h_src, size_t bytes
   } while (0)
 
 // ---- handles: H = msm_amd_tables (ctx->live_tables), msm_amd_g2_tables (ctx->live_g2_tables), msm_amd_ntt_domain
-// (ctx->live_ntt), msm_amd_fr_matrix (ctx->live_fr_mat) or msm_amd_poseidon_params (ctx->live_poseidon).  ctx->mu is held by
-// the caller, as for every helper here.
+// (ctx->live_ntt), msm_amd_fr_matrix (ctx->live_fr_mat), msm_amd_poseidon_params (ctx->live_poseidon) or msm_amd_fr_lookup
+// (ctx->live_fr_lookup).  ctx->mu is held by the caller, as for every helper here.
 template <class H>
 const H* find_handle(const std::vector<H*>& live, const void* handle) {
   for (const H* t : live)

@@ -68,6 +68,16 @@ const char* fr_unary_check(int scalar_layout, const void* in, uint64_t n, uint64
   return nullptr;
 }
 
+const char* fr_shift_check(int scalar_layout, const void* k32, const void* a, uint64_t n, const void* out, bool device) {
+  if (!fr_layout_known(scalar_layout)) return "scalars in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE only";
+  if (n >> 32) return "n >= 2^32";
+  if (n == 0) return nullptr;
+  if (!k32 || !a || !out) return "null pointer with n > 0";
+  if (device && (((uintptr_t)a | (uintptr_t)out) & 15u)) return "device buffers must be 16-byte aligned";
+  if (!fr_overlap_ok(out, a, n * 32)) return "the output must be the input itself or disjoint from it";
+  return nullptr;
+}
+
 u256 fr_read_record(int scalar_layout, const void* rec32) {
   uint32_t rec[8];
   std::memcpy(rec, rec32, 32);
@@ -336,7 +346,9 @@ int host_fr_batch_inverse(int layout, const void* in_v, size_t n, int threads, v
   return MSM_AMD_OK;
 }
 
-int host_fr_prefix_product(int layout, int mode, const void* in_v, size_t n, size_t n_vec, int threads, void* out_v) {
+// SUM: the running sums of msm_amd_host_fr_prefix_sum (fr_scan_op); "product" below reads "sum" then
+template <bool SUM>
+int host_fr_prefix(int layout, int mode, const void* in_v, size_t n, size_t n_vec, int threads, void* out_v) {
   if (!fr_mode_known(mode) || fr_unary_check(layout, in_v, n, n_vec, out_v, false)) return MSM_AMD_INPUT_ERROR;
   if (n == 0 || n_vec == 0) return MSM_AMD_OK;
   const uint8_t* in = (const uint8_t*)in_v;
@@ -344,29 +356,36 @@ int host_fr_prefix_product(int layout, int mode, const void* in_v, size_t n, siz
   const size_t total = n * n_vec;
   const unsigned T = worker_count(threads, total);
   // phase 1: per range, the product of its records from the last start of a vector in it (or from its first record)
-  std::vector<u256> tail(T, Fr::one());
+  std::vector<u256> tail(T, fr_scan_unit<SUM>());
   std::vector<char> restarts(T, 0);
   for_ranges(T, total, [&](unsigned t, size_t lo, size_t hi) {
-    u256 acc = Fr::one();
+    u256 acc = fr_scan_unit<SUM>();
     for (size_t i = lo; i < hi; ++i) {
-      if (i % n == 0) acc = Fr::one(), restarts[t] = 1;
-      acc = Fr::mul(acc, host_get(layout, in, i));
+      if (i % n == 0) acc = fr_scan_unit<SUM>(), restarts[t] = 1;
+      acc = fr_scan_op<SUM>(acc, host_get(layout, in, i));
     }
     tail[t] = acc;
   });
   // the product before the first record of every range
-  std::vector<u256> carry(T, Fr::one());
-  for (unsigned t = 1; t < T; ++t) carry[t] = restarts[t - 1] ? tail[t - 1] : Fr::mul(carry[t - 1], tail[t - 1]);
+  std::vector<u256> carry(T, fr_scan_unit<SUM>());
+  for (unsigned t = 1; t < T; ++t) carry[t] = restarts[t - 1] ? tail[t - 1] : fr_scan_op<SUM>(carry[t - 1], tail[t - 1]);
   // phase 2
   for_ranges(T, total, [&](unsigned t, size_t lo, size_t hi) {
     u256 run = carry[t];
     for (size_t i = lo; i < hi; ++i) {
-      if (i % n == 0) run = Fr::one();
-      const u256 nxt = Fr::mul(run, host_get(layout, in, i));
+      if (i % n == 0) run = fr_scan_unit<SUM>();
+      const u256 nxt = fr_scan_op<SUM>(run, host_get(layout, in, i));
       host_put(layout, out, i, mode == kFrInclusive ? nxt : run);
       run = nxt;
     }
   });
+  return MSM_AMD_OK;
+}
+
+int host_fr_shift(int layout, const void* k32, const void* a_v, size_t n, int threads, void* out_v) {
+  if (fr_shift_check(layout, k32, a_v, n, out_v, false)) return MSM_AMD_INPUT_ERROR;
+  if (n == 0) return MSM_AMD_OK;
+  host_map_op<kFrShift>(layout, fr_read_record(layout, k32), (const uint8_t*)a_v, nullptr, nullptr, n, threads, (uint8_t*)out_v);
   return MSM_AMD_OK;
 }
 
@@ -702,7 +721,15 @@ int msm_amd_host_fr_batch_inverse(int scalar_layout, const void* in, size_t n, i
 
 int msm_amd_host_fr_prefix_product(int scalar_layout, int mode, const void* in, size_t n, size_t n_vec, int threads,
                                    void* out) {
-  return msm_amd::host_fr_prefix_product(scalar_layout, mode, in, n, n_vec, threads, out);
+  return msm_amd::host_fr_prefix<false>(scalar_layout, mode, in, n, n_vec, threads, out);
+}
+
+int msm_amd_host_fr_prefix_sum(int scalar_layout, int mode, const void* in, size_t n, size_t n_vec, int threads, void* out) {
+  return msm_amd::host_fr_prefix<true>(scalar_layout, mode, in, n, n_vec, threads, out);
+}
+
+int msm_amd_host_fr_shift(int scalar_layout, const void* k32, const void* a, size_t n, int threads, void* out) {
+  return msm_amd::host_fr_shift(scalar_layout, k32, a, n, threads, out);
 }
 
 int msm_amd_test_fr_plan(size_t n, size_t n_vec, uint32_t tile_log, uint64_t out[4]) {

@@ -1,6 +1,8 @@
 // Kernels over vectors of BN254 Fr (fr_vec.hip.h):
 //   fr_map_kernel<OP>      one lane per record, consecutive lanes on consecutive records: load (to_mont for CANON_LE), the
 //                          op, store (from_mont for CANON_LE).  k arrives by value.
+//   (the two tile kernels are templates on the monoid: <false> the products, <true> the sums of msm_amd_fr_prefix_sum*,
+//   where "product" below reads "sum" and "one" reads "zero"; fr_map_kernel<kFrShift> is a + k)
 //   fr_tile_reduce_kernel  one wave per tile: every lane multiplies the records lane, lane + 64, ... of the tile, six
 //                          shuffle steps fold the 64 lane products; the inversion's form reads a zero as one and counts it.
 //   fr_tile_scan_kernel    one wave per tile: the tile goes to LDS at unit stride, lane t owns the 2^(T-6) consecutive
@@ -175,30 +177,32 @@ __global__ void __launch_bounds__(kFrMapThreads) fr_map_kernel(int layout, u256 
   store_rec(out + i * 8, fr_store(layout, fr_map_op<OP>(k, a, b, c)));
 }
 
+template <bool SUM>
 __global__ void __launch_bounds__(kFrWave) fr_tile_reduce_kernel(FrTileArgs a) {
   const uint32_t lane = threadIdx.x;
   const TilePlace t = tile_place(blockIdx.x, a.len, a.tiles, a.tile_log);
-  u256 acc = Fr::one();
+  u256 acc = fr_scan_unit<SUM>();
   uint32_t zc = 0;
   NTT_NO_UNROLL for (uint32_t m = lane; m < t.cnt; m += kFrWave) {
     u256 x = fr_load(a.layout, load_rec(a.src + tile_record(t, a.len, a.reverse, m) * 8));
-    if (a.zero_one) {
+    if (!SUM && a.zero_one) {
       const bool z = u256_is_zero(x);
       zc += z ? 1u : 0u;
       x = fr_select(z, Fr::one(), x);
     }
-    acc = Fr::mul(acc, x);
+    acc = fr_scan_op<SUM>(acc, x);
   }
   NTT_NO_UNROLL for (uint32_t d = kFrWave / 2; d != 0; d >>= 1) {
-    acc = Fr::mul(acc, wave_xor(acc, d));
+    acc = fr_scan_op<SUM>(acc, wave_xor(acc, d));
     zc += (uint32_t)__shfl_xor((int)zc, (int)d);
   }
   if (lane == 0) {
     store_rec(a.totals + (uint64_t)blockIdx.x * 8, acc);
-    if (a.zero_one && zc) atomicAdd(a.zeros, (unsigned long long)zc);
+    if (!SUM && a.zero_one && zc) atomicAdd(a.zeros, (unsigned long long)zc);
   }
 }
 
+template <bool SUM>
 __global__ void __launch_bounds__(kFrWave) fr_tile_scan_kernel(FrTileArgs a) {
   extern __shared__ uint32_t fr_lds[];
   const Image lds = image(fr_lds, a.tile_log);
@@ -211,22 +215,23 @@ __global__ void __launch_bounds__(kFrWave) fr_tile_scan_kernel(FrTileArgs a) {
   __syncthreads();
 
   // the product of the lane's records; lane 0 carries the product before the tile
-  const u256 carry = a.carry ? load_rec(a.carry + (uint64_t)blockIdx.x * 8) : Fr::one();
-  u256 acc = fr_select(lane == 0, carry, Fr::one());
+  const u256 unit = fr_scan_unit<SUM>();
+  const u256 carry = a.carry ? load_rec(a.carry + (uint64_t)blockIdx.x * 8) : unit;
+  u256 acc = fr_select(lane == 0, carry, unit);
   NTT_NO_UNROLL for (uint32_t j = 0; j < per; ++j) {
     if (m0 + j >= t.cnt) break;
-    acc = Fr::mul(acc, lds_get(lds, m0 + j));
+    acc = fr_scan_op<SUM>(acc, lds_get(lds, m0 + j));
   }
   NTT_NO_UNROLL for (uint32_t d = 1; d < kFrWave; d <<= 1) {
     const u256 y = wave_up(acc, d);
-    acc = Fr::mul(acc, fr_select(lane >= d, y, Fr::one()));
+    acc = fr_scan_op<SUM>(acc, fr_select(lane >= d, y, unit));
   }
   // the product before the lane's first record, then the running products
   u256 run = fr_select(lane == 0, carry, wave_up(acc, 1));
   NTT_NO_UNROLL for (uint32_t j = 0; j < per; ++j) {
     const uint32_t m = m0 + j;
     if (m >= t.cnt) break;
-    const u256 nxt = Fr::mul(run, lds_get(lds, m));
+    const u256 nxt = fr_scan_op<SUM>(run, lds_get(lds, m));
     lds_put(lds, m, a.mode == kFrInclusive ? nxt : run);
     run = nxt;
   }
@@ -654,11 +659,15 @@ void launch_map_op(hipStream_t st, int layout, const u256& k, const void* a, con
                      layout, k, (const uint32_t*)a, (const uint32_t*)b, (const uint32_t*)c, (uint64_t)n, (uint32_t*)out);
 }
 
-void launch_reduce(hipStream_t st, const FrTileArgs& a, uint64_t n_vec) {
-  hipLaunchKernelGGL(fr_tile_reduce_kernel, dim3((uint32_t)(a.tiles * n_vec)), dim3(kFrWave), 0, st, a);
+void launch_reduce(hipStream_t st, const FrTileArgs& a, uint64_t n_vec, bool sum) {
+  const dim3 grid((uint32_t)(a.tiles * n_vec));
+  if (sum) hipLaunchKernelGGL(fr_tile_reduce_kernel<true>, grid, dim3(kFrWave), 0, st, a);
+  else hipLaunchKernelGGL(fr_tile_reduce_kernel<false>, grid, dim3(kFrWave), 0, st, a);
 }
-void launch_scan(hipStream_t st, const FrTileArgs& a, uint64_t n_vec) {
-  hipLaunchKernelGGL(fr_tile_scan_kernel, dim3((uint32_t)(a.tiles * n_vec)), dim3(kFrWave), fr_image_bytes(a.tile_log), st, a);
+void launch_scan(hipStream_t st, const FrTileArgs& a, uint64_t n_vec, bool sum) {
+  const dim3 grid((uint32_t)(a.tiles * n_vec));
+  if (sum) hipLaunchKernelGGL(fr_tile_scan_kernel<true>, grid, dim3(kFrWave), fr_image_bytes(a.tile_log), st, a);
+  else hipLaunchKernelGGL(fr_tile_scan_kernel<false>, grid, dim3(kFrWave), fr_image_bytes(a.tile_log), st, a);
 }
 
 }  // namespace
@@ -675,6 +684,10 @@ void launch_fr_map(hipStream_t st, int op, int layout, const u256& k, const void
   }
 }
 
+void launch_fr_shift(hipStream_t st, int layout, const u256& k, const void* a, size_t n, void* out) {
+  launch_map_op<kFrShift>(st, layout, k, a, nullptr, nullptr, n, out);
+}
+
 uint32_t launch_fr_scan(hipStream_t st, const FrScanLaunch& c) {
   const FrScanPlan plan = fr_scan_plan(c.n, c.n_vec, c.tile_log);
   uint32_t* work = (uint32_t*)c.work;
@@ -689,8 +702,8 @@ uint32_t launch_fr_scan(hipStream_t st, const FrScanLaunch& c) {
     if (k + 1 < plan.levels) a.carry = a.totals = work + plan.offset[k + 1] * 8;
     return a;
   };
-  for (uint32_t k = 0; k + 1 < plan.levels; ++k) launch_reduce(st, level(k), c.n_vec);
-  for (uint32_t k = plan.levels; k-- != 0;) launch_scan(st, level(k), c.n_vec);
+  for (uint32_t k = 0; k + 1 < plan.levels; ++k) launch_reduce(st, level(k), c.n_vec, c.sum);
+  for (uint32_t k = plan.levels; k-- != 0;) launch_scan(st, level(k), c.n_vec, c.sum);
   return plan.launches;
 }
 
@@ -920,7 +933,7 @@ uint32_t launch_fr_inv_products(hipStream_t st, int layout, const void* in, uint
   FrTileArgs a{};
   a.src = (const uint32_t*)in, a.totals = work + ip.t_off * 8, a.zeros = (unsigned long long*)count;
   a.len = n, a.tiles = ip.tiles, a.tile_log = ip.tile_log, a.layout = layout, a.zero_one = 1;
-  launch_reduce(st, a, 1);
+  launch_reduce(st, a, 1, false);
   FrScanLaunch s{};
   s.in = work + ip.t_off * 8, s.work = work + ip.scan_off * 8;
   s.n = ip.tiles, s.n_vec = 1, s.tile_log = tile_log, s.layout = kFrRaw, s.mode = kFrInclusive;

@@ -1,10 +1,11 @@
-// Launch wrappers of the Fr vector kernels (k_fr.hip) for the host driver (msm_host.hip), and the argument checks the
-// driver shares with the host twin (host_fr.hip).
+// Launch wrappers of the Fr vector kernels (k_fr.hip; the lookup tables: k_lookup.hip) for the host driver (calls_fr.hip),
+// and the argument checks the driver shares with the host twins (host_fr.hip, host_lookup.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 
+#include "fr_lookup.hip.h"
 #include "fr_mat.hip.h"
 #include "fr_mle.hip.h"
 #include "fr_poseidon.hip.h"
@@ -15,6 +16,8 @@ namespace msm_amd {
 // out[i] = op(k, a[i], b[i], c[i]), i < n; k Montgomery and reduced; operands the op does not read may be null
 void launch_fr_map(hipStream_t st, int op, int layout, const u256& k, const void* a, const void* b, const void* c, size_t n,
                    void* out);
+// out[i] = a[i] + k, i < n; one more instantiation of the map kernel
+void launch_fr_shift(hipStream_t st, int layout, const u256& k, const void* a, size_t n, void* out);
 
 struct FrScanLaunch {
   const void* in;     // n_vec * n records; in == out is allowed
@@ -25,6 +28,7 @@ struct FrScanLaunch {
   int layout;         // of in and out: a scalar layout, or kFrRaw
   int mode;           // kFrInclusive, kFrExclusive
   bool reverse;       // the suffix products: every vector is scanned from its last record down
+  bool sum;           // the running sums (msm_amd_fr_prefix_sum*): the same plan over addition, an exclusive scan starts at 0
 };
 // every launch of one scan, in stream order; returns the number of launches
 uint32_t launch_fr_scan(hipStream_t st, const FrScanLaunch& c);
@@ -133,6 +137,25 @@ uint32_t launch_poseidon_tree(hipStream_t st, const PoseidonLaunch& c, const voi
 void launch_merkle_paths(hipStream_t st, int layout, uint32_t arity, uint32_t depth, const void* leaves, uint64_t n_leaves,
                          const void* tree, const void* idx, uint64_t n_idx, void* out);
 
+// Lookup tables (fr_lookup.hip.h).  The build fills the slots and the statistics of an image whose rows are there already
+// (d_table null: uploaded as residues) or come from d_table, n_rows records of `layout` in device memory.
+void launch_fr_lookup_build(hipStream_t st, const FrLookupPlan& plan, uint64_t n_rows, int layout, const void* d_table,
+                            void* image);
+struct FrLookupLaunch {
+  const void* image;   // the device allocation of the handle
+  FrLookupPlan plan;
+  uint64_t n_rows;
+  int layout, on_missing, count_form;
+  const void* in;      // total records
+  uint64_t total;      // n * n_vec; may be 0
+  void* m_out;         // n_rows records
+  uint32_t* idx_out;   // optional: total words
+  void* work;          // fr_lookup_work: counters and report, cleared by the launch
+  FrLookupWork at;
+};
+// the clears, the probe launch (if there are inputs) and the finish launch, in stream order; returns the number of kernels
+uint32_t launch_fr_lookup_multiplicities(hipStream_t st, const FrLookupLaunch& c);
+
 // host_fr.hip.  Each check returns null or what is wrong, for msm_amd_last_error.
 bool fr_layout_known(int scalar_layout);   // MONT_LE and CANON_LE
 bool fr_mode_known(int mode);
@@ -151,6 +174,16 @@ const char* fr_poly_check(int scalar_layout, const void* z32, const void* in, ui
 const char* fr_lincomb_check(int scalar_layout, const void* k32, const void* a, uint64_t n, uint64_t n_vec, const void* out,
                              bool device);
 const char* fr_unary_check(int scalar_layout, const void* in, uint64_t n, uint64_t n_vec, const void* out, bool device);
+// msm_amd_fr_shift*: out is a itself or disjoint from it
+const char* fr_shift_check(int scalar_layout, const void* k32, const void* a, uint64_t n, const void* out, bool device);
+// host_lookup.hip.  A table: 1 <= n_rows < 2^31
+const char* fr_lookup_table_check(int scalar_layout, const void* table, uint64_t n_rows, bool device);
+// msm_amd_fr_lookup_multiplicities*: layout and mode first, then the sizes; n == 0 or n_vec == 0 needs m_out only
+const char* fr_lookup_call_check(int scalar_layout, int on_missing, uint64_t n_rows, const void* in, uint64_t n, uint64_t n_vec,
+                                 const void* m_out, const uint32_t* idx_out, const uint64_t* report, bool device);
+// MSM_AMD_LOOKUP_HASH_BITS (0 .. 32, default all) and MSM_AMD_LOOKUP_COUNT (lane / wave), read at every call
+uint32_t fr_lookup_hash_bits_knob();
+int fr_lookup_count_knob();
 // a CSR matrix in host memory (msm_amd_fr_matrix_build, msm_amd_host_fr_matvec): sizes, row_ptr and EVERY column
 const char* fr_matrix_check(int scalar_layout, uint64_t n_rows, uint64_t n_cols, const uint64_t* row_ptr,
                             const uint32_t* col_idx, const void* values);

@@ -2056,6 +2056,7 @@ void msm_amd_destroy(msm_amd_ctx* ctx) {
   handle_release_all(ctx->live_ntt);
   handle_release_all(ctx->live_fr_mat);
   handle_release_all(ctx->live_poseidon);
+  handle_release_all(ctx->live_fr_lookup);
   for (DeviceBuf* b : {&ctx->scratch_a, &ctx->scratch_b, &ctx->scratch_c, &ctx->scratch_b2, &ctx->scratch_c2}) kill_buf(*b);
   bases_cache_clear(ctx);   // (entries and unused reserves go through the graveyard)
   for (const msm_amd_ctx::CacheReserve& r : ctx->cache_reserve) ctx->graveyard.push_back(r.d);
