@@ -1428,6 +1428,48 @@ int msm_amd_host_fr_lookup_multiplicities(int scalar_layout, int on_missing, con
  * image, out[2] hash bits that choose a home, out[3] byte offset of the slots in the image */
 int msm_amd_test_fr_lookup_plan(size_t n_rows, uint32_t hash_bits, uint64_t out[4]);
 
+/* halo2's lookup argument: the permuted columns A', S'.  From an input column A and a table column S of n usable rows the
+ * prover of upstream halo2 (zcash, PSE) builds A', a permutation of A, and S', a permutation of S, with A'[0] = S'[0] and
+ * A'[i] = S'[i] or A'[i] = A'[i-1] for 0 < i < n, then the product column z[i+1] = z[i] (A[i] + beta)(S[i] + gamma) /
+ * ((A'[i] + beta)(S'[i] + gamma)) ("halo2's lookup argument": the calls above this one do the rest).
+ * ROW ORDER, NOT VALUE ORDER.  With c[j] the number of inputs of a column whose representative is row j (as for m_out
+ * above), off[j] = sum of c[j'] over j' < j, and U the ascending list of the rows with c = 0 (duplicate rows included):
+ *   A'  positions off[j] .. off[j] + c[j] - 1 hold row j, for every j with c[j] > 0;
+ *   S'  position off[j] holds row j for every j with c[j] > 0; the other positions, ascending, hold rows U[0], U[1], ...
+ * halo2's own permute_expression_pair orders A' by ascending field value.  That is another arrangement of the same two
+ * multisets, equally valid, and the verifier cannot tell the two apart; matching halo2's bytes would need a 256-bit sort
+ * and is OUT OF SCOPE.  Every byte here is determined by the table and the inputs, not by the order in which atomics land.
+ * n_vec columns of n records lie back to back; each is permuted on its own against the one table; a_out and s_out are n_vec n
+ * records, column by column, fully reduced in scalar_layout.  n n_vec < 2^32 and n_rows n_vec < 2^32.  a_out and s_out are
+ * each optional, one must be given; s_out needs n == n_rows (the caller writes the blinding rows behind the n usable
+ * ones), without it any n >= 1 goes.  a_out may be `in` itself: the inputs are consumed by the probe launch before
+ * anything is written.
+ * report: as for msm_amd_fr_lookup_multiplicities*, rows_hit summed over the columns, max_multiplicity the
+ * largest counter of any column; it comes back in the call's one bounded wait.  A value that is in no row ALWAYS fails with
+ * MSM_AMD_INPUT_ERROR, as halo2 fails the proof: count and index in msm_amd_last_error, the report filled in, BOTH OUTPUTS
+ * UNTOUCHED (the kernel that writes them reads the miss counter on the device).  n == 0 or n_vec == 0: MSM_AMD_OK, nothing
+ * written, a zero report.
+ * MSM_AMD_INPUT_ERROR, before any launch: an unknown layout; a null in (with inputs) or report; neither output; s_out with
+ * n != n_rows; a freed or foreign handle; any overlap between in, a_out and s_out other than a_out == in.  After such an
+ * argument error the contents of report are undefined (it is filled in for a miss and for MSM_AMD_OK only).  n_rows < 2^31,
+ * the limit of the lookup handle; the twin and msm_amd_test_fr_permute_plan refuse more.
+ * The buffers are HOST memory and are staged through the ctx like those of the other host-buffer forms.  A form on
+ * device-resident buffers is not offered yet: the kernels take device pointers throughout, what is missing is the entry
+ * point with its alignment and image-overlap checks and its case in the guard-band suite.
+ * Ctx-owned memory: 16 bytes per row and column and the tile totals (msm_amd_test_fr_permute_plan).  The scan's tiles are
+ * 2^MSM_AMD_PERMUTE_TILE_LOG words (2 .. 11, default 11; read at every call).  MSM_AMD_PERMUTE_FILL=scan finds the row of
+ * an output position by a maximum scan instead of the default binary search (4 more bytes per position; the same bytes
+ * out). */
+int msm_amd_fr_lookup_permute(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, int scalar_layout, const void* in, size_t n,
+                              size_t n_vec, void* a_out, void* s_out, uint64_t report[4]);
+/* The same on the CPU, from the table itself (no ctx, no GPU) */
+int msm_amd_host_fr_lookup_permute(int scalar_layout, const void* table, size_t n_rows, const void* in, size_t n, size_t n_vec,
+                                   int threads, void* a_out, void* s_out, uint64_t report[4]);
+/* Test aid (no ctx): the plan of a call over n_rows rows and n_vec columns at tile_log (2 .. 11): out[0] levels of the scan,
+ * out[1] kernels of a call (the probe, 2 levels - 1 of the scan, the fill), out[2] tiles of the first level over all
+ * columns, out[3] bytes of ctx-owned memory */
+int msm_amd_test_fr_permute_plan(size_t n_rows, size_t n_vec, uint32_t tile_log, uint64_t out[4]);
+
 /* ---- pairings ---------------------------------------------------------------------------------
  * The optimal ate pairing of BN254, e: G1 x G2 -> GT, in groups of pairs: the one operation that connects the two groups
  * the calls above handle (an SRS consistency check, a Groth16 or KZG verification where the proof was made, the inner

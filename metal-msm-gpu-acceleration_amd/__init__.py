@@ -157,6 +157,7 @@ EXPORTS = [
     "msm_amd_fr_lookup_build", "msm_amd_fr_lookup_build_device", "msm_amd_fr_lookup_info", "msm_amd_fr_lookup_free",
     "msm_amd_fr_lookup_multiplicities", "msm_amd_fr_lookup_multiplicities_device", "msm_amd_host_fr_lookup_multiplicities",
     "msm_amd_test_fr_lookup_plan",
+    "msm_amd_fr_lookup_permute", "msm_amd_host_fr_lookup_permute", "msm_amd_test_fr_permute_plan",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -432,6 +433,11 @@ def _lib():
         L.msm_amd_host_fr_lookup_multiplicities.argtypes = [c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t,
                                                             c_int, c_void_p, c_void_p, POINTER(c_uint64)]
         L.msm_amd_test_fr_lookup_plan.argtypes = [c_size_t, c_uint32, POINTER(c_uint64)]
+        L.msm_amd_fr_lookup_permute.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p,
+                                                POINTER(c_uint64)]
+        L.msm_amd_host_fr_lookup_permute.argtypes = [c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_int, c_void_p,
+                                                     c_void_p, POINTER(c_uint64)]
+        L.msm_amd_test_fr_permute_plan.argtypes = [c_size_t, c_size_t, c_uint32, POINTER(c_uint64)]
         L.msm_amd_fr_poly_eval.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]
         L.msm_amd_fr_poly_eval_device.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
                                                   POINTER(c_float)]
@@ -1222,6 +1228,17 @@ class MsmConfig:
                                                             c_void_p(d_in), n, n_vec, c_void_p(d_m_out), c_void_p(d_idx_out),
                                                             rep, ctypes.byref(ms))
         return _lookup_result(self, st, None, 0, None, 0, rep)[2], ms.value
+
+    def fr_lookup_permute(self, table, data: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1, want_a=True, want_s=True,
+                          a_out=None, s_out=None):
+        """(A', S', report) of n_vec columns of host records against a table (msm_amd_fr_lookup_permute): halo2's permuted
+        columns in row order, each n_vec n records or None if not asked for.  A value that is in no row raises MsmError with
+        .report set.  a_out / s_out: ctypes buffers to write into (then that result is None)."""
+        n = len(data) // 32 // n_vec if n_vec else 0
+        a, s = _permute_buffers(n * n_vec, want_a, want_s, a_out, s_out)
+        rep = (c_uint64 * 4)()
+        st = _lib().msm_amd_fr_lookup_permute(self.h, _fr_lookup_handle(table), scalar_layout, data, n, n_vec, a, s, rep)
+        return _permute_result(self, st, a if a_out is None else None, s if s_out is None else None, n * n_vec, rep)
 
     # ---- polynomials over Fr: n_vec polynomials of n coefficients back to back, lowest degree first -------
     def fr_poly_eval(self, coeffs: bytes, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1) -> bytes:
@@ -2111,6 +2128,42 @@ def test_fr_lookup_plan(n_rows, hash_bits=32) -> dict:
     if st != OK:
         raise MsmError(st)
     return dict(zip(("capacity", "bytes", "home_bits", "slots_off"), out))
+
+
+def _permute_buffers(total, want_a, want_s, a_out, s_out):
+    a = a_out if a_out is not None else ctypes.create_string_buffer(max(1, 32 * total)) if want_a else None
+    s = s_out if s_out is not None else ctypes.create_string_buffer(max(1, 32 * total)) if want_s else None
+    return a, s
+
+
+def _permute_result(cfg, st, a, s, total, rep):
+    """(A' bytes or None, S' bytes or None, report dict) of a permute call; a failed call raises MsmError with .report set"""
+    report = dict(zip(LOOKUP_REPORT_FIELDS, rep))
+    if st != OK:
+        err = MsmError(st, _lib().msm_amd_last_error(cfg.h).decode() if cfg is not None else "")
+        err.report = report
+        raise err
+    return (a.raw[:32 * total] if a is not None else None), (s.raw[:32 * total] if s is not None else None), report
+
+
+def host_fr_lookup_permute(table: bytes, data: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1, threads=0, want_a=True,
+                           want_s=True, a_out=None, s_out=None):
+    """Host twin of MsmConfig.fr_lookup_build + fr_lookup_permute (no GPU): (A', S', report)"""
+    n_rows = len(table) // 32
+    n = len(data) // 32 // n_vec if n_vec else 0
+    a, s = _permute_buffers(n * n_vec, want_a, want_s, a_out, s_out)
+    rep = (c_uint64 * 4)()
+    st = _lib().msm_amd_host_fr_lookup_permute(scalar_layout, table, n_rows, data, n, n_vec, threads, a, s, rep)
+    return _permute_result(None, st, a if a_out is None else None, s if s_out is None else None, n * n_vec, rep)
+
+
+def test_fr_permute_plan(n_rows, n_vec=1, tile_log=11) -> dict:
+    """The plan of a permute call (msm_amd_test_fr_permute_plan)"""
+    out = (c_uint64 * 4)()
+    st = _lib().msm_amd_test_fr_permute_plan(n_rows, n_vec, tile_log, out)
+    if st != OK:
+        raise MsmError(st)
+    return dict(zip(("levels", "launches", "tiles", "bytes"), out))
 
 
 def host_fr_poly_eval(coeffs: bytes, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1, threads=0) -> bytes:

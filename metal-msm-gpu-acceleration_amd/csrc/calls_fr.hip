@@ -396,9 +396,72 @@ int fr_lookup_mult_call(msm_amd_ctx* ctx, const msm_amd_fr_lookup* handle, bool 
   return MSM_AMD_OK;
 }
 
+// msm_amd_fr_lookup_permute: one span of kernels, the report as the call's record.  the outputs asked for are staged one behind the other
+// in CallState::out and copied back in a second span, only if nothing was missing.
+int fr_lookup_permute_call(msm_amd_ctx* ctx, const msm_amd_fr_lookup* handle, int scalar_layout, const void* in, size_t n,
+                           size_t n_vec, void* a_out, void* s_out, uint64_t* report) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = "msm_amd_fr_lookup_permute";
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_fr_lookup* t = find_handle(ctx->live_fr_lookup, handle);
+  if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + kNotLookup);
+  if (const char* why = fr_permute_call_check(scalar_layout, t->n_rows, in, n, n_vec, a_out, s_out, report))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  for (int k = 0; k < 4; ++k) report[k] = 0;
+  const size_t total = n * n_vec, bytes = total * 32;
+  if (total == 0) return MSM_AMD_OK;
+  CallState& s = ctx->calls;
+  FrPermuteLaunch c{};
+  c.probe.image = t->d_mem, c.probe.plan = t->plan, c.probe.n_rows = t->n_rows, c.probe.layout = scalar_layout;
+  c.probe.count_form = fr_lookup_count_knob(), c.probe.total = total;
+  c.tile_log = fr_permute_tile_log_knob(), c.n = n, c.n_vec = n_vec;
+  c.fill_form = fr_permute_fill_knob();
+  c.plan = fr_permute_plan(t->n_rows, n_vec, c.tile_log);
+  d.host_in = 1u;
+  d.in[0] = in, d.in_bytes[0] = bytes;
+  d.work[0] = {&s.work, (size_t)(c.fill_form == kPermuteFillScan ? fr_permute_owner_plan(c.plan, n, n_vec, c.tile_log).bytes
+                                                                 : c.plan.bytes)};
+  const size_t s_at = a_out ? bytes : 0;   // S' lies behind A' if both are asked for
+  d.work[1] = {&s.out, s_at + (s_out ? bytes : 0)};
+  uint64_t rep[kLookupReportWords] = {};
+  auto staged = [&] { return (uint8_t*)s.out.p; };
+  const int rc = device_call(
+      ctx, d,
+      [&](hipStream_t st, CallIo& io) {
+        c.probe.in = io.in[0], c.work = s.work.p;
+        c.a_out = a_out ? staged() : nullptr, c.s_out = s_out ? staged() + s_at : nullptr;
+        launch_fr_lookup_permute(st, c);
+        io.record = (const uint8_t*)s.work.p + c.plan.report_off;
+        return MSM_AMD_OK;
+      },
+      [&](const uint8_t* record, float) { std::memcpy(rep, record, sizeof rep); },
+      [&](hipStream_t st, const CallIo&) -> int {
+        if (rep[kLookupMissing] || rep[kLookupReportError]) return MSM_AMD_OK;
+        if (a_out) HIP_TRY(ctx, hipMemcpyAsync(a_out, staged(), bytes, hipMemcpyDeviceToHost, st));
+        if (s_out) HIP_TRY(ctx, hipMemcpyAsync(s_out, staged() + s_at, bytes, hipMemcpyDeviceToHost, st));
+        return MSM_AMD_OK;
+      });
+  if (rc) return rc;
+  if (rep[kLookupReportError])
+    return fail(ctx, MSM_AMD_PIPELINE_ERROR, d.who + ": a probe ran through every slot of the index");
+  for (int k = 0; k < 4; ++k) report[k] = rep[k];
+  if (rep[kLookupMissing])
+    return fail(ctx, MSM_AMD_INPUT_ERROR,
+                d.who + ": " + std::to_string(rep[kLookupMissing]) + " of " + std::to_string(total) +
+                    " inputs are not in the table, the first at flat index " + std::to_string(rep[kLookupFirstMissing]) +
+                    " (a_out and s_out are untouched)");
+  return MSM_AMD_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int msm_amd_fr_lookup_permute(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, int scalar_layout, const void* in, size_t n,
+                              size_t n_vec, void* a_out, void* s_out, uint64_t report[4]) {
+  return fr_lookup_permute_call(ctx, lookup, scalar_layout, in, n, n_vec, a_out, s_out, report);
+}
 
 int msm_amd_fr_lookup_build(msm_amd_ctx* ctx, int scalar_layout, const void* table, size_t n_rows, msm_amd_fr_lookup** out) {
   return fr_lookup_build_call(ctx, true, scalar_layout, table, n_rows, out, nullptr);

@@ -12,6 +12,8 @@
 //                            <kLookupCountBlock> the same in workgroups of 16 waves, each wave holding its largest group
 //                            back: the held groups meet in LDS behind one barrier and leave as one atomic per distinct row
 //                            (a column that is half zeros sends one add per 1024 inputs to the counter of 0, not 16).
+//                            <.., COLS> (msm_amd_fr_lookup_permute*, k_permute.hip): every column of inputs counts in
+//                            counters of its own.
 //   fr_lookup_finish_kernel  one lane per row: the counter -> m_out[j] as a record of the caller's layout; rows hit and the
 //                            largest counter folded per wave.  STRICT: the lanes read the miss counter of the probe launch
 //                            and store nothing if it is not zero.
@@ -87,12 +89,15 @@ struct FrLookupProbeArgs {
   const uint32_t* in;
   uint64_t total;
   uint32_t* idx_out;              // optional
-  uint32_t* counters;             // n_rows
+  uint32_t* counters;             // n_rows; COLS: n_rows for each column
   unsigned long long* report;     // kLookupReportWords
   int layout;
+  uint32_t col_n, n_rows;         // COLS: inputs per column, counters per column
 };
 
-template <int FORM>
+// COLS (msm_amd_fr_lookup_permute*): input i of column i / col_n counts in that column's counters; a wave or a workgroup
+// that straddles a column boundary groups by the flat counter index, which is below 2^32
+template <int FORM, bool COLS>
 __global__ void __launch_bounds__(FORM == kLookupCountBlock ? kLookupBlockThreads : kLookupThreads)
     fr_lookup_probe_kernel(FrLookupProbeArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -112,6 +117,7 @@ __global__ void __launch_bounds__(FORM == kLookupCountBlock ? kLookupBlockThread
     atomicMin(a.report + kLookupFirstMissing, (unsigned long long)i);
   }
   if (exhausted) atomicMax(a.report + kLookupReportError, 1ull);
+  if (COLS && hit) idx += (uint32_t)(i / a.col_n) * a.n_rows;
   if (FORM == kLookupCountLane) {
     if (hit) atomicAdd(a.counters + idx, 1u);
     return;
@@ -173,6 +179,18 @@ __global__ void __launch_bounds__(kLookupThreads) fr_lookup_finish_kernel(int la
 
 uint32_t blocks_of(uint64_t items) { return (uint32_t)((items + kLookupThreads - 1) / kLookupThreads); }
 
+template <bool COLS>
+void launch_probe(hipStream_t st, int count_form, const FrLookupProbeArgs& a) {
+  if (count_form == kLookupCountLane)
+    hipLaunchKernelGGL((fr_lookup_probe_kernel<kLookupCountLane, COLS>), dim3(blocks_of(a.total)), dim3(kLookupThreads), 0, st, a);
+  else if (count_form == kLookupCountWave)
+    hipLaunchKernelGGL((fr_lookup_probe_kernel<kLookupCountWave, COLS>), dim3(blocks_of(a.total)), dim3(kLookupThreads), 0, st, a);
+  else
+    hipLaunchKernelGGL((fr_lookup_probe_kernel<kLookupCountBlock, COLS>),
+                       dim3((uint32_t)((a.total + kLookupBlockThreads - 1) / kLookupBlockThreads)), dim3(kLookupBlockThreads), 0,
+                       st, a);
+}
+
 }  // namespace
 
 void launch_fr_lookup_build(hipStream_t st, const FrLookupPlan& plan, uint64_t n_rows, int layout, const void* d_table,
@@ -190,27 +208,27 @@ void launch_fr_lookup_build(hipStream_t st, const FrLookupPlan& plan, uint64_t n
                      n_rows, slots, stats);
 }
 
-uint32_t launch_fr_lookup_multiplicities(hipStream_t st, const FrLookupLaunch& c) {
+void launch_fr_lookup_probe(hipStream_t st, const FrLookupLaunch& c, uint64_t col_n, uint32_t* counters,
+                            unsigned long long* report) {
   const uint8_t* image = (const uint8_t*)c.image;
+  FrLookupProbeArgs a{};
+  a.plan = c.plan;
+  a.rows = (const uint32_t*)(image + c.plan.rows_off), a.slots = (const uint32_t*)(image + c.plan.slots_off);
+  a.in = (const uint32_t*)c.in, a.total = c.total, a.idx_out = c.idx_out;
+  a.counters = counters, a.report = report, a.layout = c.layout;
+  a.col_n = (uint32_t)col_n, a.n_rows = (uint32_t)c.n_rows;
+  if (col_n) launch_probe<true>(st, c.count_form, a);
+  else launch_probe<false>(st, c.count_form, a);
+}
+
+uint32_t launch_fr_lookup_multiplicities(hipStream_t st, const FrLookupLaunch& c) {
   uint8_t* work = (uint8_t*)c.work;
   unsigned long long* report = (unsigned long long*)(work + c.at.report_off);
   (void)hipMemsetAsync(work, 0, c.at.idx_off, st);
   (void)hipMemsetAsync(report + kLookupFirstMissing, 0xFF, 8, st);
   uint32_t launches = 1;
   if (c.total) {
-    FrLookupProbeArgs a{};
-    a.plan = c.plan;
-    a.rows = (const uint32_t*)(image + c.plan.rows_off), a.slots = (const uint32_t*)(image + c.plan.slots_off);
-    a.in = (const uint32_t*)c.in, a.total = c.total, a.idx_out = c.idx_out;
-    a.counters = (uint32_t*)work, a.report = report, a.layout = c.layout;
-    if (c.count_form == kLookupCountLane)
-      hipLaunchKernelGGL(fr_lookup_probe_kernel<kLookupCountLane>, dim3(blocks_of(c.total)), dim3(kLookupThreads), 0, st, a);
-    else if (c.count_form == kLookupCountWave)
-      hipLaunchKernelGGL(fr_lookup_probe_kernel<kLookupCountWave>, dim3(blocks_of(c.total)), dim3(kLookupThreads), 0, st, a);
-    else
-      hipLaunchKernelGGL(fr_lookup_probe_kernel<kLookupCountBlock>,
-                         dim3((uint32_t)((c.total + kLookupBlockThreads - 1) / kLookupBlockThreads)), dim3(kLookupBlockThreads), 0,
-                         st, a);
+    launch_fr_lookup_probe(st, c, 0, (uint32_t*)work, report);
     ++launches;
   }
   hipLaunchKernelGGL(fr_lookup_finish_kernel, dim3(blocks_of(c.n_rows)), dim3(kLookupThreads), 0, st, c.layout, c.on_missing,

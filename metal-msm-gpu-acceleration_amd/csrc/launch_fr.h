@@ -1,11 +1,12 @@
-// Launch wrappers of the Fr vector kernels (k_fr.hip; the lookup tables: k_lookup.hip) for the host driver (calls_fr.hip),
-// and the argument checks the driver shares with the host twins (host_fr.hip, host_lookup.hip).
+// Launch wrappers of the Fr vector kernels (k_fr.hip; the lookup tables: k_lookup.hip, k_permute.hip) for the host driver
+// (calls_fr.hip), and the argument checks the driver shares with the host twins (host_fr.hip, host_lookup.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 
 #include "fr_lookup.hip.h"
+#include "fr_permute.hip.h"
 #include "fr_mat.hip.h"
 #include "fr_mle.hip.h"
 #include "fr_poseidon.hip.h"
@@ -155,6 +156,24 @@ struct FrLookupLaunch {
 };
 // the clears, the probe launch (if there are inputs) and the finish launch, in stream order; returns the number of kernels
 uint32_t launch_fr_lookup_multiplicities(hipStream_t st, const FrLookupLaunch& c);
+// the probe launch alone (total >= 1), into cleared counters and a cleared report.  col_n == 0: n_rows counters; else input i
+// belongs to column i / col_n and counts in counters[(i / col_n) n_rows + row]
+void launch_fr_lookup_probe(hipStream_t st, const FrLookupLaunch& c, uint64_t col_n, uint32_t* counters,
+                            unsigned long long* report);
+
+// halo2's permuted columns (fr_permute.hip.h, k_permute.hip): the clears, the probe, the scan with the compaction, the fill,
+// in stream order; returns the number of kernels.  n >= 1, n_vec >= 1.
+struct FrPermuteLaunch {
+  FrLookupLaunch probe;   // image, plan, n_rows, layout, count_form, in, total = n n_vec; m_out, idx_out, work, at unused
+  FrPermutePlan plan;
+  uint32_t tile_log;
+  int fill_form;          // kPermuteFillSearch, kPermuteFillScan
+  uint64_t n, n_vec;
+  void* a_out;            // optional: total records; may be probe.in
+  void* s_out;            // optional: total records, n == n_rows
+  void* work;             // plan.bytes; kPermuteFillScan: fr_permute_owner_plan(plan, n, n_vec, tile_log).bytes
+};
+uint32_t launch_fr_lookup_permute(hipStream_t st, const FrPermuteLaunch& c);
 
 // host_fr.hip.  Each check returns null or what is wrong, for msm_amd_last_error.
 bool fr_layout_known(int scalar_layout);   // MONT_LE and CANON_LE
@@ -184,6 +203,14 @@ const char* fr_lookup_call_check(int scalar_layout, int on_missing, uint64_t n_r
 // MSM_AMD_LOOKUP_HASH_BITS (0 .. 32, default all) and MSM_AMD_LOOKUP_COUNT (lane / wave), read at every call
 uint32_t fr_lookup_hash_bits_knob();
 int fr_lookup_count_knob();
+// msm_amd_fr_lookup_permute and its twin: layout, report and the outputs first, then n == 0 or n_vec == 0 passes, then sizes, pointers
+// and overlap: a_out may be `in` itself, every other pair of in, a_out, s_out is disjoint
+const char* fr_permute_call_check(int scalar_layout, uint64_t n_rows, const void* in, uint64_t n, uint64_t n_vec,
+                                  const void* a_out, const void* s_out, const uint64_t* report);
+// MSM_AMD_PERMUTE_TILE_LOG (2 .. kPermuteTileLog, the default), read at every call
+uint32_t fr_permute_tile_log_knob();
+// MSM_AMD_PERMUTE_FILL (search / scan), read at every call
+int fr_permute_fill_knob();
 // a CSR matrix in host memory (msm_amd_fr_matrix_build, msm_amd_host_fr_matvec): sizes, row_ptr and EVERY column
 const char* fr_matrix_check(int scalar_layout, uint64_t n_rows, uint64_t n_cols, const uint64_t* row_ptr,
                             const uint32_t* col_idx, const void* values);
