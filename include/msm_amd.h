@@ -1437,8 +1437,8 @@ int msm_amd_test_fr_lookup_plan(size_t n_rows, uint32_t hash_bits, uint64_t out[
  *   A'  positions off[j] .. off[j] + c[j] - 1 hold row j, for every j with c[j] > 0;
  *   S'  position off[j] holds row j for every j with c[j] > 0; the other positions, ascending, hold rows U[0], U[1], ...
  * halo2's own permute_expression_pair orders A' by ascending field value.  That is another arrangement of the same two
- * multisets, equally valid, and the verifier cannot tell the two apart; matching halo2's bytes would need a 256-bit sort
- * and is OUT OF SCOPE.  Every byte here is determined by the table and the inputs, not by the order in which atomics land.
+ * multisets, equally valid, and the verifier cannot tell the two apart; halo2's own arrangement is
+ * MSM_AMD_PERMUTE_HALO2 of msm_amd_fr_lookup_permute_as below.  Every byte here is determined by the table and the inputs, not by the order in which atomics land.
  * n_vec columns of n records lie back to back; each is permuted on its own against the one table; a_out and s_out are n_vec n
  * records, column by column, fully reduced in scalar_layout.  n n_vec < 2^32 and n_rows n_vec < 2^32.  a_out and s_out are
  * each optional, one must be given; s_out needs n == n_rows (the caller writes the blinding rows behind the n usable
@@ -1453,9 +1453,8 @@ int msm_amd_test_fr_lookup_plan(size_t n_rows, uint32_t hash_bits, uint64_t out[
  * n != n_rows; a freed or foreign handle; any overlap between in, a_out and s_out other than a_out == in.  After such an
  * argument error the contents of report are undefined (it is filled in for a miss and for MSM_AMD_OK only).  n_rows < 2^31,
  * the limit of the lookup handle; the twin and msm_amd_test_fr_permute_plan refuse more.
- * The buffers are HOST memory and are staged through the ctx like those of the other host-buffer forms.  A form on
- * device-resident buffers is not offered yet: the kernels take device pointers throughout, what is missing is the entry
- * point with its alignment and image-overlap checks and its case in the guard-band suite.
+ * The buffers are HOST memory and are staged through the ctx like those of the other host-buffer forms; the form on
+ * device-resident buffers is msm_amd_fr_lookup_permute_as(.., MSM_AMD_MEM_DEVICE, .., MSM_AMD_PERMUTE_ROWS, ..) below.
  * Ctx-owned memory: 16 bytes per row and column and the tile totals (msm_amd_test_fr_permute_plan).  The scan's tiles are
  * 2^MSM_AMD_PERMUTE_TILE_LOG words (2 .. 11, default 11; read at every call).  MSM_AMD_PERMUTE_FILL=scan finds the row of
  * an output position by a maximum scan instead of the default binary search (4 more bytes per position; the same bytes
@@ -1469,6 +1468,79 @@ int msm_amd_host_fr_lookup_permute(int scalar_layout, const void* table, size_t 
  * out[1] kernels of a call (the probe, 2 levels - 1 of the scan, the fill), out[2] tiles of the first level over all
  * columns, out[3] bytes of ctx-owned memory */
 int msm_amd_test_fr_permute_plan(size_t n_rows, size_t n_vec, uint32_t tile_log, uint64_t out[4]);
+
+/* ---- sorting Fr records by canonical value ------------------------------------------------------------------------------------
+ * n_vec columns of n records lie back to back; each column is sorted on its own, ascending by the canonical value in [0, r):
+ * halo2curves' Ord for Fr, which compares to_repr() from the top byte down.  The key is the residue -- NOT the Montgomery
+ * words and NOT the caller's unreduced word: in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE any 256-bit word is taken
+ * mod r, and `out` holds fully reduced records of scalar_layout.  The sort is STABLE: records equal mod r keep their input
+ * order.  perm_out[v n + k] is the column-relative input index of the record at sorted position k of column v; it ascends
+ * within a run of equal values.  out and perm_out are each optional, one must be given; out may be `in` itself.
+ * n n_vec < 2^32; n == 0 or n_vec == 0: MSM_AMD_OK, nothing written.  This is the sorted concatenation of plookup, a
+ * deduplication or range-table preparation, and the order halo2's permute_expression_pair gives the input column A'.
+ * mem.  MSM_AMD_MEM_DEVICE: in, out and perm_out are device pointers, records 16-byte aligned, perm_out 4-byte aligned.
+ * MSM_AMD_MEM_HOST: host memory, staged through the ctx like the other host-buffer forms.  (One entry point with a `mem`
+ * argument rather than a _device twin: DESIGN.md section 8.16.)  kernel_ms is optional.
+ * MSM_AMD_INPUT_ERROR, before any launch: an unknown mem or layout; neither output; n n_vec >= 2^32; a null in with inputs
+ * present; a misaligned device pointer; any overlap between in, out and perm_out other than out == in.
+ * How it runs.  One pass forms the 32-byte keys in ctx-owned memory and a mask of the key bytes that differ anywhere in the call;
+ * the mask comes back in the call's one bounded wait (the call is blocking, as msm_amd_scalar_width*), and a stable 8-bit
+ * radix pass then runs only for a byte that differs: columns of small values take 2 to 3 passes, not 32.  No output byte
+ * depends on the mask.  Ctx-owned memory: 32 bytes per record, 16 per record of one column, the tile histograms
+ * (msm_amd_test_fr_sort_plan); the host form stages 4 more per record when perm_out is asked for. */
+enum { MSM_AMD_MEM_HOST = 0, MSM_AMD_MEM_DEVICE = 1 };
+int msm_amd_fr_sort(msm_amd_ctx* ctx, int mem, int scalar_layout, const void* in, size_t n, size_t n_vec, void* out,
+                    uint32_t* perm_out, float* kernel_ms);
+/* The same on the CPU (no ctx, no GPU): a stable merge sort of the indices by the canonical value, on up to `threads` threads */
+int msm_amd_host_fr_sort(int scalar_layout, const void* in, size_t n, size_t n_vec, int threads, void* out, uint32_t* perm_out);
+/* Test aid (no ctx): the plan of a sort of n_vec columns of n (n, n_vec >= 1, n n_vec < 2^32) whose keys differ in the bytes of
+ * digit_mask (bit d: byte d of the little-endian residue): out[0] 8-bit passes over a column (popcount(digit_mask); the columns
+ * follow each other on the stream, so there are no passes over the column number), out[1] kernels of the call (the keys; per
+ * column one gather per 32-bit word with set bits, three per pass, the final gather), out[2] tiles of a pass, out[3] bytes of
+ * ctx-owned memory */
+int msm_amd_test_fr_sort_plan(size_t n, size_t n_vec, uint32_t digit_mask, uint64_t out[4]);
+
+/* A lookup handle over the SORTED table: the table is sorted by the kernels of msm_amd_fr_sort straight into the handle's
+ * image, the insert pass of msm_amd_fr_lookup_build* then indexes the sorted rows, and the handle is marked sorted
+ * (msm_amd_fr_lookup_sorted: *sorted = 1, 0 for a handle of the plain builds).  Row k of such a handle is sorted position k.
+ * perm_out (optional, n_rows words in `mem` space, device: 4-byte aligned, not overlapping the table) maps position k back
+ * to the caller's row: the stable sort permutation of the table.  Every call that takes a handle accepts this one unchanged;
+ * msm_amd_fr_lookup_multiplicities* on it credits POSITIONS, and because the sort is stable the representative (the first
+ * position of a run of equal values) is the image of the plain handle's representative (the smallest row):
+ * m_sorted[k] == m_plain[perm[k]].  Limits, lifetime, errors and misuse are those of msm_amd_fr_lookup_build*; an unknown
+ * mem is MSM_AMD_INPUT_ERROR.  The build has two bounded waits: the digit mask of the sort, then the statistics. */
+int msm_amd_fr_lookup_build_sorted(msm_amd_ctx* ctx, int mem, int scalar_layout, const void* table, size_t n_rows,
+                                   uint32_t* perm_out, msm_amd_fr_lookup** out, float* kernel_ms);
+int msm_amd_fr_lookup_sorted(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, int* sorted);
+/* Test aid: the device address of a handle's image (msm_amd_fr_lookup_info gives its size), so that a test can hand a call
+ * a buffer that overlaps it and see the call refused.  The image belongs to the handle: never write to it. */
+int msm_amd_test_fr_lookup_image(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, void** image);
+
+/* A', S' of msm_amd_fr_lookup_permute in a chosen arrangement, on host or on device buffers.
+ * MSM_AMD_PERMUTE_ROWS works on any handle and returns exactly the bytes of msm_amd_fr_lookup_permute (over a sorted handle
+ * "row" reads "sorted position").
+ * MSM_AMD_PERMUTE_HALO2 needs a handle of msm_amd_fr_lookup_build_sorted (otherwise MSM_AMD_INPUT_ERROR before any launch) and
+ * follows upstream's permute_expression_pair (halo2_proofs, plonk/lookup/prover.rs) with its tie-breaks: A' is the input column
+ * sorted ascending by value; at position 0 and at every position where A' differs from its predecessor S' takes A''s value,
+ * and one instance of that value leaves the table multiset; the leftover table values, ascending and duplicates included,
+ * fill the remaining positions from the LAST one downwards (repeated_input_rows.pop()).  A = [2,2,1,2,5], S = [5,1,2,7,1]
+ * give A' = [1,2,2,2,5], S' = [1,2,7,1,5] (tests/golden/permute_halo2_known.json).  halo2 is not on the build machine: the
+ * bytes follow upstream's algorithm AS WRITTEN THERE and are NOT confirmed against a halo2 build.
+ * How: over a sorted handle the row-order pipeline already yields halo2's A' and halo2's heads; only the gaps are filled from
+ * the other end of the unused rows (fr_permute.hip.h).  A' and the heads of the two arrangements agree on a sorted handle.
+ * mem.  MSM_AMD_MEM_HOST: as msm_amd_fr_lookup_permute.  MSM_AMD_MEM_DEVICE: in, a_out, s_out are device pointers to 16-byte
+ * aligned records, none of which may overlap the handle's image; a_out may be `in`; report is HOST memory; the fill kernel
+ * reads the miss counter on the device, so a miss leaves both outputs untouched here too.
+ * Everything else -- the report, a miss, s_out needs n == n_rows, n == 0, the limits, the other argument errors, the two
+ * environment knobs -- is as for msm_amd_fr_lookup_permute; an unknown mem or arrangement is MSM_AMD_INPUT_ERROR.  The twin
+ * takes the table itself and, for MSM_AMD_PERMUTE_HALO2, sorts it first. */
+enum { MSM_AMD_PERMUTE_ROWS = 0, MSM_AMD_PERMUTE_HALO2 = 1 };
+int msm_amd_fr_lookup_permute_as(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, int mem, int scalar_layout,
+                                 int arrangement, const void* in, size_t n, size_t n_vec, void* a_out, void* s_out,
+                                 uint64_t report[4] /* HOST memory */, float* kernel_ms);
+int msm_amd_host_fr_lookup_permute_as(int scalar_layout, int arrangement, const void* table, size_t n_rows,
+                                      const void* in, size_t n, size_t n_vec, int threads, void* a_out, void* s_out,
+                                      uint64_t report[4]);
 
 /* ---- pairings ---------------------------------------------------------------------------------
  * The optimal ate pairing of BN254, e: G1 x G2 -> GT, in groups of pairs: the one operation that connects the two groups

@@ -58,6 +58,8 @@ NTT_FORWARD, NTT_INVERSE = 0, 1
 FR_ADD, FR_SUB, FR_MUL, FR_SCALE, FR_AXPY, FR_MULSUB_SCALE = range(6)
 FR_PREFIX_INCLUSIVE, FR_PREFIX_EXCLUSIVE = 0, 1
 LOOKUP_STRICT, LOOKUP_COUNT_MISSING = 0, 1
+MEM_HOST, MEM_DEVICE = 0, 1    # MSM_AMD_MEM_*: where the buffers of msm_amd_fr_sort, _build_sorted and _permute_as lie
+PERMUTE_ROWS, PERMUTE_HALO2 = 0, 1   # MSM_AMD_PERMUTE_*: the arrangement of A', S'
 LOOKUP_NOT_FOUND = 0xFFFFFFFF
 MLE_LOW, MLE_HIGH = 0, 1
 WIDTH_UNSIGNED, WIDTH_SIGNED = 0, 1
@@ -158,6 +160,9 @@ EXPORTS = [
     "msm_amd_fr_lookup_multiplicities", "msm_amd_fr_lookup_multiplicities_device", "msm_amd_host_fr_lookup_multiplicities",
     "msm_amd_test_fr_lookup_plan",
     "msm_amd_fr_lookup_permute", "msm_amd_host_fr_lookup_permute", "msm_amd_test_fr_permute_plan",
+    "msm_amd_fr_sort", "msm_amd_host_fr_sort", "msm_amd_test_fr_sort_plan",
+    "msm_amd_fr_lookup_build_sorted", "msm_amd_fr_lookup_sorted", "msm_amd_test_fr_lookup_image",
+    "msm_amd_fr_lookup_permute_as", "msm_amd_host_fr_lookup_permute_as",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -438,6 +443,18 @@ def _lib():
         L.msm_amd_host_fr_lookup_permute.argtypes = [c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_int, c_void_p,
                                                      c_void_p, POINTER(c_uint64)]
         L.msm_amd_test_fr_permute_plan.argtypes = [c_size_t, c_size_t, c_uint32, POINTER(c_uint64)]
+        L.msm_amd_fr_sort.argtypes = [c_void_p, c_int, c_int, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p,
+                                      POINTER(c_float)]
+        L.msm_amd_host_fr_sort.argtypes = [c_int, c_void_p, c_size_t, c_size_t, c_int, c_void_p, c_void_p]
+        L.msm_amd_test_fr_sort_plan.argtypes = [c_size_t, c_size_t, c_uint32, POINTER(c_uint64)]
+        L.msm_amd_fr_lookup_build_sorted.argtypes = [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, POINTER(c_void_p),
+                                                     POINTER(c_float)]
+        L.msm_amd_fr_lookup_sorted.argtypes = [c_void_p, c_void_p, POINTER(c_int)]
+        L.msm_amd_test_fr_lookup_image.argtypes = [c_void_p, c_void_p, POINTER(c_void_p)]
+        L.msm_amd_fr_lookup_permute_as.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_size_t,
+                                                   c_void_p, c_void_p, POINTER(c_uint64), POINTER(c_float)]
+        L.msm_amd_host_fr_lookup_permute_as.argtypes = [c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_int,
+                                                        c_void_p, c_void_p, POINTER(c_uint64)]
         L.msm_amd_fr_poly_eval.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]
         L.msm_amd_fr_poly_eval_device.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
                                                   POINTER(c_float)]
@@ -1239,6 +1256,79 @@ class MsmConfig:
         rep = (c_uint64 * 4)()
         st = _lib().msm_amd_fr_lookup_permute(self.h, _fr_lookup_handle(table), scalar_layout, data, n, n_vec, a, s, rep)
         return _permute_result(self, st, a if a_out is None else None, s if s_out is None else None, n * n_vec, rep)
+
+    def fr_lookup_build_sorted(self, table, scalar_layout=SCALAR_MONT_LE, n_rows=None, mem=MEM_HOST, perm_out=None,
+                               want_perm=True):
+        """The handle over the table sorted by value (msm_amd_fr_lookup_build_sorted): row k is sorted position k.
+        MEM_HOST: table is bytes; returns (FrLookup, perm list or None).  MEM_DEVICE: table and perm_out (optional) are device
+        addresses and n_rows is required; returns (FrLookup, None).  kernel_ms is left in .build_ms."""
+        h, ms = c_void_p(), c_float(0)
+        if mem != MEM_HOST:
+            self._check(_lib().msm_amd_fr_lookup_build_sorted(self.h, mem, scalar_layout, c_void_p(table), n_rows or 0,
+                                                              c_void_p(perm_out), ctypes.byref(h), ctypes.byref(ms)))
+            perm = None
+        else:
+            n_rows = len(table) // 32 if n_rows is None else n_rows
+            perm = (c_uint32 * max(1, n_rows))() if want_perm else None
+            self._check(_lib().msm_amd_fr_lookup_build_sorted(self.h, mem, scalar_layout, table, n_rows, perm, ctypes.byref(h),
+                                                              ctypes.byref(ms)))
+            perm = list(perm[:n_rows]) if want_perm else None
+        t = FrLookup(self, h)
+        t.build_ms = ms.value
+        return t, perm
+
+    def fr_lookup_sorted(self, table) -> bool:
+        """whether a handle came from fr_lookup_build_sorted (msm_amd_fr_lookup_sorted)"""
+        flag = c_int(-1)
+        self._check(_lib().msm_amd_fr_lookup_sorted(self.h, _fr_lookup_handle(table), ctypes.byref(flag)))
+        return bool(flag.value)
+
+    def test_fr_lookup_image(self, table) -> int:
+        """the device address of a handle's image (msm_amd_test_fr_lookup_image): for overlap tests only"""
+        p = c_void_p()
+        self._check(_lib().msm_amd_test_fr_lookup_image(self.h, _fr_lookup_handle(table), ctypes.byref(p)))
+        return p.value
+
+    def fr_lookup_permute_as(self, table, data, arrangement=PERMUTE_HALO2, scalar_layout=SCALAR_MONT_LE, n_vec=1,
+                             mem=MEM_HOST, n=None, want_a=True, want_s=True, a_out=None, s_out=None):
+        """A', S' in a chosen arrangement (msm_amd_fr_lookup_permute_as).  MEM_HOST: as fr_lookup_permute, returns
+        (A', S', report).  MEM_DEVICE: data, a_out, s_out are device addresses (None: not asked for), n is required; returns
+        (None, None, report) and leaves kernel_ms in .last_kernel_ms.  A miss raises MsmError with .report set."""
+        rep, ms = (c_uint64 * 4)(), c_float(0)
+        if mem != MEM_HOST:
+            st = _lib().msm_amd_fr_lookup_permute_as(self.h, _fr_lookup_handle(table), mem, scalar_layout, arrangement,
+                                                     c_void_p(data), n or 0, n_vec, c_void_p(a_out), c_void_p(s_out), rep,
+                                                     ctypes.byref(ms))
+            self.last_kernel_ms = ms.value
+            return _permute_result(self, st, None, None, 0, rep)
+        if n is None:
+            n = len(data) // 32 // n_vec if n_vec else 0
+        a, s = _permute_buffers(n * n_vec, want_a, want_s, a_out, s_out)
+        st = _lib().msm_amd_fr_lookup_permute_as(self.h, _fr_lookup_handle(table), mem, scalar_layout, arrangement, data, n,
+                                                 n_vec, a, s, rep, ctypes.byref(ms))
+        self.last_kernel_ms = ms.value
+        return _permute_result(self, st, a if a_out is None else None, s if s_out is None else None, n * n_vec, rep)
+
+    # ---- sorting Fr records by canonical value ---------------------------------------------------------
+    def fr_sort(self, data, scalar_layout=SCALAR_MONT_LE, n_vec=1, mem=MEM_HOST, n=None, out=None, perm_out=None,
+                want_out=True, want_perm=True):
+        """n_vec columns of n records, each sorted ascending by canonical value, stably (msm_amd_fr_sort).
+        MEM_HOST: data is bytes or a ctypes buffer; returns (records or None, perm as a list or None, kernel_ms); out /
+        perm_out: ctypes buffers to write into (then that result is None; out may be data itself).
+        MEM_DEVICE: data, out and perm_out are device addresses (None: not asked for) and n is required; returns
+        (None, None, kernel_ms)."""
+        ms = c_float(0)
+        if mem != MEM_HOST:
+            self._check(_lib().msm_amd_fr_sort(self.h, mem, scalar_layout, c_void_p(data), n or 0, n_vec, c_void_p(out),
+                                               c_void_p(perm_out), ctypes.byref(ms)))
+            return None, None, ms.value
+        if n is None:
+            n = len(data) // 32 // n_vec if n_vec else 0
+        o = out if out is not None else ctypes.create_string_buffer(max(1, 32 * n * n_vec)) if want_out else None
+        p = perm_out if perm_out is not None else (c_uint32 * max(1, n * n_vec))() if want_perm else None
+        self._check(_lib().msm_amd_fr_sort(self.h, mem, scalar_layout, data, n, n_vec, o, p, ctypes.byref(ms)))
+        return (o.raw[:32 * n * n_vec] if o is not None and out is None else None,
+                list(p[:n * n_vec]) if p is not None and perm_out is None else None, ms.value)
 
     # ---- polynomials over Fr: n_vec polynomials of n coefficients back to back, lowest degree first -------
     def fr_poly_eval(self, coeffs: bytes, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1) -> bytes:
@@ -2157,6 +2247,17 @@ def host_fr_lookup_permute(table: bytes, data: bytes, scalar_layout=SCALAR_MONT_
     return _permute_result(None, st, a if a_out is None else None, s if s_out is None else None, n * n_vec, rep)
 
 
+def host_fr_lookup_permute_as(table: bytes, data: bytes, arrangement=PERMUTE_HALO2, scalar_layout=SCALAR_MONT_LE, n_vec=1,
+                              threads=0, want_a=True, want_s=True, a_out=None, s_out=None):
+    """Host twin of MsmConfig.fr_lookup_build_sorted + fr_lookup_permute_as (no GPU): (A', S', report)"""
+    n_rows = len(table) // 32
+    n = len(data) // 32 // n_vec if n_vec else 0
+    a, s = _permute_buffers(n * n_vec, want_a, want_s, a_out, s_out)
+    rep = (c_uint64 * 4)()
+    st = _lib().msm_amd_host_fr_lookup_permute_as(scalar_layout, arrangement, table, n_rows, data, n, n_vec, threads, a, s, rep)
+    return _permute_result(None, st, a if a_out is None else None, s if s_out is None else None, n * n_vec, rep)
+
+
 def test_fr_permute_plan(n_rows, n_vec=1, tile_log=11) -> dict:
     """The plan of a permute call (msm_amd_test_fr_permute_plan)"""
     out = (c_uint64 * 4)()
@@ -2164,6 +2265,29 @@ def test_fr_permute_plan(n_rows, n_vec=1, tile_log=11) -> dict:
     if st != OK:
         raise MsmError(st)
     return dict(zip(("levels", "launches", "tiles", "bytes"), out))
+
+
+def host_fr_sort(data, scalar_layout=SCALAR_MONT_LE, n_vec=1, threads=0, n=None, out=None, perm_out=None, want_out=True,
+                 want_perm=True):
+    """Host twin of MsmConfig.fr_sort (no GPU): (records or None, perm as a list or None)"""
+    if n is None:
+        n = len(data) // 32 // n_vec if n_vec else 0
+    o = out if out is not None else ctypes.create_string_buffer(max(1, 32 * n * n_vec)) if want_out else None
+    p = perm_out if perm_out is not None else (c_uint32 * max(1, n * n_vec))() if want_perm else None
+    st = _lib().msm_amd_host_fr_sort(scalar_layout, data, n, n_vec, threads, o, p)
+    if st != OK:
+        raise MsmError(st)
+    return (o.raw[:32 * n * n_vec] if o is not None and out is None else None,
+            list(p[:n * n_vec]) if p is not None and perm_out is None else None)
+
+
+def test_fr_sort_plan(n, n_vec=1, digit_mask=0) -> dict:
+    """The plan of a sort whose keys differ in the bytes of digit_mask (msm_amd_test_fr_sort_plan)"""
+    out = (c_uint64 * 4)()
+    st = _lib().msm_amd_test_fr_sort_plan(n, n_vec, digit_mask, out)
+    if st != OK:
+        raise MsmError(st)
+    return dict(zip(("passes", "launches", "tiles", "bytes"), out))
 
 
 def host_fr_poly_eval(coeffs: bytes, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1, threads=0) -> bytes:

@@ -335,6 +335,98 @@ int fr_lookup_build_call(msm_amd_ctx* ctx, bool host, int scalar_layout, const v
   return MSM_AMD_OK;
 }
 
+// msm_amd_fr_lookup_build_sorted: the table is sorted by the kernels of msm_amd_fr_sort straight into the rows of the new
+// image -- the keys and the digit mask, one bounded wait for the mask, the passes, and a final gather that writes reduced
+// Montgomery residues -- then the insert pass of a plain build indexes the sorted rows.  The keys and the wait for the mask
+// come before the image is allocated; the second wait is that of handle_build_tail, which also brings the statistics and
+// (host form) the staged permutation.
+int fr_lookup_build_sorted_call(msm_amd_ctx* ctx, int mem, int scalar_layout, const void* table, size_t n_rows,
+                                uint32_t* perm_out, msm_amd_fr_lookup** out, float* kernel_ms) {
+  const std::string who = "msm_amd_fr_lookup_build_sorted";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (!ctx || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": null pointer");
+  *out = nullptr;
+  if (mem != MSM_AMD_MEM_HOST && mem != MSM_AMD_MEM_DEVICE)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": mem must be MSM_AMD_MEM_HOST or MSM_AMD_MEM_DEVICE");
+  const bool host = mem == MSM_AMD_MEM_HOST;
+  if (const char* why = fr_lookup_table_check(scalar_layout, table, n_rows, !host))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": " + why);
+  if (!host && ((uintptr_t)perm_out & 3u)) return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": device perm_out must be 4-byte aligned");
+  if (perm_out && (uintptr_t)perm_out < (uintptr_t)table + n_rows * 32 && (uintptr_t)table < (uintptr_t)perm_out + n_rows * 4)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, who + ": perm_out must not overlap the table");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = recover_if_stalled(ctx)) return rc;
+  if (!drain_or_mark_stalled(ctx))
+    return fail(ctx, MSM_AMD_PIPELINE_ERROR, who + ": device busy past the wait bound of " + std::to_string(ctx->wait_timeout_ms) + " ms");
+  const FrLookupPlan plan = fr_lookup_plan(n_rows, fr_lookup_hash_bits_knob());
+  CallState& s = ctx->calls;
+  FrSortLaunch c{};
+  c.n = n_rows, c.n_vec = 1, c.layout = scalar_layout;
+  c.plan = fr_sort_plan(n_rows, 1, 0);
+  const size_t perm_at = (size_t)((c.plan.bytes + 15) & ~(uint64_t)15);   // host form: the staged permutation
+  // the ctx is idle: every buffer is sized before anything is enqueued
+  if (int rc = ensure(ctx, s.work, perm_at + (host && perm_out ? n_rows * 4 : 0))) return rc;
+  if (host)
+    if (int rc = ensure(ctx, s.in[0], n_rows * 32)) return rc;
+  if (!s.h_record) HIP_TRY(ctx, hipHostMalloc((void**)&s.h_record, sizeof(PointCounters), hipHostMallocDefault));
+  if (kernel_ms)
+    for (hipEvent_t& e : s.ev)
+      if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+  // span 1, before the image exists: the keys into CallState::work and the digit mask behind a bounded wait of its own, so
+  // that handle_build_tail below keeps its contract (its callable only enqueues, the helper waits once)
+  hipStream_t st = ctx->stream;
+  c.in = table, c.work = s.work.p;
+  if (host) {
+    if (int rc = staged_upload(ctx, s.in[0].p, table, n_rows * 32, st)) return rc;
+    c.in = s.in[0].p;
+  }
+  if (kernel_ms) HIP_TRY(ctx, hipEventRecord(s.ev[0], st));
+  launch_fr_sort_keys(st, c);
+  HIP_TRY(ctx, hipGetLastError());
+  if (kernel_ms) HIP_TRY(ctx, hipEventRecord(s.ev[1], st));
+  HIP_TRY(ctx, hipMemcpyAsync(s.h_record, s.work.p, kSortRecordBytes, hipMemcpyDeviceToHost, st));
+  if (int rc = sync_stream_bounded(ctx, st, who.c_str())) return rc;
+  uint32_t mask;
+  std::memcpy(&mask, s.h_record, 4);
+  // span 2: the passes and the final gather into the rows of the new image, the insert pass, the statistics
+  int up = MSM_AMD_OK;
+  hipError_t tail = hipSuccess;
+  if (int rc = handle_build_tail(
+          ctx, ctx->live_fr_lookup, plan.bytes, "a lookup table", "sorted lookup table build",
+          [&](void* d_mem) {
+            // the rows of the image are reduced Montgomery residues whatever the caller's layout is
+            c.layout = MSM_AMD_SCALAR_MONT_LE, c.out = (uint8_t*)d_mem + plan.rows_off;
+            c.perm_out = !perm_out ? nullptr : host ? (uint32_t*)((uint8_t*)s.work.p + perm_at) : perm_out;
+            if (kernel_ms) tail = hipEventRecord(s.ev[2], st);
+            launch_fr_sort_passes(st, c, mask);
+            launch_fr_lookup_build(st, plan, n_rows, scalar_layout, nullptr, d_mem);
+            if (kernel_ms && tail == hipSuccess) tail = hipEventRecord(s.ev[3], st);
+            if (tail == hipSuccess)
+              tail = hipMemcpyAsync(s.h_record, (const uint8_t*)d_mem + plan.stats_off, kLookupStatWords * 4,
+                                    hipMemcpyDeviceToHost, st);
+            if (tail == hipSuccess && host && perm_out)
+              tail = hipMemcpyAsync(perm_out, c.perm_out, n_rows * 4, hipMemcpyDeviceToHost, st);
+          },
+          out))
+    return rc;
+  msm_amd_fr_lookup* h = *out;
+  uint32_t stats[kLookupStatWords];
+  std::memcpy(stats, s.h_record, sizeof stats);
+  std::string why;
+  if (tail != hipSuccess) why = hipGetErrorString(tail), up = MSM_AMD_PIPELINE_ERROR;
+  else if (stats[kLookupError]) why = "an insert ran through every slot of the index", up = MSM_AMD_PIPELINE_ERROR;
+  if (up) {   // nothing may read the allocation
+    *out = nullptr;
+    handle_free(ctx, ctx->live_fr_lookup, h, "");
+    return fail(ctx, up, who + ": " + why);
+  }
+  if (kernel_ms) *kernel_ms = event_span(s.ev[0], s.ev[1]) + event_span(s.ev[2], s.ev[3]);
+  h->n_rows = n_rows, h->n_distinct = stats[kLookupDistinct], h->longest_probe = stats[kLookupLongest], h->plan = plan;
+  h->sorted = true;
+  return MSM_AMD_OK;
+}
+
 int fr_lookup_mult_call(msm_amd_ctx* ctx, const msm_amd_fr_lookup* handle, bool host, int scalar_layout, int on_missing,
                         const void* in, size_t n, size_t n_vec, void* m_out, uint32_t* idx_out, uint64_t* report,
                         float* kernel_ms) {
@@ -396,52 +488,75 @@ int fr_lookup_mult_call(msm_amd_ctx* ctx, const msm_amd_fr_lookup* handle, bool 
   return MSM_AMD_OK;
 }
 
-// msm_amd_fr_lookup_permute: one span of kernels, the report as the call's record.  the outputs asked for are staged one behind the other
-// in CallState::out and copied back in a second span, only if nothing was missing.
-int fr_lookup_permute_call(msm_amd_ctx* ctx, const msm_amd_fr_lookup* handle, int scalar_layout, const void* in, size_t n,
-                           size_t n_vec, void* a_out, void* s_out, uint64_t* report) {
+// msm_amd_fr_lookup_permute and msm_amd_fr_lookup_permute_as: one span of kernels, the report as the call's record.  Host form:
+// the outputs asked for are staged one behind the other in CallState::out and copied back in a second span, only if nothing
+// was missing.  Device form: the fill kernel writes the caller's buffers, and writes nothing if anything was missing; the call
+// is done after the one wait for its record.
+int fr_lookup_permute_call(msm_amd_ctx* ctx, const char* who, const msm_amd_fr_lookup* handle, int mem, int scalar_layout,
+                           int arrangement, const void* in, size_t n, size_t n_vec, void* a_out, void* s_out, uint64_t* report,
+                           float* kernel_ms) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
   DeviceCall d;
-  d.who = "msm_amd_fr_lookup_permute";
+  d.who = who;
+  if (kernel_ms) *kernel_ms = 0.f;
   std::lock_guard<std::mutex> lk(ctx->mu);
   const msm_amd_fr_lookup* t = find_handle(ctx->live_fr_lookup, handle);
   if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + kNotLookup);
+  if (mem != MSM_AMD_MEM_HOST && mem != MSM_AMD_MEM_DEVICE)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": mem must be MSM_AMD_MEM_HOST or MSM_AMD_MEM_DEVICE");
+  if (arrangement != kPermuteRows && arrangement != kPermuteHalo2)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": arrangement must be MSM_AMD_PERMUTE_ROWS or MSM_AMD_PERMUTE_HALO2");
+  if (arrangement == kPermuteHalo2 && !t->sorted)
+    return fail(ctx, MSM_AMD_INPUT_ERROR,
+                d.who + ": MSM_AMD_PERMUTE_HALO2 needs a handle of msm_amd_fr_lookup_build_sorted (the rows in value order)");
+  const bool host = mem == MSM_AMD_MEM_HOST;
   if (const char* why = fr_permute_call_check(scalar_layout, t->n_rows, in, n, n_vec, a_out, s_out, report))
     return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
-  for (int k = 0; k < 4; ++k) report[k] = 0;
   const size_t total = n * n_vec, bytes = total * 32;
+  if (!host && total) {
+    if (((uintptr_t)in | (uintptr_t)a_out | (uintptr_t)s_out) & 15u)
+      return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": device records must be 16-byte aligned");
+    const uintptr_t lo = (uintptr_t)t->d_mem, hi = lo + t->bytes;
+    for (const void* p : {in, (const void*)a_out, (const void*)s_out})
+      if (p && (uintptr_t)p < hi && lo < (uintptr_t)p + bytes)
+        return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": in, a_out and s_out must not overlap the table");
+  }
+  for (int k = 0; k < 4; ++k) report[k] = 0;
   if (total == 0) return MSM_AMD_OK;
   CallState& s = ctx->calls;
   FrPermuteLaunch c{};
   c.probe.image = t->d_mem, c.probe.plan = t->plan, c.probe.n_rows = t->n_rows, c.probe.layout = scalar_layout;
   c.probe.count_form = fr_lookup_count_knob(), c.probe.total = total;
   c.tile_log = fr_permute_tile_log_knob(), c.n = n, c.n_vec = n_vec;
-  c.fill_form = fr_permute_fill_knob();
+  c.fill_form = fr_permute_fill_knob(), c.arrangement = arrangement;
   c.plan = fr_permute_plan(t->n_rows, n_vec, c.tile_log);
-  d.host_in = 1u;
+  d.host_in = host ? 1u : 0u, d.kernel_ms = kernel_ms;
   d.in[0] = in, d.in_bytes[0] = bytes;
   d.work[0] = {&s.work, (size_t)(c.fill_form == kPermuteFillScan ? fr_permute_owner_plan(c.plan, n, n_vec, c.tile_log).bytes
                                                                  : c.plan.bytes)};
   const size_t s_at = a_out ? bytes : 0;   // S' lies behind A' if both are asked for
-  d.work[1] = {&s.out, s_at + (s_out ? bytes : 0)};
+  if (host) d.work[1] = {&s.out, s_at + (s_out ? bytes : 0)};
   uint64_t rep[kLookupReportWords] = {};
   auto staged = [&] { return (uint8_t*)s.out.p; };
-  const int rc = device_call(
-      ctx, d,
-      [&](hipStream_t st, CallIo& io) {
-        c.probe.in = io.in[0], c.work = s.work.p;
-        c.a_out = a_out ? staged() : nullptr, c.s_out = s_out ? staged() + s_at : nullptr;
-        launch_fr_lookup_permute(st, c);
-        io.record = (const uint8_t*)s.work.p + c.plan.report_off;
-        return MSM_AMD_OK;
-      },
-      [&](const uint8_t* record, float) { std::memcpy(rep, record, sizeof rep); },
-      [&](hipStream_t st, const CallIo&) -> int {
-        if (rep[kLookupMissing] || rep[kLookupReportError]) return MSM_AMD_OK;
-        if (a_out) HIP_TRY(ctx, hipMemcpyAsync(a_out, staged(), bytes, hipMemcpyDeviceToHost, st));
-        if (s_out) HIP_TRY(ctx, hipMemcpyAsync(s_out, staged() + s_at, bytes, hipMemcpyDeviceToHost, st));
-        return MSM_AMD_OK;
-      });
+  auto launch = [&](hipStream_t st, CallIo& io) {
+    c.probe.in = io.in[0], c.work = s.work.p;
+    c.a_out = !a_out ? nullptr : host ? staged() : a_out;
+    c.s_out = !s_out ? nullptr : host ? staged() + s_at : s_out;
+    launch_fr_lookup_permute(st, c);
+    io.record = (const uint8_t*)s.work.p + c.plan.report_off;
+    return MSM_AMD_OK;
+  };
+  auto then = [&](const uint8_t* record, float) { std::memcpy(rep, record, sizeof rep); };
+  int rc;
+  if (host)
+    rc = device_call(ctx, d, launch, then, [&](hipStream_t st, const CallIo&) -> int {
+      if (rep[kLookupMissing] || rep[kLookupReportError]) return MSM_AMD_OK;
+      if (a_out) HIP_TRY(ctx, hipMemcpyAsync(a_out, staged(), bytes, hipMemcpyDeviceToHost, st));
+      if (s_out) HIP_TRY(ctx, hipMemcpyAsync(s_out, staged() + s_at, bytes, hipMemcpyDeviceToHost, st));
+      return MSM_AMD_OK;
+    });
+  else
+    rc = device_call(ctx, d, launch, then);
   if (rc) return rc;
   if (rep[kLookupReportError])
     return fail(ctx, MSM_AMD_PIPELINE_ERROR, d.who + ": a probe ran through every slot of the index");
@@ -460,7 +575,35 @@ extern "C" {
 
 int msm_amd_fr_lookup_permute(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, int scalar_layout, const void* in, size_t n,
                               size_t n_vec, void* a_out, void* s_out, uint64_t report[4]) {
-  return fr_lookup_permute_call(ctx, lookup, scalar_layout, in, n, n_vec, a_out, s_out, report);
+  return fr_lookup_permute_call(ctx, "msm_amd_fr_lookup_permute", lookup, MSM_AMD_MEM_HOST, scalar_layout, kPermuteRows, in, n,
+                                n_vec, a_out, s_out, report, nullptr);
+}
+
+int msm_amd_fr_lookup_permute_as(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, int mem, int scalar_layout, int arrangement,
+                                 const void* in, size_t n, size_t n_vec, void* a_out, void* s_out, uint64_t report[4],
+                                 float* kernel_ms) {
+  return fr_lookup_permute_call(ctx, "msm_amd_fr_lookup_permute_as", lookup, mem, scalar_layout, arrangement, in, n, n_vec,
+                                a_out, s_out, report, kernel_ms);
+}
+
+int msm_amd_fr_lookup_sorted(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, int* sorted) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_fr_lookup* t = find_handle(ctx->live_fr_lookup, lookup);
+  if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, std::string("msm_amd_fr_lookup_sorted") + kNotLookup);
+  if (!sorted) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_fr_lookup_sorted: null pointer");
+  *sorted = t->sorted ? 1 : 0;
+  return MSM_AMD_OK;
+}
+
+int msm_amd_test_fr_lookup_image(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, void** image) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const msm_amd_fr_lookup* t = find_handle(ctx->live_fr_lookup, lookup);
+  if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, std::string("msm_amd_test_fr_lookup_image") + kNotLookup);
+  if (!image) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_fr_lookup_image: null pointer");
+  *image = t->d_mem;
+  return MSM_AMD_OK;
 }
 
 int msm_amd_fr_lookup_build(msm_amd_ctx* ctx, int scalar_layout, const void* table, size_t n_rows, msm_amd_fr_lookup** out) {
@@ -470,6 +613,11 @@ int msm_amd_fr_lookup_build(msm_amd_ctx* ctx, int scalar_layout, const void* tab
 int msm_amd_fr_lookup_build_device(msm_amd_ctx* ctx, int scalar_layout, const void* d_table, size_t n_rows,
                                    msm_amd_fr_lookup** out, float* kernel_ms) {
   return fr_lookup_build_call(ctx, false, scalar_layout, d_table, n_rows, out, kernel_ms);
+}
+
+int msm_amd_fr_lookup_build_sorted(msm_amd_ctx* ctx, int mem, int scalar_layout, const void* table, size_t n_rows,
+                                   uint32_t* perm_out, msm_amd_fr_lookup** out, float* kernel_ms) {
+  return fr_lookup_build_sorted_call(ctx, mem, scalar_layout, table, n_rows, perm_out, out, kernel_ms);
 }
 
 int msm_amd_fr_lookup_info(msm_amd_ctx* ctx, const msm_amd_fr_lookup* lookup, size_t* n_rows, size_t* n_distinct,
@@ -503,6 +651,64 @@ int msm_amd_fr_lookup_multiplicities_device(msm_amd_ctx* ctx, const msm_amd_fr_l
                                             uint32_t* d_idx_out, uint64_t report[4], float* kernel_ms) {
   return fr_lookup_mult_call(ctx, lookup, false, scalar_layout, on_missing, d_in, n, n_vec, d_m_out, d_idx_out, report,
                              kernel_ms);
+}
+
+}  // extern "C"
+
+// ---- sort by canonical value (msm_amd_fr_sort) -------------------------------------------------------------------------------
+// A device_call of two spans: the keys and the digit mask, which comes back as the first word of the call's 64-byte record in
+// the one bounded wait, then the passes the mask asks for and the final gather.  The keys, the pairs and the histograms live in
+// CallState::work.  The host form sorts over the staged copy of its input; its permutation is staged behind the workspace
+// and copied back at the end of the second span.
+namespace {
+
+int fr_sort_call(msm_amd_ctx* ctx, int mem, int scalar_layout, const void* in, size_t n, size_t n_vec, void* out,
+                 uint32_t* perm_out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = "msm_amd_fr_sort";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_sort_call_check(mem, scalar_layout, in, n, n_vec, out, perm_out))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  const size_t total = n * n_vec;
+  if (total == 0) return MSM_AMD_OK;
+  const bool host = mem == MSM_AMD_MEM_HOST;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  CallState& s = ctx->calls;
+  FrSortLaunch c{};
+  c.n = n, c.n_vec = n_vec, c.layout = scalar_layout;
+  c.plan = fr_sort_plan(n, n_vec, 0);
+  const size_t perm_at = (size_t)((c.plan.bytes + 15) & ~(uint64_t)15);   // host form: the staged permutation
+  d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = total * 32;
+  d.out = out, d.out_bytes = out ? total * 32 : 0;
+  d.work[0] = {&s.work, perm_at + (host && perm_out ? total * 4 : 0)};
+  uint32_t mask = 0;
+  return device_call(
+      ctx, d,
+      [&](hipStream_t st, CallIo& io) {
+        c.in = io.in[0], c.work = s.work.p;
+        launch_fr_sort_keys(st, c);
+        io.record = s.work.p;
+        return MSM_AMD_OK;
+      },
+      [&](const uint8_t* record, float) { std::memcpy(&mask, record, 4); },
+      [&](hipStream_t st, const CallIo& io) -> int {
+        c.out = out ? io.out : nullptr;
+        c.perm_out = !perm_out ? nullptr : host ? (uint32_t*)((uint8_t*)s.work.p + perm_at) : perm_out;
+        launch_fr_sort_passes(st, c, mask);
+        if (host && perm_out) HIP_TRY(ctx, hipMemcpyAsync(perm_out, c.perm_out, total * 4, hipMemcpyDeviceToHost, st));
+        return MSM_AMD_OK;
+      });
+}
+
+}  // namespace
+
+extern "C" {
+
+int msm_amd_fr_sort(msm_amd_ctx* ctx, int mem, int scalar_layout, const void* in, size_t n, size_t n_vec, void* out,
+                    uint32_t* perm_out, float* kernel_ms) {
+  return fr_sort_call(ctx, mem, scalar_layout, in, n, n_vec, out, perm_out, kernel_ms);
 }
 
 }  // extern "C"

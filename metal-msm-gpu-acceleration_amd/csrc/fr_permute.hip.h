@@ -15,8 +15,8 @@
 // S' needs n = n_rows: then there are as many positions that are no head as there are rows in U.  A' is a permutation of
 // the inputs, S' of the table, A'[0] = S'[0], and A'[p] = S'[p] or A'[p] = A'[p - 1] for every p > 0: what halo2's
 // verifier asks of the two columns.  halo2's own prover orders A' by ascending field value; that is another arrangement
-// of the same multisets which the verifier cannot tell from this one, and matching its bytes would need a 256-bit sort:
-// out of scope.  Every byte is determined by the table and the inputs, not by the order in which atomics land.
+// of the same multisets which the verifier cannot tell from this one: kPermuteHalo2 below, over a handle whose rows were
+// sorted (fr_sort.hip.h).  Every byte is determined by the table and the inputs, not by the order in which atomics land.
 //
 // Phases, in launch order on one stream (no lane waits for another, every loop has a bound known at launch):
 //   count    the probe of k_lookup.hip, counting into per-column counters: counter (v n_rows + j) for column v
@@ -112,6 +112,22 @@ MSM_HD bool fr_permute_head(uint32_t p, uint32_t j, uint64_t pair, uint32_t* k) 
   if (p == fr_permute_off(pair)) return true;
   *k = p - (j - fr_permute_ub(pair)) - 1u;
   return false;
+}
+
+// The two arrangements (MSM_AMD_PERMUTE_*).  Over a handle whose rows are sorted by value (msm_amd_fr_lookup_build_sorted:
+// row k is sorted position k, equal values in their input order) the columns above ARE those of halo2's
+// permute_expression_pair but for the gaps: A' is the input column ascending, the heads are the positions where A' changes,
+// and U lists the leftover table values ascending, duplicates included.  halo2 fills the positions that are no head from
+// the LAST one downwards (repeated_input_rows.pop()), so the g-th of them, ascending, holds U[G - 1 - g], G = |U|, where the
+// row-order arrangement holds U[g].
+enum { kPermuteRows = 0, kPermuteHalo2 = 1 };
+// G of a column from its last scanned pair and that row's own counter
+MSM_HD uint32_t fr_permute_unused_rows(uint64_t last_pair, uint32_t last_counter) {
+  return fr_permute_ub(last_pair) + (uint32_t)(last_counter == 0);
+}
+// the index into U of the g-th position that is no head, g < unused_rows
+MSM_HD uint32_t fr_permute_gap(int arrangement, uint32_t g, uint32_t unused_rows) {
+  return arrangement == kPermuteHalo2 ? unused_rows - 1u - g : g;
 }
 
 }  // namespace msm_amd

@@ -213,6 +213,7 @@ struct msm_amd_poseidon_params : DeviceHandle {
 struct msm_amd_fr_lookup : DeviceHandle {
   uint64_t n_rows = 0, n_distinct = 0, longest_probe = 0;
   FrLookupPlan plan{};
+  bool sorted = false;   // msm_amd_fr_lookup_build_sorted: row k is sorted position k of the caller's table
 };
 
 // Buffers of the blocking vector calls (device_call.h): the staging of the host-buffer forms, the 64-byte record a

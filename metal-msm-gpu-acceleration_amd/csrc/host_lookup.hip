@@ -15,6 +15,7 @@
 namespace msm_amd {
 
 static_assert(kLookupStrict == MSM_AMD_LOOKUP_STRICT && kLookupCountMissing == MSM_AMD_LOOKUP_COUNT_MISSING, "modes");
+static_assert(kPermuteRows == MSM_AMD_PERMUTE_ROWS && kPermuteHalo2 == MSM_AMD_PERMUTE_HALO2, "arrangements");
 
 uint32_t fr_lookup_hash_bits_knob() {
   if (const char* e = std::getenv("MSM_AMD_LOOKUP_HASH_BITS"))
@@ -188,15 +189,23 @@ int host_fr_lookup_multiplicities(int layout, int on_missing, const void* table_
 }
 
 // The columns of fr_permute.hip.h, straight from the definition: every input is looked up before anything is written (a_out
-// may be the inputs), the counters are scanned by one thread, the rows of a column are filled by many.
-int host_fr_lookup_permute(int layout, const void* table_v, size_t n_rows, const void* in_v, size_t n, size_t n_vec, int threads,
-                           void* a_out_v, void* s_out_v, uint64_t report[4]) {
-  if (fr_lookup_table_check(layout, table_v, n_rows, false) ||
+// may be the inputs), the counters are scanned by one thread, the rows of a column are filled by many.  kPermuteHalo2: the
+// twin sorts the table itself (host_fr_sort: what msm_amd_fr_lookup_build_sorted leaves in a handle) and fills the gaps from
+// the far end of the unused rows.
+int host_fr_lookup_permute(int layout, int arrangement, const void* table_v, size_t n_rows, const void* in_v, size_t n,
+                           size_t n_vec, int threads, void* a_out_v, void* s_out_v, uint64_t report[4]) {
+  if ((arrangement != kPermuteRows && arrangement != kPermuteHalo2) || fr_lookup_table_check(layout, table_v, n_rows, false) ||
       fr_permute_call_check(layout, n_rows, in_v, n, n_vec, a_out_v, s_out_v, report))
     return MSM_AMD_INPUT_ERROR;
   report[0] = report[1] = report[2] = report[3] = 0;
   const size_t total = n * n_vec;
   if (total == 0) return MSM_AMD_OK;
+  std::vector<uint8_t> sorted;
+  if (arrangement == kPermuteHalo2) {
+    sorted.resize(n_rows * 32);
+    if (int rc = host_fr_sort(layout, table_v, n_rows, 1, threads, sorted.data(), nullptr)) return rc;
+    table_v = sorted.data();
+  }
   const uint8_t *table = (const uint8_t*)table_v, *in = (const uint8_t*)in_v;
   uint8_t *a_out = (uint8_t*)a_out_v, *s_out = (uint8_t*)s_out_v;
   HostIndex index;
@@ -231,6 +240,7 @@ int host_fr_lookup_permute(int layout, const void* table_v, size_t n_rows, const
       if (c[j] == 0) unused[fr_permute_ub(run)] = (uint32_t)j;
       run += fr_permute_pair(c[j]);
     }
+    const uint32_t gaps = fr_permute_unused_rows(pairs[n_rows - 1], c[n_rows - 1]);
     for_ranges(worker_count(threads, n), n, [&](unsigned, size_t lo, size_t hi) {
       for (size_t p = lo; p < hi; ++p) {
         const uint32_t j = fr_permute_owner(pairs.data(), (uint32_t)n_rows, plan.search_steps, (uint32_t)p);
@@ -238,7 +248,7 @@ int host_fr_lookup_permute(int layout, const void* table_v, size_t n_rows, const
         if (!s_out) continue;
         uint32_t k = 0;
         const bool head = fr_permute_head((uint32_t)p, j, pairs[j], &k);
-        host_put(layout, s_out, v * n + p, index.rows[head ? j : unused[k]]);
+        host_put(layout, s_out, v * n + p, index.rows[head ? j : unused[fr_permute_gap(arrangement, k, gaps)]]);
       }
     });
   }
@@ -251,7 +261,13 @@ extern "C" {
 
 int msm_amd_host_fr_lookup_permute(int scalar_layout, const void* table, size_t n_rows, const void* in, size_t n, size_t n_vec,
                                    int threads, void* a_out, void* s_out, uint64_t report[4]) {
-  return msm_amd::host_fr_lookup_permute(scalar_layout, table, n_rows, in, n, n_vec, threads, a_out, s_out, report);
+  return msm_amd::host_fr_lookup_permute(scalar_layout, msm_amd::kPermuteRows, table, n_rows, in, n, n_vec, threads, a_out, s_out,
+                                         report);
+}
+
+int msm_amd_host_fr_lookup_permute_as(int scalar_layout, int arrangement, const void* table, size_t n_rows, const void* in,
+                                      size_t n, size_t n_vec, int threads, void* a_out, void* s_out, uint64_t report[4]) {
+  return msm_amd::host_fr_lookup_permute(scalar_layout, arrangement, table, n_rows, in, n, n_vec, threads, a_out, s_out, report);
 }
 
 int msm_amd_test_fr_permute_plan(size_t n_rows, size_t n_vec, uint32_t tile_log, uint64_t out[4]) {

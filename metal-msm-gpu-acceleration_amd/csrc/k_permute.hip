@@ -8,6 +8,7 @@
 //                             folds rows_hit and max_multiplicity of the wave into the report.
 //   fr_permute_fill_kernel    one lane per output position: fr_permute_owner, then A'[p] and S'[p] as 16-byte stores.  The
 //                             lanes read the miss counter of the probe launch and store nothing if it is not zero.
+//                             kPermuteHalo2 (over a sorted handle): a position that is no head takes U from its far end.
 //   fr_permute_max_*_kernel   MSM_AMD_PERMUTE_FILL=scan: the heads' rows spread over their groups by a maximum scan on the
 //                             same tiles, and fr_permute_fill_kernel<true> reads its owner instead of searching for it.
 // Phases are ordered by launch order on one stream.  A tile walk has 2^T / 64 trips, the owner search ceil(log2 n_rows).
@@ -165,12 +166,14 @@ struct FrPermuteFill {
   const uint32_t* rows;                  // the handle's residues
   const unsigned long long* pairs;       // n_vec columns of n_rows scanned pairs
   const uint32_t* unused;                // n_vec columns of U
+  const uint32_t* counters;              // n_vec columns of n_rows counters
   const unsigned long long* report;
   uint32_t* a_out;                       // optional
   uint32_t* s_out;                       // optional
   const uint32_t* owner;                 // SCAN: n_vec columns of n scanned owner words
   uint32_t n, n_rows, total, steps;      // total = n n_vec < 2^32
   int layout;
+  int arrangement;                       // kPermuteRows, kPermuteHalo2: which unused row a gap takes
 };
 
 template <bool SCAN>
@@ -193,6 +196,12 @@ __global__ void __launch_bounds__(kPermuteThreads) fr_permute_fill_kernel(FrPerm
   }
   // k < the number of unused rows when n == n_rows and nothing is missing; the tests hold without either being trusted
   if (k >= a.n_rows) return;
+  if (a.arrangement == kPermuteHalo2) {
+    const uint64_t last = (uint64_t)col * a.n_rows + a.n_rows - 1;
+    const uint32_t gaps = fr_permute_unused_rows(a.pairs[last], a.counters[last]);
+    if (k >= gaps) return;   // as above: cannot happen when n == n_rows and nothing is missing
+    k = fr_permute_gap(a.arrangement, k, gaps);
+  }
   const uint32_t r = a.unused[(uint64_t)col * a.n_rows + k];
   if (r >= a.n_rows) return;
   store_rec(a.s_out + q * 8, fr_store(a.layout, load_rec(a.rows + (uint64_t)r * 8)));
@@ -263,7 +272,7 @@ uint32_t launch_fr_lookup_permute(hipStream_t st, const FrPermuteLaunch& c) {
   FrPermuteFill f{};
   f.owner = owner;
   f.rows = (const uint32_t*)((const uint8_t*)c.probe.image + c.probe.plan.rows_off);
-  f.pairs = pairs, f.unused = unused, f.report = report;
+  f.pairs = pairs, f.unused = unused, f.counters = counters, f.report = report, f.arrangement = c.arrangement;
   f.a_out = (uint32_t*)c.a_out, f.s_out = (uint32_t*)c.s_out;
   f.n = (uint32_t)c.n, f.n_rows = (uint32_t)c.probe.n_rows, f.total = (uint32_t)(c.n * c.n_vec), f.steps = p.search_steps;
   f.layout = c.probe.layout;

@@ -10,6 +10,7 @@
 #include "fr_mat.hip.h"
 #include "fr_mle.hip.h"
 #include "fr_poseidon.hip.h"
+#include "fr_sort.hip.h"
 #include "fr_vec.hip.h"
 
 namespace msm_amd {
@@ -168,12 +169,28 @@ struct FrPermuteLaunch {
   FrPermutePlan plan;
   uint32_t tile_log;
   int fill_form;          // kPermuteFillSearch, kPermuteFillScan
+  int arrangement;        // kPermuteRows, kPermuteHalo2 (the handle is sorted)
   uint64_t n, n_vec;
   void* a_out;            // optional: total records; may be probe.in
   void* s_out;            // optional: total records, n == n_rows
   void* work;             // plan.bytes; kPermuteFillScan: fr_permute_owner_plan(plan, n, n_vec, tile_log).bytes
 };
 uint32_t launch_fr_lookup_permute(hipStream_t st, const FrPermuteLaunch& c);
+
+// The sort by canonical value (fr_sort.hip.h, k_fr_sort.hip) in its two spans: the keys with the digit mask, left in the
+// first word of the 64-byte record at the start of the workspace, and, once the host has read the mask, the passes and the
+// final gather of every column; the second returns its number of kernels.  n >= 1, n_vec >= 1, n n_vec < 2^32.
+struct FrSortLaunch {
+  const void* in;         // n n_vec records; read by the first span only, so out may be in
+  void* out;              // optional: n n_vec records
+  uint32_t* perm_out;     // optional: n n_vec words, column-relative
+  void* work;             // plan.bytes
+  FrSortPlan plan;        // of any mask: the workspace does not depend on it
+  uint64_t n, n_vec;
+  int layout;
+};
+void launch_fr_sort_keys(hipStream_t st, const FrSortLaunch& c);
+uint32_t launch_fr_sort_passes(hipStream_t st, const FrSortLaunch& c, uint32_t mask);
 
 // host_fr.hip.  Each check returns null or what is wrong, for msm_amd_last_error.
 bool fr_layout_known(int scalar_layout);   // MONT_LE and CANON_LE
@@ -211,6 +228,12 @@ const char* fr_permute_call_check(int scalar_layout, uint64_t n_rows, const void
 uint32_t fr_permute_tile_log_knob();
 // MSM_AMD_PERMUTE_FILL (search / scan), read at every call
 int fr_permute_fill_knob();
+// host_fr_sort.hip.  msm_amd_fr_sort and its twin: mem and layout first, then the outputs, then n == 0 or n_vec == 0 passes,
+// then sizes, pointers, alignment (device) and overlap: out may be `in` itself, every other pair of in, out, perm_out is disjoint
+const char* fr_sort_call_check(int mem, int scalar_layout, const void* in, uint64_t n, uint64_t n_vec, const void* out,
+                               const uint32_t* perm_out);
+// the twin of the sort itself, for the twin of the permuted columns in value order (host_lookup.hip)
+int host_fr_sort(int layout, const void* in, size_t n, size_t n_vec, int threads, void* out, uint32_t* perm_out);
 // a CSR matrix in host memory (msm_amd_fr_matrix_build, msm_amd_host_fr_matvec): sizes, row_ptr and EVERY column
 const char* fr_matrix_check(int scalar_layout, uint64_t n_rows, uint64_t n_cols, const uint64_t* row_ptr,
                             const uint32_t* col_idx, const void* values);

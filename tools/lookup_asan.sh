@@ -10,12 +10,12 @@ OUT=$ROOT/build_ab/lookup_asan
 SAN="-Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fsanitize-trap=undefined -Xarch_host -fno-omit-frame-pointer"
 mkdir -p "$OUT"
 cd "$ROOT/metal-msm-gpu-acceleration_amd/csrc"
-for f in host_lookup host_fr host_ntt; do
+for f in host_lookup host_fr_sort host_fr host_ntt; do
   $HIPCC -O1 -g -std=c++17 -fPIC --offload-arch=${ARCH:-gfx950} -Wall -Wno-unused-function $SAN -c -o "$OUT/$f.o" $f.hip
 done
 HOST_SAN="-fsanitize=address -fsanitize=undefined -fsanitize-trap=undefined -fno-omit-frame-pointer"
 $HIPCC -x c++ -O1 -g -std=c++17 $HOST_SAN -c -o "$OUT/main.o" "$ROOT/tools/lookup_asan_check.cpp"
-$HIPCC --offload-arch=${ARCH:-gfx950} $HOST_SAN -o "$OUT/lookup_asan_check" "$OUT/main.o" "$OUT/host_lookup.o" "$OUT/host_fr.o" "$OUT/host_ntt.o" -lpthread
+$HIPCC --offload-arch=${ARCH:-gfx950} $HOST_SAN -o "$OUT/lookup_asan_check" "$OUT/main.o" "$OUT/host_lookup.o" "$OUT/host_fr_sort.o" "$OUT/host_fr.o" "$OUT/host_ntt.o" -lpthread
 for bits in 32 3 0; do
   MSM_AMD_LOOKUP_HASH_BITS=$bits ASAN_OPTIONS=detect_leaks=1:halt_on_error=1 "$OUT/lookup_asan_check"
 done
