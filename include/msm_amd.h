@@ -1605,16 +1605,21 @@ int msm_amd_test_pairing_plan(size_t n_groups, size_t group_size, uint32_t pairs
  * limbs 0..8); an Fq6 in the first 54 words.  Operands obey the bounds contract of that header (normalised limbs,
  * at most 4 p per component; line coefficients below 8 p).  LINE_MUL: b = l0, l1, l3.  DOUBLE_STEP: a = T (X, Y, Z),
  * b = x_P, y_P (9 words each); out = T', then l0, l1, l3.  ADD_STEP: the same with Q (x, y) behind T in a.
- * An unknown op is refused. */
+ * FINAL_EXP: fq12_final_exp on the raw element a (the path of the fused product kernel), raw element out; a = 0 gives
+ * an element, not a fault.  An unknown op is refused.
+ * The *_ops forms run count records (count * MSM_AMD_FQ12_WORDS words each way, at most 2^20 records) in one launch, one
+ * lane per record; count = 0 returns MSM_AMD_OK and touches nothing.  The one-record calls are the count = 1 case. */
 enum {
   MSM_AMD_FQ12_OP_FQ6_MUL = 0, MSM_AMD_FQ12_OP_MUL = 1, MSM_AMD_FQ12_OP_SQR = 2, MSM_AMD_FQ12_OP_CYCLO_SQR = 3,
   MSM_AMD_FQ12_OP_LINE_MUL = 4, MSM_AMD_FQ12_OP_FROB1 = 5, MSM_AMD_FQ12_OP_FROB2 = 6, MSM_AMD_FQ12_OP_FROB3 = 7,
   MSM_AMD_FQ12_OP_CONJ = 8, MSM_AMD_FQ12_OP_INV = 9, MSM_AMD_FQ12_OP_POW_X = 10, MSM_AMD_FQ12_OP_DOUBLE_STEP = 11,
-  MSM_AMD_FQ12_OP_ADD_STEP = 12
+  MSM_AMD_FQ12_OP_ADD_STEP = 12, MSM_AMD_FQ12_OP_FINAL_EXP = 13
 };
 enum { MSM_AMD_FQ12_WORDS = 108 };
 int msm_amd_test_fq12_op(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out);
 int msm_amd_test_fq12_op_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out);
+int msm_amd_test_fq12_ops(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count);
+int msm_amd_test_fq12_ops_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count);
 
 /* ---- introspection --------------------------------------------------------------------------- */
 int msm_amd_last_timings(const msm_amd_ctx* ctx, msm_amd_timings* out);

@@ -70,7 +70,8 @@ GT_MONT_LE, GT_CANON_LE = 0, 1
 GT_BYTES = 384
 PAIRING_MILLER_ONLY = 1
 (FQ12_OP_FQ6_MUL, FQ12_OP_MUL, FQ12_OP_SQR, FQ12_OP_CYCLO_SQR, FQ12_OP_LINE_MUL, FQ12_OP_FROB1, FQ12_OP_FROB2,
- FQ12_OP_FROB3, FQ12_OP_CONJ, FQ12_OP_INV, FQ12_OP_POW_X, FQ12_OP_DOUBLE_STEP, FQ12_OP_ADD_STEP) = range(13)
+ FQ12_OP_FROB3, FQ12_OP_CONJ, FQ12_OP_INV, FQ12_OP_POW_X, FQ12_OP_DOUBLE_STEP, FQ12_OP_ADD_STEP,
+ FQ12_OP_FINAL_EXP) = range(14)
 FQ12_WORDS = 108
 
 
@@ -153,7 +154,8 @@ EXPORTS = [
     "msm_amd_test_poseidon_plan",
     "msm_amd_pairing_product", "msm_amd_pairing_product_device", "msm_amd_host_pairing_product",
     "msm_amd_final_exponentiation", "msm_amd_final_exponentiation_device", "msm_amd_host_final_exponentiation",
-    "msm_amd_test_pairing_plan", "msm_amd_test_fq12_op", "msm_amd_test_fq12_op_host",
+    "msm_amd_test_pairing_plan", "msm_amd_test_fq12_op", "msm_amd_test_fq12_op_host", "msm_amd_test_fq12_ops",
+    "msm_amd_test_fq12_ops_host",
     "msm_amd_fr_prefix_sum", "msm_amd_fr_prefix_sum_device", "msm_amd_host_fr_prefix_sum",
     "msm_amd_fr_shift", "msm_amd_fr_shift_device", "msm_amd_host_fr_shift",
     "msm_amd_fr_lookup_build", "msm_amd_fr_lookup_build_device", "msm_amd_fr_lookup_info", "msm_amd_fr_lookup_free",
@@ -528,6 +530,8 @@ def _lib():
             L.msm_amd_test_pairing_plan.argtypes = [c_size_t, c_size_t, c_uint32, c_uint64, POINTER(c_uint32)]
             L.msm_amd_test_fq12_op.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p]
             L.msm_amd_test_fq12_op_host.argtypes = [c_int, c_void_p, c_void_p, c_void_p]
+            L.msm_amd_test_fq12_ops.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t]
+            L.msm_amd_test_fq12_ops_host.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         L.msm_amd_generate_instance_host.argtypes = [c_uint64, c_size_t, c_int, c_void_p, c_void_p, c_int]
         L.msm_amd_test_op_ifma.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_size_t]
         if hasattr(L, "msm_amd_scalar_width"):   # (an MSM_AMD_LIB build from before the bounded-width calls still loads)
@@ -1600,6 +1604,12 @@ class MsmConfig:
         self._check(_lib().msm_amd_test_fq12_op(self.h, op, _fq12_raw(a), _fq12_raw(b), out))
         return list(out)
 
+    def test_fq12_ops(self, op, a, b, count):
+        """count raw-limb Fq12 ops in one launch: a, b flat u32 lists of count * FQ12_WORDS; returns count * FQ12_WORDS."""
+        out = (c_uint32 * max(1, count * FQ12_WORDS))()
+        self._check(_lib().msm_amd_test_fq12_ops(self.h, op, _fq12_raw(a, count), _fq12_raw(b, count), out, count))
+        return list(out)[:count * FQ12_WORDS]
+
     def test_op_g2(self, op, a, b, count):
         """Raw-limb G2 op (MSM_AMD_G2_RAW_*) on the device: a, b flat u32 lists of count * G2_RAW_IN_WORDS; returns
         count * G2_RAW_OUT_WORDS u32."""
@@ -1884,11 +1894,11 @@ def host_compress_points(points: bytes, n: int, fmt=COMPRESSED_ARK, point_layout
     return out.raw[:n * size], bad.value
 
 
-def _fq12_raw(words):
-    buf = (c_uint32 * FQ12_WORDS)()
-    for i, w in enumerate(words):
-        buf[i] = w
-    return buf
+def _fq12_raw(words, count=1):
+    """count records of FQ12_WORDS u32; one record may be shorter (padded with zeros), a batch must be exact"""
+    if count != 1 and len(words) != count * FQ12_WORDS:
+        raise ValueError("expected %d words, got %d" % (count * FQ12_WORDS, len(words)))
+    return (c_uint32 * max(1, count * FQ12_WORDS))(*words)
 
 
 def test_fq12_op_host(op, a, b):
@@ -1898,6 +1908,15 @@ def test_fq12_op_host(op, a, b):
     if st != OK:
         raise MsmError(st)
     return list(out)
+
+
+def test_fq12_ops_host(op, a, b, count):
+    """The same op bodies as MsmConfig.test_fq12_ops, on the host CPU (no GPU)."""
+    out = (c_uint32 * max(1, count * FQ12_WORDS))()
+    st = _lib().msm_amd_test_fq12_ops_host(op, _fq12_raw(a, count), _fq12_raw(b, count), out, count)
+    if st != OK:
+        raise MsmError(st)
+    return list(out)[:count * FQ12_WORDS]
 
 
 def host_pairing_product(g1_points: bytes, g2_points: bytes, n_groups: int, group_size: int, flags=0, gt_layout=GT_MONT_LE,

@@ -17,7 +17,8 @@
 // 0..7 < 2^29 + 8) and at most 4 p.  Every function takes elements and returns elements unless it says otherwise.
 //   acc2_*       : six limb-product sets of normalised operands and the nine terms of the quotient digits: a column
 //                  stays below [columns] 2^63.98; the reduced value is below (1 + rho' sum A_t B_t) p
-//   second operand of an accumulated product: below 8 p (sub<8> negates its imaginary part);
+//   second operand of an accumulated product: below 8 p (fq12_neg1 negates its imaginary part to 8 p - b1, exactly: see
+//                  fq12_neg_exact);
 //                  xi b = Fq2::mul(xi, b): [xi_b] 1.24 p
 //   fq12_mul     : two reductions of six sets per component, added and normalised: [fq12_mul] 3.71 p
 //   fq12_sqr     : symmetric: doubled first operands (8 p) on the cross terms; an even coefficient two reductions of two
@@ -26,7 +27,8 @@
 //   fq12_mul_line: line coefficients below 8 p, one reduction: [fq12_mul_line] 2.14 p
 //   fq12_cyclo_sqr (Granger-Scott, elements of the cyclotomic subgroup): 3 (a^2 + xi b^2) - 2 z as (3 a) a + (3 xi b) b +
 //                  z (-2), five sets: [cyclo_even] 2.18 p;  3 (2 a b) + 2 z as (6 a) b + z 2, three sets: [cyclo_odd] 2.75 p
-//   fq12_conj    : odd coefficients 4 p - c: at most 4 p (exactly 4 p for a zero component: why second operands take 8 p)
+//   fq12_conj    : odd coefficients 4 p - c: at most 4 p (exactly 4 p for a zero component: why second operands take 8 p,
+//                  and why 4 p - c is formed with the carry run through, fq12_neg_exact: the conjugate of a conjugate)
 //   fq12_frob<K> : Fq2::mul(gamma, conj^K(c)): [fq12_frob] 1.22 p
 //   fq12_inv     : c0^2 - v c1^2 + 4 p: [inv_t] 5.86 p (fq6_inv takes components below 8 p); fq6_inv: [fq6_inv] 1.25 p;
 //                  the two closing products: [fq12_inv] 2.32 p
@@ -34,7 +36,8 @@
 //   double_step, add_step: T = (X, Y, Z) homogeneous with components at most 4 p in; out X [step_x] 3.11 p,
 //                  Y [step_y] 1.07 p, Z [step_z] 1.83 p.  Q affine, y possibly a negation (at most 4 p); P canonical.
 //                  Lines: l0 [line_l0] 1.09 p, l1 [line_l1] 1.19 p, l3 [line_l3] 5.31 p (below the 8 p of a second operand).
-//                  Division-free: T = +-Q in an addition step gives T = (0, 0, 0) and zero lines from there on, no fault.
+//                  Division-free, no exceptional case and no fault: T = Q in an addition step gives T = (0, 0, 0) and zero
+//                  lines from there on; T = -Q gives the point at infinity (0, Y', 0) and the vertical line (0, l1, l3).
 //   fq12_from_record / fq12_to_record: any 256-bit words in (Fq29::from_ext: < 1.04 p); canonical out
 // A Miller value is a representative: it is defined up to factors of proper subfields, which the final exponentiation
 // removes.  Only fq12_final_exp's result is a unique GT element.
@@ -122,9 +125,26 @@ MSM_HD void acc2_scale(Acc2& A, const fq2& a, const fe29& s) {
 }
 MSM_HD fq2 acc2_reduce(Acc2& A) { return fq2{Fq29::reduce_columns(A.re), Fq29::reduce_columns(A.im)}; }
 
-MSM_HD fe29 fq12_neg1(const fe29& b) { return Fq2::sub1<8>(Fq29::zero(), b); }   // 8 p - b, b < 8 p
+// K p - b for EVERY normalised b <= K p, plain limbs out.  Fq2::sub1<K>(0, b) runs one parallel carry round over a K p
+// whose limbs 0..7 are lifted by 2^30 and whose top limb is two short for it: when K p - b is below 2^233 (b = 4 p, the
+// conjugate of a zero component; a line coefficient of 8 p - 1) nothing carries into the top limb and it wraps.  Here
+// the carry runs through all nine limbs, so the contract's "at most 4 p" and "below 8 p" hold up to the last value.
+template <int SEL>
+MSM_HD fe29 fq12_neg_exact(const fe29& b) {
+  fe29 r;
+  uint32_t c = 0;
+  MSM_UNROLL for (int i = 0; i < 8; ++i) {
+    const uint32_t t = Fq29::kc(SEL, i) - b.l[i] + c;   // kc >= 2^30 > b.l[i]: no wrap
+    r.l[i] = t & Fq29::MASK;
+    c = t >> 29;
+  }
+  r.l[8] = Fq29::kc(SEL, 8) - b.l[8] + c;
+  return r;
+}
+MSM_HD fe29 fq12_neg1(const fe29& b) { return fq12_neg_exact<K8E30>(b); }   // 8 p - b, b < 8 p
+MSM_HD fe29 fq12_neg4(const fe29& b) { return fq12_neg_exact<K4E30>(b); }   // 4 p - b, b <= 4 p
 MSM_HD fq2 fq2_neg8(const fq2& a) { return fq2{fq12_neg1(a.c0), fq12_neg1(a.c1)}; }
-MSM_HD fq2 fq2_conj(const fq2& a) { return fq2{a.c0, Fq2::sub1<4>(Fq29::zero(), a.c1)}; }   // a.c1 < 4 p
+MSM_HD fq2 fq2_conj(const fq2& a) { return fq2{a.c0, fq12_neg4(a.c1)}; }   // a.c1 <= 4 p
 MSM_HD fq2 fq2_mul_xi(const fq2& a) { return Fq2::mul(Fq12K::xi(), a); }
 MSM_HD fq2 fq2_scale(const fq2& a, const fe29& s) { return fq2{Fq29::mul(a.c0, s), Fq29::mul(a.c1, s)}; }
 MSM_HD fq2 fq2_add_n(const fq2& a, const fq2& b) { return Fq2::norm(Fq2::add(a, b)); }
@@ -301,7 +321,7 @@ MSM_HD void fq12_mul_line(fq12& f, const line_coeffs& l) { fq12_mul_line_t(Fq12P
 
 // a^(p^6): w -> -w
 MSM_HD void fq12_conj(fq12& out, const fq12& a) {
-  MSM_NO_UNROLL for (int i = 0; i < 6; ++i) out.c[i] = (i & 1) ? Fq2::sub<4>(Fq2::zero(), a.c[i]) : a.c[i];
+  MSM_NO_UNROLL for (int i = 0; i < 6; ++i) out.c[i] = (i & 1) ? fq2{fq12_neg4(a.c[i].c0), fq12_neg4(a.c[i].c1)} : a.c[i];
 }
 
 // a^(p^K), K = 1, 2, 3: coefficient i becomes conj^K(a_i) gamma[K][i]
@@ -578,10 +598,10 @@ MSM_HD void fq12_to_raw(uint32_t* w, const fq12& a) {
 // ---- raw-limb test ops (msm_amd_test_fq12_op, msm_amd_test_fq12_op_host) -------------------------------------------------
 // a, b, out: 108 words each.  An fq12 / fq6 sits in the tower order (fq6: the first 54 words).  LINE_MUL: b = l0, l1,
 // l3 (54 words).  DOUBLE_STEP: a = T (X, Y, Z: 54 words), b = x_P, y_P (18 words); out = T' (54 words), then l0, l1, l3.
-// ADD_STEP: the same with Q (x, y: 36 words) behind T in a.
+// ADD_STEP: the same with Q (x, y: 36 words) behind T in a.  FINAL_EXP: fq12_final_exp on the raw element a.
 enum {
   FQ12OP_FQ6_MUL = 0, FQ12OP_MUL, FQ12OP_SQR, FQ12OP_CYCLO_SQR, FQ12OP_LINE_MUL, FQ12OP_FROB1, FQ12OP_FROB2, FQ12OP_FROB3,
-  FQ12OP_CONJ, FQ12OP_INV, FQ12OP_POW_X, FQ12OP_DOUBLE_STEP, FQ12OP_ADD_STEP, FQ12OP_COUNT
+  FQ12OP_CONJ, FQ12OP_INV, FQ12OP_POW_X, FQ12OP_DOUBLE_STEP, FQ12OP_ADD_STEP, FQ12OP_FINAL_EXP, FQ12OP_COUNT
 };
 MSM_HD fq2 fq12raw_fq2(const uint32_t* w) {
   fq2 r;
@@ -652,6 +672,10 @@ MSM_HD void run_test_fq12_op(int op, const uint32_t* a, const uint32_t* b, uint3
     case FQ12OP_CONJ: fq12_conj(r, x); break;
     case FQ12OP_INV: fq12_inv(r, x); break;
     case FQ12OP_POW_X: fq12_pow_x(r, x); break;
+    case FQ12OP_FINAL_EXP:
+      r = x;
+      fq12_final_exp(r);
+      break;
     default: return;
   }
   fq12_to_raw(out, r);

@@ -531,13 +531,15 @@ int msm_amd_final_exponentiation_device(msm_amd_ctx* ctx, int gt_layout, const v
   return final_exp_call(ctx, false, gt_layout, d_in, n, d_out, d_is_one, kernel_ms);
 }
 
-int msm_amd_test_fq12_op(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+int msm_amd_test_fq12_ops(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
-  if (op < 0 || op > MSM_AMD_FQ12_OP_ADD_STEP || !a || !b || !out)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_fq12_op: unknown op or null pointer");
+  if (op < 0 || op > MSM_AMD_FQ12_OP_FINAL_EXP || count > kTestFq12OpsMax)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_fq12_ops: unknown op or more than 2^20 records");
+  if (count == 0) return MSM_AMD_OK;
+  if (!a || !b || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_fq12_ops: null pointer with count > 0");
   DeviceCall c;
-  c.who = "msm_amd_test_fq12_op";
-  const size_t bytes = kPairingPartialWords * sizeof(uint32_t);
+  c.who = "msm_amd_test_fq12_ops";
+  const size_t bytes = count * kPairingPartialWords * sizeof(uint32_t);
   c.all_host(true);
   c.host_in = 3u;
   c.in[0] = a, c.in_bytes[0] = bytes;
@@ -545,9 +547,15 @@ int msm_amd_test_fq12_op(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint
   c.out = out, c.out_bytes = bytes;
   std::lock_guard<std::mutex> lk(ctx->mu);
   return device_call(ctx, c, [&](hipStream_t st, const CallIo& io) -> int {
-    launch_test_fq12_op(st, op, (const uint32_t*)io.in[0], (const uint32_t*)io.in[1], (uint32_t*)io.out, 1);
+    launch_test_fq12_op(st, op, (const uint32_t*)io.in[0], (const uint32_t*)io.in[1], (uint32_t*)io.out, (uint32_t)count);
     return MSM_AMD_OK;
   });
+}
+
+int msm_amd_test_fq12_op(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  if (!a || !b || !out) return fail(ctx, MSM_AMD_INPUT_ERROR, "msm_amd_test_fq12_op: null pointer");
+  return msm_amd_test_fq12_ops(ctx, op, a, b, out, 1);
 }
 
 }  // extern "C"

@@ -19,7 +19,7 @@
 namespace msm_amd {
 
 static_assert(MSM_AMD_GT_MONT_LE == kGtMontLe && MSM_AMD_GT_CANON_LE == kGtCanonLe && MSM_AMD_GT_BYTES == kGtBytes, "GT layouts");
-static_assert(MSM_AMD_FQ12_WORDS == kFq12Words && MSM_AMD_FQ12_OP_ADD_STEP + 1 == FQ12OP_COUNT, "raw fq12 ops");
+static_assert(MSM_AMD_FQ12_WORDS == kFq12Words && MSM_AMD_FQ12_OP_FINAL_EXP + 1 == FQ12OP_COUNT, "raw fq12 ops");
 
 bool pairing_gt_layout_known(int gt_layout) { return gt_layout == MSM_AMD_GT_MONT_LE || gt_layout == MSM_AMD_GT_CANON_LE; }
 
@@ -141,11 +141,18 @@ int msm_amd_test_pairing_plan(size_t n_groups, size_t group_size, uint32_t pairs
   return MSM_AMD_OK;
 }
 
-int msm_amd_test_fq12_op_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+int msm_amd_test_fq12_ops_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
   using namespace msm_amd;
-  if (op < 0 || op >= FQ12OP_COUNT || !a || !b || !out) return MSM_AMD_INPUT_ERROR;
-  run_test_fq12_op(op, a, b, out);
+  if (op < 0 || op >= FQ12OP_COUNT || count > kTestFq12OpsMax) return MSM_AMD_INPUT_ERROR;
+  if (count == 0) return MSM_AMD_OK;
+  if (!a || !b || !out) return MSM_AMD_INPUT_ERROR;
+  for (size_t i = 0; i < count; ++i) run_test_fq12_op(op, a + i * kFq12Words, b + i * kFq12Words, out + i * kFq12Words);
   return MSM_AMD_OK;
+}
+
+int msm_amd_test_fq12_op_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+  if (!a || !b || !out) return MSM_AMD_INPUT_ERROR;
+  return msm_amd_test_fq12_ops_host(op, a, b, out, 1);
 }
 
 }  // extern "C"

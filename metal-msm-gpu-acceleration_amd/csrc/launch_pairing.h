@@ -55,6 +55,8 @@ void launch_pairing_fold(hipStream_t st, const uint32_t* in, uint32_t n_groups, 
 // gt_layout.  miller_only: no exponentiation, the value is only converted.
 void launch_pairing_final(hipStream_t st, const void* in, bool in_raw, uint32_t n, bool miller_only, int gt_layout, void* out,
                           uint8_t* is_one);
+// one lane per record of 108 words each way; count at most kTestFq12OpsMax (msm_amd_test_fq12_ops*)
+constexpr uint64_t kTestFq12OpsMax = 1u << 20;
 void launch_test_fq12_op(hipStream_t st, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t count);
 
 }  // namespace msm_amd

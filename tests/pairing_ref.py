@@ -38,7 +38,8 @@ PAIRING_MILLER_ONLY = 1
 GT_BYTES = 384
 # msm_amd_test_fq12_op
 (FQ12_OP_FQ6_MUL, FQ12_OP_MUL, FQ12_OP_SQR, FQ12_OP_CYCLO_SQR, FQ12_OP_LINE_MUL, FQ12_OP_FROB1, FQ12_OP_FROB2,
- FQ12_OP_FROB3, FQ12_OP_CONJ, FQ12_OP_INV, FQ12_OP_POW_X, FQ12_OP_DOUBLE_STEP, FQ12_OP_ADD_STEP) = range(13)
+ FQ12_OP_FROB3, FQ12_OP_CONJ, FQ12_OP_INV, FQ12_OP_POW_X, FQ12_OP_DOUBLE_STEP, FQ12_OP_ADD_STEP,
+ FQ12_OP_FINAL_EXP) = range(14)
 FQ12_WORDS = 108
 
 

@@ -60,7 +60,7 @@ def test_raw_ops_match_the_limb_model_and_the_host(cfg, msm_pkg):
         check_raw_outputs(name, w)
         assert w == msm_pkg.test_fq12_op_host(op, a, b), name          # bit for bit, limbs included
     z = (ctypes.c_uint32 * 108)()
-    assert msm_pkg.lib().msm_amd_test_fq12_op(cfg.h, 13, z, z, z) == msm_pkg.INPUT_ERROR
+    assert msm_pkg.lib().msm_amd_test_fq12_op(cfg.h, 14, z, z, z) == msm_pkg.INPUT_ERROR
     assert msm_pkg.lib().msm_amd_test_fq12_op(cfg.h, -1, z, z, z) == msm_pkg.INPUT_ERROR
 
 

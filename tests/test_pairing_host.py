@@ -246,12 +246,18 @@ def raw_cases(rng):
     for negated in (False, True):                   # Q.y canonical, or a negation at 4 p - y
         qw, qq = g2.aff_rec(q_aff, rng, negated)
         yield "add", pr.FQ12_OP_ADD_STEP, tw + qw, pw, lambda w, qq=qq: step_ok(w, pr.add_step(T, qq, p1))
-    # T = Q and T = -Q: zeros, no fault (division-free)
+    # T = Q: zeros throughout.  T = -Q: the point at infinity (0, Y', 0) and the vertical line (0, l1, l3), as the
+    # polynomial map gives them.  No fault either way (division-free)
     t1 = (q_aff[0], q_aff[1], pr.ONE2)
     t1w = sum((g2.fq2_rec(c, 1, rng) for c in t1), [])
     qw, _ = g2.aff_rec(q_aff, rng)
     yield "add T=Q", pr.FQ12_OP_ADD_STEP, t1w + qw, pw, \
         lambda w: all(g2.fq2_of(w[18 * k:18 * k + 18]) == pr.ZERO2 for k in range(6))
+    t2 = (q_aff[0], pr.neg2(q_aff[1]), pr.ONE2)
+    t2w = sum((g2.fq2_rec(c, 4, rng) for c in t2), [])
+    want2 = pr.add_step(t2, q_aff, p1)
+    assert want2[0][0] == want2[0][2] == want2[1][0] == pr.ZERO2 and pr.ZERO2 not in (want2[0][1], want2[1][1], want2[1][2])
+    yield "add T=-Q", pr.FQ12_OP_ADD_STEP, t2w + qw, pw, lambda w: step_ok(w, want2)
 
 
 def check_raw_outputs(name, w):
@@ -259,7 +265,7 @@ def check_raw_outputs(name, w):
     comps = [g2.value(w[9 * i:9 * i + 9]) for i in range(12)]
     assert g2.normalised(w, 12), name
     assert all(v <= 8 * pr.P for v in comps), name
-    if name not in ("double", "add", "add T=Q"):
+    if name not in ("double", "add", "add T=Q", "add T=-Q"):
         assert all(v <= 4 * pr.P for v in comps), name
 
 
@@ -269,7 +275,7 @@ def test_raw_ops_on_the_host_match_the_limb_model(msm_pkg):
             w = msm_pkg.test_fq12_op_host(op, a, b)
             assert ok(w), name
             check_raw_outputs(name, w)
-    assert msm_pkg.lib().msm_amd_test_fq12_op_host(13, (ctypes.c_uint32 * 108)(), (ctypes.c_uint32 * 108)(),
+    assert msm_pkg.lib().msm_amd_test_fq12_op_host(14, (ctypes.c_uint32 * 108)(), (ctypes.c_uint32 * 108)(),
                                                    (ctypes.c_uint32 * 108)()) == msm_pkg.INPUT_ERROR
     assert msm_pkg.lib().msm_amd_test_fq12_op_host(-1, (ctypes.c_uint32 * 108)(), (ctypes.c_uint32 * 108)(),
                                                    (ctypes.c_uint32 * 108)()) == msm_pkg.INPUT_ERROR
@@ -333,14 +339,16 @@ def test_exports_constants_and_bindings(msm_pkg):
     for name in ("msm_amd_pairing_product", "msm_amd_pairing_product_device", "msm_amd_host_pairing_product",
                  "msm_amd_final_exponentiation", "msm_amd_final_exponentiation_device",
                  "msm_amd_host_final_exponentiation", "msm_amd_test_pairing_plan", "msm_amd_test_fq12_op",
-                 "msm_amd_test_fq12_op_host"):
+                 "msm_amd_test_fq12_op_host", "msm_amd_test_fq12_ops", "msm_amd_test_fq12_ops_host"):
         assert name in msm_pkg.EXPORTS and hasattr(L, name)
     hdr = open(os.path.join(ROOT, "include", "msm_amd.h")).read()
     for text in ("MSM_AMD_GT_MONT_LE = 0", "MSM_AMD_GT_CANON_LE = 1", "MSM_AMD_GT_BYTES = 384",
-                 "MSM_AMD_PAIRING_MILLER_ONLY = 1", "MSM_AMD_FQ12_OP_ADD_STEP = 12", "MSM_AMD_FQ12_WORDS = 108"):
+                 "MSM_AMD_PAIRING_MILLER_ONLY = 1", "MSM_AMD_FQ12_OP_ADD_STEP = 12", "MSM_AMD_FQ12_OP_FINAL_EXP = 13",
+                 "MSM_AMD_FQ12_WORDS = 108"):
         assert text in hdr
     assert (msm_pkg.GT_MONT_LE, msm_pkg.GT_CANON_LE, msm_pkg.GT_BYTES, msm_pkg.PAIRING_MILLER_ONLY) == (0, 1, 384, 1)
     assert msm_pkg.FQ12_OP_ADD_STEP == 12 == pr.FQ12_OP_ADD_STEP and msm_pkg.FQ12_WORDS == 108
+    assert msm_pkg.FQ12_OP_FINAL_EXP == 13 == pr.FQ12_OP_FINAL_EXP
     for f in ("pairing_product", "pairing_product_device", "final_exponentiation", "final_exponentiation_device",
-              "test_fq12_op"):
+              "test_fq12_op", "test_fq12_ops"):
         assert hasattr(msm_pkg.MsmConfig, f)

@@ -83,8 +83,13 @@ int main() {
     expect(msm_amd_test_pairing_plan(3, 130, 4, 0, plan) == MSM_AMD_OK && plan[0] == 4 && plan[1] == 33 && plan[2] == 3 && plan[3] == 1, "plan");
     std::vector<uint32_t> a(MSM_AMD_FQ12_WORDS, 0), b(MSM_AMD_FQ12_WORDS, 0), out(MSM_AMD_FQ12_WORDS);
     a[0] = 5, b[0] = 7;
-    for (int op = 0; op <= MSM_AMD_FQ12_OP_ADD_STEP; ++op) expect(msm_amd_test_fq12_op_host(op, a.data(), b.data(), out.data()) == MSM_AMD_OK, "raw op");
-    expect(msm_amd_test_fq12_op_host(13, a.data(), b.data(), out.data()) == MSM_AMD_INPUT_ERROR, "unknown op");
+    for (int op = 0; op <= MSM_AMD_FQ12_OP_FINAL_EXP; ++op) expect(msm_amd_test_fq12_op_host(op, a.data(), b.data(), out.data()) == MSM_AMD_OK, "raw op");
+    expect(msm_amd_test_fq12_op_host(14, a.data(), b.data(), out.data()) == MSM_AMD_INPUT_ERROR, "unknown op");
+    // the batched form on exactly sized buffers: three records each way
+    std::vector<uint32_t> a3(3 * MSM_AMD_FQ12_WORDS, 0), b3(3 * MSM_AMD_FQ12_WORDS, 0), out3(3 * MSM_AMD_FQ12_WORDS);
+    for (int i = 0; i < 3; ++i) a3[i * MSM_AMD_FQ12_WORDS] = 5 + i, b3[i * MSM_AMD_FQ12_WORDS] = 7;
+    expect(msm_amd_test_fq12_ops_host(MSM_AMD_FQ12_OP_MUL, a3.data(), b3.data(), out3.data(), 3) == MSM_AMD_OK, "raw ops");
+    expect(msm_amd_test_fq12_ops_host(MSM_AMD_FQ12_OP_MUL, nullptr, nullptr, nullptr, 0) == MSM_AMD_OK, "raw ops, count 0");
   }
   std::printf(failures ? "pairing_asan_check: %d failure(s)\n" : "pairing_asan_check: ok\n", failures);
   return failures ? 1 : 0;
