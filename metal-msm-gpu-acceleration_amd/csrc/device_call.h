@@ -2,7 +2,8 @@
 // One driver for all of them (device_call): the device set, a bounded drain of the ctx's earlier work, every buffer sized
 // on the idle ctx before anything is enqueued, host input through the page-locked staging ring, the caller's kernels on
 // the main stream (between events when the call is timed), the 64-byte record of a call that has one behind a bounded
-// wait, output and reason bytes behind a bounded stream wait.  Each call below validates its own arguments, takes
+// wait, output and reason bytes behind a bounded stream wait.  The test ops and the reference-shaped prepare and sort
+// stage entries (calls_stages.hip) run on it as well.  Each call validates its own arguments, takes
 // ctx->mu, describes its buffers in a DeviceCall and passes a callable that enqueues its kernels; one that takes the
 // finished record, and the kernels that follow it, are optional.
 #pragma once

@@ -5,7 +5,8 @@
 // namespace (every unit must see the same ones now), are in msm_amd::drv, with hidden visibility, so that nothing here
 // becomes an exported name of the library (the attribute does not carry over to a reopened namespace: msm_host.hip
 // repeats it).  The list is closed on purpose: nothing of the planner, the instance pipeline, the uploader or the bases
-// cache is declared here.
+// cache is declared here; what the units of the MSM driver itself (msm_host.hip, msm_plan.hip, msm_g2.hip,
+// calls_stages.hip) take from each other is in msm_driver.h, which the vector calls do not include.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -8,23 +8,24 @@
 // bucket_wise_accumulation.rs:104-105, sum_reduction.rs:80-81); the only device->host hand-off is the
 // (c-2)*W partial window points for the host Horner pass.
 //
-// This file is the MSM driver: the ctx's lifecycle, bounded waits and buffer growth, the staging ring and uploader, the
-// bases cache, the planner, the instance pipeline of G1 and G2, the stage entry points and taps.  The ctx and the other
-// types are in host_ctx.h.  The blocking vector calls (point calls, transforms, vectors over Fr) are units of their own --
-// calls_points.hip, calls_ntt.hip, calls_fr.hip, all on device_call.h -- and reach into this file only through the
-// helpers host_ctx.h declares (msm_amd::drv, defined below).
+// This file is the ctx and the G1 pipeline: the ctx's lifecycle, bounded waits and buffer growth, the staging ring and
+// uploader, the bases cache, the instance pipeline (enqueue_instance is the body of a G2 instance too), the G1 entry
+// points and the small device utilities.  The ctx and the other types are in host_ctx.h.  The planner is msm_plan.hip,
+// the G2 MSM msm_g2.hip, the stage entry points and the test aids calls_stages.hip; what those three and this file take
+// from each other is declared in msm_driver.h.  The blocking vector calls (point calls, transforms, vectors over Fr) are
+// units of their own -- calls_points.hip, calls_ntt.hip, calls_fr.hip, all on device_call.h -- and reach into this file
+// only through the helpers host_ctx.h declares.  Every msm_amd::drv helper of this file is defined in the one block
+// below, between the anonymous namespace it needs and the one that needs it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <array>
 #include <atomic>
 #include <chrono>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <condition_variable>
-#include <functional>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -34,17 +35,13 @@
 #include "../../include/msm_amd.h"
 #include "device_common.hip.h"
 #include "launch.h"
-#include "launch_g2.h"
 #include "launch_check.h"
-#include "launch_compress.h"
 #include "launch_mul.h"
 #include "launch_fr.h"
 #include "launch_ntt.h"
 #include "launch_nttp.h"
 #include "host_fq64.h"
-#include "test_ops.hip.h"
-#include "test_ops_g2.hip.h"
-#include "host_ctx.h"
+#include "msm_driver.h"
 
 using namespace msm_amd;
 
@@ -56,16 +53,6 @@ msm_amd_ctx* g_global_ctx = nullptr;
 // A helper thread of the library (the uploader) reports through its own string: ctx->last_error belongs to the thread
 // that holds ctx->mu.
 thread_local std::string* tl_error_sink = nullptr;
-
-}  // namespace
-namespace msm_amd { namespace drv __attribute__((visibility("hidden"))) {
-int fail(msm_amd_ctx* ctx, int status, const std::string& msg) {
-  if (tl_error_sink) *tl_error_sink = msg;
-  else if (ctx) ctx->last_error = msg;
-  return status;
-}
-}}  // namespace msm_amd::drv
-namespace {
 
 // Wait for everything this ctx has enqueued (error paths and set-up steps that reuse workspace 0).
 void drain_streams(msm_amd_ctx* ctx) {
@@ -100,30 +87,6 @@ bool drain_streams_bounded(msm_amd_ctx* ctx) {
   return true;
 }
 
-// hipEventSynchronize may park the thread (it did, for more than a millisecond, inside a process that also hosts
-// torch's thread pools) and it waits without bound: a device that stalls would block the caller of a blocking MSM
-// for ever, where the reference's call always returns (msm.rs:237-349).  The waits on the critical path therefore
-// poll the event -- spinning for the first few milliseconds, then with short sleeps -- up to `timeout_ms`
-// (0 = unbounded) and report hipErrorNotReady when the bound is reached.
-hipError_t wait_event(hipEvent_t ev, uint32_t timeout_ms) {
-  const auto t0 = std::chrono::steady_clock::now();
-  for (;;) {
-    const hipError_t q = hipEventQuery(ev);
-    if (q == hipSuccess) return hipSuccess;
-    if (q != hipErrorNotReady) {
-      (void)hipGetLastError();
-      return q;
-    }
-    (void)hipGetLastError();
-    const auto waited = std::chrono::steady_clock::now() - t0;
-    if (timeout_ms && waited > std::chrono::milliseconds(timeout_ms)) return hipErrorNotReady;
-    if (waited > std::chrono::milliseconds(4))
-      std::this_thread::sleep_for(std::chrono::microseconds(50));
-    else
-      __builtin_ia32_pause();
-  }
-}
-
 uint32_t default_wait_timeout_ms() {
   if (const char* e = std::getenv("MSM_AMD_WAIT_TIMEOUT_MS")) return (uint32_t)std::strtoul(e, nullptr, 10);
   return 60000;
@@ -131,365 +94,8 @@ uint32_t default_wait_timeout_ms() {
 
 const char* const kEventNames[] = {"start", "convert", "digits", "sort", "accumulate-start", "accumulate", "reduce"};
 
-}  // namespace
-namespace msm_amd { namespace drv __attribute__((visibility("hidden"))) {
-// A wait on this ctx ran into its bound earlier.  Before anything new is enqueued: has the device caught up?  If every
-// stream is idle the batches a blocking entry point abandoned are released; otherwise the call fails like the wait did.
-int recover_if_stalled(msm_amd_ctx* ctx) {
-  if (!ctx->stalled) return MSM_AMD_OK;
-  if (!streams_idle(ctx))
-    return fail(ctx, MSM_AMD_PIPELINE_ERROR,
-                "the device is still busy with work whose wait timed out earlier (msm_amd_synchronize waits again; "
-                "msm_amd_destroy gives the ctx up)");
-  for (Batch& b : ctx->batches)
-    if (b.abandoned) b.active = b.abandoned = false;
-  ctx->stalled = false;
-  return MSM_AMD_OK;
-}
-}}  // namespace msm_amd::drv
-namespace {
-
-// Nothing of this ctx is in flight (every submitted batch has been waited for): outgrown buffers can go.
-void reap_graveyard(msm_amd_ctx* ctx) {
-  if (ctx->graveyard.empty() || ctx->stalled) return;
-  for (const Batch& b : ctx->batches)
-    if (b.active) return;
-  for (void* p : ctx->graveyard) (void)hipFree(p);
-  (void)hipGetLastError();
-  ctx->graveyard.clear();
-}
-
-}  // namespace
-namespace msm_amd { namespace drv __attribute__((visibility("hidden"))) {
-// hipMalloc / hipHostMalloc / hipFree / hipHostFree may wait for the device (hipFree always does).  With work in flight
-// on a device that does not answer they would block without bound, before any bounded wait is reached -- so nothing
-// is allocated or released while the ctx has work in flight: a buffer that must grow first waits, WITH the ctx's wait
-// bound, for the ctx's streams to run empty, and the call fails with MSM_AMD_PIPELINE_ERROR if they do not.  (On a
-// healthy device this costs a pipeline drain on the first use of a workspace, never in steady state.)
-int quiesce_for_allocation(msm_amd_ctx* ctx, const char* what) {
-  if (streams_idle(ctx)) return MSM_AMD_OK;
-  if (drain_streams_bounded(ctx)) return MSM_AMD_OK;
-  ctx->stalled = true;
-  return fail(ctx, MSM_AMD_PIPELINE_ERROR,
-              std::string("device busy past the wait bound of ") + std::to_string(ctx->wait_timeout_ms) +
-                  " ms: cannot grow " + what + " while earlier work is in flight (msm_amd_synchronize waits again)");
-}
-
-// hipStreamSynchronize with the ctx's wait bound (the stream is polled): PIPELINE_ERROR, ctx marked stalled, when the
-// device does not get there.
-int sync_stream_bounded(msm_amd_ctx* ctx, hipStream_t st, const char* what) {
-  const auto t0 = std::chrono::steady_clock::now();
-  for (;;) {
-    const hipError_t q = hipStreamQuery(st);
-    if (q == hipSuccess) return MSM_AMD_OK;
-    (void)hipGetLastError();
-    if (q != hipErrorNotReady)
-      return fail(ctx, MSM_AMD_PIPELINE_ERROR, std::string("hipStreamQuery (") + what + "): " + hipGetErrorString(q));
-    const auto waited = std::chrono::steady_clock::now() - t0;
-    if (ctx->wait_timeout_ms && waited > std::chrono::milliseconds(ctx->wait_timeout_ms)) {
-      ctx->stalled = true;
-      return fail(ctx, MSM_AMD_PIPELINE_ERROR, "timed out after " + std::to_string(ctx->wait_timeout_ms) +
-                                                   " ms waiting for the stream (" + what + ")");
-    }
-    if (waited > std::chrono::milliseconds(2)) std::this_thread::sleep_for(std::chrono::microseconds(50));
-    else __builtin_ia32_pause();
-  }
-}
-
-bool drain_or_mark_stalled(msm_amd_ctx* ctx) {
-  if (drain_streams_bounded(ctx)) return true;
-  ctx->stalled = true;
-  return false;
-}
-
-int ensure(msm_amd_ctx* ctx, DeviceBuf& b, size_t bytes) {
-  if (bytes <= b.cap) return MSM_AMD_OK;
-  if (int rc = quiesce_for_allocation(ctx, "a device workspace")) return rc;
-  if (b.p) ctx->graveyard.push_back(b.p);   // freed later, see msm_amd_ctx::graveyard
-  b.p = nullptr;
-  b.cap = 0;
-  // grow by 25% to avoid re-allocating for every slightly larger instance
-  const size_t want = bytes + bytes / 4;
-  HIP_TRY(ctx, hipMalloc(&b.p, want));
-  b.cap = want;
-  return MSM_AMD_OK;
-}
-}}  // namespace msm_amd::drv
-namespace {
-
-uint32_t floor_log2(size_t n) {
-  uint32_t l = 0;
-  while ((n >> (l + 1)) != 0) ++l;
-  return l;
-}
-
-uint32_t auto_window(size_t n) {
-  // The reference uses 3 below 32 points and 15 from there on (msm.rs:137-141).  Measured on MI355X in pipelined
-  // batches (ms per MSM, round 2 -- the row / column-sum reduction made buckets cheaper, which moved every
-  // boundary one size down): 2^12 c=5 0.23 | 2^14 c=5 0.24 | 2^16 c=13 0.33 | 2^18 c=15 0.47 (16: 0.50) |
-  // 2^19 c=16 0.79 (15: 0.80, 17: 0.84) | 2^20 c=17 1.41 (16: 1.43, 15: 1.54) | 2^21 c=17 2.72 (16: 2.83) |
-  // 2^22 c=17 5.82 (16: 6.21).  Windows whose TOP digit is narrow are traps: the n entries of the top window then
-  // share a handful of buckets (c = 14 leaves 2 bits for the top window of a 254-bit scalar, c = 11 one bit: 2^17
-  // points cost 1.2 ms with c = 10 or 11, 0.38 with 15).
-  if (n < 32) return 3;   // msm.rs:137-138
-  const uint32_t l = floor_log2(n);
-  if (l <= 14) return 5;
-  if (l <= 18) return 15;   // 2^16 in batches of 40 after the 64-bit host pass: c=15 0.207, c=13 0.233, c=16 0.246 ms per MSM
-  if (l == 19) return 16;   // u32 digits from here on
-  return kMaxWindow;
-}
-
-// Window size of a LONE call (one instance, nothing else in flight: lone_call()).  The pipelined policy above minimises
-// GPU work per MSM; a lone call is a chain of launches and of dependent point additions, where a wide window costs
-// little (the window reduction is a fixed number of levels, the accumulate kernel is far from filling the machine)
-// and a narrow top window costs a lot (split buckets -> the combine pass).  Median ms of one blocking device-resident
-// call on MI355X (tools/lone_latency.py, profiles/r02_lone_call_window_sweep.txt), best | pipelined policy:
-//   2^8 c=8 0.346 | c=5 0.357     2^12 c=8 0.446 | c=5 0.538     2^14 c=15 0.487 | c=5 0.596
-//   2^16 c=15 0.543 | c=13 0.661  2^18 c=15 0.810 (16: 0.796)    2^19 c=17 1.201 | c=16 1.253
-uint32_t auto_window_lone(size_t n) {
-  if (n < 32) return 3;
-  const uint32_t l = floor_log2(n);
-  if (l <= 6) return 5;
-  if (l <= 12) return 8;
-  if (l <= 18) return 15;
-  return kMaxWindow;
-}
-
-// Window of a bounded call (msm_amd_msm_bounded*).  254 bits: the two policies above.  Below: read from the sweep of every
-// window 3..17 at 2^16, 2^18, 2^20, 2^22 points x 1, 8, 16, 32, 64, 128 bits, lone and pipelined, uniform scalars below
-// 2^bits on prepared bases (tools/bounded_bench.py --sweep, profiles/bounded_sweep.txt; ms per MSM).  What it shows:
-//  - the window count W = bits / c + 1 decides first: every window sorts and accumulates all n entries.  One window
-//    that holds the whole scalar (c = bits + 1, no digit is ever negative) is the fastest form of every width up to 16:
-//    8 bits c = 9 (2^22 pipelined 0.57; c = 17: 5.87, c = 5: 2.68), 16 bits c = 17 (2^22: 0.56; c = 9: 0.83, c = 15: 7.4);
-//  - the trap of auto_window is much deeper here, because a short scalar has few other windows to hide it behind: a top
-//    digit of t = bits - (W - 1) c bits puts n entries into 2^t buckets.  32 bits at 2^20 pipelined: c = 17 (t = 15)
-//    0.35, c = 16 (the top window holds the carry alone) 2.2, c = 13 (t = 6) 1.45.  The rule below takes the fewest
-//    windows among the c whose top digit is full (t = c - 1) or wide enough that a bucket stays below the longest work
-//    item (2^t >= n / 512), and the widest top digit if there is none;
-//  - at 2^16 and 2^18 points the 2^16 buckets per window of c = 17 cost more than a fifth window saves: 64 and 128 bits
-//    want c = 13 there (2^18 lone 64 bits: 0.455 | c = 17 0.499; 128 bits: 0.674 | 0.791; pipelined 0.233 | 0.282 and
-//    0.367 | 0.593), and so does every width in a pipeline of 2^16-point instances (32 bits: c = 11 0.163 | c = 17 0.204);
-//  - 128 bits from 2^20 points: c = 10 (W = 13, t = 8) beats the rule's c = 13 at 2^20 (pipelined 1.22 | 1.83, lone
-//    1.94 | 2.78) and ties with it at 2^22 (4.31 | 4.15, lone 5.50 | 5.77): no reading of the other cells explains it,
-//    so it stands as an exception for the width of a 128-bit challenge alone;
-//  - one bit: no window differs by more than the spread (every point lands in slot 1; 2^20 lone 4.49 .. 4.52).
-// Cells where the rule is not the fastest window: 2^16 pipelined 16 bits (c = 9 0.179 | c = 6 0.152), 2^18 pipelined
-// 16 bits (c = 17 0.199 | c = 9 0.181), 2^22 pipelined 128 bits (above); all others within 3 %.  Sizes below 2^15 were
-// not swept: they keep the window of the unbounded call (and still run bits / c + 1 windows of it).
-uint32_t auto_window_bounded(size_t n, uint32_t bits, bool lone) {
-  const uint32_t c0 = lone ? auto_window_lone(n) : auto_window(n);
-  if (bits >= kModulusBits) return c0;
-  const uint32_t l = floor_log2(n);
-  if (l < 15) return c0;
-  uint32_t cmax = (uint32_t)kMaxWindow;
-  if ((!lone && l <= 17) || (l <= 18 && bits / kMaxWindow + 1 >= 4)) cmax = 13;
-  if (l >= 19 && bits > 124 && bits <= 128) return 10;
-  if (bits + 1 <= cmax) return std::max<uint32_t>(kMinWindow, bits + 1);   // one window, every digit positive
-  uint32_t best = cmax, best_W = 0, best_t = 0;
-  bool best_ok = false;
-  for (uint32_t c = 9; c <= cmax; ++c) {
-    const uint32_t W = bits / c + 1, t = bits - (W - 1) * c;
-    const bool ok = t >= std::min(c - 1, l > 9 ? l - 9 : 0u);
-    bool take;
-    if (ok != best_ok) take = ok;
-    else if (ok) take = best_W == 0 || W < best_W || (W == best_W && l >= 19);   // ties: the larger window from 2^19 points
-    else take = best_W == 0 || t > best_t || (t == best_t && l >= 19);
-    if (take) best = c, best_W = W, best_t = t, best_ok = ok;
-  }
-  return best;
-}
-
-// `windows` = 0: the per-call pipeline (every signed-digit window owns a bucket set).  `windows` > 0: the
-// precomputed-table pipeline of a table with that many windows, where the [W_digits][n_scalars] digit matrix is sorted
-// as ONE window of W_digits * n_scalars entries whose "point index" addresses the table entry 2^(c w) P_i directly (the
-// table is window-major: a bounded call's W_digits windows are a prefix of it).
-// `width`: magnitudes stay below 2^width.width() (scalar_width.hip.h) -- W_digits = width / c + 1 windows, of which the
-// top one holds at most c - 1 bits and so absorbs the last carry (254 bits: ceil(255 / c)).  Everything below follows
-// from W_digits, W and n.
-Plan make_plan(size_t n_scalars, uint32_t c, uint32_t windows = 0, WidthBound width = WidthBound{}) {
-  Plan p{};
-  p.c = c;
-  p.W_digits = width.width() / c + 1;
-  if (!(width.bits == kScalarBits && !width.sign)) p.bits = width.bits, p.sign = width.sign;   // 254 unsigned: the unbounded plan
-  if (windows) windows = std::min(windows, p.W_digits);
-  const size_t n = windows ? n_scalars * windows : n_scalars;
-  p.n = (uint32_t)n;
-  p.W = windows ? 1u : p.W_digits;
-  p.n_scalars = (uint32_t)n_scalars;
-  p.wide_digits = c > 15;
-  p.lb = std::max(c - 1, (uint32_t)kSegLog);
-  p.nb = 1u << p.lb;                  // slot i <-> digit magnitude i + 1 (c = 3 is padded to 8 slots)
-  // sort / planning workgroup size: big workgroups are the fastest alone, but they can hardly be placed while
-  // an accumulate grid of another instance is resident (they need 16 free wave slots on one CU at once)
-  p.front_threads = 1024;
-  if (const char* e = std::getenv("MSM_AMD_FRONT_THREADS")) {
-    const int v = std::atoi(e);
-    if (v == 256 || v == 512 || v == 1024) p.front_threads = (uint32_t)v;
-  }
-  // sort pass 1: one workgroup per (chunk, window); about 2 x 1024 threads per CU in total
-  uint32_t Q = std::max(1u, (512u * (1024u / p.front_threads)) / p.W);
-  const uint32_t max_q = (uint32_t)((n + 4095) / 4096);
-  Q = std::max(1u, std::min(Q, max_q));
-  p.Q = Q;
-  p.chunk = (uint32_t)((((n + Q - 1) / Q) + 63) & ~(size_t)63);
-  // Sort geometry.  Pass 2 sorts a region inside LDS, so the coarse passes must cut a window into regions of
-  // ~16 k entries: T = ceil(log2(n / 16384)) coarse bits.  Up to 7 bits (128 regions) one coarse pass does it
-  // (every per-call plan up to 2^21 points); beyond that the bits are split over TWO coarse passes of <= 6 bits
-  // each (hb + mb, three-level sort): one pass with 1024 regions keeps too many partially written lines open
-  // (2^24 points: 10.2 ms), and 128 regions of 131 k entries force pass 2 to scatter in global memory (6.0 ms).
-  uint32_t T = 0;
-  while (T + 2 < p.lb && (n >> T) > 16384) ++T;
-  uint32_t hb = T, mb = 0;
-  if (T > 7) {
-    hb = (T + 1) / 2;
-    mb = T - hb;
-  }
-  if (const char* e = std::getenv("MSM_AMD_HB")) {   // experiments: coarse bits of the two-pass sort
-    const int v = std::atoi(e);
-    if (v >= 0 && (uint32_t)v + 2 <= p.lb) {
-      hb = (uint32_t)v;
-      mb = 0;
-    }
-  }
-  if (const char* e = std::getenv("MSM_AMD_MB")) {   // experiments: middle-pass bits
-    const int v = std::atoi(e);
-    if (v >= 0 && hb + (uint32_t)v + 2 <= p.lb) mb = (uint32_t)v;
-  }
-  p.hb = hb;
-  p.mb = mb;
-  p.fb = p.lb - hb - mb;
-  if (p.fb > 10) {   // the fine histogram is scanned with one bin per thread (<= 1024 bins)
-    const uint32_t extra = p.fb - 10;
-    p.fb = 10;
-    if (p.mb || p.hb + extra > 7) p.mb += extra; else p.hb += extra;
-  }
-  // what pass 1 leaves in the u16 tmp_fine is mb + fb bits
-  while (p.mb + p.fb > 16) {
-    ++p.hb;
-    --p.mb;
-  }
-  // Tile-staged scatter (k_sort.hip tile_scatter): 26 % less sort time for ONE huge instance (2^24 points: 7.0 ->
-  // 5.2 ms with 1024-thread workgroups), but its 60 VGPRs x 1024 threads cannot be placed beside a resident
-  // accumulate grid, so inside a pipeline of instances it loses (headline 695 -> 643 MSM/s; with 512 threads: no
-  // difference to the direct scatter).  Used where the sort is not hidden behind another instance's accumulation:
-  // per-call plans that need the three-level sort (2^22 points and more).
-  p.tiled = (p.mb != 0 && windows == 0) ? 1u : 0u;
-  if (const char* e = std::getenv("MSM_AMD_TILED")) p.tiled = std::atoi(e) != 0;
-  p.tile_threads = 1024;
-  if (const char* e = std::getenv("MSM_AMD_TILE_THREADS")) {
-    const int v = std::atoi(e);
-    if (v == 256 || v == 512 || v == 1024) p.tile_threads = (uint32_t)v;
-  }
-  p.ballot = kDefaultBallot;
-  if (const char* e = std::getenv("MSM_AMD_BALLOT")) p.ballot = (uint32_t)std::atoi(e) & 3u;
-  // front-end traffic: digits_hist_kernel counts the digits it has just made, and where index, sign and fine digit
-  // fit one u32 (headline: 20 + 1 + 10 bits) pass 1 hands pass 2 one array instead of two (k_sort.hip)
-  p.fused_front = windows == 0;
-  p.packed = p.mb == 0 && n >= 1 && floor_log2(std::max<size_t>(n - 1, 1)) + 1 + 1 + p.fb <= 32;
-  p.Q2 = 1;
-  if (p.mb) {
-    const uint32_t regions = p.W << p.hb;
-    p.Q2 = std::max(1u, 1024u / regions);
-    while (p.Q2 > 1 && (n >> p.hb) / p.Q2 < 4096) p.Q2 >>= 1;
-  }
-  // accumulate work items: at most CH points each; buckets longer than CH are cut into several items whose partial
-  // sums the combine kernels add up (one extra full addition per cut, and a second affine+affine start).  Uniform
-  // scalars must split (almost) nothing: CH >= mean + 5 sigma of the Poisson bucket size (2^20 points, c = 16: mean
-  // 32, CH = 64; the round-1 rule picked 32 there and cut 228 k of 524 k buckets in two).  Only when the buckets
-  // alone cannot fill the chip twice (2 waves/SIMD x 1024 SIMDs x 64 lanes = 131 k lanes per round) are items made
-  // shorter on purpose.  Skewed inputs (equal scalars, narrow top windows) still get cut at CH.
-  const double mean_len = (double)n / (double)p.nb;
-  uint32_t ch = 16;
-  while (ch < 512 && (double)ch < mean_len + 5.0 * std::sqrt(mean_len)) ch <<= 1;
-  while (ch > 16 && (size_t)p.W * p.nb + ((size_t)p.W * n) / ch < 262144) ch >>= 1;
-  if (const char* e = std::getenv("MSM_AMD_CH")) {
-    const int v = std::atoi(e);
-    if (v >= 16 && v <= 512 && (v & (v - 1)) == 0) ch = (uint32_t)v;
-  }
-  p.CH = ch;
-  p.red_L = (p.lb + 1) / 2;
-  p.red_H = p.lb - p.red_L;
-  p.red_group = kReduceGroup;
-  p.total_buckets = (size_t)p.W * p.nb;
-  p.total_segs = (size_t)p.W * reduce_scratch_elems(p.lb);   // scratch elements of each of the two sum families
-  p.max_items = p.total_buckets + ((size_t)p.W * n) / ch + 1;
-  p.partial_count = (size_t)p.W * (p.lb + 1);
-  return p;
-}
-
-// Geometry of the window reduction alone (stage entry point sum_reduction).
-Plan make_reduce_plan(uint32_t lb, uint32_t W) {
-  Plan p{};
-  p.c = lb + 1;   // only used to space bit positions in host_combine (one window at a time)
-  p.W = W;
-  p.lb = lb;
-  p.nb = 1u << lb;
-  p.red_L = (lb + 1) / 2;
-  p.red_H = lb - p.red_L;
-  p.red_group = kReduceGroup;
-  p.total_buckets = (size_t)p.W * p.nb;
-  p.total_segs = (size_t)p.W * reduce_scratch_elems(lb);
-  p.partial_count = (size_t)p.W * (lb + 1);
-  return p;
-}
-
-// ---- host-side big-endian-limb helpers (reference wire layout) ----------------------------------
-u256 be32_to_u256(const uint32_t* l) {
-  u256 r;
-  for (int i = 0; i < 8; ++i) r.v[i] = l[7 - i];
-  return r;
-}
-void u256_to_be32(const u256& a, uint32_t* l) {
-  for (int i = 0; i < 8; ++i) l[i] = a.v[7 - i];
-}
-Jacobian be32_to_jac(const uint32_t* l) {
-  Jacobian r;
-  r.x = be32_to_u256(l);
-  r.y = be32_to_u256(l + 8);
-  r.z = be32_to_u256(l + 16);
-  return r;
-}
-void jac_to_be32(const Jacobian& p, uint32_t* l) {
-  u256_to_be32(p.x, l);
-  u256_to_be32(p.y, l + 8);
-  u256_to_be32(p.z, l + 16);
-}
-
 // Normalise to z = R mod p (or the canonical identity (1,1,0) in Montgomery form).
 Jacobian normalise(const Jacobian& p) { return h64::store(h64::normalise(h64::load(p))); }
-
-// E' -> E for a Jacobian point (Plan::on_iso): x = 4 x', y = 8 y' is Z <- Z / 2.  The identity (Z = 0) stays.
-Jacobian iso_to_e(const Jacobian& q) {
-  static const h64::Fe half = h64::inv(h64::dbl(h64::one()));
-  h64::Jac j = h64::load(q);
-  j.z = h64::mul(j.z, half);
-  return h64::store(j);
-}
-
-// Window value  W_w = partial[w][lb] + sum_k 2^k * partial[w][k]  (total; bit sums of the column sums for k < L, of the
-// row sums -- already offset by L -- for L <= k < lb; see k_reduce.hip) and the final Horner sum_w 2^(c*w) W_w, fused
-// into ONE pass over bit positions: term partial[w][k] sits at bit c*w + k, the total at bit c*w.
-// Replaces sum_reduction_final + final_accumulation.rs:19-39.
-Jacobian host_combine(const Jacobian* partial, const Plan& p) {
-  const uint32_t top = p.c * (p.W - 1) + p.lb;   // highest bit position in use
-  // 4 x 64-bit host arithmetic (host_fq64.h): this pass is the whole CPU tail of an MSM
-  h64::Jac acc = h64::identity();
-  for (int pos = (int)top; pos >= 0; --pos) {
-    acc = h64::jdouble(acc);
-    // the terms at this bit: partial[w][k] with c w + k = pos and k < lb, and the window total partial[w][lb] at k = 0.
-    // Production plans have lb = c - 1 (one window per position); tiny windows keep lb >= kSegLog > c - 1, where the
-    // upper bit sums of window w share positions with window w + 1
-    for (uint32_t w = std::min((uint32_t)pos / p.c, p.W - 1);; --w) {
-      const uint32_t k = (uint32_t)pos - p.c * w;
-      if (k > p.lb) break;
-      const Jacobian* pw = partial + (size_t)w * (p.lb + 1);
-      if (k == 0) acc = h64::jadd(acc, h64::load(pw[p.lb]));
-      if (k < p.lb) acc = h64::jadd(acc, h64::load(pw[k]));
-      if (w == 0) break;
-    }
-  }
-  return h64::store(acc);
-}
 
 int set_kernel_attributes(msm_amd_ctx* ctx) {
   const char* failed = nullptr;
@@ -611,46 +217,6 @@ size_t point_bytes(int layout) {
   return 0;
 }
 
-// Room for the window reduction of plan p in workspace w: the two scratch families S, T (internal points) and the
-// partial points (external points).
-int reduce_buffers(msm_amd_ctx* ctx, Workspace& w, const Plan& p, size_t internal_bytes, size_t ext_bytes) {
-  int rc;
-  if ((rc = ensure(ctx, w.S, p.total_segs * internal_bytes))) return rc;
-  if ((rc = ensure(ctx, w.T, p.total_segs * internal_bytes))) return rc;
-  return ensure(ctx, w.partial, p.partial_count * ext_bytes);
-}
-
-// window_size 0 = `auto_c`; the window and the number of windows of a table over n points
-int tables_geometry(msm_amd_ctx* ctx, size_t n, uint32_t window_size, uint32_t auto_c, uint32_t* c, uint32_t* W) {
-  *c = window_size ? window_size : auto_c;
-  if (*c < 4 || *c > 21) return fail(ctx, MSM_AMD_INPUT_ERROR, "table window_size must be 0 (auto) or 4..21");
-  *W = kModulusBits / *c + 1;
-  if ((size_t)*W * n > 0x7FFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, "windows * n must stay below 2^31");
-  return MSM_AMD_OK;
-}
-
-// Room for W * n records of record_bytes and handle_build_tail; `group` is "" or "G2 " in messages.
-template <class H, class Launch>
-int tables_build_tail(msm_amd_ctx* ctx, std::vector<H*>& live, size_t n, uint32_t c, uint32_t W, size_t record_bytes,
-                      const std::string& group, Launch&& launch, H** out) {
-  if (int rc = handle_build_tail(ctx, live, (size_t)W * n * record_bytes, "the " + group + "window tables",
-                                 group + "table build", launch, out)) return rc;
-  (*out)->n = n, (*out)->c = c, (*out)->W = W;
-  return MSM_AMD_OK;
-}
-
-template <class H>
-int tables_info(msm_amd_ctx* ctx, const std::vector<H*>& live, const H* tables, const char* not_a_handle, size_t* n,
-                uint32_t* window_size, uint32_t* num_windows, size_t* device_bytes) {
-  const H* t = find_handle(live, tables);
-  if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, not_a_handle);
-  if (n) *n = t->n;
-  if (window_size) *window_size = t->c;
-  if (num_windows) *num_windows = t->W;
-  if (device_bytes) *device_bytes = t->bytes;
-  return MSM_AMD_OK;
-}
-
 // msm_amd_destroy: handles the caller did not free
 template <class H>
 void handle_release_all(std::vector<H*>& live) {
@@ -659,60 +225,6 @@ void handle_release_all(std::vector<H*>& live) {
     delete h;
   }
   live.clear();
-}
-
-// Host points -> `stage` (device scratch) -> a fresh device array of out_bytes that `convert(staged, d_out)` fills and
-// waits for with the ctx's bound (prepare_bases_locked and its G2 twin); *d_prepared receives the array.
-template <class Convert>
-int upload_and_prepare(msm_amd_ctx* ctx, DeviceBuf& stage, const void* points, size_t in_bytes, size_t out_bytes,
-                       const char* what, Convert&& convert, void** d_prepared) {
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (int rc = ensure(ctx, stage, in_bytes)) return rc;
-  void* d_out = nullptr;
-  if (int qrc = quiesce_for_allocation(ctx, what)) return qrc;
-  HIP_TRY(ctx, hipMalloc(&d_out, out_bytes));
-  hipError_t e = hipMemcpy(stage.p, points, in_bytes, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(d_out);
-    HIP_TRY(ctx, e);
-  }
-  if (int rc = convert(stage.p, d_out)) {
-    // a bounded wait that timed out: the conversion may still be running, and hipFree would wait for the device
-    // without bound -- released when the ctx is idle
-    if (rc == MSM_AMD_PIPELINE_ERROR) ctx->graveyard.push_back(d_out);
-    else (void)hipFree(d_out);
-    return rc;
-  }
-  *d_prepared = d_out;
-  return MSM_AMD_OK;
-}
-
-bool scalar_layout_ok(int scalar_layout) {
-  return scalar_layout >= MSM_AMD_SCALAR_MONT_LE && scalar_layout <= MSM_AMD_SCALAR_CANON_BE32;
-}
-
-}  // namespace
-namespace msm_amd { namespace drv __attribute__((visibility("hidden"))) {
-// ms between two recorded events (0 if either cannot be read)
-float event_span(hipEvent_t a, hipEvent_t b) {
-  float t = 0;
-  if (hipEventElapsedTime(&t, a, b) != hipSuccess) {
-    (void)hipGetLastError();
-    t = 0;
-  }
-  return t;
-}
-}}  // namespace msm_amd::drv
-namespace {
-
-// Row / column sums of the window reduction for a LONE call: with no neighbouring instance to fill the machine, the
-// 15-addition chains of the pipelined setting (one lane per 16 buckets: 35 k lanes at 2^18 points, 7.7 k in the second
-// level at 2^20) are pure latency.  launch_reduce then takes, level by level, the smallest group (>= this minimum) whose
-// outputs still fit the lanes one launch can have resident; a further level costs one launch (~5 us), one addition
-// in a chain about 6 us.
-uint32_t pick_reduce_group(const Plan&) {
-  if (const char* e = std::getenv("MSM_AMD_REDUCE_GROUP")) return (uint32_t)std::atoi(e);
-  return kReduceGroupMin;
 }
 
 // The buffers of the scalar front end (digits, sort, work-item planning) of one MSM in workspace w, grown to plan p,
@@ -763,31 +275,6 @@ int front_buffers(msm_amd_ctx* ctx, Workspace& w, const Plan& p, SortBuffers* sb
   sb->counters = (PlanCounters*)w.counters.p;
   return MSM_AMD_OK;
 }
-
-// The plan of one instance: make_plan and what depends on whether the instance has the machine to itself.
-Plan instance_plan(size_t n, uint32_t c, uint32_t table_windows, bool lone, WidthBound width = WidthBound{}) {
-  Plan p = make_plan(n, c, table_windows, width);
-  if (lone) p.red_group = pick_reduce_group(p);   // (pipelined small instances: 2^16 -6 %, 2^18 +3 % -- not taken)
-  p.rb_threads = lone ? 0u : 64u;                 // one wave per bit-subset sum beside a resident accumulate grid (k_reduce.hip)
-  // the tile-staged scatter (1024-thread workgroups, 60 VGPRs, 64 KB of LDS) is for a sort that has the machine to
-  // itself; beside a resident accumulate grid it is slower than the plain scatter (4 x 2^22 points: 6.15 vs 5.65 ms per MSM)
-  if (!lone && !std::getenv("MSM_AMD_TILED")) p.tiled = 0;
-  return p;
-}
-
-// What the instance body knows of the group it runs (G1 or G2): the record sizes of the point-valued buffers and the
-// four launches, bound by the caller to the plan and the workspace of the instance.  Each launch enqueues on the
-// stream it is handed.
-struct PointStages {
-  size_t bases_bytes;      // room the base conversion needs in Workspace::bases29 (0: the bases are resident elsewhere)
-  size_t internal_bytes;   // internal point (PtI / PtI2): buckets, item partials, S, T
-  size_t ext_bytes;        // external point (Jacobian / Jacobian2): the partial points
-  std::function<int(hipStream_t)> convert_bases;   // the caller's points -> packed bases
-  // `before` / `after` are recorded directly around the accumulate kernel
-  std::function<void(hipStream_t, const SortBuffers&, hipEvent_t before, hipEvent_t after)> accumulate;
-  std::function<void(hipStream_t, const SortBuffers&)> combine;
-  std::function<void(hipStream_t)> reduce;   // Workspace::buckets, bsize -> partial
-};
 
 // The group-independent front end of one instance on stream fs: scalar conversion, the group's base conversion (inside
 // the convert span), digits, sort and work-item planning, with their stage events; then the main stream waits for it.
@@ -863,35 +350,6 @@ int enqueue_points(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, const Pla
   return MSM_AMD_OK;
 }
 
-// Enqueue one whole instance of plan p, G1 or G2, in workspace w; the partial points and the plan counters land in
-// slot.h_partial after slot.ev[EV_REDUCE].  Four streams (front, main, two alternating reduce streams), kWorkspaces
-// workspaces (consecutive instances take consecutive workspaces):
-//   front  : conversion, digits, sort, planning of instance i -- needs the workspace's previous accumulate and
-//            reduction done; runs while instance i-1 accumulates and i-2 reduces
-//   main   : accumulate of instance i                         -- needs front(i)
-//   reduce : combine + window reduction + copy of instance i  -- needs main(i)
-// A lone instance has all three on the main stream (lone_call).
-int enqueue_instance(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, const Plan& p, bool lone, int scalar_layout,
-                     const void* d_scalars, const PointStages& g) {
-  int rc;
-  if ((rc = slot_prepare(ctx, slot, p.partial_count, g.ext_bytes))) return rc;
-  SortBuffers sb{};
-  if ((rc = front_buffers(ctx, w, p, &sb))) return rc;
-  if (ctx->acc_variant == 4) {   // experiments build: the hand-allocated kernel's redo pass
-    if ((rc = ensure(ctx, w.redo_list, p.max_items * sizeof(uint32_t)))) return rc;
-    sb.redo_list = (uint32_t*)w.redo_list.p;
-  }
-  if (g.bases_bytes && (rc = ensure(ctx, w.bases29, g.bases_bytes))) return rc;
-  if ((rc = ensure(ctx, w.buckets, p.total_buckets * g.internal_bytes))) return rc;
-  if ((rc = ensure(ctx, w.item_partials, p.max_items * g.internal_bytes))) return rc;
-  hipStream_t fs = front_stream_of(ctx, lone);
-  hipStream_t rs = (lone || !ctx->overlap_reduce)
-                       ? ctx->stream
-                       : ctx->reduce_streams[ctx->alt_reduce ? ctx->seq++ % kReduceStreams : 0];
-  if ((rc = enqueue_front(ctx, w, slot, p, sb, fs, rs, lone, scalar_layout, d_scalars, g))) return rc;
-  return enqueue_points(ctx, w, slot, p, sb, rs, g);
-}
-
 // One G1 instance: d_points holds n points of point_layout, prepared bases or, with MSM_AMD_POINT_TABLES, is the handle
 // of msm_amd_tables_build*.
 int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_layout, int point_layout, const void* d_scalars,
@@ -950,33 +408,6 @@ int enqueue_msm(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, int scalar_l
     launch_reduce(st, p, (const PtI*)w.buckets.p, (const uint32_t*)w.bsize.p, (PtI*)w.S.p, (PtI*)w.T.p, (Jacobian*)w.partial.p);
   };
   return enqueue_instance(ctx, w, slot, p, lone, scalar_layout, d_scalars, g);
-}
-
-void accumulate_timings(msm_amd_ctx* ctx, InstanceSlot& s, const Plan& p, float final_ms, size_t n_inst) {
-  auto span = [&](int a, int b) { return event_span(s.ev[a], s.ev[b]); };
-  float ms[EV_COUNT] = {0};
-  ms[EV_CONVERT] = span(EV_START, EV_CONVERT);
-  ms[EV_DIGITS] = span(EV_CONVERT, EV_DIGITS);
-  ms[EV_SORT] = span(EV_DIGITS, EV_SORT);
-  ms[EV_ACC] = span(EV_ACC_S, EV_ACC);
-  ms[EV_REDUCE] = span(EV_RED_S, EV_REDUCE);
-  msm_amd_timings& T = ctx->timings;
-  const float inv = 1.0f / (float)n_inst;
-  T.convert_ms += ms[EV_CONVERT] * inv;
-  T.digits_ms += ms[EV_DIGITS] * inv;
-  T.sort_ms += ms[EV_SORT] * inv;
-  T.accumulate_ms += ms[EV_ACC] * inv;
-  T.reduce_ms += ms[EV_REDUCE] * inv;
-  T.accumulate_kernel_ms += span(EV_ACC_K0, EV_ACC_K1) * inv;
-  T.final_ms += final_ms * inv;
-  T.total_gpu_ms += (ms[EV_CONVERT] + ms[EV_DIGITS] + ms[EV_SORT] + ms[EV_ACC] + ms[EV_REDUCE]) * inv;
-  T.n = p.n_scalars;
-  T.window_size = p.c;
-  T.num_windows = p.W_digits;
-  T.reserved = (uint32_t)n_inst;
-  T.reserved2[0] = (float)s.counters().total_items;   // work items (= lanes with work) of the last instance's accumulate grid
-  T.reserved2[1] = ctx->after_sort_state;
-  T.reserved2[2] = ctx->after_sort_lead_ms;
 }
 
 // Batch of MSMs with device-resident inputs, in two halves so that callers can pipeline batches:
@@ -1040,33 +471,6 @@ unsigned finish_threads(size_t n_inst) {
   if (const char* e = std::getenv("MSM_AMD_FINISH_THREADS")) return (unsigned)std::max(1, std::atoi(e));
   const unsigned hw = std::max(2u, std::thread::hardware_concurrency());
   return (unsigned)std::max<size_t>(1, std::min<size_t>({(size_t)4, n_inst / 4, (size_t)hw / 2}));
-}
-
-// wait_event on s.ev[EV_REDUCE] ran into the ctx's bound: the ctx is stalled, and the error names `what` and the last
-// stage event of the instance the device did get to.
-// msm_amd_last_error of a bounded call that met records beyond its bound
-std::string width_violation_message(const Plan& p, size_t records, size_t instances, size_t instance, size_t n_inst,
-                                    size_t index) {
-  std::string m = std::to_string(records) + " record(s) with a magnitude of 2^" + std::to_string(p.bits) + " or more (" +
-                  (p.sign ? "signed" : "unsigned") + " bound of " + std::to_string(p.bits) + " bits)";
-  if (n_inst > 1)
-    m += " in " + std::to_string(instances) + " of " + std::to_string(n_inst) + " instances; one of them: instance " +
-         std::to_string(instance) + ", index " + std::to_string(index);
-  else
-    m += "; one of them: index " + std::to_string(index);
-  return m + "; the output was not written";
-}
-
-int wait_timed_out(msm_amd_ctx* ctx, const InstanceSlot& s, const std::string& what, const char* tail = "") {
-  ctx->stalled = true;
-  int reached = -1;
-  for (int e = 0; e < EV_COUNT; ++e) {
-    if (hipEventQuery(s.ev[e]) == hipSuccess) reached = e;
-  }
-  (void)hipGetLastError();
-  return fail(ctx, MSM_AMD_PIPELINE_ERROR,
-              "timed out after " + std::to_string(ctx->wait_timeout_ms) + " ms waiting for event 'reduce' of " + what +
-                  "; last event reached: " + (reached < 0 ? "none" : kEventNames[reached]) + tail);
 }
 
 // `internal`: the caller is one of the library's blocking entry points, which cannot hand the ticket back to its own
@@ -1253,6 +657,253 @@ bool stage_pageable(msm_amd_ctx* ctx, const void* src, size_t bytes) {
 
 }  // namespace
 namespace msm_amd { namespace drv __attribute__((visibility("hidden"))) {
+int fail(msm_amd_ctx* ctx, int status, const std::string& msg) {
+  if (tl_error_sink) *tl_error_sink = msg;
+  else if (ctx) ctx->last_error = msg;
+  return status;
+}
+
+// hipEventSynchronize may park the thread (it did, for more than a millisecond, inside a process that also hosts
+// torch's thread pools) and it waits without bound: a device that stalls would block the caller of a blocking MSM
+// for ever, where the reference's call always returns (msm.rs:237-349).  The waits on the critical path therefore
+// poll the event -- spinning for the first few milliseconds, then with short sleeps -- up to `timeout_ms`
+// (0 = unbounded) and report hipErrorNotReady when the bound is reached.
+hipError_t wait_event(hipEvent_t ev, uint32_t timeout_ms) {
+  const auto t0 = std::chrono::steady_clock::now();
+  for (;;) {
+    const hipError_t q = hipEventQuery(ev);
+    if (q == hipSuccess) return hipSuccess;
+    if (q != hipErrorNotReady) {
+      (void)hipGetLastError();
+      return q;
+    }
+    (void)hipGetLastError();
+    const auto waited = std::chrono::steady_clock::now() - t0;
+    if (timeout_ms && waited > std::chrono::milliseconds(timeout_ms)) return hipErrorNotReady;
+    if (waited > std::chrono::milliseconds(4))
+      std::this_thread::sleep_for(std::chrono::microseconds(50));
+    else
+      __builtin_ia32_pause();
+  }
+}
+
+// A wait on this ctx ran into its bound earlier.  Before anything new is enqueued: has the device caught up?  If every
+// stream is idle the batches a blocking entry point abandoned are released; otherwise the call fails like the wait did.
+int recover_if_stalled(msm_amd_ctx* ctx) {
+  if (!ctx->stalled) return MSM_AMD_OK;
+  if (!streams_idle(ctx))
+    return fail(ctx, MSM_AMD_PIPELINE_ERROR,
+                "the device is still busy with work whose wait timed out earlier (msm_amd_synchronize waits again; "
+                "msm_amd_destroy gives the ctx up)");
+  for (Batch& b : ctx->batches)
+    if (b.abandoned) b.active = b.abandoned = false;
+  ctx->stalled = false;
+  return MSM_AMD_OK;
+}
+
+// Nothing of this ctx is in flight (every submitted batch has been waited for): outgrown buffers can go.
+void reap_graveyard(msm_amd_ctx* ctx) {
+  if (ctx->graveyard.empty() || ctx->stalled) return;
+  for (const Batch& b : ctx->batches)
+    if (b.active) return;
+  for (void* p : ctx->graveyard) (void)hipFree(p);
+  (void)hipGetLastError();
+  ctx->graveyard.clear();
+}
+
+// hipMalloc / hipHostMalloc / hipFree / hipHostFree may wait for the device (hipFree always does).  With work in flight
+// on a device that does not answer they would block without bound, before any bounded wait is reached -- so nothing
+// is allocated or released while the ctx has work in flight: a buffer that must grow first waits, WITH the ctx's wait
+// bound, for the ctx's streams to run empty, and the call fails with MSM_AMD_PIPELINE_ERROR if they do not.  (On a
+// healthy device this costs a pipeline drain on the first use of a workspace, never in steady state.)
+int quiesce_for_allocation(msm_amd_ctx* ctx, const char* what) {
+  if (streams_idle(ctx)) return MSM_AMD_OK;
+  if (drain_streams_bounded(ctx)) return MSM_AMD_OK;
+  ctx->stalled = true;
+  return fail(ctx, MSM_AMD_PIPELINE_ERROR,
+              std::string("device busy past the wait bound of ") + std::to_string(ctx->wait_timeout_ms) +
+                  " ms: cannot grow " + what + " while earlier work is in flight (msm_amd_synchronize waits again)");
+}
+
+// hipStreamSynchronize with the ctx's wait bound (the stream is polled): PIPELINE_ERROR, ctx marked stalled, when the
+// device does not get there.
+int sync_stream_bounded(msm_amd_ctx* ctx, hipStream_t st, const char* what) {
+  const auto t0 = std::chrono::steady_clock::now();
+  for (;;) {
+    const hipError_t q = hipStreamQuery(st);
+    if (q == hipSuccess) return MSM_AMD_OK;
+    (void)hipGetLastError();
+    if (q != hipErrorNotReady)
+      return fail(ctx, MSM_AMD_PIPELINE_ERROR, std::string("hipStreamQuery (") + what + "): " + hipGetErrorString(q));
+    const auto waited = std::chrono::steady_clock::now() - t0;
+    if (ctx->wait_timeout_ms && waited > std::chrono::milliseconds(ctx->wait_timeout_ms)) {
+      ctx->stalled = true;
+      return fail(ctx, MSM_AMD_PIPELINE_ERROR, "timed out after " + std::to_string(ctx->wait_timeout_ms) +
+                                                   " ms waiting for the stream (" + what + ")");
+    }
+    if (waited > std::chrono::milliseconds(2)) std::this_thread::sleep_for(std::chrono::microseconds(50));
+    else __builtin_ia32_pause();
+  }
+}
+
+bool drain_or_mark_stalled(msm_amd_ctx* ctx) {
+  if (drain_streams_bounded(ctx)) return true;
+  ctx->stalled = true;
+  return false;
+}
+
+int ensure(msm_amd_ctx* ctx, DeviceBuf& b, size_t bytes) {
+  if (bytes <= b.cap) return MSM_AMD_OK;
+  if (int rc = quiesce_for_allocation(ctx, "a device workspace")) return rc;
+  if (b.p) ctx->graveyard.push_back(b.p);   // freed later, see msm_amd_ctx::graveyard
+  b.p = nullptr;
+  b.cap = 0;
+  // grow by 25% to avoid re-allocating for every slightly larger instance
+  const size_t want = bytes + bytes / 4;
+  HIP_TRY(ctx, hipMalloc(&b.p, want));
+  b.cap = want;
+  return MSM_AMD_OK;
+}
+
+// E' -> E for a Jacobian point (Plan::on_iso): x = 4 x', y = 8 y' is Z <- Z / 2.  The identity (Z = 0) stays.
+Jacobian iso_to_e(const Jacobian& q) {
+  static const h64::Fe half = h64::inv(h64::dbl(h64::one()));
+  h64::Jac j = h64::load(q);
+  j.z = h64::mul(j.z, half);
+  return h64::store(j);
+}
+
+// Window value  W_w = partial[w][lb] + sum_k 2^k * partial[w][k]  (total; bit sums of the column sums for k < L, of the
+// row sums -- already offset by L -- for L <= k < lb; see k_reduce.hip) and the final Horner sum_w 2^(c*w) W_w, fused
+// into ONE pass over bit positions: term partial[w][k] sits at bit c*w + k, the total at bit c*w.
+// Replaces sum_reduction_final + final_accumulation.rs:19-39.
+Jacobian host_combine(const Jacobian* partial, const Plan& p) {
+  const uint32_t top = p.c * (p.W - 1) + p.lb;   // highest bit position in use
+  // 4 x 64-bit host arithmetic (host_fq64.h): this pass is the whole CPU tail of an MSM
+  h64::Jac acc = h64::identity();
+  for (int pos = (int)top; pos >= 0; --pos) {
+    acc = h64::jdouble(acc);
+    // the terms at this bit: partial[w][k] with c w + k = pos and k < lb, and the window total partial[w][lb] at k = 0.
+    // Production plans have lb = c - 1 (one window per position); tiny windows keep lb >= kSegLog > c - 1, where the
+    // upper bit sums of window w share positions with window w + 1
+    for (uint32_t w = std::min((uint32_t)pos / p.c, p.W - 1);; --w) {
+      const uint32_t k = (uint32_t)pos - p.c * w;
+      if (k > p.lb) break;
+      const Jacobian* pw = partial + (size_t)w * (p.lb + 1);
+      if (k == 0) acc = h64::jadd(acc, h64::load(pw[p.lb]));
+      if (k < p.lb) acc = h64::jadd(acc, h64::load(pw[k]));
+      if (w == 0) break;
+    }
+  }
+  return h64::store(acc);
+}
+
+// Room for the window reduction of plan p in workspace w: the two scratch families S, T (internal points) and the
+// partial points (external points).
+int reduce_buffers(msm_amd_ctx* ctx, Workspace& w, const Plan& p, size_t internal_bytes, size_t ext_bytes) {
+  int rc;
+  if ((rc = ensure(ctx, w.S, p.total_segs * internal_bytes))) return rc;
+  if ((rc = ensure(ctx, w.T, p.total_segs * internal_bytes))) return rc;
+  return ensure(ctx, w.partial, p.partial_count * ext_bytes);
+}
+
+bool scalar_layout_ok(int scalar_layout) {
+  return scalar_layout >= MSM_AMD_SCALAR_MONT_LE && scalar_layout <= MSM_AMD_SCALAR_CANON_BE32;
+}
+
+// ms between two recorded events (0 if either cannot be read)
+float event_span(hipEvent_t a, hipEvent_t b) {
+  float t = 0;
+  if (hipEventElapsedTime(&t, a, b) != hipSuccess) {
+    (void)hipGetLastError();
+    t = 0;
+  }
+  return t;
+}
+
+// Enqueue one whole instance of plan p, G1 or G2, in workspace w; the partial points and the plan counters land in
+// slot.h_partial after slot.ev[EV_REDUCE].  Four streams (front, main, two alternating reduce streams), kWorkspaces
+// workspaces (consecutive instances take consecutive workspaces):
+//   front  : conversion, digits, sort, planning of instance i -- needs the workspace's previous accumulate and
+//            reduction done; runs while instance i-1 accumulates and i-2 reduces
+//   main   : accumulate of instance i                         -- needs front(i)
+//   reduce : combine + window reduction + copy of instance i  -- needs main(i)
+// A lone instance has all three on the main stream (lone_call).
+int enqueue_instance(msm_amd_ctx* ctx, Workspace& w, InstanceSlot& slot, const Plan& p, bool lone, int scalar_layout,
+                     const void* d_scalars, const PointStages& g) {
+  int rc;
+  if ((rc = slot_prepare(ctx, slot, p.partial_count, g.ext_bytes))) return rc;
+  SortBuffers sb{};
+  if ((rc = front_buffers(ctx, w, p, &sb))) return rc;
+  if (ctx->acc_variant == 4) {   // experiments build: the hand-allocated kernel's redo pass
+    if ((rc = ensure(ctx, w.redo_list, p.max_items * sizeof(uint32_t)))) return rc;
+    sb.redo_list = (uint32_t*)w.redo_list.p;
+  }
+  if (g.bases_bytes && (rc = ensure(ctx, w.bases29, g.bases_bytes))) return rc;
+  if ((rc = ensure(ctx, w.buckets, p.total_buckets * g.internal_bytes))) return rc;
+  if ((rc = ensure(ctx, w.item_partials, p.max_items * g.internal_bytes))) return rc;
+  hipStream_t fs = front_stream_of(ctx, lone);
+  hipStream_t rs = (lone || !ctx->overlap_reduce)
+                       ? ctx->stream
+                       : ctx->reduce_streams[ctx->alt_reduce ? ctx->seq++ % kReduceStreams : 0];
+  if ((rc = enqueue_front(ctx, w, slot, p, sb, fs, rs, lone, scalar_layout, d_scalars, g))) return rc;
+  return enqueue_points(ctx, w, slot, p, sb, rs, g);
+}
+
+void accumulate_timings(msm_amd_ctx* ctx, InstanceSlot& s, const Plan& p, float final_ms, size_t n_inst) {
+  auto span = [&](int a, int b) { return event_span(s.ev[a], s.ev[b]); };
+  float ms[EV_COUNT] = {0};
+  ms[EV_CONVERT] = span(EV_START, EV_CONVERT);
+  ms[EV_DIGITS] = span(EV_CONVERT, EV_DIGITS);
+  ms[EV_SORT] = span(EV_DIGITS, EV_SORT);
+  ms[EV_ACC] = span(EV_ACC_S, EV_ACC);
+  ms[EV_REDUCE] = span(EV_RED_S, EV_REDUCE);
+  msm_amd_timings& T = ctx->timings;
+  const float inv = 1.0f / (float)n_inst;
+  T.convert_ms += ms[EV_CONVERT] * inv;
+  T.digits_ms += ms[EV_DIGITS] * inv;
+  T.sort_ms += ms[EV_SORT] * inv;
+  T.accumulate_ms += ms[EV_ACC] * inv;
+  T.reduce_ms += ms[EV_REDUCE] * inv;
+  T.accumulate_kernel_ms += span(EV_ACC_K0, EV_ACC_K1) * inv;
+  T.final_ms += final_ms * inv;
+  T.total_gpu_ms += (ms[EV_CONVERT] + ms[EV_DIGITS] + ms[EV_SORT] + ms[EV_ACC] + ms[EV_REDUCE]) * inv;
+  T.n = p.n_scalars;
+  T.window_size = p.c;
+  T.num_windows = p.W_digits;
+  T.reserved = (uint32_t)n_inst;
+  T.reserved2[0] = (float)s.counters().total_items;   // work items (= lanes with work) of the last instance's accumulate grid
+  T.reserved2[1] = ctx->after_sort_state;
+  T.reserved2[2] = ctx->after_sort_lead_ms;
+}
+
+// wait_event on s.ev[EV_REDUCE] ran into the ctx's bound: the ctx is stalled, and the error names `what` and the last
+// stage event of the instance the device did get to.
+// msm_amd_last_error of a bounded call that met records beyond its bound
+std::string width_violation_message(const Plan& p, size_t records, size_t instances, size_t instance, size_t n_inst,
+                                    size_t index) {
+  std::string m = std::to_string(records) + " record(s) with a magnitude of 2^" + std::to_string(p.bits) + " or more (" +
+                  (p.sign ? "signed" : "unsigned") + " bound of " + std::to_string(p.bits) + " bits)";
+  if (n_inst > 1)
+    m += " in " + std::to_string(instances) + " of " + std::to_string(n_inst) + " instances; one of them: instance " +
+         std::to_string(instance) + ", index " + std::to_string(index);
+  else
+    m += "; one of them: index " + std::to_string(index);
+  return m + "; the output was not written";
+}
+
+int wait_timed_out(msm_amd_ctx* ctx, const InstanceSlot& s, const std::string& what, const char* tail) {
+  ctx->stalled = true;
+  int reached = -1;
+  for (int e = 0; e < EV_COUNT; ++e) {
+    if (hipEventQuery(s.ev[e]) == hipSuccess) reached = e;
+  }
+  (void)hipGetLastError();
+  return fail(ctx, MSM_AMD_PIPELINE_ERROR,
+              "timed out after " + std::to_string(ctx->wait_timeout_ms) + " ms waiting for event 'reduce' of " + what +
+                  "; last event reached: " + (reached < 0 ? "none" : kEventNames[reached]) + tail);
+}
+
 // hipMemcpyAsync(dst, src, bytes, H2D, stream) for a pageable src, through the ring.  Returns when the last chunk has
 // been handed to the DMA engine (the caller's buffer is no longer needed), not when it has arrived.
 int staged_upload(msm_amd_ctx* ctx, void* d_dst, const void* h_src, size_t bytes, hipStream_t stream) {
@@ -1286,6 +937,13 @@ int staged_upload(msm_amd_ctx* ctx, void* d_dst, const void* h_src, size_t bytes
     HIP_TRY(ctx, hipEventRecord(S.sent[k], stream));
     S.busy[k] = true;
   }
+  return MSM_AMD_OK;
+}
+
+// the (bits, sign) of a bounded entry point `who`
+int bound_args(msm_amd_ctx* ctx, const char* who, uint32_t bits, int sign) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  if (const char* why = width_bound_check(bits, sign)) return fail(ctx, MSM_AMD_INPUT_ERROR, std::string(who) + ": " + why);
   return MSM_AMD_OK;
 }
 }}  // namespace msm_amd::drv
@@ -1813,20 +1471,6 @@ int stage_upload(msm_amd_ctx* ctx, void* dst, const void* src, size_t bytes) {
   return MSM_AMD_OK;
 }
 
-// The instances submitted while this lives are planned with `width` (ctx->mu is held by the entry point).
-struct BoundScope {
-  msm_amd_ctx* ctx;
-  BoundScope(msm_amd_ctx* c, uint32_t bits, int sign) : ctx(c) { ctx->bound.bits = bits, ctx->bound.sign = (uint32_t)sign; }
-  ~BoundScope() { ctx->bound = WidthBound{}; }
-};
-
-// the (bits, sign) of a bounded entry point `who`
-int bound_args(msm_amd_ctx* ctx, const char* who, uint32_t bits, int sign) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  if (const char* why = width_bound_check(bits, sign)) return fail(ctx, MSM_AMD_INPUT_ERROR, std::string(who) + ": " + why);
-  return MSM_AMD_OK;
-}
-
 }  // namespace
 
 // ================================================================================================
@@ -2120,12 +1764,6 @@ int msm_amd_set_window_size(msm_amd_ctx* ctx, uint32_t window_size) {
   std::lock_guard<std::mutex> g(ctx->mu);
   ctx->forced_window = window_size;
   return MSM_AMD_OK;
-}
-
-uint32_t msm_amd_auto_window_size(size_t n) { return auto_window(n); }
-uint32_t msm_amd_auto_window_size_lone(size_t n) { return auto_window_lone(n); }
-uint32_t msm_amd_auto_window_size_bounded(size_t n, uint32_t bits, int lone) {
-  return auto_window_bounded(n, std::max(1u, std::min(bits, kModulusBits)), lone != 0);
 }
 
 int msm_amd_msm_batch(msm_amd_ctx* ctx, int scalar_layout, int point_layout, size_t n_inst,
@@ -2507,27 +2145,6 @@ int msm_amd_bases_upload(msm_amd_ctx* ctx, int point_layout, const void* points,
 }
 
 // ---- precomputed window tables ------------------------------------------------------------
-static uint32_t auto_table_window(size_t n) {
-  // One bucket set serves all windows, so the window can grow until the 2^(c-1) buckets of the window reduction
-  // (2 full additions each) cost as much as the mixed additions they save.  Windows whose top digit is narrow are
-  // excluded: the n entries of the top window would all fall into its few slots (c = 19 leaves 7 bits for the top
-  // window of a 254-bit scalar: 2^20 entries in 128 buckets and in ONE region of the sort).
-  uint32_t best = 4;
-  double best_cost = 1e300;
-  for (uint32_t c = 4; c <= 21; ++c) {
-    const uint32_t W = kModulusBits / c + 1;
-    const uint32_t top = kModulusBits - (W - 1) * c;          // bits of the top window
-    if (top + 6 < c && c > 6) continue;                        // top window concentrated > 64-fold
-    if ((size_t)W * n > 0x7FFFFFFFull) continue;
-    const double cost = 9.5 * (double)W * (double)n + 27.0 * (double)((size_t)1 << (c - 1)) + 14.0 * (double)W * (double)n / 32.0;
-    if (cost < best_cost) {
-      best_cost = cost;
-      best = c;
-    }
-  }
-  return best;
-}
-
 static int tables_build_locked(msm_amd_ctx* ctx, int point_layout, const void* d_points, size_t n, uint32_t window_size,
                                msm_amd_tables** out) {
   uint32_t c, W;
@@ -2686,854 +2303,16 @@ int msm_amd_generate_instance(msm_amd_ctx* ctx, uint64_t seed, size_t n, int sca
   return MSM_AMD_OK;
 }
 
-// ---- per-stage entry points ------------------------------------------------------------------------
-int msm_amd_prepare_buckets_indices(msm_amd_ctx* ctx, const uint32_t* scalars_be32, size_t n, uint32_t window_size,
-                                    uint32_t num_windows, uint32_t* pairs_out) {
-  if (!ctx || !scalars_be32 || !pairs_out || n == 0 || window_size == 0 || window_size > 32 || num_windows == 0)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "bad prepare_buckets_indices arguments");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  int rc;
-  const size_t pair_bytes = n * num_windows * 8;
-  if ((rc = ensure(ctx, ctx->scratch_a, n * 32))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch_b, n * 32))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch_c, pair_bytes))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_a.p, scalars_be32, n * 32, hipMemcpyHostToDevice, st));
-  launch_be32_to_le(st, (const uint32_t*)ctx->scratch_a.p, n, (uint32_t*)ctx->scratch_b.p);
-  launch_ref_prepare(st, (const u256*)ctx->scratch_b.p, (uint32_t)n, window_size, num_windows,
-                     (uint2*)ctx->scratch_c.p);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(pairs_out, ctx->scratch_c.p, pair_bytes, hipMemcpyDeviceToHost, st));
-  if (int src_ = sync_stream_bounded(ctx, st, __func__)) return src_;
-  return MSM_AMD_OK;
-}
-
-int msm_amd_sort_buckets_indices(msm_amd_ctx* ctx, uint32_t* pairs, size_t n_pairs) {
-  if (!ctx || !pairs) return fail(ctx, MSM_AMD_INPUT_ERROR, "null pointer");
-  if (n_pairs == 0) return MSM_AMD_OK;
-  if (n_pairs > 0xFFFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, "too many pairs");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  int rc;
-  const uint32_t tiles = (uint32_t)((n_pairs + kRadixTile - 1) / kRadixTile);
-  if ((rc = ensure(ctx, ctx->scratch_a, n_pairs * 8))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch_b, n_pairs * 8))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch_c, ((size_t)tiles + 1) * 256 * 4))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_a.p, pairs, n_pairs * 8, hipMemcpyHostToDevice, st));
-  uint2* src = nullptr;
-  launch_radix_sort_pairs(st, (uint2*)ctx->scratch_a.p, (uint2*)ctx->scratch_b.p, n_pairs,
-                          (uint32_t*)ctx->scratch_c.p, &src);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(pairs, src, n_pairs * 8, hipMemcpyDeviceToHost, st));
-  if (int src_ = sync_stream_bounded(ctx, st, __func__)) return src_;
-  return MSM_AMD_OK;
-}
-
-int msm_amd_sort_pairs_device(msm_amd_ctx* ctx, void* d_pairs, size_t n_pairs, uint32_t key_bits, float* kernel_ms) {
-  if (!ctx || !d_pairs || key_bits == 0 || key_bits > 32) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad sort arguments");
-  if (kernel_ms) *kernel_ms = 0.f;
-  if (n_pairs == 0) return MSM_AMD_OK;
-  if (n_pairs > 0xFFFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, "too many pairs");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  int rc;
-  const uint32_t tiles = (uint32_t)((n_pairs + kRadixTile - 1) / kRadixTile);
-  if ((rc = ensure(ctx, ctx->scratch_b, n_pairs * 8))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch_c, ((size_t)tiles + 1) * 256 * 4))) return rc;
-  hipEvent_t e0, e1;
-  HIP_TRY(ctx, hipEventCreate(&e0));
-  HIP_TRY(ctx, hipEventCreate(&e1));
-  HIP_TRY(ctx, hipEventRecord(e0, st));
-  uint2* src = nullptr;
-  launch_radix_sort_pairs(st, (uint2*)d_pairs, (uint2*)ctx->scratch_b.p, n_pairs, (uint32_t*)ctx->scratch_c.p, &src,
-                          key_bits);
-  hipError_t le = hipGetLastError();
-  if (le == hipSuccess && src != (uint2*)d_pairs)   // odd number of passes: the result sits in the scratch buffer
-    le = hipMemcpyAsync(d_pairs, src, n_pairs * 8, hipMemcpyDeviceToDevice, st);
-  if (le == hipSuccess) le = hipEventRecord(e1, st);
-  if (le == hipSuccess && sync_stream_bounded(ctx, st, "pair sort")) le = hipErrorNotReady;
-  float ms = 0.f;
-  if (le == hipSuccess) le = hipEventElapsedTime(&ms, e0, e1);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  HIP_TRY(ctx, le);
-  if (kernel_ms) *kernel_ms = ms;
-  return MSM_AMD_OK;
-}
-
-int msm_amd_bucket_wise_accumulation(msm_amd_ctx* ctx, const uint32_t* sorted_pairs, size_t n_pairs,
-                                     const uint32_t* points_be32, size_t n_points, uint32_t total_buckets,
-                                     uint32_t* buckets_out) {
-  if (!ctx || !sorted_pairs || !points_be32 || !buckets_out || n_points == 0 || total_buckets == 0)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "bad bucket_wise_accumulation arguments");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (!drain_or_mark_stalled(ctx))   // workspace 0 may belong to an MSM between submit_batch_device and wait_batch
-    return fail(ctx, MSM_AMD_PIPELINE_ERROR, "device busy past the wait bound");
-  hipStream_t st = ctx->stream;
-  int rc;
-  const size_t pts_bytes = n_points * 96, bkt_bytes = (size_t)total_buckets * 96;
-  if ((rc = ensure(ctx, ctx->scratch_a, std::max(pts_bytes, bkt_bytes)))) return rc;   // BE32 staging
-  if ((rc = ensure(ctx, ctx->scratch_b, pts_bytes))) return rc;                        // points LE
-  if ((rc = ensure(ctx, ctx->scratch_c, std::max<size_t>(n_pairs * 8, 8)))) return rc;
-  if ((rc = ensure(ctx, ctx->ws[0].buckets, bkt_bytes))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_a.p, points_be32, pts_bytes, hipMemcpyHostToDevice, st));
-  launch_be32_to_le(st, (const uint32_t*)ctx->scratch_a.p, n_points * 3, (uint32_t*)ctx->scratch_b.p);
-  HIP_TRY(ctx, hipMemsetAsync(ctx->ws[0].buckets.p, 0, bkt_bytes, st));   // Appendix B item 8: explicit zero fill
-  if (n_pairs) {
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_c.p, sorted_pairs, n_pairs * 8, hipMemcpyHostToDevice, st));
-    launch_ref_accumulate(st, (const uint2*)ctx->scratch_c.p, n_pairs, (const Jacobian*)ctx->scratch_b.p,
-                          (uint32_t)n_points, total_buckets, (Jacobian*)ctx->ws[0].buckets.p);
-  }
-  // LE -> BE32 is the same limb reversal
-  launch_be32_to_le(st, (const uint32_t*)ctx->ws[0].buckets.p, (size_t)total_buckets * 3, (uint32_t*)ctx->scratch_a.p);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(buckets_out, ctx->scratch_a.p, bkt_bytes, hipMemcpyDeviceToHost, st));
-  if (int src_ = sync_stream_bounded(ctx, st, __func__)) return src_;
-  return MSM_AMD_OK;
-}
-
-int msm_amd_sum_reduction(msm_amd_ctx* ctx, const uint32_t* buckets_be32, uint32_t buckets_size,
-                          uint32_t num_windows, uint32_t* res_out) {
-  if (!ctx || !buckets_be32 || !res_out || buckets_size == 0 || num_windows == 0)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "bad sum_reduction arguments");
-  // production layout: nb = 2^lb >= buckets_size slots per window, slot i carries weight i + 1
-  uint32_t c = kSegLog;
-  while ((1u << c) < buckets_size) ++c;
-  if (c > 24) return fail(ctx, MSM_AMD_INPUT_ERROR, "buckets_size too large");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (!drain_or_mark_stalled(ctx))   // workspace 0 may belong to an MSM between submit_batch_device and wait_batch
-    return fail(ctx, MSM_AMD_PIPELINE_ERROR, "device busy past the wait bound");
-  hipStream_t st = ctx->stream;
-  const Plan p = make_reduce_plan(c, num_windows);
-  int rc;
-  const size_t in_bytes = (size_t)buckets_size * num_windows * 96;
-  if ((rc = ensure(ctx, ctx->scratch_a, in_bytes))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch_b, in_bytes))) return rc;
-  Workspace& ws = ctx->ws[0];
-  if ((rc = ensure(ctx, ws.buckets, p.total_buckets * sizeof(PtI)))) return rc;
-  if ((rc = reduce_buffers(ctx, ws, p, sizeof(PtI), sizeof(Jacobian)))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_a.p, buckets_be32, in_bytes, hipMemcpyHostToDevice, st));
-  const size_t words = (size_t)buckets_size * num_windows * 3;
-  launch_be32_to_le(st, (const uint32_t*)ctx->scratch_a.p, words, (uint32_t*)ctx->scratch_b.p);
-  launch_pad_buckets(st, (const Jacobian*)ctx->scratch_b.p, buckets_size, p.W, p.lb, (PtI*)ws.buckets.p);
-  // every bucket holds a valid point: no bucket_size
-  launch_reduce(st, p, (const PtI*)ws.buckets.p, nullptr, (PtI*)ws.S.p, (PtI*)ws.T.p, (Jacobian*)ws.partial.p);
-  HIP_TRY(ctx, hipGetLastError());
-  std::vector<Jacobian> partial(p.partial_count);
-  HIP_TRY(ctx, hipMemcpyAsync(partial.data(), ws.partial.p, p.partial_count * sizeof(Jacobian), hipMemcpyDeviceToHost, st));
-  if (int src_ = sync_stream_bounded(ctx, st, __func__)) return src_;
-  // per-window value: reuse the fused Horner with a single window
-  Plan one = p;
-  one.W = 1;
-  for (uint32_t w = 0; w < num_windows; ++w) {
-    const Jacobian r = host_combine(partial.data() + (size_t)w * (p.lb + 1), one);
-    jac_to_be32(r, res_out + (size_t)w * 24);
-  }
-  return MSM_AMD_OK;
-}
-
 size_t msm_amd_scalar_bytes(int scalar_layout) {
   return (scalar_layout == MSM_AMD_SCALAR_MONT_LE || scalar_layout == MSM_AMD_SCALAR_CANON_LE ||
           scalar_layout == MSM_AMD_SCALAR_CANON_BE32) ? 32 : 0;
 }
 size_t msm_amd_point_bytes(int point_layout) { return point_bytes(point_layout); }
 
-int msm_amd_sum_points(const void* points96, size_t count, void* out96) {
-  if ((!points96 && count) || !out96) return MSM_AMD_INPUT_ERROR;
-  h64::Jac acc = h64::identity();
-  for (size_t i = 0; i < count; ++i) {
-    h64::Jac p;
-    std::memcpy(&p, (const uint8_t*)points96 + i * 96, 96);
-    acc = h64::jadd(acc, p);
-  }
-  const h64::Jac res = h64::normalise(acc);
-  std::memcpy(out96, &res, 96);
-  return MSM_AMD_OK;
-}
-
-int msm_amd_final_accumulation(const uint32_t* res_be32, uint32_t num_windows, uint32_t window_size,
-                               uint32_t* point_out) {
-  if (!res_be32 || !point_out || num_windows == 0) return MSM_AMD_INPUT_ERROR;
-  h64::Jac acc = h64::identity();   // same formulas as jac_double / jac_add: identical coordinates, not only the same point
-  for (int w = (int)num_windows - 1; w >= 0; --w) {
-    for (uint32_t i = 0; i < window_size; ++i) acc = h64::jdouble(acc);
-    acc = h64::jadd(acc, h64::load(be32_to_jac(res_be32 + (size_t)w * 24)));
-  }
-  jac_to_be32(h64::store(acc), point_out);
-  return MSM_AMD_OK;
-}
-
-// Layout helper for the test-op entry points: limb reversal between the BE32 wire format and LE u256.
-static void test_op_widths(int op, size_t* wa, size_t* wb) {
-  const bool pt = test_op_is_point(op);
-  *wa = pt ? 3 : 1;
-  *wb = (op == MSM_AMD_OP_EC_MUL) ? 1 : *wa;
-}
-
-int msm_amd_test_op(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
-  if (!ctx || !a || !b || !out || count == 0 || op < 0 || op > kTestOpMax ||
-      (op >= MSM_AMD_OP_H64_FP_MUL && op <= MSM_AMD_OP_H64_EC_DBL))   // (host-only ops 37, 38 are above kTestOpMax)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_op arguments");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  size_t wa, wb;
-  test_op_widths(op, &wa, &wb);
-  const size_t wo = wa;
-  std::vector<uint32_t> la(count * wa * 8), lb(count * wb * 8), lo(count * wo * 8);
-  for (size_t i = 0; i < count * wa; ++i)
-    for (int l = 0; l < 8; ++l) la[i * 8 + l] = a[i * 8 + 7 - l];
-  for (size_t i = 0; i < count * wb; ++i)
-    for (int l = 0; l < 8; ++l) lb[i * 8 + l] = b[i * 8 + 7 - l];
-  int rc;
-  if ((rc = ensure(ctx, ctx->scratch_a, la.size() * 4))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch_b, lb.size() * 4))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch_c, lo.size() * 4))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_a.p, la.data(), la.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_b.p, lb.data(), lb.size() * 4, hipMemcpyHostToDevice, st));
-  launch_test_op(st, op, (const u256*)ctx->scratch_a.p, (const u256*)ctx->scratch_b.p, (u256*)ctx->scratch_c.p,
-                 (uint32_t)count);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(lo.data(), ctx->scratch_c.p, lo.size() * 4, hipMemcpyDeviceToHost, st));
-  if (int src_ = sync_stream_bounded(ctx, st, __func__)) return src_;
-  for (size_t i = 0; i < count * wo; ++i)
-    for (int l = 0; l < 8; ++l) out[i * 8 + l] = lo[i * 8 + 7 - l];
-  return MSM_AMD_OK;
-}
-
-// ops 27..31, 37, 38 exist on the host only: the 4 x 64-bit arithmetic of the CPU tail (host_fq64.h)
-static bool host64_test_op(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
-  const bool inverse = op == MSM_AMD_OP_H64_FP_INV || op == MSM_AMD_OP_H64_FP_INV_FERMAT;
-  if ((op < MSM_AMD_OP_H64_FP_MUL || op > MSM_AMD_OP_H64_EC_DBL) && !inverse) return false;
-  const bool pt = op == MSM_AMD_OP_H64_EC_ADD || op == MSM_AMD_OP_H64_EC_DBL;
-  for (size_t t = 0; t < count; ++t) {
-    if (!pt) {
-      const u256 xa = be32_to_u256(a + t * 8), xb = be32_to_u256(b + t * 8);
-      h64::Fe x, y, r;
-      std::memcpy(&x, &xa, 32);
-      std::memcpy(&y, &xb, 32);
-      if (inverse) r = op == MSM_AMD_OP_H64_FP_INV ? h64::inv(x) : h64::inv_fermat(x);
-      else r = op == MSM_AMD_OP_H64_FP_MUL ? h64::mul(x, y) : (op == MSM_AMD_OP_H64_FP_ADD ? h64::add(x, y) : h64::sub(x, y));
-      u256 ro;
-      std::memcpy(&ro, &r, 32);
-      u256_to_be32(ro, out + t * 8);
-    } else {
-      const h64::Jac p = h64::load(be32_to_jac(a + t * 24)), q = h64::load(be32_to_jac(b + t * 24));
-      jac_to_be32(h64::store(op == MSM_AMD_OP_H64_EC_ADD ? h64::jadd(p, q) : h64::jdouble(p)), out + t * 24);
-    }
-  }
-  return true;
-}
-
-int msm_amd_test_op_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
-  if (!a || !b || !out || count == 0 || op < 0) return MSM_AMD_INPUT_ERROR;
-  if (host64_test_op(op, a, b, out, count)) return MSM_AMD_OK;
-  if (op > kTestOpMax) return MSM_AMD_INPUT_ERROR;
-  size_t wa, wb;
-  test_op_widths(op, &wa, &wb);
-  const size_t wo = wa;
-  // the op bodies index points as 3 consecutive u256 per element, scalars of EC_MUL as 1 per element
-  std::vector<u256> la(count * wa), lb(count * std::max(wb, wa)), lo(count * wo);
-  for (size_t i = 0; i < count * wa; ++i) la[i] = be32_to_u256(a + i * 8);
-  for (size_t i = 0; i < count * wb; ++i) lb[i] = be32_to_u256(b + i * 8);
-  for (size_t t = 0; t < count; ++t) run_test_op(op, la.data(), lb.data(), lo.data(), (uint32_t)t);
-  for (size_t i = 0; i < count * wo; ++i) u256_to_be32(lo[i], out + i * 8);
-  return MSM_AMD_OK;
-}
-
-// Raw-limb test ops: the internal limbs pass through unchanged (no from_ext, no reversal, no normalisation).
-static bool test_op_raw_args(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
-  return a && b && out && count > 0 && count <= (1u << 24) && op >= 0 &&
-         (op < kRawOpCount || (op >= kRawWideFirst && op < kRawWideFirst + kRawWideCount) || op == MSM_AMD_RAW_FE_SQRT ||
-          op == MSM_AMD_RAW_BASES_IN_PLACE || (op >= kRawFoldFirst && op < kRawFoldFirst + kRawFoldCount));
-}
-
-int msm_amd_test_op_raw(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
-  if (!ctx || !test_op_raw_args(op, a, b, out, count)) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_op_raw arguments");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const size_t in_bytes = count * kRawInWords * 4, out_bytes = count * kRawOutWords * 4;
-  int rc;
-  if ((rc = ensure(ctx, ctx->scratch_a, in_bytes))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch_b, in_bytes))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch_c, out_bytes))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_a.p, a, in_bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_b.p, b, in_bytes, hipMemcpyHostToDevice, st));
-  if (op == MSM_AMD_RAW_FE_SQRT)   // the root ladder has a kernel of its own (k_compress.hip)
-    launch_sqrt_raw(st, false, (const uint32_t*)ctx->scratch_a.p, (uint32_t*)ctx->scratch_c.p, (uint32_t)count);
-  else
-    launch_test_op_raw(st, op, (const uint32_t*)ctx->scratch_a.p, (const uint32_t*)ctx->scratch_b.p,
-                       (uint32_t*)ctx->scratch_c.p, (uint32_t)count);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch_c.p, out_bytes, hipMemcpyDeviceToHost, st));
-  return sync_stream_bounded(ctx, st, __func__);
-}
-
-int msm_amd_test_op_raw_host(int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
-  if (!test_op_raw_args(op, a, b, out, count)) return MSM_AMD_INPUT_ERROR;
-  if (op == MSM_AMD_RAW_FE_SQRT) {
-    for (size_t t = 0; t < count; ++t) raw_sqrt_fq(a + t * kRawInWords, out + t * kRawOutWords);
-    return MSM_AMD_OK;
-  }
-  for (size_t t = 0; t < count; ++t) run_test_op_raw(op, a, b, out, (uint32_t)t);
-  return MSM_AMD_OK;
-}
-
-// Test aid: occupy the ctx's main stream for at most max_ms (<= 5000) or until msm_amd_test_release -- what a stalled
-// device looks like to the host waits.  The kernel has its own time bound, so nothing can stay blocked.
-int msm_amd_test_hold(msm_amd_ctx* ctx, uint32_t max_ms, void** handle) {
-  if (!ctx || !handle || max_ms == 0 || max_ms > 5000) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_hold arguments");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  uint32_t* flag = nullptr;
-  HIP_TRY(ctx, hipHostMalloc((void**)&flag, 64, hipHostMallocDefault));
-  *flag = 0;
-  launch_hold(ctx->stream, flag, (uint64_t)max_ms * 100000ull);   // wall_clock64 ticks at 100 MHz
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    (void)hipHostFree(flag);
-    HIP_TRY(ctx, e);
-  }
-  *handle = flag;
-  return MSM_AMD_OK;
-}
-
-int msm_amd_test_release(msm_amd_ctx* ctx, void* handle) {
-  if (!ctx || !handle) return MSM_AMD_INPUT_ERROR;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  *(volatile uint32_t*)handle = 1u;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // bounded by the kernel's own limit
-  HIP_TRY(ctx, hipHostFree(handle));
-  return MSM_AMD_OK;
-}
-
-// Stage tap (test aid): what the last instance batch left in its workspaces.  Nothing here runs inside enqueue_msm;
-// it reads the host record of the batch (plans, workspace indices, the plan counters copied behind the partial points)
-// and copies device buffers after the wait, so the pipeline under test is exactly the shipped one.
-static int tap_batch(msm_amd_ctx* ctx, uint32_t j, const Batch** out) {
-  if (ctx->last_waited < 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "stage tap: no batch has been waited for");
-  const Batch& B = ctx->batches[ctx->last_waited];
-  if (B.active || B.n_inst > (size_t)kWorkspaces || B.ws_index.size() != B.n_inst)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "stage tap: the last batch had more instances than the ctx has workspaces");
-  if (j >= B.n_inst) return fail(ctx, MSM_AMD_INPUT_ERROR, "stage tap: no such instance in the last batch");
-  *out = &B;
-  return MSM_AMD_OK;
-}
-
-// The MSM_AMD_TP_* words of one instance (G1: instance j of a batch; G2: the last run_msm_g2)
-static void tap_plan_words(const Plan& p, const PlanCounters& pc, bool lone, uint32_t instances, uint32_t workspace,
-                           uint32_t* out) {
-  uint32_t v[MSM_AMD_TEST_PLAN_WORDS] = {};
-  v[MSM_AMD_TP_C] = p.c;
-  v[MSM_AMD_TP_W] = p.W;
-  v[MSM_AMD_TP_W_DIGITS] = p.W_digits;
-  v[MSM_AMD_TP_N] = p.n;
-  v[MSM_AMD_TP_N_SCALARS] = p.n_scalars;
-  v[MSM_AMD_TP_LB] = p.lb;
-  v[MSM_AMD_TP_NB] = p.nb;
-  v[MSM_AMD_TP_CH] = p.CH;
-  v[MSM_AMD_TP_HB] = p.hb;
-  v[MSM_AMD_TP_MB] = p.mb;
-  v[MSM_AMD_TP_FB] = p.fb;
-  v[MSM_AMD_TP_Q] = p.Q;
-  v[MSM_AMD_TP_TILED] = p.tiled;
-  v[MSM_AMD_TP_BALLOT] = p.ballot;
-  v[MSM_AMD_TP_WIDE_DIGITS] = p.wide_digits ? 1u : 0u;
-  v[MSM_AMD_TP_LONE] = lone ? 1u : 0u;
-  v[MSM_AMD_TP_TOTAL_ITEMS] = pc.total_items;
-  v[MSM_AMD_TP_MULTI_COUNT] = pc.multi_count;
-  v[MSM_AMD_TP_DEFERRED] = pc.pad[0];
-  v[MSM_AMD_TP_RED_GROUP] = p.red_group;
-  v[MSM_AMD_TP_RB_THREADS] = p.rb_threads;
-  v[MSM_AMD_TP_INSTANCES] = instances;
-  v[MSM_AMD_TP_WORKSPACE] = workspace;
-  v[MSM_AMD_TP_FRONT_THREADS] = p.front_threads;
-  v[MSM_AMD_TP_FUSED_FRONT] = p.fused_front ? 1u : 0u;
-  v[MSM_AMD_TP_PACKED] = p.packed ? 1u : 0u;
-  std::memcpy(out, v, sizeof v);
-}
-
-int msm_amd_test_last_plan(msm_amd_ctx* ctx, uint32_t j, uint32_t* out, size_t count) {
-  if (!ctx || !out || count < MSM_AMD_TEST_PLAN_WORDS) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_last_plan arguments");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  const Batch* B = nullptr;
-  if (int rc = tap_batch(ctx, j, &B)) return rc;
-  tap_plan_words(B->plans[j], B->slots[j].counters(), B->lone, (uint32_t)B->n_inst, (uint32_t)B->ws_index[j], out);
-  return MSM_AMD_OK;
-}
-
-// The point-valued buffers of a group and how one record of each leaves through the tap
-struct TapPoints {
-  const DeviceBuf* buckets;   // [W][nb] internal points
-  const DeviceBuf* partial;   // [W][lb + 1] external points
-  size_t bucket_bytes, partial_bytes, out_bytes;   // record sizes: internal point, external point, tap output
-  // on_iso: the tapped plan ran on E' (Plan::on_iso) and the record is mapped back to E on its way out
-  void (*bucket_out)(const uint8_t* rec, uint8_t* out, bool on_iso);
-  void (*partial_out)(const uint8_t* rec, uint8_t* out, bool on_iso);
-};
-
-// One buffer of a finished call: `w` holds the index and count buffers (the same formats for G1 and G2), `pts` the
-// point-valued ones.  ctx->mu held by the caller.
-static int tap_stage_copy(msm_amd_ctx* ctx, const Workspace& w, const Plan& p, const PlanCounters& pc,
-                          const TapPoints& pts, int which, void* out, size_t* bytes) {
-  const DeviceBuf* src = nullptr;
-  size_t dev_bytes = 0, records = 0;
-  switch (which) {
-    case MSM_AMD_STAGE_DIGITS:
-      src = &w.digits;
-      dev_bytes = (size_t)p.W_digits * p.n_scalars * (p.wide_digits ? 4 : 2);
-      break;
-    case MSM_AMD_STAGE_SORTED: src = &w.sorted; dev_bytes = (size_t)p.W * p.n * 4; break;
-    case MSM_AMD_STAGE_BUCKET_SIZE: src = &w.bsize; dev_bytes = p.total_buckets * 4; break;
-    case MSM_AMD_STAGE_BUCKET_START: src = &w.bstart; dev_bytes = p.total_buckets * 4; break;
-    case MSM_AMD_STAGE_ITEM_START: src = &w.istart; dev_bytes = p.total_buckets * 4; break;
-    case MSM_AMD_STAGE_WIN_ITEMS: src = &w.win_items; dev_bytes = (size_t)p.W * 4; break;
-    case MSM_AMD_STAGE_ORDER: src = &w.order; dev_bytes = (size_t)pc.total_items * 8; break;
-    case MSM_AMD_STAGE_MULTI_LIST: src = &w.multi_list; dev_bytes = (size_t)pc.multi_count * 4; break;
-    case MSM_AMD_STAGE_BUCKETS:
-      src = pts.buckets;
-      records = p.total_buckets;
-      dev_bytes = records * pts.bucket_bytes;
-      break;
-    case MSM_AMD_STAGE_PARTIAL:
-      src = pts.partial;
-      records = p.partial_count;
-      dev_bytes = records * pts.partial_bytes;
-      break;
-    default: return fail(ctx, MSM_AMD_INPUT_ERROR, "test_stage_copy: unknown buffer");
-  }
-  const bool points = which == MSM_AMD_STAGE_BUCKETS || which == MSM_AMD_STAGE_PARTIAL;
-  const size_t out_bytes = points ? records * pts.out_bytes : dev_bytes;
-  if (!out) {   // size query
-    *bytes = out_bytes;
-    return MSM_AMD_OK;
-  }
-  if (*bytes != out_bytes)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "test_stage_copy: the buffer holds " + std::to_string(out_bytes) + " bytes");
-  if (dev_bytes > src->cap) return fail(ctx, MSM_AMD_INPUT_ERROR, "test_stage_copy: buffer smaller than the plan");
-  if (dev_bytes == 0) return MSM_AMD_OK;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  std::vector<uint8_t> h(dev_bytes);
-  HIP_TRY(ctx, hipMemcpyAsync(h.data(), src->p, dev_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  if (int rc = sync_stream_bounded(ctx, ctx->stream, __func__)) return rc;
-  if (!points) {
-    std::memcpy(out, h.data(), dev_bytes);
-    return MSM_AMD_OK;
-  }
-  const bool bk = which == MSM_AMD_STAGE_BUCKETS;
-  const size_t rec = bk ? pts.bucket_bytes : pts.partial_bytes;
-  for (size_t i = 0; i < records; ++i)
-    (bk ? pts.bucket_out : pts.partial_out)(h.data() + i * rec, (uint8_t*)out + i * pts.out_bytes, p.on_iso);
-  return MSM_AMD_OK;
-}
-
-// G1 point buffers leave in the wire layout of the stage entry points: Jacobian, 3 x 8 u32 most significant first
-static void tap_g1_bucket(const uint8_t* rec, uint8_t* out, bool on_iso) {
-  PtI q;
-  std::memcpy(&q, rec, sizeof q);
-  const Jacobian j = pti_to_ext(q);
-  jac_to_be32(on_iso ? iso_to_e(j) : j, (uint32_t*)out);
-}
-static void tap_g1_partial(const uint8_t* rec, uint8_t* out, bool on_iso) {
-  Jacobian q;
-  std::memcpy(&q, rec, sizeof q);
-  jac_to_be32(on_iso ? iso_to_e(q) : q, (uint32_t*)out);
-}
-
-int msm_amd_test_stage_copy(msm_amd_ctx* ctx, uint32_t j, int which, void* out, size_t* bytes) {
-  if (!ctx || !bytes) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_stage_copy arguments");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  const Batch* B = nullptr;
-  if (int rc = tap_batch(ctx, j, &B)) return rc;
-  const Workspace& w = ctx->ws[B->ws_index[j]];
-  const TapPoints pts = {&w.buckets, &w.partial, sizeof(PtI), sizeof(Jacobian), 96, tap_g1_bucket, tap_g1_partial};
-  return tap_stage_copy(ctx, w, B->plans[j], B->slots[j].counters(), pts, which, out, bytes);
-}
-
-// Point-valued workspace buffers only: a poisoned index or count could make a kernel gather from wild addresses, a
-// poisoned point can only make a result wrong.
-int msm_amd_test_fill_workspaces(msm_amd_ctx* ctx, uint8_t byte) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int rc = recover_if_stalled(ctx)) return rc;
-  for (const Batch& b : ctx->batches)
-    if (b.active) return fail(ctx, MSM_AMD_INPUT_ERROR, "test_fill_workspaces: a batch is in flight");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (!drain_or_mark_stalled(ctx)) return fail(ctx, MSM_AMD_PIPELINE_ERROR, "test_fill_workspaces: device busy");
-  Workspace* all[kWorkspaces + 1];
-  for (int k = 0; k < kWorkspaces; ++k) all[k] = &ctx->ws[k];
-  all[kWorkspaces] = &ctx->g2.ws;
-  for (Workspace* w : all)
-    for (DeviceBuf* b : {&w->buckets, &w->item_partials, &w->S, &w->T, &w->partial})
-      if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
-  for (CallState* cs : {&ctx->calls, &ctx->g2.calls})   // staging and work buffers of the vector calls; never their 64-byte record
-    for (DeviceBuf* b : cs->scratch_bufs())
-      if (b->p && b->cap) HIP_TRY(ctx, hipMemsetAsync(b->p, byte, b->cap, ctx->stream));
-  return sync_stream_bounded(ctx, ctx->stream, __func__);
-}
-
 int msm_amd_last_timings(const msm_amd_ctx* ctx, msm_amd_timings* out) {
   if (!ctx || !out) return MSM_AMD_INPUT_ERROR;
   *out = ctx->timings;
   return MSM_AMD_OK;
-}
-
-uint64_t msm_amd_algorithmic_bytes(size_t n, uint32_t window_size, int accumulate_only) {
-  // A(n) = 32n + 72nW + 2*96*totB ; A3(n) = 72nW + 96*totB, with
-  // totB = W * (2^c - 1), 64-byte affine bases, 8-byte (bucket, point) pairs, 96-byte buckets.
-  const uint64_t c = window_size ? window_size : auto_window(n);
-  const uint64_t W = (kModulusBits + c - 1) / c;
-  const uint64_t totB = W * ((1ull << c) - 1);
-  if (accumulate_only) return 72ull * n * W + 96ull * totB;
-  return 32ull * n + 72ull * n * W + 2ull * 96ull * totB;
-}
-
-}  // extern "C"
-
-// ---- BN254 G2 MSM (one blocking call on the main stream) -----------------------------------------------------------
-namespace {
-
-// The whole G2 MSM of device-resident inputs: one lone instance (enqueue_instance with the G2 launches) in the G2
-// state's own workspace and slot on the main stream, a bounded wait and the host Horner pass.  d_points: n records of a
-// host layout, a prepared array (MSM_AMD_G2_POINT_PREPARED: no base conversion) or a table handle
-// (MSM_AMD_G2_POINT_TABLES: the one-window plan, every digit window adds into one bucket set).  ctx->mu held by the caller.
-int run_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars, const void* d_points,
-               size_t n, void* out192) {
-  G2State& g2 = ctx->g2;
-  g2.has_last_plan = false;   // the stage tap reads nothing of a call that failed
-  if (n > 0x7FFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, "n >= 2^31");
-  if (int rc = recover_if_stalled(ctx)) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const msm_amd_g2_tables* tb = nullptr;
-  if (g2_point_layout == MSM_AMD_G2_POINT_TABLES) {   // d_points is the handle of msm_amd_g2_tables_build*
-    tb = find_handle(ctx->live_g2_tables, d_points);
-    if (!tb) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
-    if (n != tb->n) return fail(ctx, MSM_AMD_INPUT_ERROR, "n differs from the number of points the tables hold");
-  }
-  const bool prepared = tb != nullptr || g2_point_layout == MSM_AMD_G2_POINT_PREPARED;
-  const WidthBound width = ctx->bound;
-  const uint32_t c = tb ? tb->c : (ctx->forced_window ? ctx->forced_window : auto_window_bounded(n, width.width(), true));
-  const Plan p = instance_plan(n, c, tb ? tb->W : 0, true, width);
-  Workspace& w = g2.ws;
-  InstanceSlot& slot = g2.slot;
-  PointStages g;
-  g.bases_bytes = prepared ? 0 : n * sizeof(Aff2Packed);
-  g.internal_bytes = sizeof(PtI2);
-  g.ext_bytes = sizeof(Jacobian2);
-  g.convert_bases = [&](hipStream_t st) -> int {
-    if (!prepared)
-      launch_convert_bases_g2(st, d_points, g2_point_layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n,
-                              (Aff2Packed*)w.bases29.p);
-    return MSM_AMD_OK;
-  };
-  g.accumulate = [&](hipStream_t st, const SortBuffers& sb, hipEvent_t before, hipEvent_t after) {
-    const void* bases = tb ? tb->d_mem : (prepared ? d_points : w.bases29.p);
-    (void)hipEventRecord(before, st);
-    launch_accumulate_g2(st, p, (const Aff2Packed*)bases, sb, (PtI2*)w.buckets.p, (PtI2*)w.item_partials.p);
-    (void)hipEventRecord(after, st);
-  };
-  g.combine = [&](hipStream_t st, const SortBuffers& sb) { launch_combine_g2(st, p, sb, (PtI2*)w.buckets.p, (PtI2*)w.item_partials.p); };
-  g.reduce = [&](hipStream_t st) {
-    launch_reduce_g2(st, p, (const PtI2*)w.buckets.p, (const uint32_t*)w.bsize.p, (PtI2*)w.S.p, (PtI2*)w.T.p, (Jacobian2*)w.partial.p);
-  };
-  if (int rc = enqueue_instance(ctx, w, slot, p, true, scalar_layout, d_scalars, g)) return rc;
-  const hipError_t we = wait_event(slot.ev[EV_REDUCE], ctx->wait_timeout_ms);
-  if (we == hipErrorNotReady) return wait_timed_out(ctx, slot, "the G2 MSM");
-  if (we != hipSuccess) return fail(ctx, MSM_AMD_PIPELINE_ERROR, std::string("G2 MSM: ") + hipGetErrorString(we));
-  const auto t0 = std::chrono::steady_clock::now();
-  const Jacobian2 res = host_combine_g2((const Jacobian2*)slot.h_partial, p);
-  const float final_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (p.bits) {
-    const PlanCounters pc = slot.counters();
-    if (pc.viol[0]) {
-      reap_graveyard(ctx);
-      return fail(ctx, MSM_AMD_INPUT_ERROR, width_violation_message(p, pc.viol[0], 1, 0, 1, ~pc.viol[1]));
-    }
-  }
-  std::memcpy(out192, &res, 192);
-  ctx->timings = msm_amd_timings{};
-  accumulate_timings(ctx, slot, p, final_ms, 1);
-  reap_graveyard(ctx);
-  g2.last_plan = p;
-  g2.has_last_plan = true;
-  return MSM_AMD_OK;
-}
-
-// the identity result ((R, 0), (R, 0), (0, 0)) of an empty G2 MSM
-void g2_identity_out(void* out192) {
-  Jacobian2 r{};
-  r.x.c0 = Fq::one();
-  r.y.c0 = Fq::one();
-  std::memcpy(out192, &r, 192);
-}
-
-// `device`: the device-resident entry point, which also takes the two device-only layouts (host layouts are the ones
-// msm_amd_g2_point_bytes knows)
-int g2_args(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points, size_t n,
-            const void* out192, bool device = false) {
-  if (!ctx || !out192) return MSM_AMD_INPUT_ERROR;
-  if (!scalar_layout_ok(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
-  const bool device_only = g2_point_layout == MSM_AMD_G2_POINT_PREPARED || g2_point_layout == MSM_AMD_G2_POINT_TABLES;
-  if (msm_amd_g2_point_bytes(g2_point_layout) == 0 && !(device && device_only))
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown G2 point layout");
-  if (n > 0 && (!scalars || !points)) return fail(ctx, MSM_AMD_INPUT_ERROR, "null pointer with n > 0");
-  return MSM_AMD_OK;
-}
-
-// Conversion of a resident G2 point array (a host layout) to Aff2Packed records; ctx->mu held by the caller.
-int prepare_bases_g2_locked(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n, void* d_prepared) {
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (!drain_or_mark_stalled(ctx)) return fail(ctx, MSM_AMD_PIPELINE_ERROR, "device busy past the wait bound");   // a set-up step
-  hipStream_t st = ctx->stream;
-  launch_convert_bases_g2(st, d_points, g2_point_layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n,
-                          (Aff2Packed*)d_prepared);
-  HIP_TRY(ctx, hipGetLastError());
-  return sync_stream_bounded(ctx, st, __func__);
-}
-
-int g2_tables_build_locked(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n, uint32_t window_size,
-                           msm_amd_g2_tables** out) {
-  // The automatic table window: auto_table_window (G1) balances the W n mixed additions against the 2^(c-1) buckets of
-  // the window reduction; the same balance holds on G2 (every term costs the same factor more), so it is the starting
-  // point, and the measurement of DESIGN.md section 8 keeps it.
-  uint32_t c, W;
-  if (int grc = tables_geometry(ctx, n, window_size, auto_table_window(n), &c, &W)) return grc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (!drain_or_mark_stalled(ctx)) return fail(ctx, MSM_AMD_PIPELINE_ERROR, "device busy past the wait bound");   // a set-up step
-  return tables_build_tail(ctx, ctx->live_g2_tables, n, c, W, sizeof(Aff2Packed), "G2 ", [&](void* d_tab) {
-    launch_build_tables_g2(ctx->stream, d_points, g2_point_layout == MSM_AMD_G2_POINT_ARK_AFFINE, (uint32_t)n, c, W,
-                           (Aff2Packed*)d_tab);
-  }, out);
-}
-
-}  // namespace
-
-extern "C" {
-
-// msm_amd_msm_g2_device and its bounded form (bits = 0: unbounded)
-static int msm_g2_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars, const void* d_points,
-                         size_t n, uint32_t bits, int sign, void* out192) {
-  if (int rc = g2_args(ctx, scalar_layout, g2_point_layout, d_scalars, d_points, n, out192, true)) return rc;
-  if (n == 0 && g2_point_layout != MSM_AMD_G2_POINT_TABLES) {   // (a table never holds 0 points: n mismatch below)
-    g2_identity_out(out192);
-    return MSM_AMD_OK;
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  BoundScope scope(ctx, bits, sign);
-  return run_msm_g2(ctx, scalar_layout, g2_point_layout, d_scalars, d_points, n, out192);
-}
-
-int msm_amd_msm_g2_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars,
-                          const void* d_points, size_t n, void* out192) {
-  return msm_g2_device(ctx, scalar_layout, g2_point_layout, d_scalars, d_points, n, 0, 0, out192);
-}
-
-int msm_amd_msm_g2_bounded_device(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* d_scalars,
-                                  const void* d_points, size_t n, uint32_t bits, int sign, void* out192) {
-  if (int rc = bound_args(ctx, __func__, bits, sign)) return rc;
-  return msm_g2_device(ctx, scalar_layout, g2_point_layout, d_scalars, d_points, n, bits, sign, out192);
-}
-
-int msm_amd_g2_bases_prepare_device(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n,
-                                    void* d_prepared) {
-  if (!ctx || !d_points || !d_prepared || n == 0 || n > 0x7FFFFFFFull)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "bad g2_bases_prepare arguments");
-  if (msm_amd_g2_point_bytes(g2_point_layout) == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad G2 point layout");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  return prepare_bases_g2_locked(ctx, g2_point_layout, d_points, n, d_prepared);
-}
-
-int msm_amd_g2_bases_upload(msm_amd_ctx* ctx, int g2_point_layout, const void* points, size_t n, void** d_prepared) {
-  if (!ctx || !points || !d_prepared || n == 0 || n > 0x7FFFFFFFull)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "bad g2_bases_upload arguments");
-  const size_t pb = msm_amd_g2_point_bytes(g2_point_layout);
-  if (pb == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad G2 point layout");
-  *d_prepared = nullptr;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  return upload_and_prepare(
-      ctx, ctx->g2.in_points, points, n * pb, n * sizeof(Aff2Packed), "the resident copy of the G2 bases",
-      [&](const void* staged, void* d_out) { return prepare_bases_g2_locked(ctx, g2_point_layout, staged, n, d_out); },
-      d_prepared);
-}
-
-// host scalars -> the G2 state's staging buffer, on the stream the MSM runs on (stream order does the rest)
-static int g2_stage_scalars(msm_amd_ctx* ctx, const void* scalars, size_t n) {
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (int rc = recover_if_stalled(ctx)) return rc;
-  if (int rc = ensure(ctx, ctx->g2.in_scalars, n * 32)) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->g2.in_scalars.p, scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
-  return MSM_AMD_OK;
-}
-
-int msm_amd_msm_g2_prepared(msm_amd_ctx* ctx, int scalar_layout, const void* scalars, const void* d_prepared, size_t n,
-                            void* out192) {
-  if (!ctx || !scalars || !d_prepared || !out192 || n == 0)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "bad msm_g2_prepared arguments");
-  if (!scalar_layout_ok(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  if (int rc = g2_stage_scalars(ctx, scalars, n)) return rc;
-  return run_msm_g2(ctx, scalar_layout, MSM_AMD_G2_POINT_PREPARED, ctx->g2.in_scalars.p, d_prepared, n, out192);
-}
-
-int msm_amd_g2_tables_build_device(msm_amd_ctx* ctx, int g2_point_layout, const void* d_points, size_t n,
-                                   uint32_t window_size, msm_amd_g2_tables** out) {
-  if (!ctx || !d_points || !out || n == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad g2_tables_build arguments");
-  *out = nullptr;
-  if (msm_amd_g2_point_bytes(g2_point_layout) == 0)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "G2 tables are built from one of the host point layouts");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  return g2_tables_build_locked(ctx, g2_point_layout, d_points, n, window_size, out);
-}
-
-int msm_amd_g2_tables_build(msm_amd_ctx* ctx, int g2_point_layout, const void* points, size_t n, uint32_t window_size,
-                            msm_amd_g2_tables** out) {
-  if (!ctx || !points || !out || n == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad g2_tables_build arguments");
-  *out = nullptr;
-  const size_t pb = msm_amd_g2_point_bytes(g2_point_layout);
-  if (pb == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "G2 tables are built from one of the host point layouts");
-  if (n > 0x7FFFFFFFull) return fail(ctx, MSM_AMD_INPUT_ERROR, "windows * n must stay below 2^31");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (int rc = ensure(ctx, ctx->g2.in_points, n * pb)) return rc;
-  HIP_TRY(ctx, hipMemcpy(ctx->g2.in_points.p, points, n * pb, hipMemcpyHostToDevice));
-  return g2_tables_build_locked(ctx, g2_point_layout, ctx->g2.in_points.p, n, window_size, out);
-}
-
-int msm_amd_g2_tables_info(msm_amd_ctx* ctx, const msm_amd_g2_tables* tables, size_t* n, uint32_t* window_size,
-                           uint32_t* num_windows, size_t* device_bytes) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  return tables_info(ctx, ctx->live_g2_tables, tables, "not a G2 table handle of this ctx", n,
-                     window_size, num_windows, device_bytes);
-}
-
-int msm_amd_g2_tables_free(msm_amd_ctx* ctx, msm_amd_g2_tables* tables) {
-  if (!ctx) return MSM_AMD_INPUT_ERROR;
-  std::lock_guard<std::mutex> g(ctx->mu);
-  return handle_free(ctx, ctx->live_g2_tables, tables, "not a G2 table handle of this ctx");
-}
-
-int msm_amd_msm_g2_tables(msm_amd_ctx* ctx, const msm_amd_g2_tables* tables, int scalar_layout, const void* scalars,
-                          void* out192) {
-  if (!ctx || !tables || !scalars || !out192) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad msm_g2_tables arguments");
-  if (!scalar_layout_ok(scalar_layout)) return fail(ctx, MSM_AMD_INPUT_ERROR, "unknown scalar layout");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  const msm_amd_g2_tables* t = find_handle(ctx->live_g2_tables, tables);
-  if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
-  if (int rc = g2_stage_scalars(ctx, scalars, t->n)) return rc;
-  return run_msm_g2(ctx, scalar_layout, MSM_AMD_G2_POINT_TABLES, ctx->g2.in_scalars.p, tables, t->n, out192);
-}
-
-int msm_amd_test_g2_tables_read(msm_amd_ctx* ctx, const msm_amd_g2_tables* tables, uint32_t w, size_t first,
-                                size_t count, void* out) {
-  if (!ctx || !out || count == 0) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad g2_tables_read arguments");
-  std::lock_guard<std::mutex> g(ctx->mu);
-  const msm_amd_g2_tables* t = find_handle(ctx->live_g2_tables, tables);
-  if (!t) return fail(ctx, MSM_AMD_INPUT_ERROR, "not a G2 table handle of this ctx");
-  if (w >= t->W || first >= t->n || count > t->n - first)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "window or point range outside the table");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  std::vector<Aff2Packed> rec(count);
-  HIP_TRY(ctx, hipMemcpyAsync(rec.data(), (const Aff2Packed*)t->d_mem + (size_t)w * t->n + first,
-                              count * sizeof(Aff2Packed), hipMemcpyDeviceToHost, ctx->stream));
-  if (int rc = sync_stream_bounded(ctx, ctx->stream, __func__)) return rc;
-  for (size_t i = 0; i < count; ++i) {
-    const Affine2 e = aff2packed_to_ext(rec[i]);
-    std::memcpy((uint8_t*)out + i * 128, &e, 128);
-  }
-  return MSM_AMD_OK;
-}
-
-// msm_amd_msm_g2 and its bounded form (bits = 0: unbounded)
-static int msm_g2_host(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points,
-                       size_t n, uint32_t bits, int sign, void* out192) {
-  if (int rc = g2_args(ctx, scalar_layout, g2_point_layout, scalars, points, n, out192)) return rc;
-  if (n == 0) {
-    g2_identity_out(out192);
-    return MSM_AMD_OK;
-  }
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  BoundScope scope(ctx, bits, sign);
-  G2State& g = ctx->g2;
-  const size_t pb = n * msm_amd_g2_point_bytes(g2_point_layout);
-  if (int rc = g2_stage_scalars(ctx, scalars, n)) return rc;
-  if (int rc = ensure(ctx, g.in_points, pb)) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(g.in_points.p, points, pb, hipMemcpyHostToDevice, ctx->stream));
-  return run_msm_g2(ctx, scalar_layout, g2_point_layout, g.in_scalars.p, g.in_points.p, n, out192);
-}
-
-int msm_amd_msm_g2(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points,
-                   size_t n, void* out192) {
-  return msm_g2_host(ctx, scalar_layout, g2_point_layout, scalars, points, n, 0, 0, out192);
-}
-
-int msm_amd_msm_g2_bounded(msm_amd_ctx* ctx, int scalar_layout, int g2_point_layout, const void* scalars, const void* points,
-                           size_t n, uint32_t bits, int sign, void* out192) {
-  if (int rc = bound_args(ctx, __func__, bits, sign)) return rc;
-  return msm_g2_host(ctx, scalar_layout, g2_point_layout, scalars, points, n, bits, sign, out192);
-}
-
-// Stage tap of the G2 MSM (test aid): plan, plan counters (behind the partial points in the G2 slot, as for a G1
-// instance) and buffers of the last run_msm_g2, read after the call.
-static const char* const kNoG2Plan = "G2 stage tap: no G2 MSM of this ctx has succeeded last";
-
-// G2 point buffers leave in the result form of msm_amd_msm_g2 (192 B Jacobian, Montgomery LE; identity: z all zero)
-static void tap_g2_bucket(const uint8_t* rec, uint8_t* out, bool) {
-  PtI2 q;
-  std::memcpy(&q, rec, sizeof q);
-  const Jacobian2 e = pt2_to_ext(q);
-  std::memcpy(out, &e, sizeof e);
-}
-static void tap_g2_partial(const uint8_t* rec, uint8_t* out, bool) { std::memcpy(out, rec, sizeof(Jacobian2)); }
-
-int msm_amd_test_g2_last_plan(msm_amd_ctx* ctx, uint32_t* out, size_t count) {
-  if (!ctx || !out || count < MSM_AMD_TEST_PLAN_WORDS)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_g2_last_plan arguments");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (!ctx->g2.has_last_plan) return fail(ctx, MSM_AMD_INPUT_ERROR, kNoG2Plan);
-  tap_plan_words(ctx->g2.last_plan, ctx->g2.slot.counters(), true, 1, 0, out);
-  return MSM_AMD_OK;
-}
-
-int msm_amd_test_g2_stage_copy(msm_amd_ctx* ctx, int which, void* out, size_t* bytes) {
-  if (!ctx || !bytes) return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_g2_stage_copy arguments");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const G2State& g = ctx->g2;
-  if (!g.has_last_plan) return fail(ctx, MSM_AMD_INPUT_ERROR, kNoG2Plan);
-  const TapPoints pts = {&g.ws.buckets, &g.ws.partial, sizeof(PtI2), sizeof(Jacobian2), sizeof(Jacobian2), tap_g2_bucket,
-                         tap_g2_partial};
-  return tap_stage_copy(ctx, g.ws, g.last_plan, g.slot.counters(), pts, which, out, bytes);
-}
-
-int msm_amd_test_op_g2(msm_amd_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t count) {
-  if (!ctx || op < 0 || (op >= G2RAW_OPS && op != MSM_AMD_G2_RAW_FQ2_SQRT) || count == 0 || count > (1u << 20) || !a || !b ||
-      !out)
-    return fail(ctx, MSM_AMD_INPUT_ERROR, "bad test_op_g2 arguments");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const size_t in_bytes = count * kG2RawIn * 4, out_bytes = count * kG2RawOut * 4;
-  int rc;
-  if ((rc = ensure(ctx, ctx->scratch_a, in_bytes))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch_b, in_bytes))) return rc;
-  if ((rc = ensure(ctx, ctx->scratch_c, out_bytes))) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_a.p, a, in_bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_b.p, b, in_bytes, hipMemcpyHostToDevice, st));
-  if (op == MSM_AMD_G2_RAW_FQ2_SQRT)
-    launch_sqrt_raw(st, true, (const uint32_t*)ctx->scratch_a.p, (uint32_t*)ctx->scratch_c.p, (uint32_t)count);
-  else
-    launch_test_op_g2(st, op, (const uint32_t*)ctx->scratch_a.p, (const uint32_t*)ctx->scratch_b.p,
-                      (uint32_t*)ctx->scratch_c.p, (uint32_t)count);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch_c.p, out_bytes, hipMemcpyDeviceToHost, st));
-  return sync_stream_bounded(ctx, st, __func__);
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@ the counted ideal: the ratio of the window counts.  Signed rows: +-values below 
 The width scan is timed as the wall time of its blocking call against MSM_AMD_FR_MUL on the same count (same bytes in,
 one product per record).
 --sweep: instead, every forced window 3..17 per cell, as text (profiles/bounded_sweep.txt): what the window policy of
-auto_window_bounded (msm_host.hip) was read from.
+auto_window_bounded (msm_plan.hip) was read from.
 
   python tools/bounded_bench.py [--logs 16 20 22] [--bits 1 8 16 32 64 128 254] [--out profiles/bounded_bench.json]
   python tools/bounded_bench.py --sweep [--logs 16 18 20 22] [--out profiles/bounded_sweep.txt]

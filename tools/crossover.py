@@ -2,8 +2,8 @@
 
 Times ONE blocking call per size through the C ABI: msm_amd_gpu_msm_h2c (GPU, host buffers, upload included) against
 the product's host bucket method (msm_amd_gpu_with_cpu with split_at = 0: every point goes to the CPU half), 1 thread
-and all threads.  Prints a table and the largest n for which the host wins; kCpuDispatchBelow in csrc/msm_host.hip is
-set from it (profiles/r02_crossover.txt)."""
+and all threads.  Prints a table and the largest n for which the host wins; kCpuDispatchBelow in csrc/host_ctx.h (read by
+cpu_dispatch_below in csrc/msm_host.hip) is set from it (profiles/r02_crossover.txt)."""
 import importlib
 import os
 import statistics
