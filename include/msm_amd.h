@@ -1295,6 +1295,61 @@ enum { MSM_AMD_MLE_CALL_BIND = 0, MSM_AMD_MLE_CALL_EVAL = 1, MSM_AMD_MLE_CALL_EQ
 int msm_amd_test_fr_mle_plan(int call, int order, int form, size_t n, size_t n_vec, uint32_t n_bind, uint32_t chunk_log,
                              uint32_t tile_log, uint64_t counts[8]);
 
+/* ---- sumcheck rounds over a caller-described sum of products, and the step that binds first ----------------------
+ * arkworks' ListOfProductsOfPolynomials, HyperPlonk's gate zero checks and GKR layers are sums of products of tables
+ * under an optional common factor:
+ *   F = [f_outer] sum_k c_k prod_j f_(factors[k][j]),   d = max_k term_len[k] + (outer given ? 1 : 0),   1 <= d <= 7.
+ * Up to 16 tables, 16 terms, 6 factors per term; an index may repeat inside a term (powers) and across terms, and the
+ * outer table may also be a factor.  The coefficients are records in HOST memory in the call's layout, any 256-bit
+ * word taken mod r; 1 and r - 1 cost no product.  Tables, stride, orders, layouts, "any word mod r", fully reduced
+ * outputs, alignment, the bounded wait and msm_amd_last_error are those of msm_amd_fr_sumcheck_round*; g_out is HOST
+ * memory, d + 1 records g(0) .. g(d).  n_vec == 0: MSM_AMD_OK, nothing is touched, the term list is not looked at.
+ * MSM_AMD_INPUT_ERROR, each with its own text: n_terms outside 1 .. 16; a term length outside 1 .. 6; a table index
+ * (outer included) not below n_vec; n_vec above 16; a null pointer in the list or a null list. */
+enum { MSM_AMD_SUMCHECK_MAX_TABLES = 16, MSM_AMD_SUMCHECK_MAX_TERMS = 16, MSM_AMD_SUMCHECK_MAX_FACTORS = 6 };
+#define MSM_AMD_SUMCHECK_NO_OUTER 0xFFFFFFFFu
+typedef struct msm_amd_fr_sumcheck_terms {
+  uint32_t n_terms;          /* 1 .. 16 */
+  uint32_t outer;            /* a table index < n_vec, or MSM_AMD_SUMCHECK_NO_OUTER */
+  const void* coeff;         /* n_terms records, HOST memory, the call's scalar layout, any 256-bit word taken mod r */
+  const uint32_t* term_len;  /* n_terms values, each 1 .. 6 */
+  const uint32_t* factors;   /* sum(term_len) table indices < n_vec, term after term; an index may repeat (powers) */
+} msm_amd_fr_sumcheck_terms;
+/* The shared check of a term list against n_vec tables (no ctx, CPU only; the coefficients are not read) and its
+ * degree in *d.  MSM_AMD_INPUT_ERROR for a list the calls below refuse, n_vec == 0 and a null d included. */
+int msm_amd_fr_sumcheck_terms_degree(const msm_amd_fr_sumcheck_terms* terms, size_t n_vec, uint32_t* d);
+/* One round's polynomial of F, as msm_amd_fr_sumcheck_round*: `in` is never written.  mem (MSM_AMD_MEM_HOST /
+ * MSM_AMD_MEM_DEVICE, below): where `in` lies -- host memory staged through the ctx like the other host-buffer forms, or
+ * device-resident tables, 16-byte aligned; an unknown mem is MSM_AMD_INPUT_ERROR.  (One entry point with a `mem` argument
+ * rather than a _device twin, as msm_amd_fr_sort: DESIGN.md section 8.16.)  g_out is HOST memory either way; kernel_ms is
+ * optional. */
+int msm_amd_fr_sumcheck_round_terms(msm_amd_ctx* ctx, int mem, int scalar_layout, int order,
+                                    const msm_amd_fr_sumcheck_terms* terms, const void* in, size_t n, size_t n_vec,
+                                    size_t stride, void* g_out /* d + 1 HOST records */, float* kernel_ms);
+int msm_amd_host_fr_sumcheck_round_terms(int scalar_layout, int order, const msm_amd_fr_sumcheck_terms* terms, const void* in,
+                                         size_t n, size_t n_vec, size_t stride, int threads, void* g_out);
+/* One step of a sumcheck in one call and one bounded wait: bind the previous round's challenge r (one HOST record),
+ * then the next round's values (a bind launch and the round's launches on the ctx's stream).  By definition the result is that of
+ * msm_amd_fr_mle_bind*(n_bind = 1, r) followed by msm_amd_fr_sumcheck_round_terms* at n / 2 on the bound tables: the
+ * first n / 2 records of every output table (at out + 32 v stride) are the bound table, fully reduced, in the call's
+ * layout, and g_out is that table set's round polynomial.  The call writes NO OTHER BYTE of out (stricter than bind).
+ * n a power of two, n >= 4: the last variable is msm_amd_fr_mle_bind / msm_amd_fr_mle_eval.  MSM_AMD_MLE_HIGH: out ==
+ * in is allowed; otherwise out must be disjoint from the whole input span.  MSM_AMD_MLE_LOW is out of place only; a
+ * partial overlap is MSM_AMD_INPUT_ERROR.  An out-of-place call leaves `in` unchanged.  A whole sumcheck of m
+ * variables: round_terms once, step_terms per challenge but the last, mle_eval or mle_bind for the last variable. */
+int msm_amd_fr_sumcheck_step_terms(msm_amd_ctx* ctx, int mem /* of in and out */, int scalar_layout, int order,
+                                   const msm_amd_fr_sumcheck_terms* terms, const void* r /* HOST memory */, const void* in,
+                                   size_t n, size_t n_vec, size_t stride, void* out, void* g_out /* d + 1 HOST records */,
+                                   float* kernel_ms);
+int msm_amd_host_fr_sumcheck_step_terms(int scalar_layout, int order, const msm_amd_fr_sumcheck_terms* terms, const void* r,
+                                        const void* in, size_t n, size_t n_vec, size_t stride, int threads, void* out,
+                                        void* g_out);
+/* Test aid (no ctx, CPU only): the plan of one of these calls at chunk_log (6 .. 20); step != 0: the step call at n.
+ * counts as the round row of msm_amd_test_fr_mle_plan: [0] launches, [1] dispatched waves, [2] records of ctx-owned
+ * device memory, [3] the same in bytes, [4] levels, [5] waves of the first launch, [6] d + 1, [7] 0. */
+int msm_amd_test_fr_sumcheck_terms_plan(const msm_amd_fr_sumcheck_terms* terms, size_t n, size_t n_vec, uint32_t chunk_log,
+                                        int step, uint64_t counts[8]);
+
 /* ---- Poseidon over Fr: permutations, hashes and Merkle trees ------------------------------------------------------------
  * The algebraic hash of the circomlib / circomlibjs / iden3 family (Grassi et al., S-box x^5) over BN254 Fr for a state of
  * t = 2 .. 5 records: Semaphore / Tornado style membership trees, Poseidon-Merkle commitments to columns that

@@ -65,6 +65,8 @@ MLE_LOW, MLE_HIGH = 0, 1
 WIDTH_UNSIGNED, WIDTH_SIGNED = 0, 1
 SUMCHECK_PRODUCT, SUMCHECK_EQ_AB_C = 0, 1
 MLE_CALL_BIND, MLE_CALL_EVAL, MLE_CALL_EQ_TABLE, MLE_CALL_ROUND = range(4)
+SUMCHECK_MAX_TABLES, SUMCHECK_MAX_TERMS, SUMCHECK_MAX_FACTORS = 16, 16, 6
+SUMCHECK_NO_OUTER = 0xFFFFFFFF
 # pairings (MSM_AMD_GT_*, MSM_AMD_PAIRING_*, MSM_AMD_FQ12_OP_*)
 GT_MONT_LE, GT_CANON_LE = 0, 1
 GT_BYTES = 384
@@ -142,6 +144,9 @@ EXPORTS = [
     "msm_amd_fr_eq_table", "msm_amd_fr_eq_table_device", "msm_amd_host_fr_eq_table",
     "msm_amd_fr_sumcheck_round", "msm_amd_fr_sumcheck_round_device", "msm_amd_host_fr_sumcheck_round",
     "msm_amd_test_fr_mle_plan",
+    "msm_amd_fr_sumcheck_terms_degree", "msm_amd_fr_sumcheck_round_terms",
+    "msm_amd_host_fr_sumcheck_round_terms", "msm_amd_fr_sumcheck_step_terms",
+    "msm_amd_host_fr_sumcheck_step_terms", "msm_amd_test_fr_sumcheck_terms_plan",
     "msm_amd_scalar_width", "msm_amd_scalar_width_device", "msm_amd_host_scalar_width",
     "msm_amd_msm_bounded", "msm_amd_msm_bounded_device", "msm_amd_msm_batch_bounded_device",
     "msm_amd_submit_batch_bounded_device", "msm_amd_msm_g2_bounded", "msm_amd_msm_g2_bounded_device",
@@ -498,6 +503,18 @@ def _lib():
                                                      c_void_p]
         L.msm_amd_test_fr_mle_plan.argtypes = [c_int, c_int, c_int, c_size_t, c_size_t, c_uint32, c_uint32, c_uint32,
                                                POINTER(c_uint64)]
+        if hasattr(L, "msm_amd_fr_sumcheck_round_terms"):   # (an MSM_AMD_LIB build from before the term lists still loads)
+            tp = c_void_p                                   # const msm_amd_fr_sumcheck_terms*
+            L.msm_amd_fr_sumcheck_terms_degree.argtypes = [tp, c_size_t, POINTER(c_uint32)]
+            L.msm_amd_fr_sumcheck_round_terms.argtypes = [c_void_p, c_int, c_int, c_int, tp, c_void_p, c_size_t, c_size_t, c_size_t,
+                                                          c_void_p, POINTER(c_float)]
+            L.msm_amd_host_fr_sumcheck_round_terms.argtypes = [c_int, c_int, tp, c_void_p, c_size_t, c_size_t, c_size_t, c_int,
+                                                               c_void_p]
+            L.msm_amd_fr_sumcheck_step_terms.argtypes = [c_void_p, c_int, c_int, c_int, tp, c_void_p, c_void_p, c_size_t, c_size_t,
+                                                         c_size_t, c_void_p, c_void_p, POINTER(c_float)]
+            L.msm_amd_host_fr_sumcheck_step_terms.argtypes = [c_int, c_int, tp, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t,
+                                                              c_int, c_void_p, c_void_p]
+            L.msm_amd_test_fr_sumcheck_terms_plan.argtypes = [tp, c_size_t, c_size_t, c_uint32, c_int, POINTER(c_uint64)]
         if hasattr(L, "msm_amd_poseidon_constants"):   # (an MSM_AMD_LIB build from before the Poseidon calls still loads)
             shape = [c_uint32, c_uint32, c_uint32, c_int, c_void_p, c_void_p]   # t, r_f, r_p, layout, ark, mds
             L.msm_amd_poseidon_constants.argtypes = shape
@@ -1563,6 +1580,49 @@ class MsmConfig:
                                                             n if stride is None else stride, g, ctypes.byref(ms)))
         return g.raw[:32 * sumcheck_values(form, n_vec)], ms.value
 
+    def fr_sumcheck_round_terms(self, data: bytes, n: int, terms, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, n_vec=1,
+                                stride=None) -> bytes:
+        """The d + 1 records g(0) .. g(d) of one round of a SumcheckTerms list over host tables
+        (msm_amd_fr_sumcheck_round_terms with MEM_HOST)"""
+        g = ctypes.create_string_buffer(32 * 8)
+        self._check(_lib().msm_amd_fr_sumcheck_round_terms(self.h, MEM_HOST, scalar_layout, order, _terms_ptr(terms), data, n, n_vec,
+                                                           n if stride is None else stride, g, None))
+        return g.raw[:32 * sumcheck_terms_values(terms, n_vec)]
+
+    def fr_sumcheck_round_terms_device(self, d_in, n: int, terms, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, n_vec=1,
+                                       stride=None):
+        """The same on device-resident tables (msm_amd_fr_sumcheck_round_terms with MEM_DEVICE); returns (records, kernel_ms)."""
+        ms = c_float(0)
+        g = ctypes.create_string_buffer(32 * 8)
+        self._check(_lib().msm_amd_fr_sumcheck_round_terms(self.h, MEM_DEVICE, scalar_layout, order, _terms_ptr(terms), c_void_p(d_in),
+                                                                  n, n_vec, n if stride is None else stride, g,
+                                                                  ctypes.byref(ms)))
+        return g.raw[:32 * sumcheck_terms_values(terms, n_vec)], ms.value
+
+    def fr_sumcheck_step_terms(self, data: bytes, r: bytes, n: int, terms, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, n_vec=1,
+                               stride=None, out: bytes = None):
+        """Bind r, then the next round's values, over host tables (msm_amd_fr_sumcheck_step_terms): (the output span of
+        (n_vec - 1) stride + n / 2 records, or all of `out` if given, written over a copy of it; the d + 1 records)"""
+        stride = n if stride is None else stride
+        span = 32 * ((n_vec - 1) * stride + n // 2) if n_vec else 0
+        size = len(out) if out is not None else span
+        buf = ctypes.create_string_buffer(out if out is not None else b"\xFF" * span, size + 1)
+        g = ctypes.create_string_buffer(32 * 8)
+        self._check(_lib().msm_amd_fr_sumcheck_step_terms(self.h, MEM_HOST, scalar_layout, order, _terms_ptr(terms), r, data, n, n_vec,
+                                                          stride, buf, g, None))
+        return buf.raw[:size], g.raw[:32 * sumcheck_terms_values(terms, n_vec)]
+
+    def fr_sumcheck_step_terms_device(self, d_in, n: int, d_out, r: bytes, terms, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE,
+                                      n_vec=1, stride=None):
+        """The same on device-resident tables, d_out == d_in with MLE_HIGH or disjoint
+        (msm_amd_fr_sumcheck_step_terms with MEM_DEVICE); returns (records, kernel_ms)."""
+        ms = c_float(0)
+        g = ctypes.create_string_buffer(32 * 8)
+        self._check(_lib().msm_amd_fr_sumcheck_step_terms(self.h, MEM_DEVICE, scalar_layout, order, _terms_ptr(terms), r,
+                                                                 c_void_p(d_in), n, n_vec, n if stride is None else stride,
+                                                                 c_void_p(d_out), g, ctypes.byref(ms)))
+        return g.raw[:32 * sumcheck_terms_values(terms, n_vec)], ms.value
+
     # ---- pairings -------------------------------------------------------------------------------
     def pairing_product(self, g1_points: bytes, g2_points: bytes, n_groups: int, group_size: int, flags=0,
                         gt_layout=GT_MONT_LE, point_layout=POINT_H2C_AFFINE, g2_point_layout=G2_POINT_H2C_AFFINE,
@@ -2504,6 +2564,83 @@ def host_fr_sumcheck_round(data: bytes, n: int, form=SUMCHECK_PRODUCT, order=MLE
     if st != OK:
         raise MsmError(st)
     return g.raw[:32 * sumcheck_values(form, n_vec)]
+
+
+class _SumcheckTermsC(ctypes.Structure):
+    _fields_ = [("n_terms", c_uint32), ("outer", c_uint32), ("coeff", c_void_p), ("term_len", POINTER(c_uint32)),
+                ("factors", POINTER(c_uint32))]
+
+
+class SumcheckTerms:
+    """A term list F = [f_outer] sum_k c_k prod_j f_(factors[k][j]) for the *_terms calls (msm_amd_fr_sumcheck_terms):
+    `terms` is a sequence of (coefficient record of 32 bytes in the call's layout, sequence of table indices)."""
+
+    def __init__(self, terms, outer=None):
+        terms = list(terms)
+        self.coeff = ctypes.create_string_buffer(b"".join(c for c, _ in terms), max(1, 32 * len(terms)))
+        self.term_len = (c_uint32 * max(1, len(terms)))(*[len(f) for _, f in terms])
+        flat = [i for _, f in terms for i in f]
+        self.factors = (c_uint32 * max(1, len(flat)))(*flat)
+        self.c = _SumcheckTermsC(len(terms), SUMCHECK_NO_OUTER if outer is None else outer,
+                                 ctypes.cast(self.coeff, c_void_p), self.term_len, self.factors)
+
+
+def _terms_ptr(terms):
+    return None if terms is None else ctypes.addressof(terms.c)
+
+
+def sumcheck_terms_degree(terms, n_vec) -> int:
+    """The degree d of a round over `terms` and n_vec tables (msm_amd_fr_sumcheck_terms_degree: the shared check of a list)"""
+    d = c_uint32(0)
+    st = _lib().msm_amd_fr_sumcheck_terms_degree(_terms_ptr(terms), n_vec, ctypes.byref(d))
+    if st != OK:
+        raise MsmError(st)
+    return d.value
+
+
+def sumcheck_terms_values(terms, n_vec) -> int:
+    """d + 1 of a round over a term list: the records the *_terms calls return (0 when there is nothing to do)"""
+    return 0 if n_vec == 0 else sumcheck_terms_degree(terms, n_vec) + 1
+
+
+def host_fr_sumcheck_round_terms(data: bytes, n: int, terms, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, n_vec=1, stride=None,
+                                 threads=0) -> bytes:
+    """Host twin of MsmConfig.fr_sumcheck_round_terms (no GPU)."""
+    g = ctypes.create_string_buffer(32 * 8)
+    st = _lib().msm_amd_host_fr_sumcheck_round_terms(scalar_layout, order, _terms_ptr(terms), data, n, n_vec,
+                                                     n if stride is None else stride, threads, g)
+    if st != OK:
+        raise MsmError(st)
+    return g.raw[:32 * sumcheck_terms_values(terms, n_vec)]
+
+
+def host_fr_sumcheck_step_terms(data: bytes, r: bytes, n: int, terms, order=MLE_LOW, scalar_layout=SCALAR_MONT_LE, n_vec=1,
+                                stride=None, threads=0, out: bytes = None):
+    """Host twin of MsmConfig.fr_sumcheck_step_terms (no GPU); out == "in place": the call runs on one buffer (MLE_HIGH)."""
+    stride = n if stride is None else stride
+    span = 32 * ((n_vec - 1) * stride + n // 2) if n_vec else 0
+    g = ctypes.create_string_buffer(32 * 8)
+    if out == "in place":
+        buf = ctypes.create_string_buffer(data, len(data) + 1)
+        size, src = len(data), buf
+    else:
+        size = len(out) if out is not None else span
+        buf = ctypes.create_string_buffer(out if out is not None else b"\xFF" * span, size + 1)
+        src = data
+    st = _lib().msm_amd_host_fr_sumcheck_step_terms(scalar_layout, order, _terms_ptr(terms), r, src, n, n_vec, stride, threads,
+                                                    buf, g)
+    if st != OK:
+        raise MsmError(st)
+    return buf.raw[:size], g.raw[:32 * sumcheck_terms_values(terms, n_vec)]
+
+
+def test_fr_sumcheck_terms_plan(terms, n, n_vec=1, chunk_log=8, step=False) -> dict:
+    """The plan of a *_terms call (msm_amd_test_fr_sumcheck_terms_plan); step: msm_amd_fr_sumcheck_step_terms at n."""
+    out = (c_uint64 * 8)()
+    st = _lib().msm_amd_test_fr_sumcheck_terms_plan(_terms_ptr(terms), n, n_vec, chunk_log, int(step), out)
+    if st != OK:
+        raise MsmError(st)
+    return dict(zip(("launches", "waves", "records", "bytes", "levels", "first_waves", "values"), out))
 
 
 def test_fr_mle_plan(call, n, n_vec=1, order=MLE_LOW, form=SUMCHECK_PRODUCT, n_bind=1, chunk_log=8, tile_log=9) -> dict:

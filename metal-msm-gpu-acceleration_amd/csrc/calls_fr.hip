@@ -819,7 +819,7 @@ int msm_amd_fr_matvec_device(msm_amd_ctx* ctx, const msm_amd_fr_matrix* matrix, 
 }  // extern "C"
 
 // ---- multilinear tables over Fr and sumcheck rounds (msm_amd_fr_mle_bind*, msm_amd_fr_mle_eval*, msm_amd_fr_eq_table*,
-// msm_amd_fr_sumcheck_round*) ------------------------------------------------------------------------------------------------
+// msm_amd_fr_sumcheck_round*, _round_terms*, _step_terms*) ------------------------------------------------------------------------------------------------
 // Through device_call.  Challenges and points are read once on the host and reach the kernels by value.  The values of an
 // evaluation or a round come back through CallState::h_values.  The host form of a bind copies back the records the call
 // defines and no byte between the tables: one strided copy behind the kernels.
@@ -938,6 +938,52 @@ int fr_sumcheck_round_call(msm_amd_ctx* ctx, bool host, int scalar_layout, int o
   return rc;
 }
 
+// A round over a term list, and the step: the bind launch of every table at r and the round launch over what it wrote, on
+// the stream under the call's one wait (a kernel that folds and sums in one pass was measured and is slower than the two
+// launches at every size: DESIGN.md section 8.17).  The host
+// form of the step works from the staged input into the staged output and brings back the n / 2 records of every table the
+// call defines, as the host form of a bind does.
+int fr_sumcheck_terms_call(msm_amd_ctx* ctx, int mem, bool step, int scalar_layout, int order,
+                           const msm_amd_fr_sumcheck_terms* terms, const void* r32, const void* in, size_t n, size_t n_vec,
+                           size_t stride, void* out, void* g_out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = step ? "msm_amd_fr_sumcheck_step_terms" : "msm_amd_fr_sumcheck_round_terms";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (mem != MSM_AMD_MEM_HOST && mem != MSM_AMD_MEM_DEVICE)
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": mem must be MSM_AMD_MEM_HOST or MSM_AMD_MEM_DEVICE");
+  const bool host = mem == MSM_AMD_MEM_HOST;
+  FrTermRoundLaunch c{};
+  if (const char* why = step ? fr_sumcheck_step_check(scalar_layout, order, terms, r32, in, n, n_vec, stride, out, g_out, !host, &c.terms)
+                             : fr_sumcheck_terms_round_check(scalar_layout, order, terms, in, n, n_vec, stride, g_out, !host, &c.terms))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n_vec == 0) return MSM_AMD_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  CallState& s = ctx->calls;
+  c.n = n, c.n_vec = n_vec, c.stride = stride, c.chunk_log = ctx->fr_mle_chunk_log;
+  c.layout = scalar_layout, c.order = order, c.step = step;
+  if (step) c.r = fr_read_record(scalar_layout, r32);
+  const uint32_t values = fr_sum_degree(c.terms) + 1;
+  const FrMleRoundPlan plan = fr_mle_round_plan(step ? n / 2 : n, values, c.chunk_log);
+  const size_t span = ((n_vec - 1) * stride + n) * 32;
+  d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = span;
+  d.out = out;
+  d.work[0] = {&s.work, plan.records * 32};
+  if (host && step) d.work[1] = {&s.out, span};
+  d.values_bytes = values * 32;
+  const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) -> int {
+    c.in = io.in[0], c.out = !step ? nullptr : host ? s.out.p : io.out, c.work = s.work.p;
+    launch_fr_sumcheck_terms(st, c);
+    if (host && step)
+      HIP_TRY(ctx, hipMemcpy2DAsync(out, stride * 32, s.out.p, stride * 32, n / 2 * 32, n_vec, hipMemcpyDeviceToHost, st));
+    io.values = (const uint8_t*)s.work.p + plan.values_off * 32;
+    return MSM_AMD_OK;
+  });
+  if (rc == MSM_AMD_OK) fr_values_out(s, scalar_layout, values, g_out);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -979,6 +1025,18 @@ int msm_amd_fr_sumcheck_round(msm_amd_ctx* ctx, int scalar_layout, int order, in
 int msm_amd_fr_sumcheck_round_device(msm_amd_ctx* ctx, int scalar_layout, int order, int form, const void* d_in, size_t n,
                                      size_t n_vec, size_t stride, void* g_out, float* kernel_ms) {
   return fr_sumcheck_round_call(ctx, false, scalar_layout, order, form, d_in, n, n_vec, stride, g_out, kernel_ms);
+}
+
+int msm_amd_fr_sumcheck_round_terms(msm_amd_ctx* ctx, int mem, int scalar_layout, int order,
+                                    const msm_amd_fr_sumcheck_terms* terms, const void* in, size_t n, size_t n_vec,
+                                    size_t stride, void* g_out, float* kernel_ms) {
+  return fr_sumcheck_terms_call(ctx, mem, false, scalar_layout, order, terms, nullptr, in, n, n_vec, stride, nullptr, g_out, kernel_ms);
+}
+
+int msm_amd_fr_sumcheck_step_terms(msm_amd_ctx* ctx, int mem, int scalar_layout, int order,
+                                   const msm_amd_fr_sumcheck_terms* terms, const void* r, const void* in, size_t n, size_t n_vec,
+                                   size_t stride, void* out, void* g_out, float* kernel_ms) {
+  return fr_sumcheck_terms_call(ctx, mem, true, scalar_layout, order, terms, r, in, n, n_vec, stride, out, g_out, kernel_ms);
 }
 
 }  // extern "C"

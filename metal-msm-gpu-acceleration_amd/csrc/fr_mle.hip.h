@@ -83,6 +83,113 @@ struct FrMleSums {
   }
 };
 
+// ---- a round over a caller's sum of products (msm_amd_fr_sumcheck_round_terms*, msm_amd_fr_sumcheck_step_terms*) ---------
+// F = [f_outer] sum_k c_k prod_j f_(idx[k][j]).  The image of a checked term list is plain data and travels by value (664
+// bytes): reduced Montgomery coefficients, and the lengths, the kinds and the table indices as bytes packed into words, so
+// that a kernel reads them with scalar loads at wave-uniform offsets.
+constexpr uint32_t kFrSumMaxTables = 16, kFrSumMaxTerms = 16, kFrSumMaxFactors = 6;
+constexpr uint32_t kFrSumMaxValues = kFrSumMaxFactors + 2;   // d + 1 with an outer factor
+constexpr uint32_t kFrSumNoOuter = 0xFFFFFFFFu;
+constexpr uint32_t kFrCoeffAny = 0, kFrCoeffOne = 1, kFrCoeffMinusOne = 2;   // 1 and r - 1 cost no product
+struct FrSumTerms {
+  u256 coeff[kFrSumMaxTerms];
+  uint32_t n_terms, outer;
+  uint32_t len[kFrSumMaxTerms / 4], kind[kFrSumMaxTerms / 4];
+  uint32_t idx[kFrSumMaxTerms * kFrSumMaxFactors / 4];
+};
+MSM_HD uint32_t fr_sum_byte(const uint32_t* words, uint32_t i) { return (words[i >> 2] >> ((i & 3u) * 8u)) & 0xFFu; }
+inline void fr_sum_set_byte(uint32_t* words, uint32_t i, uint32_t b) { words[i >> 2] |= b << ((i & 3u) * 8u); }
+// the degree d of the round's polynomial
+inline uint32_t fr_sum_degree(const FrSumTerms& s) {
+  uint32_t longest = 0;
+  for (uint32_t k = 0; k < s.n_terms; ++k) longest = fr_sum_byte(s.len, k) > longest ? fr_sum_byte(s.len, k) : longest;
+  return longest + (s.outer != kFrSumNoOuter ? 1u : 0u);
+}
+// The V = d + 1 running sums of such a round.  Terms outermost, so that a pair of a table is loaded once per use: the first
+// factor of a term gives p[t] = c_k f(t) (the coefficient goes into f and its difference: two products, none for 1 and
+// r - 1, which is subtracted), every further factor multiplies p[t] by its f(t), every operand advancing from t to t + 1 by
+// its difference; acc[t] collects the terms of the pair and meets the outer factor once per t.  Live across a factor: the V
+// sums, acc and p.  Beyond four values that does not fit 256 registers, so the values are taken in passes of W (3, or 2 of 8) at a time
+// (fr_sum_pass): a pass walks the terms for t = T0 .. T0 + W - 1, its operands starting at f(T0) = lo + T0 diff (additions).
+// The loops over terms and factors are runtime loops with the same trip counts in every lane; the t loops are unrolled and
+// no array is indexed at run time.  load(table, lo, hi) brings the two records of a pair.  Field arithmetic is exact: any
+// order gives these bytes.
+MSM_HD constexpr int fr_sum_pass(int values) { return values <= 4 ? values : values <= 7 ? 3 : 2; }
+template <int V>
+struct FrTermSums {
+  static constexpr int kPass = fr_sum_pass(V);
+  u256 g[V];
+  MSM_HD void clear() {
+    MSM_UNROLL for (int t = 0; t < V; ++t) g[t] = u256_zero();
+  }
+  // f(T0) and the difference of one operand
+  template <int T0>
+  static MSM_HD void operand(const u256& lo, const u256& hi, u256& f, u256& diff) {
+    f = lo, diff = Fr::sub(hi, lo);
+    MSM_UNROLL for (int t = 0; t < T0; ++t) f = Fr::add(f, diff);
+  }
+  template <int T0, int W, class Load>
+  MSM_HD void pass(const FrSumTerms& s, Load&& load) {
+    u256 acc[W], lo, hi, f, diff;
+    MSM_UNROLL for (int t = 0; t < W; ++t) acc[t] = u256_zero();
+    uint32_t at = 0;
+    NTT_NO_UNROLL for (uint32_t k = 0; k < s.n_terms; ++k) {
+      const uint32_t len = fr_sum_byte(s.len, k), kind = fr_sum_byte(s.kind, k);
+      u256 p[W];
+      load(fr_sum_byte(s.idx, at), lo, hi);
+      operand<T0>(lo, hi, f, diff);
+      if (kind == kFrCoeffAny) f = Fr::mul(s.coeff[k], f), diff = Fr::mul(s.coeff[k], diff);
+      MSM_UNROLL for (int t = 0; t < W; ++t) {
+        if (t > 0) f = Fr::add(f, diff);
+        p[t] = f;
+      }
+      NTT_NO_UNROLL for (uint32_t j = 1; j < len; ++j) {
+        load(fr_sum_byte(s.idx, at + j), lo, hi);
+        operand<T0>(lo, hi, f, diff);
+        MSM_UNROLL for (int t = 0; t < W; ++t) {
+          if (t > 0) f = Fr::add(f, diff);
+          p[t] = Fr::mul(p[t], f);
+        }
+      }
+      if (kind == kFrCoeffMinusOne) {
+        MSM_UNROLL for (int t = 0; t < W; ++t) acc[t] = Fr::sub(acc[t], p[t]);
+      } else {
+        MSM_UNROLL for (int t = 0; t < W; ++t) acc[t] = Fr::add(acc[t], p[t]);
+      }
+      at += len;
+    }
+    if (s.outer != kFrSumNoOuter) {
+      load(s.outer, lo, hi);
+      operand<T0>(lo, hi, f, diff);
+      MSM_UNROLL for (int t = 0; t < W; ++t) {
+        if (t > 0) f = Fr::add(f, diff);
+        g[T0 + t] = Fr::add(g[T0 + t], Fr::mul(f, acc[t]));
+      }
+    } else {
+      MSM_UNROLL for (int t = 0; t < W; ++t) g[T0 + t] = Fr::add(g[T0 + t], acc[t]);
+    }
+  }
+  template <int T0, class Load>
+  MSM_HD void passes_from(const FrSumTerms& s, Load&& load) {
+    if constexpr (T0 < V) {
+      pass<T0, (V - T0 < kPass ? V - T0 : kPass)>(s, load);
+      passes_from<T0 + kPass>(s, load);
+    }
+  }
+  template <class Load>
+  MSM_HD void add_pair(const FrSumTerms& s, Load&& load) { passes_from<0>(s, load); }
+};
+
+// products per pair of that order: (len_k - 1) V per term, V for the outer factor, and per pass two for every coefficient
+// that is neither 1 nor r - 1
+inline uint64_t fr_sum_products(const FrSumTerms& s) {
+  const uint64_t values = fr_sum_degree(s) + 1, pass = fr_sum_pass((int)values), passes = (values + pass - 1) / pass;
+  uint64_t c = s.outer != kFrSumNoOuter ? values : 0;
+  for (uint32_t k = 0; k < s.n_terms; ++k)
+    c += (fr_sum_byte(s.len, k) - 1) * values + (fr_sum_byte(s.kind, k) == kFrCoeffAny ? 2u * passes : 0u);
+  return c;
+}
+
 // ---- plans: pure functions of the sizes ----------------------------------------------------------------------------------
 struct FrMleRoundPlan {
   uint32_t values;                          // d + 1

@@ -4,7 +4,8 @@
 // the polynomial calls likewise (a range's Horner value, then the ranges from the sums behind them), the sparse product
 // row by row over ranges of equal entry count, the multilinear calls step by step over ranges of outputs (a round: the sums
 // of every range of pairs, added in range order), the Poseidon calls permutation by permutation over ranges, a tree level by
-// level (and the constants of the paper's Grain generator, msm_amd_poseidon_constants);
+// level, a round over a term list as the sums of every range of pairs in range order and its step as the bind followed by
+// that round (and the constants of the paper's Grain generator, msm_amd_poseidon_constants);
 // and the argument checks the twins share with the host driver (msm_host.hip).  The bytes of a result are unique, so the
 // way a twin cuts the work shows nowhere.
 #include <hip/hip_runtime.h>
@@ -196,6 +197,76 @@ const char* fr_sumcheck_check(int scalar_layout, int order, int form, const void
   if (const char* why = fr_mle_tables_check(n, n_vec, stride)) return why;
   if (!in || !g_out) return "null pointer with work to do";
   if (device && ((uintptr_t)in & 15u)) return kMleAlign;
+  return nullptr;
+}
+
+static_assert(kFrSumMaxTables == MSM_AMD_SUMCHECK_MAX_TABLES && kFrSumMaxTerms == MSM_AMD_SUMCHECK_MAX_TERMS &&
+              kFrSumMaxFactors == MSM_AMD_SUMCHECK_MAX_FACTORS && kFrSumNoOuter == MSM_AMD_SUMCHECK_NO_OUTER, "term lists");
+
+const char* fr_sumcheck_terms_check(int scalar_layout, const ::msm_amd_fr_sumcheck_terms* terms, uint64_t n_vec,
+                                    FrSumTerms* image) {
+  if (!terms) return "null term list";
+  if (n_vec < 1 || n_vec > kFrSumMaxTables) return "n_vec must be 1 .. 16 for a term list";
+  if (terms->n_terms < 1 || terms->n_terms > kFrSumMaxTerms) return "n_terms must be 1 .. 16";
+  if (!terms->coeff || !terms->term_len || !terms->factors) return "null pointer in the term list";
+  if (terms->outer != kFrSumNoOuter && terms->outer >= n_vec)
+    return "outer must be a table index below n_vec or MSM_AMD_SUMCHECK_NO_OUTER";
+  uint32_t at = 0;
+  for (uint32_t k = 0; k < terms->n_terms; ++k) {
+    const uint32_t len = terms->term_len[k];
+    if (len < 1 || len > kFrSumMaxFactors) return "a term length must be 1 .. 6";
+    for (uint32_t j = 0; j < len; ++j)
+      if (terms->factors[at + j] >= n_vec) return "a table index of a term is not below n_vec";
+    at += len;
+  }
+  if (!image) return nullptr;
+  *image = FrSumTerms{};
+  image->n_terms = terms->n_terms, image->outer = terms->outer;
+  const u256 one = Fr::one(), minus_one = Fr::sub(u256_zero(), one);
+  auto same = [](const u256& a, const u256& b) {
+    for (int i = 0; i < 8; ++i)
+      if (a.v[i] != b.v[i]) return false;
+    return true;
+  };
+  at = 0;
+  for (uint32_t k = 0; k < terms->n_terms; ++k) {
+    const u256 c = fr_read_record(scalar_layout, (const uint8_t*)terms->coeff + (size_t)k * 32);
+    image->coeff[k] = c;
+    fr_sum_set_byte(image->kind, k, same(c, one) ? kFrCoeffOne : same(c, minus_one) ? kFrCoeffMinusOne : kFrCoeffAny);
+    fr_sum_set_byte(image->len, k, terms->term_len[k]);
+    for (uint32_t j = 0; j < terms->term_len[k]; ++j) fr_sum_set_byte(image->idx, at + j, terms->factors[at + j]);
+    at += terms->term_len[k];
+  }
+  return nullptr;
+}
+
+const char* fr_sumcheck_terms_round_check(int scalar_layout, int order, const ::msm_amd_fr_sumcheck_terms* terms, const void* in,
+                                          uint64_t n, uint64_t n_vec, uint64_t stride, const void* g_out, bool device,
+                                          FrSumTerms* image) {
+  if (!fr_layout_known(scalar_layout)) return kMleLayout;
+  if (!fr_mle_order_known(order)) return kMleOrder;
+  if (n_vec == 0) return nullptr;
+  if (const char* why = fr_sumcheck_terms_check(scalar_layout, terms, n_vec, image)) return why;
+  if (const char* why = fr_mle_tables_check(n, n_vec, stride)) return why;
+  if (!in || !g_out) return "null pointer with work to do";
+  if (device && ((uintptr_t)in & 15u)) return kMleAlign;
+  return nullptr;
+}
+
+const char* fr_sumcheck_step_check(int scalar_layout, int order, const ::msm_amd_fr_sumcheck_terms* terms, const void* r,
+                                   const void* in, uint64_t n, uint64_t n_vec, uint64_t stride, const void* out,
+                                   const void* g_out, bool device, FrSumTerms* image) {
+  if (!fr_layout_known(scalar_layout)) return kMleLayout;
+  if (!fr_mle_order_known(order)) return kMleOrder;
+  if (n_vec == 0) return nullptr;
+  if (const char* why = fr_sumcheck_terms_check(scalar_layout, terms, n_vec, image)) return why;
+  if (const char* why = fr_mle_tables_check(n, n_vec, stride)) return why;
+  if (n < 4) return "n must be at least 4: the last variable is msm_amd_fr_mle_bind or msm_amd_fr_mle_eval";
+  if (!r || !in || !out || !g_out) return "null pointer with work to do";
+  if (device && (((uintptr_t)in | (uintptr_t)out) & 15u)) return kMleAlign;
+  if (out == in) return order == kFrMleHigh ? nullptr : "MSM_AMD_MLE_LOW is out of place only";
+  if (!spans_apart(in, ((n_vec - 1) * stride + n) * 32, out, ((n_vec - 1) * stride + n / 2) * 32))
+    return "the output must be the input itself (MSM_AMD_MLE_HIGH) or disjoint from all of it";
   return nullptr;
 }
 
@@ -614,6 +685,70 @@ int host_fr_sumcheck_round(int layout, int order, int form, const void* in_v, si
   return MSM_AMD_OK;
 }
 
+// the same body over ranges of pairs, the sums of the ranges added in range order
+template <int V>
+void host_terms_values(const FrSumTerms& terms, int layout, int order, const uint8_t* in, uint64_t n, uint64_t stride, int threads,
+                       u256* g) {
+  const uint64_t h = n / 2;
+  const unsigned T = mle_workers(threads, h);
+  std::vector<FrTermSums<V>> part(T);
+  for_ranges(T, h, [&](unsigned t, size_t a, size_t b) {
+    FrTermSums<V> s;
+    s.clear();
+    for (size_t x = a; x < b; ++x)
+      s.add_pair(terms, [&](uint32_t v, u256& lo, u256& hi) {
+        lo = host_get(layout, in + (size_t)v * stride * 32, order == kFrMleHigh ? x : 2 * x);
+        hi = host_get(layout, in + (size_t)v * stride * 32, order == kFrMleHigh ? x + h : 2 * x + 1);
+      });
+    part[t] = s;
+  });
+  for (int v = 0; v < V; ++v) {
+    g[v] = u256_zero();
+    for (unsigned t = 0; t < T; ++t) g[v] = Fr::add(g[v], part[t].g[v]);
+  }
+}
+
+void host_terms_round(const FrSumTerms& terms, int layout, int order, const uint8_t* in, uint64_t n, uint64_t stride, int threads,
+                      void* g_out) {
+  u256 g[kFrSumMaxValues];
+  const uint32_t d = fr_sum_degree(terms);
+  switch (d) {
+    case 1: host_terms_values<2>(terms, layout, order, in, n, stride, threads, g); break;
+    case 2: host_terms_values<3>(terms, layout, order, in, n, stride, threads, g); break;
+    case 3: host_terms_values<4>(terms, layout, order, in, n, stride, threads, g); break;
+    case 4: host_terms_values<5>(terms, layout, order, in, n, stride, threads, g); break;
+    case 5: host_terms_values<6>(terms, layout, order, in, n, stride, threads, g); break;
+    case 6: host_terms_values<7>(terms, layout, order, in, n, stride, threads, g); break;
+    default: host_terms_values<8>(terms, layout, order, in, n, stride, threads, g); break;
+  }
+  for (uint32_t t = 0; t <= d; ++t) host_put(layout, (uint8_t*)g_out, t, g[t]);
+}
+
+int host_fr_sumcheck_round_terms(int layout, int order, const ::msm_amd_fr_sumcheck_terms* terms, const void* in_v, size_t n,
+                                 size_t n_vec, size_t stride, int threads, void* g_out) {
+  FrSumTerms image;
+  if (fr_sumcheck_terms_round_check(layout, order, terms, in_v, n, n_vec, stride, g_out, false, &image)) return MSM_AMD_INPUT_ERROR;
+  if (n_vec == 0) return MSM_AMD_OK;
+  host_terms_round(image, layout, order, (const uint8_t*)in_v, n, stride, threads, g_out);
+  return MSM_AMD_OK;
+}
+
+// bind, then the round over what the bind wrote: the definition of the step
+int host_fr_sumcheck_step_terms(int layout, int order, const ::msm_amd_fr_sumcheck_terms* terms, const void* r32, const void* in_v,
+                                size_t n, size_t n_vec, size_t stride, int threads, void* out_v, void* g_out) {
+  FrSumTerms image;
+  if (fr_sumcheck_step_check(layout, order, terms, r32, in_v, n, n_vec, stride, out_v, g_out, false, &image))
+    return MSM_AMD_INPUT_ERROR;
+  if (n_vec == 0) return MSM_AMD_OK;
+  const u256 r = fr_read_record(layout, r32);
+  for (size_t v = 0; v < n_vec; ++v) {
+    const std::vector<u256> left = host_mle_fold(layout, order, &r, 1, (const uint8_t*)in_v + v * stride * 32, n, threads);
+    for (size_t i = 0; i < left.size(); ++i) host_put(layout, (uint8_t*)out_v + v * stride * 32, i, left[i]);
+  }
+  host_terms_round(image, layout, order, (const uint8_t*)out_v, n / 2, stride, threads, g_out);
+  return MSM_AMD_OK;
+}
+
 }  // namespace
 }  // namespace msm_amd
 
@@ -669,6 +804,39 @@ int msm_amd_test_fr_mle_plan(int call, int order, int form, size_t n, size_t n_v
     }
   }
   c[3] = c[2] * 32;
+  std::memcpy(counts, c, sizeof c);
+  return MSM_AMD_OK;
+}
+
+int msm_amd_fr_sumcheck_terms_degree(const msm_amd_fr_sumcheck_terms* terms, size_t n_vec, uint32_t* d) {
+  using namespace msm_amd;
+  if (!d || fr_sumcheck_terms_check(MSM_AMD_SCALAR_MONT_LE, terms, n_vec, nullptr)) return MSM_AMD_INPUT_ERROR;
+  uint32_t longest = 0;
+  for (uint32_t k = 0; k < terms->n_terms; ++k) longest = terms->term_len[k] > longest ? terms->term_len[k] : longest;
+  *d = longest + (terms->outer != kFrSumNoOuter ? 1u : 0u);
+  return MSM_AMD_OK;
+}
+
+int msm_amd_host_fr_sumcheck_round_terms(int scalar_layout, int order, const msm_amd_fr_sumcheck_terms* terms, const void* in,
+                                         size_t n, size_t n_vec, size_t stride, int threads, void* g_out) {
+  return msm_amd::host_fr_sumcheck_round_terms(scalar_layout, order, terms, in, n, n_vec, stride, threads, g_out);
+}
+
+int msm_amd_host_fr_sumcheck_step_terms(int scalar_layout, int order, const msm_amd_fr_sumcheck_terms* terms, const void* r,
+                                        const void* in, size_t n, size_t n_vec, size_t stride, int threads, void* out,
+                                        void* g_out) {
+  return msm_amd::host_fr_sumcheck_step_terms(scalar_layout, order, terms, r, in, n, n_vec, stride, threads, out, g_out);
+}
+
+int msm_amd_test_fr_sumcheck_terms_plan(const msm_amd_fr_sumcheck_terms* terms, size_t n, size_t n_vec, uint32_t chunk_log,
+                                        int step, uint64_t counts[8]) {
+  using namespace msm_amd;
+  uint32_t d = 0;
+  if (!counts || chunk_log < kFrMleMinChunkLog || chunk_log > kFrMleMaxChunkLog ||
+      msm_amd_fr_sumcheck_terms_degree(terms, n_vec, &d) != MSM_AMD_OK || fr_mle_tables_check(n, n_vec, n) || (step && n < 4))
+    return MSM_AMD_INPUT_ERROR;
+  const FrMleRoundPlan p = fr_mle_round_plan(step ? n / 2 : n, d + 1, chunk_log);
+  const uint64_t c[8] = {p.launches, p.waves, p.records, p.records * 32, p.levels, p.count[0], p.values, 0};
   std::memcpy(counts, c, sizeof c);
   return MSM_AMD_OK;
 }

@@ -35,6 +35,8 @@
 //                          the chunk (HIGH: both records at unit stride across the wave; LOW: the two records of a pair are 64
 //                          contiguous bytes), d + 1 sums per lane in registers, six xor-shuffle additions each, lane 0 stores
 //                          d + 1 raw partial records.
+//   fr_sumcheck_terms_kernel<D>  the same wave per chunk over a caller's sum of products of degree D (FrTermSums): the terms
+//                          and their factors in runtime loops of wave-uniform trip counts, a pair loaded per use.
 //   fr_mle_fold_kernel     one wave per 2^10 partials of one t: their sum, the same fold.
 //   fr_mle_eval_kernel<P>  one wave per tile of 2^c records: lane l folds the records l, l + 64, ... (a tree in registers
 //                          over the tile's upper variables), six xor-shuffle steps fold the variables of the lane index,
@@ -495,6 +497,37 @@ __global__ void __launch_bounds__(kFrWave, 2) fr_sumcheck_round_kernel(FrMleRoun
   }
 }
 
+// A round over a term list (fr_mle.hip.h, FrTermSums<D + 1>): the geometry and the partial planes of the kernel above
+struct FrTermRoundArgs {
+  const uint32_t* in;
+  uint32_t* partial;         // plane t: waves raw records
+  uint64_t stride, h, waves;
+  uint32_t chunk_log;
+  int layout, order;
+  FrSumTerms terms;
+};
+
+template <int D>
+__global__ void __launch_bounds__(kFrWave, 2) fr_sumcheck_terms_kernel(FrTermRoundArgs a) {
+  const uint32_t lane = threadIdx.x;
+  const uint64_t first = (uint64_t)blockIdx.x << a.chunk_log;
+  const uint32_t cnt = 1u << a.chunk_log;
+  FrTermSums<D + 1> s;
+  s.clear();
+  NTT_NO_UNROLL for (uint32_t m = lane; m < cnt; m += kFrWave) {
+    const uint64_t x = first + m;
+    const uint64_t i_lo = a.order == kFrMleHigh ? x : 2 * x, i_hi = a.order == kFrMleHigh ? x + a.h : 2 * x + 1;
+    s.add_pair(a.terms, [&](uint32_t v, u256& lo, u256& hi) {
+      lo = fr_load(a.layout, load_rec(a.in + ((uint64_t)v * a.stride + i_lo) * 8));
+      hi = fr_load(a.layout, load_rec(a.in + ((uint64_t)v * a.stride + i_hi) * 8));
+    });
+  }
+  MSM_UNROLL for (int t = 0; t <= D; ++t) {
+    const u256 sum = wave_sum(s.g[t]);
+    if (lane == 0) store_rec(a.partial + ((uint64_t)t * a.waves + blockIdx.x) * 8, sum);
+  }
+}
+
 __global__ void __launch_bounds__(kFrWave) fr_mle_fold_kernel(FrMleFoldArgs a) {
   const uint32_t lane = threadIdx.x;
   const uint64_t t = blockIdx.x / a.groups, g = blockIdx.x - t * a.groups;
@@ -798,6 +831,46 @@ uint32_t launch_fr_sumcheck_round(hipStream_t st, const FrMleRoundLaunch& c) {
     hipLaunchKernelGGL(fr_mle_fold_kernel, dim3((uint32_t)(f.groups * plan.values)), dim3(kFrWave), 0, st, f);
   }
   return plan.launches;
+}
+
+template <int D>
+void launch_terms_degree(hipStream_t st, const FrTermRoundArgs& a) {
+  hipLaunchKernelGGL((fr_sumcheck_terms_kernel<D>), dim3((uint32_t)a.waves), dim3(kFrWave), 0, st, a);
+}
+
+uint32_t launch_fr_sumcheck_terms(hipStream_t st, const FrTermRoundLaunch& c) {
+  const uint32_t d = fr_sum_degree(c.terms);
+  const uint64_t n = c.step ? c.n / 2 : c.n;   // the tables the sums run over
+  const FrMleRoundPlan plan = fr_mle_round_plan(n, d + 1, c.chunk_log);
+  uint32_t* work = (uint32_t*)c.work;
+  uint32_t launches = plan.launches;
+  FrTermRoundArgs a{};
+  a.in = (const uint32_t*)c.in, a.partial = work + plan.offset[0] * 8;
+  a.stride = c.stride, a.h = n / 2, a.waves = plan.count[0], a.chunk_log = plan.chunk_log;
+  a.layout = c.layout, a.order = c.order, a.terms = c.terms;
+  if (c.step) {   // the bind launch in front, on the same stream: the round reads what it wrote
+    FrMleBindLaunch b{};
+    b.in = c.in, b.out = c.out, b.work = nullptr, b.n = c.n, b.n_vec = c.n_vec, b.stride = c.stride, b.n_bind = 1;
+    b.layout = c.layout, b.order = c.order, b.r[0] = c.r;
+    launches += launch_fr_mle_bind(st, b);
+    a.in = (const uint32_t*)c.out;
+  }
+  switch (d) {
+    case 1: launch_terms_degree<1>(st, a); break;
+    case 2: launch_terms_degree<2>(st, a); break;
+    case 3: launch_terms_degree<3>(st, a); break;
+    case 4: launch_terms_degree<4>(st, a); break;
+    case 5: launch_terms_degree<5>(st, a); break;
+    case 6: launch_terms_degree<6>(st, a); break;
+    default: launch_terms_degree<7>(st, a); break;
+  }
+  for (uint32_t k = 1; k < plan.levels; ++k) {
+    FrMleFoldArgs f{};
+    f.src = work + plan.offset[k - 1] * 8, f.dst = work + plan.offset[k] * 8;
+    f.count = plan.count[k - 1], f.groups = plan.count[k];
+    hipLaunchKernelGGL(fr_mle_fold_kernel, dim3((uint32_t)(f.groups * plan.values)), dim3(kFrWave), 0, st, f);
+  }
+  return launches;
 }
 
 uint32_t launch_fr_mle_eval(hipStream_t st, const FrMleEvalLaunch& c) {

@@ -13,6 +13,8 @@
 #include "fr_sort.hip.h"
 #include "fr_vec.hip.h"
 
+struct msm_amd_fr_sumcheck_terms;   // include/msm_amd.h
+
 namespace msm_amd {
 
 // out[i] = op(k, a[i], b[i], c[i]), i < n; k Montgomery and reduced; operands the op does not read may be null
@@ -99,6 +101,19 @@ struct FrMleRoundLaunch {
   int layout, order, form;
 };
 uint32_t launch_fr_sumcheck_round(hipStream_t st, const FrMleRoundLaunch& c);
+// A round over a term list; step: a bind launch of every table at r into `out` first, the sums over the n / 2 records left
+struct FrTermRoundLaunch {
+  const void* in;      // n_vec tables of n records
+  void* out;           // step: the bound tables (HIGH: may be in)
+  void* work;          // fr_mle_round_plan(step ? n / 2 : n, d + 1, chunk_log).records raw records
+  uint64_t n, n_vec, stride;
+  uint32_t chunk_log;
+  int layout, order;
+  bool step;
+  u256 r;
+  FrSumTerms terms;
+};
+uint32_t launch_fr_sumcheck_terms(hipStream_t st, const FrTermRoundLaunch& c);
 struct FrMleEvalLaunch {
   const void* in;
   void* work;          // fr_scan_plan(n, n_vec, tile_log).records + n_vec raw records; the n_vec values behind the levels
@@ -250,6 +265,17 @@ const char* fr_mle_eval_check(int scalar_layout, int order, const void* point, c
 const char* fr_eq_table_check(int scalar_layout, int order, const void* point, uint64_t m, const void* out, bool device);
 const char* fr_sumcheck_check(int scalar_layout, int order, int form, const void* in, uint64_t n, uint64_t n_vec,
                               uint64_t stride, const void* g_out, bool device);
+// The term list of msm_amd_fr_sumcheck_round_terms* / _step_terms*: its sizes, pointers and indices (no ctx); on success
+// and with `image` given, the image the kernels and the twins run on.  fr_sumcheck_terms_round_check and
+// fr_sumcheck_step_check are the whole checks of the two calls; n_vec == 0 passes them before the list is looked at.
+const char* fr_sumcheck_terms_check(int scalar_layout, const ::msm_amd_fr_sumcheck_terms* terms, uint64_t n_vec,
+                                    FrSumTerms* image);
+const char* fr_sumcheck_terms_round_check(int scalar_layout, int order, const ::msm_amd_fr_sumcheck_terms* terms, const void* in,
+                                          uint64_t n, uint64_t n_vec, uint64_t stride, const void* g_out, bool device,
+                                          FrSumTerms* image);
+const char* fr_sumcheck_step_check(int scalar_layout, int order, const ::msm_amd_fr_sumcheck_terms* terms, const void* r,
+                                   const void* in, uint64_t n, uint64_t n_vec, uint64_t stride, const void* out,
+                                   const void* g_out, bool device, FrSumTerms* image);
 // The Poseidon calls.  The shape (t, r_f, r_p) is that of a parameter handle or of the twin's arguments; every check first
 // looks at the layout, then at the sizes, lets n == 0 pass where a call has one, then at pointers, alignment and overlap.
 const char* poseidon_shape_check(uint64_t t, uint64_t r_f, uint64_t r_p);
