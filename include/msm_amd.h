@@ -1166,6 +1166,44 @@ int msm_amd_fr_lincomb_device(msm_amd_ctx* ctx, int scalar_layout, const void* k
                               size_t n_vec, void* d_out, float* kernel_ms);
 int msm_amd_host_fr_lincomb(int scalar_layout, const void* k32, const void* a, size_t n, size_t n_vec, int threads, void* out);
 
+/* Several points in one pass: the multi-point opening at the end of a halo2 / PLONK proof -- every column at all of its
+ * rotations (z, w z, w^-1 z, ..), and SHPLONK's division of a rotation set's folded polynomial by the set's vanishing
+ * polynomial Z_S(X) = prod_j (X - z_j), which upstream does as div_by_vanishing: k chained kate_divisions.  z is k records
+ * in HOST memory, 1 <= k <= MSM_AMD_POLY_MAX_POINTS, in scalar_layout, any 256-bit word taken mod r.  mem
+ * (MSM_AMD_MEM_HOST / MSM_AMD_MEM_DEVICE, below) says where coeffs / in / out lie, as for msm_amd_fr_sort; y_out / vals_out
+ * are HOST memory either way and come back through ctx-owned page-locked memory in the call's one bounded wait.  Records,
+ * layouts, alignment of device pointers, n n_vec < 2^32 with any n >= 1, the empty calls and msm_amd_last_error are
+ * those of msm_amd_fr_poly_*.  The launches are those of ONE point whatever k is (levels for the evaluation, 2 levels - 1
+ * for the division): level 0 reads every tile once and carries k scans through it, the upper levels hold k copies of the
+ * single-point totals (ctx-owned memory of about k n n_vec / 2^9 records plus k n_vec).  The division uses
+ *     q_i = sum_j w_j s^(j)_(i+1),   w_j = 1 / prod_(m != j) (z_j - z_m),   s^(j)_i = sum_(t >= i) c_t z_j^(t - i);
+ * the host inverts once per call for the k weights.  DESIGN.md section 8.18.
+ * MSM_AMD_INPUT_ERROR, with the reason in msm_amd_last_error and no byte of out, y_out or vals_out written: k == 0 or
+ * k > MSM_AMD_POLY_MAX_POINTS, an unknown mem or layout, a null z, a null required pointer with work to do, a partial
+ * overlap of out and in and, for the division only, two points that are equal mod r (the raw words 1 and r + 1, say): the
+ * message names both indices.  k == 1 gives the bytes of msm_amd_fr_poly_eval* / msm_amd_fr_poly_div_linear*. */
+enum { MSM_AMD_POLY_MAX_POINTS = 8 };
+/* y[v k + j] = p_v(z_j): n_vec k HOST records, fully reduced.  Points may repeat. */
+int msm_amd_fr_poly_eval_points(msm_amd_ctx* ctx, int mem, int scalar_layout, const void* z /* k HOST records */, size_t k,
+                                const void* coeffs, size_t n, size_t n_vec, void* y_out /* HOST memory */, float* kernel_ms);
+/* out = the floor quotient p_v div prod_j (X - z_j), n records per polynomial of which the top min(k, n) are zero -- the
+ * coefficients of upstream's div_by_vanishing(p_v, [z_0 .. z_(k-1)]), the same whether or not the caller subtracted the
+ * remainder r(X) first; n < k is a valid call and leaves zeros.  In place (out == in) or disjoint: an out-of-place call
+ * leaves `in` unchanged.  vals_out (optional): vals[v k + j] = p_v(z_j), the remainder in evaluation form. */
+int msm_amd_fr_poly_div_points(msm_amd_ctx* ctx, int mem, int scalar_layout, const void* z /* k HOST records */, size_t k,
+                               const void* in, size_t n, size_t n_vec, void* out, void* vals_out /* HOST memory, optional */,
+                               float* kernel_ms);
+/* The twins: the division is upstream's shape, k chained divisions by X - z_j, and the values come from k evaluations -- a
+ * different algorithm from the device's partial fractions.  The bytes do not depend on `threads`. */
+int msm_amd_host_fr_poly_eval_points(int scalar_layout, const void* z, size_t k, const void* coeffs, size_t n, size_t n_vec,
+                                     int threads, void* y_out);
+int msm_amd_host_fr_poly_div_points(int scalar_layout, const void* z, size_t k, const void* in, size_t n, size_t n_vec,
+                                    int threads, void* out, void* vals_out);
+/* Test aid (no ctx, CPU only): the plan of a call at k points and a tile of 2^tile_log (2 .. 9).  counts: [0] launches (those
+ * of one point), [1] waves over all launches, [2] records and [3] bytes of ctx-owned device memory, [4] levels, [5] bytes
+ * of the kernel arguments of a level-0 launch (< 4096), [6] waves of the level-0 launches, [7] 0. */
+int msm_amd_test_fr_poly_points_plan(size_t n, size_t n_vec, size_t k, uint32_t tile_log, int divide, uint64_t counts[8]);
+
 /* ---- sparse matrix times vector over Fr: the R1CS witness map ------------------------------------------------
  * Every R1CS prover starts from A z, B z, C z: three sparse matrices over Fr, fixed per circuit, times the assignment of
  * one proof (arkworks witness_map_from_matrices; the same step in snarkjs and bellman; Marlin and Spartan-style provers

@@ -170,6 +170,8 @@ EXPORTS = [
     "msm_amd_fr_sort", "msm_amd_host_fr_sort", "msm_amd_test_fr_sort_plan",
     "msm_amd_fr_lookup_build_sorted", "msm_amd_fr_lookup_sorted", "msm_amd_test_fr_lookup_image",
     "msm_amd_fr_lookup_permute_as", "msm_amd_host_fr_lookup_permute_as",
+    "msm_amd_fr_poly_eval_points", "msm_amd_fr_poly_div_points", "msm_amd_host_fr_poly_eval_points",
+    "msm_amd_host_fr_poly_div_points", "msm_amd_test_fr_poly_points_plan",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -471,6 +473,15 @@ def _lib():
                                                         c_void_p, POINTER(c_float)]
         L.msm_amd_host_fr_poly_div_linear.argtypes = [c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_int, c_void_p,
                                                       c_void_p]
+        L.msm_amd_fr_poly_eval_points.argtypes = [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t,
+                                                  c_void_p, POINTER(c_float)]
+        L.msm_amd_fr_poly_div_points.argtypes = [c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t,
+                                                 c_void_p, c_void_p, POINTER(c_float)]
+        L.msm_amd_host_fr_poly_eval_points.argtypes = [c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_int,
+                                                       c_void_p]
+        L.msm_amd_host_fr_poly_div_points.argtypes = [c_int, c_void_p, c_size_t, c_void_p, c_size_t, c_size_t, c_int,
+                                                      c_void_p, c_void_p]
+        L.msm_amd_test_fr_poly_points_plan.argtypes = [c_size_t, c_size_t, c_size_t, c_uint32, c_int, POINTER(c_uint64)]
         L.msm_amd_fr_lincomb.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]
         L.msm_amd_fr_lincomb_device.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p,
                                                 POINTER(c_float)]
@@ -1384,6 +1395,39 @@ class MsmConfig:
         self._check(_lib().msm_amd_fr_poly_div_linear_device(self.h, scalar_layout, z, c_void_p(d_in), n, n_vec,
                                                              c_void_p(d_out), r, ctypes.byref(ms)))
         return ((r.raw[:32 * n_vec] if n else b"") if rem else None), ms.value
+
+    def fr_poly_eval_points(self, coeffs, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1, mem=MEM_HOST, n=None):
+        """p_v(z_j) at the k = len(z) // 32 points of z in one pass (msm_amd_fr_poly_eval_points): returns (the n_vec k
+        records y[v k + j], kernel_ms).  MEM_HOST: coeffs is bytes; MEM_DEVICE: a device address, and n is required."""
+        k = len(z) // 32
+        if mem == MEM_HOST and n is None:
+            n = len(coeffs) // 32 // n_vec if n_vec else 0
+        ms = c_float(0)
+        y = ctypes.create_string_buffer(max(1, 32 * n_vec * k))
+        src = coeffs if mem == MEM_HOST else c_void_p(coeffs)
+        self._check(_lib().msm_amd_fr_poly_eval_points(self.h, mem, scalar_layout, z, k, src, n or 0, n_vec, y,
+                                                       ctypes.byref(ms)))
+        return (y.raw[:32 * n_vec * k] if n else b""), ms.value
+
+    def fr_poly_div_points(self, data, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1, mem=MEM_HOST, n=None, out=None,
+                           vals=True):
+        """The quotients of p_v by prod_j (X - z_j) over the k = len(z) // 32 distinct points of z, n records each, and the
+        values p_v(z_j) (msm_amd_fr_poly_div_points).  MEM_HOST: data is bytes, returns (quotients, values or None,
+        kernel_ms).  MEM_DEVICE: data and out are device addresses (out == data or disjoint), n is required, returns
+        (None, values or None, kernel_ms).  vals=False: vals_out is null."""
+        k = len(z) // 32
+        ms = c_float(0)
+        val = ctypes.create_string_buffer(max(1, 32 * n_vec * k)) if vals else None
+        if mem != MEM_HOST:
+            self._check(_lib().msm_amd_fr_poly_div_points(self.h, mem, scalar_layout, z, k, c_void_p(data), n or 0, n_vec,
+                                                          c_void_p(out), val, ctypes.byref(ms)))
+            return None, ((val.raw[:32 * n_vec * k] if n else b"") if vals else None), ms.value
+        if n is None:
+            n = len(data) // 32 // n_vec if n_vec else 0
+        o = ctypes.create_string_buffer(max(1, 32 * n * n_vec))
+        self._check(_lib().msm_amd_fr_poly_div_points(self.h, mem, scalar_layout, z, k, data, n, n_vec, o, val,
+                                                      ctypes.byref(ms)))
+        return o.raw[:32 * n * n_vec], ((val.raw[:32 * n_vec * k] if n else b"") if vals else None), ms.value
 
     def fr_lincomb(self, data: bytes, k: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1) -> bytes:
         """out[i] = sum_v k^v a[v n + i] of host records (msm_amd_fr_lincomb)"""
@@ -2388,6 +2432,40 @@ def host_fr_poly_div_linear(data: bytes, z: bytes, scalar_layout=SCALAR_MONT_LE,
     if st != OK:
         raise MsmError(st)
     return out.raw[:32 * n * n_vec], (rem.raw[:32 * n_vec] if n else b"")
+
+
+def host_fr_poly_eval_points(coeffs: bytes, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1, threads=0) -> bytes:
+    """Host twin of MsmConfig.fr_poly_eval_points (no GPU): the n_vec k records y[v k + j]."""
+    k = len(z) // 32
+    n = len(coeffs) // 32 // n_vec if n_vec else 0
+    y = ctypes.create_string_buffer(max(1, 32 * n_vec * k))
+    st = _lib().msm_amd_host_fr_poly_eval_points(scalar_layout, z, k, coeffs, n, n_vec, threads, y)
+    if st != OK:
+        raise MsmError(st)
+    return y.raw[:32 * n_vec * k] if n else b""
+
+
+def host_fr_poly_div_points(data: bytes, z: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1, threads=0):
+    """Host twin of MsmConfig.fr_poly_div_points (no GPU), k chained divisions: (quotients, values)."""
+    k = len(z) // 32
+    n = len(data) // 32 // n_vec if n_vec else 0
+    out = ctypes.create_string_buffer(max(1, len(data)))
+    val = ctypes.create_string_buffer(max(1, 32 * n_vec * k))
+    st = _lib().msm_amd_host_fr_poly_div_points(scalar_layout, z, k, data, n, n_vec, threads, out, val)
+    if st != OK:
+        raise MsmError(st)
+    return out.raw[:32 * n * n_vec], (val.raw[:32 * n_vec * k] if n else b"")
+
+
+def test_fr_poly_points_plan(n, n_vec=1, k=1, tile_log=9, divide=True) -> dict:
+    """The plan of a multi-point evaluation or division (msm_amd_test_fr_poly_points_plan): launches (those of one point),
+    waves over all launches, records and bytes of ctx-owned device memory, levels, bytes of the kernel arguments of a
+    level-0 launch, waves of the level-0 launches."""
+    out = (c_uint64 * 8)()
+    st = _lib().msm_amd_test_fr_poly_points_plan(n, n_vec, k, tile_log, 1 if divide else 0, out)
+    if st != OK:
+        raise MsmError(st)
+    return dict(zip(("launches", "waves", "records", "bytes", "levels", "arg_bytes", "level0_waves"), out))
 
 
 def host_fr_lincomb(data: bytes, k: bytes, scalar_layout=SCALAR_MONT_LE, n_vec=1, threads=0) -> bytes:

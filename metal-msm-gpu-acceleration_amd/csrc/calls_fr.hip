@@ -167,6 +167,48 @@ int fr_poly_call(msm_amd_ctx* ctx, bool host, bool divide, int scalar_layout, co
   return rc;
 }
 
+// msm_amd_fr_poly_eval_points (divide false: out is unused, values required) and msm_amd_fr_poly_div_points: the launches
+// of one point at k points (launch_fr_poly_points), the workspace k times that of fr_poly_call.  The k n_vec values come
+// back point-major and leave as values[v k + j].
+int fr_poly_points_call(msm_amd_ctx* ctx, int mem, bool divide, int scalar_layout, const void* z, size_t k, const void* in,
+                        size_t n, size_t n_vec, void* out, void* values, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = divide ? "msm_amd_fr_poly_div_points" : "msm_amd_fr_poly_eval_points";
+  if (kernel_ms) *kernel_ms = 0.f;
+  if (const char* why = fr_poly_points_check(mem, scalar_layout, z, k, in, n, n_vec, out, values, divide))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
+  const bool host = mem == MSM_AMD_MEM_HOST;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  CallState& s = ctx->calls;
+  FrPolyPointsLaunch c{};
+  c.n = n, c.n_vec = n_vec, c.tile_log = ctx->fr_tile_log, c.layout = scalar_layout, c.divide = divide, c.k = (uint32_t)k;
+  for (size_t j = 0; j < k; ++j) c.z[j] = fr_read_record(scalar_layout, (const uint8_t*)z + j * 32);
+  const FrScanPlan plan = fr_scan_plan(n, n_vec, c.tile_log);
+  d.host = d.in_place = host, d.host_in = host, d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = n * n_vec * 32;
+  d.out = out, d.out_bytes = divide ? n * n_vec * 32 : 0;
+  d.work[0] = {&s.work, (size_t)fr_poly_points_records(plan, n_vec, k) * 32};
+  d.values_bytes = values ? k * n_vec * 32 : 0;
+  const int rc = device_call(ctx, d, [&](hipStream_t st, CallIo& io) {
+    c.in = io.in[0], c.out = io.out, c.work = s.work.p;
+    launch_fr_poly_points(st, c);
+    io.values = (const uint8_t*)s.work.p + fr_poly_points_values(plan, k);
+    return MSM_AMD_OK;
+  });
+  if (rc != MSM_AMD_OK || !values) return rc;
+  for (size_t j = 0; j < k; ++j)
+    for (size_t v = 0; v < n_vec; ++v) {
+      u256 x;
+      std::memcpy(x.v, s.h_values + (j * n_vec + v) * 32, 32);
+      uint32_t rec[8];
+      ntt_store(scalar_layout, x, rec);
+      std::memcpy((uint8_t*)values + (v * k + j) * 32, rec, 32);
+    }
+  return rc;
+}
+
 int fr_lincomb_call(msm_amd_ctx* ctx, bool host, int scalar_layout, const void* k32, const void* a, size_t n, size_t n_vec,
                     void* out, float* kernel_ms) {
   if (!ctx) return MSM_AMD_INPUT_ERROR;
@@ -209,6 +251,16 @@ int msm_amd_fr_poly_div_linear(msm_amd_ctx* ctx, int scalar_layout, const void* 
 int msm_amd_fr_poly_div_linear_device(msm_amd_ctx* ctx, int scalar_layout, const void* z32, const void* d_in, size_t n,
                                       size_t n_vec, void* d_out, void* rem_out, float* kernel_ms) {
   return fr_poly_call(ctx, false, true, scalar_layout, z32, d_in, n, n_vec, d_out, rem_out, kernel_ms);
+}
+
+int msm_amd_fr_poly_eval_points(msm_amd_ctx* ctx, int mem, int scalar_layout, const void* z, size_t k, const void* coeffs,
+                                size_t n, size_t n_vec, void* y_out, float* kernel_ms) {
+  return fr_poly_points_call(ctx, mem, false, scalar_layout, z, k, coeffs, n, n_vec, nullptr, y_out, kernel_ms);
+}
+
+int msm_amd_fr_poly_div_points(msm_amd_ctx* ctx, int mem, int scalar_layout, const void* z, size_t k, const void* in, size_t n,
+                               size_t n_vec, void* out, void* vals_out, float* kernel_ms) {
+  return fr_poly_points_call(ctx, mem, true, scalar_layout, z, k, in, n, n_vec, out, vals_out, kernel_ms);
 }
 
 int msm_amd_fr_lincomb(msm_amd_ctx* ctx, int scalar_layout, const void* k32, const void* a, size_t n, size_t n_vec, void* out) {

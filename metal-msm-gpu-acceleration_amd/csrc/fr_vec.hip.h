@@ -106,6 +106,32 @@ inline FrScanPlan fr_scan_plan(uint64_t n, uint64_t n_vec, uint32_t tile_log) {
   return p;
 }
 
+// Several points per pass (msm_amd_fr_poly_eval_points, msm_amd_fr_poly_div_points; launch_fr.h).  With pairwise distinct
+// z_0 .. z_(k-1), w_j = 1 / prod_(m != j) (z_j - z_m) and s^(j)_i = sum_(t >= i) c_t z_j^(t - i), the suffix sums of the
+// division by X - z_j, the floor quotient of p by prod_j (X - z_j) is
+//     q_i = sum_j w_j s^(j)_(i+1)                                       (partial fractions of 1 / prod_j (X - z_j))
+// and s^(j)_0 = p(z_j).  sum_j w_j z_j^m = 0 for m < k - 1: the top min(k, n) records come out as exact zeros, and with
+// m = 0 the sum is sum_(j < k-1) w_j (s^(j) - s^(k-1)), k - 1 products per record.  The k scans run side by side on the
+// scan plan of one point: level 0 reads the caller's tile once and carries k running values through it, the levels above
+// hold k copies of the single-point totals, point-major, and run in one launch per level over (point, vector, tile).
+constexpr uint32_t kFrPolyMaxPoints = 8;
+// The arguments of both kernels, by value: the powers of every point's level point x_j = z_j^(2^(T level)) and the weights
+struct FrPolyPointsArgs {
+  const uint32_t* src;
+  uint32_t* dst;               // scan
+  const uint32_t* carry;       // scan: the level above; null: every carry is zero
+  uint32_t* totals;            // reduce: one raw record per point and tile; scan: s_0 of every tile, raw (optional)
+  uint64_t len, tiles;         // records and tiles per vector
+  uint64_t src_stride;         // records between the copies of src / dst of two points (0 at level 0: one src for all)
+  uint64_t tot_stride;         // records between the carry / totals of two points
+  uint32_t tile_log;
+  int layout, level0;          // level0 (scan): slot i takes sum_j w_j s^(j)_(i+1); else s_i of the block's one point
+  u256 z[kFrPolyMaxPoints];         // x_j
+  u256 step[kFrPolyMaxPoints][7];   // reduce: x_j^(2^s), s < 6, and x_j^64; scan: x_j^(per 2^s), s < 6
+  u256 w[kFrPolyMaxPoints];         // level 0 of a division
+};
+static_assert(sizeof(FrPolyPointsArgs) < 4096, "the kernel arguments stay under 4 KiB");
+
 // The workspace of one inversion of n records, in records: the tile products t, P with one record more (the zero
 // count, so that T = P_last and the count leave in one copy), S, and the workspace of the scans of t.
 struct FrInvPlan {

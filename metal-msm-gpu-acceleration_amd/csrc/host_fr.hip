@@ -1,7 +1,8 @@
 // Host twins of the Fr vector calls (no ctx, no GPU): the load, store and op bodies of fr_vec.hip.h on the CPU, the
 // records split over the host threads -- the map record by record, the inversion with one inversion per range (the
 // classic trick), the prefix products in two phases (the product of every range, then the ranges from their carries),
-// the polynomial calls likewise (a range's Horner value, then the ranges from the sums behind them), the sparse product
+// the polynomial calls likewise (a range's Horner value, then the ranges from the sums behind them; at several points: k
+// evaluations and k chained divisions, upstream's div_by_vanishing), the sparse product
 // row by row over ranges of equal entry count, the multilinear calls step by step over ranges of outputs (a round: the sums
 // of every range of pairs, added in range order), the Poseidon calls permutation by permutation over ranges, a tree level by
 // level, a round over a term list as the sums of every range of pairs in range order and its step as the bind followed by
@@ -10,6 +11,7 @@
 // way a twin cuts the work shows nowhere.
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
 #include <cstring>
 
 #include "../../include/msm_amd.h"
@@ -94,6 +96,49 @@ const char* fr_poly_check(int scalar_layout, const void* z32, const void* in, ui
   if (device && (((uintptr_t)in | (uintptr_t)out) & 15u)) return "device buffers must be 16-byte aligned";
   if (divide && !fr_overlap_ok(out, in, n * n_vec * 32)) return "the output must be the input itself or disjoint from it";
   return nullptr;
+}
+
+const char* fr_poly_points_check(int mem, int scalar_layout, const void* z, uint64_t k, const void* in, uint64_t n,
+                                 uint64_t n_vec, const void* out, const void* values, bool divide) {
+  if (!fr_layout_known(scalar_layout)) return "scalars in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE only";
+  if (mem != MSM_AMD_MEM_HOST && mem != MSM_AMD_MEM_DEVICE) return "mem must be MSM_AMD_MEM_HOST or MSM_AMD_MEM_DEVICE";
+  if (k == 0 || k > kFrPolyMaxPoints) return "k must be 1 .. MSM_AMD_POLY_MAX_POINTS";
+  if (!z) return "null z";
+  if ((n >> 32) || (n_vec >> 32) || ((n * n_vec) >> 32)) return "n * n_vec >= 2^32";
+  if (n == 0 || n_vec == 0) return nullptr;
+  if (!in || (divide ? !out : !values)) return "null pointer with n > 0";
+  if (mem == MSM_AMD_MEM_DEVICE && (((uintptr_t)in | (uintptr_t)out) & 15u)) return "device buffers must be 16-byte aligned";
+  if (!divide) return nullptr;
+  if (!fr_overlap_ok(out, in, n * n_vec * 32)) return "the output must be the input itself or disjoint from it";
+  u256 x[kFrPolyMaxPoints];
+  for (uint64_t j = 0; j < k; ++j) x[j] = fr_read_record(scalar_layout, (const uint8_t*)z + j * 32);
+  for (uint64_t i = 0; i < k; ++i)
+    for (uint64_t j = i + 1; j < k; ++j)
+      if (u256_eq(x[i], x[j])) {
+        static thread_local char why[96];
+        std::snprintf(why, sizeof why, "the points %u and %u are equal mod r: the division needs distinct points", (unsigned)i,
+                      (unsigned)j);
+        return why;
+      }
+  return nullptr;
+}
+
+void fr_poly_points_weights(const u256* z, uint32_t k, u256* w) {
+  // d_j = prod_(m != j) (z_j - z_m), then Montgomery's trick: one inversion of d_0 .. d_(k-1)
+  u256 d[kFrPolyMaxPoints], pre[kFrPolyMaxPoints];
+  u256 run = Fr::one();
+  for (uint32_t j = 0; j < k; ++j) {
+    d[j] = Fr::one();
+    for (uint32_t m = 0; m < k; ++m)
+      if (m != j) d[j] = Fr::mul(d[j], Fr::sub(z[j], z[m]));
+    pre[j] = run;
+    run = Fr::mul(run, d[j]);
+  }
+  u256 inv = ntt_fr_inv(run);   // of d_0 .. d_j
+  for (uint32_t j = k; j-- != 0;) {
+    w[j] = Fr::mul(inv, pre[j]);
+    inv = Fr::mul(inv, d[j]);
+  }
 }
 
 const char* fr_lincomb_check(int scalar_layout, const void* k32, const void* a, uint64_t n, uint64_t n_vec, const void* out,
@@ -528,6 +573,27 @@ int host_fr_poly(int layout, const void* z32, const void* in_v, size_t n, size_t
   return MSM_AMD_OK;
 }
 
+// Upstream's shape (halo2 div_by_vanishing: roots.iter().fold(poly, kate_division)): the values from k evaluations of the
+// input, then k chained divisions by X - z_j, the first from `in` to `out` and the others in place.  The values are
+// gathered first and written last, so that an in-place call still evaluates the caller's polynomial.
+int host_fr_poly_points(int layout, const void* z_v, size_t k, const void* in_v, size_t n, size_t n_vec, int threads, void* out_v,
+                        void* val_v, bool divide) {
+  if (fr_poly_points_check(MSM_AMD_MEM_HOST, layout, z_v, k, in_v, n, n_vec, out_v, val_v, divide)) return MSM_AMD_INPUT_ERROR;
+  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
+  const uint8_t* z = (const uint8_t*)z_v;
+  std::vector<uint8_t> vals(val_v ? k * n_vec * 32 : 0), y(n_vec * 32);
+  if (val_v)
+    for (size_t j = 0; j < k; ++j) {
+      if (int rc = host_fr_poly(layout, z + j * 32, in_v, n, n_vec, threads, nullptr, y.data(), false)) return rc;
+      for (size_t v = 0; v < n_vec; ++v) std::memcpy(vals.data() + (v * k + j) * 32, y.data() + v * 32, 32);
+    }
+  if (divide)
+    for (size_t j = 0; j < k; ++j)
+      if (int rc = host_fr_poly(layout, z + j * 32, j == 0 ? in_v : out_v, n, n_vec, threads, out_v, nullptr, true)) return rc;
+  if (val_v) std::memcpy(val_v, vals.data(), vals.size());
+  return MSM_AMD_OK;
+}
+
 int host_fr_lincomb(int layout, const void* k32, const void* a_v, size_t n, size_t n_vec, int threads, void* out_v) {
   if (fr_lincomb_check(layout, k32, a_v, n, n_vec, out_v, false)) return MSM_AMD_INPUT_ERROR;
   if (n == 0 || n_vec == 0) return MSM_AMD_OK;
@@ -872,6 +938,37 @@ int msm_amd_host_fr_poly_eval(int scalar_layout, const void* z32, const void* co
 int msm_amd_host_fr_poly_div_linear(int scalar_layout, const void* z32, const void* in, size_t n, size_t n_vec, int threads,
                                     void* out, void* rem_out) {
   return msm_amd::host_fr_poly(scalar_layout, z32, in, n, n_vec, threads, out, rem_out, true);
+}
+
+int msm_amd_host_fr_poly_eval_points(int scalar_layout, const void* z, size_t k, const void* coeffs, size_t n, size_t n_vec,
+                                     int threads, void* y_out) {
+  return msm_amd::host_fr_poly_points(scalar_layout, z, k, coeffs, n, n_vec, threads, nullptr, y_out, false);
+}
+
+int msm_amd_host_fr_poly_div_points(int scalar_layout, const void* z, size_t k, const void* in, size_t n, size_t n_vec,
+                                    int threads, void* out, void* vals_out) {
+  return msm_amd::host_fr_poly_points(scalar_layout, z, k, in, n, n_vec, threads, out, vals_out, true);
+}
+
+int msm_amd_test_fr_poly_points_plan(size_t n, size_t n_vec, size_t k, uint32_t tile_log, int divide, uint64_t counts[8]) {
+  using namespace msm_amd;
+  const uint64_t n64 = n, v64 = n_vec;
+  if (!counts || tile_log < kFrMinTileLog || tile_log > kFrTileLog || k == 0 || k > kFrPolyMaxPoints || n == 0 || n_vec == 0 ||
+      (n64 >> 32) || (v64 >> 32) || ((n64 * v64) >> 32))
+    return MSM_AMD_INPUT_ERROR;
+  const FrScanPlan p = fr_scan_plan(n, n_vec, tile_log);
+  // level 0 runs all k points in one wave per tile, a level above one wave per point and tile; a division reduces every
+  // level but the top one and scans every level
+  uint64_t waves = 0;
+  for (uint32_t l = 0; l < p.levels; ++l) {
+    const uint64_t w = p.tiles[l] * n_vec * (l == 0 ? 1 : k);
+    waves += divide ? (l + 1 < p.levels ? 2 * w : w) : w;
+  }
+  const uint64_t records = fr_poly_points_records(p, n_vec, k);
+  const uint64_t level0 = p.tiles[0] * n_vec * (divide && p.levels > 1 ? 2 : 1);
+  const uint64_t c[8] = {divide ? p.launches : p.levels, waves, records, records * 32, p.levels, sizeof(FrPolyPointsArgs), level0, 0};
+  std::memcpy(counts, c, sizeof c);
+  return MSM_AMD_OK;
 }
 
 int msm_amd_host_fr_lincomb(int scalar_layout, const void* k32, const void* a, size_t n, size_t n_vec, int threads, void* out) {

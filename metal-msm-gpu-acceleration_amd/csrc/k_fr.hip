@@ -23,6 +23,15 @@
 //                          walk that writes s_(i+1) (the division) or s_i (the upper levels) to LDS, and the tile leaves
 //                          at unit stride.  Tiles start at index 0 of a vector, so that only the highest tile is partial
 //                          and its carry is zero: every multiplier is uniform.
+//   fr_poly_points_reduce_kernel<K>, fr_poly_points_scan_kernel<K>  the two kernels above at K points side by side (fr_vec.hip.h):
+//                          a record is loaded (reduce) or read from the LDS image (scan) once and feeds K running values,
+//                          which live in registers -- K is a template argument and every loop over the points is unrolled;
+//                          the K chains of products are independent, so one wave has K of them in flight where the
+//                          single-point kernels have one.  The scan of level 0 writes sum_j w_j s^(j)_(i+1) per record as
+//                          sum_(j < K-1) w_j (s^(j) - s^(K-1)).  blockIdx.y picks the block's group of K points: one group
+//                          at level 0, and K = 1 with one block row per point at the levels above, where point j reads and
+//                          writes its own copy of the totals.  The powers and weights of all points come by value and
+//                          are read at wave-uniform offsets.
 //   fr_lincomb_kernel      one lane per index i: Horner in k over a_v[i], v from the last vector down.
 //   fr_mat_lane_kernel     y = M x, rows of at most LONG entries (fr_mat.hip.h): one lane per row, consecutive lanes on
 //                          consecutive rows; per entry one 8-byte (column, id) load, the dictionary record and the gathered
@@ -352,6 +361,94 @@ __global__ void __launch_bounds__(kFrWave) fr_poly_scan_kernel(FrPolyArgs a) {
 
   NTT_NO_UNROLL for (uint32_t m = lane; m < t.cnt; m += kFrWave)
     store_rec(a.dst + (t.base + t.first + m) * 8, fr_store(a.layout, lds_get(lds, m)));
+}
+
+// The points p0 .. p0 + K - 1 of the block: acc[j] belongs to point p0 + j.  blockIdx.x is the tile over all vectors.
+template <int K>
+__global__ void __launch_bounds__(kFrWave) fr_poly_points_reduce_kernel(FrPolyPointsArgs a) {
+  const uint32_t lane = threadIdx.x, p0 = blockIdx.y * K;
+  const TilePlace t = tile_place(blockIdx.x, a.len, a.tiles, a.tile_log);
+  const uint32_t* src = a.src + ((uint64_t)blockIdx.y * a.src_stride + t.base) * 8;
+  u256 acc[K];
+  MSM_UNROLL for (int j = 0; j < K; ++j) acc[j] = u256_zero();
+  if (lane < t.cnt) {
+    // the lane's highest record first
+    uint64_t i = t.first + lane + ((t.cnt - 1 - lane) & ~(kFrWave - 1));
+    const u256 c = fr_load(a.layout, load_rec(src + i * 8));
+    MSM_UNROLL for (int j = 0; j < K; ++j) acc[j] = c;
+    NTT_NO_UNROLL while (i >= t.first + kFrWave) {
+      i -= kFrWave;
+      const u256 x = fr_load(a.layout, load_rec(src + i * 8));
+      MSM_UNROLL for (int j = 0; j < K; ++j) acc[j] = Fr::add(Fr::mul(acc[j], a.step[p0 + j][6]), x);
+    }
+  }
+  NTT_NO_UNROLL for (uint32_t s = 0; s < 6; ++s) {
+    MSM_UNROLL for (int j = 0; j < K; ++j) acc[j] = Fr::add(acc[j], Fr::mul(a.step[p0 + j][s], wave_xor(acc[j], 1u << s)));
+  }
+  if (lane == 0) {
+    MSM_UNROLL for (int j = 0; j < K; ++j) store_rec(a.totals + ((p0 + j) * a.tot_stride + blockIdx.x) * 8, acc[j]);
+  }
+}
+
+template <int K>
+__global__ void __launch_bounds__(kFrWave) fr_poly_points_scan_kernel(FrPolyPointsArgs a) {
+  extern __shared__ uint32_t fr_lds[];
+  const Image lds = image(fr_lds, a.tile_log);
+  const uint32_t lane = threadIdx.x, p0 = blockIdx.y * K;
+  const uint64_t v = blockIdx.x / a.tiles, b = blockIdx.x - v * a.tiles;
+  const TilePlace t = tile_place(blockIdx.x, a.len, a.tiles, a.tile_log);
+  const uint32_t per = 1u << lds.per_log, m0 = lane << lds.per_log;
+  const uint32_t top = ((1u << a.tile_log) >> lds.per_log) - 1u;   // the lane of a full tile's last record
+  const uint64_t at = ((uint64_t)blockIdx.y * a.src_stride + t.base + t.first) * 8;
+  const bool weighted = K > 1 || a.level0;   // more than one point per block: level 0 only
+
+  NTT_NO_UNROLL for (uint32_t m = lane; m < t.cnt; m += kFrWave)
+    lds_put(lds, m, fr_load(a.layout, load_rec(a.src + at + (uint64_t)m * 8)));
+  __syncthreads();
+
+  // s^(j) at the first record of the next tile: record b + 1 of this vector in point j's level above (read twice, at a
+  // wave-uniform address, so that it does not hold K records of registers across the first walk)
+  const bool has_carry = a.carry && b + 1 < a.tiles;
+  auto carry = [&](int j) {
+    return has_carry ? load_rec(a.carry + ((p0 + j) * a.tot_stride + blockIdx.x + 1) * 8) : u256_zero();
+  };
+  u256 acc[K];
+  MSM_UNROLL for (int j = 0; j < K; ++j) acc[j] = fr_select(lane == top, carry(j), u256_zero());
+  NTT_NO_UNROLL for (uint32_t i = per; i-- != 0;) {
+    if (m0 + i >= t.cnt) continue;
+    const u256 c = lds_get(lds, m0 + i);
+    MSM_UNROLL for (int j = 0; j < K; ++j) acc[j] = Fr::add(Fr::mul(acc[j], a.z[p0 + j]), c);
+  }
+  // the suffix scans of the lane values: acc[j] becomes s^(j) at the lane's first record
+  NTT_NO_UNROLL for (uint32_t s = 0; s < 6; ++s) {
+    const uint32_t d = 1u << s;
+    MSM_UNROLL for (int j = 0; j < K; ++j) {
+      const u256 y = wave_down(acc[j], d);
+      acc[j] = Fr::add(acc[j], Fr::mul(a.step[p0 + j][s], fr_select(lane + d < kFrWave, y, u256_zero())));
+    }
+  }
+  if (a.totals && lane == 0) {
+    MSM_UNROLL for (int j = 0; j < K; ++j) store_rec(a.totals + ((p0 + j) * a.tot_stride + blockIdx.x) * 8, acc[j]);
+  }
+  // s^(j) behind the lane's last record, then down the lane
+  MSM_UNROLL for (int j = 0; j < K; ++j) acc[j] = fr_select(lane == top, carry(j), wave_down(acc[j], 1));
+  NTT_NO_UNROLL for (uint32_t i = per; i-- != 0;) {
+    const uint32_t m = m0 + i;
+    if (m >= t.cnt) continue;
+    const u256 c = lds_get(lds, m);
+    // sum_j w_j s^(j)_(m+1) = sum_(j < K-1) w_j (s^(j) - s^(K-1)), for sum_j w_j = 0; one point: w = 1, no product
+    u256 q = acc[0];
+    if (K > 1) {
+      q = Fr::mul(a.w[p0], Fr::sub(acc[0], acc[K - 1]));
+      MSM_UNROLL for (int j = 1; j < K - 1; ++j) q = Fr::add(q, Fr::mul(a.w[p0 + j], Fr::sub(acc[j], acc[K - 1])));
+    }
+    MSM_UNROLL for (int j = 0; j < K; ++j) acc[j] = Fr::add(Fr::mul(acc[j], a.z[p0 + j]), c);
+    lds_put(lds, m, weighted ? q : acc[0]);
+  }
+  __syncthreads();
+
+  NTT_NO_UNROLL for (uint32_t m = lane; m < t.cnt; m += kFrWave)
+    store_rec(a.dst + at + (uint64_t)m * 8, fr_store(a.layout, lds_get(lds, m)));
 }
 
 __global__ void __launch_bounds__(kFrMapThreads) fr_lincomb_kernel(int layout, u256 k, const uint32_t* A, uint64_t n,
@@ -782,6 +879,83 @@ uint32_t launch_fr_poly(hipStream_t st, const FrPolyLaunch& c) {
     const FrPolyArgs a = level(k, true);
     hipLaunchKernelGGL(fr_poly_scan_kernel, dim3((uint32_t)(a.tiles * c.n_vec)), dim3(kFrWave), fr_image_bytes(a.tile_log), st, a);
   }
+  return plan.launches;
+}
+
+namespace {
+
+// grid: x the tiles over all vectors, y the groups of K points
+template <int K>
+void launch_points_reduce(hipStream_t st, const FrPolyPointsArgs& a, uint64_t n_vec, uint32_t groups) {
+  hipLaunchKernelGGL(fr_poly_points_reduce_kernel<K>, dim3((uint32_t)(a.tiles * n_vec), groups), dim3(kFrWave), 0, st, a);
+}
+template <int K>
+void launch_points_scan(hipStream_t st, const FrPolyPointsArgs& a, uint64_t n_vec, uint32_t groups) {
+  hipLaunchKernelGGL(fr_poly_points_scan_kernel<K>, dim3((uint32_t)(a.tiles * n_vec), groups), dim3(kFrWave),
+                     fr_image_bytes(a.tile_log), st, a);
+}
+// level 0: all k points in one block; above: one block row per point
+void launch_points(hipStream_t st, const FrPolyPointsArgs& a, uint64_t n_vec, uint32_t k, bool level0, bool scan) {
+  if (!level0) return scan ? launch_points_scan<1>(st, a, n_vec, k) : launch_points_reduce<1>(st, a, n_vec, k);
+  switch (k) {
+    case 1: return scan ? launch_points_scan<1>(st, a, n_vec, 1) : launch_points_reduce<1>(st, a, n_vec, 1);
+    case 2: return scan ? launch_points_scan<2>(st, a, n_vec, 1) : launch_points_reduce<2>(st, a, n_vec, 1);
+    case 3: return scan ? launch_points_scan<3>(st, a, n_vec, 1) : launch_points_reduce<3>(st, a, n_vec, 1);
+    case 4: return scan ? launch_points_scan<4>(st, a, n_vec, 1) : launch_points_reduce<4>(st, a, n_vec, 1);
+    case 5: return scan ? launch_points_scan<5>(st, a, n_vec, 1) : launch_points_reduce<5>(st, a, n_vec, 1);
+    case 6: return scan ? launch_points_scan<6>(st, a, n_vec, 1) : launch_points_reduce<6>(st, a, n_vec, 1);
+    case 7: return scan ? launch_points_scan<7>(st, a, n_vec, 1) : launch_points_reduce<7>(st, a, n_vec, 1);
+    default: return scan ? launch_points_scan<8>(st, a, n_vec, 1) : launch_points_reduce<8>(st, a, n_vec, 1);
+  }
+}
+
+}  // namespace
+
+uint32_t launch_fr_poly_points(hipStream_t st, const FrPolyPointsLaunch& c) {
+  const FrScanPlan plan = fr_scan_plan(c.n, c.n_vec, c.tile_log);
+  const uint32_t per_log = c.tile_log > 6u ? c.tile_log - 6u : 0u;
+  uint32_t* work = (uint32_t*)c.work;
+  uint32_t* values = work + fr_poly_points_values(plan, c.k) / 4;
+  // z_j^(2^e): level l works at the points z_j^(2^(T l))
+  u256 pw[kFrPolyMaxPoints][kFrPolyPowers], w[kFrPolyMaxPoints];
+  for (uint32_t p = 0; p < c.k; ++p) {
+    pw[p][0] = c.z[p];
+    for (uint32_t e = 1; e < kFrPolyPowers; ++e) pw[p][e] = Fr::mul(pw[p][e - 1], pw[p][e - 1]);
+  }
+  if (c.divide) fr_poly_points_weights(c.z, c.k, w);
+  auto level = [&](uint32_t l, bool scan) {
+    FrPolyPointsArgs a{};
+    a.len = plan.len[l], a.tiles = plan.tiles[l], a.tile_log = c.tile_log;
+    a.src = l == 0 ? (const uint32_t*)c.in : work + plan.offset[l] * 8;
+    a.src_stride = l == 0 ? 0 : plan.records;
+    a.layout = l == 0 ? c.layout : kFrRaw;
+    const bool last = l + 1 == plan.levels;
+    uint32_t* above = last ? values : work + plan.offset[l + 1] * 8;
+    a.tot_stride = last ? c.n_vec : plan.records;
+    const uint32_t e = c.tile_log * l;
+    for (uint32_t p = 0; p < c.k; ++p) {
+      a.z[p] = pw[p][e];
+      if (scan) {
+        for (uint32_t s = 0; s < 6; ++s) a.step[p][s] = pw[p][e + per_log + s];
+        if (l == 0) a.w[p] = w[p];
+      } else {
+        for (uint32_t s = 0; s < 7; ++s) a.step[p][s] = pw[p][e + s];
+      }
+    }
+    if (scan) {
+      a.dst = l == 0 ? (uint32_t*)c.out : work + plan.offset[l] * 8;
+      a.level0 = l == 0;
+      a.carry = last ? nullptr : above;
+      a.totals = last ? above : nullptr;
+    } else {
+      a.totals = above;
+    }
+    return a;
+  };
+  const uint32_t reductions = c.divide ? plan.levels - 1 : plan.levels;
+  for (uint32_t l = 0; l < reductions; ++l) launch_points(st, level(l, false), c.n_vec, c.k, l == 0, false);
+  if (!c.divide) return plan.levels;
+  for (uint32_t l = plan.levels; l-- != 0;) launch_points(st, level(l, true), c.n_vec, c.k, l == 0, true);
   return plan.launches;
 }
 

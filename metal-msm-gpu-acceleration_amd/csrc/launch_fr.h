@@ -61,6 +61,24 @@ struct FrPolyLaunch {
 inline size_t fr_poly_values(const FrScanPlan& p) { return (size_t)p.records * 32; }
 // every launch of one evaluation or division, in stream order; returns the number of launches
 uint32_t launch_fr_poly(hipStream_t st, const FrPolyLaunch& c);
+// The same at k points in one pass (fr_vec.hip.h): evaluation leaves p_v(z_j), division the quotient by prod_j (X - z_j)
+// and p_v(z_j).  The levels >= 1 of the plan exist once per point: point j owns the records j plan.records .. of the
+// workspace, and the k n_vec values lie behind all of them, point-major (value of point j, vector v at j n_vec + v).
+// The launches are those of one point: levels for an evaluation, 2 levels - 1 for a division.
+struct FrPolyPointsLaunch {
+  const void* in;     // n_vec * n records
+  void* out;          // division: n_vec * n records, in == out is allowed
+  void* work;         // fr_poly_points_records(plan, n_vec, k) records
+  uint64_t n, n_vec;
+  uint32_t tile_log;
+  int layout;
+  bool divide;
+  uint32_t k;                    // 1 .. kFrPolyMaxPoints
+  u256 z[kFrPolyMaxPoints];      // Montgomery and reduced; a division: pairwise distinct
+};
+inline size_t fr_poly_points_values(const FrScanPlan& p, uint64_t k) { return (size_t)(k * p.records) * 32; }
+inline uint64_t fr_poly_points_records(const FrScanPlan& p, uint64_t n_vec, uint64_t k) { return k * (p.records + n_vec); }
+uint32_t launch_fr_poly_points(hipStream_t st, const FrPolyPointsLaunch& c);
 // out[i] = sum_v k^v a[v n + i], i < n; out may be a
 void launch_fr_lincomb(hipStream_t st, int layout, const u256& k, const void* a, uint64_t n, uint64_t n_vec, void* out);
 
@@ -221,6 +239,14 @@ u256 fr_read_record(int scalar_layout, const void* rec32);
 // msm_amd_fr_poly_eval* (values required, out unused) and msm_amd_fr_poly_div_linear* (out required, values optional)
 const char* fr_poly_check(int scalar_layout, const void* z32, const void* in, uint64_t n, uint64_t n_vec, const void* out,
                           const void* values, bool divide, bool device);
+// msm_amd_fr_poly_eval_points (values required, out unused), msm_amd_fr_poly_div_points (out required, values optional)
+// and their twins (mem: MSM_AMD_MEM_HOST): layout, mem, k and z first, then the sizes, then n == 0 or n_vec == 0 passes,
+// then pointers, alignment (device), overlap and, for a division, that no two points are equal mod r.  The message of that
+// last refusal names both indices and lives in a buffer of the calling thread.
+const char* fr_poly_points_check(int mem, int scalar_layout, const void* z, uint64_t k, const void* in, uint64_t n,
+                                 uint64_t n_vec, const void* out, const void* values, bool divide);
+// w_j = 1 / prod_(m != j) (z_j - z_m) of pairwise distinct reduced residues, one inversion for all (k == 1: one)
+void fr_poly_points_weights(const u256* z, uint32_t k, u256* w);
 // msm_amd_fr_lincomb*: out is the first vector of a or disjoint from all of a
 const char* fr_lincomb_check(int scalar_layout, const void* k32, const void* a, uint64_t n, uint64_t n_vec, const void* out,
                              bool device);
