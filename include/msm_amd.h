@@ -1204,6 +1204,66 @@ int msm_amd_host_fr_poly_div_points(int scalar_layout, const void* z, size_t k, 
  * of the kernel arguments of a level-0 launch (< 4096), [6] waves of the level-0 launches, [7] 0. */
 int msm_amd_test_fr_poly_points_plan(size_t n, size_t n_vec, size_t k, uint32_t tile_log, int divide, uint64_t counts[8]);
 
+/* ---- gate polynomials over rotated columns: sums of products, row by row ---------------------------------------
+ * The quotient numerator on the extended coset (halo2 evaluate_h; the gate and copy-constraint sums of a PLONK prover):
+ * n_vec columns of n records, column v at in + 32 v stride, and for every row 0 <= i < n
+ *     v[i]   = sum_k c_k prod_j col_(factors[k][j])[(i + rotations[k][j] rot_step) mod n]
+ *     out[i] = v[i]                                  plain
+ *     out[i] = k_acc out[i] + v[i]                   MSM_AMD_GATE_ACCUMULATE: halo2's values * y + gate
+ *     out[i] = (either of the above) scale[i mod period]      scale given: the periodic 1 / Z_H
+ * Up to 256 columns, 16 terms, 8 factors per term; an index may repeat inside a term (powers) and across terms.  The
+ * effective offset of a factor is (rot rot_step) mod n with the non-negative remainder, for any int32 rot and any
+ * rot_step >= 1 (2^(extended_k - k) on an extended domain); a call may use at most MSM_AMD_GATE_MAX_OFFSETS DISTINCT
+ * effective offsets.  The host reduces them once; what travels to the kernel by value is the 8 offsets and, per factor, a
+ * column byte and an offset-slot byte: a row costs one addition and one conditional subtraction.  The coefficients are
+ * records in HOST memory in the call's layout, any 256-bit word taken mod r; 1 and r - 1 cost no product.
+ * Records, layouts, "any word mod r", fully reduced outputs (unique bytes), 16-byte alignment of device pointers, the
+ * bounded wait, the busy-ctx error and msm_amd_last_error are those of msm_amd_fr_map*.  Any n >= 1 below 2^32 (not only
+ * powers of two), stride >= n, n_vec stride < 2^32.  n == 0 or n_vec == 0: MSM_AMD_OK, nothing is touched, the term list is
+ * not looked at.  One launch per call, one lane per row.
+ * out: n records, disjoint from the whole input span (an overlap is MSM_AMD_INPUT_ERROR: rotated reads make in-place
+ * evaluation meaningless); without ACCUMULATE its old bytes are never read; the input is never written.
+ * MSM_AMD_INPUT_ERROR, each with its own text and no byte of out written: n_terms outside 1 .. 16; a term length outside
+ * 1 .. 8; a column index not below n_vec; n_vec above 256; more than 8 distinct offsets; rot_step == 0; n >= 2^32; a period
+ * that is no power of two in 1 .. 256 or does not divide n; an unknown flag, mem or layout; stride < n; a null pointer the
+ * call reads (k_acc32 only with ACCUMULATE); a device pointer that is not 16-byte aligned; an overlap of out and in. */
+enum { MSM_AMD_GATE_MAX_COLUMNS = 256, MSM_AMD_GATE_MAX_TERMS = 16, MSM_AMD_GATE_MAX_FACTORS = 8, MSM_AMD_GATE_MAX_OFFSETS = 8,
+       MSM_AMD_GATE_MAX_PERIOD = 256 };
+enum { MSM_AMD_GATE_ACCUMULATE = 1 };   /* flags */
+typedef struct msm_amd_fr_gate_terms {
+  uint32_t n_terms;          /* 1 .. 16 */
+  const void* coeff;         /* n_terms records, HOST memory, the call's scalar layout, any 256-bit word taken mod r */
+  const uint32_t* term_len;  /* n_terms values, each 1 .. 8 */
+  const uint32_t* factors;   /* sum(term_len) column indices < n_vec, term after term; an index may repeat (powers) */
+  const int32_t* rotations;  /* one per factor, any value */
+} msm_amd_fr_gate_terms;
+/* The check of a term list every entry point shares (no ctx, CPU only; the coefficients are not read): the longest term in
+ * *degree and the number of distinct effective offsets in *n_offsets (both optional).  MSM_AMD_INPUT_ERROR for a list the
+ * calls below refuse, n_vec == 0 and n == 0 included; msm_amd_fr_gate_last_error has the text. */
+int msm_amd_fr_gate_check(const msm_amd_fr_gate_terms* terms, size_t n_vec, size_t n, uint64_t rot_step, uint32_t* degree,
+                          uint32_t* n_offsets);
+/* Why the last msm_amd_fr_gate_check, msm_amd_host_fr_gate_eval or msm_amd_test_fr_gate_plan of the calling thread
+ * refused its arguments ("" after a call that did not): the calls without a ctx have no msm_amd_last_error. */
+const char* msm_amd_fr_gate_last_error(void);
+/* mem (MSM_AMD_MEM_HOST / MSM_AMD_MEM_DEVICE, below): where in and out lie -- host memory staged through the ctx like the
+ * other host-buffer forms, or device-resident columns.  k_acc32 (one record) and scale (period records; NULL: no
+ * scaling, period is ignored) are HOST memory either way, in the call's layout; the scale table goes to ctx-owned device
+ * memory (period 32 bytes).  kernel_ms is optional. */
+int msm_amd_fr_gate_eval(msm_amd_ctx* ctx, int mem, int scalar_layout, uint32_t flags, const msm_amd_fr_gate_terms* terms,
+                         const void* in, size_t n, size_t n_vec, size_t stride, uint64_t rot_step,
+                         const void* k_acc32 /* HOST memory */, const void* scale /* HOST memory, optional */, size_t period,
+                         void* out, float* kernel_ms);
+/* The same on the CPU (no ctx, no GPU; the same bodies compiled for the host); threads <= 0: up to 16 host threads. */
+int msm_amd_host_fr_gate_eval(int scalar_layout, uint32_t flags, const msm_amd_fr_gate_terms* terms, const void* in, size_t n,
+                              size_t n_vec, size_t stride, uint64_t rot_step, const void* k_acc32, const void* scale,
+                              size_t period, int threads, void* out);
+/* Test aid (no ctx, CPU only): the plan of a call; period == 0: no scale.  counts: [0] launches (1), [1] workgroups,
+ * [2] records read per row (the factors, the old output of ACCUMULATE, the scale), [3] field products per row: len - 1 per
+ * term, one for a coefficient that is neither 1 nor r - 1, one each for ACCUMULATE and the scale, [4] distinct offsets,
+ * [5] bytes of ctx-owned device memory (the scale table, else 0), [6] the degree, [7] 0. */
+int msm_amd_test_fr_gate_plan(int scalar_layout, uint32_t flags, const msm_amd_fr_gate_terms* terms, size_t n, size_t n_vec,
+                              uint64_t rot_step, size_t period, uint64_t counts[8]);
+
 /* ---- sparse matrix times vector over Fr: the R1CS witness map ------------------------------------------------
  * Every R1CS prover starts from A z, B z, C z: three sparse matrices over Fr, fixed per circuit, times the assignment of
  * one proof (arkworks witness_map_from_matrices; the same step in snarkjs and bellman; Marlin and Spartan-style provers

@@ -58,6 +58,8 @@ NTT_FORWARD, NTT_INVERSE = 0, 1
 FR_ADD, FR_SUB, FR_MUL, FR_SCALE, FR_AXPY, FR_MULSUB_SCALE = range(6)
 FR_PREFIX_INCLUSIVE, FR_PREFIX_EXCLUSIVE = 0, 1
 LOOKUP_STRICT, LOOKUP_COUNT_MISSING = 0, 1
+GATE_ACCUMULATE = 1            # MSM_AMD_GATE_*: flags of msm_amd_fr_gate_eval
+GATE_MAX_OFFSETS = 8
 MEM_HOST, MEM_DEVICE = 0, 1    # MSM_AMD_MEM_*: where the buffers of msm_amd_fr_sort, _build_sorted and _permute_as lie
 PERMUTE_ROWS, PERMUTE_HALO2 = 0, 1   # MSM_AMD_PERMUTE_*: the arrangement of A', S'
 LOOKUP_NOT_FOUND = 0xFFFFFFFF
@@ -172,6 +174,8 @@ EXPORTS = [
     "msm_amd_fr_lookup_permute_as", "msm_amd_host_fr_lookup_permute_as",
     "msm_amd_fr_poly_eval_points", "msm_amd_fr_poly_div_points", "msm_amd_host_fr_poly_eval_points",
     "msm_amd_host_fr_poly_div_points", "msm_amd_test_fr_poly_points_plan",
+    "msm_amd_fr_gate_check", "msm_amd_fr_gate_last_error", "msm_amd_fr_gate_eval", "msm_amd_host_fr_gate_eval",
+    "msm_amd_test_fr_gate_plan",
 ]
 
 # stage tap (msm_amd_test_last_plan: word order of MSM_AMD_TP_*; msm_amd_test_stage_copy: MSM_AMD_STAGE_*)
@@ -526,6 +530,17 @@ def _lib():
             L.msm_amd_host_fr_sumcheck_step_terms.argtypes = [c_int, c_int, tp, c_void_p, c_void_p, c_size_t, c_size_t, c_size_t,
                                                               c_int, c_void_p, c_void_p]
             L.msm_amd_test_fr_sumcheck_terms_plan.argtypes = [tp, c_size_t, c_size_t, c_uint32, c_int, POINTER(c_uint64)]
+        if hasattr(L, "msm_amd_fr_gate_eval"):   # (an MSM_AMD_LIB build from before the gate polynomials still loads)
+            tp = c_void_p                        # const msm_amd_fr_gate_terms*
+            L.msm_amd_fr_gate_check.argtypes = [tp, c_size_t, c_size_t, c_uint64, POINTER(c_uint32), POINTER(c_uint32)]
+            L.msm_amd_fr_gate_last_error.argtypes = []
+            L.msm_amd_fr_gate_last_error.restype = c_char_p
+            L.msm_amd_fr_gate_eval.argtypes = [c_void_p, c_int, c_int, c_uint32, tp, c_void_p, c_size_t, c_size_t, c_size_t,
+                                               c_uint64, c_void_p, c_void_p, c_size_t, c_void_p, POINTER(c_float)]
+            L.msm_amd_host_fr_gate_eval.argtypes = [c_int, c_uint32, tp, c_void_p, c_size_t, c_size_t, c_size_t, c_uint64,
+                                                    c_void_p, c_void_p, c_size_t, c_int, c_void_p]
+            L.msm_amd_test_fr_gate_plan.argtypes = [c_int, c_uint32, tp, c_size_t, c_size_t, c_uint64, c_size_t,
+                                                    POINTER(c_uint64)]
         if hasattr(L, "msm_amd_poseidon_constants"):   # (an MSM_AMD_LIB build from before the Poseidon calls still loads)
             shape = [c_uint32, c_uint32, c_uint32, c_int, c_void_p, c_void_p]   # t, r_f, r_p, layout, ark, mds
             L.msm_amd_poseidon_constants.argtypes = shape
@@ -1667,6 +1682,28 @@ class MsmConfig:
                                                                  c_void_p(d_out), g, ctypes.byref(ms)))
         return g.raw[:32 * sumcheck_terms_values(terms, n_vec)], ms.value
 
+    def fr_gate_eval(self, columns, terms, n=None, n_vec=1, stride=None, rot_step=1, flags=0, k_acc: bytes = None,
+                     scale: bytes = None, out=None, scalar_layout=SCALAR_MONT_LE, mem=MEM_HOST):
+        """out[i] = sum_k c_k prod_j col[(i + rot rot_step) mod n] of a GateTerms list (msm_amd_fr_gate_eval); with
+        GATE_ACCUMULATE out[i] = k_acc out[i] + that, and with `scale` (period = len(scale) // 32 records) times
+        scale[i mod period].  MEM_HOST: columns is bytes and `out` the old n records (required with GATE_ACCUMULATE, else a
+        poison the call must not read); returns (the n records, kernel_ms).  MEM_DEVICE: columns and out are device
+        addresses and n is required; returns (None, kernel_ms)."""
+        ms = c_float(0)
+        period = len(scale) // 32 if scale is not None else 0
+        if mem != MEM_HOST:
+            self._check(_lib().msm_amd_fr_gate_eval(self.h, mem, scalar_layout, flags, _terms_ptr(terms), c_void_p(columns), n or 0,
+                                                    n_vec, (n or 0) if stride is None else stride, rot_step, k_acc, scale, period,
+                                                    c_void_p(out), ctypes.byref(ms)))
+            return None, ms.value
+        if n is None:
+            n = len(columns) // 32 // n_vec if n_vec else 0
+        buf = ctypes.create_string_buffer(out if out is not None else b"\xFF" * (32 * n), 32 * n + 1)
+        self._check(_lib().msm_amd_fr_gate_eval(self.h, mem, scalar_layout, flags, _terms_ptr(terms), columns, n, n_vec,
+                                                n if stride is None else stride, rot_step, k_acc, scale, period, buf,
+                                                ctypes.byref(ms)))
+        return buf.raw[:32 * n], ms.value
+
     # ---- pairings -------------------------------------------------------------------------------
     def pairing_product(self, g1_points: bytes, g2_points: bytes, n_groups: int, group_size: int, flags=0,
                         gt_layout=GT_MONT_LE, point_layout=POINT_H2C_AFFINE, g2_point_layout=G2_POINT_H2C_AFFINE,
@@ -2719,6 +2756,63 @@ def test_fr_sumcheck_terms_plan(terms, n, n_vec=1, chunk_log=8, step=False) -> d
     if st != OK:
         raise MsmError(st)
     return dict(zip(("launches", "waves", "records", "bytes", "levels", "first_waves", "values"), out))
+
+
+class _GateTermsC(ctypes.Structure):
+    _fields_ = [("n_terms", c_uint32), ("coeff", c_void_p), ("term_len", POINTER(c_uint32)), ("factors", POINTER(c_uint32)),
+                ("rotations", POINTER(ctypes.c_int32))]
+
+
+class GateTerms:
+    """A gate polynomial sum_k c_k prod_j col_(index)[i + rotation rot_step] for msm_amd_fr_gate_eval
+    (msm_amd_fr_gate_terms): `terms` is a sequence of (coefficient record of 32 bytes in the call's layout, sequence of
+    factors), a factor being a column index or a (column index, rotation) pair."""
+
+    def __init__(self, terms):
+        terms = [(c, [f if isinstance(f, tuple) else (f, 0) for f in fs]) for c, fs in terms]
+        self.coeff = ctypes.create_string_buffer(b"".join(c for c, _ in terms), max(1, 32 * len(terms)))
+        self.term_len = (c_uint32 * max(1, len(terms)))(*[len(f) for _, f in terms])
+        flat = [f for _, fs in terms for f in fs]
+        self.factors = (c_uint32 * max(1, len(flat)))(*[col for col, _ in flat])
+        self.rotations = (ctypes.c_int32 * max(1, len(flat)))(*[rot for _, rot in flat])
+        self.c = _GateTermsC(len(terms), ctypes.cast(self.coeff, c_void_p), self.term_len, self.factors, self.rotations)
+
+
+def fr_gate_last_error() -> str:
+    """Why the last fr_gate_check, host_fr_gate_eval or test_fr_gate_plan of this thread refused (msm_amd_fr_gate_last_error)"""
+    return _lib().msm_amd_fr_gate_last_error().decode()
+
+
+def fr_gate_check(terms, n_vec, n, rot_step=1):
+    """The shared check of a GateTerms list (msm_amd_fr_gate_check): (degree, distinct offsets); MsmError with the reason."""
+    d, k = c_uint32(0), c_uint32(0)
+    st = _lib().msm_amd_fr_gate_check(_terms_ptr(terms), n_vec, n, rot_step, ctypes.byref(d), ctypes.byref(k))
+    if st != OK:
+        raise MsmError(st, fr_gate_last_error())
+    return d.value, k.value
+
+
+def host_fr_gate_eval(columns: bytes, terms, n=None, n_vec=1, stride=None, rot_step=1, flags=0, k_acc: bytes = None,
+                      scale: bytes = None, out: bytes = None, scalar_layout=SCALAR_MONT_LE, threads=0) -> bytes:
+    """Host twin of MsmConfig.fr_gate_eval with MEM_HOST (no GPU): the n records."""
+    if n is None:
+        n = len(columns) // 32 // n_vec if n_vec else 0
+    buf = ctypes.create_string_buffer(out if out is not None else b"\xFF" * (32 * n), 32 * n + 1)
+    st = _lib().msm_amd_host_fr_gate_eval(scalar_layout, flags, _terms_ptr(terms), columns, n, n_vec,
+                                          n if stride is None else stride, rot_step, k_acc, scale,
+                                          len(scale) // 32 if scale is not None else 0, threads, buf)
+    if st != OK:
+        raise MsmError(st, fr_gate_last_error())
+    return buf.raw[:32 * n]
+
+
+def test_fr_gate_plan(terms, n, n_vec=1, rot_step=1, flags=0, period=0, scalar_layout=SCALAR_MONT_LE) -> dict:
+    """The plan of an fr_gate_eval call (msm_amd_test_fr_gate_plan); period 0: no scale."""
+    out = (c_uint64 * 8)()
+    st = _lib().msm_amd_test_fr_gate_plan(scalar_layout, flags, _terms_ptr(terms), n, n_vec, rot_step, period, out)
+    if st != OK:
+        raise MsmError(st, fr_gate_last_error())
+    return dict(zip(("launches", "workgroups", "reads", "products", "offsets", "bytes", "degree"), out))
 
 
 def test_fr_mle_plan(call, n, n_vec=1, order=MLE_LOW, form=SUMCHECK_PRODUCT, n_bind=1, chunk_log=8, tile_log=9) -> dict:

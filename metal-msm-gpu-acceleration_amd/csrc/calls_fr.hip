@@ -1,5 +1,5 @@
 // The blocking vector calls over Fr (device_call.h): map, prefix product, batch inversion, polynomials, linear
-// combinations, sparse matrices, multilinear tables and sumcheck rounds, the width scan, Poseidon.
+// combinations, sparse matrices, multilinear tables and sumcheck rounds, gate polynomials, the width scan, Poseidon.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1036,9 +1036,50 @@ int fr_sumcheck_terms_call(msm_amd_ctx* ctx, int mem, bool step, int scalar_layo
   return rc;
 }
 
+// A gate polynomial over rotated columns: one launch.  The host form stages the columns, and with ACCUMULATE the old
+// records of out as the second input; the result leaves through the staged output.  The scale table is host memory in
+// either form: it is reduced here and goes up as the third input into ctx-owned memory.
+int fr_gate_call(msm_amd_ctx* ctx, int mem, int scalar_layout, uint32_t flags, const msm_amd_fr_gate_terms* terms, const void* in,
+                 size_t n, size_t n_vec, size_t stride, uint64_t rot_step, const void* k_acc32, const void* scale, size_t period,
+                 void* out, float* kernel_ms) {
+  if (!ctx) return MSM_AMD_INPUT_ERROR;
+  DeviceCall d;
+  d.who = "msm_amd_fr_gate_eval";
+  if (kernel_ms) *kernel_ms = 0.f;
+  FrGateLaunch c{};
+  if (const char* why = fr_gate_eval_check(mem, scalar_layout, flags, terms, in, n, n_vec, stride, rot_step, k_acc32, scale, period,
+                                           out, &c.terms))
+    return fail(ctx, MSM_AMD_INPUT_ERROR, d.who + ": " + why);
+  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
+  const bool host = mem == MSM_AMD_MEM_HOST;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  c.n = n, c.stride = stride, c.layout = scalar_layout, c.accumulate = flags & kFrGateAccumulate;
+  if (c.accumulate) c.k_acc = fr_read_record(scalar_layout, k_acc32);
+  std::vector<u256> table(scale ? period : 0);
+  for (size_t j = 0; j < table.size(); ++j) table[j] = fr_read_record(scalar_layout, (const uint8_t*)scale + j * 32);
+  c.period = scale ? (uint32_t)period : 1;
+  d.host = host, d.host_in = (host ? 1u | (c.accumulate ? 2u : 0u) : 0u) | (scale ? 4u : 0u), d.kernel_ms = kernel_ms;
+  d.in[0] = in, d.in_bytes[0] = ((n_vec - 1) * stride + n) * 32;
+  if (c.accumulate) d.in[1] = out, d.in_bytes[1] = n * 32;
+  if (scale) d.in[2] = table.data(), d.in_bytes[2] = period * 32;
+  d.out = out, d.out_bytes = n * 32;
+  return device_call(ctx, d, [&](hipStream_t st, const CallIo& io) {
+    c.in = io.in[0], c.acc = c.accumulate ? io.in[1] : nullptr, c.scale = scale ? io.in[2] : nullptr, c.out = io.out;
+    launch_fr_gate(st, c);
+    return MSM_AMD_OK;
+  });
+}
+
 }  // namespace
 
 extern "C" {
+
+int msm_amd_fr_gate_eval(msm_amd_ctx* ctx, int mem, int scalar_layout, uint32_t flags, const msm_amd_fr_gate_terms* terms,
+                         const void* in, size_t n, size_t n_vec, size_t stride, uint64_t rot_step, const void* k_acc32,
+                         const void* scale, size_t period, void* out, float* kernel_ms) {
+  return fr_gate_call(ctx, mem, scalar_layout, flags, terms, in, n, n_vec, stride, rot_step, k_acc32, scale, period, out,
+                      kernel_ms);
+}
 
 int msm_amd_fr_mle_bind(msm_amd_ctx* ctx, int scalar_layout, int order, const void* r, size_t n_bind, const void* in, size_t n,
                         size_t n_vec, size_t stride, void* out) {

@@ -6,7 +6,8 @@
 // row by row over ranges of equal entry count, the multilinear calls step by step over ranges of outputs (a round: the sums
 // of every range of pairs, added in range order), the Poseidon calls permutation by permutation over ranges, a tree level by
 // level, a round over a term list as the sums of every range of pairs in range order and its step as the bind followed by
-// that round (and the constants of the paper's Grain generator, msm_amd_poseidon_constants);
+// that round, a gate polynomial over rotated columns row by row over ranges of rows (and the constants of the paper's Grain
+// generator, msm_amd_poseidon_constants);
 // and the argument checks the twins share with the host driver (msm_host.hip).  The bytes of a result are unique, so the
 // way a twin cuts the work shows nowhere.
 #include <hip/hip_runtime.h>
@@ -312,6 +313,77 @@ const char* fr_sumcheck_step_check(int scalar_layout, int order, const ::msm_amd
   if (out == in) return order == kFrMleHigh ? nullptr : "MSM_AMD_MLE_LOW is out of place only";
   if (!spans_apart(in, ((n_vec - 1) * stride + n) * 32, out, ((n_vec - 1) * stride + n / 2) * 32))
     return "the output must be the input itself (MSM_AMD_MLE_HIGH) or disjoint from all of it";
+  return nullptr;
+}
+
+static_assert(kFrGateMaxCols == MSM_AMD_GATE_MAX_COLUMNS && kFrGateMaxTerms == MSM_AMD_GATE_MAX_TERMS &&
+              kFrGateMaxFactors == MSM_AMD_GATE_MAX_FACTORS && kFrGateMaxOffsets == MSM_AMD_GATE_MAX_OFFSETS &&
+              kFrGateMaxPeriod == MSM_AMD_GATE_MAX_PERIOD && kFrGateAccumulate == MSM_AMD_GATE_ACCUMULATE, "gates");
+
+const char* fr_gate_terms_check(int scalar_layout, const ::msm_amd_fr_gate_terms* terms, uint64_t n_vec, uint64_t n,
+                                uint64_t rot_step, FrGateTerms* image, bool coeffs) {
+  if (!terms) return "null term list";
+  if (n_vec < 1 || n_vec > kFrGateMaxCols) return "n_vec must be 1 .. 256 for a gate";
+  if (n < 1 || (n >> 32)) return "n must be 1 .. 2^32 - 1";
+  if (terms->n_terms < 1 || terms->n_terms > kFrGateMaxTerms) return "n_terms must be 1 .. 16";
+  if (!terms->coeff || !terms->term_len || !terms->factors || !terms->rotations) return "null pointer in the term list";
+  if (rot_step == 0) return "rot_step must be at least 1";
+  FrGateTerms g{};
+  g.n_terms = terms->n_terms;
+  uint32_t at = 0;
+  for (uint32_t k = 0; k < terms->n_terms; ++k) {
+    const uint32_t len = terms->term_len[k];
+    if (len < 1 || len > kFrGateMaxFactors) return "a term length must be 1 .. 8";
+    for (uint32_t j = 0; j < len; ++j)
+      if (terms->factors[at + j] >= n_vec) return "a column index of a term is not below n_vec";
+    at += len;
+  }
+  at = 0;
+  for (uint32_t k = 0; k < terms->n_terms; ++k) {
+    fr_sum_set_byte(g.len, k, terms->term_len[k]);
+    for (uint32_t j = 0; j < terms->term_len[k]; ++j, ++at) {
+      // (rot rot_step) mod n, the non-negative remainder: |rot| <= 2^31 and rot_step < 2^64, so the product fits 128 bits
+      const int64_t rot = terms->rotations[at];
+      const unsigned __int128 mag = (unsigned __int128)(uint64_t)(rot < 0 ? -rot : rot) * rot_step;
+      uint64_t off = (uint64_t)(mag % n);
+      if (rot < 0 && off != 0) off = n - off;
+      uint32_t s = 0;
+      while (s < g.n_offsets && g.offset[s] != (uint32_t)off) ++s;
+      if (s == g.n_offsets) {
+        if (s == kFrGateMaxOffsets) return "more than MSM_AMD_GATE_MAX_OFFSETS (8) distinct offsets (rot * rot_step) mod n";
+        g.offset[g.n_offsets++] = (uint32_t)off;
+      }
+      fr_sum_set_byte(g.col, at, terms->factors[at]);
+      fr_sum_set_byte(g.slot, at, s);
+    }
+  }
+  const u256 one = Fr::one(), minus_one = Fr::sub(u256_zero(), one);
+  for (uint32_t k = 0; coeffs && k < terms->n_terms; ++k) {
+    const u256 c = fr_read_record(scalar_layout, (const uint8_t*)terms->coeff + (size_t)k * 32);
+    g.coeff[k] = c;
+    fr_sum_set_byte(g.kind, k, u256_eq(c, one) ? kFrCoeffOne : u256_eq(c, minus_one) ? kFrCoeffMinusOne : kFrCoeffAny);
+  }
+  if (image) *image = g;
+  return nullptr;
+}
+
+const char* fr_gate_eval_check(int mem, int scalar_layout, uint32_t flags, const ::msm_amd_fr_gate_terms* terms, const void* in,
+                               uint64_t n, uint64_t n_vec, uint64_t stride, uint64_t rot_step, const void* k_acc32,
+                               const void* scale, uint64_t period, const void* out, FrGateTerms* image) {
+  if (!fr_layout_known(scalar_layout)) return kMleLayout;
+  if (mem != MSM_AMD_MEM_HOST && mem != MSM_AMD_MEM_DEVICE) return "mem must be MSM_AMD_MEM_HOST or MSM_AMD_MEM_DEVICE";
+  if (flags & ~kFrGateAccumulate) return "flags must be 0 or MSM_AMD_GATE_ACCUMULATE";
+  if (n >> 32) return "n >= 2^32";
+  if (n == 0 || n_vec == 0) return nullptr;
+  if (const char* why = fr_gate_terms_check(scalar_layout, terms, n_vec, n, rot_step, image, true)) return why;
+  if (stride < n) return "stride < n";
+  if ((stride >> 32) || ((n_vec * stride) >> 32)) return "n_vec * stride >= 2^32";
+  if (!in || !out) return "null pointer with work to do";
+  if ((flags & kFrGateAccumulate) && !k_acc32) return "null k_acc32 with MSM_AMD_GATE_ACCUMULATE";
+  if (scale && (period < 1 || period > kFrGateMaxPeriod || (period & (period - 1)) || n % period))
+    return "period must be a power of two, 1 .. 256, that divides n";
+  if (mem == MSM_AMD_MEM_DEVICE && (((uintptr_t)in | (uintptr_t)out) & 15u)) return kMleAlign;
+  if (!spans_apart(in, ((n_vec - 1) * stride + n) * 32, out, n * 32)) return "the output must be disjoint from all of the input";
   return nullptr;
 }
 
@@ -815,6 +887,38 @@ int host_fr_sumcheck_step_terms(int layout, int order, const ::msm_amd_fr_sumche
   return MSM_AMD_OK;
 }
 
+// the calls of a gate that have no ctx leave their refusal here
+thread_local const char* gate_why = "";
+
+// the body of fr_gate_kernel row by row over ranges of rows
+int host_fr_gate_eval(int layout, uint32_t flags, const ::msm_amd_fr_gate_terms* terms, const void* in_v, size_t n, size_t n_vec,
+                      size_t stride, uint64_t rot_step, const void* k_acc32, const void* scale_v, size_t period, int threads,
+                      void* out_v) {
+  FrGateTerms image;
+  gate_why = "";
+  if (const char* why = fr_gate_eval_check(MSM_AMD_MEM_HOST, layout, flags, terms, in_v, n, n_vec, stride, rot_step, k_acc32,
+                                           scale_v, period, out_v, &image)) {
+    gate_why = why;
+    return MSM_AMD_INPUT_ERROR;
+  }
+  if (n == 0 || n_vec == 0) return MSM_AMD_OK;
+  const uint8_t* in = (const uint8_t*)in_v;
+  uint8_t* out = (uint8_t*)out_v;
+  const bool accumulate = flags & kFrGateAccumulate;
+  const u256 k_acc = accumulate ? fr_read_record(layout, k_acc32) : u256_zero();
+  std::vector<u256> scale(scale_v ? period : 0);
+  if (scale_v) host_read_records(layout, scale_v, period, scale.data());
+  for_ranges(worker_count(threads, n), n, [&](unsigned, size_t lo, size_t hi) {
+    for (size_t i = lo; i < hi; ++i) {
+      u256 v = fr_gate_row(image, i, n, [&](uint32_t col, uint64_t row) { return host_get(layout, in + (size_t)col * stride * 32, row); });
+      if (accumulate) v = Fr::add(Fr::mul(k_acc, host_get(layout, out, i)), v);
+      if (scale_v) v = Fr::mul(v, scale[i & (period - 1)]);
+      host_put(layout, out, i, v);
+    }
+  });
+  return MSM_AMD_OK;
+}
+
 }  // namespace
 }  // namespace msm_amd
 
@@ -903,6 +1007,51 @@ int msm_amd_test_fr_sumcheck_terms_plan(const msm_amd_fr_sumcheck_terms* terms, 
     return MSM_AMD_INPUT_ERROR;
   const FrMleRoundPlan p = fr_mle_round_plan(step ? n / 2 : n, d + 1, chunk_log);
   const uint64_t c[8] = {p.launches, p.waves, p.records, p.records * 32, p.levels, p.count[0], p.values, 0};
+  std::memcpy(counts, c, sizeof c);
+  return MSM_AMD_OK;
+}
+
+int msm_amd_fr_gate_check(const msm_amd_fr_gate_terms* terms, size_t n_vec, size_t n, uint64_t rot_step, uint32_t* degree,
+                          uint32_t* n_offsets) {
+  using namespace msm_amd;
+  FrGateTerms image;
+  gate_why = "";
+  if (const char* why = fr_gate_terms_check(MSM_AMD_SCALAR_MONT_LE, terms, n_vec, n, rot_step, &image, false)) {
+    gate_why = why;
+    return MSM_AMD_INPUT_ERROR;
+  }
+  if (degree) *degree = fr_gate_degree(image);
+  if (n_offsets) *n_offsets = image.n_offsets;
+  return MSM_AMD_OK;
+}
+
+const char* msm_amd_fr_gate_last_error(void) { return msm_amd::gate_why; }
+
+int msm_amd_host_fr_gate_eval(int scalar_layout, uint32_t flags, const msm_amd_fr_gate_terms* terms, const void* in, size_t n,
+                              size_t n_vec, size_t stride, uint64_t rot_step, const void* k_acc32, const void* scale,
+                              size_t period, int threads, void* out) {
+  return msm_amd::host_fr_gate_eval(scalar_layout, flags, terms, in, n, n_vec, stride, rot_step, k_acc32, scale, period, threads,
+                                    out);
+}
+
+int msm_amd_test_fr_gate_plan(int scalar_layout, uint32_t flags, const msm_amd_fr_gate_terms* terms, size_t n, size_t n_vec,
+                              uint64_t rot_step, size_t period, uint64_t counts[8]) {
+  using namespace msm_amd;
+  FrGateTerms g;
+  gate_why = "";
+  const char* why = !counts                              ? "null counts"
+                    : !fr_layout_known(scalar_layout)    ? "scalars in MSM_AMD_SCALAR_MONT_LE or MSM_AMD_SCALAR_CANON_LE only"
+                    : (flags & ~kFrGateAccumulate)       ? "flags must be 0 or MSM_AMD_GATE_ACCUMULATE"
+                                                         : fr_gate_terms_check(scalar_layout, terms, n_vec, n, rot_step, &g, true);
+  if (!why && period && (period > kFrGateMaxPeriod || (period & (period - 1)) || n % period))
+    why = "period must be a power of two, 1 .. 256, that divides n";
+  if (why) {
+    gate_why = why;
+    return MSM_AMD_INPUT_ERROR;
+  }
+  const uint64_t extra = (flags & kFrGateAccumulate ? 1u : 0u) + (period ? 1u : 0u);
+  const uint64_t c[8] = {1, ((uint64_t)n + kFrMapThreads - 1) / kFrMapThreads, fr_gate_factors(g) + extra,
+                         fr_gate_products(g) + extra, g.n_offsets, (uint64_t)period * 32, fr_gate_degree(g), 0};
   std::memcpy(counts, c, sizeof c);
   return MSM_AMD_OK;
 }

@@ -46,6 +46,10 @@
 //                          d + 1 raw partial records.
 //   fr_sumcheck_terms_kernel<D>  the same wave per chunk over a caller's sum of products of degree D (FrTermSums): the terms
 //                          and their factors in runtime loops of wave-uniform trip counts, a pair loaded per use.
+//   fr_gate_kernel         (fr_gate.hip.h) one lane per row of a sum of products of rotated columns, consecutive lanes on
+//                          consecutive rows: every rotated read is coalesced except in the one workgroup where it wraps;
+//                          the terms and their factors in runtime loops of wave-uniform trip counts, a record loaded per
+//                          use; the image by value, the periodic scale from a table of at most 256 raw records.
 //   fr_mle_fold_kernel     one wave per 2^10 partials of one t: their sum, the same fold.
 //   fr_mle_eval_kernel<P>  one wave per tile of 2^c records: lane l folds the records l, l + 64, ... (a tree in registers
 //                          over the tile's upper variables), six xor-shuffle steps fold the variables of the lane index,
@@ -625,6 +629,30 @@ __global__ void __launch_bounds__(kFrWave, 2) fr_sumcheck_terms_kernel(FrTermRou
   }
 }
 
+// A gate polynomial over rotated columns (fr_gate.hip.h): the image, k_acc and the geometry by value
+struct FrGateArgs {
+  const uint32_t* in;
+  const uint32_t* acc;     // ACCUMULATE: the old records of out (out itself, or the staged copy of a host call)
+  const uint32_t* scale;   // raw records, or null
+  uint32_t* out;
+  uint64_t n, stride;
+  uint32_t period_mask;
+  int layout, accumulate;
+  u256 k_acc;
+  FrGateTerms terms;
+};
+
+__global__ void __launch_bounds__(kFrMapThreads) fr_gate_kernel(FrGateArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * kFrMapThreads + threadIdx.x;
+  if (i >= a.n) return;
+  u256 v = fr_gate_row(a.terms, i, a.n, [&](uint32_t col, uint64_t row) {
+    return fr_load(a.layout, load_rec(a.in + ((uint64_t)col * a.stride + row) * 8));
+  });
+  if (a.accumulate) v = Fr::add(Fr::mul(a.k_acc, fr_load(a.layout, load_rec(a.acc + i * 8))), v);
+  if (a.scale) v = Fr::mul(v, load_rec(a.scale + (i & a.period_mask) * 8));
+  store_rec(a.out + i * 8, fr_store(a.layout, v));
+}
+
 __global__ void __launch_bounds__(kFrWave) fr_mle_fold_kernel(FrMleFoldArgs a) {
   const uint32_t lane = threadIdx.x;
   const uint64_t t = blockIdx.x / a.groups, g = blockIdx.x - t * a.groups;
@@ -1045,6 +1073,14 @@ uint32_t launch_fr_sumcheck_terms(hipStream_t st, const FrTermRoundLaunch& c) {
     hipLaunchKernelGGL(fr_mle_fold_kernel, dim3((uint32_t)(f.groups * plan.values)), dim3(kFrWave), 0, st, f);
   }
   return launches;
+}
+
+void launch_fr_gate(hipStream_t st, const FrGateLaunch& c) {
+  FrGateArgs a{};
+  a.in = (const uint32_t*)c.in, a.acc = (const uint32_t*)c.acc, a.scale = (const uint32_t*)c.scale, a.out = (uint32_t*)c.out;
+  a.n = c.n, a.stride = c.stride, a.period_mask = c.scale ? c.period - 1 : 0;
+  a.layout = c.layout, a.accumulate = c.accumulate, a.k_acc = c.k_acc, a.terms = c.terms;
+  hipLaunchKernelGGL(fr_gate_kernel, dim3((uint32_t)((c.n + kFrMapThreads - 1) / kFrMapThreads)), dim3(kFrMapThreads), 0, st, a);
 }
 
 uint32_t launch_fr_mle_eval(hipStream_t st, const FrMleEvalLaunch& c) {

@@ -5,6 +5,7 @@
 
 #include <cstddef>
 
+#include "fr_gate.hip.h"
 #include "fr_lookup.hip.h"
 #include "fr_permute.hip.h"
 #include "fr_mat.hip.h"
@@ -14,6 +15,7 @@
 #include "fr_vec.hip.h"
 
 struct msm_amd_fr_sumcheck_terms;   // include/msm_amd.h
+struct msm_amd_fr_gate_terms;
 
 namespace msm_amd {
 
@@ -132,6 +134,20 @@ struct FrTermRoundLaunch {
   FrSumTerms terms;
 };
 uint32_t launch_fr_sumcheck_terms(hipStream_t st, const FrTermRoundLaunch& c);
+// A gate polynomial over rotated columns (fr_gate.hip.h): one launch, one lane per row
+struct FrGateLaunch {
+  const void* in;      // n_vec columns of n records, `stride` records apart
+  const void* acc;     // accumulate: the n records out[i] is computed from (out itself, or a staged copy of it)
+  const void* scale;   // optional: `period` raw records (reduced Montgomery residues)
+  void* out;           // n records, disjoint from in
+  uint64_t n, stride;
+  uint32_t period;     // a power of two that divides n
+  int layout;
+  bool accumulate;
+  u256 k_acc;          // Montgomery and reduced
+  FrGateTerms terms;
+};
+void launch_fr_gate(hipStream_t st, const FrGateLaunch& c);
 struct FrMleEvalLaunch {
   const void* in;
   void* work;          // fr_scan_plan(n, n_vec, tile_log).records + n_vec raw records; the n_vec values behind the levels
@@ -302,6 +318,16 @@ const char* fr_sumcheck_terms_round_check(int scalar_layout, int order, const ::
 const char* fr_sumcheck_step_check(int scalar_layout, int order, const ::msm_amd_fr_sumcheck_terms* terms, const void* r,
                                    const void* in, uint64_t n, uint64_t n_vec, uint64_t stride, const void* out,
                                    const void* g_out, bool device, FrSumTerms* image);
+// The term list of msm_amd_fr_gate_eval and its twin against n_vec columns of n rows (msm_amd_fr_gate_check; no ctx): sizes,
+// pointers, indices, rot_step and the number of distinct offsets (rot rot_step) mod n; on success and with `image` given,
+// the image the kernel and the twin run on; its coefficients are read (in scalar_layout) only with `coeffs`.
+const char* fr_gate_terms_check(int scalar_layout, const ::msm_amd_fr_gate_terms* terms, uint64_t n_vec, uint64_t n,
+                                uint64_t rot_step, FrGateTerms* image, bool coeffs);
+// The whole check of the call: layout, mem and flags first, then n >= 2^32, then n == 0 or n_vec == 0 passes, then the list,
+// the stride, the pointers the call reads, the period of a scale, alignment (device) and the overlap of out and in
+const char* fr_gate_eval_check(int mem, int scalar_layout, uint32_t flags, const ::msm_amd_fr_gate_terms* terms, const void* in,
+                               uint64_t n, uint64_t n_vec, uint64_t stride, uint64_t rot_step, const void* k_acc32,
+                               const void* scale, uint64_t period, const void* out, FrGateTerms* image);
 // The Poseidon calls.  The shape (t, r_f, r_p) is that of a parameter handle or of the twin's arguments; every check first
 // looks at the layout, then at the sizes, lets n == 0 pass where a call has one, then at pointers, alignment and overlap.
 const char* poseidon_shape_check(uint64_t t, uint64_t r_f, uint64_t r_p);
