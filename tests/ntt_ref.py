@@ -1,9 +1,12 @@
-"""Model side of the transform tests (msm_amd_ntt*, msm_amd_host_ntt): Python integers only.  The two 2^28-th roots as
+"""Model side of the transform tests (msm_amd_ntt*, msm_amd_host_ntt): Python integers; np_random_records builds the
+columns that are too long for them (pinned by tests/test_np_models_host.py).  The two 2^28-th roots as
 g^t, a naive O(n^2) DFT, a recursive radix-2 transform for the sizes the naive one cannot reach, the closed form for
 sparse inputs, the state of the library's network after some of its levels, and the record encoders of the two scalar
 layouts.  Nothing here calls the library."""
 import functools
 import random
+
+import numpy as np
 
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617   # BN254 scalar field
 MONT = 1 << 256
@@ -153,3 +156,15 @@ def shift_record(g, layout):
 def random_vector(seed, n):
     rng = random.Random(seed)
     return [rng.randrange(R) for _ in range(n)]
+
+
+# ---- numpy: columns too long for Python integers -----------------------------------------------------------------------------------
+TOP_WORD_BELOW = 0x30000000      # r's top word is 0x30644e72: a record whose top word is below this is a reduced word
+
+
+def np_random_records(seed, n):
+    """(n, 8) uint32 records, every one a reduced 256-bit word; in MONT_LE the word w stands for w / MONT"""
+    rec = np.random.default_rng(seed).integers(0, 1 << 32, size=(n, 8), dtype=np.uint32)
+    rec[:, 7] %= np.uint32(TOP_WORD_BELOW)
+    return rec
+

@@ -1,5 +1,6 @@
 """The (tile_log, log_n) shapes the GPU transform tests run, in one place: EXISTING restates the sizes of
-tests/test_gpu_ntt.py, tests/test_gpu_ntt_geometry.py takes its sizes from here, and tests/test_ntt_plan_host.py accounts
+tests/test_gpu_ntt.py, tests/test_gpu_ntt_geometry.py takes its sizes from here, MANY_WORKGROUPS restates those of
+tests/test_gpu_many_workgroups.py, and tests/test_ntt_plan_host.py accounts
 on the CPU for the pass geometries these shapes reach (every pass of a shape runs on the GPU, in both directions)."""
 
 DEFAULT_TILE = 10
@@ -25,7 +26,10 @@ GEOMETRY_TILES = [(tile_log, log_n) for tile_log in MID_TILES for log_n in mid_t
 # pass taps: (tile_log, log_n)
 TAPS = [(DEFAULT_TILE, 12), (DEFAULT_TILE, 16), (DEFAULT_TILE, 20), (DEFAULT_TILE, 21), (3, 7), (6, 13)]
 
-ALL = EXISTING + GEOMETRY_DEFAULT + GEOMETRY_TILES
+# tests/test_gpu_many_workgroups.py: the three-pass sizes whose middle passes are (8, 2) and (9, 1)
+MANY_WORKGROUPS = [(DEFAULT_TILE, 23), (DEFAULT_TILE, 26)]
+
+ALL = EXISTING + GEOMETRY_DEFAULT + GEOMETRY_TILES + MANY_WORKGROUPS
 
 
 def geometry(passes):

@@ -10,6 +10,9 @@ from fr_ref import decode, encode, first_difference, raw  # noqa: F401
 from lookup_ref import CANON_LE, LAYOUTS, MONT_LE, NO_MISS, R  # noqa: F401
 
 DEFAULT_TILE_LOG = 11                                              # kPermuteTileLog
+# n_rows round the shipped tile and well into its second level (tests/test_gpu_many_workgroups.py); the third level starts
+# above 2^22 rows and is reached with MSM_AMD_PERMUTE_TILE_LOG only
+SHIPPED_TILE_SIZES = (2047, 2048, 2049, (1 << 16) + 3)
 
 
 def permute(table, data, layout, n_vec=1, want_s=True):
